@@ -26,11 +26,20 @@ Workloads (--workload; default c3):
        all-gather of the minimizer lists (exchange 2: nts_mx_allgather).  The family, the filter and therefore the work
        per genome are the same at every N: strong scaling.  At N=1 all eight genomes live on one GPU.
   c2   BASELINE configs[1]: 3 x 100 Mbp at 1 %, sketched as one batch genome (round 1's bench line).
-Extra legs at N=1 (rank 0), all inside the one JSON line: `cold` (first sketch of a fresh genome, three times, split into allocation
-and the rest), `roofline.unpruned` (every k-mer probed), `valley` (filters that accept a few per cent of the k-mers: 3 x 3 Gbp at
-10 %, 8 x 3 Gbp at 4 %), `e2e` (FASTA files on disk -> final synteny TSV through the product
+A plain run does only what the headline needs: it sets up (the family and its common filter), warms up, times --steps steps, writes
+the last timed step's minimizer lists if --dump-outputs DIR is given, and prints the line.  Everything else runs with --full only:
+the filter built a second time (`bloom.build_again_s`), the untimed pass with every kernel group between events
+(`roofline.other_kernels_avg_ms`), the VALU microbenchmark (`roofline.valu`), and the extra legs, all inside the one JSON line:
+`c4` (config 4 at this N), and at N=1 (rank 0) `cold` (first sketch of a fresh genome, three times, split into allocation
+and the rest), `nruns`, `roofline.unpruned` (every k-mer probed), `valley` (filters that accept a few per cent of the k-mers: 3 x 3 Gbp
+at 10 %, 8 x 3 Gbp at 4 %), `c5_like`, `e2e` (FASTA files on disk -> final synteny TSV through the product
 pipeline, per stage), `cpu_baseline` (the CPU oracle on the host cores, per stage, at the reference's default
-parallelism and on all cores).
+parallelism and on all cores).  The --no-*-leg options switch single legs of a --full run off.
+
+--dump-outputs DIR: per minimizer list of the last timed step (one per genome of the family; N > 1: the lists every rank receives,
+written by rank 0) DIR/genome<g>_digest.npy (count, XOR of the hashes and a mixed sum over the WHOLE list: mx_digest) and a fixed,
+seeded sample of at most DUMP_SAMPLE minimizers in all: _index (their places in the list), _h1_hi / _h1_lo (the two 32-bit halves of
+the hash), _rec, _pos -- float64 throughout, every value exact.  The inputs are the same from run to run at the same arguments.
 """
 import argparse
 import hashlib
@@ -58,6 +67,8 @@ WORKLOADS = {
 }
 SKETCH_KERNELS = ["hash_select", "cand_compact", "sparse_win", "gather_winners", "hash_probe", "window_min", "sort_minimizers",
                   "merge_lists", "finalize"]
+DUMP_SAMPLE = 1 << 20                                # --dump-outputs: sampled minimizers over all lists (5 float64 columns: 40 MiB)
+DUMP_SEED = 20241015
 
 
 def parse():
@@ -65,6 +76,8 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true", help="every leg and check of the line besides the headline (see the module's docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's minimizer lists (digest + sample) as DIR/*.npy")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default=None)
     ap.add_argument("--genomes", type=int, default=None, help="override: genomes in the family")
     ap.add_argument("--mbp", type=float, default=None, help="override: Mbp per genome")
@@ -91,7 +104,10 @@ def parse():
     ap.add_argument("--no-c5-leg", action="store_true")
     ap.add_argument("--no-valley-leg", action="store_true")
     ap.add_argument("--e2e-dir", default=None, help="where the e2e leg writes its FASTA files [a temp dir]")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def effective_cores():
@@ -368,6 +384,34 @@ def mx_digest(h1, rec, pos):
         return {"n": int(h1.size), "xor_h1": int(np.bitwise_xor.reduce(h1)) if h1.size else 0, "sum_mix": int(mix.sum(dtype=np.uint64)) if h1.size else 0}
 
 
+def dump_outputs(out_dir, lists, sample=DUMP_SAMPLE, seed=DUMP_SEED):
+    """--dump-outputs: `lists` = [(name, (h1, rec, pos))] as Minimizers.to_numpy() gives them.  Per list: <name>_digest (count, XOR of
+    the hashes, mixed sum: mx_digest, 64-bit words as two 32-bit halves) over the whole list, and the same seeded sample of places
+    whenever the list has the same length: <name>_index, _h1_hi, _h1_lo, _rec, _pos.  float64 only, every value exact."""
+    os.makedirs(out_dir, exist_ok=True)
+    per_list = sample // max(len(lists), 1)
+
+    def halves(v):
+        v = np.asarray(v, dtype=np.uint64)
+        return (v >> np.uint64(32)).astype(np.float64), (v & np.uint64(0xFFFFFFFF)).astype(np.float64)
+
+    for i, (name, (h1, rec, pos)) in enumerate(lists):
+        dg = mx_digest(h1, rec, pos)
+        x_hi, x_lo = halves([dg["xor_h1"]])
+        s_hi, s_lo = halves([dg["sum_mix"]])
+        np.save(os.path.join(out_dir, f"{name}_digest.npy"), np.array([dg["n"], x_hi[0], x_lo[0], s_hi[0], s_lo[0]], dtype=np.float64))
+        n = int(h1.size)
+        if n > per_list:
+            idx = np.sort(np.random.default_rng([seed, i, n]).choice(n, per_list, replace=False))
+        else:
+            idx = np.arange(n)
+        hi, lo = halves(h1[idx])
+        cols = {"index": idx.astype(np.float64), "h1_hi": hi, "h1_lo": lo, "rec": rec[idx].astype(np.float64),
+                "pos": np.asarray(pos[idx], dtype=np.uint64).astype(np.float64)}
+        for col, arr in cols.items():
+            np.save(os.path.join(out_dir, f"{name}_{col}.npy"), arr)
+
+
 def e2e_key(args, n_fam, total_bp, contigs, div):
     "identity of an e2e family + parameter set (the oracle's recorded md5 applies to exactly this)"
     fam = "substitutions-only" if args.substitutions_only else "structural+softmask"
@@ -616,6 +660,7 @@ class Rig:
         self.common = None
         self.n_all = None
         self.t_sketch = 0.0                          # seconds spent in the sketch calls of step() (reset by the caller around a timed region)
+        self.kept = None                             # step(keep=True): [(name, Minimizers)] of that step, what a caller receives
 
     def build_filter(self, again=False, levels=False, trim=False):
         "per-genome filters, local cascade, exchange 1; returns the timings"
@@ -676,9 +721,12 @@ class Rig:
             ctx.trim_bf_build()                      # as the pipeline does once its common filter stands (pipeline.run): the buckets go to the allocation cache
         return {"build_s": t_build, "build_again_s": t_warm, "allreduce_s": t_allreduce, "occ_single": occ_single}
 
-    def step(self, pool=None):
+    def step(self, pool=None, keep=False):
+        """one sketch pass + exchange 2; returns this rank's minimizer count.  keep: the step's lists -- this rank's (N = 1), or the
+        family's lists every rank receives (N > 1) -- stay in self.kept, named per genome, until free_kept()"""
         from ntsynt_amd.device import Minimizers, sketch
         ctx, comm, world, k, w = self.ctx, self.comm, self.world, self.args.k, self.args.w
+        self.free_kept()
         held, n = [], 0
         t0 = time.time()
         if pool is not None:
@@ -699,21 +747,34 @@ class Rig:
                         by_genome.setdefault(g_, []).append((parts[at], a))
                         at += 1
                 n_all = 0
+                whole = []
                 for g_ in range(self.n_fam):                        # the genome's list: its parts in record order
                     whole_list = Minimizers.concat(ctx, [m for m, _ in by_genome[g_]], [a for _, a in by_genome[g_]])
                     n_all += len(whole_list)
-                    whole_list.free()
+                    whole.append((f"genome{g_}", whole_list))
                 self.n_all = n_all
                 for mx in parts:
                     mx.free()
             else:
                 everything = comm.allgather_minimizers(held, self.mine, self.n_fam)
                 self.n_all = sum(len(mx) for mx in everything)
-                for mx in everything:
+                whole = [(f"genome{g_}", mx) for g_, mx in enumerate(everything)]
+            if keep:
+                self.kept = whole
+            else:
+                for _, mx in whole:
                     mx.free()
-        for mx in held:
-            mx.free()
+        if keep and world == 1:
+            self.kept = [("batch" if len(self.units) != len(self.mine) else f"genome{g_}", mx) for g_, mx in zip(self.mine, held)]
+        else:
+            for mx in held:
+                mx.free()
         return n
+
+    def free_kept(self):
+        for _, mx in self.kept or []:
+            mx.free()
+        self.kept = None
 
     def free(self):
         for g in self.genomes:
@@ -902,10 +963,11 @@ def main():
     from ntsynt_amd.pipeline import plan_bytes
     arena_plan, arena_got, t_arena = 0, 0, 0.0
     if os.environ.get("NTS_BENCH_ARENA", "1") != "0":
-        n_res = max(3, -(-8 // world)) if not args.workload or args.workload == "c3" else 3
+        n_res = max(3, -(-8 // world)) if args.full and (not args.workload or args.workload == "c3") else 3
         per_genome = int((args.mbp or {"c2": 100, "c3": 3000, "c4": 3000}.get(args.workload or "c3", 3000)) * 1e6)
-        # (the largest leg's family + 0.7 of the headline family's plan: its filter and workspaces stay live next to the leg's)
-        arena_plan = plan_bytes([per_genome] * n_res, args.fpr, True) + int(0.7 * plan_bytes([per_genome] * 3, args.fpr, True))
+        # (--full: the largest leg's family + 0.7 of the headline family's plan: its filter and workspaces stay live next to the leg's;
+        # a plain run: the headline family's plan alone)
+        arena_plan = plan_bytes([per_genome] * n_res, args.fpr, True) + (int(0.7 * plan_bytes([per_genome] * 3, args.fpr, True)) if args.full else 0)
         t_ar = time.time()
         arena_got = ctx.mem_reserve(arena_plan)
         t_arena = time.time() - t_ar
@@ -929,7 +991,7 @@ def main():
     genomes, units, mine, fam_bases, bases, t_synth = rig.genomes, rig.units, rig.mine, rig.fam_bases, rig.bases, rig.t_synth
     shard = rig.plan
     ctx.profile(True)
-    bt = rig.build_filter(again=True, trim=True)    # (the headline rig does what a run does; the later legs' rigs keep their buckets for one another)
+    bt = rig.build_filter(again=args.full, trim=True)    # (the headline rig does what a run does; the later legs' rigs keep their buckets for one another)
     common, nbytes = rig.common, rig.nbytes
     t_build, t_build_warm, t_allreduce, occ_single = bt["build_s"], bt["build_again_s"], bt["allreduce_s"], bt["occ_single"]
     ins_ms, ins_n = ctx.timing("bf_insert")
@@ -938,7 +1000,7 @@ def main():
 
     # ---- cold leg: the first sketch of a genome nothing has been derived from yet ---------------------------------
     cold = None
-    if world == 1 and not args.no_cold_leg:
+    if args.full and world == 1 and not args.no_cold_leg:
         cold = cold_leg(args, ctx, rig)
 
     # --at-once: the genomes of a step are sketched at once, each on a context of its own (device.SketchPool; NTS_SKETCH_POOL=3
@@ -950,8 +1012,8 @@ def main():
         pool = SketchPool(ctx, min(len(units), 3))
         pool.configure(lambda c: c.sketch_mode(args.mode, args.prune_c))
 
-    def step():
-        return rig.step(pool)
+    def step(keep=False):
+        return rig.step(pool, keep)
 
     def fence():
         ctx.sync()
@@ -966,15 +1028,15 @@ def main():
     def timing_of(n):
         return pool.timing(n) if pool is not None else ctx.timing(n)
 
-    def timed(n_warm, n_steps, level=2, step=step):
+    def timed(n_warm, n_steps, level=2, step=step, keep=False):
         for _ in range(n_warm):
             step()
         all_ctx(lambda c: c.profile(level))   # 2: HIP events around the dominant kernel only (every pair is a bubble in the stream)
         fence()
         t_start = time.time()
         n_mx = 0
-        for _ in range(n_steps):
-            n_mx = step()
+        for i in range(n_steps):
+            n_mx = step(keep=True) if keep and i == n_steps - 1 else step()
         fence()
         el = time.time() - t_start
         if world > 1:
@@ -986,7 +1048,10 @@ def main():
     for _ in range(args.warmup):
         step()
     rig.t_sketch = 0.0
-    dt, n_mx = timed(0, args.steps)
+    dt, n_mx = timed(0, args.steps, keep=True)      # (the last step's lists are freed after the clock stops, with or without a dump)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [(nm, mx.to_numpy()) for nm, mx in rig.kept])
+    rig.free_kept()
     x2_headline = comm.last_exchange2() if comm is not None else None     # (of the last timed step: the later legs exchange other lists)
     t_sk = rig.t_sketch
     if world > 1:                                                   # the slowest rank's sketch time
@@ -994,15 +1059,17 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         t_sk = float(tt.item())
     tm = {n: timing_of(n) for n in SKETCH_KERNELS}
-    # the other kernels of the call: one more pass, untimed, with every kernel group bracketed by events
-    all_ctx(lambda c: c.profile(1))
-    step()
-    fence()
-    detail = {n: timing_of(n) for n in SKETCH_KERNELS}
+    detail = None
+    if args.full:
+        # the other kernels of the call: one more pass, untimed, with every kernel group bracketed by events
+        all_ctx(lambda c: c.profile(1))
+        step()
+        fence()
+        detail = {n: timing_of(n) for n in SKETCH_KERNELS}
     # and the dominant kernel alone on the GPU: one genome after the other on one stream (with the genomes sketched at once its
     # launches share the chip with another genome's tail kernels, so the duration above is the one under that load)
     alone_ms = None
-    if pool is not None:
+    if pool is not None and args.full:
         ctx.profile(2)
         for g in units:
             sketch(ctx, g, k, w, common).free()
@@ -1019,7 +1086,7 @@ def main():
         return tm[n][0] / max(tm[n][1], 1)
 
     nruns = None
-    if world == 1 and name == "c3" and not args.no_nruns_leg:
+    if args.full and world == 1 and name == "c3" and not args.no_nruns_leg:
         # SURVEY.md 8(d)'s N-run variant: 0.5 % of the bases in runs of 100-50,000 N -- the valid-k-mer path (run table, tiles that
         # span runs) at full size, against the same common filter
         g_n = family_genome(ctx, args, total_bp, contigs, mine[0], div / 2.0, n_runs=True)
@@ -1044,7 +1111,7 @@ def main():
     if pool is not None:                  # the remaining legs run one sketch at a time on the main context
         pool.close()
         pool = None
-    if args.mode != "dense" and not args.no_dense_leg and world == 1:
+    if args.full and args.mode != "dense" and not args.no_dense_leg and world == 1:
         ctx.sketch_mode("dense")
         n_d = max(2, args.steps // 2)
         d_dt, _ = timed(1, n_d, level=1)
@@ -1063,7 +1130,7 @@ def main():
         ctx.sketch_mode(args.mode, args.prune_c)
 
     valu = None
-    if world == 1:
+    if args.full and world == 1:
         # VALU roof of the issue-bound kernel: measured issue rate of its instruction mix's slowest member (nts_bench_valu)
         rows = {kind: ctx.bench_valu(kind, 8, 20000) for kind in ("v_xor_b32", "v_alignbit_b32", "v_lshl_add_u64", "v_add3_u32",
                                                                   "v_cmp_ge_u32+v_addc_co_u32", "roll31 step (9 instructions)")}
@@ -1071,7 +1138,7 @@ def main():
                 "unit": "G wave-instructions/s/CU", "how": "nts_bench_valu: 8 waves per SIMD, eight independent chains per lane, wall clock"}
 
     c4 = valley = rows = None
-    if name == "c3" and not args.no_c4_leg:
+    if args.full and name == "c3" and not args.no_c4_leg:
         # BASELINE configs[3] at this N, in the same line: eight genomes at 10 %, genome g on rank g mod N, the filter's cascade local,
         # then the AND all-reduce; every step ends with the all-gather of the lists.  (At N = 1: all eight on this GPU.)
         for g in rig.genomes:
@@ -1214,7 +1281,7 @@ def main():
                          "genomes_sketched_at_once": n_at_once,
                          "avg_launch_ms_alone_on_the_gpu": round(alone_ms, 4) if alone_ms else None,
                          "frac_alone_on_the_gpu": round(bpb * per_launch_bases / (alone_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if alone_ms else None,
-                         "other_kernels_avg_ms": {n: round(detail[n][0] / detail[n][1], 4) for n in SKETCH_KERNELS if detail[n][1]},
+                         "other_kernels_avg_ms": {n: round(detail[n][0] / detail[n][1], 4) for n in SKETCH_KERNELS if detail[n][1]} if detail else None,
                          "candidates_per_launch": cand, "uncovered_ranges": gaps, "uncovered_kmers": gap_kmers,
                          # the formulation with one sector read per k-mer moves 65.03 B/base, i.e. at
                          # most 8 TB/s / 65.03 B = 123 Gbases/s; the timed path, expressed in those bytes:
@@ -1257,7 +1324,8 @@ def main():
                 "valu.mix, valu.peak": "profiles/r03_valu_mix.json (instruction classes counted from the ISA) priced at this run's measured issue rates"
                 if valu and "kernel" in valu else None},
             "constants": {"peak": "MI355X_MICROARCH.md: HBM3E 8 TB/s", "algorithmic_bytes_per_base": "SURVEY.md 8(d): 64 B per probe; DESIGN.md 4.1"}}
-        out["allocator"] = {"what": "one nts_mem_reserve at start, sized for the largest leg; every leg's genomes, filters and workspaces are cut from it",
+        out["allocator"] = {"what": "one nts_mem_reserve at start, sized for the largest leg; every leg's genomes, filters and workspaces are cut from it"
+                            if args.full else "one nts_mem_reserve at start, sized for the headline family; its genomes, filter and workspaces are cut from it",
                             "arena_planned_GB": round(arena_plan / 1e9, 2), "arena_reserved_GB": round(arena_got / 1e9, 2), "reserve_s": round(t_arena, 4),
                             # what this box charges for memory it has not handed out before (0.004 on a box whose memory had been used, 28 on one fresh from its driver)
                             "reserve_ms_per_GB": round(t_arena * 1e3 / max(arena_got / 1e9, 1e-9), 3) if arena_got else None,
@@ -1274,7 +1342,7 @@ def main():
             out["c4"] = c4
             if world == 1:
                 out["c4_n1"] = c4                                       # (the name rounds 2-4 gave the N = 1 point)
-    if world == 1:
+    if args.full and world == 1:
         sample = bf_np = None
         e2e_slices = e2e_par = None
         if not args.no_cpu_baseline:

@@ -2,8 +2,8 @@
 """HBM traffic per launch from two rocprofv3 PMC passes (MI355X_MICROARCH.md, HBM section: FETCH_SIZE and
 WRITE_SIZE are collected in separate runs, with --kernel-trace only).
 
-  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_fetch -o f -- python bench.py ...
-  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_write -o w -- python bench.py ...
+  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d out/pmc_fetch -o f -- python bench.py --full ...
+  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d out/pmc_write -o w -- python bench.py --full ...
   python profiles/pmc_summarize.py <f_counter_collection.csv> <w_counter_collection.csv> profiles/rNN_pmc_traffic "<workload>"
 
 Writes <out>.json (read by bench.py for roofline.traffic) and <out>.md.  Values are raw counters (KB) / 1024 = MB,

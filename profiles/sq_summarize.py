@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """Instruction-issue counters per kernel from rocprofv3 PMC passes (each pass: --pmc <counters> --kernel-trace only):
 
-  rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES --kernel-trace --output-format csv -d gpurun_out/pmc_sq1 -o s -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-dense-leg
+  rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES --kernel-trace --output-format csv -d out/pmc_sq1 -o s -- python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-dense-leg
   rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU ...   (pmc_sq2)
   rocprofv3 --pmc SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT ...                                (pmc_sq3)
-  python profiles/sq_summarize.py gpurun_out/pmc_sq1 gpurun_out/pmc_sq2 gpurun_out/pmc_sq3 > profiles/rNN_sq_counters.json
+  python profiles/sq_summarize.py out/pmc_sq1 out/pmc_sq2 out/pmc_sq3 > profiles/rNN_sq_counters.json
 
 Largest launch of each kernel: the sketch kernels see the batch of three 100 Mbp genomes (300.19 M k-mers), the Bloom
 build kernels one genome (100.06 M).  valu_issue_utilisation = wave-level VALU
@@ -51,7 +51,7 @@ def main():
     what = os.environ.get("NTS_PROF_WORKLOAD") or (
         "one 3 Gbp genome per launch (bench.py's default family)" if "NTS_PROF_KMERS" in os.environ
         else "sketch kernels: the batch of three 100 Mbp genomes; k_bin*: one genome")
-    res = {"workload": "python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-dense-leg under rocprofv3 --pmc "
+    res = {"workload": "python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-dense-leg under rocprofv3 --pmc "
                        f"(three passes); largest launch of each kernel ({what}); k-mers per launch taken as {BATCH_KMERS:.0f}", "kernels": {}}
     for k in KEEP:
         if k not in out:

@@ -143,7 +143,7 @@ def test_mx_allgather_between_ranks(world, tmp_path):
 
 def test_bench_two_ranks(tmp_path):
     r = _torchrun(2, [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "c4", "--genomes", "4",
-                      "--mbp", "6", "--contigs", "2"], {"NTS_BENCH_BACKEND": "gloo"}, tmp_path)
+                      "--mbp", "6", "--contigs", "2", "--full"], {"NTS_BENCH_BACKEND": "gloo"}, tmp_path)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -168,7 +168,7 @@ def test_bench_starts_its_own_ranks_and_keeps_one_workload_along_the_curve(tmp_p
     """`python bench.py --gpus 4 --steps 2` -- plain, no torchrun, the driver's command form -- starts four ranks itself and reports
     n_gpus 4 with rccl_ranks 4 on the SAME workload as N = 1 (c3: three genomes, their records shared out by bases across genome
     boundaries), config 4 as the `c4` leg of the same line at both N; a launcher whose WORLD_SIZE disagrees with --gpus is refused"""
-    small = ["--steps", "2", "--warmup", "1", "--mbp", "8", "--contigs", "4"]
+    small = ["--full", "--steps", "2", "--warmup", "1", "--mbp", "8", "--contigs", "4"]
     env = _env(NTS_BENCH_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
     out = _bench_line([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4"] + small, env, tmp_path)
@@ -196,7 +196,7 @@ def test_bench_with_eight_ranks_the_driver_command_at_small_size(tmp_path):
     """`python bench.py --gpus 8` (the driver's scaling command, here with eight ranks on the visible GPU through the stand-in): three
     genomes shared out over eight ranks by bases (a rank holds up to two parts), config 4's eight genomes one per rank; the lists
     cross exchange 2 packed (12 bytes per minimizer and a record table instead of 20) and add up to the one-rank run's"""
-    small = ["--steps", "2", "--warmup", "1", "--mbp", "8", "--contigs", "4"]
+    small = ["--full", "--steps", "2", "--warmup", "1", "--mbp", "8", "--contigs", "4"]
     env = _env(NTS_BENCH_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
     out = _bench_line([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8"] + small, env, tmp_path)
