@@ -407,6 +407,11 @@ int nts_mx_upload(nts_ctx* ctx,
 /* test/bench hook: canonical h0 of every valid k-mer in (record, position) order (row B1) */
 int nts_hash_all(nts_ctx* ctx, const nts_genome* g, uint32_t k, uint64_t** h0, uint64_t* n_out);
 
+/* The s smallest DISTINCT canonical ntHash values (h0, as nts_hash_all returns them) over the valid k-mers of g,
+ * ascending; *n_out = min(s, number of distinct values).  h0 == UINT64_MAX is never part of a sketch (sentinel).
+ * Exact (a bottom-s MinHash sketch, the input of the Mash distance in ntsynt_amd/divergence.py); `out` holds s values. */
+int nts_minhash(nts_ctx* ctx, const nts_genome* g, uint32_t k, uint32_t s, uint64_t* out, uint32_t* n_out);
+
 /* ---- C1-C5: minimizer graph -> collinear chains -----------------------------------------------------
  * replaces ntjoin_utils.read_minimizers' duplicate removal, filter_minimizers and build_graph
  * (call sites bin/ntsynt_synteny.py:607-612, 483, 539) and the path walk of Ntjoin.find_paths

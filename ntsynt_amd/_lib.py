@@ -155,6 +155,7 @@ SYMBOLS = [
     ("nts_mx_screen", ctypes.c_int, [c_vp, c_vp, c_vp, u32, c_vp, ctypes.POINTER(c_vp)]),
     ("nts_mx_upload", ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, u64, ctypes.POINTER(c_vp)]),
     ("nts_hash_all", ctypes.c_int, [c_vp, c_vp, u32, ctypes.POINTER(c_u64p), c_u64p]),
+    ("nts_minhash", ctypes.c_int, [c_vp, c_vp, u32, u32, c_u64p, c_u32p]),
     ("nts_graph_build", ctypes.c_int, [c_vp, u32, ctypes.POINTER(MxList), ctypes.POINTER(Graph)]),
     ("nts_engine_create", ctypes.c_int, [c_vp, u32, u32, ctypes.POINTER(c_vp)]),
     ("nts_engine_free", None, [c_vp, c_vp]),

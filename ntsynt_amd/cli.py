@@ -19,6 +19,16 @@ def read_fasta_files(filename):
         return [line.strip() for line in fin]
 
 
+def divergence_value(text):
+    "-d: a percentage, or `auto` (estimated on the GPU from the genomes: ntsynt_amd/divergence.py)"
+    if text == "auto":
+        return text
+    return float(text)
+
+
+divergence_value.__name__ = "float"        # argparse's message for a bad value stays "invalid float value: ..."
+
+
 def build_parser():
     epilog = "\n".join([
         "Parameters derived from -d unless given explicitly (the reference's table, bin/ntSynt:89-99):",
@@ -33,7 +43,9 @@ def build_parser():
     p.add_argument("--fastas_list", help="text file naming the assemblies, one path per line (instead of positional arguments)",
                    required=False, type=str)
     p.add_argument("-d", "--divergence", help="upper estimate of the sequence divergence between the assemblies, in percent (-d 1 = 1%%);\n"
-                   "selects --indel, --merge, --w_rounds and --block_size (table below)", required=True, type=float)
+                   "selects --indel, --merge, --w_rounds and --block_size (table below);\n"
+                   "`auto`: estimated from the assemblies on the GPU (Mash distance of MinHash sketches, k 21, sketch 10000)",
+                   required=True, type=divergence_value)
     p.add_argument("-p", "--prefix", help="prefix of the output files [ntSynt.k<k>.w<w>]", required=False)
     p.add_argument("-k", help="k-mer size of the minimizers [24]", type=int, required=False, default=24)
     p.add_argument("-w", help="window size of the minimizers [1000]", type=int, required=False, default=1000)
@@ -78,6 +90,11 @@ def resolve(parser, args):
     for w in args.w_rounds:
         if w > args.w:
             parser.error("All values specified for --w_rounds must be smaller than -w")
+    return input_fastas(parser, args)
+
+
+def input_fastas(parser, args):
+    "the assemblies named on the command line, after the checks that do not depend on the divergence (bin/ntSynt:114-120)"
     if not args.fastas and not args.fastas_list:
         parser.error("Please supply the input genome fasta files as positional arguments, "
                      "or specify a file listing the files (one fasta per line) with --fastas_list")
@@ -90,12 +107,33 @@ def resolve(parser, args):
     return fastas
 
 
+def estimate_divergence(parser, args, say):
+    """-d auto: every check that does not depend on the divergence first, then the estimate over all genomes (under torchrun every
+    rank makes the same exact estimate on its own GPU), then args.divergence = the printed value, as if it had been given"""
+    fastas = input_fastas(parser, args)
+    for fasta in fastas:
+        if not os.path.isfile(fasta):
+            raise FileNotFoundError(f"Input file {fasta} not found.")
+    device = args.device
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:              # the GPU this rank will run on (main, below)
+        device = int(os.environ.get("LOCAL_RANK", "0"))
+        if os.environ.get("NTS_DIST_BACKEND", "nccl") != "nccl":
+            import torch
+            device %= max(torch.cuda.device_count(), 1)
+    from . import divergence
+    est = divergence.estimate(fastas, k=divergence.K_DEFAULT, s=divergence.S_DEFAULT, device=device)
+    say(est.summary(), flush=True)
+    args.divergence = float(str(est.divergence))
+
+
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
-    fastas = resolve(parser, args)
     rank0 = int(os.environ.get("RANK", "0")) == 0                # under torchrun every rank runs this; one of them talks
     say = print if rank0 else (lambda *a, **k: None)
+    if args.divergence == "auto":
+        estimate_divergence(parser, args, say)
+    fastas = resolve(parser, args)
     say(NTSYNT_BANNER)
     say("\n".join(["Running ntSynt...",
                      f"Specified percent divergence: {args.divergence}",

@@ -119,9 +119,10 @@ __global__ __launch_bounds__(256) void k_stretch(const uint8_t* __restrict__ cod
 //   MODE_CASCADE: if bf_in has bit(h0): bf_out |= bit(h0)                             (row A3, literal)
 //   MODE_REPEAT : if bit(h0) was set in bf_in already: bf_out |= bit(h0); bf_in |= bit(h0)   (bin/ntsynt_make_repeat_bfs.py:56-67;
 //                 the returning atomic makes "the second hit of a bit" well defined whatever the order of the lanes)
+//   MODE_MINHASH: if h0 < mh.tau: h0 joins the open-addressing set mh (nts_minhash.inc: bottom-s sketch of the distinct hashes)
 // Key layout in HBM is tile-transposed so that both this kernel's stores and the window kernel's loads
 // coalesce: phys(j) = tile*8192 + (j%32)*256 + (j%8192)/32.
-enum { MODE_KEYS = 0, MODE_INSERT = 1, MODE_CASCADE = 2, MODE_REPEAT = 3 };
+enum { MODE_KEYS = 0, MODE_INSERT = 1, MODE_CASCADE = 2, MODE_REPEAT = 3, MODE_MINHASH = 4 };
 constexpr uint32_t KEY_TILE = HASH_THREADS * HASH_PER_THREAD; // 8192
 constexpr uint32_t FAST_K_MAX = 128;
 constexpr uint32_t SEQ_LDS_DWORDS = 2400; // (15 + 8192 + 127) bytes in the padded layout, rounded up
@@ -159,6 +160,40 @@ __device__ __forceinline__ void hash_emit(uint64_t h0, bool live, uint64_t phys,
   }
 }
 
+// Device set of MODE_MINHASH: `slots` holds cap = mask + 1 entries, KEY_MAX = empty (h0 == KEY_MAX never survives: tau <= KEY_MAX and
+// the test is strict).  Entries only ever go from empty to a hash, so a plain load that sees a hash sees its final value; a stale
+// empty is settled by the CAS.  `count` = distinct hashes inserted; past `limit` the sweep stops inserting (its result is discarded
+// and tau lowered), and a probe that walks the whole table adds cap, so that a full table can never loop.
+struct MhSet
+{
+  uint64_t* slots = nullptr;
+  unsigned long long* count = nullptr;
+  uint64_t mask = 0;
+  uint64_t limit = 0;
+  uint64_t tau = 0;
+};
+
+__device__ __forceinline__ void mh_insert(const MhSet& mh, uint64_t h)
+{
+  if (*reinterpret_cast<volatile unsigned long long*>(mh.count) > mh.limit) return;
+  uint64_t i = h & mh.mask; // survivors have zero top bits; the low bits of h0 are as random as the rest
+  for (uint64_t probe = 0; probe <= mh.mask; ++probe) {
+    const uint64_t cur = mh.slots[i];
+    if (cur == h) return;
+    if (cur == KEY_MAX) {
+      const unsigned long long prev = atomicCAS(reinterpret_cast<unsigned long long*>(mh.slots + i), (unsigned long long)KEY_MAX,
+                                                (unsigned long long)h);
+      if (prev == KEY_MAX) {
+        atomicAdd(mh.count, 1ULL);
+        return;
+      }
+      if (prev == h) return;
+    }
+    i = (i + 1) & mh.mask;
+  }
+  atomicAdd(mh.count, (unsigned long long)mh.mask + 1ULL);
+}
+
 template <int MODE>
 __global__ __launch_bounds__(HASH_THREADS) void k_hash(const uint8_t* __restrict__ code,
                                                        const uint64_t* __restrict__ run_pos,
@@ -173,7 +208,8 @@ __global__ __launch_bounds__(HASH_THREADS) void k_hash(const uint8_t* __restrict
                                                        const uint32_t* __restrict__ tile_ids,
                                                        const uint2* __restrict__ tile_span,
                                                        const uint32_t* __restrict__ bf_rep,
-                                                       FastMod fm_rep)
+                                                       FastMod fm_rep,
+                                                       MhSet mh)
 {
   // bf_rep (MODE_KEYS): filter-out Bloom filter, indexlr -r -- a k-mer present in it is rejected like one absent from bf_in
   // tile_span (with tile_ids): per listed tile the first and last in-tile index whose key anybody reads (the uncovered ranges
@@ -271,6 +307,10 @@ __global__ __launch_bounds__(HASH_THREADS) void k_hash(const uint8_t* __restrict
 #pragma unroll
         for (int u = 0; u < 8; ++u)
           if (b0 + u < n_mine) keys[out_base + (uint64_t)(b0 + u) * 256u] = h[u];
+      } else if (MODE == MODE_MINHASH) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+          if (b0 + u < n_mine && h[u] < mh.tau) mh_insert(mh, h[u]);
       } else {
 #pragma unroll
         for (int u = 0; u < 8; ++u) hash_emit<MODE>(h[u], b0 + u < n_mine, 0, bf_in, bf_out, fm, keys);
@@ -304,7 +344,9 @@ __global__ __launch_bounds__(HASH_THREADS) void k_hash(const uint8_t* __restrict
     }
     for (;;) {
       const uint32_t e = (uint32_t)(j - J0);
-      if (MODE == MODE_KEYS && (e < span.x || e > span.y))
+      if (MODE == MODE_MINHASH) {
+        if (f + r < mh.tau) mh_insert(mh, f + r);
+      } else if (MODE == MODE_KEYS && (e < span.x || e > span.y))
         keys[KB + (key_phys(j) - J0)] = KEY_MAX;
       else
         hash_emit<MODE>(f + r, true, KB + (key_phys(j) - J0), bf_in, bf_out, fm, keys, bf_rep, &fm_rep);
@@ -1503,7 +1545,7 @@ int get_tables(nts_ctx* ctx, const nts_genome* g, uint32_t k, const nts_interval
 template <int MODE>
 int launch_hash(nts_ctx* ctx, const char* name, const nts_genome* g, const GenomeTables& T, uint32_t k,
                 const nts_bf* bf_in, nts_bf* bf_out, uint64_t* keys, const uint32_t* d_tile_ids = nullptr, uint64_t n_tile_ids = 0,
-                const uint2* d_tile_span = nullptr)
+                const uint2* d_tile_span = nullptr, const MhSet& mh = MhSet{})
 {
   const RunTable& rt = T.rt;
   if (rt.n_valid == 0) return NTS_OK;
@@ -1529,7 +1571,7 @@ int launch_hash(nts_ctx* ctx, const char* name, const nts_genome* g, const Genom
   NTS_LAUNCH(k_hash<MODE>, dim3((uint32_t)blocks), dim3(HASH_THREADS), 0, ctx->stream, g->d_code + PAD, T.d_run_pos,
                      T.d_run_vstart, T.n_runs, rt.n_valid, hp, bf_in ? bf_in->d_words : nullptr, bf_out ? bf_out->d_words : nullptr,
                      fm, keys, d_tile_ids, d_tile_span, (MODE == MODE_KEYS && ctx->cur_rep) ? ctx->cur_rep->d_words : nullptr,
-                     make_fastmod((MODE == MODE_KEYS && ctx->cur_rep) ? ctx->cur_rep->bytes * 8 : 64));
+                     make_fastmod((MODE == MODE_KEYS && ctx->cur_rep) ? ctx->cur_rep->bytes * 8 : 64), mh);
   HIP_TRY(ctx, hipGetLastError());
   return NTS_OK;
 }
@@ -1539,6 +1581,7 @@ int launch_hash(nts_ctx* ctx, const char* name, const nts_genome* g, const Genom
 #include "nts_bloom_bin.inc"
 #include "nts_bf_sparse.inc"
 #include "nts_microbench.inc"
+#include "nts_minhash.inc"
 
 // acc &= the filter of genome g the literal way, for a running filter that holds few bits (defined behind the sketch's host code,
 // whose accept kernels and summary it uses): 0 = done, 1 = does not apply or did not fit (acc is untouched), < 0 = error
@@ -2648,6 +2691,13 @@ int nts_hash_all(nts_ctx* ctx, const nts_genome* g, uint32_t k, uint64_t** h0, u
   *h0 = host;
   *n_out = rt.n_valid;
   return NTS_OK;
+}
+
+int nts_minhash(nts_ctx* ctx, const nts_genome* g, uint32_t k, uint32_t s, uint64_t* out, uint32_t* n_out)
+{
+  if (!ctx || !g || !out || !n_out || k == 0 || s == 0) return fail(ctx, NTS_EINVAL, "nts_minhash: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return minhash_run(ctx, g, k, s, out, n_out);
 }
 
 } // extern "C"

@@ -366,6 +366,15 @@ class Genome:
         self.ctx.lib.nts_free(p)
         return out
 
+    def minhash(self, k, s):
+        """bottom-s MinHash sketch (nts_minhash): the s smallest distinct canonical h0 over the valid k-mers, ascending --
+        exactly np.unique(hash_all(k))[:s] without the sentinel 2^64 - 1 (fewer than s if there are fewer distinct k-mers)"""
+        out = np.empty(max(int(s), 1), dtype=np.uint64)
+        n = _lib.u32()
+        self.ctx.check(self.ctx.lib.nts_minhash(self.ctx.h, self.h, int(k), int(s), out.ctypes.data_as(_lib.c_u64p), ctypes.byref(n)),
+                       "nts_minhash")
+        return out[:n.value].copy()
+
     def free(self):
         if self.h:
             self.ctx.lib.nts_genome_free(self.ctx.h, self.h)

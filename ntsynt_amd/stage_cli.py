@@ -119,6 +119,43 @@ def indexlr(argv=None):
     return 0
 
 
+# ---- ntsynt_divergence --------------------------------------------------------------------------------------------------------------
+def divergence_parser():
+    p = argparse.ArgumentParser(prog="ntsynt_divergence", description="pairwise Mash distances of genome assemblies from MinHash sketches made "
+                                "on the GPU, and the ntSynt -d they suggest (100 x the largest distance, rounded up to 0.001)")
+    p.add_argument("fastas", nargs="*", help="genome assemblies (FASTA, plain or .gz), two or more")
+    p.add_argument("--fastas_list", help="text file naming the assemblies, one path per line (instead of positional arguments)")
+    p.add_argument("-k", type=int, default=21, help="k-mer size [21]")
+    p.add_argument("-s", "--sketch-size", type=int, default=10000, help="hashes per sketch [10000]")
+    p.add_argument("--device", type=int, default=0, help="GPU index [0]")
+    p.add_argument("-o", metavar="FILE", default="/dev/stdout", help="output file [stdout]")
+    return p
+
+
+def ntsynt_divergence(argv=None):
+    "TSV genome_a genome_b distance shared_hashes sketch_size, one line per unordered pair in input order, then `# ntSynt -d <value>`"
+    parser = divergence_parser()
+    args = parser.parse_args(argv)
+    if args.fastas and args.fastas_list:
+        parser.error("give the FASTA files as positional arguments or with --fastas_list, not both")
+    fastas = args.fastas
+    if args.fastas_list:
+        with open(args.fastas_list, "r", encoding="utf-8") as fin:
+            fastas = [line.strip() for line in fin if line.strip()]
+    if len(fastas) < 2:
+        parser.error("at least two genome FASTA files are needed")
+    if args.k < 1 or args.sketch_size < 1:
+        parser.error("-k and --sketch-size must be positive")
+    for fasta in fastas:
+        if not os.path.isfile(fasta):
+            raise FileNotFoundError(f"Input file {fasta} not found.")
+    from . import divergence
+    est = divergence.estimate(fastas, k=args.k, s=args.sketch_size, device=args.device)
+    with open(args.o, "w", encoding="utf-8") as out:
+        out.write(est.table())
+    return 0
+
+
 # ---- ntsynt_run.py ----------------------------------------------------------------------------------------------------------------
 def run_parser():
     "bin/ntsynt_run.py:10-44, flag for flag"
