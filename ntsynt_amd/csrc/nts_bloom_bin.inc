@@ -1069,11 +1069,8 @@ int bf_insert_binned(nts_ctx* ctx, nts_bf* bf, const nts_genome* g, const Genome
   const uint64_t tiles = (V + KEY_TILE - 1) / KEY_TILE;
   const uint64_t tiles2 = (cap1 + KEY_TILE - 1) / KEY_TILE;
   if (tiles > 0x7FFFFFFFULL || tiles2 * (B1 + 8ull) > 0x7FFFFFFFULL || B1 > 65535 || n_final > 0x7FFFFFFFULL) return 1;
-#define BN_WS(ptr, type, name, bytes)                                                               \
-  type ptr = (type)ws_get(ctx, name, bytes);                                                        \
-  if (!ptr) return NTS_ENOMEM
-  BN_WS(d_cnt1, uint32_t*, "bin_cnt1", (uint64_t)B1 * BIN_CNT_STRIDE * 4);
-  BN_WS(d_out1, uint32_t*, "bin_out1", (uint64_t)B1 * cap1 * 4);
+  NTS_WS(d_cnt1, uint32_t*, "bin_cnt1", (uint64_t)B1 * BIN_CNT_STRIDE * 4);
+  NTS_WS(d_out1, uint32_t*, "bin_out1", (uint64_t)B1 * cap1 * 4);
   uint32_t* d_cnt2 = nullptr;
   uint32_t* d_out2 = nullptr;
   if (log2_b2) {
@@ -1081,7 +1078,6 @@ int bf_insert_binned(nts_ctx* ctx, nts_bf* bf, const nts_genome* g, const Genome
     d_out2 = (uint32_t*)ws_get(ctx, "bin_out2", n_final * cap2 * 8);
     if (!d_cnt2 || !d_out2) return NTS_ENOMEM;
   }
-#undef BN_WS
   const size_t lds3 = (size_t)BIN_FINAL_WORDS * 4;
   if (!ctx->bin_lds_set) {
     HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_bin3<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3));

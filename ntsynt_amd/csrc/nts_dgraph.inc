@@ -43,9 +43,6 @@ constexpr uint32_t E_NONE = 0xFFFFFFFFu;
 constexpr uint32_t E_BAD = 0xFFFFFFFEu;
 constexpr uint64_t IV_OFF = (uint64_t)1 << 40; // composite interval key: record * 2^40 + position (ntsynt_amd/synteny.py)
 
-#define E_WS(ptr, type, name, bytes)                                                                \
-  type ptr = (type)ws_get(ctx, name, std::max<uint64_t>((bytes), 16));                              \
-  if (!ptr) return NTS_ENOMEM
 #define E_GRID(n) dim3((uint32_t)(((n) + 255) / 256)), dim3(256), 0, ctx->stream
 
 template <typename T>
@@ -886,7 +883,7 @@ int e_count(nts_ctx* ctx, const uint64_t* flag, const uint64_t* scan, uint64_t n
 int e_degrees(nts_ctx* ctx, nts_engine* E, uint32_t** deg, uint32_t** nbr, uint32_t** nbe)
 {
   const uint64_t nv = std::max<uint64_t>(E->nv, 1);
-  E_WS(d_deg, uint32_t*, "e_deg", nv * 4);
+  NTS_WS(d_deg, uint32_t*, "e_deg", nv * 4);
   HIP_TRY(ctx, hipMemsetAsync(d_deg, 0, nv * 4, ctx->stream));
   uint32_t *d_nbr = nullptr, *d_nbe = nullptr;
   if (nbr) {
@@ -913,8 +910,8 @@ struct RefineHook : ListHook
   int operator()(nts_ctx* ctx, uint64_t n, const uint8_t* d_valid, const uint32_t* d_asm, const uint32_t* d_rec, const uint64_t* d_pos,
                  uint32_t* d_list) override
   {
-    E_WS(d_a, uint64_t*, "e_hook_a", n * 8);
-    E_WS(d_b, uint64_t*, "e_hook_b", n * 8);
+    NTS_WS(d_a, uint64_t*, "e_hook_a", n * 8);
+    NTS_WS(d_b, uint64_t*, "e_hook_b", n * 8);
     NTS_LAUNCH(k_e_lastvalid_in, E_GRID(n), d_valid, n, d_a);
     size_t tmp = 0;
     HIP_TRY(ctx, rocprim::inclusive_scan(nullptr, tmp, d_a, d_b, n, rocprim::maximum<uint64_t>(), ctx->stream));
@@ -1101,10 +1098,10 @@ int nts_engine_add(nts_ctx* ctx, nts_engine* E, const nts_mx* const* lists, cons
   const bool refine = spans != nullptr;
   if (nv0) {
     // live index: (hash, vertex) of the live vertices, by hash -- a deleted vertex may share its hash with a re-created one
-    E_WS(d_f, uint64_t*, "e_flag", nv0 * 8);
-    E_WS(d_s, uint64_t*, "e_scan", nv0 * 8);
-    E_WS(d_k, uint64_t*, "e_hs0", nv0 * 8);
-    E_WS(d_i, uint32_t*, "e_hid0", nv0 * 4);
+    NTS_WS(d_f, uint64_t*, "e_flag", nv0 * 8);
+    NTS_WS(d_s, uint64_t*, "e_scan", nv0 * 8);
+    NTS_WS(d_k, uint64_t*, "e_hs0", nv0 * 8);
+    NTS_WS(d_i, uint32_t*, "e_hid0", nv0 * 4);
     d_hs = (uint64_t*)ws_get(ctx, "e_hs", nv0 * 8);
     d_hid = (uint32_t*)ws_get(ctx, "e_hid", nv0 * 4);
     if (!d_hs || !d_hid) return NTS_ENOMEM;
@@ -1125,9 +1122,9 @@ int nts_engine_add(nts_ctx* ctx, nts_engine* E, const nts_mx* const* lists, cons
     std::vector<uint64_t> off(G + 1, 0);
     for (uint32_t a = 0; a < G; ++a) off[a + 1] = off[a] + spans[a].n;
     const uint64_t tot = off[G];
-    E_WS(d_cs, uint64_t*, "e_iv_s", tot * 8);
-    E_WS(d_cm, uint64_t*, "e_iv_m", tot * 8);
-    E_WS(d_off, uint64_t*, "e_iv_off", (G + 1) * 8);
+    NTS_WS(d_cs, uint64_t*, "e_iv_s", tot * 8);
+    NTS_WS(d_cm, uint64_t*, "e_iv_m", tot * 8);
+    NTS_WS(d_off, uint64_t*, "e_iv_off", (G + 1) * 8);
     for (uint32_t a = 0; a < G; ++a) {
       if (!spans[a].n) continue;
       if (!spans[a].start || !spans[a].end_max) return fail(ctx, NTS_EINVAL, "nts_engine_add: NULL span arrays");
@@ -1146,9 +1143,9 @@ int nts_engine_add(nts_ctx* ctx, nts_engine* E, const nts_mx* const* lists, cons
   const uint64_t lnv = GD.nv, lne = GD.ne;
   if (lnv == 0) return NTS_OK;
   // ---- vertices
-  E_WS(d_l2g, uint32_t*, "e_l2g", lnv * 4);
-  E_WS(d_new, uint64_t*, "e_new", lnv * 8);
-  E_WS(d_rank, uint64_t*, "e_rank", lnv * 8);
+  NTS_WS(d_l2g, uint32_t*, "e_l2g", lnv * 4);
+  NTS_WS(d_new, uint64_t*, "e_new", lnv * 8);
+  NTS_WS(d_rank, uint64_t*, "e_rank", lnv * 8);
   uint64_t n_new = lnv;
   if (nv0) {
     NTS_LAUNCH(k_e_lookup, E_GRID(lnv), GD.v_hash, lnv, d_hs, d_hid, nl, d_l2g, d_new);
@@ -1168,10 +1165,10 @@ int nts_engine_add(nts_ctx* ctx, nts_engine* E, const nts_mx* const* lists, cons
   E->nv = nv0 + n_new;
   // ---- edges (already in ntJoin's dict order)
   if (lne) {
-    E_WS(d_gu, uint32_t*, "e_gu", lne * 4);
-    E_WS(d_gv, uint32_t*, "e_gv", lne * 4);
-    E_WS(d_oo, uint64_t*, "e_oo", lne * 8);
-    E_WS(d_oos, uint64_t*, "e_oos", lne * 8);
+    NTS_WS(d_gu, uint32_t*, "e_gu", lne * 4);
+    NTS_WS(d_gv, uint32_t*, "e_gv", lne * 4);
+    NTS_WS(d_oo, uint64_t*, "e_oo", lne * 8);
+    NTS_WS(d_oos, uint64_t*, "e_oos", lne * 8);
     NTS_LAUNCH(k_e_map_edges, E_GRID(lne), GD.e_u, GD.e_v, lne, d_l2g, nv0, d_gu, d_gv, d_oo);
     uint64_t n_oo = 0;
     if (nv0 && ne0) {
@@ -1183,24 +1180,24 @@ int nts_engine_add(nts_ctx* ctx, nts_engine* E, const nts_mx* const* lists, cons
       // an edge that already exists (alive) keeps its slot and takes the new weight; only an edge between two vertices that
       // existed before this build can be one.  The candidates and the live edges among their end points are few: joined on
       // the host.
-      E_WS(q_idx, uint32_t*, "e_q_idx", n_oo * 4);
-      E_WS(q_u, uint32_t*, "e_q_u", n_oo * 4);
-      E_WS(q_v, uint32_t*, "e_q_v", n_oo * 4);
-      E_WS(q_w, uint32_t*, "e_q_w", n_oo * 4);
+      NTS_WS(q_idx, uint32_t*, "e_q_idx", n_oo * 4);
+      NTS_WS(q_u, uint32_t*, "e_q_u", n_oo * 4);
+      NTS_WS(q_v, uint32_t*, "e_q_v", n_oo * 4);
+      NTS_WS(q_w, uint32_t*, "e_q_w", n_oo * 4);
       NTS_LAUNCH(k_e_take_flagged, E_GRID(lne), d_oo, d_oos, lne, d_gu, d_gv, GD.e_w, q_idx, q_u, q_v, q_w);
-      E_WS(d_touched, uint8_t*, "e_touched", nv0);
+      NTS_WS(d_touched, uint8_t*, "e_touched", nv0);
       HIP_TRY(ctx, hipMemsetAsync(d_touched, 0, nv0, ctx->stream));
       NTS_LAUNCH(k_e_touch, E_GRID(n_oo), q_u, q_v, n_oo, d_touched);
-      E_WS(d_tf, uint64_t*, "e_flag", std::max(ne0, nv0) * 8);
-      E_WS(d_ts, uint64_t*, "e_scan", std::max(ne0, nv0) * 8);
+      NTS_WS(d_tf, uint64_t*, "e_flag", std::max(ne0, nv0) * 8);
+      NTS_WS(d_ts, uint64_t*, "e_scan", std::max(ne0, nv0) * 8);
       NTS_LAUNCH(k_e_touched_edges, E_GRID(ne0), E->e_u, E->e_v, E->e_alive, ne0, d_touched, d_tf);
       if (int rc = e_scan(ctx, d_tf, d_ts, ne0)) return rc;
       uint64_t n_te = 0;
       if (int rc = e_count(ctx, d_tf, d_ts, ne0, &n_te)) return rc;
       if (n_te) {
-        E_WS(t_idx, uint32_t*, "e_t_idx", n_te * 4);
-        E_WS(t_u, uint32_t*, "e_t_u", n_te * 4);
-        E_WS(t_v, uint32_t*, "e_t_v", n_te * 4);
+        NTS_WS(t_idx, uint32_t*, "e_t_idx", n_te * 4);
+        NTS_WS(t_u, uint32_t*, "e_t_u", n_te * 4);
+        NTS_WS(t_v, uint32_t*, "e_t_v", n_te * 4);
         NTS_LAUNCH(k_e_take_flagged, E_GRID(ne0), d_tf, d_ts, ne0, E->e_u, E->e_v, (const uint32_t*)nullptr, t_idx, t_u, t_v,
                            (uint32_t*)nullptr);
         // the join on the device: the live edges' pairs sorted (stable: of two live edges of one pair -- which cannot be -- the older comes
@@ -1208,9 +1205,9 @@ int nts_engine_add(nts_ctx* ctx, nts_engine* E, const nts_mx* const* lists, cons
         // 3 x 1 Gbp, second refinement round: 10.5 M new edges between old vertices against 13.6 M live edges -- 20 s through a std::map.)
         if (NTS_KNOB("NTS_DEBUG_ENGINE")) fprintf(stderr, "[engine add] new edges between old vertices %llu, live edges at their ends %llu (of %llu edges, %llu new)\n",
                                                   (unsigned long long)n_oo, (unsigned long long)n_te, (unsigned long long)ne0, (unsigned long long)lne);
-        E_WS(d_tk, uint64_t*, "e_join_key", n_te * 8);
-        E_WS(d_tk2, uint64_t*, "e_join_key2", n_te * 8);
-        E_WS(t_idx2, uint32_t*, "e_join_idx2", n_te * 4);
+        NTS_WS(d_tk, uint64_t*, "e_join_key", n_te * 8);
+        NTS_WS(d_tk2, uint64_t*, "e_join_key2", n_te * 8);
+        NTS_WS(t_idx2, uint32_t*, "e_join_idx2", n_te * 4);
         NTS_LAUNCH(k_e_pair_keys, E_GRID(n_te), t_u, t_v, n_te, d_tk);
         {
           size_t tmp = 0;
@@ -1219,17 +1216,17 @@ int nts_engine_add(nts_ctx* ctx, nts_engine* E, const nts_mx* const* lists, cons
           if (!d_tmp) return NTS_ENOMEM;
           HIP_TRY(ctx, rocprim::radix_sort_pairs(d_tmp, tmp, d_tk, d_tk2, t_idx, t_idx2, n_te, 0, 64, ctx->stream));
         }
-        E_WS(d_hit, uint64_t*, "e_join_hit", n_oo * 8);
-        E_WS(d_hits, uint64_t*, "e_join_hits", n_oo * 8);
-        E_WS(d_hedge, uint32_t*, "e_join_edge", n_oo * 4);
+        NTS_WS(d_hit, uint64_t*, "e_join_hit", n_oo * 8);
+        NTS_WS(d_hits, uint64_t*, "e_join_hits", n_oo * 8);
+        NTS_WS(d_hedge, uint32_t*, "e_join_edge", n_oo * 4);
         NTS_LAUNCH(k_e_join_pairs, E_GRID(n_oo), q_u, q_v, n_oo, d_tk2, t_idx2, n_te, d_hit, d_hedge);
         if (int rc = e_scan(ctx, d_hit, d_hits, n_oo)) return rc;
         if (int rc = e_count(ctx, d_hit, d_hits, n_oo, &n_dup)) return rc;
         if (n_dup) {
-          E_WS(d_dl, uint32_t*, "e_dup_l", n_dup * 4);
-          E_WS(d_he, uint32_t*, "e_dup_e", n_dup * 4);
-          E_WS(d_hw, uint32_t*, "e_dup_w", n_dup * 4);
-          E_WS(d_di, uint32_t*, "e_dup_i", n_dup * 4);
+          NTS_WS(d_dl, uint32_t*, "e_dup_l", n_dup * 4);
+          NTS_WS(d_he, uint32_t*, "e_dup_e", n_dup * 4);
+          NTS_WS(d_hw, uint32_t*, "e_dup_w", n_dup * 4);
+          NTS_WS(d_di, uint32_t*, "e_dup_i", n_dup * 4);
           NTS_LAUNCH(k_e_take_flagged, E_GRID(n_oo), d_hit, d_hits, n_oo, q_idx, d_hedge, q_w, d_di, d_dl, d_he, d_hw);
           NTS_LAUNCH(k_e_set_u32, E_GRID(n_dup), E->e_w, d_he, d_hw, 0u, n_dup);
           // keep flags of the new edges: all but the duplicates
@@ -1262,18 +1259,18 @@ int nts_engine_bubbles(nts_ctx* ctx, nts_engine* E, nts_bubbles* out)
   if (E->ne == 0) return NTS_OK;
   uint32_t* d_deg = nullptr;
   if (int rc = e_degrees(ctx, E, &d_deg, nullptr, nullptr)) return rc;
-  E_WS(d_cv, uint8_t*, "e_iscv", E->nv);
-  E_WS(d_f, uint64_t*, "e_flag", std::max(E->ne, E->nv) * 8);
-  E_WS(d_s, uint64_t*, "e_scan", std::max(E->ne, E->nv) * 8);
+  NTS_WS(d_cv, uint8_t*, "e_iscv", E->nv);
+  NTS_WS(d_f, uint64_t*, "e_flag", std::max(E->ne, E->nv) * 8);
+  NTS_WS(d_s, uint64_t*, "e_scan", std::max(E->ne, E->nv) * 8);
   HIP_TRY(ctx, hipMemsetAsync(d_cv, 0, E->nv, ctx->stream));
   NTS_LAUNCH(k_e_bubble_cand, E_GRID(E->ne), E->e_u, E->e_v, E->e_alive, E->ne, d_deg, d_cv, d_f);
   if (int rc = e_scan(ctx, d_f, d_s, E->ne)) return rc;
   uint64_t n_cand = 0;
   if (int rc = e_count(ctx, d_f, d_s, E->ne, &n_cand)) return rc;
   if (n_cand == 0) return NTS_OK;
-  E_WS(c_idx, uint32_t*, "e_c_idx", n_cand * 4);
-  E_WS(c_u, uint32_t*, "e_c_u", n_cand * 4);
-  E_WS(c_v, uint32_t*, "e_c_v", n_cand * 4);
+  NTS_WS(c_idx, uint32_t*, "e_c_idx", n_cand * 4);
+  NTS_WS(c_u, uint32_t*, "e_c_u", n_cand * 4);
+  NTS_WS(c_v, uint32_t*, "e_c_v", n_cand * 4);
   NTS_LAUNCH(k_e_take_flagged, E_GRID(E->ne), d_f, d_s, E->ne, E->e_u, E->e_v, (const uint32_t*)nullptr, c_idx, c_u, c_v, (uint32_t*)nullptr);
   out->n_cand = n_cand;
   out->cand_edge = e_host(ctx, c_idx, n_cand);
@@ -1282,10 +1279,10 @@ int nts_engine_bubbles(nts_ctx* ctx, nts_engine* E, nts_bubbles* out)
   if (int rc = e_scan(ctx, d_f, d_s, E->ne)) return rc;
   uint64_t n_inc = 0;
   if (int rc = e_count(ctx, d_f, d_s, E->ne, &n_inc)) return rc;
-  E_WS(i_idx, uint32_t*, "e_i_idx", n_inc * 4);
-  E_WS(i_u, uint32_t*, "e_i_u", n_inc * 4);
-  E_WS(i_v, uint32_t*, "e_i_v", n_inc * 4);
-  E_WS(i_w, uint32_t*, "e_i_w", n_inc * 4);
+  NTS_WS(i_idx, uint32_t*, "e_i_idx", n_inc * 4);
+  NTS_WS(i_u, uint32_t*, "e_i_u", n_inc * 4);
+  NTS_WS(i_v, uint32_t*, "e_i_v", n_inc * 4);
+  NTS_WS(i_w, uint32_t*, "e_i_w", n_inc * 4);
   NTS_LAUNCH(k_e_take_flagged, E_GRID(E->ne), d_f, d_s, E->ne, E->e_u, E->e_v, E->e_w, i_idx, i_u, i_v, i_w);
   out->n_inc = n_inc;
   out->inc_edge = e_host(ctx, i_idx, n_inc);
@@ -1323,13 +1320,13 @@ int nts_engine_apply(nts_ctx* ctx, nts_engine* E, const uint32_t* dead, uint64_t
   for (uint64_t i = 0; i < n_promote; ++i)
     if (promote[i] >= E->ne) return fail(ctx, NTS_EINVAL, "nts_engine_apply: edge out of range");
   if (n_promote) {
-    E_WS(d_p, uint32_t*, "e_apply_p", n_promote * 4);
+    NTS_WS(d_p, uint32_t*, "e_apply_p", n_promote * 4);
     HIP_TRY(ctx, hipMemcpyAsync(d_p, promote, n_promote * 4, hipMemcpyHostToDevice, ctx->stream));
     NTS_LAUNCH(k_e_set_u32, E_GRID(n_promote), E->e_w, d_p, (const uint32_t*)nullptr, weight, n_promote);
   }
   if (n_dead) {
-    E_WS(d_d, uint32_t*, "e_apply_d", n_dead * 4);
-    E_WS(d_dead, uint8_t*, "e_dead", E->nv);
+    NTS_WS(d_d, uint32_t*, "e_apply_d", n_dead * 4);
+    NTS_WS(d_dead, uint8_t*, "e_dead", E->nv);
     HIP_TRY(ctx, hipMemcpyAsync(d_d, dead, n_dead * 4, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(d_dead, 0, E->nv, ctx->stream));
     NTS_LAUNCH(k_e_set_u8, E_GRID(n_dead), d_dead, d_d, (uint8_t)1, n_dead);
@@ -1349,8 +1346,8 @@ int nts_engine_filter(nts_ctx* ctx, nts_engine* E, uint32_t min_weight, int flag
   E->n_flag = 0;
   if (n_light) *n_light = 0;
   if (E->ne == 0) return NTS_OK;
-  E_WS(d_f, uint64_t*, "e_flag", std::max(E->ne, E->nv) * 8);
-  E_WS(d_s, uint64_t*, "e_scan", std::max(E->ne, E->nv) * 8);
+  NTS_WS(d_f, uint64_t*, "e_flag", std::max(E->ne, E->nv) * 8);
+  NTS_WS(d_s, uint64_t*, "e_scan", std::max(E->ne, E->nv) * 8);
   NTS_LAUNCH(k_e_light, E_GRID(E->ne), E->e_w, E->e_alive, E->ne, min_weight, d_f);
   if (!flag && !n_light) return NTS_OK;
   if (int rc = e_scan(ctx, d_f, d_s, E->ne)) return rc;
@@ -1367,7 +1364,7 @@ int nts_engine_filter(nts_ctx* ctx, nts_engine* E, uint32_t min_weight, int flag
         return fail(ctx, NTS_ENOMEM, "nts_engine_filter: hipMalloc");
       E->cap_flag = n;
     }
-    E_WS(d_idx, uint32_t*, "e_fl_idx", n * 4);
+    NTS_WS(d_idx, uint32_t*, "e_fl_idx", n * 4);
     NTS_LAUNCH(k_e_take_flagged, E_GRID(E->ne), d_f, d_s, E->ne, E->e_u, E->e_v, (const uint32_t*)nullptr, d_idx, E->fl_u, E->fl_v,
                        (uint32_t*)nullptr);
     E->n_flag = n;
@@ -1385,9 +1382,9 @@ int nts_engine_erode(nts_ctx* ctx, nts_engine* E, uint32_t k, uint64_t* n_dead_e
   if (E->n_flag == 0 || E->ne == 0) return NTS_OK;
   uint32_t *d_deg = nullptr, *d_nbr = nullptr, *d_nbe = nullptr;
   if (int rc = e_degrees(ctx, E, &d_deg, &d_nbr, &d_nbe)) return rc;
-  E_WS(d_edead, uint8_t*, "e_edead", E->ne);
-  E_WS(d_ctl, unsigned long long*, "e_ctl", 64);
-  E_WS(d_later, uint32_t*, "e_later", E->n_flag * 4);
+  NTS_WS(d_edead, uint8_t*, "e_edead", E->ne);
+  NTS_WS(d_ctl, unsigned long long*, "e_ctl", 64);
+  NTS_WS(d_later, uint32_t*, "e_later", E->n_flag * 4);
   HIP_TRY(ctx, hipMemsetAsync(d_edead, 0, E->ne, ctx->stream));
   HIP_TRY(ctx, hipMemsetAsync(d_ctl, 0, 64, ctx->stream));
   const uint32_t all_later = NTS_KNOB("NTS_ERODE_HOST") && atoi(NTS_KNOB("NTS_ERODE_HOST")) ? 1u : 0u; // (tests: every pair on the host)
@@ -1485,7 +1482,7 @@ int nts_engine_erode(nts_ctx* ctx, nts_engine* E, uint32_t k, uint64_t* n_dead_e
       }
     }
     if (!dead.empty()) {
-      E_WS(d_didx, uint64_t*, "e_later_dead", dead.size() * 8);
+      NTS_WS(d_didx, uint64_t*, "e_later_dead", dead.size() * 8);
       HIP_TRY(ctx, hipMemcpyAsync(d_didx, dead.data(), dead.size() * 8, hipMemcpyHostToDevice, ctx->stream));
       NTS_LAUNCH(k_e_mark_u8, E_GRID(dead.size()), d_didx, dead.size(), d_edead);
       HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); // (`dead` leaves scope)
@@ -1525,8 +1522,8 @@ int nts_engine_blocks(nts_ctx* ctx, nts_engine* E, int64_t bp, double m_percent,
   if (int rc = e_degrees(ctx, E, &d_deg, &d_nbr, &d_nbe)) return rc;
   lap("degrees");
   // ---- list ranking
-  E_WS(d_st0, uint4*, "e_arc0", 2 * nv * 16);
-  E_WS(d_st1, uint4*, "e_arc1", 2 * nv * 16);
+  NTS_WS(d_st0, uint4*, "e_arc0", 2 * nv * 16);
+  NTS_WS(d_st1, uint4*, "e_arc1", 2 * nv * 16);
   NTS_LAUNCH(k_e_arc_init, E_GRID(2 * nv), d_deg, d_nbr, nv, d_st0);
   int rounds = 1;
   while (((uint64_t)1 << rounds) < nv + 1) ++rounds;
@@ -1540,38 +1537,38 @@ int nts_engine_blocks(nts_ctx* ctx, nts_engine* E, int64_t bp, double m_percent,
     }
   }
   lap("pointer jumps");
-  E_WS(d_pstart, uint32_t*, "e_pstart", nv * 4);
-  E_WS(d_pidx, uint32_t*, "e_pidx", nv * 4);
-  E_WS(d_plen, uint32_t*, "e_plen", nv * 4);
-  E_WS(d_f, uint64_t*, "e_flag", std::max(E->ne, nv) * 8);
-  E_WS(d_s, uint64_t*, "e_scan", std::max(E->ne, nv) * 8);
+  NTS_WS(d_pstart, uint32_t*, "e_pstart", nv * 4);
+  NTS_WS(d_pidx, uint32_t*, "e_pidx", nv * 4);
+  NTS_WS(d_plen, uint32_t*, "e_plen", nv * 4);
+  NTS_WS(d_f, uint64_t*, "e_flag", std::max(E->ne, nv) * 8);
+  NTS_WS(d_s, uint64_t*, "e_scan", std::max(E->ne, nv) * 8);
   NTS_LAUNCH(k_e_classify, E_GRID(nv), d_deg, a, nv, E->v_pos + (uint64_t)E->ref * E->cap_v, d_pstart, d_pidx, d_plen, d_f);
   if (int rc = e_scan(ctx, d_f, d_s, nv)) return rc;
   uint64_t n_paths = 0;
   if (int rc = e_count(ctx, d_f, d_s, nv, &n_paths)) return rc;
   out->stats_paths = n_paths;
   if (n_paths == 0) return NTS_OK;
-  E_WS(d_lens, uint64_t*, "e_lens", (n_paths + 1) * 8);
-  E_WS(d_poff, uint64_t*, "e_poff", (n_paths + 1) * 8);
+  NTS_WS(d_lens, uint64_t*, "e_lens", (n_paths + 1) * 8);
+  NTS_WS(d_poff, uint64_t*, "e_poff", (n_paths + 1) * 8);
   HIP_TRY(ctx, hipMemsetAsync(d_lens + n_paths, 0, 8, ctx->stream));
   NTS_LAUNCH(k_e_path_len, E_GRID(nv), d_f, d_s, d_plen, nv, d_lens);
   if (int rc = e_scan(ctx, d_lens, d_poff, n_paths + 1)) return rc;
   uint64_t N = 0;
   if (int rc = e_fetch(ctx, d_poff + n_paths, &N)) return rc;
-  E_WS(d_verts, uint32_t*, "e_verts", (N + 1) * 4);
-  E_WS(d_vpath, uint32_t*, "e_vpath", N * 4);
+  NTS_WS(d_verts, uint32_t*, "e_verts", (N + 1) * 4);
+  NTS_WS(d_vpath, uint32_t*, "e_vpath", N * 4);
   NTS_LAUNCH(k_e_place, E_GRID(nv), d_pstart, d_pidx, d_s, d_poff, nv, d_verts, d_vpath);
   E->n_paths = n_paths;
   E->n_path_verts = N;
   lap("path order");
   // ---- per-path scan
-  E_WS(d_pst, uint32_t*, "e_pst", n_paths * 4);
-  E_WS(d_nup, uint32_t*, "e_nup", G * n_paths * 4);
-  E_WS(d_over, uint8_t*, "e_over", N + 1);
-  E_WS(d_pcode, uint8_t*, "e_pcode", G * n_paths);
-  E_WS(d_pgood, uint8_t*, "e_pgood", n_paths);
-  E_WS(d_ctl, unsigned long long*, "e_ctl", 64);
-  E_WS(d_dead, uint8_t*, "e_dead", nv);
+  NTS_WS(d_pst, uint32_t*, "e_pst", n_paths * 4);
+  NTS_WS(d_nup, uint32_t*, "e_nup", G * n_paths * 4);
+  NTS_WS(d_over, uint8_t*, "e_over", N + 1);
+  NTS_WS(d_pcode, uint8_t*, "e_pcode", G * n_paths);
+  NTS_WS(d_pgood, uint8_t*, "e_pgood", n_paths);
+  NTS_WS(d_ctl, unsigned long long*, "e_ctl", 64);
+  NTS_WS(d_dead, uint8_t*, "e_dead", nv);
   HIP_TRY(ctx, hipMemsetAsync(d_nup, 0, G * n_paths * 4, ctx->stream));
   HIP_TRY(ctx, hipMemsetAsync(d_ctl, 0, 64, ctx->stream));
   HIP_TRY(ctx, hipMemsetAsync(d_dead, 0, nv, ctx->stream));
@@ -1581,8 +1578,8 @@ int nts_engine_blocks(nts_ctx* ctx, nts_engine* E, int64_t bp, double m_percent,
   NTS_LAUNCH(k_e_orient, E_GRID(n_paths), d_poff, d_pst, d_nup, n_paths, E->G, m_percent, d_pcode, d_pgood, d_ctl);
   lap("path scans");
   // ---- blocks
-  E_WS(d_bs, uint64_t*, "e_bstart", N * 8);
-  E_WS(d_bscan, uint64_t*, "e_bscan", N * 8);
+  NTS_WS(d_bs, uint64_t*, "e_bstart", N * 8);
+  NTS_WS(d_bscan, uint64_t*, "e_bscan", N * 8);
   NTS_LAUNCH(k_e_block_starts, E_GRID(N), d_verts, d_vpath, N, d_poff, d_pst, d_pgood, d_over, d_dead, d_bs);
   NTS_LAUNCH(k_e_cuts, E_GRID(N), d_verts, N, d_over, d_nbr, d_nbe, E->e_alive, d_ctl + 1);
   if (int rc = e_scan(ctx, d_bs, d_bscan, N)) return rc;
@@ -1614,13 +1611,13 @@ int nts_engine_blocks(nts_ctx* ctx, nts_engine* E, int64_t bp, double m_percent,
   out->stats_small = ctl[2];
   out->n_blocks = n_kept;
   if (n_kept == 0) return NTS_OK;
-  E_WS(o_first, uint32_t*, "e_o_first", n_kept * 4);
-  E_WS(o_last, uint32_t*, "e_o_last", n_kept * 4);
-  E_WS(o_n, uint32_t*, "e_o_n", n_kept * 4);
-  E_WS(o_rec, uint32_t*, "e_o_rec", G * n_kept * 4);
-  E_WS(o_fp, uint64_t*, "e_o_fp", G * n_kept * 8);
-  E_WS(o_lp, uint64_t*, "e_o_lp", G * n_kept * 8);
-  E_WS(o_ori, uint8_t*, "e_o_ori", G * n_kept);
+  NTS_WS(o_first, uint32_t*, "e_o_first", n_kept * 4);
+  NTS_WS(o_last, uint32_t*, "e_o_last", n_kept * 4);
+  NTS_WS(o_n, uint32_t*, "e_o_n", n_kept * 4);
+  NTS_WS(o_rec, uint32_t*, "e_o_rec", G * n_kept * 4);
+  NTS_WS(o_fp, uint64_t*, "e_o_fp", G * n_kept * 8);
+  NTS_WS(o_lp, uint64_t*, "e_o_lp", G * n_kept * 8);
+  NTS_WS(o_ori, uint8_t*, "e_o_ori", G * n_kept);
   NTS_LAUNCH(k_e_block_table, E_GRID(n_blocks), d_bkeep, d_bwhere, n_blocks, n_kept, d_bfirst, d_blast, d_bpath, d_verts, d_pst, d_pcode,
                      n_paths, E->v_rec, E->v_pos, E->cap_v, E->G, o_first, o_last, o_n, o_rec, o_fp, o_lp, o_ori);
   HIP_TRY(ctx, hipGetLastError());
@@ -1783,5 +1780,4 @@ void nts_blocks_free(nts_blocks* b)
 
 } // extern "C"
 
-#undef E_WS
 #undef E_GRID

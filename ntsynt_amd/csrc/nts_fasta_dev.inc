@@ -430,9 +430,6 @@ extern "C" int nts_genome_from_fasta(nts_ctx* ctx, const char* path, nts_genome*
     if (q < n && raw[q] == '@') return fail(ctx, NTS_EFORMAT, std::string(path) + " is not FASTA (FASTQ?)");
     if (q == n) n = 0; // blank file: no records
   }
-#define FA_WS(ptr, type, name, bytes)                                                               \
-  type ptr = (type)ws_get(ctx, name, std::max<uint64_t>((bytes), 64));                              \
-  if (!ptr) return NTS_ENOMEM
   const uint64_t n_tiles = (n + FA_TILE - 1) / FA_TILE;
   uint64_t n_hdr = 0, n_seq = 0;
   std::vector<uint64_t> hs, he, le, roff, lcnt; // lcnt[r]: bases before the end of record r's first sequence line
@@ -456,11 +453,11 @@ extern "C" int nts_genome_from_fasta(nts_ctx* ctx, const char* path, nts_genome*
     if (fd >= 0) close(fd);
     if (rc_up) return rc_up;
     lap("upload");
-    FA_WS(d_tnl, uint64_t*, "fa_tile_nl", n_tiles * 8);
-    FA_WS(d_ctl, unsigned long long*, "fa_ctl", 64);
+    NTS_WS(d_tnl, uint64_t*, "fa_tile_nl", n_tiles * 8);
+    NTS_WS(d_ctl, unsigned long long*, "fa_ctl", 64);
     uint64_t cap = std::max<uint64_t>(1024, n / 4096);
     for (int attempt = 0;; ++attempt) {
-      FA_WS(d_hdr, uint64_t*, "fa_hdr", cap * 8);
+      NTS_WS(d_hdr, uint64_t*, "fa_hdr", cap * 8);
       HIP_TRY(ctx, hipMemsetAsync(d_ctl, 0, 64, ctx->stream));
       NTS_LAUNCH(k_fa_scan, dim3((uint32_t)n_tiles), dim3(256), 0, ctx->stream, d_raw, n, d_hdr, cap, d_ctl, d_tnl);
       unsigned long long cnt = 0;
@@ -477,16 +474,16 @@ extern "C" int nts_genome_from_fasta(nts_ctx* ctx, const char* path, nts_genome*
     uint64_t* d_hdr = (uint64_t*)ws_get(ctx, "fa_hdr", cap * 8);
     d_hs = (uint64_t*)ws_get(ctx, "fa_hs", n_hdr * 8);
     d_he = (uint64_t*)ws_get(ctx, "fa_he", n_hdr * 8);
-    FA_WS(d_le, uint64_t*, "fa_le", n_hdr * 8);
-    FA_WS(d_roff, uint64_t*, "fa_roff", n_hdr * 8);
+    NTS_WS(d_le, uint64_t*, "fa_le", n_hdr * 8);
+    NTS_WS(d_roff, uint64_t*, "fa_roff", n_hdr * 8);
     if (!d_hs || !d_he) return NTS_ENOMEM;
     size_t tmp = 0;
     HIP_TRY(ctx, rocprim::radix_sort_keys(nullptr, tmp, d_hdr, d_hs, n_hdr, 0, 64, ctx->stream));
-    FA_WS(d_tmp, void*, "fa_sort_tmp", tmp);
+    NTS_WS(d_tmp, void*, "fa_sort_tmp", tmp);
     HIP_TRY(ctx, rocprim::radix_sort_keys(d_tmp, tmp, d_hdr, d_hs, n_hdr, 0, 64, ctx->stream));
     NTS_LAUNCH(k_fa_headers, dim3((uint32_t)n_hdr), dim3(256), 0, ctx->stream, d_raw, n, d_hs, n_hdr, d_tnl, n_tiles, d_he, d_le);
     // bases per tile -> offsets
-    FA_WS(d_tcnt, uint64_t*, "fa_tile_cnt", (n_tiles + 1) * 8);
+    NTS_WS(d_tcnt, uint64_t*, "fa_tile_cnt", (n_tiles + 1) * 8);
     d_toff = (uint64_t*)ws_get(ctx, "fa_tile_off", (n_tiles + 1) * 8);
     if (!d_toff) return NTS_ENOMEM;
     HIP_TRY(ctx, hipMemsetAsync(d_tcnt + n_tiles, 0, 8, ctx->stream));
@@ -494,10 +491,10 @@ extern "C" int nts_genome_from_fasta(nts_ctx* ctx, const char* path, nts_genome*
                        (uint8_t*)nullptr, (uint32_t*)(d_ctl + 1));
     size_t tmp2 = 0;
     HIP_TRY(ctx, rocprim::exclusive_scan(nullptr, tmp2, d_tcnt, d_toff, (uint64_t)0, n_tiles + 1, rocprim::plus<uint64_t>(), ctx->stream));
-    FA_WS(d_tmp2, void*, "fa_scan_tmp", tmp2);
+    NTS_WS(d_tmp2, void*, "fa_scan_tmp", tmp2);
     HIP_TRY(ctx, rocprim::exclusive_scan(d_tmp2, tmp2, d_tcnt, d_toff, (uint64_t)0, n_tiles + 1, rocprim::plus<uint64_t>(), ctx->stream));
     NTS_LAUNCH(k_fa_rec_off, dim3((uint32_t)n_hdr), dim3(256), 0, ctx->stream, d_raw, n, d_hs, d_he, n_hdr, d_toff, d_hs, d_roff);
-    FA_WS(d_lcnt, uint64_t*, "fa_lcnt", n_hdr * 8);
+    NTS_WS(d_lcnt, uint64_t*, "fa_lcnt", n_hdr * 8);
     NTS_LAUNCH(k_fa_rec_off, dim3((uint32_t)n_hdr), dim3(256), 0, ctx->stream, d_raw, n, d_hs, d_he, n_hdr, d_toff, d_le, d_lcnt);
     hs.resize(n_hdr);
     he.resize(n_hdr);
@@ -583,7 +580,6 @@ extern "C" int nts_genome_from_fasta(nts_ctx* ctx, const char* path, nts_genome*
   lap("names");
   *out = g;
   return NTS_OK;
-#undef FA_WS
 }
 
 extern "C" int nts_ingest_trim(nts_ctx* ctx)

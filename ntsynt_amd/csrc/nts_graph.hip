@@ -213,27 +213,24 @@ int graph_build_core(nts_ctx* ctx, uint32_t n_asm, uint64_t n, GraphDev* G, List
   *G = GraphDev();
   G->n = n;
   if (n == 0) return NTS_OK;
-#define G_WS(ptr, type, name, bytes)                                                                \
-  type ptr = (type)ws_get(ctx, name, bytes);                                                        \
-  if (!ptr) return NTS_ENOMEM
-  G_WS(d_h, uint64_t*, "g_h", n * 8);
-  G_WS(d_idx, uint64_t*, "g_idx", n * 8);
-  G_WS(d_h2, uint64_t*, "g_h2", n * 8);
-  G_WS(d_idx2, uint64_t*, "g_idx2", n * 8);
-  G_WS(d_asm, uint32_t*, "g_asm", n * 4);
-  G_WS(d_rec, uint32_t*, "g_rec", n * 4);
-  G_WS(d_pos, uint64_t*, "g_pos", n * 8);
-  G_WS(d_keep, uint8_t*, "g_keep", n);
-  G_WS(d_list, uint32_t*, "g_list", n * 4);
-  G_WS(d_valid, uint8_t*, "g_valid", n);
-  G_WS(d_flag, uint64_t*, "g_flag", n * 8);
-  G_WS(d_scan, uint64_t*, "g_scan", (n + 1) * 8);
-  G_WS(d_evid, uint32_t*, "g_evid", n * 4);
+  NTS_WS(d_h, uint64_t*, "g_h", n * 8);
+  NTS_WS(d_idx, uint64_t*, "g_idx", n * 8);
+  NTS_WS(d_h2, uint64_t*, "g_h2", n * 8);
+  NTS_WS(d_idx2, uint64_t*, "g_idx2", n * 8);
+  NTS_WS(d_asm, uint32_t*, "g_asm", n * 4);
+  NTS_WS(d_rec, uint32_t*, "g_rec", n * 4);
+  NTS_WS(d_pos, uint64_t*, "g_pos", n * 8);
+  NTS_WS(d_keep, uint8_t*, "g_keep", n);
+  NTS_WS(d_list, uint32_t*, "g_list", n * 4);
+  NTS_WS(d_valid, uint8_t*, "g_valid", n);
+  NTS_WS(d_flag, uint64_t*, "g_flag", n * 8);
+  NTS_WS(d_scan, uint64_t*, "g_scan", (n + 1) * 8);
+  NTS_WS(d_evid, uint32_t*, "g_evid", n * 4);
   const uint32_t nb = (uint32_t)((n + 255) / 256);
   size_t tmp_sort = 0, tmp_scan = 0;
   HIP_TRY(ctx, rocprim::radix_sort_pairs(nullptr, tmp_sort, d_h, d_h2, d_idx, d_idx2, n, 0, 64, ctx->stream));
   HIP_TRY(ctx, rocprim::exclusive_scan(nullptr, tmp_scan, d_flag, d_scan, (uint64_t)0, n, rocprim::plus<uint64_t>(), ctx->stream));
-  G_WS(d_tmp, void*, "g_tmp", std::max<size_t>(std::max(tmp_sort, tmp_scan), 16));
+  NTS_WS(d_tmp, void*, "g_tmp", std::max<size_t>(std::max(tmp_sort, tmp_scan), 16));
   {
     ScopedTimer t(ctx, "graph_build");
     // C1 + keep mask
@@ -241,7 +238,7 @@ int graph_build_core(nts_ctx* ctx, uint32_t n_asm, uint64_t n, GraphDev* G, List
     NTS_LAUNCH(k_g_valid, dim3(nb), dim3(256), 0, ctx->stream, d_h2, d_idx2, d_asm, d_keep, n, d_valid);
   }
   if (hook) {
-    G_WS(d_valid_elem, uint8_t*, "g_valid_elem", n);
+    NTS_WS(d_valid_elem, uint8_t*, "g_valid_elem", n);
     NTS_LAUNCH(k_g_valid_scatter, dim3(nb), dim3(256), 0, ctx->stream, d_idx2, d_valid, n, d_valid_elem);
     if (int rc = (*hook)(ctx, n, d_valid_elem, d_asm, d_rec, d_pos, d_list)) return rc;
   }
@@ -258,9 +255,9 @@ int graph_build_core(nts_ctx* ctx, uint32_t n_asm, uint64_t n, GraphDev* G, List
   const uint64_t nv = last_scan + last_flag;
   G->nv = nv;
   if (nv == 0) return NTS_OK;
-  G_WS(d_vhash, uint64_t*, "g_vhash", nv * 8);
-  G_WS(d_orec, uint32_t*, "g_orec", (uint64_t)n_asm * nv * 4);
-  G_WS(d_opos, uint64_t*, "g_opos", (uint64_t)n_asm * nv * 8);
+  NTS_WS(d_vhash, uint64_t*, "g_vhash", nv * 8);
+  NTS_WS(d_orec, uint32_t*, "g_orec", (uint64_t)n_asm * nv * 4);
+  NTS_WS(d_opos, uint64_t*, "g_opos", (uint64_t)n_asm * nv * 8);
   HIP_TRY(ctx, hipMemsetAsync(d_evid, 0xFF, n * 4, ctx->stream));
   {
     ScopedTimer t(ctx, "graph_build");
@@ -271,19 +268,19 @@ int graph_build_core(nts_ctx* ctx, uint32_t n_asm, uint64_t n, GraphDev* G, List
     HIP_TRY(ctx, rocprim::exclusive_scan(d_tmp, tmp_scan, d_flag, d_scan, (uint64_t)0, n, rocprim::plus<uint64_t>(), ctx->stream));
   }
   const uint64_t m = (uint64_t)n_asm * nv; // every common hash occurs once per assembly
-  G_WS(d_cvid, uint32_t*, "g_cvid", (m + 1) * 4);
-  G_WS(d_casm, uint32_t*, "g_casm", m * 4);
-  G_WS(d_clist, uint32_t*, "g_clist", m * 4);
-  G_WS(d_key, uint64_t*, "g_key", m * 8);
-  G_WS(d_seq, uint64_t*, "g_seq", m * 8);
-  G_WS(d_key2, uint64_t*, "g_key2", m * 8);
-  G_WS(d_seq2, uint64_t*, "g_seq2", m * 8);
-  G_WS(d_eh, uint64_t*, "g_eh", m * 8);
-  G_WS(d_es, uint64_t*, "g_es", (m + 1) * 8);
+  NTS_WS(d_cvid, uint32_t*, "g_cvid", (m + 1) * 4);
+  NTS_WS(d_casm, uint32_t*, "g_casm", m * 4);
+  NTS_WS(d_clist, uint32_t*, "g_clist", m * 4);
+  NTS_WS(d_key, uint64_t*, "g_key", m * 8);
+  NTS_WS(d_seq, uint64_t*, "g_seq", m * 8);
+  NTS_WS(d_key2, uint64_t*, "g_key2", m * 8);
+  NTS_WS(d_seq2, uint64_t*, "g_seq2", m * 8);
+  NTS_WS(d_eh, uint64_t*, "g_eh", m * 8);
+  NTS_WS(d_es, uint64_t*, "g_es", (m + 1) * 8);
   size_t tmp_sort2 = 0, tmp_scan2 = 0;
   HIP_TRY(ctx, rocprim::radix_sort_pairs(nullptr, tmp_sort2, d_key, d_key2, d_seq, d_seq2, m, 0, 64, ctx->stream));
   HIP_TRY(ctx, rocprim::exclusive_scan(nullptr, tmp_scan2, d_eh, d_es, (uint64_t)0, m, rocprim::plus<uint64_t>(), ctx->stream));
-  G_WS(d_tmp2, void*, "g_tmp2", std::max<size_t>(std::max(tmp_sort2, tmp_scan2), 16));
+  NTS_WS(d_tmp2, void*, "g_tmp2", std::max<size_t>(std::max(tmp_sort2, tmp_scan2), 16));
   const uint32_t mb = (uint32_t)((m + 255) / 256);
   {
     ScopedTimer t(ctx, "graph_build");
@@ -298,20 +295,20 @@ int graph_build_core(nts_ctx* ctx, uint32_t n_asm, uint64_t n, GraphDev* G, List
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   const uint64_t ne = last_scan + last_flag;
   G->ne = ne;
-  G_WS(d_eu, uint32_t*, "g_eu", std::max<uint64_t>(ne, 1) * 4);
-  G_WS(d_ev, uint32_t*, "g_ev", std::max<uint64_t>(ne, 1) * 4);
-  G_WS(d_ew, uint32_t*, "g_ew", std::max<uint64_t>(ne, 1) * 4);
-  G_WS(d_ef, uint64_t*, "g_ef", std::max<uint64_t>(ne, 1) * 8);
+  NTS_WS(d_eu, uint32_t*, "g_eu", std::max<uint64_t>(ne, 1) * 4);
+  NTS_WS(d_ev, uint32_t*, "g_ev", std::max<uint64_t>(ne, 1) * 4);
+  NTS_WS(d_ew, uint32_t*, "g_ew", std::max<uint64_t>(ne, 1) * 4);
+  NTS_WS(d_ef, uint64_t*, "g_ef", std::max<uint64_t>(ne, 1) * 8);
   if (ne) {
     // the unordered edge arrays reuse buffers the pair stage is done with; d_key/d_seq become sort keys again
-    G_WS(d_eu0, uint32_t*, "g_eu0", ne * 4);
-    G_WS(d_ev0, uint32_t*, "g_ev0", ne * 4);
-    G_WS(d_ew0, uint32_t*, "g_ew0", ne * 4);
-    G_WS(d_ef0, uint64_t*, "g_ef0", ne * 8);
-    G_WS(d_srank, unsigned long long*, "g_srank", nv * 8);
+    NTS_WS(d_eu0, uint32_t*, "g_eu0", ne * 4);
+    NTS_WS(d_ev0, uint32_t*, "g_ev0", ne * 4);
+    NTS_WS(d_ew0, uint32_t*, "g_ew0", ne * 4);
+    NTS_WS(d_ef0, uint64_t*, "g_ef0", ne * 8);
+    NTS_WS(d_srank, unsigned long long*, "g_srank", nv * 8);
     size_t tmp_sort3 = 0;
     HIP_TRY(ctx, rocprim::radix_sort_pairs(nullptr, tmp_sort3, d_key, d_key2, d_seq, d_seq2, ne, 0, 64, ctx->stream));
-    G_WS(d_tmp3, void*, "g_tmp3", std::max<size_t>(tmp_sort3, 16));
+    NTS_WS(d_tmp3, void*, "g_tmp3", std::max<size_t>(tmp_sort3, 16));
     const uint32_t eb = (uint32_t)((ne + 255) / 256);
     ScopedTimer t(ctx, "graph_build");
     NTS_LAUNCH(k_g_edges, dim3(mb), dim3(256), 0, ctx->stream, d_key2, d_seq2, d_eh, d_es, m, d_cvid, d_eu0, d_ev0, d_ew0, d_ef0);
@@ -330,7 +327,6 @@ int graph_build_core(nts_ctx* ctx, uint32_t n_asm, uint64_t n, GraphDev* G, List
   G->e_w = d_ew;
   G->e_first = d_ef;
   return NTS_OK;
-#undef G_WS
 }
 
 // scratch buffers of the concatenation, sized for n elements

@@ -467,7 +467,6 @@ struct nts_ctx
   size_t win_lds_set = 0;
   bool bin_lds_set = false;
   uint32_t n_cus = 0; // compute units of the device (asked once)
-  bool small_gap_path = true; // uncovered ranges: device-side sort + merge when they are few (nts_pruned.inc)
   bool sel_ctl_clean = false; // the pruned pass's control block was cleared by the previous call's last kernel
   int bf_build_mode = 0; // 0 auto (binned build for large genomes), 1 one atomic per k-mer, 2 binned whenever it applies
   int sketch_mode = 0;
@@ -482,14 +481,9 @@ struct nts_ctx
   uint32_t last_bf_fallback = 0; // 1: its late list ran full (store-only build fell back to read-and-OR / fused AND build was redone unfused)
   uint32_t last_bf_sparse_level = 0;     // the last nts_bf_insert_and went the literal way over a sparse running filter (bf_level_sparse)
   uint64_t last_bf_sparse_accepted = 0;  // and accepted this many k-mers
-  // dense sketch over a sparse filter: summary consulted before the filter, key tiles without an accepted k-mer skipped
-  const uint32_t* cur_summary = nullptr;
-  const uint32_t* cur_fold = nullptr; // folded copy of the filter for the LDS first look (k_hash_accept4), or null
   int fold_mode = 0;                  // 0 auto, 1 never (tests)
   bool acc4_lds_set = false;
   bool acc4r_lds_set = false;
-  uint32_t cur_summary_shift = 0;
-  uint32_t* cur_tile_any = nullptr;
   // pinned staging buffers + streams of the bulk transfers done by host threads (FASTA bytes up: nts_genome_from_fasta; filter
   // bits down: nts_bf_save), allocated on first use and kept: allocating pinned memory per call cost more than a small transfer
   struct IoLane
@@ -498,7 +492,6 @@ struct nts_ctx
     uint8_t* stage[2] = { nullptr, nullptr };
   };
   std::vector<IoLane> io_up, io_down;
-  const nts_bf* cur_rep = nullptr; // filter-out filter of the running nts_sketch_ex call (indexlr -r), or null
   double dense_seg_per_window = 3.0; // minimizers per w k-mers the every-k-mer path sizes its output segments for; raised by the call that needed more
                                      // (accepted k-mers in clusters: 4 % divergence at w = 48 gives 3.4), so that only that one call runs twice
   double fused_seg_per_window = 2.5; // the same for the window tiles that hash their own k-mers (per w + 1 k-mers)
@@ -625,6 +618,11 @@ void* ws_get(nts_ctx* ctx, const char* name, size_t bytes)
   b.first = p;
   return p;
 }
+
+// scratch buffer `ptr` from ws_get; the enclosing function returns NTS_ENOMEM when it cannot be had
+#define NTS_WS(ptr, type, name, bytes)                                                              \
+  type ptr = (type)ws_get(ctx, name, bytes);                                                        \
+  if (!ptr) return NTS_ENOMEM
 
 void ws_release(nts_ctx* ctx)
 {

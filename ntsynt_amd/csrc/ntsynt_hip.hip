@@ -1542,10 +1542,47 @@ int get_tables(nts_ctx* ctx, const nts_genome* g, uint32_t k, const nts_interval
   return NTS_OK;
 }
 
+// Tiered selection (nts_tiers.inc): thresholds tau_0 2^t, tau_0 = c0 / w of the hash range
+struct TierPlan
+{
+  float scale = 0;
+  uint32_t exp_shift = 23;
+  int32_t exp_bias = 126;
+  uint32_t n_tiers = 2, halo = 0, core = 0;
+  double c0 = 0;
+};
+
+// How one nts_sketch_ex call finds its minimizers.  plan_sketch decides; the sketch's host code follows the plan.
+//   Dense         every k-mer probed: the key array, or the window tiles that hash their own k-mers (run_dense_sorted)
+//   OneThreshold  the k-mers with h0 <= (c/w) 2^64 are listed and probed (k_hash_select / _hi); the windows without an accepted one,
+//                 the uncovered ranges, are evaluated apart (run_pruned)
+//   Tiers         the tiered selection: every window's minimizer is found, no uncovered ranges (run_pruned)
+//   AcceptList    a sparse filter's summary is in place: every k-mer is looked up, the accepted ones are listed (run_pruned)
+enum class SketchSel { Dense, OneThreshold, Tiers, AcceptList };
+
+struct SketchPlan
+{
+  SketchSel sel = SketchSel::Dense;
+  // candidates per window of the threshold (OneThreshold), or of the first tier rounded up (Tiers, and AcceptList where it replaced
+  // the tiers); 0 otherwise.  The call reports it (nts_sketch_stats).
+  uint32_t c = 0;
+  double p = 1.0; // accepted share of the candidates (1 when unknown: sizes the candidate arrays)
+  TierPlan tiers;
+  // a sparse filter's summary, consulted before the filter (AcceptList; Dense under sketch mode "dense": k_hash_keys_sparse, which marks
+  // the key tiles with an accepted k-mer in tile_any for the window pass over the whole genome)
+  const uint32_t* summary = nullptr;
+  uint32_t summary_shift = 0;
+  uint32_t* tile_any = nullptr;
+  const uint32_t* fold = nullptr;     // folded copy of the filter for the LDS first look (k_hash_accept4), or null
+  const nts_bf* filter_out = nullptr; // filter-out filter (indexlr -r), or null
+  bool few_ranges = true;             // uncovered ranges: device-side sort + merge when they are few (off for the call's second attempt)
+};
+
+// plan: given by the sketch's key pass (MODE_KEYS) alone: a summary in front of the probes, the filter-out filter
 template <int MODE>
 int launch_hash(nts_ctx* ctx, const char* name, const nts_genome* g, const GenomeTables& T, uint32_t k,
                 const nts_bf* bf_in, nts_bf* bf_out, uint64_t* keys, const uint32_t* d_tile_ids = nullptr, uint64_t n_tile_ids = 0,
-                const uint2* d_tile_span = nullptr, const MhSet& mh = MhSet{})
+                const uint2* d_tile_span = nullptr, const MhSet& mh = MhSet{}, const SketchPlan* plan = nullptr)
 {
   const RunTable& rt = T.rt;
   if (rt.n_valid == 0) return NTS_OK;
@@ -1561,17 +1598,16 @@ int launch_hash(nts_ctx* ctx, const char* name, const nts_genome* g, const Genom
   const uint64_t blocks = d_tile_ids ? n_tile_ids : (rt.n_valid + per_block - 1) / per_block;
   if (blocks > 0x7FFFFFFFULL) return fail(ctx, NTS_ERANGE, "genome too large for one launch");
   ScopedTimer t(ctx, name, true);
-  if (MODE == MODE_KEYS && bf_in && !d_tile_ids && ctx->cur_summary && ctx->cur_tile_any) {
+  if (MODE == MODE_KEYS && plan && bf_in && !d_tile_ids && plan->summary && plan->tile_any) {
     NTS_LAUNCH(k_hash_keys_sparse, dim3((uint32_t)blocks), dim3(HASH_THREADS), 0, ctx->stream, g->d_code + PAD, T.d_run_pos,
-                       T.d_run_vstart, T.n_runs, rt.n_valid, hp, bf_in->d_words, fm, ctx->cur_summary, ctx->cur_summary_shift, keys,
-                       ctx->cur_tile_any);
+                       T.d_run_vstart, T.n_runs, rt.n_valid, hp, bf_in->d_words, fm, plan->summary, plan->summary_shift, keys, plan->tile_any);
     HIP_TRY(ctx, hipGetLastError());
     return NTS_OK;
   }
+  const nts_bf* const rep = plan ? plan->filter_out : nullptr;
   NTS_LAUNCH(k_hash<MODE>, dim3((uint32_t)blocks), dim3(HASH_THREADS), 0, ctx->stream, g->d_code + PAD, T.d_run_pos,
                      T.d_run_vstart, T.n_runs, rt.n_valid, hp, bf_in ? bf_in->d_words : nullptr, bf_out ? bf_out->d_words : nullptr,
-                     fm, keys, d_tile_ids, d_tile_span, (MODE == MODE_KEYS && ctx->cur_rep) ? ctx->cur_rep->d_words : nullptr,
-                     make_fastmod((MODE == MODE_KEYS && ctx->cur_rep) ? ctx->cur_rep->bytes * 8 : 64), mh);
+                     fm, keys, d_tile_ids, d_tile_span, rep ? rep->d_words : nullptr, make_fastmod(rep ? rep->bytes * 8 : 64), mh);
   HIP_TRY(ctx, hipGetLastError());
   return NTS_OK;
 }
@@ -2739,7 +2775,7 @@ struct WinFuse // what k_window_min<true> hashes and probes with (launch_window_
   uint32_t* dir_cnt = nullptr;
 };
 
-int launch_window_dense(nts_ctx* ctx, const uint64_t* d_keys, const uint64_t* d_vs, const uint64_t* d_nv, const uint64_t* d_ts,
+int launch_window_dense(nts_ctx* ctx, const SketchPlan& plan, const uint64_t* d_keys, const uint64_t* d_vs, const uint64_t* d_nv, const uint64_t* d_ts,
                         uint32_t n_rec, uint64_t n_tiles, uint32_t w, const OutSegs& out, const char* tag,
                         const uint32_t* d_tile_ids = nullptr, uint64_t n_tile_ids = 0, const WinFuse* fuse = nullptr)
 {
@@ -2778,7 +2814,7 @@ int launch_window_dense(nts_ctx* ctx, const uint64_t* d_keys, const uint64_t* d_
   P.seg_cap = out.seg_cap;
   P.tile_cnt = out.d_tile_cnt;
   P.tile_cap = out.tile_cap;
-  P.tile_any = (d_tile_ids == nullptr && out.d_tile_cnt == nullptr && !fuse) ? ctx->cur_tile_any : nullptr;
+  P.tile_any = (d_tile_ids == nullptr && out.d_tile_cnt == nullptr && !fuse) ? plan.tile_any : nullptr;
   P.code = nullptr;
   P.run_pos = P.run_vstart = nullptr;
   P.n_runs = 0;
@@ -2916,7 +2952,7 @@ struct SortedOut
   uint64_t* d_key = nullptr; // their keys (h0)
   uint64_t count = 0;        // their number -- or an upper bound when d_ctl is set:
   // few uncovered ranges are merged in on the device; d_ctl[1] = number of minimizers, d_ctl[2] = 1 if that path
-  // gave up (the call is repeated with ctx->small_gap_path = false)
+  // gave up (the call is repeated with SketchPlan::few_ranges off)
   uint64_t* d_ctl = nullptr;
   // ... in which case d_j/d_key hold the first `na` of them (the sparse winners) and b_j/b_key the others (the winners of
   // the uncovered ranges, d_ctl[0] of them): k_finalize merges the two lists
@@ -2931,17 +2967,14 @@ struct SortedOut
 // and handed on as a second list next to it (k_gap_collect; k_finalize merges): `res` then has res.d_ctl and res.b_j set
 // and res.count is an upper bound, and no synchronisation happens here.
 int run_dense_sorted(nts_ctx* ctx, const nts_genome* g, const GenomeTables& T, uint32_t k, uint32_t w, const nts_bf* filter,
-                     const std::vector<uint64_t>* pseudo_vstart, const std::vector<uint64_t>* pseudo_nv, const std::vector<uint32_t>* tiles,
+                     const SketchPlan& plan, const std::vector<uint64_t>* pseudo_vstart, const std::vector<uint64_t>* pseudo_nv, const std::vector<uint32_t>* tiles,
                      uint64_t est_kmers, const char* slot_prefix, SortedOut& res, const SortedOut* sparse = nullptr,
                      const std::vector<uint32_t>* tile_spans = nullptr)
 {
   // tile_spans (with tiles): 2 words per listed tile, the first and last in-tile index inside an uncovered range
   const RunTable& rt = T.rt;
-#define DN_WS(ptr, type, name, bytes)                                                               \
-  type ptr = (type)ws_get(ctx, name, bytes);                                                        \
-  if (!ptr) return NTS_ENOMEM
   const std::string pre(slot_prefix);
-  DN_WS(d_seg, unsigned long long*, "seg_count", N_SEG * sizeof(unsigned long long));
+  NTS_WS(d_seg, unsigned long long*, "seg_count", N_SEG * sizeof(unsigned long long));
   int rc;
   uint32_t* d_tiles = nullptr;
   const uint2* d_spans = nullptr;
@@ -2984,7 +3017,7 @@ int run_dense_sorted(nts_ctx* ctx, const nts_genome* g, const GenomeTables& T, u
   // short windows over the whole genome: the window tiles hash and probe their own k-mers, no key array (k_window_min<true>)
   WinFuse fuse_args;
   const WinFuse* fuse = nullptr;
-  if (!pseudo_vstart && w < WIN_FUSE_W && k <= FAST_K_MAX && !ctx->cur_rep && !(ctx->cur_summary && ctx->cur_tile_any) &&
+  if (!pseudo_vstart && w < WIN_FUSE_W && k <= FAST_K_MAX && !plan.filter_out && !(plan.summary && plan.tile_any) &&
       !(NTS_KNOB("NTS_WIN_FUSE") && atoi(NTS_KNOB("NTS_WIN_FUSE")) == 0)) {
     fuse_args.code = g->d_code + PAD;
     fuse_args.run_pos = T.d_run_pos;
@@ -3000,7 +3033,7 @@ int run_dense_sorted(nts_ctx* ctx, const nts_genome* g, const GenomeTables& T, u
   if (!fuse) {
     d_keys = (uint64_t*)ws_get(ctx, d_tiles ? "gap_keys" : "keys", (d_tiles ? n_tile_ids * KEY_TILE : key_buffer_elems(rt.n_valid)) * 8);
     if (!d_keys) return NTS_ENOMEM;
-    if ((rc = launch_hash<MODE_KEYS>(ctx, filter ? "hash_probe" : "hash_only", g, T, k, filter, nullptr, d_keys, d_tiles, n_tile_ids, d_spans))) return rc;
+    if ((rc = launch_hash<MODE_KEYS>(ctx, filter ? "hash_probe" : "hash_only", g, T, k, filter, nullptr, d_keys, d_tiles, n_tile_ids, d_spans, MhSet{}, &plan))) return rc;
   }
   const char* win_tag = fuse ? (filter ? "hash_probe" : "hash_only") : "window_min"; // (the fused pass is timed as the hashing pass it replaces)
   OutSegs segs;
@@ -3010,17 +3043,17 @@ int run_dense_sorted(nts_ctx* ctx, const nts_genome* g, const GenomeTables& T, u
   // the window kernel writes every tile's winners in order to a slot of its own; one workgroup (k_gap_collect) strings
   // the tiles together, k_finalize merges them into the sparse winners; the count is read at the call's end
   const uint64_t expect_winners = 2 * est_kmers / std::max<uint32_t>(w, 1) + n_rec;
-  if (sparse && ctx->small_gap_path && n_tiles <= GAP_TILES_MAX && expect_winners <= GAP_LIST_CAP * 3 / 4) {
+  if (sparse && plan.few_ranges && n_tiles <= GAP_TILES_MAX && expect_winners <= GAP_LIST_CAP * 3 / 4) {
     OutSegs tl;
     tl.tile_cap = GAP_TILE_CAP;
     tl.d_j = (uint64_t*)ws_get(ctx, "gap_tile_j", n_tiles * GAP_TILE_CAP * 8);
     tl.d_key = (uint64_t*)ws_get(ctx, "gap_tile_key", n_tiles * GAP_TILE_CAP * 8);
     tl.d_tile_cnt = (uint32_t*)ws_get(ctx, "gap_tile_cnt", (n_tiles + 4) * 4);
-    DN_WS(d_gj, uint64_t*, "gap_sorted_j", GAP_LIST_CAP * 8);
-    DN_WS(d_gk, uint64_t*, "gap_sorted_key", GAP_LIST_CAP * 8);
-    DN_WS(d_gctl, uint64_t*, "gap_ctl", 4 * 8);
+    NTS_WS(d_gj, uint64_t*, "gap_sorted_j", GAP_LIST_CAP * 8);
+    NTS_WS(d_gk, uint64_t*, "gap_sorted_key", GAP_LIST_CAP * 8);
+    NTS_WS(d_gctl, uint64_t*, "gap_ctl", 4 * 8);
     if (!tl.d_j || !tl.d_key || !tl.d_tile_cnt) return NTS_ENOMEM;
-    if ((rc = launch_window_dense(ctx, d_keys, d_vs, d_nv, d_ts, n_rec, n_tiles, w, tl, win_tag, d_tiles, n_tile_ids, fuse))) return rc;
+    if ((rc = launch_window_dense(ctx, plan, d_keys, d_vs, d_nv, d_ts, n_rec, n_tiles, w, tl, win_tag, d_tiles, n_tile_ids, fuse))) return rc;
     {
       ScopedTimer t(ctx, "merge_lists");
       NTS_LAUNCH(k_gap_collect, dim3(1), dim3(GAP_COLLECT_THREADS), 0, ctx->stream, tl.d_tile_cnt, (uint32_t)n_tiles, tl.d_j, tl.d_key,
@@ -3063,7 +3096,7 @@ int run_dense_sorted(nts_ctx* ctx, const nts_genome* g, const GenomeTables& T, u
       HIP_TRY(ctx, hipMemsetAsync(d_ovf, 0, 8, ctx->stream));
       fuse_args.dir_off = d_doff;
       fuse_args.dir_cnt = d_dcnt;
-      if ((rc = launch_window_dense(ctx, nullptr, d_vs, d_nv, d_ts, n_rec, n_tiles, w, od, win_tag, nullptr, 0, fuse))) return rc;
+      if ((rc = launch_window_dense(ctx, plan, nullptr, d_vs, d_nv, d_ts, n_rec, n_tiles, w, od, win_tag, nullptr, 0, fuse))) return rc;
       {
         ScopedTimer t(ctx, "merge_lists");
         if (int rc_s = scan_counts<uint32_t>(ctx, d_dcnt, n_tiles, d_dscan)) return rc_s;
@@ -3103,7 +3136,7 @@ int run_dense_sorted(nts_ctx* ctx, const nts_genome* g, const GenomeTables& T, u
     if (!segs.d_j || !segs.d_key) return NTS_ENOMEM;
     HIP_TRY(ctx, hipMemsetAsync(segs.d_j, 0xFF, slots * 8, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(d_seg, 0, N_SEG * sizeof(unsigned long long), ctx->stream));
-    if ((rc = launch_window_dense(ctx, d_keys, d_vs, d_nv, d_ts, n_rec, n_tiles, w, segs, win_tag, d_tiles, n_tile_ids, fuse))) return rc;
+    if ((rc = launch_window_dense(ctx, plan, d_keys, d_vs, d_nv, d_ts, n_rec, n_tiles, w, segs, win_tag, d_tiles, n_tile_ids, fuse))) return rc;
     {
       Mail m(ctx);
       const uint32_t at = m.add(d_seg, N_SEG);
@@ -3125,15 +3158,15 @@ int run_dense_sorted(nts_ctx* ctx, const nts_genome* g, const GenomeTables& T, u
   res.count = count;
   if (count == 0) return NTS_OK;
   const uint64_t slots = segs.seg_cap * N_SEG;
-  DN_WS(d_oj2, uint64_t*, (pre + "out_j2").c_str(), slots * 8);
-  DN_WS(d_ok2, uint64_t*, (pre + "out_key2").c_str(), slots * 8);
+  NTS_WS(d_oj2, uint64_t*, (pre + "out_j2").c_str(), slots * 8);
+  NTS_WS(d_ok2, uint64_t*, (pre + "out_key2").c_str(), slots * 8);
   size_t tmp_bytes = 0;
   // compact indices are < n_valid: sort only the bits that can differ (sentinel slots are all ones)
   uint32_t bits = 1;
   while (bits < 64 && (rt.n_valid >> bits) != 0) ++bits;
   const uint32_t end_bit = std::min<uint32_t>(64, bits + 1);
   HIP_TRY(ctx, rocprim::radix_sort_pairs(nullptr, tmp_bytes, segs.d_j, d_oj2, segs.d_key, d_ok2, slots, 0, end_bit, ctx->stream));
-  DN_WS(d_tmp, void*, "sort_tmp", std::max<size_t>(tmp_bytes, 16));
+  NTS_WS(d_tmp, void*, "sort_tmp", std::max<size_t>(tmp_bytes, 16));
   {
     ScopedTimer t(ctx, "sort_minimizers");
     HIP_TRY(ctx, rocprim::radix_sort_pairs(d_tmp, tmp_bytes, segs.d_j, d_oj2, segs.d_key, d_ok2, slots, 0, end_bit, ctx->stream));
@@ -3141,7 +3174,6 @@ int run_dense_sorted(nts_ctx* ctx, const nts_genome* g, const GenomeTables& T, u
   res.d_j = d_oj2;
   res.d_key = d_ok2;
   return NTS_OK;
-#undef DN_WS
 }
 
 // 2-bit image of the genome for k_hash_select (built once per genome)
@@ -3197,9 +3229,23 @@ int bf_make_summary(nts_ctx* ctx, const nts_bf* filter, uint32_t shift)
   return NTS_OK;
 }
 
+// The genome, hash and filter fields of the sketch's parameter blocks (SelParams, AcceptParams, TierParams)
+template <class P>
+int genome_params(nts_ctx* ctx, const nts_genome* g, const GenomeTables& T, uint32_t k, const nts_bf* filter, P& out)
+{
+  out.code = g->d_code + PAD;
+  out.run_pos = T.d_run_pos;
+  out.run_vstart = T.d_run_vstart;
+  out.n_runs = T.n_runs;
+  out.n_valid = T.rt.n_valid;
+  out.bf = filter ? filter->d_words : nullptr;
+  out.fm = make_fastmod((filter ? filter->bytes : 8) * 8);
+  return hash_params_for(ctx, k, &out.hp);
+}
+
 // The kernel that looks every k-mer of g up in a sparse filter through its summary (and, where they pay, the two folded tables in
 // LDS) and lists the accepted ones per 8192-k-mer tile: tile t's list sits in segment t % N_SEG at tile_off[t], tile_cnt[t] entries
-// (j, h0) in index order.  Used by the sketch (run_pruned, accept_all) and by the cascade level over a sparse running filter
+// (j, h0) in index order.  Used by the sketch (run_pruned, AcceptList) and by the cascade level over a sparse running filter
 // (bf_level_sparse).
 int launch_accept(nts_ctx* ctx, const nts_genome* g, uint32_t k, const AcceptParams& A, const uint32_t* fold, uint64_t n_kt)
 {
@@ -3282,26 +3328,15 @@ int bf_level_sparse(nts_ctx* ctx, nts_bf* acc, const nts_genome* g, const Genome
   const double own = bits * (1.0 - std::exp(-(double)V / bits));
   const double p = own > 0 ? std::min(1.0, (double)pop_before / own) : 1.0;
   const uint64_t seg_cap = (uint64_t)((double)V * std::min(1.0, 1.5 * p + 1e-4) * 1.25 / N_SEG) + 8192;
-#define SL_WS(ptr, type, name, bytes)                                                               \
-  type ptr = (type)ws_get(ctx, name, bytes);                                                        \
-  if (!ptr) return NTS_ENOMEM
-  SL_WS(d_toff, uint64_t*, "spl_tile_off", n_kt * 8);
-  SL_WS(d_tcnt, uint32_t*, "spl_tile_cnt", n_kt * 4 + 8);
-  SL_WS(d_tord, uint8_t*, "spl_tile_ord", n_kt);
-  SL_WS(d_ctl, unsigned long long*, "spl_ctl", (N_SEG + 2) * 8); // [0..63] segment counters, [64] bits turned on
-  SL_WS(d_sj, uint64_t*, "spl_seg_j", seg_cap * N_SEG * 8);
-  SL_WS(d_sk, uint64_t*, "spl_seg_key", seg_cap * N_SEG * 8);
-#undef SL_WS
+  NTS_WS(d_toff, uint64_t*, "spl_tile_off", n_kt * 8);
+  NTS_WS(d_tcnt, uint32_t*, "spl_tile_cnt", n_kt * 4 + 8);
+  NTS_WS(d_tord, uint8_t*, "spl_tile_ord", n_kt);
+  NTS_WS(d_ctl, unsigned long long*, "spl_ctl", (N_SEG + 2) * 8); // [0..63] segment counters, [64] bits turned on
+  NTS_WS(d_sj, uint64_t*, "spl_seg_j", seg_cap * N_SEG * 8);
+  NTS_WS(d_sk, uint64_t*, "spl_seg_key", seg_cap * N_SEG * 8);
   HIP_TRY(ctx, hipMemsetAsync(d_ctl, 0, (N_SEG + 2) * 8, ctx->stream));
   AcceptParams A;
-  A.code = g->d_code + PAD;
-  A.run_pos = T.d_run_pos;
-  A.run_vstart = T.d_run_vstart;
-  A.n_runs = T.n_runs;
-  A.n_valid = V;
-  if (int rc_hp = hash_params_for(ctx, k, &A.hp)) return rc_hp;
-  A.bf = acc->d_words;
-  A.fm = make_fastmod(acc->bytes * 8);
+  if (int rc_gp = genome_params(ctx, g, T, k, acc, A)) return rc_gp;
   A.summary = acc->d_summary;
   A.shift = shift;
   A.probe_mask = ~0u;
@@ -3346,21 +3381,6 @@ int bf_level_sparse(nts_ctx* ctx, nts_bf* acc, const nts_genome* g, const Genome
   return 0;
 }
 
-// Pruned path; see nts_pruned.inc.  `res` gets every minimizer, ordered (sparse winners come out ordered by
-// construction; winners of uncovered ranges, if any, are sorted and merged in).
-// accept_all: the filter is sparse and its summary (ctx->cur_summary) is in place -- every k-mer is looked up, the accepted
-// ones are the candidates (k_hash_accept), windows without one have no minimizer: no uncovered ranges to evaluate
-// (tp: the tiered selection of nts_tiers.inc instead of one threshold -- its list holds every window's minimizer, like the
-//  accepted-list path's, so no range is left to the dense kernels)
-struct TierPlan
-{
-  float scale = 0;
-  uint32_t exp_shift = 23;
-  int32_t exp_bias = 126;
-  uint32_t n_tiers = 2, halo = 0, core = 0;
-  double c0 = 0;
-};
-
 void launch_tiers(nts_ctx* ctx, const TierParams& Q, uint64_t n_tiles)
 {
   const dim3 grid((uint32_t)n_tiles), block(TR_THREADS);
@@ -3382,14 +3402,46 @@ __global__ void k_gap_tiers_ctl(const uint64_t* __restrict__ blk_scan_last, cons
   ctl[2] = bad ? 1 : 0;
 }
 
+// TierParams' genome, hash and filter part; the callers add the tiles, the exclusion, the thresholds and the output segments
+int tier_params(nts_ctx* ctx, const nts_genome* g, const GenomeTables& T, uint32_t k, uint32_t w, const nts_bf* filter, TierParams& Q)
+{
+  Q.pack = g->d_pack;
+  Q.rec_vstart = T.d_rec_vstart;
+  Q.n_rec = g->n_rec;
+  Q.w = w;
+  return genome_params(ctx, g, T, k, filter, Q);
+}
+
+// SparseParams' candidate part: the candidates (pj, pk) compacted from n_tiles tile lists (tscan / tcnt: their scanned and own counts),
+// the staging areas, and the control block: ctl[N_SEG] counts the uncovered ranges, ctl[N_SEG + 1] says the candidates were cut short.
+// The callers add the records and where the uncovered ranges go.
+SparseParams sparse_params(const uint64_t* pj, const uint64_t* pk, const uint64_t* tscan, const uint32_t* tcnt, uint64_t n_tiles, uint64_t m_max,
+                           uint64_t n_valid, uint32_t w, uint64_t* stj, uint64_t* stk, uint64_t* bcnt, unsigned long long* ctl)
+{
+  SparseParams S;
+  S.pj = pj;
+  S.pk = pk;
+  S.m_scan_last = tscan + (n_tiles - 1);
+  S.m_cnt_last = tcnt + (n_tiles - 1);
+  S.m_max = m_max;
+  S.n_valid = n_valid;
+  S.w = w;
+  S.stage_j = stj;
+  S.stage_k = stk;
+  S.blk_cnt = bcnt;
+  S.gap_count = ctl + N_SEG;
+  S.overflow = ctl + N_SEG + 1;
+  return S;
+}
+
 // The uncovered ranges of the one-threshold selection through the tiered selection (nts_tiers.inc, gap mode) instead of a probe of
 // every k-mer in them: the ranges as tiles (position 0 = the range's first index, both ends closed; ranges longer than a tile cut into
 // tiles with halos), the thresholds going on from tau; the accepted k-mers found, in index order, are put to the window decision with
 // the ranges as records (k_sparse_win: a window lies inside its range), and the winners come back as the second list k_finalize
 // merges into the first -- what run_dense_sorted's few-ranges path hands back, in its format (ctl[0] winners, ctl[1] total, ctl[2] gave up).
 // Returns NTS_OK with res.d_ctl == nullptr when the path does not apply (the caller goes the dense way).
-int run_gap_tiers(nts_ctx* ctx, const nts_genome* g, const GenomeTables& T, uint32_t k, uint32_t w, const nts_bf* filter, uint64_t tau, uint32_t prune_c,
-                  const std::vector<uint64_t>& pv, const std::vector<uint64_t>& pn, uint64_t covered, const SortedOut& sparse, SortedOut& res)
+int run_gap_tiers(nts_ctx* ctx, const nts_genome* g, const GenomeTables& T, uint32_t k, uint32_t w, const nts_bf* filter, const SketchPlan& plan,
+                  uint64_t tau, const std::vector<uint64_t>& pv, const std::vector<uint64_t>& pn, uint64_t covered, const SortedOut& sparse, SortedOut& res)
 {
   res = SortedOut();
   if (!filter || k > FAST_K_MAX || w < 64 || w > 4097 || pv.empty() || ctx->gap_tiers_off) return NTS_OK;
@@ -3420,20 +3472,17 @@ int run_gap_tiers(nts_ctx* ctx, const nts_genome* g, const GenomeTables& T, uint
   }
   const uint64_t n_gt = tiles.size();
   if (n_gt > (1u << 20)) return NTS_OK;
-#define GT_WS(ptr, type, name, bytes)                                                               \
-  type ptr = (type)ws_get(ctx, name, bytes);                                                        \
-  if (!ptr) return NTS_ENOMEM
   void* dev[3];
   if (int rc = upload_packed(ctx, "gt_tables", { { tiles.data(), tiles.size() * sizeof(TierTile) }, { pv.data(), pv.size() * 8 }, { pn.data(), pn.size() * 8 } }, dev))
     return rc;
   const TierTile* d_tiles = (const TierTile*)dev[0];
   const uint64_t *d_vs = (const uint64_t*)dev[1], *d_nv = (const uint64_t*)dev[2];
-  GT_WS(d_dir, uint32_t*, "gt_dir", n_gt * 12);
-  GT_WS(d_toff, uint64_t*, "gt_tile_off", n_gt * 8);
-  GT_WS(d_tcnt, uint32_t*, "gt_tile_cnt", n_gt * 4 + 8);
-  GT_WS(d_tord, uint8_t*, "gt_tile_ord", n_gt);
-  GT_WS(d_tscan, uint64_t*, "gt_tile_scan", n_gt * 8);
-  GT_WS(d_ctl, unsigned long long*, "gt_ctl", (N_SEG + 4) * 8); // [0..63] segment counters, [64] ranges (unused), [65] overflow, [66..67] tier statistics
+  NTS_WS(d_dir, uint32_t*, "gt_dir", n_gt * 12);
+  NTS_WS(d_toff, uint64_t*, "gt_tile_off", n_gt * 8);
+  NTS_WS(d_tcnt, uint32_t*, "gt_tile_cnt", n_gt * 4 + 8);
+  NTS_WS(d_tord, uint8_t*, "gt_tile_ord", n_gt);
+  NTS_WS(d_tscan, uint64_t*, "gt_tile_scan", n_gt * 8);
+  NTS_WS(d_ctl, unsigned long long*, "gt_ctl", (N_SEG + 4) * 8); // [0..63] segment counters, [64] ranges (unused), [65] overflow, [66..67] tier statistics
   // the accepted k-mers of the ranges: a few per window at most where the filter accepts anything at all (the ranges are what the
   // other genomes do not share); a list that does not fit raises the flag and the call is repeated the dense way
   // Room per output segment: 5 % of the ranges' k-mers dealt out over the segments -- and never less than what the tiles of one
@@ -3444,35 +3493,24 @@ int run_gap_tiers(nts_ctx* ctx, const nts_genome* g, const GenomeTables& T, uint
   const uint64_t rich = std::min<uint64_t>(tiles_per_seg, 8) * (uint64_t)(core / 8 + 64);
   const uint64_t seg_cap = std::max<uint64_t>((uint64_t)((double)covered * 0.05 / N_SEG) + 2048, rich);
   const uint64_t m_max = seg_cap * N_SEG, n_blk = (m_max + SPARSE_BLOCK - 1) / SPARSE_BLOCK;
-  GT_WS(d_sj, uint64_t*, "gt_seg_j", m_max * 8);
-  GT_WS(d_sk, uint64_t*, "gt_seg_key", m_max * 8);
-  GT_WS(d_pj, uint64_t*, "gt_cand_j", m_max * 8);
-  GT_WS(d_pk, uint64_t*, "gt_cand_key", m_max * 8);
-  GT_WS(d_stj, uint64_t*, "gt_stage_j", n_blk * SPARSE_BLOCK * 8);
-  GT_WS(d_stk, uint64_t*, "gt_stage_k", n_blk * SPARSE_BLOCK * 8);
-  GT_WS(d_bcnt, uint64_t*, "gt_blk_cnt", n_blk * 8);
-  GT_WS(d_bscan, uint64_t*, "gt_blk_scan", n_blk * 8);
-  GT_WS(d_gj, uint64_t*, "gt_win_j", n_blk * SPARSE_BLOCK * 8);
-  GT_WS(d_gk, uint64_t*, "gt_win_key", n_blk * SPARSE_BLOCK * 8);
-  GT_WS(d_gctl, uint64_t*, "gap_ctl", 4 * 8);
+  NTS_WS(d_sj, uint64_t*, "gt_seg_j", m_max * 8);
+  NTS_WS(d_sk, uint64_t*, "gt_seg_key", m_max * 8);
+  NTS_WS(d_pj, uint64_t*, "gt_cand_j", m_max * 8);
+  NTS_WS(d_pk, uint64_t*, "gt_cand_key", m_max * 8);
+  NTS_WS(d_stj, uint64_t*, "gt_stage_j", n_blk * SPARSE_BLOCK * 8);
+  NTS_WS(d_stk, uint64_t*, "gt_stage_k", n_blk * SPARSE_BLOCK * 8);
+  NTS_WS(d_bcnt, uint64_t*, "gt_blk_cnt", n_blk * 8);
+  NTS_WS(d_bscan, uint64_t*, "gt_blk_scan", n_blk * 8);
+  NTS_WS(d_gj, uint64_t*, "gt_win_j", n_blk * SPARSE_BLOCK * 8);
+  NTS_WS(d_gk, uint64_t*, "gt_win_key", n_blk * SPARSE_BLOCK * 8);
+  NTS_WS(d_gctl, uint64_t*, "gap_ctl", 4 * 8);
   HIP_TRY(ctx, hipMemsetAsync(d_ctl, 0, (N_SEG + 4) * 8, ctx->stream));
   TierParams Q;
-  Q.code = g->d_code + PAD;
-  Q.pack = g->d_pack;
-  Q.run_pos = T.d_run_pos;
-  Q.run_vstart = T.d_run_vstart;
-  Q.n_runs = T.n_runs;
-  Q.n_valid = T.rt.n_valid;
-  Q.rec_vstart = T.d_rec_vstart;
-  Q.n_rec = g->n_rec;
+  if (int rc_q = tier_params(ctx, g, T, k, w, filter, Q)) return rc_q;
   Q.tiles = d_tiles;
   Q.excl_on = 1;
   Q.excl_hi = (uint32_t)(tau >> 32);
   Q.dir = d_dir;
-  if (int rc_hp = hash_params_for(ctx, k, &Q.hp)) return rc_hp;
-  Q.bf = filter->d_words;
-  Q.fm = make_fastmod(filter->bytes * 8);
-  Q.w = w;
   Q.halo = halo;
   Q.core = core;
   // tiers going on from tau: (tau, 2 tau], (2 tau, 4 tau], ... while the threshold stays below ~3/4 of all hashes; the last takes the rest
@@ -3480,7 +3518,7 @@ int run_gap_tiers(nts_ctx* ctx, const nts_genome* g, const GenomeTables& T, uint
   Q.exp_shift = 23;
   Q.exp_bias = 127;
   uint32_t n_exp = 1;
-  while (n_exp < TR_TIERS_MAX - 1 && (double)prune_c * (double)(2u << n_exp) <= 0.75 * (double)w) ++n_exp;
+  while (n_exp < TR_TIERS_MAX - 1 && (double)plan.c * (double)(2u << n_exp) <= 0.75 * (double)w) ++n_exp;
   Q.n_tiers = n_exp + 1;
   Q.seg_j = d_sj;
   Q.seg_key = d_sk;
@@ -3502,24 +3540,12 @@ int run_gap_tiers(nts_ctx* ctx, const nts_genome* g, const GenomeTables& T, uint
     if (int rc_s = scan_counts<uint32_t>(ctx, d_tcnt, n_gt, d_tscan)) return rc_s;
     NTS_LAUNCH(k_cand_compact, dim3((uint32_t)((n_gt + CC_TILES - 1) / CC_TILES)), dim3(256), 0, ctx->stream, d_sj, d_sk, seg_cap, d_toff, d_tcnt, d_tord,
                        d_tscan, n_gt, d_pj, d_pk, m_max, d_ctl + N_SEG + 1, false);
-    SparseParams S;
-    S.pj = d_pj;
-    S.pk = d_pk;
-    S.m_scan_last = d_tscan + (n_gt - 1);
-    S.m_cnt_last = d_tcnt + (n_gt - 1);
-    S.m_max = m_max;
+    SparseParams S = sparse_params(d_pj, d_pk, d_tscan, d_tcnt, n_gt, m_max, T.rt.n_valid, w, d_stj, d_stk, d_bcnt, d_ctl);
     S.rec_vstart = d_vs;
     S.rec_nv = d_nv;
-    S.n_valid = T.rt.n_valid;
     S.n_rec = (uint32_t)pv.size();
-    S.w = w;
-    S.stage_j = d_stj;
-    S.stage_k = d_stk;
-    S.blk_cnt = d_bcnt;
     S.gap_lo = S.gap_hi = nullptr;
-    S.gap_count = d_ctl + N_SEG;
     S.gap_cap = 0;
-    S.overflow = d_ctl + N_SEG + 1;
     S.rec_holes = 1;
     NTS_LAUNCH(k_sparse_win, dim3((uint32_t)n_blk), dim3(SPARSE_THREADS), 0, ctx->stream, S);
     if (int rc_s = scan_counts<uint64_t>(ctx, d_bcnt, n_blk, d_bscan)) return rc_s;
@@ -3535,14 +3561,24 @@ int run_gap_tiers(nts_ctx* ctx, const nts_genome* g, const GenomeTables& T, uint
   res.count = sparse.count + std::min<uint64_t>(m_max, covered); // (an upper bound: the real number comes with the call's last mail)
   res.d_ctl = d_gctl;
   return NTS_OK;
-#undef GT_WS
 }
 
-int run_pruned(nts_ctx* ctx, const nts_genome* g, const GenomeTables& T, uint32_t k, uint32_t w, const nts_bf* filter, uint32_t prune_c,
-               double p_accept, SortedOut& res, bool accept_all = false, const TierPlan* tp = nullptr)
+// Pruned path; see nts_pruned.inc.  `res` gets every minimizer, ordered (sparse winners come out ordered by
+// construction; winners of uncovered ranges, if any, are sorted and merged in).  plan.sel is one of
+//   OneThreshold  the k-mers under one threshold are the candidates; windows without an accepted one are evaluated apart
+//   AcceptList    the filter is sparse and its summary is in place: every k-mer is looked up, the accepted ones are the candidates
+//                 (k_hash_accept), windows without one have no minimizer: no uncovered ranges to evaluate
+//   Tiers         the tiered selection of nts_tiers.inc: its list holds every window's minimizer, like the accepted list's, so no range
+//                 is left to the dense kernels
+int run_pruned(nts_ctx* ctx, const nts_genome* g, const GenomeTables& T, uint32_t k, uint32_t w, const nts_bf* filter, const SketchPlan& plan,
+               SortedOut& res)
 {
   const RunTable& rt = T.rt;
   const uint64_t V = rt.n_valid;
+  const uint32_t prune_c = plan.c;
+  const bool tiers = plan.sel == SketchSel::Tiers, accept_list = plan.sel == SketchSel::AcceptList;
+  // (both lists hold every accepted k-mer that can win: a window without one has no minimizer)
+  const bool every_window = tiers || accept_list;
   // the upper-halves select kernel (k <= 32, threshold below half the hash range) works on wave tiles
   // (and a listing that fits one round of 4 per lane with room to spare: ~4096 c/w k-mers per tile; beyond that k_hash_select)
   // (and an assembly that is not in pieces: a tile that spans runs lists 64 k-mers per boundary and looks positions up
@@ -3552,10 +3588,10 @@ int run_pruned(nts_ctx* ctx, const nts_genome* g, const GenomeTables& T, uint32_
   // Margins measured at 3 Gbp, pairs at 2-8 % divergence: two per lane up to a mean of 107 (c = 22: select 1.79 ms against 2.00
   // with four per lane), four per lane up to 223 (c = 53: 4.32 ms against 4.79 for k_hash_select); NTS_HI_M2 / NTS_HI_M4 override)
   const double hi_m4 = NTS_KNOB("NTS_HI_M4") ? atof(NTS_KNOB("NTS_HI_M4")) : 1.15, hi_m2 = NTS_KNOB("NTS_HI_M2") ? atof(NTS_KNOB("NTS_HI_M2")) : 1.2;
-  const bool sel_hi = !accept_all && !tp && ctx->select_impl != 1 && k <= HI_K_MAX && 4096.0 * prune_c / w * hi_m4 <= 256.0 &&
+  const bool sel_hi = !every_window && ctx->select_impl != 1 && k <= HI_K_MAX && 4096.0 * prune_c / w * hi_m4 <= 256.0 &&
                       (ctx->select_impl == 2 || 2ull * T.n_runs <= (V + HIW_TILE - 1) / HIW_TILE + 64);
   const uint32_t hi_per = 4096.0 * prune_c / w * hi_m2 <= 128.0 ? 2u : 4u; // listed k-mers per lane and round
-  const uint64_t sel_tile = tp ? (uint64_t)tp->core : accept_all ? (uint64_t)KEY_TILE : sel_hi ? (uint64_t)HIW_TILE : (uint64_t)SEL_TILE;
+  const uint64_t sel_tile = tiers ? (uint64_t)plan.tiers.core : accept_list ? (uint64_t)KEY_TILE : sel_hi ? (uint64_t)HIW_TILE : (uint64_t)SEL_TILE;
   const uint64_t n_kt = (V + sel_tile - 1) / sel_tile; // tiles of the select kernel (16384 indices each; 8192 for k_hash_accept)
   if (n_kt > 0x7FFFFFFFULL) return fail(ctx, NTS_ERANGE, "genome too large for one launch");
   // threshold: a fraction c/w of all hashes
@@ -3564,24 +3600,20 @@ int run_pruned(nts_ctx* ctx, const nts_genome* g, const GenomeTables& T, uint32_
   // low 32 bits set: "h0 <= tau" is then a test of the high word alone (k_hash_select's rolling loop relies on it)
   uint64_t tau = t128 >= full - 1 ? KEY_MAX - 1 : ((uint64_t)t128 | 0xFFFFFFFFULL);
   if (tau == KEY_MAX) tau = KEY_MAX - 1;
-  const double frac = accept_all ? 1.0 : std::min(1.0, (double)prune_c / (double)w);
-  if (tp) accept_all = true; // (everything behind the selection is the accepted-list path's)
-#define PR_WS(ptr, type, name, bytes)                                                               \
-  type ptr = (type)ws_get(ctx, name, bytes);                                                        \
-  if (!ptr) return NTS_ENOMEM
-  PR_WS(d_toff, uint64_t*, "sel_tile_off", n_kt * 8);
-  PR_WS(d_tcnt, uint32_t*, "sel_tile_cnt", n_kt * 4 + 8);
-  PR_WS(d_tord, uint8_t*, "sel_tile_ord", n_kt);
-  PR_WS(d_tscan, uint64_t*, "sel_tile_scan", n_kt * 8);
+  const double frac = accept_list ? 1.0 : std::min(1.0, (double)prune_c / (double)w);
+  NTS_WS(d_toff, uint64_t*, "sel_tile_off", n_kt * 8);
+  NTS_WS(d_tcnt, uint32_t*, "sel_tile_cnt", n_kt * 4 + 8);
+  NTS_WS(d_tord, uint8_t*, "sel_tile_ord", n_kt);
+  NTS_WS(d_tscan, uint64_t*, "sel_tile_scan", n_kt * 8);
   // control block: [0..63] candidate segment counters, [64] uncovered-range counter, [65] "a tile list did not fit"
-  PR_WS(d_ctl, unsigned long long*, "sel_ctl", (N_SEG + 2) * 8);
+  NTS_WS(d_ctl, unsigned long long*, "sel_ctl", (N_SEG + 2) * 8);
   const uint64_t gap_cap = V / w + g->n_rec + 16;
-  PR_WS(d_glo, uint64_t*, "gap_lo", gap_cap * 8);
-  PR_WS(d_ghi, uint64_t*, "gap_hi", gap_cap * 8);
-  // room for the ACCEPTED candidates (share p_accept of the candidates, 1 if unknown); too little is seen and retried
-  uint64_t cseg_cap = (uint64_t)((double)V * frac * std::min(1.0, 1.5 * p_accept + (accept_all ? 1e-4 : 0.02)) * 1.25 / N_SEG) + 8192;
-  // tiers: the accepted k-mers found are ~p x (3.4/p probes per window) plus what conserved stretches add; a retry follows if it was too small
-  if (tp) cseg_cap = (uint64_t)((double)V * (std::max(6.0, 2.5 * ctx->tier_x0) / (double)w + 0.002) * 1.25 / N_SEG) + 8192;
+  NTS_WS(d_glo, uint64_t*, "gap_lo", gap_cap * 8);
+  NTS_WS(d_ghi, uint64_t*, "gap_hi", gap_cap * 8);
+  // room for the ACCEPTED candidates (share p of the candidates, 1 if unknown); too little is seen and retried
+  // (tiers: the accepted k-mers found are ~p x (3.4/p probes per window) plus what conserved stretches add)
+  uint64_t cseg_cap = tiers ? (uint64_t)((double)V * (std::max(6.0, 2.5 * ctx->tier_x0) / (double)w + 0.002) * 1.25 / N_SEG) + 8192
+                            : (uint64_t)((double)V * frac * std::min(1.0, 1.5 * plan.p + (accept_list ? 1e-4 : 0.02)) * 1.25 / N_SEG) + 8192;
   // the upper-halves kernel drops about 70 % of the accepted k-mers again (those that cannot win a window) -- where its tiles lie inside
   // one run; the window and gather kernels are launched over the capacity, so half of it is what they get until a call has
   // needed more (an assembly in pieces: the retry below, once per context)
@@ -3598,62 +3630,34 @@ int run_pruned(nts_ctx* ctx, const nts_genome* g, const GenomeTables& T, uint32_
     const uint64_t slot_words = sel_hi ? n_kt * 64ull * hi_per : 0ull;
     d_sj = (uint64_t*)ws_get(ctx, "sel_seg_j", (slot_words + m_max) * 8);
     d_sk = (uint64_t*)ws_get(ctx, "sel_seg_key", (slot_words + m_max) * 8);
-    PR_WS(d_pj, uint64_t*, "cand_j", m_max * 8);
-    PR_WS(d_pk, uint64_t*, "cand_key", m_max * 8);
-    PR_WS(d_stj, uint64_t*, "stage_j", n_blk * SPARSE_BLOCK * 8);
-    PR_WS(d_stk, uint64_t*, "stage_k", n_blk * SPARSE_BLOCK * 8);
-    PR_WS(d_bcnt, uint64_t*, "blk_cnt", n_blk * 8);
-    PR_WS(d_bscan, uint64_t*, "blk_scan", n_blk * 8);
+    NTS_WS(d_pj, uint64_t*, "cand_j", m_max * 8);
+    NTS_WS(d_pk, uint64_t*, "cand_key", m_max * 8);
+    NTS_WS(d_stj, uint64_t*, "stage_j", n_blk * SPARSE_BLOCK * 8);
+    NTS_WS(d_stk, uint64_t*, "stage_k", n_blk * SPARSE_BLOCK * 8);
+    NTS_WS(d_bcnt, uint64_t*, "blk_cnt", n_blk * 8);
+    NTS_WS(d_bscan, uint64_t*, "blk_scan", n_blk * 8);
     if (!d_sj || !d_sk) return NTS_ENOMEM;
     if (!ctx->sel_ctl_clean) HIP_TRY(ctx, hipMemsetAsync(d_ctl, 0, (N_SEG + 2) * 8, ctx->stream)); // (else: cleared by the previous call's last kernel)
     ctx->sel_ctl_clean = false;
-    SelParams S;
-    S.code = g->d_code + PAD;
-    if (!accept_all || tp) {
+    if (!accept_list) {
       if (int rc_pk = ensure_pack(ctx, g)) return rc_pk;
     }
-    S.pack = g->d_pack;
-    S.run_pos = T.d_run_pos;
-    S.run_vstart = T.d_run_vstart;
-    S.n_runs = T.n_runs;
-    S.n_valid = V;
-    if (int rc_hp = hash_params_for(ctx, k, &S.hp)) return rc_hp;
-    S.bf = filter ? filter->d_words : nullptr;
-    S.fm = make_fastmod((filter ? filter->bytes : 8) * 8);
-    S.tau = tau;
-    S.seg_j = d_sj;
-    S.seg_key = d_sk;
-    S.seg_cap = cseg_cap;
-    S.seg_count = d_ctl;
-    S.tile_off = d_toff;
-    S.tile_cnt = d_tcnt;
-    S.tile_ordered = d_tord;
-    // k_hash_select_hi drops accepted k-mers that cannot be a window's minimum (NTS_SELECT_ELIM=0: keeps them all; same result)
-    S.w_elim = (NTS_KNOB("NTS_SELECT_ELIM") && atoi(NTS_KNOB("NTS_SELECT_ELIM")) == 0) ? 0u : w;
-    if (tp) {
-      PR_WS(d_dir, uint32_t*, "tier_dir", n_kt * 12);
-      PR_WS(d_tstats, unsigned long long*, "tier_stats", 16);
-      HIP_TRY(ctx, hipMemsetAsync(d_tstats, 0, 16, ctx->stream));
+    if (tiers) {
+      const TierPlan& tp = plan.tiers;
       TierParams Q;
-      Q.code = S.code;
-      Q.pack = S.pack;
-      Q.run_pos = S.run_pos;
-      Q.run_vstart = S.run_vstart;
-      Q.n_runs = S.n_runs;
-      Q.n_valid = V;
-      Q.rec_vstart = T.d_rec_vstart;
-      Q.n_rec = g->n_rec;
+      if (int rc_q = tier_params(ctx, g, T, k, w, filter, Q)) return rc_q;
+      NTS_WS(d_dir, uint32_t*, "tier_dir", n_kt * 12);
+      NTS_WS(d_tstats, unsigned long long*, "tier_stats", 16);
+      HIP_TRY(ctx, hipMemsetAsync(d_tstats, 0, 16, ctx->stream));
+      Q.tiles = nullptr;
+      Q.excl_on = Q.excl_hi = 0;
       Q.dir = d_dir;
-      Q.hp = S.hp;
-      Q.bf = S.bf;
-      Q.fm = S.fm;
-      Q.w = w;
-      Q.halo = tp->halo;
-      Q.core = tp->core;
-      Q.scale = tp->scale;
-      Q.exp_shift = tp->exp_shift;
-      Q.exp_bias = tp->exp_bias;
-      Q.n_tiers = tp->n_tiers;
+      Q.halo = tp.halo;
+      Q.core = tp.core;
+      Q.scale = tp.scale;
+      Q.exp_shift = tp.exp_shift;
+      Q.exp_bias = tp.exp_bias;
+      Q.n_tiers = tp.n_tiers;
       Q.seg_j = d_sj;
       Q.seg_key = d_sk;
       Q.seg_cap = cseg_cap;
@@ -3663,24 +3667,15 @@ int run_pruned(nts_ctx* ctx, const nts_genome* g, const GenomeTables& T, uint32_
       Q.tile_ordered = d_tord;
       Q.stats = d_tstats;
       Q.exp_stop = NTS_KNOB("NTS_TR_STOP") ? (uint32_t)atoi(NTS_KNOB("NTS_TR_STOP")) : 0u;
-      Q.tiles = nullptr;
-      Q.excl_on = Q.excl_hi = 0;
       ScopedTimer t(ctx, "hash_tiers", true);
       NTS_LAUNCH(k_tier_dir, dim3((uint32_t)((n_kt + 255) / 256)), dim3(256), 0, ctx->stream, T.d_run_vstart, T.n_runs, T.d_rec_vstart, g->n_rec, V,
-                         tp->halo, tp->core, n_kt, (const TierTile*)nullptr, d_dir);
+                         tp.halo, tp.core, n_kt, (const TierTile*)nullptr, d_dir);
       launch_tiers(ctx, Q, n_kt);
-    } else if (accept_all) {
+    } else if (accept_list) {
       AcceptParams A;
-      A.code = S.code;
-      A.run_pos = S.run_pos;
-      A.run_vstart = S.run_vstart;
-      A.n_runs = S.n_runs;
-      A.n_valid = V;
-      A.hp = S.hp;
-      A.bf = S.bf;
-      A.fm = S.fm;
-      A.summary = ctx->cur_summary;
-      A.shift = ctx->cur_summary_shift;
+      if (int rc_gp = genome_params(ctx, g, T, k, filter, A)) return rc_gp;
+      A.summary = plan.summary;
+      A.shift = plan.summary_shift;
       A.probe_mask = ~0u;
 #ifdef NTS_EXPERIMENTS
       if (NTS_KNOB("NTS_ACC_NO_LOOKUP") && atoi(NTS_KNOB("NTS_ACC_NO_LOOKUP"))) { // a measurement switch that changes the RESULT: never silently, never in the product build
@@ -3697,8 +3692,21 @@ int run_pruned(nts_ctx* ctx, const nts_genome* g, const GenomeTables& T, uint32_
       A.tile_cnt = d_tcnt;
       A.tile_ordered = d_tord;
       ScopedTimer t(ctx, "hash_accept", true);
-      if (int rc_a = launch_accept(ctx, g, k, A, ctx->cur_fold, n_kt)) return rc_a;
+      if (int rc_a = launch_accept(ctx, g, k, A, plan.fold, n_kt)) return rc_a;
     } else {
+      SelParams S;
+      if (int rc_gp = genome_params(ctx, g, T, k, filter, S)) return rc_gp;
+      S.pack = g->d_pack;
+      S.tau = tau;
+      S.seg_j = d_sj;
+      S.seg_key = d_sk;
+      S.seg_cap = cseg_cap;
+      S.seg_count = d_ctl;
+      S.tile_off = d_toff;
+      S.tile_cnt = d_tcnt;
+      S.tile_ordered = d_tord;
+      // k_hash_select_hi drops accepted k-mers that cannot be a window's minimum (NTS_SELECT_ELIM=0: keeps them all; same result)
+      S.w_elim = (NTS_KNOB("NTS_SELECT_ELIM") && atoi(NTS_KNOB("NTS_SELECT_ELIM")) == 0) ? 0u : w;
       const bool chained = g_live_contexts.load() > 1 && ctx->device < 32 && !(NTS_KNOB("NTS_SELECT_CHAIN") && atoi(NTS_KNOB("NTS_SELECT_CHAIN")) == 0);
       std::unique_lock<std::mutex> chain_lock(nts_chain::mu, std::defer_lock);
       if (chained) {
@@ -3758,26 +3766,14 @@ int run_pruned(nts_ctx* ctx, const nts_genome* g, const GenomeTables& T, uint32_
         NTS_LAUNCH(k_cand_compact, dim3((uint32_t)((n_kt + CC_TILES - 1) / CC_TILES)), dim3(256), 0, ctx->stream, d_sj, d_sk, cseg_cap, d_toff, d_tcnt, d_tord, d_tscan, n_kt,
                            d_pj, d_pk, m_max, d_ctl + N_SEG + 1, false);
     }
-    SparseParams Q;
-    Q.pj = d_pj;
-    Q.pk = d_pk;
-    Q.m_scan_last = d_tscan + (n_kt - 1);
-    Q.m_cnt_last = d_tcnt + (n_kt - 1);
-    Q.m_max = m_max;
+    SparseParams Q = sparse_params(d_pj, d_pk, d_tscan, d_tcnt, n_kt, m_max, V, w, d_stj, d_stk, d_bcnt, d_ctl);
     Q.rec_vstart = T.d_rec_vstart;
     Q.rec_nv = T.d_rec_nv;
-    Q.n_valid = V;
     Q.n_rec = g->n_rec;
-    Q.w = w;
-    Q.stage_j = d_stj;
-    Q.stage_k = d_stk;
-    Q.blk_cnt = d_bcnt;
     Q.gap_lo = d_glo;
     Q.gap_hi = d_ghi;
-    Q.gap_count = d_ctl + N_SEG;
     Q.gap_cap = gap_cap;
-    Q.overflow = d_ctl + N_SEG + 1;
-    Q.no_gaps = accept_all ? 1u : 0u; // (the list holds every accepted k-mer that can win: a window without one has no minimizer)
+    Q.no_gaps = every_window ? 1u : 0u;
     {
       ScopedTimer t(ctx, "sparse_win");
       NTS_LAUNCH(k_sparse_win, dim3((uint32_t)n_blk), dim3(SPARSE_THREADS), 0, ctx->stream, Q);
@@ -3798,7 +3794,7 @@ int run_pruned(nts_ctx* ctx, const nts_genome* g, const GenomeTables& T, uint32_
       const uint32_t a_tcnt = mb.add((const uint64_t*)(d_tcnt + ((n_kt - 1) & ~1ull)), 1); // (32-bit counts: the pair holding the last one)
       const uint32_t a_lo = mb.add(d_glo, peek, d_ctl + N_SEG); // (the first n_gap of them: the count travels in the same mail)
       const uint32_t a_hi = mb.add(d_ghi, peek, d_ctl + N_SEG);
-      const uint32_t a_tier = tp ? mb.add((const uint64_t*)ws_get(ctx, "tier_stats", 16), 2) : 0u;
+      const uint32_t a_tier = tiers ? mb.add((const uint64_t*)ws_get(ctx, "tier_stats", 16), 2) : 0u;
       // the gather runs behind the mail kernel: the counters are on their way to the host while it works
       int rc_m = mb.launch(ctx);
       if (rc_m) return rc_m;
@@ -3814,7 +3810,7 @@ int run_pruned(nts_ctx* ctx, const nts_genome* g, const GenomeTables& T, uint32_
       listed = ctx->mail[a_tscan] + (uint32_t)(ctx->mail[a_tcnt] >> (32 * ((n_kt - 1) & 1ull)));
       memcpy(glo.data(), ctx->mail + a_lo, (size_t)peek * 8);
       memcpy(ghi.data(), ctx->mail + a_hi, (size_t)peek * 8);
-      if (tp) {
+      if (tiers) {
         ctx->last_tier_probes = ctx->mail[a_tier];
         ctx->last_tier_rounds = ctx->mail[a_tier + 1];
       }
@@ -3832,14 +3828,14 @@ int run_pruned(nts_ctx* ctx, const nts_genome* g, const GenomeTables& T, uint32_
       m = listed;
       if (listed > m_max) worst = std::max<uint64_t>(worst, listed / N_SEG + 1); // the compacted array was cut short
     }
-    if (NTS_KNOB("NTS_DEBUG_RETRY")) fprintf(stderr, "[select] attempt %d: worst segment %llu of %llu, listed %llu, tiers %d\n", attempt, (unsigned long long)worst, (unsigned long long)cseg_cap, (unsigned long long)m, tp ? 1 : 0);
+    if (NTS_KNOB("NTS_DEBUG_RETRY")) fprintf(stderr, "[select] attempt %d: worst segment %llu of %llu, listed %llu, tiers %d\n", attempt, (unsigned long long)worst, (unsigned long long)cseg_cap, (unsigned long long)m, tiers ? 1 : 0);
     if (worst <= cseg_cap) break;
     if (elim_on) ctx->elim_needs_full_cap = true;
     if (attempt == 1) return fail(ctx, NTS_EHIP, "candidate segments overflowed twice");
     cseg_cap = worst + 1024; // candidate lists were truncated: everything downstream of them is void; run again
   }
   ctx->last_candidates = m;
-  if (accept_all) n_gap = 0; // every accepted k-mer is a candidate: a window without candidates has no minimizer
+  if (every_window) n_gap = 0; // every accepted k-mer is a candidate: a window without candidates has no minimizer
   ctx->last_gaps = n_gap;
   res.d_j = d_sj;
   res.d_key = d_sk;
@@ -3883,15 +3879,15 @@ int run_pruned(nts_ctx* ctx, const nts_genome* g, const GenomeTables& T, uint32_
   sparse_list.d_j = d_sj;
   sparse_list.d_key = d_sk;
   sparse_list.count = n_sparse;
-  if (ctx->small_gap_path) { // the ranges through the tiered selection; not applicable, or a retry after it gave up: the dense kernels
-    int rc_g = run_gap_tiers(ctx, g, T, k, w, filter, tau, prune_c, pv, pn, covered, sparse_list, dense);
+  if (plan.few_ranges) { // the ranges through the tiered selection; not applicable, or a retry after it gave up: the dense kernels
+    int rc_g = run_gap_tiers(ctx, g, T, k, w, filter, plan, tau, pv, pn, covered, sparse_list, dense);
     if (rc_g) return rc_g;
     if (dense.d_ctl) {
       res = dense;
       return NTS_OK;
     }
   }
-  int rc = run_dense_sorted(ctx, g, T, k, w, filter, &pv, &pn, &tiles, covered, "gap_", dense, &sparse_list, &spans);
+  int rc = run_dense_sorted(ctx, g, T, k, w, filter, plan, &pv, &pn, &tiles, covered, "gap_", dense, &sparse_list, &spans);
   if (rc) return rc;
   if (dense.d_ctl) { // merged on the device: the caller reads the count after its own synchronisation
     res = dense;
@@ -3899,8 +3895,8 @@ int run_pruned(nts_ctx* ctx, const nts_genome* g, const GenomeTables& T, uint32_
   }
   if (dense.count == 0) return NTS_OK;
   const uint64_t total = n_sparse + dense.count;
-  PR_WS(d_mj, uint64_t*, "merged_j", total * 8);
-  PR_WS(d_mk, uint64_t*, "merged_key", total * 8);
+  NTS_WS(d_mj, uint64_t*, "merged_j", total * 8);
+  NTS_WS(d_mk, uint64_t*, "merged_key", total * 8);
   {
     ScopedTimer t(ctx, "merge_lists");
     NTS_LAUNCH(k_merge_lists, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, ctx->stream, d_sj, d_sk, n_sparse, dense.d_j, dense.d_key,
@@ -3911,9 +3907,163 @@ int run_pruned(nts_ctx* ctx, const nts_genome* g, const GenomeTables& T, uint32_
   res.d_key = d_mk;
   res.count = total;
   return NTS_OK;
-#undef PR_WS
 }
 
+// The sketch's one decision: which selection runs, with which c, p and tiers, and which views of the filter the kernels consult.
+// Reads the filter's popcount and builds its summary (under the filter's lock); launches nothing else.
+int plan_sketch(nts_ctx* ctx, const nts_genome* g, const GenomeTables& T, uint32_t k, uint32_t w, const nts_bf* filter, const nts_bf* filter_out,
+                SketchPlan& plan)
+{
+  const RunTable& rt = T.rt;
+  plan = SketchPlan();
+  plan.filter_out = filter_out;
+  // Pruning policy.  p = share of this genome's k-mers the filter accepts, estimated from occupancies: the
+  // genome alone would set about bits*(1-exp(-V/bits)) bits, the common filter kept popcount of them.  A window
+  // of w k-mers holds ~c*p accepted candidates when hashes <= (c/w)*2^64 are kept; c*p = 12 leaves ~6e-6 of the
+  // windows uncovered (they are re-evaluated densely).  The select kernel probes its candidates in batches and keeps
+  // only the accepted ones, so c may grow until a quarter of the k-mers are candidates (p down to 48/w); below that
+  // the dense kernels take over.
+  // (one threshold from w = 200; below it the tiers, with or without a filter -- without one, ntSynt --no-common, every listed k-mer is accepted and
+  //  the rounds only decide which k-mers are hashed in full: 3 Gbp at w = 10 / 33 / 63 / 90 / 150 / 200: 35 / 14 / 10 / 8 / 6.5 / 6.1 ms, against 64 / 57 /
+  //  49 ms through the window tiles and 23 / 8.5 / 7.0 with one threshold; scripts/mode_sweep.py)
+  const uint32_t prune_min_w = 200u;
+  bool pruned = ctx->sketch_mode == 2 || (ctx->sketch_mode == 0 && w >= prune_min_w);
+  // a filter-out filter (indexlr -r: experimental in the reference) is served by the every-k-mer-probed kernels only
+  if (filter_out) pruned = false;
+  uint32_t prune_c = ctx->prune_c;
+  bool tiered = false;
+  // (tiers forced: wherever the kernel applies.  Windows of 64 .. 199 k-mers, where one threshold never paid and every k-mer was probed:
+  //  the tiered selection is looked at there too -- a whole 3 Gbp genome at w = 100 against its family's filter: 90 ms the dense way)
+  const bool tiers_forced = ctx->tier_mode == 2 && ctx->sketch_mode == 0 && !filter_out && prune_c == 0;
+  // (windows below WIN_FUSE_W = 64, round 6: the same selection down to w = 8 where its estimated cost stays below tier_small_c of the every-k-mer pass)
+  const uint32_t tier_min_w = NTS_KNOB("NTS_TIER_MIN_W") ? (uint32_t)atoi(NTS_KNOB("NTS_TIER_MIN_W")) : 8u;
+  const double tier_small_c = NTS_KNOB("NTS_TIER_SMALL_C") ? atof(NTS_KNOB("NTS_TIER_SMALL_C")) : 0.85;
+  // (without a filter -- ntSynt --no-common -- below the window where one threshold takes over: every listed k-mer is accepted, the tiers only
+  //  decide which k-mers are hashed in full at all)
+  const bool tiers_small_w = ctx->tier_mode == 0 && ctx->sketch_mode == 0 && !filter_out && prune_c == 0 && w >= tier_min_w && w < 200;
+  if ((pruned || tiers_forced || tiers_small_w) && prune_c == 0) {
+    if (filter) {
+      uint64_t pc = 0;
+      if (int rc = nts_bf_popcount(ctx, filter, &pc)) return rc;
+      const double bits = (double)filter->bytes * 8.0;
+      auto share = [&](double kmers) { // of a genome with that many (distinct) k-mers
+        const double own = bits * (1.0 - std::exp(-kmers / bits));
+        return own > 0 ? std::min(1.0, (double)pc / own) : 1.0;
+      };
+      if (g->part_bases.size() > 1 && g->total_bases) {
+        // a batch: every part is a genome of its own as far as the filter is concerned (the parts of a batch are
+        // assemblies of one family: their k-mers are largely the same ones, not three times as many)
+        double acc = 0;
+        for (uint64_t b : g->part_bases) {
+          const double f = (double)b / (double)g->total_bases;
+          acc += f * share((double)rt.n_valid * f);
+        }
+        plan.p = acc;
+      } else {
+        plan.p = share((double)rt.n_valid);
+      }
+    }
+    // c*p = 11 accepted candidates per window on average (`cp` below; 10.5 until round 3).  (More would not empty the list of uncovered ranges:
+    // beyond the ~V*(cp/w)*exp(-cp) chance ones there are the stretches the other genomes do not share at all.
+    // Measured at 3 x 3 Gbp, w = 1000, p = 0.70, with k_hash_select_hi and the uncovered ranges probed only where a window
+    // reads them: c = 12 / 13 / 14 / 15 / 16 -> 1021 / 1085 / 1124 / 1134 / 1124 Gbases/s; with k_hash_select, whose rolling
+    // cost twice as much per k-mer, and whole key tiles probed around every range, the optimum was c = 18, cp = 12.)
+    // (round 3, with the select kernel dropping hopeless candidates and a family with insertions: c = 13 .. 17 ->
+    //  1280 / 1397 / 1420 / 1476 / 1413 Gbases/s; c = 16 at p = 0.70.  Round 5, same family: c = 12 .. 17 -> 1118 / 1250 / 1432 / 1468 /
+    //  1522 / 1516.)  An assembly in thousands of pieces (more than one run of valid bases per 2^20 k-mers) has its uncovered
+    //  ranges whatever c is -- scaffold ends, gaps, repeats -- and a listing cost that rises faster with c (tiles that list more than
+    //  their slots hold): the assembly-like family at 3 x 3 Gbp, p = 0.55: c = 14 / 16 / 18 / 21 -> 986 / 1134 / 1121 / 1070 Gbases/s; with the uncovered
+    //  ranges through the tiered selection (run_gap_tiers): c = 12 / 14 / 16 / 18 -> 933 / 1193 / 1291 / 1250.
+    const bool in_pieces = (uint64_t)T.n_runs > (rt.n_valid >> 20) + 64;
+    const double cp = in_pieces ? 8.7 : 11.0;
+    const double want = std::max(8.0, std::ceil(cp / std::max(plan.p, 1e-4)));
+    // (measured: at a quarter of the k-mers as candidates the pruned pass is still twice as fast as the dense one;
+    // at 40 % single lanes run out of slots in most tiles and it is half as fast)
+    // (with short windows the accepted candidates per lane of k_hash_select get dense sooner: measured at w = 250,
+    // 3 x 100 Mbp: c = 35 -> 56 Gbases/s against 34 dense, c = 50 -> 17; at w = 1000, c = 203 still gives 94)
+    const double cap = (w >= 512 ? 0.25 : 0.15) * (double)w;
+    prune_c = (uint32_t)std::min(want, cap);
+    if ((ctx->sketch_mode == 0 && want > cap) || w < prune_min_w) pruned = ctx->sketch_mode == 2;
+    // Tiered selection (nts_tiers.inc): thresholds tau_0 2^t instead of one threshold, each probed only where a window is still
+    // without an accepted k-mer -- ~3.4/p probes per window instead of 11/p.  It takes over where one threshold lists so many
+    // k-mers that the upper-halves kernel no longer applies, down to accepted shares where even the first tier is half of all k-mers.
+    if (!filter_out && ctx->sketch_mode == 0 && ctx->tier_mode != 1 && k <= FAST_K_MAX && w >= tier_min_w && w <= 4097) {
+      // (first tier: 2.4 accepted k-mers per window on average; 1.2 below w = 64, where every tier is a large share of the k-mers and a
+      //  thinner first one saves 8-12 % of the probes: scripts/tiers_x0_sweep.py)
+      const double x0 = ctx->tier_x0 > 0 ? ctx->tier_x0 : (w < WIN_FUSE_W ? 1.2 : 2.4);
+      const double c0 = x0 / std::max(plan.p, 1e-6);
+      const double switch_c = 54.0 * (double)w / 1000.0; // (beyond it k_hash_select takes over from k_hash_select_hi)
+      // Below w = 200 the other way probes every k-mer (k_window_min<true> under 64: ~85 ms per 3 Gbp at k = 24, 105 at k = 100; the key array
+      // above: 110-120).  The tiers cost ~91 ms per (probe per k-mer) at k = 24 and more with k -- a listed k-mer is hashed from scratch,
+      // ceil(k / 4) table reads: 290 ms at k = 100 -- and where w <= k they probe every k-mer of the stretch a substitution empties.  Probes
+      // per k-mer, fitted to scripts/tiers_small_w.py, tiers_x0_sweep.py and the k = 16 / 100 runs: 0.9 (1 - p) min(1, (k/w)^2) + 2.5 / (p w).
+      bool pays = true;
+      if (w < 200 && ctx->tier_mode != 2) {
+        const double kw = std::min(1.0, (double)k / (double)w);
+        const double est = std::min(1.0, 0.9 * (1.0 - plan.p) * kw * kw + 2.5 / std::max(plan.p * (double)w, 1e-9));
+        const double per_probe = 0.3 + 0.7 * (double)k / 24.0;
+        pays = per_probe * est <= tier_small_c * (1.0 + 0.002 * ((double)k - 24.0));
+      }
+      const double c0_max = 0.5 * (double)w;
+      const bool fits = w >= WIN_FUSE_W || 48.0 * 7.5 * (double)rt.n_valid / (double)w <= 120e9;
+      // (an assembly in pieces lists fewer candidates per window -- cp = 8.7 -- but that says nothing about where the tiers overtake the one
+      //  threshold: the comparison is made with the whole-genome figure; 200,000 contigs at w = 250, p = 0.7: tiers 7.4 ms, one threshold 10.4)
+      const double want_whole = std::max(8.0, std::ceil(11.0 / std::max(plan.p, 1e-4)));
+      if (c0 <= c0_max && fits && pays && (ctx->tier_mode == 2 || want_whole > switch_c)) {
+        tiered = true;
+        pruned = false;
+        plan.tiers.c0 = c0;
+        const double t0 = std::max(1.0, std::floor(c0 / (double)w * 4294967296.0));
+        plan.tiers.scale = (float)(1.0 / (t0 + 1.0));
+        plan.tiers.exp_shift = ctx->tier_half ? 22u : 23u;
+        plan.tiers.exp_bias = ctx->tier_half ? 253 : 126;
+        // explicit tiers while their threshold stays below ~3/4 of all hashes; the last tier takes the rest
+        uint32_t n_exp = 1;
+        auto c_of = [&](uint32_t t) { return ctx->tier_half ? c0 * ((t & 1u) ? 1.5 : 1.0) * (double)(1u << (t >> 1)) : c0 * (double)(1u << t); };
+        while (n_exp < TR_TIERS_MAX - 1 && c_of(n_exp) <= 0.75 * (double)w) ++n_exp;
+        plan.tiers.n_tiers = n_exp + 1;
+        plan.tiers.halo = ((w - 1 + 63) / 64) * 64;
+        plan.tiers.core = TR_EXT - 2 * plan.tiers.halo;
+        prune_c = (uint32_t)std::max(1.0, std::ceil(c0));
+      }
+    }
+  }
+  plan.sel = tiered ? SketchSel::Tiers : pruned ? SketchSel::OneThreshold : SketchSel::Dense;
+  plan.c = plan.sel == SketchSel::Dense ? 0 : prune_c;
+  // Dense pass over a sparse filter: with occupancy o, a summary bit covering 2^shift filter bits is set with probability
+  // ~ o * 2^shift; when that is small the summary answers nearly every probe from the L2 (k_hash_keys_sparse).
+  if (plan.sel != SketchSel::OneThreshold && !(plan.sel == SketchSel::Tiers && ctx->tier_mode == 2) && filter && filter->owned && ctx->summary_mode == 0 && !filter_out) {
+    std::lock_guard<std::mutex> summary_lock(filter->mu);
+    uint64_t pc = 0;
+    if (int rc = nts_bf_popcount(ctx, filter, &pc)) return rc;
+    const double bits = (double)filter->bytes * 8.0;
+    uint32_t shift = 7;
+    const uint32_t sum_log2 = NTS_KNOB("NTS_SUMMARY_LOG2_BITS") ? (uint32_t)std::max(16, std::min(28, atoi(NTS_KNOB("NTS_SUMMARY_LOG2_BITS")))) : SUMMARY_LOG2_BITS;
+    while ((bits / (double)(1ull << shift)) > (double)(1ull << sum_log2) && shift < 30) ++shift; // summary <= 2^sum_log2 bits
+    // How full may the summary be?  A set summary bit sends the k-mer to HBM, so the path costs ~8 ms of hashing and look-ups per 3 Gbp plus
+    // P(bit set) = 1 - exp(-occupancy 2^shift) of the every-k-mer pass (75 ms).  Against the tiered selection (families of 4 .. 7 genomes at
+    // 6-10 %, scripts/summary_switch.py): 32 against 92 ms at 0.31 (five genomes at 10 %: neither path applied there until round 5 --
+    // every k-mer was probed), 52 against 50 at 0.82, 56 against 50 at 0.96: it wins below ~0.7; against every k-mer probed, where the
+    // tiers do not apply, as long as a summary bit says anything at all.
+    const double sum_max = NTS_KNOB("NTS_SUMMARY_MAX") ? atof(NTS_KNOB("NTS_SUMMARY_MAX")) : (plan.sel == SketchSel::Tiers ? 0.7 : 3.0);
+    if ((double)pc / bits * (double)(1ull << shift) < sum_max) {
+      if (int rc = bf_make_summary(ctx, filter, shift)) return rc;
+      const uint64_t key_tiles = (rt.n_valid + KEY_TILE - 1) / KEY_TILE;
+      NTS_WS(d_any, uint32_t*, "tile_any", (key_tiles + 4) * 4);
+      plan.summary = filter->d_summary;
+      plan.summary_shift = shift;
+      plan.tile_any = d_any;
+      // accepted share of the k-mers, for sizing the candidate segments (a retry follows if it was too small)
+      const double own = bits * (1.0 - std::exp(-(double)rt.n_valid / bits));
+      plan.p = own > 0 ? std::min(1.0, (double)pc / own) : 1.0;
+      if (ctx->sketch_mode != 1) plan.sel = SketchSel::AcceptList; // (mode "dense" keeps the key / window kernels, with the summary in front of the probes)
+      // the folded copy pays while it rejects a good share of the k-mers: set bits / 2^19 below ~1.2 (about 70 % of its bits set)
+      plan.fold = (ctx->fold_mode == 0 && bits >= (double)(1u << FOLD_BITS_LOG2) && (double)pc < 1.2 * (double)(1u << FOLD_BITS_LOG2))
+                    ? filter->d_fold : nullptr;
+    }
+  }
+  return NTS_OK;
+}
 
 } // namespace
 
@@ -3997,12 +4147,6 @@ extern "C" int nts_sketch_ex(nts_ctx* ctx, const nts_genome* g, uint32_t k, uint
                              const nts_interval* mask, uint64_t n_mask, nts_mx** out)
 {
   if (!ctx || !g || !out || k == 0 || w == 0 || (n_mask && !mask)) return fail(ctx, NTS_EINVAL, "nts_sketch: bad arguments");
-  ctx->cur_rep = filter_out; // (read by the key kernel's launch; cleared on every way out)
-  struct RepGuard
-  {
-    nts_ctx* c;
-    ~RepGuard() { c->cur_rep = nullptr; }
-  } rep_guard{ ctx };
   if (w > WIN_MAX_W) return fail(ctx, NTS_ERANGE, "nts_sketch: w exceeds the LDS-resident window limit (12000)");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   GenomeTables scratch;
@@ -4012,7 +4156,6 @@ extern "C" int nts_sketch_ex(nts_ctx* ctx, const nts_genome* g, uint32_t k, uint
   const RunTable& rt = T->rt;
   nts_mx* mx = new nts_mx();
   ctx->last_candidates = ctx->last_gaps = ctx->last_gap_kmers = ctx->last_many_listed = 0;
-  ctx->small_gap_path = true;
   if (rt.n_valid == 0 || T->n_win_tiles(w) == 0) {
     *out = mx;
     return NTS_OK;
@@ -4020,8 +4163,6 @@ extern "C" int nts_sketch_ex(nts_ctx* ctx, const nts_genome* g, uint32_t k, uint
   auto bail = [&](int code) {
     hipStreamSynchronize(ctx->stream);
     nts_mx_free(ctx, mx);
-    ctx->cur_summary = nullptr;
-    ctx->cur_tile_any = nullptr;
     return code;
   };
 #define SK_TRY(expr)                                                                                \
@@ -4041,180 +4182,29 @@ extern "C" int nts_sketch_ex(nts_ctx* ctx, const nts_genome* g, uint32_t k, uint
   type ptr = (type)ws_get(ctx, name, bytes);                                                        \
   if (!ptr) return bail(NTS_ENOMEM)
 
-  // Pruning policy.  p = share of this genome's k-mers the filter accepts, estimated from occupancies: the
-  // genome alone would set about bits*(1-exp(-V/bits)) bits, the common filter kept popcount of them.  A window
-  // of w k-mers holds ~c*p accepted candidates when hashes <= (c/w)*2^64 are kept; c*p = 12 leaves ~6e-6 of the
-  // windows uncovered (they are re-evaluated densely).  The select kernel probes its candidates in batches and keeps
-  // only the accepted ones, so c may grow until a quarter of the k-mers are candidates (p down to 48/w); below that
-  // the dense kernels take over.
-  // (one threshold from w = 200; below it the tiers, with or without a filter -- without one, ntSynt --no-common, every listed k-mer is accepted and
-  //  the rounds only decide which k-mers are hashed in full: 3 Gbp at w = 10 / 33 / 63 / 90 / 150 / 200: 35 / 14 / 10 / 8 / 6.5 / 6.1 ms, against 64 / 57 /
-  //  49 ms through the window tiles and 23 / 8.5 / 7.0 with one threshold; scripts/mode_sweep.py)
-  const uint32_t prune_min_w = 200u;
-  bool pruned = ctx->sketch_mode == 2 || (ctx->sketch_mode == 0 && w >= prune_min_w);
-  // a filter-out filter (indexlr -r: experimental in the reference) is served by the every-k-mer-probed kernels only
-  if (filter_out) pruned = false;
-  uint32_t prune_c = ctx->prune_c;
-  double p = 1.0; // accepted share of the candidates (1 when unknown: sizes the candidate arrays)
-  bool tiered = false;
-  TierPlan plan;
-  // (tiers forced: wherever the kernel applies.  Windows of 64 .. 199 k-mers, where one threshold never paid and every k-mer was probed:
-  //  the tiered selection is looked at there too -- a whole 3 Gbp genome at w = 100 against its family's filter: 90 ms the dense way)
-  const bool tiers_forced = ctx->tier_mode == 2 && ctx->sketch_mode == 0 && !filter_out && prune_c == 0;
-  // (windows below WIN_FUSE_W = 64, round 6: the same selection down to w = 8 where its estimated cost stays below tier_small_c of the every-k-mer pass)
-  const uint32_t tier_min_w = NTS_KNOB("NTS_TIER_MIN_W") ? (uint32_t)atoi(NTS_KNOB("NTS_TIER_MIN_W")) : 8u;
-  const double tier_small_c = NTS_KNOB("NTS_TIER_SMALL_C") ? atof(NTS_KNOB("NTS_TIER_SMALL_C")) : 0.85;
-  // (without a filter -- ntSynt --no-common -- below the window where one threshold takes over: every listed k-mer is accepted, the tiers only
-  //  decide which k-mers are hashed in full at all)
-  const bool tiers_small_w = ctx->tier_mode == 0 && ctx->sketch_mode == 0 && !filter_out && prune_c == 0 && w >= tier_min_w && w < 200;
-  if ((pruned || tiers_forced || tiers_small_w) && prune_c == 0) {
-    if (filter) {
-      uint64_t pc = 0;
-      SK_TRY(nts_bf_popcount(ctx, filter, &pc));
-      const double bits = (double)filter->bytes * 8.0;
-      auto share = [&](double kmers) { // of a genome with that many (distinct) k-mers
-        const double own = bits * (1.0 - std::exp(-kmers / bits));
-        return own > 0 ? std::min(1.0, (double)pc / own) : 1.0;
-      };
-      if (g->part_bases.size() > 1 && g->total_bases) {
-        // a batch: every part is a genome of its own as far as the filter is concerned (the parts of a batch are
-        // assemblies of one family: their k-mers are largely the same ones, not three times as many)
-        double acc = 0;
-        for (uint64_t b : g->part_bases) {
-          const double f = (double)b / (double)g->total_bases;
-          acc += f * share((double)rt.n_valid * f);
-        }
-        p = acc;
-      } else {
-        p = share((double)rt.n_valid);
-      }
-    }
-    // c*p = 11 accepted candidates per window on average (`cp` below; 10.5 until round 3).  (More would not empty the list of uncovered ranges:
-    // beyond the ~V*(cp/w)*exp(-cp) chance ones there are the stretches the other genomes do not share at all.
-    // Measured at 3 x 3 Gbp, w = 1000, p = 0.70, with k_hash_select_hi and the uncovered ranges probed only where a window
-    // reads them: c = 12 / 13 / 14 / 15 / 16 -> 1021 / 1085 / 1124 / 1134 / 1124 Gbases/s; with k_hash_select, whose rolling
-    // cost twice as much per k-mer, and whole key tiles probed around every range, the optimum was c = 18, cp = 12.)
-    // (round 3, with the select kernel dropping hopeless candidates and a family with insertions: c = 13 .. 17 ->
-    //  1280 / 1397 / 1420 / 1476 / 1413 Gbases/s; c = 16 at p = 0.70.  Round 5, same family: c = 12 .. 17 -> 1118 / 1250 / 1432 / 1468 /
-    //  1522 / 1516.)  An assembly in thousands of pieces (more than one run of valid bases per 2^20 k-mers) has its uncovered
-    //  ranges whatever c is -- scaffold ends, gaps, repeats -- and a listing cost that rises faster with c (tiles that list more than
-    //  their slots hold): the assembly-like family at 3 x 3 Gbp, p = 0.55: c = 14 / 16 / 18 / 21 -> 986 / 1134 / 1121 / 1070 Gbases/s; with the uncovered
-    //  ranges through the tiered selection (run_gap_tiers): c = 12 / 14 / 16 / 18 -> 933 / 1193 / 1291 / 1250.
-    const bool in_pieces = (uint64_t)T->n_runs > (rt.n_valid >> 20) + 64;
-    const double cp = in_pieces ? 8.7 : 11.0;
-    const double want = std::max(8.0, std::ceil(cp / std::max(p, 1e-4)));
-    // (measured: at a quarter of the k-mers as candidates the pruned pass is still twice as fast as the dense one;
-    // at 40 % single lanes run out of slots in most tiles and it is half as fast)
-    // (with short windows the accepted candidates per lane of k_hash_select get dense sooner: measured at w = 250,
-    // 3 x 100 Mbp: c = 35 -> 56 Gbases/s against 34 dense, c = 50 -> 17; at w = 1000, c = 203 still gives 94)
-    const double cap = (w >= 512 ? 0.25 : 0.15) * (double)w;
-    prune_c = (uint32_t)std::min(want, cap);
-    if ((ctx->sketch_mode == 0 && want > cap) || w < prune_min_w) pruned = ctx->sketch_mode == 2;
-    // Tiered selection (nts_tiers.inc): thresholds tau_0 2^t instead of one threshold, each probed only where a window is still
-    // without an accepted k-mer -- ~3.4/p probes per window instead of 11/p.  It takes over where one threshold lists so many
-    // k-mers that the upper-halves kernel no longer applies, down to accepted shares where even the first tier is half of all k-mers.
-    if (!filter_out && ctx->sketch_mode == 0 && ctx->tier_mode != 1 && k <= FAST_K_MAX && w >= tier_min_w && w <= 4097) {
-      // (first tier: 2.4 accepted k-mers per window on average; 1.2 below w = 64, where every tier is a large share of the k-mers and a
-      //  thinner first one saves 8-12 % of the probes: scripts/tiers_x0_sweep.py)
-      const double x0 = ctx->tier_x0 > 0 ? ctx->tier_x0 : (w < WIN_FUSE_W ? 1.2 : 2.4);
-      const double c0 = x0 / std::max(p, 1e-6);
-      const double switch_c = 54.0 * (double)w / 1000.0; // (beyond it k_hash_select takes over from k_hash_select_hi)
-      // Below w = 200 the other way probes every k-mer (k_window_min<true> under 64: ~85 ms per 3 Gbp at k = 24, 105 at k = 100; the key array
-      // above: 110-120).  The tiers cost ~91 ms per (probe per k-mer) at k = 24 and more with k -- a listed k-mer is hashed from scratch,
-      // ceil(k / 4) table reads: 290 ms at k = 100 -- and where w <= k they probe every k-mer of the stretch a substitution empties.  Probes
-      // per k-mer, fitted to scripts/tiers_small_w.py, tiers_x0_sweep.py and the k = 16 / 100 runs: 0.9 (1 - p) min(1, (k/w)^2) + 2.5 / (p w).
-      bool pays = true;
-      if (w < 200 && ctx->tier_mode != 2) {
-        const double kw = std::min(1.0, (double)k / (double)w);
-        const double est = std::min(1.0, 0.9 * (1.0 - p) * kw * kw + 2.5 / std::max(p * (double)w, 1e-9));
-        const double per_probe = 0.3 + 0.7 * (double)k / 24.0;
-        pays = per_probe * est <= tier_small_c * (1.0 + 0.002 * ((double)k - 24.0));
-      }
-      const double c0_max = 0.5 * (double)w;
-      const bool fits = w >= WIN_FUSE_W || 48.0 * 7.5 * (double)rt.n_valid / (double)w <= 120e9;
-      // (an assembly in pieces lists fewer candidates per window -- cp = 8.7 -- but that says nothing about where the tiers overtake the one
-      //  threshold: the comparison is made with the whole-genome figure; 200,000 contigs at w = 250, p = 0.7: tiers 7.4 ms, one threshold 10.4)
-      const double want_whole = std::max(8.0, std::ceil(11.0 / std::max(p, 1e-4)));
-      if (c0 <= c0_max && fits && pays && (ctx->tier_mode == 2 || want_whole > switch_c)) {
-        tiered = true;
-        pruned = false;
-        plan.c0 = c0;
-        const double t0 = std::max(1.0, std::floor(c0 / (double)w * 4294967296.0));
-        plan.scale = (float)(1.0 / (t0 + 1.0));
-        plan.exp_shift = ctx->tier_half ? 22u : 23u;
-        plan.exp_bias = ctx->tier_half ? 253 : 126;
-        // explicit tiers while their threshold stays below ~3/4 of all hashes; the last tier takes the rest
-        uint32_t n_exp = 1;
-        auto c_of = [&](uint32_t t) { return ctx->tier_half ? c0 * ((t & 1u) ? 1.5 : 1.0) * (double)(1u << (t >> 1)) : c0 * (double)(1u << t); };
-        while (n_exp < TR_TIERS_MAX - 1 && c_of(n_exp) <= 0.75 * (double)w) ++n_exp;
-        plan.n_tiers = n_exp + 1;
-        plan.halo = ((w - 1 + 63) / 64) * 64;
-        plan.core = TR_EXT - 2 * plan.halo;
-        prune_c = (uint32_t)std::max(1.0, std::ceil(c0));
-      }
-    }
-  }
-  ctx->last_c = (pruned || tiered) ? prune_c : 0;
-  ctx->last_tiers = tiered ? plan.n_tiers : 0;
+  SketchPlan plan;
+  SK_TRY(plan_sketch(ctx, g, *T, k, w, filter, filter_out, plan));
+  ctx->last_c = plan.c;
+  ctx->last_tiers = plan.sel == SketchSel::Tiers ? plan.tiers.n_tiers : 0;
   ctx->last_tier_probes = ctx->last_tier_rounds = 0;
-  // Dense pass over a sparse filter: with occupancy o, a summary bit covering 2^shift filter bits is set with probability
-  // ~ o * 2^shift; when that is small the summary answers nearly every probe from the L2 (k_hash_keys_sparse).
-  ctx->cur_summary = nullptr;
-  ctx->cur_fold = nullptr;
-  ctx->cur_tile_any = nullptr;
-  ctx->last_summary = 0;
-  bool accept_all = false;
-  if (!pruned && !(tiered && ctx->tier_mode == 2) && filter && filter->owned && ctx->summary_mode == 0 && !filter_out) {
-    std::lock_guard<std::mutex> summary_lock(filter->mu);
-    uint64_t pc = 0;
-    SK_TRY(nts_bf_popcount(ctx, filter, &pc));
-    const double bits = (double)filter->bytes * 8.0;
-    uint32_t shift = 7;
-    const uint32_t sum_log2 = NTS_KNOB("NTS_SUMMARY_LOG2_BITS") ? (uint32_t)std::max(16, std::min(28, atoi(NTS_KNOB("NTS_SUMMARY_LOG2_BITS")))) : SUMMARY_LOG2_BITS;
-    while ((bits / (double)(1ull << shift)) > (double)(1ull << sum_log2) && shift < 30) ++shift; // summary <= 2^sum_log2 bits
-    // How full may the summary be?  A set summary bit sends the k-mer to HBM, so the path costs ~8 ms of hashing and look-ups per 3 Gbp plus
-    // P(bit set) = 1 - exp(-occupancy 2^shift) of the every-k-mer pass (75 ms).  Against the tiered selection (families of 4 .. 7 genomes at
-    // 6-10 %, scripts/summary_switch.py): 32 against 92 ms at 0.31 (five genomes at 10 %: neither path applied there until round 5 --
-    // every k-mer was probed), 52 against 50 at 0.82, 56 against 50 at 0.96: it wins below ~0.7; against every k-mer probed, where the
-    // tiers do not apply, as long as a summary bit says anything at all.
-    const double sum_max = NTS_KNOB("NTS_SUMMARY_MAX") ? atof(NTS_KNOB("NTS_SUMMARY_MAX")) : (tiered ? 0.7 : 3.0);
-    if ((double)pc / bits * (double)(1ull << shift) < sum_max) {
-      SK_TRY(bf_make_summary(ctx, filter, shift));
-      const uint64_t key_tiles = (rt.n_valid + KEY_TILE - 1) / KEY_TILE;
-      SK_WS(d_any, uint32_t*, "tile_any", (key_tiles + 4) * 4);
-      ctx->cur_summary = filter->d_summary;
-      ctx->cur_summary_shift = shift;
-      ctx->cur_tile_any = d_any;
-      ctx->last_summary = shift;
-      // accepted share of the k-mers, for sizing the candidate segments (a retry follows if it was too small)
-      const double own = bits * (1.0 - std::exp(-(double)rt.n_valid / bits));
-      p = own > 0 ? std::min(1.0, (double)pc / own) : 1.0;
-      accept_all = ctx->sketch_mode != 1; // (mode "dense" keeps the key / window kernels, with the summary in front of the probes)
-      if (accept_all) {
-        tiered = false;
-        ctx->last_tiers = 0;
-      }
-      // the folded copy pays while it rejects a good share of the k-mers: set bits / 2^19 below ~1.2 (about 70 % of its bits set)
-      ctx->cur_fold = (ctx->fold_mode == 0 && bits >= (double)(1u << FOLD_BITS_LOG2) && (double)pc < 1.2 * (double)(1u << FOLD_BITS_LOG2))
-                        ? filter->d_fold : nullptr;
-    }
-  }
+  ctx->last_summary = plan.summary ? plan.summary_shift : 0;
 
   for (int attempt = 0;; ++attempt) {
     SortedOut res;
-    if (pruned || accept_all || tiered) {
-      const int rc_p = run_pruned(ctx, g, *T, k, w, filter, prune_c, p, res, accept_all, tiered ? &plan : nullptr);
-      if (rc_p == NTS_ENOMEM && tiered && !pruned && !accept_all && w < WIN_FUSE_W) {
+    if (plan.sel != SketchSel::Dense) {
+      const int rc_p = run_pruned(ctx, g, *T, k, w, filter, plan, res);
+      if (rc_p == NTS_ENOMEM && plan.sel == SketchSel::Tiers && w < WIN_FUSE_W) {
         // short windows have a second way that keeps nothing but the minimizers (k_window_min<true>): the lists of accepted k-mers
         // the tiers fill did not fit the device next to what the caller holds
-        tiered = false;
+        plan.sel = SketchSel::Dense;
+        plan.c = 0;
         ctx->last_c = ctx->last_tiers = 0;
-        SK_TRY(run_dense_sorted(ctx, g, *T, k, w, filter, nullptr, nullptr, nullptr, rt.n_valid, "", res));
+        SK_TRY(run_dense_sorted(ctx, g, *T, k, w, filter, plan, nullptr, nullptr, nullptr, rt.n_valid, "", res));
       } else {
         SK_TRY(rc_p);
       }
     } else
-      SK_TRY(run_dense_sorted(ctx, g, *T, k, w, filter, nullptr, nullptr, nullptr, rt.n_valid, "", res));
+      SK_TRY(run_dense_sorted(ctx, g, *T, k, w, filter, plan, nullptr, nullptr, nullptr, rt.n_valid, "", res));
     const uint64_t count = res.count; // exact, or an upper bound when the count still lives on the device
     mx->n = count;
     if (count) {
@@ -4238,7 +4228,7 @@ extern "C" int nts_sketch_ex(nts_ctx* ctx, const nts_genome* g, uint32_t k, uint
     }
     // the last kernel of the call also clears the pruned pass's control block for the next call (one fill launch less
     // at the head of every sketch)
-    uint64_t* const sel_ctl = (pruned || accept_all || tiered) ? (uint64_t*)ws_get(ctx, "sel_ctl", (N_SEG + 2) * 8) : nullptr;
+    uint64_t* const sel_ctl = plan.sel != SketchSel::Dense ? (uint64_t*)ws_get(ctx, "sel_ctl", (N_SEG + 2) * 8) : nullptr;
     if (!res.d_ctl) {
       Mail done(ctx); // nothing to fetch: only the arrival flag
       if (sel_ctl) done.clear_after(sel_ctl, N_SEG + 2);
@@ -4261,11 +4251,8 @@ extern "C" int nts_sketch_ex(nts_ctx* ctx, const nts_genome* g, uint32_t k, uint
     mx->d_h1 = nullptr;
     mx->d_pos = nullptr;
     mx->d_rec = nullptr;
-    ctx->small_gap_path = false;
+    plan.few_ranges = false;
   }
-  ctx->small_gap_path = true;
-  ctx->cur_summary = nullptr;
-  ctx->cur_tile_any = nullptr;
   *out = mx;
   return NTS_OK;
 #undef SK_TRY
