@@ -1065,6 +1065,7 @@ int nts_engine_add(nts_ctx* ctx, nts_engine* E, const nts_mx* const* lists, cons
 {
   if (!ctx || !E || !lists) return fail(ctx, NTS_EINVAL, "nts_engine_add: bad arguments");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ctx->graph_live0 = nts_mem::live.load();
   const uint32_t G = E->G;
   uint64_t n = 0;
   for (uint32_t a = 0; a < G; ++a) {

@@ -206,13 +206,11 @@ __global__ __launch_bounds__(256) void k_g_valid_scatter(const uint64_t* __restr
   if (i < n) valid_elem[idx_sorted[i]] = valid[i];
 }
 
-// The build proper.  Expects the concatenated elements (assembly-major) already in the scratch buffers g_h / g_rec / g_pos /
-// g_keep / g_list / g_asm / g_idx (filled by the callers below); leaves the graph in scratch and describes it in `G`.
-int graph_build_core(nts_ctx* ctx, uint32_t n_asm, uint64_t n, GraphDev* G, ListHook* hook)
+// The build in one pass, every sort over all n elements.  Expects the concatenated elements (assembly-major) already in the
+// scratch buffers g_h / g_rec / g_pos / g_keep / g_list / g_asm / g_idx (filled by the callers below); leaves the graph in scratch
+// and describes it in `G`.
+int graph_build_one_pass(nts_ctx* ctx, uint32_t n_asm, uint64_t n, GraphDev* G, ListHook* hook)
 {
-  *G = GraphDev();
-  G->n = n;
-  if (n == 0) return NTS_OK;
   NTS_WS(d_h, uint64_t*, "g_h", n * 8);
   NTS_WS(d_idx, uint64_t*, "g_idx", n * 8);
   NTS_WS(d_h2, uint64_t*, "g_h2", n * 8);
@@ -329,6 +327,550 @@ int graph_build_core(nts_ctx* ctx, uint32_t n_asm, uint64_t n, GraphDev* G, List
   return NTS_OK;
 }
 
+// ---- the build in hash-range slices (when the one-pass sorts do not fit the scratch budget) --------------------------------------
+// Vertex ids are ranks in ascending hash order.  The elements whose hashes fall into one contiguous range of hash values are
+// deduplicated, intersected and numbered on their own: the slices, taken in range order and numbered on from the vertices of the
+// slices before them, give the one-pass build's vertices.  A slice holds whole hash values (k_g_valid / k_g_common look at the
+// neighbours with an equal hash).  Edges are sliced by their smaller end (the pair key's upper half) and the dict-order sort by the
+// rank of the edge's source: both keys order the whole, so the slices' results, one after the other, are the one-pass order.
+// What stays n-sized: the input columns (g_h, g_idx, g_asm, g_rec, g_pos, g_keep, g_list: 45 B per element), the elements' vertex
+// ids (g_evid, 4 B), the valid mask the refinement hook reads (g_valid_elem, 1 B) and the hook's own scan (16 B, released before the
+// edge pass).  Survivor-sized: the survivors' columns (12 B), the unordered edges (20 B per adjacent pair) and the results.
+// Everything else is sized to the largest slice and given back at the end of the build.
+
+constexpr uint32_t HIST_BINS = 65536;
+constexpr uint32_t HIST_CHUNK = 65535; // elements one workgroup counts: a bin's count fits the 16-bit half of an LDS word
+
+// 16-bit bins of a key: counted in LDS (two bins per 32-bit word), one global add per non-empty bin and workgroup
+template <typename Key>
+__global__ __launch_bounds__(256) void k_g_hist(Key key, uint64_t n, unsigned long long* __restrict__ hist)
+{
+  __shared__ uint32_t bins[HIST_BINS / 2];
+  for (uint32_t b = threadIdx.x; b < HIST_BINS / 2; b += blockDim.x) bins[b] = 0;
+  __syncthreads();
+  const uint64_t i0 = (uint64_t)blockIdx.x * HIST_CHUNK;
+  const uint64_t i1 = n - i0 < HIST_CHUNK ? n : i0 + HIST_CHUNK;
+  for (uint64_t i = i0 + threadIdx.x; i < i1; i += blockDim.x) {
+    uint32_t b = 0;
+    if (key(i, &b)) atomicAdd(&bins[b >> 1], 1u << ((b & 1u) * 16));
+  }
+  __syncthreads();
+  for (uint32_t w = threadIdx.x; w < HIST_BINS / 2; w += blockDim.x) {
+    const uint32_t v = bins[w];
+    if (v & 0xFFFFu) atomicAdd(&hist[2 * w], (unsigned long long)(v & 0xFFFFu));
+    if (v >> 16) atomicAdd(&hist[2 * w + 1], (unsigned long long)(v >> 16));
+  }
+}
+
+// k_g_pairs' key of survivor c
+__device__ inline uint64_t g_pair_key(const uint32_t* c_vid, const uint32_t* c_asm, const uint32_t* c_list, uint64_t m, uint64_t c)
+{
+  if (c + 1 < m && c_asm[c] == c_asm[c + 1] && c_list[c] == c_list[c + 1]) {
+    const uint64_t u = c_vid[c], v = c_vid[c + 1];
+    return u < v ? ((u << 32) | v) : ((v << 32) | u);
+  }
+  return ~0ULL;
+}
+
+// histogram keys (the bin of item i; false: not counted) and slice predicates (item i's key is in [lo, hi])
+struct HashBin
+{
+  const uint64_t* h;
+  uint64_t lo, hi;
+  uint32_t shift;
+  __device__ bool operator()(uint64_t i, uint32_t* b) const
+  {
+    const uint64_t x = h[i];
+    *b = (uint32_t)(x >> shift) & 0xFFFFu;
+    return x >= lo && x <= hi;
+  }
+};
+struct HashIn
+{
+  const uint64_t* h;
+  uint64_t lo, hi;
+  __device__ bool operator()(uint64_t i) const { return h[i] >= lo && h[i] <= hi; }
+};
+struct KeptIn
+{
+  const uint32_t* evid;
+  __device__ bool operator()(uint64_t i) const { return evid[i] != 0xFFFFFFFFu; }
+};
+struct PairBin
+{
+  const uint32_t *vid, *asm_id, *list;
+  uint64_t m;
+  uint32_t shift;
+  __device__ bool operator()(uint64_t c, uint32_t* b) const
+  {
+    const uint64_t k = g_pair_key(vid, asm_id, list, m, c);
+    *b = (uint32_t)((k >> 32) >> shift);
+    return k != ~0ULL;
+  }
+};
+struct PairIn
+{
+  const uint32_t *vid, *asm_id, *list;
+  uint64_t m, lo, hi;
+  __device__ bool operator()(uint64_t c) const
+  {
+    const uint64_t k = g_pair_key(vid, asm_id, list, m, c);
+    return k != ~0ULL && (k >> 32) >= lo && (k >> 32) <= hi;
+  }
+};
+struct RankBin
+{
+  const uint32_t* e_u;
+  const unsigned long long* srank;
+  uint32_t shift;
+  __device__ bool operator()(uint64_t e, uint32_t* b) const
+  {
+    *b = (uint32_t)(srank[e_u[e]] >> shift);
+    return true;
+  }
+};
+struct RankIn
+{
+  const uint32_t* e_u;
+  const unsigned long long* srank;
+  uint64_t lo, hi;
+  __device__ bool operator()(uint64_t e) const { return srank[e_u[e]] >= lo && srank[e_u[e]] <= hi; }
+};
+
+__global__ __launch_bounds__(256) void k_g_gather_h(const uint64_t* __restrict__ idx, uint64_t ns, const uint64_t* __restrict__ h,
+                                                    uint64_t* __restrict__ out)
+{
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < ns) out[i] = h[idx[i]];
+}
+
+// k_g_assign's numbering within one slice: every valid element of a common group gets vid_off + the group's rank in the slice
+__global__ __launch_bounds__(256) void k_g_slice_vid(const uint64_t* __restrict__ h_sorted, const uint64_t* __restrict__ idx_sorted,
+                                                     const uint8_t* __restrict__ valid, const uint64_t* __restrict__ head_common,
+                                                     const uint64_t* __restrict__ vid_scan, uint64_t ns, uint64_t vid_off,
+                                                     uint32_t* __restrict__ elem_vid)
+{
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= ns) return;
+  const uint64_t h = h_sorted[i];
+  if (!(i == 0 || h_sorted[i - 1] != h) || !head_common[i]) return;
+  const uint32_t vid = (uint32_t)(vid_off + vid_scan[i]);
+  for (uint64_t j = i; j < ns && h_sorted[j] == h; ++j)
+    if (valid[j]) elem_vid[idx_sorted[j]] = vid;
+}
+
+// the rest of k_g_assign once every slice is numbered: each element with a vertex writes its hash and its occurrence
+__global__ __launch_bounds__(256) void k_g_vertex_tables(const uint32_t* __restrict__ elem_vid, uint64_t n, const uint64_t* __restrict__ h,
+                                                         const uint32_t* __restrict__ asm_of, const uint32_t* __restrict__ rec,
+                                                         const uint64_t* __restrict__ pos, uint64_t nv, uint64_t* __restrict__ v_hash,
+                                                         uint32_t* __restrict__ occ_rec, uint64_t* __restrict__ occ_pos)
+{
+  const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n) return;
+  const uint32_t vid = elem_vid[e];
+  if (vid == 0xFFFFFFFFu) return;
+  v_hash[vid] = h[e]; // (one writer per assembly, all with the same value)
+  occ_rec[(uint64_t)asm_of[e] * nv + vid] = rec[e];
+  occ_pos[(uint64_t)asm_of[e] * nv + vid] = pos[e];
+}
+
+__global__ __launch_bounds__(256) void k_g_gather_survivors(const uint64_t* __restrict__ sel, uint64_t m, const uint32_t* __restrict__ elem_vid,
+                                                            const uint32_t* __restrict__ asm_of, const uint32_t* __restrict__ list_id,
+                                                            uint32_t* __restrict__ c_vid, uint32_t* __restrict__ c_asm, uint32_t* __restrict__ c_list)
+{
+  const uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= m) return;
+  const uint64_t e = sel[c];
+  c_vid[c] = elem_vid[e];
+  c_asm[c] = asm_of[e];
+  c_list[c] = list_id[e];
+}
+
+__global__ __launch_bounds__(256) void k_g_gather_pairs(const uint64_t* __restrict__ seq, uint64_t ms, const uint32_t* __restrict__ c_vid,
+                                                        const uint32_t* __restrict__ c_asm, const uint32_t* __restrict__ c_list, uint64_t m,
+                                                        uint64_t* __restrict__ key)
+{
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < ms) key[i] = g_pair_key(c_vid, c_asm, c_list, m, seq[i]);
+}
+
+__global__ __launch_bounds__(256) void k_g_gather_order(const uint64_t* __restrict__ idx, uint64_t ns, const uint32_t* __restrict__ e_u,
+                                                        const uint64_t* __restrict__ e_first, const unsigned long long* __restrict__ src_rank,
+                                                        uint64_t* __restrict__ key)
+{
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= ns) return;
+  const uint64_t e = idx[i];
+  key[i] = ((uint64_t)src_rank[e_u[e]] << 32) | e_first[e];
+}
+
+// scratch buffer `name` back to the allocator (ws_get keeps buffers by name until ws_release)
+void ws_drop(nts_ctx* ctx, const char* name)
+{
+  auto it = ctx->ws.find(name);
+  if (it == ctx->ws.end()) return;
+  if (it->second.first) {
+    hipStreamSynchronize(ctx->stream);
+    dev_free(it->second.first);
+  }
+  ctx->ws.erase(it);
+}
+
+// nts_graph_last_plan's scratch figure: library bytes live beyond those live when the call began, highest where sampled
+void graph_sample_peak(nts_ctx* ctx)
+{
+  const uint64_t now = nts_mem::live.load();
+  if (now > ctx->graph_live0) ctx->last_graph_peak = std::max(ctx->last_graph_peak, now - ctx->graph_live0);
+}
+
+// the one-pass build's sort and scan buffers, and this path's slice buffers
+const char* const ONE_PASS_SCRATCH[] = { "g_h2", "g_idx2", "g_valid", "g_flag", "g_scan", "g_tmp", "g_key", "g_seq", "g_key2", "g_seq2",
+                                         "g_eh", "g_es", "g_tmp2", "g_tmp3" };
+const char* const SLICE_SCRATCH[] = { "gs_h", "gs_idx", "gs_h2", "gs_idx2", "gs_valid", "gs_flag", "gs_scan", "gs_tmp", "gs_sel_tmp", "gs_cnt",
+                                      "gs_hist" };
+
+struct KeyRange
+{
+  uint64_t lo, hi, n; // [lo, hi] of the key, items in it
+};
+
+// 16-bit histogram of `key` over n items (host copy)
+template <typename Key>
+int slice_hist(nts_ctx* ctx, Key key, uint64_t n, std::vector<uint64_t>* out)
+{
+  NTS_WS(d_hist, unsigned long long*, "gs_hist", HIST_BINS * 8);
+  out->assign(HIST_BINS, 0);
+  if (n == 0) return NTS_OK;
+  HIP_TRY(ctx, hipMemsetAsync(d_hist, 0, HIST_BINS * 8, ctx->stream));
+  NTS_LAUNCH(k_g_hist<Key>, dim3((uint32_t)((n + HIST_CHUNK - 1) / HIST_CHUNK)), dim3(256), 0, ctx->stream, key, n, d_hist);
+  HIP_TRY(ctx, hipMemcpyAsync(out->data(), d_hist, HIST_BINS * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return NTS_OK;
+}
+
+// key ranges of the planned slices, from their first to their last non-empty bin (bin b covers [base + (b << shift),
+// base + ((b + 1) << shift) - 1]); empty slices are left out.  *oversize counts the slices of one bin that hold more than `cap` items.
+void slice_ranges(const std::vector<uint64_t>& hist, uint64_t cap, uint64_t base, uint32_t shift, std::vector<KeyRange>* out, uint32_t* oversize)
+{
+  std::vector<uint32_t> cuts(HIST_BINS + 1);
+  uint32_t S = 0;
+  nts_graph_plan_slices(hist.data(), HIST_BINS, 1, std::max<uint64_t>(cap, 1), cuts.data(), &S);
+  for (uint32_t s = 0; s < S; ++s) {
+    uint64_t cnt = 0;
+    uint32_t first = cuts[s + 1], last = cuts[s];
+    for (uint32_t b = cuts[s]; b < cuts[s + 1]; ++b)
+      if (hist[b]) {
+        cnt += hist[b];
+        first = std::min(first, b);
+        last = b;
+      }
+    if (!cnt) continue;
+    if (first == last && cnt > cap) ++*oversize;
+    out->push_back({ base + ((uint64_t)first << shift), base + ((uint64_t)last << shift) + ((1ULL << shift) - 1), cnt });
+  }
+}
+
+// members of one slice, ascending (rocprim::select keeps the input order): the numbers i < n with pred(i)
+template <typename Pred>
+int slice_select(nts_ctx* ctx, Pred pred, uint64_t n, uint64_t* d_out)
+{
+  NTS_WS(d_cnt, uint64_t*, "gs_cnt", 8);
+  auto in = rocprim::make_counting_iterator<uint64_t>(0);
+  size_t tmp = 0;
+  HIP_TRY(ctx, rocprim::select(nullptr, tmp, in, d_out, d_cnt, n, pred, ctx->stream));
+  NTS_WS(d_tmp, void*, "gs_sel_tmp", std::max<size_t>(tmp, 16));
+  HIP_TRY(ctx, rocprim::select(d_tmp, tmp, in, d_out, d_cnt, n, pred, ctx->stream));
+  return NTS_OK;
+}
+
+// the last flag plus the last entry of its exclusive scan: how many were flagged
+int flag_count(nts_ctx* ctx, const uint64_t* flag, const uint64_t* scan, uint64_t n, uint64_t* count)
+{
+  uint64_t a = 0, b = 0;
+  HIP_TRY(ctx, hipMemcpyAsync(&a, flag + (n - 1), 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(&b, scan + (n - 1), 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  *count = a + b;
+  return NTS_OK;
+}
+
+// the slice buffers, for slices of up to `ns` items (one set serves the vertex, pair and order passes)
+struct SliceBufs
+{
+  uint64_t *h, *idx, *h2, *idx2, *flag, *scan;
+  uint8_t* valid;
+  void* tmp;
+  size_t tmp_sort, tmp_scan;
+};
+int slice_bufs(nts_ctx* ctx, uint64_t ns, SliceBufs* b)
+{
+  ns = std::max<uint64_t>(ns, 1);
+  NTS_WS(h, uint64_t*, "gs_h", ns * 8);
+  NTS_WS(idx, uint64_t*, "gs_idx", ns * 8);
+  NTS_WS(h2, uint64_t*, "gs_h2", ns * 8);
+  NTS_WS(idx2, uint64_t*, "gs_idx2", ns * 8);
+  NTS_WS(flag, uint64_t*, "gs_flag", ns * 8);
+  NTS_WS(scan, uint64_t*, "gs_scan", ns * 8);
+  NTS_WS(valid, uint8_t*, "gs_valid", ns);
+  size_t tmp_sort = 0, tmp_scan = 0;
+  HIP_TRY(ctx, rocprim::radix_sort_pairs(nullptr, tmp_sort, h, h2, idx, idx2, ns, 0, 64, ctx->stream));
+  HIP_TRY(ctx, rocprim::exclusive_scan(nullptr, tmp_scan, flag, scan, (uint64_t)0, ns, rocprim::plus<uint64_t>(), ctx->stream));
+  NTS_WS(tmp, void*, "gs_tmp", std::max<size_t>(std::max(tmp_sort, tmp_scan), 16));
+  *b = { h, idx, h2, idx2, flag, scan, valid, tmp, tmp_sort, tmp_scan };
+  return NTS_OK;
+}
+
+uint64_t max_range(const std::vector<KeyRange>& r)
+{
+  uint64_t m = 0;
+  for (const KeyRange& x : r) m = std::max(m, x.n);
+  return m;
+}
+
+// smallest shift that brings every key below `limit` into 16 bits
+uint32_t bin_shift(uint64_t limit)
+{
+  uint32_t s = 0;
+  while (limit > 0 && ((limit - 1) >> s) >= HIST_BINS) ++s;
+  return s;
+}
+
+constexpr uint32_t MAX_REFINED_BINS = 16; // top-16-bit bins over the cap split again on the next 16 bits (one pass over n each)
+
+// `cap`: items per slice
+int graph_build_sliced(nts_ctx* ctx, uint32_t n_asm, uint64_t n, GraphDev* G, ListHook* hook, uint64_t cap)
+{
+  for (const char* nm : ONE_PASS_SCRATCH) ws_drop(ctx, nm); // (what an earlier one-pass build on this context left)
+  NTS_WS(d_h, uint64_t*, "g_h", n * 8);
+  NTS_WS(d_asm, uint32_t*, "g_asm", n * 4);
+  NTS_WS(d_rec, uint32_t*, "g_rec", n * 4);
+  NTS_WS(d_pos, uint64_t*, "g_pos", n * 8);
+  NTS_WS(d_keep, uint8_t*, "g_keep", n);
+  NTS_WS(d_list, uint32_t*, "g_list", n * 4);
+  NTS_WS(d_evid, uint32_t*, "g_evid", n * 4);
+  uint8_t* d_valid_elem = nullptr;
+  if (hook) {
+    NTS_WS(p, uint8_t*, "g_valid_elem", n);
+    d_valid_elem = p;
+  }
+  HIP_TRY(ctx, hipMemsetAsync(d_evid, 0xFF, n * 4, ctx->stream));
+  // ---- plan: the top 16 bits of the hash; a bin over the cap is split on the next 16 bits (the first few such bins)
+  uint32_t oversize = 0, refined = 0, top_over = 0;
+  std::vector<uint64_t> hist;
+  if (int rc = slice_hist(ctx, HashBin{ d_h, 0, ~0ULL, 48 }, n, &hist)) return rc;
+  std::vector<KeyRange> top, vr;
+  slice_ranges(hist, cap, 0, 48, &top, &top_over);
+  for (const KeyRange& r : top) {
+    if (r.n > cap && r.hi - r.lo == (1ULL << 48) - 1 && refined < MAX_REFINED_BINS) {
+      ++refined;
+      std::vector<uint64_t> sub;
+      if (int rc = slice_hist(ctx, HashBin{ d_h, r.lo, r.hi, 32 }, n, &sub)) return rc;
+      slice_ranges(sub, cap, r.lo, 32, &vr, &oversize);
+    } else {
+      if (r.n > cap) ++oversize;
+      vr.push_back(r);
+    }
+  }
+  // ---- vertices, slice by slice
+  SliceBufs b;
+  if (int rc = slice_bufs(ctx, max_range(vr), &b)) return rc;
+  uint64_t nv = 0;
+  for (const KeyRange& r : vr) {
+    const uint64_t ns = r.n;
+    const uint32_t sb = (uint32_t)((ns + 255) / 256);
+    if (int rc = slice_select(ctx, HashIn{ d_h, r.lo, r.hi }, n, b.idx)) return rc;
+    {
+      ScopedTimer t(ctx, "graph_build");
+      NTS_LAUNCH(k_g_gather_h, dim3(sb), dim3(256), 0, ctx->stream, b.idx, ns, d_h, b.h);
+      HIP_TRY(ctx, rocprim::radix_sort_pairs(b.tmp, b.tmp_sort, b.h, b.h2, b.idx, b.idx2, ns, 0, 64, ctx->stream));
+      NTS_LAUNCH(k_g_valid, dim3(sb), dim3(256), 0, ctx->stream, b.h2, b.idx2, d_asm, d_keep, ns, b.valid);
+      if (hook) {
+        NTS_LAUNCH(k_g_valid_scatter, dim3(sb), dim3(256), 0, ctx->stream, b.idx2, b.valid, ns, d_valid_elem);
+      }
+      NTS_LAUNCH(k_g_common, dim3(sb), dim3(256), 0, ctx->stream, b.h2, b.valid, ns, n_asm, b.flag);
+      HIP_TRY(ctx, rocprim::exclusive_scan(b.tmp, b.tmp_scan, b.flag, b.scan, (uint64_t)0, ns, rocprim::plus<uint64_t>(), ctx->stream));
+      NTS_LAUNCH(k_g_slice_vid, dim3(sb), dim3(256), 0, ctx->stream, b.h2, b.idx2, b.valid, b.flag, b.scan, ns, nv, d_evid);
+    }
+    uint64_t nv_s = 0;
+    if (int rc = flag_count(ctx, b.flag, b.scan, ns, &nv_s)) return rc;
+    nv += nv_s;
+  }
+  graph_sample_peak(ctx);
+  G->nv = nv;
+  const uint64_t n_vslices = vr.size();
+  // The hook rewrites list ids only (RefineHook: d_list from the valid mask, records and positions), and the vertex pass does not
+  // read them: it runs once, after the last slice.  Its n-sized scan buffers and the slice buffers are not live at the same time.
+  if (hook) {
+    for (const char* nm : SLICE_SCRATCH) ws_drop(ctx, nm);
+    if (int rc = (*hook)(ctx, n, d_valid_elem, d_asm, d_rec, d_pos, d_list)) return rc;
+    graph_sample_peak(ctx);
+    for (const char* nm : { "e_hook_a", "e_hook_b", "e_scan_tmp" }) ws_drop(ctx, nm);
+  }
+  uint64_t n_eslices = 1;
+  if (nv) {
+    const uint32_t nb = (uint32_t)((n + 255) / 256);
+    NTS_WS(d_vhash, uint64_t*, "g_vhash", nv * 8);
+    NTS_WS(d_orec, uint32_t*, "g_orec", (uint64_t)n_asm * nv * 4);
+    NTS_WS(d_opos, uint64_t*, "g_opos", (uint64_t)n_asm * nv * 8);
+    const uint64_t m = (uint64_t)n_asm * nv; // every common hash occurs once per assembly
+    const uint32_t mb = (uint32_t)((m + 255) / 256);
+    NTS_WS(d_cvid, uint32_t*, "g_cvid", (m + 1) * 4);
+    NTS_WS(d_casm, uint32_t*, "g_casm", m * 4);
+    NTS_WS(d_clist, uint32_t*, "g_clist", m * 4);
+    NTS_WS(d_sel, uint64_t*, "gs_idx", m * 8); // (the survivors' element numbers; a slice buffer again below)
+    {
+      ScopedTimer t(ctx, "graph_build");
+      NTS_LAUNCH(k_g_vertex_tables, dim3(nb), dim3(256), 0, ctx->stream, d_evid, n, d_h, d_asm, d_rec, d_pos, nv, d_vhash, d_orec, d_opos);
+    }
+    // survivors in traversal order
+    if (int rc = slice_select(ctx, KeptIn{ d_evid }, n, d_sel)) return rc;
+    {
+      ScopedTimer t(ctx, "graph_build");
+      NTS_LAUNCH(k_g_gather_survivors, dim3(mb), dim3(256), 0, ctx->stream, d_sel, m, d_evid, d_asm, d_list, d_cvid, d_casm, d_clist);
+    }
+    G->v_hash = d_vhash;
+    G->occ_rec = d_orec;
+    G->occ_pos = d_opos;
+    // ---- edges: the pair keys in ranges of their smaller end
+    std::vector<uint64_t> ph;
+    const uint32_t ushift = bin_shift(nv);
+    if (int rc = slice_hist(ctx, PairBin{ d_cvid, d_casm, d_clist, m, ushift }, m, &ph)) return rc;
+    uint64_t n_pairs = 0;
+    for (uint64_t x : ph) n_pairs += x;
+    std::vector<KeyRange> er;
+    slice_ranges(ph, cap, 0, ushift, &er, &oversize);
+    NTS_WS(d_eu0, uint32_t*, "g_eu0", std::max<uint64_t>(n_pairs, 1) * 4);
+    NTS_WS(d_ev0, uint32_t*, "g_ev0", std::max<uint64_t>(n_pairs, 1) * 4);
+    NTS_WS(d_ew0, uint32_t*, "g_ew0", std::max<uint64_t>(n_pairs, 1) * 4);
+    NTS_WS(d_ef0, uint64_t*, "g_ef0", std::max<uint64_t>(n_pairs, 1) * 8);
+    if (int rc = slice_bufs(ctx, max_range(er), &b)) return rc;
+    graph_sample_peak(ctx);
+    uint64_t ne = 0;
+    for (const KeyRange& r : er) {
+      const uint64_t ms = r.n;
+      const uint32_t sb = (uint32_t)((ms + 255) / 256);
+      if (int rc = slice_select(ctx, PairIn{ d_cvid, d_casm, d_clist, m, r.lo, r.hi }, m, b.idx)) return rc;
+      {
+        ScopedTimer t(ctx, "graph_build");
+        NTS_LAUNCH(k_g_gather_pairs, dim3(sb), dim3(256), 0, ctx->stream, b.idx, ms, d_cvid, d_casm, d_clist, m, b.h);
+        HIP_TRY(ctx, rocprim::radix_sort_pairs(b.tmp, b.tmp_sort, b.h, b.h2, b.idx, b.idx2, ms, 0, 64, ctx->stream));
+        NTS_LAUNCH(k_g_edge_heads, dim3(sb), dim3(256), 0, ctx->stream, b.h2, ms, b.flag);
+        HIP_TRY(ctx, rocprim::exclusive_scan(b.tmp, b.tmp_scan, b.flag, b.scan, (uint64_t)0, ms, rocprim::plus<uint64_t>(), ctx->stream));
+        NTS_LAUNCH(k_g_edges, dim3(sb), dim3(256), 0, ctx->stream, b.h2, b.idx2, b.flag, b.scan, ms, d_cvid, d_eu0 + ne, d_ev0 + ne, d_ew0 + ne,
+                           d_ef0 + ne);
+      }
+      uint64_t ne_s = 0;
+      if (int rc = flag_count(ctx, b.flag, b.scan, ms, &ne_s)) return rc;
+      ne += ne_s;
+    }
+    G->ne = ne;
+    n_eslices = std::max<uint64_t>(er.size(), 1);
+    NTS_WS(d_eu, uint32_t*, "g_eu", std::max<uint64_t>(ne, 1) * 4);
+    NTS_WS(d_ev, uint32_t*, "g_ev", std::max<uint64_t>(ne, 1) * 4);
+    NTS_WS(d_ew, uint32_t*, "g_ew", std::max<uint64_t>(ne, 1) * 4);
+    NTS_WS(d_ef, uint64_t*, "g_ef", std::max<uint64_t>(ne, 1) * 8);
+    if (ne) {
+      // ---- ntJoin's dict order, sorted in ranges of the source's rank
+      NTS_WS(d_srank, unsigned long long*, "g_srank", nv * 8);
+      const uint32_t eb = (uint32_t)((ne + 255) / 256);
+      {
+        ScopedTimer t(ctx, "graph_build");
+        HIP_TRY(ctx, hipMemsetAsync(d_srank, 0xFF, nv * 8, ctx->stream));
+        NTS_LAUNCH(k_g_src_rank, dim3(eb), dim3(256), 0, ctx->stream, d_eu0, d_ef0, ne, d_srank);
+      }
+      std::vector<uint64_t> rh;
+      const uint32_t rshift = bin_shift(m); // (a rank is the sequence number of a pair: below m)
+      if (int rc = slice_hist(ctx, RankBin{ d_eu0, d_srank, rshift }, ne, &rh)) return rc;
+      std::vector<KeyRange> orr;
+      slice_ranges(rh, cap, 0, rshift, &orr, &oversize);
+      n_eslices = std::max<uint64_t>(n_eslices, orr.size());
+      if (int rc = slice_bufs(ctx, max_range(orr), &b)) return rc;
+      graph_sample_peak(ctx);
+      uint64_t off = 0;
+      for (const KeyRange& r : orr) {
+        const uint64_t ns = r.n;
+        const uint32_t sb = (uint32_t)((ns + 255) / 256);
+        if (int rc = slice_select(ctx, RankIn{ d_eu0, d_srank, r.lo, r.hi }, ne, b.idx)) return rc;
+        ScopedTimer t(ctx, "graph_build");
+        NTS_LAUNCH(k_g_gather_order, dim3(sb), dim3(256), 0, ctx->stream, b.idx, ns, d_eu0, d_ef0, d_srank, b.h);
+        HIP_TRY(ctx, rocprim::radix_sort_pairs(b.tmp, b.tmp_sort, b.h, b.h2, b.idx, b.idx2, ns, 0, 64, ctx->stream));
+        NTS_LAUNCH(k_g_permute_edges, dim3(sb), dim3(256), 0, ctx->stream, b.idx2, ns, d_eu0, d_ev0, d_ew0, d_ef0, d_eu + off, d_ev + off,
+                           d_ew + off, d_ef + off);
+        off += ns;
+      }
+    }
+    G->e_u = d_eu;
+    G->e_v = d_ev;
+    G->e_w = d_ew;
+    G->e_first = d_ef;
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  graph_sample_peak(ctx);
+  // the slice buffers and the survivor-sized intermediates do not stay cached into the caller's table growth
+  for (const char* nm : SLICE_SCRATCH) ws_drop(ctx, nm);
+  for (const char* nm : { "g_eu0", "g_ev0", "g_ew0", "g_ef0", "g_srank", "g_cvid", "g_casm", "g_clist" }) ws_drop(ctx, nm);
+  ctx->last_graph_v_slices = (uint32_t)n_vslices;
+  ctx->last_graph_e_slices = (uint32_t)n_eslices;
+  ctx->last_graph_oversize = oversize;
+  return NTS_OK;
+}
+
+// slice scratch per item: the vertex pass's buffers (the pair and order passes use fewer of them) and the sort's temporary storage
+uint64_t slice_bytes_per_item(nts_ctx* ctx, uint64_t n)
+{
+  size_t tmp = 0;
+  (void)rocprim::radix_sort_pairs(nullptr, tmp, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t*)nullptr, n, 0, 64,
+                                  ctx->stream);
+  return 6 * 8 + 1 + (tmp + n - 1) / n;
+}
+
+// what the results of a build and the engine's tables may grow by, per input minimizer (vertices <= n / n_asm with a hash and n_asm
+// occurrences each; survivors <= n with their columns, pairs, unordered and ordered edges; the engine's copies of both)
+constexpr uint64_t GRAPH_RESULT_BYTES = 96;
+
+// automatic budget: free device memory and the allocation cache's free bytes, less a margin, less what the build keeps n-sized
+// besides the slices and what its results and the engine's tables may grow by
+uint64_t graph_auto_budget(uint64_t n, bool hook)
+{
+  size_t fr = 0, tot = 0;
+  if (hipMemGetInfo(&fr, &tot) != hipSuccess) {
+    (void)hipGetLastError();
+    return ~0ULL; // (cannot tell: one pass, as before)
+  }
+  uint64_t cached = 0;
+  {
+    std::lock_guard<std::mutex> g(nts_mem::mu);
+    cached = nts_mem::cached_bytes - nts_mem::cached_small;
+  }
+  const uint64_t margin = 1ull << 30;
+  const uint64_t kept = n * (4 + 1 + (hook ? 16 : 0) + GRAPH_RESULT_BYTES);
+  const uint64_t avail = (uint64_t)fr + cached;
+  return avail > margin + kept ? avail - margin - kept : 1;
+}
+
+// The build proper: in one pass when the slice scratch of all n elements fits the budget (every build that fitted before takes the
+// launch sequence it always took), in hash-range slices otherwise.  The same graph either way.
+int graph_build_core(nts_ctx* ctx, uint32_t n_asm, uint64_t n, GraphDev* G, ListHook* hook)
+{
+  *G = GraphDev();
+  G->n = n;
+  ctx->last_graph_v_slices = ctx->last_graph_e_slices = 1;
+  ctx->last_graph_oversize = 0;
+  ctx->last_graph_peak = 0;
+  if (n == 0) return NTS_OK;
+  const uint64_t per_item = slice_bytes_per_item(ctx, n);
+  const uint64_t budget = ctx->graph_budget ? ctx->graph_budget : graph_auto_budget(n, hook != nullptr);
+  if (budget / per_item >= n) {
+    const int rc = graph_build_one_pass(ctx, n_asm, n, G, hook);
+    graph_sample_peak(ctx);
+    return rc;
+  }
+  const int rc = graph_build_sliced(ctx, n_asm, n, G, hook, budget / per_item);
+  if (rc == NTS_ENOMEM)
+    ctx->err += " (graph build in slices: budget " + std::to_string(budget) + " B, " + std::to_string(budget / per_item) + " minimizers per slice)";
+  return rc;
+}
+
 // scratch buffers of the concatenation, sized for n elements
 struct GraphIn
 {
@@ -361,6 +903,7 @@ extern "C" int nts_graph_build(nts_ctx* ctx, uint32_t n_asm, const nts_mxlist* l
   if (!ctx || !out || n_asm == 0 || !lists) return fail(ctx, NTS_EINVAL, "nts_graph_build: bad arguments");
   memset(out, 0, sizeof(*out));
   HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ctx->graph_live0 = nts_mem::live.load();
   uint64_t n = 0;
   for (uint32_t a = 0; a < n_asm; ++a) {
     if (lists[a].n && (!lists[a].h1 || !lists[a].rec || !lists[a].pos)) return fail(ctx, NTS_EINVAL, "nts_graph_build: NULL list arrays");
@@ -416,6 +959,44 @@ extern "C" int nts_graph_build(nts_ctx* ctx, uint32_t n_asm, const nts_mxlist* l
     nts_graph_free(out);
     return fail(ctx, NTS_ENOMEM, "nts_graph_build: host allocation failed");
   }
+  return NTS_OK;
+}
+
+extern "C" int nts_graph_budget(nts_ctx* ctx, uint64_t bytes)
+{
+  if (!ctx) return NTS_EINVAL;
+  ctx->graph_budget = bytes;
+  return NTS_OK;
+}
+
+extern "C" int nts_graph_last_plan(nts_ctx* ctx, uint32_t* v_slices, uint32_t* e_slices, uint64_t* scratch_peak_bytes, uint32_t* oversize_slices)
+{
+  if (!ctx) return NTS_EINVAL;
+  if (v_slices) *v_slices = ctx->last_graph_v_slices;
+  if (e_slices) *e_slices = ctx->last_graph_e_slices;
+  if (scratch_peak_bytes) *scratch_peak_bytes = ctx->last_graph_peak;
+  if (oversize_slices) *oversize_slices = ctx->last_graph_oversize;
+  return NTS_OK;
+}
+
+// greedy: bins go into the running slice while its items times bytes_per_elem stay within the budget; a bin that alone exceeds it
+// is a slice of its own
+extern "C" int nts_graph_plan_slices(const uint64_t* hist, uint32_t n_bins, uint64_t bytes_per_elem, uint64_t budget, uint32_t* cuts, uint32_t* n_slices)
+{
+  if (!hist || !cuts || !n_slices || n_bins == 0 || bytes_per_elem == 0 || budget == 0) return NTS_EINVAL;
+  const uint64_t cap = budget / bytes_per_elem;
+  uint32_t s = 0;
+  uint64_t acc = 0;
+  cuts[0] = 0;
+  for (uint32_t b = 0; b < n_bins; ++b) {
+    if (acc > 0 && hist[b] > 0 && acc + hist[b] > cap) {
+      cuts[++s] = b;
+      acc = 0;
+    }
+    acc += hist[b];
+  }
+  cuts[++s] = n_bins;
+  *n_slices = s;
   return NTS_OK;
 }
 

@@ -509,6 +509,11 @@ struct nts_ctx
   double tier_x0 = 0;       // accepted k-mers per window the first tier aims at (0: the default)
   uint32_t tier_half = 0;   // 1: tiers in steps of 1.5 / 1.33 instead of 2
   uint64_t last_tier_probes = 0, last_tier_rounds = 0, last_tiers = 0;
+  // graph build (nts_graph.hip): scratch budget of the per-slice buffers (0 = automatic) and the plan of the last build
+  uint64_t graph_budget = 0;
+  uint32_t last_graph_v_slices = 0, last_graph_e_slices = 0, last_graph_oversize = 0;
+  uint64_t last_graph_peak = 0;
+  uint64_t graph_live0 = 0; // library bytes live when the running build's call began
 };
 
 struct nts_genome

@@ -146,6 +146,18 @@ class Context:
                 # 4 SIMDs per CU, each issuing one wave-instruction per `cycles`: the clock the two figures imply
                 "implied_clock_GHz": round(per_cu * cyc.value / 4 / 1e9, 3)}
 
+    def set_graph_budget(self, nbytes):
+        """Bytes the graph build's per-slice scratch may take on this context (nts_graph_budget); 0 = automatic (free device memory).
+        A build whose sorts do not fit runs in hash-range slices; same graph."""
+        self.check(self.lib.nts_graph_budget(self.h, int(nbytes)), "nts_graph_budget")
+
+    def graph_last_plan(self):
+        "dict(v_slices, e_slices, scratch_peak, oversize) of the last graph build on this context (nts_graph_last_plan)"
+        v, e, o, p = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32(), u64()
+        self.check(self.lib.nts_graph_last_plan(self.h, ctypes.byref(v), ctypes.byref(e), ctypes.byref(p), ctypes.byref(o)),
+                   "nts_graph_last_plan")
+        return {"v_slices": v.value, "e_slices": e.value, "scratch_peak": p.value, "oversize": o.value}
+
     def mem_stats(self):
         """Device memory of the library's allocations in this process: dict(live, peak, device_used, device_total) in bytes
         (nts_mem_stats; `peak` is the high-water mark since the last mem_reset_peak())."""

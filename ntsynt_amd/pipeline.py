@@ -495,7 +495,8 @@ def reserve_for_run(ctx, fastas, fpr, build_filter, log=None, w=1000):
 def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=10000, merge=10000,
         block_size=500, common=True, simplify=True, device=0, write_mx_tsv=True, mx_with_seq=True,
         benchmark=False, log=print, ctx=None, backend=None, bf_rounding="up", bf_signature=BF_SIGNATURE, dev=False, interarrivals=False, repeat=False,
-        mx_tsvs=None, common_file=None, m=90, n=0, initial_only=False, write_fai=True, engine="device", refine_repeat_file=None, screen_repeat_file=None):
+        mx_tsvs=None, common_file=None, m=90, n=0, initial_only=False, write_fai=True, engine="device", refine_repeat_file=None, screen_repeat_file=None,
+        graph_budget=None):
     """FASTA paths -> engine (outputs in .outputs and in the CWD).  Mirrors oracle.synteny_oracle.run_pipeline's
     signature so the parity tests read alike.  Under torch.distributed (WORLD_SIZE > 1, process group already
     initialised by the caller) genomes are sharded over the ranks.
@@ -503,7 +504,8 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
     The reference's stage 3 on its own (bin/ntsynt_run.py, rule ntsynt_synteny smk:87-103): mx_tsvs = the minimizer TSV of
     every assembly (aligned with `fastas`: read instead of sketched, ntJoin's read_minimizers) and common_file = the
     `--common` filter file (uploaded instead of built; None with common=False: the refinement rounds sketch unfiltered);
-    m / n: ntsynt_run.py's -m / -n."""
+    m / n: ntsynt_run.py's -m / -n.  graph_budget: bytes of per-slice scratch the graph builds may take (Context.set_graph_budget;
+    None leaves the context's setting, 0 = automatic)."""
     prefix = prefix or f"ntSynt.k{k}.w{w}"
     if mx_tsvs is not None and len(mx_tsvs) != len(fastas):
         raise ValueError("one minimizer TSV per FASTA file")
@@ -518,6 +520,8 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
     backend = backend or GpuBackend(device, ctx)
     st = Stages()
     if isinstance(backend, GpuBackend):
+        if graph_budget is not None:
+            backend.ctx.set_graph_budget(graph_budget)
         lib = backend.ctx.lib                                  # (ctx = NULL: live / peak of the process, readable after the contexts closed)
         lib.nts_mem_reset_peak()
 

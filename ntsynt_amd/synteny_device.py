@@ -154,6 +154,11 @@ class DeviceSyntenyEngine(SyntenyEngine):
     # ------------------------------------------------------------------ device steps
     def _add(self, lists, spans):
         self.graph.add(lists, spans)
+        if self.dev and self.log:
+            plan = self.ctx.graph_last_plan()
+            if plan["v_slices"] > 1:
+                self.log(f"Graph build in slices: {plan['v_slices']} vertex, {plan['e_slices']} edge; scratch peak {plan['scratch_peak']} bytes; "
+                         f"{plan['oversize']} slices over the budget")
 
     def _simplify_dev(self, apply_deletions):
         "run_graph_simplification (S:548-590) on the table of candidate edges and their neighbourhood (nts_bubble_rule)"
