@@ -461,15 +461,16 @@ typedef struct
 int nts_graph_build(nts_ctx* ctx, uint32_t n_asm, const nts_mxlist* lists, nts_graph* out);
 void nts_graph_free(nts_graph* g);
 
-/* Scratch of the graph build (nts_graph_build and nts_engine_add).  The build sorts all n input minimizers at once when the sort
- * buffers of all of them fit the context's budget, and otherwise in slices: contiguous ranges of hash values (vertex ids are ranks
- * in hash order), then ranges of the pair keys' smaller end and of the edge order's source rank.  Same output either way.
+/* Scratch of the graph build (nts_graph_build and nts_engine_add).  The build sorts its items in slices: contiguous ranges of hash
+ * values (vertex ids are ranks in hash order), then ranges of the pair keys' smaller end and of the edge order's source rank.  When
+ * the slice buffers of all n input minimizers fit the context's budget there is one slice, which holds everything.  Same output
+ * however many there are.
  * nts_graph_budget: bytes the per-slice buffers may take (sort keys and values, flags, scans, the sort's temporary storage);
  *     0 = automatic (the default): free device memory plus the allocation cache's free bytes, less a margin, less what the build
  *     keeps n-sized and what its results may grow by.  The input columns, the elements' vertex ids and the results stay n-sized
  *     whatever the budget (docs/design/04_4_graph_stage.md).
  * nts_graph_last_plan: the last build on this context: vertex slices, edge slices (the larger of the pair and order passes; 1 and
- *     1 for a one-pass build), library bytes live at its highest beyond those live when the call began, and slices over the budget
+ *     1 for a build that fits), library bytes live at its highest beyond those live when the call began, and slices over the budget
  *     (a 32-bit hash prefix, or a bin of the edge passes, that alone does not fit).
  * nts_graph_plan_slices: the host planner.  hist[n_bins] items per bin; cuts[0..*n_slices] (n_bins + 1 entries to hold) with
  *     cuts[0] = 0 and cuts[*n_slices] = n_bins, slice s = bins [cuts[s], cuts[s+1]).  Greedy: a slice takes bins while its items

@@ -867,19 +867,6 @@ int e_scan(nts_ctx* ctx, const uint64_t* in, uint64_t* out, uint64_t n, bool inc
   return NTS_OK;
 }
 
-// number of set flags = scan[n-1] + flag[n-1]
-int e_count(nts_ctx* ctx, const uint64_t* flag, const uint64_t* scan, uint64_t n, uint64_t* count)
-{
-  *count = 0;
-  if (n == 0) return NTS_OK;
-  uint64_t a = 0, b = 0;
-  HIP_TRY(ctx, hipMemcpyAsync(&a, flag + (n - 1), 8, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(&b, scan + (n - 1), 8, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  *count = a + b;
-  return NTS_OK;
-}
-
 int e_degrees(nts_ctx* ctx, nts_engine* E, uint32_t** deg, uint32_t** nbr, uint32_t** nbe)
 {
   const uint64_t nv = std::max<uint64_t>(E->nv, 1);
@@ -925,14 +912,6 @@ struct RefineHook : ListHook
     return NTS_OK;
   }
 };
-
-template <typename T>
-T* e_host(nts_ctx* ctx, const T* d, uint64_t n)
-{
-  T* h = (T*)malloc(std::max<uint64_t>(n, 1) * sizeof(T));
-  if (h && n) hipMemcpyAsync(h, d, n * sizeof(T), hipMemcpyDeviceToHost, ctx->stream);
-  return h;
-}
 
 // ntJoin's read_minimizers with a repeat filter (stage 3's `--filter Filter`, bin/ntsynt_synteny.py:183-184,601-604): a minimizer whose
 // k-mer the filter holds is not read.  One lane per minimizer: canonical ntHash of its k bases (one byte per base in the genome's code
@@ -1086,7 +1065,7 @@ int nts_engine_add(nts_ctx* ctx, nts_engine* E, const nts_mx* const* lists, cons
       HIP_TRY(ctx, hipMemcpyAsync(in.rec + o, lists[a]->d_rec, m * 4, hipMemcpyDeviceToDevice, ctx->stream));
       HIP_TRY(ctx, hipMemcpyAsync(in.pos + o, lists[a]->d_pos, m * 8, hipMemcpyDeviceToDevice, ctx->stream));
       HIP_TRY(ctx, hipMemcpyAsync(in.list + o, lists[a]->d_rec, m * 4, hipMemcpyDeviceToDevice, ctx->stream));
-      NTS_LAUNCH(k_g_number, E_GRID(m), in.idx + o, in.asm_id + o, m, o, a);
+      HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)(in.asm_id + o), (int)a, m, ctx->stream));
     }
     o += m;
   }
@@ -1108,7 +1087,7 @@ int nts_engine_add(nts_ctx* ctx, nts_engine* E, const nts_mx* const* lists, cons
     if (!d_hs || !d_hid) return NTS_ENOMEM;
     NTS_LAUNCH(k_e_live_flag, E_GRID(nv0), E->v_alive, nv0, d_f);
     if (int rc = e_scan(ctx, d_f, d_s, nv0)) return rc;
-    if (int rc = e_count(ctx, d_f, d_s, nv0, &nl)) return rc;
+    if (int rc = flag_count(ctx, d_f, d_s, nv0, &nl)) return rc;
     NTS_LAUNCH(k_e_live_pairs, E_GRID(nv0), E->v_alive, d_s, E->v_hash, nv0, d_k, d_i);
     if (nl) {
       size_t tmp = 0;
@@ -1151,7 +1130,7 @@ int nts_engine_add(nts_ctx* ctx, nts_engine* E, const nts_mx* const* lists, cons
   if (nv0) {
     NTS_LAUNCH(k_e_lookup, E_GRID(lnv), GD.v_hash, lnv, d_hs, d_hid, nl, d_l2g, d_new);
     if (int rc = e_scan(ctx, d_new, d_rank, lnv)) return rc;
-    if (int rc = e_count(ctx, d_new, d_rank, lnv, &n_new)) return rc;
+    if (int rc = flag_count(ctx, d_new, d_rank, lnv, &n_new)) return rc;
   } else {
     HIP_TRY(ctx, hipMemsetAsync(d_l2g, 0xFF, lnv * 4, ctx->stream));
     // rank = the local id: fill through a scan of ones
@@ -1174,7 +1153,7 @@ int nts_engine_add(nts_ctx* ctx, nts_engine* E, const nts_mx* const* lists, cons
     uint64_t n_oo = 0;
     if (nv0 && ne0) {
       if (int rc = e_scan(ctx, d_oo, d_oos, lne)) return rc;
-      if (int rc = e_count(ctx, d_oo, d_oos, lne, &n_oo)) return rc;
+      if (int rc = flag_count(ctx, d_oo, d_oos, lne, &n_oo)) return rc;
     }
     uint64_t n_dup = 0;
     if (n_oo) {
@@ -1194,7 +1173,7 @@ int nts_engine_add(nts_ctx* ctx, nts_engine* E, const nts_mx* const* lists, cons
       NTS_LAUNCH(k_e_touched_edges, E_GRID(ne0), E->e_u, E->e_v, E->e_alive, ne0, d_touched, d_tf);
       if (int rc = e_scan(ctx, d_tf, d_ts, ne0)) return rc;
       uint64_t n_te = 0;
-      if (int rc = e_count(ctx, d_tf, d_ts, ne0, &n_te)) return rc;
+      if (int rc = flag_count(ctx, d_tf, d_ts, ne0, &n_te)) return rc;
       if (n_te) {
         NTS_WS(t_idx, uint32_t*, "e_t_idx", n_te * 4);
         NTS_WS(t_u, uint32_t*, "e_t_u", n_te * 4);
@@ -1222,7 +1201,7 @@ int nts_engine_add(nts_ctx* ctx, nts_engine* E, const nts_mx* const* lists, cons
         NTS_WS(d_hedge, uint32_t*, "e_join_edge", n_oo * 4);
         NTS_LAUNCH(k_e_join_pairs, E_GRID(n_oo), q_u, q_v, n_oo, d_tk2, t_idx2, n_te, d_hit, d_hedge);
         if (int rc = e_scan(ctx, d_hit, d_hits, n_oo)) return rc;
-        if (int rc = e_count(ctx, d_hit, d_hits, n_oo, &n_dup)) return rc;
+        if (int rc = flag_count(ctx, d_hit, d_hits, n_oo, &n_dup)) return rc;
         if (n_dup) {
           NTS_WS(d_dl, uint32_t*, "e_dup_l", n_dup * 4);
           NTS_WS(d_he, uint32_t*, "e_dup_e", n_dup * 4);
@@ -1267,29 +1246,29 @@ int nts_engine_bubbles(nts_ctx* ctx, nts_engine* E, nts_bubbles* out)
   NTS_LAUNCH(k_e_bubble_cand, E_GRID(E->ne), E->e_u, E->e_v, E->e_alive, E->ne, d_deg, d_cv, d_f);
   if (int rc = e_scan(ctx, d_f, d_s, E->ne)) return rc;
   uint64_t n_cand = 0;
-  if (int rc = e_count(ctx, d_f, d_s, E->ne, &n_cand)) return rc;
+  if (int rc = flag_count(ctx, d_f, d_s, E->ne, &n_cand)) return rc;
   if (n_cand == 0) return NTS_OK;
   NTS_WS(c_idx, uint32_t*, "e_c_idx", n_cand * 4);
   NTS_WS(c_u, uint32_t*, "e_c_u", n_cand * 4);
   NTS_WS(c_v, uint32_t*, "e_c_v", n_cand * 4);
   NTS_LAUNCH(k_e_take_flagged, E_GRID(E->ne), d_f, d_s, E->ne, E->e_u, E->e_v, (const uint32_t*)nullptr, c_idx, c_u, c_v, (uint32_t*)nullptr);
   out->n_cand = n_cand;
-  out->cand_edge = e_host(ctx, c_idx, n_cand);
+  out->cand_edge = host_copy(ctx, c_idx, n_cand);
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   NTS_LAUNCH(k_e_incident, E_GRID(E->ne), E->e_u, E->e_v, E->e_alive, E->ne, d_cv, d_f);
   if (int rc = e_scan(ctx, d_f, d_s, E->ne)) return rc;
   uint64_t n_inc = 0;
-  if (int rc = e_count(ctx, d_f, d_s, E->ne, &n_inc)) return rc;
+  if (int rc = flag_count(ctx, d_f, d_s, E->ne, &n_inc)) return rc;
   NTS_WS(i_idx, uint32_t*, "e_i_idx", n_inc * 4);
   NTS_WS(i_u, uint32_t*, "e_i_u", n_inc * 4);
   NTS_WS(i_v, uint32_t*, "e_i_v", n_inc * 4);
   NTS_WS(i_w, uint32_t*, "e_i_w", n_inc * 4);
   NTS_LAUNCH(k_e_take_flagged, E_GRID(E->ne), d_f, d_s, E->ne, E->e_u, E->e_v, E->e_w, i_idx, i_u, i_v, i_w);
   out->n_inc = n_inc;
-  out->inc_edge = e_host(ctx, i_idx, n_inc);
-  out->inc_u = e_host(ctx, i_u, n_inc);
-  out->inc_v = e_host(ctx, i_v, n_inc);
-  out->inc_w = e_host(ctx, i_w, n_inc);
+  out->inc_edge = host_copy(ctx, i_idx, n_inc);
+  out->inc_u = host_copy(ctx, i_u, n_inc);
+  out->inc_v = host_copy(ctx, i_v, n_inc);
+  out->inc_w = host_copy(ctx, i_w, n_inc);
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   if (!out->cand_edge || !out->inc_edge || !out->inc_u || !out->inc_v || !out->inc_w) {
     nts_bubbles_free(out);
@@ -1353,7 +1332,7 @@ int nts_engine_filter(nts_ctx* ctx, nts_engine* E, uint32_t min_weight, int flag
   if (!flag && !n_light) return NTS_OK;
   if (int rc = e_scan(ctx, d_f, d_s, E->ne)) return rc;
   uint64_t n = 0;
-  if (int rc = e_count(ctx, d_f, d_s, E->ne, &n)) return rc;
+  if (int rc = flag_count(ctx, d_f, d_s, E->ne, &n)) return rc;
   if (n_light) *n_light = n;
   if (flag && n) {
     if (n > E->cap_flag) {
@@ -1546,7 +1525,7 @@ int nts_engine_blocks(nts_ctx* ctx, nts_engine* E, int64_t bp, double m_percent,
   NTS_LAUNCH(k_e_classify, E_GRID(nv), d_deg, a, nv, E->v_pos + (uint64_t)E->ref * E->cap_v, d_pstart, d_pidx, d_plen, d_f);
   if (int rc = e_scan(ctx, d_f, d_s, nv)) return rc;
   uint64_t n_paths = 0;
-  if (int rc = e_count(ctx, d_f, d_s, nv, &n_paths)) return rc;
+  if (int rc = flag_count(ctx, d_f, d_s, nv, &n_paths)) return rc;
   out->stats_paths = n_paths;
   if (n_paths == 0) return NTS_OK;
   NTS_WS(d_lens, uint64_t*, "e_lens", (n_paths + 1) * 8);
@@ -1585,7 +1564,7 @@ int nts_engine_blocks(nts_ctx* ctx, nts_engine* E, int64_t bp, double m_percent,
   NTS_LAUNCH(k_e_cuts, E_GRID(N), d_verts, N, d_over, d_nbr, d_nbe, E->e_alive, d_ctl + 1);
   if (int rc = e_scan(ctx, d_bs, d_bscan, N)) return rc;
   uint64_t n_blocks = 0;
-  if (int rc = e_count(ctx, d_bs, d_bscan, N, &n_blocks)) return rc;
+  if (int rc = flag_count(ctx, d_bs, d_bscan, N, &n_blocks)) return rc;
   uint64_t n_kept = 0;
   uint64_t *d_bkeep = nullptr, *d_bwhere = nullptr;
   uint32_t *d_bfirst = nullptr, *d_blast = nullptr, *d_bpath = nullptr;
@@ -1601,7 +1580,7 @@ int nts_engine_blocks(nts_ctx* ctx, nts_engine* E, int64_t bp, double m_percent,
     NTS_LAUNCH(k_e_block_marks, E_GRID(N), d_verts, d_vpath, N, d_pst, d_pgood, d_bs, d_bscan, d_bkeep, d_bfirst, d_blast, d_dead,
                        E->internal, E->terminal);
     if (int rc = e_scan(ctx, d_bkeep, d_bwhere, n_blocks)) return rc;
-    if (int rc = e_count(ctx, d_bkeep, d_bwhere, n_blocks, &n_kept)) return rc;
+    if (int rc = flag_count(ctx, d_bkeep, d_bwhere, n_blocks, &n_kept)) return rc;
   }
   NTS_LAUNCH(k_e_kill, E_GRID(std::max(nv, E->ne)), d_dead, nv, E->v_alive, E->e_u, E->e_v, E->ne, E->e_alive);
   unsigned long long ctl[3] = { 0, 0, 0 };
@@ -1622,13 +1601,13 @@ int nts_engine_blocks(nts_ctx* ctx, nts_engine* E, int64_t bp, double m_percent,
   NTS_LAUNCH(k_e_block_table, E_GRID(n_blocks), d_bkeep, d_bwhere, n_blocks, n_kept, d_bfirst, d_blast, d_bpath, d_verts, d_pst, d_pcode,
                      n_paths, E->v_rec, E->v_pos, E->cap_v, E->G, o_first, o_last, o_n, o_rec, o_fp, o_lp, o_ori);
   HIP_TRY(ctx, hipGetLastError());
-  out->first_vid = e_host(ctx, o_first, n_kept);
-  out->last_vid = e_host(ctx, o_last, n_kept);
-  out->n_mx = e_host(ctx, o_n, n_kept);
-  out->rec = e_host(ctx, o_rec, G * n_kept);
-  out->first_pos = e_host(ctx, o_fp, G * n_kept);
-  out->last_pos = e_host(ctx, o_lp, G * n_kept);
-  out->ori = e_host(ctx, o_ori, G * n_kept);
+  out->first_vid = host_copy(ctx, o_first, n_kept);
+  out->last_vid = host_copy(ctx, o_last, n_kept);
+  out->n_mx = host_copy(ctx, o_n, n_kept);
+  out->rec = host_copy(ctx, o_rec, G * n_kept);
+  out->first_pos = host_copy(ctx, o_fp, G * n_kept);
+  out->last_pos = host_copy(ctx, o_lp, G * n_kept);
+  out->ori = host_copy(ctx, o_ori, G * n_kept);
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   if (!out->first_vid || !out->last_vid || !out->n_mx || !out->rec || !out->first_pos || !out->last_pos || !out->ori) {
     nts_blocks_free(out);

@@ -39,65 +39,6 @@ __global__ __launch_bounds__(256) void k_g_common(const uint64_t* __restrict__ h
   head_common[i] = flag;
 }
 
-// vid_scan = exclusive scan of head_common: every valid element of a common group gets the group's id
-__global__ __launch_bounds__(256) void k_g_assign(const uint64_t* __restrict__ h_sorted, const uint64_t* __restrict__ idx_sorted,
-                                                  const uint8_t* __restrict__ valid, const uint64_t* __restrict__ head_common,
-                                                  const uint64_t* __restrict__ vid_scan, uint64_t n, const uint32_t* __restrict__ asm_of,
-                                                  const uint32_t* __restrict__ rec, const uint64_t* __restrict__ pos, uint64_t nv,
-                                                  uint32_t* __restrict__ elem_vid, uint64_t* __restrict__ v_hash,
-                                                  uint32_t* __restrict__ occ_rec, uint64_t* __restrict__ occ_pos)
-{
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint64_t h = h_sorted[i];
-  if (!(i == 0 || h_sorted[i - 1] != h) || !head_common[i]) return;
-  const uint64_t vid = vid_scan[i];
-  v_hash[vid] = h;
-  for (uint64_t j = i; j < n && h_sorted[j] == h; ++j) {
-    if (!valid[j]) continue;
-    const uint64_t e = idx_sorted[j];
-    elem_vid[e] = (uint32_t)vid;
-    const uint32_t a = asm_of[e];
-    occ_rec[(uint64_t)a * nv + vid] = rec[e];
-    occ_pos[(uint64_t)a * nv + vid] = pos[e];
-  }
-}
-
-__global__ __launch_bounds__(256) void k_g_flag_kept(const uint32_t* __restrict__ elem_vid, uint64_t n, uint64_t* __restrict__ flag)
-{
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) flag[i] = elem_vid[i] != 0xFFFFFFFFu ? 1 : 0;
-}
-
-// compact the survivors in traversal order: c_vid / c_asm / c_list
-__global__ __launch_bounds__(256) void k_g_compact(const uint32_t* __restrict__ elem_vid, const uint64_t* __restrict__ where, uint64_t n,
-                                                   const uint32_t* __restrict__ asm_of, const uint32_t* __restrict__ list_id,
-                                                   uint32_t* __restrict__ c_vid, uint32_t* __restrict__ c_asm, uint32_t* __restrict__ c_list)
-{
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n || elem_vid[i] == 0xFFFFFFFFu) return;
-  const uint64_t c = where[i];
-  c_vid[c] = elem_vid[i];
-  c_asm[c] = asm_of[i];
-  c_list[c] = list_id[i];
-}
-
-// adjacent survivors of one list -> edge occurrence (canonical key, sequence number); others get key ~0
-__global__ __launch_bounds__(256) void k_g_pairs(const uint32_t* __restrict__ c_vid, const uint32_t* __restrict__ c_asm,
-                                                 const uint32_t* __restrict__ c_list, uint64_t m, uint64_t* __restrict__ key,
-                                                 uint64_t* __restrict__ seq)
-{
-  const uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= m) return;
-  uint64_t kk = ~0ULL;
-  if (c + 1 < m && c_asm[c] == c_asm[c + 1] && c_list[c] == c_list[c + 1]) {
-    const uint64_t u = c_vid[c], v = c_vid[c + 1];
-    kk = u < v ? ((u << 32) | v) : ((v << 32) | u);
-  }
-  key[c] = kk;
-  seq[c] = c;
-}
-
 __global__ __launch_bounds__(256) void k_g_edge_heads(const uint64_t* __restrict__ key_sorted, uint64_t m, uint64_t* __restrict__ head)
 {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -133,25 +74,6 @@ __global__ __launch_bounds__(256) void k_g_src_rank(const uint32_t* __restrict__
   if (e < ne) atomicMin(&src_rank[e_u[e]], (unsigned long long)e_first[e]);
 }
 
-__global__ __launch_bounds__(256) void k_g_order_keys(const uint32_t* __restrict__ e_u, const uint64_t* __restrict__ e_first, uint64_t ne,
-                                                      const unsigned long long* __restrict__ src_rank, uint64_t* __restrict__ key,
-                                                      uint64_t* __restrict__ idx)
-{
-  const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= ne) return;
-  key[e] = ((uint64_t)src_rank[e_u[e]] << 32) | e_first[e];
-  idx[e] = e;
-}
-
-// element numbers base .. base+m-1 and the assembly id of one list of the concatenation
-__global__ __launch_bounds__(256) void k_g_number(uint64_t* __restrict__ idx, uint32_t* __restrict__ asm_id, uint64_t m, uint64_t base, uint32_t a)
-{
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= m) return;
-  idx[i] = base + i;
-  asm_id[i] = a;
-}
-
 __global__ __launch_bounds__(256) void k_g_permute_edges(const uint64_t* __restrict__ idx_sorted, uint64_t ne, const uint32_t* __restrict__ e_u,
                                                          const uint32_t* __restrict__ e_v, const uint32_t* __restrict__ e_w,
                                                          const uint64_t* __restrict__ e_first, uint32_t* __restrict__ o_u,
@@ -174,9 +96,18 @@ T* host_copy(nts_ctx* ctx, const T* d, uint64_t n)
   return h;
 }
 
-} // namespace
-
-namespace {
+// number of set flags = scan[n-1] + flag[n-1] (scan: the flags' exclusive scan)
+int flag_count(nts_ctx* ctx, const uint64_t* flag, const uint64_t* scan, uint64_t n, uint64_t* count)
+{
+  *count = 0;
+  if (n == 0) return NTS_OK;
+  uint64_t a = 0, b = 0;
+  HIP_TRY(ctx, hipMemcpyAsync(&a, flag + (n - 1), 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(&b, scan + (n - 1), 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  *count = a + b;
+  return NTS_OK;
+}
 
 // Device-side result of one build, in the context's scratch (valid until the next build on this context)
 struct GraphDev
@@ -206,137 +137,19 @@ __global__ __launch_bounds__(256) void k_g_valid_scatter(const uint64_t* __restr
   if (i < n) valid_elem[idx_sorted[i]] = valid[i];
 }
 
-// The build in one pass, every sort over all n elements.  Expects the concatenated elements (assembly-major) already in the
-// scratch buffers g_h / g_rec / g_pos / g_keep / g_list / g_asm / g_idx (filled by the callers below); leaves the graph in scratch
-// and describes it in `G`.
-int graph_build_one_pass(nts_ctx* ctx, uint32_t n_asm, uint64_t n, GraphDev* G, ListHook* hook)
-{
-  NTS_WS(d_h, uint64_t*, "g_h", n * 8);
-  NTS_WS(d_idx, uint64_t*, "g_idx", n * 8);
-  NTS_WS(d_h2, uint64_t*, "g_h2", n * 8);
-  NTS_WS(d_idx2, uint64_t*, "g_idx2", n * 8);
-  NTS_WS(d_asm, uint32_t*, "g_asm", n * 4);
-  NTS_WS(d_rec, uint32_t*, "g_rec", n * 4);
-  NTS_WS(d_pos, uint64_t*, "g_pos", n * 8);
-  NTS_WS(d_keep, uint8_t*, "g_keep", n);
-  NTS_WS(d_list, uint32_t*, "g_list", n * 4);
-  NTS_WS(d_valid, uint8_t*, "g_valid", n);
-  NTS_WS(d_flag, uint64_t*, "g_flag", n * 8);
-  NTS_WS(d_scan, uint64_t*, "g_scan", (n + 1) * 8);
-  NTS_WS(d_evid, uint32_t*, "g_evid", n * 4);
-  const uint32_t nb = (uint32_t)((n + 255) / 256);
-  size_t tmp_sort = 0, tmp_scan = 0;
-  HIP_TRY(ctx, rocprim::radix_sort_pairs(nullptr, tmp_sort, d_h, d_h2, d_idx, d_idx2, n, 0, 64, ctx->stream));
-  HIP_TRY(ctx, rocprim::exclusive_scan(nullptr, tmp_scan, d_flag, d_scan, (uint64_t)0, n, rocprim::plus<uint64_t>(), ctx->stream));
-  NTS_WS(d_tmp, void*, "g_tmp", std::max<size_t>(std::max(tmp_sort, tmp_scan), 16));
-  {
-    ScopedTimer t(ctx, "graph_build");
-    // C1 + keep mask
-    HIP_TRY(ctx, rocprim::radix_sort_pairs(d_tmp, tmp_sort, d_h, d_h2, d_idx, d_idx2, n, 0, 64, ctx->stream));
-    NTS_LAUNCH(k_g_valid, dim3(nb), dim3(256), 0, ctx->stream, d_h2, d_idx2, d_asm, d_keep, n, d_valid);
-  }
-  if (hook) {
-    NTS_WS(d_valid_elem, uint8_t*, "g_valid_elem", n);
-    NTS_LAUNCH(k_g_valid_scatter, dim3(nb), dim3(256), 0, ctx->stream, d_idx2, d_valid, n, d_valid_elem);
-    if (int rc = (*hook)(ctx, n, d_valid_elem, d_asm, d_rec, d_pos, d_list)) return rc;
-  }
-  {
-    ScopedTimer t(ctx, "graph_build");
-    // C2a
-    NTS_LAUNCH(k_g_common, dim3(nb), dim3(256), 0, ctx->stream, d_h2, d_valid, n, n_asm, d_flag);
-    HIP_TRY(ctx, rocprim::exclusive_scan(d_tmp, tmp_scan, d_flag, d_scan, (uint64_t)0, n, rocprim::plus<uint64_t>(), ctx->stream));
-  }
-  uint64_t last_flag = 0, last_scan = 0;
-  HIP_TRY(ctx, hipMemcpyAsync(&last_flag, d_flag + (n - 1), 8, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(&last_scan, d_scan + (n - 1), 8, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  const uint64_t nv = last_scan + last_flag;
-  G->nv = nv;
-  if (nv == 0) return NTS_OK;
-  NTS_WS(d_vhash, uint64_t*, "g_vhash", nv * 8);
-  NTS_WS(d_orec, uint32_t*, "g_orec", (uint64_t)n_asm * nv * 4);
-  NTS_WS(d_opos, uint64_t*, "g_opos", (uint64_t)n_asm * nv * 8);
-  HIP_TRY(ctx, hipMemsetAsync(d_evid, 0xFF, n * 4, ctx->stream));
-  {
-    ScopedTimer t(ctx, "graph_build");
-    NTS_LAUNCH(k_g_assign, dim3(nb), dim3(256), 0, ctx->stream, d_h2, d_idx2, d_valid, d_flag, d_scan, n, d_asm, d_rec, d_pos, nv,
-                       d_evid, d_vhash, d_orec, d_opos);
-    // survivors in traversal order
-    NTS_LAUNCH(k_g_flag_kept, dim3(nb), dim3(256), 0, ctx->stream, d_evid, n, d_flag);
-    HIP_TRY(ctx, rocprim::exclusive_scan(d_tmp, tmp_scan, d_flag, d_scan, (uint64_t)0, n, rocprim::plus<uint64_t>(), ctx->stream));
-  }
-  const uint64_t m = (uint64_t)n_asm * nv; // every common hash occurs once per assembly
-  NTS_WS(d_cvid, uint32_t*, "g_cvid", (m + 1) * 4);
-  NTS_WS(d_casm, uint32_t*, "g_casm", m * 4);
-  NTS_WS(d_clist, uint32_t*, "g_clist", m * 4);
-  NTS_WS(d_key, uint64_t*, "g_key", m * 8);
-  NTS_WS(d_seq, uint64_t*, "g_seq", m * 8);
-  NTS_WS(d_key2, uint64_t*, "g_key2", m * 8);
-  NTS_WS(d_seq2, uint64_t*, "g_seq2", m * 8);
-  NTS_WS(d_eh, uint64_t*, "g_eh", m * 8);
-  NTS_WS(d_es, uint64_t*, "g_es", (m + 1) * 8);
-  size_t tmp_sort2 = 0, tmp_scan2 = 0;
-  HIP_TRY(ctx, rocprim::radix_sort_pairs(nullptr, tmp_sort2, d_key, d_key2, d_seq, d_seq2, m, 0, 64, ctx->stream));
-  HIP_TRY(ctx, rocprim::exclusive_scan(nullptr, tmp_scan2, d_eh, d_es, (uint64_t)0, m, rocprim::plus<uint64_t>(), ctx->stream));
-  NTS_WS(d_tmp2, void*, "g_tmp2", std::max<size_t>(std::max(tmp_sort2, tmp_scan2), 16));
-  const uint32_t mb = (uint32_t)((m + 255) / 256);
-  {
-    ScopedTimer t(ctx, "graph_build");
-    NTS_LAUNCH(k_g_compact, dim3(nb), dim3(256), 0, ctx->stream, d_evid, d_scan, n, d_asm, d_list, d_cvid, d_casm, d_clist);
-    NTS_LAUNCH(k_g_pairs, dim3(mb), dim3(256), 0, ctx->stream, d_cvid, d_casm, d_clist, m, d_key, d_seq);
-    HIP_TRY(ctx, rocprim::radix_sort_pairs(d_tmp2, tmp_sort2, d_key, d_key2, d_seq, d_seq2, m, 0, 64, ctx->stream));
-    NTS_LAUNCH(k_g_edge_heads, dim3(mb), dim3(256), 0, ctx->stream, d_key2, m, d_eh);
-    HIP_TRY(ctx, rocprim::exclusive_scan(d_tmp2, tmp_scan2, d_eh, d_es, (uint64_t)0, m, rocprim::plus<uint64_t>(), ctx->stream));
-  }
-  HIP_TRY(ctx, hipMemcpyAsync(&last_flag, d_eh + (m - 1), 8, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(&last_scan, d_es + (m - 1), 8, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  const uint64_t ne = last_scan + last_flag;
-  G->ne = ne;
-  NTS_WS(d_eu, uint32_t*, "g_eu", std::max<uint64_t>(ne, 1) * 4);
-  NTS_WS(d_ev, uint32_t*, "g_ev", std::max<uint64_t>(ne, 1) * 4);
-  NTS_WS(d_ew, uint32_t*, "g_ew", std::max<uint64_t>(ne, 1) * 4);
-  NTS_WS(d_ef, uint64_t*, "g_ef", std::max<uint64_t>(ne, 1) * 8);
-  if (ne) {
-    // the unordered edge arrays reuse buffers the pair stage is done with; d_key/d_seq become sort keys again
-    NTS_WS(d_eu0, uint32_t*, "g_eu0", ne * 4);
-    NTS_WS(d_ev0, uint32_t*, "g_ev0", ne * 4);
-    NTS_WS(d_ew0, uint32_t*, "g_ew0", ne * 4);
-    NTS_WS(d_ef0, uint64_t*, "g_ef0", ne * 8);
-    NTS_WS(d_srank, unsigned long long*, "g_srank", nv * 8);
-    size_t tmp_sort3 = 0;
-    HIP_TRY(ctx, rocprim::radix_sort_pairs(nullptr, tmp_sort3, d_key, d_key2, d_seq, d_seq2, ne, 0, 64, ctx->stream));
-    NTS_WS(d_tmp3, void*, "g_tmp3", std::max<size_t>(tmp_sort3, 16));
-    const uint32_t eb = (uint32_t)((ne + 255) / 256);
-    ScopedTimer t(ctx, "graph_build");
-    NTS_LAUNCH(k_g_edges, dim3(mb), dim3(256), 0, ctx->stream, d_key2, d_seq2, d_eh, d_es, m, d_cvid, d_eu0, d_ev0, d_ew0, d_ef0);
-    HIP_TRY(ctx, hipMemsetAsync(d_srank, 0xFF, nv * 8, ctx->stream));
-    NTS_LAUNCH(k_g_src_rank, dim3(eb), dim3(256), 0, ctx->stream, d_eu0, d_ef0, ne, d_srank);
-    NTS_LAUNCH(k_g_order_keys, dim3(eb), dim3(256), 0, ctx->stream, d_eu0, d_ef0, ne, d_srank, d_key, d_seq);
-    HIP_TRY(ctx, rocprim::radix_sort_pairs(d_tmp3, tmp_sort3, d_key, d_key2, d_seq, d_seq2, ne, 0, 64, ctx->stream));
-    NTS_LAUNCH(k_g_permute_edges, dim3(eb), dim3(256), 0, ctx->stream, d_seq2, ne, d_eu0, d_ev0, d_ew0, d_ef0, d_eu, d_ev, d_ew, d_ef);
-  }
-  HIP_TRY(ctx, hipGetLastError());
-  G->v_hash = d_vhash;
-  G->occ_rec = d_orec;
-  G->occ_pos = d_opos;
-  G->e_u = d_eu;
-  G->e_v = d_ev;
-  G->e_w = d_ew;
-  G->e_first = d_ef;
-  return NTS_OK;
-}
-
-// ---- the build in hash-range slices (when the one-pass sorts do not fit the scratch budget) --------------------------------------
+// ---- the build: three passes, each over a list of key ranges (slices) ------------------------------------------------------------
 // Vertex ids are ranks in ascending hash order.  The elements whose hashes fall into one contiguous range of hash values are
 // deduplicated, intersected and numbered on their own: the slices, taken in range order and numbered on from the vertices of the
-// slices before them, give the one-pass build's vertices.  A slice holds whole hash values (k_g_valid / k_g_common look at the
-// neighbours with an equal hash).  Edges are sliced by their smaller end (the pair key's upper half) and the dict-order sort by the
-// rank of the edge's source: both keys order the whole, so the slices' results, one after the other, are the one-pass order.
-// What stays n-sized: the input columns (g_h, g_idx, g_asm, g_rec, g_pos, g_keep, g_list: 45 B per element), the elements' vertex
-// ids (g_evid, 4 B), the valid mask the refinement hook reads (g_valid_elem, 1 B) and the hook's own scan (16 B, released before the
-// edge pass).  Survivor-sized: the survivors' columns (12 B), the unordered edges (20 B per adjacent pair) and the results.
-// Everything else is sized to the largest slice and given back at the end of the build.
+// slices before them, give the vertices.  A slice holds whole hash values (k_g_valid / k_g_common look at the neighbours with an
+// equal hash).  Edges are sliced by their smaller end (the pair key's upper half) and the dict-order sort by the rank of the edge's
+// source: both keys order the whole, so the slices' results, one after the other, are in order.
+// When the slice buffers of all n elements fit the budget, each pass has one range that holds every item: its members are the
+// numbers 0 .. count-1 as they stand, so nothing is counted or selected to plan it, and its buffers stay cached on the context.
+// What stays n-sized: the input columns (g_h, g_asm, g_rec, g_pos, g_keep, g_list: 29 B per element), the elements' vertex ids
+// (g_evid, 4 B), the valid mask the refinement hook reads (g_valid_elem, 1 B) and the hook's own scan (16 B).  Survivor-sized: the
+// survivors' columns (12 B), the unordered edges (20 B per edge; sized by the adjacent pairs when there are several ranges) and the
+// results.  Everything else is sized to the largest slice; a build of several ranges gives that and the survivor-sized
+// intermediates back at its end, and the hook's scan before its edge pass.
 
 constexpr uint32_t HIST_BINS = 65536;
 constexpr uint32_t HIST_CHUNK = 65535; // elements one workgroup counts: a bin's count fits the 16-bit half of an LDS word
@@ -362,7 +175,7 @@ __global__ __launch_bounds__(256) void k_g_hist(Key key, uint64_t n, unsigned lo
   }
 }
 
-// k_g_pairs' key of survivor c
+// adjacent survivors c, c + 1 of one list -> the edge occurrence's canonical key (smaller end in the upper half); others get ~0
 __device__ inline uint64_t g_pair_key(const uint32_t* c_vid, const uint32_t* c_asm, const uint32_t* c_list, uint64_t m, uint64_t c)
 {
   if (c + 1 < m && c_asm[c] == c_asm[c + 1] && c_list[c] == c_list[c + 1]) {
@@ -444,7 +257,7 @@ __global__ __launch_bounds__(256) void k_g_gather_h(const uint64_t* __restrict__
   if (i < ns) out[i] = h[idx[i]];
 }
 
-// k_g_assign's numbering within one slice: every valid element of a common group gets vid_off + the group's rank in the slice
+// vid_scan = exclusive scan of head_common: every valid element of a common group gets vid_off + the group's rank in the slice
 __global__ __launch_bounds__(256) void k_g_slice_vid(const uint64_t* __restrict__ h_sorted, const uint64_t* __restrict__ idx_sorted,
                                                      const uint8_t* __restrict__ valid, const uint64_t* __restrict__ head_common,
                                                      const uint64_t* __restrict__ vid_scan, uint64_t ns, uint64_t vid_off,
@@ -459,7 +272,7 @@ __global__ __launch_bounds__(256) void k_g_slice_vid(const uint64_t* __restrict_
     if (valid[j]) elem_vid[idx_sorted[j]] = vid;
 }
 
-// the rest of k_g_assign once every slice is numbered: each element with a vertex writes its hash and its occurrence
+// once every slice is numbered: each element with a vertex writes its hash and its occurrence
 __global__ __launch_bounds__(256) void k_g_vertex_tables(const uint32_t* __restrict__ elem_vid, uint64_t n, const uint64_t* __restrict__ h,
                                                          const uint32_t* __restrict__ asm_of, const uint32_t* __restrict__ rec,
                                                          const uint64_t* __restrict__ pos, uint64_t nv, uint64_t* __restrict__ v_hash,
@@ -486,12 +299,13 @@ __global__ __launch_bounds__(256) void k_g_gather_survivors(const uint64_t* __re
   c_list[c] = list_id[e];
 }
 
+// sort keys of a slice's members; a null member list stands for the numbers 0 .. ms-1 (the range that holds every item)
 __global__ __launch_bounds__(256) void k_g_gather_pairs(const uint64_t* __restrict__ seq, uint64_t ms, const uint32_t* __restrict__ c_vid,
                                                         const uint32_t* __restrict__ c_asm, const uint32_t* __restrict__ c_list, uint64_t m,
                                                         uint64_t* __restrict__ key)
 {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < ms) key[i] = g_pair_key(c_vid, c_asm, c_list, m, seq[i]);
+  if (i < ms) key[i] = g_pair_key(c_vid, c_asm, c_list, m, seq ? seq[i] : i);
 }
 
 __global__ __launch_bounds__(256) void k_g_gather_order(const uint64_t* __restrict__ idx, uint64_t ns, const uint32_t* __restrict__ e_u,
@@ -500,7 +314,7 @@ __global__ __launch_bounds__(256) void k_g_gather_order(const uint64_t* __restri
 {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= ns) return;
-  const uint64_t e = idx[i];
+  const uint64_t e = idx ? idx[i] : i;
   key[i] = ((uint64_t)src_rank[e_u[e]] << 32) | e_first[e];
 }
 
@@ -523,9 +337,7 @@ void graph_sample_peak(nts_ctx* ctx)
   if (now > ctx->graph_live0) ctx->last_graph_peak = std::max(ctx->last_graph_peak, now - ctx->graph_live0);
 }
 
-// the one-pass build's sort and scan buffers, and this path's slice buffers
-const char* const ONE_PASS_SCRATCH[] = { "g_h2", "g_idx2", "g_valid", "g_flag", "g_scan", "g_tmp", "g_key", "g_seq", "g_key2", "g_seq2",
-                                         "g_eh", "g_es", "g_tmp2", "g_tmp3" };
+// the buffers sized to a slice, and the planning's
 const char* const SLICE_SCRATCH[] = { "gs_h", "gs_idx", "gs_h2", "gs_idx2", "gs_valid", "gs_flag", "gs_scan", "gs_tmp", "gs_sel_tmp", "gs_cnt",
                                       "gs_hist" };
 
@@ -583,18 +395,8 @@ int slice_select(nts_ctx* ctx, Pred pred, uint64_t n, uint64_t* d_out)
   return NTS_OK;
 }
 
-// the last flag plus the last entry of its exclusive scan: how many were flagged
-int flag_count(nts_ctx* ctx, const uint64_t* flag, const uint64_t* scan, uint64_t n, uint64_t* count)
-{
-  uint64_t a = 0, b = 0;
-  HIP_TRY(ctx, hipMemcpyAsync(&a, flag + (n - 1), 8, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(&b, scan + (n - 1), 8, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  *count = a + b;
-  return NTS_OK;
-}
-
-// the slice buffers, for slices of up to `ns` items (one set serves the vertex, pair and order passes)
+// the slice buffers, for slices of up to `ns` items (one set serves the vertex, pair and order passes).  h / idx hold a slice's keys
+// and members where they are gathered: not for the vertex range that holds every element, which sorts the hash column as it stands
 struct SliceBufs
 {
   uint64_t *h, *idx, *h2, *idx2, *flag, *scan;
@@ -602,21 +404,61 @@ struct SliceBufs
   void* tmp;
   size_t tmp_sort, tmp_scan;
 };
-int slice_bufs(nts_ctx* ctx, uint64_t ns, SliceBufs* b)
+int slice_bufs(nts_ctx* ctx, uint64_t ns, bool gathered, SliceBufs* b)
 {
   ns = std::max<uint64_t>(ns, 1);
-  NTS_WS(h, uint64_t*, "gs_h", ns * 8);
-  NTS_WS(idx, uint64_t*, "gs_idx", ns * 8);
+  uint64_t *h = nullptr, *idx = nullptr;
+  if (gathered) {
+    h = (uint64_t*)ws_get(ctx, "gs_h", ns * 8);
+    idx = (uint64_t*)ws_get(ctx, "gs_idx", ns * 8);
+    if (!h || !idx) return NTS_ENOMEM;
+  }
   NTS_WS(h2, uint64_t*, "gs_h2", ns * 8);
   NTS_WS(idx2, uint64_t*, "gs_idx2", ns * 8);
   NTS_WS(flag, uint64_t*, "gs_flag", ns * 8);
   NTS_WS(scan, uint64_t*, "gs_scan", ns * 8);
   NTS_WS(valid, uint8_t*, "gs_valid", ns);
   size_t tmp_sort = 0, tmp_scan = 0;
-  HIP_TRY(ctx, rocprim::radix_sort_pairs(nullptr, tmp_sort, h, h2, idx, idx2, ns, 0, 64, ctx->stream));
+  HIP_TRY(ctx, rocprim::radix_sort_pairs(nullptr, tmp_sort, (uint64_t*)nullptr, h2, (uint64_t*)nullptr, idx2, ns, 0, 64, ctx->stream));
   HIP_TRY(ctx, rocprim::exclusive_scan(nullptr, tmp_scan, flag, scan, (uint64_t)0, ns, rocprim::plus<uint64_t>(), ctx->stream));
   NTS_WS(tmp, void*, "gs_tmp", std::max<size_t>(std::max(tmp_sort, tmp_scan), 16));
   *b = { h, idx, h2, idx2, flag, scan, valid, tmp, tmp_sort, tmp_scan };
+  return NTS_OK;
+}
+
+// stable sort of a slice's (key, member) pairs into b.h2 / b.idx2 (the inputs are left alone); a null member list stands for the
+// numbers 0 .. ns-1
+int slice_sort(nts_ctx* ctx, const SliceBufs& b, const uint64_t* keys, const uint64_t* members, uint64_t ns)
+{
+  size_t tmp = b.tmp_sort;
+  if (members)
+    HIP_TRY(ctx, rocprim::radix_sort_pairs(b.tmp, tmp, keys, b.h2, members, b.idx2, ns, 0, 64, ctx->stream));
+  else
+    HIP_TRY(ctx, rocprim::radix_sort_pairs(b.tmp, tmp, keys, b.h2, rocprim::make_counting_iterator<uint64_t>(0), b.idx2, ns, 0, 64, ctx->stream));
+  return NTS_OK;
+}
+
+int slice_scan(nts_ctx* ctx, const SliceBufs& b, uint64_t ns)
+{
+  size_t tmp = b.tmp_scan;
+  HIP_TRY(ctx, rocprim::exclusive_scan(b.tmp, tmp, b.flag, b.scan, (uint64_t)0, ns, rocprim::plus<uint64_t>(), ctx->stream));
+  return NTS_OK;
+}
+
+// the four edge columns for `ne` edges: the pair pass's, in key order ("g_eu0" ...), or the results in dict order ("g_eu" ...)
+struct EdgeCols
+{
+  uint32_t *u, *v, *w;
+  uint64_t* first;
+};
+int edge_cols(nts_ctx* ctx, bool ordered, uint64_t ne, EdgeCols* e)
+{
+  ne = std::max<uint64_t>(ne, 1);
+  NTS_WS(u, uint32_t*, ordered ? "g_eu" : "g_eu0", ne * 4);
+  NTS_WS(v, uint32_t*, ordered ? "g_ev" : "g_ev0", ne * 4);
+  NTS_WS(w, uint32_t*, ordered ? "g_ew" : "g_ew0", ne * 4);
+  NTS_WS(first, uint64_t*, ordered ? "g_ef" : "g_ef0", ne * 8);
+  *e = { u, v, w, first };
   return NTS_OK;
 }
 
@@ -637,10 +479,14 @@ uint32_t bin_shift(uint64_t limit)
 
 constexpr uint32_t MAX_REFINED_BINS = 16; // top-16-bit bins over the cap split again on the next 16 bits (one pass over n each)
 
-// `cap`: items per slice
-int graph_build_sliced(nts_ctx* ctx, uint32_t n_asm, uint64_t n, GraphDev* G, ListHook* hook, uint64_t cap)
+// The three passes.  Expects the concatenated elements (assembly-major) in the scratch buffers g_h / g_rec / g_pos / g_keep / g_list /
+// g_asm (filled by the callers below); leaves the graph in scratch and describes it in `G`.  `cap`: items per slice; with n <= cap
+// every pass has the one range that holds all its items (survivors and edges are no more than n).
+int graph_build_ranges(nts_ctx* ctx, uint32_t n_asm, uint64_t n, GraphDev* G, ListHook* hook, uint64_t cap)
 {
-  for (const char* nm : ONE_PASS_SCRATCH) ws_drop(ctx, nm); // (what an earlier one-pass build on this context left)
+  const bool sliced = n > cap;
+  if (sliced)
+    for (const char* nm : SLICE_SCRATCH) ws_drop(ctx, nm); // (what an earlier build that fitted left, sized for all its elements)
   NTS_WS(d_h, uint64_t*, "g_h", n * 8);
   NTS_WS(d_asm, uint32_t*, "g_asm", n * 4);
   NTS_WS(d_rec, uint32_t*, "g_rec", n * 4);
@@ -656,39 +502,50 @@ int graph_build_sliced(nts_ctx* ctx, uint32_t n_asm, uint64_t n, GraphDev* G, Li
   HIP_TRY(ctx, hipMemsetAsync(d_evid, 0xFF, n * 4, ctx->stream));
   // ---- plan: the top 16 bits of the hash; a bin over the cap is split on the next 16 bits (the first few such bins)
   uint32_t oversize = 0, refined = 0, top_over = 0;
-  std::vector<uint64_t> hist;
-  if (int rc = slice_hist(ctx, HashBin{ d_h, 0, ~0ULL, 48 }, n, &hist)) return rc;
-  std::vector<KeyRange> top, vr;
-  slice_ranges(hist, cap, 0, 48, &top, &top_over);
-  for (const KeyRange& r : top) {
-    if (r.n > cap && r.hi - r.lo == (1ULL << 48) - 1 && refined < MAX_REFINED_BINS) {
-      ++refined;
-      std::vector<uint64_t> sub;
-      if (int rc = slice_hist(ctx, HashBin{ d_h, r.lo, r.hi, 32 }, n, &sub)) return rc;
-      slice_ranges(sub, cap, r.lo, 32, &vr, &oversize);
-    } else {
-      if (r.n > cap) ++oversize;
-      vr.push_back(r);
+  std::vector<KeyRange> vr;
+  if (sliced) {
+    std::vector<uint64_t> hist;
+    if (int rc = slice_hist(ctx, HashBin{ d_h, 0, ~0ULL, 48 }, n, &hist)) return rc;
+    std::vector<KeyRange> top;
+    slice_ranges(hist, cap, 0, 48, &top, &top_over);
+    for (const KeyRange& r : top) {
+      if (r.n > cap && r.hi - r.lo == (1ULL << 48) - 1 && refined < MAX_REFINED_BINS) {
+        ++refined;
+        std::vector<uint64_t> sub;
+        if (int rc = slice_hist(ctx, HashBin{ d_h, r.lo, r.hi, 32 }, n, &sub)) return rc;
+        slice_ranges(sub, cap, r.lo, 32, &vr, &oversize);
+      } else {
+        if (r.n > cap) ++oversize;
+        vr.push_back(r);
+      }
     }
+  } else {
+    vr.push_back({ 0, ~0ULL, n });
   }
   // ---- vertices, slice by slice
   SliceBufs b;
-  if (int rc = slice_bufs(ctx, max_range(vr), &b)) return rc;
+  if (int rc = slice_bufs(ctx, max_range(vr), sliced, &b)) return rc;
   uint64_t nv = 0;
   for (const KeyRange& r : vr) {
     const uint64_t ns = r.n;
     const uint32_t sb = (uint32_t)((ns + 255) / 256);
-    if (int rc = slice_select(ctx, HashIn{ d_h, r.lo, r.hi }, n, b.idx)) return rc;
+    const uint64_t* members = nullptr;
+    if (sliced) {
+      if (int rc = slice_select(ctx, HashIn{ d_h, r.lo, r.hi }, n, b.idx)) return rc;
+      members = b.idx;
+    }
     {
       ScopedTimer t(ctx, "graph_build");
-      NTS_LAUNCH(k_g_gather_h, dim3(sb), dim3(256), 0, ctx->stream, b.idx, ns, d_h, b.h);
-      HIP_TRY(ctx, rocprim::radix_sort_pairs(b.tmp, b.tmp_sort, b.h, b.h2, b.idx, b.idx2, ns, 0, 64, ctx->stream));
+      if (members) {
+        NTS_LAUNCH(k_g_gather_h, dim3(sb), dim3(256), 0, ctx->stream, members, ns, d_h, b.h);
+      }
+      if (int rc = slice_sort(ctx, b, members ? b.h : d_h, members, ns)) return rc;
       NTS_LAUNCH(k_g_valid, dim3(sb), dim3(256), 0, ctx->stream, b.h2, b.idx2, d_asm, d_keep, ns, b.valid);
       if (hook) {
         NTS_LAUNCH(k_g_valid_scatter, dim3(sb), dim3(256), 0, ctx->stream, b.idx2, b.valid, ns, d_valid_elem);
       }
       NTS_LAUNCH(k_g_common, dim3(sb), dim3(256), 0, ctx->stream, b.h2, b.valid, ns, n_asm, b.flag);
-      HIP_TRY(ctx, rocprim::exclusive_scan(b.tmp, b.tmp_scan, b.flag, b.scan, (uint64_t)0, ns, rocprim::plus<uint64_t>(), ctx->stream));
+      if (int rc = slice_scan(ctx, b, ns)) return rc;
       NTS_LAUNCH(k_g_slice_vid, dim3(sb), dim3(256), 0, ctx->stream, b.h2, b.idx2, b.valid, b.flag, b.scan, ns, nv, d_evid);
     }
     uint64_t nv_s = 0;
@@ -699,12 +556,15 @@ int graph_build_sliced(nts_ctx* ctx, uint32_t n_asm, uint64_t n, GraphDev* G, Li
   G->nv = nv;
   const uint64_t n_vslices = vr.size();
   // The hook rewrites list ids only (RefineHook: d_list from the valid mask, records and positions), and the vertex pass does not
-  // read them: it runs once, after the last slice.  Its n-sized scan buffers and the slice buffers are not live at the same time.
+  // read them: it runs once, after the last slice.  A sliced build keeps the hook's n-sized scan buffers and the slice buffers from
+  // being live at the same time.
   if (hook) {
-    for (const char* nm : SLICE_SCRATCH) ws_drop(ctx, nm);
+    if (sliced)
+      for (const char* nm : SLICE_SCRATCH) ws_drop(ctx, nm);
     if (int rc = (*hook)(ctx, n, d_valid_elem, d_asm, d_rec, d_pos, d_list)) return rc;
     graph_sample_peak(ctx);
-    for (const char* nm : { "e_hook_a", "e_hook_b", "e_scan_tmp" }) ws_drop(ctx, nm);
+    if (sliced)
+      for (const char* nm : { "e_hook_a", "e_hook_b", "e_scan_tmp" }) ws_drop(ctx, nm);
   }
   uint64_t n_eslices = 1;
   if (nv) {
@@ -731,44 +591,54 @@ int graph_build_sliced(nts_ctx* ctx, uint32_t n_asm, uint64_t n, GraphDev* G, Li
     G->v_hash = d_vhash;
     G->occ_rec = d_orec;
     G->occ_pos = d_opos;
-    // ---- edges: the pair keys in ranges of their smaller end
-    std::vector<uint64_t> ph;
-    const uint32_t ushift = bin_shift(nv);
-    if (int rc = slice_hist(ctx, PairBin{ d_cvid, d_casm, d_clist, m, ushift }, m, &ph)) return rc;
-    uint64_t n_pairs = 0;
-    for (uint64_t x : ph) n_pairs += x;
+    // ---- edges: the pair keys in ranges of their smaller end.  The histogram that plans the ranges counts the adjacent pairs, which
+    // bound the edges; the one range of a build that fits has none and sizes the edge columns by its own count.
     std::vector<KeyRange> er;
-    slice_ranges(ph, cap, 0, ushift, &er, &oversize);
-    NTS_WS(d_eu0, uint32_t*, "g_eu0", std::max<uint64_t>(n_pairs, 1) * 4);
-    NTS_WS(d_ev0, uint32_t*, "g_ev0", std::max<uint64_t>(n_pairs, 1) * 4);
-    NTS_WS(d_ew0, uint32_t*, "g_ew0", std::max<uint64_t>(n_pairs, 1) * 4);
-    NTS_WS(d_ef0, uint64_t*, "g_ef0", std::max<uint64_t>(n_pairs, 1) * 8);
-    if (int rc = slice_bufs(ctx, max_range(er), &b)) return rc;
+    EdgeCols eu0 = {};
+    if (sliced) {
+      std::vector<uint64_t> ph;
+      const uint32_t ushift = bin_shift(nv);
+      if (int rc = slice_hist(ctx, PairBin{ d_cvid, d_casm, d_clist, m, ushift }, m, &ph)) return rc;
+      uint64_t n_pairs = 0;
+      for (uint64_t x : ph) n_pairs += x;
+      slice_ranges(ph, cap, 0, ushift, &er, &oversize);
+      if (int rc = edge_cols(ctx, false, n_pairs, &eu0)) return rc;
+    } else {
+      er.push_back({ 0, ~0ULL, m });
+    }
+    if (int rc = slice_bufs(ctx, max_range(er), true, &b)) return rc;
     graph_sample_peak(ctx);
     uint64_t ne = 0;
     for (const KeyRange& r : er) {
       const uint64_t ms = r.n;
       const uint32_t sb = (uint32_t)((ms + 255) / 256);
-      if (int rc = slice_select(ctx, PairIn{ d_cvid, d_casm, d_clist, m, r.lo, r.hi }, m, b.idx)) return rc;
+      const uint64_t* members = nullptr;
+      if (sliced) {
+        if (int rc = slice_select(ctx, PairIn{ d_cvid, d_casm, d_clist, m, r.lo, r.hi }, m, b.idx)) return rc;
+        members = b.idx;
+      }
       {
         ScopedTimer t(ctx, "graph_build");
-        NTS_LAUNCH(k_g_gather_pairs, dim3(sb), dim3(256), 0, ctx->stream, b.idx, ms, d_cvid, d_casm, d_clist, m, b.h);
-        HIP_TRY(ctx, rocprim::radix_sort_pairs(b.tmp, b.tmp_sort, b.h, b.h2, b.idx, b.idx2, ms, 0, 64, ctx->stream));
+        NTS_LAUNCH(k_g_gather_pairs, dim3(sb), dim3(256), 0, ctx->stream, members, ms, d_cvid, d_casm, d_clist, m, b.h);
+        if (int rc = slice_sort(ctx, b, b.h, members, ms)) return rc;
         NTS_LAUNCH(k_g_edge_heads, dim3(sb), dim3(256), 0, ctx->stream, b.h2, ms, b.flag);
-        HIP_TRY(ctx, rocprim::exclusive_scan(b.tmp, b.tmp_scan, b.flag, b.scan, (uint64_t)0, ms, rocprim::plus<uint64_t>(), ctx->stream));
-        NTS_LAUNCH(k_g_edges, dim3(sb), dim3(256), 0, ctx->stream, b.h2, b.idx2, b.flag, b.scan, ms, d_cvid, d_eu0 + ne, d_ev0 + ne, d_ew0 + ne,
-                           d_ef0 + ne);
+        if (int rc = slice_scan(ctx, b, ms)) return rc;
       }
       uint64_t ne_s = 0;
       if (int rc = flag_count(ctx, b.flag, b.scan, ms, &ne_s)) return rc;
+      if (!sliced)
+        if (int rc = edge_cols(ctx, false, ne_s, &eu0)) return rc;
+      {
+        ScopedTimer t(ctx, "graph_build");
+        NTS_LAUNCH(k_g_edges, dim3(sb), dim3(256), 0, ctx->stream, b.h2, b.idx2, b.flag, b.scan, ms, d_cvid, eu0.u + ne, eu0.v + ne, eu0.w + ne,
+                           eu0.first + ne);
+      }
       ne += ne_s;
     }
     G->ne = ne;
     n_eslices = std::max<uint64_t>(er.size(), 1);
-    NTS_WS(d_eu, uint32_t*, "g_eu", std::max<uint64_t>(ne, 1) * 4);
-    NTS_WS(d_ev, uint32_t*, "g_ev", std::max<uint64_t>(ne, 1) * 4);
-    NTS_WS(d_ew, uint32_t*, "g_ew", std::max<uint64_t>(ne, 1) * 4);
-    NTS_WS(d_ef, uint64_t*, "g_ef", std::max<uint64_t>(ne, 1) * 8);
+    EdgeCols eu;
+    if (int rc = edge_cols(ctx, true, ne, &eu)) return rc;
     if (ne) {
       // ---- ntJoin's dict order, sorted in ranges of the source's rank
       NTS_WS(d_srank, unsigned long long*, "g_srank", nv * 8);
@@ -776,39 +646,50 @@ int graph_build_sliced(nts_ctx* ctx, uint32_t n_asm, uint64_t n, GraphDev* G, Li
       {
         ScopedTimer t(ctx, "graph_build");
         HIP_TRY(ctx, hipMemsetAsync(d_srank, 0xFF, nv * 8, ctx->stream));
-        NTS_LAUNCH(k_g_src_rank, dim3(eb), dim3(256), 0, ctx->stream, d_eu0, d_ef0, ne, d_srank);
+        NTS_LAUNCH(k_g_src_rank, dim3(eb), dim3(256), 0, ctx->stream, eu0.u, eu0.first, ne, d_srank);
       }
-      std::vector<uint64_t> rh;
-      const uint32_t rshift = bin_shift(m); // (a rank is the sequence number of a pair: below m)
-      if (int rc = slice_hist(ctx, RankBin{ d_eu0, d_srank, rshift }, ne, &rh)) return rc;
       std::vector<KeyRange> orr;
-      slice_ranges(rh, cap, 0, rshift, &orr, &oversize);
+      if (sliced) {
+        std::vector<uint64_t> rh;
+        const uint32_t rshift = bin_shift(m); // (a rank is the sequence number of a pair: below m)
+        if (int rc = slice_hist(ctx, RankBin{ eu0.u, d_srank, rshift }, ne, &rh)) return rc;
+        slice_ranges(rh, cap, 0, rshift, &orr, &oversize);
+      } else {
+        orr.push_back({ 0, ~0ULL, ne });
+      }
       n_eslices = std::max<uint64_t>(n_eslices, orr.size());
-      if (int rc = slice_bufs(ctx, max_range(orr), &b)) return rc;
+      if (int rc = slice_bufs(ctx, max_range(orr), true, &b)) return rc;
       graph_sample_peak(ctx);
       uint64_t off = 0;
       for (const KeyRange& r : orr) {
         const uint64_t ns = r.n;
         const uint32_t sb = (uint32_t)((ns + 255) / 256);
-        if (int rc = slice_select(ctx, RankIn{ d_eu0, d_srank, r.lo, r.hi }, ne, b.idx)) return rc;
+        const uint64_t* members = nullptr;
+        if (sliced) {
+          if (int rc = slice_select(ctx, RankIn{ eu0.u, d_srank, r.lo, r.hi }, ne, b.idx)) return rc;
+          members = b.idx;
+        }
         ScopedTimer t(ctx, "graph_build");
-        NTS_LAUNCH(k_g_gather_order, dim3(sb), dim3(256), 0, ctx->stream, b.idx, ns, d_eu0, d_ef0, d_srank, b.h);
-        HIP_TRY(ctx, rocprim::radix_sort_pairs(b.tmp, b.tmp_sort, b.h, b.h2, b.idx, b.idx2, ns, 0, 64, ctx->stream));
-        NTS_LAUNCH(k_g_permute_edges, dim3(sb), dim3(256), 0, ctx->stream, b.idx2, ns, d_eu0, d_ev0, d_ew0, d_ef0, d_eu + off, d_ev + off,
-                           d_ew + off, d_ef + off);
+        NTS_LAUNCH(k_g_gather_order, dim3(sb), dim3(256), 0, ctx->stream, members, ns, eu0.u, eu0.first, d_srank, b.h);
+        if (int rc = slice_sort(ctx, b, b.h, members, ns)) return rc;
+        NTS_LAUNCH(k_g_permute_edges, dim3(sb), dim3(256), 0, ctx->stream, b.idx2, ns, eu0.u, eu0.v, eu0.w, eu0.first, eu.u + off, eu.v + off,
+                           eu.w + off, eu.first + off);
         off += ns;
       }
     }
-    G->e_u = d_eu;
-    G->e_v = d_ev;
-    G->e_w = d_ew;
-    G->e_first = d_ef;
+    G->e_u = eu.u;
+    G->e_v = eu.v;
+    G->e_w = eu.w;
+    G->e_first = eu.first;
   }
   HIP_TRY(ctx, hipGetLastError());
   graph_sample_peak(ctx);
-  // the slice buffers and the survivor-sized intermediates do not stay cached into the caller's table growth
-  for (const char* nm : SLICE_SCRATCH) ws_drop(ctx, nm);
-  for (const char* nm : { "g_eu0", "g_ev0", "g_ew0", "g_ef0", "g_srank", "g_cvid", "g_casm", "g_clist" }) ws_drop(ctx, nm);
+  // a build that fits leaves its buffers cached for the next one on this context; the slice buffers and the survivor-sized
+  // intermediates of a sliced one do not stay cached into the caller's table growth
+  if (sliced) {
+    for (const char* nm : SLICE_SCRATCH) ws_drop(ctx, nm);
+    for (const char* nm : { "g_eu0", "g_ev0", "g_ew0", "g_ef0", "g_srank", "g_cvid", "g_casm", "g_clist" }) ws_drop(ctx, nm);
+  }
   ctx->last_graph_v_slices = (uint32_t)n_vslices;
   ctx->last_graph_e_slices = (uint32_t)n_eslices;
   ctx->last_graph_oversize = oversize;
@@ -835,7 +716,7 @@ uint64_t graph_auto_budget(uint64_t n, bool hook)
   size_t fr = 0, tot = 0;
   if (hipMemGetInfo(&fr, &tot) != hipSuccess) {
     (void)hipGetLastError();
-    return ~0ULL; // (cannot tell: one pass, as before)
+    return ~0ULL; // (cannot tell: one range)
   }
   uint64_t cached = 0;
   {
@@ -848,8 +729,8 @@ uint64_t graph_auto_budget(uint64_t n, bool hook)
   return avail > margin + kept ? avail - margin - kept : 1;
 }
 
-// The build proper: in one pass when the slice scratch of all n elements fits the budget (every build that fitted before takes the
-// launch sequence it always took), in hash-range slices otherwise.  The same graph either way.
+// The build proper: slices of budget / slice_bytes_per_item items; a build whose elements all fit one slice has one range per pass
+// and plans nothing.  The same graph either way.
 int graph_build_core(nts_ctx* ctx, uint32_t n_asm, uint64_t n, GraphDev* G, ListHook* hook)
 {
   *G = GraphDev();
@@ -860,14 +741,10 @@ int graph_build_core(nts_ctx* ctx, uint32_t n_asm, uint64_t n, GraphDev* G, List
   if (n == 0) return NTS_OK;
   const uint64_t per_item = slice_bytes_per_item(ctx, n);
   const uint64_t budget = ctx->graph_budget ? ctx->graph_budget : graph_auto_budget(n, hook != nullptr);
-  if (budget / per_item >= n) {
-    const int rc = graph_build_one_pass(ctx, n_asm, n, G, hook);
-    graph_sample_peak(ctx);
-    return rc;
-  }
-  const int rc = graph_build_sliced(ctx, n_asm, n, G, hook, budget / per_item);
-  if (rc == NTS_ENOMEM)
-    ctx->err += " (graph build in slices: budget " + std::to_string(budget) + " B, " + std::to_string(budget / per_item) + " minimizers per slice)";
+  const uint64_t cap = budget / per_item;
+  const int rc = graph_build_ranges(ctx, n_asm, n, G, hook, cap);
+  if (rc == NTS_ENOMEM && n > cap)
+    ctx->err += " (graph build in slices: budget " + std::to_string(budget) + " B, " + std::to_string(cap) + " minimizers per slice)";
   return rc;
 }
 
@@ -875,7 +752,6 @@ int graph_build_core(nts_ctx* ctx, uint32_t n_asm, uint64_t n, GraphDev* G, List
 struct GraphIn
 {
   uint64_t* h = nullptr;
-  uint64_t* idx = nullptr;
   uint32_t* asm_id = nullptr;
   uint32_t* rec = nullptr;
   uint64_t* pos = nullptr;
@@ -887,13 +763,12 @@ int graph_inputs(nts_ctx* ctx, uint64_t n, GraphIn* in)
 {
   const uint64_t c = std::max<uint64_t>(n, 1);
   in->h = (uint64_t*)ws_get(ctx, "g_h", c * 8);
-  in->idx = (uint64_t*)ws_get(ctx, "g_idx", c * 8);
   in->asm_id = (uint32_t*)ws_get(ctx, "g_asm", c * 4);
   in->rec = (uint32_t*)ws_get(ctx, "g_rec", c * 4);
   in->pos = (uint64_t*)ws_get(ctx, "g_pos", c * 8);
   in->keep = (uint8_t*)ws_get(ctx, "g_keep", c);
   in->list = (uint32_t*)ws_get(ctx, "g_list", c * 4);
-  return (in->h && in->idx && in->asm_id && in->rec && in->pos && in->keep && in->list) ? NTS_OK : NTS_ENOMEM;
+  return (in->h && in->asm_id && in->rec && in->pos && in->keep && in->list) ? NTS_OK : NTS_ENOMEM;
 }
 
 } // namespace
@@ -923,8 +798,7 @@ extern "C" int nts_graph_build(nts_ctx* ctx, uint32_t n_asm, const nts_mxlist* l
   if (n == 0) return finish_empty();
   GraphIn in;
   if (graph_inputs(ctx, n, &in) != NTS_OK) return NTS_ENOMEM;
-  // assembly-major concatenation; element numbers and assembly ids are generated on the device (each assembly's range is
-  // one launch), the keep mask is uploaded only where a list brings one
+  // assembly-major concatenation; the assembly ids are filled on the device, the keep mask is uploaded only where a list brings one
   uint64_t o = 0;
   for (uint32_t a = 0; a < n_asm; ++a) {
     const uint64_t m = lists[a].n;
@@ -937,7 +811,7 @@ extern "C" int nts_graph_build(nts_ctx* ctx, uint32_t n_asm, const nts_mxlist* l
         HIP_TRY(ctx, hipMemcpyAsync(in.keep + o, lists[a].keep, m, hipMemcpyHostToDevice, ctx->stream));
       else
         HIP_TRY(ctx, hipMemsetAsync(in.keep + o, 1, m, ctx->stream));
-      NTS_LAUNCH(k_g_number, dim3((uint32_t)((m + 255) / 256)), dim3(256), 0, ctx->stream, in.idx + o, in.asm_id + o, m, o, a);
+      HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)(in.asm_id + o), (int)a, m, ctx->stream));
     }
     o += m;
   }

@@ -1,7 +1,7 @@
-"""The graph build in hash-range slices (csrc/nts_graph.hip, graph_build_sliced): forced by a small scratch budget
-(Context.set_graph_budget) it must give the one-pass build's graph bit for bit -- vertices, occurrences, edges in ntJoin's dict
-order -- through nts_graph_build and through the device engine's adds across rounds, in less scratch; with the automatic budget
-the builds that fit take the one pass as before."""
+"""The graph build over key ranges (csrc/nts_graph.hip, graph_build_core): forced into many hash-range slices by a small scratch
+budget (Context.set_graph_budget) it must give the graph of the build with one range per pass bit for bit -- vertices, occurrences,
+edges in ntJoin's dict order -- through nts_graph_build and through the device engine's adds across rounds, in less scratch; with
+the automatic budget the builds that fit have one range, plan nothing and keep their buffers on the context."""
 import os
 
 import numpy as np
@@ -272,8 +272,8 @@ def test_an_existing_edge_keeps_its_slot_with_slicing_forced(ctx, tmp_path):
 
 def test_capacity_sliced_add_peaks_far_below_the_one_pass(tmp_path):
     """Scratch of one nts_engine_add (nts_mem_stats peak over the live bytes before it), each on a fresh context: with the budget an
-    eighth of the one-pass scratch the same add completes, gives the same graph and peaks within the budget plus the arrays that
-    stay n- and survivor-sized (docs/design/04_4_graph_stage.md), well under the one pass."""
+    eighth of the one-range build's scratch the same add completes, gives the same graph and peaks within the budget plus the arrays
+    that stay n- and survivor-sized (docs/design/04_4_graph_stage.md), well under the one-range build."""
     from ntsynt_amd.device import Context, Minimizers
     from ntsynt_amd.synteny_device import DeviceGraph
     rng = np.random.default_rng(11)
@@ -290,7 +290,7 @@ def test_capacity_sliced_add_peaks_far_below_the_one_pass(tmp_path):
     n = G * n_each
     results, peaks = [], []
     budget = None
-    for phase in ("one pass", "sliced"):
+    for phase in ("one range", "sliced"):
         c = Context(0)
         try:
             if phase == "sliced":
@@ -311,7 +311,7 @@ def test_capacity_sliced_add_peaks_far_below_the_one_pass(tmp_path):
                 h.free()
         finally:
             c.close()
-        if phase == "one pass":
+        if phase == "one range":
             assert plan["v_slices"] == 1
             budget = peak // 8
         else:
@@ -334,6 +334,10 @@ def test_automatic_budget_keeps_the_one_pass(ctx, tmp_path):
     build_graph_device(ctx, lists)
     assert ctx.graph_last_plan()["v_slices"] == 1 and ctx.graph_last_plan()["e_slices"] == 1
     assert ctx.graph_last_plan()["oversize"] == 0
+    # a build that fits keeps its scratch on the context: the same build again allocates nothing
+    live = ctx.mem_stats()["live"]
+    build_graph_device(ctx, lists)
+    assert ctx.mem_stats()["live"] == live
 
 
 def test_pipeline_with_graph_budget_writes_the_same_blocks(tmp_path):
