@@ -412,6 +412,28 @@ int nts_hash_all(nts_ctx* ctx, const nts_genome* g, uint32_t k, uint64_t** h0, u
  * Exact (a bottom-s MinHash sketch, the input of the Mash distance in ntsynt_amd/divergence.py); `out` holds s values. */
 int nts_minhash(nts_ctx* ctx, const nts_genome* g, uint32_t k, uint32_t s, uint64_t* out, uint32_t* n_out);
 
+/* ---- assessment of synteny blocks ---------------------------------------------------------------------
+ * The block statistics of the reference's analysis_scripts/denovo_synteny_block_stats.py (README "Basic assessment of synteny
+ * blocks") are host arithmetic over the block table and the .fai files: ntsynt_amd/assess.py block_stats, bin/ntsynt_block_stats.
+ * The two calls below have no counterpart there: they give the Mash distance of `-d auto` (nts_minhash) per block.
+ *
+ * nts_minhash_intervals: the bottom-s sketch of each of n_iv intervals of g in one sweep.  For interval i, out[i * s ..] holds the
+ *   n_out[i] = min(s, distinct) smallest DISTINCT canonical h0, ascending, over the valid k-mers that lie wholly inside
+ *   [start, end) of record rec (start <= p and p + k <= end; end is clipped to the record length); n_kmers[i] (may be NULL) = how
+ *   many such k-mers there are.  Hashing as nts_minhash / nts_hash_all; exact.  Intervals in any order, overlapping, shorter than
+ *   k (an empty sketch).  NTS_EINVAL for a record index out of range.  Any k >= 1; s >= 1.  Memory: at most 256 s bytes of hash
+ *   sets per interval, the intervals taken in chunks of 2 GiB of them (csrc/nts_minhash_iv.inc).
+ * nts_minhash_intervals_stats: of the last call on ctx -- the sweeps of the chunk that took most (1: every threshold held at once),
+ *   the chunks, the sweeps of all chunks (each sweep is one launch of the timer "minhash_iv").
+ * nts_minhash_pairs: sk = n_sketches sketches of s slots each (n_sk[i] <= s of them used, ascending, distinct: as the call above
+ *   returns them), all in host memory.  For pair p of sketches A = pair_a[p], B = pair_b[p]: usize[p] = |bottom-s(A u B)|,
+ *   shared[p] = |bottom-s(A u B) n A n B| -- the two integers of the Mash distance (ntsynt_amd/divergence.py). */
+int nts_minhash_intervals(nts_ctx* ctx, const nts_genome* g, uint32_t k, uint32_t s, const nts_interval* iv, uint64_t n_iv, uint64_t* out,
+                          uint32_t* n_out, uint64_t* n_kmers);
+int nts_minhash_intervals_stats(nts_ctx* ctx, uint32_t* passes, uint32_t* chunks, uint64_t* sweeps);
+int nts_minhash_pairs(nts_ctx* ctx, uint32_t s, const uint64_t* sk, const uint32_t* n_sk, uint64_t n_sketches, const uint64_t* pair_a,
+                      const uint64_t* pair_b, uint64_t n_pairs, uint32_t* shared, uint32_t* usize);
+
 /* ---- C1-C5: minimizer graph -> collinear chains -----------------------------------------------------
  * replaces ntjoin_utils.read_minimizers' duplicate removal, filter_minimizers and build_graph
  * (call sites bin/ntsynt_synteny.py:607-612, 483, 539) and the path walk of Ntjoin.find_paths

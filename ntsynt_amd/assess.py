@@ -1,0 +1,221 @@
+"""Assessment of a run's synteny blocks (`ntSynt --assess`, bin/ntsynt_block_stats).
+
+Two things, both over `<prefix>.synteny_blocks.tsv`:
+
+* block_stats: the one-line summary of the reference's analysis_scripts/denovo_synteny_block_stats.py (README "Basic assessment of
+  synteny blocks"), restated: the same ten columns under the same rules.  Host arithmetic; no GPU, no torch, no numpy.
+* block_divergence: the Mash distance of `-d auto` (ntsynt_amd/divergence.py) per block and pair of its genomes, from bottom-s
+  sketches of the blocks' intervals taken in one sweep per genome (nts_minhash_intervals) and one pair-count call
+  (nts_minhash_pairs); docs/design/04_8_block_assessment.md."""
+import os
+import re
+from collections import namedtuple
+
+K_DEFAULT = 21
+S_DEFAULT = 1000
+
+STATS_COLUMNS = ("Number_blocks", "Number_blocks_all_asm", "Average_coverage", "Average_coverage_all_asm", "Coverage_min_genome_size",
+                 "Average_length", "Median_length", "Total_length", "NG50_length", "N50_length")
+DIVERGENCE_COLUMNS = ("block_id", "genome_a", "genome_b", "distance", "shared_hashes", "sketch_size", "kmers_a", "kmers_b")
+
+# one line of a block table (README "Output files"): the block's interval on `contig` of `genome` is [start, end)
+BlockRow = namedtuple("BlockRow", ["block_id", "genome", "contig", "start", "end", "strand", "minimizers", "reason"])
+
+
+def read_blocks(tsv_path):
+    "the lines of a synteny block table, in file order"
+    rows = []
+    with open(tsv_path, "r", encoding="utf-8") as fh:
+        for line in fh:
+            f = line.strip().split("\t")
+            if len(f) < 5:
+                continue
+            rows.append(BlockRow(f[0], f[1], f[2], int(f[3]), int(f[4]), f[5] if len(f) > 5 else "+", f[6] if len(f) > 6 else "",
+                                 f[7] if len(f) > 7 else ""))
+    return rows
+
+
+def genome_sizes(fai_paths):
+    """{genome name: sum of the .fai's second column}, in the order given.  The name is the base name of the path in front of its
+    `.fai`; a path that does not carry one names no genome (it still counts as an input of the averages)."""
+    sizes = {}
+    for path in fai_paths:
+        m = re.match(r"(\S+).fai", path)
+        if not m:
+            continue
+        total = 0
+        with open(path, "r", encoding="utf-8") as fh:
+            for line in fh:
+                total += int(line.strip().split("\t")[1])
+        sizes[os.path.basename(m.group(1))] = total
+    return sizes
+
+
+def _n50(lengths, against):
+    "the length at which the lengths, longest first, have summed to half of `against` (0 if they never do)"
+    half, run = against * 0.5, 0
+    for v in sorted(lengths, reverse=True):
+        run += v
+        if run >= half:
+            return v
+    return 0
+
+
+def _median(lengths):
+    v = sorted(lengths)
+    mid = len(v) // 2
+    return float(v[mid]) if len(v) % 2 else (v[mid - 1] + v[mid]) / 2.0
+
+
+def block_stats(tsv_path, fai_paths, sizes=None):
+    """The reference's de novo statistics of a block table, as a dict keyed by STATS_COLUMNS.  Every figure is taken per genome of the
+    table and the per-genome figures are summed and divided by the number of .fai files given; "all_asm" counts the blocks present in
+    that many distinct genomes; coverage and NG50 are against the genome's size from its .fai, N50 against the genome's own total
+    block length; the two counts and NG50 / N50 are truncated to integers AFTER the averaging.  sizes: {genome name: bases} of the
+    genomes instead of .fai files (a run that has them at hand)."""
+    n_genomes = len(sizes) if sizes is not None else len(fai_paths)
+    sizes = dict(sizes) if sizes is not None else genome_sizes(fai_paths)
+    lengths = {}            # genome -> [(length, block id)] in file order
+    members = {}            # block id -> genomes that have it
+    for r in read_blocks(tsv_path):
+        lengths.setdefault(r.genome, []).append((r.end - r.start, r.block_id))
+        members.setdefault(r.block_id, set()).add(r.genome)
+    for name in lengths:
+        if name not in sizes:
+            raise ValueError(f"{tsv_path}: no size for genome {name} (have {sorted(sizes)})")
+    in_all = {b for b, gs in members.items() if len(gs) >= n_genomes}
+    every = {g: [v for v, _ in rows] for g, rows in lengths.items()}
+    shared = {g: [v for v, b in rows if b in in_all] for g, rows in lengths.items()}
+
+    def avg(per_genome):
+        return sum(per_genome(g) for g in every) / n_genomes
+
+    smallest = min(sizes, key=lambda g: sizes[g])         # (the first of several of one size, in the order of the .fai files)
+    out = {
+        "Number_blocks": int(avg(lambda g: len(every[g]))),
+        "Number_blocks_all_asm": int(avg(lambda g: len(shared[g]))),
+        "Average_coverage": avg(lambda g: sum(every[g]) / sizes[g] * 100),
+        "Average_coverage_all_asm": avg(lambda g: sum(shared[g]) / sizes[g] * 100),
+        "Coverage_min_genome_size": sum(every[smallest]) / sizes[smallest] * 100,
+        "Average_length": avg(lambda g: sum(every[g]) / len(every[g])),
+        "Median_length": avg(lambda g: _median(every[g])),
+        "Total_length": avg(lambda g: sum(every[g])),
+        "NG50_length": int(avg(lambda g: _n50(every[g], sizes[g]))),
+        "N50_length": int(avg(lambda g: _n50(every[g], sum(every[g])))),
+    }
+    return out
+
+
+def stats_table(stats):
+    "the header line and the statistics line, as the reference prints them"
+    return "\t".join(STATS_COLUMNS) + "\n" + "\t".join(str(stats[c]) for c in STATS_COLUMNS) + "\n"
+
+
+def _block_order(rows):
+    "block ids ascending (numerically where they are numbers), each with the indices of its lines in file order"
+    by_id = {}
+    for i, r in enumerate(rows):
+        by_id.setdefault(r.block_id, []).append(i)
+
+    def key(b):
+        return (0, int(b), "") if b.lstrip("-").isdigit() else (1, 0, b)
+    return [(b, by_id[b]) for b in sorted(by_id, key=key)]
+
+
+def block_divergence(ctx, genomes_by_name, blocks, k=K_DEFAULT, s=S_DEFAULT):
+    """Per block and unordered pair of its genomes the Mash distance of the two intervals.  genomes_by_name: the name in column 2 ->
+    resident device.Genome, or a callable that returns one (it is then freed after its sweep: one genome resident at a time).
+    blocks: read_blocks' rows.  Returns dicts keyed by DIVERGENCE_COLUMNS: block ids ascending, pairs in the order of the block's
+    lines.  One nts_minhash_intervals call per genome, one nts_minhash_pairs call for all pairs; the strand is ignored (the hash is
+    canonical)."""
+    import numpy as np
+    from .divergence import distance_of_counts
+    k, s = int(k), int(s)
+    n = len(blocks)
+    sketches = np.zeros((n, s), dtype=np.uint64)
+    counts = np.zeros(n, dtype=np.uint32)
+    kmers = np.zeros(n, dtype=np.uint64)
+    lines_of = {}
+    for i, r in enumerate(blocks):
+        lines_of.setdefault(r.genome, []).append(i)
+    for name, lines in lines_of.items():
+        if name not in genomes_by_name:
+            raise ValueError(f"block table names genome {name}, which is not among {sorted(genomes_by_name)}")
+        g = genomes_by_name[name]
+        loaded = callable(g)
+        if loaded:
+            g = g()
+        try:
+            rec_of = {c: j for j, c in enumerate(g.names)}
+            iv = np.zeros((len(lines), 3), dtype=np.uint64)
+            for q, i in enumerate(lines):
+                r = blocks[i]
+                if r.contig not in rec_of:
+                    raise ValueError(f"block {r.block_id}: genome {name} has no record {r.contig}")
+                iv[q] = (rec_of[r.contig], max(r.start, 0), max(r.end, 0))
+            sk, cnt, nk = g.minhash_intervals(iv, k, s)
+        finally:
+            if loaded:
+                g.free()
+        sketches[lines], counts[lines], kmers[lines] = sk, cnt, nk
+    pair_a, pair_b, ids = [], [], []
+    for b, lines in _block_order(blocks):
+        for x in range(len(lines)):
+            for y in range(x + 1, len(lines)):
+                pair_a.append(lines[x])
+                pair_b.append(lines[y])
+                ids.append(b)
+    shared, size = ctx.minhash_pairs(sketches, counts, pair_a, pair_b) if ids else ((), ())
+    out = []
+    for b, a_, b_, sh, sz in zip(ids, pair_a, pair_b, shared, size):
+        out.append({"block_id": b, "genome_a": blocks[a_].genome, "genome_b": blocks[b_].genome, "distance": distance_of_counts(sh, sz, k),
+                    "shared_hashes": int(sh), "sketch_size": int(sz), "kmers_a": int(kmers[a_]), "kmers_b": int(kmers[b_])})
+    return out
+
+
+def divergence_table(rows, k, s):
+    "TSV with a header, one line per block and pair, then `# k K, sketch S`"
+    lines = ["\t".join(DIVERGENCE_COLUMNS)]
+    for r in rows:
+        lines.append(f"{r['block_id']}\t{r['genome_a']}\t{r['genome_b']}\t{r['distance']:.6g}\t{r['shared_hashes']}\t{r['sketch_size']}\t"
+                     f"{r['kmers_a']}\t{r['kmers_b']}")
+    lines.append(f"# k {int(k)}, sketch {int(s)}")
+    return "\n".join(lines) + "\n"
+
+
+def main(argv=None):
+    "bin/ntsynt_block_stats"
+    import argparse
+    p = argparse.ArgumentParser(prog="ntsynt_block_stats", description="Summary statistics of a synteny block table (number of blocks, coverage, "
+                                "mean / median length, NG50, N50) and, with --fastas, the Mash distance of every block per pair of its genomes (GPU)")
+    p.add_argument("--tsv", help="synteny block table (<prefix>.synteny_blocks.tsv)", required=True)
+    p.add_argument("--fai", help=".fai files of the compared genomes", nargs="+", required=True)
+    p.add_argument("--fastas", help="the genomes themselves: per-block divergence on the GPU (matched to column 2 of the table by base name)",
+                   nargs="+")
+    p.add_argument("-k", help=f"k-mer size of the sketches [{K_DEFAULT}]", type=int, default=K_DEFAULT)
+    p.add_argument("-s", help=f"sketch size [{S_DEFAULT}]", type=int, default=S_DEFAULT)
+    p.add_argument("--divergence-out", help="file for the per-block table [stdout, after the statistics]")
+    p.add_argument("--device", help="GPU index [0]", type=int, default=0)
+    args = p.parse_args(argv)
+    if args.k < 1 or args.s < 1:
+        p.error("-k and -s must be positive")
+    print(stats_table(block_stats(args.tsv, args.fai)), end="")
+    if not args.fastas:
+        return 0
+    for path in args.fastas:
+        if not os.path.isfile(path):
+            raise FileNotFoundError(f"Input file {path} not found.")
+    from .device import Context
+    from .fasta import basename, read_fasta_device
+    ctx = Context(args.device)
+    try:
+        loaders = {basename(path): (lambda path=path: read_fasta_device(ctx, path)[0]) for path in args.fastas}
+        text = divergence_table(block_divergence(ctx, loaders, read_blocks(args.tsv), args.k, args.s), args.k, args.s)
+    finally:
+        ctx.close()
+    if args.divergence_out:
+        with open(args.divergence_out, "w", encoding="utf-8") as fh:
+            fh.write(text)
+    else:
+        print(text, end="")
+    return 0

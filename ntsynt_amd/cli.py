@@ -64,6 +64,11 @@ def build_parser():
     p.add_argument("--dev", help="developer mode: verbose log, overlap self-check of the final blocks", action="store_true")
     p.add_argument("--repeat", help=argparse.SUPPRESS, action="store_true")   # the Snakefile's experimental config "repeat": <prefix>.repeat.bf + indexlr -r
     p.add_argument("--interarrivals", help=argparse.SUPPRESS, action="store_true")   # ntsynt_run.py --interarrivals: <prefix>.interarrivals.tsv
+    p.add_argument("--assess", help="after the run, write <prefix>.block_stats.tsv (number of blocks, coverage, mean / median length, NG50, N50)\n"
+                   "and <prefix>.block_divergence.tsv (Mash distance of every block per pair of its genomes), from the genomes still on the GPU",
+                   action="store_true")
+    p.add_argument("--assess-k", help="k-mer size of the per-block sketches [21]", type=int, default=21)
+    p.add_argument("--assess-s", help="size of the per-block sketches [1000]", type=int, default=1000)
     p.add_argument("--device", help="GPU index [0]", type=int, default=0)
     # switches for the two btllib details this implementation recalls rather than reads
     p.add_argument("--bf-rounding", help=argparse.SUPPRESS, choices=["up", "down", "none"], default="up")
@@ -131,6 +136,12 @@ def main(argv=None):
     args = parser.parse_args(argv)
     rank0 = int(os.environ.get("RANK", "0")) == 0                # under torchrun every rank runs this; one of them talks
     say = print if rank0 else (lambda *a, **k: None)
+    if args.assess:
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            parser.error("--assess works from the genomes resident on one GPU: run it on one rank, or assess the finished run with "
+                         "ntsynt_block_stats --tsv <prefix>.synteny_blocks.tsv --fai ... --fastas ...")
+        if args.assess_k < 1 or args.assess_s < 1:
+            parser.error("--assess-k and --assess-s must be positive")
     if args.divergence == "auto":
         estimate_divergence(parser, args, say)
     fastas = resolve(parser, args)
@@ -156,7 +167,7 @@ def main(argv=None):
         if not os.path.isfile(fasta):
             raise FileNotFoundError(f"Input file {fasta} not found.")
     plan = ["faidx x%d" % len(fastas)] + ([] if args.no_common else ["make_common_bf"]) + \
-           ["indexlr x%d" % len(fastas), "ntsynt_synteny"]
+           ["indexlr x%d" % len(fastas), "ntsynt_synteny"] + (["assess"] if args.assess else [])
     if args.dry_run:
         say("Stages (GPU, in process):", " -> ".join(plan))
         return 0
@@ -211,7 +222,7 @@ def _run(pipeline, fastas, args, device, quiet):
     pipeline.run(fastas, k=args.k, w=args.w, fpr=args.fpr, prefix=args.prefix, w_rounds=args.w_rounds,
                  indel=args.indel, merge=args.merge, block_size=args.block_size, common=not args.no_common,
                  simplify=not args.no_simplify_graph, device=device, benchmark=args.benchmark,
-                 dev=args.dev, interarrivals=args.interarrivals, repeat=args.repeat, bf_rounding=args.bf_rounding, bf_signature=args.bf_signature or pipeline.BF_SIGNATURE,
+                 dev=args.dev, interarrivals=args.interarrivals, assess=(args.assess_k, args.assess_s) if args.assess else None, repeat=args.repeat, bf_rounding=args.bf_rounding, bf_signature=args.bf_signature or pipeline.BF_SIGNATURE,
                  log=print if (args.dev and int(os.environ.get("RANK", "0")) == 0) else quiet)
 
 

@@ -514,6 +514,9 @@ struct nts_ctx
   uint32_t last_graph_v_slices = 0, last_graph_e_slices = 0, last_graph_oversize = 0;
   uint64_t last_graph_peak = 0;
   uint64_t graph_live0 = 0; // library bytes live when the running build's call began
+  // the last nts_minhash_intervals (nts_minhash_iv.inc): sweeps of its slowest chunk, chunks, sweeps in all
+  uint32_t last_mhi_passes = 0, last_mhi_chunks = 0;
+  uint64_t last_mhi_sweeps = 0;
 };
 
 struct nts_genome

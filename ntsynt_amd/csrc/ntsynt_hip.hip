@@ -1618,6 +1618,7 @@ int launch_hash(nts_ctx* ctx, const char* name, const nts_genome* g, const Genom
 #include "nts_bf_sparse.inc"
 #include "nts_microbench.inc"
 #include "nts_minhash.inc"
+#include "nts_minhash_iv.inc"
 
 // acc &= the filter of genome g the literal way, for a running filter that holds few bits (defined behind the sketch's host code,
 // whose accept kernels and summary it uses): 0 = done, 1 = does not apply or did not fit (acc is untouched), < 0 = error
@@ -2734,6 +2735,32 @@ int nts_minhash(nts_ctx* ctx, const nts_genome* g, uint32_t k, uint32_t s, uint6
   if (!ctx || !g || !out || !n_out || k == 0 || s == 0) return fail(ctx, NTS_EINVAL, "nts_minhash: bad arguments");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   return minhash_run(ctx, g, k, s, out, n_out);
+}
+
+int nts_minhash_intervals(nts_ctx* ctx, const nts_genome* g, uint32_t k, uint32_t s, const nts_interval* iv, uint64_t n_iv, uint64_t* out,
+                          uint32_t* n_out, uint64_t* n_kmers)
+{
+  if (!ctx || !g || k == 0 || s == 0 || (n_iv && (!iv || !out || !n_out))) return fail(ctx, NTS_EINVAL, "nts_minhash_intervals: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return minhash_intervals_run(ctx, g, k, s, iv, n_iv, out, n_out, n_kmers);
+}
+
+int nts_minhash_intervals_stats(nts_ctx* ctx, uint32_t* passes, uint32_t* chunks, uint64_t* sweeps)
+{
+  if (!ctx) return NTS_EINVAL;
+  if (passes) *passes = ctx->last_mhi_passes;
+  if (chunks) *chunks = ctx->last_mhi_chunks;
+  if (sweeps) *sweeps = ctx->last_mhi_sweeps;
+  return NTS_OK;
+}
+
+int nts_minhash_pairs(nts_ctx* ctx, uint32_t s, const uint64_t* sk, const uint32_t* n_sk, uint64_t n_sketches, const uint64_t* pair_a,
+                      const uint64_t* pair_b, uint64_t n_pairs, uint32_t* shared, uint32_t* usize)
+{
+  if (!ctx || s == 0 || (n_sketches && (!sk || !n_sk)) || (n_pairs && (!pair_a || !pair_b || !shared || !usize)))
+    return fail(ctx, NTS_EINVAL, "nts_minhash_pairs: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return minhash_pairs_run(ctx, s, sk, n_sk, n_sketches, pair_a, pair_b, n_pairs, shared, usize);
 }
 
 } // extern "C"

@@ -67,6 +67,27 @@ class Context:
         level = int(enable) if not isinstance(enable, bool) else (1 if enable else 0)
         self.check(self.lib.nts_profile(self.h, level), "nts_profile")
 
+    def minhash_intervals_stats(self):
+        "(sweeps of the slowest chunk, chunks, sweeps in all) of the last Genome.minhash_intervals on this context"
+        p, c, t = _lib.u32(), _lib.u32(), u64()
+        self.check(self.lib.nts_minhash_intervals_stats(self.h, ctypes.byref(p), ctypes.byref(c), ctypes.byref(t)), "nts_minhash_intervals_stats")
+        return p.value, c.value, t.value
+
+    def minhash_pairs(self, sketches, counts, pair_a, pair_b):
+        """(shared, size) of the Mash distance for pairs of bottom-s sketches (nts_minhash_pairs): sketches [n, s] uint64 with
+        counts[i] hashes used in row i; pair p compares rows pair_a[p] and pair_b[p].  Two uint32 arrays."""
+        sk = np.ascontiguousarray(sketches, dtype=np.uint64)
+        cnt = np.ascontiguousarray(counts, dtype=np.uint32)
+        a = np.ascontiguousarray(pair_a, dtype=np.uint64)
+        b = np.ascontiguousarray(pair_b, dtype=np.uint64)
+        if sk.ndim != 2 or cnt.size != sk.shape[0] or a.size != b.size:
+            raise ValueError("minhash_pairs: sketches [n, s], one count per row, pair lists of one length")
+        shared = np.zeros(a.size, dtype=np.uint32)
+        size = np.zeros(a.size, dtype=np.uint32)
+        self.check(self.lib.nts_minhash_pairs(self.h, sk.shape[1], sk.ctypes.data, cnt.ctypes.data, sk.shape[0], a.ctypes.data, b.ctypes.data,
+                                              a.size, shared.ctypes.data, size.ctypes.data), "nts_minhash_pairs")
+        return shared, size
+
     def timing(self, name):
         ms, n = ctypes.c_double(), u64()
         self.check(self.lib.nts_timing(self.h, name.encode(), ctypes.byref(ms), ctypes.byref(n)), "nts_timing")
@@ -386,6 +407,22 @@ class Genome:
         self.ctx.check(self.ctx.lib.nts_minhash(self.ctx.h, self.h, int(k), int(s), out.ctypes.data_as(_lib.c_u64p), ctypes.byref(n)),
                        "nts_minhash")
         return out[:n.value].copy()
+
+    def minhash_intervals(self, intervals, k, s):
+        """bottom-s sketches of many intervals in one sweep (nts_minhash_intervals).  intervals: (rec, start, end) rows -- the valid
+        k-mers wholly inside [start, end) of record rec, end clipped to the record.  Returns (sketches [n, s] uint64 -- row i holds
+        counts[i] hashes, ascending, distinct --, counts [n] uint32, n_kmers [n] uint64)."""
+        rows = np.asarray(intervals, dtype=np.uint64).reshape(-1, 3)
+        n, s = rows.shape[0], int(s)
+        iv = np.zeros(n, dtype=np.dtype([("rec", "<u4"), ("start", "<u8"), ("end", "<u8")], align=True))
+        assert iv.dtype.itemsize == ctypes.sizeof(Interval)
+        iv["rec"], iv["start"], iv["end"] = rows[:, 0], rows[:, 1], rows[:, 2]
+        out = np.zeros((n, max(s, 1)), dtype=np.uint64)
+        counts = np.zeros(n, dtype=np.uint32)
+        n_kmers = np.zeros(n, dtype=np.uint64)
+        self.ctx.check(self.ctx.lib.nts_minhash_intervals(self.ctx.h, self.h, int(k), s, ctypes.cast(iv.ctypes.data, ctypes.POINTER(Interval)), n,
+                                                          out.ctypes.data, counts.ctypes.data, n_kmers.ctypes.data), "nts_minhash_intervals")
+        return out, counts, n_kmers
 
     def free(self):
         if self.h:

@@ -27,18 +27,24 @@ def merge(a, b, s):
     return np.union1d(np.asarray(a, dtype=np.uint64), np.asarray(b, dtype=np.uint64))[:int(s)]
 
 
+def distance_of_counts(shared, size, k):
+    "Mash distance from shared = |bottom-s(A u B) n A n B| and size = |bottom-s(A u B)|"
+    shared, size = int(shared), int(size)
+    if size == 0 or shared == 0:
+        return 1.0
+    if shared == size:
+        return 0.0
+    j = shared / size
+    return min(1.0, -math.log(2.0 * j / (1.0 + j)) / int(k))
+
+
 def distance(a, b, k, s):
     "(Mash distance, shared hashes, |bottom-s(A u B)|) of two sketches"
     a = np.asarray(a, dtype=np.uint64)
     b = np.asarray(b, dtype=np.uint64)
     u = merge(a, b, s)
     shared = int(np.intersect1d(np.intersect1d(u, a, assume_unique=True), b, assume_unique=True).size)
-    if u.size == 0 or shared == 0:
-        return 1.0, shared, int(u.size)
-    if shared == u.size:
-        return 0.0, shared, int(u.size)
-    j = shared / u.size
-    return min(1.0, -math.log(2.0 * j / (1.0 + j)) / int(k)), shared, int(u.size)
+    return distance_of_counts(shared, u.size, k), shared, int(u.size)
 
 
 def suggested_divergence(d_max):

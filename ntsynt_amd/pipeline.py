@@ -496,7 +496,7 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         block_size=500, common=True, simplify=True, device=0, write_mx_tsv=True, mx_with_seq=True,
         benchmark=False, log=print, ctx=None, backend=None, bf_rounding="up", bf_signature=BF_SIGNATURE, dev=False, interarrivals=False, repeat=False,
         mx_tsvs=None, common_file=None, m=90, n=0, initial_only=False, write_fai=True, engine="device", refine_repeat_file=None, screen_repeat_file=None,
-        graph_budget=None):
+        graph_budget=None, assess=None):
     """FASTA paths -> engine (outputs in .outputs and in the CWD).  Mirrors oracle.synteny_oracle.run_pipeline's
     signature so the parity tests read alike.  Under torch.distributed (WORLD_SIZE > 1, process group already
     initialised by the caller) genomes are sharded over the ranks.
@@ -505,7 +505,8 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
     every assembly (aligned with `fastas`: read instead of sketched, ntJoin's read_minimizers) and common_file = the
     `--common` filter file (uploaded instead of built; None with common=False: the refinement rounds sketch unfiltered);
     m / n: ntsynt_run.py's -m / -n.  graph_budget: bytes of per-slice scratch the graph builds may take (Context.set_graph_budget;
-    None leaves the context's setting, 0 = automatic)."""
+    None leaves the context's setting, 0 = automatic).  assess = (k, s): after the final block table, <prefix>.block_stats.tsv and
+    <prefix>.block_divergence.tsv from the genomes still resident (ntsynt_amd/assess.py; one rank only)."""
     prefix = prefix or f"ntSynt.k{k}.w{w}"
     if mx_tsvs is not None and len(mx_tsvs) != len(fastas):
         raise ValueError("one minimizer TSV per FASTA file")
@@ -531,6 +532,8 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
             lib.nts_mem_stats(None, ctypes.byref(a), ctypes.byref(b), None, None)
             return {"live": a.value, "peak": b.value}
         st.mem = _mem
+    if assess is not None and (world > 1 or (mx_tsvs is not None and initial_only)):
+        raise ValueError("assess needs every genome resident on one GPU (one rank, genomes loaded)")
     st.mark("start")
     if world > 1 and hasattr(backend, "init_comm"):
         backend.init_comm()
@@ -1014,6 +1017,20 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         f.result()                      # re-raises a writer's exception
     writers.shutdown()
     st.stop()
+    if assess is not None:
+        st.start("assess")
+        from . import assess as assess_
+        a_k, a_s = int(assess[0]), int(assess[1])
+        blocks_tsv = f"{prefix}.synteny_blocks.tsv"
+        sizes = {fa.basename(p): int(meta[p][1]) for p in fastas}
+        stats_text = assess_.stats_table(assess_.block_stats(blocks_tsv, None, sizes=sizes))
+        rows = assess_.block_divergence(backend.ctx, {fa.basename(p): genomes[p] for p in fastas}, assess_.read_blocks(blocks_tsv), a_k, a_s)
+        for name, text in ((f"{prefix}.block_stats.tsv", stats_text), (f"{prefix}.block_divergence.tsv", assess_.divergence_table(rows, a_k, a_s))):
+            with open(name, "w", encoding="utf-8") as fh:
+                fh.write(text)
+            eng.outputs[name] = text
+        st.stop()
+        st.mark("assess_done")
     memory = st.memory()
     if benchmark and rank == 0:
         st.write(f"{prefix}.stage_times.tsv", memory)
