@@ -434,6 +434,19 @@ int nts_minhash_intervals_stats(nts_ctx* ctx, uint32_t* passes, uint32_t* chunks
 int nts_minhash_pairs(nts_ctx* ctx, uint32_t s, const uint64_t* sk, const uint32_t* n_sk, uint64_t n_sketches, const uint64_t* pair_a,
                       const uint64_t* pair_b, uint64_t n_pairs, uint32_t* shared, uint32_t* usize);
 
+/* ---- what the blocks leave out: gap content ----------------------------------------------------------
+ * nts_bf_count_intervals: for interval i of g, n_kmers[i] = the valid k-mers that lie wholly inside [start, end) of record rec
+ *   (the rule, the clipping and the NTS_EINVAL of nts_minhash_intervals) and n_hits[i] = how many of them bf holds: bit
+ *   h0 mod (8 * bytes) of the filter, h0 the canonical hash as nts_bf_insert and the sketch form it (one hash function).  Exact, every
+ *   k-mer probed once, one sweep for all intervals of the call (timer "bf_count_iv", one launch per 2^23 tiles of 8192 k-mers).
+ *   Intervals in any order, overlapping, shorter than k (both counts 0).  Any k >= 1.  ntsynt_amd/gaps.py, `ntSynt --gaps`,
+ *   bin/ntsynt_gaps; csrc/nts_bf_iv.inc.
+ * nts_genome_valid_bases: n_valid[i] = the A/C/G/T bases of interval i (the rest of its length is N or another letter), from the
+ *   genome's table of valid stretches on the host: no GPU work. */
+int nts_bf_count_intervals(nts_ctx* ctx, const nts_genome* g, uint32_t k, const nts_bf* bf, const nts_interval* iv, uint64_t n_iv,
+                           uint64_t* n_kmers, uint64_t* n_hits);
+int nts_genome_valid_bases(nts_ctx* ctx, const nts_genome* g, const nts_interval* iv, uint64_t n_iv, uint64_t* n_valid);
+
 /* ---- C1-C5: minimizer graph -> collinear chains -----------------------------------------------------
  * replaces ntjoin_utils.read_minimizers' duplicate removal, filter_minimizers and build_graph
  * (call sites bin/ntsynt_synteny.py:607-612, 483, 539) and the path walk of Ntjoin.find_paths

@@ -158,6 +158,8 @@ SYMBOLS = [
     ("nts_minhash", ctypes.c_int, [c_vp, c_vp, u32, u32, c_u64p, c_u32p]),
     ("nts_minhash_intervals", ctypes.c_int, [c_vp, c_vp, u32, u32, ctypes.POINTER(Interval), u64, c_vp, c_vp, c_vp]),
     ("nts_minhash_intervals_stats", ctypes.c_int, [c_vp, c_u32p, c_u32p, c_u64p]),
+    ("nts_bf_count_intervals", ctypes.c_int, [c_vp, c_vp, u32, c_vp, ctypes.POINTER(Interval), u64, c_vp, c_vp]),
+    ("nts_genome_valid_bases", ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(Interval), u64, c_vp]),
     ("nts_minhash_pairs", ctypes.c_int, [c_vp, u32, c_vp, c_vp, u64, c_vp, c_vp, u64, c_vp, c_vp]),
     ("nts_graph_build", ctypes.c_int, [c_vp, u32, ctypes.POINTER(MxList), ctypes.POINTER(Graph)]),
     ("nts_graph_budget", ctypes.c_int, [c_vp, u64]),

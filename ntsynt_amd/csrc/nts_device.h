@@ -206,9 +206,20 @@ __host__ __device__ __forceinline__ uint32_t fold2_slot(uint64_t idx)
 
 // Bloom bit `idx` lives in byte idx/8 at bit idx%8 (LSB first) == bit idx%32 of little-endian
 // 32-bit word idx/32.
+// (the two halves of the address on their own, for kernels that issue the word loads of several k-mers before they look at any)
+__device__ __forceinline__ uint64_t bf_word(uint64_t idx)
+{
+  return idx >> 5;
+}
+
+__device__ __forceinline__ uint32_t bf_bit(uint64_t idx)
+{
+  return (uint32_t)idx & 31u;
+}
+
 __device__ __forceinline__ bool bf_test(const uint32_t* __restrict__ words, uint64_t idx)
 {
-  return (words[idx >> 5] >> (idx & 31)) & 1u;
+  return (words[bf_word(idx)] >> bf_bit(idx)) & 1u;
 }
 
 __device__ __forceinline__ void bf_set(uint32_t* words, uint64_t idx)

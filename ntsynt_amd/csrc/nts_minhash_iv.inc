@@ -1,9 +1,6 @@
 // ---- bottom-s MinHash sketches of many intervals of a resident genome (nts_minhash_intervals; ntsynt_amd/assess.py) -------------
-// One sweep serves every interval of a call (docs/design/04_8_block_assessment.md).  The host cuts each interval against the genome's
-// stretches of valid bases (nts_genome::st_a / st_b) into pieces of at least k bases, and the pieces into tiles of at most KEY_TILE
-// k-mers: every k-mer of a tile is valid, lies wholly inside its interval, and the tile's bases are contiguous -- so a workgroup does
-// what k_hash's fast path does (bases staged through LDS with 16-byte loads, each lane hashes its first k-mer from the init table and
-// rolls 31 times) and needs no run table.  n_kmers[i] falls out of the cutting.
+// One sweep serves every interval of a call (docs/design/04_8_block_assessment.md).  The host cuts the intervals into tiles of valid
+// k-mers (nts_iv_cut.inc, shared with nts_bf_count_intervals); a workgroup hashes one tile as k_hash's fast path does.
 //   survivors: per-interval open-addressing sets (MhSet, next to k_hash; mhi_insert below), NOT an (interval, h0) list sorted and made
 //        unique afterwards: a set removes copies where they arise, so that a satellite array -- 10^5 k-mers, a few hundred distinct
 //        hashes, all of them below any threshold that keeps s of them -- fills a few hundred slots; in a list its copies overflow
@@ -21,13 +18,6 @@
 //        the first min(s, count_i) of each segment are gathered and copied to the host in one piece.
 // Experiments build only: NTS_MINHASH_TAU0 = the first tau of every interval, NTS_MINHASH_CAP = the slots of every interval (raised to
 // 4 s and to a power of two): the tests force both retry directions with them.
-
-struct MhiTile
-{
-  uint64_t pos; // index into the genome's codes of the tile's first k-mer
-  uint32_t iv;  // interval (within the chunk)
-  uint32_t len; // k-mers, 1 .. KEY_TILE
-};
 
 struct MhiState
 {
@@ -57,7 +47,7 @@ __device__ __forceinline__ unsigned long long mhi_insert(const MhSet& mh, uint64
 
 constexpr uint32_t MHI_SUB = 8; // workgroups per interval of the small kernels (reset, compact, take)
 
-__global__ __launch_bounds__(HASH_THREADS) void k_minhash_intervals(const uint8_t* __restrict__ code, const MhiTile* __restrict__ tiles,
+__global__ __launch_bounds__(HASH_THREADS) void k_minhash_intervals(const uint8_t* __restrict__ code, const IvTile* __restrict__ tiles,
                                                                     const MhiState* __restrict__ state, uint64_t* __restrict__ slots,
                                                                     unsigned long long* __restrict__ counts, HashParams hp)
 {
@@ -72,7 +62,7 @@ __global__ __launch_bounds__(HASH_THREADS) void k_minhash_intervals(const uint8_
   if (tid < 4) s_tab[32 + tid] = hp.seed[tid];
   if (tid == 0) s_added = 0;
   const uint32_t k = hp.k;
-  const MhiTile tile = tiles[blockIdx.x];
+  const IvTile tile = tiles[blockIdx.x];
   const MhiState st = state[tile.iv];
   MhSet mh;
   mh.slots = slots + st.slot_off;
@@ -182,14 +172,9 @@ __global__ __launch_bounds__(256) void k_mhi_take(const uint64_t* __restrict__ s
   for (uint64_t i = (uint64_t)sub * 256 + threadIdx.x; i < n; i += (uint64_t)MHI_SUB * 256) out[t + i] = sorted[o + i];
 }
 
-struct MhiPiece
-{
-  uint64_t pos, nk;
-};
-
 // one chunk of intervals [i0, i1): pieces[piece_at[i] .. piece_at[i + 1]) are interval i's runs of k-mers, nk[i] their sum
 int minhash_intervals_chunk(nts_ctx* ctx, const nts_genome* g, const HashParams& hp, uint32_t s, uint64_t i0, uint64_t i1,
-                            const std::vector<MhiPiece>& pieces, const std::vector<uint64_t>& piece_at, const std::vector<uint64_t>& nk,
+                            const std::vector<IvPiece>& pieces, const std::vector<uint64_t>& piece_at, const std::vector<uint64_t>& nk,
                             const std::vector<uint64_t>& caps, uint64_t* out, uint32_t* n_out, uint32_t* passes_out)
 {
   using u128 = unsigned __int128;
@@ -245,17 +230,14 @@ int minhash_intervals_chunk(nts_ctx* ctx, const nts_genome* g, const HashParams&
   std::vector<uint32_t> active(n), retry;
   for (uint32_t j = 0; j < n; ++j) active[j] = j;
   std::vector<unsigned long long> counts(n, 0);
-  std::vector<MhiTile> tiles;
+  std::vector<IvTile> tiles;
   uint32_t passes = 0;
   while (!active.empty()) {
     tiles.clear();
-    for (uint32_t j : active)
-      for (uint64_t q = piece_at[i0 + j]; q < piece_at[i0 + j + 1]; ++q)
-        for (uint64_t at = 0; at < pieces[q].nk; at += KEY_TILE)
-          tiles.push_back({ pieces[q].pos + at, j, (uint32_t)std::min<uint64_t>(KEY_TILE, pieces[q].nk - at) });
+    for (uint32_t j : active) iv_append_tiles(pieces, piece_at, i0 + j, j, tiles);
     MHI_HIP(hipMemcpyAsync(d_state, st.data(), (size_t)n * sizeof(MhiState), hipMemcpyHostToDevice, ctx->stream));
     if (!tiles.empty()) {
-      MhiTile* d_tiles = nullptr;
+      IvTile* d_tiles = nullptr;
       MHI_RC(ws_upload(ctx, "mhi_tiles", tiles, &d_tiles));
       ScopedTimer t(ctx, "minhash_iv", true);
       constexpr uint64_t SLICE = (uint64_t)1 << 23; // tiles per launch: 2^31 work-items
@@ -350,26 +332,15 @@ int minhash_intervals_run(nts_ctx* ctx, const nts_genome* g, uint32_t k, uint32_
   ctx->last_mhi_sweeps = 0;
   if (n_iv == 0) return NTS_OK;
   // ---- the intervals against the stretches of valid bases: runs of k-mers that lie wholly inside an interval
-  std::vector<MhiPiece> pieces;
-  std::vector<uint64_t> piece_at(n_iv + 1, 0), nk(n_iv, 0), caps(n_iv, 0);
-  const size_t ns = g->st_a.size();
+  std::vector<IvPiece> pieces;
+  std::vector<uint64_t> piece_at, nk, caps(n_iv, 0);
+  {
+    const int rc = iv_cut_pieces(ctx, g, k, iv, n_iv, "nts_minhash_intervals", pieces, piece_at, nk);
+    if (rc) return rc;
+  }
   uint64_t knob_cap = 0;
   if (const char* v = NTS_KNOB("NTS_MINHASH_CAP")) knob_cap = strtoull(v, nullptr, 0);
   for (uint64_t i = 0; i < n_iv; ++i) {
-    if (iv[i].rec >= g->n_rec) return fail(ctx, NTS_EINVAL, "nts_minhash_intervals: record index out of range");
-    const uint64_t len = g->rec_len[iv[i].rec];
-    const uint64_t a = g->rec_off[iv[i].rec] + std::min(iv[i].start, len), b = g->rec_off[iv[i].rec] + std::min(iv[i].end, len);
-    if (b > a && b - a >= k) {
-      size_t q = (size_t)(std::upper_bound(g->st_b.begin(), g->st_b.end(), a) - g->st_b.begin()); // first stretch that ends behind a
-      for (; q < ns && g->st_a[q] < b; ++q) {
-        const uint64_t pa = std::max(a, g->st_a[q]), pb = std::min(b, g->st_b[q]);
-        if (pb > pa && pb - pa >= k) {
-          pieces.push_back({ pa, pb - pa - k + 1 });
-          nk[i] += pb - pa - k + 1;
-        }
-      }
-    }
-    piece_at[i + 1] = pieces.size();
     if (n_kmers) n_kmers[i] = nk[i];
     n_out[i] = 0;
     uint64_t cap = std::max<uint64_t>(64, std::min<uint64_t>(nk[i] > ((uint64_t)1 << 60) ? ~0ull : 4 * nk[i], (uint64_t)16 * s));

@@ -1618,7 +1618,9 @@ int launch_hash(nts_ctx* ctx, const char* name, const nts_genome* g, const Genom
 #include "nts_bf_sparse.inc"
 #include "nts_microbench.inc"
 #include "nts_minhash.inc"
+#include "nts_iv_cut.inc"
 #include "nts_minhash_iv.inc"
+#include "nts_bf_iv.inc"
 
 // acc &= the filter of genome g the literal way, for a running filter that holds few bits (defined behind the sketch's host code,
 // whose accept kernels and summary it uses): 0 = done, 1 = does not apply or did not fit (acc is untouched), < 0 = error
@@ -2751,6 +2753,25 @@ int nts_minhash_intervals_stats(nts_ctx* ctx, uint32_t* passes, uint32_t* chunks
   if (passes) *passes = ctx->last_mhi_passes;
   if (chunks) *chunks = ctx->last_mhi_chunks;
   if (sweeps) *sweeps = ctx->last_mhi_sweeps;
+  return NTS_OK;
+}
+
+int nts_bf_count_intervals(nts_ctx* ctx, const nts_genome* g, uint32_t k, const nts_bf* bf, const nts_interval* iv, uint64_t n_iv,
+                           uint64_t* n_kmers, uint64_t* n_hits)
+{
+  if (!ctx || !g || !bf || k == 0 || (n_iv && (!iv || !n_kmers || !n_hits))) return fail(ctx, NTS_EINVAL, "nts_bf_count_intervals: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return bf_count_intervals_run(ctx, g, k, bf, iv, n_iv, n_kmers, n_hits);
+}
+
+int nts_genome_valid_bases(nts_ctx* ctx, const nts_genome* g, const nts_interval* iv, uint64_t n_iv, uint64_t* n_valid)
+{
+  if (!ctx || !g || (n_iv && (!iv || !n_valid))) return fail(ctx, NTS_EINVAL, "nts_genome_valid_bases: bad arguments");
+  std::vector<IvPiece> pieces;
+  std::vector<uint64_t> piece_at, nk; // (the valid 1-mers of an interval are its valid bases)
+  const int rc = iv_cut_pieces(ctx, g, 1, iv, n_iv, "nts_genome_valid_bases", pieces, piece_at, nk);
+  if (rc) return rc;
+  for (uint64_t i = 0; i < n_iv; ++i) n_valid[i] = nk[i];
   return NTS_OK;
 }
 

@@ -424,6 +424,34 @@ class Genome:
                                                           out.ctypes.data, counts.ctypes.data, n_kmers.ctypes.data), "nts_minhash_intervals")
         return out, counts, n_kmers
 
+    @staticmethod
+    def _interval_array(intervals):
+        "(rec, start, end) rows in nts_interval's layout"
+        rows = np.asarray(intervals, dtype=np.uint64).reshape(-1, 3)
+        iv = np.zeros(rows.shape[0], dtype=np.dtype([("rec", "<u4"), ("start", "<u8"), ("end", "<u8")], align=True))
+        assert iv.dtype.itemsize == ctypes.sizeof(Interval)
+        iv["rec"], iv["start"], iv["end"] = rows[:, 0], rows[:, 1], rows[:, 2]
+        return iv
+
+    def valid_bases(self, intervals):
+        "per interval its A/C/G/T bases (nts_genome_valid_bases: host arithmetic over the genome's valid stretches); [n] uint64"
+        iv = self._interval_array(intervals)
+        out = np.zeros(iv.size, dtype=np.uint64)
+        self.ctx.check(self.ctx.lib.nts_genome_valid_bases(self.ctx.h, self.h, ctypes.cast(iv.ctypes.data, ctypes.POINTER(Interval)), iv.size,
+                                                           out.ctypes.data), "nts_genome_valid_bases")
+        return out
+
+    def bf_count_intervals(self, bf, intervals, k):
+        """per interval the valid k-mers wholly inside it and how many of them the Bloom filter `bf` holds (nts_bf_count_intervals):
+        intervals as in minhash_intervals; returns (kmers [n] uint64, hits [n] uint64), exact"""
+        iv = self._interval_array(intervals)
+        n = iv.size
+        kmers = np.zeros(n, dtype=np.uint64)
+        hits = np.zeros(n, dtype=np.uint64)
+        self.ctx.check(self.ctx.lib.nts_bf_count_intervals(self.ctx.h, self.h, int(k), bf.h, ctypes.cast(iv.ctypes.data, ctypes.POINTER(Interval)), n,
+                                                           kmers.ctypes.data, hits.ctypes.data), "nts_bf_count_intervals")
+        return kmers, hits
+
     def free(self):
         if self.h:
             self.ctx.lib.nts_genome_free(self.ctx.h, self.h)

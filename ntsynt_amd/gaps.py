@@ -1,0 +1,205 @@
+"""What a run's synteny blocks leave out, and how much of it every genome shares (`ntSynt --gaps`, bin/ntsynt_gaps).
+
+Per genome and record the complement of the blocks' intervals is cut into gaps (cut: host arithmetic; no GPU, no torch, no numpy), and
+for every gap -- and, as the baseline, for every merged in-block interval -- the k-mers that the run's common Bloom filter holds are
+counted on the GPU in one sweep per genome (report: nts_bf_count_intervals).  A gap whose k-mers are mostly in the filter is sequence
+every genome has and the chaining dropped; one at the filter's occupancy is the genome's own; one without valid k-mers is an assembly
+gap.  docs/design/04_9_gap_content.md."""
+import os
+from collections import namedtuple
+
+GAP_COLUMNS = ("genome", "contig", "start", "end", "length", "kind", "left_block", "right_block", "n_bases", "kmers", "shared_kmers",
+               "shared_fraction", "excess")
+SUMMARY_COLUMNS = ("genome", "part", "intervals", "bases", "n_bases", "kmers", "shared_kmers", "shared_fraction", "excess")
+
+# a stretch of `contig` of `genome` outside every block: [start, end); kind: between / leading / trailing / unplaced (the record has no
+# block at all); left_block / right_block: the block that ends at `start` / starts at `end`, "." where there is none
+Gap = namedtuple("Gap", ["genome", "contig", "start", "end", "kind", "left_block", "right_block"])
+# the union of the blocks' intervals, overlapping and touching ones merged
+Merged = namedtuple("Merged", ["genome", "contig", "start", "end"])
+
+
+def read_fai(path):
+    "[(record name, length)] of a .fai file, in file order"
+    out = []
+    with open(path, "r", encoding="utf-8") as fh:
+        for line in fh:
+            f = line.rstrip("\n").split("\t")
+            if len(f) >= 2:
+                out.append((f[0], int(f[1])))
+    return out
+
+
+def cut(blocks, records):
+    """blocks: assess.read_blocks' rows; records: {genome name: [(record name, length), ...] in file order}.  Returns (gaps, merged):
+    per genome and record the union of the blocks' intervals clipped to the record (merged) and its complement (gaps; none of length
+    zero).  Genomes by name ascending, records in file order, gaps by start.  A genome of `records` the table does not name has
+    every record unplaced; a block on a genome or record that `records` does not have is an error.  On ties the first block in file
+    order names left_block / right_block."""
+    placed = {}                                                 # genome -> contig -> [(start, end, file index, block id)]
+    for i, r in enumerate(blocks):
+        if r.genome not in records:
+            raise ValueError(f"block table names genome {r.genome}, which is not among {sorted(records)}")
+        placed.setdefault(r.genome, {}).setdefault(r.contig, []).append((r.start, r.end, i, r.block_id))
+    gaps, merged = [], []
+    for genome in sorted(records):
+        lengths = dict(records[genome])
+        for contig in placed.get(genome, {}):
+            if contig not in lengths:
+                raise ValueError(f"block table names record {contig} of genome {genome}, which that genome does not have")
+        for contig, length in records[genome]:
+            rows = []
+            for start, end, i, bid in placed.get(genome, {}).get(contig, []):
+                start, end = max(start, 0), min(end, length)
+                if end > start:
+                    rows.append((start, end, i, bid))
+            if not rows:
+                if length > 0:
+                    gaps.append(Gap(genome, contig, 0, length, "unplaced", ".", "."))
+                continue
+            rows.sort(key=lambda t: (t[0], t[2]))
+            runs = []                                           # [start, end, id of the first block that starts at start, .. ends at end]
+            for start, end, i, bid in rows:
+                if runs and start <= runs[-1][1]:
+                    run = runs[-1]
+                    if end > run[1] or (end == run[1] and i < run[4]):
+                        run[1], run[3], run[4] = end, bid, i
+                else:
+                    runs.append([start, end, bid, bid, i])
+            at, left = 0, "."
+            for n, (start, end, first_id, last_id, _) in enumerate(runs):
+                if start > at:
+                    gaps.append(Gap(genome, contig, at, start, "between" if n else "leading", left, first_id))
+                merged.append(Merged(genome, contig, start, end))
+                at, left = end, last_id
+            if length > at:
+                gaps.append(Gap(genome, contig, at, length, "trailing", left, "."))
+    return gaps, merged
+
+
+def excess(shared, kmers, occupancy):
+    """the share of the k-mers the filter holds beyond what its false positives alone give: max(0, (shared / kmers - occ) / (1 - occ));
+    None without k-mers; 0 for a full filter (occ = 1: every answer is a false positive)"""
+    if kmers == 0:
+        return None
+    if occupancy >= 1.0:
+        return 0.0
+    return max(0.0, (shared / kmers - occupancy) / (1.0 - occupancy))
+
+
+def _ratio(x):
+    return "NA" if x is None else f"{x:.6g}"
+
+
+def _footer(k, bits, occupancy):
+    return f"# k {int(k)}, filter {int(bits)} bits, occupancy {occupancy:.6g}"
+
+
+def table(rows, k, bits, occupancy):
+    "<prefix>.gaps.tsv: a header, one line per gap (report()'s gap rows), then `# k K, filter BITS bits, occupancy OCC`"
+    lines = ["\t".join(GAP_COLUMNS)]
+    for r in rows:
+        frac = None if r["kmers"] == 0 else r["shared_kmers"] / r["kmers"]
+        lines.append("\t".join([r["genome"], r["contig"], str(r["start"]), str(r["end"]), str(r["end"] - r["start"]), r["kind"], r["left_block"],
+                                r["right_block"], str(r["n_bases"]), str(r["kmers"]), str(r["shared_kmers"]), _ratio(frac),
+                                _ratio(excess(r["shared_kmers"], r["kmers"], occupancy))]))
+    lines.append(_footer(k, bits, occupancy))
+    return "\n".join(lines) + "\n"
+
+
+def summary(gap_rows, block_rows, k, bits, occupancy, genomes=None):
+    """<prefix>.gap_summary.tsv: per genome (ascending; `genomes` names those without a row of either kind) a line `in_blocks` over the
+    merged in-block intervals and a line `outside` over the gaps, then the footer of table().  A k-mer that straddles a block's end
+    lies wholly inside neither an interval nor a gap and is counted in neither line."""
+    names = sorted(set(genomes or ()) | {r["genome"] for r in gap_rows} | {r["genome"] for r in block_rows})
+    lines = ["\t".join(SUMMARY_COLUMNS)]
+    for name in names:
+        for part, rows in (("in_blocks", block_rows), ("outside", gap_rows)):
+            mine = [r for r in rows if r["genome"] == name]
+            kmers, shared = sum(r["kmers"] for r in mine), sum(r["shared_kmers"] for r in mine)
+            frac = None if kmers == 0 else shared / kmers
+            lines.append("\t".join([name, part, str(len(mine)), str(sum(r["end"] - r["start"] for r in mine)), str(sum(r["n_bases"] for r in mine)),
+                                    str(kmers), str(shared), _ratio(frac), _ratio(excess(shared, kmers, occupancy))]))
+    lines.append(_footer(k, bits, occupancy))
+    return "\n".join(lines) + "\n"
+
+
+def report(ctx, genomes_by_name, bf, k, blocks):
+    """(gap rows, in-block rows, filter bits, occupancy): cut()'s gaps and merged intervals as dicts with n_bases, kmers and
+    shared_kmers added.  genomes_by_name: the name in column 2 of the table -> resident device.Genome, or a callable that returns
+    one (it is then freed after its sweep: one genome resident at a time).  bf: the common filter (device.BloomFilter), built with
+    this k.  One nts_bf_count_intervals call per genome, its gaps and its merged block intervals together.  ctx is not used: every
+    call goes through the context the genome and the filter were made on (the argument mirrors assess.block_divergence)."""
+    for r in blocks:
+        if r.genome not in genomes_by_name:
+            raise ValueError(f"block table names genome {r.genome}, which is not among {sorted(genomes_by_name)}")
+    bits = int(bf.bytes) * 8
+    occupancy = bf.popcount() / float(bits)
+    gap_rows, block_rows = [], []
+    for name in sorted(genomes_by_name):
+        g = genomes_by_name[name]
+        loaded = callable(g)
+        if loaded:
+            g = g()
+        try:
+            rec_of = {c: j for j, c in enumerate(g.names)}
+            gaps, merged = cut([r for r in blocks if r.genome == name], {name: [(c, int(n)) for c, n in zip(g.names, g.rec_len)]})
+            both = gaps + merged
+            iv = [(rec_of[r.contig], r.start, r.end) for r in both]
+            kmers, hits = g.bf_count_intervals(bf, iv, k)
+            valid = g.valid_bases(iv)
+        finally:
+            if loaded:
+                g.free()
+        for q, r in enumerate(both):
+            row = dict(r._asdict(), n_bases=(r.end - r.start) - int(valid[q]), kmers=int(kmers[q]), shared_kmers=int(hits[q]))
+            (gap_rows if q < len(gaps) else block_rows).append(row)
+    return gap_rows, block_rows, bits, occupancy
+
+
+def report_texts(ctx, genomes_by_name, bf, k, blocks):
+    "(text of <prefix>.gaps.tsv, text of <prefix>.gap_summary.tsv)"
+    gap_rows, block_rows, bits, occupancy = report(ctx, genomes_by_name, bf, k, blocks)
+    return table(gap_rows, k, bits, occupancy), summary(gap_rows, block_rows, k, bits, occupancy, genomes=list(genomes_by_name))
+
+
+def main(argv=None):
+    "bin/ntsynt_gaps"
+    import argparse
+    import sys
+    p = argparse.ArgumentParser(prog="ntsynt_gaps", description="What the synteny blocks of a finished run leave out: every gap of every genome "
+                                "with its N bases and the share of its k-mers that the run's common Bloom filter holds (GPU)")
+    p.add_argument("--tsv", help="synteny block table (<prefix>.synteny_blocks.tsv)", required=True)
+    p.add_argument("--fastas", help="the compared genomes (matched to column 2 of the table by base name)", nargs="+", required=True)
+    p.add_argument("--common", help="the run's common Bloom filter (<prefix>.common.bf); k is read from its header", required=True)
+    p.add_argument("--out", help="file for the per-gap table [stdout]")
+    p.add_argument("--summary-out", help="file for the per-genome summary [stdout, after the table]")
+    p.add_argument("--device", help="GPU index [0]", type=int, default=0)
+    args = p.parse_args(argv)
+    for path in args.fastas + [args.common, args.tsv]:
+        if not os.path.isfile(path):
+            raise FileNotFoundError(f"Input file {path} not found.")
+    from .assess import read_blocks
+    from .device import BloomFilter, Context
+    from .fasta import basename, read_fasta_device
+    from .pipeline import read_bf
+    ctx = Context(args.device)
+    try:
+        bits, k = read_bf(args.common)
+        bf = BloomFilter(ctx, bits.size, k)
+        bf.from_numpy(bits)
+        del bits
+        loaders = {basename(path): (lambda path=path: read_fasta_device(ctx, path)[0]) for path in args.fastas}
+        try:
+            texts = report_texts(ctx, loaders, bf, k, read_blocks(args.tsv))
+        finally:
+            bf.free()
+    finally:
+        ctx.close()
+    for text, path in zip(texts, (args.out, args.summary_out)):
+        if path:
+            with open(path, "w", encoding="utf-8") as fh:
+                fh.write(text)
+        else:
+            sys.stdout.write(text)
+    return 0

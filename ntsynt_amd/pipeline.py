@@ -496,7 +496,7 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         block_size=500, common=True, simplify=True, device=0, write_mx_tsv=True, mx_with_seq=True,
         benchmark=False, log=print, ctx=None, backend=None, bf_rounding="up", bf_signature=BF_SIGNATURE, dev=False, interarrivals=False, repeat=False,
         mx_tsvs=None, common_file=None, m=90, n=0, initial_only=False, write_fai=True, engine="device", refine_repeat_file=None, screen_repeat_file=None,
-        graph_budget=None, assess=None):
+        graph_budget=None, assess=None, gaps=False):
     """FASTA paths -> engine (outputs in .outputs and in the CWD).  Mirrors oracle.synteny_oracle.run_pipeline's
     signature so the parity tests read alike.  Under torch.distributed (WORLD_SIZE > 1, process group already
     initialised by the caller) genomes are sharded over the ranks.
@@ -506,7 +506,9 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
     `--common` filter file (uploaded instead of built; None with common=False: the refinement rounds sketch unfiltered);
     m / n: ntsynt_run.py's -m / -n.  graph_budget: bytes of per-slice scratch the graph builds may take (Context.set_graph_budget;
     None leaves the context's setting, 0 = automatic).  assess = (k, s): after the final block table, <prefix>.block_stats.tsv and
-    <prefix>.block_divergence.tsv from the genomes still resident (ntsynt_amd/assess.py; one rank only)."""
+    <prefix>.block_divergence.tsv from the genomes still resident (ntsynt_amd/assess.py; one rank only).  gaps: after that,
+    <prefix>.gaps.tsv and <prefix>.gap_summary.tsv from the resident genomes and the resident common filter (ntsynt_amd/gaps.py; one
+    rank only, and only with a common filter)."""
     prefix = prefix or f"ntSynt.k{k}.w{w}"
     if mx_tsvs is not None and len(mx_tsvs) != len(fastas):
         raise ValueError("one minimizer TSV per FASTA file")
@@ -534,6 +536,12 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         st.mem = _mem
     if assess is not None and (world > 1 or (mx_tsvs is not None and initial_only)):
         raise ValueError("assess needs every genome resident on one GPU (one rank, genomes loaded)")
+    if gaps and (world > 1 or (mx_tsvs is not None and initial_only)):
+        raise ValueError("gaps needs every genome resident on one GPU (one rank, genomes loaded)")
+    if gaps and not isinstance(backend, GpuBackend):
+        raise ValueError("gaps counts on the GPU: it needs the GPU backend's resident genomes and filter")
+    if gaps and not common and common_file is None:
+        raise ValueError("gaps needs the common Bloom filter (common=True or a filter file)")
     st.mark("start")
     if world > 1 and hasattr(backend, "init_comm"):
         backend.init_comm()
@@ -1031,6 +1039,16 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
             eng.outputs[name] = text
         st.stop()
         st.mark("assess_done")
+    if gaps:
+        st.start("gaps")
+        from . import assess as assess_, gaps as gaps_
+        texts = gaps_.report_texts(backend.ctx, {fa.basename(p): genomes[p] for p in fastas}, bf, k, assess_.read_blocks(f"{prefix}.synteny_blocks.tsv"))
+        for name, text in zip((f"{prefix}.gaps.tsv", f"{prefix}.gap_summary.tsv"), texts):
+            with open(name, "w", encoding="utf-8") as fh:
+                fh.write(text)
+            eng.outputs[name] = text
+        st.stop()
+        st.mark("gaps_done")
     memory = st.memory()
     if benchmark and rank == 0:
         st.write(f"{prefix}.stage_times.tsv", memory)
