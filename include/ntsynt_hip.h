@@ -447,6 +447,40 @@ int nts_bf_count_intervals(nts_ctx* ctx, const nts_genome* g, uint32_t k, const 
                            uint64_t* n_kmers, uint64_t* n_hits);
 int nts_genome_valid_bases(nts_ctx* ctx, const nts_genome* g, const nts_interval* iv, uint64_t n_iv, uint64_t* n_valid);
 
+/* ---- where a gap's shared sequence lies in the other genomes: gap links -------------------------------
+ * nts_bf_sample_intervals: the sibling of nts_bf_count_intervals that writes survivors instead of counting them.  A k-mer of
+ *   interval i is sampled when it is valid and lies wholly inside the interval (the counting call's rule, clipping and NTS_EINVAL),
+ *   bf holds it (bit h0 mod (8 * bytes)) and h0 <= UINT64_MAX / rate (integer division; rate >= 1, rate 1 samples every k-mer the
+ *   filter holds).  n_sampled[i] = how many there are; *out = their records in interval order, then k-mer order -- iv = i, off = the
+ *   k-mer's position minus the interval's start (the start clipped to the record) --, *n_out of them; (NULL, 0) when there is none.
+ *   Released with nts_free().  Two launches per 2^23 tiles (timers "bf_sample_count", "bf_sample_write"), no atomic: the output is
+ *   deterministic.  NTS_ERANGE for an interval of 2^32 bases or more and for 2^32 records or more.  csrc/nts_bf_sample.inc.
+ * nts_iv_links: n_lists (at most 64) arrays of such records, one per genome (iv = the interval's index within that genome's
+ *   list), joined by hash.  A hash is usable when no list has it more than once; an anchor of interval a (list A) and interval b
+ *   (list B, A < B) is a usable hash in both; a link is a pair (a, b) with at least min_anchors (>= 1) anchors.  Per link: anchors;
+ *   the smallest and largest off of its anchors in a and in b; fwd / rev = with the anchors ordered by off in a (equal offsets,
+ *   which one sweep's records never have within a link, by hash), the consecutive pairs whose off in b rises / falls.  *out = the
+ *   links sorted by (list_a, iv_a, list_b, iv_b), *n_out of them; (NULL, 0) for no link, an empty input or a single list.  Released
+ *   with nts_free().  Radix sorts, scans and a reduction by key on the context's stream (timers "iv_links_join", "iv_links_pairs",
+ *   "iv_links_select"); NTS_ERANGE for 2^32 records, intervals or anchor pairs or more.  csrc/nts_iv_links.inc.
+ *   ntsynt_amd/gaps.py links, `ntSynt --gap-links`, `bin/ntsynt_gaps --links-out`. */
+typedef struct
+{
+  uint64_t h0;
+  uint32_t iv;
+  uint32_t off;
+} nts_sample;
+typedef struct
+{
+  uint32_t list_a, iv_a, list_b, iv_b;
+  uint32_t anchors, fwd, rev;
+  uint32_t min_off_a, max_off_a, min_off_b, max_off_b;
+} nts_iv_link;
+int nts_bf_sample_intervals(nts_ctx* ctx, const nts_genome* g, uint32_t k, const nts_bf* bf, uint64_t rate, const nts_interval* iv,
+                            uint64_t n_iv, uint64_t* n_sampled, nts_sample** out, uint64_t* n_out);
+int nts_iv_links(nts_ctx* ctx, uint32_t n_lists, const nts_sample* const* lists, const uint64_t* n, uint32_t min_anchors, nts_iv_link** out,
+                 uint64_t* n_out);
+
 /* ---- C1-C5: minimizer graph -> collinear chains -----------------------------------------------------
  * replaces ntjoin_utils.read_minimizers' duplicate removal, filter_minimizers and build_graph
  * (call sites bin/ntsynt_synteny.py:607-612, 483, 539) and the path walk of Ntjoin.find_paths

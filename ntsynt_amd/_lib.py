@@ -25,6 +25,16 @@ class Interval(ctypes.Structure):
     _fields_ = [("rec", u32), ("start", u64), ("end", u64)]
 
 
+class Sample(ctypes.Structure):
+    "nts_sample: a sampled k-mer of an interval (nts_bf_sample_intervals)"
+    _fields_ = [("h0", u64), ("iv", u32), ("off", u32)]
+
+
+class IvLink(ctypes.Structure):
+    "nts_iv_link: a link of two intervals of different lists (nts_iv_links)"
+    _fields_ = [(n, u32) for n in ("list_a", "iv_a", "list_b", "iv_b", "anchors", "fwd", "rev", "min_off_a", "max_off_a", "min_off_b", "max_off_b")]
+
+
 class MxList(ctypes.Structure):
     _fields_ = [("h1", c_vp), ("rec", c_vp), ("pos", c_vp), ("keep", c_vp), ("list_id", c_vp), ("n", u64)]
 
@@ -159,6 +169,8 @@ SYMBOLS = [
     ("nts_minhash_intervals", ctypes.c_int, [c_vp, c_vp, u32, u32, ctypes.POINTER(Interval), u64, c_vp, c_vp, c_vp]),
     ("nts_minhash_intervals_stats", ctypes.c_int, [c_vp, c_u32p, c_u32p, c_u64p]),
     ("nts_bf_count_intervals", ctypes.c_int, [c_vp, c_vp, u32, c_vp, ctypes.POINTER(Interval), u64, c_vp, c_vp]),
+    ("nts_bf_sample_intervals", ctypes.c_int, [c_vp, c_vp, u32, c_vp, u64, ctypes.POINTER(Interval), u64, c_vp, ctypes.POINTER(c_vp), c_u64p]),
+    ("nts_iv_links", ctypes.c_int, [c_vp, u32, ctypes.POINTER(c_vp), c_u64p, u32, ctypes.POINTER(c_vp), c_u64p]),
     ("nts_genome_valid_bases", ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(Interval), u64, c_vp]),
     ("nts_minhash_pairs", ctypes.c_int, [c_vp, u32, c_vp, c_vp, u64, c_vp, c_vp, u64, c_vp, c_vp]),
     ("nts_graph_build", ctypes.c_int, [c_vp, u32, ctypes.POINTER(MxList), ctypes.POINTER(Graph)]),

@@ -72,6 +72,11 @@ def build_parser():
     p.add_argument("--gaps", help="after the run, write <prefix>.gaps.tsv (every stretch of every genome outside the blocks: its N bases and the\n"
                    "share of its k-mers that every genome has, from the common Bloom filter still on the GPU) and <prefix>.gap_summary.tsv",
                    action="store_true")
+    p.add_argument("--gap-links", help="with --gaps (which it implies), write <prefix>.gap_links.tsv: the pairs of gaps of different genomes that\n"
+                   "share sampled k-mers of the common Bloom filter, with the orientation of the shared stretch and whether both gaps lie\n"
+                   "between the same two blocks", action="store_true")
+    p.add_argument("--gap-links-rate", help="sample one in this many of the gap k-mers the filter holds [16]", type=int, default=16)
+    p.add_argument("--gap-links-min", help="anchors (sampled k-mers in common, unique in every genome) a link needs [4]", type=int, default=4)
     p.add_argument("--device", help="GPU index [0]", type=int, default=0)
     # switches for the two btllib details this implementation recalls rather than reads
     p.add_argument("--bf-rounding", help=argparse.SUPPRESS, choices=["up", "down", "none"], default="up")
@@ -145,6 +150,15 @@ def main(argv=None):
                          "ntsynt_block_stats --tsv <prefix>.synteny_blocks.tsv --fai ... --fastas ...")
         if args.assess_k < 1 or args.assess_s < 1:
             parser.error("--assess-k and --assess-s must be positive")
+    if args.gap_links:
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            parser.error("--gap-links works from the genomes resident on one GPU: run it on one rank, or report on the finished run with "
+                         "ntsynt_gaps --tsv <prefix>.synteny_blocks.tsv --fastas ... --common <prefix>.common.bf --links-out <prefix>.gap_links.tsv")
+        if args.no_common:
+            parser.error("--gap-links reads the common Bloom filter: not with --no-common")
+        if args.gap_links_rate < 1 or args.gap_links_min < 1:
+            parser.error("--gap-links-rate and --gap-links-min must be positive")
+        args.gaps = True
     if args.gaps:
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             parser.error("--gaps works from the genomes resident on one GPU: run it on one rank, or report on the finished run with "
@@ -176,7 +190,8 @@ def main(argv=None):
         if not os.path.isfile(fasta):
             raise FileNotFoundError(f"Input file {fasta} not found.")
     plan = ["faidx x%d" % len(fastas)] + ([] if args.no_common else ["make_common_bf"]) + \
-           ["indexlr x%d" % len(fastas), "ntsynt_synteny"] + (["assess"] if args.assess else []) + (["gaps"] if args.gaps else [])
+           ["indexlr x%d" % len(fastas), "ntsynt_synteny"] + (["assess"] if args.assess else []) + (["gaps"] if args.gaps else []) + \
+           (["gap_links"] if args.gap_links else [])
     if args.dry_run:
         say("Stages (GPU, in process):", " -> ".join(plan))
         return 0
@@ -231,7 +246,7 @@ def _run(pipeline, fastas, args, device, quiet):
     pipeline.run(fastas, k=args.k, w=args.w, fpr=args.fpr, prefix=args.prefix, w_rounds=args.w_rounds,
                  indel=args.indel, merge=args.merge, block_size=args.block_size, common=not args.no_common,
                  simplify=not args.no_simplify_graph, device=device, benchmark=args.benchmark,
-                 dev=args.dev, interarrivals=args.interarrivals, assess=(args.assess_k, args.assess_s) if args.assess else None, gaps=args.gaps, repeat=args.repeat, bf_rounding=args.bf_rounding, bf_signature=args.bf_signature or pipeline.BF_SIGNATURE,
+                 dev=args.dev, interarrivals=args.interarrivals, assess=(args.assess_k, args.assess_s) if args.assess else None, gaps=args.gaps, gap_links=(args.gap_links_rate, args.gap_links_min) if args.gap_links else None, repeat=args.repeat, bf_rounding=args.bf_rounding, bf_signature=args.bf_signature or pipeline.BF_SIGNATURE,
                  log=print if (args.dev and int(os.environ.get("RANK", "0")) == 0) else quiet)
 
 

@@ -836,6 +836,23 @@ extern "C" int nts_graph_build(nts_ctx* ctx, uint32_t n_asm, const nts_mxlist* l
   return NTS_OK;
 }
 
+namespace {
+#include "nts_iv_links.inc"
+} // namespace
+
+extern "C" int nts_iv_links(nts_ctx* ctx, uint32_t n_lists, const nts_sample* const* lists, const uint64_t* n, uint32_t min_anchors, nts_iv_link** out,
+                            uint64_t* n_out)
+{
+  if (!ctx || !out || !n_out || min_anchors == 0 || n_lists > IVL_MAX_LISTS || (n_lists && (!lists || !n)))
+    return fail(ctx, NTS_EINVAL, "nts_iv_links: bad arguments (at most 64 lists, min_anchors >= 1)");
+  for (uint32_t l = 0; l < n_lists; ++l)
+    if (n[l] && !lists[l]) return fail(ctx, NTS_EINVAL, "nts_iv_links: NULL list");
+  *out = nullptr;
+  *n_out = 0;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return iv_links_run(ctx, n_lists, lists, n, min_anchors, out, n_out);
+}
+
 extern "C" int nts_graph_budget(nts_ctx* ctx, uint64_t bytes)
 {
   if (!ctx) return NTS_EINVAL;

@@ -40,6 +40,12 @@ def mem_events_since(lib, before):
             "reserve_calls": d["reserve_calls"]}
 
 
+# nts_sample / nts_iv_link (include/ntsynt_hip.h) as numpy records: what Genome.bf_sample_intervals returns and Context.iv_links joins
+SAMPLE_DTYPE = np.dtype([("h0", "<u8"), ("iv", "<u4"), ("off", "<u4")])
+LINK_DTYPE = np.dtype([(n, "<u4") for n in ("list_a", "iv_a", "list_b", "iv_b", "anchors", "fwd", "rev", "min_off_a", "max_off_a", "min_off_b",
+                                            "max_off_b")])
+
+
 class Context:
     """One per GPU (owns a HIP stream)."""
 
@@ -87,6 +93,24 @@ class Context:
         self.check(self.lib.nts_minhash_pairs(self.h, sk.shape[1], sk.ctypes.data, cnt.ctypes.data, sk.shape[0], a.ctypes.data, b.ctypes.data,
                                               a.size, shared.ctypes.data, size.ctypes.data), "nts_minhash_pairs")
         return shared, size
+
+    def iv_links(self, lists, min_anchors):
+        """the sampled k-mers of several lists of intervals joined by hash (nts_iv_links).  lists: one SAMPLE_DTYPE array per genome, as
+        Genome.bf_sample_intervals returns them (iv = the interval's index within that list).  Returns a LINK_DTYPE array sorted by
+        (list_a, iv_a, list_b, iv_b): every pair of intervals of different lists with at least min_anchors hashes in common among
+        those no list has twice."""
+        arrs = [np.ascontiguousarray(a, dtype=SAMPLE_DTYPE) for a in lists]
+        assert SAMPLE_DTYPE.itemsize == ctypes.sizeof(_lib.Sample) and LINK_DTYPE.itemsize == ctypes.sizeof(_lib.IvLink)
+        ptrs = (c_vp * max(len(arrs), 1))(*[a.ctypes.data for a in arrs])
+        counts = np.array([a.size for a in arrs], dtype=np.uint64)
+        p, n = c_vp(), u64()
+        self.check(self.lib.nts_iv_links(self.h, len(arrs), ptrs, counts.ctypes.data_as(_lib.c_u64p), int(min_anchors), ctypes.byref(p),
+                                         ctypes.byref(n)), "nts_iv_links")
+        out = np.empty(n.value, dtype=LINK_DTYPE)
+        if n.value:
+            ctypes.memmove(out.ctypes.data, p.value, out.nbytes)
+        self.lib.nts_free(p)
+        return out
 
     def timing(self, name):
         ms, n = ctypes.c_double(), u64()
@@ -451,6 +475,23 @@ class Genome:
         self.ctx.check(self.ctx.lib.nts_bf_count_intervals(self.ctx.h, self.h, int(k), bf.h, ctypes.cast(iv.ctypes.data, ctypes.POINTER(Interval)), n,
                                                            kmers.ctypes.data, hits.ctypes.data), "nts_bf_count_intervals")
         return kmers, hits
+
+    def bf_sample_intervals(self, bf, intervals, k, rate):
+        """a thin sample of the k-mers of the intervals that the Bloom filter `bf` holds (nts_bf_sample_intervals): those with
+        h0 <= (2^64 - 1) // rate.  intervals as in minhash_intervals.  Returns (records, counts): a SAMPLE_DTYPE array in interval
+        order, then k-mer order (iv = the interval's row, off = the k-mer's position minus the interval's clipped start), and the
+        records per interval [n] uint64.  Exact and deterministic."""
+        iv = self._interval_array(intervals)
+        n = iv.size
+        counts = np.zeros(n, dtype=np.uint64)
+        p, m = c_vp(), u64()
+        self.ctx.check(self.ctx.lib.nts_bf_sample_intervals(self.ctx.h, self.h, int(k), bf.h, int(rate), ctypes.cast(iv.ctypes.data, ctypes.POINTER(Interval)),
+                                                            n, counts.ctypes.data, ctypes.byref(p), ctypes.byref(m)), "nts_bf_sample_intervals")
+        out = np.empty(m.value, dtype=SAMPLE_DTYPE)
+        if m.value:
+            ctypes.memmove(out.ctypes.data, p.value, out.nbytes)
+        self.ctx.lib.nts_free(p)
+        return out, counts
 
     def free(self):
         if self.h:

@@ -4,13 +4,22 @@ Per genome and record the complement of the blocks' intervals is cut into gaps (
 for every gap -- and, as the baseline, for every merged in-block interval -- the k-mers that the run's common Bloom filter holds are
 counted on the GPU in one sweep per genome (report: nts_bf_count_intervals).  A gap whose k-mers are mostly in the filter is sequence
 every genome has and the chaining dropped; one at the filter's occupancy is the genome's own; one without valid k-mers is an assembly
-gap.  docs/design/04_9_gap_content.md."""
+gap.  docs/design/04_9_gap_content.md.
+
+Where a gap's shared sequence lies in the other genomes (`ntSynt --gap-links`, `bin/ntsynt_gaps --links-out`): a thin sample of the gap
+k-mers the filter holds is taken per genome (links: nts_bf_sample_intervals over the gaps only) and joined across genomes by hash on
+the GPU (nts_iv_links); a pair of gaps of two genomes with enough hashes in common is a link, with its orientation from the order of
+the anchors and its placement from the gaps' flanking blocks.  docs/design/04_10_gap_links.md."""
 import os
 from collections import namedtuple
 
 GAP_COLUMNS = ("genome", "contig", "start", "end", "length", "kind", "left_block", "right_block", "n_bases", "kmers", "shared_kmers",
                "shared_fraction", "excess")
 SUMMARY_COLUMNS = ("genome", "part", "intervals", "bases", "n_bases", "kmers", "shared_kmers", "shared_fraction", "excess")
+
+LINK_COLUMNS = ("genome_a", "contig_a", "start_a", "end_a", "left_a", "right_a", "genome_b", "contig_b", "start_b", "end_b", "left_b", "right_b",
+                "anchors", "orientation", "from_a", "to_a", "from_b", "to_b", "sampled_a", "sampled_b", "placement")
+LINKS_RATE, LINKS_MIN = 16, 4                                   # --gap-links-rate / --gap-links-min
 
 # a stretch of `contig` of `genome` outside every block: [start, end); kind: between / leading / trailing / unplaced (the record has no
 # block at all); left_block / right_block: the block that ends at `start` / starts at `end`, "." where there is none
@@ -163,6 +172,66 @@ def report_texts(ctx, genomes_by_name, bf, k, blocks):
     return table(gap_rows, k, bits, occupancy), summary(gap_rows, block_rows, k, bits, occupancy, genomes=list(genomes_by_name))
 
 
+def orientation(fwd, rev):
+    """of a link, from its anchors ordered by their offset in gap a: `+` when more consecutive pairs rise in gap b than fall, `-` when
+    more fall, `.` otherwise (a single anchor included).  The canonical hash carries no strand; the order of the anchors does."""
+    return "+" if fwd > rev else "-" if rev > fwd else "."
+
+
+def placement(a, b):
+    """`same` when the two gaps (rows with left_block / right_block) lie between the same two blocks, in either order -- an inversion
+    or an eroded block --, `other` otherwise -- a translocation; a pair of gaps without any flanking block is never `same`"""
+    fa, fb = {a["left_block"], a["right_block"]}, {b["left_block"], b["right_block"]}
+    return "same" if fa == fb and fa != {"."} else "other"
+
+
+def links(ctx, genomes_by_name, bf, k, gap_rows, rate=LINKS_RATE, min_anchors=LINKS_MIN):
+    """the links between the gaps of different genomes: gap_rows are report()'s (every genome's, in its order); genomes_by_name and bf
+    as for report().  Per genome, ascending by name, one nts_bf_sample_intervals call over its gaps only (the k-mers the filter
+    holds with h0 <= (2^64 - 1) // rate; a genome given as a loader is freed after its sweep), then one nts_iv_links over all of
+    them on ctx: a hash no genome has twice among its sampled gap k-mers is an anchor of every two gaps that have it, and two gaps
+    with at least min_anchors anchors are a link.  Returns one dict per link with LINK_COLUMNS' keys, in the join's order: by
+    genome a, gap a, genome b, gap b (a before b in the order of the names)."""
+    if rate < 1 or min_anchors < 1:
+        raise ValueError("links: rate and min_anchors must be at least 1")
+    names = sorted(genomes_by_name)
+    rows_of = {name: [r for r in gap_rows if r["genome"] == name] for name in names}
+    lists, sampled = [], []
+    for name in names:
+        g = genomes_by_name[name]
+        loaded = callable(g)
+        if loaded:
+            g = g()
+        try:
+            rec_of = {c: j for j, c in enumerate(g.names)}
+            rec, counts = g.bf_sample_intervals(bf, [(rec_of[r["contig"]], r["start"], r["end"]) for r in rows_of[name]], k, rate)
+        finally:
+            if loaded:
+                g.free()
+        lists.append(rec)
+        sampled.append(counts)
+    out = []
+    for ln in ctx.iv_links(lists, min_anchors):
+        la, lb = int(ln["list_a"]), int(ln["list_b"])
+        a, b = rows_of[names[la]][int(ln["iv_a"])], rows_of[names[lb]][int(ln["iv_b"])]
+        row = {"anchors": int(ln["anchors"]), "orientation": orientation(int(ln["fwd"]), int(ln["rev"])), "placement": placement(a, b)}
+        for x, r, lst in (("a", a, la), ("b", b, lb)):
+            row.update({f"genome_{x}": r["genome"], f"contig_{x}": r["contig"], f"start_{x}": r["start"], f"end_{x}": r["end"],
+                        f"left_{x}": r["left_block"], f"right_{x}": r["right_block"], f"from_{x}": r["start"] + int(ln[f"min_off_{x}"]),
+                        f"to_{x}": r["start"] + int(ln[f"max_off_{x}"]) + int(k), f"sampled_{x}": int(sampled[lst][int(ln[f"iv_{x}"])])})
+        out.append(row)
+    return out
+
+
+def links_table(rows, k, rate, min_anchors, bits):
+    "<prefix>.gap_links.tsv: a header, one line per link (links()' rows, in their order), then `# k K, rate R, min_anchors M, filter BITS bits`"
+    lines = ["\t".join(LINK_COLUMNS)]
+    for r in rows:
+        lines.append("\t".join(str(r[c]) for c in LINK_COLUMNS))
+    lines.append(f"# k {int(k)}, rate {int(rate)}, min_anchors {int(min_anchors)}, filter {int(bits)} bits")
+    return "\n".join(lines) + "\n"
+
+
 def main(argv=None):
     "bin/ntsynt_gaps"
     import argparse
@@ -174,8 +243,13 @@ def main(argv=None):
     p.add_argument("--common", help="the run's common Bloom filter (<prefix>.common.bf); k is read from its header", required=True)
     p.add_argument("--out", help="file for the per-gap table [stdout]")
     p.add_argument("--summary-out", help="file for the per-genome summary [stdout, after the table]")
+    p.add_argument("--links-out", help="also write the links between the gaps of different genomes to this file (<prefix>.gap_links.tsv)")
+    p.add_argument("--links-rate", help=f"sample one in this many of the gap k-mers the filter holds [{LINKS_RATE}]", type=int, default=LINKS_RATE)
+    p.add_argument("--links-min", help=f"anchors a link needs [{LINKS_MIN}]", type=int, default=LINKS_MIN)
     p.add_argument("--device", help="GPU index [0]", type=int, default=0)
     args = p.parse_args(argv)
+    if args.links_rate < 1 or args.links_min < 1:
+        p.error("--links-rate and --links-min must be positive")
     for path in args.fastas + [args.common, args.tsv]:
         if not os.path.isfile(path):
             raise FileNotFoundError(f"Input file {path} not found.")
@@ -191,7 +265,12 @@ def main(argv=None):
         del bits
         loaders = {basename(path): (lambda path=path: read_fasta_device(ctx, path)[0]) for path in args.fastas}
         try:
-            texts = report_texts(ctx, loaders, bf, k, read_blocks(args.tsv))
+            gap_rows, block_rows, n_bits, occupancy = report(ctx, loaders, bf, k, read_blocks(args.tsv))
+            texts = table(gap_rows, k, n_bits, occupancy), summary(gap_rows, block_rows, k, n_bits, occupancy, genomes=list(loaders))
+            if args.links_out:
+                link_rows = links(ctx, loaders, bf, k, gap_rows, args.links_rate, args.links_min)
+                with open(args.links_out, "w", encoding="utf-8") as fh:
+                    fh.write(links_table(link_rows, k, args.links_rate, args.links_min, n_bits))
         finally:
             bf.free()
     finally:

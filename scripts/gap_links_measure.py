@@ -1,0 +1,132 @@
+"""Measurement behind docs/design/04_10_gap_links.md "Measured": the two launches of nts_bf_sample_intervals (k_bf_sample<false> counts,
+k_bf_sample<true> writes) against k_bf_count_intervals on the same genome, the same intervals and the same filter in the same process,
+and nts_iv_links on three genomes' samples.
+
+    python scripts/gap_links_measure.py [--bp 3000000000] [--calls 6] [--out FILE.json]
+
+A 3 Gbp synthetic genome (24 contigs) cut into 10^4 tiling intervals, the common filter of the three-genome 1 % family.  The launches
+are timed with device events (nts_timing), the whole call with the host clock around it.  Rate 1 writes a record for every k-mer the
+filter holds -- 16 bytes each, copied to the host --, so it is taken over the first tenth of the intervals.  Run it under
+`rocprofv3 --kernel-trace --stats -- python scripts/gap_links_measure.py` for the kernel times of the trace, in a run of its own.
+Needs the GPU: there is no fallback."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+import numpy as np  # noqa: E402
+
+from ntsynt_amd.device import BloomFilter, Context, Genome, bf_size_bytes  # noqa: E402
+
+SEED, DIVERGENCE = 20240207, 0.005                              # scripts/gaps_measure.py's family
+
+
+def tiling(g, n):
+    "n intervals of equal length that tile the records of g"
+    per_rec = max(1, n // len(g.names))
+    rows = []
+    for rec, length in enumerate(int(x) for x in g.rec_len):
+        step = -(-length // per_rec)
+        rows += [(rec, a, min(a + step, length)) for a in range(0, length, step)]
+    return np.array(rows, dtype=np.uint64)
+
+
+def timed(ctx, names, fn, calls):
+    """per timer of `names` the (median, min, max) ms per launch by device events over `calls` calls of fn and the timed launches per
+    call; the host-clock ms of the calls"""
+    per = {n: [] for n in names}
+    counted = {n: set() for n in names}
+    host = []
+    for _ in range(calls):
+        before = {n: ctx.timing(n) for n in names}
+        t0 = time.perf_counter()
+        fn()
+        ctx.sync()
+        host.append((time.perf_counter() - t0) * 1e3)
+        for n in names:
+            ms1, n1 = ctx.timing(n)
+            per[n].append((ms1 - before[n][0]) / max(n1 - before[n][1], 1))
+            counted[n].add(int(n1 - before[n][1]))
+    out = {n: {"median_ms": statistics.median(per[n]), "min_ms": min(per[n]), "max_ms": max(per[n]), "timed_launches_per_call": sorted(counted[n])}
+           for n in names}
+    out["calls"] = calls
+    out["host_ms_median"] = statistics.median(host)
+    return out
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("--bp", type=int, default=3_000_000_000)
+    p.add_argument("--k", type=int, default=24)
+    p.add_argument("--calls", type=int, default=6)
+    p.add_argument("--intervals", type=int, default=10_000)
+    p.add_argument("--min-anchors", type=int, default=4)
+    p.add_argument("--no-join", action="store_true", help="the sampling launches only")
+    p.add_argument("--out")
+    args = p.parse_args()
+    k = args.k
+    ctx = Context(0)
+    synth = lambda j: Genome.synth(ctx, args.bp, 24, SEED, 1000 + j, DIVERGENCE)      # noqa: E731
+    g = synth(0)
+    _, nbytes = bf_size_bytes(g.total_bp, 0.025)
+    bf = BloomFilter(ctx, nbytes, k)
+    bf.insert(g)
+    for j in (1, 2):                                            # the family's other two genomes, one resident at a time
+        other = synth(j)
+        bf.insert_and(other)
+        other.free()
+    out = {"bp": args.bp, "k": k, "filter_bytes": nbytes, "occupancy": bf.get_fpr(), "valid_kmers": g.valid_kmers(k)}
+    iv = tiling(g, args.intervals)
+    tenth = iv[:max(1, iv.shape[0] // 10)]
+    ctx.profile(2)
+    kmers, hits = g.bf_count_intervals(bf, iv, k)             # warm-up, and the figures themselves
+    out["intervals"], out["kmers"], out["held"] = int(iv.shape[0]), int(kmers.sum()), int(hits.sum())
+    # the yardstick: the counting launch, which probes every k-mer
+    out["bf_count_iv"] = timed(ctx, ["bf_count_iv"], lambda: g.bf_count_intervals(bf, iv, k), args.calls)
+    sample_timers = ["bf_sample_count", "bf_sample_write"]
+    rec, _ = g.bf_sample_intervals(bf, iv, k, 16)
+    out["rate16"] = dict(timed(ctx, sample_timers, lambda: g.bf_sample_intervals(bf, iv, k, 16), args.calls), records=int(rec.size))
+    both = out["rate16"]["bf_sample_count"]["median_ms"] + out["rate16"]["bf_sample_write"]["median_ms"]
+    out["rate16"]["both_launches_ms"] = both
+    out["rate16"]["ratio_to_count_launch"] = both / out["bf_count_iv"]["bf_count_iv"]["median_ms"]
+    k10, h10 = g.bf_count_intervals(bf, tenth, k)
+    out["tenth"] = {"intervals": int(tenth.shape[0]), "kmers": int(k10.sum()), "held": int(h10.sum()),
+                    "bf_count_iv": timed(ctx, ["bf_count_iv"], lambda: g.bf_count_intervals(bf, tenth, k), args.calls)}
+    r1, _ = g.bf_sample_intervals(bf, tenth, k, 1)
+    assert r1.size == int(h10.sum())
+    out["tenth"]["rate1"] = dict(timed(ctx, sample_timers, lambda: g.bf_sample_intervals(bf, tenth, k, 1), args.calls), records=int(r1.size))
+    del r1
+    out["tenth"]["rate16"] = timed(ctx, sample_timers, lambda: g.bf_sample_intervals(bf, tenth, k, 16), args.calls)
+    if not args.no_join:
+        # three such lists: every genome of the family sampled over its own tiling, joined
+        lists = [rec]
+        g.free()
+        for j in (1, 2):
+            other = synth(j)
+            lists.append(other.bf_sample_intervals(bf, tiling(other, args.intervals), k, 16)[0])
+            other.free()
+        join_timers = ["iv_links_join", "iv_links_pairs", "iv_links_select"]
+        ctx.profile(1)
+        links = ctx.iv_links(lists, args.min_anchors)
+        out["join"] = dict(timed(ctx, join_timers, lambda: ctx.iv_links(lists, args.min_anchors), max(3, args.calls // 2)),
+                           records=[int(x.size) for x in lists], links=int(links.size), anchors=int(links["anchors"].sum()) if links.size else 0)
+    else:
+        g.free()
+    ctx.profile(False)
+    text = json.dumps(out, indent=1)
+    print(text)
+    if args.out:
+        with open(args.out, "w", encoding="utf-8") as fh:
+            fh.write(text + "\n")
+    # the comparison holds only if each call timed exactly one launch of each kernel
+    assert out["bf_count_iv"]["bf_count_iv"]["timed_launches_per_call"] == [1], out
+    assert all(out["rate16"][t]["timed_launches_per_call"] == [1] for t in sample_timers), out
+    bf.free()
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
