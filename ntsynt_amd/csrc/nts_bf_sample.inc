@@ -1,7 +1,7 @@
 // ---- a thin sample of the k-mers of many intervals that a Bloom filter holds (nts_bf_sample_intervals; ntsynt_amd/gaps.py links) ----
 // docs/design/04_10_gap_links.md.  The sibling of k_bf_count_intervals (nts_bf_iv.inc) that writes survivors instead of counting them:
-// the same tiles from the same cutter (nts_iv_cut.inc), the same two paths (bases staged through LDS for k <= FAST_K_MAX, per-lane
-// loads above), one workgroup per tile, a lane rolls 32 consecutive k-mers.  A k-mer survives when h0 <= UINT64_MAX / rate AND the
+// the same tiles from the same cutter and host driver (nts_iv_cut.inc), the same sweep of a tile (nts_tile_sweep.inc: this file holds
+// the policy only), one workgroup per tile, a lane rolls 32 consecutive k-mers.  A k-mer survives when h0 <= UINT64_MAX / rate AND the
 // filter holds it; its record is {h0, interval, offset of the k-mer from the interval's (clipped) start}.
 //   two launches over the same tiles, no atomic:
 //     k_bf_sample<false>  every lane gathers the survivors among its 32 k-mers as a bit mask; the workgroup adds the popcounts (wave
@@ -27,47 +27,12 @@ struct SampleRec // == nts_sample (include/ntsynt_hip.h)
 };
 static_assert(sizeof(SampleRec) == 16 && sizeof(nts_sample) == 16, "sample records are 16 bytes");
 
-// the survivors among the n_mine (1 .. 32) k-mers of a lane, bit j = its j-th k-mer; base(i) = base i of the lane's stretch
-template <typename BaseAt>
-__device__ __forceinline__ uint32_t bfs_mask(const HashParams& hp, const uint64_t* s_tab, uint32_t n_mine, BaseAt&& base,
-                                             const uint32_t* __restrict__ bf, const FastMod& fm, uint64_t thresh)
-{
-  const uint32_t k = hp.k;
-  uint64_t f = 0, r = 0;
-  hash_init(hp, base, f, r);
-  uint32_t mask = 0, s = 0;
-#pragma unroll 1
-  for (uint32_t b0 = 0; b0 < 32; b0 += BFS_BATCH) {
-    if (b0 >= n_mine) break;
-    uint32_t wd[BFS_BATCH], bit[BFS_BATCH];
-#pragma unroll
-    for (int u = 0; u < BFS_BATCH; ++u) { // (a lane with fewer than 32 k-mers rolls on inside the bytes the tile may read and probes nothing for those)
-      const uint64_t h0 = f + r;
-      wd[u] = 0;
-      bit[u] = 0;
-      if (b0 + u < n_mine && h0 <= thresh) {
-        const uint64_t idx = fm(h0);
-        wd[u] = bf[bf_word(idx)];
-        bit[u] = bf_bit(idx);
-      }
-      const uint32_t cout = base(s), cin = base(s + k);
-      f = srol1(f) ^ s_tab[cin * 4 + cout];
-      r = sror1(r ^ s_tab[16 + cin * 4 + cout]);
-      ++s;
-    }
-#pragma unroll
-    for (int u = 0; u < BFS_BATCH; ++u) mask |= ((wd[u] >> bit[u]) & 1u) << (b0 + u);
-  }
-  return mask;
-}
-
 // the second roll of the write launch: the records of the k-mers in `mask`, in k-mer order, from out[0] on
 template <typename BaseAt>
 __device__ __forceinline__ void bfs_emit(const HashParams& hp, const uint64_t* s_tab, uint32_t mask, BaseAt&& base, uint32_t iv, uint32_t off0,
                                          SampleRec* __restrict__ out)
 {
-  const uint32_t k = hp.k;
-  const uint32_t last = 31u - (uint32_t)__clz((int)mask);
+  const uint32_t last = 31u - (uint32_t)__builtin_clz(mask); // (mask != 0: the caller checks)
   uint64_t f = 0, r = 0;
   hash_init(hp, base, f, r);
   for (uint32_t j = 0;; ++j) {
@@ -81,9 +46,7 @@ __device__ __forceinline__ void bfs_emit(const HashParams& hp, const uint64_t* s
       *reinterpret_cast<uint4*>(out++) = v;
     }
     if (j >= last) break;
-    const uint32_t cout = base(j), cin = base(j + k);
-    f = srol1(f) ^ s_tab[cin * 4 + cout];
-    r = sror1(r ^ s_tab[16 + cin * 4 + cout]);
+    hash_roll(s_tab, base, j, hp.k, f, r);
   }
 }
 
@@ -98,65 +61,39 @@ __global__ __launch_bounds__(HASH_THREADS) void k_bf_sample(const uint8_t* __res
   __shared__ uint64_t s_tab[36];
   __shared__ uint32_t s_seq[SEQ_LDS_DWORDS];
   __shared__ uint32_t s_w[HASH_THREADS / 64];
-  const uint32_t tid = threadIdx.x;
-  if (tid < 16) {
-    s_tab[tid] = hp.roll_f[tid];
-    s_tab[16 + tid] = hp.roll_r[tid];
-  }
-  if (tid < 4) s_tab[32 + tid] = hp.seed[tid];
-  const uint32_t k = hp.k;
   const IvTile tile = tiles[blockIdx.x];
-  const uint32_t tile_len = min(tile.len, KEY_TILE);
-  const uint32_t first = 32u * tid;
-  const uint32_t n_mine = first < tile_len ? min(32u, tile_len - first) : 0u;
-  const bool staged = k <= FAST_K_MAX;
-  const uint32_t a = (uint32_t)(tile.pos & 15u);
-  if (staged) {
-    // ---- the tile's bases into LDS: 16-byte loads, 4 bytes of padding per 32 (lane stride 36 B: conflict-free byte reads)
-    const uint8_t* src = code + (tile.pos - a);
-    const uint32_t n_bytes = a + tile_len + k - 1;
-    const uint32_t n16 = (n_bytes + 15u) >> 4;
-    for (uint32_t c = tid; c < n16; c += HASH_THREADS) {
-      const uint4 v = *reinterpret_cast<const uint4*>(src + 16u * c);
-      const uint32_t d = 4u * c + (c >> 1);
-      s_seq[d] = v.x;
-      s_seq[d + 1] = v.y;
-      s_seq[d + 2] = v.z;
-      s_seq[d + 3] = v.w;
-    }
-  }
-  __syncthreads();
-  const uint8_t* sb = reinterpret_cast<const uint8_t*>(s_seq);
-  const uint32_t s0 = a + first;
-  auto base_lds = [&](uint32_t i) -> uint32_t { const uint32_t s = s0 + i; return sb[s + 4u * (s >> 5)] & 3u; };
-  // k > FAST_K_MAX: the bases do not fit the staging area; every lane reads its own (the tile lies inside one stretch of valid bases)
-  const uint8_t* p = code + tile.pos + first;
-  auto base_mem = [&](uint32_t i) -> uint32_t { return p[i] & 3u; };
+  const TileLane lane = tile_enter(s_tab, s_seq, code, tile.pos, tile.len, hp);
+  // the survivors among the lane's k-mers, bit j = its j-th k-mer
   uint32_t mask = 0;
-  if (n_mine) mask = staged ? bfs_mask(hp, s_tab, n_mine, base_lds, bf, fm, thresh) : bfs_mask(hp, s_tab, n_mine, base_mem, bf, fm, thresh);
-  uint32_t mine = __popc(mask);
+  uint32_t wd[BFS_BATCH], bit[BFS_BATCH];
+  lane.sweep(
+    hp, s_tab,
+    [&](uint32_t j, int u, uint64_t h0) { // (nothing is probed for a k-mer past the lane's last)
+      wd[u] = 0;
+      bit[u] = 0;
+      if (j < lane.n_mine && h0 <= thresh) {
+        const uint64_t idx = fm(h0);
+        wd[u] = bf[bf_word(idx)];
+        bit[u] = bf_bit(idx);
+      }
+    },
+    [&](uint32_t b0) {
+#pragma unroll
+      for (int u = 0; u < BFS_BATCH; ++u) mask |= ((wd[u] >> bit[u]) & 1u) << (b0 + u);
+    });
+  const uint32_t mine = __popc(mask);
   if (!WRITE) {
-    // ---- the tile's survivors: lanes -> wave -> workgroup, one plain store
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) mine += __shfl_down(mine, d, 64);
-    if ((tid & 63u) == 0) s_w[tid >> 6] = mine;
-    __syncthreads();
-    if (tid == 0) {
-      uint32_t sum = 0;
-#pragma unroll
-      for (int wv = 0; wv < HASH_THREADS / 64; ++wv) sum += s_w[wv];
-      tile_cnt[blockIdx.x] = sum;
-    }
+    block_sum_store(mine, s_w, tile_cnt + blockIdx.x);
   } else {
     uint32_t total;
     const uint32_t slot = block_excl_scan_256(mine, s_w, &total);
     const uint64_t at = tile_at[blockIdx.x] + slot;
     if (mask && at + mine <= n_out) {
-      const uint32_t off0 = tile_off0[blockIdx.x] + first;
-      if (staged)
-        bfs_emit(hp, s_tab, mask, base_lds, tile.iv, off0, out + at);
+      const uint32_t off0 = tile_off0[blockIdx.x] + lane.first;
+      if (lane.staged)
+        bfs_emit(hp, s_tab, mask, lane.lds, tile.iv, off0, out + at);
       else
-        bfs_emit(hp, s_tab, mask, base_mem, tile.iv, off0, out + at);
+        bfs_emit(hp, s_tab, mask, lane.mem, tile.iv, off0, out + at);
     }
   }
 }
@@ -167,30 +104,24 @@ int bf_sample_intervals_run(nts_ctx* ctx, const nts_genome* g, uint32_t k, const
   *out = nullptr;
   *n_out = 0;
   if (n_iv == 0) return NTS_OK;
-  std::vector<IvPiece> pieces;
-  std::vector<uint64_t> piece_at, nk;
+  std::vector<uint64_t> nk;
+  std::vector<IvTile> tiles;
+  HashParams hp;
   {
-    const int rc = iv_cut_pieces(ctx, g, k, iv, n_iv, "nts_bf_sample_intervals", pieces, piece_at, nk);
+    const int rc = iv_cut_tiles(ctx, g, k, iv, n_iv, "nts_bf_sample_intervals", nk, tiles, &hp);
     if (rc) return rc;
   }
-  if (n_iv > 0xFFFFFFFFull) return fail(ctx, NTS_ERANGE, "nts_bf_sample_intervals: more than 2^32 - 1 intervals in one call");
-  std::vector<IvTile> tiles;
-  std::vector<uint32_t> off0;
+  std::vector<uint64_t> iv_a(n_iv); // the intervals' (clipped) starts, as iv_cut_pieces clips
   for (uint64_t i = 0; i < n_iv; ++i) {
     n_sampled[i] = 0;
     const uint64_t len = g->rec_len[iv[i].rec];
-    const uint64_t a = g->rec_off[iv[i].rec] + std::min(iv[i].start, len), b = g->rec_off[iv[i].rec] + std::min(iv[i].end, len); // (as iv_cut_pieces clips)
+    const uint64_t a = g->rec_off[iv[i].rec] + std::min(iv[i].start, len), b = g->rec_off[iv[i].rec] + std::min(iv[i].end, len);
     if (b > a && b - a > 0xFFFFFFFFull) return fail(ctx, NTS_ERANGE, "nts_bf_sample_intervals: an interval of 2^32 bases or more (offsets are 32-bit)");
-    const size_t t0 = tiles.size();
-    iv_append_tiles(pieces, piece_at, i, (uint32_t)i, tiles);
-    for (size_t t = t0; t < tiles.size(); ++t) off0.push_back((uint32_t)(tiles[t].pos - a));
+    iv_a[i] = a;
   }
   if (tiles.empty()) return NTS_OK;
-  HashParams hp;
-  {
-    const int rc = hash_params_for(ctx, k, &hp);
-    if (rc) return rc;
-  }
+  std::vector<uint32_t> off0(tiles.size());
+  for (size_t t = 0; t < tiles.size(); ++t) off0[t] = (uint32_t)(tiles[t].pos - iv_a[tiles[t].iv]);
   const FastMod fm = make_fastmod(bf->bytes * 8);
   const uint64_t thresh = ~0ULL / rate;
   const size_t nt = tiles.size();
@@ -206,28 +137,21 @@ int bf_sample_intervals_run(nts_ctx* ctx, const nts_genome* g, uint32_t k, const
       return rc;
     }
   }
-  uint64_t slice = (uint64_t)1 << 23; // tiles per launch: 2^31 work-items
-  if (const char* v = NTS_KNOB("NTS_BF_SAMPLE_SLICE")) slice = std::min<uint64_t>(std::max<uint64_t>(strtoull(v, nullptr, 0), 1), slice);
-  for (uint64_t t0 = 0; t0 < nt; t0 += slice) {
-    const uint32_t n = (uint32_t)std::min<uint64_t>(slice, nt - t0);
-    ScopedTimer t(ctx, "bf_sample_count", true);
+  const uint64_t slice = iv_slice(NTS_KNOB("NTS_BF_SAMPLE_SLICE"));
+  iv_for_slices(ctx, "bf_sample_count", nt, slice, [&](uint64_t t0, uint32_t n) {
     NTS_LAUNCH(k_bf_sample<false>, dim3(n), dim3(HASH_THREADS), 0, ctx->stream, g->d_code + PAD, d_tiles + t0, d_off0 + t0, bf->d_words, fm, thresh,
                d_cnt + t0, (const uint64_t*)nullptr, (SampleRec*)nullptr, (uint64_t)0, hp);
-  }
-  std::vector<uint32_t> cnt(nt);
+  });
+  std::vector<uint32_t> cnt;
   {
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(cnt.data(), d_cnt, nt * 4, hipMemcpyDeviceToHost, ctx->stream);
-    const hipError_t e_sync = hipStreamSynchronize(ctx->stream); // (whatever happened: the host vectors are read and written by asynchronous copies)
-    HIP_TRY(ctx, e);
-    HIP_TRY(ctx, e_sync);
+    const int rc = iv_counts_back(ctx, d_cnt, tiles, cnt, n_sampled);
+    if (rc) return rc;
   }
   std::vector<uint64_t> at(nt);
   uint64_t total = 0;
   for (size_t t = 0; t < nt; ++t) {
     at[t] = total;
     total += cnt[t];
-    n_sampled[tiles[t].iv] += cnt[t];
   }
   if (total > 0xFFFFFFFFull) return fail(ctx, NTS_ERANGE, "nts_bf_sample_intervals: 2^32 records or more (raise the rate or pass fewer intervals)");
   if (total == 0) return NTS_OK;
@@ -236,12 +160,10 @@ int bf_sample_intervals_run(nts_ctx* ctx, const nts_genome* g, uint32_t k, const
   if (!host) return fail(ctx, NTS_ENOMEM, "nts_bf_sample_intervals: host memory for the records");
   hipError_t e = hipMemcpyAsync(d_at, at.data(), nt * 8, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) {
-    for (uint64_t t0 = 0; t0 < nt; t0 += slice) {
-      const uint32_t n = (uint32_t)std::min<uint64_t>(slice, nt - t0);
-      ScopedTimer t(ctx, "bf_sample_write", true);
+    iv_for_slices(ctx, "bf_sample_write", nt, slice, [&](uint64_t t0, uint32_t n) {
       NTS_LAUNCH(k_bf_sample<true>, dim3(n), dim3(HASH_THREADS), 0, ctx->stream, g->d_code + PAD, d_tiles + t0, d_off0 + t0, bf->d_words, fm, thresh,
                  (uint32_t*)nullptr, (const uint64_t*)(d_at + t0), d_out, total, hp);
-    }
+    });
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpyAsync(host, d_out, total * sizeof(SampleRec), hipMemcpyDeviceToHost, ctx->stream);

@@ -1,6 +1,6 @@
 // ---- bottom-s MinHash sketches of many intervals of a resident genome (nts_minhash_intervals; ntsynt_amd/assess.py) -------------
 // One sweep serves every interval of a call (docs/design/04_8_block_assessment.md).  The host cuts the intervals into tiles of valid
-// k-mers (nts_iv_cut.inc, shared with nts_bf_count_intervals); a workgroup hashes one tile as k_hash's fast path does.
+// k-mers (nts_iv_cut.inc); a workgroup sweeps one tile (nts_tile_sweep.inc) and inserts what the tile's interval keeps.
 //   survivors: per-interval open-addressing sets (MhSet, next to k_hash; mhi_insert below), NOT an (interval, h0) list sorted and made
 //        unique afterwards: a set removes copies where they arise, so that a satellite array -- 10^5 k-mers, a few hundred distinct
 //        hashes, all of them below any threshold that keeps s of them -- fills a few hundred slots; in a list its copies overflow
@@ -54,14 +54,7 @@ __global__ __launch_bounds__(HASH_THREADS) void k_minhash_intervals(const uint8_
   __shared__ uint64_t s_tab[36];
   __shared__ uint32_t s_seq[SEQ_LDS_DWORDS];
   __shared__ unsigned long long s_added;
-  const uint32_t tid = threadIdx.x;
-  if (tid < 16) {
-    s_tab[tid] = hp.roll_f[tid];
-    s_tab[16 + tid] = hp.roll_r[tid];
-  }
-  if (tid < 4) s_tab[32 + tid] = hp.seed[tid];
-  if (tid == 0) s_added = 0;
-  const uint32_t k = hp.k;
+  if (threadIdx.x == 0) s_added = 0;
   const IvTile tile = tiles[blockIdx.x];
   const MhiState st = state[tile.iv];
   MhSet mh;
@@ -73,69 +66,20 @@ __global__ __launch_bounds__(HASH_THREADS) void k_minhash_intervals(const uint8_
   // an interval whose count is past its limit already is swept again with a lower tau: its remaining tiles of this pass do nothing
   // (the whole workgroup leaves: the value is read once, by a load every lane shares)
   if (__hip_atomic_load(mh.count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > mh.limit) return;
+  const TileLane lane = tile_enter(s_tab, s_seq, code, tile.pos, tile.len, hp);
   unsigned long long added = 0;
-  const uint32_t tile_len = min(tile.len, KEY_TILE);
-  const uint32_t first = 32u * tid;
-  const uint32_t n_mine = first < tile_len ? min(32u, tile_len - first) : 0u;
-  if (k > FAST_K_MAX) {
-    // ---- long k-mers: the bases do not fit the staging area; every lane reads its own from the L2 (the tile lies inside one stretch
-    //      of valid bases, so positions are plain offsets) and never looks past its last k-mer
-    __syncthreads();
-    if (n_mine) {
-      const uint8_t* p = code + tile.pos + first;
-      uint64_t f = 0, r = 0;
-      hash_init(hp, [&](uint32_t i) -> uint32_t { return p[i] & 3u; }, f, r);
-      for (uint32_t i = 0;;) {
-        const uint64_t h = f + r;
-        if (h < mh.tau) added += mhi_insert(mh, h);
-        if (++i >= n_mine) break;
-        const uint32_t cout = p[0] & 3u, cin = p[k] & 3u;
-        f = srol1(f) ^ s_tab[cin * 4 + cout];
-        r = sror1(r ^ s_tab[16 + cin * 4 + cout]);
-        ++p;
-      }
-    }
-  } else {
-  // ---- the tile's bases into LDS: 16-byte loads, 4 bytes of padding per 32 (lane stride 36 B: conflict-free byte reads)
-  const uint32_t a = (uint32_t)(tile.pos & 15u);
-  const uint8_t* src = code + (tile.pos - a);
-  const uint32_t n_bytes = a + tile_len + k - 1;
-  const uint32_t n16 = (n_bytes + 15u) >> 4;
-  for (uint32_t c = tid; c < n16; c += HASH_THREADS) {
-    const uint4 v = *reinterpret_cast<const uint4*>(src + 16u * c);
-    const uint32_t d = 4u * c + (c >> 1);
-    s_seq[d] = v.x;
-    s_seq[d + 1] = v.y;
-    s_seq[d + 2] = v.z;
-    s_seq[d + 3] = v.w;
-  }
-  __syncthreads();
-  const uint8_t* sb = reinterpret_cast<const uint8_t*>(s_seq);
-  auto base_at = [&](uint32_t s) -> uint32_t { return sb[s + 4u * (s >> 5)] & 3u; };
-  uint32_t s = a + first;
-  uint64_t f = 0, r = 0;
-  if (n_mine) hash_init(hp, [&](uint32_t i) { return base_at(s + i); }, f, r);
-#pragma unroll 1
-  for (uint32_t b0 = 0; b0 < 32; b0 += 8) {
-    if (b0 >= n_mine) break;
-    uint64_t h[8];
+  uint64_t h[8];
+  lane.sweep(
+    hp, s_tab, [&](uint32_t, int u, uint64_t h0) { h[u] = h0; },
+    [&](uint32_t b0) { // (the inserts behind the batch's hashing: their probe loops diverge)
 #pragma unroll
-    for (int u = 0; u < 8; ++u) { // (a lane with fewer than 32 k-mers rolls on inside the staging area; what it computes there is not used)
-      h[u] = f + r;
-      const uint32_t cout = base_at(s), cin = base_at(s + k);
-      f = srol1(f) ^ s_tab[cin * 4 + cout];
-      r = sror1(r ^ s_tab[16 + cin * 4 + cout]);
-      ++s;
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u)
-      if (b0 + u < n_mine && h[u] < mh.tau) added += mhi_insert(mh, h[u]);
-  }
-  }
+      for (int u = 0; u < 8; ++u)
+        if (b0 + u < lane.n_mine && h[u] < mh.tau) added += mhi_insert(mh, h[u]);
+    });
   // ---- the tile's new hashes onto the interval's counter: one atomic per workgroup
   if (added) atomicAdd(&s_added, added);
   __syncthreads();
-  if (tid == 0 && s_added) atomicAdd(mh.count, s_added);
+  if (threadIdx.x == 0 && s_added) atomicAdd(mh.count, s_added);
 }
 
 // the sets and counts of the listed intervals back to empty (a retry pass)
@@ -239,12 +183,9 @@ int minhash_intervals_chunk(nts_ctx* ctx, const nts_genome* g, const HashParams&
     if (!tiles.empty()) {
       IvTile* d_tiles = nullptr;
       MHI_RC(ws_upload(ctx, "mhi_tiles", tiles, &d_tiles));
-      ScopedTimer t(ctx, "minhash_iv", true);
-      constexpr uint64_t SLICE = (uint64_t)1 << 23; // tiles per launch: 2^31 work-items
-      for (uint64_t t0 = 0; t0 < tiles.size(); t0 += SLICE) {
-        const uint32_t nt = (uint32_t)std::min<uint64_t>(SLICE, tiles.size() - t0);
+      iv_for_slices(ctx, "minhash_iv", tiles.size(), iv_slice(nullptr), [&](uint64_t t0, uint32_t nt) {
         NTS_LAUNCH(k_minhash_intervals, dim3(nt), dim3(HASH_THREADS), 0, ctx->stream, g->d_code + PAD, d_tiles + t0, d_state, d_slots, d_counts, hp);
-      }
+      });
       MHI_HIP(hipGetLastError());
     }
     ++passes;

@@ -1712,18 +1712,7 @@ __global__ __launch_bounds__(HASH_THREADS) void k_hash_accept(AcceptParams P)
   };
   if (single) {
     const uint64_t P0 = P.run_pos[lo] + (J0 - v0);
-    a = (uint32_t)(P0 & 15u);
-    const uint8_t* src = P.code + (P0 - a);
-    const uint32_t n_bytes = a + tile_len + k - 1;
-    const uint32_t n16 = (n_bytes + 15u) >> 4;
-    for (uint32_t c = tid; c < n16; c += HASH_THREADS) {
-      const uint4 v = *reinterpret_cast<const uint4*>(src + 16u * c);
-      const uint32_t d = 4u * c + (c >> 1);
-      s_seq[d] = v.x;
-      s_seq[d + 1] = v.y;
-      s_seq[d + 2] = v.z;
-      s_seq[d + 3] = v.w;
-    }
+    a = seq_stage(s_seq, P.code, P0, tile_len, k, tid);
     __syncthreads();
     uint32_t s = a + first;
     uint64_t f = 0, r = 0;
@@ -1735,6 +1724,7 @@ __global__ __launch_bounds__(HASH_THREADS) void k_hash_accept(AcceptParams P)
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         h[u] = f + r;
+        // (hash_roll, nts_tile_sweep.inc, spelled out: through the helper this kernel compiles to other code)
         const uint32_t cout = base_at(s), cin = base_at(s + k);
         f = srol1(f) ^ s_tab[cin * 4 + cout];
         r = sror1(r ^ s_tab[16 + cin * 4 + cout]);
@@ -1925,18 +1915,7 @@ __global__ __launch_bounds__(ACC4_THREADS) void k_hash_accept4(AcceptParams P, c
   };
   if (single) {
     const uint64_t P0 = P.run_pos[lo] + (J0 - v0);
-    a = (uint32_t)(P0 & 15u);
-    const uint8_t* src = P.code + (P0 - a);
-    const uint32_t n_bytes = a + tile_len + k - 1;
-    const uint32_t n16 = (n_bytes + 15u) >> 4;
-    for (uint32_t c = tid; c < n16; c += 256u) {
-      const uint4 v = *reinterpret_cast<const uint4*>(src + 16u * c);
-      const uint32_t d = 4u * c + (c >> 1);
-      s_seq[d] = v.x;
-      s_seq[d + 1] = v.y;
-      s_seq[d + 2] = v.z;
-      s_seq[d + 3] = v.w;
-    }
+    a = seq_stage(s_seq, P.code, P0, tile_len, k, tid);
   }
   __syncthreads(); // folded filter, tables and every quarter's bases are in LDS
   if (single) {
@@ -1950,6 +1929,7 @@ __global__ __launch_bounds__(ACC4_THREADS) void k_hash_accept4(AcceptParams P, c
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         h[u] = f + r;
+        // (hash_roll, nts_tile_sweep.inc, spelled out: through the helper this kernel compiles to other code)
         const uint32_t cout = base_at(s), cin = base_at(s + k);
         f = srol1(f) ^ s_tab[cin * 4 + cout];
         r = sror1(r ^ s_tab[16 + cin * 4 + cout]);

@@ -128,6 +128,8 @@ constexpr uint32_t FAST_K_MAX = 128;
 constexpr uint32_t SEQ_LDS_DWORDS = 2400; // (15 + 8192 + 127) bytes in the padded layout, rounded up
 static_assert(HASH_PER_THREAD == 32 && HASH_THREADS == 256, "key layout assumes 256 x 32 tiles");
 
+#include "nts_tile_sweep.inc"
+
 __host__ __device__ __forceinline__ uint64_t key_phys(uint64_t j)
 {
   const uint64_t tile = j / KEY_TILE;
@@ -218,11 +220,7 @@ __global__ __launch_bounds__(HASH_THREADS) void k_hash(const uint8_t* __restrict
   __shared__ uint64_t s_tab[36];
   __shared__ uint32_t s_seq[SEQ_LDS_DWORDS];
   const uint32_t tid = threadIdx.x;
-  if (tid < 16) {
-    s_tab[tid] = hp.roll_f[tid];
-    s_tab[16 + tid] = hp.roll_r[tid];
-  }
-  if (tid < 4) s_tab[32 + tid] = hp.seed[tid];
+  tab_load(s_tab, hp, tid);
   const uint32_t k = hp.k;
   // tile_ids (optional): the key tiles to compute, for the dense fallback on uncovered ranges only
   const uint64_t J0 = (uint64_t)(tile_ids ? tile_ids[blockIdx.x] : blockIdx.x) * KEY_TILE;
@@ -244,18 +242,7 @@ __global__ __launch_bounds__(HASH_THREADS) void k_hash(const uint8_t* __restrict
   if (single) {
     // ---- fast path --------------------------------------------------------------------------------
     const uint64_t P0 = run_pos[lo] + (J0 - v0);
-    const uint32_t a = (uint32_t)(P0 & 15u);
-    const uint8_t* src = code + (P0 - a);
-    const uint32_t n_bytes = a + tile_len + k - 1;
-    const uint32_t n16 = (n_bytes + 15u) >> 4;
-    for (uint32_t c = tid; c < n16; c += HASH_THREADS) {
-      const uint4 v = *reinterpret_cast<const uint4*>(src + 16u * c);
-      const uint32_t d = 4u * c + (c >> 1);
-      s_seq[d] = v.x;
-      s_seq[d + 1] = v.y;
-      s_seq[d + 2] = v.z;
-      s_seq[d + 3] = v.w;
-    }
+    const uint32_t a = seq_stage(s_seq, code, P0, tile_len, k, tid);
     __syncthreads();
     const uint8_t* sb = reinterpret_cast<const uint8_t*>(s_seq);
     auto base_at = [&](uint32_t s) -> uint32_t { return sb[s + 4u * (s >> 5)] & 3u; };
@@ -271,6 +258,7 @@ __global__ __launch_bounds__(HASH_THREADS) void k_hash(const uint8_t* __restrict
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         h[u] = f + r;
+        // (hash_roll, nts_tile_sweep.inc, spelled out: through the helper this kernel compiles to other code)
         const uint32_t cout = base_at(s), cin = base_at(s + k);
         f = srol1(f) ^ s_tab[cin * 4 + cout];
         r = sror1(r ^ s_tab[16 + cin * 4 + cout]);
@@ -407,11 +395,7 @@ __global__ __launch_bounds__(HASH_THREADS) void k_hash_keys_sparse(const uint8_t
   __shared__ uint64_t s_tab[36];
   __shared__ uint32_t s_seq[SEQ_LDS_DWORDS];
   const uint32_t tid = threadIdx.x;
-  if (tid < 16) {
-    s_tab[tid] = hp.roll_f[tid];
-    s_tab[16 + tid] = hp.roll_r[tid];
-  }
-  if (tid < 4) s_tab[32 + tid] = hp.seed[tid];
+  tab_load(s_tab, hp, tid);
   const uint32_t k = hp.k;
   const uint64_t J0 = (uint64_t)blockIdx.x * KEY_TILE;
   const uint32_t tile_len = (uint32_t)min((uint64_t)KEY_TILE, n_valid - J0);
@@ -433,18 +417,7 @@ __global__ __launch_bounds__(HASH_THREADS) void k_hash_keys_sparse(const uint8_t
   };
   if (single) {
     const uint64_t P0 = run_pos[lo] + (J0 - v0);
-    const uint32_t a = (uint32_t)(P0 & 15u);
-    const uint8_t* src = code + (P0 - a);
-    const uint32_t n_bytes = a + tile_len + k - 1;
-    const uint32_t n16 = (n_bytes + 15u) >> 4;
-    for (uint32_t c = tid; c < n16; c += HASH_THREADS) {
-      const uint4 v = *reinterpret_cast<const uint4*>(src + 16u * c);
-      const uint32_t d = 4u * c + (c >> 1);
-      s_seq[d] = v.x;
-      s_seq[d + 1] = v.y;
-      s_seq[d + 2] = v.z;
-      s_seq[d + 3] = v.w;
-    }
+    const uint32_t a = seq_stage(s_seq, code, P0, tile_len, k, tid);
     __syncthreads();
     const uint8_t* sb = reinterpret_cast<const uint8_t*>(s_seq);
     auto base_at = [&](uint32_t s) -> uint32_t { return sb[s + 4u * (s >> 5)] & 3u; };
@@ -463,6 +436,7 @@ __global__ __launch_bounds__(HASH_THREADS) void k_hash_keys_sparse(const uint8_t
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         h[u] = f + r;
+        // (hash_roll, nts_tile_sweep.inc, spelled out: through the helper this kernel compiles to other code)
         const uint32_t cout = base_at(s), cin = base_at(s + k);
         f = srol1(f) ^ s_tab[cin * 4 + cout];
         r = sror1(r ^ s_tab[16 + cin * 4 + cout]);

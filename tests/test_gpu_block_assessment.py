@@ -15,7 +15,7 @@ import pytest
 from ntsynt_amd import assess, divergence, synth
 from oracle import nts_oracle as O
 from tests.divergence_ref import SENTINEL
-from tests.helpers import random_records, to_device
+from tests.helpers import END_CASE_KMERS, genome_end_case, random_records, to_device
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -107,6 +107,20 @@ def test_interval_sketches_equal_the_oracle(ctx, records, k):
             print(f"k {k} s {s}: passes/chunks/sweeps {ctx.minhash_intervals_stats()}")
         out, counts, n_kmers = g.minhash_intervals(np.zeros((0, 3), np.uint64), k, 100)
         assert out.shape == (0, 100) and counts.size == 0
+    finally:
+        g.free()
+
+
+@pytest.mark.parametrize("k", [150, 24])
+def test_partial_lanes_up_to_the_last_base_of_the_genome(ctx, k):
+    "k = 150: every lane reads its own bases and a partial one rolls on past the tile; k = 24: the same intervals through the staging area"
+    names, seqs, iv = genome_end_case(k)
+    g = to_device(ctx, names, seqs)
+    try:
+        for s in (100, 10_000):                                  # a threshold for the long intervals; every hash of every interval
+            ref, ref_nk = _check(g, seqs, k, s, iv, note="genome end")
+            assert ref_nk[:12] == list(END_CASE_KMERS) * 2, ref_nk
+            assert all(r.size == min(s, n) for r, n in zip(ref[:12], ref_nk[:12])), [r.size for r in ref]      # random sequence: no repeated k-mer
     finally:
         g.free()
 

@@ -15,7 +15,7 @@ import pytest
 
 from ntsynt_amd import assess, gaps, synth
 from oracle import nts_oracle as O
-from tests.helpers import random_records, to_device
+from tests.helpers import END_CASE_KMERS, genome_end_case, random_records, to_device
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -144,6 +144,29 @@ def test_samples_equal_the_oracle(ctx, k):
                 assert got.size <= 4, (k, got.size)                                            # 10^5 held k-mers, one in 2^20 sampled
         empty = g.bf_sample_intervals(bf, np.zeros((0, 3), np.uint64), k, 16)
         assert empty[0].size == 0 and empty[1].size == 0
+    finally:
+        g.free()
+        bf.free()
+
+
+@pytest.mark.parametrize("k", [150, 24])
+def test_partial_lanes_up_to_the_last_base_of_the_genome(ctx, k):
+    "k = 150: every lane reads its own bases and a partial one rolls on past the tile; k = 24: the same intervals through the staging area"
+    names, seqs, iv = genome_end_case(k)
+    copy = [c.tobytes() for c in synth.derive_genome([np.frombuffer(s, dtype=np.uint8) for s in seqs], SUBSTITUTIONS, 1, seed=79, structural=False)]
+    bf = _filter_of(ctx, names, copy, k, nbytes=1 << 16)
+    g = to_device(ctx, names, seqs)
+    try:
+        bits = bf.to_numpy()
+        kmers, _ = g.bf_count_intervals(bf, iv, k)
+        assert [int(x) for x in kmers[:12]] == list(END_CASE_KMERS) * 2, k
+        for rate in (1, 16):
+            got, counts = g.bf_sample_intervals(bf, iv, k, rate)
+            exp, exp_counts = oracle_sample(seqs, k, bits, iv, rate)
+            print(f"k {k} rate {rate}: {got.size} records, oracle {exp.size}; per interval {[int(c) for c in counts]}")
+            assert np.array_equal(counts, exp_counts), (k, rate)
+            assert got.size == exp.size and np.array_equal(got, exp), (k, rate)              # order, h0, iv and off
+            assert 0 < got.size < int(kmers.sum()), (k, rate)                                # never a vacuous match
     finally:
         g.free()
         bf.free()

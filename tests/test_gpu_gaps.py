@@ -15,7 +15,7 @@ import pytest
 
 from ntsynt_amd import assess, gaps, synth
 from oracle import nts_oracle as O
-from tests.helpers import random_records, to_device
+from tests.helpers import END_CASE_KMERS, genome_end_case, random_records, to_device
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -122,6 +122,26 @@ def test_interval_counts_equal_the_oracle(ctx, k):
         for (rec, start, end), v in zip(iv, valid):
             seg = seqs[rec][min(start, len(seqs[rec])):max(min(end, len(seqs[rec])), min(start, len(seqs[rec])))]
             assert int(v) == sum(seg.upper().count(b) for b in (b"A", b"C", b"G", b"T")), (rec, start, end)
+    finally:
+        g.free()
+        bf.free()
+
+
+@pytest.mark.parametrize("k", [150, 24])
+def test_partial_lanes_up_to_the_last_base_of_the_genome(ctx, k):
+    "k = 150: every lane reads its own bases and a partial one rolls on past the tile; k = 24: the same intervals through the staging area"
+    names, seqs, iv = genome_end_case(k)
+    copy = [c.tobytes() for c in synth.derive_genome([np.frombuffer(s, dtype=np.uint8) for s in seqs], SUBSTITUTIONS, 1, seed=79, structural=False)]
+    bf = _filter_of(ctx, names, copy, k, nbytes=1 << 16)
+    g = to_device(ctx, names, seqs)
+    try:
+        kmers, hits = g.bf_count_intervals(bf, iv, k)
+        ref = oracle_counts(seqs, k, bf.to_numpy(), iv)
+        for i, row in enumerate(iv):
+            print(f"k {k} {row}: kmers {int(kmers[i])} hits {int(hits[i])} oracle {ref[i]}")
+        assert [r[0] for r in ref[:12]] == list(END_CASE_KMERS) * 2 and ref[12][0] == 500 - k + 1 + 460 - k + 1, ref
+        assert [(int(a), int(b)) for a, b in zip(kmers, hits)] == ref
+        assert 0 < sum(r[1] for r in ref) < sum(r[0] for r in ref)               # never a vacuous match
     finally:
         g.free()
         bf.free()
