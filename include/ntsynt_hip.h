@@ -35,6 +35,7 @@ typedef struct nts_ctx nts_ctx;
 typedef struct nts_genome nts_genome; /* one FASTA resident in HBM */
 typedef struct nts_bf nts_bf;         /* Bloom bit array resident in HBM */
 typedef struct nts_mx nts_mx;         /* minimizer list resident in HBM */
+typedef struct nts_hset nts_hset;     /* exact set of 64-bit hashes resident in HBM */
 typedef struct nts_comm nts_comm;     /* RCCL communicator of the multi-GPU path (one rank per GPU) */
 
 /* hard-mask interval [start, end) in record coordinates (bedtools maskfasta semantics) */
@@ -480,6 +481,24 @@ int nts_bf_sample_intervals(nts_ctx* ctx, const nts_genome* g, uint32_t k, const
                             uint64_t n_iv, uint64_t* n_sampled, nts_sample** out, uint64_t* n_out);
 int nts_iv_links(nts_ctx* ctx, uint32_t n_lists, const nts_sample* const* lists, const uint64_t* n, uint32_t min_anchors, nts_iv_link** out,
                  uint64_t* n_out);
+
+/* ---- where a gap's shared sequence lies inside the blocks: gap block links ---------------------------
+ * nts_hset_build: an exact set of the n 64-bit values of the host array h (duplicates allowed; n = 0: the empty set), in device memory
+ *   from the context's allocator: open addressing, at most half full, 8 bytes per slot; the home slot mixes every bit of the value
+ *   (values under a sampling threshold have their top bits zero).  Built by one kernel with 64-bit compare-and-swap: the order of
+ *   the slots may differ from run to run, membership does not.  Exact for every value, 0 and 2^64 - 1 included.  Timer
+ *   "hset_build".  NTS_ERANGE for more than 2^31 values.  Released with nts_hset_free().
+ * nts_hset_contains: out[i] = 1 when h[i] is a member, 0 otherwise (host arrays; fewer than 2^32 queries per call).
+ * nts_hset_sample_intervals: nts_bf_sample_intervals with "the set has h0" in place of "the filter holds h0": the same records in
+ *   the same order, the same clipping, NTS_EINVAL and NTS_ERANGE, two launches per 2^23 tiles (timers "hset_sample_count",
+ *   "hset_sample_write"), no atomic, deterministic; *out released with nts_free().  The threshold is tested first: one k-mer in
+ *   `rate` touches the table.  csrc/nts_hset.inc; ntsynt_amd/gaps.py block_links, `ntSynt --gap-block-links`,
+ *   `bin/ntsynt_gaps --block-links-out`. */
+int nts_hset_build(nts_ctx* ctx, const uint64_t* h, uint64_t n, nts_hset** out);
+void nts_hset_free(nts_ctx* ctx, nts_hset* set);
+int nts_hset_contains(nts_ctx* ctx, const nts_hset* set, const uint64_t* h, uint64_t n, uint8_t* out);
+int nts_hset_sample_intervals(nts_ctx* ctx, const nts_genome* g, uint32_t k, const nts_hset* set, uint64_t rate, const nts_interval* iv,
+                              uint64_t n_iv, uint64_t* n_sampled, nts_sample** out, uint64_t* n_out);
 
 /* ---- C1-C5: minimizer graph -> collinear chains -----------------------------------------------------
  * replaces ntjoin_utils.read_minimizers' duplicate removal, filter_minimizers and build_graph

@@ -171,6 +171,10 @@ SYMBOLS = [
     ("nts_bf_count_intervals", ctypes.c_int, [c_vp, c_vp, u32, c_vp, ctypes.POINTER(Interval), u64, c_vp, c_vp]),
     ("nts_bf_sample_intervals", ctypes.c_int, [c_vp, c_vp, u32, c_vp, u64, ctypes.POINTER(Interval), u64, c_vp, ctypes.POINTER(c_vp), c_u64p]),
     ("nts_iv_links", ctypes.c_int, [c_vp, u32, ctypes.POINTER(c_vp), c_u64p, u32, ctypes.POINTER(c_vp), c_u64p]),
+    ("nts_hset_build", ctypes.c_int, [c_vp, c_vp, u64, ctypes.POINTER(c_vp)]),
+    ("nts_hset_free", None, [c_vp, c_vp]),
+    ("nts_hset_contains", ctypes.c_int, [c_vp, c_vp, c_vp, u64, c_vp]),
+    ("nts_hset_sample_intervals", ctypes.c_int, [c_vp, c_vp, u32, c_vp, u64, ctypes.POINTER(Interval), u64, c_vp, ctypes.POINTER(c_vp), c_u64p]),
     ("nts_genome_valid_bases", ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(Interval), u64, c_vp]),
     ("nts_minhash_pairs", ctypes.c_int, [c_vp, u32, c_vp, c_vp, u64, c_vp, c_vp, u64, c_vp, c_vp]),
     ("nts_graph_build", ctypes.c_int, [c_vp, u32, ctypes.POINTER(MxList), ctypes.POINTER(Graph)]),

@@ -556,6 +556,16 @@ struct nts_bf
   mutable std::mutex mu;              // sketches of several genomes may run on contexts of their own at once (SketchPool): the summary is built once
 };
 
+struct nts_hset // an exact set of 64-bit values: open addressing, 2^m slots of one uint64, at most half full (csrc/nts_hset.inc)
+{
+  uint64_t* d_slots = nullptr;
+  uint64_t n_slots = 0; // 2^m
+  uint32_t shift = 0;   // 64 - m: the home slot of h is (h * HSET_MULT) >> shift
+  uint64_t n_in = 0;    // values given (duplicates included)
+  bool has_max = false; // 2^64 - 1, which marks an empty slot, is a member
+  int device = 0;
+};
+
 struct nts_mx
 {
   uint64_t n = 0;

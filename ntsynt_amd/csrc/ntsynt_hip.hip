@@ -1596,6 +1596,7 @@ int launch_hash(nts_ctx* ctx, const char* name, const nts_genome* g, const Genom
 #include "nts_minhash_iv.inc"
 #include "nts_bf_iv.inc"
 #include "nts_bf_sample.inc"
+#include "nts_hset.inc"
 
 // acc &= the filter of genome g the literal way, for a running filter that holds few bits (defined behind the sketch's host code,
 // whose accept kernels and summary it uses): 0 = done, 1 = does not apply or did not fit (acc is untouched), < 0 = error
@@ -2746,6 +2747,37 @@ int nts_bf_sample_intervals(nts_ctx* ctx, const nts_genome* g, uint32_t k, const
     return fail(ctx, NTS_EINVAL, "nts_bf_sample_intervals: bad arguments");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   return bf_sample_intervals_run(ctx, g, k, bf, rate, iv, n_iv, n_sampled, out, n_out);
+}
+
+int nts_hset_build(nts_ctx* ctx, const uint64_t* h, uint64_t n, nts_hset** out)
+{
+  if (!ctx || !out || (n && !h)) return fail(ctx, NTS_EINVAL, "nts_hset_build: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return hset_build_run(ctx, h, n, out);
+}
+
+void nts_hset_free(nts_ctx* ctx, nts_hset* set)
+{
+  if (!set) return;
+  if (ctx) hipSetDevice(ctx->device);
+  if (set->d_slots) dev_free(set->d_slots);
+  delete set;
+}
+
+int nts_hset_contains(nts_ctx* ctx, const nts_hset* set, const uint64_t* h, uint64_t n, uint8_t* out)
+{
+  if (!ctx || !set || (n && (!h || !out))) return fail(ctx, NTS_EINVAL, "nts_hset_contains: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return hset_contains_run(ctx, set, h, n, out);
+}
+
+int nts_hset_sample_intervals(nts_ctx* ctx, const nts_genome* g, uint32_t k, const nts_hset* set, uint64_t rate, const nts_interval* iv,
+                              uint64_t n_iv, uint64_t* n_sampled, nts_sample** out, uint64_t* n_out)
+{
+  if (!ctx || !g || !set || k == 0 || rate == 0 || !out || !n_out || (n_iv && (!iv || !n_sampled)))
+    return fail(ctx, NTS_EINVAL, "nts_hset_sample_intervals: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return hset_sample_intervals_run(ctx, g, k, set, rate, iv, n_iv, n_sampled, out, n_out);
 }
 
 int nts_genome_valid_bases(nts_ctx* ctx, const nts_genome* g, const nts_interval* iv, uint64_t n_iv, uint64_t* n_valid)

@@ -493,9 +493,56 @@ class Genome:
         self.ctx.lib.nts_free(p)
         return out, counts
 
+    def hset_sample_intervals(self, hset, intervals, k, rate):
+        """bf_sample_intervals with the exact hash set `hset` (HashSet) in place of the filter (nts_hset_sample_intervals): the k-mers of
+        the intervals with h0 <= (2^64 - 1) // rate whose h0 is a member.  The same (records, counts), exact and deterministic."""
+        iv = self._interval_array(intervals)
+        n = iv.size
+        counts = np.zeros(n, dtype=np.uint64)
+        p, m = c_vp(), u64()
+        self.ctx.check(self.ctx.lib.nts_hset_sample_intervals(self.ctx.h, self.h, int(k), hset.h, int(rate), ctypes.cast(iv.ctypes.data, ctypes.POINTER(Interval)),
+                                                              n, counts.ctypes.data, ctypes.byref(p), ctypes.byref(m)), "nts_hset_sample_intervals")
+        out = np.empty(m.value, dtype=SAMPLE_DTYPE)
+        if m.value:
+            ctypes.memmove(out.ctypes.data, p.value, out.nbytes)
+        self.ctx.lib.nts_free(p)
+        return out, counts
+
     def free(self):
         if self.h:
             self.ctx.lib.nts_genome_free(self.ctx.h, self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class HashSet:
+    """An exact set of 64-bit hashes in HBM (nts_hset_build): what Genome.hset_sample_intervals probes.  After free() every call with
+    it is refused (the handle is NULL)."""
+
+    def __init__(self, ctx, values):
+        "values: any array of uint64, duplicates allowed, empty allowed"
+        self.ctx = ctx
+        v = np.ascontiguousarray(values, dtype=np.uint64).ravel()
+        h = c_vp()
+        ctx.check(ctx.lib.nts_hset_build(ctx.h, v.ctypes.data if v.size else None, v.size, ctypes.byref(h)), "nts_hset_build")
+        self.h = h
+
+    def contains(self, values):
+        "[n] bool: which of the values are members (nts_hset_contains)"
+        v = np.ascontiguousarray(values, dtype=np.uint64).ravel()
+        out = np.zeros(v.size, dtype=np.uint8)
+        self.ctx.check(self.ctx.lib.nts_hset_contains(self.ctx.h, self.h, v.ctypes.data if v.size else None, v.size, out.ctypes.data if v.size else None),
+                       "nts_hset_contains")
+        return out.astype(bool)
+
+    def free(self):
+        if self.h:
+            self.ctx.lib.nts_hset_free(self.ctx.h, self.h)
             self.h = None
 
     def __del__(self):

@@ -9,7 +9,12 @@ gap.  docs/design/04_9_gap_content.md.
 Where a gap's shared sequence lies in the other genomes (`ntSynt --gap-links`, `bin/ntsynt_gaps --links-out`): a thin sample of the gap
 k-mers the filter holds is taken per genome (links: nts_bf_sample_intervals over the gaps only) and joined across genomes by hash on
 the GPU (nts_iv_links); a pair of gaps of two genomes with enough hashes in common is a link, with its orientation from the order of
-the anchors and its placement from the gaps' flanking blocks.  docs/design/04_10_gap_links.md."""
+the anchors and its placement from the gaps' flanking blocks.  docs/design/04_10_gap_links.md.
+
+Where it lies INSIDE the blocks, the gap's own genome included (`ntSynt --gap-block-links`, `bin/ntsynt_gaps --block-links-out`): the
+gaps' sampled hashes become an exact hash set on the GPU (nts_hset_build), every genome's merged block intervals are swept against it
+(block_links: nts_hset_sample_intervals writes only the hits) and the same join links gaps to block intervals.
+docs/design/04_11_gap_block_links.md."""
 import os
 from collections import namedtuple
 
@@ -20,6 +25,9 @@ SUMMARY_COLUMNS = ("genome", "part", "intervals", "bases", "n_bases", "kmers", "
 LINK_COLUMNS = ("genome_a", "contig_a", "start_a", "end_a", "left_a", "right_a", "genome_b", "contig_b", "start_b", "end_b", "left_b", "right_b",
                 "anchors", "orientation", "from_a", "to_a", "from_b", "to_b", "sampled_a", "sampled_b", "placement")
 LINKS_RATE, LINKS_MIN = 16, 4                                   # --gap-links-rate / --gap-links-min
+BLOCK_LINK_COLUMNS = ("genome", "contig", "start", "end", "left_block", "right_block", "target_genome", "target_contig", "target_start", "target_end",
+                      "blocks", "anchors", "orientation", "from", "to", "from_t", "to_t", "sampled", "target_hits", "placement")
+MAX_BLOCK_LINK_GENOMES = 32                                     # nts_iv_links takes at most 64 lists: every genome's gaps and its blocks
 
 # a stretch of `contig` of `genome` outside every block: [start, end); kind: between / leading / trailing / unplaced (the record has no
 # block at all); left_block / right_block: the block that ends at `start` / starts at `end`, "." where there is none
@@ -185,31 +193,53 @@ def placement(a, b):
     return "same" if fa == fb and fa != {"."} else "other"
 
 
-def links(ctx, genomes_by_name, bf, k, gap_rows, rate=LINKS_RATE, min_anchors=LINKS_MIN):
-    """the links between the gaps of different genomes: gap_rows are report()'s (every genome's, in its order); genomes_by_name and bf
-    as for report().  Per genome, ascending by name, one nts_bf_sample_intervals call over its gaps only (the k-mers the filter
-    holds with h0 <= (2^64 - 1) // rate; a genome given as a loader is freed after its sweep), then one nts_iv_links over all of
-    them on ctx: a hash no genome has twice among its sampled gap k-mers is an anchor of every two gaps that have it, and two gaps
-    with at least min_anchors anchors are a link.  Returns one dict per link with LINK_COLUMNS' keys, in the join's order: by
-    genome a, gap a, genome b, gap b (a before b in the order of the names)."""
-    if rate < 1 or min_anchors < 1:
-        raise ValueError("links: rate and min_anchors must be at least 1")
-    names = sorted(genomes_by_name)
-    rows_of = {name: [r for r in gap_rows if r["genome"] == name] for name in names}
-    lists, sampled = [], []
+def _each_genome(genomes_by_name, names, sweep):
+    "sweep(name, resident genome) per genome in the order of `names`; one given as a loader is loaded for its sweep and freed after it"
     for name in names:
         g = genomes_by_name[name]
         loaded = callable(g)
         if loaded:
             g = g()
         try:
-            rec_of = {c: j for j, c in enumerate(g.names)}
-            rec, counts = g.bf_sample_intervals(bf, [(rec_of[r["contig"]], r["start"], r["end"]) for r in rows_of[name]], k, rate)
+            sweep(name, g)
         finally:
             if loaded:
                 g.free()
+
+
+def _interval_rows(g, rows):
+    rec_of = {c: j for j, c in enumerate(g.names)}
+    return [(rec_of[r["contig"]], r["start"], r["end"]) for r in rows]
+
+
+def sample_gaps(genomes_by_name, bf, k, gap_rows, rate=LINKS_RATE):
+    """(lists, sampled): per genome, ascending by name, the records and the per-gap counts of one nts_bf_sample_intervals call over
+    its gaps only (the k-mers the filter holds with h0 <= (2^64 - 1) // rate).  gap_rows are report()'s (every genome's, in its
+    order); genomes_by_name and bf as for report().  One sampling serves links() and block_links()."""
+    if rate < 1:
+        raise ValueError("sample_gaps: rate must be at least 1")
+    lists, sampled = [], []
+
+    def sweep(name, g):
+        rec, counts = g.bf_sample_intervals(bf, _interval_rows(g, [r for r in gap_rows if r["genome"] == name]), k, rate)
         lists.append(rec)
         sampled.append(counts)
+    _each_genome(genomes_by_name, sorted(genomes_by_name), sweep)
+    return lists, sampled
+
+
+def links(ctx, genomes_by_name, bf, k, gap_rows, rate=LINKS_RATE, min_anchors=LINKS_MIN, sampling=None):
+    """the links between the gaps of different genomes: gap_rows are report()'s (every genome's, in its order); genomes_by_name and bf
+    as for report().  Per genome, ascending by name, one nts_bf_sample_intervals call over its gaps only (sample_gaps; `sampling`:
+    its result at this rate, where the caller has it already), then one nts_iv_links over all of them on ctx: a hash no genome has
+    twice among its sampled gap k-mers is an anchor of every two gaps that have it, and two gaps with at least min_anchors anchors
+    are a link.  Returns one dict per link with LINK_COLUMNS' keys, in the join's order: by genome a, gap a, genome b, gap b (a
+    before b in the order of the names)."""
+    if rate < 1 or min_anchors < 1:
+        raise ValueError("links: rate and min_anchors must be at least 1")
+    names = sorted(genomes_by_name)
+    rows_of = {name: [r for r in gap_rows if r["genome"] == name] for name in names}
+    lists, sampled = sampling if sampling is not None else sample_gaps(genomes_by_name, bf, k, gap_rows, rate)
     out = []
     for ln in ctx.iv_links(lists, min_anchors):
         la, lb = int(ln["list_a"]), int(ln["list_b"])
@@ -232,6 +262,86 @@ def links_table(rows, k, rate, min_anchors, bits):
     return "\n".join(lines) + "\n"
 
 
+def blocks_in_span(blocks, genome, contig, a, b):
+    "the ids of the table's blocks (assess.read_blocks' rows) whose interval on `contig` of `genome` intersects [a, b): file order, each once"
+    ids = []
+    for r in blocks:
+        if r.genome == genome and r.contig == contig and r.start < b and r.end > a and r.block_id not in ids:
+            ids.append(r.block_id)
+    return ids
+
+
+def block_placement(gap, target_genome, ids):
+    """of a gap's link into a block interval: `own` when the interval is the gap's own genome's -- a second copy of sequence the genome
+    has inside a block --; otherwise `flank` when the blocks the anchors span (ids) include the gap's left or right block -- sequence
+    the neighbouring block covers in the other genome --; `other` otherwise -- it lies in a block elsewhere"""
+    if target_genome == gap["genome"]:
+        return "own"
+    flanks = {gap["left_block"], gap["right_block"]} - {"."}
+    return "flank" if flanks & set(ids) else "other"
+
+
+def gap_to_block(found, n):
+    "of the links of the 2n lists (n lists of gaps, then n of block intervals: a LINK_DTYPE array), those of a gap and a block interval, in their order"
+    return found[(found["list_a"] < n) & (found["list_b"] >= n)]
+
+
+def block_links(ctx, genomes_by_name, bf, k, gap_rows, block_rows, blocks, lists, sampled, rate=LINKS_RATE, min_anchors=LINKS_MIN):
+    """where the gaps' sampled k-mers occur inside the blocks of every genome, the gap's own included.  gap_rows, block_rows: report()'s
+    (block_rows = the merged in-block intervals); blocks: assess.read_blocks' rows; lists, sampled: sample_gaps() at this rate.  The
+    hashes of all lists become one exact set on the GPU (nts_hset_build); per genome, ascending by name, one
+    nts_hset_sample_intervals call over its merged intervals writes the k-mers under the threshold whose hash is in the set (every
+    member is held by the filter, so bf is not probed; a genome given as a loader is loaded once more and freed after its sweep);
+    one nts_iv_links over the 2n lists -- a hash is usable when none of them has it twice --, of which the links of a gap and a
+    block interval are kept.  Returns (rows, hashes in the set): one dict per link with BLOCK_LINK_COLUMNS' keys, by gap genome, gap,
+    target genome, target interval."""
+    import numpy as np
+    from .device import HashSet
+    if rate < 1 or min_anchors < 1:
+        raise ValueError("block_links: rate and min_anchors must be at least 1")
+    names = sorted(genomes_by_name)
+    n = len(names)
+    if n > MAX_BLOCK_LINK_GENOMES:
+        raise ValueError(f"block_links: {n} genomes; at most {MAX_BLOCK_LINK_GENOMES} (the join takes 64 lists: every genome's gaps and its blocks)")
+    gaps_of = {name: [r for r in gap_rows if r["genome"] == name] for name in names}
+    merged_of = {name: [r for r in block_rows if r["genome"] == name] for name in names}
+    members = np.unique(np.concatenate([np.asarray(lst["h0"], dtype=np.uint64) for lst in lists] + [np.zeros(0, dtype=np.uint64)]))
+    hset = HashSet(ctx, members)
+    hits, hit_counts = [], []
+    try:
+        def sweep(name, g):
+            rec, counts = g.hset_sample_intervals(hset, _interval_rows(g, merged_of[name]), k, rate)
+            hits.append(rec)
+            hit_counts.append(counts)
+        _each_genome(genomes_by_name, names, sweep)
+    finally:
+        hset.free()
+    out = []
+    for ln in gap_to_block(ctx.iv_links(list(lists) + hits, min_anchors), n):
+        la, lt = int(ln["list_a"]), int(ln["list_b"]) - n
+        gap, target = gaps_of[names[la]][int(ln["iv_a"])], merged_of[names[lt]][int(ln["iv_b"])]
+        from_t, to_t = target["start"] + int(ln["min_off_b"]), target["start"] + int(ln["max_off_b"]) + int(k)
+        ids = blocks_in_span(blocks, target["genome"], target["contig"], from_t, to_t)
+        row = {c: gap[c] for c in ("genome", "contig", "start", "end", "left_block", "right_block")}
+        row.update({"target_genome": target["genome"], "target_contig": target["contig"], "target_start": target["start"], "target_end": target["end"],
+                    "blocks": ",".join(ids), "anchors": int(ln["anchors"]), "orientation": orientation(int(ln["fwd"]), int(ln["rev"])),
+                    "from": gap["start"] + int(ln["min_off_a"]), "to": gap["start"] + int(ln["max_off_a"]) + int(k), "from_t": from_t, "to_t": to_t,
+                    "sampled": int(sampled[la][int(ln["iv_a"])]), "target_hits": int(hit_counts[lt][int(ln["iv_b"])]),
+                    "placement": block_placement(gap, target["genome"], ids)})
+        out.append(row)
+    return out, int(members.size)
+
+
+def block_links_table(rows, k, rate, min_anchors, bits, n_set):
+    """<prefix>.gap_block_links.tsv: a header, one line per link (block_links()' rows, in their order), then
+    `# k K, rate R, min_anchors M, filter BITS bits, set N hashes`"""
+    lines = ["\t".join(BLOCK_LINK_COLUMNS)]
+    for r in rows:
+        lines.append("\t".join(str(r[c]) for c in BLOCK_LINK_COLUMNS))
+    lines.append(f"# k {int(k)}, rate {int(rate)}, min_anchors {int(min_anchors)}, filter {int(bits)} bits, set {int(n_set)} hashes")
+    return "\n".join(lines) + "\n"
+
+
 def main(argv=None):
     "bin/ntsynt_gaps"
     import argparse
@@ -244,12 +354,16 @@ def main(argv=None):
     p.add_argument("--out", help="file for the per-gap table [stdout]")
     p.add_argument("--summary-out", help="file for the per-genome summary [stdout, after the table]")
     p.add_argument("--links-out", help="also write the links between the gaps of different genomes to this file (<prefix>.gap_links.tsv)")
+    p.add_argument("--block-links-out", help="also write the links between the gaps and the block intervals of every genome, the gap's own included, "
+                   "to this file (<prefix>.gap_block_links.tsv); uses --links-rate and --links-min")
     p.add_argument("--links-rate", help=f"sample one in this many of the gap k-mers the filter holds [{LINKS_RATE}]", type=int, default=LINKS_RATE)
     p.add_argument("--links-min", help=f"anchors a link needs [{LINKS_MIN}]", type=int, default=LINKS_MIN)
     p.add_argument("--device", help="GPU index [0]", type=int, default=0)
     args = p.parse_args(argv)
     if args.links_rate < 1 or args.links_min < 1:
         p.error("--links-rate and --links-min must be positive")
+    if args.block_links_out and len(args.fastas) > MAX_BLOCK_LINK_GENOMES:
+        p.error(f"--block-links-out takes at most {MAX_BLOCK_LINK_GENOMES} genomes")
     for path in args.fastas + [args.common, args.tsv]:
         if not os.path.isfile(path):
             raise FileNotFoundError(f"Input file {path} not found.")
@@ -265,12 +379,19 @@ def main(argv=None):
         del bits
         loaders = {basename(path): (lambda path=path: read_fasta_device(ctx, path)[0]) for path in args.fastas}
         try:
-            gap_rows, block_rows, n_bits, occupancy = report(ctx, loaders, bf, k, read_blocks(args.tsv))
+            blocks = read_blocks(args.tsv)
+            gap_rows, block_rows, n_bits, occupancy = report(ctx, loaders, bf, k, blocks)
             texts = table(gap_rows, k, n_bits, occupancy), summary(gap_rows, block_rows, k, n_bits, occupancy, genomes=list(loaders))
+            if args.links_out or args.block_links_out:
+                sampling = sample_gaps(loaders, bf, k, gap_rows, args.links_rate)
             if args.links_out:
-                link_rows = links(ctx, loaders, bf, k, gap_rows, args.links_rate, args.links_min)
+                link_rows = links(ctx, loaders, bf, k, gap_rows, args.links_rate, args.links_min, sampling=sampling)
                 with open(args.links_out, "w", encoding="utf-8") as fh:
                     fh.write(links_table(link_rows, k, args.links_rate, args.links_min, n_bits))
+            if args.block_links_out:
+                b_rows, n_set = block_links(ctx, loaders, bf, k, gap_rows, block_rows, blocks, sampling[0], sampling[1], args.links_rate, args.links_min)
+                with open(args.block_links_out, "w", encoding="utf-8") as fh:
+                    fh.write(block_links_table(b_rows, k, args.links_rate, args.links_min, n_bits, n_set))
         finally:
             bf.free()
     finally:

@@ -496,7 +496,7 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         block_size=500, common=True, simplify=True, device=0, write_mx_tsv=True, mx_with_seq=True,
         benchmark=False, log=print, ctx=None, backend=None, bf_rounding="up", bf_signature=BF_SIGNATURE, dev=False, interarrivals=False, repeat=False,
         mx_tsvs=None, common_file=None, m=90, n=0, initial_only=False, write_fai=True, engine="device", refine_repeat_file=None, screen_repeat_file=None,
-        graph_budget=None, assess=None, gaps=False, gap_links=None):
+        graph_budget=None, assess=None, gaps=False, gap_links=None, gap_block_links=False):
     """FASTA paths -> engine (outputs in .outputs and in the CWD).  Mirrors oracle.synteny_oracle.run_pipeline's
     signature so the parity tests read alike.  Under torch.distributed (WORLD_SIZE > 1, process group already
     initialised by the caller) genomes are sharded over the ranks.
@@ -509,7 +509,9 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
     <prefix>.block_divergence.tsv from the genomes still resident (ntsynt_amd/assess.py; one rank only).  gaps: after that,
     <prefix>.gaps.tsv and <prefix>.gap_summary.tsv from the resident genomes and the resident common filter (ntsynt_amd/gaps.py; one
     rank only, and only with a common filter).  gap_links = (rate, min_anchors): implies gaps; after the two gap files,
-    <prefix>.gap_links.tsv (gaps.links: where each gap's shared sequence lies in the other genomes)."""
+    <prefix>.gap_links.tsv (gaps.links: where each gap's shared sequence lies in the other genomes).  gap_block_links: needs
+    gap_links, whose rate and min_anchors it shares; after that file, <prefix>.gap_block_links.tsv (gaps.block_links: where it lies
+    inside the blocks of every genome, the gap's own included)."""
     prefix = prefix or f"ntSynt.k{k}.w{w}"
     if mx_tsvs is not None and len(mx_tsvs) != len(fastas):
         raise ValueError("one minimizer TSV per FASTA file")
@@ -537,6 +539,10 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         st.mem = _mem
     if assess is not None and (world > 1 or (mx_tsvs is not None and initial_only)):
         raise ValueError("assess needs every genome resident on one GPU (one rank, genomes loaded)")
+    if gap_block_links and gap_links is None:
+        raise ValueError("gap_block_links needs gap_links = (rate, min_anchors)")
+    if gap_block_links and len(fastas) > 32:
+        raise ValueError("gap_block_links takes at most 32 genomes (the join takes 64 lists: every genome's gaps and its blocks)")
     if gap_links is not None:
         gaps = True                     # the links are drawn between the gaps the report cuts
         if int(gap_links[0]) < 1 or int(gap_links[1]) < 1:
@@ -1048,7 +1054,8 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         st.start("gaps")
         from . import assess as assess_, gaps as gaps_
         by_name = {fa.basename(p): genomes[p] for p in fastas}
-        gap_rows, block_rows, n_bits, occupancy = gaps_.report(backend.ctx, by_name, bf, k, assess_.read_blocks(f"{prefix}.synteny_blocks.tsv"))
+        table_rows = assess_.read_blocks(f"{prefix}.synteny_blocks.tsv")
+        gap_rows, block_rows, n_bits, occupancy = gaps_.report(backend.ctx, by_name, bf, k, table_rows)
         texts = gaps_.table(gap_rows, k, n_bits, occupancy), gaps_.summary(gap_rows, block_rows, k, n_bits, occupancy, genomes=list(by_name))
         for name, text in zip((f"{prefix}.gaps.tsv", f"{prefix}.gap_summary.tsv"), texts):
             with open(name, "w", encoding="utf-8") as fh:
@@ -1059,12 +1066,22 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         if gap_links is not None:
             st.start("gap_links")
             l_rate, l_min = int(gap_links[0]), int(gap_links[1])
-            text = gaps_.links_table(gaps_.links(backend.ctx, by_name, bf, k, gap_rows, l_rate, l_min), k, l_rate, l_min, n_bits)
+            sampling = gaps_.sample_gaps(by_name, bf, k, gap_rows, l_rate)
+            text = gaps_.links_table(gaps_.links(backend.ctx, by_name, bf, k, gap_rows, l_rate, l_min, sampling=sampling), k, l_rate, l_min, n_bits)
             with open(f"{prefix}.gap_links.tsv", "w", encoding="utf-8") as fh:
                 fh.write(text)
             eng.outputs[f"{prefix}.gap_links.tsv"] = text
             st.stop()
             st.mark("gap_links_done")
+            if gap_block_links:
+                st.start("gap_block_links")
+                b_rows, n_set = gaps_.block_links(backend.ctx, by_name, bf, k, gap_rows, block_rows, table_rows, sampling[0], sampling[1], l_rate, l_min)
+                text = gaps_.block_links_table(b_rows, k, l_rate, l_min, n_bits, n_set)
+                with open(f"{prefix}.gap_block_links.tsv", "w", encoding="utf-8") as fh:
+                    fh.write(text)
+                eng.outputs[f"{prefix}.gap_block_links.tsv"] = text
+                st.stop()
+                st.mark("gap_block_links_done")
     memory = st.memory()
     if benchmark and rank == 0:
         st.write(f"{prefix}.stage_times.tsv", memory)

@@ -1,8 +1,10 @@
 """Measurement behind docs/design/04_10_gap_links.md "Measured": the two launches of nts_bf_sample_intervals (k_bf_sample<false> counts,
 k_bf_sample<true> writes) against k_bf_count_intervals on the same genome, the same intervals and the same filter in the same process,
-and nts_iv_links on three genomes' samples.
+and nts_iv_links on three genomes' samples.  With --hset, the measurement behind docs/design/04_11_gap_block_links.md instead: hset_build for
+the hashes of a tenth of the intervals' rate-16 samples, the two launches of nts_hset_sample_intervals over all intervals, and the two
+launches of nts_bf_sample_intervals over the same intervals in the same process as the yardstick.
 
-    python scripts/gap_links_measure.py [--bp 3000000000] [--calls 6] [--out FILE.json]
+    python scripts/gap_links_measure.py [--bp 3000000000] [--calls 6] [--out FILE.json] [--hset]
 
 A 3 Gbp synthetic genome (24 contigs) cut into 10^4 tiling intervals, the common filter of the three-genome 1 % family.  The launches
 are timed with device events (nts_timing), the whole call with the host clock around it.  Rate 1 writes a record for every k-mer the
@@ -19,7 +21,7 @@ import time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import numpy as np  # noqa: E402
 
-from ntsynt_amd.device import BloomFilter, Context, Genome, bf_size_bytes  # noqa: E402
+from ntsynt_amd.device import BloomFilter, Context, Genome, HashSet, bf_size_bytes  # noqa: E402
 
 SEED, DIVERGENCE = 20240207, 0.005                              # scripts/gaps_measure.py's family
 
@@ -57,6 +59,32 @@ def timed(ctx, names, fn, calls):
     return out
 
 
+def measure_hset(ctx, g, bf, iv, tenth, k, calls, out):
+    "the set sweep beside the filter sweep: same genome, same intervals, same process"
+    rec10, _ = g.bf_sample_intervals(bf, tenth, k, 16)
+    members = np.unique(rec10["h0"])
+    del rec10
+    made = []
+
+    def build():
+        made.append(HashSet(ctx, members))
+        if len(made) > 1:
+            made.pop(0).free()
+    out["hset_build"] = dict(timed(ctx, ["hset_build"], build, calls), hashes=int(members.size))
+    hset = made[0]
+    set_timers, bf_timers = ["hset_sample_count", "hset_sample_write"], ["bf_sample_count", "bf_sample_write"]
+    hit, _ = g.hset_sample_intervals(hset, iv, k, 16)           # warm-up, and the record count
+    out["hset_sample"] = dict(timed(ctx, set_timers, lambda: g.hset_sample_intervals(hset, iv, k, 16), calls), records=int(hit.size))
+    rec, _ = g.bf_sample_intervals(bf, iv, k, 16)
+    out["bf_sample"] = dict(timed(ctx, bf_timers, lambda: g.bf_sample_intervals(bf, iv, k, 16), calls), records=int(rec.size))
+    both_set = sum(out["hset_sample"][t]["median_ms"] for t in set_timers)
+    both_bf = sum(out["bf_sample"][t]["median_ms"] for t in bf_timers)
+    out["both_launches_ms"] = {"hset_sample": both_set, "bf_sample": both_bf, "ratio": both_set / both_bf}
+    assert all(out["hset_sample"][t]["timed_launches_per_call"] == [1] for t in set_timers), out
+    assert all(out["bf_sample"][t]["timed_launches_per_call"] == [1] for t in bf_timers), out
+    hset.free()
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--bp", type=int, default=3_000_000_000)
@@ -65,6 +93,7 @@ def main():
     p.add_argument("--intervals", type=int, default=10_000)
     p.add_argument("--min-anchors", type=int, default=4)
     p.add_argument("--no-join", action="store_true", help="the sampling launches only")
+    p.add_argument("--hset", action="store_true", help="the set sweep of gap block links beside the filter sweep, and nothing else")
     p.add_argument("--out")
     args = p.parse_args()
     k = args.k
@@ -84,6 +113,18 @@ def main():
     ctx.profile(2)
     kmers, hits = g.bf_count_intervals(bf, iv, k)             # warm-up, and the figures themselves
     out["intervals"], out["kmers"], out["held"] = int(iv.shape[0]), int(kmers.sum()), int(hits.sum())
+    if args.hset:
+        measure_hset(ctx, g, bf, iv, tenth, k, args.calls, out)
+        ctx.profile(False)
+        text = json.dumps(out, indent=1)
+        print(text)
+        if args.out:
+            with open(args.out, "w", encoding="utf-8") as fh:
+                fh.write(text + "\n")
+        g.free()
+        bf.free()
+        ctx.close()
+        return
     # the yardstick: the counting launch, which probes every k-mer
     out["bf_count_iv"] = timed(ctx, ["bf_count_iv"], lambda: g.bf_count_intervals(bf, iv, k), args.calls)
     sample_timers = ["bf_sample_count", "bf_sample_write"]
