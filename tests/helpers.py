@@ -1,8 +1,12 @@
 """Shared helpers for the parity tests: random sequences with the edge cases the domain has
-(N runs, lower case, ragged / empty / short records) in both containers (oracle and HIP)."""
+(N runs, lower case, ragged / empty / short records) in both containers (oracle and HIP), and the oracle's statements of the
+interval sweeps (counts, samples against a filter and against a set, sketches) that more than one module compares with."""
 import numpy as np
 
 from oracle import nts_oracle as O
+from tests.divergence_ref import SENTINEL
+
+U64_MAX = (1 << 64) - 1
 
 
 def random_records(rng, lengths, n_frac=0.01, lower_frac=0.05, n_runs=True):
@@ -65,3 +69,82 @@ def genome_end_case(k):
     iv.append((0, 2500, 3500))
     assert (500 - k + 1) % 32 not in (0, 1)
     return [f"e{i}" for i in range(3)], seqs, iv
+
+
+# ---- the interval sweeps by their definitions: what the GPU modules compare with, exactly ---------------------------------------------
+def oracle_counts(seqs, k, bits, intervals):
+    "per interval (valid k-mers wholly inside, those the filter holds)"
+    per_rec, out = {}, []
+    for rec, start, end in intervals:
+        if rec not in per_rec:
+            pos, h0 = O.hash_all(seqs[rec], k)
+            per_rec[rec] = (pos.astype(np.int64), np.array([O.bf_contains(bits, h) for h in h0], dtype=bool))
+        pos, held = per_rec[rec]
+        inside = (pos >= start) & (pos + k <= min(end, len(seqs[rec])))
+        out.append((int(inside.sum()), int(held[inside].sum())))
+    return out
+
+
+_per_k = {}
+
+
+def oracle_kmers(seqs, k, bits):
+    "per record (positions, hashes, held by the filter), once per k and filter"
+    key = (k, bits.tobytes())
+    if key not in _per_k:
+        out = []
+        for s in seqs:
+            pos, h0 = O.hash_all(s, k)
+            out.append((pos.astype(np.int64), h0, np.array([O.bf_contains(bits, h) for h in h0], dtype=bool)))
+        _per_k.clear()
+        _per_k[key] = out
+    return _per_k[key]
+
+
+def oracle_sample(seqs, k, bits, intervals, rate):
+    "(records, per-interval counts) by the definitions: valid, wholly inside, held, h0 <= (2^64 - 1) // rate"
+    from ntsynt_amd.device import SAMPLE_DTYPE
+    per_rec = oracle_kmers(seqs, k, bits)
+    thresh = np.uint64(U64_MAX // rate)
+    parts, counts = [], []
+    for i, (rec, start, end) in enumerate(intervals):
+        pos, h0, held = per_rec[rec]
+        a = min(start, len(seqs[rec]))
+        take = (pos >= a) & (pos + k <= min(end, len(seqs[rec]))) & held & (h0 <= thresh)
+        part = np.zeros(int(take.sum()), dtype=SAMPLE_DTYPE)
+        part["h0"], part["iv"], part["off"] = h0[take], i, pos[take] - a
+        parts.append(part)
+        counts.append(part.size)
+    return np.concatenate(parts), np.array(counts, dtype=np.uint64)
+
+
+def oracle_set_sample(per_rec, seqs, k, members, intervals, rate):
+    "(records, per-interval counts) by the definitions: valid, wholly inside, h0 <= (2^64 - 1) // rate, h0 in the set"
+    from ntsynt_amd.device import SAMPLE_DTYPE
+    thresh = np.uint64(U64_MAX // rate)
+    parts, counts = [], []
+    for i, (rec, start, end) in enumerate(intervals):
+        pos, h0 = per_rec[rec]
+        a = min(start, len(seqs[rec]))
+        take = (pos >= a) & (pos + k <= min(end, len(seqs[rec]))) & (h0 <= thresh) & np.isin(h0, members)
+        part = np.zeros(int(take.sum()), dtype=SAMPLE_DTYPE)
+        part["h0"], part["iv"], part["off"] = h0[take], i, pos[take] - a
+        parts.append(part)
+        counts.append(part.size)
+    return np.concatenate(parts), np.array(counts, dtype=np.uint64)
+
+
+def oracle_sketches(seqs, k, s, intervals):
+    "per interval (its s smallest distinct hashes, ascending; its valid k-mers)"
+    per_rec = {}
+    sk, nk = [], []
+    for rec, start, end in intervals:
+        if rec not in per_rec:
+            per_rec[rec] = O.hash_all(seqs[rec], k)
+        pos, h0 = per_rec[rec]
+        pos = pos.astype(np.int64)
+        inside = (pos >= start) & (pos + k <= min(end, len(seqs[rec])))
+        h = np.unique(h0[inside])
+        sk.append(h[h != SENTINEL][:s])
+        nk.append(int(inside.sum()))
+    return sk, nk

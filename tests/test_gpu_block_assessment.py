@@ -16,6 +16,7 @@ from ntsynt_amd import assess, divergence, synth
 from oracle import nts_oracle as O
 from tests.divergence_ref import SENTINEL
 from tests.helpers import END_CASE_KMERS, genome_end_case, random_records, to_device
+from tests.helpers import oracle_sketches as _oracle
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -63,21 +64,6 @@ def _intervals(k, s):
             (2, 0, 102_600), (2, 1000, 50_000),    # satellite array: many k-mers, few distinct
             (4, 100, 200), (4, 0, 15),             # starts past the record; a record shorter than most k
             (5, 0, 60_000)]
-
-
-def _oracle(seqs, k, s, intervals):
-    per_rec = {}
-    sk, nk = [], []
-    for rec, start, end in intervals:
-        if rec not in per_rec:
-            per_rec[rec] = O.hash_all(seqs[rec], k)
-        pos, h0 = per_rec[rec]
-        pos = pos.astype(np.int64)
-        inside = (pos >= start) & (pos + k <= min(end, len(seqs[rec])))
-        h = np.unique(h0[inside])
-        sk.append(h[h != SENTINEL][:s])
-        nk.append(int(inside.sum()))
-    return sk, nk
 
 
 def _check(g, seqs, k, s, intervals, note=""):

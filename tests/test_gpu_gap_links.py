@@ -15,7 +15,7 @@ import pytest
 
 from ntsynt_amd import assess, gaps, synth
 from oracle import nts_oracle as O
-from tests.helpers import END_CASE_KMERS, genome_end_case, random_records, to_device
+from tests.helpers import END_CASE_KMERS, genome_end_case, oracle_sample, random_records, to_device
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -69,39 +69,6 @@ def sample_intervals(k):
            (0, 20_050, 40_000),                                                 # three tiles, the last one short
            (1, 900, 900), (2, 13_000, 14_000)]                                  # empty; starts beyond the record
     return iv
-
-
-_per_k = {}
-
-
-def oracle_kmers(seqs, k, bits):
-    "per record (positions, hashes, held by the filter), once per k and filter"
-    key = (k, bits.tobytes())
-    if key not in _per_k:
-        out = []
-        for s in seqs:
-            pos, h0 = O.hash_all(s, k)
-            out.append((pos.astype(np.int64), h0, np.array([O.bf_contains(bits, h) for h in h0], dtype=bool)))
-        _per_k.clear()
-        _per_k[key] = out
-    return _per_k[key]
-
-
-def oracle_sample(seqs, k, bits, intervals, rate):
-    "(records, per-interval counts) by the definitions: valid, wholly inside, held, h0 <= (2^64 - 1) // rate"
-    from ntsynt_amd.device import SAMPLE_DTYPE
-    per_rec = oracle_kmers(seqs, k, bits)
-    thresh = np.uint64(U64_MAX // rate)
-    parts, counts = [], []
-    for i, (rec, start, end) in enumerate(intervals):
-        pos, h0, held = per_rec[rec]
-        a = min(start, len(seqs[rec]))
-        take = (pos >= a) & (pos + k <= min(end, len(seqs[rec]))) & held & (h0 <= thresh)
-        part = np.zeros(int(take.sum()), dtype=SAMPLE_DTYPE)
-        part["h0"], part["iv"], part["off"] = h0[take], i, pos[take] - a
-        parts.append(part)
-        counts.append(part.size)
-    return np.concatenate(parts), np.array(counts, dtype=np.uint64)
 
 
 def _filter_of(ctx, names, seqs, k, nbytes=FILTER_BYTES):

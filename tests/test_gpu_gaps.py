@@ -15,7 +15,7 @@ import pytest
 
 from ntsynt_amd import assess, gaps, synth
 from oracle import nts_oracle as O
-from tests.helpers import END_CASE_KMERS, genome_end_case, random_records, to_device
+from tests.helpers import END_CASE_KMERS, genome_end_case, oracle_counts, random_records, to_device
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -64,19 +64,6 @@ def intervals_for(k, seqs):
     assert n_at
     iv.append((0, max(n_at[len(n_at) // 2] - 300, 0), n_at[len(n_at) // 2] + 300))      # crosses an N run
     return iv
-
-
-def oracle_counts(seqs, k, bits, intervals):
-    "per interval (valid k-mers wholly inside, those the filter holds)"
-    per_rec, out = {}, []
-    for rec, start, end in intervals:
-        if rec not in per_rec:
-            pos, h0 = O.hash_all(seqs[rec], k)
-            per_rec[rec] = (pos.astype(np.int64), np.array([O.bf_contains(bits, h) for h in h0], dtype=bool))
-        pos, held = per_rec[rec]
-        inside = (pos >= start) & (pos + k <= min(end, len(seqs[rec])))
-        out.append((int(inside.sum()), int(held[inside].sum())))
-    return out
 
 
 def _filter_of(ctx, names, seqs, k, nbytes=FILTER_BYTES):

@@ -11,6 +11,7 @@ from ntsynt_amd import synth
 from oracle import nts_oracle as O
 from tests import test_gpu_gap_links as L
 from tests.helpers import END_CASE_KMERS, genome_end_case, to_device
+from tests.helpers import oracle_set_sample as oracle_sample
 
 pytestmark = pytest.mark.gpu
 STEP_SECONDS = 600
@@ -111,22 +112,6 @@ def kmers_of(tag, seqs, k):
     if (tag, k) not in _hashes:
         _hashes[(tag, k)] = [(p.astype(np.int64), h) for p, h in (O.hash_all(s, k) for s in seqs)]
     return _hashes[(tag, k)]
-
-
-def oracle_sample(per_rec, seqs, k, members, intervals, rate):
-    "(records, per-interval counts) by the definitions: valid, wholly inside, h0 <= (2^64 - 1) // rate, h0 in the set"
-    from ntsynt_amd.device import SAMPLE_DTYPE
-    thresh = np.uint64(U64_MAX // rate)
-    parts, counts = [], []
-    for i, (rec, start, end) in enumerate(intervals):
-        pos, h0 = per_rec[rec]
-        a = min(start, len(seqs[rec]))
-        take = (pos >= a) & (pos + k <= min(end, len(seqs[rec]))) & (h0 <= thresh) & np.isin(h0, members)
-        part = np.zeros(int(take.sum()), dtype=SAMPLE_DTYPE)
-        part["h0"], part["iv"], part["off"] = h0[take], i, pos[take] - a
-        parts.append(part)
-        counts.append(part.size)
-    return np.concatenate(parts), np.array(counts, dtype=np.uint64)
 
 
 def set_of_copy(tag, copy, k, rate):
