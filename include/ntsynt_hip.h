@@ -36,7 +36,8 @@ typedef struct nts_genome nts_genome; /* one FASTA resident in HBM */
 typedef struct nts_bf nts_bf;         /* Bloom bit array resident in HBM */
 typedef struct nts_mx nts_mx;         /* minimizer list resident in HBM */
 typedef struct nts_hset nts_hset;     /* exact set of 64-bit hashes resident in HBM */
-typedef struct nts_comm nts_comm;     /* RCCL communicator of the multi-GPU path (one rank per GPU) */
+typedef struct nts_hcount nts_hcount; /* per member of an nts_hset, how often it was seen: 32-bit counts resident in HBM */
+typedef struct nts_comm nts_comm;    /* RCCL communicator of the multi-GPU path (one rank per GPU) */
 
 /* hard-mask interval [start, end) in record coordinates (bedtools maskfasta semantics) */
 typedef struct
@@ -499,6 +500,32 @@ void nts_hset_free(nts_ctx* ctx, nts_hset* set);
 int nts_hset_contains(nts_ctx* ctx, const nts_hset* set, const uint64_t* h, uint64_t n, uint8_t* out);
 int nts_hset_sample_intervals(nts_ctx* ctx, const nts_genome* g, uint32_t k, const nts_hset* set, uint64_t rate, const nts_interval* iv,
                               uint64_t n_iv, uint64_t* n_sampled, nts_sample** out, uint64_t* n_out);
+
+/* ---- how often each genome holds a gap's sampled k-mers: gap copies ----------------------------------
+ * nts_hcount_create: a counter for `set`: one uint32 per slot of the set's table and one for the value 2^64 - 1, in device memory
+ *   from the context's allocator, all zero.  It belongs to that set: every other call takes both, and NTS_EINVAL when they do not
+ *   match.  Free the counter before its set.  Released with nts_hcount_free() (NULL: nothing happens).
+ * nts_hcount_clear: every count back to zero, and the running total (below) with them.  Timer "hcount_clear".
+ * nts_hcount_add: every h[i] (host array) that is a member of the set adds 1 to its count; a non-member adds nothing.  One lane per
+ *   value, the set's own walk, one 32-bit atomic add on global memory per member.  Timer "hcount_add".
+ * nts_hset_count_intervals: for every valid k-mer that lies wholly inside interval i of g (the rule, the clipping and the NTS_EINVAL
+ *   of nts_hset_sample_intervals) with h0 <= UINT64_MAX / rate and h0 in the set: 1 to that member's count and 1 to n_hits[i].
+ *   Overlapping intervals count a k-mer once per interval; counts accumulate over calls until cleared.  One launch per 2^23 tiles
+ *   (timer "hcount_sweep"): the sampling sweep's probe, then one atomic add per hit, its result unused; n_hits through one plain
+ *   store per tile.  Integer adds commute: counts are exact and the same from run to run.
+ * nts_hcount_read: out[i] = the count of h[i], 0 for a non-member (host arrays; fewer than 2^32 queries per call).  The order of the
+ *   set's slots differs from run to run, so counts are only ever read by key.
+ * Range: counts are 32-bit.  The counter keeps on the host how many values (nts_hcount_add: n) and k-mers (nts_hset_count_intervals:
+ *   every k-mer of the intervals, hit or not) it has been offered since the last clear; a call that would bring that total to 2^32 or
+ *   more is refused with NTS_ERANGE before anything is launched (and before h is read).
+ *   csrc/nts_hcount.inc; ntsynt_amd/gaps.py copies, `ntSynt --gap-copies`, `bin/ntsynt_gaps --copies-out`. */
+int nts_hcount_create(nts_ctx* ctx, const nts_hset* set, nts_hcount** out);
+int nts_hcount_clear(nts_ctx* ctx, nts_hcount* cnt);
+void nts_hcount_free(nts_ctx* ctx, nts_hcount* cnt);
+int nts_hcount_add(nts_ctx* ctx, const nts_hset* set, nts_hcount* cnt, const uint64_t* h, uint64_t n);
+int nts_hcount_read(nts_ctx* ctx, const nts_hset* set, const nts_hcount* cnt, const uint64_t* h, uint64_t n, uint32_t* out);
+int nts_hset_count_intervals(nts_ctx* ctx, const nts_genome* g, uint32_t k, const nts_hset* set, nts_hcount* cnt, uint64_t rate,
+                             const nts_interval* iv, uint64_t n_iv, uint64_t* n_hits);
 
 /* ---- C1-C5: minimizer graph -> collinear chains -----------------------------------------------------
  * replaces ntjoin_utils.read_minimizers' duplicate removal, filter_minimizers and build_graph

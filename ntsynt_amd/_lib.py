@@ -175,6 +175,12 @@ SYMBOLS = [
     ("nts_hset_free", None, [c_vp, c_vp]),
     ("nts_hset_contains", ctypes.c_int, [c_vp, c_vp, c_vp, u64, c_vp]),
     ("nts_hset_sample_intervals", ctypes.c_int, [c_vp, c_vp, u32, c_vp, u64, ctypes.POINTER(Interval), u64, c_vp, ctypes.POINTER(c_vp), c_u64p]),
+    ("nts_hcount_create", ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(c_vp)]),
+    ("nts_hcount_clear", ctypes.c_int, [c_vp, c_vp]),
+    ("nts_hcount_free", None, [c_vp, c_vp]),
+    ("nts_hcount_add", ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, u64]),
+    ("nts_hcount_read", ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, u64, c_vp]),
+    ("nts_hset_count_intervals", ctypes.c_int, [c_vp, c_vp, u32, c_vp, c_vp, u64, ctypes.POINTER(Interval), u64, c_vp]),
     ("nts_genome_valid_bases", ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(Interval), u64, c_vp]),
     ("nts_minhash_pairs", ctypes.c_int, [c_vp, u32, c_vp, c_vp, u64, c_vp, c_vp, u64, c_vp, c_vp]),
     ("nts_graph_build", ctypes.c_int, [c_vp, u32, ctypes.POINTER(MxList), ctypes.POINTER(Graph)]),

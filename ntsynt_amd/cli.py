@@ -78,6 +78,9 @@ def build_parser():
     p.add_argument("--gap-block-links", help="with --gap-links (which it implies, and whose rate and minimum it shares), write <prefix>.gap_block_links.tsv:\n"
                    "where each gap's sampled k-mers lie inside the blocks of every genome, its own included (a second copy, a moved segment)",
                    action="store_true")
+    p.add_argument("--gap-copies", help="with --gaps (which it implies), write <prefix>.gap_copies.tsv: how often each genome holds each gap's sampled\n"
+                   "k-mers, genome-wide, and whether the gap is unique everywhere, a repeat of its own genome or neither (shares --gap-links-rate)",
+                   action="store_true")
     p.add_argument("--gap-links-rate", help="sample one in this many of the gap k-mers the filter holds [16]", type=int, default=16)
     p.add_argument("--gap-links-min", help="anchors (sampled k-mers in common, unique in every genome) a link needs [4]", type=int, default=4)
     p.add_argument("--device", help="GPU index [0]", type=int, default=0)
@@ -143,7 +146,7 @@ def estimate_divergence(parser, args, say):
 
 
 def check_reports(parser, args):
-    "the switches of the reports behind the run (--assess, --gaps, --gap-links, --gap-block-links): what each implies and where each is refused"
+    "the switches of the reports behind the run (--assess, --gaps, --gap-links, --gap-block-links, --gap-copies): what each implies and where each is refused"
     if args.assess:
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             parser.error("--assess works from the genomes resident on one GPU: run it on one rank, or assess the finished run with "
@@ -166,6 +169,15 @@ def check_reports(parser, args):
             parser.error("--gap-links reads the common Bloom filter: not with --no-common")
         if args.gap_links_rate < 1 or args.gap_links_min < 1:
             parser.error("--gap-links-rate and --gap-links-min must be positive")
+        args.gaps = True
+    if args.gap_copies:
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            parser.error("--gap-copies works from the genomes resident on one GPU: run it on one rank, or report on the finished run with "
+                         "ntsynt_gaps --tsv <prefix>.synteny_blocks.tsv --fastas ... --common <prefix>.common.bf --copies-out <prefix>.gap_copies.tsv")
+        if args.no_common:
+            parser.error("--gap-copies reads the common Bloom filter: not with --no-common")
+        if args.gap_links_rate < 1:
+            parser.error("--gap-links-rate must be positive")
         args.gaps = True
     if args.gaps:
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -207,7 +219,8 @@ def main(argv=None):
             raise FileNotFoundError(f"Input file {fasta} not found.")
     plan = ["faidx x%d" % len(fastas)] + ([] if args.no_common else ["make_common_bf"]) + \
            ["indexlr x%d" % len(fastas), "ntsynt_synteny"] + (["assess"] if args.assess else []) + (["gaps"] if args.gaps else []) + \
-           (["gap_links"] if args.gap_links else []) + (["gap_block_links"] if args.gap_block_links else [])
+           (["gap_links"] if args.gap_links else []) + (["gap_block_links"] if args.gap_block_links else []) + \
+           (["gap_copies"] if args.gap_copies else [])
     if args.dry_run:
         say("Stages (GPU, in process):", " -> ".join(plan))
         return 0
@@ -262,7 +275,7 @@ def _run(pipeline, fastas, args, device, quiet):
     pipeline.run(fastas, k=args.k, w=args.w, fpr=args.fpr, prefix=args.prefix, w_rounds=args.w_rounds,
                  indel=args.indel, merge=args.merge, block_size=args.block_size, common=not args.no_common,
                  simplify=not args.no_simplify_graph, device=device, benchmark=args.benchmark,
-                 dev=args.dev, interarrivals=args.interarrivals, assess=(args.assess_k, args.assess_s) if args.assess else None, gaps=args.gaps, gap_links=(args.gap_links_rate, args.gap_links_min) if args.gap_links else None, gap_block_links=args.gap_block_links, repeat=args.repeat, bf_rounding=args.bf_rounding, bf_signature=args.bf_signature or pipeline.BF_SIGNATURE,
+                 dev=args.dev, interarrivals=args.interarrivals, assess=(args.assess_k, args.assess_s) if args.assess else None, gaps=args.gaps, gap_links=(args.gap_links_rate, args.gap_links_min) if args.gap_links else None, gap_block_links=args.gap_block_links, gap_copies=args.gap_links_rate if args.gap_copies else None, repeat=args.repeat, bf_rounding=args.bf_rounding, bf_signature=args.bf_signature or pipeline.BF_SIGNATURE,
                  log=print if (args.dev and int(os.environ.get("RANK", "0")) == 0) else quiet)
 
 

@@ -31,16 +31,35 @@ struct HsetView // what a kernel takes
   __device__ __forceinline__ uint64_t home(uint64_t h) const { return (h * HSET_MULT) >> shift; }
 };
 
-// is h (!= HSET_EMPTY) in the table, given that slot s was found to hold v
-__device__ __forceinline__ bool hset_walk(const HsetView& t, uint64_t h, uint64_t s, uint64_t v)
+constexpr uint64_t HSET_NONE = ~0ULL; // hset_find's "not a member" (no table has 2^64 slots)
+
+// the one walk, from slot s, which was found to hold v, for h (!= HSET_EMPTY); what it answers is the caller's: As::hit(slot) / As::miss()
+template <typename As>
+__device__ __forceinline__ auto hset_walk_as(const HsetView& t, uint64_t h, uint64_t s, uint64_t v) -> decltype(As::miss())
 {
   for (;;) {
-    if (v == h) return true;
-    if (v == HSET_EMPTY) return false;
+    if (v == h) return As::hit(s);
+    if (v == HSET_EMPTY) return As::miss();
     s = (s + 1) & t.mask;
     v = t.slots[s];
   }
 }
+struct HsetAsHeld
+{
+  static __device__ __forceinline__ bool hit(uint64_t) { return true; }
+  static __device__ __forceinline__ bool miss() { return false; }
+};
+struct HsetAsSlot
+{
+  static __device__ __forceinline__ uint64_t hit(uint64_t s) { return s; }
+  static __device__ __forceinline__ uint64_t miss() { return HSET_NONE; }
+};
+
+// is h (!= HSET_EMPTY) in the table, given that slot s was found to hold v
+__device__ __forceinline__ bool hset_walk(const HsetView& t, uint64_t h, uint64_t s, uint64_t v) { return hset_walk_as<HsetAsHeld>(t, h, s, v); }
+
+// the slot that holds it, HSET_NONE when the table does not have it (nts_hcount.inc: a member's count lies at its slot's index)
+__device__ __forceinline__ uint64_t hset_find(const HsetView& t, uint64_t h, uint64_t s, uint64_t v) { return hset_walk_as<HsetAsSlot>(t, h, s, v); }
 
 __global__ __launch_bounds__(256) void k_hset_insert(const uint64_t* __restrict__ in, uint64_t n, uint64_t* slots, uint64_t mask, uint32_t shift)
 {

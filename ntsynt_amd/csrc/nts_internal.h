@@ -566,6 +566,15 @@ struct nts_hset // an exact set of 64-bit values: open addressing, 2^m slots of 
   int device = 0;
 };
 
+struct nts_hcount // one uint32 per slot of a set's table, and one for 2^64 - 1: how often each member was seen (csrc/nts_hcount.inc)
+{
+  uint32_t* d_cnt = nullptr;     // n_slots + 1 counts; [n_slots] is the count of 2^64 - 1
+  const nts_hset* set = nullptr; // the set it belongs to (compared, never followed)
+  uint64_t n_slots = 0;
+  uint64_t offered = 0; // values and k-mers offered since the last clear, hits or not: stays below 2^32
+  int device = 0;
+};
+
 struct nts_mx
 {
   uint64_t n = 0;

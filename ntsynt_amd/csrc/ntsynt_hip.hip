@@ -1597,6 +1597,7 @@ int launch_hash(nts_ctx* ctx, const char* name, const nts_genome* g, const Genom
 #include "nts_bf_iv.inc"
 #include "nts_bf_sample.inc"
 #include "nts_hset.inc"
+#include "nts_hcount.inc"
 
 // acc &= the filter of genome g the literal way, for a running filter that holds few bits (defined behind the sketch's host code,
 // whose accept kernels and summary it uses): 0 = done, 1 = does not apply or did not fit (acc is untouched), < 0 = error
@@ -2778,6 +2779,51 @@ int nts_hset_sample_intervals(nts_ctx* ctx, const nts_genome* g, uint32_t k, con
     return fail(ctx, NTS_EINVAL, "nts_hset_sample_intervals: bad arguments");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   return hset_sample_intervals_run(ctx, g, k, set, rate, iv, n_iv, n_sampled, out, n_out);
+}
+
+int nts_hcount_create(nts_ctx* ctx, const nts_hset* set, nts_hcount** out)
+{
+  if (!ctx || !set || !out) return fail(ctx, NTS_EINVAL, "nts_hcount_create: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return hcount_create_run(ctx, set, out);
+}
+
+int nts_hcount_clear(nts_ctx* ctx, nts_hcount* cnt)
+{
+  if (!ctx || !cnt) return fail(ctx, NTS_EINVAL, "nts_hcount_clear: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return hcount_clear_run(ctx, cnt);
+}
+
+void nts_hcount_free(nts_ctx* ctx, nts_hcount* cnt)
+{
+  if (!cnt) return;
+  if (ctx) hipSetDevice(ctx->device);
+  if (cnt->d_cnt) dev_free(cnt->d_cnt);
+  delete cnt;
+}
+
+int nts_hcount_add(nts_ctx* ctx, const nts_hset* set, nts_hcount* cnt, const uint64_t* h, uint64_t n)
+{
+  if (!ctx || !set || !cnt || (n && !h)) return fail(ctx, NTS_EINVAL, "nts_hcount_add: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return hcount_add_run(ctx, set, cnt, h, n);
+}
+
+int nts_hcount_read(nts_ctx* ctx, const nts_hset* set, const nts_hcount* cnt, const uint64_t* h, uint64_t n, uint32_t* out)
+{
+  if (!ctx || !set || !cnt || (n && (!h || !out))) return fail(ctx, NTS_EINVAL, "nts_hcount_read: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return hcount_read_run(ctx, set, cnt, h, n, out);
+}
+
+int nts_hset_count_intervals(nts_ctx* ctx, const nts_genome* g, uint32_t k, const nts_hset* set, nts_hcount* cnt, uint64_t rate,
+                             const nts_interval* iv, uint64_t n_iv, uint64_t* n_hits)
+{
+  if (!ctx || !g || !set || !cnt || k == 0 || rate == 0 || (n_iv && (!iv || !n_hits)))
+    return fail(ctx, NTS_EINVAL, "nts_hset_count_intervals: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return hset_count_intervals_run(ctx, g, k, set, cnt, rate, iv, n_iv, n_hits);
 }
 
 int nts_genome_valid_bases(nts_ctx* ctx, const nts_genome* g, const nts_interval* iv, uint64_t n_iv, uint64_t* n_valid)

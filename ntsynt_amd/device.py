@@ -508,6 +508,18 @@ class Genome:
         self.ctx.lib.nts_free(p)
         return out, counts
 
+    def hset_count_intervals(self, hset, counts, intervals, k, rate):
+        """for every k-mer of the intervals with h0 <= (2^64 - 1) // rate whose h0 is a member of `hset` (HashSet), 1 to its count in
+        `counts` (HashCounts of that set) (nts_hset_count_intervals).  intervals as in minhash_intervals; a k-mer counts once per
+        interval that holds it; counts accumulate until counts.clear().  Returns the hits per interval [n] uint64."""
+        iv = self._interval_array(intervals)
+        n = iv.size
+        hits = np.zeros(n, dtype=np.uint64)
+        self.ctx.check(self.ctx.lib.nts_hset_count_intervals(self.ctx.h, self.h, int(k), hset.h, counts.h, int(rate),
+                                                             ctypes.cast(iv.ctypes.data, ctypes.POINTER(Interval)), n, hits.ctypes.data),
+                       "nts_hset_count_intervals")
+        return hits
+
     def free(self):
         if self.h:
             self.ctx.lib.nts_genome_free(self.ctx.h, self.h)
@@ -543,6 +555,46 @@ class HashSet:
     def free(self):
         if self.h:
             self.ctx.lib.nts_hset_free(self.ctx.h, self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class HashCounts:
+    """Per member of a HashSet, how often it was seen: 32-bit counts in HBM beside the set's table (nts_hcount_create), all zero at
+    first.  Genome.hset_count_intervals and add() add to them; they are read by key.  Free it before its set.  After free() every
+    call with it is refused (the handle is NULL)."""
+
+    def __init__(self, ctx, hset):
+        self.ctx, self.hset = ctx, hset
+        h = c_vp()
+        ctx.check(ctx.lib.nts_hcount_create(ctx.h, hset.h, ctypes.byref(h)), "nts_hcount_create")
+        self.h = h
+
+    def add(self, values):
+        "every value that is a member adds 1 to its count; the others add nothing (nts_hcount_add)"
+        v = np.ascontiguousarray(values, dtype=np.uint64).ravel()
+        self.ctx.check(self.ctx.lib.nts_hcount_add(self.ctx.h, self.hset.h, self.h, v.ctypes.data if v.size else None, v.size), "nts_hcount_add")
+
+    def read(self, values):
+        "[n] uint32: the count of each value, 0 for one that is not a member (nts_hcount_read)"
+        v = np.ascontiguousarray(values, dtype=np.uint64).ravel()
+        out = np.zeros(v.size, dtype=np.uint32)
+        self.ctx.check(self.ctx.lib.nts_hcount_read(self.ctx.h, self.hset.h, self.h, v.ctypes.data if v.size else None, v.size,
+                                                    out.ctypes.data if v.size else None), "nts_hcount_read")
+        return out
+
+    def clear(self):
+        "every count back to zero (nts_hcount_clear)"
+        self.ctx.check(self.ctx.lib.nts_hcount_clear(self.ctx.h, self.h), "nts_hcount_clear")
+
+    def free(self):
+        if self.h:
+            self.ctx.lib.nts_hcount_free(self.ctx.h, self.h)
             self.h = None
 
     def __del__(self):

@@ -14,7 +14,13 @@ the anchors and its placement from the gaps' flanking blocks.  docs/design/04_10
 Where it lies INSIDE the blocks, the gap's own genome included (`ntSynt --gap-block-links`, `bin/ntsynt_gaps --block-links-out`): the
 gaps' sampled hashes become an exact hash set on the GPU (nts_hset_build), every genome's merged block intervals are swept against it
 (block_links: nts_hset_sample_intervals writes only the hits) and the same join links gaps to block intervals.
-docs/design/04_11_gap_block_links.md."""
+docs/design/04_11_gap_block_links.md.
+
+How often each genome holds a gap's sampled k-mers, genome-wide (`ntSynt --gap-copies`, `bin/ntsynt_gaps --copies-out`): the same set
+gets a table of counts beside it (nts_hcount_create), every genome is swept WHOLE against it (copies: nts_hset_count_intervals adds 1
+per occurrence) and the counts are read back by hash; a gap whose sampled k-mers occur once in every genome could have been chained, one
+whose k-mers its own genome holds several times is a repeat and no threshold brings it back (copy_stats).
+docs/design/04_12_gap_copies.md."""
 import os
 from collections import namedtuple
 
@@ -27,6 +33,8 @@ LINK_COLUMNS = ("genome_a", "contig_a", "start_a", "end_a", "left_a", "right_a",
 LINKS_RATE, LINKS_MIN = 16, 4                                   # --gap-links-rate / --gap-links-min
 BLOCK_LINK_COLUMNS = ("genome", "contig", "start", "end", "left_block", "right_block", "target_genome", "target_contig", "target_start", "target_end",
                       "blocks", "anchors", "orientation", "from", "to", "from_t", "to_t", "sampled", "target_hits", "placement")
+COPY_COLUMNS = ("genome", "contig", "start", "end", "left_block", "right_block", "sampled", "single_own", "single_all", "absent_some",
+                "copies_own_median", "copies_own_max", "copies_any_median", "class")
 MAX_BLOCK_LINK_GENOMES = 32                                     # nts_iv_links takes at most 64 lists: every genome's gaps and its blocks
 
 # a stretch of `contig` of `genome` outside every block: [start, end); kind: between / leading / trailing / unplaced (the record has no
@@ -342,10 +350,96 @@ def block_links_table(rows, k, rate, min_anchors, bits, n_set):
     return "\n".join(lines) + "\n"
 
 
-def main(argv=None):
-    "bin/ntsynt_gaps"
+def copy_stats(counts, own):
+    """a gap's line of <prefix>.gap_copies.tsv from its count matrix: counts[t][j] = how often genome t holds the hash of the gap's
+    j-th sampled record, genome-wide (records, not distinct hashes: a hash the gap has twice has two columns); own = the row of the
+    gap's own genome.  sampled = m, the records; single_own: those its own genome holds exactly once; single_all: those every genome
+    holds exactly once; absent_some: those some genome does not hold (the common filter let them through: a false positive);
+    copies_own_median / copies_own_max: the lower median and the maximum of the own genome's counts; copies_any_median: the lower
+    median of the largest count over the genomes; class: `unique` when more than half of the records are single_all -- the chaining
+    could have used the gap: look at the thresholds --, else `repeat` when more than half are not single_own -- the graph stage drops
+    what a genome has twice, no threshold brings it back --, else `mixed`.  Without records the last five are None and the class `.`."""
+    import numpy as np
+    c = np.asarray(counts, dtype=np.int64)
+    c = c.reshape(c.shape[0], -1) if c.ndim == 2 else c.reshape(0, 0)
+    m = int(c.shape[1]) if c.shape[0] else 0
+    if m == 0:
+        return {"sampled": 0, "single_own": 0, "single_all": 0, "absent_some": None, "copies_own_median": None, "copies_own_max": None,
+                "copies_any_median": None, "class": "."}
+    mine = c[own]
+    single_own, single_all = int((mine == 1).sum()), int((c == 1).all(axis=0).sum())
+    kind = "unique" if 2 * single_all > m else "repeat" if 2 * (m - single_own) > m else "mixed"
+    return {"sampled": m, "single_own": single_own, "single_all": single_all, "absent_some": int((c == 0).any(axis=0).sum()),
+            "copies_own_median": int(np.sort(mine)[(m - 1) // 2]), "copies_own_max": int(mine.max()),
+            "copies_any_median": int(np.sort(c.max(axis=0))[(m - 1) // 2]), "class": kind}
+
+
+def copies(ctx, genomes_by_name, k, gap_rows, lists, sampled, rate=LINKS_RATE):
+    """how often each genome holds each gap's sampled k-mers, genome-wide.  gap_rows: report()'s; lists, sampled: sample_gaps() at
+    this rate (one sampling serves links(), block_links() and this).  The distinct hashes of all lists become one exact set and one
+    table of counts on the GPU; per genome, ascending by name: clear, one nts_hset_count_intervals call over the WHOLE genome -- one
+    interval per record --, the counts of the set read back by hash (a genome given as a loader is loaded once more and freed after its
+    sweep; the filter is not probed: every member is held by it).  Returns (rows, hashes in the set, absent, sampled): one dict per gap
+    with COPY_COLUMNS' keys (copy_stats), in gap_rows' order; absent = the sampled records some genome does not hold at all, of
+    `sampled` records in all -- the filter's false positives among them, counted.  A gap's own genome must hold each of the gap's
+    hashes at least as often as the gap's records do: anything else is a fault of the device code and raises."""
+    import numpy as np
+    from .device import HashCounts, HashSet
+    if rate < 1:
+        raise ValueError("copies: rate must be at least 1")
+    names = sorted(genomes_by_name)
+    gaps_of = {name: [r for r in gap_rows if r["genome"] == name] for name in names}
+    members = np.unique(np.concatenate([np.asarray(lst["h0"], dtype=np.uint64) for lst in lists] + [np.zeros(0, dtype=np.uint64)]))
+    hset = HashSet(ctx, members)
+    per_genome = []
+    try:
+        counts = HashCounts(ctx, hset)
+        try:
+            def sweep(name, g):
+                counts.clear()
+                g.hset_count_intervals(hset, counts, [(j, 0, int(n)) for j, n in enumerate(g.rec_len)], k, rate)
+                per_genome.append(counts.read(members))
+            _each_genome(genomes_by_name, names, sweep)
+        finally:
+            counts.free()
+    finally:
+        hset.free()
+    matrix = np.stack(per_genome).astype(np.int64) if per_genome else np.zeros((0, members.size), dtype=np.int64)
+    out, absent, total = [], 0, 0
+    for li, name in enumerate(names):
+        h0 = np.asarray(lists[li]["h0"], dtype=np.uint64)
+        of_records = matrix[:, np.searchsorted(members, h0)]                    # [genome, record]
+        ends = np.concatenate(([0], np.cumsum(np.asarray(sampled[li], dtype=np.int64))))
+        if len(sampled[li]) != len(gaps_of[name]) or int(ends[-1]) != h0.size:
+            raise ValueError(f"copies: the sampling of {name} is not that of these gaps")
+        for q, gap in enumerate(gaps_of[name]):
+            a, b = int(ends[q]), int(ends[q + 1])
+            sub = of_records[:, a:b]
+            _, inverse, times = np.unique(h0[a:b], return_inverse=True, return_counts=True)
+            if (sub[li] < times[inverse]).any():
+                raise RuntimeError(f"copies: {name} {gap['contig']}:{gap['start']}-{gap['end']}: the genome-wide count of a sampled k-mer is below "
+                                   "its count inside the gap (device counts are wrong)")
+            row = {c: gap[c] for c in ("genome", "contig", "start", "end", "left_block", "right_block")}
+            row.update(copy_stats(sub, li))
+            absent += row["absent_some"] or 0
+            total += row["sampled"]
+            out.append(row)
+    return out, int(members.size), absent, total
+
+
+def copies_table(rows, k, rate, bits, n_set, absent_total, sampled_total):
+    """<prefix>.gap_copies.tsv: a header, one line per gap (copies()' rows: the gaps of <prefix>.gaps.tsv, in its order; NA where a gap
+    has no sampled k-mer), then `# k K, rate R, filter BITS bits, set N hashes, absent A of T sampled`"""
+    lines = ["\t".join(COPY_COLUMNS)]
+    for r in rows:
+        lines.append("\t".join("NA" if r[c] is None else str(r[c]) for c in COPY_COLUMNS))
+    lines.append(f"# k {int(k)}, rate {int(rate)}, filter {int(bits)} bits, set {int(n_set)} hashes, absent {int(absent_total)} of {int(sampled_total)} sampled")
+    return "\n".join(lines) + "\n"
+
+
+def build_parser():
+    "bin/ntsynt_gaps' options"
     import argparse
-    import sys
     p = argparse.ArgumentParser(prog="ntsynt_gaps", description="What the synteny blocks of a finished run leave out: every gap of every genome "
                                 "with its N bases and the share of its k-mers that the run's common Bloom filter holds (GPU)")
     p.add_argument("--tsv", help="synteny block table (<prefix>.synteny_blocks.tsv)", required=True)
@@ -356,9 +450,18 @@ def main(argv=None):
     p.add_argument("--links-out", help="also write the links between the gaps of different genomes to this file (<prefix>.gap_links.tsv)")
     p.add_argument("--block-links-out", help="also write the links between the gaps and the block intervals of every genome, the gap's own included, "
                    "to this file (<prefix>.gap_block_links.tsv); uses --links-rate and --links-min")
+    p.add_argument("--copies-out", help="also write how often each genome holds each gap's sampled k-mers, genome-wide, and the gap's class "
+                   "(unique / repeat / mixed) to this file (<prefix>.gap_copies.tsv); uses --links-rate")
     p.add_argument("--links-rate", help=f"sample one in this many of the gap k-mers the filter holds [{LINKS_RATE}]", type=int, default=LINKS_RATE)
     p.add_argument("--links-min", help=f"anchors a link needs [{LINKS_MIN}]", type=int, default=LINKS_MIN)
     p.add_argument("--device", help="GPU index [0]", type=int, default=0)
+    return p
+
+
+def main(argv=None):
+    "bin/ntsynt_gaps"
+    import sys
+    p = build_parser()
     args = p.parse_args(argv)
     if args.links_rate < 1 or args.links_min < 1:
         p.error("--links-rate and --links-min must be positive")
@@ -382,7 +485,7 @@ def main(argv=None):
             blocks = read_blocks(args.tsv)
             gap_rows, block_rows, n_bits, occupancy = report(ctx, loaders, bf, k, blocks)
             texts = table(gap_rows, k, n_bits, occupancy), summary(gap_rows, block_rows, k, n_bits, occupancy, genomes=list(loaders))
-            if args.links_out or args.block_links_out:
+            if args.links_out or args.block_links_out or args.copies_out:
                 sampling = sample_gaps(loaders, bf, k, gap_rows, args.links_rate)
             if args.links_out:
                 link_rows = links(ctx, loaders, bf, k, gap_rows, args.links_rate, args.links_min, sampling=sampling)
@@ -392,6 +495,10 @@ def main(argv=None):
                 b_rows, n_set = block_links(ctx, loaders, bf, k, gap_rows, block_rows, blocks, sampling[0], sampling[1], args.links_rate, args.links_min)
                 with open(args.block_links_out, "w", encoding="utf-8") as fh:
                     fh.write(block_links_table(b_rows, k, args.links_rate, args.links_min, n_bits, n_set))
+            if args.copies_out:
+                c_rows, n_set, absent, n_sampled = copies(ctx, loaders, k, gap_rows, sampling[0], sampling[1], args.links_rate)
+                with open(args.copies_out, "w", encoding="utf-8") as fh:
+                    fh.write(copies_table(c_rows, k, args.links_rate, n_bits, n_set, absent, n_sampled))
         finally:
             bf.free()
     finally:

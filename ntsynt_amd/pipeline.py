@@ -496,7 +496,7 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         block_size=500, common=True, simplify=True, device=0, write_mx_tsv=True, mx_with_seq=True,
         benchmark=False, log=print, ctx=None, backend=None, bf_rounding="up", bf_signature=BF_SIGNATURE, dev=False, interarrivals=False, repeat=False,
         mx_tsvs=None, common_file=None, m=90, n=0, initial_only=False, write_fai=True, engine="device", refine_repeat_file=None, screen_repeat_file=None,
-        graph_budget=None, assess=None, gaps=False, gap_links=None, gap_block_links=False):
+        graph_budget=None, assess=None, gaps=False, gap_links=None, gap_block_links=False, gap_copies=None):
     """FASTA paths -> engine (outputs in .outputs and in the CWD).  Mirrors oracle.synteny_oracle.run_pipeline's
     signature so the parity tests read alike.  Under torch.distributed (WORLD_SIZE > 1, process group already
     initialised by the caller) genomes are sharded over the ranks.
@@ -511,7 +511,9 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
     rank only, and only with a common filter).  gap_links = (rate, min_anchors): implies gaps; after the two gap files,
     <prefix>.gap_links.tsv (gaps.links: where each gap's shared sequence lies in the other genomes).  gap_block_links: needs
     gap_links, whose rate and min_anchors it shares; after that file, <prefix>.gap_block_links.tsv (gaps.block_links: where it lies
-    inside the blocks of every genome, the gap's own included)."""
+    inside the blocks of every genome, the gap's own included).  gap_copies = rate: implies gaps; after those files,
+    <prefix>.gap_copies.tsv (gaps.copies: how often each genome holds each gap's sampled k-mers, genome-wide); the gaps are sampled
+    once for it and the links, so with gap_links its rate is theirs."""
     prefix = prefix or f"ntSynt.k{k}.w{w}"
     if mx_tsvs is not None and len(mx_tsvs) != len(fastas):
         raise ValueError("one minimizer TSV per FASTA file")
@@ -547,6 +549,12 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         gaps = True                     # the links are drawn between the gaps the report cuts
         if int(gap_links[0]) < 1 or int(gap_links[1]) < 1:
             raise ValueError("gap_links = (rate, min_anchors), both at least 1")
+    if gap_copies is not None:
+        gaps = True                     # the copies are counted for the gaps the report cuts
+        if int(gap_copies) < 1:
+            raise ValueError("gap_copies = rate, at least 1")
+        if gap_links is not None and int(gap_links[0]) != int(gap_copies):
+            raise ValueError("gap_copies and gap_links share one sampling: the same rate for both")
     if gaps and (world > 1 or (mx_tsvs is not None and initial_only)):
         raise ValueError("gaps needs every genome resident on one GPU (one rank, genomes loaded)")
     if gaps and not isinstance(backend, GpuBackend):
@@ -1063,6 +1071,7 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
             eng.outputs[name] = text
         st.stop()
         st.mark("gaps_done")
+        sampling = None                 # one sampling of the gaps serves the links, the block links and the copies
         if gap_links is not None:
             st.start("gap_links")
             l_rate, l_min = int(gap_links[0]), int(gap_links[1])
@@ -1082,6 +1091,18 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
                 eng.outputs[f"{prefix}.gap_block_links.tsv"] = text
                 st.stop()
                 st.mark("gap_block_links_done")
+        if gap_copies is not None:
+            st.start("gap_copies")
+            c_rate = int(gap_copies)
+            if sampling is None:
+                sampling = gaps_.sample_gaps(by_name, bf, k, gap_rows, c_rate)
+            c_rows, n_set, absent, n_sampled = gaps_.copies(backend.ctx, by_name, k, gap_rows, sampling[0], sampling[1], c_rate)
+            text = gaps_.copies_table(c_rows, k, c_rate, n_bits, n_set, absent, n_sampled)
+            with open(f"{prefix}.gap_copies.tsv", "w", encoding="utf-8") as fh:
+                fh.write(text)
+            eng.outputs[f"{prefix}.gap_copies.tsv"] = text
+            st.stop()
+            st.mark("gap_copies_done")
     memory = st.memory()
     if benchmark and rank == 0:
         st.write(f"{prefix}.stage_times.tsv", memory)

@@ -2,9 +2,13 @@
 k_bf_sample<true> writes) against k_bf_count_intervals on the same genome, the same intervals and the same filter in the same process,
 and nts_iv_links on three genomes' samples.  With --hset, the measurement behind docs/design/04_11_gap_block_links.md instead: hset_build for
 the hashes of a tenth of the intervals' rate-16 samples, the two launches of nts_hset_sample_intervals over all intervals, and the two
-launches of nts_bf_sample_intervals over the same intervals in the same process as the yardstick.
+launches of nts_bf_sample_intervals over the same intervals in the same process as the yardstick.  With --hcount, the measurement behind
+docs/design/04_12_gap_copies.md: the counting sweep (nts_hset_count_intervals, timer hcount_sweep) over the whole genome against the same
+set, beside k_hset_sample<false> (timer hset_sample_count) on the same tiles in the same process; nts_hcount_add of as many values as the
+sweep had hits; the clear and the read-back of the set's counts; and the same sweep of an assembly-like genome (satellite arrays: many
+adds to one address) beside that of the uniform one, each against the hashes of a tenth of its own rate-16 sample.
 
-    python scripts/gap_links_measure.py [--bp 3000000000] [--calls 6] [--out FILE.json] [--hset]
+    python scripts/gap_links_measure.py [--bp 3000000000] [--calls 6] [--out FILE.json] [--hset | --hcount]
 
 A 3 Gbp synthetic genome (24 contigs) cut into 10^4 tiling intervals, the common filter of the three-genome 1 % family.  The launches
 are timed with device events (nts_timing), the whole call with the host clock around it.  Rate 1 writes a record for every k-mer the
@@ -21,7 +25,7 @@ import time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import numpy as np  # noqa: E402
 
-from ntsynt_amd.device import BloomFilter, Context, Genome, HashSet, bf_size_bytes  # noqa: E402
+from ntsynt_amd.device import BloomFilter, Context, Genome, HashCounts, HashSet, bf_size_bytes  # noqa: E402
 
 SEED, DIVERGENCE = 20240207, 0.005                              # scripts/gaps_measure.py's family
 
@@ -85,6 +89,83 @@ def measure_hset(ctx, g, bf, iv, tenth, k, calls, out):
     hset.free()
 
 
+def counted_sweep(ctx, g, hset, counts, iv, k, calls):
+    "hcount_sweep over `iv`, cleared before every call (a 3 Gbp genome offers the counter most of its 2^32); (figures, hits, k-mers)"
+    def call():
+        counts.clear()
+        return g.hset_count_intervals(hset, counts, iv, k, 16)
+    hits = int(call().sum())                                    # warm-up, and the hit count
+    return dict(timed(ctx, ["hcount_sweep", "hcount_clear"], call, calls), hits=hits), hits
+
+
+def measure_hcount(ctx, g, bf, iv, tenth, k, calls, out, bp):
+    "the counting sweep beside the sampling sweep's count launch: same genome, same set, same tiles, same process"
+    rec10, _ = g.bf_sample_intervals(bf, tenth, k, 16)
+    members = np.unique(rec10["h0"])
+    del rec10
+    hset = HashSet(ctx, members)
+    counts = HashCounts(ctx, hset)
+    out["set_hashes"] = int(members.size)
+    set_timers = ["hset_sample_count", "hset_sample_write"]
+    g.hset_sample_intervals(hset, iv, k, 16)                    # warm-up
+    out["hset_sample"] = timed(ctx, set_timers, lambda: g.hset_sample_intervals(hset, iv, k, 16), calls)
+    out["hcount_sweep"], hits = counted_sweep(ctx, g, hset, counts, iv, k, calls)
+    top = counts.read(members)
+    out["hcount_sweep"].update(largest_count=int(top.max()), members_met=int((top > 0).sum()), counts_sum_equals_hits=bool(int(top.sum()) == hits))
+    # the atomics alone: as many member values as the sweep had hits, one add each
+    values = np.resize(members, hits)
+
+    def add():
+        counts.clear()
+        counts.add(values)
+    add()
+    out["hcount_add"] = dict(timed(ctx, ["hcount_add"], add, calls), values=int(values.size))
+    del values
+    out["hcount_read"] = dict(timed(ctx, ["hcount_read"], lambda: counts.read(members), calls), values=int(members.size))
+    sweep, yard = out["hcount_sweep"]["hcount_sweep"], out["hset_sample"]["hset_sample_count"]
+    out["sweep_vs_count_launch"] = {"hcount_sweep_ms": sweep["median_ms"], "hset_sample_count_ms": yard["median_ms"],
+                                    "difference_ms": sweep["median_ms"] - yard["median_ms"],
+                                    "yardstick_spread_ms": yard["max_ms"] - yard["min_ms"], "hcount_add_ms": out["hcount_add"]["hcount_add"]["median_ms"]}
+    assert sweep["timed_launches_per_call"] == [1] and yard["timed_launches_per_call"] == [1], out
+    counts.free()
+    hset.free()
+    g.free()
+    bf.free()
+    # contention: an assembly-like genome (satellite arrays, repeat families) against the hashes of a tenth of its own sample
+    from ntsynt_amd import synth
+    plan = synth.realistic_plan(24, bp // 24, 0, SEED)
+    ga = Genome.synth_plan(ctx, plan, SEED, 1000, 0.0065, rep=synth.REPEATS, names=plan[2])
+    _, nbytes = bf_size_bytes(ga.total_bp, 0.025)
+    own = BloomFilter(ctx, nbytes, k)
+    own.insert(ga)
+    iv_a = np.array([(r, 0, int(n)) for r, n in enumerate(ga.rec_len)], dtype=np.uint64)
+    order = np.argsort(-ga.rec_len.astype(np.int64), kind="stable")
+    tenth_a, bases = [], 0
+    for r in order:                                             # the longest records up to a tenth of the bases
+        tenth_a.append(iv_a[r])
+        bases += int(ga.rec_len[r])
+        if bases >= ga.total_bp // 10:
+            break
+    rec_a, _ = ga.bf_sample_intervals(own, np.array(tenth_a, dtype=np.uint64), k, 16)
+    members_a = np.unique(rec_a["h0"])
+    del rec_a
+    own.free()
+    hset_a = HashSet(ctx, members_a)
+    counts_a = HashCounts(ctx, hset_a)
+    figures, hits_a = counted_sweep(ctx, ga, hset_a, counts_a, iv_a, k, calls)
+    top = counts_a.read(members_a)
+    kmers_a = int(ga.valid_kmers(k))
+    out["assembly_like"] = dict(figures, bp=int(ga.total_bp), records=int(iv_a.shape[0]), valid_kmers=kmers_a, set_hashes=int(members_a.size),
+                                largest_count=int(top.max()), counts_above_1000=int((top > 1000).sum()), adds_to_counts_above_1000=int(top[top > 1000].sum()))
+    uni_ns = out["hcount_sweep"]["hcount_sweep"]["median_ms"] * 1e6 / out["kmers"]
+    asm_ns = figures["hcount_sweep"]["median_ms"] * 1e6 / kmers_a
+    out["contention"] = {"uniform_ns_per_kmer": uni_ns, "assembly_like_ns_per_kmer": asm_ns, "ratio": asm_ns / uni_ns,
+                         "uniform_hits_per_kmer": hits / out["kmers"], "assembly_like_hits_per_kmer": hits_a / kmers_a}
+    counts_a.free()
+    hset_a.free()
+    ga.free()
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--bp", type=int, default=3_000_000_000)
@@ -94,6 +175,7 @@ def main():
     p.add_argument("--min-anchors", type=int, default=4)
     p.add_argument("--no-join", action="store_true", help="the sampling launches only")
     p.add_argument("--hset", action="store_true", help="the set sweep of gap block links beside the filter sweep, and nothing else")
+    p.add_argument("--hcount", action="store_true", help="the counting sweep of gap copies beside the set sweep's count launch, and nothing else")
     p.add_argument("--out")
     args = p.parse_args()
     k = args.k
@@ -113,6 +195,16 @@ def main():
     ctx.profile(2)
     kmers, hits = g.bf_count_intervals(bf, iv, k)             # warm-up, and the figures themselves
     out["intervals"], out["kmers"], out["held"] = int(iv.shape[0]), int(kmers.sum()), int(hits.sum())
+    if args.hcount:
+        measure_hcount(ctx, g, bf, iv, tenth, k, args.calls, out, args.bp)     # (frees the genome and the filter: it loads another pair)
+        ctx.profile(False)
+        text = json.dumps(out, indent=1)
+        print(text)
+        if args.out:
+            with open(args.out, "w", encoding="utf-8") as fh:
+                fh.write(text + "\n")
+        ctx.close()
+        return
     if args.hset:
         measure_hset(ctx, g, bf, iv, tenth, k, args.calls, out)
         ctx.profile(False)
