@@ -527,6 +527,37 @@ int nts_hcount_read(nts_ctx* ctx, const nts_hset* set, const nts_hcount* cnt, co
 int nts_hset_count_intervals(nts_ctx* ctx, const nts_genome* g, uint32_t k, const nts_hset* set, nts_hcount* cnt, uint64_t rate,
                              const nts_interval* iv, uint64_t n_iv, uint64_t* n_hits);
 
+/* ---- where each genome holds the copies of a gap: gap copy sites --------------------------------------
+ * nts_hset_sample_intervals_capped: nts_hset_sample_intervals with "the set has h0 and 1 <= its count in cnt <= cap" in place of "the
+ *   set has h0": the same records in the same order (interval order, then k-mer order), the same clipping, NTS_EINVAL and
+ *   NTS_ERANGE, two launches per 2^23 tiles (timers "hcount_sample_count", "hcount_sample_write"), no atomic, deterministic; *out
+ *   released with nts_free().  cnt is the set's own counter (NTS_EINVAL otherwise, and for cap = 0 or rate = 0) and is only read:
+ *   its counts and its running total stay what they are.  Per member under the threshold, one dependent 4-byte load of the count
+ *   behind the set's walk.  With cap = 2^32 - 1 after a count sweep of the same intervals the records are those of
+ *   nts_hset_sample_intervals.  csrc/nts_hcount.inc.
+ * nts_iv_sites: n_lists (at most 64) arrays of query records as for nts_iv_links (iv = the gap's index within its list), joined by
+ *   hash against ONE target genome's occurrence records (iv = record index, off = position in the record), multiplicity allowed on
+ *   both sides: a pair is a query record q and a target record o of one hash (a hash a gap has twice and the target three times
+ *   gives six pairs).  For one gap, its pairs ordered by (o.iv, o.off, q's place in its list), a site is a maximal run of
+ *   consecutive pairs with equal o.iv whose consecutive o.off differ by at most `step`.  Per site: hits = its pairs; first_t /
+ *   last_t = the smallest / largest o.off; min_off_q / max_off_q = the smallest / largest q.off; fwd / rev = the consecutive pairs of
+ *   the site, in that order, whose q.off rises / falls (equal: neither).  *out = the sites with hits >= min_hits (>= 1) sorted by
+ *   (list_q, iv_q, rec_t, first_t), *n_out of them; (NULL, 0) for no site, an empty target, an empty list or no list.  Released with
+ *   nts_free().  One radix sort of the target, a lower / upper bound per query record, a scan, ONE LANE PER PAIR to write the
+ *   pairs, two stable radix sorts, a scan and a reduction by key, all on the context's stream and in its workspace, no atomic and
+ *   no launch per gap (timers "iv_sites_join", "iv_sites_pairs", "iv_sites_select"); NTS_ERANGE for 2^32 records, gaps or pairs
+ *   or more.  csrc/nts_iv_sites.inc; ntsynt_amd/gaps.py copy_sites, `ntSynt --gap-copy-sites`, `bin/ntsynt_gaps --copy-sites-out`. */
+typedef struct
+{
+  uint32_t list_q, iv_q, rec_t;
+  uint32_t hits, fwd, rev;
+  uint32_t min_off_q, max_off_q, first_t, last_t;
+} nts_iv_site;
+int nts_hset_sample_intervals_capped(nts_ctx* ctx, const nts_genome* g, uint32_t k, const nts_hset* set, const nts_hcount* cnt, uint32_t cap,
+                                     uint64_t rate, const nts_interval* iv, uint64_t n_iv, uint64_t* n_sampled, nts_sample** out, uint64_t* n_out);
+int nts_iv_sites(nts_ctx* ctx, uint32_t n_lists, const nts_sample* const* lists, const uint64_t* n, const nts_sample* target, uint64_t n_target,
+                 uint32_t step, uint32_t min_hits, nts_iv_site** out, uint64_t* n_out);
+
 /* ---- C1-C5: minimizer graph -> collinear chains -----------------------------------------------------
  * replaces ntjoin_utils.read_minimizers' duplicate removal, filter_minimizers and build_graph
  * (call sites bin/ntsynt_synteny.py:607-612, 483, 539) and the path walk of Ntjoin.find_paths

@@ -35,6 +35,11 @@ class IvLink(ctypes.Structure):
     _fields_ = [(n, u32) for n in ("list_a", "iv_a", "list_b", "iv_b", "anchors", "fwd", "rev", "min_off_a", "max_off_a", "min_off_b", "max_off_b")]
 
 
+class IvSite(ctypes.Structure):
+    "nts_iv_site: a site of a gap in one target genome (nts_iv_sites)"
+    _fields_ = [(n, u32) for n in ("list_q", "iv_q", "rec_t", "hits", "fwd", "rev", "min_off_q", "max_off_q", "first_t", "last_t")]
+
+
 class MxList(ctypes.Structure):
     _fields_ = [("h1", c_vp), ("rec", c_vp), ("pos", c_vp), ("keep", c_vp), ("list_id", c_vp), ("n", u64)]
 
@@ -181,6 +186,9 @@ SYMBOLS = [
     ("nts_hcount_add", ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, u64]),
     ("nts_hcount_read", ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, u64, c_vp]),
     ("nts_hset_count_intervals", ctypes.c_int, [c_vp, c_vp, u32, c_vp, c_vp, u64, ctypes.POINTER(Interval), u64, c_vp]),
+    ("nts_hset_sample_intervals_capped", ctypes.c_int, [c_vp, c_vp, u32, c_vp, c_vp, u32, u64, ctypes.POINTER(Interval), u64, c_vp, ctypes.POINTER(c_vp),
+                                                        c_u64p]),
+    ("nts_iv_sites", ctypes.c_int, [c_vp, u32, ctypes.POINTER(c_vp), c_u64p, c_vp, u64, u32, u32, ctypes.POINTER(c_vp), c_u64p]),
     ("nts_genome_valid_bases", ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(Interval), u64, c_vp]),
     ("nts_minhash_pairs", ctypes.c_int, [c_vp, u32, c_vp, c_vp, u64, c_vp, c_vp, u64, c_vp, c_vp]),
     ("nts_graph_build", ctypes.c_int, [c_vp, u32, ctypes.POINTER(MxList), ctypes.POINTER(Graph)]),

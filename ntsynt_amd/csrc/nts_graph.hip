@@ -838,6 +838,7 @@ extern "C" int nts_graph_build(nts_ctx* ctx, uint32_t n_asm, const nts_mxlist* l
 
 namespace {
 #include "nts_iv_links.inc"
+#include "nts_iv_sites.inc"
 } // namespace
 
 extern "C" int nts_iv_links(nts_ctx* ctx, uint32_t n_lists, const nts_sample* const* lists, const uint64_t* n, uint32_t min_anchors, nts_iv_link** out,
@@ -851,6 +852,19 @@ extern "C" int nts_iv_links(nts_ctx* ctx, uint32_t n_lists, const nts_sample* co
   *n_out = 0;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   return iv_links_run(ctx, n_lists, lists, n, min_anchors, out, n_out);
+}
+
+extern "C" int nts_iv_sites(nts_ctx* ctx, uint32_t n_lists, const nts_sample* const* lists, const uint64_t* n, const nts_sample* target,
+                            uint64_t n_target, uint32_t step, uint32_t min_hits, nts_iv_site** out, uint64_t* n_out)
+{
+  if (!ctx || !out || !n_out || min_hits == 0 || n_lists > IVL_MAX_LISTS || (n_lists && (!lists || !n)) || (n_target && !target))
+    return fail(ctx, NTS_EINVAL, "nts_iv_sites: bad arguments (at most 64 lists, min_hits >= 1)");
+  for (uint32_t l = 0; l < n_lists; ++l)
+    if (n[l] && !lists[l]) return fail(ctx, NTS_EINVAL, "nts_iv_sites: NULL list");
+  *out = nullptr;
+  *n_out = 0;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return iv_sites_run(ctx, n_lists, lists, n, target, n_target, step, min_hits, out, n_out);
 }
 
 extern "C" int nts_graph_budget(nts_ctx* ctx, uint64_t bytes)

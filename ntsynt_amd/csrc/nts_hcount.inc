@@ -16,7 +16,11 @@
 //     design note says what is and is not measured).  The atomic returns nothing, so no lane waits on a contended address.
 //   range: counts are 32-bit.  The counter keeps on the host how many values and k-mers it has been offered since the last clear
 //     (every k-mer of a sweep, hit or not: known before the launch); a call that would bring the total to 2^32 is refused.
-// Experiments build only: NTS_HSET_COUNT_SLICE = tiles per launch (default 2^23), as NTS_HSET_SAMPLE_SLICE.
+//   k_hset_sample_capped<WRITE>: the sampling sweep (nts_bf_sample.inc's sample_tile, as k_hset_sample) that keeps a k-mer when the set
+//     has it AND its count lies in 1..cap (HcapProbe: HcountProbe's slot, then one dependent 4-byte load of the count there).  The
+//     counter is only read: no atomic, the records are deterministic.  docs/design/04_13_gap_copy_sites.md.
+// Experiments build only: NTS_HSET_COUNT_SLICE = tiles per launch (default 2^23), as NTS_HSET_SAMPLE_SLICE (which also cuts the capped
+// sweep's launches).
 
 // the index of h's count: its slot, n_slots for 2^64 - 1 when that is a member, HSET_NONE for a non-member
 __device__ __forceinline__ uint64_t hset_slot_of(const HsetView& t, uint64_t h)
@@ -222,4 +226,54 @@ int hset_count_intervals_run(nts_ctx* ctx, const nts_genome* g, uint32_t k, cons
   });
   std::vector<uint32_t> hits;
   return iv_counts_back(ctx, d_hits, tiles, hits, n_hits);
+}
+
+struct HcapProbe // HcountProbe's loads; held = a member whose count lies in 1..cap
+{
+  HcountProbe p;
+  const uint32_t* __restrict__ cnt;
+  uint32_t cap;
+  __device__ __forceinline__ void issue(int u, uint64_t h0) { p.issue(u, h0); }
+  __device__ __forceinline__ void skip(int u) { p.skip(u); }
+  __device__ __forceinline__ bool held(int u) const
+  {
+    const uint64_t at = p.slot(u); // (at most n_slots: the counter has n_slots + 1 counts)
+    if (at == HSET_NONE) return false;
+    return cnt[at] - 1u < cap; // (a count of 0 wraps to 2^32 - 1, which no cap exceeds)
+  }
+};
+
+template <bool WRITE>
+__global__ __launch_bounds__(HASH_THREADS) void k_hset_sample_capped(const uint8_t* __restrict__ code, const IvTile* __restrict__ tiles,
+                                                                     const uint32_t* __restrict__ tile_off0, HsetView set,
+                                                                     const uint32_t* __restrict__ cnt, uint32_t cap, uint64_t thresh,
+                                                                     uint32_t* __restrict__ tile_cnt, const uint64_t* __restrict__ tile_at,
+                                                                     SampleRec* __restrict__ out, uint64_t n_out, HashParams hp)
+{
+  HcapProbe probe{ HcountProbe{ HsetProbe{ set } }, cnt, cap };
+  sample_tile<WRITE>(code, tiles, tile_off0, probe, thresh, tile_cnt, tile_at, out, n_out, hp);
+}
+
+// hset_sample_intervals_run with the counter beside the set: read only, `offered` stays what it is
+int hset_sample_intervals_capped_run(nts_ctx* ctx, const nts_genome* g, uint32_t k, const nts_hset* s, const nts_hcount* c, uint32_t cap, uint64_t rate,
+                                     const nts_interval* iv, uint64_t n_iv, uint64_t* n_sampled, nts_sample** out, uint64_t* n_out)
+{
+  {
+    const int rc = hcount_check(ctx, s, c, 0, "nts_hset_sample_intervals_capped");
+    if (rc) return rc;
+  }
+  const HsetView set = hset_view(s);
+  const uint32_t* cnt = c->d_cnt;
+  const uint8_t* code = g->d_code + PAD;
+  const SampleNames nm{ "nts_hset_sample_intervals_capped", "hcount_sample_count", "hcount_sample_write", NTS_KNOB("NTS_HSET_SAMPLE_SLICE") };
+  return sample_intervals_run(ctx, g, k, rate, iv, n_iv, n_sampled, out, n_out, nm,
+                              [&](bool write, uint32_t n, const IvTile* d_tiles, const uint32_t* d_off0, uint64_t thresh, uint32_t* d_cnt,
+                                  const uint64_t* d_at, SampleRec* d_out, uint64_t total, const HashParams& hp) {
+                                if (write)
+                                  NTS_LAUNCH(k_hset_sample_capped<true>, dim3(n), dim3(HASH_THREADS), 0, ctx->stream, code, d_tiles, d_off0, set, cnt, cap,
+                                             thresh, d_cnt, d_at, d_out, total, hp);
+                                else
+                                  NTS_LAUNCH(k_hset_sample_capped<false>, dim3(n), dim3(HASH_THREADS), 0, ctx->stream, code, d_tiles, d_off0, set, cnt, cap,
+                                             thresh, d_cnt, d_at, d_out, total, hp);
+                              });
 }

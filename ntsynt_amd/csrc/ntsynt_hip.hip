@@ -2826,6 +2826,15 @@ int nts_hset_count_intervals(nts_ctx* ctx, const nts_genome* g, uint32_t k, cons
   return hset_count_intervals_run(ctx, g, k, set, cnt, rate, iv, n_iv, n_hits);
 }
 
+int nts_hset_sample_intervals_capped(nts_ctx* ctx, const nts_genome* g, uint32_t k, const nts_hset* set, const nts_hcount* cnt, uint32_t cap,
+                                     uint64_t rate, const nts_interval* iv, uint64_t n_iv, uint64_t* n_sampled, nts_sample** out, uint64_t* n_out)
+{
+  if (!ctx || !g || !set || !cnt || k == 0 || cap == 0 || rate == 0 || !out || !n_out || (n_iv && (!iv || !n_sampled)))
+    return fail(ctx, NTS_EINVAL, "nts_hset_sample_intervals_capped: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return hset_sample_intervals_capped_run(ctx, g, k, set, cnt, cap, rate, iv, n_iv, n_sampled, out, n_out);
+}
+
 int nts_genome_valid_bases(nts_ctx* ctx, const nts_genome* g, const nts_interval* iv, uint64_t n_iv, uint64_t* n_valid)
 {
   if (!ctx || !g || (n_iv && (!iv || !n_valid))) return fail(ctx, NTS_EINVAL, "nts_genome_valid_bases: bad arguments");

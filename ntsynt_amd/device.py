@@ -44,6 +44,8 @@ def mem_events_since(lib, before):
 SAMPLE_DTYPE = np.dtype([("h0", "<u8"), ("iv", "<u4"), ("off", "<u4")])
 LINK_DTYPE = np.dtype([(n, "<u4") for n in ("list_a", "iv_a", "list_b", "iv_b", "anchors", "fwd", "rev", "min_off_a", "max_off_a", "min_off_b",
                                             "max_off_b")])
+# nts_iv_site: what Context.iv_sites returns
+SITE_DTYPE = np.dtype([(n, "<u4") for n in ("list_q", "iv_q", "rec_t", "hits", "fwd", "rev", "min_off_q", "max_off_q", "first_t", "last_t")])
 
 
 class Context:
@@ -107,6 +109,27 @@ class Context:
         self.check(self.lib.nts_iv_links(self.h, len(arrs), ptrs, counts.ctypes.data_as(_lib.c_u64p), int(min_anchors), ctypes.byref(p),
                                          ctypes.byref(n)), "nts_iv_links")
         out = np.empty(n.value, dtype=LINK_DTYPE)
+        if n.value:
+            ctypes.memmove(out.ctypes.data, p.value, out.nbytes)
+        self.lib.nts_free(p)
+        return out
+
+    def iv_sites(self, lists, target, step, min_hits):
+        """the sampled k-mers of several lists of gaps joined by hash against one genome's occurrence records, multiplicity allowed on
+        both sides, and grouped into sites (nts_iv_sites).  lists: one SAMPLE_DTYPE array per genome (iv = the gap's index within that
+        list); target: a SAMPLE_DTYPE array with iv = record index and off = position, as Genome.hset_sample_intervals_capped
+        returns it for one interval per record.  Returns a SITE_DTYPE array sorted by (list_q, iv_q, rec_t, first_t): per gap, every
+        maximal run of its pairs within one record whose consecutive positions differ by at most `step`, with at least min_hits
+        pairs."""
+        arrs = [np.ascontiguousarray(a, dtype=SAMPLE_DTYPE) for a in lists]
+        tgt = np.ascontiguousarray(target, dtype=SAMPLE_DTYPE)
+        assert SAMPLE_DTYPE.itemsize == ctypes.sizeof(_lib.Sample) and SITE_DTYPE.itemsize == ctypes.sizeof(_lib.IvSite)
+        ptrs = (c_vp * max(len(arrs), 1))(*[a.ctypes.data for a in arrs])
+        counts = np.array([a.size for a in arrs], dtype=np.uint64)
+        p, n = c_vp(), u64()
+        self.check(self.lib.nts_iv_sites(self.h, len(arrs), ptrs, counts.ctypes.data_as(_lib.c_u64p), tgt.ctypes.data if tgt.size else None, tgt.size,
+                                         int(step), int(min_hits), ctypes.byref(p), ctypes.byref(n)), "nts_iv_sites")
+        out = np.empty(n.value, dtype=SITE_DTYPE)
         if n.value:
             ctypes.memmove(out.ctypes.data, p.value, out.nbytes)
         self.lib.nts_free(p)
@@ -519,6 +542,23 @@ class Genome:
                                                              ctypes.cast(iv.ctypes.data, ctypes.POINTER(Interval)), n, hits.ctypes.data),
                        "nts_hset_count_intervals")
         return hits
+
+    def hset_sample_intervals_capped(self, hset, counts, cap, intervals, k, rate):
+        """hset_sample_intervals that keeps a k-mer only when its count in `counts` (HashCounts of `hset`) lies in 1..cap
+        (nts_hset_sample_intervals_capped).  The counter is only read.  The same (records, per-interval counts), exact and
+        deterministic."""
+        iv = self._interval_array(intervals)
+        n = iv.size
+        per_iv = np.zeros(n, dtype=np.uint64)
+        p, m = c_vp(), u64()
+        self.ctx.check(self.ctx.lib.nts_hset_sample_intervals_capped(self.ctx.h, self.h, int(k), hset.h, counts.h, int(cap), int(rate),
+                                                                     ctypes.cast(iv.ctypes.data, ctypes.POINTER(Interval)), n, per_iv.ctypes.data,
+                                                                     ctypes.byref(p), ctypes.byref(m)), "nts_hset_sample_intervals_capped")
+        out = np.empty(m.value, dtype=SAMPLE_DTYPE)
+        if m.value:
+            ctypes.memmove(out.ctypes.data, p.value, out.nbytes)
+        self.ctx.lib.nts_free(p)
+        return out, per_iv
 
     def free(self):
         if self.h:

@@ -20,7 +20,12 @@ How often each genome holds a gap's sampled k-mers, genome-wide (`ntSynt --gap-c
 gets a table of counts beside it (nts_hcount_create), every genome is swept WHOLE against it (copies: nts_hset_count_intervals adds 1
 per occurrence) and the counts are read back by hash; a gap whose sampled k-mers occur once in every genome could have been chained, one
 whose k-mers its own genome holds several times is a repeat and no threshold brings it back (copy_stats).
-docs/design/04_12_gap_copies.md."""
+docs/design/04_12_gap_copies.md.
+
+WHERE each genome holds those copies (`ntSynt --gap-copy-sites`, `bin/ntsynt_gaps --copy-sites-out`): behind a genome's count sweep the
+same genome is swept once more and the positions of the members whose count lies in 1..cap are written
+(nts_hset_sample_intervals_capped), then joined against the gaps' records with multiplicity allowed on both sides and grouped into
+sites (copy_sites: nts_iv_sites, one call per target genome).  docs/design/04_13_gap_copy_sites.md."""
 import os
 from collections import namedtuple
 
@@ -35,6 +40,9 @@ BLOCK_LINK_COLUMNS = ("genome", "contig", "start", "end", "left_block", "right_b
                       "blocks", "anchors", "orientation", "from", "to", "from_t", "to_t", "sampled", "target_hits", "placement")
 COPY_COLUMNS = ("genome", "contig", "start", "end", "left_block", "right_block", "sampled", "single_own", "single_all", "absent_some",
                 "copies_own_median", "copies_own_max", "copies_any_median", "class")
+SITE_COLUMNS = ("genome", "contig", "start", "end", "left_block", "right_block", "class", "target_genome", "target_contig", "from_t", "to_t", "blocks",
+                "hits", "orientation", "from", "to", "sampled", "usable", "placement")
+SITES_CAP, SITES_STEP = 16, 1000                                # --gap-sites-cap / --gap-sites-step
 MAX_BLOCK_LINK_GENOMES = 32                                     # nts_iv_links takes at most 64 lists: every genome's gaps and its blocks
 
 # a stretch of `contig` of `genome` outside every block: [start, end); kind: between / leading / trailing / unplaced (the record has no
@@ -374,56 +382,82 @@ def copy_stats(counts, own):
             "copies_any_median": int(np.sort(c.max(axis=0))[(m - 1) // 2]), "class": kind}
 
 
-def copies(ctx, genomes_by_name, k, gap_rows, lists, sampled, rate=LINKS_RATE):
-    """how often each genome holds each gap's sampled k-mers, genome-wide.  gap_rows: report()'s; lists, sampled: sample_gaps() at
-    this rate (one sampling serves links(), block_links() and this).  The distinct hashes of all lists become one exact set and one
-    table of counts on the GPU; per genome, ascending by name: clear, one nts_hset_count_intervals call over the WHOLE genome -- one
-    interval per record --, the counts of the set read back by hash (a genome given as a loader is loaded once more and freed after its
-    sweep; the filter is not probed: every member is held by it).  Returns (rows, hashes in the set, absent, sampled): one dict per gap
-    with COPY_COLUMNS' keys (copy_stats), in gap_rows' order; absent = the sampled records some genome does not hold at all, of
-    `sampled` records in all -- the filter's false positives among them, counted.  A gap's own genome must hold each of the gap's
-    hashes at least as often as the gap's records do: anything else is a fault of the device code and raises."""
+def count_genomes(ctx, genomes_by_name, k, lists, rate=LINKS_RATE, sites=None):
+    """the device side of copies() and copy_sites(): the distinct hashes of all lists become one exact set and one table of counts on
+    the GPU; per genome, ascending by name: clear, one nts_hset_count_intervals call over the WHOLE genome -- one interval per record
+    --, the counts of the set read back by hash (a genome given as a loader is loaded once and freed after its sweeps; the filter is
+    not probed: every member is held by it).  sites = (cap, step, min_hits): behind a genome's counts, while they are still in the
+    table, one nts_hset_sample_intervals_capped call over the same intervals writes where the members with a count in 1..cap occur
+    -- at most members * cap records of 16 bytes -- and one nts_iv_sites call joins the lists against them.  Returns (members,
+    matrix, found): the sorted distinct hashes, matrix[t][i] = how often genome t holds members[i], and per genome (record names,
+    SITE_DTYPE array) -- None without `sites`."""
     import numpy as np
     from .device import HashCounts, HashSet
-    if rate < 1:
-        raise ValueError("copies: rate must be at least 1")
     names = sorted(genomes_by_name)
-    gaps_of = {name: [r for r in gap_rows if r["genome"] == name] for name in names}
     members = np.unique(np.concatenate([np.asarray(lst["h0"], dtype=np.uint64) for lst in lists] + [np.zeros(0, dtype=np.uint64)]))
     hset = HashSet(ctx, members)
-    per_genome = []
+    per_genome, found = [], []
     try:
         counts = HashCounts(ctx, hset)
         try:
             def sweep(name, g):
+                whole = [(j, 0, int(n)) for j, n in enumerate(g.rec_len)]
                 counts.clear()
-                g.hset_count_intervals(hset, counts, [(j, 0, int(n)) for j, n in enumerate(g.rec_len)], k, rate)
+                g.hset_count_intervals(hset, counts, whole, k, rate)
                 per_genome.append(counts.read(members))
+                if sites is not None:
+                    cap, step, min_hits = sites
+                    occurrences, _ = g.hset_sample_intervals_capped(hset, counts, cap, whole, k, rate)
+                    found.append((list(g.names), ctx.iv_sites(lists, occurrences, step, min_hits)))
             _each_genome(genomes_by_name, names, sweep)
         finally:
             counts.free()
     finally:
         hset.free()
     matrix = np.stack(per_genome).astype(np.int64) if per_genome else np.zeros((0, members.size), dtype=np.int64)
-    out, absent, total = [], 0, 0
+    return members, matrix, (found if sites is not None else None)
+
+
+def _gap_counts(names, gap_rows, lists, sampled, members, matrix, who):
+    "(list index, gap index, gap row, counts[genome][record], the records' hashes) per gap, in gap_rows' order"
+    import numpy as np
+    gaps_of = {name: [r for r in gap_rows if r["genome"] == name] for name in names}
     for li, name in enumerate(names):
         h0 = np.asarray(lists[li]["h0"], dtype=np.uint64)
         of_records = matrix[:, np.searchsorted(members, h0)]                    # [genome, record]
         ends = np.concatenate(([0], np.cumsum(np.asarray(sampled[li], dtype=np.int64))))
         if len(sampled[li]) != len(gaps_of[name]) or int(ends[-1]) != h0.size:
-            raise ValueError(f"copies: the sampling of {name} is not that of these gaps")
+            raise ValueError(f"{who}: the sampling of {name} is not that of these gaps")
         for q, gap in enumerate(gaps_of[name]):
             a, b = int(ends[q]), int(ends[q + 1])
-            sub = of_records[:, a:b]
-            _, inverse, times = np.unique(h0[a:b], return_inverse=True, return_counts=True)
-            if (sub[li] < times[inverse]).any():
-                raise RuntimeError(f"copies: {name} {gap['contig']}:{gap['start']}-{gap['end']}: the genome-wide count of a sampled k-mer is below "
-                                   "its count inside the gap (device counts are wrong)")
-            row = {c: gap[c] for c in ("genome", "contig", "start", "end", "left_block", "right_block")}
-            row.update(copy_stats(sub, li))
-            absent += row["absent_some"] or 0
-            total += row["sampled"]
-            out.append(row)
+            yield li, q, gap, of_records[:, a:b], h0[a:b]
+
+
+def copies(ctx, genomes_by_name, k, gap_rows, lists, sampled, rate=LINKS_RATE, counted=None):
+    """how often each genome holds each gap's sampled k-mers, genome-wide.  gap_rows: report()'s; lists, sampled: sample_gaps() at
+    this rate (one sampling serves links(), block_links() and this).  The distinct hashes of all lists become one exact set and one
+    table of counts on the GPU; per genome, ascending by name: clear, one nts_hset_count_intervals call over the WHOLE genome -- one
+    interval per record --, the counts of the set read back by hash (count_genomes; `counted`: its result for these lists at this
+    rate, where the caller has it already -- one count sweep per genome serves this and copy_sites()).  Returns (rows, hashes in the
+    set, absent, sampled): one dict per gap with COPY_COLUMNS' keys (copy_stats), in gap_rows' order; absent = the sampled records some genome does not hold at all, of
+    `sampled` records in all -- the filter's false positives among them, counted.  A gap's own genome must hold each of the gap's
+    hashes at least as often as the gap's records do: anything else is a fault of the device code and raises."""
+    import numpy as np
+    if rate < 1:
+        raise ValueError("copies: rate must be at least 1")
+    names = sorted(genomes_by_name)
+    members, matrix, _ = counted if counted is not None else count_genomes(ctx, genomes_by_name, k, lists, rate)
+    out, absent, total = [], 0, 0
+    for li, _, gap, sub, h0 in _gap_counts(names, gap_rows, lists, sampled, members, matrix, "copies"):
+        _, inverse, times = np.unique(h0, return_inverse=True, return_counts=True)
+        if (sub[li] < times[inverse]).any():
+            raise RuntimeError(f"copies: {names[li]} {gap['contig']}:{gap['start']}-{gap['end']}: the genome-wide count of a sampled k-mer is below "
+                               "its count inside the gap (device counts are wrong)")
+        row = {c: gap[c] for c in ("genome", "contig", "start", "end", "left_block", "right_block")}
+        row.update(copy_stats(sub, li))
+        absent += row["absent_some"] or 0
+        total += row["sampled"]
+        out.append(row)
     return out, int(members.size), absent, total
 
 
@@ -434,6 +468,78 @@ def copies_table(rows, k, rate, bits, n_set, absent_total, sampled_total):
     for r in rows:
         lines.append("\t".join("NA" if r[c] is None else str(r[c]) for c in COPY_COLUMNS))
     lines.append(f"# k {int(k)}, rate {int(rate)}, filter {int(bits)} bits, set {int(n_set)} hashes, absent {int(absent_total)} of {int(sampled_total)} sampled")
+    return "\n".join(lines) + "\n"
+
+
+def site_placement(gap, target_genome, target_contig, from_t, to_t):
+    """of a site [from_t, to_t) on `target_contig` of `target_genome`, seen from the gap (a row with genome, contig, start, end):
+    `self` when it lies on the gap's own contig and intersects the gap -- the gap's k-mers found where they were taken --; `own` when
+    the target is the gap's own genome otherwise -- another copy in that genome --; `other` when it is another genome"""
+    if target_genome != gap["genome"]:
+        return "other"
+    if target_contig == gap["contig"] and from_t < gap["end"] and to_t > gap["start"]:
+        return "self"
+    return "own"
+
+
+def site_usable(counts, cap):
+    """from a gap's count matrix (counts[t][j] = how often genome t holds the hash of the gap's j-th sampled record): ([per genome t,
+    the records usable against it: 1 <= counts[t][j] <= cap], the (record, genome) pairs over the cap)"""
+    import numpy as np
+    c = np.asarray(counts, dtype=np.int64)
+    c = c.reshape(c.shape[0], -1) if c.ndim == 2 else c.reshape(0, 0)
+    return [int(x) for x in ((c >= 1) & (c <= int(cap))).sum(axis=1)], int((c > int(cap)).sum())
+
+
+def copy_sites(ctx, genomes_by_name, k, gap_rows, blocks, lists, sampled, rate=LINKS_RATE, cap=SITES_CAP, step=SITES_STEP, min_hits=LINKS_MIN, counted=None):
+    """where each genome, the gap's own included, holds the gaps' sampled k-mers close together.  gap_rows: report()'s; blocks:
+    assess.read_blocks' rows; lists, sampled: sample_gaps() at this rate; counted: count_genomes(..., sites=(cap, step, min_hits)) for
+    these lists where the caller has it already (one count sweep per genome serves copies() and this), else it is run here.  A hash of
+    a gap is usable against genome t when t holds it 1..cap times; the occurrences of the usable hashes in t, paired with the gap's
+    records of the same hash, ordered by (record, position, the record's place in its list), fall into sites: maximal runs within one
+    record whose consecutive positions differ by at most `step`; a site with at least min_hits pairs is kept.  Returns (rows, hashes
+    in the set, over_cap, of): one dict per gap and site with SITE_COLUMNS' keys, by gap genome, gap, target genome, target record,
+    from_t; over_cap = the (sampled record, genome) pairs whose count is above the cap, of `of` = records * genomes.  When the pairs
+    of one target reach 2^32 the join refuses the call and this raises with its message."""
+    if rate < 1 or cap < 1 or step < 0 or min_hits < 1:
+        raise ValueError("copy_sites: rate, cap and min_hits must be at least 1, step at least 0")
+    names = sorted(genomes_by_name)
+    members, matrix, found = counted if counted is not None else count_genomes(ctx, genomes_by_name, k, lists, rate, sites=(cap, step, min_hits))
+    if found is None:
+        raise ValueError("copy_sites: `counted` was made without sites")
+    facts, over_cap, total = {}, 0, 0                            # (list, gap) -> (gap row, class, sampled, usable per genome)
+    for li, q, gap, sub, _ in _gap_counts(names, gap_rows, lists, sampled, members, matrix, "copy_sites"):
+        usable, over = site_usable(sub, cap)
+        facts[(li, q)] = (gap, copy_stats(sub, li)["class"], int(sub.shape[1]), usable)
+        over_cap += over
+        total += int(sub.shape[1]) * len(names)
+    keyed = []
+    for ti, (contigs, sites) in enumerate(found):
+        for s in sites:
+            keyed.append(((int(s["list_q"]), int(s["iv_q"]), ti, int(s["rec_t"]), int(s["first_t"])), contigs, s))
+    keyed.sort(key=lambda t: t[0])
+    out = []
+    for (li, q, ti, _, _), contigs, s in keyed:
+        gap, kind, m, usable = facts[(li, q)]
+        contig, from_t, to_t = contigs[int(s["rec_t"])], int(s["first_t"]), int(s["last_t"]) + int(k)
+        row = {c: gap[c] for c in ("genome", "contig", "start", "end", "left_block", "right_block")}
+        row.update({"class": kind, "target_genome": names[ti], "target_contig": contig, "from_t": from_t, "to_t": to_t,
+                    "blocks": ",".join(blocks_in_span(blocks, names[ti], contig, from_t, to_t)) or ".", "hits": int(s["hits"]),
+                    "orientation": orientation(int(s["fwd"]), int(s["rev"])), "from": gap["start"] + int(s["min_off_q"]),
+                    "to": gap["start"] + int(s["max_off_q"]) + int(k), "sampled": m, "usable": usable[ti],
+                    "placement": site_placement(gap, names[ti], contig, from_t, to_t)})
+        out.append(row)
+    return out, int(members.size), over_cap, total
+
+
+def copy_sites_table(rows, k, rate, cap, step, min_hits, bits, n_set, over_cap, of_total):
+    """<prefix>.gap_copy_sites.tsv: a header, one line per gap and site (copy_sites()' rows, in their order), then
+    `# k K, rate R, cap C, step D, min_hits M, filter BITS bits, set N hashes, over_cap X of Y`"""
+    lines = ["\t".join(SITE_COLUMNS)]
+    for r in rows:
+        lines.append("\t".join(str(r[c]) for c in SITE_COLUMNS))
+    lines.append(f"# k {int(k)}, rate {int(rate)}, cap {int(cap)}, step {int(step)}, min_hits {int(min_hits)}, filter {int(bits)} bits, "
+                 f"set {int(n_set)} hashes, over_cap {int(over_cap)} of {int(of_total)}")
     return "\n".join(lines) + "\n"
 
 
@@ -452,6 +558,10 @@ def build_parser():
                    "to this file (<prefix>.gap_block_links.tsv); uses --links-rate and --links-min")
     p.add_argument("--copies-out", help="also write how often each genome holds each gap's sampled k-mers, genome-wide, and the gap's class "
                    "(unique / repeat / mixed) to this file (<prefix>.gap_copies.tsv); uses --links-rate")
+    p.add_argument("--copy-sites-out", help="also write where each genome, the gap's own included, holds each gap's sampled k-mers close together "
+                   "(the copies of a repeat gap) to this file (<prefix>.gap_copy_sites.tsv); uses --links-rate and --links-min")
+    p.add_argument("--sites-cap", help=f"use a k-mer against a genome that holds it at most this many times [{SITES_CAP}]", type=int, default=SITES_CAP)
+    p.add_argument("--sites-step", help=f"two hits of a site lie at most this many bases apart [{SITES_STEP}]", type=int, default=SITES_STEP)
     p.add_argument("--links-rate", help=f"sample one in this many of the gap k-mers the filter holds [{LINKS_RATE}]", type=int, default=LINKS_RATE)
     p.add_argument("--links-min", help=f"anchors a link needs [{LINKS_MIN}]", type=int, default=LINKS_MIN)
     p.add_argument("--device", help="GPU index [0]", type=int, default=0)
@@ -465,6 +575,10 @@ def main(argv=None):
     args = p.parse_args(argv)
     if args.links_rate < 1 or args.links_min < 1:
         p.error("--links-rate and --links-min must be positive")
+    if args.sites_cap < 1 or args.sites_cap > 0xFFFFFFFF or args.sites_step < 0 or args.sites_step > 0xFFFFFFFF:
+        p.error("--sites-cap must be positive and --sites-step not negative (32-bit values)")
+    if args.copy_sites_out and len(args.fastas) > 2 * MAX_BLOCK_LINK_GENOMES:
+        p.error(f"--copy-sites-out takes at most {2 * MAX_BLOCK_LINK_GENOMES} genomes")
     if args.block_links_out and len(args.fastas) > MAX_BLOCK_LINK_GENOMES:
         p.error(f"--block-links-out takes at most {MAX_BLOCK_LINK_GENOMES} genomes")
     for path in args.fastas + [args.common, args.tsv]:
@@ -485,7 +599,7 @@ def main(argv=None):
             blocks = read_blocks(args.tsv)
             gap_rows, block_rows, n_bits, occupancy = report(ctx, loaders, bf, k, blocks)
             texts = table(gap_rows, k, n_bits, occupancy), summary(gap_rows, block_rows, k, n_bits, occupancy, genomes=list(loaders))
-            if args.links_out or args.block_links_out or args.copies_out:
+            if args.links_out or args.block_links_out or args.copies_out or args.copy_sites_out:
                 sampling = sample_gaps(loaders, bf, k, gap_rows, args.links_rate)
             if args.links_out:
                 link_rows = links(ctx, loaders, bf, k, gap_rows, args.links_rate, args.links_min, sampling=sampling)
@@ -495,8 +609,15 @@ def main(argv=None):
                 b_rows, n_set = block_links(ctx, loaders, bf, k, gap_rows, block_rows, blocks, sampling[0], sampling[1], args.links_rate, args.links_min)
                 with open(args.block_links_out, "w", encoding="utf-8") as fh:
                     fh.write(block_links_table(b_rows, k, args.links_rate, args.links_min, n_bits, n_set))
+            counted = None                                      # one count sweep per genome serves the copies and the copy sites
+            if args.copy_sites_out:
+                counted = count_genomes(ctx, loaders, k, sampling[0], args.links_rate, sites=(args.sites_cap, args.sites_step, args.links_min))
+                s_rows, n_set, over_cap, of_total = copy_sites(ctx, loaders, k, gap_rows, blocks, sampling[0], sampling[1], args.links_rate, args.sites_cap,
+                                                               args.sites_step, args.links_min, counted=counted)
+                with open(args.copy_sites_out, "w", encoding="utf-8") as fh:
+                    fh.write(copy_sites_table(s_rows, k, args.links_rate, args.sites_cap, args.sites_step, args.links_min, n_bits, n_set, over_cap, of_total))
             if args.copies_out:
-                c_rows, n_set, absent, n_sampled = copies(ctx, loaders, k, gap_rows, sampling[0], sampling[1], args.links_rate)
+                c_rows, n_set, absent, n_sampled = copies(ctx, loaders, k, gap_rows, sampling[0], sampling[1], args.links_rate, counted=counted)
                 with open(args.copies_out, "w", encoding="utf-8") as fh:
                     fh.write(copies_table(c_rows, k, args.links_rate, n_bits, n_set, absent, n_sampled))
         finally:

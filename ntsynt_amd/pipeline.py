@@ -496,7 +496,7 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         block_size=500, common=True, simplify=True, device=0, write_mx_tsv=True, mx_with_seq=True,
         benchmark=False, log=print, ctx=None, backend=None, bf_rounding="up", bf_signature=BF_SIGNATURE, dev=False, interarrivals=False, repeat=False,
         mx_tsvs=None, common_file=None, m=90, n=0, initial_only=False, write_fai=True, engine="device", refine_repeat_file=None, screen_repeat_file=None,
-        graph_budget=None, assess=None, gaps=False, gap_links=None, gap_block_links=False, gap_copies=None):
+        graph_budget=None, assess=None, gaps=False, gap_links=None, gap_block_links=False, gap_copies=None, gap_copy_sites=None):
     """FASTA paths -> engine (outputs in .outputs and in the CWD).  Mirrors oracle.synteny_oracle.run_pipeline's
     signature so the parity tests read alike.  Under torch.distributed (WORLD_SIZE > 1, process group already
     initialised by the caller) genomes are sharded over the ranks.
@@ -513,7 +513,10 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
     gap_links, whose rate and min_anchors it shares; after that file, <prefix>.gap_block_links.tsv (gaps.block_links: where it lies
     inside the blocks of every genome, the gap's own included).  gap_copies = rate: implies gaps; after those files,
     <prefix>.gap_copies.tsv (gaps.copies: how often each genome holds each gap's sampled k-mers, genome-wide); the gaps are sampled
-    once for it and the links, so with gap_links its rate is theirs."""
+    once for it and the links, so with gap_links its rate is theirs.  gap_copy_sites = (cap, step, min_hits): needs gap_copies, whose
+    rate it shares; after that file, <prefix>.gap_copy_sites.tsv (gaps.copy_sites: where each genome holds the copies of a gap).  Each
+    genome is then swept for its positions and joined right behind its count sweep, inside the stage gap_copies -- one count sweep
+    per genome serves both files --, and the stage gap_copy_sites makes the table."""
     prefix = prefix or f"ntSynt.k{k}.w{w}"
     if mx_tsvs is not None and len(mx_tsvs) != len(fastas):
         raise ValueError("one minimizer TSV per FASTA file")
@@ -555,6 +558,13 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
             raise ValueError("gap_copies = rate, at least 1")
         if gap_links is not None and int(gap_links[0]) != int(gap_copies):
             raise ValueError("gap_copies and gap_links share one sampling: the same rate for both")
+    if gap_copy_sites is not None:
+        if gap_copies is None:
+            raise ValueError("gap_copy_sites needs gap_copies = rate")
+        if int(gap_copy_sites[0]) < 1 or int(gap_copy_sites[1]) < 0 or int(gap_copy_sites[2]) < 1:
+            raise ValueError("gap_copy_sites = (cap, step, min_hits): cap and min_hits at least 1, step at least 0")
+        if len(fastas) > 64:
+            raise ValueError("gap_copy_sites takes at most 64 genomes (the join takes 64 lists)")
     if gaps and (world > 1 or (mx_tsvs is not None and initial_only)):
         raise ValueError("gaps needs every genome resident on one GPU (one rank, genomes loaded)")
     if gaps and not isinstance(backend, GpuBackend):
@@ -1096,13 +1106,27 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
             c_rate = int(gap_copies)
             if sampling is None:
                 sampling = gaps_.sample_gaps(by_name, bf, k, gap_rows, c_rate)
-            c_rows, n_set, absent, n_sampled = gaps_.copies(backend.ctx, by_name, k, gap_rows, sampling[0], sampling[1], c_rate)
+            counted = None              # with the copy sites: each genome's positions and join right behind its count sweep
+            if gap_copy_sites is not None:
+                s_cap, s_step, s_min = (int(x) for x in gap_copy_sites)
+                counted = gaps_.count_genomes(backend.ctx, by_name, k, sampling[0], c_rate, sites=(s_cap, s_step, s_min))
+            c_rows, n_set, absent, n_sampled = gaps_.copies(backend.ctx, by_name, k, gap_rows, sampling[0], sampling[1], c_rate, counted=counted)
             text = gaps_.copies_table(c_rows, k, c_rate, n_bits, n_set, absent, n_sampled)
             with open(f"{prefix}.gap_copies.tsv", "w", encoding="utf-8") as fh:
                 fh.write(text)
             eng.outputs[f"{prefix}.gap_copies.tsv"] = text
             st.stop()
             st.mark("gap_copies_done")
+            if gap_copy_sites is not None:
+                st.start("gap_copy_sites")
+                s_rows, n_set, over_cap, of_total = gaps_.copy_sites(backend.ctx, by_name, k, gap_rows, table_rows, sampling[0], sampling[1], c_rate,
+                                                                     s_cap, s_step, s_min, counted=counted)
+                text = gaps_.copy_sites_table(s_rows, k, c_rate, s_cap, s_step, s_min, n_bits, n_set, over_cap, of_total)
+                with open(f"{prefix}.gap_copy_sites.tsv", "w", encoding="utf-8") as fh:
+                    fh.write(text)
+                eng.outputs[f"{prefix}.gap_copy_sites.tsv"] = text
+                st.stop()
+                st.mark("gap_copy_sites_done")
     memory = st.memory()
     if benchmark and rank == 0:
         st.write(f"{prefix}.stage_times.tsv", memory)

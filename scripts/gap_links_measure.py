@@ -6,9 +6,15 @@ launches of nts_bf_sample_intervals over the same intervals in the same process 
 docs/design/04_12_gap_copies.md: the counting sweep (nts_hset_count_intervals, timer hcount_sweep) over the whole genome against the same
 set, beside k_hset_sample<false> (timer hset_sample_count) on the same tiles in the same process; nts_hcount_add of as many values as the
 sweep had hits; the clear and the read-back of the set's counts; and the same sweep of an assembly-like genome (satellite arrays: many
-adds to one address) beside that of the uniform one, each against the hashes of a tenth of its own rate-16 sample.
+adds to one address) beside that of the uniform one, each against the hashes of a tenth of its own rate-16 sample.  With --sites, the
+measurement behind docs/design/04_13_gap_copy_sites.md: after one count sweep of the same tiles, the two launches of
+nts_hset_sample_intervals_capped (timers hcount_sample_count / hcount_sample_write) at cap 16 and at cap 2^32 - 1 beside
+k_hset_sample<false / true> on the same tiles in the same process -- the difference at cap 2^32 - 1 is the price of the dependent 4-byte
+load per member hit, the difference between the two caps the stores saved --; and one nts_iv_sites call of three genomes' lists (the
+rate-16 samples of a tenth of each genome's intervals) against the first genome's cap-16 occurrences, its three timers beside
+nts_iv_links' on the same lists.
 
-    python scripts/gap_links_measure.py [--bp 3000000000] [--calls 6] [--out FILE.json] [--hset | --hcount]
+    python scripts/gap_links_measure.py [--bp 3000000000] [--calls 6] [--out FILE.json] [--hset | --hcount | --sites]
 
 A 3 Gbp synthetic genome (24 contigs) cut into 10^4 tiling intervals, the common filter of the three-genome 1 % family.  The launches
 are timed with device events (nts_timing), the whole call with the host clock around it.  Rate 1 writes a record for every k-mer the
@@ -166,6 +172,50 @@ def measure_hcount(ctx, g, bf, iv, tenth, k, calls, out, bp):
     ga.free()
 
 
+def measure_sites(ctx, g, bf, iv, tenth, k, calls, out, synth, n_intervals, min_hits):
+    "the capped sweep beside the set sweep after one count sweep of the same tiles; one nts_iv_sites call beside nts_iv_links on the same lists"
+    rec10, _ = g.bf_sample_intervals(bf, tenth, k, 16)
+    members = np.unique(rec10["h0"])
+    hset = HashSet(ctx, members)
+    counts = HashCounts(ctx, hset)
+    out["set_hashes"] = int(members.size)
+    out["count_hits"] = int(g.hset_count_intervals(hset, counts, iv, k, 16).sum())      # the one count sweep, of the same tiles
+    set_timers, cap_timers = ["hset_sample_count", "hset_sample_write"], ["hcount_sample_count", "hcount_sample_write"]
+    plain, _ = g.hset_sample_intervals(hset, iv, k, 16)         # warm-up, and the record count
+    out["hset_sample"] = dict(timed(ctx, set_timers, lambda: g.hset_sample_intervals(hset, iv, k, 16), calls), records=int(plain.size))
+    both = {"hset_sample": sum(out["hset_sample"][t]["median_ms"] for t in set_timers)}
+    occurrences = None
+    for name, cap in (("cap_16", 16), ("cap_max", (1 << 32) - 1)):
+        rec, _ = g.hset_sample_intervals_capped(hset, counts, cap, iv, k, 16)
+        out[name] = dict(timed(ctx, cap_timers, lambda cap=cap: g.hset_sample_intervals_capped(hset, counts, cap, iv, k, 16), calls), cap=cap, records=int(rec.size))
+        assert all(out[name][t]["timed_launches_per_call"] == [1] for t in cap_timers), out
+        both[name] = sum(out[name][t]["median_ms"] for t in cap_timers)
+        if cap == 16:
+            occurrences = rec
+        else:
+            assert np.array_equal(rec, plain)                   # the largest cap after a count sweep of the same tiles: the uncapped records
+    del plain, rec
+    both.update(dependent_count_load_ms=both["cap_max"] - both["hset_sample"], stores_saved_ms=both["cap_max"] - both["cap_16"])
+    out["both_launches_ms"] = both
+    counts.free()
+    hset.free()
+    g.free()
+    lists = [rec10]
+    for j in (1, 2):
+        other = synth(j)
+        lists.append(other.bf_sample_intervals(bf, tiling(other, n_intervals)[:tenth.shape[0]], k, 16)[0])
+        other.free()
+    ctx.profile(1)
+    links = ctx.iv_links(lists, min_hits)
+    out["iv_links"] = dict(timed(ctx, ["iv_links_join", "iv_links_pairs", "iv_links_select"], lambda: ctx.iv_links(lists, min_hits), max(3, calls // 2)),
+                           records=[int(x.size) for x in lists], links=int(links.size))
+    sites = ctx.iv_sites(lists, occurrences, 1000, min_hits)
+    out["iv_sites"] = dict(timed(ctx, ["iv_sites_join", "iv_sites_pairs", "iv_sites_select"], lambda: ctx.iv_sites(lists, occurrences, 1000, min_hits),
+                                 max(3, calls // 2)), records=[int(x.size) for x in lists], target_records=int(occurrences.size), sites=int(sites.size),
+                           pairs_in_kept_sites=int(sites["hits"].sum()) if sites.size else 0)
+    bf.free()
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--bp", type=int, default=3_000_000_000)
@@ -176,6 +226,7 @@ def main():
     p.add_argument("--no-join", action="store_true", help="the sampling launches only")
     p.add_argument("--hset", action="store_true", help="the set sweep of gap block links beside the filter sweep, and nothing else")
     p.add_argument("--hcount", action="store_true", help="the counting sweep of gap copies beside the set sweep's count launch, and nothing else")
+    p.add_argument("--sites", action="store_true", help="the capped sweep of gap copy sites beside the set sweep, the site join beside the link join, and nothing else")
     p.add_argument("--out")
     args = p.parse_args()
     k = args.k
@@ -195,6 +246,16 @@ def main():
     ctx.profile(2)
     kmers, hits = g.bf_count_intervals(bf, iv, k)             # warm-up, and the figures themselves
     out["intervals"], out["kmers"], out["held"] = int(iv.shape[0]), int(kmers.sum()), int(hits.sum())
+    if args.sites:
+        measure_sites(ctx, g, bf, iv, tenth, k, args.calls, out, synth, args.intervals, args.min_anchors)     # (frees the genome and the filter)
+        ctx.profile(False)
+        text = json.dumps(out, indent=1)
+        print(text)
+        if args.out:
+            with open(args.out, "w", encoding="utf-8") as fh:
+                fh.write(text + "\n")
+        ctx.close()
+        return
     if args.hcount:
         measure_hcount(ctx, g, bf, iv, tenth, k, args.calls, out, args.bp)     # (frees the genome and the filter: it loads another pair)
         ctx.profile(False)
