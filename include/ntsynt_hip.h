@@ -558,6 +558,31 @@ int nts_hset_sample_intervals_capped(nts_ctx* ctx, const nts_genome* g, uint32_t
 int nts_iv_sites(nts_ctx* ctx, uint32_t n_lists, const nts_sample* const* lists, const uint64_t* n, const nts_sample* target, uint64_t n_target,
                  uint32_t step, uint32_t min_hits, nts_iv_site** out, uint64_t* n_out);
 
+/* ---- the tandem arrays in what the blocks leave out: gap periods ---------------------------------------
+ * nts_sample_intervals: nts_bf_sample_intervals without the filter: a k-mer of interval i is sampled when it is valid, lies wholly
+ *   inside the interval and h0 <= UINT64_MAX / rate -- nothing is probed, so sequence that one genome alone has is sampled like any
+ *   other (rate 1: every k-mer).  The same records in the same order (interval order, then k-mer order), the same clipping,
+ *   NTS_EINVAL (rate = 0 included) and NTS_ERANGE, two launches per 2^23 tiles (timers "iv_sample_count", "iv_sample_write"), no
+ *   atomic, deterministic; *out released with nts_free().  csrc/nts_iv_sample.inc.
+ * nts_iv_periods: recs = n records of ONE list exactly as a sampler returns them (iv does not decrease, off rises strictly within
+ *   an iv; checked on the host in one pass: NTS_EINVAL otherwise and for iv >= n_iv).  Within interval i, take the records with
+ *   equal h0 in order of off: every one but the first has the lag d = off - its predecessor's off (>= 1); hashes are never paired
+ *   across intervals.  out[i] (a host array of n_iv entries, all written): recurring = the records with a lag; period = the lag
+ *   held by the most of them, the smallest on a tie; period_hits = how many hold it; first_off = the smallest off - period and
+ *   last_off = the largest off over the records whose lag is the period.  All five 0 for an interval without a record or without a
+ *   recurrence; n = 0 zeroes out and launches nothing.  Sampling is by hash value, so a k-mer that recurs is sampled at every
+ *   recurrence or at none: the lags are exact at any rate.  Three radix sorts, a run-length encoding and two reductions by key on
+ *   the context's stream and in its workspace, no atomic, no launch per interval, no floating point: the same input gives the same
+ *   bytes (timers "iv_periods_sort", "iv_periods_mode", "iv_periods_extent").  NTS_ERANGE for 2^32 records or intervals or more.
+ *   csrc/nts_iv_periods.inc; ntsynt_amd/gaps.py periods, `ntSynt --gap-periods`, `bin/ntsynt_gaps --periods-out`. */
+typedef struct
+{
+  uint32_t recurring, period, period_hits, first_off, last_off;
+} nts_iv_period;
+int nts_sample_intervals(nts_ctx* ctx, const nts_genome* g, uint32_t k, uint64_t rate, const nts_interval* iv, uint64_t n_iv, uint64_t* n_sampled,
+                         nts_sample** out, uint64_t* n_out);
+int nts_iv_periods(nts_ctx* ctx, const nts_sample* recs, uint64_t n, uint64_t n_iv, nts_iv_period* out);
+
 /* ---- C1-C5: minimizer graph -> collinear chains -----------------------------------------------------
  * replaces ntjoin_utils.read_minimizers' duplicate removal, filter_minimizers and build_graph
  * (call sites bin/ntsynt_synteny.py:607-612, 483, 539) and the path walk of Ntjoin.find_paths

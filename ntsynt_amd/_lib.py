@@ -40,6 +40,11 @@ class IvSite(ctypes.Structure):
     _fields_ = [(n, u32) for n in ("list_q", "iv_q", "rec_t", "hits", "fwd", "rev", "min_off_q", "max_off_q", "first_t", "last_t")]
 
 
+class IvPeriod(ctypes.Structure):
+    "nts_iv_period: the dominant lag of one interval's sampled records (nts_iv_periods)"
+    _fields_ = [(n, u32) for n in ("recurring", "period", "period_hits", "first_off", "last_off")]
+
+
 class MxList(ctypes.Structure):
     _fields_ = [("h1", c_vp), ("rec", c_vp), ("pos", c_vp), ("keep", c_vp), ("list_id", c_vp), ("n", u64)]
 
@@ -189,6 +194,8 @@ SYMBOLS = [
     ("nts_hset_sample_intervals_capped", ctypes.c_int, [c_vp, c_vp, u32, c_vp, c_vp, u32, u64, ctypes.POINTER(Interval), u64, c_vp, ctypes.POINTER(c_vp),
                                                         c_u64p]),
     ("nts_iv_sites", ctypes.c_int, [c_vp, u32, ctypes.POINTER(c_vp), c_u64p, c_vp, u64, u32, u32, ctypes.POINTER(c_vp), c_u64p]),
+    ("nts_sample_intervals", ctypes.c_int, [c_vp, c_vp, u32, u64, ctypes.POINTER(Interval), u64, c_vp, ctypes.POINTER(c_vp), c_u64p]),
+    ("nts_iv_periods", ctypes.c_int, [c_vp, c_vp, u64, u64, c_vp]),
     ("nts_genome_valid_bases", ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(Interval), u64, c_vp]),
     ("nts_minhash_pairs", ctypes.c_int, [c_vp, u32, c_vp, c_vp, u64, c_vp, c_vp, u64, c_vp, c_vp]),
     ("nts_graph_build", ctypes.c_int, [c_vp, u32, ctypes.POINTER(MxList), ctypes.POINTER(Graph)]),

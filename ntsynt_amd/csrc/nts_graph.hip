@@ -839,6 +839,7 @@ extern "C" int nts_graph_build(nts_ctx* ctx, uint32_t n_asm, const nts_mxlist* l
 namespace {
 #include "nts_iv_links.inc"
 #include "nts_iv_sites.inc"
+#include "nts_iv_periods.inc"
 } // namespace
 
 extern "C" int nts_iv_links(nts_ctx* ctx, uint32_t n_lists, const nts_sample* const* lists, const uint64_t* n, uint32_t min_anchors, nts_iv_link** out,
@@ -865,6 +866,13 @@ extern "C" int nts_iv_sites(nts_ctx* ctx, uint32_t n_lists, const nts_sample* co
   *n_out = 0;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   return iv_sites_run(ctx, n_lists, lists, n, target, n_target, step, min_hits, out, n_out);
+}
+
+extern "C" int nts_iv_periods(nts_ctx* ctx, const nts_sample* recs, uint64_t n, uint64_t n_iv, nts_iv_period* out)
+{
+  if (!ctx || (n && !recs) || (n_iv && !out)) return fail(ctx, NTS_EINVAL, "nts_iv_periods: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return iv_periods_run(ctx, recs, n, n_iv, out);
 }
 
 extern "C" int nts_graph_budget(nts_ctx* ctx, uint64_t bytes)

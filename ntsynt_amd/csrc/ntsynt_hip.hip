@@ -1598,6 +1598,7 @@ int launch_hash(nts_ctx* ctx, const char* name, const nts_genome* g, const Genom
 #include "nts_bf_sample.inc"
 #include "nts_hset.inc"
 #include "nts_hcount.inc"
+#include "nts_iv_sample.inc"
 
 // acc &= the filter of genome g the literal way, for a running filter that holds few bits (defined behind the sketch's host code,
 // whose accept kernels and summary it uses): 0 = done, 1 = does not apply or did not fit (acc is untouched), < 0 = error
@@ -2748,6 +2749,14 @@ int nts_bf_sample_intervals(nts_ctx* ctx, const nts_genome* g, uint32_t k, const
     return fail(ctx, NTS_EINVAL, "nts_bf_sample_intervals: bad arguments");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   return bf_sample_intervals_run(ctx, g, k, bf, rate, iv, n_iv, n_sampled, out, n_out);
+}
+
+int nts_sample_intervals(nts_ctx* ctx, const nts_genome* g, uint32_t k, uint64_t rate, const nts_interval* iv, uint64_t n_iv, uint64_t* n_sampled,
+                         nts_sample** out, uint64_t* n_out)
+{
+  if (!ctx || !g || k == 0 || rate == 0 || !out || !n_out || (n_iv && (!iv || !n_sampled))) return fail(ctx, NTS_EINVAL, "nts_sample_intervals: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return iv_sample_intervals_run(ctx, g, k, rate, iv, n_iv, n_sampled, out, n_out);
 }
 
 int nts_hset_build(nts_ctx* ctx, const uint64_t* h, uint64_t n, nts_hset** out)

@@ -46,6 +46,8 @@ LINK_DTYPE = np.dtype([(n, "<u4") for n in ("list_a", "iv_a", "list_b", "iv_b", 
                                             "max_off_b")])
 # nts_iv_site: what Context.iv_sites returns
 SITE_DTYPE = np.dtype([(n, "<u4") for n in ("list_q", "iv_q", "rec_t", "hits", "fwd", "rev", "min_off_q", "max_off_q", "first_t", "last_t")])
+# nts_iv_period: what Context.iv_periods returns, one per interval
+PERIOD_DTYPE = np.dtype([(n, "<u4") for n in ("recurring", "period", "period_hits", "first_off", "last_off")])
 
 
 class Context:
@@ -133,6 +135,20 @@ class Context:
         if n.value:
             ctypes.memmove(out.ctypes.data, p.value, out.nbytes)
         self.lib.nts_free(p)
+        return out
+
+    def iv_periods(self, records, n_iv):
+        """per interval the dominant lag between the recurrences of a hash among its sampled records (nts_iv_periods).  records: ONE
+        SAMPLE_DTYPE array as a sampler returns it (Genome.sample_intervals: iv does not decrease, off rises strictly within an iv);
+        n_iv: the intervals of that call.  Returns a PERIOD_DTYPE array of n_iv entries: recurring = the records that repeat the hash of
+        an earlier record of their interval, period = the distance to that record held by the most of them (the smallest on a tie),
+        period_hits = how many hold it, first_off / last_off = the smallest off - period / the largest off among those; zeros where
+        nothing recurs.  Exact and deterministic."""
+        rec = np.ascontiguousarray(records, dtype=SAMPLE_DTYPE)
+        assert SAMPLE_DTYPE.itemsize == ctypes.sizeof(_lib.Sample) and PERIOD_DTYPE.itemsize == ctypes.sizeof(_lib.IvPeriod)
+        out = np.zeros(int(n_iv), dtype=PERIOD_DTYPE)
+        self.check(self.lib.nts_iv_periods(self.h, rec.ctypes.data if rec.size else None, rec.size, int(n_iv), out.ctypes.data if out.size else None),
+                   "nts_iv_periods")
         return out
 
     def timing(self, name):
@@ -510,6 +526,21 @@ class Genome:
         p, m = c_vp(), u64()
         self.ctx.check(self.ctx.lib.nts_bf_sample_intervals(self.ctx.h, self.h, int(k), bf.h, int(rate), ctypes.cast(iv.ctypes.data, ctypes.POINTER(Interval)),
                                                             n, counts.ctypes.data, ctypes.byref(p), ctypes.byref(m)), "nts_bf_sample_intervals")
+        out = np.empty(m.value, dtype=SAMPLE_DTYPE)
+        if m.value:
+            ctypes.memmove(out.ctypes.data, p.value, out.nbytes)
+        self.ctx.lib.nts_free(p)
+        return out, counts
+
+    def sample_intervals(self, intervals, k, rate):
+        """bf_sample_intervals without a filter (nts_sample_intervals): every valid k-mer wholly inside an interval with
+        h0 <= (2^64 - 1) // rate, whatever holds it.  The same (records, counts), exact and deterministic."""
+        iv = self._interval_array(intervals)
+        n = iv.size
+        counts = np.zeros(n, dtype=np.uint64)
+        p, m = c_vp(), u64()
+        self.ctx.check(self.ctx.lib.nts_sample_intervals(self.ctx.h, self.h, int(k), int(rate), ctypes.cast(iv.ctypes.data, ctypes.POINTER(Interval)), n,
+                                                         counts.ctypes.data, ctypes.byref(p), ctypes.byref(m)), "nts_sample_intervals")
         out = np.empty(m.value, dtype=SAMPLE_DTYPE)
         if m.value:
             ctypes.memmove(out.ctypes.data, p.value, out.nbytes)

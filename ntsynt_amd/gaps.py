@@ -25,7 +25,12 @@ docs/design/04_12_gap_copies.md.
 WHERE each genome holds those copies (`ntSynt --gap-copy-sites`, `bin/ntsynt_gaps --copy-sites-out`): behind a genome's count sweep the
 same genome is swept once more and the positions of the members whose count lies in 1..cap are written
 (nts_hset_sample_intervals_capped), then joined against the gaps' records with multiplicity allowed on both sides and grouped into
-sites (copy_sites: nts_iv_sites, one call per target genome).  docs/design/04_13_gap_copy_sites.md."""
+sites (copy_sites: nts_iv_sites, one call per target genome).  docs/design/04_13_gap_copy_sites.md.
+
+Which gaps are tandem arrays (`ntSynt --gap-periods`, `bin/ntsynt_gaps --periods-out`): every genome's gaps are sampled once more
+WITHOUT any filter (sample_all: nts_sample_intervals -- an array that one genome alone has is in no common filter), and per genome one
+call finds, for every gap, the distance that most often separates two consecutive copies of a sampled k-mer (periods: nts_iv_periods):
+the period, how many records hold it, and the stretch they cover.  docs/design/04_14_gap_periods.md."""
 import os
 from collections import namedtuple
 
@@ -42,6 +47,8 @@ COPY_COLUMNS = ("genome", "contig", "start", "end", "left_block", "right_block",
                 "copies_own_median", "copies_own_max", "copies_any_median", "class")
 SITE_COLUMNS = ("genome", "contig", "start", "end", "left_block", "right_block", "class", "target_genome", "target_contig", "from_t", "to_t", "blocks",
                 "hits", "orientation", "from", "to", "sampled", "usable", "placement")
+PERIOD_COLUMNS = ("genome", "contig", "start", "end", "length", "kind", "sampled", "recurring", "period", "period_hits", "from", "to", "copies",
+                  "covered_fraction", "class")
 SITES_CAP, SITES_STEP = 16, 1000                                # --gap-sites-cap / --gap-sites-step
 MAX_BLOCK_LINK_GENOMES = 32                                     # nts_iv_links takes at most 64 lists: every genome's gaps and its blocks
 
@@ -543,6 +550,74 @@ def copy_sites_table(rows, k, rate, cap, step, min_hits, bits, n_set, over_cap, 
     return "\n".join(lines) + "\n"
 
 
+def sample_all(genomes_by_name, k, gap_rows, rate=LINKS_RATE):
+    """(lists, sampled): sample_gaps() without a filter -- per genome, ascending by name, the records and the per-gap counts of one
+    nts_sample_intervals call over its gaps only: every valid k-mer wholly inside a gap with h0 <= (2^64 - 1) // rate, whatever holds
+    it.  A k-mer that recurs is sampled at every recurrence or at none."""
+    if rate < 1:
+        raise ValueError("sample_all: rate must be at least 1")
+    lists, sampled = [], []
+
+    def sweep(name, g):
+        rec, counts = g.sample_intervals(_interval_rows(g, [r for r in gap_rows if r["genome"] == name]), k, rate)
+        lists.append(rec)
+        sampled.append(counts)
+    _each_genome(genomes_by_name, sorted(genomes_by_name), sweep)
+    return lists, sampled
+
+
+def period_row(gap, k, sampled, result, min_hits):
+    """a gap's line of <prefix>.gap_periods.tsv: gap = its row (genome, contig, start, end, kind); sampled = its unfiltered records;
+    result = its (recurring, period, period_hits, first_off, last_off) of nts_iv_periods.  from / to = the stretch the records at the
+    period cover, one unit before the first of them to the end of the last; copies = covered / period in tenths, rounded down;
+    class: `.` below min_hits records at the period (period, from, to, copies and covered_fraction are then None), else `tandem` when
+    the stretch is more than half of the gap, else `partial`.  Integer arithmetic throughout."""
+    recurring, period, hits, first_off, last_off = (int(x) for x in result)
+    length = gap["end"] - gap["start"]
+    row = {c: gap[c] for c in ("genome", "contig", "start", "end", "kind")}
+    row.update({"length": length, "sampled": int(sampled), "recurring": recurring, "period_hits": hits})
+    if hits < int(min_hits) or period < 1:
+        row.update({"period": None, "from": None, "to": None, "copies": None, "covered_fraction": None, "class": "."})
+        return row
+    lo, hi = gap["start"] + first_off, gap["start"] + last_off + int(k)
+    covered = hi - lo
+    tenths = (10 * covered) // period
+    row.update({"period": period, "from": lo, "to": hi, "copies": f"{tenths // 10}.{tenths % 10}", "covered_fraction": _ratio(covered / length),
+                "class": "tandem" if 2 * covered > length else "partial"})
+    return row
+
+
+def periods(ctx, genomes_by_name, k, gap_rows, rate=LINKS_RATE, min_hits=LINKS_MIN):
+    """which gaps are tandem arrays: gap_rows are report()'s (every genome's, in its order); genomes_by_name as for report().  Per
+    genome, ascending by name, one nts_sample_intervals call over its gaps (sample_all: a genome given as a loader is loaded once and
+    freed after its sweep), then one nts_iv_periods call on ctx over that genome's records.  Returns one dict per gap with
+    PERIOD_COLUMNS' keys (period_row), in gap_rows' order.  2^32 records of one genome or more: the call refuses and this raises with
+    its message (raise the rate)."""
+    if rate < 1 or min_hits < 1:
+        raise ValueError("periods: rate and min_hits must be at least 1")
+    names = sorted(genomes_by_name)
+    lists, sampled = sample_all(genomes_by_name, k, gap_rows, rate)
+    out = []
+    for li, name in enumerate(names):
+        mine = [r for r in gap_rows if r["genome"] == name]
+        if len(sampled[li]) != len(mine):
+            raise ValueError(f"periods: the sampling of {name} is not that of these gaps")
+        found = ctx.iv_periods(lists[li], len(mine))
+        for q, gap in enumerate(mine):
+            out.append(period_row(gap, k, int(sampled[li][q]), tuple(int(found[q][c]) for c in ("recurring", "period", "period_hits", "first_off", "last_off")),
+                                  min_hits))
+    return out
+
+
+def periods_table(rows, k, rate, min_hits):
+    "<prefix>.gap_periods.tsv: a header, one line per gap (periods()' rows: the gaps of <prefix>.gaps.tsv, in its order; `.` where a gap has no period), then `# k K, rate R, min_hits M`"
+    lines = ["\t".join(PERIOD_COLUMNS)]
+    for r in rows:
+        lines.append("\t".join("." if r[c] is None else str(r[c]) for c in PERIOD_COLUMNS))
+    lines.append(f"# k {int(k)}, rate {int(rate)}, min_hits {int(min_hits)}")
+    return "\n".join(lines) + "\n"
+
+
 def build_parser():
     "bin/ntsynt_gaps' options"
     import argparse
@@ -560,6 +635,8 @@ def build_parser():
                    "(unique / repeat / mixed) to this file (<prefix>.gap_copies.tsv); uses --links-rate")
     p.add_argument("--copy-sites-out", help="also write where each genome, the gap's own included, holds each gap's sampled k-mers close together "
                    "(the copies of a repeat gap) to this file (<prefix>.gap_copy_sites.tsv); uses --links-rate and --links-min")
+    p.add_argument("--periods-out", help="also write, per gap, the period, the copy count and the extent of a tandem array in it, from an unfiltered "
+                   "sample of its k-mers, to this file (<prefix>.gap_periods.tsv); uses --links-rate and --links-min")
     p.add_argument("--sites-cap", help=f"use a k-mer against a genome that holds it at most this many times [{SITES_CAP}]", type=int, default=SITES_CAP)
     p.add_argument("--sites-step", help=f"two hits of a site lie at most this many bases apart [{SITES_STEP}]", type=int, default=SITES_STEP)
     p.add_argument("--links-rate", help=f"sample one in this many of the gap k-mers the filter holds [{LINKS_RATE}]", type=int, default=LINKS_RATE)
@@ -620,6 +697,10 @@ def main(argv=None):
                 c_rows, n_set, absent, n_sampled = copies(ctx, loaders, k, gap_rows, sampling[0], sampling[1], args.links_rate, counted=counted)
                 with open(args.copies_out, "w", encoding="utf-8") as fh:
                     fh.write(copies_table(c_rows, k, args.links_rate, n_bits, n_set, absent, n_sampled))
+            if args.periods_out:
+                p_rows = periods(ctx, loaders, k, gap_rows, args.links_rate, args.links_min)
+                with open(args.periods_out, "w", encoding="utf-8") as fh:
+                    fh.write(periods_table(p_rows, k, args.links_rate, args.links_min))
         finally:
             bf.free()
     finally:

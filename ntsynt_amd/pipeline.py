@@ -496,7 +496,8 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         block_size=500, common=True, simplify=True, device=0, write_mx_tsv=True, mx_with_seq=True,
         benchmark=False, log=print, ctx=None, backend=None, bf_rounding="up", bf_signature=BF_SIGNATURE, dev=False, interarrivals=False, repeat=False,
         mx_tsvs=None, common_file=None, m=90, n=0, initial_only=False, write_fai=True, engine="device", refine_repeat_file=None, screen_repeat_file=None,
-        graph_budget=None, assess=None, gaps=False, gap_links=None, gap_block_links=False, gap_copies=None, gap_copy_sites=None):
+        graph_budget=None, assess=None, gaps=False, gap_links=None, gap_block_links=False, gap_copies=None, gap_copy_sites=None,
+        gap_periods=None):
     """FASTA paths -> engine (outputs in .outputs and in the CWD).  Mirrors oracle.synteny_oracle.run_pipeline's
     signature so the parity tests read alike.  Under torch.distributed (WORLD_SIZE > 1, process group already
     initialised by the caller) genomes are sharded over the ranks.
@@ -516,7 +517,10 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
     once for it and the links, so with gap_links its rate is theirs.  gap_copy_sites = (cap, step, min_hits): needs gap_copies, whose
     rate it shares; after that file, <prefix>.gap_copy_sites.tsv (gaps.copy_sites: where each genome holds the copies of a gap).  Each
     genome is then swept for its positions and joined right behind its count sweep, inside the stage gap_copies -- one count sweep
-    per genome serves both files --, and the stage gap_copy_sites makes the table."""
+    per genome serves both files --, and the stage gap_copy_sites makes the table.  gap_periods = (rate, min_hits):
+    implies gaps; after the other gap files, <prefix>.gap_periods.tsv (gaps.periods: the period, the copy count and the extent of a
+    tandem array in each gap, from an unfiltered sample of its own: it shares nothing with the sampling above, so the rate is its
+    own)."""
     prefix = prefix or f"ntSynt.k{k}.w{w}"
     if mx_tsvs is not None and len(mx_tsvs) != len(fastas):
         raise ValueError("one minimizer TSV per FASTA file")
@@ -565,6 +569,10 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
             raise ValueError("gap_copy_sites = (cap, step, min_hits): cap and min_hits at least 1, step at least 0")
         if len(fastas) > 64:
             raise ValueError("gap_copy_sites takes at most 64 genomes (the join takes 64 lists)")
+    if gap_periods is not None:
+        gaps = True                     # the periods are found in the gaps the report cuts
+        if int(gap_periods[0]) < 1 or int(gap_periods[1]) < 1:
+            raise ValueError("gap_periods = (rate, min_hits), both at least 1")
     if gaps and (world > 1 or (mx_tsvs is not None and initial_only)):
         raise ValueError("gaps needs every genome resident on one GPU (one rank, genomes loaded)")
     if gaps and not isinstance(backend, GpuBackend):
@@ -1127,6 +1135,15 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
                 eng.outputs[f"{prefix}.gap_copy_sites.tsv"] = text
                 st.stop()
                 st.mark("gap_copy_sites_done")
+        if gap_periods is not None:
+            st.start("gap_periods")
+            p_rate, p_min = int(gap_periods[0]), int(gap_periods[1])
+            text = gaps_.periods_table(gaps_.periods(backend.ctx, by_name, k, gap_rows, p_rate, p_min), k, p_rate, p_min)
+            with open(f"{prefix}.gap_periods.tsv", "w", encoding="utf-8") as fh:
+                fh.write(text)
+            eng.outputs[f"{prefix}.gap_periods.tsv"] = text
+            st.stop()
+            st.mark("gap_periods_done")
     memory = st.memory()
     if benchmark and rank == 0:
         st.write(f"{prefix}.stage_times.tsv", memory)

@@ -12,9 +12,12 @@ nts_hset_sample_intervals_capped (timers hcount_sample_count / hcount_sample_wri
 k_hset_sample<false / true> on the same tiles in the same process -- the difference at cap 2^32 - 1 is the price of the dependent 4-byte
 load per member hit, the difference between the two caps the stores saved --; and one nts_iv_sites call of three genomes' lists (the
 rate-16 samples of a tenth of each genome's intervals) against the first genome's cap-16 occurrences, its three timers beside
-nts_iv_links' on the same lists.
+nts_iv_links' on the same lists.  With --periods, the measurement behind docs/design/04_14_gap_periods.md: the two launches of
+nts_sample_intervals (timers iv_sample_count / iv_sample_write) beside k_bf_sample<false / true> on the same tiles in the same process
+-- the sampler that probes nothing does strictly less per k-mer --, and one nts_iv_periods call on the records of a tenth of the
+intervals, its three timers (--sites times nts_iv_sites on lists of that size from the same input).
 
-    python scripts/gap_links_measure.py [--bp 3000000000] [--calls 6] [--out FILE.json] [--hset | --hcount | --sites]
+    python scripts/gap_links_measure.py [--bp 3000000000] [--calls 6] [--out FILE.json] [--hset | --hcount | --sites | --periods]
 
 A 3 Gbp synthetic genome (24 contigs) cut into 10^4 tiling intervals, the common filter of the three-genome 1 % family.  The launches
 are timed with device events (nts_timing), the whole call with the host clock around it.  Rate 1 writes a record for every k-mer the
@@ -216,6 +219,31 @@ def measure_sites(ctx, g, bf, iv, tenth, k, calls, out, synth, n_intervals, min_
     bf.free()
 
 
+def measure_periods(ctx, g, bf, iv, tenth, k, calls, out):
+    "the sampler that probes nothing beside the filter sweep on the same tiles; one nts_iv_periods call on a tenth's records"
+    bf_timers, iv_timers = ["bf_sample_count", "bf_sample_write"], ["iv_sample_count", "iv_sample_write"]
+    rec, _ = g.bf_sample_intervals(bf, iv, k, 16)               # warm-up, and the record count
+    out["bf_sample"] = dict(timed(ctx, bf_timers, lambda: g.bf_sample_intervals(bf, iv, k, 16), calls), records=int(rec.size))
+    del rec
+    rec, _ = g.sample_intervals(iv, k, 16)
+    out["iv_sample"] = dict(timed(ctx, iv_timers, lambda: g.sample_intervals(iv, k, 16), calls), records=int(rec.size))
+    del rec
+    assert all(out["bf_sample"][t]["timed_launches_per_call"] == [1] for t in bf_timers), out
+    assert all(out["iv_sample"][t]["timed_launches_per_call"] == [1] for t in iv_timers), out
+    out["launch_by_launch"] = {}
+    for mine, theirs in zip(iv_timers, bf_timers):
+        a, b = out["iv_sample"][mine], out["bf_sample"][theirs]
+        out["launch_by_launch"][mine] = {"median_ms": a["median_ms"], "yardstick_median_ms": b["median_ms"], "difference_ms": a["median_ms"] - b["median_ms"],
+                                         "spread_ms": max(a["max_ms"] - a["min_ms"], b["max_ms"] - b["min_ms"])}
+    rec10, _ = g.sample_intervals(tenth, k, 16)
+    n_iv = int(tenth.shape[0])
+    ctx.profile(1)
+    found = ctx.iv_periods(rec10, n_iv)
+    out["iv_periods"] = dict(timed(ctx, ["iv_periods_sort", "iv_periods_mode", "iv_periods_extent"], lambda: ctx.iv_periods(rec10, n_iv), calls),
+                             records=int(rec10.size), intervals=n_iv, recurring=int(found["recurring"].sum()),
+                             intervals_with_4_hits=int((found["period_hits"] >= 4).sum()))
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--bp", type=int, default=3_000_000_000)
@@ -227,6 +255,7 @@ def main():
     p.add_argument("--hset", action="store_true", help="the set sweep of gap block links beside the filter sweep, and nothing else")
     p.add_argument("--hcount", action="store_true", help="the counting sweep of gap copies beside the set sweep's count launch, and nothing else")
     p.add_argument("--sites", action="store_true", help="the capped sweep of gap copy sites beside the set sweep, the site join beside the link join, and nothing else")
+    p.add_argument("--periods", action="store_true", help="the sampler without a filter of gap periods beside the filter sweep, one nts_iv_periods call, and nothing else")
     p.add_argument("--out")
     args = p.parse_args()
     k = args.k
@@ -246,6 +275,18 @@ def main():
     ctx.profile(2)
     kmers, hits = g.bf_count_intervals(bf, iv, k)             # warm-up, and the figures themselves
     out["intervals"], out["kmers"], out["held"] = int(iv.shape[0]), int(kmers.sum()), int(hits.sum())
+    if args.periods:
+        measure_periods(ctx, g, bf, iv, tenth, k, args.calls, out)
+        ctx.profile(False)
+        text = json.dumps(out, indent=1)
+        print(text)
+        if args.out:
+            with open(args.out, "w", encoding="utf-8") as fh:
+                fh.write(text + "\n")
+        g.free()
+        bf.free()
+        ctx.close()
+        return
     if args.sites:
         measure_sites(ctx, g, bf, iv, tenth, k, args.calls, out, synth, args.intervals, args.min_anchors)     # (frees the genome and the filter)
         ctx.profile(False)
