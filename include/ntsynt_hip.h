@@ -583,6 +583,42 @@ int nts_sample_intervals(nts_ctx* ctx, const nts_genome* g, uint32_t k, uint64_t
                          nts_sample** out, uint64_t* n_out);
 int nts_iv_periods(nts_ctx* ctx, const nts_sample* recs, uint64_t n, uint64_t n_iv, nts_iv_period* out);
 
+/* ---- the tandem arrays grouped into families and found genome-wide: gap families --------------------------
+ * Three passes, each linear in its records, all on the context's stream and in its workspace, no atomic, no launch per interval
+ * or array, no floating point: the same input gives the same bytes.  csrc/nts_iv_families.inc; ntsynt_amd/gaps.py families,
+ * `ntSynt --gap-families`, `bin/ntsynt_gaps --families-out / --family-sites-out`.
+ * nts_iv_period_hashes: recs = n records of ONE list exactly as a sampler returns them (the order and the NTS_EINVAL are
+ *   nts_iv_periods'); period[i] = interval i's period, 0 = skip the interval (a host array of n_iv entries).  *out = one record per
+ *   distinct (iv, h0) that has at least one record whose lag (nts_iv_periods) equals period[iv], off = how many such records there
+ *   are, sorted by (iv, h0); (NULL, 0) for none.  Released with nts_free().  Steps 1 - 3 of nts_iv_periods, a scan, a reduction by
+ *   key and a selection (timer "iv_phash").  NTS_ERANGE for 2^32 records or intervals or more.
+ * nts_iv_families: pairs = n pairs (h0, iv = an array's index; off is ignored, duplicates are allowed), NTS_EINVAL for
+ *   iv >= n_arrays.  Two arrays that hold one h0 are joined; family[a] (a host array of n_arrays entries, all written) = the
+ *   smallest array index of a's component, a itself for an array without a pair.  *hashes = the distinct h0 ascending,
+ *   (*hash_family)[j] = the component of (*hashes)[j] -- every hash belongs to exactly one --, *n_hashes of them; (NULL, NULL, 0)
+ *   without a pair.  Both released with nts_free().  Two radix sorts to (h0, iv) order, one lane per pair writes the edge to its
+ *   predecessor, a sort and a run-length encoding make the edges unique and another the hashes; the distinct edges -- at most n --
+ *   come to the host, where a union-find in which the smaller root wins gives the components (timer "iv_families_join").
+ *   NTS_ERANGE for 2^32 pairs or arrays or more.
+ * nts_iv_family_sites: occ = ONE genome's records of nts_hset_sample_intervals over whole records (iv = record, off = position; iv
+ *   does not decrease, off rises strictly within an iv: checked on the host, NTS_EINVAL otherwise); hashes must ascend strictly
+ *   (NTS_EINVAL), hash_family[j] = the family of hashes[j]; an occurrence whose h0 is not among them is dropped.  Within one family
+ *   the occurrences in (rec, off) order fall into sites: maximal runs within one record whose consecutive positions differ by at
+ *   most `step`; occurrences of other families in between break nothing.  *out = the sites with hits >= min_hits (>= 1: NTS_EINVAL
+ *   for 0) sorted by (family, rec, first), *n_out of them; first / last = the first and last position; (NULL, 0) for no site or an
+ *   empty input.  Released with nts_free().  A binary search per occurrence, ONE stable radix sort on the family, a scan, a
+ *   reduction by key and a selection (timers "iv_family_sites_label", "iv_family_sites_select").  NTS_ERANGE for 2^32 occurrences
+ *   or hashes or more. */
+typedef struct
+{
+  uint32_t family, rec, first, last, hits;
+} nts_iv_fsite;
+int nts_iv_period_hashes(nts_ctx* ctx, const nts_sample* recs, uint64_t n, uint64_t n_iv, const uint32_t* period, nts_sample** out, uint64_t* n_out);
+int nts_iv_families(nts_ctx* ctx, const nts_sample* pairs, uint64_t n, uint64_t n_arrays, uint32_t* family, uint64_t** hashes, uint32_t** hash_family,
+                    uint64_t* n_hashes);
+int nts_iv_family_sites(nts_ctx* ctx, const nts_sample* occ, uint64_t n_occ, const uint64_t* hashes, const uint32_t* hash_family, uint64_t n_hashes,
+                        uint32_t step, uint32_t min_hits, nts_iv_fsite** out, uint64_t* n_out);
+
 /* ---- C1-C5: minimizer graph -> collinear chains -----------------------------------------------------
  * replaces ntjoin_utils.read_minimizers' duplicate removal, filter_minimizers and build_graph
  * (call sites bin/ntsynt_synteny.py:607-612, 483, 539) and the path walk of Ntjoin.find_paths

@@ -45,6 +45,11 @@ class IvPeriod(ctypes.Structure):
     _fields_ = [(n, u32) for n in ("recurring", "period", "period_hits", "first_off", "last_off")]
 
 
+class IvFsite(ctypes.Structure):
+    "nts_iv_fsite: one site of a family of tandem arrays in one genome (nts_iv_family_sites)"
+    _fields_ = [(n, u32) for n in ("family", "rec", "first", "last", "hits")]
+
+
 class MxList(ctypes.Structure):
     _fields_ = [("h1", c_vp), ("rec", c_vp), ("pos", c_vp), ("keep", c_vp), ("list_id", c_vp), ("n", u64)]
 
@@ -196,6 +201,9 @@ SYMBOLS = [
     ("nts_iv_sites", ctypes.c_int, [c_vp, u32, ctypes.POINTER(c_vp), c_u64p, c_vp, u64, u32, u32, ctypes.POINTER(c_vp), c_u64p]),
     ("nts_sample_intervals", ctypes.c_int, [c_vp, c_vp, u32, u64, ctypes.POINTER(Interval), u64, c_vp, ctypes.POINTER(c_vp), c_u64p]),
     ("nts_iv_periods", ctypes.c_int, [c_vp, c_vp, u64, u64, c_vp]),
+    ("nts_iv_period_hashes", ctypes.c_int, [c_vp, c_vp, u64, u64, c_vp, ctypes.POINTER(c_vp), c_u64p]),
+    ("nts_iv_families", ctypes.c_int, [c_vp, c_vp, u64, u64, c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_u64p]),
+    ("nts_iv_family_sites", ctypes.c_int, [c_vp, c_vp, u64, c_vp, c_vp, u64, u32, u32, ctypes.POINTER(c_vp), c_u64p]),
     ("nts_genome_valid_bases", ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(Interval), u64, c_vp]),
     ("nts_minhash_pairs", ctypes.c_int, [c_vp, u32, c_vp, c_vp, u64, c_vp, c_vp, u64, c_vp, c_vp]),
     ("nts_graph_build", ctypes.c_int, [c_vp, u32, ctypes.POINTER(MxList), ctypes.POINTER(Graph)]),

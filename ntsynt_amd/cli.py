@@ -87,6 +87,9 @@ def build_parser():
     p.add_argument("--gap-periods", help="with --gaps (which it implies), write <prefix>.gap_periods.tsv: per gap, the period, the copy count and the extent\n"
                    "of a tandem array in it, from an unfiltered sample of its k-mers (shares --gap-links-rate and --gap-links-min)",
                    action="store_true")
+    p.add_argument("--gap-families", help="with --gap-periods (which it implies), write <prefix>.gap_families.tsv and <prefix>.gap_family_sites.tsv: which\n"
+                   "tandem arrays share the hashes that carry their period, and where each genome holds each such family, inside the gaps\n"
+                   "and inside the blocks (shares --gap-links-rate, --gap-links-min and --gap-sites-step)", action="store_true")
     p.add_argument("--gap-sites-cap", help="use a k-mer against a genome that holds it at most this many times [16]", type=int, default=16)
     p.add_argument("--gap-sites-step", help="two hits of a site lie at most this many bases apart [1000]", type=int, default=1000)
     p.add_argument("--gap-links-rate", help="sample one in this many of the gap k-mers the filter holds [16]", type=int, default=16)
@@ -154,7 +157,7 @@ def estimate_divergence(parser, args, say):
 
 
 def check_reports(parser, args):
-    "the switches of the reports behind the run (--assess, --gaps, --gap-links, --gap-block-links, --gap-copies, --gap-copy-sites, --gap-periods): what each implies and where each is refused"
+    "the switches of the reports behind the run (--assess, --gaps, --gap-links, --gap-block-links, --gap-copies, --gap-copy-sites, --gap-periods, --gap-families): what each implies and where each is refused"
     if args.assess:
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             parser.error("--assess works from the genomes resident on one GPU: run it on one rank, or assess the finished run with "
@@ -197,6 +200,18 @@ def check_reports(parser, args):
         if args.gap_links_rate < 1:
             parser.error("--gap-links-rate must be positive")
         args.gaps = True
+    if args.gap_families:
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            parser.error("--gap-families works from the genomes resident on one GPU: run it on one rank, or report on the finished run with "
+                         "ntsynt_gaps --tsv <prefix>.synteny_blocks.tsv --fastas ... --common <prefix>.common.bf --families-out <prefix>.gap_families.tsv "
+                         "--family-sites-out <prefix>.gap_family_sites.tsv")
+        if args.no_common:
+            parser.error("--gap-families reads the common Bloom filter: not with --no-common")
+        if args.gap_links_rate < 1 or args.gap_links_min < 1:
+            parser.error("--gap-links-rate and --gap-links-min must be positive")
+        if args.gap_sites_step < 0 or args.gap_sites_step > 0xFFFFFFFF:
+            parser.error("--gap-sites-step must not be negative (a 32-bit value)")
+        args.gap_periods = True
     if args.gap_periods:
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             parser.error("--gap-periods works from the genomes resident on one GPU: run it on one rank, or report on the finished run with "
@@ -248,7 +263,7 @@ def main(argv=None):
            ["indexlr x%d" % len(fastas), "ntsynt_synteny"] + (["assess"] if args.assess else []) + (["gaps"] if args.gaps else []) + \
            (["gap_links"] if args.gap_links else []) + (["gap_block_links"] if args.gap_block_links else []) + \
            (["gap_copies"] if args.gap_copies else []) + (["gap_copy_sites"] if args.gap_copy_sites else []) + \
-           (["gap_periods"] if args.gap_periods else [])
+           (["gap_periods"] if args.gap_periods else []) + (["gap_families"] if args.gap_families else [])
     if args.dry_run:
         say("Stages (GPU, in process):", " -> ".join(plan))
         return 0
@@ -303,7 +318,7 @@ def _run(pipeline, fastas, args, device, quiet):
     pipeline.run(fastas, k=args.k, w=args.w, fpr=args.fpr, prefix=args.prefix, w_rounds=args.w_rounds,
                  indel=args.indel, merge=args.merge, block_size=args.block_size, common=not args.no_common,
                  simplify=not args.no_simplify_graph, device=device, benchmark=args.benchmark,
-                 dev=args.dev, interarrivals=args.interarrivals, assess=(args.assess_k, args.assess_s) if args.assess else None, gaps=args.gaps, gap_links=(args.gap_links_rate, args.gap_links_min) if args.gap_links else None, gap_block_links=args.gap_block_links, gap_copies=args.gap_links_rate if args.gap_copies else None, gap_copy_sites=(args.gap_sites_cap, args.gap_sites_step, args.gap_links_min) if args.gap_copy_sites else None, gap_periods=(args.gap_links_rate, args.gap_links_min) if args.gap_periods else None, repeat=args.repeat, bf_rounding=args.bf_rounding, bf_signature=args.bf_signature or pipeline.BF_SIGNATURE,
+                 dev=args.dev, interarrivals=args.interarrivals, assess=(args.assess_k, args.assess_s) if args.assess else None, gaps=args.gaps, gap_links=(args.gap_links_rate, args.gap_links_min) if args.gap_links else None, gap_block_links=args.gap_block_links, gap_copies=args.gap_links_rate if args.gap_copies else None, gap_copy_sites=(args.gap_sites_cap, args.gap_sites_step, args.gap_links_min) if args.gap_copy_sites else None, gap_periods=(args.gap_links_rate, args.gap_links_min) if args.gap_periods else None, gap_families=args.gap_sites_step if args.gap_families else None, repeat=args.repeat, bf_rounding=args.bf_rounding, bf_signature=args.bf_signature or pipeline.BF_SIGNATURE,
                  log=print if (args.dev and int(os.environ.get("RANK", "0")) == 0) else quiet)
 
 

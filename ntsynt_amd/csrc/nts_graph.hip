@@ -840,6 +840,7 @@ namespace {
 #include "nts_iv_links.inc"
 #include "nts_iv_sites.inc"
 #include "nts_iv_periods.inc"
+#include "nts_iv_families.inc"
 } // namespace
 
 extern "C" int nts_iv_links(nts_ctx* ctx, uint32_t n_lists, const nts_sample* const* lists, const uint64_t* n, uint32_t min_anchors, nts_iv_link** out,
@@ -873,6 +874,37 @@ extern "C" int nts_iv_periods(nts_ctx* ctx, const nts_sample* recs, uint64_t n, 
   if (!ctx || (n && !recs) || (n_iv && !out)) return fail(ctx, NTS_EINVAL, "nts_iv_periods: bad arguments");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   return iv_periods_run(ctx, recs, n, n_iv, out);
+}
+
+extern "C" int nts_iv_period_hashes(nts_ctx* ctx, const nts_sample* recs, uint64_t n, uint64_t n_iv, const uint32_t* period, nts_sample** out, uint64_t* n_out)
+{
+  if (!ctx || !out || !n_out || (n && !recs) || (n_iv && !period)) return fail(ctx, NTS_EINVAL, "nts_iv_period_hashes: bad arguments");
+  *out = nullptr;
+  *n_out = 0;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return iv_period_hashes_run(ctx, recs, n, n_iv, period, out, n_out);
+}
+
+extern "C" int nts_iv_families(nts_ctx* ctx, const nts_sample* pairs, uint64_t n, uint64_t n_arrays, uint32_t* family, uint64_t** hashes,
+                               uint32_t** hash_family, uint64_t* n_hashes)
+{
+  if (!ctx || !hashes || !hash_family || !n_hashes || (n && !pairs) || (n_arrays && !family)) return fail(ctx, NTS_EINVAL, "nts_iv_families: bad arguments");
+  *hashes = nullptr;
+  *hash_family = nullptr;
+  *n_hashes = 0;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return iv_families_run(ctx, pairs, n, n_arrays, family, hashes, hash_family, n_hashes);
+}
+
+extern "C" int nts_iv_family_sites(nts_ctx* ctx, const nts_sample* occ, uint64_t n_occ, const uint64_t* hashes, const uint32_t* hash_family,
+                                   uint64_t n_hashes, uint32_t step, uint32_t min_hits, nts_iv_fsite** out, uint64_t* n_out)
+{
+  if (!ctx || !out || !n_out || min_hits == 0 || (n_occ && !occ) || (n_hashes && (!hashes || !hash_family)))
+    return fail(ctx, NTS_EINVAL, "nts_iv_family_sites: bad arguments (min_hits >= 1)");
+  *out = nullptr;
+  *n_out = 0;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return iv_family_sites_run(ctx, occ, n_occ, hashes, hash_family, n_hashes, step, min_hits, out, n_out);
 }
 
 extern "C" int nts_graph_budget(nts_ctx* ctx, uint64_t bytes)

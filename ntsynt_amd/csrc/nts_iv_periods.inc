@@ -16,6 +16,8 @@
 //      without a record, or without a recurrence, keeps its zeros)
 //   6  k_ivp_extent: one lane per record of step 2's order; a record whose lag is its interval's period gives (off - lag, off), any
 //      other the identity of (min, max); one rocprim::reduce_by_key over iv; k_ivp_extents stores first_off / last_off at out[iv]
+// Steps 1 - 3 are the helper ivp_lags and the order check is ivp_check: nts_iv_period_hashes (nts_iv_families.inc) starts from the same
+// (iv, h0, off) order and the same lags.
 // The two scatter kernels read how many keys the reductions produced from device memory; the host needs only the number of runs of
 // step 4 (one synchronise), which is also where the caller's array is the caller's again.
 
@@ -124,22 +126,55 @@ __global__ __launch_bounds__(256) void k_ivp_extents(const uint32_t* __restrict_
   out[i].last_off = e.hi;
 }
 
-int iv_periods_run(nts_ctx* ctx, const nts_sample* recs, uint64_t n, uint64_t n_iv, nts_iv_period* out)
+// the order a sampler's records have, checked in one pass (`who`: the call the message names)
+int ivp_check(nts_ctx* ctx, const char* who, const nts_sample* recs, uint64_t n, uint64_t n_iv)
 {
-  if (n > 0xFFFFFFFFull || n_iv > 0xFFFFFFFFull) return fail(ctx, NTS_ERANGE, "nts_iv_periods: 2^32 records or intervals or more (raise the rate)");
   for (uint64_t i = 0; i < n; ++i) {
-    if (recs[i].iv >= n_iv) return fail(ctx, NTS_EINVAL, "nts_iv_periods: a record names an interval at or beyond n_iv");
+    if (recs[i].iv >= n_iv) return fail(ctx, NTS_EINVAL, std::string(who) + ": a record names an interval at or beyond n_iv");
     if (i && (recs[i].iv < recs[i - 1].iv || (recs[i].iv == recs[i - 1].iv && recs[i].off <= recs[i - 1].off)))
-      return fail(ctx, NTS_EINVAL, "nts_iv_periods: the records are not in (iv, off) order, off rising strictly within an interval");
+      return fail(ctx, NTS_EINVAL, std::string(who) + ": the records are not in (iv, off) order, off rising strictly within an interval");
   }
-  if (n_iv) memset(out, 0, n_iv * sizeof(nts_iv_period));
-  if (n == 0 || n_iv == 0) return NTS_OK;
+  return NTS_OK;
+}
+
+// steps 1 - 3 for nts_iv_periods and nts_iv_period_hashes (nts_iv_families.inc): h, v = the records' h0 and off << 32 | iv in
+// (iv, h0, off) order, lag = each record's lag (0 = none), h2 = the keys of step 3, v2 = free; all n long, in the workspace
+struct IvpLags
+{
+  uint64_t *h, *v, *h2, *v2;
+  uint32_t* lag;
+};
+
+int ivp_lags(nts_ctx* ctx, const nts_sample* recs, uint64_t n, const char* t_sort, const char* t_lags, IvpLags* B)
+{
   NTS_WS(d_rec, nts_sample*, "ivp_rec", n * sizeof(nts_sample));
   NTS_WS(d_h, uint64_t*, "ivp_h", n * 8);
   NTS_WS(d_v, uint64_t*, "ivp_v", n * 8);
   NTS_WS(d_h2, uint64_t*, "ivp_h2", n * 8);
   NTS_WS(d_v2, uint64_t*, "ivp_v2", n * 8);
   NTS_WS(d_lag, uint32_t*, "ivp_lag", n * 4);
+  HIP_TRY(ctx, hipMemcpyAsync(d_rec, recs, n * sizeof(nts_sample), hipMemcpyHostToDevice, ctx->stream));
+  {
+    ScopedTimer t(ctx, t_sort);
+    NTS_LAUNCH(k_ivp_split, IVL_GRID(n), (const nts_sample*)d_rec, n, d_h, d_v);
+    if (int rc = ivs_sort(ctx, d_h, d_h2, d_v, d_v2, n, 64)) return rc;
+    if (int rc = ivs_sort(ctx, d_v2, d_v, d_h2, d_h, n, 32)) return rc; // (by the interval only: within one the (h0, off) order stays)
+  }
+  {
+    ScopedTimer t(ctx, t_lags);
+    // (d_h2 and d_v2 are free again: the lag keys and, for the caller, their sorted copy)
+    NTS_LAUNCH(k_ivp_lags, IVL_GRID(n), (const uint64_t*)d_h, (const uint64_t*)d_v, n, d_h2, d_lag);
+  }
+  *B = { d_h, d_v, d_h2, d_v2, d_lag };
+  return NTS_OK;
+}
+
+int iv_periods_run(nts_ctx* ctx, const nts_sample* recs, uint64_t n, uint64_t n_iv, nts_iv_period* out)
+{
+  if (n > 0xFFFFFFFFull || n_iv > 0xFFFFFFFFull) return fail(ctx, NTS_ERANGE, "nts_iv_periods: 2^32 records or intervals or more (raise the rate)");
+  if (int rc = ivp_check(ctx, "nts_iv_periods", recs, n, n_iv)) return rc;
+  if (n_iv) memset(out, 0, n_iv * sizeof(nts_iv_period));
+  if (n == 0 || n_iv == 0) return NTS_OK;
   NTS_WS(d_cnt, uint32_t*, "ivp_cnt", n * 4);
   NTS_WS(d_riv, uint32_t*, "ivp_riv", n * 4);
   NTS_WS(d_uiv, uint32_t*, "ivp_uiv", n * 4);
@@ -149,19 +184,16 @@ int iv_periods_run(nts_ctx* ctx, const nts_sample* recs, uint64_t n, uint64_t n_
   NTS_WS(d_uext, IvpExt*, "ivp_uext", n * sizeof(IvpExt));
   NTS_WS(d_num, uint64_t*, "ivp_num", 8);
   NTS_WS(d_out, nts_iv_period*, "ivp_out", n_iv * sizeof(nts_iv_period));
-  HIP_TRY(ctx, hipMemcpyAsync(d_rec, recs, n * sizeof(nts_sample), hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemsetAsync(d_out, 0, n_iv * sizeof(nts_iv_period), ctx->stream));
-  {
-    ScopedTimer t(ctx, "iv_periods_sort");
-    NTS_LAUNCH(k_ivp_split, IVL_GRID(n), (const nts_sample*)d_rec, n, d_h, d_v);
-    if (int rc = ivs_sort(ctx, d_h, d_h2, d_v, d_v2, n, 64)) return rc;
-    if (int rc = ivs_sort(ctx, d_v2, d_v, d_h2, d_h, n, 32)) return rc; // (by the interval only: within one the (h0, off) order stays)
-  }
+  IvpLags B;
+  if (int rc = ivp_lags(ctx, recs, n, "iv_periods_sort", "iv_periods_mode", &B)) return rc;
+  uint64_t* const d_h2 = B.h2;
+  uint64_t* const d_v2 = B.v2;
+  const uint64_t* const d_v = B.v;
+  const uint32_t* const d_lag = B.lag;
   uint64_t nr = 0;
   {
     ScopedTimer t(ctx, "iv_periods_mode");
-    // (d_h2 and d_v2 are free again: the lag keys and their sorted copy)
-    NTS_LAUNCH(k_ivp_lags, IVL_GRID(n), (const uint64_t*)d_h, (const uint64_t*)d_v, n, d_h2, d_lag);
     size_t tmp = 0;
     HIP_TRY(ctx, rocprim::radix_sort_keys(nullptr, tmp, d_h2, d_v2, n, 0, 64, ctx->stream));
     {
@@ -187,8 +219,8 @@ int iv_periods_run(nts_ctx* ctx, const nts_sample* recs, uint64_t n, uint64_t n_
   }
   {
     ScopedTimer t(ctx, "iv_periods_extent");
-    NTS_LAUNCH(k_ivp_extent, IVL_GRID(n), (const uint64_t*)d_v, (const uint32_t*)d_lag, n, n_iv, (const nts_iv_period*)d_out, d_ext);
-    auto keys = rocprim::make_transform_iterator((const uint64_t*)d_v, IvpLow32());
+    NTS_LAUNCH(k_ivp_extent, IVL_GRID(n), d_v, d_lag, n, n_iv, (const nts_iv_period*)d_out, d_ext);
+    auto keys = rocprim::make_transform_iterator(d_v, IvpLow32());
     size_t tmp = 0;
     HIP_TRY(ctx, rocprim::reduce_by_key(nullptr, tmp, keys, d_ext, n, d_uiv, d_uext, d_num, IvpSpan(), rocprim::equal_to<uint32_t>(), ctx->stream));
     NTS_WS(d_tmp, void*, "ivs_tmp", std::max<size_t>(tmp, 16));

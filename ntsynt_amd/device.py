@@ -48,6 +48,8 @@ LINK_DTYPE = np.dtype([(n, "<u4") for n in ("list_a", "iv_a", "list_b", "iv_b", 
 SITE_DTYPE = np.dtype([(n, "<u4") for n in ("list_q", "iv_q", "rec_t", "hits", "fwd", "rev", "min_off_q", "max_off_q", "first_t", "last_t")])
 # nts_iv_period: what Context.iv_periods returns, one per interval
 PERIOD_DTYPE = np.dtype([(n, "<u4") for n in ("recurring", "period", "period_hits", "first_off", "last_off")])
+# nts_iv_fsite: what Context.iv_family_sites returns
+FSITE_DTYPE = np.dtype([(n, "<u4") for n in ("family", "rec", "first", "last", "hits")])
 
 
 class Context:
@@ -150,6 +152,57 @@ class Context:
         self.check(self.lib.nts_iv_periods(self.h, rec.ctypes.data if rec.size else None, rec.size, int(n_iv), out.ctypes.data if out.size else None),
                    "nts_iv_periods")
         return out
+
+    def _take(self, p, n, dtype):
+        "n elements of the library's array p as a numpy array of its own; p is released"
+        out = np.empty(int(n), dtype=dtype)
+        if out.size:
+            ctypes.memmove(out.ctypes.data, p.value, out.nbytes)
+        self.lib.nts_free(p)
+        return out
+
+    def iv_period_hashes(self, records, n_iv, period):
+        """per interval the distinct hashes that carry its period (nts_iv_period_hashes).  records: ONE SAMPLE_DTYPE array as a sampler
+        returns it (as for iv_periods); period: one value per interval, 0 = skip it.  Returns a SAMPLE_DTYPE array sorted by (iv, h0):
+        one record per distinct (iv, h0) that has at least one record whose lag equals period[iv], off = how many such records there
+        are.  Exact and deterministic."""
+        rec = np.ascontiguousarray(records, dtype=SAMPLE_DTYPE)
+        per = np.ascontiguousarray(period, dtype=np.uint32)
+        if per.shape != (int(n_iv),):
+            raise ValueError("iv_period_hashes: one period per interval")
+        p, m = c_vp(), u64()
+        self.check(self.lib.nts_iv_period_hashes(self.h, rec.ctypes.data if rec.size else None, rec.size, int(n_iv), per.ctypes.data if per.size else None,
+                                                 ctypes.byref(p), ctypes.byref(m)), "nts_iv_period_hashes")
+        return self._take(p, m.value, SAMPLE_DTYPE)
+
+    def iv_families(self, pairs, n_arrays):
+        """the arrays that share a hash joined into families (nts_iv_families).  pairs: a SAMPLE_DTYPE array of (h0, iv = the array's
+        index; off is ignored, duplicates are allowed).  Returns (family, hashes, hash_family): family[a] = the smallest array index of
+        a's component (a itself without a pair), hashes = the distinct h0 ascending, hash_family[j] = the component of hashes[j]."""
+        rec = np.ascontiguousarray(pairs, dtype=SAMPLE_DTYPE)
+        family = np.zeros(int(n_arrays), dtype=np.uint32)
+        ph, pf, m = c_vp(), c_vp(), u64()
+        self.check(self.lib.nts_iv_families(self.h, rec.ctypes.data if rec.size else None, rec.size, int(n_arrays), family.ctypes.data if family.size else None,
+                                            ctypes.byref(ph), ctypes.byref(pf), ctypes.byref(m)), "nts_iv_families")
+        return family, self._take(ph, m.value, np.uint64), self._take(pf, m.value, np.uint32)
+
+    def iv_family_sites(self, occurrences, hashes, hash_family, step, min_hits):
+        """where ONE genome holds each family's hashes close together (nts_iv_family_sites).  occurrences: the records of
+        Genome.hset_sample_intervals over whole records (iv = record, off = position); hashes: ascending strictly, hash_family: the
+        family of each.  Returns a FSITE_DTYPE array sorted by (family, rec, first): per family the maximal runs within one record
+        whose consecutive positions differ by at most `step`, kept with at least min_hits occurrences; first / last = the first and
+        the last position.  Exact and deterministic."""
+        occ = np.ascontiguousarray(occurrences, dtype=SAMPLE_DTYPE)
+        hs = np.ascontiguousarray(hashes, dtype=np.uint64)
+        hf = np.ascontiguousarray(hash_family, dtype=np.uint32)
+        if hs.ndim != 1 or hf.shape != hs.shape:
+            raise ValueError("iv_family_sites: one family per hash")
+        assert FSITE_DTYPE.itemsize == ctypes.sizeof(_lib.IvFsite)
+        p, m = c_vp(), u64()
+        self.check(self.lib.nts_iv_family_sites(self.h, occ.ctypes.data if occ.size else None, occ.size, hs.ctypes.data if hs.size else None,
+                                                hf.ctypes.data if hf.size else None, hs.size, int(step), int(min_hits), ctypes.byref(p), ctypes.byref(m)),
+                   "nts_iv_family_sites")
+        return self._take(p, m.value, FSITE_DTYPE)
 
     def timing(self, name):
         ms, n = ctypes.c_double(), u64()

@@ -30,7 +30,13 @@ sites (copy_sites: nts_iv_sites, one call per target genome).  docs/design/04_13
 Which gaps are tandem arrays (`ntSynt --gap-periods`, `bin/ntsynt_gaps --periods-out`): every genome's gaps are sampled once more
 WITHOUT any filter (sample_all: nts_sample_intervals -- an array that one genome alone has is in no common filter), and per genome one
 call finds, for every gap, the distance that most often separates two consecutive copies of a sampled k-mer (periods: nts_iv_periods):
-the period, how many records hold it, and the stretch they cover.  docs/design/04_14_gap_periods.md."""
+the period, how many records hold it, and the stretch they cover.  docs/design/04_14_gap_periods.md.
+
+Which of those arrays are the same satellite, and where else a genome holds it (`ntSynt --gap-families`, `bin/ntsynt_gaps
+--families-out / --family-sites-out`): every array is reduced to the distinct hashes that carry its period (nts_iv_period_hashes), the
+arrays that share a hash are joined into families (nts_iv_families), the hashes become an exact set, every genome is swept WHOLE against
+it (nts_hset_sample_intervals) and its occurrences fall into sites per family (families: nts_iv_family_sites, then nts_iv_periods on
+the kept sites) -- a join that is linear in the occurrences.  docs/design/04_15_gap_families.md."""
 import os
 from collections import namedtuple
 
@@ -49,6 +55,9 @@ SITE_COLUMNS = ("genome", "contig", "start", "end", "left_block", "right_block",
                 "hits", "orientation", "from", "to", "sampled", "usable", "placement")
 PERIOD_COLUMNS = ("genome", "contig", "start", "end", "length", "kind", "sampled", "recurring", "period", "period_hits", "from", "to", "copies",
                   "covered_fraction", "class")
+FAMILY_COLUMNS = ("genome", "contig", "start", "end", "length", "kind", "period", "class", "family", "members", "genomes", "array_hashes",
+                  "shared_hashes")
+FAMILY_SITE_COLUMNS = ("family", "genome", "contig", "from", "to", "length", "hits", "period", "period_hits", "copies", "blocks", "placement")
 SITES_CAP, SITES_STEP = 16, 1000                                # --gap-sites-cap / --gap-sites-step
 MAX_BLOCK_LINK_GENOMES = 32                                     # nts_iv_links takes at most 64 lists: every genome's gaps and its blocks
 
@@ -587,16 +596,17 @@ def period_row(gap, k, sampled, result, min_hits):
     return row
 
 
-def periods(ctx, genomes_by_name, k, gap_rows, rate=LINKS_RATE, min_hits=LINKS_MIN):
+def periods(ctx, genomes_by_name, k, gap_rows, rate=LINKS_RATE, min_hits=LINKS_MIN, sampling=None, with_sampling=False):
     """which gaps are tandem arrays: gap_rows are report()'s (every genome's, in its order); genomes_by_name as for report().  Per
     genome, ascending by name, one nts_sample_intervals call over its gaps (sample_all: a genome given as a loader is loaded once and
     freed after its sweep), then one nts_iv_periods call on ctx over that genome's records.  Returns one dict per gap with
     PERIOD_COLUMNS' keys (period_row), in gap_rows' order.  2^32 records of one genome or more: the call refuses and this raises with
-    its message (raise the rate)."""
+    its message (raise the rate).  sampling: sample_all()'s result at this rate, where the caller has it already; with_sampling: return
+    (rows, sampling) -- one sample_all serves this and families()."""
     if rate < 1 or min_hits < 1:
         raise ValueError("periods: rate and min_hits must be at least 1")
     names = sorted(genomes_by_name)
-    lists, sampled = sample_all(genomes_by_name, k, gap_rows, rate)
+    lists, sampled = sampling if sampling is not None else sample_all(genomes_by_name, k, gap_rows, rate)
     out = []
     for li, name in enumerate(names):
         mine = [r for r in gap_rows if r["genome"] == name]
@@ -606,7 +616,7 @@ def periods(ctx, genomes_by_name, k, gap_rows, rate=LINKS_RATE, min_hits=LINKS_M
         for q, gap in enumerate(mine):
             out.append(period_row(gap, k, int(sampled[li][q]), tuple(int(found[q][c]) for c in ("recurring", "period", "period_hits", "first_off", "last_off")),
                                   min_hits))
-    return out
+    return (out, (lists, sampled)) if with_sampling else out
 
 
 def periods_table(rows, k, rate, min_hits):
@@ -615,6 +625,159 @@ def periods_table(rows, k, rate, min_hits):
     for r in rows:
         lines.append("\t".join("." if r[c] is None else str(r[c]) for c in PERIOD_COLUMNS))
     lines.append(f"# k {int(k)}, rate {int(rate)}, min_hits {int(min_hits)}")
+    return "\n".join(lines) + "\n"
+
+
+def family_row(period_row_, family, members, genomes, array_hashes, shared_hashes):
+    """an array's line of <prefix>.gap_families.tsv: period_row_ = its row of periods() (class `tandem` or `partial`); family = its
+    family's number (1, 2, ... by the smallest array index); members = the arrays of the family, genomes = the genomes that have one;
+    array_hashes = the distinct hashes that carry the array's period, shared_hashes = those of them another array also holds"""
+    row = {c: period_row_[c] for c in ("genome", "contig", "start", "end", "length", "kind", "period", "class")}
+    row.update({"family": int(family), "members": int(members), "genomes": int(genomes), "array_hashes": int(array_hashes),
+                "shared_hashes": int(shared_hashes)})
+    return row
+
+
+def family_site_placement(genome, contig, from_, to, member_gaps, gap_rows):
+    """of a family's site [from_, to) on `contig` of `genome`, by precedence: `array` when it intersects a gap that is a member array of
+    its family (member_gaps: those gaps' rows), `gap` when it intersects any other gap (gap_rows: every gap's row), `block` otherwise"""
+    def hit(rows):
+        return any(r["genome"] == genome and r["contig"] == contig and from_ < r["end"] and to > r["start"] for r in rows)
+    return "array" if hit(member_gaps) else "gap" if hit(gap_rows) else "block"
+
+
+def family_site_row(family, genome, contig, first, last, hits, k, period, period_hits, min_hits, block_ids, placement_):
+    """a site's line of <prefix>.gap_family_sites.tsv: first / last = its first and last position (from = first, to = last + k);
+    period, period_hits = nts_iv_periods' over the site's own occurrences; copies = (10 * (to - from)) // period in tenths, rounded
+    down; with period_hits < min_hits the three read None.  block_ids: blocks_in_span of the site.  Integer arithmetic throughout."""
+    from_, to = int(first), int(last) + int(k)
+    row = {"family": int(family), "genome": genome, "contig": contig, "from": from_, "to": to, "length": to - from_, "hits": int(hits),
+           "blocks": ",".join(block_ids) or ".", "placement": placement_}
+    if int(period_hits) < int(min_hits) or int(period) < 1:
+        row.update({"period": None, "period_hits": None, "copies": None})
+    else:
+        tenths = (10 * (to - from_)) // int(period)
+        row.update({"period": int(period), "period_hits": int(period_hits), "copies": f"{tenths // 10}.{tenths % 10}"})
+    return row
+
+
+def _site_records(occurrences, hashes, hash_family, sites):
+    """the occurrences that lie in a kept site, as records for nts_iv_periods: iv = the site's index in `sites` (FSITE_DTYPE, in
+    (family, rec, first) order), off = position - the site's first position; in (iv, off) order"""
+    import numpy as np
+    from .device import SAMPLE_DTYPE
+    out = np.zeros(0, dtype=SAMPLE_DTYPE)
+    if not len(sites) or not len(occurrences):
+        return out
+    at = np.searchsorted(hashes, occurrences["h0"])
+    member = (at < hashes.size) & (hashes[np.minimum(at, hashes.size - 1)] == occurrences["h0"])
+    occ = occurrences[member]
+    fam = hash_family[at[member]].astype(np.uint64)
+    order = np.argsort(fam, kind="stable")                      # (family, rec, off): the input order supplies the rest
+    occ, fam = occ[order], fam[order]
+    key_o = (fam << np.uint64(32)) | occ["iv"].astype(np.uint64)
+    key_s = (sites["family"].astype(np.uint64) << np.uint64(32)) | sites["rec"].astype(np.uint64)
+    _, rank = np.unique(np.concatenate([key_s, key_o]), return_inverse=True)
+    rank = rank.astype(np.uint64)
+    place_s = (rank[:key_s.size] << np.uint64(32)) | sites["first"].astype(np.uint64)
+    place_o = (rank[key_s.size:] << np.uint64(32)) | occ["off"].astype(np.uint64)
+    j = np.searchsorted(place_s, place_o, side="right").astype(np.int64) - 1
+    jj = np.maximum(j, 0)
+    inside = (j >= 0) & (key_s[jj] == key_o) & (occ["off"] <= sites["last"][jj])
+    out = np.zeros(int(inside.sum()), dtype=SAMPLE_DTYPE)
+    out["h0"], out["iv"], out["off"] = occ["h0"][inside], jj[inside], occ["off"][inside] - sites["first"][jj[inside]]
+    return out
+
+
+def families(ctx, genomes_by_name, k, gap_rows, blocks, period_rows, rate=LINKS_RATE, min_hits=LINKS_MIN, step=SITES_STEP, sampling=None):
+    """which tandem arrays are the same satellite, and where each genome holds it.  gap_rows: report()'s; blocks: assess.read_blocks'
+    rows; period_rows: periods()' at this rate and min_hits, one per gap in gap_rows' order -- a gap whose class is `tandem` or
+    `partial` is an array, numbered 0, 1, ... in that order; sampling: sample_all()'s at this rate where the caller has it (periods(...,
+    with_sampling=True)), else taken here.  Per genome one nts_iv_period_hashes call reduces its arrays to the distinct hashes that
+    carry their periods; one nts_iv_families joins the arrays that share a hash; the hashes become one exact set (nts_hset_build) and
+    per genome, ascending by name (a loader is loaded once and freed after its sweep): one nts_hset_sample_intervals over the WHOLE
+    genome, one nts_iv_family_sites, one nts_iv_periods on the kept sites.  Returns (rows, site rows, hashes in the set): one dict per
+    array with FAMILY_COLUMNS' keys, in array order, and one per kept site with FAMILY_SITE_COLUMNS' keys, by (family, genome,
+    record, from).  A record of 2^32 bases, or 2^32 occurrences in one genome: the call refuses and this raises with its message."""
+    import numpy as np
+    from .device import SAMPLE_DTYPE, HashSet
+    if rate < 1 or min_hits < 1 or step < 0:
+        raise ValueError("families: rate and min_hits must be at least 1, step at least 0")
+    if len(period_rows) != len(gap_rows):
+        raise ValueError("families: one period row per gap")
+    names = sorted(genomes_by_name)
+    lists, sampled = sampling if sampling is not None else sample_all(genomes_by_name, k, gap_rows, rate)
+    arrays = [i for i, r in enumerate(period_rows) if r["class"] in ("tandem", "partial")]
+    index_of = {i: a for a, i in enumerate(arrays)}            # gap (its place in gap_rows) -> array
+    parts = []
+    for li, name in enumerate(names):
+        mine = [i for i, r in enumerate(gap_rows) if r["genome"] == name]
+        if len(sampled[li]) != len(mine):
+            raise ValueError(f"families: the sampling of {name} is not that of these gaps")
+        period = np.array([period_rows[i]["period"] if i in index_of else 0 for i in mine], dtype=np.uint32)
+        if not period.any():
+            continue
+        found = ctx.iv_period_hashes(lists[li], len(mine), period)
+        found["iv"] = np.array([index_of.get(i, 0) for i in mine], dtype=np.uint32)[found["iv"]]
+        parts.append(found)
+    pairs = np.concatenate(parts) if parts else np.zeros(0, dtype=SAMPLE_DTYPE)
+    family, hashes, hash_family = ctx.iv_families(pairs, len(arrays))
+    number = {int(root): n + 1 for n, root in enumerate(sorted(set(family.tolist())))}       # by the smallest array index
+    _, inverse, holders = np.unique(pairs["h0"], return_inverse=True, return_counts=True)      # (pairs are distinct: holders = arrays)
+    rows = []
+    for a, i in enumerate(arrays):
+        of_family = [b for b in range(len(arrays)) if family[b] == family[a]]
+        mine = pairs["iv"] == a
+        rows.append(family_row(period_rows[i], number[int(family[a])], len(of_family), len({period_rows[arrays[b]]["genome"] for b in of_family}),
+                               int(mine.sum()), int((holders[inverse[mine]] > 1).sum())))
+    site_rows = []
+    if hashes.size:
+        numbered = np.array([number[int(f)] for f in hash_family], dtype=np.uint32)
+        member_gaps = {}
+        for a, i in enumerate(arrays):
+            member_gaps.setdefault(number[int(family[a])], []).append(gap_rows[i])
+        hset = HashSet(ctx, hashes)
+        try:
+            def sweep(name, g):
+                whole = [(j, 0, int(n)) for j, n in enumerate(g.rec_len)]
+                occurrences, _ = g.hset_sample_intervals(hset, whole, k, rate)
+                sites = ctx.iv_family_sites(occurrences, hashes, numbered, step, min_hits)
+                found = ctx.iv_periods(_site_records(occurrences, hashes, numbered, sites), len(sites))
+                contigs = list(g.names)
+                for s, p in zip(sites, found):
+                    contig, from_, to = contigs[int(s["rec"])], int(s["first"]), int(s["last"]) + int(k)
+                    site_rows.append(family_site_row(int(s["family"]), name, contig, from_, int(s["last"]), int(s["hits"]), k, int(p["period"]),
+                                                     int(p["period_hits"]), min_hits, blocks_in_span(blocks, name, contig, from_, to),
+                                                     family_site_placement(name, contig, from_, to, member_gaps[int(s["family"])], gap_rows)))
+            _each_genome(genomes_by_name, names, sweep)
+        finally:
+            hset.free()
+        site_rows.sort(key=lambda r: r["family"])               # stable: genomes by name, then (record, from) within a family
+    return rows, site_rows, int(hashes.size)
+
+
+def _families_footer(k, rate, min_hits, step, n_arrays, n_families, n_set):
+    return (f"# k {int(k)}, rate {int(rate)}, min_hits {int(min_hits)}, step {int(step)}, arrays {int(n_arrays)}, families {int(n_families)}, "
+            f"set {int(n_set)} hashes")
+
+
+def families_table(rows, k, rate, min_hits, step, n_set):
+    """<prefix>.gap_families.tsv: a header, one line per array (families()' rows, in their order), then
+    `# k K, rate R, min_hits M, step D, arrays A, families F, set N hashes`"""
+    lines = ["\t".join(FAMILY_COLUMNS)]
+    for r in rows:
+        lines.append("\t".join(str(r[c]) for c in FAMILY_COLUMNS))
+    lines.append(_families_footer(k, rate, min_hits, step, len(rows), len({r["family"] for r in rows}), n_set))
+    return "\n".join(lines) + "\n"
+
+
+def family_sites_table(site_rows, k, rate, min_hits, step, n_arrays, n_families, n_set):
+    """<prefix>.gap_family_sites.tsv: a header, one line per kept site (families()' site rows, in their order; `.` where a site has no
+    period), then the footer of families_table()"""
+    lines = ["\t".join(FAMILY_SITE_COLUMNS)]
+    for r in site_rows:
+        lines.append("\t".join("." if r[c] is None else str(r[c]) for c in FAMILY_SITE_COLUMNS))
+    lines.append(_families_footer(k, rate, min_hits, step, n_arrays, n_families, n_set))
     return "\n".join(lines) + "\n"
 
 
@@ -637,6 +800,10 @@ def build_parser():
                    "(the copies of a repeat gap) to this file (<prefix>.gap_copy_sites.tsv); uses --links-rate and --links-min")
     p.add_argument("--periods-out", help="also write, per gap, the period, the copy count and the extent of a tandem array in it, from an unfiltered "
                    "sample of its k-mers, to this file (<prefix>.gap_periods.tsv); uses --links-rate and --links-min")
+    p.add_argument("--families-out", help="also write, per tandem array of the periods, its family -- the arrays that share a hash carrying their period -- "
+                   "to this file (<prefix>.gap_families.tsv); uses --links-rate, --links-min and --sites-step")
+    p.add_argument("--family-sites-out", help="also write where each genome holds each family's k-mers close together, in an array gap, in another gap "
+                   "or inside a block, to this file (<prefix>.gap_family_sites.tsv); uses --links-rate, --links-min and --sites-step")
     p.add_argument("--sites-cap", help=f"use a k-mer against a genome that holds it at most this many times [{SITES_CAP}]", type=int, default=SITES_CAP)
     p.add_argument("--sites-step", help=f"two hits of a site lie at most this many bases apart [{SITES_STEP}]", type=int, default=SITES_STEP)
     p.add_argument("--links-rate", help=f"sample one in this many of the gap k-mers the filter holds [{LINKS_RATE}]", type=int, default=LINKS_RATE)
@@ -697,10 +864,21 @@ def main(argv=None):
                 c_rows, n_set, absent, n_sampled = copies(ctx, loaders, k, gap_rows, sampling[0], sampling[1], args.links_rate, counted=counted)
                 with open(args.copies_out, "w", encoding="utf-8") as fh:
                     fh.write(copies_table(c_rows, k, args.links_rate, n_bits, n_set, absent, n_sampled))
-            if args.periods_out:
-                p_rows = periods(ctx, loaders, k, gap_rows, args.links_rate, args.links_min)
-                with open(args.periods_out, "w", encoding="utf-8") as fh:
-                    fh.write(periods_table(p_rows, k, args.links_rate, args.links_min))
+            if args.periods_out or args.families_out or args.family_sites_out:
+                p_rows, unfiltered = periods(ctx, loaders, k, gap_rows, args.links_rate, args.links_min, with_sampling=True)
+                if args.periods_out:
+                    with open(args.periods_out, "w", encoding="utf-8") as fh:
+                        fh.write(periods_table(p_rows, k, args.links_rate, args.links_min))
+            if args.families_out or args.family_sites_out:
+                f_rows, fs_rows, n_set = families(ctx, loaders, k, gap_rows, blocks, p_rows, args.links_rate, args.links_min, args.sites_step,
+                                                  sampling=unfiltered)
+                if args.families_out:
+                    with open(args.families_out, "w", encoding="utf-8") as fh:
+                        fh.write(families_table(f_rows, k, args.links_rate, args.links_min, args.sites_step, n_set))
+                if args.family_sites_out:
+                    with open(args.family_sites_out, "w", encoding="utf-8") as fh:
+                        fh.write(family_sites_table(fs_rows, k, args.links_rate, args.links_min, args.sites_step, len(f_rows),
+                                                    len({r["family"] for r in f_rows}), n_set))
         finally:
             bf.free()
     finally:

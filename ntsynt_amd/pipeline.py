@@ -497,7 +497,7 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         benchmark=False, log=print, ctx=None, backend=None, bf_rounding="up", bf_signature=BF_SIGNATURE, dev=False, interarrivals=False, repeat=False,
         mx_tsvs=None, common_file=None, m=90, n=0, initial_only=False, write_fai=True, engine="device", refine_repeat_file=None, screen_repeat_file=None,
         graph_budget=None, assess=None, gaps=False, gap_links=None, gap_block_links=False, gap_copies=None, gap_copy_sites=None,
-        gap_periods=None):
+        gap_periods=None, gap_families=None):
     """FASTA paths -> engine (outputs in .outputs and in the CWD).  Mirrors oracle.synteny_oracle.run_pipeline's
     signature so the parity tests read alike.  Under torch.distributed (WORLD_SIZE > 1, process group already
     initialised by the caller) genomes are sharded over the ranks.
@@ -520,7 +520,9 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
     per genome serves both files --, and the stage gap_copy_sites makes the table.  gap_periods = (rate, min_hits):
     implies gaps; after the other gap files, <prefix>.gap_periods.tsv (gaps.periods: the period, the copy count and the extent of a
     tandem array in each gap, from an unfiltered sample of its own: it shares nothing with the sampling above, so the rate is its
-    own)."""
+    own).  gap_families = step: needs gap_periods, whose rate and min_hits it shares; after that file, <prefix>.gap_families.tsv and
+    <prefix>.gap_family_sites.tsv (gaps.families: the arrays that share the hashes carrying their period, and where each genome holds
+    each such family; the unfiltered sampling of gap_periods serves both stages)."""
     prefix = prefix or f"ntSynt.k{k}.w{w}"
     if mx_tsvs is not None and len(mx_tsvs) != len(fastas):
         raise ValueError("one minimizer TSV per FASTA file")
@@ -573,6 +575,11 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         gaps = True                     # the periods are found in the gaps the report cuts
         if int(gap_periods[0]) < 1 or int(gap_periods[1]) < 1:
             raise ValueError("gap_periods = (rate, min_hits), both at least 1")
+    if gap_families is not None:
+        if gap_periods is None:
+            raise ValueError("gap_families needs gap_periods (it groups the arrays that stage finds)")
+        if int(gap_families) < 0 or int(gap_families) > 0xFFFFFFFF:
+            raise ValueError("gap_families = step, at least 0 (a 32-bit value)")
     if gaps and (world > 1 or (mx_tsvs is not None and initial_only)):
         raise ValueError("gaps needs every genome resident on one GPU (one rank, genomes loaded)")
     if gaps and not isinstance(backend, GpuBackend):
@@ -1138,12 +1145,29 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         if gap_periods is not None:
             st.start("gap_periods")
             p_rate, p_min = int(gap_periods[0]), int(gap_periods[1])
-            text = gaps_.periods_table(gaps_.periods(backend.ctx, by_name, k, gap_rows, p_rate, p_min), k, p_rate, p_min)
+            if gap_families is not None:                 # (one unfiltered sampling serves both stages)
+                p_rows, unfiltered = gaps_.periods(backend.ctx, by_name, k, gap_rows, p_rate, p_min, with_sampling=True)
+            else:
+                p_rows = gaps_.periods(backend.ctx, by_name, k, gap_rows, p_rate, p_min)
+            text = gaps_.periods_table(p_rows, k, p_rate, p_min)
             with open(f"{prefix}.gap_periods.tsv", "w", encoding="utf-8") as fh:
                 fh.write(text)
             eng.outputs[f"{prefix}.gap_periods.tsv"] = text
             st.stop()
             st.mark("gap_periods_done")
+        if gap_families is not None:
+            st.start("gap_families")
+            f_step = int(gap_families)
+            f_rows, fs_rows, n_set = gaps_.families(backend.ctx, by_name, k, gap_rows, table_rows, p_rows, p_rate, p_min, f_step, sampling=unfiltered)
+            del unfiltered
+            for out_name, text in ((f"{prefix}.gap_families.tsv", gaps_.families_table(f_rows, k, p_rate, p_min, f_step, n_set)),
+                                   (f"{prefix}.gap_family_sites.tsv", gaps_.family_sites_table(fs_rows, k, p_rate, p_min, f_step, len(f_rows),
+                                                                                               len({r["family"] for r in f_rows}), n_set))):
+                with open(out_name, "w", encoding="utf-8") as fh:
+                    fh.write(text)
+                eng.outputs[out_name] = text
+            st.stop()
+            st.mark("gap_families_done")
     memory = st.memory()
     if benchmark and rank == 0:
         st.write(f"{prefix}.stage_times.tsv", memory)

@@ -15,9 +15,13 @@ rate-16 samples of a tenth of each genome's intervals) against the first genome'
 nts_iv_links' on the same lists.  With --periods, the measurement behind docs/design/04_14_gap_periods.md: the two launches of
 nts_sample_intervals (timers iv_sample_count / iv_sample_write) beside k_bf_sample<false / true> on the same tiles in the same process
 -- the sampler that probes nothing does strictly less per k-mer --, and one nts_iv_periods call on the records of a tenth of the
-intervals, its three timers (--sites times nts_iv_sites on lists of that size from the same input).
+intervals, its three timers (--sites times nts_iv_sites on lists of that size from the same input).  With --families, the measurement
+behind docs/design/04_15_gap_families.md: on the unfiltered rate-16 records of a tenth of the intervals, nts_iv_period_hashes (timer
+iv_phash) with the periods nts_iv_periods finds on them, nts_iv_families (iv_families_join) with those records as pairs, and
+nts_iv_family_sites (iv_family_sites_label / iv_family_sites_select) on the whole genome's occurrences of their hashes, beside the
+parent's nts_iv_periods on the same records and nts_iv_sites of those records against as many occurrences, the yardsticks.
 
-    python scripts/gap_links_measure.py [--bp 3000000000] [--calls 6] [--out FILE.json] [--hset | --hcount | --sites | --periods]
+    python scripts/gap_links_measure.py [--bp 3000000000] [--calls 6] [--out FILE.json] [--hset | --hcount | --sites | --periods | --families]
 
 A 3 Gbp synthetic genome (24 contigs) cut into 10^4 tiling intervals, the common filter of the three-genome 1 % family.  The launches
 are timed with device events (nts_timing), the whole call with the host clock around it.  Rate 1 writes a record for every k-mer the
@@ -244,6 +248,33 @@ def measure_periods(ctx, g, bf, iv, tenth, k, calls, out):
                              intervals_with_4_hits=int((found["period_hits"] >= 4).sum()))
 
 
+def measure_families(ctx, g, iv, tenth, k, calls, out):
+    "the three calls of the gap families on a tenth's unfiltered records, beside nts_iv_periods and nts_iv_sites on lists of the same size"
+    rec10, _ = g.sample_intervals(tenth, k, 16)
+    n_iv = int(tenth.shape[0])
+    ctx.profile(1)
+    found = ctx.iv_periods(rec10, n_iv)
+    out["iv_periods"] = dict(timed(ctx, ["iv_periods_sort", "iv_periods_mode", "iv_periods_extent"], lambda: ctx.iv_periods(rec10, n_iv), calls),
+                             records=int(rec10.size), intervals=n_iv)
+    period = np.where(found["period_hits"] >= 4, found["period"], 0).astype(np.uint32)
+    carried = ctx.iv_period_hashes(rec10, n_iv, period)
+    out["iv_period_hashes"] = dict(timed(ctx, ["iv_phash"], lambda: ctx.iv_period_hashes(rec10, n_iv, period), calls), records=int(rec10.size),
+                                   intervals_with_a_period=int((period > 0).sum()), lines=int(carried.size))
+    family, hashes, hash_family = ctx.iv_families(rec10, n_iv)  # (every record a pair: the join on a list of the yardstick's size)
+    out["iv_families"] = dict(timed(ctx, ["iv_families_join"], lambda: ctx.iv_families(rec10, n_iv), calls), pairs=int(rec10.size), arrays=n_iv,
+                              families=int(np.unique(family).size), hashes=int(hashes.size))
+    hset = HashSet(ctx, hashes)
+    occurrences, _ = g.hset_sample_intervals(hset, iv, k, 16)   # the whole genome against the set
+    hset.free()
+    sites = ctx.iv_family_sites(occurrences, hashes, hash_family, 1000, 4)
+    out["iv_family_sites"] = dict(timed(ctx, ["iv_family_sites_label", "iv_family_sites_select"],
+                                        lambda: ctx.iv_family_sites(occurrences, hashes, hash_family, 1000, 4), calls), occurrences=int(occurrences.size),
+                                  hashes=int(hashes.size), sites=int(sites.size))
+    found_sites = ctx.iv_sites([rec10], occurrences, 1000, 4)
+    out["iv_sites"] = dict(timed(ctx, ["iv_sites_join", "iv_sites_pairs", "iv_sites_select"], lambda: ctx.iv_sites([rec10], occurrences, 1000, 4), calls),
+                           records=int(rec10.size), target_records=int(occurrences.size), sites=int(found_sites.size))
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--bp", type=int, default=3_000_000_000)
@@ -256,6 +287,7 @@ def main():
     p.add_argument("--hcount", action="store_true", help="the counting sweep of gap copies beside the set sweep's count launch, and nothing else")
     p.add_argument("--sites", action="store_true", help="the capped sweep of gap copy sites beside the set sweep, the site join beside the link join, and nothing else")
     p.add_argument("--periods", action="store_true", help="the sampler without a filter of gap periods beside the filter sweep, one nts_iv_periods call, and nothing else")
+    p.add_argument("--families", action="store_true", help="the three calls of gap families beside nts_iv_periods and nts_iv_sites on lists of the same size, and nothing else")
     p.add_argument("--out")
     args = p.parse_args()
     k = args.k
@@ -275,6 +307,18 @@ def main():
     ctx.profile(2)
     kmers, hits = g.bf_count_intervals(bf, iv, k)             # warm-up, and the figures themselves
     out["intervals"], out["kmers"], out["held"] = int(iv.shape[0]), int(kmers.sum()), int(hits.sum())
+    if args.families:
+        measure_families(ctx, g, iv, tenth, k, args.calls, out)
+        ctx.profile(False)
+        text = json.dumps(out, indent=1)
+        print(text)
+        if args.out:
+            with open(args.out, "w", encoding="utf-8") as fh:
+                fh.write(text + "\n")
+        g.free()
+        bf.free()
+        ctx.close()
+        return
     if args.periods:
         measure_periods(ctx, g, bf, iv, tenth, k, args.calls, out)
         ctx.profile(False)
