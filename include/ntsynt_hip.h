@@ -619,6 +619,63 @@ int nts_iv_families(nts_ctx* ctx, const nts_sample* pairs, uint64_t n, uint64_t 
 int nts_iv_family_sites(nts_ctx* ctx, const nts_sample* occ, uint64_t n_occ, const uint64_t* hashes, const uint32_t* hash_family, uint64_t n_hashes,
                         uint32_t step, uint32_t min_hits, nts_iv_fsite** out, uint64_t* n_out);
 
+/* ---- how identical the two sides of a block are, base for base: block identity ----------------------------
+ * Two calls, both on the context's stream and in its workspace, no atomic, no launch per interval or segment, no floating point:
+ * the same input gives the same bytes.  docs/design/04_16_block_identity.md; ntsynt_amd/assess.py block_identity,
+ * `ntSynt --block-identity`, `bin/ntsynt_block_stats --identity-out`.
+ * nts_iv_anchor_segments: recs_a / recs_b = ONE genome's records each, exactly as nts_sample_intervals returns them (the order is
+ *   checked as nts_iv_periods checks it: NTS_EINVAL, also for a record of A with iv >= n_iv_a).  mate, len_b, flip: host arrays of
+ *   n_iv_a entries: mate[i] = the interval of B that interval i of A is paired with (2^32 - 1: none), len_b[i] = that interval's
+ *   clipped length, flip[i] = 1 when the two strands differ (anything but 0 or 1: NTS_EINVAL).  An anchor of interval i is a hash
+ *   that occurs exactly once among ALL records of A and exactly once among all of B, in i and in mate[i]; x = its off in A, y = its
+ *   off in B, or len_b[i] - k - off for a flipped pair (a flipped record with off + k > len_b[i] is no anchor).  Anchors are ordered
+ *   by (i, x); two consecutive anchors of one interval make a segment {iv_a = i, x, dx, y_lo = the first one's y, dy, kind}: kind =
+ *   NTS_SEG_BACKWARD for dy <= 0, else NTS_SEG_LONG for max(dx, dy) > max_len, else NTS_SEG_OFFBAND for |dy - dx| > band, else
+ *   NTS_SEG_CANDIDATE.  *segs = the segments in (iv_a, x) order, *n_segs of them, (NULL, 0) for none; released with nts_free().
+ *   anchors_per_iv (a host array of n_iv_a entries, all written) = the anchors of each interval.  A radix sort by hash, a selection,
+ *   a radix sort by (iv_a, x), a selection and a run-length encoding (timers "iv_anchors_join", "iv_anchors_segments").  NTS_EINVAL
+ *   for k = 0, band outside 1..31, max_len outside 1..65535; NTS_ERANGE before any launch for 2^32 records or more in both lists
+ *   together (anchors and segments are fewer) or 2^32 - 1 intervals or more.  csrc/nts_iv_anchors.inc.
+ * nts_edit_segments: segs = n_segs segments in iv_a order (NTS_EINVAL otherwise, and for iv_a >= n_iv_a) over the intervals iv_a[i]
+ *   of genome g_a and iv_b[i] of g_b -- iv_b[i] is the interval of the MATE of A's interval i; both lists have n_iv_a entries, clipped
+ *   to their records as the sampling calls clip; the entries of an interval without a segment are not read.  For a candidate the two
+ *   strings are the dx bases of A's interval from x and the dy bases of B's interval from y_lo in the oriented frame: for flip[i] = 1
+ *   the reverse complement (A <-> T, C <-> G) of the interval's bases [len - y_lo - dy, len - y_lo).  A candidate that leaves its
+ *   interval, has dx or dy outside 1..65535 or |dy - dx| > band is refused with NTS_EINVAL before any launch.  Per segment (dist_out,
+ *   n_segs entries, may be NULL): NTS_EDIT_PASSED for kind backward / long / offband, NTS_EDIT_NOT_CANDIDATE for any other kind that
+ *   is not a candidate, NTS_EDIT_INVALID when either string holds a base that is not A, C, G or T, else with D the unit-cost edit
+ *   distance (Levenshtein) of the two strings NTS_EDIT_OVERBAND when (D + |dy - dx|) / 2 > band, else D -- exact: a distance
+ *   restricted to the diagonals -band .. band satisfies the inequality exactly when the unrestricted one does, and then equals it.
+ *   per_iv_out[i] (n_iv_a entries, all written): segments = all of interval i's, aligned = those with a D, aligned_a / aligned_b /
+ *   edits = their dx / dy / D summed, and the count of each other outcome (too_long: kind long).  One 64-lane wave per segment, a lane
+ *   per diagonal, the bases staged through LDS (timer "edit_segments"); a reduction by key (timer "edit_reduce").  NTS_ERANGE
+ *   before any launch for 2^32 segments or intervals or more.  csrc/nts_edit.inc. */
+#define NTS_SEG_CANDIDATE 0u
+#define NTS_SEG_BACKWARD 1u
+#define NTS_SEG_LONG 2u
+#define NTS_SEG_OFFBAND 3u
+#define NTS_EDIT_NOT_CANDIDATE 0xFFFFFFFFu
+#define NTS_EDIT_PASSED 0xFFFFFFFEu
+#define NTS_EDIT_OVERBAND 0xFFFFFFFDu
+#define NTS_EDIT_INVALID 0xFFFFFFFCu
+typedef struct
+{
+  uint32_t iv_a, x, dx, y_lo;
+  int32_t dy;
+  uint32_t kind;
+} nts_iv_segment;
+typedef struct
+{
+  uint64_t aligned_a, aligned_b, edits;
+  uint32_t segments, aligned, backward, too_long, offband, invalid, overband, reserved;
+} nts_iv_identity;
+int nts_iv_anchor_segments(nts_ctx* ctx, const nts_sample* recs_a, uint64_t n_a, const nts_sample* recs_b, uint64_t n_b, const uint32_t* mate,
+                           uint64_t n_iv_a, const uint32_t* len_b, const uint8_t* flip, uint32_t k, uint32_t band, uint32_t max_len,
+                           nts_iv_segment** segs, uint64_t* n_segs, uint32_t* anchors_per_iv);
+int nts_edit_segments(nts_ctx* ctx, const nts_genome* g_a, const nts_genome* g_b, const nts_interval* iv_a, const nts_interval* iv_b,
+                      const nts_iv_segment* segs, uint64_t n_segs, uint64_t n_iv_a, const uint8_t* flip, uint32_t band,
+                      nts_iv_identity* per_iv_out, uint32_t* dist_out);
+
 /* ---- C1-C5: minimizer graph -> collinear chains -----------------------------------------------------
  * replaces ntjoin_utils.read_minimizers' duplicate removal, filter_minimizers and build_graph
  * (call sites bin/ntsynt_synteny.py:607-612, 483, 539) and the path walk of Ntjoin.find_paths

@@ -50,6 +50,17 @@ class IvFsite(ctypes.Structure):
     _fields_ = [(n, u32) for n in ("family", "rec", "first", "last", "hits")]
 
 
+class IvSegment(ctypes.Structure):
+    "nts_iv_segment: what lies between two consecutive anchors of a pair of intervals (nts_iv_anchor_segments)"
+    _fields_ = [("iv_a", u32), ("x", u32), ("dx", u32), ("y_lo", u32), ("dy", ctypes.c_int32), ("kind", u32)]
+
+
+class IvIdentity(ctypes.Structure):
+    "nts_iv_identity: the sums of one interval's segments (nts_edit_segments)"
+    _fields_ = [(n, u64) for n in ("aligned_a", "aligned_b", "edits")] + \
+               [(n, u32) for n in ("segments", "aligned", "backward", "too_long", "offband", "invalid", "overband", "reserved")]
+
+
 class MxList(ctypes.Structure):
     _fields_ = [("h1", c_vp), ("rec", c_vp), ("pos", c_vp), ("keep", c_vp), ("list_id", c_vp), ("n", u64)]
 
@@ -204,6 +215,8 @@ SYMBOLS = [
     ("nts_iv_period_hashes", ctypes.c_int, [c_vp, c_vp, u64, u64, c_vp, ctypes.POINTER(c_vp), c_u64p]),
     ("nts_iv_families", ctypes.c_int, [c_vp, c_vp, u64, u64, c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_u64p]),
     ("nts_iv_family_sites", ctypes.c_int, [c_vp, c_vp, u64, c_vp, c_vp, u64, u32, u32, ctypes.POINTER(c_vp), c_u64p]),
+    ("nts_iv_anchor_segments", ctypes.c_int, [c_vp, c_vp, u64, c_vp, u64, c_vp, u64, c_vp, c_vp, u32, u32, u32, ctypes.POINTER(c_vp), c_u64p, c_vp]),
+    ("nts_edit_segments", ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.POINTER(Interval), ctypes.POINTER(Interval), c_vp, u64, u64, c_vp, u32, c_vp, c_vp]),
     ("nts_genome_valid_bases", ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(Interval), u64, c_vp]),
     ("nts_minhash_pairs", ctypes.c_int, [c_vp, u32, c_vp, c_vp, u64, c_vp, c_vp, u64, c_vp, c_vp]),
     ("nts_graph_build", ctypes.c_int, [c_vp, u32, ctypes.POINTER(MxList), ctypes.POINTER(Graph)]),

@@ -6,7 +6,10 @@ Two things, both over `<prefix>.synteny_blocks.tsv`:
   synteny blocks"), restated: the same ten columns under the same rules.  Host arithmetic; no GPU, no torch, no numpy.
 * block_divergence: the Mash distance of `-d auto` (ntsynt_amd/divergence.py) per block and pair of its genomes, from bottom-s
   sketches of the blocks' intervals taken in one sweep per genome (nts_minhash_intervals) and one pair-count call
-  (nts_minhash_pairs); docs/design/04_8_block_assessment.md."""
+  (nts_minhash_pairs); docs/design/04_8_block_assessment.md.
+* block_identity (`ntSynt --block-identity`, `ntsynt_block_stats --identity-out`): per block and pair of its lines the exact edit
+  distance of the stretches between consecutive anchors -- sampled k-mers either genome has once (nts_sample_intervals,
+  nts_iv_anchor_segments, nts_edit_segments); docs/design/04_16_block_identity.md."""
 import os
 import re
 from collections import namedtuple
@@ -17,6 +20,10 @@ S_DEFAULT = 1000
 STATS_COLUMNS = ("Number_blocks", "Number_blocks_all_asm", "Average_coverage", "Average_coverage_all_asm", "Coverage_min_genome_size",
                  "Average_length", "Median_length", "Total_length", "NG50_length", "N50_length")
 DIVERGENCE_COLUMNS = ("block_id", "genome_a", "genome_b", "distance", "shared_hashes", "sketch_size", "kmers_a", "kmers_b")
+
+IDENTITY_K, IDENTITY_RATE, IDENTITY_BAND, IDENTITY_MAX_LEN = 21, 16, 31, 4096
+IDENTITY_COLUMNS = ("block_id", "genome_a", "genome_b", "orientation", "length_a", "length_b", "anchors", "segments", "aligned", "aligned_a",
+                    "aligned_b", "edits", "identity", "covered_a", "covered_b", "backward", "long", "offband", "invalid", "overband")
 
 # one line of a block table (README "Output files"): the block's interval on `contig` of `genome` is [start, end)
 BlockRow = namedtuple("BlockRow", ["block_id", "genome", "contig", "start", "end", "strand", "minimizers", "reason"])
@@ -183,6 +190,139 @@ def divergence_table(rows, k, s):
     return "\n".join(lines) + "\n"
 
 
+def check_identity_parameters(k, rate, band, max_len):
+    "the ranges of the four parameters of the block identity; the message of the first that is out of range, or None"
+    if k < 1:
+        return "--identity-k must be positive"
+    if rate < 1:
+        return "--identity-rate must be positive"
+    if not 1 <= band <= 31:
+        return "--identity-band must lie in 1..31"
+    if not 1 <= max_len <= 65535:
+        return "--identity-max-len must lie in 1..65535"
+    return None
+
+
+def block_identity(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_RATE, band=IDENTITY_BAND, max_len=IDENTITY_MAX_LEN):
+    """Per block and unordered pair of its lines (a before b in file order) the exact edit distance between consecutive anchors.
+    genomes_by_name: the name in column 2 -> resident device.Genome, or a callable that returns one: it is called once, and the genome
+    is freed after the last pair that needs it (both genomes of a pair are resident at once).  blocks: read_blocks' rows.  Returns
+    dicts of integers and names (identity_row formats one): block ids ascending, pairs in the order of the block's lines.  One
+    nts_sample_intervals per genome over all its lines; per ordered pair of genomes one nts_iv_anchor_segments and one
+    nts_edit_segments for every round of pairs in which no line of the first genome occurs twice."""
+    import numpy as np
+    from .device import NO_MATE
+    message = check_identity_parameters(int(k), int(rate), int(band), int(max_len))
+    if message:
+        raise ValueError(message)
+    k, rate, band, max_len = int(k), int(rate), int(band), int(max_len)
+    lines_of, index_of = {}, {}
+    for i, r in enumerate(blocks):
+        index_of[i] = len(lines_of.setdefault(r.genome, []))
+        lines_of[r.genome].append(i)
+    for name in lines_of:
+        if name not in genomes_by_name:
+            raise ValueError(f"block table names genome {name}, which is not among {sorted(genomes_by_name)}")
+    pairs = []                                                # (line a, line b) in the order of the file's rows
+    for _, lines in _block_order(blocks):
+        pairs += [(lines[x], lines[y]) for x in range(len(lines)) for y in range(x + 1, len(lines))]
+    rounds = {}                                               # (genome a, genome b) -> rounds of pairs, a line of a once per round
+    for p in pairs:
+        todo = rounds.setdefault((blocks[p[0]].genome, blocks[p[1]].genome), [])
+        for rnd in todo:
+            if p[0] not in rnd:
+                rnd[p[0]] = p[1]
+                break
+        else:
+            todo.append({p[0]: p[1]})
+    last_use = {}
+    for q, (ga, gb) in enumerate(rounds):
+        last_use[ga] = last_use[gb] = q
+    resident, loaded, intervals, length, records = {}, set(), {}, {}, {}
+
+    def genome(name):
+        if name not in resident:
+            g = genomes_by_name[name]
+            if callable(g):
+                g = g()
+                loaded.add(name)
+            resident[name] = g
+            rec_of = {c: j for j, c in enumerate(g.names)}
+            iv = np.zeros((len(lines_of[name]), 3), dtype=np.uint64)
+            for q, i in enumerate(lines_of[name]):
+                r = blocks[i]
+                if r.contig not in rec_of:
+                    raise ValueError(f"block {r.block_id}: genome {name} has no record {r.contig}")
+                n = int(g.rec_len[rec_of[r.contig]])
+                a, b = min(max(r.start, 0), n), min(max(r.end, 0), n)
+                iv[q] = (rec_of[r.contig], a, max(a, b))
+                length[i] = max(b - a, 0)
+            intervals[name] = iv
+            records[name] = g.sample_intervals(iv, k, rate)[0]
+        return resident[name]
+    found = {}
+    try:
+        for q, ((name_a, name_b), todo) in enumerate(rounds.items()):
+            g_a, g_b = genome(name_a), genome(name_b)
+            n_a = len(lines_of[name_a])
+            for rnd in todo:
+                mate = np.full(n_a, NO_MATE, dtype=np.uint32)
+                len_b = np.zeros(n_a, dtype=np.uint32)
+                flip = np.zeros(n_a, dtype=np.uint8)
+                iv_b = np.zeros((n_a, 3), dtype=np.uint64)
+                for la, lb in rnd.items():
+                    i = index_of[la]
+                    mate[i], len_b[i], flip[i] = index_of[lb], length[lb], blocks[la].strand != blocks[lb].strand
+                    iv_b[i] = intervals[name_b][index_of[lb]]
+                segs, anchors = ctx.iv_anchor_segments(records[name_a], records[name_b], mate, len_b, flip, k, band, max_len)
+                per_iv = ctx.edit_segments(g_a, g_b, intervals[name_a], iv_b, segs, flip, band)
+                for la, lb in rnd.items():
+                    found[(la, lb)] = (int(anchors[index_of[la]]), per_iv[index_of[la]])
+            for name in (name_a, name_b):
+                if last_use[name] == q and name in loaded and name in resident:
+                    resident.pop(name).free()
+                    loaded.discard(name)
+    finally:
+        for name in loaded:
+            if name in resident:
+                resident[name].free()
+    out = []
+    for la, lb in pairs:
+        anchors, s = found[(la, lb)]
+        ra, rb = blocks[la], blocks[lb]
+        out.append({"block_id": ra.block_id, "genome_a": ra.genome, "genome_b": rb.genome, "orientation": "+" if ra.strand == rb.strand else "-",
+                    "length_a": length[la], "length_b": length[lb], "anchors": anchors, "segments": int(s["segments"]), "aligned": int(s["aligned"]),
+                    "aligned_a": int(s["aligned_a"]), "aligned_b": int(s["aligned_b"]), "edits": int(s["edits"]), "backward": int(s["backward"]),
+                    "long": int(s["too_long"]), "offband": int(s["offband"]), "invalid": int(s["invalid"]), "overband": int(s["overband"])})
+    return out
+
+
+def identity_row(r):
+    """one line of the identity table, integer arithmetic throughout: identity = (10^6 (M - edits)) // M with M the larger of the two
+    aligned lengths, six decimals, `.` for M = 0; covered_* = (1000 aligned) // length as per cent with one decimal, `.` for length 0"""
+    m = max(r["aligned_a"], r["aligned_b"])
+    if m == 0:
+        identity = "."
+    else:
+        v = (1000000 * (m - r["edits"])) // m
+        identity = f"{v // 1000000}.{v % 1000000:06d}"
+
+    def covered(aligned, length):
+        if length == 0:
+            return "."
+        v = (1000 * aligned) // length
+        return f"{v // 10}.{v % 10}"
+    shown = dict(r, identity=identity, covered_a=covered(r["aligned_a"], r["length_a"]), covered_b=covered(r["aligned_b"], r["length_b"]))
+    return "\t".join(str(shown[c]) for c in IDENTITY_COLUMNS)
+
+
+def identity_table(rows, k, rate, band, max_len):
+    "TSV with a header, one line per block and pair of its lines, then `# k K, rate R, band W, max_len L`"
+    lines = ["\t".join(IDENTITY_COLUMNS)] + [identity_row(r) for r in rows]
+    lines.append(f"# k {int(k)}, rate {int(rate)}, band {int(band)}, max_len {int(max_len)}")
+    return "\n".join(lines) + "\n"
+
+
 def main(argv=None):
     "bin/ntsynt_block_stats"
     import argparse
@@ -195,10 +335,22 @@ def main(argv=None):
     p.add_argument("-k", help=f"k-mer size of the sketches [{K_DEFAULT}]", type=int, default=K_DEFAULT)
     p.add_argument("-s", help=f"sketch size [{S_DEFAULT}]", type=int, default=S_DEFAULT)
     p.add_argument("--divergence-out", help="file for the per-block table [stdout, after the statistics]")
+    p.add_argument("--identity-out", help="with --fastas: file for the per-block identity table (exact edit distance between anchors; GPU)")
+    p.add_argument("--identity-k", help=f"k-mer size of the anchors [{IDENTITY_K}]", type=int, default=IDENTITY_K)
+    p.add_argument("--identity-rate", help=f"sample one in this many k-mers as anchor candidates [{IDENTITY_RATE}]", type=int, default=IDENTITY_RATE)
+    p.add_argument("--identity-band", help=f"half-width of the alignment band, 1..31 [{IDENTITY_BAND}]", type=int, default=IDENTITY_BAND)
+    p.add_argument("--identity-max-len", help=f"longest stretch between two anchors that is aligned, 1..65535 [{IDENTITY_MAX_LEN}]", type=int,
+                   default=IDENTITY_MAX_LEN)
     p.add_argument("--device", help="GPU index [0]", type=int, default=0)
     args = p.parse_args(argv)
     if args.k < 1 or args.s < 1:
         p.error("-k and -s must be positive")
+    if args.identity_out:
+        if not args.fastas:
+            p.error("--identity-out needs the genomes: --fastas")
+        message = check_identity_parameters(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len)
+        if message:
+            p.error(message)
     print(stats_table(block_stats(args.tsv, args.fai)), end="")
     if not args.fastas:
         return 0
@@ -211,6 +363,11 @@ def main(argv=None):
     try:
         loaders = {basename(path): (lambda path=path: read_fasta_device(ctx, path)[0]) for path in args.fastas}
         text = divergence_table(block_divergence(ctx, loaders, read_blocks(args.tsv), args.k, args.s), args.k, args.s)
+        if args.identity_out:
+            id_args = (args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len)
+            id_text = identity_table(block_identity(ctx, loaders, read_blocks(args.tsv), *id_args), *id_args)
+            with open(args.identity_out, "w", encoding="utf-8") as fh:
+                fh.write(id_text)
     finally:
         ctx.close()
     if args.divergence_out:

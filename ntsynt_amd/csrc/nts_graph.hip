@@ -841,6 +841,8 @@ namespace {
 #include "nts_iv_sites.inc"
 #include "nts_iv_periods.inc"
 #include "nts_iv_families.inc"
+#include "nts_iv_anchors.inc"
+#include "nts_edit.inc"
 } // namespace
 
 extern "C" int nts_iv_links(nts_ctx* ctx, uint32_t n_lists, const nts_sample* const* lists, const uint64_t* n, uint32_t min_anchors, nts_iv_link** out,
@@ -905,6 +907,29 @@ extern "C" int nts_iv_family_sites(nts_ctx* ctx, const nts_sample* occ, uint64_t
   *n_out = 0;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   return iv_family_sites_run(ctx, occ, n_occ, hashes, hash_family, n_hashes, step, min_hits, out, n_out);
+}
+
+extern "C" int nts_iv_anchor_segments(nts_ctx* ctx, const nts_sample* recs_a, uint64_t n_a, const nts_sample* recs_b, uint64_t n_b, const uint32_t* mate,
+                                      uint64_t n_iv_a, const uint32_t* len_b, const uint8_t* flip, uint32_t k, uint32_t band, uint32_t max_len,
+                                      nts_iv_segment** segs, uint64_t* n_segs, uint32_t* anchors_per_iv)
+{
+  if (!ctx || !segs || !n_segs || (n_a && !recs_a) || (n_b && !recs_b) || (n_iv_a && (!mate || !len_b || !flip || !anchors_per_iv)) || k == 0 || band < 1 ||
+      band > EDIT_MAX_BAND || max_len < 1 || max_len > EDIT_MAX_LEN)
+    return fail(ctx, NTS_EINVAL, "nts_iv_anchor_segments: bad arguments (k >= 1, band 1..31, max_len 1..65535)");
+  *segs = nullptr;
+  *n_segs = 0;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return iv_anchor_segments_run(ctx, recs_a, n_a, recs_b, n_b, mate, n_iv_a, len_b, flip, k, band, max_len, segs, n_segs, anchors_per_iv);
+}
+
+extern "C" int nts_edit_segments(nts_ctx* ctx, const nts_genome* g_a, const nts_genome* g_b, const nts_interval* iv_a, const nts_interval* iv_b,
+                                 const nts_iv_segment* segs, uint64_t n_segs, uint64_t n_iv_a, const uint8_t* flip, uint32_t band,
+                                 nts_iv_identity* per_iv_out, uint32_t* dist_out)
+{
+  if (!ctx || !g_a || !g_b || (n_segs && !segs) || (n_iv_a && (!iv_a || !iv_b || !flip || !per_iv_out)) || band < 1 || band > EDIT_MAX_BAND)
+    return fail(ctx, NTS_EINVAL, "nts_edit_segments: bad arguments (band 1..31)");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return edit_segments_run(ctx, g_a, g_b, iv_a, iv_b, segs, n_segs, n_iv_a, flip, band, per_iv_out, dist_out);
 }
 
 extern "C" int nts_graph_budget(nts_ctx* ctx, uint64_t bytes)

@@ -50,6 +50,13 @@ SITE_DTYPE = np.dtype([(n, "<u4") for n in ("list_q", "iv_q", "rec_t", "hits", "
 PERIOD_DTYPE = np.dtype([(n, "<u4") for n in ("recurring", "period", "period_hits", "first_off", "last_off")])
 # nts_iv_fsite: what Context.iv_family_sites returns
 FSITE_DTYPE = np.dtype([(n, "<u4") for n in ("family", "rec", "first", "last", "hits")])
+# nts_iv_segment / nts_iv_identity: what Context.iv_anchor_segments and Context.edit_segments return
+SEGMENT_DTYPE = np.dtype([("iv_a", "<u4"), ("x", "<u4"), ("dx", "<u4"), ("y_lo", "<u4"), ("dy", "<i4"), ("kind", "<u4")])
+IDENTITY_DTYPE = np.dtype([(n, "<u8") for n in ("aligned_a", "aligned_b", "edits")] +
+                          [(n, "<u4") for n in ("segments", "aligned", "backward", "too_long", "offband", "invalid", "overband", "reserved")])
+SEG_CANDIDATE, SEG_BACKWARD, SEG_LONG, SEG_OFFBAND = 0, 1, 2, 3
+EDIT_NOT_CANDIDATE, EDIT_PASSED, EDIT_OVERBAND, EDIT_INVALID = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD, 0xFFFFFFFC
+NO_MATE = 0xFFFFFFFF
 
 
 class Context:
@@ -203,6 +210,50 @@ class Context:
                                                 hf.ctypes.data if hf.size else None, hs.size, int(step), int(min_hits), ctypes.byref(p), ctypes.byref(m)),
                    "nts_iv_family_sites")
         return self._take(p, m.value, FSITE_DTYPE)
+
+    def iv_anchor_segments(self, records_a, records_b, mate, len_b, flip, k, band, max_len):
+        """the anchors of pairs of intervals of two genomes and the segments between consecutive anchors (nts_iv_anchor_segments).
+        records_a / records_b: ONE SAMPLE_DTYPE array per genome as Genome.sample_intervals returns it; mate[i] = the interval of B
+        paired with interval i of A (NO_MATE: none), len_b[i] = its clipped length, flip[i] = 1 when the strands differ.  An anchor
+        is a hash either genome has exactly once, in two intervals that are mates.  Returns (segments, anchors_per_iv): a
+        SEGMENT_DTYPE array in (iv_a, x) order with kind SEG_CANDIDATE / SEG_BACKWARD / SEG_LONG / SEG_OFFBAND, and the anchors of each
+        interval of A [n_iv_a] uint32.  Exact and deterministic."""
+        ra = np.ascontiguousarray(records_a, dtype=SAMPLE_DTYPE)
+        rb = np.ascontiguousarray(records_b, dtype=SAMPLE_DTYPE)
+        mt = np.ascontiguousarray(mate, dtype=np.uint32)
+        lb = np.ascontiguousarray(len_b, dtype=np.uint32)
+        fl = np.ascontiguousarray(flip, dtype=np.uint8)
+        if mt.ndim != 1 or lb.shape != mt.shape or fl.shape != mt.shape:
+            raise ValueError("iv_anchor_segments: one mate, length and flip per interval of A")
+        assert SEGMENT_DTYPE.itemsize == ctypes.sizeof(_lib.IvSegment)
+        per_iv = np.zeros(mt.size, dtype=np.uint32)
+        p, m = c_vp(), u64()
+        self.check(self.lib.nts_iv_anchor_segments(self.h, ra.ctypes.data if ra.size else None, ra.size, rb.ctypes.data if rb.size else None, rb.size,
+                                                   mt.ctypes.data if mt.size else None, mt.size, lb.ctypes.data if mt.size else None,
+                                                   fl.ctypes.data if mt.size else None, int(k), int(band), int(max_len), ctypes.byref(p), ctypes.byref(m),
+                                                   per_iv.ctypes.data if mt.size else None), "nts_iv_anchor_segments")
+        return self._take(p, m.value, SEGMENT_DTYPE), per_iv
+
+    def edit_segments(self, genome_a, genome_b, intervals_a, intervals_b, segments, flip, band, with_distances=False):
+        """the exact edit distance of every candidate segment and the sums per interval (nts_edit_segments).  intervals_a /
+        intervals_b: (rec, start, end) rows, row i of intervals_b being the MATE of A's interval i; segments: a SEGMENT_DTYPE array in
+        iv_a order; flip[i] = 1: B's interval is read as its reverse complement.  Returns an IDENTITY_DTYPE array, one entry per
+        interval of A -- and with with_distances the per-segment results [n] uint32: the distance, or EDIT_PASSED / EDIT_INVALID /
+        EDIT_OVERBAND / EDIT_NOT_CANDIDATE.  Exact and deterministic."""
+        iva = Genome._interval_array(intervals_a)
+        ivb = Genome._interval_array(intervals_b)
+        seg = np.ascontiguousarray(segments, dtype=SEGMENT_DTYPE)
+        fl = np.ascontiguousarray(flip, dtype=np.uint8)
+        if ivb.size != iva.size or fl.shape != (iva.size,):
+            raise ValueError("edit_segments: one interval of B and one flip per interval of A")
+        assert IDENTITY_DTYPE.itemsize == ctypes.sizeof(_lib.IvIdentity)
+        out = np.zeros(iva.size, dtype=IDENTITY_DTYPE)
+        dist = np.zeros(seg.size, dtype=np.uint32) if with_distances else None
+        self.check(self.lib.nts_edit_segments(self.h, genome_a.h, genome_b.h, ctypes.cast(iva.ctypes.data, ctypes.POINTER(Interval)),
+                                              ctypes.cast(ivb.ctypes.data, ctypes.POINTER(Interval)), seg.ctypes.data if seg.size else None, seg.size,
+                                              iva.size, fl.ctypes.data if fl.size else None, int(band), out.ctypes.data if out.size else None,
+                                              dist.ctypes.data if with_distances and dist.size else None), "nts_edit_segments")
+        return (out, dist) if with_distances else out
 
     def timing(self, name):
         ms, n = ctypes.c_double(), u64()

@@ -497,7 +497,7 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         benchmark=False, log=print, ctx=None, backend=None, bf_rounding="up", bf_signature=BF_SIGNATURE, dev=False, interarrivals=False, repeat=False,
         mx_tsvs=None, common_file=None, m=90, n=0, initial_only=False, write_fai=True, engine="device", refine_repeat_file=None, screen_repeat_file=None,
         graph_budget=None, assess=None, gaps=False, gap_links=None, gap_block_links=False, gap_copies=None, gap_copy_sites=None,
-        gap_periods=None, gap_families=None):
+        gap_periods=None, gap_families=None, block_identity=None):
     """FASTA paths -> engine (outputs in .outputs and in the CWD).  Mirrors oracle.synteny_oracle.run_pipeline's
     signature so the parity tests read alike.  Under torch.distributed (WORLD_SIZE > 1, process group already
     initialised by the caller) genomes are sharded over the ranks.
@@ -550,6 +550,12 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         st.mem = _mem
     if assess is not None and (world > 1 or (mx_tsvs is not None and initial_only)):
         raise ValueError("assess needs every genome resident on one GPU (one rank, genomes loaded)")
+    if block_identity is not None:
+        if world > 1 or (mx_tsvs is not None and initial_only):
+            raise ValueError("block_identity needs every genome resident on one GPU (one rank, genomes loaded)")
+        from .assess import check_identity_parameters
+        if check_identity_parameters(*(int(x) for x in block_identity)):
+            raise ValueError("block_identity = (k, rate, band, max_len): " + check_identity_parameters(*(int(x) for x in block_identity)))
     if gap_block_links and gap_links is None:
         raise ValueError("gap_block_links needs gap_links = (rate, min_anchors)")
     if gap_block_links and len(fastas) > 32:
@@ -1083,6 +1089,18 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
             eng.outputs[name] = text
         st.stop()
         st.mark("assess_done")
+    if block_identity is not None:
+        st.start("block_identity")
+        from . import assess as assess_
+        i_args = tuple(int(x) for x in block_identity)
+        rows = assess_.block_identity(backend.ctx, {fa.basename(p): genomes[p] for p in fastas}, assess_.read_blocks(f"{prefix}.synteny_blocks.tsv"),
+                                      *i_args)
+        text = assess_.identity_table(rows, *i_args)
+        with open(f"{prefix}.block_identity.tsv", "w", encoding="utf-8") as fh:
+            fh.write(text)
+        eng.outputs[f"{prefix}.block_identity.tsv"] = text
+        st.stop()
+        st.mark("block_identity_done")
     if gaps:
         st.start("gaps")
         from . import assess as assess_, gaps as gaps_
