@@ -676,6 +676,33 @@ int nts_edit_segments(nts_ctx* ctx, const nts_genome* g_a, const nts_genome* g_b
                       const nts_iv_segment* segs, uint64_t n_segs, uint64_t n_iv_a, const uint8_t* flip, uint32_t band,
                       nts_iv_identity* per_iv_out, uint32_t* dist_out);
 
+/* ---- which edits a segment's distance consists of: block variants -------------------------------------------
+ * nts_edit_script: the arguments of nts_edit_segments and its dist_out; all of that call's checks on segments, intervals and flip
+ *   are made here too.  For every segment i with a distance D = dist[i] >= 1 the D edits of the CANONICAL script of its two strings A
+ *   (n = dx bases) and B (m = dy bases, oriented): with T the unrestricted Levenshtein table, walk from (n, m) to (0, 0) and at (i, j)
+ *   take the first that applies -- A[i-1] = B[j-1]: to (i-1, j-1), no edit; T[i-1][j-1] + 1 = T[i][j]: SUB p = i-1, q = j-1;
+ *   T[i-1][j] + 1 = T[i][j]: DEL p = i-1, q = j; otherwise INS p = i, q = j-1 -- reported in ascending path order (the reverse of
+ *   the walk).  *ops (release with nts_free; NULL for none) holds the scripts one behind the other in segment order, n_ops = the sum
+ *   of the distances; first (n_segs + 1 host entries, may be NULL): segment i's ops are first[i] .. first[i+1] - 1.  seg = i; base_a =
+ *   the code of A[p] for SUB and DEL, base_b = the code of the oriented (complemented) B[q] for SUB and INS, else 0xFF.
+ *   NTS_EINVAL before any launch for a distance on a segment that is no candidate or one with (D + |dy - dx|) / 2 > band (what
+ *   nts_edit_segments never returns); NTS_ERANGE for 2^32 edits or more; NTS_EINVAL after the launch, with no ops returned, when some
+ *   dist[i] is not the distance of segment i ("dist is not the distance of segment ...") or a string holds a base that is not A, C,
+ *   G or T.  A scan and a selection (timer "edit_script_plan"), one 64-lane wave per segment with D >= 1, the furthest-reaching table
+ *   of (D + 1) x (2 band + 1) entries in LDS (timer "edit_script").  No atomic, no launch per segment, no floating point: the same
+ *   input gives the same bytes.  docs/design/04_17_block_variants.md; csrc/nts_edit_script.inc. */
+#define NTS_OP_SUB 1u
+#define NTS_OP_DEL 2u
+#define NTS_OP_INS 3u
+typedef struct
+{
+  uint32_t seg, p, q;
+  uint8_t op, base_a, base_b, pad;
+} nts_edit_op;
+int nts_edit_script(nts_ctx* ctx, const nts_genome* g_a, const nts_genome* g_b, const nts_interval* iv_a, const nts_interval* iv_b,
+                    const nts_iv_segment* segs, uint64_t n_segs, uint64_t n_iv_a, const uint8_t* flip, uint32_t band, const uint32_t* dist,
+                    nts_edit_op** ops, uint64_t* n_ops, uint64_t* first);
+
 /* ---- C1-C5: minimizer graph -> collinear chains -----------------------------------------------------
  * replaces ntjoin_utils.read_minimizers' duplicate removal, filter_minimizers and build_graph
  * (call sites bin/ntsynt_synteny.py:607-612, 483, 539) and the path walk of Ntjoin.find_paths

@@ -61,6 +61,12 @@ class IvIdentity(ctypes.Structure):
                [(n, u32) for n in ("segments", "aligned", "backward", "too_long", "offband", "invalid", "overband", "reserved")]
 
 
+class EditOp(ctypes.Structure):
+    "nts_edit_op: one edit of a segment's canonical script (nts_edit_script)"
+    _fields_ = [("seg", u32), ("p", u32), ("q", u32), ("op", ctypes.c_uint8), ("base_a", ctypes.c_uint8), ("base_b", ctypes.c_uint8),
+                ("pad", ctypes.c_uint8)]
+
+
 class MxList(ctypes.Structure):
     _fields_ = [("h1", c_vp), ("rec", c_vp), ("pos", c_vp), ("keep", c_vp), ("list_id", c_vp), ("n", u64)]
 
@@ -217,6 +223,8 @@ SYMBOLS = [
     ("nts_iv_family_sites", ctypes.c_int, [c_vp, c_vp, u64, c_vp, c_vp, u64, u32, u32, ctypes.POINTER(c_vp), c_u64p]),
     ("nts_iv_anchor_segments", ctypes.c_int, [c_vp, c_vp, u64, c_vp, u64, c_vp, u64, c_vp, c_vp, u32, u32, u32, ctypes.POINTER(c_vp), c_u64p, c_vp]),
     ("nts_edit_segments", ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.POINTER(Interval), ctypes.POINTER(Interval), c_vp, u64, u64, c_vp, u32, c_vp, c_vp]),
+    ("nts_edit_script", ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.POINTER(Interval), ctypes.POINTER(Interval), c_vp, u64, u64, c_vp, u32, c_vp,
+                                       ctypes.POINTER(c_vp), c_u64p, c_vp]),
     ("nts_genome_valid_bases", ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(Interval), u64, c_vp]),
     ("nts_minhash_pairs", ctypes.c_int, [c_vp, u32, c_vp, c_vp, u64, c_vp, c_vp, u64, c_vp, c_vp]),
     ("nts_graph_build", ctypes.c_int, [c_vp, u32, ctypes.POINTER(MxList), ctypes.POINTER(Graph)]),

@@ -9,7 +9,10 @@ Two things, both over `<prefix>.synteny_blocks.tsv`:
   (nts_minhash_pairs); docs/design/04_8_block_assessment.md.
 * block_identity (`ntSynt --block-identity`, `ntsynt_block_stats --identity-out`): per block and pair of its lines the exact edit
   distance of the stretches between consecutive anchors -- sampled k-mers either genome has once (nts_sample_intervals,
-  nts_iv_anchor_segments, nts_edit_segments); docs/design/04_16_block_identity.md."""
+  nts_iv_anchor_segments, nts_edit_segments); docs/design/04_16_block_identity.md.
+* block_variants (`ntSynt --block-variants`, `ntsynt_block_stats --variants-out`): the edits behind those distances -- the canonical
+  script of every aligned stretch (nts_edit_script), merged into snv / ins / del events in both genomes' coordinates;
+  docs/design/04_17_block_variants.md."""
 import os
 import re
 from collections import namedtuple
@@ -24,6 +27,7 @@ DIVERGENCE_COLUMNS = ("block_id", "genome_a", "genome_b", "distance", "shared_ha
 IDENTITY_K, IDENTITY_RATE, IDENTITY_BAND, IDENTITY_MAX_LEN = 21, 16, 31, 4096
 IDENTITY_COLUMNS = ("block_id", "genome_a", "genome_b", "orientation", "length_a", "length_b", "anchors", "segments", "aligned", "aligned_a",
                     "aligned_b", "edits", "identity", "covered_a", "covered_b", "backward", "long", "offband", "invalid", "overband")
+VARIANT_COLUMNS = ("block_id", "genome_a", "contig_a", "pos_a", "genome_b", "contig_b", "pos_b", "orientation", "type", "length", "seq_a", "seq_b")
 
 # one line of a block table (README "Output files"): the block's interval on `contig` of `genome` is [start, end)
 BlockRow = namedtuple("BlockRow", ["block_id", "genome", "contig", "start", "end", "strand", "minimizers", "reason"])
@@ -203,19 +207,19 @@ def check_identity_parameters(k, rate, band, max_len):
     return None
 
 
-def block_identity(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_RATE, band=IDENTITY_BAND, max_len=IDENTITY_MAX_LEN):
-    """Per block and unordered pair of its lines (a before b in file order) the exact edit distance between consecutive anchors.
-    genomes_by_name: the name in column 2 -> resident device.Genome, or a callable that returns one: it is called once, and the genome
-    is freed after the last pair that needs it (both genomes of a pair are resident at once).  blocks: read_blocks' rows.  Returns
-    dicts of integers and names (identity_row formats one): block ids ascending, pairs in the order of the block's lines.  One
-    nts_sample_intervals per genome over all its lines; per ordered pair of genomes one nts_iv_anchor_segments and one
-    nts_edit_segments for every round of pairs in which no line of the first genome occurs twice."""
+# one call's worth of pairs: the two resident genomes, A's intervals and per interval of A its mate's interval and flip, the segments and
+# anchors nts_iv_anchor_segments found, and the pairs served as (line a, line b, index of a's interval)
+_Round = namedtuple("_Round", ["name_a", "name_b", "g_a", "g_b", "iv_a", "iv_b", "flip", "segs", "anchors", "lines"])
+
+
+def _identity_rounds(ctx, genomes_by_name, blocks, k, rate, band, max_len, pairs, length):
+    """The loop of block_identity and block_variants over pairs of genomes and rounds, as a generator of _Round.  Appends the pairs
+    (line a, line b) in the order of the file's rows to `pairs` before the first round and fills length[line] = its clipped length as
+    genomes become resident.  One nts_sample_intervals per genome over all its lines; per ordered pair of genomes one
+    nts_iv_anchor_segments for every round of pairs in which no line of the first genome occurs twice; the consumer makes the edit
+    calls on what a round holds before it asks for the next (the genomes of a round are resident until then)."""
     import numpy as np
     from .device import NO_MATE
-    message = check_identity_parameters(int(k), int(rate), int(band), int(max_len))
-    if message:
-        raise ValueError(message)
-    k, rate, band, max_len = int(k), int(rate), int(band), int(max_len)
     lines_of, index_of = {}, {}
     for i, r in enumerate(blocks):
         index_of[i] = len(lines_of.setdefault(r.genome, []))
@@ -223,8 +227,7 @@ def block_identity(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_RAT
     for name in lines_of:
         if name not in genomes_by_name:
             raise ValueError(f"block table names genome {name}, which is not among {sorted(genomes_by_name)}")
-    pairs = []                                                # (line a, line b) in the order of the file's rows
-    for _, lines in _block_order(blocks):
+    for _, lines in _block_order(blocks):                     # (line a, line b) in the order of the file's rows
         pairs += [(lines[x], lines[y]) for x in range(len(lines)) for y in range(x + 1, len(lines))]
     rounds = {}                                               # (genome a, genome b) -> rounds of pairs, a line of a once per round
     for p in pairs:
@@ -238,7 +241,7 @@ def block_identity(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_RAT
     last_use = {}
     for q, (ga, gb) in enumerate(rounds):
         last_use[ga] = last_use[gb] = q
-    resident, loaded, intervals, length, records = {}, set(), {}, {}, {}
+    resident, loaded, intervals, records = {}, set(), {}, {}
 
     def genome(name):
         if name not in resident:
@@ -260,7 +263,6 @@ def block_identity(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_RAT
             intervals[name] = iv
             records[name] = g.sample_intervals(iv, k, rate)[0]
         return resident[name]
-    found = {}
     try:
         for q, ((name_a, name_b), todo) in enumerate(rounds.items()):
             g_a, g_b = genome(name_a), genome(name_b)
@@ -275,9 +277,7 @@ def block_identity(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_RAT
                     mate[i], len_b[i], flip[i] = index_of[lb], length[lb], blocks[la].strand != blocks[lb].strand
                     iv_b[i] = intervals[name_b][index_of[lb]]
                 segs, anchors = ctx.iv_anchor_segments(records[name_a], records[name_b], mate, len_b, flip, k, band, max_len)
-                per_iv = ctx.edit_segments(g_a, g_b, intervals[name_a], iv_b, segs, flip, band)
-                for la, lb in rnd.items():
-                    found[(la, lb)] = (int(anchors[index_of[la]]), per_iv[index_of[la]])
+                yield _Round(name_a, name_b, g_a, g_b, intervals[name_a], iv_b, flip, segs, anchors, [(la, lb, index_of[la]) for la, lb in rnd.items()])
             for name in (name_a, name_b):
                 if last_use[name] == q and name in loaded and name in resident:
                     resident.pop(name).free()
@@ -286,6 +286,10 @@ def block_identity(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_RAT
         for name in loaded:
             if name in resident:
                 resident[name].free()
+
+
+def _identity_rows(blocks, pairs, length, found):
+    "the dicts block_identity returns, from found[(line a, line b)] = (anchors, the interval's nts_iv_identity)"
     out = []
     for la, lb in pairs:
         anchors, s = found[(la, lb)]
@@ -295,6 +299,96 @@ def block_identity(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_RAT
                     "aligned_a": int(s["aligned_a"]), "aligned_b": int(s["aligned_b"]), "edits": int(s["edits"]), "backward": int(s["backward"]),
                     "long": int(s["too_long"]), "offband": int(s["offband"]), "invalid": int(s["invalid"]), "overband": int(s["overband"])})
     return out
+
+
+def block_identity(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_RATE, band=IDENTITY_BAND, max_len=IDENTITY_MAX_LEN):
+    """Per block and unordered pair of its lines (a before b in file order) the exact edit distance between consecutive anchors.
+    genomes_by_name: the name in column 2 -> resident device.Genome, or a callable that returns one: it is called once, and the genome
+    is freed after the last pair that needs it (both genomes of a pair are resident at once).  blocks: read_blocks' rows.  Returns
+    dicts of integers and names (identity_row formats one): block ids ascending, pairs in the order of the block's lines.  One
+    nts_sample_intervals per genome over all its lines; per ordered pair of genomes one nts_iv_anchor_segments and one
+    nts_edit_segments for every round of pairs in which no line of the first genome occurs twice."""
+    message = check_identity_parameters(int(k), int(rate), int(band), int(max_len))
+    if message:
+        raise ValueError(message)
+    k, rate, band, max_len = int(k), int(rate), int(band), int(max_len)
+    pairs, length, found = [], {}, {}
+    for r in _identity_rounds(ctx, genomes_by_name, blocks, k, rate, band, max_len, pairs, length):
+        per_iv = ctx.edit_segments(r.g_a, r.g_b, r.iv_a, r.iv_b, r.segs, r.flip, band)
+        for la, lb, i in r.lines:
+            found[(la, lb)] = (int(r.anchors[i]), per_iv[i])
+    return _identity_rows(blocks, pairs, length, found)
+
+
+def block_variants(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_RATE, band=IDENTITY_BAND, max_len=IDENTITY_MAX_LEN):
+    """block_identity and, from the same pass, the edits behind every pair's `edits`: returns (identity rows, variant rows).  Per
+    round one nts_edit_segments with the per-segment distances and one nts_edit_script on them; the ops of a pair's segments become
+    events (variant_events) in the coordinates of the two records.  Variant rows are dicts of VARIANT_COLUMNS (variant_row formats
+    one): pairs in the order of the identity rows, events ascending by pos_a, then in script order."""
+    import numpy as np
+    message = check_identity_parameters(int(k), int(rate), int(band), int(max_len))
+    if message:
+        raise ValueError(message)
+    k, rate, band, max_len = int(k), int(rate), int(band), int(max_len)
+    pairs, length, found, events = [], {}, {}, {}
+    for r in _identity_rounds(ctx, genomes_by_name, blocks, k, rate, band, max_len, pairs, length):
+        per_iv, dist = ctx.edit_segments(r.g_a, r.g_b, r.iv_a, r.iv_b, r.segs, r.flip, band, with_distances=True)
+        ops, first = ctx.edit_script(r.g_a, r.g_b, r.iv_a, r.iv_b, r.segs, r.flip, band, dist)
+        for la, lb, i in r.lines:
+            found[(la, lb)] = (int(r.anchors[i]), per_iv[i])
+            s0, s1 = (int(x) for x in np.searchsorted(r.segs["iv_a"], [i, i + 1]))          # (the segments come in iv_a order)
+            mine = ops[int(first[s0]):int(first[s1])]
+            if mine.size != int(per_iv[i]["edits"]):
+                raise RuntimeError(f"block {blocks[la].block_id}: {mine.size} ops for {int(per_iv[i]['edits'])} edits")
+            events[(la, lb)] = variant_events(mine, r.segs, int(r.iv_a[i][1]), int(r.iv_b[i][1]), length[lb], bool(r.flip[i]))
+    rows = []
+    for la, lb in pairs:
+        ra, rb = blocks[la], blocks[lb]
+        head = {"block_id": ra.block_id, "genome_a": ra.genome, "contig_a": ra.contig, "genome_b": rb.genome, "contig_b": rb.contig,
+                "orientation": "+" if ra.strand == rb.strand else "-"}
+        rows += [dict(head, **e) for e in events[(la, lb)]]
+    return _identity_rows(blocks, pairs, length, found), rows
+
+
+def variant_events(ops, segs, start_a, start_b, len_b, flipped):
+    """The events of one pair of lines.  ops: OP_DTYPE entries in script order whose `seg` indexes segs (SEGMENT_DTYPE); start_a /
+    start_b: the clipped interval starts within their records, len_b: B's clipped length.  A maximal run of adjacent DEL ops with
+    consecutive p and one q is one `del`, a maximal run of adjacent INS ops with one p and consecutive q one `ins`, every SUB an
+    `snv`.  Returns dicts of type, pos_a, pos_b, length, seq_a, seq_b (0-based positions on the forward strand of the records; seq_b in
+    the oriented frame; `-` for no bases; the side without bases has the position of the base that follows in the oriented frame),
+    ascending by pos_a, then in script order.  Pure."""
+    sub, dele, ins = 1, 2, 3
+    runs = []                                                 # [seg, op, p0, q0, bases of A, bases of B]
+    for seg, p, q, op, base_a, base_b, _ in (ops.tolist() if hasattr(ops, "tolist") else ops):
+        if op not in (sub, dele, ins) or (op != ins and base_a > 3) or (op != dele and base_b > 3):
+            raise ValueError(f"not an edit op: {(seg, p, q, op, base_a, base_b)}")
+        last = runs[-1] if runs else None
+        if last and last[0] == seg and last[1] == op == dele and p == last[2] + len(last[4]) and q == last[3]:
+            last[4] += "ACGT"[base_a]
+        elif last and last[0] == seg and last[1] == op == ins and p == last[2] and q == last[3] + len(last[5]):
+            last[5] += "ACGT"[base_b]
+        else:
+            runs.append([seg, op, p, q, "" if op == ins else "ACGT"[base_a], "" if op == dele else "ACGT"[base_b]])
+    out = []
+    for seg, op, p0, q0, seq_a, seq_b in runs:
+        y = int(segs[seg]["y_lo"]) + q0
+        out.append({"type": {sub: "snv", dele: "del", ins: "ins"}[op], "pos_a": start_a + int(segs[seg]["x"]) + p0,
+                    "pos_b": start_b + len_b - y - len(seq_b) if flipped else start_b + y, "length": max(len(seq_a), len(seq_b)),
+                    "seq_a": seq_a or "-", "seq_b": seq_b or "-"})
+    out.sort(key=lambda e: e["pos_a"])                        # (stable: script order within one position)
+    return out
+
+
+def variant_row(r):
+    "one line of the variants table"
+    return "\t".join(str(r[c]) for c in VARIANT_COLUMNS)
+
+
+def variants_table(rows, k, rate, band, max_len):
+    "TSV with a header, one line per event, then `# k K, rate R, band W, max_len L`"
+    lines = ["\t".join(VARIANT_COLUMNS)] + [variant_row(r) for r in rows]
+    lines.append(f"# k {int(k)}, rate {int(rate)}, band {int(band)}, max_len {int(max_len)}")
+    return "\n".join(lines) + "\n"
 
 
 def identity_row(r):
@@ -336,6 +430,8 @@ def main(argv=None):
     p.add_argument("-s", help=f"sketch size [{S_DEFAULT}]", type=int, default=S_DEFAULT)
     p.add_argument("--divergence-out", help="file for the per-block table [stdout, after the statistics]")
     p.add_argument("--identity-out", help="with --fastas: file for the per-block identity table (exact edit distance between anchors; GPU)")
+    p.add_argument("--variants-out", help="with --fastas: file for the per-block variants table (the edits behind the identity table's `edits`, as snv / ins / "
+                   "del events in both genomes' coordinates; GPU); it takes the --identity-* parameters")
     p.add_argument("--identity-k", help=f"k-mer size of the anchors [{IDENTITY_K}]", type=int, default=IDENTITY_K)
     p.add_argument("--identity-rate", help=f"sample one in this many k-mers as anchor candidates [{IDENTITY_RATE}]", type=int, default=IDENTITY_RATE)
     p.add_argument("--identity-band", help=f"half-width of the alignment band, 1..31 [{IDENTITY_BAND}]", type=int, default=IDENTITY_BAND)
@@ -345,9 +441,9 @@ def main(argv=None):
     args = p.parse_args(argv)
     if args.k < 1 or args.s < 1:
         p.error("-k and -s must be positive")
-    if args.identity_out:
+    if args.identity_out or args.variants_out:
         if not args.fastas:
-            p.error("--identity-out needs the genomes: --fastas")
+            p.error(("--identity-out" if args.identity_out else "--variants-out") + " needs the genomes: --fastas")
         message = check_identity_parameters(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len)
         if message:
             p.error(message)
@@ -363,11 +459,16 @@ def main(argv=None):
     try:
         loaders = {basename(path): (lambda path=path: read_fasta_device(ctx, path)[0]) for path in args.fastas}
         text = divergence_table(block_divergence(ctx, loaders, read_blocks(args.tsv), args.k, args.s), args.k, args.s)
+        id_args = (args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len)
+        if args.variants_out:                                 # (one pass gives both tables)
+            id_rows, var_rows = block_variants(ctx, loaders, read_blocks(args.tsv), *id_args)
+            with open(args.variants_out, "w", encoding="utf-8") as fh:
+                fh.write(variants_table(var_rows, *id_args))
+        elif args.identity_out:
+            id_rows = block_identity(ctx, loaders, read_blocks(args.tsv), *id_args)
         if args.identity_out:
-            id_args = (args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len)
-            id_text = identity_table(block_identity(ctx, loaders, read_blocks(args.tsv), *id_args), *id_args)
             with open(args.identity_out, "w", encoding="utf-8") as fh:
-                fh.write(id_text)
+                fh.write(identity_table(id_rows, *id_args))
     finally:
         ctx.close()
     if args.divergence_out:

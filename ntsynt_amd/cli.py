@@ -72,6 +72,9 @@ def build_parser():
     p.add_argument("--block-identity", help="after the run, write <prefix>.block_identity.tsv: per block and pair of its genomes the exact edit distance\n"
                    "of the stretches between consecutive anchors (sampled k-mers either genome has once), how much of the block they cover\n"
                    "and why the rest was not aligned, from the genomes still on the GPU", action="store_true")
+    p.add_argument("--block-variants", help="after the run, write <prefix>.block_variants.tsv: the edits behind the `edits` of --block-identity, as snv /\n"
+                   "ins / del events in both genomes' coordinates; works with or without --block-identity and takes the --identity-* parameters",
+                   action="store_true")
     p.add_argument("--identity-k", help="k-mer size of the anchors [21]", type=int, default=21)
     p.add_argument("--identity-rate", help="sample one in this many k-mers as anchor candidates [16]", type=int, default=16)
     p.add_argument("--identity-band", help="half-width of the alignment band, 1..31 [31]", type=int, default=31)
@@ -171,8 +174,12 @@ def check_reports(parser, args):
                          "ntsynt_block_stats --tsv <prefix>.synteny_blocks.tsv --fai ... --fastas ...")
         if args.assess_k < 1 or args.assess_s < 1:
             parser.error("--assess-k and --assess-s must be positive")
-    if args.block_identity:
+    if args.block_variants:
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            parser.error("--block-variants works from the genomes resident on one GPU: run it on one rank, or assess the finished run with "
+                         "ntsynt_block_stats --tsv <prefix>.synteny_blocks.tsv --fai ... --fastas ... --variants-out <prefix>.block_variants.tsv")
+    if args.block_identity or args.block_variants:
+        if args.block_identity and int(os.environ.get("WORLD_SIZE", "1")) > 1:
             parser.error("--block-identity works from the genomes resident on one GPU: run it on one rank, or assess the finished run with "
                          "ntsynt_block_stats --tsv <prefix>.synteny_blocks.tsv --fai ... --fastas ... --identity-out <prefix>.block_identity.tsv")
         from .assess import check_identity_parameters
@@ -276,6 +283,7 @@ def main(argv=None):
             raise FileNotFoundError(f"Input file {fasta} not found.")
     plan = ["faidx x%d" % len(fastas)] + ([] if args.no_common else ["make_common_bf"]) + \
            ["indexlr x%d" % len(fastas), "ntsynt_synteny"] + (["assess"] if args.assess else []) + (["block_identity"] if args.block_identity else []) + \
+           (["block_variants"] if args.block_variants else []) + \
            (["gaps"] if args.gaps else []) + \
            (["gap_links"] if args.gap_links else []) + (["gap_block_links"] if args.gap_block_links else []) + \
            (["gap_copies"] if args.gap_copies else []) + (["gap_copy_sites"] if args.gap_copy_sites else []) + \
@@ -335,7 +343,7 @@ def _run(pipeline, fastas, args, device, quiet):
                  indel=args.indel, merge=args.merge, block_size=args.block_size, common=not args.no_common,
                  simplify=not args.no_simplify_graph, device=device, benchmark=args.benchmark,
                  dev=args.dev, interarrivals=args.interarrivals, assess=(args.assess_k, args.assess_s) if args.assess else None,
-                 block_identity=(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len) if args.block_identity else None, gaps=args.gaps, gap_links=(args.gap_links_rate, args.gap_links_min) if args.gap_links else None, gap_block_links=args.gap_block_links, gap_copies=args.gap_links_rate if args.gap_copies else None, gap_copy_sites=(args.gap_sites_cap, args.gap_sites_step, args.gap_links_min) if args.gap_copy_sites else None, gap_periods=(args.gap_links_rate, args.gap_links_min) if args.gap_periods else None, gap_families=args.gap_sites_step if args.gap_families else None, repeat=args.repeat, bf_rounding=args.bf_rounding, bf_signature=args.bf_signature or pipeline.BF_SIGNATURE,
+                 block_identity=(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len) if args.block_identity else None, block_variants=(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len) if args.block_variants else None, gaps=args.gaps, gap_links=(args.gap_links_rate, args.gap_links_min) if args.gap_links else None, gap_block_links=args.gap_block_links, gap_copies=args.gap_links_rate if args.gap_copies else None, gap_copy_sites=(args.gap_sites_cap, args.gap_sites_step, args.gap_links_min) if args.gap_copy_sites else None, gap_periods=(args.gap_links_rate, args.gap_links_min) if args.gap_periods else None, gap_families=args.gap_sites_step if args.gap_families else None, repeat=args.repeat, bf_rounding=args.bf_rounding, bf_signature=args.bf_signature or pipeline.BF_SIGNATURE,
                  log=print if (args.dev and int(os.environ.get("RANK", "0")) == 0) else quiet)
 
 

@@ -164,12 +164,13 @@ int edit_clip(nts_ctx* ctx, const nts_genome* g, const nts_interval& iv, uint64_
   return NTS_OK;
 }
 
-int edit_segments_run(nts_ctx* ctx, const nts_genome* ga, const nts_genome* gb, const nts_interval* iv_a, const nts_interval* iv_b,
-                      const nts_iv_segment* segs, uint64_t n, uint64_t n_iv, const uint8_t* flip, uint32_t band, nts_iv_identity* per_iv,
-                      uint32_t* dist_out)
+// the host checks on segments, intervals and flip that nts_edit_segments and nts_edit_script share, and what the kernels need of
+// every interval that has a segment
+int edit_prepare(nts_ctx* ctx, const nts_genome* ga, const nts_genome* gb, const nts_interval* iv_a, const nts_interval* iv_b,
+                 const nts_iv_segment* segs, uint64_t n, uint64_t n_iv, const uint8_t* flip, uint32_t band, std::vector<EditIv>& ivs)
 {
   if (n > 0xFFFFFFFFull || n_iv > 0xFFFFFFFFull) return fail(ctx, NTS_ERANGE, "nts_edit_segments: 2^32 segments or intervals or more");
-  std::vector<EditIv> ivs(n_iv);
+  ivs.resize(n_iv);
   std::vector<uint8_t> used(n_iv, 0);
   for (uint64_t i = 0; i < n; ++i) {
     if (segs[i].iv_a >= n_iv) return fail(ctx, NTS_EINVAL, "nts_edit_segments: a segment names an interval at or beyond n_iv_a");
@@ -193,6 +194,15 @@ int edit_segments_run(nts_ctx* ctx, const nts_genome* ga, const nts_genome* gb, 
         (uint64_t)s.x + s.dx > v.la || (uint64_t)s.y_lo + (uint32_t)s.dy > v.lb)
       return fail(ctx, NTS_EINVAL, "nts_edit_segments: a candidate segment leaves its interval, the band or the length limit");
   }
+  return NTS_OK;
+}
+
+int edit_segments_run(nts_ctx* ctx, const nts_genome* ga, const nts_genome* gb, const nts_interval* iv_a, const nts_interval* iv_b,
+                      const nts_iv_segment* segs, uint64_t n, uint64_t n_iv, const uint8_t* flip, uint32_t band, nts_iv_identity* per_iv,
+                      uint32_t* dist_out)
+{
+  std::vector<EditIv> ivs;
+  if (int rc = edit_prepare(ctx, ga, gb, iv_a, iv_b, segs, n, n_iv, flip, band, ivs)) return rc;
   if (n_iv) memset(per_iv, 0, n_iv * sizeof(nts_iv_identity));
   if (n == 0 || n_iv == 0) return NTS_OK;
   NTS_WS(d_ivs, EditIv*, "edit_ivs", n_iv * sizeof(EditIv));

@@ -843,6 +843,7 @@ namespace {
 #include "nts_iv_families.inc"
 #include "nts_iv_anchors.inc"
 #include "nts_edit.inc"
+#include "nts_edit_script.inc"
 } // namespace
 
 extern "C" int nts_iv_links(nts_ctx* ctx, uint32_t n_lists, const nts_sample* const* lists, const uint64_t* n, uint32_t min_anchors, nts_iv_link** out,
@@ -930,6 +931,17 @@ extern "C" int nts_edit_segments(nts_ctx* ctx, const nts_genome* g_a, const nts_
     return fail(ctx, NTS_EINVAL, "nts_edit_segments: bad arguments (band 1..31)");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   return edit_segments_run(ctx, g_a, g_b, iv_a, iv_b, segs, n_segs, n_iv_a, flip, band, per_iv_out, dist_out);
+}
+
+extern "C" int nts_edit_script(nts_ctx* ctx, const nts_genome* g_a, const nts_genome* g_b, const nts_interval* iv_a, const nts_interval* iv_b,
+                               const nts_iv_segment* segs, uint64_t n_segs, uint64_t n_iv_a, const uint8_t* flip, uint32_t band, const uint32_t* dist,
+                               nts_edit_op** ops, uint64_t* n_ops, uint64_t* first)
+{
+  if (!ctx || !g_a || !g_b || !ops || !n_ops || (n_segs && (!segs || !dist)) || (n_iv_a && (!iv_a || !iv_b || !flip)) || band < 1 ||
+      band > EDIT_MAX_BAND)
+    return fail(ctx, NTS_EINVAL, "nts_edit_script: bad arguments (band 1..31)");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return edit_script_run(ctx, g_a, g_b, iv_a, iv_b, segs, n_segs, n_iv_a, flip, band, dist, ops, n_ops, first);
 }
 
 extern "C" int nts_graph_budget(nts_ctx* ctx, uint64_t bytes)

@@ -54,6 +54,9 @@ FSITE_DTYPE = np.dtype([(n, "<u4") for n in ("family", "rec", "first", "last", "
 SEGMENT_DTYPE = np.dtype([("iv_a", "<u4"), ("x", "<u4"), ("dx", "<u4"), ("y_lo", "<u4"), ("dy", "<i4"), ("kind", "<u4")])
 IDENTITY_DTYPE = np.dtype([(n, "<u8") for n in ("aligned_a", "aligned_b", "edits")] +
                           [(n, "<u4") for n in ("segments", "aligned", "backward", "too_long", "offband", "invalid", "overband", "reserved")])
+# nts_edit_op: what Context.edit_script returns, one per edit
+OP_DTYPE = np.dtype([("seg", "<u4"), ("p", "<u4"), ("q", "<u4"), ("op", "u1"), ("base_a", "u1"), ("base_b", "u1"), ("pad", "u1")])
+OP_SUB, OP_DEL, OP_INS = 1, 2, 3
 SEG_CANDIDATE, SEG_BACKWARD, SEG_LONG, SEG_OFFBAND = 0, 1, 2, 3
 EDIT_NOT_CANDIDATE, EDIT_PASSED, EDIT_OVERBAND, EDIT_INVALID = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD, 0xFFFFFFFC
 NO_MATE = 0xFFFFFFFF
@@ -254,6 +257,31 @@ class Context:
                                               iva.size, fl.ctypes.data if fl.size else None, int(band), out.ctypes.data if out.size else None,
                                               dist.ctypes.data if with_distances and dist.size else None), "nts_edit_segments")
         return (out, dist) if with_distances else out
+
+    def edit_script(self, genome_a, genome_b, intervals_a, intervals_b, segments, flip, band, dist):
+        """the edits behind every segment's distance (nts_edit_script): the arguments of edit_segments and the per-segment results it
+        returns with with_distances.  Returns (ops, first): an OP_DTYPE array with the canonical script of every segment that has a
+        distance, one behind the other in segment order and each in path order, and first [n + 1] uint64 -- segment i's ops are
+        ops[first[i]:first[i + 1]].  op is OP_SUB / OP_DEL / OP_INS at offset p of string A and q of the oriented string B; base_a /
+        base_b are the codes of A[p] and of the oriented B[q], 0xFF where the op has none.  A dist that is not the segments' own is
+        refused.  Exact and deterministic."""
+        iva = Genome._interval_array(intervals_a)
+        ivb = Genome._interval_array(intervals_b)
+        seg = np.ascontiguousarray(segments, dtype=SEGMENT_DTYPE)
+        fl = np.ascontiguousarray(flip, dtype=np.uint8)
+        ds = np.ascontiguousarray(dist, dtype=np.uint32)
+        if ivb.size != iva.size or fl.shape != (iva.size,):
+            raise ValueError("edit_script: one interval of B and one flip per interval of A")
+        if ds.shape != (seg.size,):
+            raise ValueError("edit_script: one dist per segment")
+        assert OP_DTYPE.itemsize == ctypes.sizeof(_lib.EditOp)
+        first = np.zeros(seg.size + 1, dtype=np.uint64)
+        p, m = c_vp(), u64()
+        self.check(self.lib.nts_edit_script(self.h, genome_a.h, genome_b.h, ctypes.cast(iva.ctypes.data, ctypes.POINTER(Interval)),
+                                            ctypes.cast(ivb.ctypes.data, ctypes.POINTER(Interval)), seg.ctypes.data if seg.size else None, seg.size,
+                                            iva.size, fl.ctypes.data if fl.size else None, int(band), ds.ctypes.data if ds.size else None,
+                                            ctypes.byref(p), ctypes.byref(m), first.ctypes.data), "nts_edit_script")
+        return self._take(p, m.value, OP_DTYPE), first
 
     def timing(self, name):
         ms, n = ctypes.c_double(), u64()

@@ -497,7 +497,7 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         benchmark=False, log=print, ctx=None, backend=None, bf_rounding="up", bf_signature=BF_SIGNATURE, dev=False, interarrivals=False, repeat=False,
         mx_tsvs=None, common_file=None, m=90, n=0, initial_only=False, write_fai=True, engine="device", refine_repeat_file=None, screen_repeat_file=None,
         graph_budget=None, assess=None, gaps=False, gap_links=None, gap_block_links=False, gap_copies=None, gap_copy_sites=None,
-        gap_periods=None, gap_families=None, block_identity=None):
+        gap_periods=None, gap_families=None, block_identity=None, block_variants=None):
     """FASTA paths -> engine (outputs in .outputs and in the CWD).  Mirrors oracle.synteny_oracle.run_pipeline's
     signature so the parity tests read alike.  Under torch.distributed (WORLD_SIZE > 1, process group already
     initialised by the caller) genomes are sharded over the ranks.
@@ -522,7 +522,10 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
     tandem array in each gap, from an unfiltered sample of its own: it shares nothing with the sampling above, so the rate is its
     own).  gap_families = step: needs gap_periods, whose rate and min_hits it shares; after that file, <prefix>.gap_families.tsv and
     <prefix>.gap_family_sites.tsv (gaps.families: the arrays that share the hashes carrying their period, and where each genome holds
-    each such family; the unfiltered sampling of gap_periods serves both stages)."""
+    each such family; the unfiltered sampling of gap_periods serves both stages).  block_identity = (k, rate, band, max_len): after
+    the final block table (and assess), <prefix>.block_identity.tsv (assess.block_identity; one rank only).  block_variants = the same
+    four: behind it, <prefix>.block_variants.tsv (assess.block_variants: the edits behind the identity table's `edits`); with both,
+    the parameters are the same and one pass serves both files."""
     prefix = prefix or f"ntSynt.k{k}.w{w}"
     if mx_tsvs is not None and len(mx_tsvs) != len(fastas):
         raise ValueError("one minimizer TSV per FASTA file")
@@ -556,6 +559,14 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         from .assess import check_identity_parameters
         if check_identity_parameters(*(int(x) for x in block_identity)):
             raise ValueError("block_identity = (k, rate, band, max_len): " + check_identity_parameters(*(int(x) for x in block_identity)))
+    if block_variants is not None:
+        if world > 1 or (mx_tsvs is not None and initial_only):
+            raise ValueError("block_variants needs every genome resident on one GPU (one rank, genomes loaded)")
+        from .assess import check_identity_parameters
+        if check_identity_parameters(*(int(x) for x in block_variants)):
+            raise ValueError("block_variants = (k, rate, band, max_len): " + check_identity_parameters(*(int(x) for x in block_variants)))
+        if block_identity is not None and tuple(int(x) for x in block_identity) != tuple(int(x) for x in block_variants):
+            raise ValueError("block_identity and block_variants take the same (k, rate, band, max_len)")
     if gap_block_links and gap_links is None:
         raise ValueError("gap_block_links needs gap_links = (rate, min_anchors)")
     if gap_block_links and len(fastas) > 32:
@@ -1093,14 +1104,30 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         st.start("block_identity")
         from . import assess as assess_
         i_args = tuple(int(x) for x in block_identity)
-        rows = assess_.block_identity(backend.ctx, {fa.basename(p): genomes[p] for p in fastas}, assess_.read_blocks(f"{prefix}.synteny_blocks.tsv"),
-                                      *i_args)
+        by_name, table_rows = {fa.basename(p): genomes[p] for p in fastas}, assess_.read_blocks(f"{prefix}.synteny_blocks.tsv")
+        if block_variants is not None:                        # (one pass gives both tables: the variants are written in their own stage)
+            rows, variant_rows = assess_.block_variants(backend.ctx, by_name, table_rows, *i_args)
+        else:
+            rows = assess_.block_identity(backend.ctx, by_name, table_rows, *i_args)
         text = assess_.identity_table(rows, *i_args)
         with open(f"{prefix}.block_identity.tsv", "w", encoding="utf-8") as fh:
             fh.write(text)
         eng.outputs[f"{prefix}.block_identity.tsv"] = text
         st.stop()
         st.mark("block_identity_done")
+    if block_variants is not None:
+        st.start("block_variants")
+        from . import assess as assess_
+        v_args = tuple(int(x) for x in block_variants)
+        if block_identity is None:
+            variant_rows = assess_.block_variants(backend.ctx, {fa.basename(p): genomes[p] for p in fastas},
+                                                  assess_.read_blocks(f"{prefix}.synteny_blocks.tsv"), *v_args)[1]
+        text = assess_.variants_table(variant_rows, *v_args)
+        with open(f"{prefix}.block_variants.tsv", "w", encoding="utf-8") as fh:
+            fh.write(text)
+        eng.outputs[f"{prefix}.block_variants.tsv"] = text
+        st.stop()
+        st.mark("block_variants_done")
     if gaps:
         st.start("gaps")
         from . import assess as assess_, gaps as gaps_
