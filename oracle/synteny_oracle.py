@@ -346,6 +346,7 @@ class SyntenyOracle:
                 if len(common) == 1:            # direct edge + exactly one 2-step path  (S:581-582)
                     doomed.append(common[0])
                     e[2] = wmax                 # in-loop mutation, visible to later edges (S:586)
+        self.last_doomed = doomed               # (bookkeeping for tests/engine_brute.py: one entry per bubble found)
         g = graph.copy()
         g.delete_vertices(doomed)
         return g
