@@ -703,6 +703,26 @@ int nts_edit_script(nts_ctx* ctx, const nts_genome* g_a, const nts_genome* g_b, 
                     const nts_iv_segment* segs, uint64_t n_segs, uint64_t n_iv_a, const uint8_t* flip, uint32_t band, const uint32_t* dist,
                     nts_edit_op** ops, uint64_t* n_ops, uint64_t* first);
 
+/* ---- the stretches a 31-diagonal band leaves out: the unrestricted distance up to max_edits edits -----------------
+ * nts_edit_wide: the arguments of nts_edit_segments, max_edits = E with 2 band + 1 <= E <= 1023 (NTS_EINVAL otherwise), and dist = that
+ *   call's dist_out for the same arguments; all of that call's checks on segments, intervals and flip are made here too.  The WORK SET:
+ *   segments of kind offband with |dy - dx| <= E (dist[i] = NTS_EDIT_PASSED) and candidates with dist[i] = NTS_EDIT_OVERBAND.  For a
+ *   segment of the work set dist_out[i] = NTS_EDIT_INVALID when either string holds a base that is not A, C, G or T, else with D the
+ *   unrestricted unit-cost edit distance of its two strings D when D <= E, else NTS_EDIT_OVERBAND; every other entry is dist[i] (an
+ *   offband segment with |dy - dx| > E stays NTS_EDIT_PASSED).  Everything the narrow pass aligns has D <= 2 band + 1 <= E, so after this
+ *   call a segment that is neither backward, long nor invalid has a distance exactly when D <= E.  per_iv_out (n_iv_a entries, all
+ *   written): the sums of nts_edit_segments over the FINAL results -- aligned = those with a D, offband = kind offband still passed,
+ *   overband = every final NTS_EDIT_OVERBAND of either kind.  dist_out (n_segs entries) may be NULL.  NTS_EINVAL before any launch: a
+ *   dist[i] that nts_edit_segments does not give a segment of that kind; an offband segment of the work set that leaves its interval
+ *   or has dx or dy outside 1..65535.  A selection over a counting iterator keeps the work set (timer "edit_wide_plan"); one 64-lane
+ *   wave per kept segment runs the furthest-reaching recurrence over all diagonals, two rows of 2 E + 3 entries in LDS (timer
+ *   "edit_wide"); an empty work set launches neither; the sums by nts_edit_segments' reduction (timer "edit_reduce").  On the
+ *   context's stream, in its workspace; no atomic, no launch per segment, no floating point: the same input gives the same bytes.
+ *   docs/design/04_18_block_identity_wide.md; csrc/nts_edit_wide.inc. */
+int nts_edit_wide(nts_ctx* ctx, const nts_genome* g_a, const nts_genome* g_b, const nts_interval* iv_a, const nts_interval* iv_b,
+                  const nts_iv_segment* segs, uint64_t n_segs, uint64_t n_iv_a, const uint8_t* flip, uint32_t band, uint32_t max_edits,
+                  const uint32_t* dist, nts_iv_identity* per_iv_out, uint32_t* dist_out);
+
 /* ---- C1-C5: minimizer graph -> collinear chains -----------------------------------------------------
  * replaces ntjoin_utils.read_minimizers' duplicate removal, filter_minimizers and build_graph
  * (call sites bin/ntsynt_synteny.py:607-612, 483, 539) and the path walk of Ntjoin.find_paths

@@ -194,8 +194,13 @@ def divergence_table(rows, k, s):
     return "\n".join(lines) + "\n"
 
 
-def check_identity_parameters(k, rate, band, max_len):
-    "the ranges of the four parameters of the block identity; the message of the first that is out of range, or None"
+WIDE_NOT_WITH_VARIANTS = ("--identity-max-edits does not go with the block variants: the scripts of the wide stretches (more than 31 diagonals off the "
+                          "main one) are not listed yet")
+
+
+def check_identity_parameters(k, rate, band, max_len, max_edits=0):
+    """the ranges of the parameters of the block identity; the message of the first that is out of range, or None.  max_edits: 0 = no wide
+    pass, else 2 band + 1 .. 1023 (everything the narrow pass aligns has at most 2 band + 1 edits)"""
     if k < 1:
         return "--identity-k must be positive"
     if rate < 1:
@@ -204,6 +209,8 @@ def check_identity_parameters(k, rate, band, max_len):
         return "--identity-band must lie in 1..31"
     if not 1 <= max_len <= 65535:
         return "--identity-max-len must lie in 1..65535"
+    if max_edits != 0 and not 2 * band + 1 <= max_edits <= 1023:
+        return f"--identity-max-edits must be 0 (off) or lie in 2 * --identity-band + 1 = {2 * band + 1}..1023"
     return None
 
 
@@ -301,20 +308,27 @@ def _identity_rows(blocks, pairs, length, found):
     return out
 
 
-def block_identity(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_RATE, band=IDENTITY_BAND, max_len=IDENTITY_MAX_LEN):
+def block_identity(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_RATE, band=IDENTITY_BAND, max_len=IDENTITY_MAX_LEN, max_edits=0):
     """Per block and unordered pair of its lines (a before b in file order) the exact edit distance between consecutive anchors.
     genomes_by_name: the name in column 2 -> resident device.Genome, or a callable that returns one: it is called once, and the genome
     is freed after the last pair that needs it (both genomes of a pair are resident at once).  blocks: read_blocks' rows.  Returns
     dicts of integers and names (identity_row formats one): block ids ascending, pairs in the order of the block's lines.  One
     nts_sample_intervals per genome over all its lines; per ordered pair of genomes one nts_iv_anchor_segments and one
-    nts_edit_segments for every round of pairs in which no line of the first genome occurs twice."""
-    message = check_identity_parameters(int(k), int(rate), int(band), int(max_len))
+    nts_edit_segments for every round of pairs in which no line of the first genome occurs twice.  max_edits = E > 0: behind each of
+    them one nts_edit_wide on its per-segment results -- the stretches the band leaves out (offband with |dy - dx| <= E, overband) get
+    their unrestricted distance where it is at most E, and the sums are those over the final results
+    (docs/design/04_18_block_identity_wide.md)."""
+    message = check_identity_parameters(int(k), int(rate), int(band), int(max_len), int(max_edits))
     if message:
         raise ValueError(message)
-    k, rate, band, max_len = int(k), int(rate), int(band), int(max_len)
+    k, rate, band, max_len, max_edits = int(k), int(rate), int(band), int(max_len), int(max_edits)
     pairs, length, found = [], {}, {}
     for r in _identity_rounds(ctx, genomes_by_name, blocks, k, rate, band, max_len, pairs, length):
-        per_iv = ctx.edit_segments(r.g_a, r.g_b, r.iv_a, r.iv_b, r.segs, r.flip, band)
+        if max_edits > 0:
+            _, dist = ctx.edit_segments(r.g_a, r.g_b, r.iv_a, r.iv_b, r.segs, r.flip, band, with_distances=True)
+            per_iv, _ = ctx.edit_wide(r.g_a, r.g_b, r.iv_a, r.iv_b, r.segs, r.flip, band, max_edits, dist)
+        else:
+            per_iv = ctx.edit_segments(r.g_a, r.g_b, r.iv_a, r.iv_b, r.segs, r.flip, band)
         for la, lb, i in r.lines:
             found[(la, lb)] = (int(r.anchors[i]), per_iv[i])
     return _identity_rows(blocks, pairs, length, found)
@@ -410,10 +424,10 @@ def identity_row(r):
     return "\t".join(str(shown[c]) for c in IDENTITY_COLUMNS)
 
 
-def identity_table(rows, k, rate, band, max_len):
-    "TSV with a header, one line per block and pair of its lines, then `# k K, rate R, band W, max_len L`"
+def identity_table(rows, k, rate, band, max_len, max_edits=0):
+    "TSV with a header, one line per block and pair of its lines, then `# k K, rate R, band W, max_len L` -- and `, max_edits E` for E > 0"
     lines = ["\t".join(IDENTITY_COLUMNS)] + [identity_row(r) for r in rows]
-    lines.append(f"# k {int(k)}, rate {int(rate)}, band {int(band)}, max_len {int(max_len)}")
+    lines.append(f"# k {int(k)}, rate {int(rate)}, band {int(band)}, max_len {int(max_len)}" + (f", max_edits {int(max_edits)}" if int(max_edits) else ""))
     return "\n".join(lines) + "\n"
 
 
@@ -437,6 +451,8 @@ def main(argv=None):
     p.add_argument("--identity-band", help=f"half-width of the alignment band, 1..31 [{IDENTITY_BAND}]", type=int, default=IDENTITY_BAND)
     p.add_argument("--identity-max-len", help=f"longest stretch between two anchors that is aligned, 1..65535 [{IDENTITY_MAX_LEN}]", type=int,
                    default=IDENTITY_MAX_LEN)
+    p.add_argument("--identity-max-edits", help="with --identity-out: also align the stretches the band leaves out (indels of 32 bases or more), up to this "
+                   "many edits: 0 = off, else 2 * --identity-band + 1 .. 1023; not with --variants-out [0]", type=int, default=0)
     p.add_argument("--device", help="GPU index [0]", type=int, default=0)
     args = p.parse_args(argv)
     if args.k < 1 or args.s < 1:
@@ -444,9 +460,11 @@ def main(argv=None):
     if args.identity_out or args.variants_out:
         if not args.fastas:
             p.error(("--identity-out" if args.identity_out else "--variants-out") + " needs the genomes: --fastas")
-        message = check_identity_parameters(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len)
+        message = check_identity_parameters(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits)
         if message:
             p.error(message)
+        if args.identity_max_edits and args.variants_out:
+            p.error(WIDE_NOT_WITH_VARIANTS)
     print(stats_table(block_stats(args.tsv, args.fai)), end="")
     if not args.fastas:
         return 0
@@ -465,10 +483,10 @@ def main(argv=None):
             with open(args.variants_out, "w", encoding="utf-8") as fh:
                 fh.write(variants_table(var_rows, *id_args))
         elif args.identity_out:
-            id_rows = block_identity(ctx, loaders, read_blocks(args.tsv), *id_args)
+            id_rows = block_identity(ctx, loaders, read_blocks(args.tsv), *id_args, max_edits=args.identity_max_edits)
         if args.identity_out:
             with open(args.identity_out, "w", encoding="utf-8") as fh:
-                fh.write(identity_table(id_rows, *id_args))
+                fh.write(identity_table(id_rows, *id_args, max_edits=args.identity_max_edits))
     finally:
         ctx.close()
     if args.divergence_out:

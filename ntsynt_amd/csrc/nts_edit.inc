@@ -197,6 +197,25 @@ int edit_prepare(nts_ctx* ctx, const nts_genome* ga, const nts_genome* gb, const
   return NTS_OK;
 }
 
+// the sums per interval of what `kinds` makes of every segment: one reduction by key over iv_a (segments arrive in iv_a order), stored at
+// out[iv_a].  nts_edit_segments and nts_edit_wide (csrc/nts_edit_wide.inc) differ in the kinds kernel alone.
+using EditKinds = void (*)(const nts_iv_segment*, const uint32_t*, uint64_t, nts_iv_identity*);
+
+hipError_t edit_sums(nts_ctx* ctx, EditKinds kinds, const nts_iv_segment* d_seg, const uint32_t* d_dist, uint64_t n, uint64_t n_iv, nts_iv_identity* d_agg,
+                     nts_iv_identity* d_uagg, uint32_t* d_uiv, uint64_t* d_num, nts_iv_identity* d_out)
+{
+  ScopedTimer t(ctx, "edit_reduce");
+  NTS_LAUNCH(kinds, IVL_GRID(n), d_seg, d_dist, n, d_agg);
+  auto keys = rocprim::make_transform_iterator(d_seg, EditIvOf());
+  size_t tmp = 0;
+  hipError_t e = rocprim::reduce_by_key(nullptr, tmp, keys, d_agg, n, d_uiv, d_uagg, d_num, EditAdd(), rocprim::equal_to<uint32_t>(), ctx->stream);
+  void* d_tmp = e == hipSuccess ? ws_get(ctx, "ivs_tmp", std::max<size_t>(tmp, 16)) : nullptr;
+  if (e == hipSuccess && !d_tmp) e = hipErrorOutOfMemory;
+  if (e == hipSuccess) e = rocprim::reduce_by_key(d_tmp, tmp, keys, d_agg, n, d_uiv, d_uagg, d_num, EditAdd(), rocprim::equal_to<uint32_t>(), ctx->stream);
+  if (e == hipSuccess) NTS_LAUNCH(k_edit_store, IVL_GRID(n), (const uint32_t*)d_uiv, (const nts_iv_identity*)d_uagg, (const uint64_t*)d_num, n, n_iv, d_out);
+  return e;
+}
+
 int edit_segments_run(nts_ctx* ctx, const nts_genome* ga, const nts_genome* gb, const nts_interval* iv_a, const nts_interval* iv_b,
                       const nts_iv_segment* segs, uint64_t n, uint64_t n_iv, const uint8_t* flip, uint32_t band, nts_iv_identity* per_iv,
                       uint32_t* dist_out)
@@ -223,20 +242,7 @@ int edit_segments_run(nts_ctx* ctx, const nts_genome* ga, const nts_genome* gb, 
     NTS_LAUNCH(k_edit_wave, dim3((uint32_t)((n + EDIT_WAVES - 1) / EDIT_WAVES)), dim3(EDIT_WAVES * 64), 0, ctx->stream, (const uint8_t*)ga->d_code + PAD,
                (const uint8_t*)gb->d_code + PAD, (const EditIv*)d_ivs, n_iv, (const nts_iv_segment*)d_seg, n, band, d_dist);
   }
-  hipError_t e_reduce = hipSuccess;
-  {
-    ScopedTimer t(ctx, "edit_reduce");
-    NTS_LAUNCH(k_edit_kinds, IVL_GRID(n), (const nts_iv_segment*)d_seg, (const uint32_t*)d_dist, n, d_agg);
-    auto keys = rocprim::make_transform_iterator((const nts_iv_segment*)d_seg, EditIvOf());
-    size_t tmp = 0;
-    e_reduce = rocprim::reduce_by_key(nullptr, tmp, keys, d_agg, n, d_uiv, d_uagg, d_num, EditAdd(), rocprim::equal_to<uint32_t>(), ctx->stream);
-    void* d_tmp = e_reduce == hipSuccess ? ws_get(ctx, "ivs_tmp", std::max<size_t>(tmp, 16)) : nullptr;
-    if (e_reduce == hipSuccess && !d_tmp) e_reduce = hipErrorOutOfMemory;
-    if (e_reduce == hipSuccess)
-      e_reduce = rocprim::reduce_by_key(d_tmp, tmp, keys, d_agg, n, d_uiv, d_uagg, d_num, EditAdd(), rocprim::equal_to<uint32_t>(), ctx->stream);
-    if (e_reduce == hipSuccess)
-      NTS_LAUNCH(k_edit_store, IVL_GRID(n), (const uint32_t*)d_uiv, (const nts_iv_identity*)d_uagg, (const uint64_t*)d_num, n, n_iv, d_out);
-  }
+  hipError_t e_reduce = edit_sums(ctx, k_edit_kinds, d_seg, d_dist, n, n_iv, d_agg, d_uagg, d_uiv, d_num, d_out);
   if (e_reduce == hipSuccess) e_reduce = hipGetLastError();
   if (e_reduce == hipSuccess) e_reduce = hipMemcpyAsync(per_iv, d_out, n_iv * sizeof(nts_iv_identity), hipMemcpyDeviceToHost, ctx->stream);
   if (e_reduce == hipSuccess && dist_out) e_reduce = hipMemcpyAsync(dist_out, d_dist, n * 4, hipMemcpyDeviceToHost, ctx->stream);

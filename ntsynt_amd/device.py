@@ -283,6 +283,30 @@ class Context:
                                             ctypes.byref(p), ctypes.byref(m), first.ctypes.data), "nts_edit_script")
         return self._take(p, m.value, OP_DTYPE), first
 
+    def edit_wide(self, genome_a, genome_b, intervals_a, intervals_b, segments, flip, band, max_edits, dist):
+        """the stretches the band leaves out (nts_edit_wide): the arguments of edit_segments, max_edits = E in 2 band + 1 .. 1023 and the
+        per-segment results edit_segments returns with with_distances.  The unrestricted edit distance of every offband segment with
+        |dy - dx| <= E and of every candidate that came back EDIT_OVERBAND: the distance where it is at most E, else EDIT_OVERBAND, or
+        EDIT_INVALID; every other entry as it was.  Returns (an IDENTITY_DTYPE array over the final results, one entry per interval of
+        A; the final per-segment results [n] uint32).  A dist that contradicts a segment's kind is refused.  Exact and deterministic."""
+        iva = Genome._interval_array(intervals_a)
+        ivb = Genome._interval_array(intervals_b)
+        seg = np.ascontiguousarray(segments, dtype=SEGMENT_DTYPE)
+        fl = np.ascontiguousarray(flip, dtype=np.uint8)
+        ds = np.ascontiguousarray(dist, dtype=np.uint32)
+        if ivb.size != iva.size or fl.shape != (iva.size,):
+            raise ValueError("edit_wide: one interval of B and one flip per interval of A")
+        if ds.shape != (seg.size,):
+            raise ValueError("edit_wide: one dist per segment")
+        assert IDENTITY_DTYPE.itemsize == ctypes.sizeof(_lib.IvIdentity)
+        out = np.zeros(iva.size, dtype=IDENTITY_DTYPE)
+        final = np.zeros(seg.size, dtype=np.uint32)
+        self.check(self.lib.nts_edit_wide(self.h, genome_a.h, genome_b.h, ctypes.cast(iva.ctypes.data, ctypes.POINTER(Interval)),
+                                          ctypes.cast(ivb.ctypes.data, ctypes.POINTER(Interval)), seg.ctypes.data if seg.size else None, seg.size,
+                                          iva.size, fl.ctypes.data if fl.size else None, int(band), int(max_edits), ds.ctypes.data if ds.size else None,
+                                          out.ctypes.data if out.size else None, final.ctypes.data if final.size else None), "nts_edit_wide")
+        return out, final
+
     def timing(self, name):
         ms, n = ctypes.c_double(), u64()
         self.check(self.lib.nts_timing(self.h, name.encode(), ctypes.byref(ms), ctypes.byref(n)), "nts_timing")

@@ -523,7 +523,9 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
     own).  gap_families = step: needs gap_periods, whose rate and min_hits it shares; after that file, <prefix>.gap_families.tsv and
     <prefix>.gap_family_sites.tsv (gaps.families: the arrays that share the hashes carrying their period, and where each genome holds
     each such family; the unfiltered sampling of gap_periods serves both stages).  block_identity = (k, rate, band, max_len): after
-    the final block table (and assess), <prefix>.block_identity.tsv (assess.block_identity; one rank only).  block_variants = the same
+    the final block table (and assess), <prefix>.block_identity.tsv (assess.block_identity; one rank only); a fifth entry max_edits > 0
+    adds the wide pass over the stretches the band leaves out (not together with block_variants; with `benchmark` the stage times gain the
+    device times block_identity:edit_segments / :edit_wide_plan / :edit_wide).  block_variants = the same
     four: behind it, <prefix>.block_variants.tsv (assess.block_variants: the edits behind the identity table's `edits`); with both,
     the parameters are the same and one pass serves both files."""
     prefix = prefix or f"ntSynt.k{k}.w{w}"
@@ -557,16 +559,21 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         if world > 1 or (mx_tsvs is not None and initial_only):
             raise ValueError("block_identity needs every genome resident on one GPU (one rank, genomes loaded)")
         from .assess import check_identity_parameters
+        if len(block_identity) not in (4, 5):
+            raise ValueError("block_identity = (k, rate, band, max_len[, max_edits])")
         if check_identity_parameters(*(int(x) for x in block_identity)):
-            raise ValueError("block_identity = (k, rate, band, max_len): " + check_identity_parameters(*(int(x) for x in block_identity)))
+            raise ValueError("block_identity = (k, rate, band, max_len[, max_edits]): " + check_identity_parameters(*(int(x) for x in block_identity)))
     if block_variants is not None:
         if world > 1 or (mx_tsvs is not None and initial_only):
             raise ValueError("block_variants needs every genome resident on one GPU (one rank, genomes loaded)")
         from .assess import check_identity_parameters
         if check_identity_parameters(*(int(x) for x in block_variants)):
             raise ValueError("block_variants = (k, rate, band, max_len): " + check_identity_parameters(*(int(x) for x in block_variants)))
-        if block_identity is not None and tuple(int(x) for x in block_identity) != tuple(int(x) for x in block_variants):
+        if block_identity is not None and tuple(int(x) for x in block_identity[:4]) != tuple(int(x) for x in block_variants):
             raise ValueError("block_identity and block_variants take the same (k, rate, band, max_len)")
+        if block_identity is not None and len(block_identity) == 5 and int(block_identity[4]):
+            from .assess import WIDE_NOT_WITH_VARIANTS
+            raise ValueError("block_identity with max_edits and block_variants: " + WIDE_NOT_WITH_VARIANTS)
     if gap_block_links and gap_links is None:
         raise ValueError("gap_block_links needs gap_links = (rate, min_anchors)")
     if gap_block_links and len(fastas) > 32:
@@ -1104,6 +1111,10 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         st.start("block_identity")
         from . import assess as assess_
         i_args = tuple(int(x) for x in block_identity)
+        wide_timers = ("edit_segments", "edit_wide_plan", "edit_wide") if benchmark and len(i_args) == 5 and i_args[4] else ()
+        if wide_timers:                                       # (device events around the calls of this stage only)
+            backend.ctx.profile(True)
+            before = {name: backend.ctx.timing(name)[0] for name in wide_timers}
         by_name, table_rows = {fa.basename(p): genomes[p] for p in fastas}, assess_.read_blocks(f"{prefix}.synteny_blocks.tsv")
         if block_variants is not None:                        # (one pass gives both tables: the variants are written in their own stage)
             rows, variant_rows = assess_.block_variants(backend.ctx, by_name, table_rows, *i_args)
@@ -1114,6 +1125,9 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
             fh.write(text)
         eng.outputs[f"{prefix}.block_identity.tsv"] = text
         st.stop()
+        if wide_timers:
+            st.rows += [(f"block_identity:{name}", (backend.ctx.timing(name)[0] - before[name]) * 1e-3) for name in wide_timers]
+            backend.ctx.profile(False)
         st.mark("block_identity_done")
     if block_variants is not None:
         st.start("block_variants")
