@@ -723,6 +723,31 @@ int nts_edit_wide(nts_ctx* ctx, const nts_genome* g_a, const nts_genome* g_b, co
                   const nts_iv_segment* segs, uint64_t n_segs, uint64_t n_iv_a, const uint8_t* flip, uint32_t band, uint32_t max_edits,
                   const uint32_t* dist, nts_iv_identity* per_iv_out, uint32_t* dist_out);
 
+/* ---- which edits the distance of a stretch beyond the band consists of: block wide variants ---------------------
+ * nts_edit_wide_script: the arguments of nts_edit_wide, dist = that call's dist_out for the same arguments, and table_budget.  The
+ *   SCRIPT SET, decided from dist and the segments alone: dist[i] < NTS_EDIT_INVALID and kind offband, or kind candidate with
+ *   D + |dy - dx| > 2 band + 1.  (A candidate with D + |dy - dx| <= 2 band + 1 is nts_edit_script's: it adds nothing here and its
+ *   `first` entries are equal.)  For every member the D = dist[i] >= 1 edits of the CANONICAL script nts_edit_script defines, the same
+ *   nts_edit_op, in path order, at first[i] .. first[i] + D - 1.  *ops (release with nts_free; NULL for none), n_ops = the members' sum
+ *   of D; first (n_segs + 1 host entries, may be NULL; all 0 for an empty script set).  NTS_EINVAL before any launch, with nothing
+ *   written: everything nts_edit_segments checks, max_edits outside 2 band + 1 .. 1023; an offband member that leaves its interval or
+ *   has dx or dy outside 1..65535; a distance on a kind that is neither candidate nor offband, or D > max_edits, or D < |dy - dx|, or
+ *   D = 0 on an offband segment; a
+ *   table_budget that is not 0 and below 4 (max_edits + 1)^2 bytes; NTS_ERANGE for 2^32 edits or more.  NTS_EINVAL after the launch,
+ *   with no ops returned, when some dist[i] is not the distance of member i ("dist is not the distance of segment ...", the smallest
+ *   such index) or a member's string holds a base that is not A, C, G or T.  A member's furthest-reaching table, rows e = 0 .. D as
+ *   int32 at e * e + d + e, (D + 1)^2 entries (4 MiB at D = 1023), lies in global memory; the tables of one launch share one block of at
+ *   most table_budget bytes (0 = 1 GiB) that is released when the call ends, the host cuts the script set in index order into batches that fit, one launch per batch, and
+ *   the result does not depend on the budget.  Two scans and a selection (timer "edit_wide_script_plan"), one 64-lane wave per member
+ *   (timer "edit_wide_script"); an empty script set launches nothing.  No atomic, no launch per segment, no floating point: the same
+ *   input gives the same bytes.  docs/design/04_19_block_wide_variants.md; csrc/nts_edit_wide_script.inc.
+ * nts_edit_wide_script_last_plan: the last such call on this context: members of the script set, bytes of all their tables, batches
+ *   (all 0 when nothing was launched); any pointer may be NULL. */
+int nts_edit_wide_script(nts_ctx* ctx, const nts_genome* g_a, const nts_genome* g_b, const nts_interval* iv_a, const nts_interval* iv_b,
+                         const nts_iv_segment* segs, uint64_t n_segs, uint64_t n_iv_a, const uint8_t* flip, uint32_t band, uint32_t max_edits,
+                         const uint32_t* dist, uint64_t table_budget, nts_edit_op** ops, uint64_t* n_ops, uint64_t* first);
+int nts_edit_wide_script_last_plan(nts_ctx* ctx, uint64_t* members, uint64_t* table_bytes, uint64_t* batches);
+
 /* ---- C1-C5: minimizer graph -> collinear chains -----------------------------------------------------
  * replaces ntjoin_utils.read_minimizers' duplicate removal, filter_minimizers and build_graph
  * (call sites bin/ntsynt_synteny.py:607-612, 483, 539) and the path walk of Ntjoin.find_paths

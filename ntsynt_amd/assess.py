@@ -12,7 +12,9 @@ Two things, both over `<prefix>.synteny_blocks.tsv`:
   nts_iv_anchor_segments, nts_edit_segments); docs/design/04_16_block_identity.md.
 * block_variants (`ntSynt --block-variants`, `ntsynt_block_stats --variants-out`): the edits behind those distances -- the canonical
   script of every aligned stretch (nts_edit_script), merged into snv / ins / del events in both genomes' coordinates;
-  docs/design/04_17_block_variants.md."""
+  docs/design/04_17_block_variants.md.
+* block_wide_variants (`ntSynt --block-wide-variants`, `ntsynt_block_stats --wide-variants-out`): the same list with the stretches the
+  band leaves out included (nts_edit_wide, nts_edit_wide_script), under --identity-max-edits; docs/design/04_19_block_wide_variants.md."""
 import os
 import re
 from collections import namedtuple
@@ -195,7 +197,10 @@ def divergence_table(rows, k, s):
 
 
 WIDE_NOT_WITH_VARIANTS = ("--identity-max-edits does not go with the block variants: the scripts of the wide stretches (more than 31 diagonals off the "
-                          "main one) are not listed yet")
+                          "main one) are not listed yet in block_variants.tsv -- --block-wide-variants (ntsynt_block_stats --wide-variants-out) writes a "
+                          "file of its own that holds them")
+WIDE_VARIANTS_NEED_E = ("the block wide variants list the stretches beyond the band and need --identity-max-edits E > 0 (2 * --identity-band + 1 .. 1023); "
+                        "--block-variants (ntsynt_block_stats --variants-out) lists the edits of the band alone")
 
 
 def check_identity_parameters(k, rate, band, max_len, max_edits=0):
@@ -364,6 +369,55 @@ def block_variants(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_RAT
     return _identity_rows(blocks, pairs, length, found), rows
 
 
+def block_wide_variants(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_RATE, band=IDENTITY_BAND, max_len=IDENTITY_MAX_LEN, max_edits=0):
+    """block_identity with max_edits = E > 0 and, from the same pass, the edits behind every pair's `edits`, those of the stretches the
+    band leaves out included: returns (identity rows under E, variant rows).  Per round nts_edit_segments with the per-segment
+    distances, nts_edit_wide on them, nts_edit_script on the narrow distances and nts_edit_wide_script on the final ones; a segment's
+    ops come from exactly one of the two script calls.  A pair's ops, in segment order, become events through variant_events, as
+    block_variants makes them.  docs/design/04_19_block_wide_variants.md."""
+    import numpy as np
+    if int(max_edits) == 0:
+        raise ValueError("block_wide_variants lists the stretches beyond the band and needs max_edits (--identity-max-edits) > 0; "
+                         "block_variants (--block-variants) lists the edits of the band alone")
+    message = check_identity_parameters(int(k), int(rate), int(band), int(max_len), int(max_edits))
+    if message:
+        raise ValueError(message)
+    k, rate, band, max_len, max_edits = int(k), int(rate), int(band), int(max_len), int(max_edits)
+    pairs, length, found, events = [], {}, {}, {}
+    for r in _identity_rounds(ctx, genomes_by_name, blocks, k, rate, band, max_len, pairs, length):
+        _, dist = ctx.edit_segments(r.g_a, r.g_b, r.iv_a, r.iv_b, r.segs, r.flip, band, with_distances=True)
+        per_iv, final = ctx.edit_wide(r.g_a, r.g_b, r.iv_a, r.iv_b, r.segs, r.flip, band, max_edits, dist)
+        ops_n, first_n = ctx.edit_script(r.g_a, r.g_b, r.iv_a, r.iv_b, r.segs, r.flip, band, dist)
+        ops_w, first_w = ctx.edit_wide_script(r.g_a, r.g_b, r.iv_a, r.iv_b, r.segs, r.flip, band, max_edits, final)
+        n_n, n_w = np.diff(first_n.astype(np.int64)), np.diff(first_w.astype(np.int64))
+        if np.any((n_n > 0) & (n_w > 0)):
+            raise RuntimeError("a segment has ops from both script calls")
+        for la, lb, i in r.lines:
+            found[(la, lb)] = (int(r.anchors[i]), per_iv[i])
+            s0, s1 = (int(x) for x in np.searchsorted(r.segs["iv_a"], [i, i + 1]))          # (the segments come in iv_a order)
+            parts = [ops_w[int(first_w[s]):int(first_w[s + 1])] if n_w[s] else ops_n[int(first_n[s]):int(first_n[s + 1])]
+                     for s in range(s0, s1) if n_w[s] or n_n[s]]
+            mine = np.concatenate(parts) if parts else ops_n[:0]
+            if mine.size != int(per_iv[i]["edits"]):
+                raise RuntimeError(f"block {blocks[la].block_id}: {mine.size} ops for {int(per_iv[i]['edits'])} edits")
+            events[(la, lb)] = variant_events(mine, r.segs, int(r.iv_a[i][1]), int(r.iv_b[i][1]), length[lb], bool(r.flip[i]))
+    rows = []
+    for la, lb in pairs:
+        ra, rb = blocks[la], blocks[lb]
+        head = {"block_id": ra.block_id, "genome_a": ra.genome, "contig_a": ra.contig, "genome_b": rb.genome, "contig_b": rb.contig,
+                "orientation": "+" if ra.strand == rb.strand else "-"}
+        rows += [dict(head, **e) for e in events[(la, lb)]]
+    return _identity_rows(blocks, pairs, length, found), rows
+
+
+def wide_variants_table(rows, k, rate, band, max_len, max_edits):
+    """TSV of block_wide_variants' variant rows: the columns and the order of variants_table, every event of every aligned stretch,
+    narrow and wide, then `# k K, rate R, band W, max_len L, max_edits E`"""
+    lines = ["\t".join(VARIANT_COLUMNS)] + [variant_row(r) for r in rows]
+    lines.append(f"# k {int(k)}, rate {int(rate)}, band {int(band)}, max_len {int(max_len)}, max_edits {int(max_edits)}")
+    return "\n".join(lines) + "\n"
+
+
 def variant_events(ops, segs, start_a, start_b, len_b, flipped):
     """The events of one pair of lines.  ops: OP_DTYPE entries in script order whose `seg` indexes segs (SEGMENT_DTYPE); start_a /
     start_b: the clipped interval starts within their records, len_b: B's clipped length.  A maximal run of adjacent DEL ops with
@@ -446,25 +500,31 @@ def main(argv=None):
     p.add_argument("--identity-out", help="with --fastas: file for the per-block identity table (exact edit distance between anchors; GPU)")
     p.add_argument("--variants-out", help="with --fastas: file for the per-block variants table (the edits behind the identity table's `edits`, as snv / ins / "
                    "del events in both genomes' coordinates; GPU); it takes the --identity-* parameters")
+    p.add_argument("--wide-variants-out", help="with --fastas and --identity-max-edits E > 0: file for the complete per-block variants table, the events of "
+                   "the stretches the band leaves out (indels of 32 bases or more) included; GPU; it takes the --identity-* parameters")
     p.add_argument("--identity-k", help=f"k-mer size of the anchors [{IDENTITY_K}]", type=int, default=IDENTITY_K)
     p.add_argument("--identity-rate", help=f"sample one in this many k-mers as anchor candidates [{IDENTITY_RATE}]", type=int, default=IDENTITY_RATE)
     p.add_argument("--identity-band", help=f"half-width of the alignment band, 1..31 [{IDENTITY_BAND}]", type=int, default=IDENTITY_BAND)
     p.add_argument("--identity-max-len", help=f"longest stretch between two anchors that is aligned, 1..65535 [{IDENTITY_MAX_LEN}]", type=int,
                    default=IDENTITY_MAX_LEN)
-    p.add_argument("--identity-max-edits", help="with --identity-out: also align the stretches the band leaves out (indels of 32 bases or more), up to this "
-                   "many edits: 0 = off, else 2 * --identity-band + 1 .. 1023; not with --variants-out [0]", type=int, default=0)
+    p.add_argument("--identity-max-edits", help="with --identity-out or --wide-variants-out (which needs it): also align the stretches the band leaves "
+                   "out (indels of 32 bases or more), up to this many edits: 0 = off, else 2 * --identity-band + 1 .. 1023; not with "
+                   "--variants-out [0]", type=int, default=0)
     p.add_argument("--device", help="GPU index [0]", type=int, default=0)
     args = p.parse_args(argv)
     if args.k < 1 or args.s < 1:
         p.error("-k and -s must be positive")
-    if args.identity_out or args.variants_out:
+    if args.identity_out or args.variants_out or args.wide_variants_out:
         if not args.fastas:
-            p.error(("--identity-out" if args.identity_out else "--variants-out") + " needs the genomes: --fastas")
+            p.error(("--identity-out" if args.identity_out else "--variants-out" if args.variants_out else "--wide-variants-out") +
+                    " needs the genomes: --fastas")
         message = check_identity_parameters(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits)
         if message:
             p.error(message)
         if args.identity_max_edits and args.variants_out:
             p.error(WIDE_NOT_WITH_VARIANTS)
+        if args.wide_variants_out and not args.identity_max_edits:
+            p.error("--wide-variants-out: " + WIDE_VARIANTS_NEED_E)
     print(stats_table(block_stats(args.tsv, args.fai)), end="")
     if not args.fastas:
         return 0
@@ -482,6 +542,10 @@ def main(argv=None):
             id_rows, var_rows = block_variants(ctx, loaders, read_blocks(args.tsv), *id_args)
             with open(args.variants_out, "w", encoding="utf-8") as fh:
                 fh.write(variants_table(var_rows, *id_args))
+        elif args.wide_variants_out:                          # (one pass gives both tables)
+            id_rows, var_rows = block_wide_variants(ctx, loaders, read_blocks(args.tsv), *id_args, max_edits=args.identity_max_edits)
+            with open(args.wide_variants_out, "w", encoding="utf-8") as fh:
+                fh.write(wide_variants_table(var_rows, *id_args, args.identity_max_edits))
         elif args.identity_out:
             id_rows = block_identity(ctx, loaders, read_blocks(args.tsv), *id_args, max_edits=args.identity_max_edits)
         if args.identity_out:

@@ -75,12 +75,16 @@ def build_parser():
     p.add_argument("--block-variants", help="after the run, write <prefix>.block_variants.tsv: the edits behind the `edits` of --block-identity, as snv /\n"
                    "ins / del events in both genomes' coordinates; works with or without --block-identity and takes the --identity-* parameters",
                    action="store_true")
+    p.add_argument("--block-wide-variants", help="after the run, write <prefix>.block_wide_variants.tsv: the complete list of edits behind the `edits` of\n"
+                   "--block-identity --identity-max-edits E, the large insertions and deletions of the stretches the band leaves out included;\n"
+                   "needs --identity-max-edits E > 0, works with or without --block-identity", action="store_true")
     p.add_argument("--identity-k", help="k-mer size of the anchors [21]", type=int, default=21)
     p.add_argument("--identity-rate", help="sample one in this many k-mers as anchor candidates [16]", type=int, default=16)
     p.add_argument("--identity-band", help="half-width of the alignment band, 1..31 [31]", type=int, default=31)
     p.add_argument("--identity-max-len", help="longest stretch between two anchors that is aligned, 1..65535 [4096]", type=int, default=4096)
-    p.add_argument("--identity-max-edits", help="with --block-identity: also align the stretches the band leaves out (indels of 32 bases or more), up to\n"
-                   "this many edits: 0 = off, else 2 * --identity-band + 1 .. 1023; not with --block-variants [0]", type=int, default=0)
+    p.add_argument("--identity-max-edits", help="with --block-identity or --block-wide-variants (which needs it): also align the stretches the band\n"
+                   "leaves out (indels of 32 bases or more), up to this many edits: 0 = off, else 2 * --identity-band + 1 .. 1023;\n"
+                   "not with --block-variants [0]", type=int, default=0)
     p.add_argument("--gaps", help="after the run, write <prefix>.gaps.tsv (every stretch of every genome outside the blocks: its N bases and the\n"
                    "share of its k-mers that every genome has, from the common Bloom filter still on the GPU) and <prefix>.gap_summary.tsv",
                    action="store_true")
@@ -180,16 +184,23 @@ def check_reports(parser, args):
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             parser.error("--block-variants works from the genomes resident on one GPU: run it on one rank, or assess the finished run with "
                          "ntsynt_block_stats --tsv <prefix>.synteny_blocks.tsv --fai ... --fastas ... --variants-out <prefix>.block_variants.tsv")
-    if args.block_identity or args.block_variants:
+    if args.block_wide_variants:
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            parser.error("--block-wide-variants works from the genomes resident on one GPU: run it on one rank, or assess the finished run with "
+                         "ntsynt_block_stats --tsv <prefix>.synteny_blocks.tsv --fai ... --fastas ... --identity-max-edits E "
+                         "--wide-variants-out <prefix>.block_wide_variants.tsv")
+    if args.block_identity or args.block_variants or args.block_wide_variants:
         if args.block_identity and int(os.environ.get("WORLD_SIZE", "1")) > 1:
             parser.error("--block-identity works from the genomes resident on one GPU: run it on one rank, or assess the finished run with "
                          "ntsynt_block_stats --tsv <prefix>.synteny_blocks.tsv --fai ... --fastas ... --identity-out <prefix>.block_identity.tsv")
-        from .assess import WIDE_NOT_WITH_VARIANTS, check_identity_parameters
+        from .assess import WIDE_NOT_WITH_VARIANTS, WIDE_VARIANTS_NEED_E, check_identity_parameters
         message = check_identity_parameters(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits)
         if message:
             parser.error(message)
         if args.identity_max_edits and args.block_variants:
             parser.error(WIDE_NOT_WITH_VARIANTS)
+        if args.block_wide_variants and not args.identity_max_edits:
+            parser.error("--block-wide-variants: " + WIDE_VARIANTS_NEED_E)
     if args.gap_block_links:
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             parser.error("--gap-block-links works from the genomes resident on one GPU: run it on one rank, or report on the finished run with "
@@ -289,6 +300,7 @@ def main(argv=None):
            ["indexlr x%d" % len(fastas), "ntsynt_synteny"] + (["assess"] if args.assess else []) + (["block_identity"] if args.block_identity else []) + \
            (["block_identity_wide (edit_wide_plan, edit_wide)"] if args.block_identity and args.identity_max_edits else []) + \
            (["block_variants"] if args.block_variants else []) + \
+           (["block_wide_variants (edit_script_plan, edit_script, edit_wide_script_plan, edit_wide_script)"] if args.block_wide_variants else []) + \
            (["gaps"] if args.gaps else []) + \
            (["gap_links"] if args.gap_links else []) + (["gap_block_links"] if args.gap_block_links else []) + \
            (["gap_copies"] if args.gap_copies else []) + (["gap_copy_sites"] if args.gap_copy_sites else []) + \
@@ -348,7 +360,7 @@ def _run(pipeline, fastas, args, device, quiet):
                  indel=args.indel, merge=args.merge, block_size=args.block_size, common=not args.no_common,
                  simplify=not args.no_simplify_graph, device=device, benchmark=args.benchmark,
                  dev=args.dev, interarrivals=args.interarrivals, assess=(args.assess_k, args.assess_s) if args.assess else None,
-                 block_identity=((args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len) + ((args.identity_max_edits,) if args.identity_max_edits else ())) if args.block_identity else None, block_variants=(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len) if args.block_variants else None, gaps=args.gaps, gap_links=(args.gap_links_rate, args.gap_links_min) if args.gap_links else None, gap_block_links=args.gap_block_links, gap_copies=args.gap_links_rate if args.gap_copies else None, gap_copy_sites=(args.gap_sites_cap, args.gap_sites_step, args.gap_links_min) if args.gap_copy_sites else None, gap_periods=(args.gap_links_rate, args.gap_links_min) if args.gap_periods else None, gap_families=args.gap_sites_step if args.gap_families else None, repeat=args.repeat, bf_rounding=args.bf_rounding, bf_signature=args.bf_signature or pipeline.BF_SIGNATURE,
+                 block_identity=((args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len) + ((args.identity_max_edits,) if args.identity_max_edits else ())) if args.block_identity else None, block_variants=(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len) if args.block_variants else None, block_wide_variants=(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits) if args.block_wide_variants else None, gaps=args.gaps, gap_links=(args.gap_links_rate, args.gap_links_min) if args.gap_links else None, gap_block_links=args.gap_block_links, gap_copies=args.gap_links_rate if args.gap_copies else None, gap_copy_sites=(args.gap_sites_cap, args.gap_sites_step, args.gap_links_min) if args.gap_copy_sites else None, gap_periods=(args.gap_links_rate, args.gap_links_min) if args.gap_periods else None, gap_families=args.gap_sites_step if args.gap_families else None, repeat=args.repeat, bf_rounding=args.bf_rounding, bf_signature=args.bf_signature or pipeline.BF_SIGNATURE,
                  log=print if (args.dev and int(os.environ.get("RANK", "0")) == 0) else quiet)
 
 

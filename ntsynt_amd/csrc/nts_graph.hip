@@ -845,6 +845,7 @@ namespace {
 #include "nts_edit.inc"
 #include "nts_edit_script.inc"
 #include "nts_edit_wide.inc"
+#include "nts_edit_wide_script.inc"
 } // namespace
 
 extern "C" int nts_iv_links(nts_ctx* ctx, uint32_t n_lists, const nts_sample* const* lists, const uint64_t* n, uint32_t min_anchors, nts_iv_link** out,
@@ -954,6 +955,26 @@ extern "C" int nts_edit_wide(nts_ctx* ctx, const nts_genome* g_a, const nts_geno
     return fail(ctx, NTS_EINVAL, "nts_edit_wide: bad arguments (band 1..31, max_edits 2 band + 1..1023)");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   return edit_wide_run(ctx, g_a, g_b, iv_a, iv_b, segs, n_segs, n_iv_a, flip, band, max_edits, dist, per_iv_out, dist_out);
+}
+
+extern "C" int nts_edit_wide_script(nts_ctx* ctx, const nts_genome* g_a, const nts_genome* g_b, const nts_interval* iv_a, const nts_interval* iv_b,
+                                    const nts_iv_segment* segs, uint64_t n_segs, uint64_t n_iv_a, const uint8_t* flip, uint32_t band, uint32_t max_edits,
+                                    const uint32_t* dist, uint64_t table_budget, nts_edit_op** ops, uint64_t* n_ops, uint64_t* first)
+{
+  if (!ctx || !g_a || !g_b || !ops || !n_ops || (n_segs && (!segs || !dist)) || (n_iv_a && (!iv_a || !iv_b || !flip)) || band < 1 || band > EDIT_MAX_BAND ||
+      max_edits < 2 * band + 1 || max_edits > WIDE_MAX_EDITS)
+    return fail(ctx, NTS_EINVAL, "nts_edit_wide_script: bad arguments (band 1..31, max_edits 2 band + 1..1023)");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return edit_wide_script_run(ctx, g_a, g_b, iv_a, iv_b, segs, n_segs, n_iv_a, flip, band, max_edits, dist, table_budget, ops, n_ops, first);
+}
+
+extern "C" int nts_edit_wide_script_last_plan(nts_ctx* ctx, uint64_t* members, uint64_t* table_bytes, uint64_t* batches)
+{
+  if (!ctx) return NTS_EINVAL;
+  if (members) *members = ctx->last_wscript_members;
+  if (table_bytes) *table_bytes = ctx->last_wscript_table_bytes;
+  if (batches) *batches = ctx->last_wscript_batches;
+  return NTS_OK;
 }
 
 extern "C" int nts_graph_budget(nts_ctx* ctx, uint64_t bytes)

@@ -13,3 +13,7 @@
 inline const char* nts_knob_off() { return nullptr; }
 #define NTS_KNOB(name) nts_knob_off()
 #endif
+
+// Fixed choices that are not switches.  The bytes nts_edit_wide_script's tables may take at once when the caller passes table_budget 0:
+// 1 GiB, a choice and not a measurement (docs/design/04_19_block_wide_variants.md).
+#define NTS_WIDE_SCRIPT_TABLE_BUDGET (1ull << 30)

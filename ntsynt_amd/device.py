@@ -307,6 +307,40 @@ class Context:
                                           out.ctypes.data if out.size else None, final.ctypes.data if final.size else None), "nts_edit_wide")
         return out, final
 
+    def edit_wide_script(self, genome_a, genome_b, intervals_a, intervals_b, segments, flip, band, max_edits, dist, table_budget=0):
+        """the edits of the stretches beyond the band (nts_edit_wide_script): the arguments of edit_wide and the final per-segment
+        results it returns.  The script set: every segment with a distance that edit_script does not take -- kind offband, or a
+        candidate with D + |dy - dx| > 2 band + 1.  Returns (ops, first) as edit_script does: the canonical script of every member in
+        an OP_DTYPE array, member i's ops at ops[first[i]:first[i + 1]]; every other segment adds nothing.  table_budget: the bytes the
+        members' furthest-reaching tables may take at once (0 = 1 GiB; at least 4 (max_edits + 1)^2); the result does not depend on it.
+        A dist that is not the segments' own is refused.  Exact and deterministic."""
+        iva = Genome._interval_array(intervals_a)
+        ivb = Genome._interval_array(intervals_b)
+        seg = np.ascontiguousarray(segments, dtype=SEGMENT_DTYPE)
+        fl = np.ascontiguousarray(flip, dtype=np.uint8)
+        ds = np.ascontiguousarray(dist, dtype=np.uint32)
+        if ivb.size != iva.size or fl.shape != (iva.size,):
+            raise ValueError("edit_wide_script: one interval of B and one flip per interval of A")
+        if ds.shape != (seg.size,):
+            raise ValueError("edit_wide_script: one dist per segment")
+        if int(table_budget) < 0:
+            raise ValueError("edit_wide_script: table_budget is a number of bytes, 0 for the default")
+        assert OP_DTYPE.itemsize == ctypes.sizeof(_lib.EditOp)
+        first = np.zeros(seg.size + 1, dtype=np.uint64)
+        p, m = c_vp(), u64()
+        self.check(self.lib.nts_edit_wide_script(self.h, genome_a.h, genome_b.h, ctypes.cast(iva.ctypes.data, ctypes.POINTER(Interval)),
+                                                 ctypes.cast(ivb.ctypes.data, ctypes.POINTER(Interval)), seg.ctypes.data if seg.size else None, seg.size,
+                                                 iva.size, fl.ctypes.data if fl.size else None, int(band), int(max_edits),
+                                                 ds.ctypes.data if ds.size else None, int(table_budget), ctypes.byref(p), ctypes.byref(m),
+                                                 first.ctypes.data), "nts_edit_wide_script")
+        return self._take(p, m.value, OP_DTYPE), first
+
+    def edit_wide_script_last_plan(self):
+        "dict(members, table_bytes, batches) of the last edit_wide_script on this context (nts_edit_wide_script_last_plan)"
+        a, b, c = u64(), u64(), u64()
+        self.check(self.lib.nts_edit_wide_script_last_plan(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "nts_edit_wide_script_last_plan")
+        return {"members": a.value, "table_bytes": b.value, "batches": c.value}
+
     def timing(self, name):
         ms, n = ctypes.c_double(), u64()
         self.check(self.lib.nts_timing(self.h, name.encode(), ctypes.byref(ms), ctypes.byref(n)), "nts_timing")

@@ -497,7 +497,7 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         benchmark=False, log=print, ctx=None, backend=None, bf_rounding="up", bf_signature=BF_SIGNATURE, dev=False, interarrivals=False, repeat=False,
         mx_tsvs=None, common_file=None, m=90, n=0, initial_only=False, write_fai=True, engine="device", refine_repeat_file=None, screen_repeat_file=None,
         graph_budget=None, assess=None, gaps=False, gap_links=None, gap_block_links=False, gap_copies=None, gap_copy_sites=None,
-        gap_periods=None, gap_families=None, block_identity=None, block_variants=None):
+        gap_periods=None, gap_families=None, block_identity=None, block_variants=None, block_wide_variants=None):
     """FASTA paths -> engine (outputs in .outputs and in the CWD).  Mirrors oracle.synteny_oracle.run_pipeline's
     signature so the parity tests read alike.  Under torch.distributed (WORLD_SIZE > 1, process group already
     initialised by the caller) genomes are sharded over the ranks.
@@ -527,7 +527,11 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
     adds the wide pass over the stretches the band leaves out (not together with block_variants; with `benchmark` the stage times gain the
     device times block_identity:edit_segments / :edit_wide_plan / :edit_wide).  block_variants = the same
     four: behind it, <prefix>.block_variants.tsv (assess.block_variants: the edits behind the identity table's `edits`); with both,
-    the parameters are the same and one pass serves both files."""
+    the parameters are the same and one pass serves both files.  block_wide_variants = (k, rate, band, max_len, max_edits > 0):
+    <prefix>.block_wide_variants.tsv (assess.block_wide_variants: every edit of every aligned stretch, those the band leaves out
+    included); with block_identity, which then takes the same five, one pass in the stage block_identity serves both files; not together
+    with block_variants; with `benchmark` the stage times gain block_wide_variants:edit_script_plan / :edit_script /
+    :edit_wide_script_plan / :edit_wide_script."""
     prefix = prefix or f"ntSynt.k{k}.w{w}"
     if mx_tsvs is not None and len(mx_tsvs) != len(fastas):
         raise ValueError("one minimizer TSV per FASTA file")
@@ -574,6 +578,21 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         if block_identity is not None and len(block_identity) == 5 and int(block_identity[4]):
             from .assess import WIDE_NOT_WITH_VARIANTS
             raise ValueError("block_identity with max_edits and block_variants: " + WIDE_NOT_WITH_VARIANTS)
+    if block_wide_variants is not None:
+        if world > 1 or (mx_tsvs is not None and initial_only):
+            raise ValueError("block_wide_variants needs every genome resident on one GPU (one rank, genomes loaded)")
+        from .assess import WIDE_VARIANTS_NEED_E, check_identity_parameters
+        if len(block_wide_variants) != 5:
+            raise ValueError("block_wide_variants = (k, rate, band, max_len, max_edits)")
+        if int(block_wide_variants[4]) == 0:
+            raise ValueError("block_wide_variants = (k, rate, band, max_len, max_edits): " + WIDE_VARIANTS_NEED_E)
+        if check_identity_parameters(*(int(x) for x in block_wide_variants)):
+            raise ValueError("block_wide_variants = (k, rate, band, max_len, max_edits): " + check_identity_parameters(*(int(x) for x in block_wide_variants)))
+        if block_variants is not None:
+            from .assess import WIDE_NOT_WITH_VARIANTS
+            raise ValueError("block_wide_variants and block_variants: " + WIDE_NOT_WITH_VARIANTS)
+        if block_identity is not None and tuple(int(x) for x in block_identity) != tuple(int(x) for x in block_wide_variants):
+            raise ValueError("block_identity and block_wide_variants take the same (k, rate, band, max_len, max_edits)")
     if gap_block_links and gap_links is None:
         raise ValueError("gap_block_links needs gap_links = (rate, min_anchors)")
     if gap_block_links and len(fastas) > 32:
@@ -1118,6 +1137,11 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         by_name, table_rows = {fa.basename(p): genomes[p] for p in fastas}, assess_.read_blocks(f"{prefix}.synteny_blocks.tsv")
         if block_variants is not None:                        # (one pass gives both tables: the variants are written in their own stage)
             rows, variant_rows = assess_.block_variants(backend.ctx, by_name, table_rows, *i_args)
+        elif block_wide_variants is not None:                 # (the same: its own timers belong to its own stage's rows)
+            wv_timers = ("edit_script_plan", "edit_script", "edit_wide_script_plan", "edit_wide_script") if benchmark else ()
+            wv_before = {name: backend.ctx.timing(name)[0] for name in wv_timers}
+            rows, wide_variant_rows = assess_.block_wide_variants(backend.ctx, by_name, table_rows, *i_args)
+            wv_times = [(f"block_wide_variants:{name}", (backend.ctx.timing(name)[0] - wv_before[name]) * 1e-3) for name in wv_timers]
         else:
             rows = assess_.block_identity(backend.ctx, by_name, table_rows, *i_args)
         text = assess_.identity_table(rows, *i_args)
@@ -1142,6 +1166,27 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         eng.outputs[f"{prefix}.block_variants.tsv"] = text
         st.stop()
         st.mark("block_variants_done")
+    if block_wide_variants is not None:
+        st.start("block_wide_variants")
+        from . import assess as assess_
+        w_args = tuple(int(x) for x in block_wide_variants)
+        if block_identity is None:
+            wv_timers = ("edit_script_plan", "edit_script", "edit_wide_script_plan", "edit_wide_script") if benchmark else ()
+            if wv_timers:                                     # (device events around the calls of this stage only)
+                backend.ctx.profile(True)
+            wv_before = {name: backend.ctx.timing(name)[0] for name in wv_timers}
+            wide_variant_rows = assess_.block_wide_variants(backend.ctx, {fa.basename(p): genomes[p] for p in fastas},
+                                                            assess_.read_blocks(f"{prefix}.synteny_blocks.tsv"), *w_args)[1]
+            wv_times = [(f"block_wide_variants:{name}", (backend.ctx.timing(name)[0] - wv_before[name]) * 1e-3) for name in wv_timers]
+            if wv_timers:
+                backend.ctx.profile(False)
+        text = assess_.wide_variants_table(wide_variant_rows, *w_args)
+        with open(f"{prefix}.block_wide_variants.tsv", "w", encoding="utf-8") as fh:
+            fh.write(text)
+        eng.outputs[f"{prefix}.block_wide_variants.tsv"] = text
+        st.stop()
+        st.rows += wv_times
+        st.mark("block_wide_variants_done")
     if gaps:
         st.start("gaps")
         from . import assess as assess_, gaps as gaps_
