@@ -205,6 +205,15 @@ int nts_bf_insert(nts_ctx* ctx, nts_bf* bf, const nts_genome* g, uint32_t k);
  * filter; small ones: one atomic OR per k-mer), 1 = always one atomic OR per k-mer, 2 = partitioned build whenever
  * the filter layout allows it (tests). */
 int nts_bf_build_mode(nts_ctx* ctx, int mode);
+/* The geometry of the partitioned build for n_valid k-mers of length k and a filter of `bytes` bytes, from the numbers alone (a host
+ * function, no GPU: the build itself calls it).  forced: build mode 2; and_mode: the build of nts_bf_insert_and.  Returns 0 when the
+ * partitioned build applies and 1 when it does not (no k-mers, 0xFF000000 k-mers or more, a filter beyond 2^37 bits, AND with
+ * k > 128, too small to pay for its passes unless forced); out[10] (zeros when it does not apply) = final buckets that hold filter
+ * bits F = ceil(bits / 2^19), log2_b2, B2 = 2^log2_b2 <= 512 level-2 buckets per level-1 bucket, B1 = ceil(F / B2) <= 512 level-1
+ * buckets, n_final = B1 * B2 final buckets launched (n_final - F < B2 of them lie behind the filter's end), cap1 residues per
+ * level-1 bucket, cap2 packed words per level-2 bucket, tiles of the first pass, tiles per level-1 bucket of the second, and
+ * idx32 = (B1 * cap1 < 2^32). */
+int nts_bf_bin_plan(uint64_t n_valid, uint64_t bytes, uint32_t k, int forced, int and_mode, uint64_t* out);
 int nts_bf_cascade(nts_ctx* ctx, const nts_bf* prev, nts_bf* next, const nts_genome* g, uint32_t k);
 /* the per-genome loop of the experimental repeat filter (bin/ntsynt_make_repeat_bfs.py:56-67; rule make_repeat_bf,
  * smk:65-72): `if genome_bf.contains(h): repeat_bf.insert(h) else: genome_bf.insert(h)` over every k-mer of g */
@@ -368,6 +377,10 @@ int nts_sketch_stats(nts_ctx* ctx, uint64_t* candidates, uint64_t* uncovered_ran
  * with a filter of the genome's own).  The Bloom figures are read at the next synchronising call on the filter
  * (nts_bf_popcount, nts_bf_download, nts_sync). */
 int nts_path_stats(nts_ctx* ctx, uint64_t* sketch_many_listed, uint64_t* bf_direct_indices, uint32_t* bf_list_fallback);
+/* Of the last partitioned Bloom build on this context (tests assert the shape a case was built for): the workgroups its first pass
+ * k_bin1 was launched with (min(tiles, 2 per CU); 0 when the build did not apply or k > 128 took the run-table walk), its level-1
+ * buckets B1 and log2 of its level-2 buckets per level-1 bucket (nts_bf_bin_plan). */
+int nts_bf_bin_last(nts_ctx* ctx, uint32_t* bin1_workgroups, uint32_t* B1, uint32_t* log2_b2);
 /* Of the last nts_bf_insert_and: whether the level went the literal way of src/ntsynt_make_common_bf.cpp:134-160 -- every k-mer of
  * the genome looked up in the running filter, the bits that were hit kept -- which the library chooses by itself once the running
  * filter is all but empty (its popcount known and below ~6 * 10^5 bits, where two folded tables in LDS answer most look-ups: what is

@@ -1036,27 +1036,37 @@ __global__ __launch_bounds__(256) void k_bin_late(const uint64_t* __restrict__ l
 
 constexpr uint64_t BIN_LATE_MIN = 1ull << 20; // entries of the list of bucket-bypassing indices: this, or one per 24 k-mers (1 GB at 3 Gbp)
 
-// returns NTS_OK when the binned build ran, 1 when it does not apply (caller uses the atomic kernel)
-// was_empty: no bit of the filter is set (a new or cleared filter: every build of the pipeline)
-// and_mode: 0 = OR into the filter, 1 = AND into it (BinLate), 2 = the same with the host's word that the filter holds few bits.
-// late_ctl (pinned host, 8 words; may be NULL): receives {dirty, -, count lo, count hi, popcount lo, popcount hi} behind the build (the
-// caller synchronises); word 6 is set at once: 1 = the popcount words will hold the filter's popcount (store-only / AND finish)
-int bf_insert_binned(nts_ctx* ctx, nts_bf* bf, const nts_genome* g, const GenomeTables& T, uint32_t k, bool forced, bool was_empty, int and_mode = 0,
-                     uint32_t* late_ctl = nullptr)
+// The geometry of a build: what bf_insert_binned launches with, from the numbers alone (exported as nts_bf_bin_plan for the CPU suite).
+struct BinPlan
 {
-  const RunTable& rt = T.rt;
-  const uint64_t V = rt.n_valid;
-  const uint64_t bits = bf->bytes * 8;
+  uint64_t F;        // final buckets that hold filter bits: ceil(bits / 2^BIN_FINAL_SHIFT)
+  uint32_t log2_b2;  // level-2 buckets per level-1 bucket (0: one partition level)
+  uint32_t B2, B1;   // B1 = ceil(F / B2) <= BIN_MAX_B1
+  uint64_t n_final;  // B1 * B2 >= F final buckets are launched; those from F on lie behind the filter's end and stay empty
+  uint64_t cap1;     // residues per level-1 bucket (a multiple of four)
+  uint64_t cap2;     // packed words per level-2 bucket (even; 0 with one level)
+  uint64_t tiles;    // k_bin1's tiles of KEY_TILE k-mers
+  uint64_t tiles2;   // k_bin2's tiles per level-1 bucket
+  uint32_t idx32;    // B1 * cap1 < 2^32: a residue's place in out1 is a 32-bit index
+};
+
+// returns 0 when the binned build applies to V valid k-mers and a filter of `bytes` bytes, 1 when it does not (V = 0 included: nothing to build)
+int bf_bin_plan(uint64_t V, uint64_t bytes, uint32_t k, bool forced, bool and_mode, BinPlan& p)
+{
+  p = BinPlan{};
+  if (V == 0 || bytes == 0 || bytes > (1ull << 60)) return 1;
+  const uint64_t bits = bytes * 8;
   const uint64_t F = (bits + (1ull << BIN_FINAL_SHIFT) - 1) >> BIN_FINAL_SHIFT; // final buckets
-  if (V == 0) return NTS_OK;
   if (V >= 0xFF000000ULL) return 1;                    // 32-bit bucket cursors
   if (!forced && (V < (1u << 22) || F < 64)) return 1; // too small to pay for three passes
   uint32_t log2_b2 = 0;
-  while ((F >> log2_b2) > BIN_MAX_B1) ++log2_b2;
+  // (the ceiling, as B1 below: F >> log2_b2 let F = 512 * 2^j + r, 0 < r < 2^j, through with 513 buckets for k_bin1's tables of 512)
+  while (log2_b2 <= BIN_MAX_LOG2_B2 && ((F + (1ull << log2_b2) - 1) >> log2_b2) > BIN_MAX_B1) ++log2_b2;
   if (log2_b2 > BIN_MAX_LOG2_B2) return 1;             // filter beyond 2^37 bits (17 GB)
   if (and_mode && k > FAST_K_MAX) return 1;            // (k_bin1_long sets every index directly)
   const uint32_t B2 = 1u << log2_b2;
   const uint32_t B1 = (uint32_t)((F + B2 - 1) >> log2_b2);
+  if (B1 > BIN_MAX_B1) return 1;                       // (k_bin1's s_cnt and s_gbase)
   const uint64_t n_final = (uint64_t)B1 << log2_b2;
   // capacities: mean + slack (uniform hashes: sigma ~ sqrt(mean)); what does not fit is OR-ed directly
   const uint64_t mean1 = V / B1 + 1, mean2 = V / F + 1;
@@ -1069,6 +1079,38 @@ int bf_insert_binned(nts_ctx* ctx, nts_bf* bf, const nts_genome* g, const Genome
   const uint64_t tiles = (V + KEY_TILE - 1) / KEY_TILE;
   const uint64_t tiles2 = (cap1 + KEY_TILE - 1) / KEY_TILE;
   if (tiles > 0x7FFFFFFFULL || tiles2 * (B1 + 8ull) > 0x7FFFFFFFULL || B1 > 65535 || n_final > 0x7FFFFFFFULL) return 1;
+  p.F = F;
+  p.log2_b2 = log2_b2;
+  p.B2 = B2;
+  p.B1 = B1;
+  p.n_final = n_final;
+  p.cap1 = cap1;
+  p.cap2 = cap2;
+  p.tiles = tiles;
+  p.tiles2 = tiles2;
+  p.idx32 = ((uint64_t)B1 * cap1 < (1ull << 32)) ? 1u : 0u;
+  return 0;
+}
+
+// returns NTS_OK when the binned build ran, 1 when it does not apply (caller uses the atomic kernel)
+// was_empty: no bit of the filter is set (a new or cleared filter: every build of the pipeline)
+// and_mode: 0 = OR into the filter, 1 = AND into it (BinLate), 2 = the same with the host's word that the filter holds few bits.
+// late_ctl (pinned host, 8 words; may be NULL): receives {dirty, -, count lo, count hi, popcount lo, popcount hi} behind the build (the
+// caller synchronises); word 6 is set at once: 1 = the popcount words will hold the filter's popcount (store-only / AND finish)
+int bf_insert_binned(nts_ctx* ctx, nts_bf* bf, const nts_genome* g, const GenomeTables& T, uint32_t k, bool forced, bool was_empty, int and_mode = 0,
+                     uint32_t* late_ctl = nullptr)
+{
+  const RunTable& rt = T.rt;
+  const uint64_t V = rt.n_valid;
+  if (V == 0) return NTS_OK;
+  BinPlan plan;
+  ctx->last_bin1_grid = 0;
+  if (bf_bin_plan(V, bf->bytes, k, forced, and_mode != 0, plan)) return 1;
+  ctx->last_bin_b1 = plan.B1;
+  ctx->last_bin_log2_b2 = plan.log2_b2;
+  const uint64_t bits = bf->bytes * 8;
+  const uint32_t log2_b2 = plan.log2_b2, B1 = plan.B1;
+  const uint64_t n_final = plan.n_final, cap1 = plan.cap1, cap2 = plan.cap2, tiles = plan.tiles, tiles2 = plan.tiles2;
   NTS_WS(d_cnt1, uint32_t*, "bin_cnt1", (uint64_t)B1 * BIN_CNT_STRIDE * 4);
   NTS_WS(d_out1, uint32_t*, "bin_out1", (uint64_t)B1 * cap1 * 4);
   uint32_t* d_cnt2 = nullptr;
@@ -1117,7 +1159,7 @@ int bf_insert_binned(nts_ctx* ctx, nts_bf* bf, const nts_genome* g, const Genome
   P.cnt1 = d_cnt1;
   P.out1 = d_out1;
   P.cap1 = (uint32_t)cap1;
-  P.idx32 = ((uint64_t)B1 * cap1 < (1ull << 32)) ? 1u : 0u;
+  P.idx32 = plan.idx32;
   P.late = late;
   ScopedTimer t(ctx, and_mode ? "bf_insert_and" : "bf_insert", true);
   if (k > FAST_K_MAX) {
@@ -1129,7 +1171,10 @@ int bf_insert_binned(nts_ctx* ctx, nts_bf* bf, const nts_genome* g, const Genome
       ctx->n_cus = (uint32_t)prop.multiProcessorCount;
     }
     const uint32_t per_cu = NTS_KNOB("NTS_BIN1_PER_CU") ? (uint32_t)std::max(1, atoi(NTS_KNOB("NTS_BIN1_PER_CU"))) : 2u; // (workgroups that fit a CU)
-    const dim3 grid1((uint32_t)std::min<uint64_t>(tiles, (uint64_t)ctx->n_cus * per_cu));
+    uint32_t n_wg1 = (uint32_t)std::min<uint64_t>(tiles, (uint64_t)ctx->n_cus * per_cu);
+    if (NTS_KNOB("NTS_BIN1_GRID")) n_wg1 = (uint32_t)std::min<uint64_t>(tiles, (uint64_t)std::max(1, atoi(NTS_KNOB("NTS_BIN1_GRID")))); // (tests: several turns per workgroup on a small genome)
+    const dim3 grid1(n_wg1);
+    ctx->last_bin1_grid = n_wg1;
     if (P.fm.form == 2)
       NTS_LAUNCH(k_bin1<2>, grid1, dim3(BIN1_THREADS), 0, ctx->stream, P);
     else if (P.fm.form == 1)

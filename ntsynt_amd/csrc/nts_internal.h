@@ -474,7 +474,9 @@ struct nts_ctx
   uint32_t last_c = 0;
   uint64_t last_candidates = 0, last_gaps = 0, last_gap_kmers = 0;
   uint64_t last_many_listed = 0; // candidates of k_hash_select_hi tiles that listed more than their slots hold (repeats, pieces)
-  uint64_t last_bf_direct = 0;   // indices of the last partitioned Bloom build that bypassed the buckets (full bucket, lanes in pieces)
+  uint32_t last_bin1_grid = 0;   // of the last partitioned Bloom build: k_bin1's workgroups (0: k_bin1 did not run), level-1 buckets, log2 of the
+  uint32_t last_bin_b1 = 0, last_bin_log2_b2 = 0; // level-2 buckets per level-1 bucket (nts_bf_bin_last)
+  uint64_t last_bf_direct = 0;  // indices of the last partitioned Bloom build that bypassed the buckets (full bucket, lanes in pieces)
   size_t win_fused_lds_set = 0;  // dynamic LDS k_window_min<true> was last allowed
   uint32_t last_comm_sparse = 0; // the last all-reduce of a filter gathered set-bit indices instead of chunks
   uint64_t last_x2_packed_bytes = 0, last_x2_unpacked_bytes = 0, last_x2_sent_bytes = 0; // the last exchange 2 (nts_comm_last_exchange2)

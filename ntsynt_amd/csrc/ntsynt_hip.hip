@@ -4247,6 +4247,25 @@ extern "C" int nts_path_stats(nts_ctx* ctx, uint64_t* sketch_many_listed, uint64
   return NTS_OK;
 }
 
+extern "C" int nts_bf_bin_plan(uint64_t n_valid, uint64_t bytes, uint32_t k, int forced, int and_mode, uint64_t* out)
+{
+  if (!out) return NTS_EINVAL;
+  BinPlan p;
+  const int rc = bf_bin_plan(n_valid, bytes, k, forced != 0, and_mode != 0, p);
+  const uint64_t v[10] = { p.F, p.log2_b2, p.B2, p.B1, p.n_final, p.cap1, p.cap2, p.tiles, p.tiles2, p.idx32 };
+  for (int i = 0; i < 10; ++i) out[i] = v[i];
+  return rc;
+}
+
+extern "C" int nts_bf_bin_last(nts_ctx* ctx, uint32_t* bin1_workgroups, uint32_t* B1, uint32_t* log2_b2)
+{
+  if (!ctx) return NTS_EINVAL;
+  if (bin1_workgroups) *bin1_workgroups = ctx->last_bin1_grid;
+  if (B1) *B1 = ctx->last_bin_b1;
+  if (log2_b2) *log2_b2 = ctx->last_bin_log2_b2;
+  return NTS_OK;
+}
+
 extern "C" int nts_bf_level_stats(nts_ctx* ctx, uint32_t* sparse_level, uint64_t* accepted_kmers)
 {
   if (!ctx) return NTS_EINVAL;

@@ -396,6 +396,13 @@ class Context:
         self.check(self.lib.nts_path_stats(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "nts_path_stats")
         return {"sketch_many_listed": a.value, "bf_direct_indices": b.value, "bf_list_fallback": c.value}
 
+    def bf_bin_last(self):
+        """dict(bin1_workgroups, B1, log2_b2) of the last partitioned Bloom build: the workgroups of its first pass (0: it did not run)
+        and the bucket geometry it was launched with (nts_bf_bin_last)"""
+        a, b, c = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+        self.check(self.lib.nts_bf_bin_last(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "nts_bf_bin_last")
+        return {"bin1_workgroups": a.value, "B1": b.value, "log2_b2": c.value}
+
     def bf_level_stats(self):
         """dict(sparse_level, accepted_kmers): whether the last BloomFilter.insert_and went the literal way over a running filter that
         is all but empty (every k-mer looked up, the bits that were hit kept) and how many k-mers it accepted (nts_bf_level_stats)"""
@@ -523,6 +530,19 @@ def bf_size_bytes(genome_bp, fpr, rounding="up"):
     if rc != 0:
         raise NtsError("nts_bf_size_bytes: bad arguments")
     return a.value, c.value
+
+
+BF_BIN_PLAN_FIELDS = ("F", "log2_b2", "B2", "B1", "n_final", "cap1", "cap2", "tiles", "tiles2", "idx32")
+
+
+def bf_bin_plan(n_valid, nbytes, k=24, forced=True, and_mode=False):
+    """The geometry of the partitioned Bloom build for n_valid k-mers and a filter of nbytes bytes (nts_bf_bin_plan, a host function:
+    no GPU): a dict of BF_BIN_PLAN_FIELDS, or None when the partitioned build does not apply."""
+    out = (u64 * len(BF_BIN_PLAN_FIELDS))()
+    rc = _lib.load().nts_bf_bin_plan(int(n_valid), int(nbytes), int(k), int(bool(forced)), int(bool(and_mode)), out)
+    if rc not in (0, 1):
+        raise NtsError("nts_bf_bin_plan: bad arguments")
+    return dict(zip(BF_BIN_PLAN_FIELDS, (int(x) for x in out))) if rc == 0 else None
 
 
 class Genome:
