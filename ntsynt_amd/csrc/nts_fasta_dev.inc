@@ -181,12 +181,15 @@ __device__ __forceinline__ bool fa_is_base(const uint8_t* __restrict__ raw, uint
   if (fa_is_blank(c)) { // (rare) trailing: only white space up to the line end; leading: only white space back to the line start
     // Every blank byte walks its own run, so the walks are bounded: a run of more than FA_BLANK_SCAN blanks (a malformed or
     // hostile file -- 100 MB of spaces would cost run^2 loads) is not looked at as a whole; its bytes farther than that from
-    // either line end count as bases (invalid ones: code 4), like white space in the middle of a line does.
+    // either line end count as bases (invalid ones: code 4), like white space in the middle of a line does.  A byte goes if
+    // FEWER than FA_BLANK_SCAN blanks lie between it and the line's end (line feed or end of file), or its start: a trailing run
+    // of b blanks keeps its first max(0, b - 4096), a leading run of a its last max(0, a - 4096), an all-blank line of L bytes
+    // max(0, L - 8192).  (The host reader trims runs of any length: the one difference, tests/test_gpu_fasta_seams.py.)
     constexpr uint64_t FA_BLANK_SCAN = 4096;
     uint64_t q = i + 1;
-    const uint64_t fwd_end = (n - i > FA_BLANK_SCAN) ? i + FA_BLANK_SCAN : n;
+    const uint64_t fwd_end = (n - i > FA_BLANK_SCAN) ? i + FA_BLANK_SCAN : n; // (fwd_end < n, or fwd_end == n == q below)
     while (q < fwd_end && fa_is_blank(raw[q])) ++q;
-    if (q == n || (q < fwd_end && raw[q] == '\n')) return false;
+    if (q == n || raw[q] == '\n') return false; // the line feed may stand at fwd_end itself: FA_BLANK_SCAN - 1 blanks between
     q = i;
     const uint64_t back_end = (i > FA_BLANK_SCAN) ? i - FA_BLANK_SCAN : 0;
     while (q > back_end && fa_is_blank(raw[q - 1])) --q;

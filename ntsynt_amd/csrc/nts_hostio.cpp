@@ -220,7 +220,9 @@ extern "C" int nts_fasta_read(const char* path, nts_fasta* out)
       first_line = true;
     } else if (in_record) {
       const size_t len = line_end - i;
-      // white space at either end of the line goes (same rule as csrc/nts_fasta_dev.inc); carriage returns go wherever they are
+      // white space at either end of the line goes; carriage returns go wherever they are.  Same rule as csrc/nts_fasta_dev.inc
+      // but for one limit: here a run goes whatever its length, there a blank byte goes only if fewer than 4096 blanks lie
+      // between it and the end of the line it runs up to (fa_is_base: FA_BLANK_SCAN) -- what lies farther in stays as invalid bases
       auto blank = [](uint8_t c) { return c == ' ' || c == '\t' || c == '\v' || c == '\f' || c == '\r'; };
       size_t a = i, b = line_end;
       while (a < b && blank(data[a])) ++a;

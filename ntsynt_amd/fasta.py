@@ -136,7 +136,9 @@ def _load_bytes(path):
 
 
 def read_fasta_numpy(path):
-    "numpy statement of the same parsing rules (tests compare it with the native reader)"
+    """numpy statement of the same parsing rules (tests compare it with the native reader).  Like the native reader it trims runs
+    of white space at a line's ends whatever their length; the parse on the GPU (read_fasta_device) looks at most 4096 bytes from a
+    blank byte to either end of its line, and what lies farther in stays as invalid bases (csrc/nts_fasta_dev.inc, fa_is_base)."""
     data = _load_bytes(path)
     n = data.size
     if n == 0:
@@ -183,7 +185,7 @@ def read_fasta_numpy(path):
         line_end = int(nl[j]) if j < nl.size and nl[j] < s1 else s1
         width = (line_end - s0 + 1) if (j < nl.size and nl[j] < s1) else (s1 - s0)
         bases = int(csum[line_end] - csum[s0])
-        if ln == 0:
+        if ln == 0 or line_end == s0:                             # a record without bases; an empty first line
             bases = width = 0
         fai.append((name, int(ln), int(s0), int(bases), int(width)))
     return FastaRecords(names, seq, rec_off, rec_len, fai)
