@@ -761,6 +761,38 @@ int nts_edit_wide_script(nts_ctx* ctx, const nts_genome* g_a, const nts_genome* 
                          const uint32_t* dist, uint64_t table_budget, nts_edit_op** ops, uint64_t* n_ops, uint64_t* first);
 int nts_edit_wide_script_last_plan(nts_ctx* ctx, uint64_t* members, uint64_t* table_bytes, uint64_t* batches);
 
+/* ---- how far a block's alignment really continues beyond its first and last anchor: the free-end extension ---------------
+ * nts_edit_extend: tasks = n_tasks pairs of strings.  String A of a task is n bases of record rec_a of g_a, read from record position
+ *   pos_a forwards (pos_a, pos_a + 1, ...) or, with NTS_EXTEND_A_BACKWARDS, backwards (pos_a, pos_a - 1, ...); string B is m bases of
+ *   record rec_b of g_b from pos_b, backwards with NTS_EXTEND_B_BACKWARDS, every base complemented (A <-> T, C <-> G) with
+ *   NTS_EXTEND_B_COMPLEMENT.  Both strings are cut before their first base that is not A, C, G or T: valid_a <= n, valid_b <= m.  With
+ *   T[i][j] the unrestricted unit-cost edit distance (Levenshtein) of the first i bases of A and the first j of B, penalty = P and
+ *   max_edits = E: among the cells 0 <= i <= valid_a, 0 <= j <= valid_b with T[i][j] <= E the one with the largest
+ *   S = i + j - P T[i][j]; ties go to the least T, then to the least j - i.  out[t] = {ext_a = i, ext_b = j, edits = T[i][j], valid_a,
+ *   valid_b} (n_tasks entries).  One end of the alignment is fixed at (0, 0), the other is free: a match adds 2 to S, a substitution
+ *   2 - P, an insertion or deletion 1 - P.  NTS_EINVAL before any launch, with nothing written: P outside 3..255, E outside 1..1023, n
+ *   or m above 65535, unknown flag bits, a record index out of range, a string that leaves its record (forwards pos + n > the record's
+ *   length, backwards n > pos + 1 or pos at or beyond the record's end; n = 0 reads nothing and is legal at any pos <= the record's
+ *   length).  NTS_ERANGE for 2^32 tasks or more.  No task: no launch.  One 64-lane wave per task runs the furthest-reaching rows of
+ *   nts_edit_wide without a target corner, two rows of 2 E + 3 entries in LDS, keeps the best entry per lane and stops at the first
+ *   row after which no entry can win (timer "edit_extend").  On the context's stream, in its workspace; no atomic, no launch per
+ *   task, no floating point: the same input gives the same bytes.  docs/design/04_20_block_ends.md; csrc/nts_edit_extend.inc;
+ *   ntsynt_amd/assess.py block_ends, `ntSynt --block-ends`, `bin/ntsynt_block_stats --ends-out`. */
+#define NTS_EXTEND_A_BACKWARDS 1u
+#define NTS_EXTEND_B_BACKWARDS 2u
+#define NTS_EXTEND_B_COMPLEMENT 4u
+typedef struct
+{
+  uint64_t pos_a, pos_b;
+  uint32_t rec_a, rec_b, n, m, flags, pad;
+} nts_extend_task;
+typedef struct
+{
+  uint32_t ext_a, ext_b, edits, valid_a, valid_b;
+} nts_extend_result;
+int nts_edit_extend(nts_ctx* ctx, const nts_genome* g_a, const nts_genome* g_b, const nts_extend_task* tasks, uint64_t n_tasks, uint32_t penalty,
+                    uint32_t max_edits, nts_extend_result* out);
+
 /* ---- C1-C5: minimizer graph -> collinear chains -----------------------------------------------------
  * replaces ntjoin_utils.read_minimizers' duplicate removal, filter_minimizers and build_graph
  * (call sites bin/ntsynt_synteny.py:607-612, 483, 539) and the path walk of Ntjoin.find_paths

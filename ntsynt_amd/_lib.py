@@ -67,6 +67,16 @@ class EditOp(ctypes.Structure):
                 ("pad", ctypes.c_uint8)]
 
 
+class ExtendTask(ctypes.Structure):
+    "nts_extend_task: the two strings of one free-end extension (nts_edit_extend)"
+    _fields_ = [("pos_a", u64), ("pos_b", u64)] + [(n, u32) for n in ("rec_a", "rec_b", "n", "m", "flags", "pad")]
+
+
+class ExtendResult(ctypes.Structure):
+    "nts_extend_result: where one extension ends (nts_edit_extend)"
+    _fields_ = [(n, u32) for n in ("ext_a", "ext_b", "edits", "valid_a", "valid_b")]
+
+
 class MxList(ctypes.Structure):
     _fields_ = [("h1", c_vp), ("rec", c_vp), ("pos", c_vp), ("keep", c_vp), ("list_id", c_vp), ("n", u64)]
 
@@ -229,6 +239,7 @@ SYMBOLS = [
                                      c_vp]),
     ("nts_edit_wide_script", ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.POINTER(Interval), ctypes.POINTER(Interval), c_vp, u64, u64, c_vp, u32, u32, c_vp,
                                             u64, ctypes.POINTER(c_vp), c_u64p, c_vp]),
+    ("nts_edit_extend", ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, u64, u32, u32, c_vp]),
     ("nts_edit_wide_script_last_plan", ctypes.c_int, [c_vp, c_u64p, c_u64p, c_u64p]),
     ("nts_genome_valid_bases", ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(Interval), u64, c_vp]),
     ("nts_minhash_pairs", ctypes.c_int, [c_vp, u32, c_vp, c_vp, u64, c_vp, c_vp, u64, c_vp, c_vp]),

@@ -14,7 +14,10 @@ Two things, both over `<prefix>.synteny_blocks.tsv`:
   script of every aligned stretch (nts_edit_script), merged into snv / ins / del events in both genomes' coordinates;
   docs/design/04_17_block_variants.md.
 * block_wide_variants (`ntSynt --block-wide-variants`, `ntsynt_block_stats --wide-variants-out`): the same list with the stretches the
-  band leaves out included (nts_edit_wide, nts_edit_wide_script), under --identity-max-edits; docs/design/04_19_block_wide_variants.md."""
+  band leaves out included (nts_edit_wide, nts_edit_wide_script), under --identity-max-edits; docs/design/04_19_block_wide_variants.md.
+* block_ends (`ntSynt --block-ends`, `ntsynt_block_stats --ends-out`): per block and pair of its lines how far the alignment continues
+  in front of the first and behind the last aligned stretch, base for base -- the breakpoints of the pair (nts_edit_extend);
+  docs/design/04_20_block_ends.md."""
 import os
 import re
 from collections import namedtuple
@@ -29,6 +32,9 @@ DIVERGENCE_COLUMNS = ("block_id", "genome_a", "genome_b", "distance", "shared_ha
 IDENTITY_K, IDENTITY_RATE, IDENTITY_BAND, IDENTITY_MAX_LEN = 21, 16, 31, 4096
 IDENTITY_COLUMNS = ("block_id", "genome_a", "genome_b", "orientation", "length_a", "length_b", "anchors", "segments", "aligned", "aligned_a",
                     "aligned_b", "edits", "identity", "covered_a", "covered_b", "backward", "long", "offband", "invalid", "overband")
+ENDS_MAX_LEN, ENDS_MAX_EDITS, ENDS_PENALTY = 4096, 255, 6
+ENDS_COLUMNS = ("block_id", "genome_a", "contig_a", "start_a", "end_a", "genome_b", "contig_b", "start_b", "end_b", "orientation", "left_a", "left_b",
+                "left_edits", "left_stop", "right_a", "right_b", "right_edits", "right_stop", "ext_start_a", "ext_end_a", "ext_start_b", "ext_end_b")
 VARIANT_COLUMNS = ("block_id", "genome_a", "contig_a", "pos_a", "genome_b", "contig_b", "pos_b", "orientation", "type", "length", "seq_a", "seq_b")
 
 # one line of a block table (README "Output files"): the block's interval on `contig` of `genome` is [start, end)
@@ -410,6 +416,129 @@ def block_wide_variants(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTIT
     return _identity_rows(blocks, pairs, length, found), rows
 
 
+def check_ends_parameters(ends_max_len, ends_max_edits, ends_penalty):
+    "the ranges of the parameters of the block ends; the message of the first that is out of range, or None"
+    if not 1 <= ends_max_len <= 65535:
+        return "--ends-max-len must lie in 1..65535"
+    if not 1 <= ends_max_edits <= 1023:
+        return "--ends-max-edits must lie in 1..1023"
+    if not 3 <= ends_penalty <= 255:
+        return "--ends-penalty must lie in 3..255 (below 3 an edit costs nothing)"
+    return None
+
+
+def ends_tasks(segs, final, iv_a, iv_b, flip, lines, rec_len_a, rec_len_b, ends_max_len):
+    """The extension tasks of one round.  segs: the round's SEGMENT_DTYPE array in iv_a order, final: its final per-segment results;
+    iv_a / iv_b: (rec, start, end) rows of the clipped intervals of A and of their mates, flip[i] = 1 for a pair of differing strands;
+    lines: (line a, line b, index of a's interval); rec_len_*: the record lengths of the two genomes.  An interval with at least one
+    segment whose result is a distance has a left end point (x, y_lo) of the first such segment and a right end point (x + dx,
+    y_lo + dy) of the last one, oriented-frame offsets; from each a flank of at most ends_max_len bases runs outwards, past the
+    interval, to the record's end at the furthest.  Returns (a TASK_DTYPE array, flanks): flanks[q] belongs to lines[q] and is None for
+    a pair without an aligned segment, else dict(x_l, y_l, x_r, y_r, left, right) with the indices of its two tasks.  Pure."""
+    import numpy as np
+    from .device import EDIT_INVALID, EXTEND_A_BACKWARDS, EXTEND_B_BACKWARDS, EXTEND_B_COMPLEMENT, TASK_DTYPE
+    cap = int(ends_max_len)
+    tasks, flanks = [], []
+    for _, _, i in lines:
+        s0, s1 = (int(x) for x in np.searchsorted(segs["iv_a"], [i, i + 1]))                  # (the segments come in iv_a order)
+        aligned = [s for s in range(s0, s1) if int(final[s]) < EDIT_INVALID]
+        if not aligned:
+            flanks.append(None)
+            continue
+        first, last = segs[aligned[0]], segs[aligned[-1]]
+        x_l, y_l = int(first["x"]), int(first["y_lo"])
+        x_r, y_r = int(last["x"]) + int(last["dx"]), int(last["y_lo"]) + int(last["dy"])
+        rec_a, start_a = int(iv_a[i][0]), int(iv_a[i][1])
+        rec_b, start_b, len_b = int(iv_b[i][0]), int(iv_b[i][1]), int(iv_b[i][2]) - int(iv_b[i][1])
+        la, lb = int(rec_len_a[rec_a]), int(rec_len_b[rec_b])
+        flipped = bool(flip[i])
+
+        def task(pos_a, n, a_back, pos_b, m, b_back):
+            "(a string of no base reads nothing: its position is put inside the record)"
+            n, m = min(cap, n), min(cap, m)
+            tasks.append((pos_a if n else 0, pos_b if m else 0, rec_a, rec_b, n, m,
+                          (EXTEND_A_BACKWARDS if a_back else 0) | (EXTEND_B_BACKWARDS if b_back else 0) | (EXTEND_B_COMPLEMENT if flipped else 0), 0))
+            return len(tasks) - 1
+        if flipped:
+            left = task(start_a + x_l - 1, start_a + x_l, True, start_b + len_b - y_l, lb - (start_b + len_b - y_l), False)
+            right = task(start_a + x_r, la - (start_a + x_r), False, start_b + len_b - 1 - y_r, start_b + len_b - y_r, True)
+        else:
+            left = task(start_a + x_l - 1, start_a + x_l, True, start_b + y_l - 1, start_b + y_l, True)
+            right = task(start_a + x_r, la - (start_a + x_r), False, start_b + y_r, lb - start_b - y_r, False)
+        flanks.append({"x_l": x_l, "y_l": y_l, "x_r": x_r, "y_r": y_r, "left": left, "right": right})
+    return np.array(tasks, dtype=TASK_DTYPE), flanks
+
+
+def ends_stop(task, result, ends_max_len, ends_max_edits):
+    """why a flank ends where it does.  The limit kind of a side: `invalid` when the string was cut at a base that is not A, C, G or T,
+    else `max_len` when ends_max_len bases were asked for, else `record`.  The stop reason: A's limit kind when the extension used
+    all of A, else B's when it used all of B, else `max_edits` when it spent them all, else `break`.  Pure."""
+    def kind(valid, asked):
+        return "invalid" if valid < asked else "max_len" if asked == int(ends_max_len) else "record"
+    if int(result["ext_a"]) == int(result["valid_a"]):
+        return kind(int(result["valid_a"]), int(task["n"]))
+    if int(result["ext_b"]) == int(result["valid_b"]):
+        return kind(int(result["valid_b"]), int(task["m"]))
+    return "max_edits" if int(result["edits"]) == int(ends_max_edits) else "break"
+
+
+def ends_row(ra, rb, iv_a, iv_b, flipped, flank, tasks, results, ends_max_len, ends_max_edits):
+    """one pair's dict of ENDS_COLUMNS.  ra / rb: the two block lines, iv_a / iv_b: their clipped (rec, start, end); flank: the pair's
+    entry of ends_tasks, tasks / results: that call's tasks and what nts_edit_extend made of them.  ext_* are half-open forward record
+    coordinates: the interval from the left breakpoint to the right one; `.` throughout for a pair without flanks.  Pure."""
+    start_a, end_a, start_b, end_b = int(iv_a[1]), int(iv_a[2]), int(iv_b[1]), int(iv_b[2])
+    row = {"block_id": ra.block_id, "genome_a": ra.genome, "contig_a": ra.contig, "start_a": start_a, "end_a": end_a, "genome_b": rb.genome,
+           "contig_b": rb.contig, "start_b": start_b, "end_b": end_b, "orientation": "-" if flipped else "+"}
+    if flank is None:
+        return dict(row, **{c: "." for c in ENDS_COLUMNS[10:]})
+    left, right = results[flank["left"]], results[flank["right"]]
+    for side, res, t in (("left", left, tasks[flank["left"]]), ("right", right, tasks[flank["right"]])):
+        row[side + "_a"], row[side + "_b"], row[side + "_edits"] = int(res["ext_a"]), int(res["ext_b"]), int(res["edits"])
+        row[side + "_stop"] = ends_stop(t, res, ends_max_len, ends_max_edits)
+    row["ext_start_a"] = start_a + flank["x_l"] - row["left_a"]
+    row["ext_end_a"] = start_a + flank["x_r"] + row["right_a"]
+    if flipped:
+        row["ext_end_b"] = end_b - flank["y_l"] + row["left_b"]
+        row["ext_start_b"] = end_b - flank["y_r"] - row["right_b"]
+    else:
+        row["ext_start_b"] = start_b + flank["y_l"] - row["left_b"]
+        row["ext_end_b"] = start_b + flank["y_r"] + row["right_b"]
+    return row
+
+
+def ends_table(rows, k, rate, band, max_len, max_edits, ends_max_len, ends_max_edits, ends_penalty):
+    "TSV with a header, one line per block and pair of its lines, then the parameters of the identity pass and of the extension"
+    lines = ["\t".join(ENDS_COLUMNS)] + ["\t".join(str(r[c]) for c in ENDS_COLUMNS) for r in rows]
+    lines.append(f"# k {int(k)}, rate {int(rate)}, band {int(band)}, max_len {int(max_len)}, max_edits {int(max_edits)}, ends_max_len {int(ends_max_len)}, "
+                 f"ends_max_edits {int(ends_max_edits)}, ends_penalty {int(ends_penalty)}")
+    return "\n".join(lines) + "\n"
+
+
+def block_ends(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_RATE, band=IDENTITY_BAND, max_len=IDENTITY_MAX_LEN, max_edits=0,
+               ends_max_len=ENDS_MAX_LEN, ends_max_edits=ENDS_MAX_EDITS, ends_penalty=ENDS_PENALTY):
+    """Per block and pair of its lines the base-exact breakpoints: from the first and the last aligned stretch of block_identity (the same
+    pairs, anchors, segments and final per-segment results for the same first five parameters) the alignment is extended outwards
+    with a free end -- at most ends_max_len bases and ends_max_edits edits, each edit costing ends_penalty against 2 for a match --
+    past the block's own interval.  Returns dicts of ENDS_COLUMNS in block_identity's order.  Per round block_identity's edit calls
+    with the per-segment results and one nts_edit_extend over both flanks of all its pairs.  docs/design/04_20_block_ends.md."""
+    message = check_identity_parameters(int(k), int(rate), int(band), int(max_len), int(max_edits)) or \
+        check_ends_parameters(int(ends_max_len), int(ends_max_edits), int(ends_penalty))
+    if message:
+        raise ValueError(message)
+    k, rate, band, max_len, max_edits = int(k), int(rate), int(band), int(max_len), int(max_edits)
+    cap, limit, penalty = int(ends_max_len), int(ends_max_edits), int(ends_penalty)
+    pairs, length, found = [], {}, {}
+    for r in _identity_rounds(ctx, genomes_by_name, blocks, k, rate, band, max_len, pairs, length):
+        _, final = ctx.edit_segments(r.g_a, r.g_b, r.iv_a, r.iv_b, r.segs, r.flip, band, with_distances=True)
+        if max_edits > 0:
+            _, final = ctx.edit_wide(r.g_a, r.g_b, r.iv_a, r.iv_b, r.segs, r.flip, band, max_edits, final)
+        tasks, flanks = ends_tasks(r.segs, final, r.iv_a, r.iv_b, r.flip, r.lines, r.g_a.rec_len, r.g_b.rec_len, cap)
+        results = ctx.edit_extend(r.g_a, r.g_b, tasks, penalty, limit)
+        for (la, lb, i), flank in zip(r.lines, flanks):
+            found[(la, lb)] = ends_row(blocks[la], blocks[lb], r.iv_a[i], r.iv_b[i], bool(r.flip[i]), flank, tasks, results, cap, limit)
+    return [found[p] for p in pairs]
+
+
 def wide_variants_table(rows, k, rate, band, max_len, max_edits):
     """TSV of block_wide_variants' variant rows: the columns and the order of variants_table, every event of every aligned stretch,
     narrow and wide, then `# k K, rate R, band W, max_len L, max_edits E`"""
@@ -510,10 +639,23 @@ def main(argv=None):
     p.add_argument("--identity-max-edits", help="with --identity-out or --wide-variants-out (which needs it): also align the stretches the band leaves "
                    "out (indels of 32 bases or more), up to this many edits: 0 = off, else 2 * --identity-band + 1 .. 1023; not with "
                    "--variants-out [0]", type=int, default=0)
+    p.add_argument("--ends-out", help="with --fastas: file for the per-block ends table (the base-exact breakpoints of every block and pair: how far the "
+                   "alignment continues beyond the first and the last aligned stretch; GPU); it takes the --identity-* parameters")
+    p.add_argument("--ends-max-len", help=f"longest flank that is extended, 1..65535 [{ENDS_MAX_LEN}]", type=int, default=ENDS_MAX_LEN)
+    p.add_argument("--ends-max-edits", help=f"most edits within one flank, 1..1023 [{ENDS_MAX_EDITS}]", type=int, default=ENDS_MAX_EDITS)
+    p.add_argument("--ends-penalty", help=f"what an edit costs the extension's score, against 2 for a matching pair of bases, 3..255 [{ENDS_PENALTY}]",
+                   type=int, default=ENDS_PENALTY)
     p.add_argument("--device", help="GPU index [0]", type=int, default=0)
     args = p.parse_args(argv)
     if args.k < 1 or args.s < 1:
         p.error("-k and -s must be positive")
+    if args.ends_out:
+        if not args.fastas:
+            p.error("--ends-out needs the genomes: --fastas")
+        message = check_identity_parameters(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits) or \
+            check_ends_parameters(args.ends_max_len, args.ends_max_edits, args.ends_penalty)
+        if message:
+            p.error(message)
     if args.identity_out or args.variants_out or args.wide_variants_out:
         if not args.fastas:
             p.error(("--identity-out" if args.identity_out else "--variants-out" if args.variants_out else "--wide-variants-out") +
@@ -551,6 +693,10 @@ def main(argv=None):
         if args.identity_out:
             with open(args.identity_out, "w", encoding="utf-8") as fh:
                 fh.write(identity_table(id_rows, *id_args, max_edits=args.identity_max_edits))
+        if args.ends_out:
+            e_args = id_args + (args.identity_max_edits, args.ends_max_len, args.ends_max_edits, args.ends_penalty)
+            with open(args.ends_out, "w", encoding="utf-8") as fh:
+                fh.write(ends_table(block_ends(ctx, loaders, read_blocks(args.tsv), *e_args), *e_args))
     finally:
         ctx.close()
     if args.divergence_out:

@@ -846,6 +846,7 @@ namespace {
 #include "nts_edit_script.inc"
 #include "nts_edit_wide.inc"
 #include "nts_edit_wide_script.inc"
+#include "nts_edit_extend.inc"
 } // namespace
 
 extern "C" int nts_iv_links(nts_ctx* ctx, uint32_t n_lists, const nts_sample* const* lists, const uint64_t* n, uint32_t min_anchors, nts_iv_link** out,
@@ -975,6 +976,16 @@ extern "C" int nts_edit_wide_script_last_plan(nts_ctx* ctx, uint64_t* members, u
   if (table_bytes) *table_bytes = ctx->last_wscript_table_bytes;
   if (batches) *batches = ctx->last_wscript_batches;
   return NTS_OK;
+}
+
+extern "C" int nts_edit_extend(nts_ctx* ctx, const nts_genome* g_a, const nts_genome* g_b, const nts_extend_task* tasks, uint64_t n_tasks,
+                               uint32_t penalty, uint32_t max_edits, nts_extend_result* out)
+{
+  if (!ctx || !g_a || !g_b || (n_tasks && (!tasks || !out)) || penalty < EXTEND_MIN_PENALTY || penalty > EXTEND_MAX_PENALTY || max_edits < 1 ||
+      max_edits > EXTEND_MAX_EDITS)
+    return fail(ctx, NTS_EINVAL, "nts_edit_extend: bad arguments (penalty 3..255, max_edits 1..1023)");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return edit_extend_run(ctx, g_a, g_b, tasks, n_tasks, penalty, max_edits, out);
 }
 
 extern "C" int nts_graph_budget(nts_ctx* ctx, uint64_t bytes)

@@ -60,6 +60,10 @@ OP_SUB, OP_DEL, OP_INS = 1, 2, 3
 SEG_CANDIDATE, SEG_BACKWARD, SEG_LONG, SEG_OFFBAND = 0, 1, 2, 3
 EDIT_NOT_CANDIDATE, EDIT_PASSED, EDIT_OVERBAND, EDIT_INVALID = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD, 0xFFFFFFFC
 NO_MATE = 0xFFFFFFFF
+# nts_extend_task / nts_extend_result: what Context.edit_extend takes and returns, one per task
+TASK_DTYPE = np.dtype([("pos_a", "<u8"), ("pos_b", "<u8"), ("rec_a", "<u4"), ("rec_b", "<u4"), ("n", "<u4"), ("m", "<u4"), ("flags", "<u4"), ("pad", "<u4")])
+EXTEND_DTYPE = np.dtype([(n, "<u4") for n in ("ext_a", "ext_b", "edits", "valid_a", "valid_b")])
+EXTEND_A_BACKWARDS, EXTEND_B_BACKWARDS, EXTEND_B_COMPLEMENT = 1, 2, 4
 
 
 class Context:
@@ -340,6 +344,25 @@ class Context:
         a, b, c = u64(), u64(), u64()
         self.check(self.lib.nts_edit_wide_script_last_plan(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "nts_edit_wide_script_last_plan")
         return {"members": a.value, "table_bytes": b.value, "batches": c.value}
+
+    def edit_extend(self, genome_a, genome_b, tasks, penalty, max_edits, out=None):
+        """how far two strings stay alignable from a common start (nts_edit_extend).  tasks: a TASK_DTYPE array -- n bases of record
+        rec_a of genome_a from pos_a and m bases of record rec_b of genome_b from pos_b, flags: EXTEND_A_BACKWARDS, EXTEND_B_BACKWARDS,
+        EXTEND_B_COMPLEMENT.  Both strings are cut before their first base that is not A, C, G or T; among the cells of the unrestricted
+        edit table with at most max_edits = E (1..1023) edits the one with the largest i + j - penalty * edits (penalty 3..255), ties to
+        the fewest edits, then to the least j - i.  Returns an EXTEND_DTYPE array (ext_a, ext_b, edits, valid_a, valid_b), one entry per
+        task -- `out` itself when given, which a refused call leaves untouched.  Exact and deterministic."""
+        tk = np.ascontiguousarray(tasks, dtype=TASK_DTYPE)
+        if tk.ndim != 1:
+            raise ValueError("edit_extend: a list of tasks")
+        assert TASK_DTYPE.itemsize == ctypes.sizeof(_lib.ExtendTask) and EXTEND_DTYPE.itemsize == ctypes.sizeof(_lib.ExtendResult)
+        if out is None:
+            out = np.zeros(tk.size, dtype=EXTEND_DTYPE)
+        if out.dtype != EXTEND_DTYPE or out.shape != (tk.size,) or not out.flags.c_contiguous:
+            raise ValueError("edit_extend: out is a contiguous EXTEND_DTYPE array, one entry per task")
+        self.check(self.lib.nts_edit_extend(self.h, genome_a.h, genome_b.h, tk.ctypes.data if tk.size else None, tk.size, int(penalty), int(max_edits),
+                                            out.ctypes.data if out.size else None), "nts_edit_extend")
+        return out
 
     def timing(self, name):
         ms, n = ctypes.c_double(), u64()

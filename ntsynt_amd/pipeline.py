@@ -497,7 +497,7 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         benchmark=False, log=print, ctx=None, backend=None, bf_rounding="up", bf_signature=BF_SIGNATURE, dev=False, interarrivals=False, repeat=False,
         mx_tsvs=None, common_file=None, m=90, n=0, initial_only=False, write_fai=True, engine="device", refine_repeat_file=None, screen_repeat_file=None,
         graph_budget=None, assess=None, gaps=False, gap_links=None, gap_block_links=False, gap_copies=None, gap_copy_sites=None,
-        gap_periods=None, gap_families=None, block_identity=None, block_variants=None, block_wide_variants=None):
+        gap_periods=None, gap_families=None, block_identity=None, block_variants=None, block_wide_variants=None, block_ends=None):
     """FASTA paths -> engine (outputs in .outputs and in the CWD).  Mirrors oracle.synteny_oracle.run_pipeline's
     signature so the parity tests read alike.  Under torch.distributed (WORLD_SIZE > 1, process group already
     initialised by the caller) genomes are sharded over the ranks.
@@ -531,7 +531,10 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
     <prefix>.block_wide_variants.tsv (assess.block_wide_variants: every edit of every aligned stretch, those the band leaves out
     included); with block_identity, which then takes the same five, one pass in the stage block_identity serves both files; not together
     with block_variants; with `benchmark` the stage times gain block_wide_variants:edit_script_plan / :edit_script /
-    :edit_wide_script_plan / :edit_wide_script."""
+    :edit_wide_script_plan / :edit_wide_script.  block_ends = (ends_max_len, ends_max_edits, ends_penalty), optionally followed by the
+    identity parameters (k, rate, band, max_len[, max_edits]) -- without them those of block_identity when that is given, else the
+    defaults: behind the other block files, <prefix>.block_ends.tsv (assess.block_ends: the base-exact breakpoints of every block and
+    pair; one rank only; it needs none of the other switches); with `benchmark` the stage times gain block_ends:edit_extend."""
     prefix = prefix or f"ntSynt.k{k}.w{w}"
     if mx_tsvs is not None and len(mx_tsvs) != len(fastas):
         raise ValueError("one minimizer TSV per FASTA file")
@@ -593,6 +596,19 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
             raise ValueError("block_wide_variants and block_variants: " + WIDE_NOT_WITH_VARIANTS)
         if block_identity is not None and tuple(int(x) for x in block_identity) != tuple(int(x) for x in block_wide_variants):
             raise ValueError("block_identity and block_wide_variants take the same (k, rate, band, max_len, max_edits)")
+    if block_ends is not None:
+        if world > 1 or (mx_tsvs is not None and initial_only):
+            raise ValueError("block_ends needs every genome resident on one GPU (one rank, genomes loaded)")
+        from .assess import IDENTITY_BAND, IDENTITY_K, IDENTITY_MAX_LEN, IDENTITY_RATE, check_ends_parameters, check_identity_parameters
+        if len(block_ends) not in (3, 7, 8):
+            raise ValueError("block_ends = (ends_max_len, ends_max_edits, ends_penalty[, k, rate, band, max_len[, max_edits]])")
+        block_ends = tuple(int(x) for x in block_ends)
+        if len(block_ends) == 3:
+            block_ends += tuple(int(x) for x in block_identity) if block_identity is not None else (IDENTITY_K, IDENTITY_RATE, IDENTITY_BAND, IDENTITY_MAX_LEN)
+        block_ends += (0,) * (8 - len(block_ends))
+        message = check_ends_parameters(*block_ends[:3]) or check_identity_parameters(*block_ends[3:])
+        if message:
+            raise ValueError("block_ends = (ends_max_len, ends_max_edits, ends_penalty[, k, rate, band, max_len[, max_edits]]): " + message)
     if gap_block_links and gap_links is None:
         raise ValueError("gap_block_links needs gap_links = (rate, min_anchors)")
     if gap_block_links and len(fastas) > 32:
@@ -1187,6 +1203,23 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         st.stop()
         st.rows += wv_times
         st.mark("block_wide_variants_done")
+    if block_ends is not None:
+        st.start("block_ends")
+        from . import assess as assess_
+        if benchmark:                                         # (device events around the calls of this stage only)
+            backend.ctx.profile(True)
+            ends_before = backend.ctx.timing("edit_extend")[0]
+        e_args = block_ends[3:] + block_ends[:3]
+        rows = assess_.block_ends(backend.ctx, {fa.basename(p): genomes[p] for p in fastas}, assess_.read_blocks(f"{prefix}.synteny_blocks.tsv"), *e_args)
+        text = assess_.ends_table(rows, *e_args)
+        with open(f"{prefix}.block_ends.tsv", "w", encoding="utf-8") as fh:
+            fh.write(text)
+        eng.outputs[f"{prefix}.block_ends.tsv"] = text
+        st.stop()
+        if benchmark:
+            st.rows.append(("block_ends:edit_extend", (backend.ctx.timing("edit_extend")[0] - ends_before) * 1e-3))
+            backend.ctx.profile(False)
+        st.mark("block_ends_done")
     if gaps:
         st.start("gaps")
         from . import assess as assess_, gaps as gaps_
