@@ -793,6 +793,33 @@ typedef struct
 int nts_edit_extend(nts_ctx* ctx, const nts_genome* g_a, const nts_genome* g_b, const nts_extend_task* tasks, uint64_t n_tasks, uint32_t penalty,
                     uint32_t max_edits, nts_extend_result* out);
 
+/* ---- which edits an extended flank consists of: block end variants ---------------------------------------------------
+ * nts_edit_extend_script: the tasks of nts_edit_extend and results = what that call wrote for them; valid_a and valid_b are not read.
+ *   For task t, A' = the first ext_a bases of its string A as nts_edit_extend reads it (forwards or backwards from pos_a), B' = the
+ *   first ext_b bases of its string B as read (forwards or backwards, complemented with NTS_EXTEND_B_COMPLEMENT), D = results[t].edits.
+ *   For every task with D >= 1 the D ops of the CANONICAL script of A' and B', exactly as nts_edit_script defines it (walk from
+ *   (ext_a, ext_b) to (0, 0), at each cell match first, then SUB, then DEL, else INS; ascending path order), at first[t] ..
+ *   first[t + 1] - 1: seg = t, p and q offsets IN THE STRINGS AS READ, base_a = the code of A'[p] for SUB and DEL, base_b = the code
+ *   of the complemented-as-read B'[q] for SUB and INS, else 0xFF.  *ops (release with nts_free; NULL for none), n_ops = the sum of D;
+ *   first (n_tasks + 1 host entries, may be NULL).  NTS_EINVAL before any launch, with nothing written and the smallest offending
+ *   task named: every task check of nts_edit_extend (lengths, flag bits, record index, a string that leaves its record);
+ *   ext_a > n or ext_b > m; edits > 1023; edits < |ext_b - ext_a|; edits > max(ext_a, ext_b); a table_budget that is not 0 and below
+ *   4 (Dmax + 1)^2 bytes, Dmax the largest edits among the results.  NTS_ERANGE for 2^32 tasks or more, or 2^32 ops or more.
+ *   NTS_EINVAL after the launch, with no ops returned ("results is not the extension of task ...", the smallest such index): D edits
+ *   do not reach the corner (ext_a, ext_b), or D - 1 already do, or A' or B' holds a base that is not A, C, G or T.  No task, or no
+ *   task with D >= 1: no launch, first all 0.  A task's furthest-reaching table, rows e = 0 .. D as int32 at e * e + d + e, (D + 1)^2
+ *   entries, lies in global memory; the tables of one launch share one block of at most table_budget bytes (0 = 1 GiB) that is
+ *   released when the call ends, the host cuts the tasks with D >= 1 in index order into batches that fit, one launch per batch, and
+ *   the result does not depend on the budget.  Two scans and a selection (timer "edit_extend_script_plan"), one 64-lane wave per task
+ *   with D >= 1, two rows of 2 Dmax + 3 entries in LDS (timer "edit_extend_script").  No atomic, no launch per task, no floating
+ *   point: the same input gives the same bytes.  docs/design/04_21_block_end_variants.md; csrc/nts_edit_extend_script.inc;
+ *   ntsynt_amd/assess.py block_ends, `ntSynt --block-end-variants`, `bin/ntsynt_block_stats --end-variants-out`.
+ * nts_edit_extend_script_last_plan: the last such call on this context: tasks with D >= 1, bytes of all their tables, batches (all 0
+ *   when nothing was launched); any pointer may be NULL. */
+int nts_edit_extend_script(nts_ctx* ctx, const nts_genome* g_a, const nts_genome* g_b, const nts_extend_task* tasks, uint64_t n_tasks,
+                           const nts_extend_result* results, uint64_t table_budget, nts_edit_op** ops, uint64_t* n_ops, uint64_t* first);
+int nts_edit_extend_script_last_plan(nts_ctx* ctx, uint64_t* members, uint64_t* table_bytes, uint64_t* batches);
+
 /* ---- C1-C5: minimizer graph -> collinear chains -----------------------------------------------------
  * replaces ntjoin_utils.read_minimizers' duplicate removal, filter_minimizers and build_graph
  * (call sites bin/ntsynt_synteny.py:607-612, 483, 539) and the path walk of Ntjoin.find_paths

@@ -241,6 +241,8 @@ SYMBOLS = [
                                             u64, ctypes.POINTER(c_vp), c_u64p, c_vp]),
     ("nts_edit_extend", ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, u64, u32, u32, c_vp]),
     ("nts_edit_wide_script_last_plan", ctypes.c_int, [c_vp, c_u64p, c_u64p, c_u64p]),
+    ("nts_edit_extend_script", ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, u64, c_vp, u64, ctypes.POINTER(c_vp), c_u64p, c_vp]),
+    ("nts_edit_extend_script_last_plan", ctypes.c_int, [c_vp, c_u64p, c_u64p, c_u64p]),
     ("nts_genome_valid_bases", ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(Interval), u64, c_vp]),
     ("nts_minhash_pairs", ctypes.c_int, [c_vp, u32, c_vp, c_vp, u64, c_vp, c_vp, u64, c_vp, c_vp]),
     ("nts_graph_build", ctypes.c_int, [c_vp, u32, ctypes.POINTER(MxList), ctypes.POINTER(Graph)]),

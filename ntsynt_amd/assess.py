@@ -17,7 +17,10 @@ Two things, both over `<prefix>.synteny_blocks.tsv`:
   band leaves out included (nts_edit_wide, nts_edit_wide_script), under --identity-max-edits; docs/design/04_19_block_wide_variants.md.
 * block_ends (`ntSynt --block-ends`, `ntsynt_block_stats --ends-out`): per block and pair of its lines how far the alignment continues
   in front of the first and behind the last aligned stretch, base for base -- the breakpoints of the pair (nts_edit_extend);
-  docs/design/04_20_block_ends.md."""
+  docs/design/04_20_block_ends.md.
+* block end variants (`ntSynt --block-ends --block-end-variants`, `ntsynt_block_stats --ends-out F --end-variants-out G`): the edits
+  behind left_edits and right_edits -- the canonical script of every extended flank (nts_edit_extend_script), as snv / ins / del
+  events in both genomes' coordinates; docs/design/04_21_block_end_variants.md."""
 import os
 import re
 from collections import namedtuple
@@ -36,6 +39,9 @@ ENDS_MAX_LEN, ENDS_MAX_EDITS, ENDS_PENALTY = 4096, 255, 6
 ENDS_COLUMNS = ("block_id", "genome_a", "contig_a", "start_a", "end_a", "genome_b", "contig_b", "start_b", "end_b", "orientation", "left_a", "left_b",
                 "left_edits", "left_stop", "right_a", "right_b", "right_edits", "right_stop", "ext_start_a", "ext_end_a", "ext_start_b", "ext_end_b")
 VARIANT_COLUMNS = ("block_id", "genome_a", "contig_a", "pos_a", "genome_b", "contig_b", "pos_b", "orientation", "type", "length", "seq_a", "seq_b")
+END_VARIANT_COLUMNS = VARIANT_COLUMNS[:8] + ("flank",) + VARIANT_COLUMNS[8:]      # (`flank`, left or right, behind `orientation`)
+END_VARIANTS_NEED_ENDS = ("the block end variants list the edits of the flanks that the block ends extend and are written from that stage's own pass: "
+                          "give --block-ends with --block-end-variants (ntsynt_block_stats: --ends-out with --end-variants-out)")
 
 # one line of a block table (README "Output files"): the block's interval on `contig` of `genome` is [start, end)
 BlockRow = namedtuple("BlockRow", ["block_id", "genome", "contig", "start", "end", "strand", "minimizers", "reason"])
@@ -514,29 +520,105 @@ def ends_table(rows, k, rate, band, max_len, max_edits, ends_max_len, ends_max_e
     return "\n".join(lines) + "\n"
 
 
+def ends_events(ops, task, side):
+    """The events of one flank.  ops: its OP_DTYPE entries in script order, p and q offsets in the task's two strings as
+    nts_edit_extend reads them; task: its TASK_DTYPE entry (pos_a, pos_b, flags); side: `left` or `right`.  Runs are merged in the
+    string frame as variant_events merges them: a maximal run of adjacent DEL ops with consecutive p and one q is one `del`, a maximal
+    run of adjacent INS ops with one p and consecutive q one `ins`, every SUB an `snv`.  An event covers the string offsets
+    [p0, p0 + La) of A and [q0, q0 + Lb) of B, either possibly empty; a string read forwards from pos holds them at the record
+    positions [pos + p0, pos + p0 + L), one read backwards at [pos - p0 - L + 1, pos - p0 + 1).  Returns dicts of type, pos_a, pos_b
+    (the starts of those forward intervals: for an empty one the boundary point, as variant_events has it), length = max(La, Lb),
+    seq_a, seq_b -- the run's bases as read (B complemented for a pair of differing strands), reversed for the left flank so that both
+    read along A's forward strand; `-` for no bases.  The right flank's events come in script order, the left flank's in reverse script
+    order: both ascend along A's forward strand.  The script is canonical on the strings as read, which run OUTWARDS from the aligned
+    core: inside a repeat an indel lies at the repeat's end nearest the core, so in forward coordinates a left flank's indel sits at the
+    opposite end from a right flank's (no left-normalisation).  Pure."""
+    sub, dele, ins = 1, 2, 3
+    if side not in ("left", "right"):
+        raise ValueError(f"not a flank: {side!r}")
+    pos_a, pos_b, flags = int(task["pos_a"]), int(task["pos_b"]), int(task["flags"])
+    a_back, b_back = bool(flags & 1), bool(flags & 2)         # (EXTEND_A_BACKWARDS, EXTEND_B_BACKWARDS)
+    runs = []                                                 # [op, p0, q0, bases of A, bases of B]
+    for _, p, q, op, base_a, base_b, _ in (ops.tolist() if hasattr(ops, "tolist") else ops):
+        if op not in (sub, dele, ins) or (op != ins and base_a > 3) or (op != dele and base_b > 3):
+            raise ValueError(f"not an edit op: {(p, q, op, base_a, base_b)}")
+        last = runs[-1] if runs else None
+        if last and last[0] == op == dele and p == last[1] + len(last[3]) and q == last[2]:
+            last[3] += "ACGT"[base_a]
+        elif last and last[0] == op == ins and p == last[1] and q == last[2] + len(last[4]):
+            last[4] += "ACGT"[base_b]
+        else:
+            runs.append([op, p, q, "" if op == ins else "ACGT"[base_a], "" if op == dele else "ACGT"[base_b]])
+    out = []
+    for op, p0, q0, seq_a, seq_b in runs:
+        if side == "left":
+            seq_a, seq_b = seq_a[::-1], seq_b[::-1]
+        out.append({"type": {sub: "snv", dele: "del", ins: "ins"}[op],
+                    "pos_a": pos_a - p0 - len(seq_a) + 1 if a_back else pos_a + p0,
+                    "pos_b": pos_b - q0 - len(seq_b) + 1 if b_back else pos_b + q0,
+                    "length": max(len(seq_a), len(seq_b)), "seq_a": seq_a or "-", "seq_b": seq_b or "-"})
+    return out[::-1] if side == "left" else out
+
+
+def end_variant_row(r):
+    "one line of the end variants table"
+    return "\t".join(str(r[c]) for c in END_VARIANT_COLUMNS)
+
+
+def end_variants_table(rows, k, rate, band, max_len, max_edits, ends_max_len, ends_max_edits, ends_penalty):
+    "TSV of block_ends' variant rows: a header, one line per event of every flank, then the footer of ends_table"
+    lines = ["\t".join(END_VARIANT_COLUMNS)] + [end_variant_row(r) for r in rows]
+    lines.append(f"# k {int(k)}, rate {int(rate)}, band {int(band)}, max_len {int(max_len)}, max_edits {int(max_edits)}, ends_max_len {int(ends_max_len)}, "
+                 f"ends_max_edits {int(ends_max_edits)}, ends_penalty {int(ends_penalty)}")
+    return "\n".join(lines) + "\n"
+
+
 def block_ends(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_RATE, band=IDENTITY_BAND, max_len=IDENTITY_MAX_LEN, max_edits=0,
-               ends_max_len=ENDS_MAX_LEN, ends_max_edits=ENDS_MAX_EDITS, ends_penalty=ENDS_PENALTY):
+               ends_max_len=ENDS_MAX_LEN, ends_max_edits=ENDS_MAX_EDITS, ends_penalty=ENDS_PENALTY, with_variants=False):
     """Per block and pair of its lines the base-exact breakpoints: from the first and the last aligned stretch of block_identity (the same
     pairs, anchors, segments and final per-segment results for the same first five parameters) the alignment is extended outwards
     with a free end -- at most ends_max_len bases and ends_max_edits edits, each edit costing ends_penalty against 2 for a match --
     past the block's own interval.  Returns dicts of ENDS_COLUMNS in block_identity's order.  Per round block_identity's edit calls
-    with the per-segment results and one nts_edit_extend over both flanks of all its pairs.  docs/design/04_20_block_ends.md."""
+    with the per-segment results and one nts_edit_extend over both flanks of all its pairs.  docs/design/04_20_block_ends.md.
+    with_variants: returns (those rows, variant rows) -- dicts of END_VARIANT_COLUMNS, the events (ends_events) of every flank with at
+    least one edit, pairs in the rows' order, the left flank before the right -- from one nts_edit_extend_script per round on that
+    round's tasks and results; a flank whose number of ops is not its left_edits or right_edits raises RuntimeError.
+    docs/design/04_21_block_end_variants.md."""
     message = check_identity_parameters(int(k), int(rate), int(band), int(max_len), int(max_edits)) or \
         check_ends_parameters(int(ends_max_len), int(ends_max_edits), int(ends_penalty))
     if message:
         raise ValueError(message)
     k, rate, band, max_len, max_edits = int(k), int(rate), int(band), int(max_len), int(max_edits)
     cap, limit, penalty = int(ends_max_len), int(ends_max_edits), int(ends_penalty)
-    pairs, length, found = [], {}, {}
+    pairs, length, found, events = [], {}, {}, {}
     for r in _identity_rounds(ctx, genomes_by_name, blocks, k, rate, band, max_len, pairs, length):
         _, final = ctx.edit_segments(r.g_a, r.g_b, r.iv_a, r.iv_b, r.segs, r.flip, band, with_distances=True)
         if max_edits > 0:
             _, final = ctx.edit_wide(r.g_a, r.g_b, r.iv_a, r.iv_b, r.segs, r.flip, band, max_edits, final)
         tasks, flanks = ends_tasks(r.segs, final, r.iv_a, r.iv_b, r.flip, r.lines, r.g_a.rec_len, r.g_b.rec_len, cap)
         results = ctx.edit_extend(r.g_a, r.g_b, tasks, penalty, limit)
+        if with_variants:
+            ops, first = ctx.edit_extend_script(r.g_a, r.g_b, tasks, results)
         for (la, lb, i), flank in zip(r.lines, flanks):
             found[(la, lb)] = ends_row(blocks[la], blocks[lb], r.iv_a[i], r.iv_b[i], bool(r.flip[i]), flank, tasks, results, cap, limit)
-    return [found[p] for p in pairs]
+            if not with_variants:
+                continue
+            events[(la, lb)] = []
+            for side in ("left", "right") if flank is not None else ():
+                t = flank[side]
+                mine = ops[int(first[t]):int(first[t + 1])]
+                if mine.size != int(results[t]["edits"]):
+                    raise RuntimeError(f"block {blocks[la].block_id}: {mine.size} ops for the {int(results[t]['edits'])} edits of a {side} flank")
+                events[(la, lb)] += [dict(e, flank=side) for e in ends_events(mine, tasks[t], side)]
+    rows = [found[p] for p in pairs]
+    if not with_variants:
+        return rows
+    variant_rows = []
+    for (la, lb), row in zip(pairs, rows):
+        head = {"block_id": row["block_id"], "genome_a": row["genome_a"], "contig_a": row["contig_a"], "genome_b": row["genome_b"],
+                "contig_b": row["contig_b"], "orientation": row["orientation"]}
+        variant_rows += [dict(head, **e) for e in events[(la, lb)]]
+    return rows, variant_rows
 
 
 def wide_variants_table(rows, k, rate, band, max_len, max_edits):
@@ -641,6 +723,8 @@ def main(argv=None):
                    "--variants-out [0]", type=int, default=0)
     p.add_argument("--ends-out", help="with --fastas: file for the per-block ends table (the base-exact breakpoints of every block and pair: how far the "
                    "alignment continues beyond the first and the last aligned stretch; GPU); it takes the --identity-* parameters")
+    p.add_argument("--end-variants-out", help="with --ends-out (which it needs): file for the per-block end variants table (the edits behind left_edits and "
+                   "right_edits of the ends table, as snv / ins / del events in both genomes' coordinates; GPU)")
     p.add_argument("--ends-max-len", help=f"longest flank that is extended, 1..65535 [{ENDS_MAX_LEN}]", type=int, default=ENDS_MAX_LEN)
     p.add_argument("--ends-max-edits", help=f"most edits within one flank, 1..1023 [{ENDS_MAX_EDITS}]", type=int, default=ENDS_MAX_EDITS)
     p.add_argument("--ends-penalty", help=f"what an edit costs the extension's score, against 2 for a matching pair of bases, 3..255 [{ENDS_PENALTY}]",
@@ -649,6 +733,8 @@ def main(argv=None):
     args = p.parse_args(argv)
     if args.k < 1 or args.s < 1:
         p.error("-k and -s must be positive")
+    if args.end_variants_out and not args.ends_out:
+        p.error("--end-variants-out: " + END_VARIANTS_NEED_ENDS)
     if args.ends_out:
         if not args.fastas:
             p.error("--ends-out needs the genomes: --fastas")
@@ -695,8 +781,14 @@ def main(argv=None):
                 fh.write(identity_table(id_rows, *id_args, max_edits=args.identity_max_edits))
         if args.ends_out:
             e_args = id_args + (args.identity_max_edits, args.ends_max_len, args.ends_max_edits, args.ends_penalty)
+            if args.end_variants_out:                         # (one pass gives both tables)
+                end_rows, end_variant_rows = block_ends(ctx, loaders, read_blocks(args.tsv), *e_args, with_variants=True)
+                with open(args.end_variants_out, "w", encoding="utf-8") as fh:
+                    fh.write(end_variants_table(end_variant_rows, *e_args))
+            else:
+                end_rows = block_ends(ctx, loaders, read_blocks(args.tsv), *e_args)
             with open(args.ends_out, "w", encoding="utf-8") as fh:
-                fh.write(ends_table(block_ends(ctx, loaders, read_blocks(args.tsv), *e_args), *e_args))
+                fh.write(ends_table(end_rows, *e_args))
     finally:
         ctx.close()
     if args.divergence_out:

@@ -847,6 +847,7 @@ namespace {
 #include "nts_edit_wide.inc"
 #include "nts_edit_wide_script.inc"
 #include "nts_edit_extend.inc"
+#include "nts_edit_extend_script.inc"
 } // namespace
 
 extern "C" int nts_iv_links(nts_ctx* ctx, uint32_t n_lists, const nts_sample* const* lists, const uint64_t* n, uint32_t min_anchors, nts_iv_link** out,
@@ -986,6 +987,23 @@ extern "C" int nts_edit_extend(nts_ctx* ctx, const nts_genome* g_a, const nts_ge
     return fail(ctx, NTS_EINVAL, "nts_edit_extend: bad arguments (penalty 3..255, max_edits 1..1023)");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   return edit_extend_run(ctx, g_a, g_b, tasks, n_tasks, penalty, max_edits, out);
+}
+
+extern "C" int nts_edit_extend_script(nts_ctx* ctx, const nts_genome* g_a, const nts_genome* g_b, const nts_extend_task* tasks, uint64_t n_tasks,
+                                      const nts_extend_result* results, uint64_t table_budget, nts_edit_op** ops, uint64_t* n_ops, uint64_t* first)
+{
+  if (!ctx || !g_a || !g_b || !ops || !n_ops || (n_tasks && (!tasks || !results))) return fail(ctx, NTS_EINVAL, "nts_edit_extend_script: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return edit_extend_script_run(ctx, g_a, g_b, tasks, n_tasks, results, table_budget, ops, n_ops, first);
+}
+
+extern "C" int nts_edit_extend_script_last_plan(nts_ctx* ctx, uint64_t* members, uint64_t* table_bytes, uint64_t* batches)
+{
+  if (!ctx) return NTS_EINVAL;
+  if (members) *members = ctx->last_escript_members;
+  if (table_bytes) *table_bytes = ctx->last_escript_table_bytes;
+  if (batches) *batches = ctx->last_escript_batches;
+  return NTS_OK;
 }
 
 extern "C" int nts_graph_budget(nts_ctx* ctx, uint64_t bytes)

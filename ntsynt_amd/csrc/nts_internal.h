@@ -516,6 +516,7 @@ struct nts_ctx
   uint32_t last_graph_v_slices = 0, last_graph_e_slices = 0, last_graph_oversize = 0;
   uint64_t last_graph_peak = 0;
   uint64_t last_wscript_members = 0, last_wscript_table_bytes = 0, last_wscript_batches = 0; // nts_edit_wide_script_last_plan
+  uint64_t last_escript_members = 0, last_escript_table_bytes = 0, last_escript_batches = 0; // nts_edit_extend_script_last_plan
   uint64_t graph_live0 = 0; // library bytes live when the running build's call began
   // the last nts_minhash_intervals (nts_minhash_iv.inc): sweeps of its slowest chunk, chunks, sweeps in all
   uint32_t last_mhi_passes = 0, last_mhi_chunks = 0;

@@ -364,6 +364,34 @@ class Context:
                                             out.ctypes.data if out.size else None), "nts_edit_extend")
         return out
 
+    def edit_extend_script(self, genome_a, genome_b, tasks, results, table_budget=0):
+        """the edits of the extended flanks (nts_edit_extend_script): the tasks of edit_extend and the results it returned for them.  For
+        task t the canonical script (as edit_script defines it) of the first ext_a bases of its string A and the first ext_b bases of
+        its string B, both as edit_extend reads them.  Returns (ops, first): an OP_DTYPE array with task t's `edits` ops at
+        ops[first[t]:first[t + 1]], seg = t, p and q offsets in the strings as read, base_b complemented as read.  table_budget: the
+        bytes the tasks' furthest-reaching tables may take at once (0 = 1 GiB; at least 4 (Dmax + 1)^2 for the largest `edits`); the
+        result does not depend on it.  Results that are not the tasks' own are refused.  Exact and deterministic."""
+        tk = np.ascontiguousarray(tasks, dtype=TASK_DTYPE)
+        rs = np.ascontiguousarray(results, dtype=EXTEND_DTYPE)
+        if tk.ndim != 1 or rs.shape != tk.shape:
+            raise ValueError("edit_extend_script: a list of tasks and one result per task")
+        if int(table_budget) < 0:
+            raise ValueError("edit_extend_script: table_budget is a number of bytes, 0 for the default")
+        assert TASK_DTYPE.itemsize == ctypes.sizeof(_lib.ExtendTask) and EXTEND_DTYPE.itemsize == ctypes.sizeof(_lib.ExtendResult)
+        assert OP_DTYPE.itemsize == ctypes.sizeof(_lib.EditOp)
+        first = np.zeros(tk.size + 1, dtype=np.uint64)
+        p, m = c_vp(), u64()
+        self.check(self.lib.nts_edit_extend_script(self.h, genome_a.h, genome_b.h, tk.ctypes.data if tk.size else None, tk.size,
+                                                   rs.ctypes.data if rs.size else None, int(table_budget), ctypes.byref(p), ctypes.byref(m),
+                                                   first.ctypes.data), "nts_edit_extend_script")
+        return self._take(p, m.value, OP_DTYPE), first
+
+    def edit_extend_script_last_plan(self):
+        "dict(members, table_bytes, batches) of the last edit_extend_script on this context (nts_edit_extend_script_last_plan)"
+        a, b, c = u64(), u64(), u64()
+        self.check(self.lib.nts_edit_extend_script_last_plan(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "nts_edit_extend_script_last_plan")
+        return {"members": a.value, "table_bytes": b.value, "batches": c.value}
+
     def timing(self, name):
         ms, n = ctypes.c_double(), u64()
         self.check(self.lib.nts_timing(self.h, name.encode(), ctypes.byref(ms), ctypes.byref(n)), "nts_timing")

@@ -497,7 +497,8 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         benchmark=False, log=print, ctx=None, backend=None, bf_rounding="up", bf_signature=BF_SIGNATURE, dev=False, interarrivals=False, repeat=False,
         mx_tsvs=None, common_file=None, m=90, n=0, initial_only=False, write_fai=True, engine="device", refine_repeat_file=None, screen_repeat_file=None,
         graph_budget=None, assess=None, gaps=False, gap_links=None, gap_block_links=False, gap_copies=None, gap_copy_sites=None,
-        gap_periods=None, gap_families=None, block_identity=None, block_variants=None, block_wide_variants=None, block_ends=None):
+        gap_periods=None, gap_families=None, block_identity=None, block_variants=None, block_wide_variants=None, block_ends=None,
+        block_end_variants=False):
     """FASTA paths -> engine (outputs in .outputs and in the CWD).  Mirrors oracle.synteny_oracle.run_pipeline's
     signature so the parity tests read alike.  Under torch.distributed (WORLD_SIZE > 1, process group already
     initialised by the caller) genomes are sharded over the ranks.
@@ -534,7 +535,10 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
     :edit_wide_script_plan / :edit_wide_script.  block_ends = (ends_max_len, ends_max_edits, ends_penalty), optionally followed by the
     identity parameters (k, rate, band, max_len[, max_edits]) -- without them those of block_identity when that is given, else the
     defaults: behind the other block files, <prefix>.block_ends.tsv (assess.block_ends: the base-exact breakpoints of every block and
-    pair; one rank only; it needs none of the other switches); with `benchmark` the stage times gain block_ends:edit_extend."""
+    pair; one rank only; it needs none of the other switches); with `benchmark` the stage times gain block_ends:edit_extend.
+    block_end_variants: needs block_ends; from that stage's own pass also <prefix>.block_end_variants.tsv (assess.block_ends with
+    with_variants: the edits of every extended flank); with `benchmark` the stage times gain block_ends:edit_extend_script_plan and
+    block_ends:edit_extend_script."""
     prefix = prefix or f"ntSynt.k{k}.w{w}"
     if mx_tsvs is not None and len(mx_tsvs) != len(fastas):
         raise ValueError("one minimizer TSV per FASTA file")
@@ -609,6 +613,9 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         message = check_ends_parameters(*block_ends[:3]) or check_identity_parameters(*block_ends[3:])
         if message:
             raise ValueError("block_ends = (ends_max_len, ends_max_edits, ends_penalty[, k, rate, band, max_len[, max_edits]]): " + message)
+    if block_end_variants and block_ends is None:
+        from .assess import END_VARIANTS_NEED_ENDS
+        raise ValueError("block_end_variants: " + END_VARIANTS_NEED_ENDS)
     if gap_block_links and gap_links is None:
         raise ValueError("gap_block_links needs gap_links = (rate, min_anchors)")
     if gap_block_links and len(fastas) > 32:
@@ -1208,16 +1215,24 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         from . import assess as assess_
         if benchmark:                                         # (device events around the calls of this stage only)
             backend.ctx.profile(True)
-            ends_before = backend.ctx.timing("edit_extend")[0]
+            ends_timers = ("edit_extend",) + (("edit_extend_script_plan", "edit_extend_script") if block_end_variants else ())
+            ends_before = {name: backend.ctx.timing(name)[0] for name in ends_timers}
         e_args = block_ends[3:] + block_ends[:3]
-        rows = assess_.block_ends(backend.ctx, {fa.basename(p): genomes[p] for p in fastas}, assess_.read_blocks(f"{prefix}.synteny_blocks.tsv"), *e_args)
+        rows = assess_.block_ends(backend.ctx, {fa.basename(p): genomes[p] for p in fastas}, assess_.read_blocks(f"{prefix}.synteny_blocks.tsv"), *e_args,
+                                  with_variants=bool(block_end_variants))
+        if block_end_variants:
+            rows, end_variant_rows = rows
+            text = assess_.end_variants_table(end_variant_rows, *e_args)
+            with open(f"{prefix}.block_end_variants.tsv", "w", encoding="utf-8") as fh:
+                fh.write(text)
+            eng.outputs[f"{prefix}.block_end_variants.tsv"] = text
         text = assess_.ends_table(rows, *e_args)
         with open(f"{prefix}.block_ends.tsv", "w", encoding="utf-8") as fh:
             fh.write(text)
         eng.outputs[f"{prefix}.block_ends.tsv"] = text
         st.stop()
         if benchmark:
-            st.rows.append(("block_ends:edit_extend", (backend.ctx.timing("edit_extend")[0] - ends_before) * 1e-3))
+            st.rows += [(f"block_ends:{name}", (backend.ctx.timing(name)[0] - ends_before[name]) * 1e-3) for name in ends_timers]
             backend.ctx.profile(False)
         st.mark("block_ends_done")
     if gaps:
