@@ -820,6 +820,41 @@ int nts_edit_extend_script(nts_ctx* ctx, const nts_genome* g_a, const nts_genome
                            const nts_extend_result* results, uint64_t table_budget, nts_edit_op** ops, uint64_t* n_ops, uint64_t* first);
 int nts_edit_extend_script_last_plan(nts_ctx* ctx, uint64_t* members, uint64_t* table_bytes, uint64_t* batches);
 
+/* ---- one CIGAR per chain of aligned pieces: block alignments ----------------------------------------------------------
+ * nts_cigar_build: pieces = n_pieces pieces in chain order, ops = the ops of all pieces one behind the other, first (n_pieces + 1 host
+ *   entries): piece t's ops are first[t] .. first[t + 1] - 1, first[n_pieces] = the number of ops.  A PIECE is two strings of n and m
+ *   bases (0 allowed) and its D ops in ascending path order with seg = t and p, q local to the piece: what nts_edit_script,
+ *   nts_edit_wide_script and nts_edit_extend_script deliver per segment or task.  Its COLUMNS: from (i, j) = (0, 0) every op gives
+ *   g = p - i = q - j >= 0 columns `=` and then one column X for SUB (p < n, q < m; to (p + 1, q + 1)), D for DEL (p < n, q <= m; to
+ *   (p + 1, q)) or I for INS (p <= n, q < m; to (p, q + 1)); behind the last op n - i = m - j >= 0 columns `=`.  A piece with
+ *   NTS_CIG_REVERSED contributes its columns in reverse order (a flank that was read backwards).  A CHAIN is the concatenation of the
+ *   columns of its pieces in the order given; its CIGAR is their run-length encoding: maximal runs of one kind, none of length 0, runs
+ *   never merge across chains.  *cigar (release with nts_free; NULL for none), *n_cigar entries len << 4 | code with BAM's codes I 1,
+ *   D 2, = 7, X 8, the chains one behind the other; a length may exceed 2^32.  chains (n_chains entries, all written): first and n_cig
+ *   locate the chain's entries, eq / x / ins / del are its columns of each kind, len_a = eq + x + del = the sum of n, len_b =
+ *   eq + x + ins = the sum of m; a chain without columns is 0 but for first = the entries of all chains before it.  No genome is
+ *   read.  NTS_ERANGE before any launch for 2^32 pieces or chains or more, for 2 n_ops + n_pieces >= 2^32, or for lengths that add
+ *   up to 2^60 or more.  NTS_EINVAL before any launch, with nothing written and the smallest offending piece named: chain not
+ *   nondecreasing or >= n_chains, unknown flag bits, first not nondecreasing from 0.  NTS_EINVAL after the launch, with no CIGAR
+ *   returned and chains untouched ("ops of piece ... are no script of its lengths", the smallest such index): an op whose seg is
+ *   not its piece's index, an op code outside 1..3, any violation of the column rules.  No piece: no launch.  One lane per op and one
+ *   per piece turn ops into (kind, length) atoms, a minimum reduction of the per-lane status (timer "cigar_atoms"); a selection drops
+ *   the empty atoms, a reduction by (chain, kind) merges the runs, a reduction by chain and a scan give the records (timer
+ *   "cigar_merge").  On the context's stream, in its workspace; no atomic, no launch per piece or chain, no floating point: the same
+ *   input gives the same bytes.  docs/design/04_22_block_alignments.md; csrc/nts_cigar.inc; ntsynt_amd/assess.py block_alignments,
+ *   `ntSynt --block-paf`, `bin/ntsynt_block_stats --paf-out`. */
+#define NTS_CIG_REVERSED 1u
+typedef struct
+{
+  uint32_t chain, n, m, flags;
+} nts_cig_piece;
+typedef struct
+{
+  uint64_t first, n_cig, eq, x, ins, del, len_a, len_b;
+} nts_cig_chain;
+int nts_cigar_build(nts_ctx* ctx, const nts_cig_piece* pieces, uint64_t n_pieces, uint64_t n_chains, const nts_edit_op* ops, const uint64_t* first,
+                    uint64_t** cigar, uint64_t* n_cigar, nts_cig_chain* chains);
+
 /* ---- C1-C5: minimizer graph -> collinear chains -----------------------------------------------------
  * replaces ntjoin_utils.read_minimizers' duplicate removal, filter_minimizers and build_graph
  * (call sites bin/ntsynt_synteny.py:607-612, 483, 539) and the path walk of Ntjoin.find_paths

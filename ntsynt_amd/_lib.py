@@ -77,6 +77,16 @@ class ExtendResult(ctypes.Structure):
     _fields_ = [(n, u32) for n in ("ext_a", "ext_b", "edits", "valid_a", "valid_b")]
 
 
+class CigPiece(ctypes.Structure):
+    "nts_cig_piece: one aligned piece of a chain (nts_cigar_build)"
+    _fields_ = [(n, u32) for n in ("chain", "n", "m", "flags")]
+
+
+class CigChain(ctypes.Structure):
+    "nts_cig_chain: where one chain's CIGAR entries lie and its columns of each kind (nts_cigar_build)"
+    _fields_ = [(n, u64) for n in ("first", "n_cig", "eq", "x", "ins", "del", "len_a", "len_b")]
+
+
 class MxList(ctypes.Structure):
     _fields_ = [("h1", c_vp), ("rec", c_vp), ("pos", c_vp), ("keep", c_vp), ("list_id", c_vp), ("n", u64)]
 
@@ -243,6 +253,7 @@ SYMBOLS = [
     ("nts_edit_wide_script_last_plan", ctypes.c_int, [c_vp, c_u64p, c_u64p, c_u64p]),
     ("nts_edit_extend_script", ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, u64, c_vp, u64, ctypes.POINTER(c_vp), c_u64p, c_vp]),
     ("nts_edit_extend_script_last_plan", ctypes.c_int, [c_vp, c_u64p, c_u64p, c_u64p]),
+    ("nts_cigar_build", ctypes.c_int, [c_vp, c_vp, u64, u64, c_vp, c_vp, ctypes.POINTER(c_vp), c_u64p, c_vp]),
     ("nts_genome_valid_bases", ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(Interval), u64, c_vp]),
     ("nts_minhash_pairs", ctypes.c_int, [c_vp, u32, c_vp, c_vp, u64, c_vp, c_vp, u64, c_vp, c_vp]),
     ("nts_graph_build", ctypes.c_int, [c_vp, u32, ctypes.POINTER(MxList), ctypes.POINTER(Graph)]),

@@ -20,7 +20,10 @@ Two things, both over `<prefix>.synteny_blocks.tsv`:
   docs/design/04_20_block_ends.md.
 * block end variants (`ntSynt --block-ends --block-end-variants`, `ntsynt_block_stats --ends-out F --end-variants-out G`): the edits
   behind left_edits and right_edits -- the canonical script of every extended flank (nts_edit_extend_script), as snv / ins / del
-  events in both genomes' coordinates; docs/design/04_21_block_end_variants.md."""
+  events in both genomes' coordinates; docs/design/04_21_block_end_variants.md.
+* block alignments (`ntSynt --block-paf`, `ntsynt_block_stats --paf-out`): one PAF record with a cg:Z: CIGAR per aligned chain of every
+  block and pair -- the scripts of all stretches and flanks stitched and run-length merged on the GPU (nts_cigar_build);
+  docs/design/04_22_block_alignments.md."""
 import os
 import re
 from collections import namedtuple
@@ -621,6 +624,214 @@ def block_ends(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_RATE, b
     return rows, variant_rows
 
 
+def alignment_pieces(segs, final, lines, flanks=None, results=None):
+    """The chains of one round and the pieces nts_cigar_build stitches them from.  segs: the round's SEGMENT_DTYPE array in iv_a order,
+    final: its final per-segment results; lines: (line a, line b, index of a's interval); flanks / results: what ends_tasks and
+    nts_edit_extend made of the round, or None for chains without flanks.  A CHAIN is a maximal run of consecutive segments of one
+    interval whose result is a distance (contiguous in x and y: a segment ends at the anchor the next one begins at); every other
+    segment ends a chain and belongs to none.  One piece per segment of a chain, n = dx, m = dy; with flanks the left one is a reversed
+    piece (n = ext_a, m = ext_b) in front of the pair's first chain and the right one a forward piece behind its last.  Returns
+    (pieces, source, chains): a PIECE_DTYPE array in chain order; source[t] = the segment piece t stands for, or -1 - task for a flank;
+    chains = dict of int64 arrays, one entry per chain in (iv_a, x) order -- line = index into `lines`, ch = the chain's number
+    within its pair, x0, x1, y0, y1 = its oriented offsets, flanks included (they may leave the interval).  Pure."""
+    import numpy as np
+    from .device import CIG_REVERSED, EDIT_INVALID, PIECE_DTYPE
+    n = len(segs)
+    iv = segs["iv_a"].astype(np.int64)
+    line_of = np.full(max([i for _, _, i in lines] + [int(iv.max()) if n else 0]) + 1, -1, dtype=np.int64)
+    for q, (_, _, i) in enumerate(lines):
+        line_of[i] = q
+    aligned = (np.asarray(final, dtype=np.uint32) < EDIT_INVALID) & (line_of[iv] >= 0)
+    follows = np.zeros(n, dtype=bool)                         # the segment in front is aligned and of the same interval
+    follows[1:] = aligned[:-1] & (iv[1:] == iv[:-1])
+    opens = aligned & ~follows
+    chain_of = np.cumsum(opens) - 1                           # (where aligned)
+    members = np.flatnonzero(aligned)
+    heads = np.flatnonzero(opens)
+    tails = members[np.append(chain_of[members][1:] != chain_of[members][:-1], True)] if members.size else members
+    x, dx, y, dy = (segs[f].astype(np.int64) for f in ("x", "dx", "y_lo", "dy"))
+    inner = members[follows[members]]
+    if np.any(x[inner] != x[inner - 1] + dx[inner - 1]) or np.any(y[inner] != y[inner - 1] + dy[inner - 1]):
+        raise ValueError("two consecutive aligned segments of an interval are not contiguous")
+    line = line_of[iv[heads]]
+    first_of_pair = np.append(True, line[1:] != line[:-1]) if heads.size else np.zeros(0, dtype=bool)
+    last_of_pair = np.append(line[1:] != line[:-1], True) if heads.size else np.zeros(0, dtype=bool)
+    number = np.arange(heads.size, dtype=np.int64)
+    chains = {"line": line, "ch": number - np.maximum.accumulate(np.where(first_of_pair, number, 0)), "x0": x[heads].copy(), "x1": x[tails] + dx[tails],
+              "y0": y[heads].copy(), "y1": y[tails] + dy[tails]}
+    chain, size_n, size_m, flags, source, rank = chain_of[members], dx[members], dy[members], np.zeros(members.size, dtype=np.int64), members, \
+        np.ones(members.size, dtype=np.int64)
+    if flanks is not None:
+        extra = []                                            # (chain, n, m, flags, source, rank: left 0 < segments 1 < right 2)
+        for c in np.flatnonzero(first_of_pair | last_of_pair).tolist():
+            flank = flanks[int(line[c])]
+            if flank is None:
+                raise ValueError("a pair with an aligned segment has no flanks")
+            if first_of_pair[c]:
+                if (flank["x_l"], flank["y_l"]) != (int(chains["x0"][c]), int(chains["y0"][c])):
+                    raise ValueError("the left flank does not start at the pair's first chain")
+                r = results[flank["left"]]
+                extra.append((c, int(r["ext_a"]), int(r["ext_b"]), CIG_REVERSED, -1 - flank["left"], 0))
+                chains["x0"][c] -= int(r["ext_a"])
+                chains["y0"][c] -= int(r["ext_b"])
+            if last_of_pair[c]:
+                if (flank["x_r"], flank["y_r"]) != (int(chains["x1"][c]), int(chains["y1"][c])):
+                    raise ValueError("the right flank does not start at the pair's last chain")
+                r = results[flank["right"]]
+                extra.append((c, int(r["ext_a"]), int(r["ext_b"]), 0, -1 - flank["right"], 2))
+                chains["x1"][c] += int(r["ext_a"])
+                chains["y1"][c] += int(r["ext_b"])
+        if extra:
+            more = np.array(extra, dtype=np.int64)
+            chain, size_n, size_m, flags, source, rank = (np.concatenate([v, more[:, j]]) for j, v in enumerate((chain, size_n, size_m, flags, source, rank)))
+    order = np.lexsort((source, rank, chain))                 # (segments of a chain ascend by index; a chain has at most one flank of a side)
+    pieces = np.zeros(order.size, dtype=PIECE_DTYPE)
+    pieces["chain"], pieces["n"], pieces["m"], pieces["flags"] = chain[order], size_n[order], size_m[order], flags[order]
+    return pieces, source[order], chains
+
+
+def alignment_ops(source, segment_scripts, flank_script=None):
+    """The ops of alignment_pieces' pieces, re-based: segment_scripts = the (ops, first) pairs of the script calls over the round's
+    segments -- a segment's ops are those of the LAST pair that holds any for it (nts_edit_script, then nts_edit_wide_script: no segment
+    has ops from both); flank_script = (ops, first) of nts_edit_extend_script over the round's tasks.  Returns (ops, first) for
+    nts_cigar_build: piece t's ops at ops[first[t]:first[t + 1]] with seg = t.  Pure; one gather, no loop over pieces or ops."""
+    import numpy as np
+    from .device import OP_DTYPE
+    source = np.asarray(source, dtype=np.int64)
+    start, count = np.zeros(source.size, dtype=np.int64), np.zeros(source.size, dtype=np.int64)
+    parts, base = [], 0
+    is_seg = source >= 0
+    for ops, first in segment_scripts:
+        first = np.asarray(first).astype(np.int64)
+        have = np.diff(first)[source[is_seg]]
+        take = np.flatnonzero(is_seg)[have > 0]
+        start[take], count[take] = base + first[source[take]], have[have > 0]
+        parts.append(ops)
+        base += len(ops)
+    if flank_script is not None and np.any(~is_seg):
+        ops, first = flank_script
+        first = np.asarray(first).astype(np.int64)
+        task = -1 - source[~is_seg]
+        start[~is_seg], count[~is_seg] = base + first[task], np.diff(first)[task]
+        parts.append(ops)
+    out_first = np.concatenate([[0], np.cumsum(count)]).astype(np.uint64)
+    total = int(out_first[-1])
+    if total == 0:
+        return np.zeros(0, dtype=OP_DTYPE), out_first
+    everything = np.concatenate(parts)
+    index = np.repeat(start - out_first[:-1].astype(np.int64), count) + np.arange(total, dtype=np.int64)
+    out = everything[index]
+    out["seg"] = np.repeat(np.arange(source.size, dtype=np.uint32), count)
+    return out, out_first
+
+
+PAF_TAGS = ("NM:i:", "bi:i:", "tg:Z:", "qg:Z:", "ch:i:", "cg:Z:")
+
+
+def cigar_texts(cigar, first, n_cig):
+    """the cg:Z: strings of several chains at once: cigar = CIGAR entries len << 4 | code (I 1, D 2, = 7, X 8), chain c's at
+    cigar[first[c]:first[c] + n_cig[c]].  Array operations over all entries (the numbers as fixed-width byte strings, the letters
+    appended, the padding taken out of the whole buffer at once) and one slice per chain: no Python loop over entries.  Pure."""
+    import numpy as np
+    cigar = np.ascontiguousarray(cigar, dtype=np.uint64)
+    first, n_cig = np.asarray(first).astype(np.int64), np.asarray(n_cig).astype(np.int64)
+    if cigar.size == 0:
+        return ["" for _ in range(first.size)]
+    letters = np.full(16, b"?", dtype="S1")
+    letters[[1, 2, 7, 8]] = [b"I", b"D", b"=", b"X"]
+    tokens = np.char.add((cigar >> np.uint64(4)).astype("S20"), letters[(cigar & np.uint64(15)).astype(np.int64)])
+    if np.any(tokens.view("S1").reshape(tokens.size, -1)[np.arange(tokens.size), np.char.str_len(tokens) - 1] == b"?"):
+        raise ValueError("a CIGAR entry with a code that is not I, D, = or X")
+    at = np.concatenate([[0], np.cumsum(np.char.str_len(tokens))])
+    text = tokens.tobytes().replace(b"\0", b"").decode()
+    return [text[at[a]:at[a + n]] for a, n in zip(first.tolist(), n_cig.tolist())]
+
+
+def cigar_text(entries):
+    "the cg:Z: string of one chain's CIGAR entries"
+    return cigar_texts(entries, [0], [len(entries)])[0]
+
+
+def paf_row(ra, rb, rec_len_a, rec_len_b, iv_a, iv_b, flipped, ch, span, record, entries):
+    """one chain's PAF line (no newline).  ra / rb: the two block lines (a is the target, b the query), rec_len_*: the lengths of their
+    records, iv_a / iv_b: their clipped (rec, start, end); span = (x0, x1, y0, y1), the chain's oriented offsets, flanks included;
+    record: its nts_cig_chain fields (eq, x, ins, del), entries: its CIGAR entries, in a's forward order, or their cg:Z: text when
+    the caller made the texts of many chains at once (cigar_texts).  Coordinates are 0-based and
+    half-open on the forward strand of the records: for a `-` pair the query interval is mirrored inside b's interval.  Pure."""
+    x0, x1, y0, y1 = (int(v) for v in span)
+    start_a, start_b, len_b = int(iv_a[1]), int(iv_b[1]), int(iv_b[2]) - int(iv_b[1])
+    eq, x, ins, dele = (int(record[f]) for f in ("eq", "x", "ins", "del"))
+    q_from, q_to = (start_b + len_b - y1, start_b + len_b - y0) if flipped else (start_b + y0, start_b + y1)
+    fields = [rb.contig, int(rec_len_b), q_from, q_to, "-" if flipped else "+", ra.contig, int(rec_len_a), start_a + x0, start_a + x1, eq, eq + x + ins + dele,
+              255, f"NM:i:{x + ins + dele}", f"bi:i:{ra.block_id}", f"tg:Z:{ra.genome}", f"qg:Z:{rb.genome}", f"ch:i:{int(ch)}",
+              "cg:Z:" + (entries if isinstance(entries, str) else cigar_text(entries))]
+    return "\t".join(str(f) for f in fields)
+
+
+def paf_table(rows):
+    "the PAF text of block_alignments' rows: one line per chain, no header and no footer (PAF has no comment syntax every reader accepts)"
+    return "".join(r + "\n" for r in rows)
+
+
+def block_alignments(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_RATE, band=IDENTITY_BAND, max_len=IDENTITY_MAX_LEN, max_edits=0, ends=None):
+    """One PAF record with a cg:Z: CIGAR per aligned chain of every block and pair of its lines (target = line a, query = line b): the
+    anchors, segments and final per-segment results of block_identity for the same first five parameters, the canonical scripts of
+    block_variants / block_wide_variants, and with ends = (ends_max_len, ends_max_edits, ends_penalty) the flanks of block_ends attached
+    to each pair's first and last chain.  A pass of its own over the rounds: per round nts_edit_segments with the per-segment
+    distances, for max_edits > 0 nts_edit_wide and both script calls, else nts_edit_script alone, with ends nts_edit_extend and
+    nts_edit_extend_script, then ONE nts_cigar_build for all pairs of the round.  Returns paf_row's lines: blocks and pairs in
+    block_identity's order, a pair's chains ascending by x; a pair without an aligned segment has none.  Per pair the NM of its chains
+    less the flanks' edits must be the identity pass's `edits`, and the target and query bases less the flanks' must be aligned_a and
+    aligned_b: RuntimeError otherwise.  docs/design/04_22_block_alignments.md."""
+    import numpy as np
+    message = check_identity_parameters(int(k), int(rate), int(band), int(max_len), int(max_edits)) or \
+        (check_ends_parameters(*(int(v) for v in ends)) if ends is not None else None)
+    if message:
+        raise ValueError(message)
+    k, rate, band, max_len, max_edits = int(k), int(rate), int(band), int(max_len), int(max_edits)
+    pairs, length, found = [], {}, {}
+    for r in _identity_rounds(ctx, genomes_by_name, blocks, k, rate, band, max_len, pairs, length):
+        per_iv, dist = ctx.edit_segments(r.g_a, r.g_b, r.iv_a, r.iv_b, r.segs, r.flip, band, with_distances=True)
+        final = dist
+        scripts = [ctx.edit_script(r.g_a, r.g_b, r.iv_a, r.iv_b, r.segs, r.flip, band, dist)]
+        if max_edits > 0:
+            per_iv, final = ctx.edit_wide(r.g_a, r.g_b, r.iv_a, r.iv_b, r.segs, r.flip, band, max_edits, dist)
+            scripts.append(ctx.edit_wide_script(r.g_a, r.g_b, r.iv_a, r.iv_b, r.segs, r.flip, band, max_edits, final))
+            if np.any((np.diff(scripts[0][1].astype(np.int64)) > 0) & (np.diff(scripts[1][1].astype(np.int64)) > 0)):
+                raise RuntimeError("a segment has ops from both script calls")
+        tasks = flanks = results = flank_script = None
+        if ends is not None:
+            tasks, flanks = ends_tasks(r.segs, final, r.iv_a, r.iv_b, r.flip, r.lines, r.g_a.rec_len, r.g_b.rec_len, int(ends[0]))
+            results = ctx.edit_extend(r.g_a, r.g_b, tasks, int(ends[2]), int(ends[1]))
+            flank_script = ctx.edit_extend_script(r.g_a, r.g_b, tasks, results)
+        pieces, source, chains = alignment_pieces(r.segs, final, r.lines, flanks, results)
+        ops, first = alignment_ops(source, scripts, flank_script)
+        n_chains = int(chains["line"].size)
+        cigar, records = ctx.cigar_build(pieces, ops, first, n_chains)
+        texts = cigar_texts(cigar, records["first"], records["n_cig"])
+        # per pair: its chains (one grouping of all chains by line) and the sums of their records
+        line, n_lines = chains["line"], len(r.lines)
+        by_line = np.argsort(line, kind="stable")
+        cut = np.searchsorted(line[by_line], np.arange(n_lines + 1))
+        sums = np.zeros((3, n_lines), dtype=np.int64)         # NM, target bases, query bases
+        for row, values in enumerate((records["x"] + records["ins"] + records["del"], records["len_a"], records["len_b"])):
+            np.add.at(sums[row], line, values.astype(np.int64))
+        for q, (la, lb, i) in enumerate(r.lines):
+            mine = by_line[cut[q]:cut[q + 1]].tolist()
+            flank = flanks[q] if flanks is not None else None
+            extra = [results[flank[side]] for side in ("left", "right")] if flank is not None else []
+            nm, bases_a, bases_b = (int(v) for v in sums[:, q])
+            if (nm - sum(int(e["edits"]) for e in extra), bases_a - sum(int(e["ext_a"]) for e in extra), bases_b - sum(int(e["ext_b"]) for e in extra)) != \
+                    (int(per_iv[i]["edits"]), int(per_iv[i]["aligned_a"]), int(per_iv[i]["aligned_b"])):
+                raise RuntimeError(f"block {blocks[la].block_id}: the chains of {blocks[la].genome} and {blocks[lb].genome} hold {nm} edits over {bases_a} and "
+                                   f"{bases_b} bases, the identity pass {int(per_iv[i]['edits'])} over {int(per_iv[i]['aligned_a'])} and "
+                                   f"{int(per_iv[i]['aligned_b'])} (flanks: {[tuple(int(v) for v in e) for e in extra]})")
+            rec_len_a, rec_len_b = int(r.g_a.rec_len[int(r.iv_a[i][0])]), int(r.g_b.rec_len[int(r.iv_b[i][0])])
+            found[(la, lb)] = [paf_row(blocks[la], blocks[lb], rec_len_a, rec_len_b, r.iv_a[i], r.iv_b[i], bool(r.flip[i]), chains["ch"][c],
+                                       [chains[f][c] for f in ("x0", "x1", "y0", "y1")], records[c], texts[c]) for c in mine]
+    return [row for p in pairs for row in found[p]]
+
+
 def wide_variants_table(rows, k, rate, band, max_len, max_edits):
     """TSV of block_wide_variants' variant rows: the columns and the order of variants_table, every event of every aligned stretch,
     narrow and wide, then `# k K, rate R, band W, max_len L, max_edits E`"""
@@ -725,6 +936,9 @@ def main(argv=None):
                    "alignment continues beyond the first and the last aligned stretch; GPU); it takes the --identity-* parameters")
     p.add_argument("--end-variants-out", help="with --ends-out (which it needs): file for the per-block end variants table (the edits behind left_edits and "
                    "right_edits of the ends table, as snv / ins / del events in both genomes' coordinates; GPU)")
+    p.add_argument("--paf-out", help="with --fastas: file for the block alignments (one PAF record with a cg:Z: CIGAR per aligned chain of every block and "
+                   "pair; GPU); it takes the --identity-* parameters, --identity-max-edits included, and with --ends-out the --ends-* parameters: the "
+                   "flanks are attached")
     p.add_argument("--ends-max-len", help=f"longest flank that is extended, 1..65535 [{ENDS_MAX_LEN}]", type=int, default=ENDS_MAX_LEN)
     p.add_argument("--ends-max-edits", help=f"most edits within one flank, 1..1023 [{ENDS_MAX_EDITS}]", type=int, default=ENDS_MAX_EDITS)
     p.add_argument("--ends-penalty", help=f"what an edit costs the extension's score, against 2 for a matching pair of bases, 3..255 [{ENDS_PENALTY}]",
@@ -740,6 +954,12 @@ def main(argv=None):
             p.error("--ends-out needs the genomes: --fastas")
         message = check_identity_parameters(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits) or \
             check_ends_parameters(args.ends_max_len, args.ends_max_edits, args.ends_penalty)
+        if message:
+            p.error(message)
+    if args.paf_out:
+        if not args.fastas:
+            p.error("--paf-out needs the genomes: --fastas")
+        message = check_identity_parameters(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits)
         if message:
             p.error(message)
     if args.identity_out or args.variants_out or args.wide_variants_out:
@@ -789,6 +1009,11 @@ def main(argv=None):
                 end_rows = block_ends(ctx, loaders, read_blocks(args.tsv), *e_args)
             with open(args.ends_out, "w", encoding="utf-8") as fh:
                 fh.write(ends_table(end_rows, *e_args))
+        if args.paf_out:
+            paf_rows = block_alignments(ctx, loaders, read_blocks(args.tsv), *id_args, max_edits=args.identity_max_edits,
+                                        ends=(args.ends_max_len, args.ends_max_edits, args.ends_penalty) if args.ends_out else None)
+            with open(args.paf_out, "w", encoding="utf-8") as fh:
+                fh.write(paf_table(paf_rows))
     finally:
         ctx.close()
     if args.divergence_out:

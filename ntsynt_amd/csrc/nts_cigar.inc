@@ -1,0 +1,308 @@
+// ---- one CIGAR per chain of aligned pieces (nts_cigar_build; ntsynt_amd/assess.py block_alignments) ----
+// docs/design/04_22_block_alignments.md.  Input: n_pieces pieces {chain, n, m, flags} in chain order, the ops of all pieces one behind
+// the other (what the three script calls deliver, seg = the piece's index, p and q local to the piece) and first[n_pieces + 1].  A piece
+// with D ops owns 2 D + 1 ATOMS: match run, op, match run, ..., trailing match run; piece t's atoms lie at slots 2 first[t] + t ..
+// 2 first[t + 1] + t, mirrored for a reversed piece.  An atom is {len << 4 | code, chain}: the encoding of a CIGAR entry.
+//   1  k_cig_atoms: one lane per op and one per piece (the trailing run).  A lane reads the previous op of its piece, checks the column
+//      rules and stores its atoms; a lane whose ops break a rule stores empty atoms and its piece's index in the status array.  A
+//      minimum reduction of the status array names the smallest offending piece (timer "cigar_atoms").
+//   2  rocprim::select drops the atoms of length 0; the host reads the status and the number M of atoms that are left.
+//   3  rocprim::reduce_by_key over (chain, code) adds the lengths of every maximal run of one kind inside one chain: the entries;
+//      k_cig_emit packs them.  A second rocprim::reduce_by_key over the chain adds up, per chain, the heads (atoms whose (chain, code)
+//      differs from their predecessor's) and the columns of each kind; k_cig_chain_sums stores the sums at their chain, an exclusive
+//      scan of the entry counts over ALL chains gives `first`, k_cig_chains writes the records (timer "cigar_merge").
+// No genome is read.  No atomic, no launch per piece or chain, no floating point, no host loop beyond the O(n_pieces) checks.
+
+constexpr uint64_t CIG_I = 1, CIG_D = 2, CIG_EQ = 7, CIG_X = 8; // BAM's codes
+constexpr uint64_t CIG_MAX_COLUMNS = 1ull << 60;               // len << 4 stays inside 64 bits
+
+struct CigAtom
+{
+  uint64_t run; // len << 4 | code
+  uint32_t chain, pad;
+};
+static_assert(sizeof(CigAtom) == 16, "one atom, one 16-byte store");
+static_assert(sizeof(nts_cig_piece) == 16 && sizeof(nts_cig_chain) == 64, "the C ABI's layout");
+
+struct CigSums // what one atom adds to its chain, and the sum of those
+{
+  uint64_t n_cig, eq, x, ins, del;
+};
+
+struct CigHasLength
+{
+  __host__ __device__ bool operator()(const CigAtom& a) const { return (a.run >> 4) != 0; }
+};
+
+struct CigKeyOf // runs merge where chain and code are equal
+{
+  __host__ __device__ uint64_t operator()(const CigAtom& a) const { return (uint64_t)a.chain << 4 | (a.run & 15u); }
+};
+
+struct CigLenOf
+{
+  __host__ __device__ uint64_t operator()(const CigAtom& a) const { return a.run >> 4; }
+};
+
+struct CigChainOf
+{
+  __host__ __device__ uint32_t operator()(const CigAtom& a) const { return a.chain; }
+};
+
+struct CigAtomSums // kept atom i: a head opens an entry; its columns by kind
+{
+  const CigAtom* atoms;
+  __host__ __device__ CigSums operator()(uint32_t i) const
+  {
+    const CigAtom a = atoms[i];
+    const uint64_t code = a.run & 15u, len = a.run >> 4;
+    bool head = i == 0;
+    if (!head) {
+      const CigAtom b = atoms[i - 1];
+      head = b.chain != a.chain || (b.run & 15u) != code;
+    }
+    return { head ? 1ull : 0ull, code == CIG_EQ ? len : 0, code == CIG_X ? len : 0, code == CIG_I ? len : 0, code == CIG_D ? len : 0 };
+  }
+};
+
+struct CigSumsAdd
+{
+  __host__ __device__ CigSums operator()(const CigSums& a, const CigSums& b) const
+  {
+    return { a.n_cig + b.n_cig, a.eq + b.eq, a.x + b.x, a.ins + b.ins, a.del + b.del };
+  }
+};
+
+struct CigEntriesOf
+{
+  __host__ __device__ uint64_t operator()(const CigSums& s) const { return s.n_cig; }
+};
+
+__global__ __launch_bounds__(256) void k_cig_atoms(const nts_cig_piece* __restrict__ pieces, uint32_t n_pieces, const nts_edit_op* __restrict__ ops,
+                                                   uint32_t n_ops, const uint64_t* __restrict__ first, CigAtom* __restrict__ atoms, uint64_t n_atoms,
+                                                   uint32_t* __restrict__ status)
+{
+  const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x; // lanes 0 .. n_ops - 1: an op each; then a piece each
+  if (g >= (uint64_t)n_ops + n_pieces) return;
+  const bool trailing = g >= n_ops;
+  uint32_t t;
+  bool ok = true;
+  if (trailing) {
+    t = (uint32_t)(g - n_ops);
+  } else {
+    t = ops[g].seg;
+    if (t >= n_pieces || g < first[t] || g >= first[t + 1]) { // seg is not the piece that owns op g: find that piece, the last with first[t] <= g
+      uint32_t lo = 0, hi = n_pieces;                        // (first[0] = 0 <= g < n_ops = first[n_pieces])
+      while (hi - lo > 1u) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        if (first[mid] <= g) lo = mid;
+        else hi = mid;
+      }
+      t = lo;
+      ok = false;
+    }
+  }
+  const nts_cig_piece pc = pieces[t];
+  const uint64_t f0 = first[t], f1 = first[t + 1];
+  // (the host refused this before the launch: a lane still touches nothing outside the ops and its piece's atoms)
+  if (f1 < f0 || f1 > n_ops || (!trailing && (g < f0 || g >= f1))) {
+    status[g] = t;
+    return;
+  }
+  const uint64_t D = f1 - f0, j = trailing ? D : g - f0; // this lane: the match run in front of op j and op j, or the run behind the last op
+  uint64_t i0 = 0, j0 = 0;                               // where the piece stands behind op j - 1
+  if (j > 0) {
+    const nts_edit_op pv = ops[f0 + j - 1]; // (f0 <= f0 + j - 1 < f1 <= n_ops)
+    i0 = (uint64_t)pv.p + (pv.op != NTS_OP_INS ? 1u : 0u);
+    j0 = (uint64_t)pv.q + (pv.op != NTS_OP_DEL ? 1u : 0u);
+  }
+  const uint64_t n = pc.n, m = pc.m;
+  uint64_t run = 0, code = 0;
+  if (trailing) {
+    ok = ok && i0 <= n && j0 <= m && n - i0 == m - j0;
+    run = n - i0;
+  } else {
+    const nts_edit_op op = ops[g];
+    const uint64_t p = op.p, q = op.q;
+    ok = ok && p >= i0 && q >= j0 && p - i0 == q - j0;
+    if (op.op == NTS_OP_SUB) ok = ok && p < n && q < m, code = CIG_X;
+    else if (op.op == NTS_OP_DEL) ok = ok && p < n && q <= m, code = CIG_D;
+    else if (op.op == NTS_OP_INS) ok = ok && p <= n && q < m, code = CIG_I;
+    else ok = false;
+    run = p - i0;
+  }
+  if (!ok) run = 0; // (empty atoms: the selection drops them; the call returns no CIGAR anyway)
+  const uint64_t base = 2u * f0 + t, last = 2u * D;      // the piece's atoms: slots base .. base + 2 D
+  const bool mirrored = (pc.flags & NTS_CIG_REVERSED) != 0;
+  const uint64_t at_run = base + (mirrored ? last - 2u * j : 2u * j);
+  if (at_run < n_atoms) atoms[at_run] = { run << 4 | CIG_EQ, pc.chain, 0u };
+  if (!trailing) {
+    const uint64_t at_op = base + (mirrored ? last - 2u * j - 1u : 2u * j + 1u); // (j < D: 2 j + 1 <= 2 D - 1)
+    if (at_op < n_atoms) atoms[at_op] = { (ok ? 1ull << 4 : 0ull) | code, pc.chain, 0u };
+  }
+  status[g] = ok ? SCRIPT_OK : t;
+}
+
+// entry e = the summed length and the code of run e
+__global__ __launch_bounds__(256) void k_cig_emit(const uint64_t* __restrict__ key, const uint64_t* __restrict__ len, const uint64_t* __restrict__ n_entries,
+                                                  uint64_t cap, uint64_t* __restrict__ out)
+{
+  const uint64_t e = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (e >= cap || e >= *n_entries) return;
+  out[e] = len[e] << 4 | (key[e] & 15u);
+}
+
+// the sums of the chains that have an atom, each at its chain (every other chain keeps its zeros)
+__global__ __launch_bounds__(256) void k_cig_chain_sums(const uint32_t* __restrict__ chain, const CigSums* __restrict__ sums, const uint64_t* __restrict__ n_keys,
+                                                        uint64_t cap, uint64_t n_chains, CigSums* __restrict__ out)
+{
+  const uint64_t j = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (j >= cap || j >= *n_keys) return;
+  const uint32_t c = chain[j];
+  if (c < n_chains) out[c] = sums[j];
+}
+
+__global__ __launch_bounds__(256) void k_cig_chains(const CigSums* __restrict__ sums, const uint64_t* __restrict__ first, uint64_t n_chains,
+                                                    nts_cig_chain* __restrict__ out)
+{
+  const uint64_t c = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (c >= n_chains) return;
+  const CigSums s = sums[c];
+  out[c] = { first[c], s.n_cig, s.eq, s.x, s.ins, s.del, s.eq + s.x + s.del, s.eq + s.x + s.ins };
+}
+
+int cigar_build_run(nts_ctx* ctx, const nts_cig_piece* pieces, uint64_t n_pieces, uint64_t n_chains, const nts_edit_op* ops, const uint64_t* first,
+                    uint64_t** cigar, uint64_t* n_cigar, nts_cig_chain* chains)
+{
+  if (n_pieces > 0xFFFFFFFFull || n_chains > 0xFFFFFFFFull) return fail(ctx, NTS_ERANGE, "nts_cigar_build: 2^32 pieces or chains or more");
+  if (first[0] != 0) return fail(ctx, NTS_EINVAL, "nts_cigar_build: first does not start at 0 (piece 0)");
+  uint64_t columns = 0;
+  for (uint64_t t = 0; t < n_pieces; ++t) {
+    const nts_cig_piece& pc = pieces[t];
+    auto who = [t] { return "nts_cigar_build: piece " + std::to_string(t); }; // (made only for a piece that is refused)
+    if (pc.chain >= n_chains) return fail(ctx, NTS_EINVAL, who() + " names a chain at or beyond n_chains");
+    if (t && pc.chain < pieces[t - 1].chain) return fail(ctx, NTS_EINVAL, who() + ": the pieces are not in chain order");
+    if (pc.flags & ~NTS_CIG_REVERSED) return fail(ctx, NTS_EINVAL, who() + " has unknown flag bits");
+    if (first[t + 1] < first[t]) return fail(ctx, NTS_EINVAL, who() + ": first is not nondecreasing");
+    columns += (uint64_t)pc.n + pc.m;
+    if (columns >= CIG_MAX_COLUMNS) return fail(ctx, NTS_ERANGE, "nts_cigar_build: 2^60 bases or more");
+  }
+  const uint64_t n_ops = first[n_pieces];
+  if (n_ops > 0xFFFFFFFFull || 2 * n_ops + n_pieces > 0xFFFFFFFFull) return fail(ctx, NTS_ERANGE, "nts_cigar_build: 2^32 atoms or more (2 ops + pieces)");
+  if (n_ops && !ops) return fail(ctx, NTS_EINVAL, "nts_cigar_build: bad arguments (no ops)");
+  *cigar = nullptr;
+  *n_cigar = 0;
+  if (n_pieces == 0) { // (nothing is launched)
+    if (n_chains) memset(chains, 0, n_chains * sizeof(nts_cig_chain));
+    return NTS_OK;
+  }
+  const uint64_t n_atoms = 2 * n_ops + n_pieces, lanes = n_ops + n_pieces;
+  NTS_WS(d_pieces, nts_cig_piece*, "cig_pieces", n_pieces * sizeof(nts_cig_piece));
+  NTS_WS(d_ops, nts_edit_op*, "cig_ops", std::max<uint64_t>(n_ops, 1) * sizeof(nts_edit_op));
+  NTS_WS(d_first, uint64_t*, "cig_first", (n_pieces + 1) * 8);
+  NTS_WS(d_atoms, CigAtom*, "cig_atoms", n_atoms * sizeof(CigAtom));
+  NTS_WS(d_kept, CigAtom*, "cig_kept", n_atoms * sizeof(CigAtom));
+  NTS_WS(d_status, uint32_t*, "cig_status", lanes * 4);
+  NTS_WS(d_num, uint64_t*, "cig_num", 4 * 8); // worst (as uint32), kept atoms, entries, chains with an atom
+  uint32_t* const d_worst = (uint32_t*)d_num;
+  hipError_t e_run = hipMemcpyAsync(d_pieces, pieces, n_pieces * sizeof(nts_cig_piece), hipMemcpyHostToDevice, ctx->stream);
+  if (e_run == hipSuccess && n_ops) e_run = hipMemcpyAsync(d_ops, ops, n_ops * sizeof(nts_edit_op), hipMemcpyHostToDevice, ctx->stream);
+  if (e_run == hipSuccess) e_run = hipMemcpyAsync(d_first, first, (n_pieces + 1) * 8, hipMemcpyHostToDevice, ctx->stream);
+  uint32_t worst = SCRIPT_OK;
+  uint64_t kept = 0;
+  if (e_run == hipSuccess) {
+    ScopedTimer t(ctx, "cigar_atoms", true);
+    NTS_LAUNCH(k_cig_atoms, IVL_GRID(lanes), (const nts_cig_piece*)d_pieces, (uint32_t)n_pieces, (const nts_edit_op*)d_ops, (uint32_t)n_ops,
+               (const uint64_t*)d_first, d_atoms, n_atoms, d_status);
+    size_t tmp = 0;
+    e_run = rocprim::reduce(nullptr, tmp, d_status, d_worst, SCRIPT_OK, lanes, ScriptMin(), ctx->stream);
+    void* d_tmp = e_run == hipSuccess ? ws_get(ctx, "ivs_tmp", std::max<size_t>(tmp, 16)) : nullptr;
+    if (e_run == hipSuccess && !d_tmp) e_run = hipErrorOutOfMemory;
+    if (e_run == hipSuccess) e_run = rocprim::reduce(d_tmp, tmp, d_status, d_worst, SCRIPT_OK, lanes, ScriptMin(), ctx->stream);
+  }
+  if (e_run == hipSuccess) {
+    ScopedTimer t(ctx, "cigar_merge");
+    size_t tmp = 0;
+    e_run = rocprim::select(nullptr, tmp, d_atoms, d_kept, d_num + 1, n_atoms, CigHasLength(), ctx->stream);
+    void* d_tmp = e_run == hipSuccess ? ws_get(ctx, "ivs_tmp", std::max<size_t>(tmp, 16)) : nullptr;
+    if (e_run == hipSuccess && !d_tmp) e_run = hipErrorOutOfMemory;
+    if (e_run == hipSuccess) e_run = rocprim::select(d_tmp, tmp, d_atoms, d_kept, d_num + 1, n_atoms, CigHasLength(), ctx->stream);
+  }
+  if (e_run == hipSuccess) e_run = hipGetLastError();
+  if (e_run == hipSuccess) e_run = hipMemcpyAsync(&worst, d_worst, 4, hipMemcpyDeviceToHost, ctx->stream);
+  if (e_run == hipSuccess) e_run = hipMemcpyAsync(&kept, d_num + 1, 8, hipMemcpyDeviceToHost, ctx->stream);
+  hipError_t e_sync = hipStreamSynchronize(ctx->stream); // (whatever happened: the caller's arrays were sources of asynchronous copies)
+  HIP_TRY(ctx, e_run);
+  HIP_TRY(ctx, e_sync);
+  if (worst != SCRIPT_OK) return fail(ctx, NTS_EINVAL, "nts_cigar_build: ops of piece " + std::to_string(worst) + " are no script of its lengths");
+  if (kept > n_atoms) return fail(ctx, NTS_EHIP, "nts_cigar_build: the selection kept more atoms than there are");
+  if (kept == 0) { // (every piece is empty: no entry, every record 0)
+    if (n_chains) memset(chains, 0, n_chains * sizeof(nts_cig_chain));
+    return NTS_OK;
+  }
+  NTS_WS(d_ekey, uint64_t*, "cig_ekey", kept * 8);
+  NTS_WS(d_elen, uint64_t*, "cig_elen", kept * 8);
+  NTS_WS(d_entries, uint64_t*, "cig_entries", kept * 8);
+  NTS_WS(d_asums, CigSums*, "cig_asums", kept * sizeof(CigSums));
+  NTS_WS(d_uchain, uint32_t*, "cig_uchain", kept * 4);
+  NTS_WS(d_csums, CigSums*, "cig_csums", n_chains * sizeof(CigSums));
+  NTS_WS(d_cfirst, uint64_t*, "cig_cfirst", n_chains * 8);
+  NTS_WS(d_chains, nts_cig_chain*, "cig_chains", n_chains * sizeof(nts_cig_chain));
+  uint64_t n_entries = 0;
+  {
+    ScopedTimer t(ctx, "cigar_merge");
+    auto keys = rocprim::make_transform_iterator((const CigAtom*)d_kept, CigKeyOf());
+    auto lens = rocprim::make_transform_iterator((const CigAtom*)d_kept, CigLenOf());
+    auto chain_of = rocprim::make_transform_iterator((const CigAtom*)d_kept, CigChainOf());
+    auto sums_of = rocprim::make_transform_iterator(rocprim::counting_iterator<uint32_t>(0), CigAtomSums{ d_kept });
+    auto entries_of = rocprim::make_transform_iterator((const CigSums*)d_csums, CigEntriesOf());
+    size_t tmp_e = 0, tmp_c = 0, tmp_f = 0;
+    e_run = rocprim::reduce_by_key(nullptr, tmp_e, keys, lens, kept, d_ekey, d_elen, d_num + 2, rocprim::plus<uint64_t>(), rocprim::equal_to<uint64_t>(),
+                                   ctx->stream);
+    if (e_run == hipSuccess)
+      e_run = rocprim::reduce_by_key(nullptr, tmp_c, chain_of, sums_of, kept, d_uchain, d_asums, d_num + 3, CigSumsAdd(), rocprim::equal_to<uint32_t>(),
+                                     ctx->stream);
+    if (e_run == hipSuccess)
+      e_run = rocprim::exclusive_scan(nullptr, tmp_f, entries_of, d_cfirst, (uint64_t)0, n_chains, rocprim::plus<uint64_t>(), ctx->stream);
+    void* d_tmp = e_run == hipSuccess ? ws_get(ctx, "ivs_tmp", std::max<size_t>(std::max(tmp_e, std::max(tmp_c, tmp_f)), 16)) : nullptr;
+    if (e_run == hipSuccess && !d_tmp) e_run = hipErrorOutOfMemory;
+    if (e_run == hipSuccess)
+      e_run = rocprim::reduce_by_key(d_tmp, tmp_e, keys, lens, kept, d_ekey, d_elen, d_num + 2, rocprim::plus<uint64_t>(), rocprim::equal_to<uint64_t>(),
+                                     ctx->stream);
+    if (e_run == hipSuccess)
+      NTS_LAUNCH(k_cig_emit, IVL_GRID(kept), (const uint64_t*)d_ekey, (const uint64_t*)d_elen, (const uint64_t*)(d_num + 2), kept, d_entries);
+    if (e_run == hipSuccess)
+      e_run = rocprim::reduce_by_key(d_tmp, tmp_c, chain_of, sums_of, kept, d_uchain, d_asums, d_num + 3, CigSumsAdd(), rocprim::equal_to<uint32_t>(),
+                                     ctx->stream);
+    if (e_run == hipSuccess) e_run = hipMemsetAsync(d_csums, 0, n_chains * sizeof(CigSums), ctx->stream);
+    if (e_run == hipSuccess) {
+      NTS_LAUNCH(k_cig_chain_sums, IVL_GRID(kept), (const uint32_t*)d_uchain, (const CigSums*)d_asums, (const uint64_t*)(d_num + 3), kept, n_chains, d_csums);
+      e_run = rocprim::exclusive_scan(d_tmp, tmp_f, entries_of, d_cfirst, (uint64_t)0, n_chains, rocprim::plus<uint64_t>(), ctx->stream);
+    }
+    if (e_run == hipSuccess) NTS_LAUNCH(k_cig_chains, IVL_GRID(n_chains), (const CigSums*)d_csums, (const uint64_t*)d_cfirst, n_chains, d_chains);
+  }
+  if (e_run == hipSuccess) e_run = hipGetLastError();
+  if (e_run == hipSuccess) e_run = hipMemcpyAsync(&n_entries, d_num + 2, 8, hipMemcpyDeviceToHost, ctx->stream);
+  e_sync = hipStreamSynchronize(ctx->stream);
+  HIP_TRY(ctx, e_run);
+  HIP_TRY(ctx, e_sync);
+  if (n_entries == 0 || n_entries > kept) return fail(ctx, NTS_EHIP, "nts_cigar_build: the merge left an impossible number of entries");
+  uint64_t* host_cigar = (uint64_t*)malloc(n_entries * 8);
+  nts_cig_chain* host_chains = (nts_cig_chain*)malloc(n_chains * sizeof(nts_cig_chain)); // (the caller's array is written only when the call succeeds)
+  if (!host_cigar || !host_chains) {
+    free(host_cigar);
+    free(host_chains);
+    return fail(ctx, NTS_ENOMEM, "nts_cigar_build: no host memory for the CIGAR");
+  }
+  e_run = hipMemcpyAsync(host_cigar, d_entries, n_entries * 8, hipMemcpyDeviceToHost, ctx->stream);
+  if (e_run == hipSuccess) e_run = hipMemcpyAsync(host_chains, d_chains, n_chains * sizeof(nts_cig_chain), hipMemcpyDeviceToHost, ctx->stream);
+  e_sync = hipStreamSynchronize(ctx->stream);
+  if (e_run == hipSuccess && e_sync == hipSuccess) memcpy(chains, host_chains, n_chains * sizeof(nts_cig_chain));
+  else free(host_cigar);
+  free(host_chains);
+  HIP_TRY(ctx, e_run);
+  HIP_TRY(ctx, e_sync);
+  *cigar = host_cigar;
+  *n_cigar = n_entries;
+  return NTS_OK;
+}

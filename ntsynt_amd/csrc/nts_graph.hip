@@ -848,6 +848,7 @@ namespace {
 #include "nts_edit_wide_script.inc"
 #include "nts_edit_extend.inc"
 #include "nts_edit_extend_script.inc"
+#include "nts_cigar.inc"
 } // namespace
 
 extern "C" int nts_iv_links(nts_ctx* ctx, uint32_t n_lists, const nts_sample* const* lists, const uint64_t* n, uint32_t min_anchors, nts_iv_link** out,
@@ -1004,6 +1005,14 @@ extern "C" int nts_edit_extend_script_last_plan(nts_ctx* ctx, uint64_t* members,
   if (table_bytes) *table_bytes = ctx->last_escript_table_bytes;
   if (batches) *batches = ctx->last_escript_batches;
   return NTS_OK;
+}
+
+extern "C" int nts_cigar_build(nts_ctx* ctx, const nts_cig_piece* pieces, uint64_t n_pieces, uint64_t n_chains, const nts_edit_op* ops,
+                               const uint64_t* first, uint64_t** cigar, uint64_t* n_cigar, nts_cig_chain* chains)
+{
+  if (!ctx || !cigar || !n_cigar || !first || (n_pieces && !pieces) || (n_chains && !chains)) return fail(ctx, NTS_EINVAL, "nts_cigar_build: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return cigar_build_run(ctx, pieces, n_pieces, n_chains, ops, first, cigar, n_cigar, chains);
 }
 
 extern "C" int nts_graph_budget(nts_ctx* ctx, uint64_t bytes)

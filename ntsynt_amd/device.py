@@ -64,6 +64,11 @@ NO_MATE = 0xFFFFFFFF
 TASK_DTYPE = np.dtype([("pos_a", "<u8"), ("pos_b", "<u8"), ("rec_a", "<u4"), ("rec_b", "<u4"), ("n", "<u4"), ("m", "<u4"), ("flags", "<u4"), ("pad", "<u4")])
 EXTEND_DTYPE = np.dtype([(n, "<u4") for n in ("ext_a", "ext_b", "edits", "valid_a", "valid_b")])
 EXTEND_A_BACKWARDS, EXTEND_B_BACKWARDS, EXTEND_B_COMPLEMENT = 1, 2, 4
+# nts_cig_piece / nts_cig_chain: what Context.cigar_build takes and returns; a CIGAR entry is len << 4 | code
+PIECE_DTYPE = np.dtype([(n, "<u4") for n in ("chain", "n", "m", "flags")])
+CHAIN_DTYPE = np.dtype([(n, "<u8") for n in ("first", "n_cig", "eq", "x", "ins", "del", "len_a", "len_b")])
+CIG_REVERSED = 1
+CIG_INS, CIG_DEL, CIG_EQ, CIG_X = 1, 2, 7, 8
 
 
 class Context:
@@ -391,6 +396,33 @@ class Context:
         a, b, c = u64(), u64(), u64()
         self.check(self.lib.nts_edit_extend_script_last_plan(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "nts_edit_extend_script_last_plan")
         return {"members": a.value, "table_bytes": b.value, "batches": c.value}
+
+    def cigar_build(self, pieces, ops, first, n_chains):
+        """one CIGAR per chain of aligned pieces (nts_cigar_build).  pieces: a PIECE_DTYPE array in chain order -- two strings of n and
+        m bases, flags CIG_REVERSED for a piece whose columns are taken backwards; ops: an OP_DTYPE array, the scripts of all pieces one
+        behind the other with seg = the piece's index and p, q local to the piece; first [len(pieces) + 1]: piece t's ops are
+        ops[first[t]:first[t + 1]].  Returns (cigar, chains): cigar [E] uint64, entries len << 4 | code (CIG_INS 1, CIG_DEL 2, CIG_EQ 7,
+        CIG_X 8) of all chains one behind the other, runs of one kind merged across pieces and never across chains; chains a
+        CHAIN_DTYPE array of n_chains entries -- chain c's entries are cigar[first:first + n_cig], eq / x / ins / del its columns of
+        each kind, len_a and len_b the bases of either side.  Ops that are no script of their piece's lengths are refused.  No genome
+        is read.  Exact and deterministic."""
+        pc = np.ascontiguousarray(pieces, dtype=PIECE_DTYPE)
+        op = np.ascontiguousarray(ops, dtype=OP_DTYPE)
+        ft = np.ascontiguousarray(first, dtype=np.uint64)
+        if pc.ndim != 1 or op.ndim != 1 or ft.shape != (pc.size + 1,):
+            raise ValueError("cigar_build: a list of pieces, a list of ops and one first entry per piece plus one")
+        if int(ft[-1]) != op.size:
+            raise ValueError("cigar_build: first ends at the number of ops")
+        if int(n_chains) < 0:
+            raise ValueError("cigar_build: n_chains is a count")
+        assert PIECE_DTYPE.itemsize == ctypes.sizeof(_lib.CigPiece) and CHAIN_DTYPE.itemsize == ctypes.sizeof(_lib.CigChain)
+        assert OP_DTYPE.itemsize == ctypes.sizeof(_lib.EditOp)
+        chains = np.zeros(int(n_chains), dtype=CHAIN_DTYPE)
+        p, m = c_vp(), u64()
+        self.check(self.lib.nts_cigar_build(self.h, pc.ctypes.data if pc.size else None, pc.size, int(n_chains), op.ctypes.data if op.size else None,
+                                            ft.ctypes.data, ctypes.byref(p), ctypes.byref(m), chains.ctypes.data if chains.size else None),
+                   "nts_cigar_build")
+        return self._take(p, m.value, np.dtype("<u8")), chains
 
     def timing(self, name):
         ms, n = ctypes.c_double(), u64()

@@ -498,7 +498,7 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         mx_tsvs=None, common_file=None, m=90, n=0, initial_only=False, write_fai=True, engine="device", refine_repeat_file=None, screen_repeat_file=None,
         graph_budget=None, assess=None, gaps=False, gap_links=None, gap_block_links=False, gap_copies=None, gap_copy_sites=None,
         gap_periods=None, gap_families=None, block_identity=None, block_variants=None, block_wide_variants=None, block_ends=None,
-        block_end_variants=False):
+        block_end_variants=False, block_paf=None):
     """FASTA paths -> engine (outputs in .outputs and in the CWD).  Mirrors oracle.synteny_oracle.run_pipeline's
     signature so the parity tests read alike.  Under torch.distributed (WORLD_SIZE > 1, process group already
     initialised by the caller) genomes are sharded over the ranks.
@@ -538,7 +538,10 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
     pair; one rank only; it needs none of the other switches); with `benchmark` the stage times gain block_ends:edit_extend.
     block_end_variants: needs block_ends; from that stage's own pass also <prefix>.block_end_variants.tsv (assess.block_ends with
     with_variants: the edits of every extended flank); with `benchmark` the stage times gain block_ends:edit_extend_script_plan and
-    block_ends:edit_extend_script."""
+    block_ends:edit_extend_script.  block_paf = (k, rate, band, max_len, max_edits, ends) with ends = (ends_max_len, ends_max_edits,
+    ends_penalty) or None: behind the other block files, <prefix>.block_alignments.paf (assess.block_alignments: one PAF record with a
+    cg:Z: CIGAR per aligned chain of every block and pair, from a pass of its own; one rank only; it needs none of the other switches);
+    with `benchmark` the stage times gain block_paf:cigar_atoms and block_paf:cigar_merge."""
     prefix = prefix or f"ntSynt.k{k}.w{w}"
     if mx_tsvs is not None and len(mx_tsvs) != len(fastas):
         raise ValueError("one minimizer TSV per FASTA file")
@@ -616,6 +619,16 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
     if block_end_variants and block_ends is None:
         from .assess import END_VARIANTS_NEED_ENDS
         raise ValueError("block_end_variants: " + END_VARIANTS_NEED_ENDS)
+    if block_paf is not None:
+        if world > 1 or (mx_tsvs is not None and initial_only):
+            raise ValueError("block_paf needs every genome resident on one GPU (one rank, genomes loaded)")
+        from .assess import check_ends_parameters, check_identity_parameters
+        if len(block_paf) != 6 or (block_paf[5] is not None and len(block_paf[5]) != 3):
+            raise ValueError("block_paf = (k, rate, band, max_len, max_edits, ends) with ends = (ends_max_len, ends_max_edits, ends_penalty) or None")
+        block_paf = tuple(int(x) for x in block_paf[:5]) + (tuple(int(x) for x in block_paf[5]) if block_paf[5] is not None else None,)
+        message = check_identity_parameters(*block_paf[:5]) or (check_ends_parameters(*block_paf[5]) if block_paf[5] is not None else None)
+        if message:
+            raise ValueError("block_paf = (k, rate, band, max_len, max_edits, ends): " + message)
     if gap_block_links and gap_links is None:
         raise ValueError("gap_block_links needs gap_links = (rate, min_anchors)")
     if gap_block_links and len(fastas) > 32:
@@ -1235,6 +1248,23 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
             st.rows += [(f"block_ends:{name}", (backend.ctx.timing(name)[0] - ends_before[name]) * 1e-3) for name in ends_timers]
             backend.ctx.profile(False)
         st.mark("block_ends_done")
+    if block_paf is not None:
+        st.start("block_paf")
+        from . import assess as assess_
+        if benchmark:                                         # (device events around the calls of this stage only)
+            backend.ctx.profile(True)
+            paf_timers = ("cigar_atoms", "cigar_merge")
+            paf_before = {name: backend.ctx.timing(name)[0] for name in paf_timers}
+        text = assess_.paf_table(assess_.block_alignments(backend.ctx, {fa.basename(p): genomes[p] for p in fastas},
+                                                          assess_.read_blocks(f"{prefix}.synteny_blocks.tsv"), *block_paf[:5], ends=block_paf[5]))
+        with open(f"{prefix}.block_alignments.paf", "w", encoding="utf-8") as fh:
+            fh.write(text)
+        eng.outputs[f"{prefix}.block_alignments.paf"] = text
+        st.stop()
+        if benchmark:
+            st.rows += [(f"block_paf:{name}", (backend.ctx.timing(name)[0] - paf_before[name]) * 1e-3) for name in paf_timers]
+            backend.ctx.profile(False)
+        st.mark("block_paf_done")
     if gaps:
         st.start("gaps")
         from . import assess as assess_, gaps as gaps_
