@@ -855,6 +855,40 @@ typedef struct
 int nts_cigar_build(nts_ctx* ctx, const nts_cig_piece* pieces, uint64_t n_pieces, uint64_t n_chains, const nts_edit_op* ops, const uint64_t* first,
                     uint64_t** cigar, uint64_t* n_cigar, nts_cig_chain* chains);
 
+/* ---- the coordinate map of the chains' CIGARs: block lift --------------------------------------------------------------
+ * nts_cigar_lift: cigar = n_cigar entries len << 4 | code (I 1, D 2, = 7, X 8), chains = n_chains records whose first / n_cig locate a
+ *   chain's entries and whose len_a / len_b are its bases (what nts_cigar_build returns; entries need not be maximal runs), queries =
+ *   n_queries of {chain, side, pos}: pos is an offset on A (side 0) or B (side 1) of the chain, "src"; the answer lies on the other
+ *   side, "oth".  An entry consumes A if it is =, X or D and B if it is =, X or I; PA[e] / PB[e] = the bases the chain's entries in
+ *   front of e consume.  For pos < len_src the HIT names the one entry e with Psrc[e] <= pos < Psrc[e + 1]: entry = e as an index into
+ *   cigar, off = pos - Psrc[e], code = e's code, pos = Poth[e] + off for = and X, and Poth[e] -- the first oth base behind the gap --
+ *   for an entry that consumes src only.  For pos = len_src, the end of a half-open interval, the hit is (len_oth, first + n_cig, 0,
+ *   0); reserved is 0.  hits: n_queries host entries, written only when the call succeeds.  NTS_ERANGE before any launch for 2^32
+ *   entries, chains or queries or more (before any array is read) and for len_a or len_b that add up to 2^63 or more over all chains.
+ *   NTS_EINVAL before any launch, the smallest chain named: first not nondecreasing, first + n_cig > n_cigar.  NTS_EINVAL after the
+ *   launch, hits untouched: "the entries of chain ... are no CIGAR of its lengths" with the smallest such chain (an entry with a code
+ *   outside {1, 2, 7, 8} or of length 0 -- every entry of the array is checked and names the last chain that starts at or in front of
+ *   it --, or entries that do not consume len_a and len_b), otherwise "query ... is outside its chain" with the smallest such query
+ *   (chain >= n_chains, side > 1, pos > len_src).  No query: the entries are checked, no search is launched, nothing is written.
+ *   One exclusive scan over all entries gives the global prefixes of (A bases, B bases), one lane per entry and one per chain check
+ *   them, a minimum reduction of the per-lane status (timer "lift_scan"); one lane per query searches its chain's prefixes for the
+ *   entry (upper bound, about log2(n_cig) dependent loads) and stores one 32-byte hit, a second minimum reduction (timer
+ *   "lift_search").  On the context's stream, in its workspace; no atomic, no launch per chain or query, no floating point: the same
+ *   input gives the same bytes.  docs/design/04_23_block_lift.md; csrc/nts_cigar.inc; ntsynt_amd/assess.py block_lift,
+ *   `ntSynt --block-lift`, `bin/ntsynt_block_stats --lift-out`. */
+typedef struct
+{
+  uint32_t chain, side;
+  uint64_t pos;
+} nts_lift_query;
+typedef struct
+{
+  uint64_t pos, entry, off;
+  uint32_t code, reserved;
+} nts_lift_hit;
+int nts_cigar_lift(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains,
+                   const nts_lift_query* queries, uint64_t n_queries, nts_lift_hit* hits);
+
 /* ---- C1-C5: minimizer graph -> collinear chains -----------------------------------------------------
  * replaces ntjoin_utils.read_minimizers' duplicate removal, filter_minimizers and build_graph
  * (call sites bin/ntsynt_synteny.py:607-612, 483, 539) and the path walk of Ntjoin.find_paths

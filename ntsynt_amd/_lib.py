@@ -87,6 +87,16 @@ class CigChain(ctypes.Structure):
     _fields_ = [(n, u64) for n in ("first", "n_cig", "eq", "x", "ins", "del", "len_a", "len_b")]
 
 
+class LiftQuery(ctypes.Structure):
+    "nts_lift_query: an offset on one side of a chain (nts_cigar_lift)"
+    _fields_ = [("chain", u32), ("side", u32), ("pos", u64)]
+
+
+class LiftHit(ctypes.Structure):
+    "nts_lift_hit: the offset on the other side and the CIGAR entry the position falls in (nts_cigar_lift)"
+    _fields_ = [("pos", u64), ("entry", u64), ("off", u64), ("code", u32), ("reserved", u32)]
+
+
 class MxList(ctypes.Structure):
     _fields_ = [("h1", c_vp), ("rec", c_vp), ("pos", c_vp), ("keep", c_vp), ("list_id", c_vp), ("n", u64)]
 
@@ -254,6 +264,7 @@ SYMBOLS = [
     ("nts_edit_extend_script", ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, u64, c_vp, u64, ctypes.POINTER(c_vp), c_u64p, c_vp]),
     ("nts_edit_extend_script_last_plan", ctypes.c_int, [c_vp, c_u64p, c_u64p, c_u64p]),
     ("nts_cigar_build", ctypes.c_int, [c_vp, c_vp, u64, u64, c_vp, c_vp, ctypes.POINTER(c_vp), c_u64p, c_vp]),
+    ("nts_cigar_lift", ctypes.c_int, [c_vp, c_vp, u64, c_vp, u64, c_vp, u64, c_vp]),
     ("nts_genome_valid_bases", ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(Interval), u64, c_vp]),
     ("nts_minhash_pairs", ctypes.c_int, [c_vp, u32, c_vp, c_vp, u64, c_vp, c_vp, u64, c_vp, c_vp]),
     ("nts_graph_build", ctypes.c_int, [c_vp, u32, ctypes.POINTER(MxList), ctypes.POINTER(Graph)]),

@@ -23,7 +23,10 @@ Two things, both over `<prefix>.synteny_blocks.tsv`:
   events in both genomes' coordinates; docs/design/04_21_block_end_variants.md.
 * block alignments (`ntSynt --block-paf`, `ntsynt_block_stats --paf-out`): one PAF record with a cg:Z: CIGAR per aligned chain of every
   block and pair -- the scripts of all stretches and flanks stitched and run-length merged on the GPU (nts_cigar_build);
-  docs/design/04_22_block_alignments.md."""
+  docs/design/04_22_block_alignments.md.
+* block lift (`ntSynt --block-lift BED --lift-genome NAME`, `ntsynt_block_stats --lift-bed --lift-genome --lift-out`): the intervals of
+  one genome mapped through those alignments into the other genomes -- the coordinate map of the chains' CIGARs on the GPU
+  (nts_cigar_lift); docs/design/04_23_block_lift.md."""
 import os
 import re
 from collections import namedtuple
@@ -773,24 +776,22 @@ def paf_table(rows):
     return "".join(r + "\n" for r in rows)
 
 
-def block_alignments(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_RATE, band=IDENTITY_BAND, max_len=IDENTITY_MAX_LEN, max_edits=0, ends=None):
-    """One PAF record with a cg:Z: CIGAR per aligned chain of every block and pair of its lines (target = line a, query = line b): the
-    anchors, segments and final per-segment results of block_identity for the same first five parameters, the canonical scripts of
-    block_variants / block_wide_variants, and with ends = (ends_max_len, ends_max_edits, ends_penalty) the flanks of block_ends attached
-    to each pair's first and last chain.  A pass of its own over the rounds: per round nts_edit_segments with the per-segment
-    distances, for max_edits > 0 nts_edit_wide and both script calls, else nts_edit_script alone, with ends nts_edit_extend and
-    nts_edit_extend_script, then ONE nts_cigar_build for all pairs of the round.  Returns paf_row's lines: blocks and pairs in
-    block_identity's order, a pair's chains ascending by x; a pair without an aligned segment has none.  Per pair the NM of its chains
-    less the flanks' edits must be the identity pass's `edits`, and the target and query bases less the flanks' must be aligned_a and
-    aligned_b: RuntimeError otherwise.  docs/design/04_22_block_alignments.md."""
+# what one round of the alignment pass produced: the _Round itself, the identity pass's per-interval sums, the flanks and their results (or
+# None), the chains of alignment_pieces (one entry per chain: line, ch, x0, x1, y0, y1) and nts_cigar_build's entries and records
+_AlignmentRound = namedtuple("_AlignmentRound", ["round", "per_iv", "flanks", "results", "chains", "cigar", "records"])
+
+
+def _alignment_rounds(ctx, genomes_by_name, blocks, k, rate, band, max_len, max_edits, ends, pairs, length, only=None):
+    """The per-round body of block_alignments and block_lift over _identity_rounds, as a generator of _AlignmentRound: per round
+    nts_edit_segments with the per-segment distances, for max_edits > 0 nts_edit_wide and both script calls, else nts_edit_script alone,
+    with ends nts_edit_extend and nts_edit_extend_script, then ONE nts_cigar_build for all pairs of the round.  Per pair the NM of its
+    chains less the flanks' edits must be the identity pass's `edits`, and the target and query bases less the flanks' must be aligned_a
+    and aligned_b: RuntimeError otherwise.  only: a genome's name -- rounds in which it takes no part are passed over before any edit
+    call."""
     import numpy as np
-    message = check_identity_parameters(int(k), int(rate), int(band), int(max_len), int(max_edits)) or \
-        (check_ends_parameters(*(int(v) for v in ends)) if ends is not None else None)
-    if message:
-        raise ValueError(message)
-    k, rate, band, max_len, max_edits = int(k), int(rate), int(band), int(max_len), int(max_edits)
-    pairs, length, found = [], {}, {}
     for r in _identity_rounds(ctx, genomes_by_name, blocks, k, rate, band, max_len, pairs, length):
+        if only is not None and only not in (r.name_a, r.name_b):
+            continue
         per_iv, dist = ctx.edit_segments(r.g_a, r.g_b, r.iv_a, r.iv_b, r.segs, r.flip, band, with_distances=True)
         final = dist
         scripts = [ctx.edit_script(r.g_a, r.g_b, r.iv_a, r.iv_b, r.segs, r.flip, band, dist)]
@@ -806,18 +807,11 @@ def block_alignments(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_R
             flank_script = ctx.edit_extend_script(r.g_a, r.g_b, tasks, results)
         pieces, source, chains = alignment_pieces(r.segs, final, r.lines, flanks, results)
         ops, first = alignment_ops(source, scripts, flank_script)
-        n_chains = int(chains["line"].size)
-        cigar, records = ctx.cigar_build(pieces, ops, first, n_chains)
-        texts = cigar_texts(cigar, records["first"], records["n_cig"])
-        # per pair: its chains (one grouping of all chains by line) and the sums of their records
-        line, n_lines = chains["line"], len(r.lines)
-        by_line = np.argsort(line, kind="stable")
-        cut = np.searchsorted(line[by_line], np.arange(n_lines + 1))
-        sums = np.zeros((3, n_lines), dtype=np.int64)         # NM, target bases, query bases
+        cigar, records = ctx.cigar_build(pieces, ops, first, int(chains["line"].size))
+        sums = np.zeros((3, len(r.lines)), dtype=np.int64)    # per pair: NM, target bases, query bases of its chains
         for row, values in enumerate((records["x"] + records["ins"] + records["del"], records["len_a"], records["len_b"])):
-            np.add.at(sums[row], line, values.astype(np.int64))
+            np.add.at(sums[row], chains["line"], values.astype(np.int64))
         for q, (la, lb, i) in enumerate(r.lines):
-            mine = by_line[cut[q]:cut[q + 1]].tolist()
             flank = flanks[q] if flanks is not None else None
             extra = [results[flank[side]] for side in ("left", "right")] if flank is not None else []
             nm, bases_a, bases_b = (int(v) for v in sums[:, q])
@@ -826,10 +820,263 @@ def block_alignments(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_R
                 raise RuntimeError(f"block {blocks[la].block_id}: the chains of {blocks[la].genome} and {blocks[lb].genome} hold {nm} edits over {bases_a} and "
                                    f"{bases_b} bases, the identity pass {int(per_iv[i]['edits'])} over {int(per_iv[i]['aligned_a'])} and "
                                    f"{int(per_iv[i]['aligned_b'])} (flanks: {[tuple(int(v) for v in e) for e in extra]})")
-            rec_len_a, rec_len_b = int(r.g_a.rec_len[int(r.iv_a[i][0])]), int(r.g_b.rec_len[int(r.iv_b[i][0])])
-            found[(la, lb)] = [paf_row(blocks[la], blocks[lb], rec_len_a, rec_len_b, r.iv_a[i], r.iv_b[i], bool(r.flip[i]), chains["ch"][c],
-                                       [chains[f][c] for f in ("x0", "x1", "y0", "y1")], records[c], texts[c]) for c in mine]
-    return [row for p in pairs for row in found[p]]
+        yield _AlignmentRound(r, per_iv, flanks, results, chains, cigar, records)
+
+
+def _round_paf_rows(blocks, a, found):
+    "found[(line a, line b)] = paf_row's lines of the pair's chains, ascending by x, for every pair of one round of the alignment pass"
+    import numpy as np
+    r, chains, records = a.round, a.chains, a.records
+    texts = cigar_texts(a.cigar, records["first"], records["n_cig"])
+    line = chains["line"]
+    by_line = np.argsort(line, kind="stable")                 # per pair its chains: one grouping of all chains by line
+    cut = np.searchsorted(line[by_line], np.arange(len(r.lines) + 1))
+    for q, (la, lb, i) in enumerate(r.lines):
+        rec_len_a, rec_len_b = int(r.g_a.rec_len[int(r.iv_a[i][0])]), int(r.g_b.rec_len[int(r.iv_b[i][0])])
+        found[(la, lb)] = [paf_row(blocks[la], blocks[lb], rec_len_a, rec_len_b, r.iv_a[i], r.iv_b[i], bool(r.flip[i]), chains["ch"][c],
+                                   [chains[f][c] for f in ("x0", "x1", "y0", "y1")], records[c], texts[c]) for c in by_line[cut[q]:cut[q + 1]].tolist()]
+
+
+def block_alignments(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_RATE, band=IDENTITY_BAND, max_len=IDENTITY_MAX_LEN, max_edits=0, ends=None,
+                     lift=None):
+    """One PAF record with a cg:Z: CIGAR per aligned chain of every block and pair of its lines (target = line a, query = line b): the
+    anchors, segments and final per-segment results of block_identity for the same first five parameters, the canonical scripts of
+    block_variants / block_wide_variants, and with ends = (ends_max_len, ends_max_edits, ends_penalty) the flanks of block_ends attached
+    to each pair's first and last chain.  A pass of its own over the rounds (_alignment_rounds): per round nts_edit_segments with the
+    per-segment distances, for max_edits > 0 nts_edit_wide and both script calls, else nts_edit_script alone, with ends nts_edit_extend
+    and nts_edit_extend_script, then ONE nts_cigar_build for all pairs of the round.  Returns paf_row's lines: blocks and pairs in
+    block_identity's order, a pair's chains ascending by x; a pair without an aligned segment has none.  Per pair the NM of its chains
+    less the flanks' edits must be the identity pass's `edits`, and the target and query bases less the flanks' must be aligned_a and
+    aligned_b: RuntimeError otherwise.  docs/design/04_22_block_alignments.md.  lift = (source, intervals): the same pass also lifts
+    read_bed's intervals of the genome `source` (block_lift); returns (those lines, block_lift's rows)."""
+    message = check_identity_parameters(int(k), int(rate), int(band), int(max_len), int(max_edits)) or \
+        (check_ends_parameters(*(int(v) for v in ends)) if ends is not None else None)
+    if message:
+        raise ValueError(message)
+    k, rate, band, max_len, max_edits = int(k), int(rate), int(band), int(max_len), int(max_edits)
+    pairs, length, found = [], {}, {}
+    lifter = _Lifter(genomes_by_name, blocks, *lift) if lift is not None else None
+    for a in _alignment_rounds(ctx, genomes_by_name, blocks, k, rate, band, max_len, max_edits, ends, pairs, length):
+        _round_paf_rows(blocks, a, found)
+        if lifter is not None:
+            lifter.add_round(ctx, a, pairs)
+    rows = [row for p in pairs for row in found[p]]
+    return rows if lifter is None else (rows, lifter.rows(genomes_by_name))
+
+
+LIFT_COLUMNS = ("genome", "contig", "start", "end", "name", "block_id", "to_genome", "to_contig", "to_start", "to_end", "orientation", "ch", "src_start",
+                "src_end", "status")
+
+
+def read_bed(path):
+    """The intervals of a BED3+ file, in file order: dict of contig and name (lists of str) and start, end (int64 arrays), 0-based and
+    half-open.  Lines that begin with `#`, `track` or `browser` and empty lines are skipped; name is column 4, `.` when absent.  Fewer
+    than 3 columns, a coordinate that is no integer or negative, or start >= end raise ValueError with the line's number."""
+    import numpy as np
+    contig, start, end, name = [], [], [], []
+    with open(path, "r", encoding="utf-8") as fh:
+        for number, line in enumerate(fh, 1):
+            text = line.rstrip("\r\n")
+            if not text.strip() or text.startswith("#") or text.split()[0] in ("track", "browser"):
+                continue
+            f = text.split("\t") if "\t" in text else text.split()
+            if len(f) < 3:
+                raise ValueError(f"{path}, line {number}: a BED line has at least 3 columns (contig, start, end)")
+            try:
+                s, e = int(f[1]), int(f[2])
+            except ValueError:
+                raise ValueError(f"{path}, line {number}: start and end are integers") from None
+            if s < 0 or e < 0:
+                raise ValueError(f"{path}, line {number}: a negative coordinate")
+            if s >= e:
+                raise ValueError(f"{path}, line {number}: start {s} is not in front of end {e}")
+            contig.append(f[0])
+            start.append(s)
+            end.append(e)
+            name.append(f[3] if len(f) > 3 and f[3] else ".")
+    return {"contig": contig, "name": name, "start": np.array(start, dtype=np.int64), "end": np.array(end, dtype=np.int64)}
+
+
+def lift_queries(spans, intervals):
+    """The join of the chains' source spans with the BED intervals, and the two queries of every overlap.  spans: dict, one entry per
+    chain in which the source genome takes part, the chains of one pair next to each other and ascending by ch -- `pair` (any id of the
+    pair), `chain` (the chain's index for nts_cigar_lift), `side` (0: the source is line a, the target; 1: line b, the query), `flip`
+    (the pair is `-`), `contig` (the source contig, list of str) and `s0`, `s1`: the chain's forward span [S0, S1) on the source (side
+    0: tstart, tend; side 1: qstart, qend of its PAF record).  intervals: read_bed's dict.  Every (interval, chain) pair of one contig
+    with a non-empty overlap [lo, hi) = [max(start, S0), min(end, S1)) has the chain-local source offsets [u_lo, u_hi) = [lo - S0,
+    hi - S0), but for side 1 of a `-` pair [S1 - hi, S1 - lo) (paf_row's mirroring, inverted), and makes two queries: pos = u_lo and
+    pos = u_hi - 1.  Returns (queries, overlaps): a LIFT_QUERY_DTYPE array, overlap o's at 2 o and 2 o + 1, and a dict of int64 arrays
+    interval, span (index into spans), lo, hi.  The chains of one pair are disjoint and ascending on both sides, so per pair the
+    overlap ranges are two searchsorted and one np.repeat, over the intervals that can reach the pair alone (a contig's intervals are
+    sorted by start once): a Python loop runs over pairs and contigs, never over intervals or queries."""
+    import numpy as np
+    from .device import LIFT_QUERY_DTYPE
+    pair, s0, s1 = (np.asarray(spans[f], dtype=np.int64) for f in ("pair", "s0", "s1"))
+    side, flip = np.asarray(spans["side"], dtype=np.int64), np.asarray(spans["flip"], dtype=bool)
+    start, end = np.asarray(intervals["start"], dtype=np.int64), np.asarray(intervals["end"], dtype=np.int64)
+    on_contig = {}                                            # source contig -> its intervals by start, those starts, the running maximum of their ends
+    names = np.array(intervals["contig"], dtype=object)
+    for c in set(spans["contig"]):
+        mine = np.flatnonzero(names == c)
+        mine = mine[np.argsort(start[mine], kind="stable")]
+        on_contig[c] = (mine, start[mine], np.maximum.accumulate(end[mine]) if mine.size else end[mine])
+    cuts = np.concatenate([[0], np.flatnonzero(pair[1:] != pair[:-1]) + 1, [pair.size]]) if pair.size else np.zeros(1, dtype=np.int64)
+    which, span_of = [], []
+    for lo_c, hi_c in zip(cuts[:-1].tolist(), cuts[1:].tolist()):
+        order = np.arange(lo_c, hi_c)
+        if hi_c - lo_c > 1 and s0[lo_c] > s0[lo_c + 1]:       # (side 1 of a `-` pair: ascending by ch is descending on the forward strand)
+            order = order[::-1]
+        if np.any(s0[order][1:] < s1[order][:-1]) or np.any(s0[order] > s1[order]):
+            raise ValueError("the chains of a pair overlap on the source or are not in order")
+        by_start, starts, ends_so_far = on_contig[spans["contig"][lo_c]]
+        # the intervals that can reach the pair: from the first whose end, or an earlier one's, lies behind the pair's first base up to
+        # the last that starts in front of the pair's end
+        mine = by_start[np.searchsorted(ends_so_far, s0[order[0]], side="right"):np.searchsorted(starts, s1[order[-1]], side="left")]
+        if mine.size == 0:
+            continue
+        first = np.searchsorted(s1[order], start[mine], side="right")          # the first chain that ends behind the interval's start
+        last = np.searchsorted(s0[order], end[mine], side="left")              # the first chain that starts at or behind its end
+        count = np.maximum(last - first, 0)
+        total = int(count.sum())
+        if total == 0:
+            continue
+        which.append(np.repeat(mine, count))
+        span_of.append(order[np.repeat(first - np.concatenate([[0], np.cumsum(count)[:-1]]), count) + np.arange(total)])
+    which = np.concatenate(which) if which else np.zeros(0, dtype=np.int64)
+    span_of = np.concatenate(span_of) if span_of else np.zeros(0, dtype=np.int64)
+    lo, hi = np.maximum(start[which], s0[span_of]), np.minimum(end[which], s1[span_of])
+    keep = lo < hi                                            # (an empty chain overlaps nothing)
+    which, span_of, lo, hi = which[keep], span_of[keep], lo[keep], hi[keep]
+    mirrored = (side[span_of] == 1) & flip[span_of]
+    u_lo = np.where(mirrored, s1[span_of] - hi, lo - s0[span_of])
+    u_hi = np.where(mirrored, s1[span_of] - lo, hi - s0[span_of])
+    queries = np.zeros(2 * which.size, dtype=LIFT_QUERY_DTYPE)
+    queries["chain"] = np.repeat(np.asarray(spans["chain"], dtype=np.int64)[span_of], 2)
+    queries["side"] = np.repeat(side[span_of], 2)
+    queries["pos"][0::2], queries["pos"][1::2] = u_lo, u_hi - 1
+    return queries, {"interval": which, "span": span_of, "lo": lo, "hi": hi}
+
+
+def lift_rows(spans, overlaps, hits):
+    """The lifted span of every overlap of lift_queries from its two hits L (of u_lo) and R (of u_hi - 1): on the other side of the
+    chain [v_lo, v_hi) = [L.pos, R.pos + 1) when R's entry is `=` or `X`, else [L.pos, R.pos) -- R lies in a run the other side does not
+    have, and R.pos is the first base behind it; an interval wholly inside such a run gives v_lo == v_hi.  With the chain's forward
+    span [O0, O1) on the other genome (`o0`, `o1` of spans) the lifted span is [O0 + v_lo, O0 + v_hi), but for a `-` pair whose other
+    side is line b [O1 - v_hi, O1 - v_lo).  Returns overlaps with to_start and to_end added.  v_lo > v_hi or a span that leaves
+    [O0, O1) raises RuntimeError."""
+    import numpy as np
+    from .device import CIG_EQ, CIG_X
+    span = overlaps["span"]
+    left, right = hits[0::2], hits[1::2]
+    v_lo = left["pos"].astype(np.int64)
+    v_hi = right["pos"].astype(np.int64) + ((right["code"] == CIG_EQ) | (right["code"] == CIG_X))
+    o0, o1 = np.asarray(spans["o0"], dtype=np.int64)[span], np.asarray(spans["o1"], dtype=np.int64)[span]
+    if np.any(v_lo > v_hi) or np.any(v_hi > o1 - o0):
+        raise RuntimeError("a lifted interval ends in front of its start or behind its chain")
+    mirrored = (np.asarray(spans["side"], dtype=np.int64)[span] == 0) & np.asarray(spans["flip"], dtype=bool)[span]
+    return dict(overlaps, to_start=np.where(mirrored, o1 - v_hi, o0 + v_lo), to_end=np.where(mirrored, o1 - v_lo, o0 + v_hi))
+
+
+def lift_table(rows, k, rate, band, max_len, max_edits=0, ends=None):
+    """TSV of block_lift's rows: a header, one line per (interval, chain) overlap and one `unmapped` line per interval without any, then
+    the footer with the parameters"""
+    lines = ["\t".join(LIFT_COLUMNS)] + ["\t".join(str(r[c]) for c in LIFT_COLUMNS) for r in rows]
+    lines.append(f"# k {int(k)}, rate {int(rate)}, band {int(band)}, max_len {int(max_len)}, max_edits {int(max_edits)}" +
+                 (f", ends_max_len {int(ends[0])}, ends_max_edits {int(ends[1])}, ends_penalty {int(ends[2])}" if ends is not None else ""))
+    return "\n".join(lines) + "\n"
+
+
+class _Lifter:
+    "block_lift's state over the rounds of the alignment pass: per round the spans, ONE nts_cigar_lift and the rows' arrays"
+
+    def __init__(self, genomes_by_name, blocks, source, intervals):
+        if source not in genomes_by_name:
+            raise ValueError(f"--lift-genome {source} is not among the genomes {sorted(genomes_by_name)}")
+        self.blocks, self.source, self.intervals = blocks, source, intervals
+        self.contigs = None                                   # the source genome's records, once it was resident
+        self.parts, self.info = [], {}                        # per round lift_rows' arrays with pair and ch; pair -> its columns
+        self.index_of = None                                  # (line a, line b) -> the pair's place in block_identity's order
+
+    def add_round(self, ctx, a, pairs):
+        import numpy as np
+        r, chains = a.round, a.chains
+        if self.source not in (r.name_a, r.name_b):
+            return
+        side = 0 if r.name_a == self.source else 1
+        self.contigs = set((r.g_b if side else r.g_a).names)
+        if self.index_of is None:                             # (`pairs` is complete before the first round)
+            self.index_of = {p: q for q, p in enumerate(pairs)}
+        index_of = self.index_of
+        line = chains["line"]
+        order = np.argsort(line, kind="stable")               # the chains of one pair next to each other, ascending by ch
+        line = line[order]
+        i = np.array([i for _, _, i in r.lines], dtype=np.int64)[line]
+        start_a, start_b = r.iv_a[i, 1].astype(np.int64), r.iv_b[i, 1].astype(np.int64)
+        end_b, flip = r.iv_b[i, 2].astype(np.int64), r.flip[i].astype(bool)
+        x0, x1, y0, y1 = (chains[f][order] for f in ("x0", "x1", "y0", "y1"))
+        t0, t1 = start_a + x0, start_a + x1                   # paf_row's tstart, tend, qstart, qend
+        q0, q1 = np.where(flip, end_b - y1, start_b + y0), np.where(flip, end_b - y0, start_b + y1)
+        pair = np.array([index_of[(la, lb)] for la, lb, _ in r.lines], dtype=np.int64)[line]
+        mine = [self.blocks[(lb if side else la)].contig for la, lb, _ in r.lines]
+        for q, (la, lb, _) in enumerate(r.lines):
+            other = self.blocks[la if side else lb]
+            self.info[index_of[(la, lb)]] = (self.blocks[la].block_id, other.genome, other.contig, "-" if self.blocks[la].strand != self.blocks[lb].strand else "+")
+        spans = {"pair": pair, "chain": order, "side": np.full(order.size, side), "flip": flip, "contig": [mine[q] for q in line.tolist()],
+                 "s0": q0 if side else t0, "s1": q1 if side else t1, "o0": t0 if side else q0, "o1": t1 if side else q1}
+        queries, overlaps = lift_queries(spans, self.intervals)
+        hits = ctx.cigar_lift(a.cigar, a.records, queries)    # (one call per round, for all pairs in which the source takes part)
+        rows = lift_rows(spans, overlaps, hits)
+        self.parts.append(dict(rows, pair=pair[rows["span"]], ch=chains["ch"][order][rows["span"]]))
+
+    def rows(self, genomes_by_name):
+        import numpy as np
+        if self.contigs is None:                              # (the source is in no pair: its records are read for the contig check alone)
+            g = genomes_by_name[self.source]
+            loaded = callable(g)
+            g = g() if loaded else g
+            self.contigs = set(g.names)
+            if loaded:
+                g.free()
+        iv = self.intervals
+        for c in iv["contig"]:
+            if c not in self.contigs:
+                raise ValueError(f"genome {self.source} has no record {c} (--block-lift)")
+        fields = ("interval", "pair", "ch", "lo", "hi", "to_start", "to_end")
+        got = {f: np.concatenate([p[f] for p in self.parts]) if self.parts else np.zeros(0, dtype=np.int64) for f in fields}
+        order = np.lexsort((got["ch"], got["pair"], got["interval"]))
+        got = {f: v[order].tolist() for f, v in got.items()}
+        starts, ends, out, o = iv["start"].tolist(), iv["end"].tolist(), [], 0
+        for j, (contig, name) in enumerate(zip(iv["contig"], iv["name"])):
+            head = {"genome": self.source, "contig": contig, "start": starts[j], "end": ends[j], "name": name}
+            if o == len(order) or got["interval"][o] != j:
+                out.append(dict(head, **{c: "." for c in LIFT_COLUMNS[5:14]}, status="unmapped"))
+            while o < len(order) and got["interval"][o] == j:
+                block_id, to_genome, to_contig, sign = self.info[got["pair"][o]]
+                out.append(dict(head, block_id=block_id, to_genome=to_genome, to_contig=to_contig, to_start=got["to_start"][o], to_end=got["to_end"][o],
+                                orientation=sign, ch=got["ch"][o], src_start=got["lo"][o], src_end=got["hi"][o],
+                                status="full" if (got["lo"][o], got["hi"][o]) == (starts[j], ends[j]) else "partial"))
+                o += 1
+        return out
+
+
+def block_lift(ctx, genomes_by_name, blocks, source, intervals, k=IDENTITY_K, rate=IDENTITY_RATE, band=IDENTITY_BAND, max_len=IDENTITY_MAX_LEN,
+               max_edits=0, ends=None):
+    """read_bed's intervals of the genome `source` mapped through the block alignments: for every interval and every chain of
+    block_alignments (same parameters, same pass: _alignment_rounds) whose source span it overlaps, the clipped part [src_start,
+    src_end) and where its first and its last base lie in the other genome of the pair, from the chain's CIGAR (nts_cigar_lift; per
+    round ONE call for all queries of all pairs in which `source` takes part, on either line).  Returns dicts of LIFT_COLUMNS: the
+    intervals in input order, per interval the pairs in block_identity's order and a pair's chains ascending by ch; status `full` when
+    nothing was clipped, else `partial`; an interval that overlaps no chain has one line, `.` in block_id .. src_end and status
+    `unmapped`.  An interval on a contig the genome does not have raises ValueError.  docs/design/04_23_block_lift.md."""
+    message = check_identity_parameters(int(k), int(rate), int(band), int(max_len), int(max_edits)) or \
+        (check_ends_parameters(*(int(v) for v in ends)) if ends is not None else None)
+    if message:
+        raise ValueError(message)
+    pairs, length = [], {}
+    lifter = _Lifter(genomes_by_name, blocks, source, intervals)
+    for a in _alignment_rounds(ctx, genomes_by_name, blocks, int(k), int(rate), int(band), int(max_len), int(max_edits), ends, pairs, length, only=source):
+        lifter.add_round(ctx, a, pairs)
+    return lifter.rows(genomes_by_name)
 
 
 def wide_variants_table(rows, k, rate, band, max_len, max_edits):
@@ -939,6 +1186,10 @@ def main(argv=None):
     p.add_argument("--paf-out", help="with --fastas: file for the block alignments (one PAF record with a cg:Z: CIGAR per aligned chain of every block and "
                    "pair; GPU); it takes the --identity-* parameters, --identity-max-edits included, and with --ends-out the --ends-* parameters: the "
                    "flanks are attached")
+    p.add_argument("--lift-bed", help="with --fastas, --lift-genome and --lift-out: a BED file of intervals of one genome that are mapped through the block "
+                   "alignments into the other genomes (GPU); it takes the parameters of --paf-out")
+    p.add_argument("--lift-genome", help="the genome the intervals of --lift-bed lie on: a FASTA base name, as in column 2 of the block table")
+    p.add_argument("--lift-out", help="file for the lifted intervals (one line per interval and aligned chain it overlaps)")
     p.add_argument("--ends-max-len", help=f"longest flank that is extended, 1..65535 [{ENDS_MAX_LEN}]", type=int, default=ENDS_MAX_LEN)
     p.add_argument("--ends-max-edits", help=f"most edits within one flank, 1..1023 [{ENDS_MAX_EDITS}]", type=int, default=ENDS_MAX_EDITS)
     p.add_argument("--ends-penalty", help=f"what an edit costs the extension's score, against 2 for a matching pair of bases, 3..255 [{ENDS_PENALTY}]",
@@ -959,6 +1210,16 @@ def main(argv=None):
     if args.paf_out:
         if not args.fastas:
             p.error("--paf-out needs the genomes: --fastas")
+        message = check_identity_parameters(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits)
+        if message:
+            p.error(message)
+    if args.lift_bed or args.lift_genome or args.lift_out:
+        if not (args.lift_bed and args.lift_genome and args.lift_out):
+            p.error("--lift-bed, --lift-genome and --lift-out go together")
+        if not args.fastas:
+            p.error("--lift-out needs the genomes: --fastas")
+        if args.lift_genome not in [os.path.basename(path) for path in args.fastas]:
+            p.error(f"--lift-genome {args.lift_genome} is not among the genomes {[os.path.basename(path) for path in args.fastas]}")
         message = check_identity_parameters(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits)
         if message:
             p.error(message)
@@ -1009,11 +1270,21 @@ def main(argv=None):
                 end_rows = block_ends(ctx, loaders, read_blocks(args.tsv), *e_args)
             with open(args.ends_out, "w", encoding="utf-8") as fh:
                 fh.write(ends_table(end_rows, *e_args))
-        if args.paf_out:
-            paf_rows = block_alignments(ctx, loaders, read_blocks(args.tsv), *id_args, max_edits=args.identity_max_edits,
-                                        ends=(args.ends_max_len, args.ends_max_edits, args.ends_penalty) if args.ends_out else None)
-            with open(args.paf_out, "w", encoding="utf-8") as fh:
-                fh.write(paf_table(paf_rows))
+        if args.paf_out or args.lift_out:                     # (one pass gives both files)
+            a_args = dict(max_edits=args.identity_max_edits, ends=(args.ends_max_len, args.ends_max_edits, args.ends_penalty) if args.ends_out else None)
+            intervals = read_bed(args.lift_bed) if args.lift_out else None
+            if args.paf_out:
+                paf_rows = block_alignments(ctx, loaders, read_blocks(args.tsv), *id_args, **a_args,
+                                            lift=(args.lift_genome, intervals) if args.lift_out else None)
+                if args.lift_out:
+                    paf_rows, lift_rows_ = paf_rows
+                with open(args.paf_out, "w", encoding="utf-8") as fh:
+                    fh.write(paf_table(paf_rows))
+            else:
+                lift_rows_ = block_lift(ctx, loaders, read_blocks(args.tsv), args.lift_genome, intervals, *id_args, **a_args)
+            if args.lift_out:
+                with open(args.lift_out, "w", encoding="utf-8") as fh:
+                    fh.write(lift_table(lift_rows_, *id_args, **a_args))
     finally:
         ctx.close()
     if args.divergence_out:

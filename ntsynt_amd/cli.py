@@ -96,6 +96,11 @@ def build_parser():
                    "chain of every block and pair of its genomes; takes the --identity-* parameters (with --identity-max-edits E the stretches\n"
                    "beyond the band join the chains) and, with --block-ends, the --ends-* parameters (the flanks are attached); works with or\n"
                    "without the other block switches", action="store_true")
+    p.add_argument("--block-lift", metavar="BED", help="after the run, write <prefix>.block_lift.tsv: the intervals of this BED file, which lie on the\n"
+                   "genome --lift-genome names, mapped through the alignments of --block-paf into the other genomes, one line per interval\n"
+                   "and aligned chain it overlaps; takes the parameters of --block-paf; works with or without the other block switches")
+    p.add_argument("--lift-genome", metavar="NAME", help="with --block-lift: the genome its intervals lie on, a FASTA base name as in column 2 of the\n"
+                   "block table")
     p.add_argument("--ends-max-len", help="longest flank that is extended, 1..65535 [4096]", type=int, default=4096)
     p.add_argument("--ends-max-edits", help="most edits within one flank, 1..1023 [255]", type=int, default=255)
     p.add_argument("--ends-penalty", help="what an edit costs the extension's score, against 2 for a matching pair of bases, 3..255 [6]", type=int,
@@ -232,6 +237,22 @@ def check_reports(parser, args):
         message = check_identity_parameters(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits)
         if message:
             parser.error(message)
+    if args.lift_genome and not args.block_lift:
+        parser.error("--lift-genome names the genome of the intervals of --block-lift BED")
+    if args.block_lift:
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            parser.error("--block-lift works from the genomes resident on one GPU: run it on one rank, or lift through the finished run with "
+                         "ntsynt_block_stats --tsv <prefix>.synteny_blocks.tsv --fai ... --fastas ... --lift-bed BED --lift-genome NAME "
+                         "--lift-out <prefix>.block_lift.tsv")
+        if not args.lift_genome:
+            parser.error("--block-lift BED needs --lift-genome NAME: the genome the intervals lie on (a FASTA base name)")
+        names = [os.path.basename(path) for path in input_fastas(parser, args)]
+        if args.lift_genome not in names:
+            parser.error(f"--lift-genome {args.lift_genome} is not among the genomes {names}")
+        from .assess import check_identity_parameters
+        message = check_identity_parameters(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits)
+        if message:
+            parser.error(message)
     if args.block_ends:
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             parser.error("--block-ends works from the genomes resident on one GPU: run it on one rank, or assess the finished run with "
@@ -346,6 +367,10 @@ def main(argv=None):
            ([f"block_paf (cigar_atoms, cigar_merge; k {args.identity_k}, rate {args.identity_rate}, band {args.identity_band}, max_len {args.identity_max_len}, "
              f"max_edits {args.identity_max_edits}" + (f", ends_max_len {args.ends_max_len}, ends_max_edits {args.ends_max_edits}, ends_penalty "
                                                        f"{args.ends_penalty}" if args.block_ends else "") + ")"] if args.block_paf else []) + \
+           ([f"block_lift (lift_scan, lift_search; {args.block_lift} on {args.lift_genome}; k {args.identity_k}, rate {args.identity_rate}, band "
+             f"{args.identity_band}, max_len {args.identity_max_len}, max_edits {args.identity_max_edits}" +
+             (f", ends_max_len {args.ends_max_len}, ends_max_edits {args.ends_max_edits}, ends_penalty {args.ends_penalty}" if args.block_ends else "") + ")"]
+            if args.block_lift else []) + \
            (["gaps"] if args.gaps else []) + \
            (["gap_links"] if args.gap_links else []) + (["gap_block_links"] if args.gap_block_links else []) + \
            (["gap_copies"] if args.gap_copies else []) + (["gap_copy_sites"] if args.gap_copy_sites else []) + \
@@ -405,7 +430,7 @@ def _run(pipeline, fastas, args, device, quiet):
                  indel=args.indel, merge=args.merge, block_size=args.block_size, common=not args.no_common,
                  simplify=not args.no_simplify_graph, device=device, benchmark=args.benchmark,
                  dev=args.dev, interarrivals=args.interarrivals, assess=(args.assess_k, args.assess_s) if args.assess else None,
-                 block_identity=((args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len) + ((args.identity_max_edits,) if args.identity_max_edits else ())) if args.block_identity else None, block_variants=(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len) if args.block_variants else None, block_wide_variants=(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits) if args.block_wide_variants else None, block_ends=(args.ends_max_len, args.ends_max_edits, args.ends_penalty, args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits) if args.block_ends else None, block_end_variants=args.block_end_variants, block_paf=(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits, (args.ends_max_len, args.ends_max_edits, args.ends_penalty) if args.block_ends else None) if args.block_paf else None, gaps=args.gaps, gap_links=(args.gap_links_rate, args.gap_links_min) if args.gap_links else None, gap_block_links=args.gap_block_links, gap_copies=args.gap_links_rate if args.gap_copies else None, gap_copy_sites=(args.gap_sites_cap, args.gap_sites_step, args.gap_links_min) if args.gap_copy_sites else None, gap_periods=(args.gap_links_rate, args.gap_links_min) if args.gap_periods else None, gap_families=args.gap_sites_step if args.gap_families else None, repeat=args.repeat, bf_rounding=args.bf_rounding, bf_signature=args.bf_signature or pipeline.BF_SIGNATURE,
+                 block_identity=((args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len) + ((args.identity_max_edits,) if args.identity_max_edits else ())) if args.block_identity else None, block_variants=(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len) if args.block_variants else None, block_wide_variants=(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits) if args.block_wide_variants else None, block_ends=(args.ends_max_len, args.ends_max_edits, args.ends_penalty, args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits) if args.block_ends else None, block_end_variants=args.block_end_variants, block_paf=(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits, (args.ends_max_len, args.ends_max_edits, args.ends_penalty) if args.block_ends else None) if args.block_paf else None, block_lift=(args.block_lift, args.lift_genome, args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits, (args.ends_max_len, args.ends_max_edits, args.ends_penalty) if args.block_ends else None) if args.block_lift else None, gaps=args.gaps, gap_links=(args.gap_links_rate, args.gap_links_min) if args.gap_links else None, gap_block_links=args.gap_block_links, gap_copies=args.gap_links_rate if args.gap_copies else None, gap_copy_sites=(args.gap_sites_cap, args.gap_sites_step, args.gap_links_min) if args.gap_copy_sites else None, gap_periods=(args.gap_links_rate, args.gap_links_min) if args.gap_periods else None, gap_families=args.gap_sites_step if args.gap_families else None, repeat=args.repeat, bf_rounding=args.bf_rounding, bf_signature=args.bf_signature or pipeline.BF_SIGNATURE,
                  log=print if (args.dev and int(os.environ.get("RANK", "0")) == 0) else quiet)
 
 

@@ -306,3 +306,179 @@ int cigar_build_run(nts_ctx* ctx, const nts_cig_piece* pieces, uint64_t n_pieces
   *n_cigar = n_entries;
   return NTS_OK;
 }
+
+// ---- the coordinate map of the chains' CIGARs (nts_cigar_lift; ntsynt_amd/assess.py block_lift) ----
+// docs/design/04_23_block_lift.md.  Input: CIGAR entries and chain records as nts_cigar_build returns them, and queries {chain, side, pos}:
+// an offset on side A (0) or B (1) of a chain.  The answer is the offset on the other side and the entry the position falls in.
+//   1  rocprim::exclusive_scan over n_cigar + 1 elements of what a transform iterator makes of an entry -- the pair (A bases, B bases)
+//      it consumes, (0, 0) for the element behind the last -- into PA and PB: the GLOBAL prefixes, the last holding the totals; a
+//      chain-local prefix is P[e] - P[first].  k_lift_check: one lane per entry (a code outside {1, 2, 7, 8}, a length of 0, a prefix
+//      that wrapped) and one per chain (P[first + n_cig] - P[first] is not its len_a / len_b); a flagged lane stores its chain's index in
+//      its status word, a minimum reduction names the smallest (timer "lift_scan").
+//   2  k_cig_lift: one lane per query; validates it, finds with an upper-bound binary search over Psrc the entry that holds pos and
+//      stores one 32 B hit; an invalid query stores nothing but its own index in its status word, a second minimum reduction names the
+//      smallest (timer "lift_search").
+// No atomic, no launch per chain or query, no floating point, no host loop over entries or queries.
+
+using LiftPair = rocprim::tuple<uint64_t, uint64_t>; // (A bases, B bases)
+constexpr uint64_t LIFT_MAX_BASES = 1ull << 63;      // the global scan must not wrap
+static_assert(sizeof(nts_lift_query) == 16 && sizeof(nts_lift_hit) == 32, "the C ABI's layout");
+
+struct LiftBasesOf // element e of the scan's input: what entry e consumes; nothing behind the last entry
+{
+  const uint64_t* cigar;
+  uint64_t n_cigar;
+  __host__ __device__ LiftPair operator()(uint64_t e) const
+  {
+    if (e >= n_cigar) return LiftPair(0, 0);
+    const uint64_t v = cigar[e], code = v & 15u, len = v >> 4;
+    const bool both = code == CIG_EQ || code == CIG_X;
+    return LiftPair(both || code == CIG_D ? len : 0, both || code == CIG_I ? len : 0);
+  }
+};
+
+struct LiftPairAdd
+{
+  __host__ __device__ LiftPair operator()(const LiftPair& x, const LiftPair& y) const
+  {
+    return LiftPair(rocprim::get<0>(x) + rocprim::get<0>(y), rocprim::get<1>(x) + rocprim::get<1>(y));
+  }
+};
+
+__global__ __launch_bounds__(256) void k_lift_check(const uint64_t* __restrict__ cigar, uint64_t n_cigar, const nts_cig_chain* __restrict__ chains,
+                                                    uint64_t n_chains, const uint64_t* __restrict__ PA, const uint64_t* __restrict__ PB,
+                                                    uint32_t* __restrict__ status)
+{
+  const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x; // lanes 0 .. n_cigar - 1: an entry each; then a chain each
+  if (g >= n_cigar + n_chains) return;
+  uint32_t say = SCRIPT_OK;
+  if (g < n_cigar) {
+    const uint64_t v = cigar[g], code = v & 15u;
+    const bool bad = (code != CIG_I && code != CIG_D && code != CIG_EQ && code != CIG_X) || (v >> 4) == 0 || PA[g + 1] < PA[g] || PB[g + 1] < PB[g];
+    if (bad && n_chains) { // its chain: the last whose first <= g, chain 0 for an entry in front of every chain (on this error path only)
+      uint64_t lo = 0, hi = n_chains;
+      while (hi - lo > 1u) {
+        const uint64_t mid = lo + (hi - lo) / 2u;
+        if (chains[mid].first <= g) lo = mid;
+        else hi = mid;
+      }
+      say = (uint32_t)lo;
+    }
+  } else {
+    const uint64_t c = g - n_cigar;
+    const nts_cig_chain ch = chains[c];
+    // (the host refused the first test before the launch: a lane still reads nothing outside PA and PB)
+    if (ch.first > n_cigar || ch.n_cig > n_cigar - ch.first || PA[ch.first + ch.n_cig] - PA[ch.first] != ch.len_a ||
+        PB[ch.first + ch.n_cig] - PB[ch.first] != ch.len_b)
+      say = (uint32_t)c;
+  }
+  status[g] = say;
+}
+
+__global__ __launch_bounds__(256) void k_cig_lift(const uint64_t* __restrict__ cigar, uint64_t n_cigar, const nts_cig_chain* __restrict__ chains,
+                                                  uint64_t n_chains, const uint64_t* __restrict__ PA, const uint64_t* __restrict__ PB,
+                                                  const nts_lift_query* __restrict__ queries, uint64_t n_queries, nts_lift_hit* __restrict__ hits,
+                                                  uint32_t* __restrict__ status)
+{
+  const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (g >= n_queries) return;
+  const nts_lift_query q = queries[g];
+  if (q.chain >= n_chains || q.side > 1u) {
+    status[g] = (uint32_t)g;
+    return;
+  }
+  const nts_cig_chain ch = chains[q.chain];
+  const uint64_t first = ch.first, n = ch.n_cig;
+  const uint64_t len_src = q.side ? ch.len_b : ch.len_a, len_oth = q.side ? ch.len_a : ch.len_b;
+  // (the host refused the first two tests before the launch; a chain without entries holds no base: every index below is <= first + n <= n_cigar)
+  if (first > n_cigar || n > n_cigar - first || q.pos > len_src || (q.pos < len_src && n == 0)) {
+    status[g] = (uint32_t)g;
+    return;
+  }
+  status[g] = SCRIPT_OK;
+  if (q.pos == len_src) { // the end of a half-open interval
+    hits[g] = { len_oth, first + n, 0, 0u, 0u };
+    return;
+  }
+  const uint64_t* __restrict__ P = q.side ? PB : PA;
+  const uint64_t* __restrict__ O = q.side ? PA : PB;
+  const uint64_t base = P[first];
+  uint64_t lo = first, hi = first + n; // P[lo] - base <= pos < P[hi] - base (k_lift_check: P[first + n] - base = len_src): the smallest such hi
+  while (hi - lo > 1u) {
+    const uint64_t mid = lo + (hi - lo) / 2u;
+    if (P[mid] - base > q.pos) hi = mid;
+    else lo = mid;
+  }
+  const uint64_t code = cigar[lo] & 15u; // (first <= lo < first + n <= n_cigar)
+  const uint64_t off = q.pos - (P[lo] - base);
+  hits[g] = { O[lo] - O[first] + (code == CIG_EQ || code == CIG_X ? off : 0), lo, off, (uint32_t)code, 0u };
+}
+
+int cigar_lift_run(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains, const nts_lift_query* queries,
+                   uint64_t n_queries, nts_lift_hit* hits)
+{
+  uint64_t sum_a = 0, sum_b = 0;
+  for (uint64_t c = 0; c < n_chains; ++c) {
+    const nts_cig_chain& ch = chains[c];
+    auto who = [c] { return "nts_cigar_lift: chain " + std::to_string(c); }; // (made only for a chain that is refused)
+    if (c && ch.first < chains[c - 1].first) return fail(ctx, NTS_EINVAL, who() + ": first is not nondecreasing");
+    if (ch.first > n_cigar || ch.n_cig > n_cigar - ch.first) return fail(ctx, NTS_EINVAL, who() + ": first + n_cig lies beyond n_cigar");
+    if (ch.len_a >= LIFT_MAX_BASES || ch.len_b >= LIFT_MAX_BASES) return fail(ctx, NTS_ERANGE, "nts_cigar_lift: 2^63 bases or more");
+    sum_a += ch.len_a;
+    sum_b += ch.len_b;
+    if (sum_a >= LIFT_MAX_BASES || sum_b >= LIFT_MAX_BASES) return fail(ctx, NTS_ERANGE, "nts_cigar_lift: 2^63 bases or more");
+  }
+  const uint64_t lanes = n_cigar + n_chains;
+  NTS_WS(d_cigar, uint64_t*, "lift_cigar", std::max<uint64_t>(n_cigar, 1) * 8);
+  NTS_WS(d_chains, nts_cig_chain*, "lift_chains", std::max<uint64_t>(n_chains, 1) * sizeof(nts_cig_chain));
+  NTS_WS(d_pa, uint64_t*, "lift_pa", (n_cigar + 1) * 8);
+  NTS_WS(d_pb, uint64_t*, "lift_pb", (n_cigar + 1) * 8);
+  NTS_WS(d_status, uint32_t*, "lift_status", std::max<uint64_t>(std::max(lanes, n_queries), 1) * 4);
+  NTS_WS(d_queries, nts_lift_query*, "lift_queries", std::max<uint64_t>(n_queries, 1) * sizeof(nts_lift_query));
+  NTS_WS(d_hits, nts_lift_hit*, "lift_hits", std::max<uint64_t>(n_queries, 1) * sizeof(nts_lift_hit));
+  NTS_WS(d_worst, uint32_t*, "lift_worst", 2 * 4); // the smallest offending chain, the smallest offending query
+  nts_lift_hit* host_hits = n_queries ? (nts_lift_hit*)malloc(n_queries * sizeof(nts_lift_hit)) : nullptr; // (the caller's array is written only on success)
+  if (n_queries && !host_hits) return fail(ctx, NTS_ENOMEM, "nts_cigar_lift: no host memory for the hits");
+  uint32_t worst[2] = { SCRIPT_OK, SCRIPT_OK };
+  hipError_t e_run = hipSuccess;
+  if (n_cigar) e_run = hipMemcpyAsync(d_cigar, cigar, n_cigar * 8, hipMemcpyHostToDevice, ctx->stream);
+  if (e_run == hipSuccess && n_chains) e_run = hipMemcpyAsync(d_chains, chains, n_chains * sizeof(nts_cig_chain), hipMemcpyHostToDevice, ctx->stream);
+  if (e_run == hipSuccess && n_queries)
+    e_run = hipMemcpyAsync(d_queries, queries, n_queries * sizeof(nts_lift_query), hipMemcpyHostToDevice, ctx->stream);
+  size_t tmp_s = 0, tmp_r = 0;
+  void* d_tmp = nullptr;
+  auto bases = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), LiftBasesOf{ d_cigar, n_cigar });
+  auto prefixes = rocprim::make_zip_iterator(rocprim::make_tuple(d_pa, d_pb));
+  if (e_run == hipSuccess) {
+    ScopedTimer t(ctx, "lift_scan", true);
+    e_run = rocprim::exclusive_scan(nullptr, tmp_s, bases, prefixes, LiftPair(0, 0), n_cigar + 1, LiftPairAdd(), ctx->stream);
+    if (e_run == hipSuccess) e_run = rocprim::reduce(nullptr, tmp_r, d_status, d_worst, SCRIPT_OK, std::max(lanes, n_queries), ScriptMin(), ctx->stream);
+    d_tmp = e_run == hipSuccess ? ws_get(ctx, "ivs_tmp", std::max<size_t>(std::max(tmp_s, tmp_r), 16)) : nullptr;
+    if (e_run == hipSuccess && !d_tmp) e_run = hipErrorOutOfMemory;
+    if (e_run == hipSuccess) e_run = rocprim::exclusive_scan(d_tmp, tmp_s, bases, prefixes, LiftPair(0, 0), n_cigar + 1, LiftPairAdd(), ctx->stream);
+    if (e_run == hipSuccess && lanes) {
+      NTS_LAUNCH(k_lift_check, IVL_GRID(lanes), (const uint64_t*)d_cigar, n_cigar, (const nts_cig_chain*)d_chains, n_chains, (const uint64_t*)d_pa,
+                 (const uint64_t*)d_pb, d_status);
+      e_run = rocprim::reduce(d_tmp, tmp_r, d_status, d_worst, SCRIPT_OK, lanes, ScriptMin(), ctx->stream);
+    }
+  }
+  if (e_run == hipSuccess && lanes) e_run = hipMemcpyAsync(&worst[0], d_worst, 4, hipMemcpyDeviceToHost, ctx->stream);
+  if (e_run == hipSuccess && n_queries) { // (no query: nothing more is launched)
+    ScopedTimer t(ctx, "lift_search", true);
+    NTS_LAUNCH(k_cig_lift, IVL_GRID(n_queries), (const uint64_t*)d_cigar, n_cigar, (const nts_cig_chain*)d_chains, n_chains, (const uint64_t*)d_pa,
+               (const uint64_t*)d_pb, (const nts_lift_query*)d_queries, n_queries, d_hits, d_status);
+    e_run = rocprim::reduce(d_tmp, tmp_r, d_status, d_worst + 1, SCRIPT_OK, n_queries, ScriptMin(), ctx->stream);
+  }
+  if (e_run == hipSuccess) e_run = hipGetLastError();
+  if (e_run == hipSuccess && n_queries) e_run = hipMemcpyAsync(&worst[1], d_worst + 1, 4, hipMemcpyDeviceToHost, ctx->stream);
+  if (e_run == hipSuccess && n_queries) e_run = hipMemcpyAsync(host_hits, d_hits, n_queries * sizeof(nts_lift_hit), hipMemcpyDeviceToHost, ctx->stream);
+  const hipError_t e_sync = hipStreamSynchronize(ctx->stream); // (whatever happened: the caller's arrays were sources of asynchronous copies)
+  const bool good = e_run == hipSuccess && e_sync == hipSuccess && worst[0] == SCRIPT_OK && worst[1] == SCRIPT_OK;
+  if (good && n_queries) memcpy(hits, host_hits, n_queries * sizeof(nts_lift_hit));
+  free(host_hits);
+  HIP_TRY(ctx, e_run);
+  HIP_TRY(ctx, e_sync);
+  if (worst[0] != SCRIPT_OK) return fail(ctx, NTS_EINVAL, "nts_cigar_lift: the entries of chain " + std::to_string(worst[0]) + " are no CIGAR of its lengths");
+  if (worst[1] != SCRIPT_OK) return fail(ctx, NTS_EINVAL, "nts_cigar_lift: query " + std::to_string(worst[1]) + " is outside its chain");
+  return NTS_OK;
+}

@@ -1015,6 +1015,17 @@ extern "C" int nts_cigar_build(nts_ctx* ctx, const nts_cig_piece* pieces, uint64
   return cigar_build_run(ctx, pieces, n_pieces, n_chains, ops, first, cigar, n_cigar, chains);
 }
 
+extern "C" int nts_cigar_lift(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains,
+                              const nts_lift_query* queries, uint64_t n_queries, nts_lift_hit* hits)
+{
+  if (!ctx) return NTS_EINVAL;
+  if (n_cigar > 0xFFFFFFFFull || n_chains > 0xFFFFFFFFull || n_queries > 0xFFFFFFFFull) // (before any array is read)
+    return fail(ctx, NTS_ERANGE, "nts_cigar_lift: 2^32 entries, chains or queries or more");
+  if ((n_cigar && !cigar) || (n_chains && !chains) || (n_queries && (!queries || !hits))) return fail(ctx, NTS_EINVAL, "nts_cigar_lift: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return cigar_lift_run(ctx, cigar, n_cigar, chains, n_chains, queries, n_queries, hits);
+}
+
 extern "C" int nts_graph_budget(nts_ctx* ctx, uint64_t bytes)
 {
   if (!ctx) return NTS_EINVAL;

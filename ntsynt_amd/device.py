@@ -69,6 +69,9 @@ PIECE_DTYPE = np.dtype([(n, "<u4") for n in ("chain", "n", "m", "flags")])
 CHAIN_DTYPE = np.dtype([(n, "<u8") for n in ("first", "n_cig", "eq", "x", "ins", "del", "len_a", "len_b")])
 CIG_REVERSED = 1
 CIG_INS, CIG_DEL, CIG_EQ, CIG_X = 1, 2, 7, 8
+# nts_lift_query / nts_lift_hit: what Context.cigar_lift takes and returns, one per query
+LIFT_QUERY_DTYPE = np.dtype([("chain", "<u4"), ("side", "<u4"), ("pos", "<u8")])
+LIFT_HIT_DTYPE = np.dtype([("pos", "<u8"), ("entry", "<u8"), ("off", "<u8"), ("code", "<u4"), ("reserved", "<u4")])
 
 
 class Context:
@@ -423,6 +426,26 @@ class Context:
                                             ft.ctypes.data, ctypes.byref(p), ctypes.byref(m), chains.ctypes.data if chains.size else None),
                    "nts_cigar_build")
         return self._take(p, m.value, np.dtype("<u8")), chains
+
+    def cigar_lift(self, cigar, chains, queries):
+        """the coordinate map of the chains' CIGARs (nts_cigar_lift).  cigar [E] uint64 and chains, a CHAIN_DTYPE array: what cigar_build
+        returns (entries need not be maximal runs); queries: a LIFT_QUERY_DTYPE array -- pos is an offset on side 0 (A) or 1 (B) of
+        `chain`, 0 .. the chain's len_a or len_b, the end included.  Returns a LIFT_HIT_DTYPE array, one hit per query: pos = the offset
+        on the other side, entry = the index into cigar of the entry that holds the query's position, off = how far into that entry,
+        code = its kind (CIG_EQ, CIG_X: pos is the aligned base; CIG_DEL for side 0, CIG_INS for side 1: pos is the first base behind
+        the gap); for the end of a chain (len_other, first + n_cig, 0, 0).  Entries that are no CIGAR of the chains' lengths and queries
+        outside their chain are refused.  Exact and deterministic."""
+        cg = np.ascontiguousarray(cigar, dtype=np.uint64)
+        ch = np.ascontiguousarray(chains, dtype=CHAIN_DTYPE)
+        qs = np.ascontiguousarray(queries, dtype=LIFT_QUERY_DTYPE)
+        if cg.ndim != 1 or ch.ndim != 1 or qs.ndim != 1:
+            raise ValueError("cigar_lift: a list of entries, a list of chain records and a list of queries")
+        assert LIFT_QUERY_DTYPE.itemsize == ctypes.sizeof(_lib.LiftQuery) and LIFT_HIT_DTYPE.itemsize == ctypes.sizeof(_lib.LiftHit)
+        assert CHAIN_DTYPE.itemsize == ctypes.sizeof(_lib.CigChain)
+        hits = np.zeros(qs.size, dtype=LIFT_HIT_DTYPE)
+        self.check(self.lib.nts_cigar_lift(self.h, cg.ctypes.data if cg.size else None, cg.size, ch.ctypes.data if ch.size else None, ch.size,
+                                           qs.ctypes.data if qs.size else None, qs.size, hits.ctypes.data if hits.size else None), "nts_cigar_lift")
+        return hits
 
     def timing(self, name):
         ms, n = ctypes.c_double(), u64()

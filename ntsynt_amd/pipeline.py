@@ -498,7 +498,7 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         mx_tsvs=None, common_file=None, m=90, n=0, initial_only=False, write_fai=True, engine="device", refine_repeat_file=None, screen_repeat_file=None,
         graph_budget=None, assess=None, gaps=False, gap_links=None, gap_block_links=False, gap_copies=None, gap_copy_sites=None,
         gap_periods=None, gap_families=None, block_identity=None, block_variants=None, block_wide_variants=None, block_ends=None,
-        block_end_variants=False, block_paf=None):
+        block_end_variants=False, block_paf=None, block_lift=None):
     """FASTA paths -> engine (outputs in .outputs and in the CWD).  Mirrors oracle.synteny_oracle.run_pipeline's
     signature so the parity tests read alike.  Under torch.distributed (WORLD_SIZE > 1, process group already
     initialised by the caller) genomes are sharded over the ranks.
@@ -541,7 +541,11 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
     block_ends:edit_extend_script.  block_paf = (k, rate, band, max_len, max_edits, ends) with ends = (ends_max_len, ends_max_edits,
     ends_penalty) or None: behind the other block files, <prefix>.block_alignments.paf (assess.block_alignments: one PAF record with a
     cg:Z: CIGAR per aligned chain of every block and pair, from a pass of its own; one rank only; it needs none of the other switches);
-    with `benchmark` the stage times gain block_paf:cigar_atoms and block_paf:cigar_merge."""
+    with `benchmark` the stage times gain block_paf:cigar_atoms and block_paf:cigar_merge.  block_lift = (bed_path, genome, k, rate, band,
+    max_len, max_edits, ends): behind that file, <prefix>.block_lift.tsv (assess.block_lift: the BED intervals of `genome`, a FASTA base
+    name, mapped through the block alignments into the other genomes; one rank only; it needs none of the other switches; with
+    block_paf, which then takes the same parameters, the pass of the stage block_paf serves both files); with `benchmark` the stage times
+    gain block_lift:lift_scan and block_lift:lift_search."""
     prefix = prefix or f"ntSynt.k{k}.w{w}"
     if mx_tsvs is not None and len(mx_tsvs) != len(fastas):
         raise ValueError("one minimizer TSV per FASTA file")
@@ -629,6 +633,22 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         message = check_identity_parameters(*block_paf[:5]) or (check_ends_parameters(*block_paf[5]) if block_paf[5] is not None else None)
         if message:
             raise ValueError("block_paf = (k, rate, band, max_len, max_edits, ends): " + message)
+    if block_lift is not None:
+        if world > 1 or (mx_tsvs is not None and initial_only):
+            raise ValueError("block_lift needs every genome resident on one GPU (one rank, genomes loaded)")
+        from .assess import check_ends_parameters, check_identity_parameters
+        if len(block_lift) != 8 or (block_lift[7] is not None and len(block_lift[7]) != 3):
+            raise ValueError("block_lift = (bed_path, genome, k, rate, band, max_len, max_edits, ends) with ends = (ends_max_len, ends_max_edits, "
+                             "ends_penalty) or None")
+        block_lift = (str(block_lift[0]), str(block_lift[1])) + tuple(int(x) for x in block_lift[2:7]) + \
+            (tuple(int(x) for x in block_lift[7]) if block_lift[7] is not None else None,)
+        message = check_identity_parameters(*block_lift[2:7]) or (check_ends_parameters(*block_lift[7]) if block_lift[7] is not None else None)
+        if message:
+            raise ValueError("block_lift = (bed_path, genome, k, rate, band, max_len, max_edits, ends): " + message)
+        if block_lift[1] not in [fa.basename(p) for p in fastas]:
+            raise ValueError(f"block_lift: genome {block_lift[1]} is not among {[fa.basename(p) for p in fastas]}")
+        if block_paf is not None and block_paf != block_lift[2:]:
+            raise ValueError("block_paf and block_lift take the same (k, rate, band, max_len, max_edits, ends)")
     if gap_block_links and gap_links is None:
         raise ValueError("gap_block_links needs gap_links = (rate, min_anchors)")
     if gap_block_links and len(fastas) > 32:
@@ -1248,23 +1268,49 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
             st.rows += [(f"block_ends:{name}", (backend.ctx.timing(name)[0] - ends_before[name]) * 1e-3) for name in ends_timers]
             backend.ctx.profile(False)
         st.mark("block_ends_done")
+    lift_timers = ("lift_scan", "lift_search")
     if block_paf is not None:
         st.start("block_paf")
         from . import assess as assess_
         if benchmark:                                         # (device events around the calls of this stage only)
             backend.ctx.profile(True)
             paf_timers = ("cigar_atoms", "cigar_merge")
-            paf_before = {name: backend.ctx.timing(name)[0] for name in paf_timers}
-        text = assess_.paf_table(assess_.block_alignments(backend.ctx, {fa.basename(p): genomes[p] for p in fastas},
-                                                          assess_.read_blocks(f"{prefix}.synteny_blocks.tsv"), *block_paf[:5], ends=block_paf[5]))
+            paf_before = {name: backend.ctx.timing(name)[0] for name in paf_timers + lift_timers}
+        paf_rows = assess_.block_alignments(backend.ctx, {fa.basename(p): genomes[p] for p in fastas}, assess_.read_blocks(f"{prefix}.synteny_blocks.tsv"),
+                                            *block_paf[:5], ends=block_paf[5],
+                                            lift=(block_lift[1], assess_.read_bed(block_lift[0])) if block_lift is not None else None)
+        if block_lift is not None:                            # (one pass serves both files)
+            paf_rows, lifted_rows = paf_rows
+        text = assess_.paf_table(paf_rows)
         with open(f"{prefix}.block_alignments.paf", "w", encoding="utf-8") as fh:
             fh.write(text)
         eng.outputs[f"{prefix}.block_alignments.paf"] = text
         st.stop()
         if benchmark:
             st.rows += [(f"block_paf:{name}", (backend.ctx.timing(name)[0] - paf_before[name]) * 1e-3) for name in paf_timers]
+            lift_times = [(f"block_lift:{name}", (backend.ctx.timing(name)[0] - paf_before[name]) * 1e-3) for name in lift_timers]
             backend.ctx.profile(False)
         st.mark("block_paf_done")
+    if block_lift is not None:
+        st.start("block_lift")
+        from . import assess as assess_
+        if block_paf is None:
+            if benchmark:                                     # (device events around the calls of this stage only)
+                backend.ctx.profile(True)
+                lift_before = {name: backend.ctx.timing(name)[0] for name in lift_timers}
+            lifted_rows = assess_.block_lift(backend.ctx, {fa.basename(p): genomes[p] for p in fastas}, assess_.read_blocks(f"{prefix}.synteny_blocks.tsv"),
+                                             block_lift[1], assess_.read_bed(block_lift[0]), *block_lift[2:7], ends=block_lift[7])
+            if benchmark:
+                lift_times = [(f"block_lift:{name}", (backend.ctx.timing(name)[0] - lift_before[name]) * 1e-3) for name in lift_timers]
+                backend.ctx.profile(False)
+        text = assess_.lift_table(lifted_rows, *block_lift[2:7], ends=block_lift[7])
+        with open(f"{prefix}.block_lift.tsv", "w", encoding="utf-8") as fh:
+            fh.write(text)
+        eng.outputs[f"{prefix}.block_lift.tsv"] = text
+        st.stop()
+        if benchmark:
+            st.rows += lift_times
+        st.mark("block_lift_done")
     if gaps:
         st.start("gaps")
         from . import assess as assess_, gaps as gaps_
