@@ -889,6 +889,41 @@ typedef struct
 int nts_cigar_lift(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains,
                    const nts_lift_query* queries, uint64_t n_queries, nts_lift_hit* hits);
 
+/* ---- the alignment counts of ranges of the chains' CIGARs: lift identity -----------------------------------------------------
+ * nts_cigar_lift_stats: cigar, chains as for nts_cigar_lift; ranges = n_ranges of {chain, side, lo, hi}: the bases lo .. hi - 1 of
+ *   side A (0) or B (1) of the chain, "src"; valid for chain < n_chains, side <= 1, lo < hi <= len_src.  c_lo / c_hi = the column of
+ *   the chain that holds base lo / base hi - 1 (both consume src).  COUNTED are the chain's columns c_lo .. c_hi: columns that
+ *   consume the other side only ("oth") are counted strictly between the two, never in front of c_lo or behind c_hi.  eq, x: the = and
+ *   X columns among them; src_gap: those that consume src only (D for side 0, I for side 1); oth_gap: those that consume oth only;
+ *   src_gaps / oth_gaps: the maximal runs of that kind in the chain's column sequence that hold a counted column (neighbouring
+ *   entries of one kind are one run; a run cut by the range's border counts once); [oth_lo, oth_hi): the lifted span -- oth_lo = the
+ *   hit position of lo, oth_hi = the hit position of hi - 1, plus 1 if that column is = or X -- so eq + x + src_gap = hi - lo and
+ *   eq + x + oth_gap = oth_hi - oth_lo; reserved is 0.  stats: n_ranges host entries, written only when the call succeeds.  Refusals
+ *   as for nts_cigar_lift with ranges in the place of queries: NTS_ERANGE before any launch (2^32 entries, chains or ranges or more,
+ *   before any array is read; 2^63 bases or more), NTS_EINVAL before any launch with the smallest chain named (first not
+ *   nondecreasing, first + n_cig > n_cigar), NTS_EINVAL after the launch with stats untouched: "the entries of chain ... are no CIGAR
+ *   of its lengths", otherwise "range ... is outside its chain" with the smallest such range (lo = hi is outside).  No range: the
+ *   entries are checked, no search is launched, nothing is written.  ONE exclusive scan over all entries gives the global prefixes of
+ *   (A bases, B bases, X columns, D columns, I heads | D heads << 32), nts_cigar_lift's check kernel and a minimum reduction (timer
+ *   "lift_stats_scan"); one lane per range makes two upper-bound searches, takes the whole entries between the two as prefix
+ *   differences, adds the partial entries at both ends and stores one 64-byte record, a second minimum reduction (timer
+ *   "lift_stats_search").  On the context's stream, in its workspace; no atomic, no launch per chain or range, no floating point: the
+ *   same input gives the same bytes.  docs/design/04_25_lift_identity.md; csrc/nts_cigar.inc; ntsynt_amd/assess.py
+ *   block_lift_identity, `ntSynt --lift-identity / --lift-windows`, `bin/ntsynt_block_stats --lift-identity-out / --lift-windows-out`. */
+typedef struct
+{
+  uint32_t chain, side;
+  uint64_t lo, hi;
+} nts_lift_range;
+typedef struct
+{
+  uint64_t oth_lo, oth_hi, eq, x, src_gap, oth_gap;
+  uint32_t src_gaps, oth_gaps;
+  uint64_t reserved;
+} nts_lift_stats;
+int nts_cigar_lift_stats(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains,
+                         const nts_lift_range* ranges, uint64_t n_ranges, nts_lift_stats* stats);
+
 /* ---- C1-C5: minimizer graph -> collinear chains -----------------------------------------------------
  * replaces ntjoin_utils.read_minimizers' duplicate removal, filter_minimizers and build_graph
  * (call sites bin/ntsynt_synteny.py:607-612, 483, 539) and the path walk of Ntjoin.find_paths

@@ -97,6 +97,16 @@ class LiftHit(ctypes.Structure):
     _fields_ = [("pos", u64), ("entry", u64), ("off", u64), ("code", u32), ("reserved", u32)]
 
 
+class LiftRange(ctypes.Structure):
+    "nts_lift_range: the bases lo .. hi - 1 of one side of a chain (nts_cigar_lift_stats)"
+    _fields_ = [("chain", u32), ("side", u32), ("lo", u64), ("hi", u64)]
+
+
+class LiftStats(ctypes.Structure):
+    "nts_lift_stats: the lifted span of a range and the columns of each kind between its two end columns (nts_cigar_lift_stats)"
+    _fields_ = [(n, u64) for n in ("oth_lo", "oth_hi", "eq", "x", "src_gap", "oth_gap")] + [("src_gaps", u32), ("oth_gaps", u32), ("reserved", u64)]
+
+
 class MxList(ctypes.Structure):
     _fields_ = [("h1", c_vp), ("rec", c_vp), ("pos", c_vp), ("keep", c_vp), ("list_id", c_vp), ("n", u64)]
 
@@ -265,6 +275,7 @@ SYMBOLS = [
     ("nts_edit_extend_script_last_plan", ctypes.c_int, [c_vp, c_u64p, c_u64p, c_u64p]),
     ("nts_cigar_build", ctypes.c_int, [c_vp, c_vp, u64, u64, c_vp, c_vp, ctypes.POINTER(c_vp), c_u64p, c_vp]),
     ("nts_cigar_lift", ctypes.c_int, [c_vp, c_vp, u64, c_vp, u64, c_vp, u64, c_vp]),
+    ("nts_cigar_lift_stats", ctypes.c_int, [c_vp, c_vp, u64, c_vp, u64, c_vp, u64, c_vp]),
     ("nts_genome_valid_bases", ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(Interval), u64, c_vp]),
     ("nts_minhash_pairs", ctypes.c_int, [c_vp, u32, c_vp, c_vp, u64, c_vp, c_vp, u64, c_vp, c_vp]),
     ("nts_graph_build", ctypes.c_int, [c_vp, u32, ctypes.POINTER(MxList), ctypes.POINTER(Graph)]),

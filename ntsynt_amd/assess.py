@@ -26,7 +26,10 @@ Two things, both over `<prefix>.synteny_blocks.tsv`:
   docs/design/04_22_block_alignments.md.
 * block lift (`ntSynt --block-lift BED --lift-genome NAME`, `ntsynt_block_stats --lift-bed --lift-genome --lift-out`): the intervals of
   one genome mapped through those alignments into the other genomes -- the coordinate map of the chains' CIGARs on the GPU
-  (nts_cigar_lift); docs/design/04_23_block_lift.md."""
+  (nts_cigar_lift); docs/design/04_23_block_lift.md.
+* lift identity (`ntSynt --lift-identity`, `--lift-windows W`, `ntsynt_block_stats --lift-identity-out`, `--lift-windows --lift-windows-out`):
+  the matches, mismatches and missing bases of every lifted interval and of a window grid over one genome -- range sums over the
+  chains' CIGARs on the GPU (nts_cigar_lift_stats); docs/design/04_25_lift_identity.md."""
 import os
 import re
 from collections import namedtuple
@@ -838,7 +841,7 @@ def _round_paf_rows(blocks, a, found):
 
 
 def block_alignments(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_RATE, band=IDENTITY_BAND, max_len=IDENTITY_MAX_LEN, max_edits=0, ends=None,
-                     lift=None):
+                     lift=None, lift_identity=None):
     """One PAF record with a cg:Z: CIGAR per aligned chain of every block and pair of its lines (target = line a, query = line b): the
     anchors, segments and final per-segment results of block_identity for the same first five parameters, the canonical scripts of
     block_variants / block_wide_variants, and with ends = (ends_max_len, ends_max_edits, ends_penalty) the flanks of block_ends attached
@@ -848,24 +851,33 @@ def block_alignments(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_R
     block_identity's order, a pair's chains ascending by x; a pair without an aligned segment has none.  Per pair the NM of its chains
     less the flanks' edits must be the identity pass's `edits`, and the target and query bases less the flanks' must be aligned_a and
     aligned_b: RuntimeError otherwise.  docs/design/04_22_block_alignments.md.  lift = (source, intervals): the same pass also lifts
-    read_bed's intervals of the genome `source` (block_lift); returns (those lines, block_lift's rows)."""
+    read_bed's intervals of the genome `source` (block_lift); returns (those lines, block_lift's rows).  lift_identity = (source,
+    [intervals, ...]): the same pass also counts the alignment columns of every set of intervals (block_lift_identity; a set that IS
+    the lift's dict is joined once for both); returns (those lines, block_lift's rows or None, [block_lift_identity's rows per set])."""
     message = check_identity_parameters(int(k), int(rate), int(band), int(max_len), int(max_edits)) or \
         (check_ends_parameters(*(int(v) for v in ends)) if ends is not None else None)
     if message:
         raise ValueError(message)
     k, rate, band, max_len, max_edits = int(k), int(rate), int(band), int(max_len), int(max_edits)
     pairs, length, found = [], {}, {}
-    lifter = _Lifter(genomes_by_name, blocks, *lift) if lift is not None else None
+    if lift_identity is not None:
+        lifter = _lifter_of(genomes_by_name, blocks, lift, lift_identity)
+    else:
+        lifter = _Lifter(genomes_by_name, blocks, *lift) if lift is not None else None
     for a in _alignment_rounds(ctx, genomes_by_name, blocks, k, rate, band, max_len, max_edits, ends, pairs, length):
         _round_paf_rows(blocks, a, found)
         if lifter is not None:
             lifter.add_round(ctx, a, pairs)
     rows = [row for p in pairs for row in found[p]]
+    if lift_identity is not None:
+        return (rows,) + lifter.results(genomes_by_name)
     return rows if lifter is None else (rows, lifter.rows(genomes_by_name))
 
 
 LIFT_COLUMNS = ("genome", "contig", "start", "end", "name", "block_id", "to_genome", "to_contig", "to_start", "to_end", "orientation", "ch", "src_start",
                 "src_end", "status")
+LIFT_IDENTITY_COLUMNS = LIFT_COLUMNS[:14] + ("matches", "mismatches", "src_gap_bases", "to_gap_bases", "src_gaps", "to_gaps", "columns", "identity", "status")
+LIFT_STATS_FIELDS = ("eq", "x", "src_gap", "oth_gap", "src_gaps", "oth_gaps")       # of LIFT_STATS_DTYPE, in the order of the columns matches .. to_gaps
 
 
 def read_bed(path):
@@ -977,25 +989,68 @@ def lift_rows(spans, overlaps, hits):
     return dict(overlaps, to_start=np.where(mirrored, o1 - v_hi, o0 + v_lo), to_end=np.where(mirrored, o1 - v_lo, o0 + v_hi))
 
 
-def lift_table(rows, k, rate, band, max_len, max_edits=0, ends=None):
+def lift_table(rows, k, rate, band, max_len, max_edits=0, ends=None, columns=LIFT_COLUMNS):
     """TSV of block_lift's rows: a header, one line per (interval, chain) overlap and one `unmapped` line per interval without any, then
     the footer with the parameters"""
-    lines = ["\t".join(LIFT_COLUMNS)] + ["\t".join(str(r[c]) for c in LIFT_COLUMNS) for r in rows]
+    lines = ["\t".join(columns)] + ["\t".join(str(r[c]) for c in columns) for r in rows]
     lines.append(f"# k {int(k)}, rate {int(rate)}, band {int(band)}, max_len {int(max_len)}, max_edits {int(max_edits)}" +
                  (f", ends_max_len {int(ends[0])}, ends_max_edits {int(ends[1])}, ends_penalty {int(ends[2])}" if ends is not None else ""))
     return "\n".join(lines) + "\n"
 
 
-class _Lifter:
-    "block_lift's state over the rounds of the alignment pass: per round the spans, ONE nts_cigar_lift and the rows' arrays"
+def lift_identity_table(rows, k, rate, band, max_len, max_edits=0, ends=None):
+    "TSV of block_lift_identity's rows: LIFT_IDENTITY_COLUMNS; line order, status, the `unmapped` line and the footer are lift_table's"
+    return lift_table(rows, k, rate, band, max_len, max_edits, ends, columns=LIFT_IDENTITY_COLUMNS)
 
-    def __init__(self, genomes_by_name, blocks, source, intervals):
+
+def window_intervals(sizes, width):
+    """The window grid of one genome in read_bed's shape: sizes = its contigs in FASTA order, (name, bases) pairs or a dict; per contig
+    the intervals [0, W), [W, 2 W), ... with a shorter last one, named w0, w1, ... (counted per contig).  W < 1 raises ValueError.  A
+    Python loop runs over contigs, never over windows."""
+    import numpy as np
+    width = int(width)
+    if width < 1:
+        raise ValueError(f"a window has at least one base (W = {width})")
+    contig, name, start, end = [], [], [], []
+    for c, bases in (sizes.items() if hasattr(sizes, "items") else sizes):
+        s = np.arange(0, int(bases), width, dtype=np.int64)
+        contig += [str(c)] * s.size
+        name += np.char.add("w", np.arange(s.size).astype(str)).tolist()
+        start.append(s)
+        end.append(np.minimum(s + width, int(bases)))
+    none = np.zeros(0, dtype=np.int64)
+    return {"contig": contig, "name": name, "start": np.concatenate(start + [none]), "end": np.concatenate(end + [none])}
+
+
+def lift_ranges(queries, overlaps, wanted=None):
+    """One range per overlap of lift_queries, for nts_cigar_lift_stats: overlap o's two queries are pos = u_lo and pos = u_hi - 1 on one
+    chain and side (the table of lift_queries), its range is (chain, side, u_lo, u_hi).  wanted: a bool per INTERVAL -- only the
+    overlaps of those intervals get a range.  Returns (ranges, which): a LIFT_RANGE_DTYPE array and the overlaps they belong to.  Array
+    operations alone."""
+    import numpy as np
+    from .device import LIFT_RANGE_DTYPE
+    interval = np.asarray(overlaps["interval"], dtype=np.int64)
+    if queries.size != 2 * interval.size:
+        raise ValueError("lift_ranges: two queries per overlap")
+    which = np.arange(interval.size) if wanted is None else np.flatnonzero(np.asarray(wanted, dtype=bool)[interval])
+    ranges = np.zeros(which.size, dtype=LIFT_RANGE_DTYPE)
+    ranges["chain"], ranges["side"] = queries["chain"][2 * which], queries["side"][2 * which]
+    ranges["lo"], ranges["hi"] = queries["pos"][2 * which], queries["pos"][2 * which + 1] + np.uint64(1)
+    return ranges, which
+
+
+class _Lifter:
+    """block_lift's state over the rounds of the alignment pass: per round the spans, ONE nts_cigar_lift and the rows' arrays.  stats: a
+    bool per interval, or None -- per round also ONE nts_cigar_lift_stats for all overlaps of the intervals it marks (block_lift_identity)"""
+
+    def __init__(self, genomes_by_name, blocks, source, intervals, stats=None):
         if source not in genomes_by_name:
             raise ValueError(f"--lift-genome {source} is not among the genomes {sorted(genomes_by_name)}")
-        self.blocks, self.source, self.intervals = blocks, source, intervals
+        self.blocks, self.source, self.intervals, self.stats = blocks, source, intervals, stats
         self.contigs = None                                   # the source genome's records, once it was resident
         self.parts, self.info = [], {}                        # per round lift_rows' arrays with pair and ch; pair -> its columns
         self.index_of = None                                  # (line a, line b) -> the pair's place in block_identity's order
+        self.sorted, self.sets = None, None                   # rows(): the parts in line order; _lifter_of: which intervals go to which table
 
     def add_round(self, ctx, a, pairs):
         import numpy as np
@@ -1026,9 +1081,22 @@ class _Lifter:
         queries, overlaps = lift_queries(spans, self.intervals)
         hits = ctx.cigar_lift(a.cigar, a.records, queries)    # (one call per round, for all pairs in which the source takes part)
         rows = lift_rows(spans, overlaps, hits)
+        if self.stats is not None:
+            from .device import CIG_EQ, CIG_X
+            ranges, which = lift_ranges(queries, overlaps, self.stats)
+            stats = ctx.cigar_lift_stats(a.cigar, a.records, ranges)                 # (one call per round, beside the lift's)
+            left, right = hits[0::2][which], hits[1::2][which]
+            both = stats["eq"] + stats["x"]
+            if np.any(stats["oth_lo"] != left["pos"]) or np.any(stats["oth_hi"] != right["pos"] + np.isin(right["code"], (CIG_EQ, CIG_X))) or \
+                    np.any(both + stats["src_gap"] != ranges["hi"] - ranges["lo"]) or np.any(both + stats["oth_gap"] != stats["oth_hi"] - stats["oth_lo"]):
+                raise RuntimeError("the counts of a lifted interval do not add up to its two spans")
+            for f in LIFT_STATS_FIELDS:                       # (-1: an overlap of an interval whose table has no counts)
+                rows[f] = np.full(overlaps["interval"].size, -1, dtype=np.int64)
+                rows[f][which] = stats[f].astype(np.int64)
         self.parts.append(dict(rows, pair=pair[rows["span"]], ch=chains["ch"][order][rows["span"]]))
 
-    def rows(self, genomes_by_name):
+    def rows(self, genomes_by_name, begin=0, end=None, identity=False):
+        "the lines of the intervals begin .. end - 1 (all): LIFT_COLUMNS, or with identity LIFT_IDENTITY_COLUMNS"
         import numpy as np
         if self.contigs is None:                              # (the source is in no pair: its records are read for the contig check alone)
             g = genomes_by_name[self.source]
@@ -1038,25 +1106,101 @@ class _Lifter:
             if loaded:
                 g.free()
         iv = self.intervals
-        for c in iv["contig"]:
+        for c in dict.fromkeys(iv["contig"]):
             if c not in self.contigs:
                 raise ValueError(f"genome {self.source} has no record {c} (--block-lift)")
-        fields = ("interval", "pair", "ch", "lo", "hi", "to_start", "to_end")
-        got = {f: np.concatenate([p[f] for p in self.parts]) if self.parts else np.zeros(0, dtype=np.int64) for f in fields}
-        order = np.lexsort((got["ch"], got["pair"], got["interval"]))
-        got = {f: v[order].tolist() for f, v in got.items()}
-        starts, ends, out, o = iv["start"].tolist(), iv["end"].tolist(), [], 0
-        for j, (contig, name) in enumerate(zip(iv["contig"], iv["name"])):
-            head = {"genome": self.source, "contig": contig, "start": starts[j], "end": ends[j], "name": name}
-            if o == len(order) or got["interval"][o] != j:
-                out.append(dict(head, **{c: "." for c in LIFT_COLUMNS[5:14]}, status="unmapped"))
-            while o < len(order) and got["interval"][o] == j:
+        if self.sorted is None:
+            fields = ("interval", "pair", "ch", "lo", "hi", "to_start", "to_end") + (LIFT_STATS_FIELDS if self.stats is not None else ())
+            got = {f: np.concatenate([p[f] for p in self.parts]) if self.parts else np.zeros(0, dtype=np.int64) for f in fields}
+            order = np.lexsort((got["ch"], got["pair"], got["interval"]))
+            self.sorted = {f: v[order] for f, v in got.items()}
+        end = len(iv["contig"]) if end is None else end
+        o, stop = (int(v) for v in np.searchsorted(self.sorted["interval"], [begin, end]))
+        got = {f: v[o:stop].tolist() for f, v in self.sorted.items()}
+        starts, ends, out, o, n = iv["start"].tolist(), iv["end"].tolist(), [], 0, stop - o
+        absent = {c: "." for c in (LIFT_IDENTITY_COLUMNS[5:-1] if identity else LIFT_COLUMNS[5:14])}
+        for j in range(begin, end):
+            head = {"genome": self.source, "contig": iv["contig"][j], "start": starts[j], "end": ends[j], "name": iv["name"][j]}
+            if o == n or got["interval"][o] != j:
+                out.append(dict(head, **absent, status="unmapped"))
+            while o < n and got["interval"][o] == j:
                 block_id, to_genome, to_contig, sign = self.info[got["pair"][o]]
-                out.append(dict(head, block_id=block_id, to_genome=to_genome, to_contig=to_contig, to_start=got["to_start"][o], to_end=got["to_end"][o],
-                                orientation=sign, ch=got["ch"][o], src_start=got["lo"][o], src_end=got["hi"][o],
-                                status="full" if (got["lo"][o], got["hi"][o]) == (starts[j], ends[j]) else "partial"))
+                row = dict(head, block_id=block_id, to_genome=to_genome, to_contig=to_contig, to_start=got["to_start"][o], to_end=got["to_end"][o],
+                           orientation=sign, ch=got["ch"][o], src_start=got["lo"][o], src_end=got["hi"][o],
+                           status="full" if (got["lo"][o], got["hi"][o]) == (starts[j], ends[j]) else "partial")
+                if identity:
+                    counts = [got[f][o] for f in LIFT_STATS_FIELDS]
+                    columns = sum(counts[:4])                 # (lo < hi: at least one column)
+                    v = (1000000 * counts[0]) // columns
+                    row.update(zip(LIFT_IDENTITY_COLUMNS[14:20], counts), columns=columns, identity=f"{v // 1000000}.{v % 1000000:06d}")
+                out.append(row)
                 o += 1
         return out
+
+    def results(self, genomes_by_name):
+        "(block_lift's rows or None, [block_lift_identity's rows per set]) of _lifter_of's sets"
+        lift, identity = self.sets
+        return (self.rows(genomes_by_name, *lift) if lift is not None else None, [self.rows(genomes_by_name, b, e, identity=True) for b, e in identity])
+
+
+def _lifter_of(genomes_by_name, blocks, lift, lift_identity):
+    """the _Lifter of one pass that serves block_lift's table (lift = (source, intervals) or None) and block_lift_identity's tables
+    (lift_identity = (source, [intervals, ...])): the sets are joined as ONE list of intervals, so a round makes one nts_cigar_lift and one
+    nts_cigar_lift_stats whatever the number of tables; a set that is the lift's own dict is joined once and read for both tables"""
+    import numpy as np
+    source, sets = lift_identity[0], list(lift_identity[1])
+    if lift is not None and lift[0] != source:
+        raise ValueError("the lift and the lift identity take the intervals of one genome")
+    shared = [i for i, s in enumerate(sets) if lift is not None and s is lift[1]]
+    every = ([lift[1]] if lift is not None and not shared else []) + sets
+    cut = np.concatenate([[0], np.cumsum([len(s["contig"]) for s in every])]).tolist()
+    spans = list(zip(cut[:-1], cut[1:]))
+    stats = np.ones(cut[-1], dtype=bool)
+    if lift is not None and not shared:
+        stats[:cut[1]] = False
+    intervals = {"contig": [c for s in every for c in s["contig"]], "name": [n for s in every for n in s["name"]],
+                 "start": np.concatenate([np.asarray(s["start"], dtype=np.int64) for s in every]),
+                 "end": np.concatenate([np.asarray(s["end"], dtype=np.int64) for s in every])}
+    lifter = _Lifter(genomes_by_name, blocks, source, intervals, stats=stats)
+    of_sets = spans[len(every) - len(sets):]
+    lifter.sets = ((of_sets[shared[0]] if shared else spans[0]) if lift is not None else None, of_sets)
+    return lifter
+
+
+def record_sizes(genomes_by_name, source):
+    "[(record, bases)] of the genome `source` in FASTA order, for window_intervals (a genome that is loaded for this alone is freed again)"
+    if source not in genomes_by_name:
+        raise ValueError(f"--lift-genome {source} is not among the genomes {sorted(genomes_by_name)}")
+    g = genomes_by_name[source]
+    loaded = callable(g)
+    g = g() if loaded else g
+    sizes = list(zip(g.names, (int(n) for n in g.rec_len)))
+    if loaded:
+        g.free()
+    return sizes
+
+
+def block_lift_identity(ctx, genomes_by_name, blocks, source, intervals, k=IDENTITY_K, rate=IDENTITY_RATE, band=IDENTITY_BAND, max_len=IDENTITY_MAX_LEN,
+                        max_edits=0, ends=None, lift=None):
+    """block_lift's lines with the alignment counts of every lifted interval: for every interval (read_bed's or window_intervals' dict) of
+    the genome `source` and every chain it overlaps, the = and X columns, the bases either genome lacks and the runs of such bases between
+    the columns of the clipped part's first and last base (nts_cigar_lift_stats; per round ONE call for all overlaps of all pairs,
+    beside block_lift's nts_cigar_lift), as dicts of LIFT_IDENTITY_COLUMNS: columns = the sum of the four counts, identity =
+    10^6 matches // columns as d.dddddd; an interval that overlaps no chain has `.` in block_id .. identity.  intervals: one dict, or a
+    list of them -- then a list of row lists, from one pass.  lift: a dict of intervals (it may be one of `intervals`) whose block_lift
+    rows the same pass makes as well; returns (those rows, the rows above).  docs/design/04_25_lift_identity.md."""
+    message = check_identity_parameters(int(k), int(rate), int(band), int(max_len), int(max_edits)) or \
+        (check_ends_parameters(*(int(v) for v in ends)) if ends is not None else None)
+    if message:
+        raise ValueError(message)
+    one = isinstance(intervals, dict)
+    pairs, length = [], {}
+    lifter = _lifter_of(genomes_by_name, blocks, (source, lift) if lift is not None else None, (source, [intervals] if one else intervals))
+    for a in _alignment_rounds(ctx, genomes_by_name, blocks, int(k), int(rate), int(band), int(max_len), int(max_edits), ends, pairs, length, only=source):
+        lifter.add_round(ctx, a, pairs)
+    lifted, identity = lifter.results(genomes_by_name)
+    identity = identity[0] if one else identity
+    return identity if lift is None else (lifted, identity)
 
 
 def block_lift(ctx, genomes_by_name, blocks, source, intervals, k=IDENTITY_K, rate=IDENTITY_RATE, band=IDENTITY_BAND, max_len=IDENTITY_MAX_LEN,
@@ -1190,6 +1334,11 @@ def main(argv=None):
                    "alignments into the other genomes (GPU); it takes the parameters of --paf-out")
     p.add_argument("--lift-genome", help="the genome the intervals of --lift-bed lie on: a FASTA base name, as in column 2 of the block table")
     p.add_argument("--lift-out", help="file for the lifted intervals (one line per interval and aligned chain it overlaps)")
+    p.add_argument("--lift-identity-out", help="with --lift-bed and --lift-genome: file for the lifted intervals with their alignment counts (matches, "
+                   "mismatches, the bases either genome lacks, identity; GPU)")
+    p.add_argument("--lift-windows", help="with --lift-genome and --lift-windows-out: the same counts for windows of this many bases over every record "
+                   "of that genome", type=int)
+    p.add_argument("--lift-windows-out", help="file for the windows of --lift-windows")
     p.add_argument("--ends-max-len", help=f"longest flank that is extended, 1..65535 [{ENDS_MAX_LEN}]", type=int, default=ENDS_MAX_LEN)
     p.add_argument("--ends-max-edits", help=f"most edits within one flank, 1..1023 [{ENDS_MAX_EDITS}]", type=int, default=ENDS_MAX_EDITS)
     p.add_argument("--ends-penalty", help=f"what an edit costs the extension's score, against 2 for a matching pair of bases, 3..255 [{ENDS_PENALTY}]",
@@ -1213,8 +1362,18 @@ def main(argv=None):
         message = check_identity_parameters(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits)
         if message:
             p.error(message)
+    if args.lift_identity_out and not args.lift_bed:
+        p.error("--lift-identity-out needs the intervals: --lift-bed (and --lift-genome)")
+    if (args.lift_windows is not None) != bool(args.lift_windows_out):
+        p.error("--lift-windows and --lift-windows-out go together")
+    if args.lift_windows is not None:
+        if not args.lift_genome:
+            p.error("--lift-windows needs --lift-genome: the genome the windows lie on")
+        if args.lift_windows < 1:
+            p.error("--lift-windows: a window has at least one base")
     if args.lift_bed or args.lift_genome or args.lift_out:
-        if not (args.lift_bed and args.lift_genome and args.lift_out):
+        if not (args.lift_genome and (args.lift_windows_out or (args.lift_bed and (args.lift_out or args.lift_identity_out))) and
+                bool(args.lift_bed) == bool(args.lift_out or args.lift_identity_out)):
             p.error("--lift-bed, --lift-genome and --lift-out go together")
         if not args.fastas:
             p.error("--lift-out needs the genomes: --fastas")
@@ -1270,7 +1429,29 @@ def main(argv=None):
                 end_rows = block_ends(ctx, loaders, read_blocks(args.tsv), *e_args)
             with open(args.ends_out, "w", encoding="utf-8") as fh:
                 fh.write(ends_table(end_rows, *e_args))
-        if args.paf_out or args.lift_out:                     # (one pass gives both files)
+        if args.lift_identity_out or args.lift_windows_out:   # (one pass gives every file of the lift, and the PAF)
+            a_args = dict(max_edits=args.identity_max_edits, ends=(args.ends_max_len, args.ends_max_edits, args.ends_penalty) if args.ends_out else None)
+            intervals = read_bed(args.lift_bed) if args.lift_bed else None
+            sets = ([intervals] if args.lift_identity_out else []) + \
+                ([window_intervals(record_sizes(loaders, args.lift_genome), args.lift_windows)] if args.lift_windows_out else [])
+            if args.paf_out:
+                paf_rows, lift_rows_, counted = block_alignments(ctx, loaders, read_blocks(args.tsv), *id_args, **a_args,
+                                                                 lift=(args.lift_genome, intervals) if args.lift_out else None,
+                                                                 lift_identity=(args.lift_genome, sets))
+                with open(args.paf_out, "w", encoding="utf-8") as fh:
+                    fh.write(paf_table(paf_rows))
+            else:
+                counted = block_lift_identity(ctx, loaders, read_blocks(args.tsv), args.lift_genome, sets, *id_args, **a_args,
+                                              lift=intervals if args.lift_out else None)
+                if args.lift_out:
+                    lift_rows_, counted = counted
+            if args.lift_out:
+                with open(args.lift_out, "w", encoding="utf-8") as fh:
+                    fh.write(lift_table(lift_rows_, *id_args, **a_args))
+            for path, rows in zip([f for f in (args.lift_identity_out, args.lift_windows_out) if f], counted):
+                with open(path, "w", encoding="utf-8") as fh:
+                    fh.write(lift_identity_table(rows, *id_args, **a_args))
+        elif args.paf_out or args.lift_out:                   # (one pass gives both files)
             a_args = dict(max_edits=args.identity_max_edits, ends=(args.ends_max_len, args.ends_max_edits, args.ends_penalty) if args.ends_out else None)
             intervals = read_bed(args.lift_bed) if args.lift_out else None
             if args.paf_out:

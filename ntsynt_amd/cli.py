@@ -99,8 +99,13 @@ def build_parser():
     p.add_argument("--block-lift", metavar="BED", help="after the run, write <prefix>.block_lift.tsv: the intervals of this BED file, which lie on the\n"
                    "genome --lift-genome names, mapped through the alignments of --block-paf into the other genomes, one line per interval\n"
                    "and aligned chain it overlaps; takes the parameters of --block-paf; works with or without the other block switches")
-    p.add_argument("--lift-genome", metavar="NAME", help="with --block-lift: the genome its intervals lie on, a FASTA base name as in column 2 of the\n"
-                   "block table")
+    p.add_argument("--lift-genome", metavar="NAME", help="with --block-lift or --lift-windows: the genome the intervals lie on, a FASTA base name as in\n"
+                   "column 2 of the block table")
+    p.add_argument("--lift-identity", help="with --block-lift BED (which it needs), write <prefix>.block_lift_identity.tsv: the lines of\n"
+                   "<prefix>.block_lift.tsv with, per lifted interval, its matches, mismatches, the bases either genome lacks, the runs of such\n"
+                   "bases and the identity", action="store_true")
+    p.add_argument("--lift-windows", metavar="W", help="with --lift-genome NAME (which it needs), write <prefix>.block_windows.tsv: the same columns for\n"
+                   "windows of W bases over every record of NAME -- identity along the genome; works with or without --block-lift", type=int)
     p.add_argument("--ends-max-len", help="longest flank that is extended, 1..65535 [4096]", type=int, default=4096)
     p.add_argument("--ends-max-edits", help="most edits within one flank, 1..1023 [255]", type=int, default=255)
     p.add_argument("--ends-penalty", help="what an edit costs the extension's score, against 2 for a matching pair of bases, 3..255 [6]", type=int,
@@ -237,8 +242,31 @@ def check_reports(parser, args):
         message = check_identity_parameters(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits)
         if message:
             parser.error(message)
-    if args.lift_genome and not args.block_lift:
+    if args.lift_genome and not args.block_lift and args.lift_windows is None:
         parser.error("--lift-genome names the genome of the intervals of --block-lift BED")
+    if args.lift_identity:
+        if not args.block_lift:
+            parser.error("--lift-identity counts the alignment columns of the intervals of --block-lift BED: it needs that switch")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            parser.error("--lift-identity works from the genomes resident on one GPU: run it on one rank, or lift through the finished run with "
+                         "ntsynt_block_stats --tsv <prefix>.synteny_blocks.tsv --fai ... --fastas ... --lift-bed BED --lift-genome NAME "
+                         "--lift-identity-out <prefix>.block_lift_identity.tsv")
+    if args.lift_windows is not None:
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            parser.error("--lift-windows works from the genomes resident on one GPU: run it on one rank, or count through the finished run with "
+                         "ntsynt_block_stats --tsv <prefix>.synteny_blocks.tsv --fai ... --fastas ... --lift-genome NAME --lift-windows W "
+                         "--lift-windows-out <prefix>.block_windows.tsv")
+        if not args.lift_genome:
+            parser.error("--lift-windows W needs --lift-genome NAME: the genome the windows lie on (a FASTA base name)")
+        if args.lift_windows < 1:
+            parser.error("--lift-windows W: a window has at least one base")
+        names = [os.path.basename(path) for path in input_fastas(parser, args)]
+        if args.lift_genome not in names:
+            parser.error(f"--lift-genome {args.lift_genome} is not among the genomes {names}")
+        from .assess import check_identity_parameters
+        message = check_identity_parameters(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits)
+        if message:
+            parser.error(message)
     if args.block_lift:
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             parser.error("--block-lift works from the genomes resident on one GPU: run it on one rank, or lift through the finished run with "
@@ -371,6 +399,11 @@ def main(argv=None):
              f"{args.identity_band}, max_len {args.identity_max_len}, max_edits {args.identity_max_edits}" +
              (f", ends_max_len {args.ends_max_len}, ends_max_edits {args.ends_max_edits}, ends_penalty {args.ends_penalty}" if args.block_ends else "") + ")"]
             if args.block_lift else []) + \
+           [f"{stage} (lift_stats_scan, lift_stats_search; {what} on {args.lift_genome}; k {args.identity_k}, rate {args.identity_rate}, band "
+            f"{args.identity_band}, max_len {args.identity_max_len}, max_edits {args.identity_max_edits}" +
+            (f", ends_max_len {args.ends_max_len}, ends_max_edits {args.ends_max_edits}, ends_penalty {args.ends_penalty}" if args.block_ends else "") + ")"
+            for stage, what, on in (("block_lift_identity", args.block_lift, args.lift_identity),
+                                    ("block_windows", f"windows of {args.lift_windows}", args.lift_windows is not None)) if on] + \
            (["gaps"] if args.gaps else []) + \
            (["gap_links"] if args.gap_links else []) + (["gap_block_links"] if args.gap_block_links else []) + \
            (["gap_copies"] if args.gap_copies else []) + (["gap_copy_sites"] if args.gap_copy_sites else []) + \
@@ -426,7 +459,14 @@ def main(argv=None):
 
 
 def _run(pipeline, fastas, args, device, quiet):
-    pipeline.run(fastas, k=args.k, w=args.w, fpr=args.fpr, prefix=args.prefix, w_rounds=args.w_rounds,
+    lift_args = (args.lift_genome, args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits,
+                 (args.ends_max_len, args.ends_max_edits, args.ends_penalty) if args.block_ends else None)
+    more = {}                                                 # (only the switches that are on: a run without them makes the call it always made)
+    if args.lift_identity:
+        more["block_lift_identity"] = (args.block_lift,) + lift_args
+    if args.lift_windows is not None:
+        more["block_windows"] = (args.lift_windows,) + lift_args
+    pipeline.run(fastas, **more, k=args.k, w=args.w, fpr=args.fpr, prefix=args.prefix, w_rounds=args.w_rounds,
                  indel=args.indel, merge=args.merge, block_size=args.block_size, common=not args.no_common,
                  simplify=not args.no_simplify_graph, device=device, benchmark=args.benchmark,
                  dev=args.dev, interarrivals=args.interarrivals, assess=(args.assess_k, args.assess_s) if args.assess else None,

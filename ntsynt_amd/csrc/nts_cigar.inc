@@ -482,3 +482,185 @@ int cigar_lift_run(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const 
   if (worst[1] != SCRIPT_OK) return fail(ctx, NTS_EINVAL, "nts_cigar_lift: query " + std::to_string(worst[1]) + " is outside its chain");
   return NTS_OK;
 }
+
+// ---- the alignment counts of ranges of the chains' CIGARs (nts_cigar_lift_stats; ntsynt_amd/assess.py block_lift_identity) ----
+// docs/design/04_25_lift_identity.md.  Input: CIGAR entries and chain records as for nts_cigar_lift, and ranges {chain, side, lo, hi}: the
+// source bases lo .. hi - 1 of one side of a chain.  The answer counts the chain's columns from the column of base lo to the column of
+// base hi - 1: =, X, the columns that consume the source only, the columns that consume the other side only, the runs of either gap
+// kind, and the lifted span [oth_lo, oth_hi) on the other side.
+//   1  ONE rocprim::exclusive_scan over n_cigar + 1 elements of what a transform iterator makes of an entry -- (A bases, B bases, X
+//      columns, D columns, I heads | D heads << 32) -- into five arrays of n_cigar + 1 GLOBAL prefixes; a head is an entry whose
+//      predecessor in the array has another code, or entry 0.  = columns are A - X - D, I columns B - A + D.  k_lift_check, unchanged,
+//      checks entries and records against the A and B prefixes, a minimum reduction names the smallest chain (timer "lift_stats_scan").
+//   2  k_cig_lift_stats: one lane per range; validates it, finds the entries of base lo and of base hi - 1 with two upper-bound
+//      binary searches over Psrc, takes the whole entries between them as prefix differences and the two partial entries from their
+//      offsets, and stores one 64 B record; an invalid range stores nothing but its own index in its status word, a second minimum
+//      reduction names the smallest (timer "lift_stats_search").
+// No atomic, no launch per chain or range, no floating point, no host loop over entries or ranges.
+
+using LiftStatTuple = rocprim::tuple<uint64_t, uint64_t, uint64_t, uint64_t, uint64_t>; // A bases, B bases, X columns, D columns, I heads | D heads << 32
+static_assert(sizeof(nts_lift_range) == 24 && sizeof(nts_lift_stats) == 64, "the C ABI's layout");
+
+struct LiftStatOf // element e of the scan's input: what entry e adds; nothing behind the last entry
+{
+  const uint64_t* cigar;
+  uint64_t n_cigar;
+  __host__ __device__ LiftStatTuple operator()(uint64_t e) const
+  {
+    if (e >= n_cigar) return LiftStatTuple(0, 0, 0, 0, 0);
+    const uint64_t v = cigar[e], code = v & 15u, len = v >> 4;
+    const bool both = code == CIG_EQ || code == CIG_X;
+    const bool head = e == 0 || (cigar[e - 1] & 15u) != code;
+    return LiftStatTuple(both || code == CIG_D ? len : 0, both || code == CIG_I ? len : 0, code == CIG_X ? len : 0, code == CIG_D ? len : 0,
+                         !head ? 0 : code == CIG_I ? 1ull : code == CIG_D ? 1ull << 32 : 0); // (at most n_cigar < 2^32 heads of a kind: no carry between the halves)
+  }
+};
+
+struct LiftStatAdd
+{
+  __host__ __device__ LiftStatTuple operator()(const LiftStatTuple& x, const LiftStatTuple& y) const
+  {
+    return LiftStatTuple(rocprim::get<0>(x) + rocprim::get<0>(y), rocprim::get<1>(x) + rocprim::get<1>(y), rocprim::get<2>(x) + rocprim::get<2>(y),
+                         rocprim::get<3>(x) + rocprim::get<3>(y), rocprim::get<4>(x) + rocprim::get<4>(y));
+  }
+};
+
+__global__ __launch_bounds__(256) void k_cig_lift_stats(const uint64_t* __restrict__ cigar, uint64_t n_cigar, const nts_cig_chain* __restrict__ chains,
+                                                        uint64_t n_chains, const uint64_t* __restrict__ PA, const uint64_t* __restrict__ PB,
+                                                        const uint64_t* __restrict__ PX, const uint64_t* __restrict__ PD, const uint64_t* __restrict__ PH,
+                                                        const nts_lift_range* __restrict__ ranges, uint64_t n_ranges, nts_lift_stats* __restrict__ stats,
+                                                        uint32_t* __restrict__ status)
+{
+  const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (g >= n_ranges) return;
+  const nts_lift_range r = ranges[g];
+  if (r.chain >= n_chains || r.side > 1u) {
+    status[g] = (uint32_t)g;
+    return;
+  }
+  const nts_cig_chain ch = chains[r.chain];
+  const uint64_t first = ch.first, n = ch.n_cig;
+  const uint64_t len_src = r.side ? ch.len_b : ch.len_a;
+  // (the host refused the first two tests before the launch; a chain without entries holds no base: every index below is <= first + n <= n_cigar)
+  if (first > n_cigar || n > n_cigar - first || n == 0 || r.lo >= r.hi || r.hi > len_src) {
+    status[g] = (uint32_t)g;
+    return;
+  }
+  status[g] = SCRIPT_OK;
+  const uint64_t* __restrict__ P = r.side ? PB : PA;
+  const uint64_t* __restrict__ O = r.side ? PA : PB;
+  const uint64_t base = P[first], last = r.hi - 1u;
+  uint64_t e_lo = first, hi = first + n; // P[e_lo] - base <= lo < P[hi] - base (k_lift_check: P[first + n] - base = len_src): the smallest such hi
+  while (hi - e_lo > 1u) {
+    const uint64_t mid = e_lo + (hi - e_lo) / 2u;
+    if (P[mid] - base > r.lo) hi = mid;
+    else e_lo = mid;
+  }
+  uint64_t e_hi = e_lo; // (P[e_lo] - base <= lo <= hi - 1: the entry of base hi - 1 is e_lo or lies behind it)
+  hi = first + n;
+  while (hi - e_hi > 1u) {
+    const uint64_t mid = e_hi + (hi - e_hi) / 2u;
+    if (P[mid] - base > last) hi = mid;
+    else e_hi = mid;
+  }
+  // first <= e_lo <= e_hi < first + n <= n_cigar: cigar[e_lo], cigar[e_hi]; the prefixes at e_lo + 1 and e_hi + 1 <= first + n <= n_cigar
+  const uint64_t v_lo = cigar[e_lo], v_hi = cigar[e_hi];
+  const uint64_t code_lo = v_lo & 15u, code_hi = v_hi & 15u;
+  const uint64_t off_lo = r.lo - (P[e_lo] - base), off_hi = last - (P[e_hi] - base);
+  const uint64_t src_only = r.side ? CIG_I : CIG_D;
+  uint64_t eq = 0, x = 0, src_gap = 0, oth_gap = 0;
+  if (e_lo == e_hi) { // off_hi - off_lo + 1 columns of that entry's kind
+    const uint64_t cols = off_hi - off_lo + 1u;
+    if (code_lo == CIG_EQ) eq = cols;
+    else if (code_lo == CIG_X) x = cols;
+    else src_gap = cols;
+  } else { // the rest of e_lo, the whole entries e_lo + 1 .. e_hi - 1 as prefix differences, the first off_hi + 1 columns of e_hi
+    const uint64_t a = PA[e_hi] - PA[e_lo + 1u], b = PB[e_hi] - PB[e_lo + 1u], mx = PX[e_hi] - PX[e_lo + 1u], md = PD[e_hi] - PD[e_lo + 1u];
+    const uint64_t meq = a - mx - md, mi = b - meq - mx;
+    const uint64_t head = (v_lo >> 4) - off_lo, tail = off_hi + 1u;
+    eq = meq + (code_lo == CIG_EQ ? head : 0) + (code_hi == CIG_EQ ? tail : 0);
+    x = mx + (code_lo == CIG_X ? head : 0) + (code_hi == CIG_X ? tail : 0);
+    src_gap = (r.side ? mi : md) + (code_lo == src_only ? head : 0) + (code_hi == src_only ? tail : 0);
+    oth_gap = r.side ? md : mi; // (e_lo and e_hi consume the source: a column of the other side alone lies in a whole entry between them)
+  }
+  const uint64_t heads = PH[e_hi + 1u] - PH[e_lo + 1u]; // the heads among the entries (e_lo, e_hi]: I in the low half, D in the high
+  const uint32_t i_heads = (uint32_t)heads, d_heads = (uint32_t)(heads >> 32);
+  const uint32_t opens = code_lo == src_only ? 1u : 0u; // (a run cut by the range's start counts once)
+  const bool both_lo = code_lo == CIG_EQ || code_lo == CIG_X, both_hi = code_hi == CIG_EQ || code_hi == CIG_X;
+  stats[g] = { O[e_lo] - O[first] + (both_lo ? off_lo : 0), O[e_hi] - O[first] + (both_hi ? off_hi + 1u : 0), eq, x, src_gap, oth_gap,
+               (r.side ? i_heads : d_heads) + opens, r.side ? d_heads : i_heads, 0 };
+}
+
+int cigar_lift_stats_run(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains, const nts_lift_range* ranges,
+                         uint64_t n_ranges, nts_lift_stats* stats)
+{
+  uint64_t sum_a = 0, sum_b = 0;
+  for (uint64_t c = 0; c < n_chains; ++c) {
+    const nts_cig_chain& ch = chains[c];
+    auto who = [c] { return "nts_cigar_lift_stats: chain " + std::to_string(c); }; // (made only for a chain that is refused)
+    if (c && ch.first < chains[c - 1].first) return fail(ctx, NTS_EINVAL, who() + ": first is not nondecreasing");
+    if (ch.first > n_cigar || ch.n_cig > n_cigar - ch.first) return fail(ctx, NTS_EINVAL, who() + ": first + n_cig lies beyond n_cigar");
+    if (ch.len_a >= LIFT_MAX_BASES || ch.len_b >= LIFT_MAX_BASES) return fail(ctx, NTS_ERANGE, "nts_cigar_lift_stats: 2^63 bases or more");
+    sum_a += ch.len_a;
+    sum_b += ch.len_b;
+    if (sum_a >= LIFT_MAX_BASES || sum_b >= LIFT_MAX_BASES) return fail(ctx, NTS_ERANGE, "nts_cigar_lift_stats: 2^63 bases or more");
+  }
+  const uint64_t lanes = n_cigar + n_chains;
+  NTS_WS(d_cigar, uint64_t*, "lstat_cigar", std::max<uint64_t>(n_cigar, 1) * 8);
+  NTS_WS(d_chains, nts_cig_chain*, "lstat_chains", std::max<uint64_t>(n_chains, 1) * sizeof(nts_cig_chain));
+  NTS_WS(d_pre, uint64_t*, "lstat_prefixes", 5 * (n_cigar + 1) * 8); // PA, PB, PX, PD, PH: n_cigar + 1 entries each
+  NTS_WS(d_status, uint32_t*, "lstat_status", std::max<uint64_t>(std::max(lanes, n_ranges), 1) * 4);
+  NTS_WS(d_ranges, nts_lift_range*, "lstat_ranges", std::max<uint64_t>(n_ranges, 1) * sizeof(nts_lift_range));
+  NTS_WS(d_stats, nts_lift_stats*, "lstat_stats", std::max<uint64_t>(n_ranges, 1) * sizeof(nts_lift_stats));
+  NTS_WS(d_worst, uint32_t*, "lstat_worst", 2 * 4); // the smallest offending chain, the smallest offending range
+  uint64_t* const d_pa = d_pre;
+  uint64_t* const d_pb = d_pre + (n_cigar + 1);
+  uint64_t* const d_px = d_pre + 2 * (n_cigar + 1);
+  uint64_t* const d_pd = d_pre + 3 * (n_cigar + 1);
+  uint64_t* const d_ph = d_pre + 4 * (n_cigar + 1);
+  nts_lift_stats* host_stats = n_ranges ? (nts_lift_stats*)malloc(n_ranges * sizeof(nts_lift_stats)) : nullptr; // (the caller's array is written only on success)
+  if (n_ranges && !host_stats) return fail(ctx, NTS_ENOMEM, "nts_cigar_lift_stats: no host memory for the records");
+  uint32_t worst[2] = { SCRIPT_OK, SCRIPT_OK };
+  hipError_t e_run = hipSuccess;
+  if (n_cigar) e_run = hipMemcpyAsync(d_cigar, cigar, n_cigar * 8, hipMemcpyHostToDevice, ctx->stream);
+  if (e_run == hipSuccess && n_chains) e_run = hipMemcpyAsync(d_chains, chains, n_chains * sizeof(nts_cig_chain), hipMemcpyHostToDevice, ctx->stream);
+  if (e_run == hipSuccess && n_ranges) e_run = hipMemcpyAsync(d_ranges, ranges, n_ranges * sizeof(nts_lift_range), hipMemcpyHostToDevice, ctx->stream);
+  size_t tmp_s = 0, tmp_r = 0;
+  void* d_tmp = nullptr;
+  auto adds = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), LiftStatOf{ d_cigar, n_cigar });
+  auto prefixes = rocprim::make_zip_iterator(rocprim::make_tuple(d_pa, d_pb, d_px, d_pd, d_ph));
+  if (e_run == hipSuccess) {
+    ScopedTimer t(ctx, "lift_stats_scan", true);
+    e_run = rocprim::exclusive_scan(nullptr, tmp_s, adds, prefixes, LiftStatTuple(0, 0, 0, 0, 0), n_cigar + 1, LiftStatAdd(), ctx->stream);
+    if (e_run == hipSuccess) e_run = rocprim::reduce(nullptr, tmp_r, d_status, d_worst, SCRIPT_OK, std::max(lanes, n_ranges), ScriptMin(), ctx->stream);
+    d_tmp = e_run == hipSuccess ? ws_get(ctx, "ivs_tmp", std::max<size_t>(std::max(tmp_s, tmp_r), 16)) : nullptr; // (once, behind both sizes)
+    if (e_run == hipSuccess && !d_tmp) e_run = hipErrorOutOfMemory;
+    if (e_run == hipSuccess) e_run = rocprim::exclusive_scan(d_tmp, tmp_s, adds, prefixes, LiftStatTuple(0, 0, 0, 0, 0), n_cigar + 1, LiftStatAdd(), ctx->stream);
+    if (e_run == hipSuccess && lanes) {
+      NTS_LAUNCH(k_lift_check, IVL_GRID(lanes), (const uint64_t*)d_cigar, n_cigar, (const nts_cig_chain*)d_chains, n_chains, (const uint64_t*)d_pa,
+                 (const uint64_t*)d_pb, d_status);
+      e_run = rocprim::reduce(d_tmp, tmp_r, d_status, d_worst, SCRIPT_OK, lanes, ScriptMin(), ctx->stream);
+    }
+  }
+  if (e_run == hipSuccess && lanes) e_run = hipMemcpyAsync(&worst[0], d_worst, 4, hipMemcpyDeviceToHost, ctx->stream);
+  if (e_run == hipSuccess && n_ranges) { // (no range: nothing more is launched)
+    ScopedTimer t(ctx, "lift_stats_search", true);
+    NTS_LAUNCH(k_cig_lift_stats, IVL_GRID(n_ranges), (const uint64_t*)d_cigar, n_cigar, (const nts_cig_chain*)d_chains, n_chains, (const uint64_t*)d_pa,
+               (const uint64_t*)d_pb, (const uint64_t*)d_px, (const uint64_t*)d_pd, (const uint64_t*)d_ph, (const nts_lift_range*)d_ranges, n_ranges, d_stats,
+               d_status);
+    e_run = rocprim::reduce(d_tmp, tmp_r, d_status, d_worst + 1, SCRIPT_OK, n_ranges, ScriptMin(), ctx->stream);
+  }
+  if (e_run == hipSuccess) e_run = hipGetLastError();
+  if (e_run == hipSuccess && n_ranges) e_run = hipMemcpyAsync(&worst[1], d_worst + 1, 4, hipMemcpyDeviceToHost, ctx->stream);
+  if (e_run == hipSuccess && n_ranges) e_run = hipMemcpyAsync(host_stats, d_stats, n_ranges * sizeof(nts_lift_stats), hipMemcpyDeviceToHost, ctx->stream);
+  const hipError_t e_sync = hipStreamSynchronize(ctx->stream); // (whatever happened: the caller's arrays were sources of asynchronous copies)
+  const bool good = e_run == hipSuccess && e_sync == hipSuccess && worst[0] == SCRIPT_OK && worst[1] == SCRIPT_OK;
+  if (good && n_ranges) memcpy(stats, host_stats, n_ranges * sizeof(nts_lift_stats));
+  free(host_stats);
+  HIP_TRY(ctx, e_run);
+  HIP_TRY(ctx, e_sync);
+  if (worst[0] != SCRIPT_OK)
+    return fail(ctx, NTS_EINVAL, "nts_cigar_lift_stats: the entries of chain " + std::to_string(worst[0]) + " are no CIGAR of its lengths");
+  if (worst[1] != SCRIPT_OK) return fail(ctx, NTS_EINVAL, "nts_cigar_lift_stats: range " + std::to_string(worst[1]) + " is outside its chain");
+  return NTS_OK;
+}

@@ -1026,6 +1026,17 @@ extern "C" int nts_cigar_lift(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_ci
   return cigar_lift_run(ctx, cigar, n_cigar, chains, n_chains, queries, n_queries, hits);
 }
 
+extern "C" int nts_cigar_lift_stats(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains,
+                                    const nts_lift_range* ranges, uint64_t n_ranges, nts_lift_stats* stats)
+{
+  if (!ctx) return NTS_EINVAL;
+  if (n_cigar > 0xFFFFFFFFull || n_chains > 0xFFFFFFFFull || n_ranges > 0xFFFFFFFFull) // (before any array is read)
+    return fail(ctx, NTS_ERANGE, "nts_cigar_lift_stats: 2^32 entries, chains or ranges or more");
+  if ((n_cigar && !cigar) || (n_chains && !chains) || (n_ranges && (!ranges || !stats))) return fail(ctx, NTS_EINVAL, "nts_cigar_lift_stats: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return cigar_lift_stats_run(ctx, cigar, n_cigar, chains, n_chains, ranges, n_ranges, stats);
+}
+
 extern "C" int nts_graph_budget(nts_ctx* ctx, uint64_t bytes)
 {
   if (!ctx) return NTS_EINVAL;

@@ -72,6 +72,10 @@ CIG_INS, CIG_DEL, CIG_EQ, CIG_X = 1, 2, 7, 8
 # nts_lift_query / nts_lift_hit: what Context.cigar_lift takes and returns, one per query
 LIFT_QUERY_DTYPE = np.dtype([("chain", "<u4"), ("side", "<u4"), ("pos", "<u8")])
 LIFT_HIT_DTYPE = np.dtype([("pos", "<u8"), ("entry", "<u8"), ("off", "<u8"), ("code", "<u4"), ("reserved", "<u4")])
+# nts_lift_range / nts_lift_stats: what Context.cigar_lift_stats takes and returns, one per range
+LIFT_RANGE_DTYPE = np.dtype([("chain", "<u4"), ("side", "<u4"), ("lo", "<u8"), ("hi", "<u8")])
+LIFT_STATS_DTYPE = np.dtype([(n, "<u8") for n in ("oth_lo", "oth_hi", "eq", "x", "src_gap", "oth_gap")] +
+                            [("src_gaps", "<u4"), ("oth_gaps", "<u4"), ("reserved", "<u8")])
 
 
 class Context:
@@ -446,6 +450,27 @@ class Context:
         self.check(self.lib.nts_cigar_lift(self.h, cg.ctypes.data if cg.size else None, cg.size, ch.ctypes.data if ch.size else None, ch.size,
                                            qs.ctypes.data if qs.size else None, qs.size, hits.ctypes.data if hits.size else None), "nts_cigar_lift")
         return hits
+
+    def cigar_lift_stats(self, cigar, chains, ranges):
+        """the alignment counts of ranges of the chains' CIGARs (nts_cigar_lift_stats).  cigar and chains as for cigar_lift; ranges: a
+        LIFT_RANGE_DTYPE array -- the bases lo .. hi - 1 (lo < hi <= the chain's len_a or len_b) of side 0 (A) or 1 (B) of `chain`.
+        Returns a LIFT_STATS_DTYPE array, one record per range, over the chain's columns from the column of base lo to the column of
+        base hi - 1: eq and x, the = and X columns; src_gap, the columns that consume the range's side only; oth_gap, the columns
+        between the two that consume the other side only; src_gaps and oth_gaps, the maximal runs of either kind that hold a counted
+        column; [oth_lo, oth_hi), the lifted span on the other side (eq + x + oth_gap long).  Entries that are no CIGAR of the chains'
+        lengths and ranges outside their chain (an empty one included) are refused.  Exact and deterministic."""
+        cg = np.ascontiguousarray(cigar, dtype=np.uint64)
+        ch = np.ascontiguousarray(chains, dtype=CHAIN_DTYPE)
+        rs = np.ascontiguousarray(ranges, dtype=LIFT_RANGE_DTYPE)
+        if cg.ndim != 1 or ch.ndim != 1 or rs.ndim != 1:
+            raise ValueError("cigar_lift_stats: a list of entries, a list of chain records and a list of ranges")
+        assert LIFT_RANGE_DTYPE.itemsize == ctypes.sizeof(_lib.LiftRange) and LIFT_STATS_DTYPE.itemsize == ctypes.sizeof(_lib.LiftStats)
+        assert CHAIN_DTYPE.itemsize == ctypes.sizeof(_lib.CigChain)
+        stats = np.zeros(rs.size, dtype=LIFT_STATS_DTYPE)
+        self.check(self.lib.nts_cigar_lift_stats(self.h, cg.ctypes.data if cg.size else None, cg.size, ch.ctypes.data if ch.size else None, ch.size,
+                                                 rs.ctypes.data if rs.size else None, rs.size, stats.ctypes.data if stats.size else None),
+                   "nts_cigar_lift_stats")
+        return stats
 
     def timing(self, name):
         ms, n = ctypes.c_double(), u64()

@@ -498,7 +498,7 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         mx_tsvs=None, common_file=None, m=90, n=0, initial_only=False, write_fai=True, engine="device", refine_repeat_file=None, screen_repeat_file=None,
         graph_budget=None, assess=None, gaps=False, gap_links=None, gap_block_links=False, gap_copies=None, gap_copy_sites=None,
         gap_periods=None, gap_families=None, block_identity=None, block_variants=None, block_wide_variants=None, block_ends=None,
-        block_end_variants=False, block_paf=None, block_lift=None):
+        block_end_variants=False, block_paf=None, block_lift=None, block_lift_identity=None, block_windows=None):
     """FASTA paths -> engine (outputs in .outputs and in the CWD).  Mirrors oracle.synteny_oracle.run_pipeline's
     signature so the parity tests read alike.  Under torch.distributed (WORLD_SIZE > 1, process group already
     initialised by the caller) genomes are sharded over the ranks.
@@ -545,7 +545,14 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
     max_len, max_edits, ends): behind that file, <prefix>.block_lift.tsv (assess.block_lift: the BED intervals of `genome`, a FASTA base
     name, mapped through the block alignments into the other genomes; one rank only; it needs none of the other switches; with
     block_paf, which then takes the same parameters, the pass of the stage block_paf serves both files); with `benchmark` the stage times
-    gain block_lift:lift_scan and block_lift:lift_search."""
+    gain block_lift:lift_scan and block_lift:lift_search.  block_lift_identity = block_lift's eight (it needs block_lift, with the same
+    eight): behind that file, <prefix>.block_lift_identity.tsv (assess.block_lift_identity: the same lines with the alignment counts and
+    the identity of every lifted interval).  block_windows = (W, genome, k, rate, band, max_len, max_edits, ends): behind that,
+    <prefix>.block_windows.tsv, the same table for windows of W bases over every record of `genome` (assess.window_intervals); it needs
+    none of the other switches, and takes the genome and the parameters of the others that are given.  One pass serves every file of
+    block_paf, block_lift and these two: it runs in the first of their stages, the later ones write their tables; with `benchmark` the
+    stage times gain <stage>:lift_stats_scan and <stage>:lift_stats_search for either stage -- one device call per round serves both
+    tables, so with both switches the two stages show the same figures."""
     prefix = prefix or f"ntSynt.k{k}.w{w}"
     if mx_tsvs is not None and len(mx_tsvs) != len(fastas):
         raise ValueError("one minimizer TSV per FASTA file")
@@ -649,6 +656,34 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
             raise ValueError(f"block_lift: genome {block_lift[1]} is not among {[fa.basename(p) for p in fastas]}")
         if block_paf is not None and block_paf != block_lift[2:]:
             raise ValueError("block_paf and block_lift take the same (k, rate, band, max_len, max_edits, ends)")
+    for name, given in (("block_lift_identity", block_lift_identity), ("block_windows", block_windows)):
+        if given is None:
+            continue
+        if world > 1 or (mx_tsvs is not None and initial_only):
+            raise ValueError(f"{name} needs every genome resident on one GPU (one rank, genomes loaded)")
+        from .assess import check_ends_parameters, check_identity_parameters
+        shape = f"{name} = ({'bed_path' if name == 'block_lift_identity' else 'W'}, genome, k, rate, band, max_len, max_edits, ends)"
+        if len(given) != 8 or (given[7] is not None and len(given[7]) != 3):
+            raise ValueError(shape + " with ends = (ends_max_len, ends_max_edits, ends_penalty) or None")
+        given = ((str(given[0]) if name == "block_lift_identity" else int(given[0])), str(given[1])) + tuple(int(x) for x in given[2:7]) + \
+            (tuple(int(x) for x in given[7]) if given[7] is not None else None,)
+        message = check_identity_parameters(*given[2:7]) or (check_ends_parameters(*given[7]) if given[7] is not None else None)
+        if message:
+            raise ValueError(shape + ": " + message)
+        if given[1] not in [fa.basename(p) for p in fastas]:
+            raise ValueError(f"{name}: genome {given[1]} is not among {[fa.basename(p) for p in fastas]}")
+        if block_paf is not None and block_paf != given[2:]:
+            raise ValueError(f"block_paf and {name} take the same (k, rate, band, max_len, max_edits, ends)")
+        if name == "block_lift_identity":
+            if block_lift is None or block_lift != given:
+                raise ValueError("block_lift_identity needs block_lift, with the same (bed_path, genome, k, rate, band, max_len, max_edits, ends)")
+            block_lift_identity = given
+        else:
+            if given[0] < 1:
+                raise ValueError(shape + ": a window has at least one base")
+            if block_lift is not None and block_lift[1:] != given[1:]:
+                raise ValueError("block_lift and block_windows take the same (genome, k, rate, band, max_len, max_edits, ends)")
+            block_windows = given
     if gap_block_links and gap_links is None:
         raise ValueError("gap_block_links needs gap_links = (rate, min_anchors)")
     if gap_block_links and len(fastas) > 32:
@@ -1269,18 +1304,39 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
             backend.ctx.profile(False)
         st.mark("block_ends_done")
     lift_timers = ("lift_scan", "lift_search")
+    counting = block_lift_identity is not None or block_windows is not None
+    stats_timers = ("lift_stats_scan", "lift_stats_search") if counting else ()
+    counted_rows = None                                       # the rows of block_lift_identity and block_windows, once their pass has run
+
+    def counted_pass(with_paf):
+        "the one pass that serves block_paf, block_lift, block_lift_identity and block_windows: (PAF rows, lift rows, [counted rows per table]), None for what is off"
+        from . import assess as assess_
+        by_name = {fa.basename(p): genomes[p] for p in fastas}
+        given = block_windows if block_windows is not None else block_lift_identity
+        source, bed = given[1], assess_.read_bed(block_lift[0]) if block_lift is not None else None
+        sets = ([bed] if block_lift_identity is not None else []) + \
+            ([assess_.window_intervals(assess_.record_sizes(by_name, source), block_windows[0])] if block_windows is not None else [])
+        table_rows = assess_.read_blocks(f"{prefix}.synteny_blocks.tsv")
+        if with_paf:
+            return assess_.block_alignments(backend.ctx, by_name, table_rows, *given[2:7], ends=given[7], lift=(source, bed) if bed is not None else None,
+                                            lift_identity=(source, sets))
+        got = assess_.block_lift_identity(backend.ctx, by_name, table_rows, source, sets, *given[2:7], ends=given[7], lift=bed)
+        return (None,) + (got if bed is not None else (None, got))
     if block_paf is not None:
         st.start("block_paf")
         from . import assess as assess_
         if benchmark:                                         # (device events around the calls of this stage only)
             backend.ctx.profile(True)
             paf_timers = ("cigar_atoms", "cigar_merge")
-            paf_before = {name: backend.ctx.timing(name)[0] for name in paf_timers + lift_timers}
-        paf_rows = assess_.block_alignments(backend.ctx, {fa.basename(p): genomes[p] for p in fastas}, assess_.read_blocks(f"{prefix}.synteny_blocks.tsv"),
-                                            *block_paf[:5], ends=block_paf[5],
-                                            lift=(block_lift[1], assess_.read_bed(block_lift[0])) if block_lift is not None else None)
-        if block_lift is not None:                            # (one pass serves both files)
-            paf_rows, lifted_rows = paf_rows
+            paf_before = {name: backend.ctx.timing(name)[0] for name in paf_timers + lift_timers + stats_timers}
+        if counting:                                          # (one pass serves every file)
+            paf_rows, lifted_rows, counted_rows = counted_pass(True)
+        else:
+            paf_rows = assess_.block_alignments(backend.ctx, {fa.basename(p): genomes[p] for p in fastas}, assess_.read_blocks(f"{prefix}.synteny_blocks.tsv"),
+                                                *block_paf[:5], ends=block_paf[5],
+                                                lift=(block_lift[1], assess_.read_bed(block_lift[0])) if block_lift is not None else None)
+            if block_lift is not None:                        # (one pass serves both files)
+                paf_rows, lifted_rows = paf_rows
         text = assess_.paf_table(paf_rows)
         with open(f"{prefix}.block_alignments.paf", "w", encoding="utf-8") as fh:
             fh.write(text)
@@ -1289,6 +1345,7 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         if benchmark:
             st.rows += [(f"block_paf:{name}", (backend.ctx.timing(name)[0] - paf_before[name]) * 1e-3) for name in paf_timers]
             lift_times = [(f"block_lift:{name}", (backend.ctx.timing(name)[0] - paf_before[name]) * 1e-3) for name in lift_timers]
+            stats_times = [(name, (backend.ctx.timing(name)[0] - paf_before[name]) * 1e-3) for name in stats_timers]
             backend.ctx.profile(False)
         st.mark("block_paf_done")
     if block_lift is not None:
@@ -1297,11 +1354,15 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         if block_paf is None:
             if benchmark:                                     # (device events around the calls of this stage only)
                 backend.ctx.profile(True)
-                lift_before = {name: backend.ctx.timing(name)[0] for name in lift_timers}
-            lifted_rows = assess_.block_lift(backend.ctx, {fa.basename(p): genomes[p] for p in fastas}, assess_.read_blocks(f"{prefix}.synteny_blocks.tsv"),
-                                             block_lift[1], assess_.read_bed(block_lift[0]), *block_lift[2:7], ends=block_lift[7])
+                lift_before = {name: backend.ctx.timing(name)[0] for name in lift_timers + stats_timers}
+            if counting:                                      # (one pass serves every file)
+                _, lifted_rows, counted_rows = counted_pass(False)
+            else:
+                lifted_rows = assess_.block_lift(backend.ctx, {fa.basename(p): genomes[p] for p in fastas}, assess_.read_blocks(f"{prefix}.synteny_blocks.tsv"),
+                                                 block_lift[1], assess_.read_bed(block_lift[0]), *block_lift[2:7], ends=block_lift[7])
             if benchmark:
                 lift_times = [(f"block_lift:{name}", (backend.ctx.timing(name)[0] - lift_before[name]) * 1e-3) for name in lift_timers]
+                stats_times = [(name, (backend.ctx.timing(name)[0] - lift_before[name]) * 1e-3) for name in stats_timers]
                 backend.ctx.profile(False)
         text = assess_.lift_table(lifted_rows, *block_lift[2:7], ends=block_lift[7])
         with open(f"{prefix}.block_lift.tsv", "w", encoding="utf-8") as fh:
@@ -1311,6 +1372,27 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         if benchmark:
             st.rows += lift_times
         st.mark("block_lift_done")
+    for stage, given in (("block_lift_identity", block_lift_identity), ("block_windows", block_windows)):
+        if given is None:
+            continue
+        st.start(stage)
+        from . import assess as assess_
+        if counted_rows is None:                              # (windows alone: neither block_paf nor block_lift has made the pass)
+            if benchmark:                                     # (device events around the calls of this stage only)
+                backend.ctx.profile(True)
+                stats_before = {name: backend.ctx.timing(name)[0] for name in stats_timers}
+            _, _, counted_rows = counted_pass(False)
+            if benchmark:
+                stats_times = [(name, (backend.ctx.timing(name)[0] - stats_before[name]) * 1e-3) for name in stats_timers]
+                backend.ctx.profile(False)
+        text = assess_.lift_identity_table(counted_rows[0 if stage == "block_lift_identity" else -1], *given[2:7], ends=given[7])
+        with open(f"{prefix}.{stage}.tsv", "w", encoding="utf-8") as fh:
+            fh.write(text)
+        eng.outputs[f"{prefix}.{stage}.tsv"] = text
+        st.stop()
+        if benchmark:                                         # (one call per round serves both tables: either stage shows that call's time)
+            st.rows += [(f"{stage}:{name}", seconds) for name, seconds in stats_times]
+        st.mark(f"{stage}_done")
     if gaps:
         st.start("gaps")
         from . import assess as assess_, gaps as gaps_
