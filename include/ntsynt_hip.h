@@ -924,6 +924,38 @@ typedef struct
 int nts_cigar_lift_stats(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains,
                          const nts_lift_range* ranges, uint64_t n_ranges, nts_lift_stats* stats);
 
+/* ---- the cg:Z: and cs:Z: texts of the chains' CIGARs: block alignments with --paf-cs ------------------------------------------
+ * nts_cigar_text: cigar, chains as nts_cigar_build returns them (entries need not be maximal runs), but the chains must TILE the
+ *   entries: first[0] = 0, first[c + 1] = first[c] + n_cig[c], the last chain ends at n_cigar.  spans = n_chains of {pos_a, pos_b,
+ *   rec_a, rec_b, flags}: chain c's len_a target bases are rec_a[pos_a .. pos_a + len_a) of genome a, read forwards; its len_b query
+ *   bases are rec_b[pos_b .. pos_b + len_b) of genome b, or with NTS_CIG_B_BACKWARDS rec_b[pos_b], rec_b[pos_b - 1], ..., each
+ *   complemented (3 - code): the reverse complement of a PAF `-` record.  spans = NULL (then a = b = NULL): only the cg text is made,
+ *   no genome is read, cs and cs_first are ignored.  cg text: per entry the decimal of len and its letter (I, D, =, X).  cs text, short
+ *   form: `=` gives `:` and the decimal of len; X gives `*tq` per column (target base, query base as read); D gives `-` and its
+ *   target bases; I gives `+` and its query bases as read; lower case acgt, a code that is no base gives n.  *cg / *cs (release with
+ *   nts_free; NULL for an empty text): chain c's text is bytes [first[c], first[c + 1]) without a terminator; cg_first / cs_first:
+ *   n_chains + 1 host entries.  NTS_ERANGE before any launch: 2^32 entries or chains or more (before any array is read), len_a or
+ *   len_b that add up to 2^62 or more.  NTS_EINVAL before any launch, the smallest chain named: chains that do not tile the entries,
+ *   unknown flag bits, rec_a / rec_b outside its genome, a span outside its record (pos_a + len_a > rec_len_a; forwards pos_b +
+ *   len_b > rec_len_b; backwards pos_b >= rec_len_b or len_b > pos_b + 1; with len_b = 0 only pos_b <= rec_len_b is asked), spans with
+ *   a genome missing or genomes without spans.  After the scan: NTS_EINVAL "the entries of chain ... are no CIGAR of its lengths"
+ *   (smallest chain; a code outside {1, 2, 7, 8} and a length of 0 included), NTS_ERANGE when either text would hold 2^32 bytes or
+ *   more.  A refused call returns no buffer and writes to no caller array.  One exclusive scan over all entries gives the global
+ *   prefixes of (A bases, B bases, cg bytes, cs bytes), nts_cigar_lift's check kernel, a minimum reduction and one lane per chain
+ *   for the firsts (timer "cigar_text_scan"); one lane per aligned 4-byte word of a text finds the entry of its first byte by an
+ *   upper-bound search over the byte prefixes, composes four bytes and stores one dword (timer "cigar_text_emit").  On the
+ *   context's stream, in its workspace; no atomic, no launch per chain or entry, no floating point: the same input gives the same
+ *   bytes.  docs/design/04_26_block_paf_cs.md; csrc/nts_cigar.inc; ntsynt_amd/assess.py block_alignments(cs=True), `ntSynt --block-paf
+ *   --paf-cs`, `bin/ntsynt_block_stats --paf-out F --paf-cs`. */
+#define NTS_CIG_B_BACKWARDS 1u
+typedef struct
+{
+  uint64_t pos_a, pos_b;
+  uint32_t rec_a, rec_b, flags, pad;
+} nts_cig_span;
+int nts_cigar_text(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains, const nts_genome* a,
+                   const nts_genome* b, const nts_cig_span* spans, uint8_t** cg, uint64_t* cg_first, uint8_t** cs, uint64_t* cs_first);
+
 /* ---- C1-C5: minimizer graph -> collinear chains -----------------------------------------------------
  * replaces ntjoin_utils.read_minimizers' duplicate removal, filter_minimizers and build_graph
  * (call sites bin/ntsynt_synteny.py:607-612, 483, 539) and the path walk of Ntjoin.find_paths

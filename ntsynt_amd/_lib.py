@@ -87,6 +87,11 @@ class CigChain(ctypes.Structure):
     _fields_ = [(n, u64) for n in ("first", "n_cig", "eq", "x", "ins", "del", "len_a", "len_b")]
 
 
+class CigSpan(ctypes.Structure):
+    "nts_cig_span: where one chain lies in a record of the target and of the query genome (nts_cigar_text)"
+    _fields_ = [("pos_a", u64), ("pos_b", u64), ("rec_a", u32), ("rec_b", u32), ("flags", u32), ("pad", u32)]
+
+
 class LiftQuery(ctypes.Structure):
     "nts_lift_query: an offset on one side of a chain (nts_cigar_lift)"
     _fields_ = [("chain", u32), ("side", u32), ("pos", u64)]
@@ -275,6 +280,7 @@ SYMBOLS = [
     ("nts_edit_extend_script_last_plan", ctypes.c_int, [c_vp, c_u64p, c_u64p, c_u64p]),
     ("nts_cigar_build", ctypes.c_int, [c_vp, c_vp, u64, u64, c_vp, c_vp, ctypes.POINTER(c_vp), c_u64p, c_vp]),
     ("nts_cigar_lift", ctypes.c_int, [c_vp, c_vp, u64, c_vp, u64, c_vp, u64, c_vp]),
+    ("nts_cigar_text", ctypes.c_int, [c_vp, c_vp, u64, c_vp, u64, c_vp, c_vp, c_vp, ctypes.POINTER(c_vp), c_vp, ctypes.POINTER(c_vp), c_vp]),
     ("nts_cigar_lift_stats", ctypes.c_int, [c_vp, c_vp, u64, c_vp, u64, c_vp, u64, c_vp]),
     ("nts_genome_valid_bases", ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(Interval), u64, c_vp]),
     ("nts_minhash_pairs", ctypes.c_int, [c_vp, u32, c_vp, c_vp, u64, c_vp, c_vp, u64, c_vp, c_vp]),

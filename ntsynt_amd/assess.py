@@ -23,7 +23,8 @@ Two things, both over `<prefix>.synteny_blocks.tsv`:
   events in both genomes' coordinates; docs/design/04_21_block_end_variants.md.
 * block alignments (`ntSynt --block-paf`, `ntsynt_block_stats --paf-out`): one PAF record with a cg:Z: CIGAR per aligned chain of every
   block and pair -- the scripts of all stretches and flanks stitched and run-length merged on the GPU (nts_cigar_build);
-  docs/design/04_22_block_alignments.md.
+  docs/design/04_22_block_alignments.md.  With `--paf-cs` also the cs:Z: tag, both tag texts written on the GPU (nts_cigar_text);
+  docs/design/04_26_block_paf_cs.md.
 * block lift (`ntSynt --block-lift BED --lift-genome NAME`, `ntsynt_block_stats --lift-bed --lift-genome --lift-out`): the intervals of
   one genome mapped through those alignments into the other genomes -- the coordinate map of the chains' CIGARs on the GPU
   (nts_cigar_lift); docs/design/04_23_block_lift.md.
@@ -758,11 +759,40 @@ def cigar_text(entries):
     return cigar_texts(entries, [0], [len(entries)])[0]
 
 
-def paf_row(ra, rb, rec_len_a, rec_len_b, iv_a, iv_b, flipped, ch, span, record, entries):
+PAF_TAGS_CS = PAF_TAGS + ("cs:Z:",)
+
+
+def alignment_spans(round, chains, flanks=None, results=None):
+    """One nts_cig_span per chain of alignment_pieces, from what paf_row uses: round = the _Round (iv_a, iv_b, flip, lines), chains =
+    alignment_pieces' dict, whose offsets already hold the flanks (flanks / results are not read again).  The target bases start at
+    pos_a = start_a + x0 of a's record; the query bases at pos_b = start_b + y0 for `+`, and for `-` at start_b + L_b - y0 - 1, read
+    downwards and complemented (CIG_B_BACKWARDS): the first base of the reverse complement of paf_row's query interval.  Array
+    operations alone.  Pure."""
+    import numpy as np
+    from .device import CIG_B_BACKWARDS, CIG_SPAN_DTYPE
+    line = np.asarray(chains["line"], dtype=np.int64)
+    spans = np.zeros(line.size, dtype=CIG_SPAN_DTYPE)
+    if line.size == 0:
+        return spans
+    iv = np.array([i for _, _, i in round.lines], dtype=np.int64)[line]
+    iv_a, iv_b = np.asarray(round.iv_a).astype(np.int64)[iv], np.asarray(round.iv_b).astype(np.int64)[iv]
+    flipped = np.asarray(round.flip)[iv] != 0
+    x0, y0 = np.asarray(chains["x0"], dtype=np.int64), np.asarray(chains["y0"], dtype=np.int64)
+    pos_a = iv_a[:, 1] + x0
+    pos_b = np.where(flipped, iv_b[:, 2] - y0 - 1, iv_b[:, 1] + y0)                        # (start_b + L_b = end_b)
+    if np.any(pos_a < 0) or np.any(pos_b < -1):
+        raise ValueError("a chain starts in front of its record")
+    spans["pos_a"], spans["pos_b"] = pos_a.astype(np.uint64), np.maximum(pos_b, 0).astype(np.uint64)
+    spans["rec_a"], spans["rec_b"], spans["flags"] = iv_a[:, 0], iv_b[:, 0], np.where(flipped, CIG_B_BACKWARDS, 0)
+    return spans
+
+
+def paf_row(ra, rb, rec_len_a, rec_len_b, iv_a, iv_b, flipped, ch, span, record, entries, cs=None):
     """one chain's PAF line (no newline).  ra / rb: the two block lines (a is the target, b the query), rec_len_*: the lengths of their
     records, iv_a / iv_b: their clipped (rec, start, end); span = (x0, x1, y0, y1), the chain's oriented offsets, flanks included;
     record: its nts_cig_chain fields (eq, x, ins, del), entries: its CIGAR entries, in a's forward order, or their cg:Z: text when
-    the caller made the texts of many chains at once (cigar_texts).  Coordinates are 0-based and
+    the caller made the texts of many chains at once (cigar_texts); cs: the chain's cs:Z: text, appended behind cg:Z: (PAF_TAGS_CS),
+    or None for the tags of PAF_TAGS.  Coordinates are 0-based and
     half-open on the forward strand of the records: for a `-` pair the query interval is mirrored inside b's interval.  Pure."""
     x0, x1, y0, y1 = (int(v) for v in span)
     start_a, start_b, len_b = int(iv_a[1]), int(iv_b[1]), int(iv_b[2]) - int(iv_b[1])
@@ -771,6 +801,8 @@ def paf_row(ra, rb, rec_len_a, rec_len_b, iv_a, iv_b, flipped, ch, span, record,
     fields = [rb.contig, int(rec_len_b), q_from, q_to, "-" if flipped else "+", ra.contig, int(rec_len_a), start_a + x0, start_a + x1, eq, eq + x + ins + dele,
               255, f"NM:i:{x + ins + dele}", f"bi:i:{ra.block_id}", f"tg:Z:{ra.genome}", f"qg:Z:{rb.genome}", f"ch:i:{int(ch)}",
               "cg:Z:" + (entries if isinstance(entries, str) else cigar_text(entries))]
+    if cs is not None:
+        fields.append("cs:Z:" + cs)
     return "\t".join(str(f) for f in fields)
 
 
@@ -780,17 +812,19 @@ def paf_table(rows):
 
 
 # what one round of the alignment pass produced: the _Round itself, the identity pass's per-interval sums, the flanks and their results (or
-# None), the chains of alignment_pieces (one entry per chain: line, ch, x0, x1, y0, y1) and nts_cigar_build's entries and records
-_AlignmentRound = namedtuple("_AlignmentRound", ["round", "per_iv", "flanks", "results", "chains", "cigar", "records"])
+# None), the chains of alignment_pieces (one entry per chain: line, ch, x0, x1, y0, y1), nts_cigar_build's entries and records, and with
+# cs nts_cigar_text's (cg, cg_first, cs, cs_first)
+_AlignmentRound = namedtuple("_AlignmentRound", ["round", "per_iv", "flanks", "results", "chains", "cigar", "records", "texts"], defaults=(None,))
 
 
-def _alignment_rounds(ctx, genomes_by_name, blocks, k, rate, band, max_len, max_edits, ends, pairs, length, only=None):
+def _alignment_rounds(ctx, genomes_by_name, blocks, k, rate, band, max_len, max_edits, ends, pairs, length, only=None, cs=False):
     """The per-round body of block_alignments and block_lift over _identity_rounds, as a generator of _AlignmentRound: per round
     nts_edit_segments with the per-segment distances, for max_edits > 0 nts_edit_wide and both script calls, else nts_edit_script alone,
     with ends nts_edit_extend and nts_edit_extend_script, then ONE nts_cigar_build for all pairs of the round.  Per pair the NM of its
     chains less the flanks' edits must be the identity pass's `edits`, and the target and query bases less the flanks' must be aligned_a
     and aligned_b: RuntimeError otherwise.  only: a genome's name -- rounds in which it takes no part are passed over before any edit
-    call."""
+    call.  cs: behind nts_cigar_build ONE nts_cigar_text per round over alignment_spans, its four arrays carried as `texts`; without it
+    no call is added."""
     import numpy as np
     for r in _identity_rounds(ctx, genomes_by_name, blocks, k, rate, band, max_len, pairs, length):
         if only is not None and only not in (r.name_a, r.name_b):
@@ -823,25 +857,38 @@ def _alignment_rounds(ctx, genomes_by_name, blocks, k, rate, band, max_len, max_
                 raise RuntimeError(f"block {blocks[la].block_id}: the chains of {blocks[la].genome} and {blocks[lb].genome} hold {nm} edits over {bases_a} and "
                                    f"{bases_b} bases, the identity pass {int(per_iv[i]['edits'])} over {int(per_iv[i]['aligned_a'])} and "
                                    f"{int(per_iv[i]['aligned_b'])} (flanks: {[tuple(int(v) for v in e) for e in extra]})")
-        yield _AlignmentRound(r, per_iv, flanks, results, chains, cigar, records)
+        texts = ctx.cigar_text(cigar, records, alignment_spans(r, chains, flanks, results), r.g_a, r.g_b) if cs else None
+        yield _AlignmentRound(r, per_iv, flanks, results, chains, cigar, records, texts)
 
 
 def _round_paf_rows(blocks, a, found):
     "found[(line a, line b)] = paf_row's lines of the pair's chains, ascending by x, for every pair of one round of the alignment pass"
     import numpy as np
     r, chains, records = a.round, a.chains, a.records
-    texts = cigar_texts(a.cigar, records["first"], records["n_cig"])
+    cs_texts = None
+    if a.texts is None:
+        texts = cigar_texts(a.cigar, records["first"], records["n_cig"])
+    else:                                                     # the device's texts: one decode per text, one slice per chain
+        cg, cg_first, cs, cs_first = a.texts
+        whole, at = cg.tobytes().decode(), cg_first.tolist()
+        texts = [whole[at[c]:at[c + 1]] for c in range(len(at) - 1)]
+        whole, at = cs.tobytes().decode(), cs_first.tolist()
+        cs_texts = [whole[at[c]:at[c + 1]] for c in range(len(at) - 1)]
+        if texts and texts[0] != cigar_texts(a.cigar, records["first"][:1], records["n_cig"][:1])[0]:
+            raise RuntimeError(f"the device's cg text of the round's first chain is {texts[0][:60]!r}, the host's "
+                               f"{cigar_texts(a.cigar, records['first'][:1], records['n_cig'][:1])[0][:60]!r}")
     line = chains["line"]
     by_line = np.argsort(line, kind="stable")                 # per pair its chains: one grouping of all chains by line
     cut = np.searchsorted(line[by_line], np.arange(len(r.lines) + 1))
     for q, (la, lb, i) in enumerate(r.lines):
         rec_len_a, rec_len_b = int(r.g_a.rec_len[int(r.iv_a[i][0])]), int(r.g_b.rec_len[int(r.iv_b[i][0])])
         found[(la, lb)] = [paf_row(blocks[la], blocks[lb], rec_len_a, rec_len_b, r.iv_a[i], r.iv_b[i], bool(r.flip[i]), chains["ch"][c],
-                                   [chains[f][c] for f in ("x0", "x1", "y0", "y1")], records[c], texts[c]) for c in by_line[cut[q]:cut[q + 1]].tolist()]
+                                   [chains[f][c] for f in ("x0", "x1", "y0", "y1")], records[c], texts[c], None if cs_texts is None else cs_texts[c])
+                           for c in by_line[cut[q]:cut[q + 1]].tolist()]
 
 
 def block_alignments(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_RATE, band=IDENTITY_BAND, max_len=IDENTITY_MAX_LEN, max_edits=0, ends=None,
-                     lift=None, lift_identity=None):
+                     lift=None, lift_identity=None, cs=False):
     """One PAF record with a cg:Z: CIGAR per aligned chain of every block and pair of its lines (target = line a, query = line b): the
     anchors, segments and final per-segment results of block_identity for the same first five parameters, the canonical scripts of
     block_variants / block_wide_variants, and with ends = (ends_max_len, ends_max_edits, ends_penalty) the flanks of block_ends attached
@@ -853,7 +900,9 @@ def block_alignments(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_R
     aligned_b: RuntimeError otherwise.  docs/design/04_22_block_alignments.md.  lift = (source, intervals): the same pass also lifts
     read_bed's intervals of the genome `source` (block_lift); returns (those lines, block_lift's rows).  lift_identity = (source,
     [intervals, ...]): the same pass also counts the alignment columns of every set of intervals (block_lift_identity; a set that IS
-    the lift's dict is joined once for both); returns (those lines, block_lift's rows or None, [block_lift_identity's rows per set])."""
+    the lift's dict is joined once for both); returns (those lines, block_lift's rows or None, [block_lift_identity's rows per set]).
+    cs: every line also carries the cs:Z: tag (short form) behind cg:Z:, both texts made by ONE nts_cigar_text per round
+    (docs/design/04_26_block_paf_cs.md); without it no call, launch or byte changes."""
     message = check_identity_parameters(int(k), int(rate), int(band), int(max_len), int(max_edits)) or \
         (check_ends_parameters(*(int(v) for v in ends)) if ends is not None else None)
     if message:
@@ -864,7 +913,7 @@ def block_alignments(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_R
         lifter = _lifter_of(genomes_by_name, blocks, lift, lift_identity)
     else:
         lifter = _Lifter(genomes_by_name, blocks, *lift) if lift is not None else None
-    for a in _alignment_rounds(ctx, genomes_by_name, blocks, k, rate, band, max_len, max_edits, ends, pairs, length):
+    for a in _alignment_rounds(ctx, genomes_by_name, blocks, k, rate, band, max_len, max_edits, ends, pairs, length, cs=bool(cs)):
         _round_paf_rows(blocks, a, found)
         if lifter is not None:
             lifter.add_round(ctx, a, pairs)
@@ -1330,6 +1379,8 @@ def main(argv=None):
     p.add_argument("--paf-out", help="with --fastas: file for the block alignments (one PAF record with a cg:Z: CIGAR per aligned chain of every block and "
                    "pair; GPU); it takes the --identity-* parameters, --identity-max-edits included, and with --ends-out the --ends-* parameters: the "
                    "flanks are attached")
+    p.add_argument("--paf-cs", help="with --paf-out (which it needs): every record also carries the cs:Z: tag (short form) behind cg:Z:; both tag texts "
+                   "are then made on the GPU", action="store_true")
     p.add_argument("--lift-bed", help="with --fastas, --lift-genome and --lift-out: a BED file of intervals of one genome that are mapped through the block "
                    "alignments into the other genomes (GPU); it takes the parameters of --paf-out")
     p.add_argument("--lift-genome", help="the genome the intervals of --lift-bed lie on: a FASTA base name, as in column 2 of the block table")
@@ -1362,6 +1413,8 @@ def main(argv=None):
         message = check_identity_parameters(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits)
         if message:
             p.error(message)
+    if args.paf_cs and not args.paf_out:
+        p.error("--paf-cs adds the cs:Z: tag to the records of --paf-out: it needs that switch")
     if args.lift_identity_out and not args.lift_bed:
         p.error("--lift-identity-out needs the intervals: --lift-bed (and --lift-genome)")
     if (args.lift_windows is not None) != bool(args.lift_windows_out):
@@ -1437,7 +1490,7 @@ def main(argv=None):
             if args.paf_out:
                 paf_rows, lift_rows_, counted = block_alignments(ctx, loaders, read_blocks(args.tsv), *id_args, **a_args,
                                                                  lift=(args.lift_genome, intervals) if args.lift_out else None,
-                                                                 lift_identity=(args.lift_genome, sets))
+                                                                 lift_identity=(args.lift_genome, sets), cs=args.paf_cs)
                 with open(args.paf_out, "w", encoding="utf-8") as fh:
                     fh.write(paf_table(paf_rows))
             else:
@@ -1456,7 +1509,7 @@ def main(argv=None):
             intervals = read_bed(args.lift_bed) if args.lift_out else None
             if args.paf_out:
                 paf_rows = block_alignments(ctx, loaders, read_blocks(args.tsv), *id_args, **a_args,
-                                            lift=(args.lift_genome, intervals) if args.lift_out else None)
+                                            lift=(args.lift_genome, intervals) if args.lift_out else None, cs=args.paf_cs)
                 if args.lift_out:
                     paf_rows, lift_rows_ = paf_rows
                 with open(args.paf_out, "w", encoding="utf-8") as fh:

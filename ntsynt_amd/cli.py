@@ -96,6 +96,8 @@ def build_parser():
                    "chain of every block and pair of its genomes; takes the --identity-* parameters (with --identity-max-edits E the stretches\n"
                    "beyond the band join the chains) and, with --block-ends, the --ends-* parameters (the flanks are attached); works with or\n"
                    "without the other block switches", action="store_true")
+    p.add_argument("--paf-cs", help="with --block-paf (which it needs), every record also carries the cs:Z: tag (short form: :n, *tq, -bases, +bases)\n"
+                   "behind cg:Z:, as paftools.js call and dot-plot viewers read it; both tag texts are then made on the GPU", action="store_true")
     p.add_argument("--block-lift", metavar="BED", help="after the run, write <prefix>.block_lift.tsv: the intervals of this BED file, which lie on the\n"
                    "genome --lift-genome names, mapped through the alignments of --block-paf into the other genomes, one line per interval\n"
                    "and aligned chain it overlaps; takes the parameters of --block-paf; works with or without the other block switches")
@@ -234,6 +236,12 @@ def check_reports(parser, args):
             parser.error("--block-end-variants works from the genomes resident on one GPU: run it on one rank, or assess the finished run with "
                          "ntsynt_block_stats --tsv <prefix>.synteny_blocks.tsv --fai ... --fastas ... --ends-out <prefix>.block_ends.tsv "
                          "--end-variants-out <prefix>.block_end_variants.tsv")
+    if args.paf_cs:
+        if not args.block_paf:
+            parser.error("--paf-cs adds the cs:Z: tag to the records of --block-paf: it needs that switch")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            parser.error("--paf-cs works from the genomes resident on one GPU: run it on one rank, or assess the finished run with "
+                         "ntsynt_block_stats --tsv <prefix>.synteny_blocks.tsv --fai ... --fastas ... --paf-out <prefix>.block_alignments.paf --paf-cs")
     if args.block_paf:
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             parser.error("--block-paf works from the genomes resident on one GPU: run it on one rank, or assess the finished run with "
@@ -392,7 +400,7 @@ def main(argv=None):
            (["block_wide_variants (edit_script_plan, edit_script, edit_wide_script_plan, edit_wide_script)"] if args.block_wide_variants else []) + \
            (["block_ends (edit_extend, edit_extend_script_plan, edit_extend_script)" if args.block_end_variants else "block_ends (edit_extend)"]
             if args.block_ends else []) + \
-           ([f"block_paf (cigar_atoms, cigar_merge; k {args.identity_k}, rate {args.identity_rate}, band {args.identity_band}, max_len {args.identity_max_len}, "
+           ([f"block_paf (cigar_atoms, cigar_merge{', cigar_text_scan, cigar_text_emit' if args.paf_cs else ''}; k {args.identity_k}, rate {args.identity_rate}, band {args.identity_band}, max_len {args.identity_max_len}, "
              f"max_edits {args.identity_max_edits}" + (f", ends_max_len {args.ends_max_len}, ends_max_edits {args.ends_max_edits}, ends_penalty "
                                                        f"{args.ends_penalty}" if args.block_ends else "") + ")"] if args.block_paf else []) + \
            ([f"block_lift (lift_scan, lift_search; {args.block_lift} on {args.lift_genome}; k {args.identity_k}, rate {args.identity_rate}, band "
@@ -470,7 +478,7 @@ def _run(pipeline, fastas, args, device, quiet):
                  indel=args.indel, merge=args.merge, block_size=args.block_size, common=not args.no_common,
                  simplify=not args.no_simplify_graph, device=device, benchmark=args.benchmark,
                  dev=args.dev, interarrivals=args.interarrivals, assess=(args.assess_k, args.assess_s) if args.assess else None,
-                 block_identity=((args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len) + ((args.identity_max_edits,) if args.identity_max_edits else ())) if args.block_identity else None, block_variants=(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len) if args.block_variants else None, block_wide_variants=(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits) if args.block_wide_variants else None, block_ends=(args.ends_max_len, args.ends_max_edits, args.ends_penalty, args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits) if args.block_ends else None, block_end_variants=args.block_end_variants, block_paf=(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits, (args.ends_max_len, args.ends_max_edits, args.ends_penalty) if args.block_ends else None) if args.block_paf else None, block_lift=(args.block_lift, args.lift_genome, args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits, (args.ends_max_len, args.ends_max_edits, args.ends_penalty) if args.block_ends else None) if args.block_lift else None, gaps=args.gaps, gap_links=(args.gap_links_rate, args.gap_links_min) if args.gap_links else None, gap_block_links=args.gap_block_links, gap_copies=args.gap_links_rate if args.gap_copies else None, gap_copy_sites=(args.gap_sites_cap, args.gap_sites_step, args.gap_links_min) if args.gap_copy_sites else None, gap_periods=(args.gap_links_rate, args.gap_links_min) if args.gap_periods else None, gap_families=args.gap_sites_step if args.gap_families else None, repeat=args.repeat, bf_rounding=args.bf_rounding, bf_signature=args.bf_signature or pipeline.BF_SIGNATURE,
+                 block_identity=((args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len) + ((args.identity_max_edits,) if args.identity_max_edits else ())) if args.block_identity else None, block_variants=(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len) if args.block_variants else None, block_wide_variants=(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits) if args.block_wide_variants else None, block_ends=(args.ends_max_len, args.ends_max_edits, args.ends_penalty, args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits) if args.block_ends else None, block_end_variants=args.block_end_variants, block_paf=(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits, (args.ends_max_len, args.ends_max_edits, args.ends_penalty) if args.block_ends else None) if args.block_paf else None, block_paf_cs=args.paf_cs, block_lift=(args.block_lift, args.lift_genome, args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits, (args.ends_max_len, args.ends_max_edits, args.ends_penalty) if args.block_ends else None) if args.block_lift else None, gaps=args.gaps, gap_links=(args.gap_links_rate, args.gap_links_min) if args.gap_links else None, gap_block_links=args.gap_block_links, gap_copies=args.gap_links_rate if args.gap_copies else None, gap_copy_sites=(args.gap_sites_cap, args.gap_sites_step, args.gap_links_min) if args.gap_copy_sites else None, gap_periods=(args.gap_links_rate, args.gap_links_min) if args.gap_periods else None, gap_families=args.gap_sites_step if args.gap_families else None, repeat=args.repeat, bf_rounding=args.bf_rounding, bf_signature=args.bf_signature or pipeline.BF_SIGNATURE,
                  log=print if (args.dev and int(os.environ.get("RANK", "0")) == 0) else quiet)
 
 

@@ -664,3 +664,326 @@ int cigar_lift_stats_run(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, 
   if (worst[1] != SCRIPT_OK) return fail(ctx, NTS_EINVAL, "nts_cigar_lift_stats: range " + std::to_string(worst[1]) + " is outside its chain");
   return NTS_OK;
 }
+
+// ---- the cg:Z: and cs:Z: texts of the chains' CIGARs (nts_cigar_text; ntsynt_amd/assess.py block_alignments with cs) ----
+// docs/design/04_26_block_paf_cs.md.  Input: CIGAR entries and chain records as nts_cigar_build returns them, the chains tiling the entries,
+// and per chain a span that places it in a record of genome a (target, forwards) and of genome b (query, forwards or backwards and
+// complemented).  A TOKEN is what one entry gives a text: cg "<len><letter>"; cs ":<len>" for =, "*tq" per column for X, "-" / "+" and
+// the bases for D / I.  Every token has at least 2 bytes.
+//   1  ONE rocprim::exclusive_scan over n_cigar + 1 elements of what a transform iterator makes of an entry -- (A bases, B bases, cg
+//      bytes, cs bytes) -- into four arrays of n_cigar + 1 GLOBAL prefixes.  k_lift_check, unchanged, checks entries and records against
+//      the A and B prefixes, a minimum reduction names the smallest chain; k_cig_text_firsts reads the byte prefixes at every chain's
+//      first entry (timer "cigar_text_scan").  The chains tile the entries (host check), so a chain's text is one byte range.
+//   2  k_cig_text<kind>: one lane per aligned 4-byte word of the text; an upper-bound binary search over the byte prefix finds the entry
+//      of the word's first byte, the lane walks on over the at most three further entries a word touches, composes four bytes in a
+//      register and stores one dword (timer "cigar_text_emit").  A base byte finds its chain by a search over the chains' first
+//      entries and reads one code at the chain's base address plus the A or B prefix difference.  No lane loops over columns.
+// No atomic, no launch per chain or entry, no floating point, no host loop over entries.
+
+using CigTextTuple = rocprim::tuple<uint64_t, uint64_t, uint64_t, uint64_t>; // A bases, B bases, cg bytes, cs bytes
+constexpr uint64_t CIG_TEXT_MAX_BASES = 1ull << 62; // cs bytes <= 3 X + D + I + 20 n_cigar <= A + B + min(A, B) + 20 n_cigar: inside 64 bits
+constexpr uint32_t CIG_TEXT_CG = 0, CIG_TEXT_CS = 1;
+static_assert(sizeof(nts_cig_span) == 32, "the C ABI's layout");
+
+__device__ const uint64_t CIG_POW10[20] = { 1ull,
+                                            10ull,
+                                            100ull,
+                                            1000ull,
+                                            10000ull,
+                                            100000ull,
+                                            1000000ull,
+                                            10000000ull,
+                                            100000000ull,
+                                            1000000000ull,
+                                            10000000000ull,
+                                            100000000000ull,
+                                            1000000000000ull,
+                                            10000000000000ull,
+                                            100000000000000ull,
+                                            1000000000000000ull,
+                                            10000000000000000ull,
+                                            100000000000000000ull,
+                                            1000000000000000000ull,
+                                            10000000000000000000ull };
+
+// len / 10^j without a division by a runtime value (the compiler expands one through floating-point reciprocals): for a dividend below
+// 2^60 and l = ceil(log2 10^j), M = floor(2^(60 + l) / 10^j) + 1 gives floor(len / 10^j) = (len M) >> (60 + l) exactly (Granlund and
+// Montgomery 1994, theorem 4.2); the table holds M and 60 + l - 64, the shift of the product's upper half, for j = 1 .. 18
+struct CigPow10Inverse
+{
+  uint64_t mul;
+  uint32_t shift;
+};
+__device__ const CigPow10Inverse CIG_POW10_INVERSE[18] = {
+  { 1844674407370955162ull, 0u },  { 1475739525896764130ull, 3u },  { 1180591620717411304ull, 6u },  { 1888946593147858086ull, 10u },
+  { 1511157274518286469ull, 13u }, { 1208925819614629175ull, 16u }, { 1934281311383406680ull, 20u }, { 1547425049106725344ull, 23u },
+  { 1237940039285380275ull, 26u }, { 1980704062856608440ull, 30u }, { 1584563250285286752ull, 33u }, { 1267650600228229402ull, 36u },
+  { 2028240960365167043ull, 40u }, { 1622592768292133634ull, 43u }, { 1298074214633706908ull, 46u }, { 2076918743413931052ull, 50u },
+  { 1661534994731144842ull, 53u }, { 1329227995784915873ull, 56u } };
+
+// the decimal digit of weight 10^j of len < 2^60, j <= 18
+__device__ __forceinline__ uint32_t cig_digit(uint64_t len, uint32_t j)
+{
+  uint64_t q = len;
+  if (j > 0) {
+    const CigPow10Inverse inv = CIG_POW10_INVERSE[(j <= 18u ? j : 18u) - 1u];
+    q = __umul64hi(len, inv.mul) >> inv.shift;
+  }
+  return (uint32_t)(q - (q / 10u) * 10u); // (by the constant 10: a multiplication)
+}
+
+// the decimal digits of v, 1 for 0: t = floor(bits * log10(2)) is the digit count or one below it (bits <= 64: t <= 19)
+__device__ __forceinline__ uint32_t cig_digits(uint64_t v)
+{
+  const uint32_t bits = 64u - (uint32_t)__builtin_clzll(v | 1u);
+  const uint32_t t = (bits * 1233u) >> 12;
+  return t + (v >= CIG_POW10[t] ? 1u : 0u) + (v == 0 ? 1u : 0u);
+}
+
+struct CigTextChain // a chain as the emit kernel reads it: where its bases lie in the code arrays
+{
+  uint64_t first, at_a, at_b, len_a, len_b; // at_*: the index into d_code (PAD included) of the chain's first base of that side
+  uint32_t flags, pad;
+};
+static_assert(sizeof(CigTextChain) == 48, "six 8-byte words");
+
+struct CigTextOf // element e of the scan's input: what entry e consumes and how long its two tokens are; nothing behind the last entry
+{
+  const uint64_t* cigar;
+  uint64_t n_cigar;
+  __device__ CigTextTuple operator()(uint64_t e) const
+  {
+    if (e >= n_cigar) return CigTextTuple(0, 0, 0, 0);
+    const uint64_t v = cigar[e], code = v & 15u, len = v >> 4;
+    const bool both = code == CIG_EQ || code == CIG_X, gap = code == CIG_I || code == CIG_D;
+    const uint64_t d = cig_digits(len);
+    return CigTextTuple(both || code == CIG_D ? len : 0, both || code == CIG_I ? len : 0, both || gap ? d + 1u : 0,
+                        code == CIG_EQ ? d + 1u : code == CIG_X ? 3u * len : gap ? len + 1u : 0); // (len < 2^60: 3 len does not wrap)
+  }
+};
+
+struct CigTextAdd
+{
+  __device__ CigTextTuple operator()(const CigTextTuple& x, const CigTextTuple& y) const
+  {
+    return CigTextTuple(rocprim::get<0>(x) + rocprim::get<0>(y), rocprim::get<1>(x) + rocprim::get<1>(y), rocprim::get<2>(x) + rocprim::get<2>(y),
+                        rocprim::get<3>(x) + rocprim::get<3>(y));
+  }
+};
+
+// lane c <= n_chains: where chain c's texts begin, the texts' lengths for c = n_chains
+__global__ __launch_bounds__(256) void k_cig_text_firsts(const nts_cig_chain* __restrict__ chains, uint64_t n_chains, uint64_t n_cigar,
+                                                         const uint64_t* __restrict__ PG, const uint64_t* __restrict__ PS, uint64_t* __restrict__ cg_first,
+                                                         uint64_t* __restrict__ cs_first)
+{
+  const uint64_t c = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (c > n_chains) return;
+  uint64_t f = c < n_chains ? chains[c].first : n_cigar;
+  if (f > n_cigar) f = n_cigar; // (the host refused this before the launch: a lane still reads nothing outside the prefixes)
+  cg_first[c] = PG[f];
+  cs_first[c] = PS[f];
+}
+
+// the letter of the base idx of one side of a chain: 'n' for a code that is no base, '?' -- never seen in a text -- instead of a load
+// outside the chain or the code array (the chain check and the host's span checks leave none)
+__device__ __forceinline__ uint32_t cig_text_base(const uint8_t* __restrict__ code, uint64_t size, uint64_t at, uint64_t idx, uint64_t len, bool backwards)
+{
+  if (idx >= len || (backwards ? idx > at : idx >= size - at)) return '?';
+  const uint64_t where = backwards ? at - idx : at + idx;
+  if (where < PAD || where >= size - PAD) return '?';
+  uint32_t c = code[where];
+  if (c >= nts::CODE_INVALID) return 'n';
+  if (backwards) c = 3u - c;
+  return (0x74676361u >> (8u * c)) & 255u; // "acgt"
+}
+
+template <uint32_t KIND>
+__global__ __launch_bounds__(256) void k_cig_text(const uint64_t* __restrict__ cigar, uint64_t n_cigar, const CigTextChain* __restrict__ chains,
+                                                  uint64_t n_chains, const uint64_t* __restrict__ PA, const uint64_t* __restrict__ PB,
+                                                  const uint64_t* __restrict__ P, const uint8_t* __restrict__ code_a, uint64_t size_a,
+                                                  const uint8_t* __restrict__ code_b, uint64_t size_b, uint32_t* __restrict__ out, uint64_t n_words)
+{
+  const uint64_t w = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (w >= n_words || n_cigar == 0) return;
+  const uint64_t total = P[n_cigar], o = 4u * w;
+  uint64_t e = 0, hi = n_cigar; // P[e] <= o, and o < P[hi] for a word inside the text: the largest such e
+  while (hi - e > 1u) {
+    const uint64_t mid = e + (hi - e) / 2u;
+    if (P[mid] <= o) e = mid;
+    else hi = mid;
+  }
+  uint64_t p0 = P[e], p1 = P[e + 1u]; // (e < n_cigar)
+  uint64_t v = cigar[e];
+  uint32_t digits = cig_digits(v >> 4);
+  uint64_t chain_of = ~0ull; // the entry whose chain `ch` is
+  CigTextChain ch = {};
+  uint32_t word = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < 4u; ++k) {
+    const uint64_t at = o + k;
+    if (at >= total) break;                  // (the padding of the last word stays 0)
+    while (at >= p1 && e + 1u < n_cigar) { // the next entry: a token has at least 2 bytes, so at most three steps per word
+      ++e;
+      p0 = p1;
+      p1 = P[e + 1u];
+      v = cigar[e];
+      digits = cig_digits(v >> 4);
+    }
+    const uint64_t off = at - p0, len = v >> 4;
+    const uint32_t code = (uint32_t)(v & 15u);
+    uint32_t byte;
+    if (KIND == CIG_TEXT_CG || code == CIG_EQ) {
+      const uint64_t lead = KIND == CIG_TEXT_CG ? 0u : 1u, i = off - lead; // cs: ':' in front of the digits
+      if (off < lead) byte = ':';
+      else if (i < digits) byte = '0' + cig_digit(len, digits - 1u - (uint32_t)i); // (len / 10^(digits - 1 - i)) % 10
+      else byte = code == CIG_I ? 'I' : code == CIG_D ? 'D' : code == CIG_EQ ? '=' : 'X';
+    } else {
+      const bool is_x = code == CIG_X;
+      const uint64_t column = is_x ? off / 3u : off - 1u;
+      const uint32_t part = is_x ? (uint32_t)(off % 3u) : (off == 0 ? 0u : code == CIG_D ? 1u : 2u); // 0: the sign, 1: a target base, 2: a query base
+      if (part == 0) {
+        byte = is_x ? '*' : code == CIG_D ? '-' : '+';
+      } else {
+        if (chain_of != e) { // the last chain with first <= e (chains[0].first = 0; empty chains in front of it share its first)
+          uint64_t c = 0, c_hi = n_chains;
+          while (c_hi - c > 1u) {
+            const uint64_t mid = c + (c_hi - c) / 2u;
+            if (chains[mid].first <= e) c = mid;
+            else c_hi = mid;
+          }
+          ch = chains[c];
+          chain_of = e;
+        }
+        const uint64_t f = ch.first <= e ? ch.first : e;
+        byte = part == 1u ? cig_text_base(code_a, size_a, ch.at_a, PA[e] - PA[f] + column, ch.len_a, false)
+                          : cig_text_base(code_b, size_b, ch.at_b, PB[e] - PB[f] + column, ch.len_b, (ch.flags & NTS_CIG_B_BACKWARDS) != 0);
+      }
+    }
+    word |= byte << (8u * k);
+  }
+  out[w] = word;
+}
+
+int cigar_text_run(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains, const nts_genome* a,
+                   const nts_genome* b, const nts_cig_span* spans, uint8_t** cg, uint64_t* cg_first, uint8_t** cs, uint64_t* cs_first)
+{
+  const bool with_cs = spans != nullptr;
+  std::vector<CigTextChain> placed(with_cs ? n_chains : 0);
+  uint64_t next = 0, sum_a = 0, sum_b = 0;
+  for (uint64_t c = 0; c < n_chains; ++c) {
+    const nts_cig_chain& ch = chains[c];
+    auto who = [c] { return "nts_cigar_text: chain " + std::to_string(c); }; // (made only for a chain that is refused)
+    if (ch.first != next || ch.n_cig > n_cigar - next) return fail(ctx, NTS_EINVAL, who() + ": the chains do not tile the entries");
+    next += ch.n_cig;
+    if (ch.len_a >= CIG_TEXT_MAX_BASES || ch.len_b >= CIG_TEXT_MAX_BASES) return fail(ctx, NTS_ERANGE, "nts_cigar_text: 2^62 bases or more");
+    sum_a += ch.len_a;
+    sum_b += ch.len_b;
+    if (sum_a >= CIG_TEXT_MAX_BASES || sum_b >= CIG_TEXT_MAX_BASES) return fail(ctx, NTS_ERANGE, "nts_cigar_text: 2^62 bases or more");
+    if (!with_cs) continue;
+    const nts_cig_span& sp = spans[c];
+    if (sp.flags & ~NTS_CIG_B_BACKWARDS) return fail(ctx, NTS_EINVAL, who() + " has unknown flag bits");
+    if (sp.rec_a >= a->n_rec || sp.rec_b >= b->n_rec) return fail(ctx, NTS_EINVAL, who() + " names a record outside its genome");
+    const uint64_t rl_a = a->rec_len[sp.rec_a], rl_b = b->rec_len[sp.rec_b];
+    const bool backwards = (sp.flags & NTS_CIG_B_BACKWARDS) != 0;
+    bool inside = sp.pos_a <= rl_a && ch.len_a <= rl_a - sp.pos_a;
+    if (ch.len_b == 0) inside = inside && sp.pos_b <= rl_b;
+    else if (backwards) inside = inside && sp.pos_b < rl_b && ch.len_b <= sp.pos_b + 1u;
+    else inside = inside && sp.pos_b <= rl_b && ch.len_b <= rl_b - sp.pos_b;
+    if (!inside) return fail(ctx, NTS_EINVAL, who() + ": its span lies outside its record");
+    placed[c] = { ch.first, PAD + a->rec_off[sp.rec_a] + sp.pos_a, PAD + b->rec_off[sp.rec_b] + sp.pos_b, ch.len_a, ch.len_b, sp.flags, 0u };
+  }
+  if (next != n_cigar)
+    return fail(ctx, NTS_EINVAL, n_chains ? "nts_cigar_text: chain " + std::to_string(n_chains - 1) + ": the chains do not tile the entries (the last one ends in front of n_cigar)"
+                                          : std::string("nts_cigar_text: entries and no chain: the chains do not tile the entries"));
+  if (n_cigar == 0) { // (nothing is launched: every text is empty)
+    *cg = nullptr;
+    memset(cg_first, 0, (n_chains + 1) * 8);
+    if (with_cs) {
+      *cs = nullptr;
+      memset(cs_first, 0, (n_chains + 1) * 8);
+    }
+    return NTS_OK;
+  }
+  const uint64_t lanes = n_cigar + n_chains;
+  NTS_WS(d_cigar, uint64_t*, "cigt_cigar", n_cigar * 8);
+  NTS_WS(d_chains, nts_cig_chain*, "cigt_chains", n_chains * sizeof(nts_cig_chain));
+  NTS_WS(d_placed, CigTextChain*, "cigt_placed", n_chains * sizeof(CigTextChain));
+  NTS_WS(d_pre, uint64_t*, "cigt_prefixes", 4 * (n_cigar + 1) * 8); // PA, PB, PG (cg bytes), PS (cs bytes): n_cigar + 1 entries each
+  NTS_WS(d_status, uint32_t*, "cigt_status", lanes * 4);
+  NTS_WS(d_first, uint64_t*, "cigt_first", 2 * (n_chains + 1) * 8);
+  NTS_WS(d_worst, uint32_t*, "cigt_worst", 4);
+  uint64_t* const d_pa = d_pre;
+  uint64_t* const d_pb = d_pre + (n_cigar + 1);
+  uint64_t* const d_pg = d_pre + 2 * (n_cigar + 1);
+  uint64_t* const d_ps = d_pre + 3 * (n_cigar + 1);
+  std::vector<uint64_t> host_first(2 * (n_chains + 1)); // (the caller's arrays are written only when the call succeeds)
+  uint32_t worst = SCRIPT_OK;
+  hipError_t e_run = hipMemcpyAsync(d_cigar, cigar, n_cigar * 8, hipMemcpyHostToDevice, ctx->stream);
+  if (e_run == hipSuccess) e_run = hipMemcpyAsync(d_chains, chains, n_chains * sizeof(nts_cig_chain), hipMemcpyHostToDevice, ctx->stream);
+  if (e_run == hipSuccess && with_cs) e_run = hipMemcpyAsync(d_placed, placed.data(), n_chains * sizeof(CigTextChain), hipMemcpyHostToDevice, ctx->stream);
+  auto adds = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), CigTextOf{ d_cigar, n_cigar });
+  auto prefixes = rocprim::make_zip_iterator(rocprim::make_tuple(d_pa, d_pb, d_pg, d_ps));
+  if (e_run == hipSuccess) {
+    ScopedTimer t(ctx, "cigar_text_scan", true);
+    size_t tmp_s = 0, tmp_r = 0;
+    e_run = rocprim::exclusive_scan(nullptr, tmp_s, adds, prefixes, CigTextTuple(0, 0, 0, 0), n_cigar + 1, CigTextAdd(), ctx->stream);
+    if (e_run == hipSuccess) e_run = rocprim::reduce(nullptr, tmp_r, d_status, d_worst, SCRIPT_OK, lanes, ScriptMin(), ctx->stream);
+    void* d_tmp = e_run == hipSuccess ? ws_get(ctx, "ivs_tmp", std::max<size_t>(std::max(tmp_s, tmp_r), 16)) : nullptr; // (once, behind both sizes)
+    if (e_run == hipSuccess && !d_tmp) e_run = hipErrorOutOfMemory;
+    if (e_run == hipSuccess) e_run = rocprim::exclusive_scan(d_tmp, tmp_s, adds, prefixes, CigTextTuple(0, 0, 0, 0), n_cigar + 1, CigTextAdd(), ctx->stream);
+    if (e_run == hipSuccess) {
+      NTS_LAUNCH(k_lift_check, IVL_GRID(lanes), (const uint64_t*)d_cigar, n_cigar, (const nts_cig_chain*)d_chains, n_chains, (const uint64_t*)d_pa,
+                 (const uint64_t*)d_pb, d_status);
+      e_run = rocprim::reduce(d_tmp, tmp_r, d_status, d_worst, SCRIPT_OK, lanes, ScriptMin(), ctx->stream);
+    }
+    if (e_run == hipSuccess)
+      NTS_LAUNCH(k_cig_text_firsts, IVL_GRID(n_chains + 1), (const nts_cig_chain*)d_chains, n_chains, n_cigar, (const uint64_t*)d_pg, (const uint64_t*)d_ps,
+                 d_first, d_first + (n_chains + 1));
+  }
+  if (e_run == hipSuccess) e_run = hipGetLastError();
+  if (e_run == hipSuccess) e_run = hipMemcpyAsync(&worst, d_worst, 4, hipMemcpyDeviceToHost, ctx->stream);
+  if (e_run == hipSuccess) e_run = hipMemcpyAsync(host_first.data(), d_first, 2 * (n_chains + 1) * 8, hipMemcpyDeviceToHost, ctx->stream);
+  hipError_t e_sync = hipStreamSynchronize(ctx->stream); // (whatever happened: the caller's arrays were sources of asynchronous copies)
+  HIP_TRY(ctx, e_run);
+  HIP_TRY(ctx, e_sync);
+  if (worst != SCRIPT_OK) return fail(ctx, NTS_EINVAL, "nts_cigar_text: the entries of chain " + std::to_string(worst) + " are no CIGAR of its lengths");
+  const uint64_t bytes_cg = host_first[n_chains], bytes_cs = with_cs ? host_first[2 * n_chains + 1] : 0;
+  if (bytes_cg > 0xFFFFFFFFull || bytes_cs > 0xFFFFFFFFull) return fail(ctx, NTS_ERANGE, "nts_cigar_text: a text of 2^32 bytes or more");
+  const uint64_t words_cg = (bytes_cg + 3) / 4, words_cs = (bytes_cs + 3) / 4; // (the device buffers are padded to whole words)
+  NTS_WS(d_cg, uint32_t*, "cigt_cg", std::max<uint64_t>(words_cg, 1) * 4);
+  NTS_WS(d_cs, uint32_t*, "cigt_cs", std::max<uint64_t>(words_cs, 1) * 4);
+  uint8_t* host_cg = (uint8_t*)malloc(std::max<uint64_t>(bytes_cg, 1));
+  uint8_t* host_cs = with_cs ? (uint8_t*)malloc(std::max<uint64_t>(bytes_cs, 1)) : nullptr;
+  if (!host_cg || (with_cs && !host_cs)) {
+    free(host_cg);
+    free(host_cs);
+    return fail(ctx, NTS_ENOMEM, "nts_cigar_text: no host memory for the texts");
+  }
+  {
+    ScopedTimer t(ctx, "cigar_text_emit", true);
+    NTS_LAUNCH(k_cig_text<CIG_TEXT_CG>, IVL_GRID(words_cg), (const uint64_t*)d_cigar, n_cigar, (const CigTextChain*)nullptr, (uint64_t)0,
+               (const uint64_t*)d_pa, (const uint64_t*)d_pb, (const uint64_t*)d_pg, (const uint8_t*)nullptr, (uint64_t)0, (const uint8_t*)nullptr, (uint64_t)0,
+               d_cg, words_cg);
+    if (with_cs)
+      NTS_LAUNCH(k_cig_text<CIG_TEXT_CS>, IVL_GRID(words_cs), (const uint64_t*)d_cigar, n_cigar, (const CigTextChain*)d_placed, n_chains,
+                 (const uint64_t*)d_pa, (const uint64_t*)d_pb, (const uint64_t*)d_ps, (const uint8_t*)a->d_code, a->n + 2 * PAD, (const uint8_t*)b->d_code,
+                 b->n + 2 * PAD, d_cs, words_cs);
+  }
+  e_run = hipGetLastError();
+  if (e_run == hipSuccess) e_run = hipMemcpyAsync(host_cg, d_cg, bytes_cg, hipMemcpyDeviceToHost, ctx->stream);
+  if (e_run == hipSuccess && with_cs && bytes_cs) e_run = hipMemcpyAsync(host_cs, d_cs, bytes_cs, hipMemcpyDeviceToHost, ctx->stream);
+  e_sync = hipStreamSynchronize(ctx->stream);
+  if (e_run != hipSuccess || e_sync != hipSuccess) {
+    free(host_cg);
+    free(host_cs);
+  }
+  HIP_TRY(ctx, e_run);
+  HIP_TRY(ctx, e_sync);
+  *cg = host_cg;
+  memcpy(cg_first, host_first.data(), (n_chains + 1) * 8);
+  if (with_cs) {
+    *cs = host_cs;
+    memcpy(cs_first, host_first.data() + (n_chains + 1), (n_chains + 1) * 8);
+  }
+  return NTS_OK;
+}

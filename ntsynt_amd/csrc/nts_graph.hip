@@ -1015,7 +1015,19 @@ extern "C" int nts_cigar_build(nts_ctx* ctx, const nts_cig_piece* pieces, uint64
   return cigar_build_run(ctx, pieces, n_pieces, n_chains, ops, first, cigar, n_cigar, chains);
 }
 
-extern "C" int nts_cigar_lift(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains,
+extern "C" int nts_cigar_text(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains, const nts_genome* a,
+                              const nts_genome* b, const nts_cig_span* spans, uint8_t** cg, uint64_t* cg_first, uint8_t** cs, uint64_t* cs_first)
+{
+  if (!ctx) return NTS_EINVAL;
+  if (n_cigar > 0xFFFFFFFFull || n_chains > 0xFFFFFFFFull) // (before any array is read)
+    return fail(ctx, NTS_ERANGE, "nts_cigar_text: 2^32 entries or chains or more");
+  if ((n_cigar && !cigar) || (n_chains && !chains) || !cg || !cg_first || (spans && (!cs || !cs_first))) return fail(ctx, NTS_EINVAL, "nts_cigar_text: bad arguments");
+  if (spans ? !a || !b : a || b) return fail(ctx, NTS_EINVAL, "nts_cigar_text: spans go with both genomes, no spans with none");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return cigar_text_run(ctx, cigar, n_cigar, chains, n_chains, a, b, spans, cg, cg_first, cs, cs_first);
+}
+
+extern "C" int nts_cigar_lift(nts_ctx* ctx,const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains,
                               const nts_lift_query* queries, uint64_t n_queries, nts_lift_hit* hits)
 {
   if (!ctx) return NTS_EINVAL;

@@ -69,6 +69,10 @@ PIECE_DTYPE = np.dtype([(n, "<u4") for n in ("chain", "n", "m", "flags")])
 CHAIN_DTYPE = np.dtype([(n, "<u8") for n in ("first", "n_cig", "eq", "x", "ins", "del", "len_a", "len_b")])
 CIG_REVERSED = 1
 CIG_INS, CIG_DEL, CIG_EQ, CIG_X = 1, 2, 7, 8
+# nts_cig_span: where Context.cigar_text finds a chain's bases -- record and start in the target (a, forwards) and the query (b; with
+# CIG_B_BACKWARDS pos_b is its first base as read: backwards and complemented)
+CIG_SPAN_DTYPE = np.dtype([("pos_a", "<u8"), ("pos_b", "<u8"), ("rec_a", "<u4"), ("rec_b", "<u4"), ("flags", "<u4"), ("pad", "<u4")])
+CIG_B_BACKWARDS = 1
 # nts_lift_query / nts_lift_hit: what Context.cigar_lift takes and returns, one per query
 LIFT_QUERY_DTYPE = np.dtype([("chain", "<u4"), ("side", "<u4"), ("pos", "<u8")])
 LIFT_HIT_DTYPE = np.dtype([("pos", "<u8"), ("entry", "<u8"), ("off", "<u8"), ("code", "<u4"), ("reserved", "<u4")])
@@ -430,6 +434,43 @@ class Context:
                                             ft.ctypes.data, ctypes.byref(p), ctypes.byref(m), chains.ctypes.data if chains.size else None),
                    "nts_cigar_build")
         return self._take(p, m.value, np.dtype("<u8")), chains
+
+    def cigar_text(self, cigar, chains, spans=None, genome_a=None, genome_b=None):
+        """the cg:Z: and cs:Z: texts of the chains' CIGARs (nts_cigar_text).  cigar [E] uint64 and chains, a CHAIN_DTYPE array: what
+        cigar_build returns (entries need not be maximal runs; the chains tile the entries).  Without spans: returns (cg, cg_first) --
+        cg a uint8 array, chain c's text is cg[cg_first[c]:cg_first[c + 1]], cg_first [len(chains) + 1] uint64 -- and no genome is
+        read.  spans: a CIG_SPAN_DTYPE array, one per chain -- its len_a target bases are record rec_a of genome_a from pos_a on,
+        forwards; its len_b query bases record rec_b of genome_b from pos_b on, or with CIG_B_BACKWARDS from pos_b downwards and
+        complemented; returns (cg, cg_first, cs, cs_first), cs the short form (:n, *tq, -bases, +bases; lower case, n for what is no
+        base).  Chains that do not tile the entries, entries that are no CIGAR of the chains' lengths, spans outside their records and
+        texts of 2^32 bytes or more are refused.  Exact and deterministic."""
+        cg = np.ascontiguousarray(cigar, dtype=np.uint64)
+        ch = np.ascontiguousarray(chains, dtype=CHAIN_DTYPE)
+        if cg.ndim != 1 or ch.ndim != 1:
+            raise ValueError("cigar_text: a list of entries and a list of chain records")
+        if spans is None and (genome_a is not None or genome_b is not None):
+            raise ValueError("cigar_text: genomes go with spans")
+        assert CHAIN_DTYPE.itemsize == ctypes.sizeof(_lib.CigChain) and CIG_SPAN_DTYPE.itemsize == ctypes.sizeof(_lib.CigSpan)
+        sp = None
+        if spans is not None:
+            sp = np.ascontiguousarray(spans, dtype=CIG_SPAN_DTYPE)
+            if sp.shape != (ch.size,):
+                raise ValueError("cigar_text: one span per chain")
+            if genome_a is None or genome_b is None:
+                raise ValueError("cigar_text: spans go with both genomes")
+            if sp.size == 0:
+                sp = np.zeros(1, dtype=CIG_SPAN_DTYPE)       # (a pointer that is not NULL: spans were given)
+        firsts = np.zeros((2, ch.size + 1), dtype=np.uint64)
+        p_cg, p_cs = c_vp(), c_vp()
+        self.check(self.lib.nts_cigar_text(self.h, cg.ctypes.data if cg.size else None, cg.size, ch.ctypes.data if ch.size else None, ch.size,
+                                           genome_a.h if sp is not None else None, genome_b.h if sp is not None else None,
+                                           sp.ctypes.data if sp is not None else None, ctypes.byref(p_cg), firsts[0].ctypes.data,
+                                           ctypes.byref(p_cs) if sp is not None else None, firsts[1].ctypes.data if sp is not None else None),
+                   "nts_cigar_text")
+        text = self._take(p_cg, int(firsts[0, -1]), np.dtype("u1"))
+        if sp is None:
+            return text, firsts[0].copy()
+        return text, firsts[0].copy(), self._take(p_cs, int(firsts[1, -1]), np.dtype("u1")), firsts[1].copy()
 
     def cigar_lift(self, cigar, chains, queries):
         """the coordinate map of the chains' CIGARs (nts_cigar_lift).  cigar [E] uint64 and chains, a CHAIN_DTYPE array: what cigar_build

@@ -498,7 +498,8 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         mx_tsvs=None, common_file=None, m=90, n=0, initial_only=False, write_fai=True, engine="device", refine_repeat_file=None, screen_repeat_file=None,
         graph_budget=None, assess=None, gaps=False, gap_links=None, gap_block_links=False, gap_copies=None, gap_copy_sites=None,
         gap_periods=None, gap_families=None, block_identity=None, block_variants=None, block_wide_variants=None, block_ends=None,
-        block_end_variants=False, block_paf=None, block_lift=None, block_lift_identity=None, block_windows=None):
+        block_end_variants=False, block_paf=None, block_lift=None, block_lift_identity=None, block_windows=None,
+        block_paf_cs=False):
     """FASTA paths -> engine (outputs in .outputs and in the CWD).  Mirrors oracle.synteny_oracle.run_pipeline's
     signature so the parity tests read alike.  Under torch.distributed (WORLD_SIZE > 1, process group already
     initialised by the caller) genomes are sharded over the ranks.
@@ -541,7 +542,9 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
     block_ends:edit_extend_script.  block_paf = (k, rate, band, max_len, max_edits, ends) with ends = (ends_max_len, ends_max_edits,
     ends_penalty) or None: behind the other block files, <prefix>.block_alignments.paf (assess.block_alignments: one PAF record with a
     cg:Z: CIGAR per aligned chain of every block and pair, from a pass of its own; one rank only; it needs none of the other switches);
-    with `benchmark` the stage times gain block_paf:cigar_atoms and block_paf:cigar_merge.  block_lift = (bed_path, genome, k, rate, band,
+    with `benchmark` the stage times gain block_paf:cigar_atoms and block_paf:cigar_merge.  block_paf_cs: needs block_paf; every record
+    also carries the cs:Z: tag, both tag texts made on the device (nts_cigar_text, one call per round); with `benchmark` the stage
+    times gain block_paf:cigar_text_scan and block_paf:cigar_text_emit.  block_lift =(bed_path, genome, k, rate, band,
     max_len, max_edits, ends): behind that file, <prefix>.block_lift.tsv (assess.block_lift: the BED intervals of `genome`, a FASTA base
     name, mapped through the block alignments into the other genomes; one rank only; it needs none of the other switches; with
     block_paf, which then takes the same parameters, the pass of the stage block_paf serves both files); with `benchmark` the stage times
@@ -630,6 +633,8 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
     if block_end_variants and block_ends is None:
         from .assess import END_VARIANTS_NEED_ENDS
         raise ValueError("block_end_variants: " + END_VARIANTS_NEED_ENDS)
+    if block_paf_cs and block_paf is None:
+        raise ValueError("block_paf_cs adds the cs:Z: tag to the records of block_paf and needs block_paf")
     if block_paf is not None:
         if world > 1 or (mx_tsvs is not None and initial_only):
             raise ValueError("block_paf needs every genome resident on one GPU (one rank, genomes loaded)")
@@ -1319,7 +1324,7 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         table_rows = assess_.read_blocks(f"{prefix}.synteny_blocks.tsv")
         if with_paf:
             return assess_.block_alignments(backend.ctx, by_name, table_rows, *given[2:7], ends=given[7], lift=(source, bed) if bed is not None else None,
-                                            lift_identity=(source, sets))
+                                            lift_identity=(source, sets), cs=bool(block_paf_cs))
         got = assess_.block_lift_identity(backend.ctx, by_name, table_rows, source, sets, *given[2:7], ends=given[7], lift=bed)
         return (None,) + (got if bed is not None else (None, got))
     if block_paf is not None:
@@ -1327,14 +1332,14 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         from . import assess as assess_
         if benchmark:                                         # (device events around the calls of this stage only)
             backend.ctx.profile(True)
-            paf_timers = ("cigar_atoms", "cigar_merge")
+            paf_timers = ("cigar_atoms", "cigar_merge") + (("cigar_text_scan", "cigar_text_emit") if block_paf_cs else ())
             paf_before = {name: backend.ctx.timing(name)[0] for name in paf_timers + lift_timers + stats_timers}
         if counting:                                          # (one pass serves every file)
             paf_rows, lifted_rows, counted_rows = counted_pass(True)
         else:
             paf_rows = assess_.block_alignments(backend.ctx, {fa.basename(p): genomes[p] for p in fastas}, assess_.read_blocks(f"{prefix}.synteny_blocks.tsv"),
                                                 *block_paf[:5], ends=block_paf[5],
-                                                lift=(block_lift[1], assess_.read_bed(block_lift[0])) if block_lift is not None else None)
+                                                lift=(block_lift[1], assess_.read_bed(block_lift[0])) if block_lift is not None else None, cs=bool(block_paf_cs))
             if block_lift is not None:                        # (one pass serves both files)
                 paf_rows, lifted_rows = paf_rows
         text = assess_.paf_table(paf_rows)
