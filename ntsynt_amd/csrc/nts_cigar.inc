@@ -16,6 +16,20 @@
 constexpr uint64_t CIG_I = 1, CIG_D = 2, CIG_EQ = 7, CIG_X = 8; // BAM's codes
 constexpr uint64_t CIG_MAX_COLUMNS = 1ull << 60;               // len << 4 stays inside 64 bits
 
+// the last i < n whose key(i) <= e over nondecreasing keys, 0 where there is none (n >= 1): the piece of an op, the chain of an
+// entry, the entry of a text byte
+template <class I, class Key>
+__device__ __forceinline__ I cig_last_at_or_before(I n, uint64_t e, Key key)
+{
+  I lo = 0, hi = n;
+  while (hi - lo > 1u) {
+    const I mid = lo + (hi - lo) / 2u;
+    if (key(mid) <= e) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
 struct CigAtom
 {
   uint64_t run; // len << 4 | code
@@ -92,13 +106,7 @@ __global__ __launch_bounds__(256) void k_cig_atoms(const nts_cig_piece* __restri
   } else {
     t = ops[g].seg;
     if (t >= n_pieces || g < first[t] || g >= first[t + 1]) { // seg is not the piece that owns op g: find that piece, the last with first[t] <= g
-      uint32_t lo = 0, hi = n_pieces;                        // (first[0] = 0 <= g < n_ops = first[n_pieces])
-      while (hi - lo > 1u) {
-        const uint32_t mid = lo + (hi - lo) / 2u;
-        if (first[mid] <= g) lo = mid;
-        else hi = mid;
-      }
-      t = lo;
+      t = cig_last_at_or_before(n_pieces, g, [first](uint32_t i) { return first[i]; }); // (first[0] = 0 <= g < n_ops = first[n_pieces])
       ok = false;
     }
   }
@@ -307,43 +315,62 @@ int cigar_build_run(nts_ctx* ctx, const nts_cig_piece* pieces, uint64_t n_pieces
   return NTS_OK;
 }
 
-// ---- the coordinate map of the chains' CIGARs (nts_cigar_lift; ntsynt_amd/assess.py block_lift) ----
-// docs/design/04_23_block_lift.md.  Input: CIGAR entries and chain records as nts_cigar_build returns them, and queries {chain, side, pos}:
-// an offset on side A (0) or B (1) of a chain.  The answer is the offset on the other side and the entry the position falls in.
-//   1  rocprim::exclusive_scan over n_cigar + 1 elements of what a transform iterator makes of an entry -- the pair (A bases, B bases)
-//      it consumes, (0, 0) for the element behind the last -- into PA and PB: the GLOBAL prefixes, the last holding the totals; a
-//      chain-local prefix is P[e] - P[first].  k_lift_check: one lane per entry (a code outside {1, 2, 7, 8}, a length of 0, a prefix
-//      that wrapped) and one per chain (P[first + n_cig] - P[first] is not its len_a / len_b); a flagged lane stores its chain's index in
-//      its status word, a minimum reduction names the smallest (timer "lift_scan").
-//   2  k_cig_lift: one lane per query; validates it, finds with an upper-bound binary search over Psrc the entry that holds pos and
-//      stores one 32 B hit; an invalid query stores nothing but its own index in its status word, a second minimum reduction names the
-//      smallest (timer "lift_search").
-// No atomic, no launch per chain or query, no floating point, no host loop over entries or queries.
+// ---- the staged prefix index of a round's CIGARs: what nts_cigar_lift, nts_cigar_lift_stats and nts_cigar_text share ----
+// Each of the three reads CIGAR entries and chain records as nts_cigar_build returns them, and each begins alike: cig_chains_check
+// looks at the records on the host; cig_index_stage copies entries and records to the device (the context's "cigx_*" buffers: one
+// name set, so a run of all three keeps one copy), runs ONE rocprim::exclusive_scan over n_cigar + 1 elements of what the caller's
+// transform functor makes of an entry -- a tuple whose first two members are the (A bases, B bases) it consumes, zeros for the element
+// behind the last -- into NP columns of n_cigar + 1 GLOBAL prefixes, the last row holding the totals (a chain-local prefix is
+// P[e] - P[first]), and then k_lift_check: one lane per entry (a code outside {1, 2, 7, 8}, a length of 0, a prefix that wrapped) and
+// one per chain (P[first + n_cig] - P[first] is not its len_a / len_b); a flagged lane stores its chain's index in its status word, a
+// minimum reduction names the smallest.  All of it runs under the caller's timer name.
 
-using LiftPair = rocprim::tuple<uint64_t, uint64_t>; // (A bases, B bases)
-constexpr uint64_t LIFT_MAX_BASES = 1ull << 63;      // the global scan must not wrap
-static_assert(sizeof(nts_lift_query) == 16 && sizeof(nts_lift_hit) == 32, "the C ABI's layout");
+using CigBases = rocprim::tuple<uint64_t, uint64_t>; // (A bases, B bases)
 
-struct LiftBasesOf // element e of the scan's input: what entry e consumes; nothing behind the last entry
+// what an entry consumes on either side
+__host__ __device__ inline CigBases cig_bases(uint64_t v)
 {
-  const uint64_t* cigar;
-  uint64_t n_cigar;
-  __host__ __device__ LiftPair operator()(uint64_t e) const
+  const uint64_t code = v & 15u, len = v >> 4;
+  const bool both = code == CIG_EQ || code == CIG_X;
+  return CigBases(both || code == CIG_D ? len : 0, both || code == CIG_I ? len : 0);
+}
+
+struct CigTupleAdd // member by member, for a tuple of any arity
+{
+  template <class T, size_t... K>
+  static __host__ __device__ T add(const T& x, const T& y, std::index_sequence<K...>)
   {
-    if (e >= n_cigar) return LiftPair(0, 0);
-    const uint64_t v = cigar[e], code = v & 15u, len = v >> 4;
-    const bool both = code == CIG_EQ || code == CIG_X;
-    return LiftPair(both || code == CIG_D ? len : 0, both || code == CIG_I ? len : 0);
+    return T((rocprim::get<K>(x) + rocprim::get<K>(y))...);
+  }
+  template <class... U>
+  __host__ __device__ rocprim::tuple<U...> operator()(const rocprim::tuple<U...>& x, const rocprim::tuple<U...>& y) const
+  {
+    return add(x, y, std::index_sequence_for<U...>());
   }
 };
 
-struct LiftPairAdd
+// the entry of base `pos` of one side of a chain with entries [lo, hi) over that side's prefix P, base = P[chain's first]: the
+// smallest hi with P[lo] - base <= pos < P[hi] - base narrows to lo + 1 (k_lift_check: P[first + n_cig] - base is the side's length)
+__device__ __forceinline__ uint64_t cig_entry_of(const uint64_t* __restrict__ P, uint64_t base, uint64_t lo, uint64_t hi, uint64_t pos)
 {
-  __host__ __device__ LiftPair operator()(const LiftPair& x, const LiftPair& y) const
-  {
-    return LiftPair(rocprim::get<0>(x) + rocprim::get<0>(y), rocprim::get<1>(x) + rocprim::get<1>(y));
+  while (hi - lo > 1u) {
+    const uint64_t mid = lo + (hi - lo) / 2u;
+    if (P[mid] - base > pos) hi = mid;
+    else lo = mid;
   }
-};
+  return lo;
+}
+
+// the record of a query's or range's {chain, side}: false, and nothing read, for a chain or a side that is none
+__device__ __forceinline__ bool cig_chain_of(const nts_cig_chain* __restrict__ chains, uint64_t n_chains, uint32_t chain, uint32_t side, nts_cig_chain& ch)
+{
+  if (chain >= n_chains || side > 1u) return false;
+  ch = chains[chain];
+  return true;
+}
+
+// a record whose entries reach beyond n_cigar (the host refused it before the launch: a lane still reads nothing outside the prefixes)
+__device__ __forceinline__ bool cig_chain_beyond(const nts_cig_chain& ch, uint64_t n_cigar) { return ch.first > n_cigar || ch.n_cig > n_cigar - ch.first; }
 
 __global__ __launch_bounds__(256) void k_lift_check(const uint64_t* __restrict__ cigar, uint64_t n_cigar, const nts_cig_chain* __restrict__ chains,
                                                     uint64_t n_chains, const uint64_t* __restrict__ PA, const uint64_t* __restrict__ PB,
@@ -355,25 +382,132 @@ __global__ __launch_bounds__(256) void k_lift_check(const uint64_t* __restrict__
   if (g < n_cigar) {
     const uint64_t v = cigar[g], code = v & 15u;
     const bool bad = (code != CIG_I && code != CIG_D && code != CIG_EQ && code != CIG_X) || (v >> 4) == 0 || PA[g + 1] < PA[g] || PB[g + 1] < PB[g];
-    if (bad && n_chains) { // its chain: the last whose first <= g, chain 0 for an entry in front of every chain (on this error path only)
-      uint64_t lo = 0, hi = n_chains;
-      while (hi - lo > 1u) {
-        const uint64_t mid = lo + (hi - lo) / 2u;
-        if (chains[mid].first <= g) lo = mid;
-        else hi = mid;
-      }
-      say = (uint32_t)lo;
-    }
+    // its chain: the last whose first <= g, chain 0 for an entry in front of every chain (on this error path only)
+    if (bad && n_chains) say = (uint32_t)cig_last_at_or_before(n_chains, g, [chains](uint64_t c) { return chains[c].first; });
   } else {
     const uint64_t c = g - n_cigar;
     const nts_cig_chain ch = chains[c];
-    // (the host refused the first test before the launch: a lane still reads nothing outside PA and PB)
-    if (ch.first > n_cigar || ch.n_cig > n_cigar - ch.first || PA[ch.first + ch.n_cig] - PA[ch.first] != ch.len_a ||
+    if (cig_chain_beyond(ch, n_cigar) || PA[ch.first + ch.n_cig] - PA[ch.first] != ch.len_a ||
         PB[ch.first + ch.n_cig] - PB[ch.first] != ch.len_b)
       say = (uint32_t)c;
   }
   status[g] = say;
 }
+
+// The chain records, on the host, for entry point `name`: `first` nondecreasing and first + n_cig inside the entries -- with `tile`,
+// the chains one behind the other over all entries instead -- and fewer than 2^limit_log2 bases a side over all chains: the global
+// scan, and what the caller adds up beside it, must not wrap.  per_chain(c, who) -> a return code: the caller's own checks of chain c,
+// behind these; who() makes "name: chain c" (only for a chain that is refused).
+template <class PerChain>
+int cig_chains_check(nts_ctx* ctx, const char* name, uint32_t limit_log2, bool tile, const nts_cig_chain* chains, uint64_t n_chains, uint64_t n_cigar,
+                     PerChain per_chain)
+{
+  const uint64_t limit = 1ull << limit_log2;
+  auto too_many = [&] { return fail(ctx, NTS_ERANGE, std::string(name) + ": 2^" + std::to_string(limit_log2) + " bases or more"); };
+  uint64_t next = 0, sum_a = 0, sum_b = 0;
+  for (uint64_t c = 0; c < n_chains; ++c) {
+    const nts_cig_chain& ch = chains[c];
+    auto who = [name, c] { return std::string(name) + ": chain " + std::to_string(c); };
+    if (tile) {
+      if (ch.first != next || ch.n_cig > n_cigar - next) return fail(ctx, NTS_EINVAL, who() + ": the chains do not tile the entries");
+      next += ch.n_cig;
+    } else {
+      if (c && ch.first < chains[c - 1].first) return fail(ctx, NTS_EINVAL, who() + ": first is not nondecreasing");
+      if (ch.first > n_cigar || ch.n_cig > n_cigar - ch.first) return fail(ctx, NTS_EINVAL, who() + ": first + n_cig lies beyond n_cigar");
+    }
+    if (ch.len_a >= limit || ch.len_b >= limit) return too_many();
+    sum_a += ch.len_a;
+    sum_b += ch.len_b;
+    if (sum_a >= limit || sum_b >= limit) return too_many();
+    if (const int rc = per_chain(c, who)) return rc;
+  }
+  if (tile && next != n_cigar)
+    return fail(ctx, NTS_EINVAL, n_chains ? std::string(name) + ": chain " + std::to_string(n_chains - 1) + ": the chains do not tile the entries (the last one ends in front of n_cigar)"
+                                          : std::string(name) + ": entries and no chain: the chains do not tile the entries");
+  return NTS_OK;
+}
+
+struct CigIndex // what cig_index_stage leaves in the context's workspace: dead behind the next call of any of the three readers
+{
+  const uint64_t* cigar;       // "cigx_cigar": the entries
+  const nts_cig_chain* chains; // "cigx_chains": the records
+  uint64_t* prefixes;          // "cigx_prefixes": NP columns of `rows` = n_cigar + 1 words; 0: A bases, 1: B bases, then the caller's own
+  uint64_t rows;
+  uint32_t* status;            // "cigx_status": max(n_cigar + n_chains, n_items) words; the caller's lanes write it behind k_lift_check's
+  uint32_t* worst;             // "cigx_worst": [0] the smallest offending chain, [1] for the caller's reduction
+  void* tmp;                   // "ivs_tmp", large enough for a ScriptMin reduction of that many status words: tmp_bytes
+  size_t tmp_bytes;
+  const uint64_t* column(uint32_t k) const { return prefixes + k * rows; }
+};
+
+// the scan of Of's tuples into the columns (the size query with tmp = nullptr)
+template <class Of, size_t... K>
+hipError_t cig_index_scan(void* tmp, size_t& bytes, const CigIndex& ix, uint64_t n_cigar, hipStream_t stream, std::index_sequence<K...>)
+{
+  auto adds = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), Of{ ix.cigar, n_cigar });
+  auto prefixes = rocprim::make_zip_iterator(rocprim::make_tuple((ix.prefixes + K * ix.rows)...));
+  return rocprim::exclusive_scan(tmp, bytes, adds, prefixes, typename Of::Tuple((uint64_t)(0 * K)...), n_cigar + 1, CigTupleAdd(), stream);
+}
+
+// Stages entries and records for one call.  Of{cigar, n_cigar}(e): element e of the scan's input, a tuple (Of::Tuple) that begins with
+// cig_bases.  n_items: the caller's queries or ranges, for which the status words and the reduction's temporary are sized as well.
+// behind(): what else the caller launches under `timer` once k_lift_check and its reduction are queued.  Returns NTS_ENOMEM while
+// nothing is queued yet; behind that NTS_OK with the stream's state in e_run, the copy of the smallest offending chain into *worst
+// queued and the stream NOT synchronised: entries and records are sources of asynchronous copies, so the caller synchronises once
+// whatever happened.
+template <class Of, class Behind>
+int cig_index_stage(nts_ctx* ctx, const char* timer, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains, uint64_t n_items,
+                    uint32_t* worst, CigIndex& ix, hipError_t& e_run, Behind behind)
+{
+  constexpr size_t NP = rocprim::tuple_size<typename Of::Tuple>::value;
+  const auto columns = std::make_index_sequence<NP>();
+  const uint64_t lanes = n_cigar + n_chains, most = std::max(lanes, n_items);
+  NTS_WS(d_cigar, uint64_t*, "cigx_cigar", std::max<uint64_t>(n_cigar, 1) * 8);
+  NTS_WS(d_chains, nts_cig_chain*, "cigx_chains", std::max<uint64_t>(n_chains, 1) * sizeof(nts_cig_chain));
+  NTS_WS(d_prefixes, uint64_t*, "cigx_prefixes", NP * (n_cigar + 1) * 8);
+  NTS_WS(d_status, uint32_t*, "cigx_status", std::max<uint64_t>(most, 1) * 4);
+  NTS_WS(d_worst, uint32_t*, "cigx_worst", 2 * 4);
+  ix = { d_cigar, d_chains, d_prefixes, n_cigar + 1, d_status, d_worst, nullptr, 0 };
+  e_run = hipSuccess;
+  if (n_cigar) e_run = hipMemcpyAsync(d_cigar, cigar, n_cigar * 8, hipMemcpyHostToDevice, ctx->stream);
+  if (e_run == hipSuccess && n_chains) e_run = hipMemcpyAsync(d_chains, chains, n_chains * sizeof(nts_cig_chain), hipMemcpyHostToDevice, ctx->stream);
+  if (e_run == hipSuccess) {
+    ScopedTimer t(ctx, timer, true);
+    size_t tmp_s = 0;
+    e_run = cig_index_scan<Of>(nullptr, tmp_s, ix, n_cigar, ctx->stream, columns);
+    if (e_run == hipSuccess) e_run = rocprim::reduce(nullptr, ix.tmp_bytes, d_status, d_worst, SCRIPT_OK, most, ScriptMin(), ctx->stream);
+    ix.tmp = e_run == hipSuccess ? ws_get(ctx, "ivs_tmp", std::max<size_t>(std::max(tmp_s, ix.tmp_bytes), 16)) : nullptr; // (once, behind both sizes)
+    if (e_run == hipSuccess && !ix.tmp) e_run = hipErrorOutOfMemory;
+    if (e_run == hipSuccess) e_run = cig_index_scan<Of>(ix.tmp, tmp_s, ix, n_cigar, ctx->stream, columns);
+    if (e_run == hipSuccess && lanes) {
+      NTS_LAUNCH(k_lift_check, IVL_GRID(lanes), ix.cigar, n_cigar, ix.chains, n_chains, ix.column(0), ix.column(1), d_status);
+      e_run = rocprim::reduce(ix.tmp, ix.tmp_bytes, d_status, d_worst, SCRIPT_OK, lanes, ScriptMin(), ctx->stream);
+    }
+    if (e_run == hipSuccess) behind();
+  }
+  if (e_run == hipSuccess && lanes) e_run = hipMemcpyAsync(worst, d_worst, 4, hipMemcpyDeviceToHost, ctx->stream);
+  return NTS_OK;
+}
+
+// ---- the coordinate map of the chains' CIGARs (nts_cigar_lift; ntsynt_amd/assess.py block_lift) ----
+// docs/design/04_23_block_lift.md.  Input: CIGAR entries and chain records as nts_cigar_build returns them, and queries {chain, side, pos}:
+// an offset on side A (0) or B (1) of a chain.  The answer is the offset on the other side and the entry the position falls in.
+//   1  cig_index_stage with the pair (A bases, B bases) alone: the columns PA and PB (timer "lift_scan").
+//   2  k_cig_lift: one lane per query; validates it, finds with an upper-bound binary search over Psrc the entry that holds pos and
+//      stores one 32 B hit; an invalid query stores nothing but its own index in its status word, a second minimum reduction names the
+//      smallest (timer "lift_search").
+// No atomic, no launch per chain or query, no floating point, no host loop over entries or queries.
+
+constexpr uint32_t LIFT_MAX_BASES_LOG2 = 63; // the global scan must not wrap
+static_assert(sizeof(nts_lift_query) == 16 && sizeof(nts_lift_hit) == 32, "the C ABI's layout");
+
+struct LiftBasesOf // element e of the scan's input: what entry e consumes; nothing behind the last entry
+{
+  using Tuple = CigBases;
+  const uint64_t* cigar;
+  uint64_t n_cigar;
+  __host__ __device__ Tuple operator()(uint64_t e) const { return e < n_cigar ? cig_bases(cigar[e]) : Tuple(0, 0); }
+};
 
 __global__ __launch_bounds__(256) void k_cig_lift(const uint64_t* __restrict__ cigar, uint64_t n_cigar, const nts_cig_chain* __restrict__ chains,
                                                   uint64_t n_chains, const uint64_t* __restrict__ PA, const uint64_t* __restrict__ PB,
@@ -383,15 +517,15 @@ __global__ __launch_bounds__(256) void k_cig_lift(const uint64_t* __restrict__ c
   const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x;
   if (g >= n_queries) return;
   const nts_lift_query q = queries[g];
-  if (q.chain >= n_chains || q.side > 1u) {
+  nts_cig_chain ch;
+  if (!cig_chain_of(chains, n_chains, q.chain, q.side, ch)) {
     status[g] = (uint32_t)g;
     return;
   }
-  const nts_cig_chain ch = chains[q.chain];
   const uint64_t first = ch.first, n = ch.n_cig;
   const uint64_t len_src = q.side ? ch.len_b : ch.len_a, len_oth = q.side ? ch.len_a : ch.len_b;
-  // (the host refused the first two tests before the launch; a chain without entries holds no base: every index below is <= first + n <= n_cigar)
-  if (first > n_cigar || n > n_cigar - first || q.pos > len_src || (q.pos < len_src && n == 0)) {
+  // (a chain without entries holds no base: every index below is <= first + n <= n_cigar)
+  if (cig_chain_beyond(ch, n_cigar) || q.pos > len_src || (q.pos < len_src && n == 0)) {
     status[g] = (uint32_t)g;
     return;
   }
@@ -403,12 +537,7 @@ __global__ __launch_bounds__(256) void k_cig_lift(const uint64_t* __restrict__ c
   const uint64_t* __restrict__ P = q.side ? PB : PA;
   const uint64_t* __restrict__ O = q.side ? PA : PB;
   const uint64_t base = P[first];
-  uint64_t lo = first, hi = first + n; // P[lo] - base <= pos < P[hi] - base (k_lift_check: P[first + n] - base = len_src): the smallest such hi
-  while (hi - lo > 1u) {
-    const uint64_t mid = lo + (hi - lo) / 2u;
-    if (P[mid] - base > q.pos) hi = mid;
-    else lo = mid;
-  }
+  const uint64_t lo = cig_entry_of(P, base, first, first + n, q.pos);
   const uint64_t code = cigar[lo] & 15u; // (first <= lo < first + n <= n_cigar)
   const uint64_t off = q.pos - (P[lo] - base);
   hits[g] = { O[lo] - O[first] + (code == CIG_EQ || code == CIG_X ? off : 0), lo, off, (uint32_t)code, 0u };
@@ -417,60 +546,29 @@ __global__ __launch_bounds__(256) void k_cig_lift(const uint64_t* __restrict__ c
 int cigar_lift_run(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains, const nts_lift_query* queries,
                    uint64_t n_queries, nts_lift_hit* hits)
 {
-  uint64_t sum_a = 0, sum_b = 0;
-  for (uint64_t c = 0; c < n_chains; ++c) {
-    const nts_cig_chain& ch = chains[c];
-    auto who = [c] { return "nts_cigar_lift: chain " + std::to_string(c); }; // (made only for a chain that is refused)
-    if (c && ch.first < chains[c - 1].first) return fail(ctx, NTS_EINVAL, who() + ": first is not nondecreasing");
-    if (ch.first > n_cigar || ch.n_cig > n_cigar - ch.first) return fail(ctx, NTS_EINVAL, who() + ": first + n_cig lies beyond n_cigar");
-    if (ch.len_a >= LIFT_MAX_BASES || ch.len_b >= LIFT_MAX_BASES) return fail(ctx, NTS_ERANGE, "nts_cigar_lift: 2^63 bases or more");
-    sum_a += ch.len_a;
-    sum_b += ch.len_b;
-    if (sum_a >= LIFT_MAX_BASES || sum_b >= LIFT_MAX_BASES) return fail(ctx, NTS_ERANGE, "nts_cigar_lift: 2^63 bases or more");
-  }
-  const uint64_t lanes = n_cigar + n_chains;
-  NTS_WS(d_cigar, uint64_t*, "lift_cigar", std::max<uint64_t>(n_cigar, 1) * 8);
-  NTS_WS(d_chains, nts_cig_chain*, "lift_chains", std::max<uint64_t>(n_chains, 1) * sizeof(nts_cig_chain));
-  NTS_WS(d_pa, uint64_t*, "lift_pa", (n_cigar + 1) * 8);
-  NTS_WS(d_pb, uint64_t*, "lift_pb", (n_cigar + 1) * 8);
-  NTS_WS(d_status, uint32_t*, "lift_status", std::max<uint64_t>(std::max(lanes, n_queries), 1) * 4);
+  if (const int rc = cig_chains_check(ctx, "nts_cigar_lift", LIFT_MAX_BASES_LOG2, false, chains, n_chains, n_cigar, [](uint64_t, auto) { return NTS_OK; })) return rc;
+  // (its own buffers first: while nothing is queued, a request that fails may still return at once)
   NTS_WS(d_queries, nts_lift_query*, "lift_queries", std::max<uint64_t>(n_queries, 1) * sizeof(nts_lift_query));
   NTS_WS(d_hits, nts_lift_hit*, "lift_hits", std::max<uint64_t>(n_queries, 1) * sizeof(nts_lift_hit));
-  NTS_WS(d_worst, uint32_t*, "lift_worst", 2 * 4); // the smallest offending chain, the smallest offending query
   nts_lift_hit* host_hits = n_queries ? (nts_lift_hit*)malloc(n_queries * sizeof(nts_lift_hit)) : nullptr; // (the caller's array is written only on success)
   if (n_queries && !host_hits) return fail(ctx, NTS_ENOMEM, "nts_cigar_lift: no host memory for the hits");
-  uint32_t worst[2] = { SCRIPT_OK, SCRIPT_OK };
-  hipError_t e_run = hipSuccess;
-  if (n_cigar) e_run = hipMemcpyAsync(d_cigar, cigar, n_cigar * 8, hipMemcpyHostToDevice, ctx->stream);
-  if (e_run == hipSuccess && n_chains) e_run = hipMemcpyAsync(d_chains, chains, n_chains * sizeof(nts_cig_chain), hipMemcpyHostToDevice, ctx->stream);
+  uint32_t worst[2] = { SCRIPT_OK, SCRIPT_OK }; // the smallest offending chain, the smallest offending query
+  CigIndex ix;
+  hipError_t e_run;
+  if (const int rc = cig_index_stage<LiftBasesOf>(ctx, "lift_scan", cigar, n_cigar, chains, n_chains, n_queries, &worst[0], ix, e_run, [] {})) {
+    free(host_hits);
+    return rc;
+  }
   if (e_run == hipSuccess && n_queries)
     e_run = hipMemcpyAsync(d_queries, queries, n_queries * sizeof(nts_lift_query), hipMemcpyHostToDevice, ctx->stream);
-  size_t tmp_s = 0, tmp_r = 0;
-  void* d_tmp = nullptr;
-  auto bases = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), LiftBasesOf{ d_cigar, n_cigar });
-  auto prefixes = rocprim::make_zip_iterator(rocprim::make_tuple(d_pa, d_pb));
-  if (e_run == hipSuccess) {
-    ScopedTimer t(ctx, "lift_scan", true);
-    e_run = rocprim::exclusive_scan(nullptr, tmp_s, bases, prefixes, LiftPair(0, 0), n_cigar + 1, LiftPairAdd(), ctx->stream);
-    if (e_run == hipSuccess) e_run = rocprim::reduce(nullptr, tmp_r, d_status, d_worst, SCRIPT_OK, std::max(lanes, n_queries), ScriptMin(), ctx->stream);
-    d_tmp = e_run == hipSuccess ? ws_get(ctx, "ivs_tmp", std::max<size_t>(std::max(tmp_s, tmp_r), 16)) : nullptr;
-    if (e_run == hipSuccess && !d_tmp) e_run = hipErrorOutOfMemory;
-    if (e_run == hipSuccess) e_run = rocprim::exclusive_scan(d_tmp, tmp_s, bases, prefixes, LiftPair(0, 0), n_cigar + 1, LiftPairAdd(), ctx->stream);
-    if (e_run == hipSuccess && lanes) {
-      NTS_LAUNCH(k_lift_check, IVL_GRID(lanes), (const uint64_t*)d_cigar, n_cigar, (const nts_cig_chain*)d_chains, n_chains, (const uint64_t*)d_pa,
-                 (const uint64_t*)d_pb, d_status);
-      e_run = rocprim::reduce(d_tmp, tmp_r, d_status, d_worst, SCRIPT_OK, lanes, ScriptMin(), ctx->stream);
-    }
-  }
-  if (e_run == hipSuccess && lanes) e_run = hipMemcpyAsync(&worst[0], d_worst, 4, hipMemcpyDeviceToHost, ctx->stream);
   if (e_run == hipSuccess && n_queries) { // (no query: nothing more is launched)
     ScopedTimer t(ctx, "lift_search", true);
-    NTS_LAUNCH(k_cig_lift, IVL_GRID(n_queries), (const uint64_t*)d_cigar, n_cigar, (const nts_cig_chain*)d_chains, n_chains, (const uint64_t*)d_pa,
-               (const uint64_t*)d_pb, (const nts_lift_query*)d_queries, n_queries, d_hits, d_status);
-    e_run = rocprim::reduce(d_tmp, tmp_r, d_status, d_worst + 1, SCRIPT_OK, n_queries, ScriptMin(), ctx->stream);
+    NTS_LAUNCH(k_cig_lift, IVL_GRID(n_queries), ix.cigar, n_cigar, ix.chains, n_chains, ix.column(0), ix.column(1), (const nts_lift_query*)d_queries, n_queries,
+               d_hits, ix.status);
+    e_run = rocprim::reduce(ix.tmp, ix.tmp_bytes, ix.status, ix.worst + 1, SCRIPT_OK, n_queries, ScriptMin(), ctx->stream);
   }
   if (e_run == hipSuccess) e_run = hipGetLastError();
-  if (e_run == hipSuccess && n_queries) e_run = hipMemcpyAsync(&worst[1], d_worst + 1, 4, hipMemcpyDeviceToHost, ctx->stream);
+  if (e_run == hipSuccess && n_queries) e_run = hipMemcpyAsync(&worst[1], ix.worst + 1, 4, hipMemcpyDeviceToHost, ctx->stream);
   if (e_run == hipSuccess && n_queries) e_run = hipMemcpyAsync(host_hits, d_hits, n_queries * sizeof(nts_lift_hit), hipMemcpyDeviceToHost, ctx->stream);
   const hipError_t e_sync = hipStreamSynchronize(ctx->stream); // (whatever happened: the caller's arrays were sources of asynchronous copies)
   const bool good = e_run == hipSuccess && e_sync == hipSuccess && worst[0] == SCRIPT_OK && worst[1] == SCRIPT_OK;
@@ -488,10 +586,8 @@ int cigar_lift_run(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const 
 // source bases lo .. hi - 1 of one side of a chain.  The answer counts the chain's columns from the column of base lo to the column of
 // base hi - 1: =, X, the columns that consume the source only, the columns that consume the other side only, the runs of either gap
 // kind, and the lifted span [oth_lo, oth_hi) on the other side.
-//   1  ONE rocprim::exclusive_scan over n_cigar + 1 elements of what a transform iterator makes of an entry -- (A bases, B bases, X
-//      columns, D columns, I heads | D heads << 32) -- into five arrays of n_cigar + 1 GLOBAL prefixes; a head is an entry whose
-//      predecessor in the array has another code, or entry 0.  = columns are A - X - D, I columns B - A + D.  k_lift_check, unchanged,
-//      checks entries and records against the A and B prefixes, a minimum reduction names the smallest chain (timer "lift_stats_scan").
+//   1  cig_index_stage with (A bases, B bases, X columns, D columns, I heads | D heads << 32): five columns; a head is an entry whose
+//      predecessor in the array has another code, or entry 0.  = columns are A - X - D, I columns B - A + D (timer "lift_stats_scan").
 //   2  k_cig_lift_stats: one lane per range; validates it, finds the entries of base lo and of base hi - 1 with two upper-bound
 //      binary searches over Psrc, takes the whole entries between them as prefix differences and the two partial entries from their
 //      offsets, and stores one 64 B record; an invalid range stores nothing but its own index in its status word, a second minimum
@@ -503,25 +599,17 @@ static_assert(sizeof(nts_lift_range) == 24 && sizeof(nts_lift_stats) == 64, "the
 
 struct LiftStatOf // element e of the scan's input: what entry e adds; nothing behind the last entry
 {
+  using Tuple = LiftStatTuple;
   const uint64_t* cigar;
   uint64_t n_cigar;
-  __host__ __device__ LiftStatTuple operator()(uint64_t e) const
+  __host__ __device__ Tuple operator()(uint64_t e) const
   {
-    if (e >= n_cigar) return LiftStatTuple(0, 0, 0, 0, 0);
+    if (e >= n_cigar) return Tuple(0, 0, 0, 0, 0);
     const uint64_t v = cigar[e], code = v & 15u, len = v >> 4;
-    const bool both = code == CIG_EQ || code == CIG_X;
+    const CigBases ab = cig_bases(v);
     const bool head = e == 0 || (cigar[e - 1] & 15u) != code;
-    return LiftStatTuple(both || code == CIG_D ? len : 0, both || code == CIG_I ? len : 0, code == CIG_X ? len : 0, code == CIG_D ? len : 0,
-                         !head ? 0 : code == CIG_I ? 1ull : code == CIG_D ? 1ull << 32 : 0); // (at most n_cigar < 2^32 heads of a kind: no carry between the halves)
-  }
-};
-
-struct LiftStatAdd
-{
-  __host__ __device__ LiftStatTuple operator()(const LiftStatTuple& x, const LiftStatTuple& y) const
-  {
-    return LiftStatTuple(rocprim::get<0>(x) + rocprim::get<0>(y), rocprim::get<1>(x) + rocprim::get<1>(y), rocprim::get<2>(x) + rocprim::get<2>(y),
-                         rocprim::get<3>(x) + rocprim::get<3>(y), rocprim::get<4>(x) + rocprim::get<4>(y));
+    return Tuple(rocprim::get<0>(ab), rocprim::get<1>(ab), code == CIG_X ? len : 0, code == CIG_D ? len : 0,
+                 !head ? 0 : code == CIG_I ? 1ull : code == CIG_D ? 1ull << 32 : 0); // (at most n_cigar < 2^32 heads of a kind: no carry between the halves)
   }
 };
 
@@ -534,15 +622,15 @@ __global__ __launch_bounds__(256) void k_cig_lift_stats(const uint64_t* __restri
   const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x;
   if (g >= n_ranges) return;
   const nts_lift_range r = ranges[g];
-  if (r.chain >= n_chains || r.side > 1u) {
+  nts_cig_chain ch;
+  if (!cig_chain_of(chains, n_chains, r.chain, r.side, ch)) {
     status[g] = (uint32_t)g;
     return;
   }
-  const nts_cig_chain ch = chains[r.chain];
   const uint64_t first = ch.first, n = ch.n_cig;
   const uint64_t len_src = r.side ? ch.len_b : ch.len_a;
-  // (the host refused the first two tests before the launch; a chain without entries holds no base: every index below is <= first + n <= n_cigar)
-  if (first > n_cigar || n > n_cigar - first || n == 0 || r.lo >= r.hi || r.hi > len_src) {
+  // (a chain without entries holds no base: every index below is <= first + n <= n_cigar)
+  if (cig_chain_beyond(ch, n_cigar) || n == 0 || r.lo >= r.hi || r.hi > len_src) {
     status[g] = (uint32_t)g;
     return;
   }
@@ -550,19 +638,8 @@ __global__ __launch_bounds__(256) void k_cig_lift_stats(const uint64_t* __restri
   const uint64_t* __restrict__ P = r.side ? PB : PA;
   const uint64_t* __restrict__ O = r.side ? PA : PB;
   const uint64_t base = P[first], last = r.hi - 1u;
-  uint64_t e_lo = first, hi = first + n; // P[e_lo] - base <= lo < P[hi] - base (k_lift_check: P[first + n] - base = len_src): the smallest such hi
-  while (hi - e_lo > 1u) {
-    const uint64_t mid = e_lo + (hi - e_lo) / 2u;
-    if (P[mid] - base > r.lo) hi = mid;
-    else e_lo = mid;
-  }
-  uint64_t e_hi = e_lo; // (P[e_lo] - base <= lo <= hi - 1: the entry of base hi - 1 is e_lo or lies behind it)
-  hi = first + n;
-  while (hi - e_hi > 1u) {
-    const uint64_t mid = e_hi + (hi - e_hi) / 2u;
-    if (P[mid] - base > last) hi = mid;
-    else e_hi = mid;
-  }
+  const uint64_t e_lo = cig_entry_of(P, base, first, first + n, r.lo);
+  const uint64_t e_hi = cig_entry_of(P, base, e_lo, first + n, last); // (P[e_lo] - base <= lo <= hi - 1: the entry of base hi - 1 is e_lo or lies behind it)
   // first <= e_lo <= e_hi < first + n <= n_cigar: cigar[e_lo], cigar[e_hi]; the prefixes at e_lo + 1 and e_hi + 1 <= first + n <= n_cigar
   const uint64_t v_lo = cigar[e_lo], v_hi = cigar[e_hi];
   const uint64_t code_lo = v_lo & 15u, code_hi = v_hi & 15u;
@@ -594,64 +671,28 @@ __global__ __launch_bounds__(256) void k_cig_lift_stats(const uint64_t* __restri
 int cigar_lift_stats_run(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains, const nts_lift_range* ranges,
                          uint64_t n_ranges, nts_lift_stats* stats)
 {
-  uint64_t sum_a = 0, sum_b = 0;
-  for (uint64_t c = 0; c < n_chains; ++c) {
-    const nts_cig_chain& ch = chains[c];
-    auto who = [c] { return "nts_cigar_lift_stats: chain " + std::to_string(c); }; // (made only for a chain that is refused)
-    if (c && ch.first < chains[c - 1].first) return fail(ctx, NTS_EINVAL, who() + ": first is not nondecreasing");
-    if (ch.first > n_cigar || ch.n_cig > n_cigar - ch.first) return fail(ctx, NTS_EINVAL, who() + ": first + n_cig lies beyond n_cigar");
-    if (ch.len_a >= LIFT_MAX_BASES || ch.len_b >= LIFT_MAX_BASES) return fail(ctx, NTS_ERANGE, "nts_cigar_lift_stats: 2^63 bases or more");
-    sum_a += ch.len_a;
-    sum_b += ch.len_b;
-    if (sum_a >= LIFT_MAX_BASES || sum_b >= LIFT_MAX_BASES) return fail(ctx, NTS_ERANGE, "nts_cigar_lift_stats: 2^63 bases or more");
-  }
-  const uint64_t lanes = n_cigar + n_chains;
-  NTS_WS(d_cigar, uint64_t*, "lstat_cigar", std::max<uint64_t>(n_cigar, 1) * 8);
-  NTS_WS(d_chains, nts_cig_chain*, "lstat_chains", std::max<uint64_t>(n_chains, 1) * sizeof(nts_cig_chain));
-  NTS_WS(d_pre, uint64_t*, "lstat_prefixes", 5 * (n_cigar + 1) * 8); // PA, PB, PX, PD, PH: n_cigar + 1 entries each
-  NTS_WS(d_status, uint32_t*, "lstat_status", std::max<uint64_t>(std::max(lanes, n_ranges), 1) * 4);
+  if (const int rc = cig_chains_check(ctx, "nts_cigar_lift_stats", LIFT_MAX_BASES_LOG2, false, chains, n_chains, n_cigar, [](uint64_t, auto) { return NTS_OK; })) return rc;
+  // (its own buffers first: while nothing is queued, a request that fails may still return at once)
   NTS_WS(d_ranges, nts_lift_range*, "lstat_ranges", std::max<uint64_t>(n_ranges, 1) * sizeof(nts_lift_range));
   NTS_WS(d_stats, nts_lift_stats*, "lstat_stats", std::max<uint64_t>(n_ranges, 1) * sizeof(nts_lift_stats));
-  NTS_WS(d_worst, uint32_t*, "lstat_worst", 2 * 4); // the smallest offending chain, the smallest offending range
-  uint64_t* const d_pa = d_pre;
-  uint64_t* const d_pb = d_pre + (n_cigar + 1);
-  uint64_t* const d_px = d_pre + 2 * (n_cigar + 1);
-  uint64_t* const d_pd = d_pre + 3 * (n_cigar + 1);
-  uint64_t* const d_ph = d_pre + 4 * (n_cigar + 1);
   nts_lift_stats* host_stats = n_ranges ? (nts_lift_stats*)malloc(n_ranges * sizeof(nts_lift_stats)) : nullptr; // (the caller's array is written only on success)
   if (n_ranges && !host_stats) return fail(ctx, NTS_ENOMEM, "nts_cigar_lift_stats: no host memory for the records");
-  uint32_t worst[2] = { SCRIPT_OK, SCRIPT_OK };
-  hipError_t e_run = hipSuccess;
-  if (n_cigar) e_run = hipMemcpyAsync(d_cigar, cigar, n_cigar * 8, hipMemcpyHostToDevice, ctx->stream);
-  if (e_run == hipSuccess && n_chains) e_run = hipMemcpyAsync(d_chains, chains, n_chains * sizeof(nts_cig_chain), hipMemcpyHostToDevice, ctx->stream);
-  if (e_run == hipSuccess && n_ranges) e_run = hipMemcpyAsync(d_ranges, ranges, n_ranges * sizeof(nts_lift_range), hipMemcpyHostToDevice, ctx->stream);
-  size_t tmp_s = 0, tmp_r = 0;
-  void* d_tmp = nullptr;
-  auto adds = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), LiftStatOf{ d_cigar, n_cigar });
-  auto prefixes = rocprim::make_zip_iterator(rocprim::make_tuple(d_pa, d_pb, d_px, d_pd, d_ph));
-  if (e_run == hipSuccess) {
-    ScopedTimer t(ctx, "lift_stats_scan", true);
-    e_run = rocprim::exclusive_scan(nullptr, tmp_s, adds, prefixes, LiftStatTuple(0, 0, 0, 0, 0), n_cigar + 1, LiftStatAdd(), ctx->stream);
-    if (e_run == hipSuccess) e_run = rocprim::reduce(nullptr, tmp_r, d_status, d_worst, SCRIPT_OK, std::max(lanes, n_ranges), ScriptMin(), ctx->stream);
-    d_tmp = e_run == hipSuccess ? ws_get(ctx, "ivs_tmp", std::max<size_t>(std::max(tmp_s, tmp_r), 16)) : nullptr; // (once, behind both sizes)
-    if (e_run == hipSuccess && !d_tmp) e_run = hipErrorOutOfMemory;
-    if (e_run == hipSuccess) e_run = rocprim::exclusive_scan(d_tmp, tmp_s, adds, prefixes, LiftStatTuple(0, 0, 0, 0, 0), n_cigar + 1, LiftStatAdd(), ctx->stream);
-    if (e_run == hipSuccess && lanes) {
-      NTS_LAUNCH(k_lift_check, IVL_GRID(lanes), (const uint64_t*)d_cigar, n_cigar, (const nts_cig_chain*)d_chains, n_chains, (const uint64_t*)d_pa,
-                 (const uint64_t*)d_pb, d_status);
-      e_run = rocprim::reduce(d_tmp, tmp_r, d_status, d_worst, SCRIPT_OK, lanes, ScriptMin(), ctx->stream);
-    }
+  uint32_t worst[2] = { SCRIPT_OK, SCRIPT_OK }; // the smallest offending chain, the smallest offending range
+  CigIndex ix; // columns PA, PB, PX, PD, PH
+  hipError_t e_run;
+  if (const int rc = cig_index_stage<LiftStatOf>(ctx, "lift_stats_scan", cigar, n_cigar, chains, n_chains, n_ranges, &worst[0], ix, e_run, [] {})) {
+    free(host_stats);
+    return rc;
   }
-  if (e_run == hipSuccess && lanes) e_run = hipMemcpyAsync(&worst[0], d_worst, 4, hipMemcpyDeviceToHost, ctx->stream);
+  if (e_run == hipSuccess && n_ranges) e_run = hipMemcpyAsync(d_ranges, ranges, n_ranges * sizeof(nts_lift_range), hipMemcpyHostToDevice, ctx->stream);
   if (e_run == hipSuccess && n_ranges) { // (no range: nothing more is launched)
     ScopedTimer t(ctx, "lift_stats_search", true);
-    NTS_LAUNCH(k_cig_lift_stats, IVL_GRID(n_ranges), (const uint64_t*)d_cigar, n_cigar, (const nts_cig_chain*)d_chains, n_chains, (const uint64_t*)d_pa,
-               (const uint64_t*)d_pb, (const uint64_t*)d_px, (const uint64_t*)d_pd, (const uint64_t*)d_ph, (const nts_lift_range*)d_ranges, n_ranges, d_stats,
-               d_status);
-    e_run = rocprim::reduce(d_tmp, tmp_r, d_status, d_worst + 1, SCRIPT_OK, n_ranges, ScriptMin(), ctx->stream);
+    NTS_LAUNCH(k_cig_lift_stats, IVL_GRID(n_ranges), ix.cigar, n_cigar, ix.chains, n_chains, ix.column(0), ix.column(1), ix.column(2), ix.column(3), ix.column(4),
+               (const nts_lift_range*)d_ranges, n_ranges, d_stats, ix.status);
+    e_run = rocprim::reduce(ix.tmp, ix.tmp_bytes, ix.status, ix.worst + 1, SCRIPT_OK, n_ranges, ScriptMin(), ctx->stream);
   }
   if (e_run == hipSuccess) e_run = hipGetLastError();
-  if (e_run == hipSuccess && n_ranges) e_run = hipMemcpyAsync(&worst[1], d_worst + 1, 4, hipMemcpyDeviceToHost, ctx->stream);
+  if (e_run == hipSuccess && n_ranges) e_run = hipMemcpyAsync(&worst[1], ix.worst + 1, 4, hipMemcpyDeviceToHost, ctx->stream);
   if (e_run == hipSuccess && n_ranges) e_run = hipMemcpyAsync(host_stats, d_stats, n_ranges * sizeof(nts_lift_stats), hipMemcpyDeviceToHost, ctx->stream);
   const hipError_t e_sync = hipStreamSynchronize(ctx->stream); // (whatever happened: the caller's arrays were sources of asynchronous copies)
   const bool good = e_run == hipSuccess && e_sync == hipSuccess && worst[0] == SCRIPT_OK && worst[1] == SCRIPT_OK;
@@ -670,10 +711,9 @@ int cigar_lift_stats_run(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, 
 // and per chain a span that places it in a record of genome a (target, forwards) and of genome b (query, forwards or backwards and
 // complemented).  A TOKEN is what one entry gives a text: cg "<len><letter>"; cs ":<len>" for =, "*tq" per column for X, "-" / "+" and
 // the bases for D / I.  Every token has at least 2 bytes.
-//   1  ONE rocprim::exclusive_scan over n_cigar + 1 elements of what a transform iterator makes of an entry -- (A bases, B bases, cg
-//      bytes, cs bytes) -- into four arrays of n_cigar + 1 GLOBAL prefixes.  k_lift_check, unchanged, checks entries and records against
-//      the A and B prefixes, a minimum reduction names the smallest chain; k_cig_text_firsts reads the byte prefixes at every chain's
-//      first entry (timer "cigar_text_scan").  The chains tile the entries (host check), so a chain's text is one byte range.
+//   1  cig_index_stage with (A bases, B bases, cg bytes, cs bytes): four columns; behind its check, k_cig_text_firsts reads the byte
+//      prefixes at every chain's first entry (timer "cigar_text_scan").  The chains tile the entries (host check), so a chain's text
+//      is one byte range.
 //   2  k_cig_text<kind>: one lane per aligned 4-byte word of the text; an upper-bound binary search over the byte prefix finds the entry
 //      of the word's first byte, the lane walks on over the at most three further entries a word touches, composes four bytes in a
 //      register and stores one dword (timer "cigar_text_emit").  A base byte finds its chain by a search over the chains' first
@@ -681,7 +721,7 @@ int cigar_lift_stats_run(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, 
 // No atomic, no launch per chain or entry, no floating point, no host loop over entries.
 
 using CigTextTuple = rocprim::tuple<uint64_t, uint64_t, uint64_t, uint64_t>; // A bases, B bases, cg bytes, cs bytes
-constexpr uint64_t CIG_TEXT_MAX_BASES = 1ull << 62; // cs bytes <= 3 X + D + I + 20 n_cigar <= A + B + min(A, B) + 20 n_cigar: inside 64 bits
+constexpr uint32_t CIG_TEXT_MAX_BASES_LOG2 = 62; // cs bytes <= 3 X + D + I + 20 n_cigar <= A + B + min(A, B) + 20 n_cigar: inside 64 bits
 constexpr uint32_t CIG_TEXT_CG = 0, CIG_TEXT_CS = 1;
 static_assert(sizeof(nts_cig_span) == 32, "the C ABI's layout");
 
@@ -749,25 +789,18 @@ static_assert(sizeof(CigTextChain) == 48, "six 8-byte words");
 
 struct CigTextOf // element e of the scan's input: what entry e consumes and how long its two tokens are; nothing behind the last entry
 {
+  using Tuple = CigTextTuple;
   const uint64_t* cigar;
   uint64_t n_cigar;
-  __device__ CigTextTuple operator()(uint64_t e) const
+  __device__ Tuple operator()(uint64_t e) const
   {
-    if (e >= n_cigar) return CigTextTuple(0, 0, 0, 0);
+    if (e >= n_cigar) return Tuple(0, 0, 0, 0);
     const uint64_t v = cigar[e], code = v & 15u, len = v >> 4;
+    const CigBases ab = cig_bases(v);
     const bool both = code == CIG_EQ || code == CIG_X, gap = code == CIG_I || code == CIG_D;
     const uint64_t d = cig_digits(len);
-    return CigTextTuple(both || code == CIG_D ? len : 0, both || code == CIG_I ? len : 0, both || gap ? d + 1u : 0,
-                        code == CIG_EQ ? d + 1u : code == CIG_X ? 3u * len : gap ? len + 1u : 0); // (len < 2^60: 3 len does not wrap)
-  }
-};
-
-struct CigTextAdd
-{
-  __device__ CigTextTuple operator()(const CigTextTuple& x, const CigTextTuple& y) const
-  {
-    return CigTextTuple(rocprim::get<0>(x) + rocprim::get<0>(y), rocprim::get<1>(x) + rocprim::get<1>(y), rocprim::get<2>(x) + rocprim::get<2>(y),
-                        rocprim::get<3>(x) + rocprim::get<3>(y));
+    return Tuple(rocprim::get<0>(ab), rocprim::get<1>(ab), both || gap ? d + 1u : 0,
+                 code == CIG_EQ ? d + 1u : code == CIG_X ? 3u * len : gap ? len + 1u : 0); // (len < 2^60: 3 len does not wrap)
   }
 };
 
@@ -806,12 +839,7 @@ __global__ __launch_bounds__(256) void k_cig_text(const uint64_t* __restrict__ c
   const uint64_t w = (uint64_t)blockIdx.x * 256u + threadIdx.x;
   if (w >= n_words || n_cigar == 0) return;
   const uint64_t total = P[n_cigar], o = 4u * w;
-  uint64_t e = 0, hi = n_cigar; // P[e] <= o, and o < P[hi] for a word inside the text: the largest such e
-  while (hi - e > 1u) {
-    const uint64_t mid = e + (hi - e) / 2u;
-    if (P[mid] <= o) e = mid;
-    else hi = mid;
-  }
+  uint64_t e = cig_last_at_or_before(n_cigar, o, [P](uint64_t i) { return P[i]; }); // the entry of the word's first byte (P[0] = 0 <= o)
   uint64_t p0 = P[e], p1 = P[e + 1u]; // (e < n_cigar)
   uint64_t v = cigar[e];
   uint32_t digits = cig_digits(v >> 4);
@@ -845,13 +873,7 @@ __global__ __launch_bounds__(256) void k_cig_text(const uint64_t* __restrict__ c
         byte = is_x ? '*' : code == CIG_D ? '-' : '+';
       } else {
         if (chain_of != e) { // the last chain with first <= e (chains[0].first = 0; empty chains in front of it share its first)
-          uint64_t c = 0, c_hi = n_chains;
-          while (c_hi - c > 1u) {
-            const uint64_t mid = c + (c_hi - c) / 2u;
-            if (chains[mid].first <= e) c = mid;
-            else c_hi = mid;
-          }
-          ch = chains[c];
+          ch = chains[cig_last_at_or_before(n_chains, e, [chains](uint64_t c) { return chains[c].first; })];
           chain_of = e;
         }
         const uint64_t f = ch.first <= e ? ch.first : e;
@@ -869,17 +891,9 @@ int cigar_text_run(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const 
 {
   const bool with_cs = spans != nullptr;
   std::vector<CigTextChain> placed(with_cs ? n_chains : 0);
-  uint64_t next = 0, sum_a = 0, sum_b = 0;
-  for (uint64_t c = 0; c < n_chains; ++c) {
+  auto place = [&](uint64_t c, auto who) -> int { // chain c's span, behind the checks of its record
+    if (!with_cs) return NTS_OK;
     const nts_cig_chain& ch = chains[c];
-    auto who = [c] { return "nts_cigar_text: chain " + std::to_string(c); }; // (made only for a chain that is refused)
-    if (ch.first != next || ch.n_cig > n_cigar - next) return fail(ctx, NTS_EINVAL, who() + ": the chains do not tile the entries");
-    next += ch.n_cig;
-    if (ch.len_a >= CIG_TEXT_MAX_BASES || ch.len_b >= CIG_TEXT_MAX_BASES) return fail(ctx, NTS_ERANGE, "nts_cigar_text: 2^62 bases or more");
-    sum_a += ch.len_a;
-    sum_b += ch.len_b;
-    if (sum_a >= CIG_TEXT_MAX_BASES || sum_b >= CIG_TEXT_MAX_BASES) return fail(ctx, NTS_ERANGE, "nts_cigar_text: 2^62 bases or more");
-    if (!with_cs) continue;
     const nts_cig_span& sp = spans[c];
     if (sp.flags & ~NTS_CIG_B_BACKWARDS) return fail(ctx, NTS_EINVAL, who() + " has unknown flag bits");
     if (sp.rec_a >= a->n_rec || sp.rec_b >= b->n_rec) return fail(ctx, NTS_EINVAL, who() + " names a record outside its genome");
@@ -891,10 +905,9 @@ int cigar_text_run(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const 
     else inside = inside && sp.pos_b <= rl_b && ch.len_b <= rl_b - sp.pos_b;
     if (!inside) return fail(ctx, NTS_EINVAL, who() + ": its span lies outside its record");
     placed[c] = { ch.first, PAD + a->rec_off[sp.rec_a] + sp.pos_a, PAD + b->rec_off[sp.rec_b] + sp.pos_b, ch.len_a, ch.len_b, sp.flags, 0u };
-  }
-  if (next != n_cigar)
-    return fail(ctx, NTS_EINVAL, n_chains ? "nts_cigar_text: chain " + std::to_string(n_chains - 1) + ": the chains do not tile the entries (the last one ends in front of n_cigar)"
-                                          : std::string("nts_cigar_text: entries and no chain: the chains do not tile the entries"));
+    return NTS_OK;
+  };
+  if (const int rc = cig_chains_check(ctx, "nts_cigar_text", CIG_TEXT_MAX_BASES_LOG2, true, chains, n_chains, n_cigar, place)) return rc;
   if (n_cigar == 0) { // (nothing is launched: every text is empty)
     *cg = nullptr;
     memset(cg_first, 0, (n_chains + 1) * 8);
@@ -904,44 +917,19 @@ int cigar_text_run(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const 
     }
     return NTS_OK;
   }
-  const uint64_t lanes = n_cigar + n_chains;
-  NTS_WS(d_cigar, uint64_t*, "cigt_cigar", n_cigar * 8);
-  NTS_WS(d_chains, nts_cig_chain*, "cigt_chains", n_chains * sizeof(nts_cig_chain));
+  // (its own buffers first: while nothing is queued, a request that fails may still return at once)
   NTS_WS(d_placed, CigTextChain*, "cigt_placed", n_chains * sizeof(CigTextChain));
-  NTS_WS(d_pre, uint64_t*, "cigt_prefixes", 4 * (n_cigar + 1) * 8); // PA, PB, PG (cg bytes), PS (cs bytes): n_cigar + 1 entries each
-  NTS_WS(d_status, uint32_t*, "cigt_status", lanes * 4);
   NTS_WS(d_first, uint64_t*, "cigt_first", 2 * (n_chains + 1) * 8);
-  NTS_WS(d_worst, uint32_t*, "cigt_worst", 4);
-  uint64_t* const d_pa = d_pre;
-  uint64_t* const d_pb = d_pre + (n_cigar + 1);
-  uint64_t* const d_pg = d_pre + 2 * (n_cigar + 1);
-  uint64_t* const d_ps = d_pre + 3 * (n_cigar + 1);
   std::vector<uint64_t> host_first(2 * (n_chains + 1)); // (the caller's arrays are written only when the call succeeds)
   uint32_t worst = SCRIPT_OK;
-  hipError_t e_run = hipMemcpyAsync(d_cigar, cigar, n_cigar * 8, hipMemcpyHostToDevice, ctx->stream);
-  if (e_run == hipSuccess) e_run = hipMemcpyAsync(d_chains, chains, n_chains * sizeof(nts_cig_chain), hipMemcpyHostToDevice, ctx->stream);
-  if (e_run == hipSuccess && with_cs) e_run = hipMemcpyAsync(d_placed, placed.data(), n_chains * sizeof(CigTextChain), hipMemcpyHostToDevice, ctx->stream);
-  auto adds = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), CigTextOf{ d_cigar, n_cigar });
-  auto prefixes = rocprim::make_zip_iterator(rocprim::make_tuple(d_pa, d_pb, d_pg, d_ps));
-  if (e_run == hipSuccess) {
-    ScopedTimer t(ctx, "cigar_text_scan", true);
-    size_t tmp_s = 0, tmp_r = 0;
-    e_run = rocprim::exclusive_scan(nullptr, tmp_s, adds, prefixes, CigTextTuple(0, 0, 0, 0), n_cigar + 1, CigTextAdd(), ctx->stream);
-    if (e_run == hipSuccess) e_run = rocprim::reduce(nullptr, tmp_r, d_status, d_worst, SCRIPT_OK, lanes, ScriptMin(), ctx->stream);
-    void* d_tmp = e_run == hipSuccess ? ws_get(ctx, "ivs_tmp", std::max<size_t>(std::max(tmp_s, tmp_r), 16)) : nullptr; // (once, behind both sizes)
-    if (e_run == hipSuccess && !d_tmp) e_run = hipErrorOutOfMemory;
-    if (e_run == hipSuccess) e_run = rocprim::exclusive_scan(d_tmp, tmp_s, adds, prefixes, CigTextTuple(0, 0, 0, 0), n_cigar + 1, CigTextAdd(), ctx->stream);
-    if (e_run == hipSuccess) {
-      NTS_LAUNCH(k_lift_check, IVL_GRID(lanes), (const uint64_t*)d_cigar, n_cigar, (const nts_cig_chain*)d_chains, n_chains, (const uint64_t*)d_pa,
-                 (const uint64_t*)d_pb, d_status);
-      e_run = rocprim::reduce(d_tmp, tmp_r, d_status, d_worst, SCRIPT_OK, lanes, ScriptMin(), ctx->stream);
-    }
-    if (e_run == hipSuccess)
-      NTS_LAUNCH(k_cig_text_firsts, IVL_GRID(n_chains + 1), (const nts_cig_chain*)d_chains, n_chains, n_cigar, (const uint64_t*)d_pg, (const uint64_t*)d_ps,
-                 d_first, d_first + (n_chains + 1));
-  }
+  CigIndex ix; // columns PA, PB, PG (cg bytes), PS (cs bytes)
+  hipError_t e_run;
+  auto firsts = [&] {
+    NTS_LAUNCH(k_cig_text_firsts, IVL_GRID(n_chains + 1), ix.chains, n_chains, n_cigar, ix.column(2), ix.column(3), d_first, d_first + (n_chains + 1));
+  };
+  if (const int rc = cig_index_stage<CigTextOf>(ctx, "cigar_text_scan", cigar, n_cigar, chains, n_chains, 0, &worst, ix, e_run, firsts)) return rc;
   if (e_run == hipSuccess) e_run = hipGetLastError();
-  if (e_run == hipSuccess) e_run = hipMemcpyAsync(&worst, d_worst, 4, hipMemcpyDeviceToHost, ctx->stream);
+  if (e_run == hipSuccess && with_cs) e_run = hipMemcpyAsync(d_placed, placed.data(), n_chains * sizeof(CigTextChain), hipMemcpyHostToDevice, ctx->stream);
   if (e_run == hipSuccess) e_run = hipMemcpyAsync(host_first.data(), d_first, 2 * (n_chains + 1) * 8, hipMemcpyDeviceToHost, ctx->stream);
   hipError_t e_sync = hipStreamSynchronize(ctx->stream); // (whatever happened: the caller's arrays were sources of asynchronous copies)
   HIP_TRY(ctx, e_run);
@@ -961,13 +949,11 @@ int cigar_text_run(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const 
   }
   {
     ScopedTimer t(ctx, "cigar_text_emit", true);
-    NTS_LAUNCH(k_cig_text<CIG_TEXT_CG>, IVL_GRID(words_cg), (const uint64_t*)d_cigar, n_cigar, (const CigTextChain*)nullptr, (uint64_t)0,
-               (const uint64_t*)d_pa, (const uint64_t*)d_pb, (const uint64_t*)d_pg, (const uint8_t*)nullptr, (uint64_t)0, (const uint8_t*)nullptr, (uint64_t)0,
-               d_cg, words_cg);
+    NTS_LAUNCH(k_cig_text<CIG_TEXT_CG>, IVL_GRID(words_cg), ix.cigar, n_cigar, (const CigTextChain*)nullptr, (uint64_t)0, ix.column(0), ix.column(1),
+               ix.column(2), (const uint8_t*)nullptr, (uint64_t)0, (const uint8_t*)nullptr, (uint64_t)0, d_cg, words_cg);
     if (with_cs)
-      NTS_LAUNCH(k_cig_text<CIG_TEXT_CS>, IVL_GRID(words_cs), (const uint64_t*)d_cigar, n_cigar, (const CigTextChain*)d_placed, n_chains,
-                 (const uint64_t*)d_pa, (const uint64_t*)d_pb, (const uint64_t*)d_ps, (const uint8_t*)a->d_code, a->n + 2 * PAD, (const uint8_t*)b->d_code,
-                 b->n + 2 * PAD, d_cs, words_cs);
+      NTS_LAUNCH(k_cig_text<CIG_TEXT_CS>, IVL_GRID(words_cs), ix.cigar, n_cigar, (const CigTextChain*)d_placed, n_chains, ix.column(0), ix.column(1),
+                 ix.column(3), (const uint8_t*)a->d_code, a->n + 2 * PAD, (const uint8_t*)b->d_code, b->n + 2 * PAD, d_cs, words_cs);
   }
   e_run = hipGetLastError();
   if (e_run == hipSuccess) e_run = hipMemcpyAsync(host_cg, d_cg, bytes_cg, hipMemcpyDeviceToHost, ctx->stream);

@@ -14,7 +14,7 @@ from tests import call_order_cases as C
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ntsynt_amd", "csrc")
 NAMES = [e.name for e in C.ENTRIES]
 REQUIRED = ["edit_segments", "edit_wide", "edit_extend", "edit_script", "edit_wide_script", "edit_extend_script", "cigar_build", "cigar_lift",
-            "iv_anchor_segments", "iv_links", "iv_sites", "iv_periods", "iv_period_hashes", "iv_families", "iv_family_sites", "hset_sweep", "hcount_capped",
+            "cigar_lift_stats", "cigar_text", "iv_anchor_segments", "iv_links", "iv_sites", "iv_periods", "iv_period_hashes", "iv_families", "iv_family_sites", "hset_sweep", "hcount_capped",
             "minhash", "minhash_intervals", "bloom_insert", "engine_add_blocks"] + ["sketch_" + w for w in ("dense", "pruned_hi", "pruned_full", "tiers", "accept_list")]
 
 
@@ -36,7 +36,7 @@ def test_the_catalogue_holds_every_entry_the_design_section_names():
 def test_the_record_layouts_are_the_device_modules():
     from ntsynt_amd import device as D
     for mine, theirs in ((C.IDENTITY, D.IDENTITY_DTYPE), (C.OP, D.OP_DTYPE), (C.SEGMENT, D.SEGMENT_DTYPE), (C.EXTEND, D.EXTEND_DTYPE), (C.CHAIN, D.CHAIN_DTYPE),
-                         (C.LIFT_HIT, D.LIFT_HIT_DTYPE), (C.LINK, D.LINK_DTYPE), (C.SITE, D.SITE_DTYPE), (C.SAMPLE, D.SAMPLE_DTYPE)):
+                         (C.LIFT_HIT, D.LIFT_HIT_DTYPE), (C.LIFT_STATS, D.LIFT_STATS_DTYPE), (C.LINK, D.LINK_DTYPE), (C.SITE, D.SITE_DTYPE), (C.SAMPLE, D.SAMPLE_DTYPE)):
         assert mine == theirs
 
 
@@ -131,7 +131,8 @@ def test_the_chain_seed_leaves_out_no_entry_and_no_size():
 # entry -> where its existing test refuses arguments (None: that entry's tests have no such case)
 REFUSED_IN = {"edit_segments": "test_gpu_edit_segments.py", "edit_wide": "test_gpu_edit_wide.py", "edit_script": "test_gpu_edit_script.py",
               "edit_wide_script": "test_gpu_edit_wide_script.py", "edit_extend": "test_gpu_edit_extend.py", "edit_extend_script": "test_gpu_edit_extend_script.py",
-              "cigar_build": "test_gpu_cigar_build.py", "cigar_lift": "test_gpu_cigar_lift.py", "iv_anchor_segments": "test_gpu_iv_anchor_segments.py",
+              "cigar_build": "test_gpu_cigar_build.py", "cigar_lift": "test_gpu_cigar_lift.py", "cigar_lift_stats": "test_gpu_cigar_lift_stats.py",
+              "cigar_text": "test_gpu_cigar_text.py", "iv_anchor_segments": "test_gpu_iv_anchor_segments.py",
               "iv_links": None, "iv_sites": "test_gpu_iv_sites.py", "iv_periods": "test_gpu_iv_periods.py", "iv_period_hashes": "test_gpu_iv_period_hashes.py",
               "iv_families": "test_gpu_iv_families.py", "iv_family_sites": "test_gpu_iv_family_sites.py", "hset_sweep": "test_gpu_hset.py",
               "hcount_capped": "test_gpu_hcount.py", "minhash": None, "minhash_intervals": "test_gpu_block_assessment.py", "bloom_insert": None, "engine_add_blocks": None}
