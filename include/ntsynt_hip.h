@@ -924,6 +924,54 @@ typedef struct
 int nts_cigar_lift_stats(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains,
                          const nts_lift_range* ranges, uint64_t n_ranges, nts_lift_stats* stats);
 
+/* ---- one span and its counts per range and pair of chains: the joined lift ------------------------------------------------------
+ * nts_cigar_lift_pairs: cigar, chains as for nts_cigar_lift.  links = n_links of {chain, reserved (0), a0, b0}: the chain occupies
+ *   [a0, a0 + len_a) on A and [b0, b0 + len_b) on B of a PAIR, in the pair's oriented offsets; pair_first (n_pairs + 1 host entries,
+ *   nondecreasing from 0 to n_links) cuts the links into pairs.  The links of one pair ascend without overlap on both sides (equality
+ *   allowed), a chain is linked at most once, a chain without entries is not linked; the records need not be ordered by pair.  ranges
+ *   = n_ranges of {pair, side, lo, hi}: the bases lo .. hi - 1 of side A (0) or B (1) of the pair, "src"; valid for pair < n_pairs,
+ *   side <= 1, lo < hi < 2^63; a range need not touch any chain.  The pair's COLUMNS are those of its linked chains in link order;
+ *   between consecutive chains lies an OPEN STRETCH of s0[i + 1] - s1[i] src and o0[i + 1] - o1[i] oth bases that no column covers.
+ *   c_lo / c_hi = the first / last column of the pair that holds a src base of [lo, hi); link_lo / link_hi = their links (the links
+ *   with s1 > lo and s0 < hi, less those at either end whose chain has no src base).  COUNTED is every column from c_lo to c_hi: the
+ *   chains between the two count whole.  src_lo, src_hi: the range clipped to [s0[link_lo], s1[link_hi]); [oth_lo, oth_hi): the lifted
+ *   span in the pair's oth offsets, o0 of the end chain plus what nts_cigar_lift_stats makes of that end; eq, x, src_gap, oth_gap: the
+ *   counted columns by kind; src_open, oth_open: the bases of the open stretches between link_lo and link_hi; src_gaps, oth_gaps: the
+ *   maximal gap runs that hold a counted column -- runs never merge across chains; link_lo, link_hi: indices into links; n_links =
+ *   link_hi - link_lo + 1.  A range that touches no chain: every field 0.  eq + x + src_gap + src_open = src_hi - src_lo and eq + x +
+ *   oth_gap + oth_open = oth_hi - oth_lo.  stats: n_ranges host entries, written only when the call succeeds.  NTS_ERANGE before any
+ *   launch: 2^32 entries, chains, links, pairs or ranges or more (before any array is read), 2^63 bases or more.  NTS_EINVAL before any
+ *   launch: nts_cigar_lift's chain checks; pair_first not nondecreasing from 0 to n_links.  NTS_EINVAL after the launch, stats
+ *   untouched, the first that applies, the smallest offender named: "the entries of chain ... are no CIGAR of its lengths"; "link ...
+ *   is no placement of its chain" (chain >= n_chains, reserved not 0, a chain without entries, a chain with more than one link -- each
+ *   of its links --, overlap or disorder against the link in front of it in its pair, a0 + len_a or b0 + len_b >= 2^63); "range ... is
+ *   no range of a pair".  No range: the entries and links are checked, no search is launched, nothing is written.  nts_cigar_lift_stats'
+ *   scan and check, one lane per link for the placements and the chains' totals, a minimum reduction and one exclusive scan over the
+ *   links (timer "lift_pairs_scan"); one lane per range makes two binary searches over its pair's links and two over the end chains'
+ *   entries and stores one 128-byte record, a minimum reduction (timer "lift_pairs_search").  On the context's stream, in its
+ *   workspace; no atomic, no launch per pair, chain or range, no floating point: the same input gives the same bytes.
+ *   docs/design/04_27_lift_joined.md; csrc/nts_cigar.inc; ntsynt_amd/assess.py lift_joined_table, `ntSynt --lift-join`,
+ *   `bin/ntsynt_block_stats --lift-joined-out`. */
+typedef struct
+{
+  uint32_t chain, reserved;
+  uint64_t a0, b0;
+} nts_lift_link;
+typedef struct
+{
+  uint32_t pair, side;
+  uint64_t lo, hi;
+} nts_pair_range;
+typedef struct
+{
+  uint64_t src_lo, src_hi, oth_lo, oth_hi, eq, x, src_gap, oth_gap, src_open, oth_open;
+  uint32_t src_gaps, oth_gaps, link_lo, link_hi, n_links, reserved;
+  uint64_t reserved2[3];
+} nts_pair_stats;
+int nts_cigar_lift_pairs(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains,
+                         const nts_lift_link* links, uint64_t n_links, const uint64_t* pair_first, uint64_t n_pairs,
+                         const nts_pair_range* ranges, uint64_t n_ranges, nts_pair_stats* stats);
+
 /* ---- the cg:Z: and cs:Z: texts of the chains' CIGARs: block alignments with --paf-cs ------------------------------------------
  * nts_cigar_text: cigar, chains as nts_cigar_build returns them (entries need not be maximal runs), but the chains must TILE the
  *   entries: first[0] = 0, first[c + 1] = first[c] + n_cig[c], the last chain ends at n_cigar.  spans = n_chains of {pos_a, pos_b,

@@ -112,6 +112,22 @@ class LiftStats(ctypes.Structure):
     _fields_ = [(n, u64) for n in ("oth_lo", "oth_hi", "eq", "x", "src_gap", "oth_gap")] + [("src_gaps", u32), ("oth_gaps", u32), ("reserved", u64)]
 
 
+class LiftLink(ctypes.Structure):
+    "nts_lift_link: where one chain lies in the oriented offsets of its pair (nts_cigar_lift_pairs)"
+    _fields_ = [("chain", u32), ("reserved", u32), ("a0", u64), ("b0", u64)]
+
+
+class PairRange(ctypes.Structure):
+    "nts_pair_range: the bases lo .. hi - 1 of one side of a pair (nts_cigar_lift_pairs)"
+    _fields_ = [("pair", u32), ("side", u32), ("lo", u64), ("hi", u64)]
+
+
+class PairStats(ctypes.Structure):
+    "nts_pair_stats: the joined span of a range over the chains of a pair, its columns by kind and the open bases between the chains (nts_cigar_lift_pairs)"
+    _fields_ = [(n, u64) for n in ("src_lo", "src_hi", "oth_lo", "oth_hi", "eq", "x", "src_gap", "oth_gap", "src_open", "oth_open")] + \
+               [(n, u32) for n in ("src_gaps", "oth_gaps", "link_lo", "link_hi", "n_links", "reserved")] + [("reserved2", u64 * 3)]
+
+
 class MxList(ctypes.Structure):
     _fields_ = [("h1", c_vp), ("rec", c_vp), ("pos", c_vp), ("keep", c_vp), ("list_id", c_vp), ("n", u64)]
 
@@ -282,6 +298,7 @@ SYMBOLS = [
     ("nts_cigar_lift", ctypes.c_int, [c_vp, c_vp, u64, c_vp, u64, c_vp, u64, c_vp]),
     ("nts_cigar_text", ctypes.c_int, [c_vp, c_vp, u64, c_vp, u64, c_vp, c_vp, c_vp, ctypes.POINTER(c_vp), c_vp, ctypes.POINTER(c_vp), c_vp]),
     ("nts_cigar_lift_stats", ctypes.c_int, [c_vp, c_vp, u64, c_vp, u64, c_vp, u64, c_vp]),
+    ("nts_cigar_lift_pairs", ctypes.c_int, [c_vp, c_vp, u64, c_vp, u64, c_vp, u64, c_vp, u64, c_vp, u64, c_vp]),
     ("nts_genome_valid_bases", ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(Interval), u64, c_vp]),
     ("nts_minhash_pairs", ctypes.c_int, [c_vp, u32, c_vp, c_vp, u64, c_vp, c_vp, u64, c_vp, c_vp]),
     ("nts_graph_build", ctypes.c_int, [c_vp, u32, ctypes.POINTER(MxList), ctypes.POINTER(Graph)]),

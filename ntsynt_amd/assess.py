@@ -1088,14 +1088,75 @@ def lift_ranges(queries, overlaps, wanted=None):
     return ranges, which
 
 
+LIFT_JOINED_COLUMNS = LIFT_COLUMNS[:11] + ("chains", "first_ch", "last_ch", "src_start", "src_end", "matches", "mismatches", "src_gap_bases", "to_gap_bases",
+                                           "src_gaps", "to_gaps", "src_open_bases", "to_open_bases", "columns", "identity", "status")
+PAIR_STATS_FIELDS = ("eq", "x", "src_gap", "oth_gap", "src_gaps", "oth_gaps", "src_open", "oth_open")   # of PAIR_STATS_DTYPE, in the order of matches .. to_open_bases
+
+
+def lift_pair_ranges(pairs, intervals):
+    """The join of the pairs' source hulls with the intervals, for nts_cigar_lift_pairs.  pairs: dict, one entry per pair with a linked
+    chain -- `side` (0: the source is line a, the target; 1: line b, the query), `flip` (the pair is `-`), `contig` (the source contig,
+    list of str), `origin` (the source interval's start on the forward strand; for side 1 of a `-` pair its END: the pair's oriented
+    offset u of a forward position p is p - origin, there origin - p, paf_row's mirroring) and `h0`, `h1`: the oriented hull [first
+    link's start, last link's end) on the source side.  intervals: read_bed's dict.  Every (interval, pair) of one contig whose
+    interval reaches the hull makes one range (pair, side, lo, hi): the interval in oriented offsets, mirrored inside the source
+    interval where the offsets run backwards, clipped to the hull.  Returns (ranges, which): a PAIR_RANGE_DTYPE array with `pair` = the
+    index into `pairs`, and the intervals they belong to.  Per pair two searchsorted over the contig's intervals (sorted by start
+    once): a Python loop runs over pairs and contigs, never over intervals, chains or ranges."""
+    import numpy as np
+    from .device import PAIR_RANGE_DTYPE
+    side, flip = np.asarray(pairs["side"], dtype=np.int64), np.asarray(pairs["flip"], dtype=bool)
+    origin, h0, h1 = (np.asarray(pairs[f], dtype=np.int64) for f in ("origin", "h0", "h1"))
+    start, end = np.asarray(intervals["start"], dtype=np.int64), np.asarray(intervals["end"], dtype=np.int64)
+    mirrored = (side == 1) & flip
+    f0, f1 = np.where(mirrored, origin - h1, origin + h0), np.where(mirrored, origin - h0, origin + h1)     # the hull on the forward strand
+    on_contig = {}                                            # source contig -> its intervals by start, those starts, the running maximum of their ends
+    names = np.array(intervals["contig"], dtype=object)
+    for c in set(pairs["contig"]):
+        mine = np.flatnonzero(names == c)
+        mine = mine[np.argsort(start[mine], kind="stable")]
+        on_contig[c] = (mine, start[mine], np.maximum.accumulate(end[mine]) if mine.size else end[mine])
+    which, pair_of = [], []
+    for p in range(side.size):
+        if h0[p] >= h1[p]:
+            continue
+        by_start, starts, ends_so_far = on_contig[pairs["contig"][p]]
+        mine = by_start[np.searchsorted(ends_so_far, f0[p], side="right"):np.searchsorted(starts, f1[p], side="left")]
+        mine = np.sort(mine[end[mine] > f0[p]])
+        which.append(mine)
+        pair_of.append(np.full(mine.size, p, dtype=np.int64))
+    which = np.concatenate(which) if which else np.zeros(0, dtype=np.int64)
+    pair_of = np.concatenate(pair_of) if pair_of else np.zeros(0, dtype=np.int64)
+    lo, hi = np.maximum(start[which], f0[pair_of]), np.minimum(end[which], f1[pair_of])      # (lo < hi: the interval reaches the hull)
+    ranges = np.zeros(which.size, dtype=PAIR_RANGE_DTYPE)
+    ranges["pair"], ranges["side"] = pair_of, side[pair_of]
+    ranges["lo"] = np.where(mirrored[pair_of], origin[pair_of] - hi, lo - origin[pair_of])
+    ranges["hi"] = np.where(mirrored[pair_of], origin[pair_of] - lo, hi - origin[pair_of])
+    return ranges, which
+
+
+def lift_joined_table(rows, k, rate, band, max_len, max_edits=0, ends=None):
+    "TSV of block_lift_joined's rows: LIFT_JOINED_COLUMNS; line order, status, the `unmapped` line and the footer are lift_table's"
+    return lift_table(rows, k, rate, band, max_len, max_edits, ends, columns=LIFT_JOINED_COLUMNS)
+
+
 class _Lifter:
     """block_lift's state over the rounds of the alignment pass: per round the spans, ONE nts_cigar_lift and the rows' arrays.  stats: a
-    bool per interval, or None -- per round also ONE nts_cigar_lift_stats for all overlaps of the intervals it marks (block_lift_identity)"""
+    bool per interval, or None -- per round also ONE nts_cigar_lift_stats for all overlaps of the intervals it marks (block_lift_identity).
+    joined: a bool per interval, or None -- per round also ONE nts_cigar_lift_pairs for the intervals it marks and the pairs they reach
+    (block_lift_joined); per_chain=False: that call alone, neither of the per-chain ones."""
 
-    def __init__(self, genomes_by_name, blocks, source, intervals, stats=None):
+    def __init__(self, genomes_by_name, blocks, source, intervals, stats=None, joined=None, per_chain=True):
         if source not in genomes_by_name:
             raise ValueError(f"--lift-genome {source} is not among the genomes {sorted(genomes_by_name)}")
         self.blocks, self.source, self.intervals, self.stats = blocks, source, intervals, stats
+        self.joined, self.per_chain, self.joined_parts, self.joined_sorted = joined, per_chain, [], None
+        if joined is not None:                                # the marked intervals, as lift_pair_ranges reads them, and which they are
+            import numpy as np
+            self.joined_which = np.flatnonzero(np.asarray(joined, dtype=bool))
+            self.joined_intervals = {"contig": [intervals["contig"][j] for j in self.joined_which.tolist()],
+                                     "start": np.asarray(intervals["start"], dtype=np.int64)[self.joined_which],
+                                     "end": np.asarray(intervals["end"], dtype=np.int64)[self.joined_which]}
         self.contigs = None                                   # the source genome's records, once it was resident
         self.parts, self.info = [], {}                        # per round lift_rows' arrays with pair and ch; pair -> its columns
         self.index_of = None                                  # (line a, line b) -> the pair's place in block_identity's order
@@ -1127,6 +1188,10 @@ class _Lifter:
             self.info[index_of[(la, lb)]] = (self.blocks[la].block_id, other.genome, other.contig, "-" if self.blocks[la].strand != self.blocks[lb].strand else "+")
         spans = {"pair": pair, "chain": order, "side": np.full(order.size, side), "flip": flip, "contig": [mine[q] for q in line.tolist()],
                  "s0": q0 if side else t0, "s1": q1 if side else t1, "o0": t0 if side else q0, "o1": t1 if side else q1}
+        if self.joined is not None:
+            self._join_round(ctx, a, side, order, line, x0, x1, y0, y1, mine)
+        if not self.per_chain:
+            return
         queries, overlaps = lift_queries(spans, self.intervals)
         hits = ctx.cigar_lift(a.cigar, a.records, queries)    # (one call per round, for all pairs in which the source takes part)
         rows = lift_rows(spans, overlaps, hits)
@@ -1144,9 +1209,58 @@ class _Lifter:
                 rows[f][which] = stats[f].astype(np.int64)
         self.parts.append(dict(rows, pair=pair[rows["span"]], ch=chains["ch"][order][rows["span"]]))
 
-    def rows(self, genomes_by_name, begin=0, end=None, identity=False):
-        "the lines of the intervals begin .. end - 1 (all): LIFT_COLUMNS, or with identity LIFT_IDENTITY_COLUMNS"
+    def _join_round(self, ctx, a, side, order, line, x0, x1, y0, y1, mine):
+        """ONE nts_cigar_lift_pairs for the round: the chains with entries as links in (pair, ch) order at their oriented offsets -- moved
+        per pair so that none is negative (a flank may leave the interval) --, one range per marked interval and pair whose hull it
+        reaches (lift_pair_ranges); the records with a link, in forward coordinates, go to joined_parts"""
         import numpy as np
+        from .device import LIFT_LINK_DTYPE
+        r, n_lines = a.round, len(a.round.lines)
+        linked = np.flatnonzero(np.asarray(a.records["n_cig"]).astype(np.int64)[order] > 0)   # (a chain without entries is not linked)
+        linked = linked[np.lexsort((a.chains["ch"][order][linked], line[linked]))]              # link order: by pair, ascending by ch
+        of_line = line[linked]
+        pair_first = np.searchsorted(of_line, np.arange(n_lines + 1)).astype(np.int64)
+        has = pair_first[1:] > pair_first[:-1]
+        first, last = np.minimum(pair_first[:-1], max(linked.size - 1, 0)), np.maximum(pair_first[1:] - 1, 0)
+        lx0, lx1, ly0, ly1 = (v[linked] for v in (x0, x1, y0, y1))
+        base_x = np.where(has, np.minimum(lx0[first], 0), 0) if linked.size else np.zeros(n_lines, dtype=np.int64)
+        base_y = np.where(has, np.minimum(ly0[first], 0), 0) if linked.size else np.zeros(n_lines, dtype=np.int64)
+        links = np.zeros(linked.size, dtype=LIFT_LINK_DTYPE)
+        links["chain"], links["a0"], links["b0"] = order[linked], lx0 - base_x[of_line], ly0 - base_y[of_line]
+        i = np.array([i for _, _, i in r.lines], dtype=np.int64)
+        flip = r.flip[i].astype(bool) if n_lines else np.zeros(0, dtype=bool)
+        origin_a = r.iv_a[i, 1].astype(np.int64) + base_x if n_lines else base_x
+        origin_b = np.where(flip, r.iv_b[i, 2].astype(np.int64) - base_y, r.iv_b[i, 1].astype(np.int64) + base_y) if n_lines else base_y
+        s0, s1 = (ly0, ly1) if side else (lx0, lx1)
+        base = base_y if side else base_x
+        hull = (np.where(has, s0[first] - base, 0), np.where(has, s1[last] - base, 0)) if linked.size else (base, base)
+        pairs = {"side": np.full(n_lines, side), "flip": flip, "contig": mine, "origin": origin_b if side else origin_a, "h0": hull[0], "h1": hull[1]}
+        ranges, which = lift_pair_ranges(pairs, self.joined_intervals)
+        stats = ctx.cigar_lift_pairs(a.cigar, a.records, links, pair_first.astype(np.uint64), ranges)     # (one call per round, for all pairs of the source)
+        keep = np.flatnonzero(stats["n_links"] > 0)
+        st, q = stats[keep], ranges["pair"][keep].astype(np.int64)
+        got = {f: st[f].astype(np.int64) for f in ("src_lo", "src_hi", "oth_lo", "oth_hi") + PAIR_STATS_FIELDS}
+        both = got["eq"] + got["x"]
+        if np.any(both + got["src_gap"] + got["src_open"] != got["src_hi"] - got["src_lo"]) or \
+                np.any(both + got["oth_gap"] + got["oth_open"] != got["oth_hi"] - got["oth_lo"]):
+            raise RuntimeError("the counts of a joined interval do not add up to its two spans")
+        oa, ob, fl = origin_a[q], origin_b[q], flip[q]
+        b_lo, b_hi = ("src_lo", "src_hi") if side else ("oth_lo", "oth_hi")         # which of the two spans lies on line b: mirrored for a `-` pair
+        a_lo, a_hi = ("oth_lo", "oth_hi") if side else ("src_lo", "src_hi")
+        on_a = (oa + got[a_lo], oa + got[a_hi])
+        on_b = (np.where(fl, ob - got[b_hi], ob + got[b_lo]), np.where(fl, ob - got[b_lo], ob + got[b_hi]))
+        src, to = (on_b, on_a) if side else (on_a, on_b)
+        chs = a.chains["ch"][order][linked]
+        index_of = self.index_of
+        pair_id = np.array([index_of[(la, lb)] for la, lb, _ in r.lines], dtype=np.int64)
+        part = {"interval": self.joined_which[which[keep]], "pair": pair_id[q], "chains": st["n_links"].astype(np.int64),
+                "first_ch": chs[st["link_lo"].astype(np.int64)], "last_ch": chs[st["link_hi"].astype(np.int64)], "src_start": src[0], "src_end": src[1],
+                "to_start": to[0], "to_end": to[1]}
+        part.update({f: got[f] for f in PAIR_STATS_FIELDS})
+        self.joined_parts.append(part)
+
+    def _known_contigs(self, genomes_by_name):
+        "every interval lies on a record of the source genome (ValueError otherwise)"
         if self.contigs is None:                              # (the source is in no pair: its records are read for the contig check alone)
             g = genomes_by_name[self.source]
             loaded = callable(g)
@@ -1154,10 +1268,48 @@ class _Lifter:
             self.contigs = set(g.names)
             if loaded:
                 g.free()
-        iv = self.intervals
-        for c in dict.fromkeys(iv["contig"]):
+        for c in dict.fromkeys(self.intervals["contig"]):
             if c not in self.contigs:
                 raise ValueError(f"genome {self.source} has no record {c} (--block-lift)")
+
+    def joined_rows(self, genomes_by_name, begin=0, end=None):
+        "the lines of the intervals begin .. end - 1 (all) of the joined table: LIFT_JOINED_COLUMNS"
+        import numpy as np
+        self._known_contigs(genomes_by_name)
+        iv = self.intervals
+        fields = ("interval", "pair", "chains", "first_ch", "last_ch", "src_start", "src_end", "to_start", "to_end") + PAIR_STATS_FIELDS
+        if self.joined_sorted is None:
+            got = {f: np.concatenate([p[f] for p in self.joined_parts]) if self.joined_parts else np.zeros(0, dtype=np.int64) for f in fields}
+            order = np.lexsort((got["pair"], got["interval"]))
+            self.joined_sorted = {f: v[order] for f, v in got.items()}
+        end = len(iv["contig"]) if end is None else end
+        o, stop = (int(v) for v in np.searchsorted(self.joined_sorted["interval"], [begin, end]))
+        got = {f: v[o:stop].tolist() for f, v in self.joined_sorted.items()}
+        starts, ends, out, o, n = iv["start"].tolist(), iv["end"].tolist(), [], 0, stop - o
+        absent = {c: "." for c in LIFT_JOINED_COLUMNS[5:-1]}
+        for j in range(begin, end):
+            head = {"genome": self.source, "contig": iv["contig"][j], "start": starts[j], "end": ends[j], "name": iv["name"][j]}
+            if o == n or got["interval"][o] != j:
+                out.append(dict(head, **absent, status="unmapped"))
+            while o < n and got["interval"][o] == j:
+                block_id, to_genome, to_contig, sign = self.info[got["pair"][o]]
+                counts = [got[f][o] for f in PAIR_STATS_FIELDS]
+                columns = sum(counts[:4])                     # (a link was reached: at least one column)
+                v = (1000000 * counts[0]) // columns
+                row = dict(head, block_id=block_id, to_genome=to_genome, to_contig=to_contig, to_start=got["to_start"][o], to_end=got["to_end"][o],
+                           orientation=sign, chains=got["chains"][o], first_ch=got["first_ch"][o], last_ch=got["last_ch"][o], src_start=got["src_start"][o],
+                           src_end=got["src_end"][o], columns=columns, identity=f"{v // 1000000}.{v % 1000000:06d}",
+                           status="full" if (got["src_start"][o], got["src_end"][o]) == (starts[j], ends[j]) else "partial")
+                row.update(zip(LIFT_JOINED_COLUMNS[16:24], counts))
+                out.append(row)
+                o += 1
+        return out
+
+    def rows(self, genomes_by_name, begin=0, end=None, identity=False):
+        "the lines of the intervals begin .. end - 1 (all): LIFT_COLUMNS, or with identity LIFT_IDENTITY_COLUMNS"
+        import numpy as np
+        self._known_contigs(genomes_by_name)
+        iv = self.intervals
         if self.sorted is None:
             fields = ("interval", "pair", "ch", "lo", "hi", "to_start", "to_end") + (LIFT_STATS_FIELDS if self.stats is not None else ())
             got = {f: np.concatenate([p[f] for p in self.parts]) if self.parts else np.zeros(0, dtype=np.int64) for f in fields}
@@ -1250,6 +1402,73 @@ def block_lift_identity(ctx, genomes_by_name, blocks, source, intervals, k=IDENT
     lifted, identity = lifter.results(genomes_by_name)
     identity = identity[0] if one else identity
     return identity if lift is None else (lifted, identity)
+
+
+def block_lifts(ctx, genomes_by_name, blocks, source, k=IDENTITY_K, rate=IDENTITY_RATE, band=IDENTITY_BAND, max_len=IDENTITY_MAX_LEN, max_edits=0, ends=None,
+                lift=None, identity=(), joined=(), paf=False, cs=False):
+    """Every table of the lift from ONE pass over _alignment_rounds, the joined ones among them: lift = a dict of intervals for block_lift's
+    rows, identity = dicts for block_lift_identity's rows, joined = dicts for the joined rows (LIFT_JOINED_COLUMNS), paf: block_alignments'
+    lines as well (cs: with the cs:Z: tag).  A dict that is given more than once is joined once and read for every table it serves.  The
+    sets become ONE list of intervals, so a round makes at most one nts_cigar_lift, one nts_cigar_lift_stats and one
+    nts_cigar_lift_pairs; the per-chain calls are made only when lift or identity asks for them.  Returns a dict: `paf` and `lift` (rows
+    or None), `identity` and `joined` (a list of rows per set)."""
+    import numpy as np
+    message = check_identity_parameters(int(k), int(rate), int(band), int(max_len), int(max_edits)) or \
+        (check_ends_parameters(*(int(v) for v in ends)) if ends is not None else None)
+    if message:
+        raise ValueError(message)
+    every = []
+
+    def place(one):
+        for at, other in enumerate(every):
+            if other is one:
+                return at
+        every.append(one)
+        return len(every) - 1
+    at_lift = place(lift) if lift is not None else None
+    at_identity, at_joined = [place(one) for one in identity], [place(one) for one in joined]
+    cut = np.concatenate([[0], np.cumsum([len(one["contig"]) for one in every])]).astype(np.int64).tolist()
+    spans = list(zip(cut[:-1], cut[1:]))
+    counted, joining = np.zeros(cut[-1], dtype=bool), np.zeros(cut[-1], dtype=bool)
+    for mask, places in ((counted, at_identity), (joining, at_joined)):
+        for at in places:
+            mask[spans[at][0]:spans[at][1]] = True
+    intervals = {"contig": [c for one in every for c in one["contig"]], "name": [n for one in every for n in one["name"]],
+                 "start": np.concatenate([np.asarray(one["start"], dtype=np.int64) for one in every] + [np.zeros(0, dtype=np.int64)]),
+                 "end": np.concatenate([np.asarray(one["end"], dtype=np.int64) for one in every] + [np.zeros(0, dtype=np.int64)])}
+    lifter = _Lifter(genomes_by_name, blocks, source, intervals, stats=counted if at_identity else None, joined=joining if at_joined else None,
+                     per_chain=lift is not None or bool(at_identity))
+    pairs, length, found = [], {}, {}
+    for a in _alignment_rounds(ctx, genomes_by_name, blocks, int(k), int(rate), int(band), int(max_len), int(max_edits), ends, pairs, length,
+                               only=None if paf else source, cs=bool(cs) and bool(paf)):
+        if paf:
+            _round_paf_rows(blocks, a, found)
+        lifter.add_round(ctx, a, pairs)
+    return {"paf": [row for p in pairs for row in found[p]] if paf else None,
+            "lift": lifter.rows(genomes_by_name, *spans[at_lift]) if lift is not None else None,
+            "identity": [lifter.rows(genomes_by_name, *spans[at], identity=True) for at in at_identity],
+            "joined": [lifter.joined_rows(genomes_by_name, *spans[at]) for at in at_joined]}
+
+
+def block_lift_joined(ctx, genomes_by_name, blocks, source, intervals, k=IDENTITY_K, rate=IDENTITY_RATE, band=IDENTITY_BAND, max_len=IDENTITY_MAX_LEN,
+                      max_edits=0, ends=None):
+    """One line per interval and PAIR of block lines: for every interval (read_bed's or window_intervals' dict) of the genome `source`
+    and every pair in which it reaches a chain, the span joined across the pair's chains -- from the first to the last base of the
+    interval that a chain holds --, the alignment counts over every column between the two, the chains between them whole, and the bases
+    of the stretches between the chains that no column covers (nts_cigar_lift_pairs; per round ONE call for all intervals and pairs, and
+    no per-chain call), as dicts of LIFT_JOINED_COLUMNS: chains = the chains reached, first_ch / last_ch their numbers, columns = the
+    sum of the four counts, identity = 10^6 matches // columns as d.dddddd; an interval that reaches no chain has `.` in block_id ..
+    identity and status `unmapped`.  docs/design/04_27_lift_joined.md."""
+    import numpy as np
+    message = check_identity_parameters(int(k), int(rate), int(band), int(max_len), int(max_edits)) or \
+        (check_ends_parameters(*(int(v) for v in ends)) if ends is not None else None)
+    if message:
+        raise ValueError(message)
+    pairs, length = [], {}
+    lifter = _Lifter(genomes_by_name, blocks, source, intervals, joined=np.ones(len(intervals["contig"]), dtype=bool), per_chain=False)
+    for a in _alignment_rounds(ctx, genomes_by_name, blocks, int(k), int(rate), int(band), int(max_len), int(max_edits), ends, pairs, length, only=source):
+        lifter.add_round(ctx, a, pairs)
+    return lifter.joined_rows(genomes_by_name)
 
 
 def block_lift(ctx, genomes_by_name, blocks, source, intervals, k=IDENTITY_K, rate=IDENTITY_RATE, band=IDENTITY_BAND, max_len=IDENTITY_MAX_LEN,
@@ -1390,6 +1609,9 @@ def main(argv=None):
     p.add_argument("--lift-windows", help="with --lift-genome and --lift-windows-out: the same counts for windows of this many bases over every record "
                    "of that genome", type=int)
     p.add_argument("--lift-windows-out", help="file for the windows of --lift-windows")
+    p.add_argument("--lift-joined-out", help="with --lift-bed and --lift-genome: file for the intervals joined per pair of block lines (one line per "
+                   "interval and pair: the span across the pair's chains, its counts and the bases between the chains; GPU)")
+    p.add_argument("--lift-windows-joined-out", help="with --lift-windows and --lift-genome: the same joined table for the windows")
     p.add_argument("--ends-max-len", help=f"longest flank that is extended, 1..65535 [{ENDS_MAX_LEN}]", type=int, default=ENDS_MAX_LEN)
     p.add_argument("--ends-max-edits", help=f"most edits within one flank, 1..1023 [{ENDS_MAX_EDITS}]", type=int, default=ENDS_MAX_EDITS)
     p.add_argument("--ends-penalty", help=f"what an edit costs the extension's score, against 2 for a matching pair of bases, 3..255 [{ENDS_PENALTY}]",
@@ -1417,7 +1639,11 @@ def main(argv=None):
         p.error("--paf-cs adds the cs:Z: tag to the records of --paf-out: it needs that switch")
     if args.lift_identity_out and not args.lift_bed:
         p.error("--lift-identity-out needs the intervals: --lift-bed (and --lift-genome)")
-    if (args.lift_windows is not None) != bool(args.lift_windows_out):
+    if args.lift_joined_out and not (args.lift_bed and args.lift_genome):
+        p.error("--lift-joined-out needs the intervals and their genome: --lift-bed and --lift-genome")
+    if args.lift_windows_joined_out and args.lift_windows is None:
+        p.error("--lift-windows-joined-out needs the windows: --lift-windows W (and --lift-genome)")
+    if (args.lift_windows is not None) != bool(args.lift_windows_out or args.lift_windows_joined_out):
         p.error("--lift-windows and --lift-windows-out go together")
     if args.lift_windows is not None:
         if not args.lift_genome:
@@ -1425,8 +1651,9 @@ def main(argv=None):
         if args.lift_windows < 1:
             p.error("--lift-windows: a window has at least one base")
     if args.lift_bed or args.lift_genome or args.lift_out:
-        if not (args.lift_genome and (args.lift_windows_out or (args.lift_bed and (args.lift_out or args.lift_identity_out))) and
-                bool(args.lift_bed) == bool(args.lift_out or args.lift_identity_out)):
+        if not (args.lift_genome and (args.lift_windows_out or args.lift_windows_joined_out or
+                                      (args.lift_bed and (args.lift_out or args.lift_identity_out or args.lift_joined_out))) and
+                bool(args.lift_bed) == bool(args.lift_out or args.lift_identity_out or args.lift_joined_out)):
             p.error("--lift-bed, --lift-genome and --lift-out go together")
         if not args.fastas:
             p.error("--lift-out needs the genomes: --fastas")
@@ -1482,7 +1709,24 @@ def main(argv=None):
                 end_rows = block_ends(ctx, loaders, read_blocks(args.tsv), *e_args)
             with open(args.ends_out, "w", encoding="utf-8") as fh:
                 fh.write(ends_table(end_rows, *e_args))
-        if args.lift_identity_out or args.lift_windows_out:   # (one pass gives every file of the lift, and the PAF)
+        if args.lift_joined_out or args.lift_windows_joined_out:                              # (one pass gives every file of the lift, the joined ones and the PAF)
+            a_args = dict(max_edits=args.identity_max_edits, ends=(args.ends_max_len, args.ends_max_edits, args.ends_penalty) if args.ends_out else None)
+            intervals = read_bed(args.lift_bed) if args.lift_bed else None
+            windows = window_intervals(record_sizes(loaders, args.lift_genome), args.lift_windows) if args.lift_windows is not None else None
+            got = block_lifts(ctx, loaders, read_blocks(args.tsv), args.lift_genome, *id_args, **a_args, lift=intervals if args.lift_out else None,
+                              identity=([intervals] if args.lift_identity_out else []) + ([windows] if args.lift_windows_out else []),
+                              joined=([intervals] if args.lift_joined_out else []) + ([windows] if args.lift_windows_joined_out else []),
+                              paf=bool(args.paf_out), cs=args.paf_cs)
+            files = [(args.paf_out, paf_table(got["paf"]))] if args.paf_out else []
+            files += [(args.lift_out, lift_table(got["lift"], *id_args, **a_args))] if args.lift_out else []
+            files += [(path, lift_identity_table(rows, *id_args, **a_args))
+                      for path, rows in zip([f for f in (args.lift_identity_out, args.lift_windows_out) if f], got["identity"])]
+            files += [(path, lift_joined_table(rows, *id_args, **a_args))
+                      for path, rows in zip([f for f in (args.lift_joined_out, args.lift_windows_joined_out) if f], got["joined"])]
+            for path, text_ in files:
+                with open(path, "w", encoding="utf-8") as fh:
+                    fh.write(text_)
+        elif args.lift_identity_out or args.lift_windows_out:   # (one pass gives every file of the lift, and the PAF)
             a_args = dict(max_edits=args.identity_max_edits, ends=(args.ends_max_len, args.ends_max_edits, args.ends_penalty) if args.ends_out else None)
             intervals = read_bed(args.lift_bed) if args.lift_bed else None
             sets = ([intervals] if args.lift_identity_out else []) + \

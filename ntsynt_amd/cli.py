@@ -108,6 +108,9 @@ def build_parser():
                    "bases and the identity", action="store_true")
     p.add_argument("--lift-windows", metavar="W", help="with --lift-genome NAME (which it needs), write <prefix>.block_windows.tsv: the same columns for\n"
                    "windows of W bases over every record of NAME -- identity along the genome; works with or without --block-lift", type=int)
+    p.add_argument("--lift-join", help="with --block-lift BED and/or --lift-windows W (it needs one of them), write <prefix>.block_lift_joined.tsv\n"
+                   "and/or <prefix>.block_windows_joined.tsv: one line per interval and PAIR of block lines, the span joined across the pair's\n"
+                   "chains, the counts over all of it and the bases of the stretches between the chains that no alignment covers", action="store_true")
     p.add_argument("--ends-max-len", help="longest flank that is extended, 1..65535 [4096]", type=int, default=4096)
     p.add_argument("--ends-max-edits", help="most edits within one flank, 1..1023 [255]", type=int, default=255)
     p.add_argument("--ends-penalty", help="what an edit costs the extension's score, against 2 for a matching pair of bases, 3..255 [6]", type=int,
@@ -259,6 +262,14 @@ def check_reports(parser, args):
             parser.error("--lift-identity works from the genomes resident on one GPU: run it on one rank, or lift through the finished run with "
                          "ntsynt_block_stats --tsv <prefix>.synteny_blocks.tsv --fai ... --fastas ... --lift-bed BED --lift-genome NAME "
                          "--lift-identity-out <prefix>.block_lift_identity.tsv")
+    if args.lift_join:
+        if not args.block_lift and args.lift_windows is None:
+            parser.error("--lift-join joins the lines of --block-lift BED and/or --lift-windows W per pair of block lines: it needs one of them")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            parser.error("--lift-join works from the genomes resident on one GPU: run it on one rank, or join through the finished run with "
+                         "ntsynt_block_stats --tsv <prefix>.synteny_blocks.tsv --fai ... --fastas ... --lift-genome NAME --lift-bed BED "
+                         "--lift-joined-out <prefix>.block_lift_joined.tsv [--lift-windows W --lift-windows-joined-out "
+                         "<prefix>.block_windows_joined.tsv]")
     if args.lift_windows is not None:
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             parser.error("--lift-windows works from the genomes resident on one GPU: run it on one rank, or count through the finished run with "
@@ -412,6 +423,12 @@ def main(argv=None):
             (f", ends_max_len {args.ends_max_len}, ends_max_edits {args.ends_max_edits}, ends_penalty {args.ends_penalty}" if args.block_ends else "") + ")"
             for stage, what, on in (("block_lift_identity", args.block_lift, args.lift_identity),
                                     ("block_windows", f"windows of {args.lift_windows}", args.lift_windows is not None)) if on] + \
+           ([f"block_lift_joined (lift_pairs_scan, lift_pairs_search; " +
+             " and ".join(([args.block_lift] if args.block_lift else []) + ([f"windows of {args.lift_windows}"] if args.lift_windows is not None else [])) +
+             f" on {args.lift_genome}; k {args.identity_k}, rate {args.identity_rate}, band {args.identity_band}, max_len {args.identity_max_len}, "
+             f"max_edits {args.identity_max_edits}" +
+             (f", ends_max_len {args.ends_max_len}, ends_max_edits {args.ends_max_edits}, ends_penalty {args.ends_penalty}" if args.block_ends else "") + ")"]
+            if args.lift_join else []) + \
            (["gaps"] if args.gaps else []) + \
            (["gap_links"] if args.gap_links else []) + (["gap_block_links"] if args.gap_block_links else []) + \
            (["gap_copies"] if args.gap_copies else []) + (["gap_copy_sites"] if args.gap_copy_sites else []) + \
@@ -474,6 +491,8 @@ def _run(pipeline, fastas, args, device, quiet):
         more["block_lift_identity"] = (args.block_lift,) + lift_args
     if args.lift_windows is not None:
         more["block_windows"] = (args.lift_windows,) + lift_args
+    if args.lift_join:
+        more["block_lift_joined"] = lift_args
     pipeline.run(fastas, **more, k=args.k, w=args.w, fpr=args.fpr, prefix=args.prefix, w_rounds=args.w_rounds,
                  indel=args.indel, merge=args.merge, block_size=args.block_size, common=not args.no_common,
                  simplify=not args.no_simplify_graph, device=device, benchmark=args.benchmark,

@@ -973,3 +973,309 @@ int cigar_text_run(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const 
   }
   return NTS_OK;
 }
+
+// ---- one span and its counts per range and PAIR of chains (nts_cigar_lift_pairs; ntsynt_amd/assess.py lift_joined_table) ----
+// docs/design/04_27_lift_joined.md.  Input: CIGAR entries and chain records as for nts_cigar_lift_stats, LINKS {chain, a0, b0} that place
+// chains in the oriented coordinates of a pair -- pair_first[n_pairs + 1] cuts them into pairs, a pair's links ascend without overlap on
+// both sides -- and ranges {pair, side, lo, hi}: the source bases lo .. hi - 1 of one side of a pair.  The answer counts the pair's
+// columns from the column of the first base of the range that a chain holds to the column of the last one, the chains between the two
+// whole, and the bases of the open stretches between the chains.
+//   1  cig_index_stage with LiftStatOf's five columns; behind its check k_lpair_claim and k_lpair_twice find the chains that are linked
+//      more than once, k_lpair_links -- one lane per link -- validates the link against the records and its predecessor in the pair and
+//      writes its placement and the chain's whole totals, read from the entry prefixes; a minimum reduction names the smallest bad link,
+//      ONE exclusive scan over n_links + 1 elements turns the totals into link prefixes (timer "lift_pairs_scan").
+//   2  k_lpair_ranges: one lane per range; validates it, finds link_lo and link_hi with two binary searches over the pair's links and
+//      the two entries with cig_entry_of, adds the partial head of link_lo, the whole chains between from the link prefixes and the
+//      partial tail of link_hi, and stores one 128 B record; an invalid range stores nothing but its own index in its status word
+//      (timer "lift_pairs_search").
+// No atomic, no launch per pair, chain or range, no floating point, no host loop over links, ranges or entries.
+
+static_assert(sizeof(nts_lift_link) == 24 && sizeof(nts_pair_range) == 24 && sizeof(nts_pair_stats) == 128, "the C ABI's layout");
+constexpr uint64_t LPAIR_MAX_BASE = 1ull << 63;  // a link ends, and a range lies, in front of it
+constexpr uint32_t LPAIR_TWICE = 0xFFFFFFFFu;    // "lpair_owner": the chain has more than one link
+
+struct LpairPlace // a validated link as the range kernel reads it: where its chain's entries lie and what it occupies; n_cig = 0: a bad link
+{
+  uint64_t first, n_cig, a0, a1, b0, b1;
+};
+static_assert(sizeof(LpairPlace) == 48, "six 8-byte words");
+
+struct LpairTotalsOf // element i of the link scan's input: the totals of link i's chain; nothing behind the last link
+{
+  using Tuple = LiftStatTuple; // A bases, B bases, X columns, D columns, I runs | D runs << 32 (the chain's own first entry opens one)
+  const uint64_t* totals;      // five columns of n_links words
+  uint64_t n_links;
+  __host__ __device__ Tuple operator()(uint64_t i) const
+  {
+    if (i >= n_links) return Tuple(0, 0, 0, 0, 0);
+    return Tuple(totals[i], totals[n_links + i], totals[2u * n_links + i], totals[3u * n_links + i], totals[4u * n_links + i]);
+  }
+};
+
+// every link stores its index at its chain: one of a chain's links stays.  Several lanes may store different words to one owner[c]
+// without an atomic: this relies on an aligned 32-bit store being written whole (one of the stored words stays, never a mixture) and on
+// the kernel boundary between this kernel and k_lpair_twice, behind which every lane reads the word that stayed.
+__global__ __launch_bounds__(256) void k_lpair_claim(const nts_lift_link* __restrict__ links, uint64_t n_links, uint64_t n_chains, uint32_t* __restrict__ owner)
+{
+  const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (g >= n_links) return;
+  const uint32_t c = links[g].chain;
+  if (c < n_chains) owner[c] = (uint32_t)g;
+}
+
+// a link that finds another one's index at its chain marks the chain (every writer stores the same word; a link that already reads the
+// mark stores it again)
+__global__ __launch_bounds__(256) void k_lpair_twice(const nts_lift_link* __restrict__ links, uint64_t n_links, uint64_t n_chains, uint32_t* __restrict__ owner)
+{
+  const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (g >= n_links) return;
+  const uint32_t c = links[g].chain;
+  if (c < n_chains && owner[c] != (uint32_t)g) owner[c] = LPAIR_TWICE;
+}
+
+__global__ __launch_bounds__(256) void k_lpair_links(const uint64_t* __restrict__ cigar, uint64_t n_cigar, const nts_cig_chain* __restrict__ chains,
+                                                     uint64_t n_chains, const uint64_t* __restrict__ PA, const uint64_t* __restrict__ PB,
+                                                     const uint64_t* __restrict__ PX, const uint64_t* __restrict__ PD, const uint64_t* __restrict__ PH,
+                                                     const nts_lift_link* __restrict__ links, uint64_t n_links, const uint64_t* __restrict__ pair_first,
+                                                     uint64_t n_pairs, const uint32_t* __restrict__ owner, LpairPlace* __restrict__ place,
+                                                     uint64_t* __restrict__ totals, uint32_t* __restrict__ status)
+{
+  const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (g >= n_links) return;
+  const nts_lift_link lk = links[g];
+  nts_cig_chain ch;
+  // (a chain without entries may not be linked; behind this first + n_cig <= n_cigar and n_cig >= 1)
+  bool ok = lk.reserved == 0 && cig_chain_of(chains, n_chains, lk.chain, 0u, ch) && !cig_chain_beyond(ch, n_cigar) && ch.n_cig != 0;
+  ok = ok && owner[lk.chain] != LPAIR_TWICE; // (lk.chain < n_chains)
+  // (the host refused 2^63 bases or more: a0 + len_a does not wrap behind a0 < 2^63)
+  ok = ok && lk.a0 < LPAIR_MAX_BASE && lk.b0 < LPAIR_MAX_BASE && ch.len_a < LPAIR_MAX_BASE - lk.a0 && ch.len_b < LPAIR_MAX_BASE - lk.b0;
+  // its pair: the last with pair_first <= g (pair_first[0] = 0 <= g < n_links = pair_first[n_pairs]: n_pairs >= 1 here)
+  const uint64_t p = cig_last_at_or_before(n_pairs, g, [pair_first](uint64_t i) { return pair_first[i]; });
+  if (ok && g > pair_first[p]) { // the link in front of it in its pair; one that is bad itself is named instead
+    const nts_lift_link pv = links[g - 1u];
+    nts_cig_chain pc;
+    if (cig_chain_of(chains, n_chains, pv.chain, 0u, pc) && pv.a0 < LPAIR_MAX_BASE && pv.b0 < LPAIR_MAX_BASE && pc.len_a < LPAIR_MAX_BASE - pv.a0 &&
+        pc.len_b < LPAIR_MAX_BASE - pv.b0)
+      ok = lk.a0 >= pv.a0 + pc.len_a && lk.b0 >= pv.b0 + pc.len_b;
+  }
+  uint64_t a = 0, b = 0, x = 0, d = 0, runs = 0;
+  if (ok) {
+    const uint64_t f = ch.first, end = f + ch.n_cig; // f < end <= n_cigar: the prefixes at f, f + 1 and end; cigar[f]
+    a = PA[end] - PA[f];
+    b = PB[end] - PB[f];
+    x = PX[end] - PX[f];
+    d = PD[end] - PD[f];
+    const uint64_t code = cigar[f] & 15u;
+    runs = PH[end] - PH[f + 1u] + (code == CIG_I ? 1ull : code == CIG_D ? 1ull << 32 : 0);
+    place[g] = { f, ch.n_cig, lk.a0, lk.a0 + ch.len_a, lk.b0, lk.b0 + ch.len_b };
+  } else {
+    place[g] = { 0, 0, lk.a0, lk.a0, lk.b0, lk.b0 };
+  }
+  totals[g] = a;
+  totals[n_links + g] = b;
+  totals[2u * n_links + g] = x;
+  totals[3u * n_links + g] = d;
+  totals[4u * n_links + g] = runs;
+  status[g] = ok ? SCRIPT_OK : (uint32_t)g;
+}
+
+__global__ __launch_bounds__(256) void k_lpair_ranges(const uint64_t* __restrict__ cigar, const uint64_t* __restrict__ PA, const uint64_t* __restrict__ PB,
+                                                      const uint64_t* __restrict__ PX, const uint64_t* __restrict__ PD, const uint64_t* __restrict__ PH,
+                                                      const LpairPlace* __restrict__ place, uint64_t n_links, const uint64_t* __restrict__ LA,
+                                                      const uint64_t* __restrict__ LB, const uint64_t* __restrict__ LX, const uint64_t* __restrict__ LD,
+                                                      const uint64_t* __restrict__ LH, const uint64_t* __restrict__ pair_first, uint64_t n_pairs,
+                                                      const nts_pair_range* __restrict__ ranges, uint64_t n_ranges, nts_pair_stats* __restrict__ stats,
+                                                      uint32_t* __restrict__ status)
+{
+  const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (g >= n_ranges) return;
+  const nts_pair_range r = ranges[g];
+  bool valid = r.pair < n_pairs && r.side <= 1u && r.lo < r.hi && r.hi < LPAIR_MAX_BASE;
+  uint64_t l0 = 0, l1 = 0;
+  if (valid) {
+    l0 = pair_first[r.pair];
+    l1 = pair_first[r.pair + 1u];
+    valid = l0 <= l1 && l1 <= n_links; // (the host refused this before the launch: a lane still reads no link outside the array)
+  }
+  if (!valid) {
+    status[g] = (uint32_t)g;
+    return;
+  }
+  status[g] = SCRIPT_OK;
+  const bool side = r.side != 0;
+  auto s0 = [place, side](uint64_t i) { return side ? place[i].b0 : place[i].a0; };
+  auto s1 = [place, side](uint64_t i) { return side ? place[i].b1 : place[i].a1; };
+  // link_lo: the first link of the pair that ends behind lo; link_end: the first at or behind link_lo that starts at or behind hi.  Both
+  // searches keep l0 <= lo_i <= hi_i <= l1 and read place[mid] with lo_i <= mid < hi_i, whatever the links hold.
+  uint64_t lo_i = l0, hi_i = l1;
+  while (lo_i < hi_i) {
+    const uint64_t mid = lo_i + (hi_i - lo_i) / 2u;
+    if (s1(mid) > r.lo) hi_i = mid;
+    else lo_i = mid + 1u;
+  }
+  uint64_t link_lo = lo_i;
+  hi_i = l1;
+  while (lo_i < hi_i) {
+    const uint64_t mid = lo_i + (hi_i - lo_i) / 2u;
+    if (s0(mid) >= r.hi) hi_i = mid;
+    else lo_i = mid + 1u;
+  }
+  uint64_t link_end = lo_i; // l0 <= link_lo <= link_end <= l1
+  // a chain without a base of the source side holds no end column: it counts only between two chains that do.  The two loops are
+  // linear in the src-empty links at either end of the run -- at most the pair's links; chains built from anchors hold bases of both
+  // sides, so they step over nothing there (docs/design/04_27_lift_joined.md)
+  while (link_lo < link_end && s1(link_lo) == s0(link_lo)) ++link_lo;
+  while (link_end > link_lo && s1(link_end - 1u) == s0(link_end - 1u)) --link_end;
+  nts_pair_stats out = {};
+  if (link_lo == link_end) { // the range touches no chain
+    stats[g] = out;
+    return;
+  }
+  const uint64_t link_hi = link_end - 1u; // l0 <= link_lo <= link_hi < l1 <= n_links
+  const LpairPlace p_lo = place[link_lo], p_hi = place[link_hi];
+  if (p_lo.n_cig == 0 || p_hi.n_cig == 0) { // a bad link (the call fails on its status): no entry is read
+    stats[g] = out;
+    return;
+  }
+  const uint64_t* __restrict__ P = side ? PB : PA;
+  const uint64_t* __restrict__ O = side ? PA : PB;
+  const uint64_t s0_lo = side ? p_lo.b0 : p_lo.a0, s1_lo = side ? p_lo.b1 : p_lo.a1, s0_hi = side ? p_hi.b0 : p_hi.a0, s1_hi = side ? p_hi.b1 : p_hi.a1;
+  const uint64_t o0_lo = side ? p_lo.a0 : p_lo.b0, o1_lo = side ? p_lo.a1 : p_lo.b1, o0_hi = side ? p_hi.a0 : p_hi.b0;
+  const uint64_t src_lo = r.lo > s0_lo ? r.lo : s0_lo, src_hi = r.hi < s1_hi ? r.hi : s1_hi;
+  const uint64_t f_lo = p_lo.first, end_lo = f_lo + p_lo.n_cig, f_hi = p_hi.first, end_hi = f_hi + p_hi.n_cig; // f < end <= n_cigar (k_lpair_links)
+  const uint64_t base_lo = P[f_lo], base_hi = P[f_hi], u_lo = src_lo - s0_lo, u_last = src_hi - 1u - s0_hi;
+  const uint64_t e_lo = cig_entry_of(P, base_lo, f_lo, end_lo, u_lo);
+  const uint64_t e_hi = cig_entry_of(P, base_hi, link_lo == link_hi ? e_lo : f_hi, end_hi, u_last);
+  // f_lo <= e_lo < end_lo and f_hi <= e_hi < end_hi, in one chain e_lo <= e_hi: cigar[e_lo], cigar[e_hi], the prefixes up to end <= n_cigar
+  const uint64_t v_lo = cigar[e_lo], v_hi = cigar[e_hi];
+  const uint64_t code_lo = v_lo & 15u, code_hi = v_hi & 15u;
+  const uint64_t off_lo = u_lo - (P[e_lo] - base_lo), off_hi = u_last - (P[e_hi] - base_hi);
+  const uint64_t src_only = side ? CIG_I : CIG_D;
+  uint64_t a, b, mx, md, heads, head, tail; // the whole entries and chains between the two end entries; the columns of the end entries
+  if (link_lo == link_hi) {                 // docs/design/04_25_lift_identity.md
+    if (e_lo == e_hi) {
+      a = b = mx = md = 0;
+      head = off_hi - off_lo + 1u;
+      tail = 0;
+    } else {
+      a = PA[e_hi] - PA[e_lo + 1u], b = PB[e_hi] - PB[e_lo + 1u], mx = PX[e_hi] - PX[e_lo + 1u], md = PD[e_hi] - PD[e_lo + 1u];
+      head = (v_lo >> 4) - off_lo;
+      tail = off_hi + 1u;
+    }
+    heads = PH[e_hi + 1u] - PH[e_lo + 1u];
+  } else { // the rest of link_lo's chain behind e_lo, the chains of the links between, the chain of link_hi in front of e_hi
+    const uint64_t m0 = link_lo + 1u; // m0 <= link_hi <= n_links - 1: the link prefixes have n_links + 1 entries
+    a = (PA[end_lo] - PA[e_lo + 1u]) + (LA[link_hi] - LA[m0]) + (PA[e_hi] - PA[f_hi]);
+    b = (PB[end_lo] - PB[e_lo + 1u]) + (LB[link_hi] - LB[m0]) + (PB[e_hi] - PB[f_hi]);
+    mx = (PX[end_lo] - PX[e_lo + 1u]) + (LX[link_hi] - LX[m0]) + (PX[e_hi] - PX[f_hi]);
+    md = (PD[end_lo] - PD[e_lo + 1u]) + (LD[link_hi] - LD[m0]) + (PD[e_hi] - PD[f_hi]);
+    const uint64_t code_f = cigar[f_hi] & 15u; // (a chain's own first entry opens a run of its kind)
+    heads = (PH[end_lo] - PH[e_lo + 1u]) + (LH[link_hi] - LH[m0]) + (PH[e_hi + 1u] - PH[f_hi + 1u]) +
+            (code_f == CIG_I ? 1ull : code_f == CIG_D ? 1ull << 32 : 0);
+    head = (v_lo >> 4) - off_lo;
+    tail = off_hi + 1u;
+  }
+  const uint64_t meq = a - mx - md, mi = b - meq - mx;
+  const uint32_t i_heads = (uint32_t)heads, d_heads = (uint32_t)(heads >> 32);
+  const uint32_t opens = code_lo == src_only ? 1u : 0u; // (a run cut by the range's start counts once)
+  const bool both_lo = code_lo == CIG_EQ || code_lo == CIG_X, both_hi = code_hi == CIG_EQ || code_hi == CIG_X;
+  // the open stretches between link_lo and link_hi: what lies between the two end chains less the chains between them
+  const uint64_t between_src = link_lo == link_hi ? 0 : (side ? LB : LA)[link_hi] - (side ? LB : LA)[link_lo + 1u];
+  const uint64_t between_oth = link_lo == link_hi ? 0 : (side ? LA : LB)[link_hi] - (side ? LA : LB)[link_lo + 1u];
+  out.src_lo = src_lo;
+  out.src_hi = src_hi;
+  out.oth_lo = o0_lo + (O[e_lo] - O[f_lo]) + (both_lo ? off_lo : 0);
+  out.oth_hi = o0_hi + (O[e_hi] - O[f_hi]) + (both_hi ? off_hi + 1u : 0);
+  out.eq = meq + (code_lo == CIG_EQ ? head : 0) + (code_hi == CIG_EQ ? tail : 0);
+  out.x = mx + (code_lo == CIG_X ? head : 0) + (code_hi == CIG_X ? tail : 0);
+  out.src_gap = (side ? mi : md) + (code_lo == src_only ? head : 0) + (code_hi == src_only ? tail : 0);
+  out.oth_gap = side ? md : mi; // (e_lo and e_hi consume the source: a column of the other side alone lies between them)
+  out.src_open = link_lo == link_hi ? 0 : s0_hi - s1_lo - between_src;
+  out.oth_open = link_lo == link_hi ? 0 : o0_hi - o1_lo - between_oth;
+  out.src_gaps = (side ? i_heads : d_heads) + opens;
+  out.oth_gaps = side ? d_heads : i_heads;
+  out.link_lo = (uint32_t)link_lo;
+  out.link_hi = (uint32_t)link_hi;
+  out.n_links = (uint32_t)(link_hi - link_lo + 1u);
+  stats[g] = out;
+}
+
+// the link scan (the size query with tmp = nullptr)
+hipError_t lpair_scan(void* tmp, size_t& bytes, const uint64_t* totals, uint64_t* prefixes, uint64_t n_links, hipStream_t stream)
+{
+  const uint64_t rows = n_links + 1;
+  auto adds = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), LpairTotalsOf{ totals, n_links });
+  auto out = rocprim::make_zip_iterator(rocprim::make_tuple(prefixes, prefixes + rows, prefixes + 2 * rows, prefixes + 3 * rows, prefixes + 4 * rows));
+  return rocprim::exclusive_scan(tmp, bytes, adds, out, LiftStatTuple(0, 0, 0, 0, 0), rows, CigTupleAdd(), stream);
+}
+
+int cigar_lift_pairs_run(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains, const nts_lift_link* links,
+                         uint64_t n_links, const uint64_t* pair_first, uint64_t n_pairs, const nts_pair_range* ranges, uint64_t n_ranges, nts_pair_stats* stats)
+{
+  if (const int rc = cig_chains_check(ctx, "nts_cigar_lift_pairs", LIFT_MAX_BASES_LOG2, false, chains, n_chains, n_cigar, [](uint64_t, auto) { return NTS_OK; })) return rc;
+  for (uint64_t p = 0; p <= n_pairs; ++p) { // (a loop over pairs: none over links)
+    const bool bad = p == 0 ? pair_first[0] != 0 : pair_first[p] < pair_first[p - 1];
+    if (bad || (p == n_pairs && pair_first[p] != n_links) || pair_first[p] > n_links)
+      return fail(ctx, NTS_EINVAL, "nts_cigar_lift_pairs: pair_first[" + std::to_string(p) + "]: pair_first is not nondecreasing from 0 to n_links");
+  }
+  // (its own buffers first: while nothing is queued, a request that fails may still return at once)
+  NTS_WS(d_links, nts_lift_link*, "lpair_links", std::max<uint64_t>(n_links, 1) * sizeof(nts_lift_link));
+  NTS_WS(d_first, uint64_t*, "lpair_first", (n_pairs + 1) * 8);
+  NTS_WS(d_owner, uint32_t*, "lpair_owner", std::max<uint64_t>(n_chains, 1) * 4);
+  NTS_WS(d_place, LpairPlace*, "lpair_place", std::max<uint64_t>(n_links, 1) * sizeof(LpairPlace));
+  NTS_WS(d_totals, uint64_t*, "lpair_totals", 5 * std::max<uint64_t>(n_links, 1) * 8);
+  NTS_WS(d_prefixes, uint64_t*, "lpair_prefixes", 5 * (n_links + 1) * 8);
+  NTS_WS(d_ranges, nts_pair_range*, "lpair_ranges", std::max<uint64_t>(n_ranges, 1) * sizeof(nts_pair_range));
+  NTS_WS(d_stats, nts_pair_stats*, "lpair_stats", std::max<uint64_t>(n_ranges, 1) * sizeof(nts_pair_stats));
+  NTS_WS(d_worst, uint32_t*, "lpair_worst", 2 * 4); // the smallest bad link, the smallest bad range
+  size_t tmp_l = 0;                                  // the link scan's temporary: a buffer of its own ("ivs_tmp" is the stage's, fetched once inside it)
+  HIP_TRY(ctx, lpair_scan(nullptr, tmp_l, d_totals, d_prefixes, n_links, ctx->stream));
+  NTS_WS(d_tmp, void*, "lpair_tmp", std::max<size_t>(tmp_l, 16));
+  nts_pair_stats* host_stats = n_ranges ? (nts_pair_stats*)malloc(n_ranges * sizeof(nts_pair_stats)) : nullptr; // (the caller's array is written only on success)
+  if (n_ranges && !host_stats) return fail(ctx, NTS_ENOMEM, "nts_cigar_lift_pairs: no host memory for the records");
+  uint32_t worst[3] = { SCRIPT_OK, SCRIPT_OK, SCRIPT_OK }; // the smallest offending chain, link, range
+  CigIndex ix; // columns PA, PB, PX, PD, PH
+  hipError_t e_run, e_behind = hipSuccess;
+  const uint64_t rows = n_links + 1;
+  auto pass_one = [&] { // behind the stage's check, under its timer
+    e_behind = hipMemcpyAsync(d_first, pair_first, (n_pairs + 1) * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (e_behind == hipSuccess && n_links) e_behind = hipMemcpyAsync(d_links, links, n_links * sizeof(nts_lift_link), hipMemcpyHostToDevice, ctx->stream);
+    if (e_behind == hipSuccess && n_links) {
+      NTS_LAUNCH(k_lpair_claim, IVL_GRID(n_links), (const nts_lift_link*)d_links, n_links, n_chains, d_owner);
+      NTS_LAUNCH(k_lpair_twice, IVL_GRID(n_links), (const nts_lift_link*)d_links, n_links, n_chains, d_owner);
+      NTS_LAUNCH(k_lpair_links, IVL_GRID(n_links), ix.cigar, n_cigar, ix.chains, n_chains, ix.column(0), ix.column(1), ix.column(2), ix.column(3), ix.column(4),
+                 (const nts_lift_link*)d_links, n_links, (const uint64_t*)d_first, n_pairs, (const uint32_t*)d_owner, d_place, d_totals, ix.status);
+      e_behind = rocprim::reduce(ix.tmp, ix.tmp_bytes, ix.status, d_worst, SCRIPT_OK, n_links, ScriptMin(), ctx->stream);
+    }
+    if (e_behind == hipSuccess) e_behind = lpair_scan(d_tmp, tmp_l, d_totals, d_prefixes, n_links, ctx->stream);
+  };
+  if (const int rc = cig_index_stage<LiftStatOf>(ctx, "lift_pairs_scan", cigar, n_cigar, chains, n_chains, std::max(n_links, n_ranges), &worst[0], ix, e_run,
+                                                 pass_one)) {
+    free(host_stats);
+    return rc;
+  }
+  if (e_run == hipSuccess) e_run = e_behind;
+  if (e_run == hipSuccess && n_ranges) e_run = hipMemcpyAsync(d_ranges, ranges, n_ranges * sizeof(nts_pair_range), hipMemcpyHostToDevice, ctx->stream);
+  if (e_run == hipSuccess && n_ranges) { // (no range: nothing more is launched)
+    ScopedTimer t(ctx, "lift_pairs_search", true);
+    NTS_LAUNCH(k_lpair_ranges, IVL_GRID(n_ranges), ix.cigar, ix.column(0), ix.column(1), ix.column(2), ix.column(3), ix.column(4), (const LpairPlace*)d_place, n_links,
+               (const uint64_t*)d_prefixes, (const uint64_t*)(d_prefixes + rows), (const uint64_t*)(d_prefixes + 2 * rows), (const uint64_t*)(d_prefixes + 3 * rows),
+               (const uint64_t*)(d_prefixes + 4 * rows), (const uint64_t*)d_first, n_pairs, (const nts_pair_range*)d_ranges, n_ranges, d_stats, ix.status);
+    e_run = rocprim::reduce(ix.tmp, ix.tmp_bytes, ix.status, d_worst + 1, SCRIPT_OK, n_ranges, ScriptMin(), ctx->stream);
+  }
+  if (e_run == hipSuccess) e_run = hipGetLastError();
+  if (e_run == hipSuccess && n_links) e_run = hipMemcpyAsync(&worst[1], d_worst, 4, hipMemcpyDeviceToHost, ctx->stream);
+  if (e_run == hipSuccess && n_ranges) e_run = hipMemcpyAsync(&worst[2], d_worst + 1, 4, hipMemcpyDeviceToHost, ctx->stream);
+  if (e_run == hipSuccess && n_ranges) e_run = hipMemcpyAsync(host_stats, d_stats, n_ranges * sizeof(nts_pair_stats), hipMemcpyDeviceToHost, ctx->stream);
+  const hipError_t e_sync = hipStreamSynchronize(ctx->stream); // (whatever happened: the caller's arrays were sources of asynchronous copies)
+  const bool good = e_run == hipSuccess && e_sync == hipSuccess && worst[0] == SCRIPT_OK && worst[1] == SCRIPT_OK && worst[2] == SCRIPT_OK;
+  if (good && n_ranges) memcpy(stats, host_stats, n_ranges * sizeof(nts_pair_stats));
+  free(host_stats);
+  HIP_TRY(ctx, e_run);
+  HIP_TRY(ctx, e_sync);
+  if (worst[0] != SCRIPT_OK)
+    return fail(ctx, NTS_EINVAL, "nts_cigar_lift_pairs: the entries of chain " + std::to_string(worst[0]) + " are no CIGAR of its lengths");
+  if (worst[1] != SCRIPT_OK) return fail(ctx, NTS_EINVAL, "nts_cigar_lift_pairs: link " + std::to_string(worst[1]) + " is no placement of its chain");
+  if (worst[2] != SCRIPT_OK) return fail(ctx, NTS_EINVAL, "nts_cigar_lift_pairs: range " + std::to_string(worst[2]) + " is no range of a pair");
+  return NTS_OK;
+}

@@ -1049,6 +1049,21 @@ extern "C" int nts_cigar_lift_stats(nts_ctx* ctx, const uint64_t* cigar, uint64_
   return cigar_lift_stats_run(ctx, cigar, n_cigar, chains, n_chains, ranges, n_ranges, stats);
 }
 
+extern "C" int nts_cigar_lift_pairs(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains,
+                                    const nts_lift_link* links, uint64_t n_links, const uint64_t* pair_first, uint64_t n_pairs,
+                                    const nts_pair_range* ranges, uint64_t n_ranges, nts_pair_stats* stats)
+{
+  if (!ctx) return NTS_EINVAL;
+  if (n_cigar > 0xFFFFFFFFull || n_chains > 0xFFFFFFFFull) // (before any array is read)
+    return fail(ctx, NTS_ERANGE, "nts_cigar_lift_pairs: 2^32 entries or chains or more");
+  if (n_links > 0xFFFFFFFFull || n_pairs > 0xFFFFFFFFull || n_ranges > 0xFFFFFFFFull)
+    return fail(ctx, NTS_ERANGE, "nts_cigar_lift_pairs: 2^32 links, pairs or ranges or more");
+  if ((n_cigar && !cigar) || (n_chains && !chains) || (n_links && !links) || !pair_first || (n_ranges && (!ranges || !stats)))
+    return fail(ctx, NTS_EINVAL, "nts_cigar_lift_pairs: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return cigar_lift_pairs_run(ctx, cigar, n_cigar, chains, n_chains, links, n_links, pair_first, n_pairs, ranges, n_ranges, stats);
+}
+
 extern "C" int nts_graph_budget(nts_ctx* ctx, uint64_t bytes)
 {
   if (!ctx) return NTS_EINVAL;

@@ -80,6 +80,11 @@ LIFT_HIT_DTYPE = np.dtype([("pos", "<u8"), ("entry", "<u8"), ("off", "<u8"), ("c
 LIFT_RANGE_DTYPE = np.dtype([("chain", "<u4"), ("side", "<u4"), ("lo", "<u8"), ("hi", "<u8")])
 LIFT_STATS_DTYPE = np.dtype([(n, "<u8") for n in ("oth_lo", "oth_hi", "eq", "x", "src_gap", "oth_gap")] +
                             [("src_gaps", "<u4"), ("oth_gaps", "<u4"), ("reserved", "<u8")])
+# nts_lift_link / nts_pair_range / nts_pair_stats: what Context.cigar_lift_pairs takes (one per linked chain, one per range) and returns
+LIFT_LINK_DTYPE = np.dtype([("chain", "<u4"), ("reserved", "<u4"), ("a0", "<u8"), ("b0", "<u8")])
+PAIR_RANGE_DTYPE = np.dtype([("pair", "<u4"), ("side", "<u4"), ("lo", "<u8"), ("hi", "<u8")])
+PAIR_STATS_DTYPE = np.dtype([(n, "<u8") for n in ("src_lo", "src_hi", "oth_lo", "oth_hi", "eq", "x", "src_gap", "oth_gap", "src_open", "oth_open")] +
+                            [(n, "<u4") for n in ("src_gaps", "oth_gaps", "link_lo", "link_hi", "n_links", "reserved")] + [("reserved2", "<u8", (3,))])
 
 
 class Context:
@@ -511,6 +516,33 @@ class Context:
         self.check(self.lib.nts_cigar_lift_stats(self.h, cg.ctypes.data if cg.size else None, cg.size, ch.ctypes.data if ch.size else None, ch.size,
                                                  rs.ctypes.data if rs.size else None, rs.size, stats.ctypes.data if stats.size else None),
                    "nts_cigar_lift_stats")
+        return stats
+
+    def cigar_lift_pairs(self, cigar, chains, links, pair_first, ranges):
+        """one span and its counts per range and pair of chains (nts_cigar_lift_pairs).  cigar and chains as for cigar_lift; links: a
+        LIFT_LINK_DTYPE array -- `chain` occupies [a0, a0 + len_a) on A and [b0, b0 + len_b) on B of its pair, in the pair's oriented
+        offsets; pair_first [P + 1] uint64, nondecreasing from 0 to len(links): pair p's links, ascending without overlap on both sides;
+        ranges: a PAIR_RANGE_DTYPE array -- the bases lo .. hi - 1 (lo < hi < 2^63) of side 0 (A) or 1 (B) of `pair`.  Returns a
+        PAIR_STATS_DTYPE array, one record per range, over the pair's columns from the first to the last column that holds a base of
+        the range: [src_lo, src_hi) the range clipped to the chains it reaches, [oth_lo, oth_hi) the lifted span, eq, x, src_gap,
+        oth_gap the columns by kind, src_open and oth_open the bases between the chains that no column covers, src_gaps and oth_gaps
+        the gap runs, link_lo .. link_hi the links reached, n_links their number -- 0, and every field 0, for a range that touches
+        no chain.  Entries that are no CIGAR of the chains' lengths, links that are no placement of their chain and ranges of no pair
+        are refused.  Exact and deterministic."""
+        cg = np.ascontiguousarray(cigar, dtype=np.uint64)
+        ch = np.ascontiguousarray(chains, dtype=CHAIN_DTYPE)
+        lk = np.ascontiguousarray(links, dtype=LIFT_LINK_DTYPE)
+        pf = np.ascontiguousarray(pair_first, dtype=np.uint64)
+        rs = np.ascontiguousarray(ranges, dtype=PAIR_RANGE_DTYPE)
+        if cg.ndim != 1 or ch.ndim != 1 or lk.ndim != 1 or pf.ndim != 1 or pf.size < 1 or rs.ndim != 1:
+            raise ValueError("cigar_lift_pairs: a list of entries, of chain records, of links, of pairs' first links (one more than pairs) and of ranges")
+        assert LIFT_LINK_DTYPE.itemsize == ctypes.sizeof(_lib.LiftLink) and PAIR_RANGE_DTYPE.itemsize == ctypes.sizeof(_lib.PairRange)
+        assert PAIR_STATS_DTYPE.itemsize == ctypes.sizeof(_lib.PairStats) == 128 and CHAIN_DTYPE.itemsize == ctypes.sizeof(_lib.CigChain)
+        stats = np.zeros(rs.size, dtype=PAIR_STATS_DTYPE)
+        self.check(self.lib.nts_cigar_lift_pairs(self.h, cg.ctypes.data if cg.size else None, cg.size, ch.ctypes.data if ch.size else None, ch.size,
+                                                 lk.ctypes.data if lk.size else None, lk.size, pf.ctypes.data, pf.size - 1,
+                                                 rs.ctypes.data if rs.size else None, rs.size, stats.ctypes.data if stats.size else None),
+                   "nts_cigar_lift_pairs")
         return stats
 
     def timing(self, name):

@@ -498,7 +498,7 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         mx_tsvs=None, common_file=None, m=90, n=0, initial_only=False, write_fai=True, engine="device", refine_repeat_file=None, screen_repeat_file=None,
         graph_budget=None, assess=None, gaps=False, gap_links=None, gap_block_links=False, gap_copies=None, gap_copy_sites=None,
         gap_periods=None, gap_families=None, block_identity=None, block_variants=None, block_wide_variants=None, block_ends=None,
-        block_end_variants=False, block_paf=None, block_lift=None, block_lift_identity=None, block_windows=None,
+        block_end_variants=False, block_paf=None, block_lift=None, block_lift_identity=None, block_windows=None, block_lift_joined=None,
         block_paf_cs=False):
     """FASTA paths -> engine (outputs in .outputs and in the CWD).  Mirrors oracle.synteny_oracle.run_pipeline's
     signature so the parity tests read alike.  Under torch.distributed (WORLD_SIZE > 1, process group already
@@ -550,7 +550,10 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
     block_paf, which then takes the same parameters, the pass of the stage block_paf serves both files); with `benchmark` the stage times
     gain block_lift:lift_scan and block_lift:lift_search.  block_lift_identity = block_lift's eight (it needs block_lift, with the same
     eight): behind that file, <prefix>.block_lift_identity.tsv (assess.block_lift_identity: the same lines with the alignment counts and
-    the identity of every lifted interval).  block_windows = (W, genome, k, rate, band, max_len, max_edits, ends): behind that,
+    the identity of every lifted interval).  block_lift_joined = (genome, k, rate, band, max_len, max_edits, ends), with block_lift and / or
+    block_windows and their seven: <prefix>.block_lift_joined.tsv / <prefix>.block_windows_joined.tsv, one line per interval and pair of block
+    lines (assess.block_lifts: one pass for every lift table; stage block_lift_joined, timers lift_pairs_scan and lift_pairs_search).
+    block_windows = (W, genome, k, rate, band, max_len, max_edits, ends): behind that,
     <prefix>.block_windows.tsv, the same table for windows of W bases over every record of `genome` (assess.window_intervals); it needs
     none of the other switches, and takes the genome and the parameters of the others that are given.  One pass serves every file of
     block_paf, block_lift and these two: it runs in the first of their stages, the later ones write their tables; with `benchmark` the
@@ -689,6 +692,18 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
             if block_lift is not None and block_lift[1:] != given[1:]:
                 raise ValueError("block_lift and block_windows take the same (genome, k, rate, band, max_len, max_edits, ends)")
             block_windows = given
+    if block_lift_joined is not None:
+        if world > 1 or (mx_tsvs is not None and initial_only):
+            raise ValueError("block_lift_joined needs every genome resident on one GPU (one rank, genomes loaded)")
+        given = block_lift_joined
+        if len(given) != 7 or (given[6] is not None and len(given[6]) != 3):
+            raise ValueError("block_lift_joined = (genome, k, rate, band, max_len, max_edits, ends) with ends = (ends_max_len, ends_max_edits, ends_penalty) or None")
+        block_lift_joined = (str(given[0]),) + tuple(int(x) for x in given[1:6]) + (tuple(int(x) for x in given[6]) if given[6] is not None else None,)
+        if block_lift is None and block_windows is None:
+            raise ValueError("block_lift_joined joins the lines of block_lift and / or block_windows: it needs one of them")
+        for name, other in (("block_lift", block_lift), ("block_windows", block_windows)):
+            if other is not None and other[1:] != block_lift_joined:
+                raise ValueError(f"{name} and block_lift_joined take the same (genome, k, rate, band, max_len, max_edits, ends)")
     if gap_block_links and gap_links is None:
         raise ValueError("gap_block_links needs gap_links = (rate, min_anchors)")
     if gap_block_links and len(fastas) > 32:
@@ -1312,6 +1327,22 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
     counting = block_lift_identity is not None or block_windows is not None
     stats_timers = ("lift_stats_scan", "lift_stats_search") if counting else ()
     counted_rows = None                                       # the rows of block_lift_identity and block_windows, once their pass has run
+    joining = block_lift_joined is not None
+    joined_rows = None                                        # the rows of block_lift_joined's tables (the BED's, the windows'), from the same pass
+    joined_timers = ("lift_pairs_scan", "lift_pairs_search")
+    if joining and benchmark:
+        joined_before = {name: backend.ctx.timing(name)[0] for name in joined_timers}
+
+    def joined_pass(with_paf):
+        "with block_lift_joined the one pass is assess.block_lifts: (PAF rows, lift rows, [counted rows per table], [joined rows per table]), None for what is off"
+        from . import assess as assess_
+        by_name = {fa.basename(p): genomes[p] for p in fastas}
+        bed = assess_.read_bed(block_lift[0]) if block_lift is not None else None
+        windows = assess_.window_intervals(assess_.record_sizes(by_name, block_lift_joined[0]), block_windows[0]) if block_windows is not None else None
+        got = assess_.block_lifts(backend.ctx, by_name, assess_.read_blocks(f"{prefix}.synteny_blocks.tsv"), block_lift_joined[0], *block_lift_joined[1:6],
+                                  ends=block_lift_joined[6], lift=bed, identity=([bed] if block_lift_identity is not None else []) + ([windows] if windows is not None else []),
+                                  joined=([bed] if bed is not None else []) + ([windows] if windows is not None else []), paf=with_paf, cs=bool(block_paf_cs))
+        return got["paf"], got["lift"], got["identity"], got["joined"]
 
     def counted_pass(with_paf):
         "the one pass that serves block_paf, block_lift, block_lift_identity and block_windows: (PAF rows, lift rows, [counted rows per table]), None for what is off"
@@ -1334,7 +1365,9 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
             backend.ctx.profile(True)
             paf_timers = ("cigar_atoms", "cigar_merge") + (("cigar_text_scan", "cigar_text_emit") if block_paf_cs else ())
             paf_before = {name: backend.ctx.timing(name)[0] for name in paf_timers + lift_timers + stats_timers}
-        if counting:                                          # (one pass serves every file)
+        if joining:                                           # (one pass serves every file)
+            paf_rows, lifted_rows, counted_rows, joined_rows = joined_pass(True)
+        elif counting:                                        # (one pass serves every file)
             paf_rows, lifted_rows, counted_rows = counted_pass(True)
         else:
             paf_rows = assess_.block_alignments(backend.ctx, {fa.basename(p): genomes[p] for p in fastas}, assess_.read_blocks(f"{prefix}.synteny_blocks.tsv"),
@@ -1360,7 +1393,9 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
             if benchmark:                                     # (device events around the calls of this stage only)
                 backend.ctx.profile(True)
                 lift_before = {name: backend.ctx.timing(name)[0] for name in lift_timers + stats_timers}
-            if counting:                                      # (one pass serves every file)
+            if joining:                                       # (one pass serves every file)
+                _, lifted_rows, counted_rows, joined_rows = joined_pass(False)
+            elif counting:                                    # (one pass serves every file)
                 _, lifted_rows, counted_rows = counted_pass(False)
             else:
                 lifted_rows = assess_.block_lift(backend.ctx, {fa.basename(p): genomes[p] for p in fastas}, assess_.read_blocks(f"{prefix}.synteny_blocks.tsv"),
@@ -1386,7 +1421,10 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
             if benchmark:                                     # (device events around the calls of this stage only)
                 backend.ctx.profile(True)
                 stats_before = {name: backend.ctx.timing(name)[0] for name in stats_timers}
-            _, _, counted_rows = counted_pass(False)
+            if joining:
+                _, _, counted_rows, joined_rows = joined_pass(False)
+            else:
+                _, _, counted_rows = counted_pass(False)
             if benchmark:
                 stats_times = [(name, (backend.ctx.timing(name)[0] - stats_before[name]) * 1e-3) for name in stats_timers]
                 backend.ctx.profile(False)
@@ -1398,6 +1436,18 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         if benchmark:                                         # (one call per round serves both tables: either stage shows that call's time)
             st.rows += [(f"{stage}:{name}", seconds) for name, seconds in stats_times]
         st.mark(f"{stage}_done")
+    if joining:                                               # (its tables come from the pass of the first lift stage that was on)
+        st.start("block_lift_joined")
+        from . import assess as assess_
+        for stem, rows in zip((["block_lift_joined"] if block_lift is not None else []) + (["block_windows_joined"] if block_windows is not None else []), joined_rows):
+            text = assess_.lift_joined_table(rows, *block_lift_joined[1:6], ends=block_lift_joined[6])
+            with open(f"{prefix}.{stem}.tsv", "w", encoding="utf-8") as fh:
+                fh.write(text)
+            eng.outputs[f"{prefix}.{stem}.tsv"] = text
+        st.stop()
+        if benchmark:
+            st.rows += [(f"block_lift_joined:{name}", (backend.ctx.timing(name)[0] - joined_before[name]) * 1e-3) for name in joined_timers]
+        st.mark("block_lift_joined_done")
     if gaps:
         st.start("gaps")
         from . import assess as assess_, gaps as gaps_
