@@ -972,6 +972,45 @@ int nts_cigar_lift_pairs(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, 
                          const nts_lift_link* links, uint64_t n_links, const uint64_t* pair_first, uint64_t n_pairs,
                          const nts_pair_range* ranges, uint64_t n_ranges, nts_pair_stats* stats);
 
+/* ---- one liftover chain per pair of chains: the blocks of a UCSC chain file and their text ---------------------------------------
+ * nts_cigar_chain_blocks: cigar, chains, links, pair_first as for nts_cigar_lift_pairs, with its validity rules.  The pair's COLUMNS
+ *   are those of its linked chains in link order; between consecutive links lies an open stretch of a0[i + 1] - a1[i] A bases and
+ *   b0[i + 1] - b1[i] B bases.  A match column is = or X; a GAP is a D entry (A bases, dt), an I entry (B bases, dq) or an open stretch
+ *   (both).  A BLOCK is a maximal run of match columns of the pair with no gap of non-zero width inside it (= next to X is one block;
+ *   a block runs across a seam that is closed on both sides).  Block j: size = its columns; dt, dq = the A and B bases of ALL gaps
+ *   between it and block j + 1, 0 and 0 for a pair's last block.  Gaps in front of the pair's first match column and behind its last
+ *   belong to no block.  pairs[p] (n_pairs host entries, written only when the call succeeds): [a0, a1) x [b0, b1) the liftover chain
+ *   in the pair's oriented offsets, from the first match column to behind the last; eq, x its match columns by kind; first_block the
+ *   blocks of all pairs in front; n_blocks; a pair without a match column: every field 0.  a1 - a0 = sum size + sum dt, b1 - b0 = sum
+ *   size + sum dq, eq + x = sum size, size > 0, dt + dq > 0 for every block but a pair's last.  *blocks (release with nts_free; NULL
+ *   for none): *n_blocks records in pair order.  text, text_first both NULL: no text is made.  Otherwise *text (release with
+ *   nts_free; NULL for an empty text) holds per block the line "size\tdt\tdq\n", for a pair's last block "size\n", decimal without
+ *   padding; pair p's lines are bytes [text_first[p], text_first[p + 1]); text_first: n_pairs + 1 host entries.  NTS_ERANGE before any
+ *   launch: 2^32 entries, chains, links or pairs or more (before any array is read), 2^63 bases or more, chain records that hold 2^32
+ *   entries or more between them.  NTS_EINVAL before any launch: nts_cigar_lift's chain checks; pair_first not nondecreasing from 0 to
+ *   n_links.  After the launch, nothing returned and pairs untouched, the first that applies, the smallest offender named: "the
+ *   entries of chain ... are no CIGAR of its lengths"; "link ... is no placement of its chain" (nts_cigar_lift_pairs' conditions,
+ *   a0 + len_a or b0 + len_b >= 2^63 among them); NTS_ERANGE for 2^32 blocks or text bytes or more.  No link: the entries are checked,
+ *   nothing more is launched, every record is 0 and blocks and text are empty.  nts_cigar_lift's scan and check, nts_cigar_lift_pairs'
+ *   two claim kernels, one lane per link, a minimum reduction and one exclusive scan over the links' entry counts (timer
+ *   "chain_blocks_scan"); one lane per linked entry finds the heads, one exclusive scan over the linked entries, one lane per block
+ *   and one per pair (timer "chain_blocks_emit"); one exclusive scan of the lines' bytes and one lane per aligned 4-byte word of the
+ *   text (timer "chain_text").  On the context's stream, in its workspace; no atomic, no launch per pair, chain, link or block, no
+ *   floating point: the same input gives the same bytes.  docs/design/04_28_block_chain.md; csrc/nts_cigar.inc; ntsynt_amd/assess.py
+ *   block_chains, `ntSynt --block-chain`, `bin/ntsynt_block_stats --chain-out`. */
+typedef struct
+{
+  uint64_t size, dt, dq;
+} nts_chain_block;
+typedef struct
+{
+  uint64_t a0, a1, b0, b1, eq, x, first_block;
+  uint32_t n_blocks, reserved;
+} nts_chain_pair;
+int nts_cigar_chain_blocks(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains,
+                           const nts_lift_link* links, uint64_t n_links, const uint64_t* pair_first, uint64_t n_pairs, nts_chain_pair* pairs,
+                           nts_chain_block** blocks, uint64_t* n_blocks, uint8_t** text, uint64_t* text_first);
+
 /* ---- the cg:Z: and cs:Z: texts of the chains' CIGARs: block alignments with --paf-cs ------------------------------------------
  * nts_cigar_text: cigar, chains as nts_cigar_build returns them (entries need not be maximal runs), but the chains must TILE the
  *   entries: first[0] = 0, first[c + 1] = first[c] + n_cig[c], the last chain ends at n_cigar.  spans = n_chains of {pos_a, pos_b,

@@ -128,6 +128,16 @@ class PairStats(ctypes.Structure):
                [(n, u32) for n in ("src_gaps", "oth_gaps", "link_lo", "link_hi", "n_links", "reserved")] + [("reserved2", u64 * 3)]
 
 
+class ChainBlock(ctypes.Structure):
+    "nts_chain_block: one ungapped block of a liftover chain and the gaps behind it (nts_cigar_chain_blocks)"
+    _fields_ = [("size", u64), ("dt", u64), ("dq", u64)]
+
+
+class ChainPair(ctypes.Structure):
+    "nts_chain_pair: the liftover chain of one pair: its span, its match columns by kind and where its blocks lie (nts_cigar_chain_blocks)"
+    _fields_ = [(n, u64) for n in ("a0", "a1", "b0", "b1", "eq", "x", "first_block")] + [("n_blocks", u32), ("reserved", u32)]
+
+
 class MxList(ctypes.Structure):
     _fields_ = [("h1", c_vp), ("rec", c_vp), ("pos", c_vp), ("keep", c_vp), ("list_id", c_vp), ("n", u64)]
 
@@ -299,6 +309,7 @@ SYMBOLS = [
     ("nts_cigar_text", ctypes.c_int, [c_vp, c_vp, u64, c_vp, u64, c_vp, c_vp, c_vp, ctypes.POINTER(c_vp), c_vp, ctypes.POINTER(c_vp), c_vp]),
     ("nts_cigar_lift_stats", ctypes.c_int, [c_vp, c_vp, u64, c_vp, u64, c_vp, u64, c_vp]),
     ("nts_cigar_lift_pairs", ctypes.c_int, [c_vp, c_vp, u64, c_vp, u64, c_vp, u64, c_vp, u64, c_vp, u64, c_vp]),
+    ("nts_cigar_chain_blocks", ctypes.c_int, [c_vp, c_vp, u64, c_vp, u64, c_vp, u64, c_vp, u64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     ("nts_genome_valid_bases", ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(Interval), u64, c_vp]),
     ("nts_minhash_pairs", ctypes.c_int, [c_vp, u32, c_vp, c_vp, u64, c_vp, c_vp, u64, c_vp, c_vp]),
     ("nts_graph_build", ctypes.c_int, [c_vp, u32, ctypes.POINTER(MxList), ctypes.POINTER(Graph)]),

@@ -21,6 +21,8 @@ Two things, both over `<prefix>.synteny_blocks.tsv`:
 * block end variants (`ntSynt --block-ends --block-end-variants`, `ntsynt_block_stats --ends-out F --end-variants-out G`): the edits
   behind left_edits and right_edits -- the canonical script of every extended flank (nts_edit_extend_script), as snv / ins / del
   events in both genomes' coordinates; docs/design/04_21_block_end_variants.md.
+* block chain file (`ntSynt --block-chain`, `ntsynt_block_stats --chain-out`): one UCSC liftover chain per block and pair, the chains of the
+  block alignments joined per pair, blocks and data lines made on the GPU (nts_cigar_chain_blocks); docs/design/04_28_block_chain.md.
 * block alignments (`ntSynt --block-paf`, `ntsynt_block_stats --paf-out`): one PAF record with a cg:Z: CIGAR per aligned chain of every
   block and pair -- the scripts of all stretches and flanks stitched and run-length merged on the GPU (nts_cigar_build);
   docs/design/04_22_block_alignments.md.  With `--paf-cs` also the cs:Z: tag, both tag texts written on the GPU (nts_cigar_text);
@@ -888,7 +890,7 @@ def _round_paf_rows(blocks, a, found):
 
 
 def block_alignments(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_RATE, band=IDENTITY_BAND, max_len=IDENTITY_MAX_LEN, max_edits=0, ends=None,
-                     lift=None, lift_identity=None, cs=False):
+                     lift=None, lift_identity=None, cs=False, chain=False):
     """One PAF record with a cg:Z: CIGAR per aligned chain of every block and pair of its lines (target = line a, query = line b): the
     anchors, segments and final per-segment results of block_identity for the same first five parameters, the canonical scripts of
     block_variants / block_wide_variants, and with ends = (ends_max_len, ends_max_edits, ends_penalty) the flanks of block_ends attached
@@ -902,13 +904,15 @@ def block_alignments(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_R
     [intervals, ...]): the same pass also counts the alignment columns of every set of intervals (block_lift_identity; a set that IS
     the lift's dict is joined once for both); returns (those lines, block_lift's rows or None, [block_lift_identity's rows per set]).
     cs: every line also carries the cs:Z: tag (short form) behind cg:Z:, both texts made by ONE nts_cigar_text per round
-    (docs/design/04_26_block_paf_cs.md); without it no call, launch or byte changes."""
+    (docs/design/04_26_block_paf_cs.md); without it no call, launch or byte changes.  chain: the same pass also makes the liftover chains
+    (block_chains: ONE nts_cigar_chain_blocks per round); chain_table's parts are appended to what is returned (a tuple then); without
+    it no call, launch or byte changes."""
     message = check_identity_parameters(int(k), int(rate), int(band), int(max_len), int(max_edits)) or \
         (check_ends_parameters(*(int(v) for v in ends)) if ends is not None else None)
     if message:
         raise ValueError(message)
     k, rate, band, max_len, max_edits = int(k), int(rate), int(band), int(max_len), int(max_edits)
-    pairs, length, found = [], {}, {}
+    pairs, length, found, chains_of = [], {}, {}, {}
     if lift_identity is not None:
         lifter = _lifter_of(genomes_by_name, blocks, lift, lift_identity)
     else:
@@ -917,10 +921,77 @@ def block_alignments(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_R
         _round_paf_rows(blocks, a, found)
         if lifter is not None:
             lifter.add_round(ctx, a, pairs)
+        if chain:
+            _round_chain_parts(ctx, blocks, a, chains_of)
     rows = [row for p in pairs for row in found[p]]
+    parts = ([chains_of[p] for p in pairs if chains_of.get(p) is not None],) if chain else ()
     if lift_identity is not None:
-        return (rows,) + lifter.results(genomes_by_name)
-    return rows if lifter is None else (rows, lifter.rows(genomes_by_name))
+        return (rows,) + lifter.results(genomes_by_name) + parts
+    if lifter is not None:
+        return (rows, lifter.rows(genomes_by_name)) + parts
+    return (rows,) + parts if chain else rows
+
+
+def chain_header(ra, rb, rec_len_a, rec_len_b, iv_a, iv_b, flipped, pair_record, base, chain_id):
+    """the header line of one liftover chain (no newline): `chain score tName tSize + tStart tEnd qName qSize qStrand qStart qEnd id`.
+    ra / rb, rec_len_*, iv_a / iv_b, flipped as for paf_row (a is the target, b the query); pair_record: the pair's nts_chain_pair
+    fields (a0, a1, b0, b1, eq) in link offsets; base = (base_x, base_y) of chain_links: link offset + base = the oriented offset
+    inside iv_a / iv_b.  score = eq.  The target is on its forward strand.  For a `-` pair the query coordinates lie on the query's
+    REVERSE strand, as the format asks: paf_row's forward interval is [end_b - y1, end_b - y0), so qStart = qSize - (end_b - y0) and
+    qEnd = qSize - (end_b - y1).  Pure."""
+    x0, x1 = int(pair_record["a0"]) + int(base[0]), int(pair_record["a1"]) + int(base[0])
+    y0, y1 = int(pair_record["b0"]) + int(base[1]), int(pair_record["b1"]) + int(base[1])
+    start_a, start_b, end_b, q_size = int(iv_a[1]), int(iv_b[1]), int(iv_b[2]), int(rec_len_b)
+    q_from, q_to = (q_size - end_b + y0, q_size - end_b + y1) if flipped else (start_b + y0, start_b + y1)
+    return (f"chain {int(pair_record['eq'])} {ra.contig} {int(rec_len_a)} + {start_a + x0} {start_a + x1} {rb.contig} {q_size} {'-' if flipped else '+'} "
+            f"{q_from} {q_to} {int(chain_id)}")
+
+
+def chain_lines(blocks):
+    "the data lines of one liftover chain from its CHAIN_BLOCK_DTYPE records, made on the host: the spot check of the device's text"
+    rows = [(int(b["size"]), int(b["dt"]), int(b["dq"])) for b in blocks]
+    return "".join(f"{s}\n" if j == len(rows) - 1 else f"{s}\t{t}\t{q}\n" for j, (s, t, q) in enumerate(rows))
+
+
+def _round_chain_parts(ctx, blocks, a, found):
+    """ONE nts_cigar_chain_blocks for a round of the alignment pass.  found[(line a, line b)] = chain_header's arguments without the id
+    and the pair's slice of the device's text, or None for a pair without a liftover chain: one decode of the buffer and one slice per
+    pair.  The lines of the round's first liftover chain are also made on the host and compared (RuntimeError)."""
+    r = a.round
+    links, pair_first, base_x, base_y = chain_links(a)
+    pairs, chain_blocks, text, text_first = ctx.cigar_chain_blocks(a.cigar, a.records, links, pair_first.astype("uint64"))
+    whole, at = text.tobytes().decode(), text_first.tolist()
+    checked = False
+    for q, (la, lb, i) in enumerate(r.lines):
+        rec = pairs[q]
+        if int(rec["n_blocks"]) == 0:
+            found[(la, lb)] = None
+            continue
+        lines = whole[at[q]:at[q + 1]]
+        if not checked:
+            checked = True
+            first = int(rec["first_block"])
+            host = chain_lines(chain_blocks[first:first + int(rec["n_blocks"])])
+            if lines != host:
+                raise RuntimeError(f"the device's chain lines of the round's first liftover chain are {lines[:60]!r}, the host's {host[:60]!r}")
+        rec_len_a, rec_len_b = int(r.g_a.rec_len[int(r.iv_a[i][0])]), int(r.g_b.rec_len[int(r.iv_b[i][0])])
+        found[(la, lb)] = (blocks[la], blocks[lb], rec_len_a, rec_len_b, r.iv_a[i].copy(), r.iv_b[i].copy(), bool(r.flip[i]),
+                           {f: int(rec[f]) for f in ("a0", "a1", "b0", "b1", "eq", "x", "n_blocks")}, (int(base_x[q]), int(base_y[q])), lines)
+
+
+def chain_table(parts):
+    """the UCSC chain file of block_chains' parts: per liftover chain chain_header's line, the pair's data lines as the device wrote
+    them and a blank line; ids count from 1 in file order.  parts: per pair (chain_header's first nine arguments..., lines), in
+    block_identity's pair order, pairs without a liftover chain left out"""
+    return "".join(chain_header(*part[:9], n + 1) + "\n" + part[9] + "\n" for n, part in enumerate(parts))
+
+
+def block_chains(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_RATE, band=IDENTITY_BAND, max_len=IDENTITY_MAX_LEN, max_edits=0, ends=None):
+    """One liftover chain per block and pair of its lines (target = line a, query = line b): the chains of block_alignments for the same
+    parameters joined per pair, the stretch between two chains as a gap with bases on both sides (docs/design/04_28_block_chain.md).  A
+    pass of its own over the rounds (_alignment_rounds) with ONE nts_cigar_chain_blocks per round, which makes the blocks and their
+    text on the device.  Returns chain_table's parts in block_identity's pair order."""
+    return block_alignments(ctx, genomes_by_name, blocks, k, rate, band, max_len, max_edits, ends, chain=True)[1]
 
 
 LIFT_COLUMNS = ("genome", "contig", "start", "end", "name", "block_id", "to_genome", "to_contig", "to_start", "to_end", "orientation", "ch", "src_start",
@@ -1140,6 +1211,37 @@ def lift_joined_table(rows, k, rate, band, max_len, max_edits=0, ends=None):
     return lift_table(rows, k, rate, band, max_len, max_edits, ends, columns=LIFT_JOINED_COLUMNS)
 
 
+def chain_links(a):
+    """(links, pair_first, base_x, base_y) of _chain_links, which see: what nts_cigar_lift_pairs and nts_cigar_chain_blocks take.  Pure."""
+    return _chain_links(a)[:4]
+
+
+def _chain_links(a):
+    """The chains of one round of the alignment pass (an _AlignmentRound) as links for nts_cigar_lift_pairs and nts_cigar_chain_blocks:
+    the chains with entries in (pair, ch) order at their oriented offsets x0, y0 -- moved per pair by base_x, base_y so that none is
+    negative (a flank may leave the interval).  Returns (links, pair_first [lines + 1] int64, base_x, base_y [lines] int64, linked): link
+    offset + base = alignment_pieces' offset; linked = the linked chains as indices into the chains sorted by line (stable), in link
+    order.  Array operations alone.  Pure."""
+    import numpy as np
+    from .device import LIFT_LINK_DTYPE
+    n_lines = len(a.round.lines)
+    order = np.argsort(a.chains["line"], kind="stable")       # the chains of one pair next to each other, ascending by ch
+    line = a.chains["line"][order]
+    x0, y0 = a.chains["x0"][order], a.chains["y0"][order]
+    linked = np.flatnonzero(np.asarray(a.records["n_cig"]).astype(np.int64)[order] > 0)   # (a chain without entries is not linked)
+    linked = linked[np.lexsort((a.chains["ch"][order][linked], line[linked]))]              # link order: by pair, ascending by ch
+    of_line = line[linked]
+    pair_first = np.searchsorted(of_line, np.arange(n_lines + 1)).astype(np.int64)
+    has = pair_first[1:] > pair_first[:-1]
+    first = np.minimum(pair_first[:-1], max(linked.size - 1, 0))
+    lx0, ly0 = x0[linked], y0[linked]
+    base_x = np.where(has, np.minimum(lx0[first], 0), 0) if linked.size else np.zeros(n_lines, dtype=np.int64)
+    base_y = np.where(has, np.minimum(ly0[first], 0), 0) if linked.size else np.zeros(n_lines, dtype=np.int64)
+    links = np.zeros(linked.size, dtype=LIFT_LINK_DTYPE)
+    links["chain"], links["a0"], links["b0"] = order[linked], lx0 - base_x[of_line], ly0 - base_y[of_line]
+    return links, pair_first, base_x, base_y, linked
+
+
 class _Lifter:
     """block_lift's state over the rounds of the alignment pass: per round the spans, ONE nts_cigar_lift and the rows' arrays.  stats: a
     bool per interval, or None -- per round also ONE nts_cigar_lift_stats for all overlaps of the intervals it marks (block_lift_identity).
@@ -1214,19 +1316,11 @@ class _Lifter:
         per pair so that none is negative (a flank may leave the interval) --, one range per marked interval and pair whose hull it
         reaches (lift_pair_ranges); the records with a link, in forward coordinates, go to joined_parts"""
         import numpy as np
-        from .device import LIFT_LINK_DTYPE
         r, n_lines = a.round, len(a.round.lines)
-        linked = np.flatnonzero(np.asarray(a.records["n_cig"]).astype(np.int64)[order] > 0)   # (a chain without entries is not linked)
-        linked = linked[np.lexsort((a.chains["ch"][order][linked], line[linked]))]              # link order: by pair, ascending by ch
-        of_line = line[linked]
-        pair_first = np.searchsorted(of_line, np.arange(n_lines + 1)).astype(np.int64)
+        links, pair_first, base_x, base_y, linked = _chain_links(a)
         has = pair_first[1:] > pair_first[:-1]
         first, last = np.minimum(pair_first[:-1], max(linked.size - 1, 0)), np.maximum(pair_first[1:] - 1, 0)
         lx0, lx1, ly0, ly1 = (v[linked] for v in (x0, x1, y0, y1))
-        base_x = np.where(has, np.minimum(lx0[first], 0), 0) if linked.size else np.zeros(n_lines, dtype=np.int64)
-        base_y = np.where(has, np.minimum(ly0[first], 0), 0) if linked.size else np.zeros(n_lines, dtype=np.int64)
-        links = np.zeros(linked.size, dtype=LIFT_LINK_DTYPE)
-        links["chain"], links["a0"], links["b0"] = order[linked], lx0 - base_x[of_line], ly0 - base_y[of_line]
         i = np.array([i for _, _, i in r.lines], dtype=np.int64)
         flip = r.flip[i].astype(bool) if n_lines else np.zeros(0, dtype=bool)
         origin_a = r.iv_a[i, 1].astype(np.int64) + base_x if n_lines else base_x
@@ -1405,7 +1499,7 @@ def block_lift_identity(ctx, genomes_by_name, blocks, source, intervals, k=IDENT
 
 
 def block_lifts(ctx, genomes_by_name, blocks, source, k=IDENTITY_K, rate=IDENTITY_RATE, band=IDENTITY_BAND, max_len=IDENTITY_MAX_LEN, max_edits=0, ends=None,
-                lift=None, identity=(), joined=(), paf=False, cs=False):
+                lift=None, identity=(), joined=(), paf=False, cs=False, chain=False):
     """Every table of the lift from ONE pass over _alignment_rounds, the joined ones among them: lift = a dict of intervals for block_lift's
     rows, identity = dicts for block_lift_identity's rows, joined = dicts for the joined rows (LIFT_JOINED_COLUMNS), paf: block_alignments'
     lines as well (cs: with the cs:Z: tag).  A dict that is given more than once is joined once and read for every table it serves.  The
@@ -1438,13 +1532,16 @@ def block_lifts(ctx, genomes_by_name, blocks, source, k=IDENTITY_K, rate=IDENTIT
                  "end": np.concatenate([np.asarray(one["end"], dtype=np.int64) for one in every] + [np.zeros(0, dtype=np.int64)])}
     lifter = _Lifter(genomes_by_name, blocks, source, intervals, stats=counted if at_identity else None, joined=joining if at_joined else None,
                      per_chain=lift is not None or bool(at_identity))
-    pairs, length, found = [], {}, {}
+    pairs, length, found, chains_of = [], {}, {}, {}
     for a in _alignment_rounds(ctx, genomes_by_name, blocks, int(k), int(rate), int(band), int(max_len), int(max_edits), ends, pairs, length,
-                               only=None if paf else source, cs=bool(cs) and bool(paf)):
+                               only=None if paf or chain else source, cs=bool(cs) and bool(paf)):
         if paf:
             _round_paf_rows(blocks, a, found)
         lifter.add_round(ctx, a, pairs)
-    return {"paf": [row for p in pairs for row in found[p]] if paf else None,
+        if chain:
+            _round_chain_parts(ctx, blocks, a, chains_of)
+    return {"chain": [chains_of[p] for p in pairs if chains_of.get(p) is not None] if chain else None,   # (chain: block_chains' parts from the same pass)
+            "paf": [row for p in pairs for row in found[p]] if paf else None,
             "lift": lifter.rows(genomes_by_name, *spans[at_lift]) if lift is not None else None,
             "identity": [lifter.rows(genomes_by_name, *spans[at], identity=True) for at in at_identity],
             "joined": [lifter.joined_rows(genomes_by_name, *spans[at]) for at in at_joined]}
@@ -1600,6 +1697,8 @@ def main(argv=None):
                    "flanks are attached")
     p.add_argument("--paf-cs", help="with --paf-out (which it needs): every record also carries the cs:Z: tag (short form) behind cg:Z:; both tag texts "
                    "are then made on the GPU", action="store_true")
+    p.add_argument("--chain-out", help="with --fastas: file for the block chain file (one UCSC liftover chain per block and pair, the chains of --paf-out "
+                   "joined per pair with the stretches between them as dt dq gaps; GPU); it takes the parameters of --paf-out")
     p.add_argument("--lift-bed", help="with --fastas, --lift-genome and --lift-out: a BED file of intervals of one genome that are mapped through the block "
                    "alignments into the other genomes (GPU); it takes the parameters of --paf-out")
     p.add_argument("--lift-genome", help="the genome the intervals of --lift-bed lie on: a FASTA base name, as in column 2 of the block table")
@@ -1632,6 +1731,12 @@ def main(argv=None):
     if args.paf_out:
         if not args.fastas:
             p.error("--paf-out needs the genomes: --fastas")
+        message = check_identity_parameters(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits)
+        if message:
+            p.error(message)
+    if args.chain_out:
+        if not args.fastas:
+            p.error("--chain-out needs the genomes: --fastas")
         message = check_identity_parameters(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits)
         if message:
             p.error(message)
@@ -1686,6 +1791,7 @@ def main(argv=None):
         loaders = {basename(path): (lambda path=path: read_fasta_device(ctx, path)[0]) for path in args.fastas}
         text = divergence_table(block_divergence(ctx, loaders, read_blocks(args.tsv), args.k, args.s), args.k, args.s)
         id_args = (args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len)
+        chain_parts = None
         if args.variants_out:                                 # (one pass gives both tables)
             id_rows, var_rows = block_variants(ctx, loaders, read_blocks(args.tsv), *id_args)
             with open(args.variants_out, "w", encoding="utf-8") as fh:
@@ -1753,7 +1859,9 @@ def main(argv=None):
             intervals = read_bed(args.lift_bed) if args.lift_out else None
             if args.paf_out:
                 paf_rows = block_alignments(ctx, loaders, read_blocks(args.tsv), *id_args, **a_args,
-                                            lift=(args.lift_genome, intervals) if args.lift_out else None, cs=args.paf_cs)
+                                            lift=(args.lift_genome, intervals) if args.lift_out else None, cs=args.paf_cs, chain=bool(args.chain_out))
+                if args.chain_out:                            # (one pass gives the PAF and the chain file)
+                    paf_rows, chain_parts = (paf_rows[:-1] if args.lift_out else paf_rows[0]), paf_rows[-1]
                 if args.lift_out:
                     paf_rows, lift_rows_ = paf_rows
                 with open(args.paf_out, "w", encoding="utf-8") as fh:
@@ -1763,6 +1871,12 @@ def main(argv=None):
             if args.lift_out:
                 with open(args.lift_out, "w", encoding="utf-8") as fh:
                     fh.write(lift_table(lift_rows_, *id_args, **a_args))
+        if args.chain_out:
+            if chain_parts is None:                           # (beside the lift tables or alone: a pass of its own)
+                chain_parts = block_chains(ctx, loaders, read_blocks(args.tsv), *id_args, max_edits=args.identity_max_edits,
+                                           ends=(args.ends_max_len, args.ends_max_edits, args.ends_penalty) if args.ends_out else None)
+            with open(args.chain_out, "w", encoding="utf-8") as fh:
+                fh.write(chain_table(chain_parts))
     finally:
         ctx.close()
     if args.divergence_out:

@@ -1279,3 +1279,472 @@ int cigar_lift_pairs_run(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, 
   if (worst[2] != SCRIPT_OK) return fail(ctx, NTS_EINVAL, "nts_cigar_lift_pairs: range " + std::to_string(worst[2]) + " is no range of a pair");
   return NTS_OK;
 }
+
+// ---- one liftover chain per PAIR of chains: blocks and their text (nts_cigar_chain_blocks; ntsynt_amd/assess.py chain_table) ----
+// docs/design/04_28_block_chain.md.  Input: CIGAR entries, chain records, links and pair_first as for nts_cigar_lift_pairs.  The pair's
+// columns are those of its linked chains in link order; a BLOCK is a maximal run of = / X columns with no gap of non-zero width inside
+// it, a gap being a D entry (A bases, dt), an I entry (B bases, dq) or the open stretch between two links (both).  Linked entry v is
+// entry v - LN[i] of link i's chain, LN the prefix of the links' entry counts: the linked entries in pair order, NV of them.
+//   1  cig_index_stage with (A bases, B bases); behind its check k_lpair_claim and k_lpair_twice, k_cchn_links -- one lane per link --
+//      validates the link as k_lpair_links does and writes its placement, its pair and its entry count; a minimum reduction names the
+//      smallest bad link, ONE exclusive scan over n_links + 1 counts gives LN (timer "chain_blocks_scan").
+//   2  k_cchn_cols: one lane per linked entry; a match entry is a HEAD when it is its pair's first linked entry or what lies in front
+//      of it in the pair is a gap of non-zero width: a seam's open stretch, else the entry in front of it (across a closed seam, the
+//      previous link's last entry).  ONE exclusive scan over the linked entries of (match columns, X columns, A gap bases, B gap bases,
+//      heads, last match entry + 1 -- a maximum) follows; k_cchn_heads stores every head at its block index, k_cchn_blocks -- one lane
+//      per block -- takes size, dt and dq as prefix differences between two heads, k_cchn_pairs -- one lane per pair -- the record
+//      (timer "chain_blocks_emit").
+//   3  ONE exclusive scan of the blocks' byte counts, k_cchn_text_firsts, and k_cchn_text: one lane per aligned 4-byte word of the
+//      text, as k_cig_text (timer "chain_text").
+// No atomic, no launch per pair, chain, link or block, no floating point, no host loop over entries, links or blocks.
+
+static_assert(sizeof(nts_chain_block) == 24 && sizeof(nts_chain_pair) == 64, "the C ABI's layout");
+
+using CchnTuple = rocprim::tuple<uint64_t, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t>; // match, X, A gap, B gap, heads, last match + 1
+constexpr uint32_t CCHN_COLUMNS = 6;
+
+struct ChainBasesOf // element e of the stage's scan: what entry e consumes; nothing behind the last entry
+{
+  using Tuple = CigBases;
+  const uint64_t* cigar;
+  uint64_t n_cigar;
+  __host__ __device__ Tuple operator()(uint64_t e) const { return e < n_cigar ? cig_bases(cigar[e]) : Tuple(0, 0); }
+};
+
+struct CchnCountOf // element i of the link scan's input: the entries of link i's chain, 0 for a bad link; nothing behind the last link
+{
+  const uint64_t* count;
+  uint64_t n_links;
+  __host__ __device__ uint64_t operator()(uint64_t i) const { return i < n_links ? count[i] : 0; }
+};
+
+struct CchnAdd // five sums and a maximum
+{
+  __host__ __device__ CchnTuple operator()(const CchnTuple& x, const CchnTuple& y) const
+  {
+    const uint64_t lx = rocprim::get<5>(x), ly = rocprim::get<5>(y);
+    return CchnTuple(rocprim::get<0>(x) + rocprim::get<0>(y), rocprim::get<1>(x) + rocprim::get<1>(y), rocprim::get<2>(x) + rocprim::get<2>(y),
+                     rocprim::get<3>(x) + rocprim::get<3>(y), rocprim::get<4>(x) + rocprim::get<4>(y), lx > ly ? lx : ly);
+  }
+};
+
+// the decimal digit of weight 10^j of any v, j <= 19: v = hi 10^9 + lo by the constant 10^9 (a multiplication), hi < 2^35 and lo < 10^9
+// are dividends cig_digit is exact for
+__device__ __forceinline__ uint32_t cchn_digit(uint64_t v, uint32_t j)
+{
+  const uint64_t hi = v / 1000000000ull, lo = v - hi * 1000000000ull;
+  return j < 9u ? cig_digit(lo, j) : cig_digit(hi, j - 9u);
+}
+
+// the bytes of a block's line: "size\n" behind a pair's last block -- the one block without a gap behind it --, else "size\tdt\tdq\n"
+__device__ __forceinline__ uint64_t cchn_line_bytes(const nts_chain_block& b)
+{
+  return (b.dt | b.dq) == 0 ? cig_digits(b.size) + 1u : cig_digits(b.size) + cig_digits(b.dt) + cig_digits(b.dq) + 3u;
+}
+
+__global__ __launch_bounds__(256) void k_cchn_links(const nts_cig_chain* __restrict__ chains, uint64_t n_chains, uint64_t n_cigar,
+                                                    const nts_lift_link* __restrict__ links, uint64_t n_links, const uint64_t* __restrict__ pair_first,
+                                                    uint64_t n_pairs, const uint32_t* __restrict__ owner, LpairPlace* __restrict__ place,
+                                                    uint32_t* __restrict__ pair_of, uint64_t* __restrict__ count, uint32_t* __restrict__ status)
+{
+  const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (g >= n_links) return;
+  const nts_lift_link lk = links[g];
+  nts_cig_chain ch;
+  // (a chain without entries may not be linked; behind this first + n_cig <= n_cigar and n_cig >= 1)
+  bool ok = lk.reserved == 0 && cig_chain_of(chains, n_chains, lk.chain, 0u, ch) && !cig_chain_beyond(ch, n_cigar) && ch.n_cig != 0;
+  ok = ok && owner[lk.chain] != LPAIR_TWICE; // (lk.chain < n_chains)
+  ok = ok && lk.a0 < LPAIR_MAX_BASE && lk.b0 < LPAIR_MAX_BASE && ch.len_a < LPAIR_MAX_BASE - lk.a0 && ch.len_b < LPAIR_MAX_BASE - lk.b0;
+  // its pair: the last with pair_first <= g (pair_first[0] = 0 <= g < n_links = pair_first[n_pairs]: n_pairs >= 1 here)
+  const uint64_t p = cig_last_at_or_before(n_pairs, g, [pair_first](uint64_t i) { return pair_first[i]; });
+  if (ok && g > pair_first[p]) { // the link in front of it in its pair; one that is bad itself is named instead
+    const nts_lift_link pv = links[g - 1u];
+    nts_cig_chain pc;
+    if (cig_chain_of(chains, n_chains, pv.chain, 0u, pc) && pv.a0 < LPAIR_MAX_BASE && pv.b0 < LPAIR_MAX_BASE && pc.len_a < LPAIR_MAX_BASE - pv.a0 &&
+        pc.len_b < LPAIR_MAX_BASE - pv.b0)
+      ok = lk.a0 >= pv.a0 + pc.len_a && lk.b0 >= pv.b0 + pc.len_b;
+  }
+  if (ok) place[g] = { ch.first, ch.n_cig, lk.a0, lk.a0 + ch.len_a, lk.b0, lk.b0 + ch.len_b };
+  else place[g] = { 0, 0, lk.a0, lk.a0, lk.b0, lk.b0 };
+  pair_of[g] = (uint32_t)p;
+  count[g] = ok ? ch.n_cig : 0;
+  status[g] = ok ? SCRIPT_OK : (uint32_t)g;
+}
+
+// lane v <= cap: what linked entry v adds to the six columns `in` (rows words each), zeros behind the last linked entry
+__global__ __launch_bounds__(256) void k_cchn_cols(const uint64_t* __restrict__ cigar, uint64_t n_cigar, const LpairPlace* __restrict__ place,
+                                                   const uint32_t* __restrict__ pair_of, const uint64_t* __restrict__ LN, uint64_t n_links,
+                                                   const uint64_t* __restrict__ pair_first, uint64_t n_pairs, uint64_t cap, uint64_t* __restrict__ in,
+                                                   uint32_t* __restrict__ link_of)
+{
+  const uint64_t v = (uint64_t)blockIdx.x * 256u + threadIdx.x, rows = cap + 1u;
+  if (v > cap) return;
+  uint64_t m = 0, x = 0, ga = 0, gb = 0, head = 0, last = 0;
+  const uint64_t nv = LN[n_links] < cap ? LN[n_links] : cap; // (good links name different chains: their entries number cap at the most)
+  if (v < nv) {
+    // its link: the last with LN <= v (LN[0] = 0 <= v < LN[n_links]); LN[i + 1] > v, so link i has entries: a good link
+    const uint64_t i = cig_last_at_or_before(n_links, v, [LN](uint64_t k) { return LN[k]; });
+    const LpairPlace pl = place[i];
+    uint64_t p = pair_of[i];
+    if (p >= n_pairs) p = n_pairs - 1u; // (k_cchn_links stored p < n_pairs)
+    uint64_t l0 = pair_first[p];
+    if (l0 > i) l0 = i;
+    uint64_t k = v - LN[i];
+    if (k >= pl.n_cig) k = pl.n_cig - 1u; // (LN[i + 1] - LN[i] = n_cig > k)
+    uint64_t e = pl.first + k;
+    if (e >= n_cigar) e = n_cigar - 1u; // (k_cchn_links: first + n_cig <= n_cigar)
+    const uint64_t val = cigar[e], code = val & 15u, len = val >> 4;
+    const bool match = code == CIG_EQ || code == CIG_X;
+    const bool opens_link = k == 0, opens_pair = v == LN[l0];
+    bool gap_in_front = false;
+    if (opens_link && !opens_pair) { // a seam: LN[i] > LN[l0] gives i > l0, link i - 1 lies in the same pair
+      const LpairPlace pv = place[i - 1u];
+      const uint64_t sa = pl.a0 - pv.a1, sb = pl.b0 - pv.b1;
+      ga = sa;
+      gb = sb;
+      if ((sa | sb) != 0 || pv.n_cig == 0) {
+        gap_in_front = true;
+      } else {
+        const uint64_t pe = pv.first + pv.n_cig - 1u; // the previous link's last entry (pe < n_cigar: k_cchn_links)
+        const uint64_t pc = pe < n_cigar ? cigar[pe] & 15u : 0;
+        gap_in_front = !(pc == CIG_EQ || pc == CIG_X);
+      }
+    } else if (!opens_link) {
+      const uint64_t pc = cigar[e ? e - 1u : 0] & 15u; // (e > first >= 0)
+      gap_in_front = !(pc == CIG_EQ || pc == CIG_X);
+    }
+    if (match) {
+      m = len;
+      x = code == CIG_X ? len : 0;
+      head = opens_pair || gap_in_front ? 1u : 0u;
+      last = v + 1u;
+    } else {
+      ga += code == CIG_D ? len : 0;
+      gb += code == CIG_I ? len : 0;
+    }
+    link_of[v] = (uint32_t)i;
+  }
+  in[v] = m;
+  in[rows + v] = x;
+  in[2u * rows + v] = ga;
+  in[3u * rows + v] = gb;
+  in[4u * rows + v] = head;
+  in[5u * rows + v] = last;
+}
+
+// every head stores its linked entry at its block index
+__global__ __launch_bounds__(256) void k_cchn_heads(const uint64_t* __restrict__ in_head, const uint64_t* __restrict__ PH, uint64_t cap,
+                                                    uint32_t* __restrict__ head_at)
+{
+  const uint64_t v = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (v >= cap || in_head[v] == 0) return;
+  const uint64_t j = PH[v];
+  if (j < cap) head_at[j] = (uint32_t)v; // (heads in front of v: fewer than cap)
+}
+
+// lane j <= cap: block j's size and the gaps behind it, and the bytes of its line; 0 bytes behind the last block
+__global__ __launch_bounds__(256) void k_cchn_blocks(const uint32_t* __restrict__ head_at, const uint32_t* __restrict__ link_of,
+                                                     const uint32_t* __restrict__ pair_of, const uint64_t* __restrict__ LN, uint64_t n_links,
+                                                     const uint64_t* __restrict__ pair_first, uint64_t n_pairs, const uint64_t* __restrict__ pre, uint64_t cap,
+                                                     nts_chain_block* __restrict__ blocks, uint64_t* __restrict__ bytes)
+{
+  const uint64_t j = (uint64_t)blockIdx.x * 256u + threadIdx.x, rows = cap + 1u;
+  if (j > cap) return;
+  const uint64_t* __restrict__ PM = pre;
+  const uint64_t* __restrict__ PGA = pre + 2u * rows;
+  const uint64_t* __restrict__ PGB = pre + 3u * rows;
+  const uint64_t nb = pre[4u * rows + cap] < cap ? pre[4u * rows + cap] : cap; // the heads of all linked entries
+  if (j >= nb) {
+    bytes[j] = 0;
+    return;
+  }
+  uint64_t v = head_at[j];
+  if (v >= cap) v = cap - 1u; // (k_cchn_heads stored v < cap)
+  uint64_t i = link_of[v];
+  if (i >= n_links) i = n_links - 1u;
+  uint64_t p = pair_of[i];
+  if (p >= n_pairs) p = n_pairs - 1u;
+  uint64_t l1 = pair_first[p + 1u];
+  if (l1 > n_links) l1 = n_links;
+  uint64_t v_end = LN[l1]; // behind the pair's last linked entry
+  if (v_end > cap) v_end = cap;
+  uint64_t next = v_end;
+  bool is_last = true;
+  if (j + 1u < nb) {
+    const uint64_t nx = head_at[j + 1u];
+    if (nx < v_end) next = nx, is_last = false;
+  }
+  if (next < v) next = v; // (heads ascend with their index)
+  nts_chain_block b = { PM[next] - PM[v], 0, 0 };
+  if (!is_last) { // the gaps of the linked entries v + 1 .. next, the seam in front of `next` included (next + 1 <= cap)
+    b.dt = PGA[next + 1u] - PGA[v + 1u];
+    b.dq = PGB[next + 1u] - PGB[v + 1u];
+  }
+  blocks[j] = b;
+  bytes[j] = cchn_line_bytes(b);
+}
+
+// lane p < n_pairs: the record of pair p's liftover chain, all 0 for a pair without a match column
+__global__ __launch_bounds__(256) void k_cchn_pairs(const LpairPlace* __restrict__ place, const uint32_t* __restrict__ head_at,
+                                                    const uint32_t* __restrict__ link_of, const uint64_t* __restrict__ LN, uint64_t n_links,
+                                                    const uint64_t* __restrict__ pair_first, uint64_t n_pairs, const uint64_t* __restrict__ pre, uint64_t cap,
+                                                    const uint64_t* __restrict__ PA, const uint64_t* __restrict__ PB, uint64_t n_cigar,
+                                                    nts_chain_pair* __restrict__ pairs)
+{
+  const uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x, rows = cap + 1u;
+  if (p >= n_pairs) return;
+  uint64_t l0 = pair_first[p], l1 = pair_first[p + 1u];
+  if (l1 > n_links) l1 = n_links; // (the host refused this before the launch: a lane still reads nothing outside the link prefixes)
+  if (l0 > l1) l0 = l1;
+  uint64_t v0 = LN[l0], v1 = LN[l1];
+  if (v1 > cap) v1 = cap;
+  if (v0 > v1) v0 = v1;
+  const uint64_t* __restrict__ PM = pre;
+  const uint64_t* __restrict__ PX = pre + rows;
+  const uint64_t* __restrict__ PH = pre + 4u * rows;
+  const uint64_t* __restrict__ PL = pre + 5u * rows;
+  const uint64_t fb = PH[v0], nb = PH[v1] - fb;
+  nts_chain_pair out = {};
+  if (nb == 0 || fb >= cap) {
+    pairs[p] = out;
+    return;
+  }
+  uint64_t h = head_at[fb], t = PL[v1] - 1u; // the pair's first and last match entry (PL[v1] >= h + 1: a maximum over all entries in front of v1)
+  if (h >= cap) h = cap - 1u;
+  if (t >= cap || t < h) t = h;
+  uint64_t ih = link_of[h], it = link_of[t];
+  if (ih >= n_links) ih = n_links - 1u;
+  if (it >= n_links) it = n_links - 1u;
+  const LpairPlace ph = place[ih], pt = place[it];
+  uint64_t eh = ph.first + (h - LN[ih]), et = pt.first + (t - LN[it]);
+  if (eh >= n_cigar) eh = n_cigar - 1u; // (first <= e < first + n_cig <= n_cigar for the entries of a good link)
+  if (et >= n_cigar) et = n_cigar - 1u;
+  const uint64_t fh = ph.first <= eh ? ph.first : eh, ft = pt.first <= et ? pt.first : et;
+  out.a0 = ph.a0 + (PA[eh] - PA[fh]);
+  out.b0 = ph.b0 + (PB[eh] - PB[fh]);
+  out.a1 = pt.a0 + (PA[et + 1u] - PA[ft]);
+  out.b1 = pt.b0 + (PB[et + 1u] - PB[ft]);
+  out.x = PX[v1] - PX[h];
+  out.eq = (PM[v1] - PM[h]) - out.x;
+  out.first_block = fb;
+  out.n_blocks = (uint32_t)nb;
+  pairs[p] = out;
+}
+
+// lane p <= n_pairs: where pair p's lines begin, the text's length for p = n_pairs
+__global__ __launch_bounds__(256) void k_cchn_text_firsts(const uint64_t* __restrict__ LN, uint64_t n_links, const uint64_t* __restrict__ pair_first,
+                                                          uint64_t n_pairs, const uint64_t* __restrict__ PH, const uint64_t* __restrict__ TB, uint64_t cap,
+                                                          uint64_t* __restrict__ text_first)
+{
+  const uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (p > n_pairs) return;
+  uint64_t l = pair_first[p];
+  if (l > n_links) l = n_links;
+  uint64_t v = LN[l];
+  if (v > cap) v = cap;
+  uint64_t fb = PH[v];
+  if (fb > cap) fb = cap;
+  text_first[p] = TB[fb];
+}
+
+// one lane per aligned 4-byte word of the text: the block of the word's first byte by a search over the byte prefix, then the at most
+// three further lines a word touches (a line has at least 2 bytes)
+__global__ __launch_bounds__(256) void k_cchn_text(const nts_chain_block* __restrict__ blocks, uint64_t n_blocks, const uint64_t* __restrict__ TB,
+                                                   uint32_t* __restrict__ out, uint64_t n_words)
+{
+  const uint64_t w = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (w >= n_words || n_blocks == 0) return;
+  const uint64_t total = TB[n_blocks], o = 4u * w;
+  uint64_t j = cig_last_at_or_before(n_blocks, o, [TB](uint64_t i) { return TB[i]; }); // (TB[0] = 0 <= o)
+  uint64_t p0 = TB[j], p1 = TB[j + 1u]; // (j < n_blocks)
+  nts_chain_block b = blocks[j];
+  uint32_t word = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < 4u; ++k) {
+    const uint64_t at = o + k;
+    if (at >= total) break; // (the padding of the last word stays 0)
+    while (at >= p1 && j + 1u < n_blocks) {
+      ++j;
+      p0 = p1;
+      p1 = TB[j + 1u];
+      b = blocks[j];
+    }
+    const bool is_last = (b.dt | b.dq) == 0;
+    uint64_t off = at - p0, number = b.size;
+    uint32_t end = is_last ? '\n' : '\t';
+    uint32_t digits = cig_digits(number);
+    if (!is_last && off > digits) { // behind "size\t"
+      off -= digits + 1u;
+      number = b.dt;
+      digits = cig_digits(number);
+      if (off > digits) { // behind "dt\t"
+        off -= digits + 1u;
+        number = b.dq;
+        digits = cig_digits(number);
+        end = '\n';
+      }
+    }
+    const uint32_t byte = off < digits ? '0' + cchn_digit(number, digits - 1u - (uint32_t)off) : end;
+    word |= byte << (8u * k);
+  }
+  out[w] = word;
+}
+
+// the link scan, the scan over the linked entries and the scan of the blocks' bytes (the size queries with tmp = nullptr)
+hipError_t cchn_link_scan(void* tmp, size_t& bytes, const uint64_t* count, uint64_t* LN, uint64_t n_links, hipStream_t stream)
+{
+  auto adds = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), CchnCountOf{ count, n_links });
+  return rocprim::exclusive_scan(tmp, bytes, adds, LN, (uint64_t)0, n_links + 1, rocprim::plus<uint64_t>(), stream);
+}
+
+hipError_t cchn_entry_scan(void* tmp, size_t& bytes, const uint64_t* in, uint64_t* pre, uint64_t cap, hipStream_t stream)
+{
+  const uint64_t rows = cap + 1;
+  auto adds = rocprim::make_zip_iterator(rocprim::make_tuple(in, in + rows, in + 2 * rows, in + 3 * rows, in + 4 * rows, in + 5 * rows));
+  auto out = rocprim::make_zip_iterator(rocprim::make_tuple(pre, pre + rows, pre + 2 * rows, pre + 3 * rows, pre + 4 * rows, pre + 5 * rows));
+  return rocprim::exclusive_scan(tmp, bytes, adds, out, CchnTuple(0, 0, 0, 0, 0, 0), rows, CchnAdd(), stream);
+}
+
+hipError_t cchn_byte_scan(void* tmp, size_t& bytes, const uint64_t* line_bytes, uint64_t* TB, uint64_t cap, hipStream_t stream)
+{
+  return rocprim::exclusive_scan(tmp, bytes, line_bytes, TB, (uint64_t)0, cap + 1, rocprim::plus<uint64_t>(), stream);
+}
+
+int cigar_chain_blocks_run(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains, const nts_lift_link* links,
+                           uint64_t n_links, const uint64_t* pair_first, uint64_t n_pairs, nts_chain_pair* pairs, nts_chain_block** blocks, uint64_t* n_blocks,
+                           uint8_t** text, uint64_t* text_first)
+{
+  const bool with_text = text != nullptr;
+  uint64_t entries = 0; // the entries of all chains: good links name different chains, so they link at most that many
+  auto count = [&](uint64_t c, auto) {
+    entries += chains[c].n_cig; // (n_cig <= n_cigar < 2^32 and fewer than 2^32 chains: no wrap)
+    return NTS_OK;
+  };
+  if (const int rc = cig_chains_check(ctx, "nts_cigar_chain_blocks", LIFT_MAX_BASES_LOG2, false, chains, n_chains, n_cigar, count)) return rc;
+  if (entries > 0xFFFFFFFFull) return fail(ctx, NTS_ERANGE, "nts_cigar_chain_blocks: the chains hold 2^32 entries or more");
+  for (uint64_t p = 0; p <= n_pairs; ++p) { // (a loop over pairs: none over links)
+    const bool bad = p == 0 ? pair_first[0] != 0 : pair_first[p] < pair_first[p - 1];
+    if (bad || (p == n_pairs && pair_first[p] != n_links) || pair_first[p] > n_links)
+      return fail(ctx, NTS_EINVAL, "nts_cigar_chain_blocks: pair_first[" + std::to_string(p) + "]: pair_first is not nondecreasing from 0 to n_links");
+  }
+  const uint64_t cap = std::max<uint64_t>(entries, 1), rows = cap + 1;
+  // (its own buffers first: while nothing is queued, a request that fails may still return at once)
+  NTS_WS(d_links, nts_lift_link*, "cchn_links", std::max<uint64_t>(n_links, 1) * sizeof(nts_lift_link));
+  NTS_WS(d_first, uint64_t*, "cchn_first", (n_pairs + 1) * 8);
+  NTS_WS(d_owner, uint32_t*, "cchn_owner", std::max<uint64_t>(n_chains, 1) * 4);
+  NTS_WS(d_place, LpairPlace*, "cchn_place", std::max<uint64_t>(n_links, 1) * sizeof(LpairPlace));
+  NTS_WS(d_pair_of, uint32_t*, "cchn_pair_of", std::max<uint64_t>(n_links, 1) * 4);
+  NTS_WS(d_count, uint64_t*, "cchn_count", std::max<uint64_t>(n_links, 1) * 8);
+  NTS_WS(d_ln, uint64_t*, "cchn_ln", (n_links + 1) * 8);
+  NTS_WS(d_in, uint64_t*, "cchn_in", CCHN_COLUMNS * rows * 8);
+  NTS_WS(d_pre, uint64_t*, "cchn_pre", CCHN_COLUMNS * rows * 8);
+  NTS_WS(d_link_of, uint32_t*, "cchn_link_of", cap * 4);
+  NTS_WS(d_head_at, uint32_t*, "cchn_head_at", cap * 4);
+  NTS_WS(d_blocks, nts_chain_block*, "cchn_blocks", cap * sizeof(nts_chain_block));
+  NTS_WS(d_bytes, uint64_t*, "cchn_bytes", rows * 8);
+  NTS_WS(d_tb, uint64_t*, "cchn_tb", rows * 8);
+  NTS_WS(d_pairs, nts_chain_pair*, "cchn_pairs", std::max<uint64_t>(n_pairs, 1) * sizeof(nts_chain_pair));
+  NTS_WS(d_tfirst, uint64_t*, "cchn_tfirst", (n_pairs + 1) * 8);
+  NTS_WS(d_worst, uint32_t*, "cchn_worst", 2 * 4);
+  size_t tmp_l = 0, tmp_v = 0, tmp_b = 0; // the three scans' temporary: a buffer of its own ("ivs_tmp" is the stage's, fetched once inside it)
+  HIP_TRY(ctx, cchn_link_scan(nullptr, tmp_l, d_count, d_ln, n_links, ctx->stream));
+  HIP_TRY(ctx, cchn_entry_scan(nullptr, tmp_v, d_in, d_pre, cap, ctx->stream));
+  HIP_TRY(ctx, cchn_byte_scan(nullptr, tmp_b, d_bytes, d_tb, cap, ctx->stream));
+  NTS_WS(d_tmp, void*, "cchn_tmp", std::max<size_t>(std::max(tmp_l, std::max(tmp_v, tmp_b)), 16));
+  std::vector<nts_chain_pair> host_pairs(n_pairs); // (the caller's arrays are written only when the call succeeds)
+  std::vector<uint64_t> host_first(n_pairs + 1, 0);
+  uint32_t worst[2] = { SCRIPT_OK, SCRIPT_OK }; // the smallest offending chain, link
+  uint64_t num[2] = { 0, 0 };                   // blocks, text bytes
+  CigIndex ix; // columns PA, PB
+  hipError_t e_run, e_behind = hipSuccess;
+  auto pass_one = [&] { // behind the stage's check, under its timer
+    if (n_links == 0) return;
+    e_behind = hipMemcpyAsync(d_first, pair_first, (n_pairs + 1) * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (e_behind == hipSuccess) e_behind = hipMemcpyAsync(d_links, links, n_links * sizeof(nts_lift_link), hipMemcpyHostToDevice, ctx->stream);
+    if (e_behind != hipSuccess) return;
+    NTS_LAUNCH(k_lpair_claim, IVL_GRID(n_links), (const nts_lift_link*)d_links, n_links, n_chains, d_owner);
+    NTS_LAUNCH(k_lpair_twice, IVL_GRID(n_links), (const nts_lift_link*)d_links, n_links, n_chains, d_owner);
+    NTS_LAUNCH(k_cchn_links, IVL_GRID(n_links), ix.chains, n_chains, n_cigar, (const nts_lift_link*)d_links, n_links, (const uint64_t*)d_first, n_pairs,
+               (const uint32_t*)d_owner, d_place, d_pair_of, d_count, ix.status);
+    e_behind = rocprim::reduce(ix.tmp, ix.tmp_bytes, ix.status, d_worst, SCRIPT_OK, n_links, ScriptMin(), ctx->stream);
+    if (e_behind == hipSuccess) e_behind = cchn_link_scan(d_tmp, tmp_l, d_count, d_ln, n_links, ctx->stream);
+  };
+  if (const int rc = cig_index_stage<ChainBasesOf>(ctx, "chain_blocks_scan", cigar, n_cigar, chains, n_chains, n_links, &worst[0], ix, e_run, pass_one)) return rc;
+  if (e_run == hipSuccess) e_run = e_behind;
+  if (e_run == hipSuccess && n_links) { // (no link: nothing more is launched)
+    ScopedTimer t(ctx, "chain_blocks_emit", true);
+    NTS_LAUNCH(k_cchn_cols, IVL_GRID(rows), ix.cigar, n_cigar, (const LpairPlace*)d_place, (const uint32_t*)d_pair_of, (const uint64_t*)d_ln, n_links,
+               (const uint64_t*)d_first, n_pairs, cap, d_in, d_link_of);
+    e_run = cchn_entry_scan(d_tmp, tmp_v, d_in, d_pre, cap, ctx->stream);
+    if (e_run == hipSuccess) {
+      NTS_LAUNCH(k_cchn_heads, IVL_GRID(cap), (const uint64_t*)(d_in + 4 * rows), (const uint64_t*)(d_pre + 4 * rows), cap, d_head_at);
+      NTS_LAUNCH(k_cchn_blocks, IVL_GRID(rows), (const uint32_t*)d_head_at, (const uint32_t*)d_link_of, (const uint32_t*)d_pair_of, (const uint64_t*)d_ln, n_links,
+                 (const uint64_t*)d_first, n_pairs, (const uint64_t*)d_pre, cap, d_blocks, d_bytes);
+      if (n_pairs)
+        NTS_LAUNCH(k_cchn_pairs, IVL_GRID(n_pairs), (const LpairPlace*)d_place, (const uint32_t*)d_head_at, (const uint32_t*)d_link_of, (const uint64_t*)d_ln,
+                   n_links, (const uint64_t*)d_first, n_pairs, (const uint64_t*)d_pre, cap, ix.column(0), ix.column(1), n_cigar, d_pairs);
+    }
+  }
+  if (e_run == hipSuccess && n_links && with_text) {
+    ScopedTimer t(ctx, "chain_text", true);
+    e_run = cchn_byte_scan(d_tmp, tmp_b, d_bytes, d_tb, cap, ctx->stream);
+    if (e_run == hipSuccess)
+      NTS_LAUNCH(k_cchn_text_firsts, IVL_GRID(n_pairs + 1), (const uint64_t*)d_ln, n_links, (const uint64_t*)d_first, n_pairs, (const uint64_t*)(d_pre + 4 * rows),
+                 (const uint64_t*)d_tb, cap, d_tfirst);
+  }
+  if (e_run == hipSuccess) e_run = hipGetLastError();
+  if (e_run == hipSuccess && n_links) e_run = hipMemcpyAsync(&worst[1], d_worst, 4, hipMemcpyDeviceToHost, ctx->stream);
+  if (e_run == hipSuccess && n_links) e_run = hipMemcpyAsync(&num[0], d_pre + 4 * rows + cap, 8, hipMemcpyDeviceToHost, ctx->stream);
+  if (e_run == hipSuccess && n_links && with_text) e_run = hipMemcpyAsync(&num[1], d_tb + cap, 8, hipMemcpyDeviceToHost, ctx->stream);
+  if (e_run == hipSuccess && n_links && n_pairs)
+    e_run = hipMemcpyAsync(host_pairs.data(), d_pairs, n_pairs * sizeof(nts_chain_pair), hipMemcpyDeviceToHost, ctx->stream);
+  if (e_run == hipSuccess && n_links && with_text) e_run = hipMemcpyAsync(host_first.data(), d_tfirst, (n_pairs + 1) * 8, hipMemcpyDeviceToHost, ctx->stream);
+  hipError_t e_sync = hipStreamSynchronize(ctx->stream); // (whatever happened: the caller's arrays were sources of asynchronous copies)
+  HIP_TRY(ctx, e_run);
+  HIP_TRY(ctx, e_sync);
+  if (worst[0] != SCRIPT_OK)
+    return fail(ctx, NTS_EINVAL, "nts_cigar_chain_blocks: the entries of chain " + std::to_string(worst[0]) + " are no CIGAR of its lengths");
+  if (worst[1] != SCRIPT_OK) return fail(ctx, NTS_EINVAL, "nts_cigar_chain_blocks: link " + std::to_string(worst[1]) + " is no placement of its chain");
+  const uint64_t nb = num[0], text_bytes = num[1];
+  if (nb > 0xFFFFFFFFull || nb > cap) return fail(ctx, NTS_ERANGE, "nts_cigar_chain_blocks: 2^32 blocks or more");
+  if (text_bytes > 0xFFFFFFFFull) return fail(ctx, NTS_ERANGE, "nts_cigar_chain_blocks: a text of 2^32 bytes or more");
+  nts_chain_block* host_blocks = nullptr;
+  uint8_t* host_text = nullptr;
+  if (nb) { // (the stream is idle: the text's buffer is fetched before its kernel is queued)
+    const uint64_t words = (text_bytes + 3) / 4; // (the device buffer is padded to whole words)
+    uint32_t* d_text = nullptr;
+    if (with_text) {
+      d_text = (uint32_t*)ws_get(ctx, "cchn_text", std::max<uint64_t>(words, 1) * 4);
+      if (!d_text) return NTS_ENOMEM;
+    }
+    host_blocks = (nts_chain_block*)malloc(nb * sizeof(nts_chain_block));
+    if (with_text) host_text = (uint8_t*)malloc(std::max<uint64_t>(text_bytes, 1));
+    if (!host_blocks || (with_text && !host_text)) {
+      free(host_blocks);
+      free(host_text);
+      return fail(ctx, NTS_ENOMEM, "nts_cigar_chain_blocks: no host memory for the blocks");
+    }
+    if (with_text) {
+      ScopedTimer t(ctx, "chain_text", true);
+      NTS_LAUNCH(k_cchn_text, IVL_GRID(words), (const nts_chain_block*)d_blocks, nb, (const uint64_t*)d_tb, d_text, words);
+    }
+    e_run = hipGetLastError();
+    if (e_run == hipSuccess) e_run = hipMemcpyAsync(host_blocks, d_blocks, nb * sizeof(nts_chain_block), hipMemcpyDeviceToHost, ctx->stream);
+    if (e_run == hipSuccess && with_text && text_bytes) e_run = hipMemcpyAsync(host_text, d_text, text_bytes, hipMemcpyDeviceToHost, ctx->stream);
+    e_sync = hipStreamSynchronize(ctx->stream);
+    if (e_run != hipSuccess || e_sync != hipSuccess) {
+      free(host_blocks);
+      free(host_text);
+    }
+    HIP_TRY(ctx, e_run);
+    HIP_TRY(ctx, e_sync);
+  }
+  if (n_pairs) memcpy(pairs, host_pairs.data(), n_pairs * sizeof(nts_chain_pair)); // (zeros where nothing was linked)
+  *blocks = host_blocks;
+  *n_blocks = nb;
+  if (with_text) {
+    *text = host_text;
+    memcpy(text_first, host_first.data(), (n_pairs + 1) * 8);
+  }
+  return NTS_OK;
+}

@@ -1064,6 +1064,21 @@ extern "C" int nts_cigar_lift_pairs(nts_ctx* ctx, const uint64_t* cigar, uint64_
   return cigar_lift_pairs_run(ctx, cigar, n_cigar, chains, n_chains, links, n_links, pair_first, n_pairs, ranges, n_ranges, stats);
 }
 
+extern "C" int nts_cigar_chain_blocks(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains,
+                                      const nts_lift_link* links, uint64_t n_links, const uint64_t* pair_first, uint64_t n_pairs, nts_chain_pair* pairs,
+                                      nts_chain_block** blocks, uint64_t* n_blocks, uint8_t** text, uint64_t* text_first)
+{
+  if (!ctx) return NTS_EINVAL;
+  if (n_cigar > 0xFFFFFFFFull || n_chains > 0xFFFFFFFFull) // (before any array is read)
+    return fail(ctx, NTS_ERANGE, "nts_cigar_chain_blocks: 2^32 entries or chains or more");
+  if (n_links > 0xFFFFFFFFull || n_pairs > 0xFFFFFFFFull) return fail(ctx, NTS_ERANGE, "nts_cigar_chain_blocks: 2^32 links or pairs or more");
+  if ((n_cigar && !cigar) || (n_chains && !chains) || (n_links && !links) || !pair_first || (n_pairs && !pairs) || !blocks || !n_blocks ||
+      (text == nullptr) != (text_first == nullptr))
+    return fail(ctx, NTS_EINVAL, "nts_cigar_chain_blocks: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return cigar_chain_blocks_run(ctx, cigar, n_cigar, chains, n_chains, links, n_links, pair_first, n_pairs, pairs, blocks, n_blocks, text, text_first);
+}
+
 extern "C" int nts_graph_budget(nts_ctx* ctx, uint64_t bytes)
 {
   if (!ctx) return NTS_EINVAL;

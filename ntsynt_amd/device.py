@@ -86,6 +86,10 @@ PAIR_RANGE_DTYPE = np.dtype([("pair", "<u4"), ("side", "<u4"), ("lo", "<u8"), ("
 PAIR_STATS_DTYPE = np.dtype([(n, "<u8") for n in ("src_lo", "src_hi", "oth_lo", "oth_hi", "eq", "x", "src_gap", "oth_gap", "src_open", "oth_open")] +
                             [(n, "<u4") for n in ("src_gaps", "oth_gaps", "link_lo", "link_hi", "n_links", "reserved")] + [("reserved2", "<u8", (3,))])
 
+# nts_chain_block / nts_chain_pair: what Context.cigar_chain_blocks returns, one per block of a liftover chain and one per pair
+CHAIN_BLOCK_DTYPE = np.dtype([(n, "<u8") for n in ("size", "dt", "dq")])
+CHAIN_PAIR_DTYPE = np.dtype([(n, "<u8") for n in ("a0", "a1", "b0", "b1", "eq", "x", "first_block")] + [("n_blocks", "<u4"), ("reserved", "<u4")])
+
 
 class Context:
     """One per GPU (owns a HIP stream)."""
@@ -544,6 +548,51 @@ class Context:
                                                  rs.ctypes.data if rs.size else None, rs.size, stats.ctypes.data if stats.size else None),
                    "nts_cigar_lift_pairs")
         return stats
+
+    def cigar_chain_blocks(self, cigar, chains, links, pair_first, text=True):
+        """one liftover chain per pair of chains: the blocks of a UCSC chain file and their text (nts_cigar_chain_blocks).  cigar, chains,
+        links and pair_first as for cigar_lift_pairs.  Returns (pairs, blocks) or, with text, (pairs, blocks, text, text_first): pairs a
+        CHAIN_PAIR_DTYPE array, one record per pair -- [a0, a1) x [b0, b1) the liftover chain in the pair's oriented offsets from its
+        first match column to behind its last, eq and x its = and X columns, blocks[first_block:first_block + n_blocks] its blocks, every
+        field 0 for a pair without a match column; blocks a CHAIN_BLOCK_DTYPE array -- size, the columns of a maximal run of = / X with
+        no gap of non-zero width inside, and dt, dq, the A and B bases of all gaps between it and the next block (D, I and the open
+        stretches between linked chains), 0 for a pair's last block; text a uint8 array, per block the line "size\\tdt\\tdq\\n", for a
+        pair's last block "size\\n"; pair p's lines are text[text_first[p]:text_first[p + 1]], text_first [P + 1] uint64.  The span and
+        count identities of every pair are checked (RuntimeError).  Entries that are no CIGAR of the chains' lengths and links that are
+        no placement of their chain are refused.  Exact and deterministic."""
+        cg = np.ascontiguousarray(cigar, dtype=np.uint64)
+        ch = np.ascontiguousarray(chains, dtype=CHAIN_DTYPE)
+        lk = np.ascontiguousarray(links, dtype=LIFT_LINK_DTYPE)
+        pf = np.ascontiguousarray(pair_first, dtype=np.uint64)
+        if cg.ndim != 1 or ch.ndim != 1 or lk.ndim != 1 or pf.ndim != 1 or pf.size < 1:
+            raise ValueError("cigar_chain_blocks: a list of entries, of chain records, of links and of pairs' first links (one more than pairs)")
+        assert LIFT_LINK_DTYPE.itemsize == ctypes.sizeof(_lib.LiftLink) and CHAIN_DTYPE.itemsize == ctypes.sizeof(_lib.CigChain)
+        assert CHAIN_BLOCK_DTYPE.itemsize == ctypes.sizeof(_lib.ChainBlock) == 24 and CHAIN_PAIR_DTYPE.itemsize == ctypes.sizeof(_lib.ChainPair) == 64
+        pairs = np.zeros(pf.size - 1, dtype=CHAIN_PAIR_DTYPE)
+        firsts = np.zeros(pf.size, dtype=np.uint64)
+        p_blocks, p_text, n_blocks = c_vp(), c_vp(), u64()
+        self.check(self.lib.nts_cigar_chain_blocks(self.h, cg.ctypes.data if cg.size else None, cg.size, ch.ctypes.data if ch.size else None, ch.size,
+                                                   lk.ctypes.data if lk.size else None, lk.size, pf.ctypes.data, pf.size - 1,
+                                                   pairs.ctypes.data if pairs.size else None, ctypes.byref(p_blocks), ctypes.byref(n_blocks),
+                                                   ctypes.byref(p_text) if text else None, firsts.ctypes.data if text else None),
+                   "nts_cigar_chain_blocks")
+        blocks = self._take(p_blocks, n_blocks.value, CHAIN_BLOCK_DTYPE)
+        chars = self._take(p_text, int(firsts[-1]), np.dtype("u1")) if text else None
+        # the identities of docs/design/04_28_block_chain.md, per pair through prefix sums: no loop over blocks
+        sums = np.zeros((3, blocks.size + 1), dtype=np.uint64)
+        for row, name in zip(sums, ("size", "dt", "dq")):
+            np.cumsum(blocks[name], out=row[1:])
+        lo, hi = pairs["first_block"], pairs["first_block"] + pairs["n_blocks"]
+        if blocks.size != int(pairs["n_blocks"].sum()) or (pairs.size and int(hi.max()) > blocks.size):
+            raise RuntimeError("cigar_chain_blocks: the pairs' blocks do not tile the block list")
+        size, dt, dq = (row[hi] - row[lo] for row in sums)
+        is_last = np.zeros(blocks.size, dtype=bool)
+        is_last[(hi[pairs["n_blocks"] > 0] - 1).astype(np.int64)] = True
+        if not (np.array_equal(pairs["a1"] - pairs["a0"], size + dt) and np.array_equal(pairs["b1"] - pairs["b0"], size + dq) and
+                np.array_equal(pairs["eq"] + pairs["x"], size) and bool((blocks["size"] > 0).all()) and
+                np.array_equal((blocks["dt"] + blocks["dq"]) == 0, is_last)):
+            raise RuntimeError("cigar_chain_blocks: a liftover chain breaks its span or count identities")
+        return (pairs, blocks, chars, firsts) if text else (pairs, blocks)
 
     def timing(self, name):
         ms, n = ctypes.c_double(), u64()

@@ -499,7 +499,7 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         graph_budget=None, assess=None, gaps=False, gap_links=None, gap_block_links=False, gap_copies=None, gap_copy_sites=None,
         gap_periods=None, gap_families=None, block_identity=None, block_variants=None, block_wide_variants=None, block_ends=None,
         block_end_variants=False, block_paf=None, block_lift=None, block_lift_identity=None, block_windows=None, block_lift_joined=None,
-        block_paf_cs=False):
+        block_paf_cs=False, block_chain=None):
     """FASTA paths -> engine (outputs in .outputs and in the CWD).  Mirrors oracle.synteny_oracle.run_pipeline's
     signature so the parity tests read alike.  Under torch.distributed (WORLD_SIZE > 1, process group already
     initialised by the caller) genomes are sharded over the ranks.
@@ -544,7 +544,10 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
     cg:Z: CIGAR per aligned chain of every block and pair, from a pass of its own; one rank only; it needs none of the other switches);
     with `benchmark` the stage times gain block_paf:cigar_atoms and block_paf:cigar_merge.  block_paf_cs: needs block_paf; every record
     also carries the cs:Z: tag, both tag texts made on the device (nts_cigar_text, one call per round); with `benchmark` the stage
-    times gain block_paf:cigar_text_scan and block_paf:cigar_text_emit.  block_lift =(bed_path, genome, k, rate, band,
+    times gain block_paf:cigar_text_scan and block_paf:cigar_text_emit.  block_chain = (k, rate, band, max_len, max_edits, ends), as block_paf and equal to it
+    where both are given: <prefix>.block_alignments.chain, one UCSC liftover chain per pair (assess.block_chains; stage block_chain behind
+    block_paf, whose pass then serves both files; with `benchmark` the stage times gain block_chain:chain_blocks_scan,
+    block_chain:chain_blocks_emit and block_chain:chain_text).  block_lift =(bed_path, genome, k, rate, band,
     max_len, max_edits, ends): behind that file, <prefix>.block_lift.tsv (assess.block_lift: the BED intervals of `genome`, a FASTA base
     name, mapped through the block alignments into the other genomes; one rank only; it needs none of the other switches; with
     block_paf, which then takes the same parameters, the pass of the stage block_paf serves both files); with `benchmark` the stage times
@@ -648,6 +651,18 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         message = check_identity_parameters(*block_paf[:5]) or (check_ends_parameters(*block_paf[5]) if block_paf[5] is not None else None)
         if message:
             raise ValueError("block_paf = (k, rate, band, max_len, max_edits, ends): " + message)
+    if block_chain is not None:
+        if world > 1 or (mx_tsvs is not None and initial_only):
+            raise ValueError("block_chain needs every genome resident on one GPU (one rank, genomes loaded)")
+        from .assess import check_ends_parameters, check_identity_parameters
+        if len(block_chain) != 6 or (block_chain[5] is not None and len(block_chain[5]) != 3):
+            raise ValueError("block_chain = (k, rate, band, max_len, max_edits, ends) with ends = (ends_max_len, ends_max_edits, ends_penalty) or None")
+        block_chain = tuple(int(x) for x in block_chain[:5]) + (tuple(int(x) for x in block_chain[5]) if block_chain[5] is not None else None,)
+        message = check_identity_parameters(*block_chain[:5]) or (check_ends_parameters(*block_chain[5]) if block_chain[5] is not None else None)
+        if message:
+            raise ValueError("block_chain = (k, rate, band, max_len, max_edits, ends): " + message)
+        if block_paf is not None and block_paf != block_chain:
+            raise ValueError("block_paf and block_chain take the same (k, rate, band, max_len, max_edits, ends)")
     if block_lift is not None:
         if world > 1 or (mx_tsvs is not None and initial_only):
             raise ValueError("block_lift needs every genome resident on one GPU (one rank, genomes loaded)")
@@ -1333,6 +1348,11 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
     if joining and benchmark:
         joined_before = {name: backend.ctx.timing(name)[0] for name in joined_timers}
 
+    chaining = block_chain is not None
+    chain_parts = None                                        # chain_table's parts, once block_paf's pass has made them beside the PAF
+    chain_timers = ("chain_blocks_scan", "chain_blocks_emit", "chain_text")
+    more = {"chain": True} if chaining else {}               # (only with the switch on: a run without it makes the calls it always made)
+
     def joined_pass(with_paf):
         "with block_lift_joined the one pass is assess.block_lifts: (PAF rows, lift rows, [counted rows per table], [joined rows per table]), None for what is off"
         from . import assess as assess_
@@ -1341,8 +1361,9 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         windows = assess_.window_intervals(assess_.record_sizes(by_name, block_lift_joined[0]), block_windows[0]) if block_windows is not None else None
         got = assess_.block_lifts(backend.ctx, by_name, assess_.read_blocks(f"{prefix}.synteny_blocks.tsv"), block_lift_joined[0], *block_lift_joined[1:6],
                                   ends=block_lift_joined[6], lift=bed, identity=([bed] if block_lift_identity is not None else []) + ([windows] if windows is not None else []),
-                                  joined=([bed] if bed is not None else []) + ([windows] if windows is not None else []), paf=with_paf, cs=bool(block_paf_cs))
-        return got["paf"], got["lift"], got["identity"], got["joined"]
+                                  joined=([bed] if bed is not None else []) + ([windows] if windows is not None else []), paf=with_paf, cs=bool(block_paf_cs),
+                                  **(more if with_paf else {}))
+        return (got["paf"], got["lift"], got["identity"], got["joined"]) + ((got["chain"],) if with_paf and chaining else ())
 
     def counted_pass(with_paf):
         "the one pass that serves block_paf, block_lift, block_lift_identity and block_windows: (PAF rows, lift rows, [counted rows per table]), None for what is off"
@@ -1355,7 +1376,7 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         table_rows = assess_.read_blocks(f"{prefix}.synteny_blocks.tsv")
         if with_paf:
             return assess_.block_alignments(backend.ctx, by_name, table_rows, *given[2:7], ends=given[7], lift=(source, bed) if bed is not None else None,
-                                            lift_identity=(source, sets), cs=bool(block_paf_cs))
+                                            lift_identity=(source, sets), cs=bool(block_paf_cs), **more)
         got = assess_.block_lift_identity(backend.ctx, by_name, table_rows, source, sets, *given[2:7], ends=given[7], lift=bed)
         return (None,) + (got if bed is not None else (None, got))
     if block_paf is not None:
@@ -1364,17 +1385,24 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         if benchmark:                                         # (device events around the calls of this stage only)
             backend.ctx.profile(True)
             paf_timers = ("cigar_atoms", "cigar_merge") + (("cigar_text_scan", "cigar_text_emit") if block_paf_cs else ())
-            paf_before = {name: backend.ctx.timing(name)[0] for name in paf_timers + lift_timers + stats_timers}
+            paf_before = {name: backend.ctx.timing(name)[0] for name in paf_timers + lift_timers + stats_timers + (chain_timers if chaining else ())}
         if joining:                                           # (one pass serves every file)
-            paf_rows, lifted_rows, counted_rows, joined_rows = joined_pass(True)
+            paf_rows, lifted_rows, counted_rows, joined_rows, *chain_made = joined_pass(True)
         elif counting:                                        # (one pass serves every file)
-            paf_rows, lifted_rows, counted_rows = counted_pass(True)
+            paf_rows, lifted_rows, counted_rows, *chain_made = counted_pass(True)
         else:
             paf_rows = assess_.block_alignments(backend.ctx, {fa.basename(p): genomes[p] for p in fastas}, assess_.read_blocks(f"{prefix}.synteny_blocks.tsv"),
                                                 *block_paf[:5], ends=block_paf[5],
-                                                lift=(block_lift[1], assess_.read_bed(block_lift[0])) if block_lift is not None else None, cs=bool(block_paf_cs))
+                                                lift=(block_lift[1], assess_.read_bed(block_lift[0])) if block_lift is not None else None, cs=bool(block_paf_cs),
+                                                **more)
+            chain_made = []
+            if chaining:                                      # (one pass serves the PAF and the chain file)
+                paf_rows, chain_made = paf_rows[:-1], [paf_rows[-1]]
+                paf_rows = paf_rows[0] if len(paf_rows) == 1 else paf_rows
             if block_lift is not None:                        # (one pass serves both files)
                 paf_rows, lifted_rows = paf_rows
+        if chaining:
+            chain_parts = chain_made[0]
         text = assess_.paf_table(paf_rows)
         with open(f"{prefix}.block_alignments.paf", "w", encoding="utf-8") as fh:
             fh.write(text)
@@ -1384,8 +1412,29 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
             st.rows += [(f"block_paf:{name}", (backend.ctx.timing(name)[0] - paf_before[name]) * 1e-3) for name in paf_timers]
             lift_times = [(f"block_lift:{name}", (backend.ctx.timing(name)[0] - paf_before[name]) * 1e-3) for name in lift_timers]
             stats_times = [(name, (backend.ctx.timing(name)[0] - paf_before[name]) * 1e-3) for name in stats_timers]
+            chain_times = [(f"block_chain:{name}", (backend.ctx.timing(name)[0] - paf_before[name]) * 1e-3) for name in (chain_timers if chaining else ())]
             backend.ctx.profile(False)
         st.mark("block_paf_done")
+    if chaining:
+        st.start("block_chain")
+        from . import assess as assess_
+        if chain_parts is None:                               # (without block_paf: a pass of its own)
+            if benchmark:                                     # (device events around the calls of this stage only)
+                backend.ctx.profile(True)
+                chain_before = {name: backend.ctx.timing(name)[0] for name in chain_timers}
+            chain_parts = assess_.block_chains(backend.ctx, {fa.basename(p): genomes[p] for p in fastas}, assess_.read_blocks(f"{prefix}.synteny_blocks.tsv"),
+                                               *block_chain[:5], ends=block_chain[5])
+            if benchmark:
+                chain_times = [(f"block_chain:{name}", (backend.ctx.timing(name)[0] - chain_before[name]) * 1e-3) for name in chain_timers]
+                backend.ctx.profile(False)
+        text = assess_.chain_table(chain_parts)
+        with open(f"{prefix}.block_alignments.chain", "w", encoding="utf-8") as fh:
+            fh.write(text)
+        eng.outputs[f"{prefix}.block_alignments.chain"] = text
+        st.stop()
+        if benchmark:
+            st.rows += chain_times
+        st.mark("block_chain_done")
     if block_lift is not None:
         st.start("block_lift")
         from . import assess as assess_
