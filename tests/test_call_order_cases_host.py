@@ -16,6 +16,9 @@ NAMES = [e.name for e in C.ENTRIES]
 REQUIRED = ["edit_segments", "edit_wide", "edit_extend", "edit_script", "edit_wide_script", "edit_extend_script", "cigar_build", "cigar_lift",
             "cigar_lift_stats", "cigar_text", "iv_anchor_segments", "iv_links", "iv_sites", "iv_periods", "iv_period_hashes", "iv_families", "iv_family_sites", "hset_sweep", "hcount_capped",
             "minhash", "minhash_intervals", "bloom_insert", "engine_add_blocks"] + ["sketch_" + w for w in ("dense", "pruned_hi", "pruned_full", "tiers", "accept_list")]
+NEW = ["fasta_parse", "graph_build", "graph_build_sliced", "bloom_insert_and", "bloom_cascade", "bloom_repeats", "bf_count_intervals", "bf_sample_intervals",
+       "mx_screen", "minhash_pairs"]                          # the calls of every round
+REQUIRED += NEW
 
 
 def requested(files):
@@ -113,10 +116,98 @@ def test_family_table_against_the_sources():
 
 def test_neighbours_stay_in_the_dozens_and_leave_no_entry_out():
     pairs = C.neighbours()
-    assert len(pairs) == len(set(pairs)) and 24 <= len(pairs) <= 96, len(pairs)
+    assert len(pairs) == len(set(pairs)) and 24 <= len(pairs) <= 120, len(pairs)
     assert {x for x, _ in pairs} | {y for _, y in pairs} == set(NAMES)
     assert ("edit_script", "edit_wide_script") in pairs and ("edit_wide_script", "edit_script") in pairs
     assert all((n, C.HEAVY_PARTNER) in pairs for n in NAMES if n != C.HEAVY_PARTNER)
+    # the calls of every round: both builds in both orders, the engine behind and before a sliced build and before a one-pass build, the
+    # FASTA parse with every way of the sketch, the first way into a filter with each of the others, the two filter sweeps
+    both = [("graph_build", "graph_build_sliced"), ("graph_build_sliced", "engine_add_blocks"), ("bf_count_intervals", "bf_sample_intervals")]
+    both += [("fasta_parse", "sketch_" + w) for w in C.SKETCH_WAYS] + [("bloom_insert", n) for n in ("bloom_insert_and", "bloom_cascade", "bloom_repeats")]
+    for x, y in both:
+        assert (x, y) in pairs and (y, x) in pairs, (x, y)
+    assert ("engine_add_blocks", "graph_build") in pairs
+    assert set(C.PAIRED) <= set(pairs)
+
+
+def functions(files):
+    """{name: body} of the functions defined at the left margin of the given sources (a signature may run over several lines; the body
+    ends at the first closing brace at the left margin)"""
+    out = {}
+    for f in files:
+        with open(os.path.join(CSRC, f)) as fh:
+            lines = fh.read().split("\n")
+        i = 0
+        while i < len(lines):
+            m = re.match(r'^(?:extern "C" )?[A-Za-z_][\w:<>\*&, ]*?\b([A-Za-z_]\w*)\(', lines[i])
+            if not m or lines[i].rstrip().endswith(";"):
+                i += 1
+                continue
+            if "{" in lines[i] and lines[i].rstrip().endswith("}"):
+                out.setdefault(m.group(1), []).append(lines[i])
+                i += 1
+                continue
+            j = i + 1
+            while j < len(lines) and lines[j] != "{" and not lines[j].rstrip().endswith(";") and (lines[j].startswith(" ") or not lines[j]):
+                j += 1
+            if j >= len(lines) or lines[j] != "{":
+                i += 1
+                continue
+            e = j
+            while e < len(lines) and lines[e] != "}":
+                e += 1
+            out.setdefault(m.group(1), []).append("\n".join(lines[i:e + 1]))
+            i = e + 1
+    return {name: "\n".join(bodies) for name, bodies in out.items()}
+
+
+SCRATCH = re.compile(r'\b(?:ws_get|NTS_WS|ws_upload)\(')
+ROUND_FILES = ["nts_graph.hip", "nts_fasta_dev.inc", "nts_bf_iv.inc", "nts_bf_sample.inc", "nts_comm.inc"]
+
+
+def test_every_exported_function_that_requests_scratch_in_the_round_files_is_named():
+    """read from the sources: the functions of nts_graph.hip, nts_fasta_dev.inc, nts_bf_iv.inc, nts_bf_sample.inc and nts_comm.inc that
+    request scratch (ws_get / NTS_WS / ws_upload), and the library's exported functions (those ntsynt_amd/_lib.py binds) that are one of
+    them or reach one through the functions they call, in any source.  Each is called by a catalogue entry (C.CALLS), by the rank test
+    (its CALLS), or has an order test of its own"""
+    from tests import test_gpu_call_order_ranks as R
+    sources = [f for f in sorted(os.listdir(CSRC)) if f.endswith((".inc", ".hip", ".h", ".cpp"))]
+    every = functions(sources)
+    asking = {name for name, body in functions(ROUND_FILES).items() if SCRATCH.search(body.split("\n", 1)[-1])}
+    assert {"graph_build_ranges", "slice_bufs", "nts_genome_from_fasta", "nts_mx_kmers", "bf_count_intervals_run", "sample_intervals_run",
+            "nts_bf_allreduce_parts", "nts_mx_allgather_ex"} <= asking, sorted(asking)
+    code = {name: re.sub(r'"(?:[^"\\\n]|\\.)*"', '""', re.sub(r"//[^\n]*", "", body)) for name, body in every.items()}      # (no comments, no strings)
+    calls = {name: {w for w in set(re.findall(r"\b[A-Za-z_]\w*\b", body)) if w in every and w != name} for name, body in code.items()}
+    reach = set(asking)
+    grew = True
+    while grew:
+        grew = False
+        for name, callees in calls.items():
+            if name not in reach and callees & reach:
+                reach.add(name)
+                grew = True
+    with open(os.path.join(os.path.dirname(CSRC), "_lib.py")) as fh:
+        exported = set(re.findall(r'\("(nts_\w+)"', fh.read()))
+    assert len(exported) > 100
+    need = sorted(reach & exported)
+    print("exported functions that request scratch in the round files:", need)
+    assert {"nts_graph_build", "nts_engine_add", "nts_genome_from_fasta", "nts_bf_count_intervals", "nts_bf_sample_intervals", "nts_mx_kmers",
+            "nts_bf_allreduce_and", "nts_bf_allreduce_groups", "nts_bf_allreduce_parts", "nts_mx_allgather", "nts_mx_allgather_ex"} <= set(need), need
+    named = {fn: entry for entry, fns in C.CALLS.items() for fn in fns}
+    assert set(C.CALLS) <= set(NAMES)
+    for fn in need:
+        if fn in named:
+            continue
+        if fn in R.CALLS:
+            with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "multirank_worker.py")) as fh:
+                assert R.CALLS[fn] in fh.read(), fn
+            continue
+        assert fn in ELSEWHERE, (fn, "requests scratch in the round files and no entry, rank test or order test names it")
+        assert os.path.exists(os.path.join(os.path.dirname(os.path.abspath(__file__)), ELSEWHERE[fn])), fn
+
+
+# exported functions that reach the round files' scratch and have an order test of their own, outside the catalogue
+ELSEWHERE = {}
 
 
 def test_the_chain_seed_leaves_out_no_entry_and_no_size():
@@ -137,6 +228,12 @@ REFUSED_IN = {"edit_segments": "test_gpu_edit_segments.py", "edit_wide": "test_g
               "iv_families": "test_gpu_iv_families.py", "iv_family_sites": "test_gpu_iv_family_sites.py", "hset_sweep": "test_gpu_hset.py",
               "hcount_capped": "test_gpu_hcount.py", "minhash": None, "minhash_intervals": "test_gpu_block_assessment.py", "bloom_insert": None, "engine_add_blocks": None}
 REFUSED_IN.update({"sketch_" + w: "test_gpu_sketch_seams.py" for w in C.SKETCH_WAYS})
+REFUSED_IN.update({name: None for name in NEW})
+# the FASTA parse's own tests refuse a file without a header (tests/test_gpu_fasta.py: the wrapper makes a ValueError of the library's
+# NTS_EFORMAT; the entry goes through the C entry point and Context.check).  tests/test_gpu_block_assessment.py refuses a record index
+# of minhash_intervals, nothing of minhash_pairs.
+REFUSED_IN["fasta_parse"] = "test_gpu_fasta.py"
+REFUSED_AS = {"fasta_parse": 'raises(ValueError, match="not a FASTA file")'}          # what the file holds where it is not NtsError
 
 
 def test_entries_with_a_refused_case_are_the_ones_whose_tests_have_one():
@@ -146,11 +243,12 @@ def test_entries_with_a_refused_case_are_the_ones_whose_tests_have_one():
     for name, f in REFUSED_IN.items():
         if f:
             with open(os.path.join(here, f)) as fh:
-                assert "NtsError" in fh.read(), (name, f)
-    # the calls whose tests refuse nothing: no NtsError is expected anywhere in the files that test them
-    for f in ("test_gpu_bloom_geometry.py", "test_gpu_engine_shapes.py", "test_gpu_interval_edges.py"):
+                assert REFUSED_AS.get(name, "NtsError") in fh.read(), (name, f)
+    # the calls whose tests refuse nothing: nothing is expected to raise anywhere in the files that test them
+    for f in ("test_gpu_bloom_geometry.py", "test_gpu_engine_shapes.py", "test_gpu_interval_edges.py", "test_gpu_fasta_seams.py", "test_gpu_graph_slices.py",
+              "test_gpu_stages.py", "test_gpu_configs.py"):
         with open(os.path.join(here, f)) as fh:
-            assert "raises(NtsError" not in fh.read(), f
+            assert "raises(" not in fh.read(), f
 
 
 def test_expectations_are_plain_bytes_of_the_documented_layouts():

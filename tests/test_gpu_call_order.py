@@ -1,6 +1,7 @@
 """Every device call gives its result after any other (docs/design/04_24_call_order.md).  The entries of tests/call_order_cases.py --
 every entry point that takes named scratch buffers from the context (ws_get) or goes through its pinned staging area -- run in orders
-the other GPU tests never take.  In a context of the test's own (`fresh`: a context's scratch only grows, so only a new one regrows):
+the other GPU tests never take.  In a context of the test's own (`fresh`: but for what a sliced graph build drops, a context's scratch
+only grows, so only a new one regrows):
 small, large, small (every buffer regrows, is freed into the allocation cache and is met again); around a neighbour that requests the
 same scratch names (the neighbour's large call is the regrowth); and small, large, small with the allocation cache emptied, or a freed
 block taken and overwritten by somebody else, between the calls.  In ONE context that every earlier test has grown (`ctx`): a refused
@@ -80,10 +81,62 @@ def test_the_sketch_goes_the_way_its_entry_is_named_for(ctx, way, size):
     assert C.SKETCH_CHECK[way](went), (way, size, went)
 
 
+class Recording:
+    "a context's library with the names of the functions taken from it written down"
+
+    def __init__(self, lib):
+        self._lib, self.seen = lib, set()
+
+    def __getattr__(self, name):
+        self.seen.add(name)
+        return getattr(self._lib, name)
+
+
+@pytest.mark.parametrize("name", sorted(C.CALLS))
+def test_an_entry_calls_the_exported_functions_its_table_names(fresh, name):
+    "C.CALLS is written by hand; that an entry's run() reaches the functions it names is read off the context's library here"
+    lib = fresh.lib
+    fresh.lib = Recording(lib)
+    try:
+        call(fresh, name, "S")
+        seen = fresh.lib.seen
+    finally:
+        fresh.lib = lib
+    assert set(C.CALLS[name]) <= seen, (name, sorted(set(C.CALLS[name]) - seen))
+
+
 # ---- neighbours -----------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("x,y", C.neighbours())
 def test_around_a_neighbour(fresh, x, y):
     play(fresh, [(x, "S"), (y, "L"), (x, "S"), (y, "S"), (x, "L")])
+
+
+@pytest.mark.parametrize("first,second", [("graph_build", "graph_build"), ("graph_build", "graph_build_sliced"), ("graph_build_sliced", "graph_build"),
+                                          ("graph_build_sliced", "graph_build_sliced")])
+def test_two_graph_builds_back_to_back(fresh, first, second):
+    """the graph a build returns lives in the context's scratch until the next build: it is read back in full (inside nts_graph_build,
+    which synchronises behind its copies) before the second build reuses, regrows or drops that scratch, and a second build of the same
+    case behind it gives the bytes the first gave"""
+    before = call(fresh, first, "S")
+    call(fresh, second, "L", [(first, "S")])
+    assert call(fresh, first, "S", [(first, "S"), (second, "L")]) == before
+    assert call(fresh, second, "S", [(second, "L"), (first, "S")]) == before      # (one case, one graph, whatever the slices)
+
+
+@pytest.mark.parametrize("size", C.SIZES)
+def test_the_sliced_build_has_the_slices_its_entry_is_named_for(ctx, size):
+    call(ctx, "graph_build_sliced", size)
+    plan = C.case_of("graph_build_sliced", size)["sliced_plan"]
+    print(f"graph_build_sliced at {size}: {plan}")
+    assert plan["v_slices"] >= C.GRAPH_SLICES, (size, plan)
+    assert fresh_budget_is_automatic(ctx)
+
+
+def fresh_budget_is_automatic(ctx):
+    "the budget a sliced entry set is gone: a one-pass build behind it plans one range per pass"
+    call(ctx, "graph_build", "S")
+    plan = ctx.graph_last_plan()
+    return plan["v_slices"] == 1 and plan["e_slices"] == 1
 
 
 # ---- the cache in between -------------------------------------------------------------------------------------------------------------

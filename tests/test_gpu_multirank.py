@@ -284,9 +284,18 @@ def test_packed_exchange_on_one_rank_round_trips_every_shape_and_refuses_unorder
             pos = rng.integers(0, (1 << 40) if case == 3 else (1 << 31), size=n).astype(np.uint64)
             h1 = rng.integers(0, 1 << 63, size=n).astype(np.uint64)
             lists.append((h1, rec, pos))
+        # the boundary between the two packed widths: a list whose largest position is exactly 2^32 - 1 (32 bits) and one whose largest
+        # is exactly 2^32 (64 bits), of an odd and an even length, so that the position block and the start table begin on both alignments
+        for n, top in ((1001, (1 << 32) - 1), (1000, 1 << 32)):
+            rec = np.sort(rng.choice(np.arange(2, 30), size=n)).astype(np.uint32)
+            pos = rng.integers(0, (1 << 32) - 1, size=n).astype(np.uint64)
+            pos[n // 3] = top
+            lists.append((rng.integers(0, 1 << 63, size=n).astype(np.uint64), rec, pos))
+        assert max(int(t[2].max()) for t in lists[5:]) == 1 << 32 and int(lists[5][2].max()) == (1 << 32) - 1
+        ids = [4, 0, 2, 1, 3, 6, 5]
         handles = [Minimizers.from_numpy(ctx, *t) for t in lists]
-        out = allgather_minimizers(ctx, None, handles, [4, 0, 2, 1, 3], 5, slots=5)
-        for gid, t in zip([4, 0, 2, 1, 3], lists):
+        out = allgather_minimizers(ctx, None, handles, ids, 7, slots=7)
+        for gid, t in zip(ids, lists):
             got = out[gid].to_numpy()
             for a, b in zip(got, t):
                 assert np.array_equal(a, b), gid
