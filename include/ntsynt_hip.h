@@ -1043,6 +1043,27 @@ typedef struct
 int nts_cigar_text(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains, const nts_genome* a,
                    const nts_genome* b, const nts_cig_span* spans, uint8_t** cg, uint64_t* cg_first, uint8_t** cs, uint64_t* cs_first);
 
+/* ---- the aligned rows of the chains' CIGARs: the sequence lines of `--block-maf` ------------------------------------------------
+ * nts_cigar_rows: cigar, chains, spans, a, b as for nts_cigar_text with spans (the chains TILE the entries; spans, a and b are
+ *   required).  A COLUMN is one unit of an entry's length; chain c has eq + x + ins + del columns and two ROWS of that many bytes.
+ *   Row A: the target base of the column, rec_a[pos_a ...] read forwards, for =, X and D; `-` for I.  Row B: the query base as read
+ *   for =, X and I -- forwards from pos_b, or with NTS_CIG_B_BACKWARDS backwards from pos_b and complemented (3 - code) -- and `-`
+ *   for D.  Upper case ACGT; a code that is no base gives N, complemented or not (the codes carry no soft-masking).  *row_a / *row_b
+ *   (release with nts_free; NULL for empty rows): chain c's rows are bytes [row_first[c], row_first[c + 1]) of BOTH buffers, without
+ *   separator or terminator; row_first: n_chains + 1 host entries.  NTS_ERANGE before any launch: 2^32 entries or chains or more
+ *   (before any array is read), len_a or len_b that add up to 2^62 or more.  NTS_EINVAL before any launch, the smallest chain named:
+ *   chains that do not tile the entries, unknown flag bits, rec_a / rec_b outside its genome, a span outside its record
+ *   (nts_cigar_text's four rules), a NULL genome or NULL spans.  After the scan: NTS_EINVAL "the entries of chain ... are no CIGAR of
+ *   its lengths", NTS_ERANGE for 2^32 columns or more.  A refused call returns no buffer and writes to no caller array.  One
+ *   exclusive scan over all entries gives the global prefixes of (A bases, B bases, columns), nts_cigar_lift's check kernel, a
+ *   minimum reduction and one lane per chain for the firsts (timer "cigar_rows_scan"); ONE kernel makes both rows: one lane per
+ *   aligned 4-byte word finds the entry of its first column by one upper-bound search over the column prefix, composes four bytes
+ *   per row and stores two dwords (timer "cigar_rows_emit").  On the context's stream, in its workspace; no atomic, no launch per
+ *   chain or entry, no floating point: the same input gives the same bytes.  docs/design/04_29_block_maf.md; csrc/nts_cigar.inc;
+ *   ntsynt_amd/assess.py block_alignments(maf=True), `ntSynt --block-maf`, `bin/ntsynt_block_stats --maf-out F`. */
+int nts_cigar_rows(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains, const nts_genome* a,
+                   const nts_genome* b, const nts_cig_span* spans, uint8_t** row_a, uint8_t** row_b, uint64_t* row_first);
+
 /* ---- C1-C5: minimizer graph -> collinear chains -----------------------------------------------------
  * replaces ntjoin_utils.read_minimizers' duplicate removal, filter_minimizers and build_graph
  * (call sites bin/ntsynt_synteny.py:607-612, 483, 539) and the path walk of Ntjoin.find_paths

@@ -310,6 +310,7 @@ SYMBOLS = [
     ("nts_cigar_lift_stats", ctypes.c_int, [c_vp, c_vp, u64, c_vp, u64, c_vp, u64, c_vp]),
     ("nts_cigar_lift_pairs", ctypes.c_int, [c_vp, c_vp, u64, c_vp, u64, c_vp, u64, c_vp, u64, c_vp, u64, c_vp]),
     ("nts_cigar_chain_blocks", ctypes.c_int, [c_vp, c_vp, u64, c_vp, u64, c_vp, u64, c_vp, u64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    ("nts_cigar_rows", ctypes.c_int, [c_vp, c_vp, u64, c_vp, u64, c_vp, c_vp, c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
     ("nts_genome_valid_bases", ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(Interval), u64, c_vp]),
     ("nts_minhash_pairs", ctypes.c_int, [c_vp, u32, c_vp, c_vp, u64, c_vp, c_vp, u64, c_vp, c_vp]),
     ("nts_graph_build", ctypes.c_int, [c_vp, u32, ctypes.POINTER(MxList), ctypes.POINTER(Graph)]),

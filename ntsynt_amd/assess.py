@@ -21,6 +21,8 @@ Two things, both over `<prefix>.synteny_blocks.tsv`:
 * block end variants (`ntSynt --block-ends --block-end-variants`, `ntsynt_block_stats --ends-out F --end-variants-out G`): the edits
   behind left_edits and right_edits -- the canonical script of every extended flank (nts_edit_extend_script), as snv / ins / del
   events in both genomes' coordinates; docs/design/04_21_block_end_variants.md.
+* block MAF (`ntSynt --block-maf`, `ntsynt_block_stats --maf-out`): one pairwise MAF block per PAF record with both aligned rows, made on the
+  GPU (nts_cigar_rows); docs/design/04_29_block_maf.md.
 * block chain file (`ntSynt --block-chain`, `ntsynt_block_stats --chain-out`): one UCSC liftover chain per block and pair, the chains of the
   block alignments joined per pair, blocks and data lines made on the GPU (nts_cigar_chain_blocks); docs/design/04_28_block_chain.md.
 * block alignments (`ntSynt --block-paf`, `ntsynt_block_stats --paf-out`): one PAF record with a cg:Z: CIGAR per aligned chain of every
@@ -815,18 +817,19 @@ def paf_table(rows):
 
 # what one round of the alignment pass produced: the _Round itself, the identity pass's per-interval sums, the flanks and their results (or
 # None), the chains of alignment_pieces (one entry per chain: line, ch, x0, x1, y0, y1), nts_cigar_build's entries and records, and with
-# cs nts_cigar_text's (cg, cg_first, cs, cs_first)
-_AlignmentRound = namedtuple("_AlignmentRound", ["round", "per_iv", "flanks", "results", "chains", "cigar", "records", "texts"], defaults=(None,))
+# cs nts_cigar_text's (cg, cg_first, cs, cs_first), and with maf nts_cigar_rows' (row_a, row_b, row_first) and the spans it was given
+_AlignmentRound = namedtuple("_AlignmentRound", ["round", "per_iv", "flanks", "results", "chains", "cigar", "records", "texts", "rows"], defaults=(None, None))
 
 
-def _alignment_rounds(ctx, genomes_by_name, blocks, k, rate, band, max_len, max_edits, ends, pairs, length, only=None, cs=False):
+def _alignment_rounds(ctx, genomes_by_name, blocks, k, rate, band, max_len, max_edits, ends, pairs, length, only=None, cs=False, maf=False):
     """The per-round body of block_alignments and block_lift over _identity_rounds, as a generator of _AlignmentRound: per round
     nts_edit_segments with the per-segment distances, for max_edits > 0 nts_edit_wide and both script calls, else nts_edit_script alone,
     with ends nts_edit_extend and nts_edit_extend_script, then ONE nts_cigar_build for all pairs of the round.  Per pair the NM of its
     chains less the flanks' edits must be the identity pass's `edits`, and the target and query bases less the flanks' must be aligned_a
     and aligned_b: RuntimeError otherwise.  only: a genome's name -- rounds in which it takes no part are passed over before any edit
     call.  cs: behind nts_cigar_build ONE nts_cigar_text per round over alignment_spans, its four arrays carried as `texts`; without it
-    no call is added."""
+    no call is added.  maf: behind nts_cigar_build ONE nts_cigar_rows per round over the same alignment_spans, its three arrays and the
+    spans carried as `rows`; without it no call is added."""
     import numpy as np
     for r in _identity_rounds(ctx, genomes_by_name, blocks, k, rate, band, max_len, pairs, length):
         if only is not None and only not in (r.name_a, r.name_b):
@@ -859,8 +862,10 @@ def _alignment_rounds(ctx, genomes_by_name, blocks, k, rate, band, max_len, max_
                 raise RuntimeError(f"block {blocks[la].block_id}: the chains of {blocks[la].genome} and {blocks[lb].genome} hold {nm} edits over {bases_a} and "
                                    f"{bases_b} bases, the identity pass {int(per_iv[i]['edits'])} over {int(per_iv[i]['aligned_a'])} and "
                                    f"{int(per_iv[i]['aligned_b'])} (flanks: {[tuple(int(v) for v in e) for e in extra]})")
-        texts = ctx.cigar_text(cigar, records, alignment_spans(r, chains, flanks, results), r.g_a, r.g_b) if cs else None
-        yield _AlignmentRound(r, per_iv, flanks, results, chains, cigar, records, texts)
+        spans = alignment_spans(r, chains, flanks, results) if cs or maf else None
+        texts = ctx.cigar_text(cigar, records, spans, r.g_a, r.g_b) if cs else None
+        rows = ctx.cigar_rows(cigar, records, spans, r.g_a, r.g_b) + (spans,) if maf else None
+        yield _AlignmentRound(r, per_iv, flanks, results, chains, cigar, records, texts, rows)
 
 
 def _round_paf_rows(blocks, a, found):
@@ -890,7 +895,7 @@ def _round_paf_rows(blocks, a, found):
 
 
 def block_alignments(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_RATE, band=IDENTITY_BAND, max_len=IDENTITY_MAX_LEN, max_edits=0, ends=None,
-                     lift=None, lift_identity=None, cs=False, chain=False):
+                     lift=None, lift_identity=None, cs=False, chain=False, maf=False):
     """One PAF record with a cg:Z: CIGAR per aligned chain of every block and pair of its lines (target = line a, query = line b): the
     anchors, segments and final per-segment results of block_identity for the same first five parameters, the canonical scripts of
     block_variants / block_wide_variants, and with ends = (ends_max_len, ends_max_edits, ends_penalty) the flanks of block_ends attached
@@ -906,30 +911,36 @@ def block_alignments(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_R
     cs: every line also carries the cs:Z: tag (short form) behind cg:Z:, both texts made by ONE nts_cigar_text per round
     (docs/design/04_26_block_paf_cs.md); without it no call, launch or byte changes.  chain: the same pass also makes the liftover chains
     (block_chains: ONE nts_cigar_chain_blocks per round); chain_table's parts are appended to what is returned (a tuple then); without
-    it no call, launch or byte changes."""
+    it no call, launch or byte changes.  maf: the same pass also makes the MAF blocks (block_mafs: ONE nts_cigar_rows per round;
+    docs/design/04_29_block_maf.md); maf_table's parts are appended last to what is returned (a tuple then); without it no call, launch
+    or byte changes."""
     message = check_identity_parameters(int(k), int(rate), int(band), int(max_len), int(max_edits)) or \
         (check_ends_parameters(*(int(v) for v in ends)) if ends is not None else None)
     if message:
         raise ValueError(message)
     k, rate, band, max_len, max_edits = int(k), int(rate), int(band), int(max_len), int(max_edits)
-    pairs, length, found, chains_of = [], {}, {}, {}
+    pairs, length, found, chains_of, mafs_of = [], {}, {}, {}, {}
     if lift_identity is not None:
         lifter = _lifter_of(genomes_by_name, blocks, lift, lift_identity)
     else:
         lifter = _Lifter(genomes_by_name, blocks, *lift) if lift is not None else None
-    for a in _alignment_rounds(ctx, genomes_by_name, blocks, k, rate, band, max_len, max_edits, ends, pairs, length, cs=bool(cs)):
+    for a in _alignment_rounds(ctx, genomes_by_name, blocks, k, rate, band, max_len, max_edits, ends, pairs, length, cs=bool(cs), maf=bool(maf)):
         _round_paf_rows(blocks, a, found)
         if lifter is not None:
             lifter.add_round(ctx, a, pairs)
         if chain:
             _round_chain_parts(ctx, blocks, a, chains_of)
+        if maf:
+            _round_maf_parts(blocks, a, mafs_of)
     rows = [row for p in pairs for row in found[p]]
     parts = ([chains_of[p] for p in pairs if chains_of.get(p) is not None],) if chain else ()
+    if maf:
+        parts += ([part for p in pairs for part in mafs_of[p]],)
     if lift_identity is not None:
         return (rows,) + lifter.results(genomes_by_name) + parts
     if lifter is not None:
         return (rows, lifter.rows(genomes_by_name)) + parts
-    return (rows,) + parts if chain else rows
+    return (rows,) + parts if parts else rows
 
 
 def chain_header(ra, rb, rec_len_a, rec_len_b, iv_a, iv_b, flipped, pair_record, base, chain_id):
@@ -992,6 +1003,117 @@ def block_chains(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_RATE,
     pass of its own over the rounds (_alignment_rounds) with ONE nts_cigar_chain_blocks per round, which makes the blocks and their
     text on the device.  Returns chain_table's parts in block_identity's pair order."""
     return block_alignments(ctx, genomes_by_name, blocks, k, rate, band, max_len, max_edits, ends, chain=True)[1]
+
+
+MAF_HEADER = "##maf version=1\n\n"
+
+
+def maf_block(name_a, rec_len_a, tstart, len_a, name_b, rec_len_b, qstart, qend, minus, eq, row_a, row_b):
+    """the four lines of one pairwise MAF block: `a score=<eq>`, the target's `s` line, the query's `s` line and a blank line.  name_* =
+    `<genome>.<contig>` (a is the target, b the query, as in paf_row and chain_header); tstart, qstart, qend: paf_row's forward
+    coordinates; len_a: the target bases of the rows; row_a / row_b: the aligned rows (str), gaps as `-`.  The target is on `+`.  The
+    start of a `-` line counts on the reverse strand, as the format asks: start_b = rec_len_b - qend, chain_header's convention.
+    Fields are separated by one blank, without padding.  Pure."""
+    start_b = int(rec_len_b) - int(qend) if minus else int(qstart)
+    return (f"a score={int(eq)}\n"
+            f"s {name_a} {int(tstart)} {int(len_a)} + {int(rec_len_a)} {row_a}\n"
+            f"s {name_b} {start_b} {int(qend) - int(qstart)} {'-' if minus else '+'} {int(rec_len_b)} {row_b}\n\n")
+
+
+def maf_table(parts):
+    """the MAF text of block_mafs' parts: `##maf version=1`, a blank line, then maf_block's lines per chain in PAF order (blocks and pairs
+    as in block_identity.tsv, a pair's chains ascending by x).  parts: per chain maf_block's arguments with `x` behind eq: (name_a,
+    rec_len_a, tstart, len_a, name_b, rec_len_b, qstart, qend, minus, eq, x, row_a, row_b).  A chain with eq + x == 0 has no aligned base
+    pair and gets no block: common readers refuse a block that is all gaps on one side."""
+    return MAF_HEADER + "".join(maf_block(*part[:10], *part[11:]) for part in parts if int(part[9]) + int(part[10]) > 0)
+
+
+_MAF_COMPLEMENT = None
+
+
+def maf_rows_host(entries, target, query_as_read):
+    """the two rows of one chain made on the host, as uint8 arrays: entries = its CIGAR entries, target / query_as_read = upper-case ASCII
+    uint8 arrays of the bases the entries consume (the query already reverse-complemented for a `-` pair).  What is not ACGT shows as N.
+    Array operations alone: one repeat over the entries and one scatter per row.  Pure: the spot check of nts_cigar_rows."""
+    import numpy as np
+    entries = np.ascontiguousarray(entries, dtype=np.uint64)
+    kind = np.repeat((entries & np.uint64(15)).astype(np.int64), (entries >> np.uint64(4)).astype(np.int64))
+    letters = np.full(256, ord("N"), dtype=np.uint8)
+    letters[[ord(c) for c in "ACGT"]] = [ord(c) for c in "ACGT"]
+    rows = []
+    for seq, gap in ((target, 1), (query_as_read, 2)):       # I has no target base, D no query base
+        row = np.full(kind.size, ord("-"), dtype=np.uint8)
+        held = kind != gap
+        if int(held.sum()) != len(seq):
+            raise ValueError("the entries do not consume the bases given")
+        row[held] = letters[np.asarray(seq, dtype=np.uint8)]
+        rows.append(row)
+    return rows[0], rows[1]
+
+
+def _maf_revcomp(seq):
+    import numpy as np
+    global _MAF_COMPLEMENT
+    if _MAF_COMPLEMENT is None:
+        table = np.full(256, ord("N"), dtype=np.uint8)
+        table[[ord(c) for c in "ACGT"]] = [ord(c) for c in "TGCA"]
+        _MAF_COMPLEMENT = table
+    return _MAF_COMPLEMENT[np.asarray(seq, dtype=np.uint8)[::-1]]
+
+
+def _genome_bases(genome, rec, start, length):
+    "upper-case ASCII of bases [start, start + length) of one record: from the genome's host copy where it has one, else one device read of that span"
+    import numpy as np
+    at = int(genome.rec_off[int(rec)]) + int(start)
+    host = getattr(genome, "host_seq", None)
+    if host is not None:
+        return np.char.upper(np.asarray(host[at:at + int(length)]).view("S1")).view(np.uint8)
+    return genome.download(at, int(length))
+
+
+def _round_maf_parts(blocks, a, found):
+    """found[(line a, line b)] = maf_table's parts of the pair's chains, ascending by x, for every pair of one round of the alignment pass
+    made with maf: one decode per row buffer and one slice per chain.  The rows of the round's first chain with an aligned base pair are
+    also made on the host (maf_rows_host over the genomes' bases) and compared (RuntimeError)."""
+    import numpy as np
+    r, chains, records = a.round, a.chains, a.records
+    row_a, row_b, row_first, spans = a.rows
+    whole_a, whole_b, at = row_a.tobytes().decode(), row_b.tobytes().decode(), row_first.tolist()
+    line = chains["line"]
+    by_line = np.argsort(line, kind="stable")                 # per pair its chains: one grouping of all chains by line
+    cut = np.searchsorted(line[by_line], np.arange(len(r.lines) + 1))
+    checked = False
+    for q, (la, lb, i) in enumerate(r.lines):
+        ra, rb, iv_a, iv_b, flipped = blocks[la], blocks[lb], r.iv_a[i], r.iv_b[i], bool(r.flip[i])
+        rec_len_a, rec_len_b = int(r.g_a.rec_len[int(iv_a[0])]), int(r.g_b.rec_len[int(iv_b[0])])
+        start_a, start_b, len_b = int(iv_a[1]), int(iv_b[1]), int(iv_b[2]) - int(iv_b[1])
+        parts = []
+        for c in by_line[cut[q]:cut[q + 1]].tolist():
+            x0, y0, y1 = int(chains["x0"][c]), int(chains["y0"][c]), int(chains["y1"][c])
+            q_from, q_to = (start_b + len_b - y1, start_b + len_b - y0) if flipped else (start_b + y0, start_b + y1)   # (paf_row's)
+            rec = records[c]
+            eq, x = int(rec["eq"]), int(rec["x"])
+            mine_a, mine_b = whole_a[at[c]:at[c + 1]], whole_b[at[c]:at[c + 1]]
+            if not checked and eq + x > 0:
+                checked = True
+                target = _genome_bases(r.g_a, iv_a[0], start_a + x0, int(rec["len_a"]))
+                query = _genome_bases(r.g_b, iv_b[0], q_from, q_to - q_from)
+                first = int(rec["first"])
+                host_a, host_b = maf_rows_host(a.cigar[first:first + int(rec["n_cig"])], target, _maf_revcomp(query) if flipped else query)
+                if (mine_a, mine_b) != (host_a.tobytes().decode(), host_b.tobytes().decode()):
+                    raise RuntimeError(f"the device's MAF rows of the round's first block are {mine_a[:60]!r} and {mine_b[:60]!r}, the host's "
+                                       f"{host_a[:60].tobytes().decode()!r} and {host_b[:60].tobytes().decode()!r}")
+            parts.append((f"{ra.genome}.{ra.contig}", rec_len_a, start_a + x0, int(rec["len_a"]), f"{rb.genome}.{rb.contig}", rec_len_b, q_from, q_to, flipped,
+                          eq, x, mine_a, mine_b))
+        found[(la, lb)] = parts
+
+
+def block_mafs(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_RATE, band=IDENTITY_BAND, max_len=IDENTITY_MAX_LEN, max_edits=0, ends=None):
+    """One pairwise MAF block per aligned chain of every block and pair of its lines (target = line a, query = line b): the chains of
+    block_alignments for the same parameters with their aligned rows (docs/design/04_29_block_maf.md).  A pass of its own over the rounds
+    (_alignment_rounds) with ONE nts_cigar_rows per round, which makes both rows of every chain on the device.  Returns maf_table's parts
+    in PAF order."""
+    return block_alignments(ctx, genomes_by_name, blocks, k, rate, band, max_len, max_edits, ends, maf=True)[1]
 
 
 LIFT_COLUMNS = ("genome", "contig", "start", "end", "name", "block_id", "to_genome", "to_contig", "to_start", "to_end", "orientation", "ch", "src_start",
@@ -1499,7 +1621,7 @@ def block_lift_identity(ctx, genomes_by_name, blocks, source, intervals, k=IDENT
 
 
 def block_lifts(ctx, genomes_by_name, blocks, source, k=IDENTITY_K, rate=IDENTITY_RATE, band=IDENTITY_BAND, max_len=IDENTITY_MAX_LEN, max_edits=0, ends=None,
-                lift=None, identity=(), joined=(), paf=False, cs=False, chain=False):
+                lift=None, identity=(), joined=(), paf=False, cs=False, chain=False, maf=False):
     """Every table of the lift from ONE pass over _alignment_rounds, the joined ones among them: lift = a dict of intervals for block_lift's
     rows, identity = dicts for block_lift_identity's rows, joined = dicts for the joined rows (LIFT_JOINED_COLUMNS), paf: block_alignments'
     lines as well (cs: with the cs:Z: tag).  A dict that is given more than once is joined once and read for every table it serves.  The
@@ -1532,15 +1654,18 @@ def block_lifts(ctx, genomes_by_name, blocks, source, k=IDENTITY_K, rate=IDENTIT
                  "end": np.concatenate([np.asarray(one["end"], dtype=np.int64) for one in every] + [np.zeros(0, dtype=np.int64)])}
     lifter = _Lifter(genomes_by_name, blocks, source, intervals, stats=counted if at_identity else None, joined=joining if at_joined else None,
                      per_chain=lift is not None or bool(at_identity))
-    pairs, length, found, chains_of = [], {}, {}, {}
+    pairs, length, found, chains_of, mafs_of = [], {}, {}, {}, {}
     for a in _alignment_rounds(ctx, genomes_by_name, blocks, int(k), int(rate), int(band), int(max_len), int(max_edits), ends, pairs, length,
-                               only=None if paf or chain else source, cs=bool(cs) and bool(paf)):
+                               only=None if paf or chain or maf else source, cs=bool(cs) and bool(paf), maf=bool(maf)):
         if paf:
             _round_paf_rows(blocks, a, found)
         lifter.add_round(ctx, a, pairs)
         if chain:
             _round_chain_parts(ctx, blocks, a, chains_of)
+        if maf:
+            _round_maf_parts(blocks, a, mafs_of)
     return {"chain": [chains_of[p] for p in pairs if chains_of.get(p) is not None] if chain else None,   # (chain: block_chains' parts from the same pass)
+            "maf": [part for p in pairs for part in mafs_of[p]] if maf else None,                      # (maf: block_mafs' parts from the same pass)
             "paf": [row for p in pairs for row in found[p]] if paf else None,
             "lift": lifter.rows(genomes_by_name, *spans[at_lift]) if lift is not None else None,
             "identity": [lifter.rows(genomes_by_name, *spans[at], identity=True) for at in at_identity],
@@ -1699,6 +1824,8 @@ def main(argv=None):
                    "are then made on the GPU", action="store_true")
     p.add_argument("--chain-out", help="with --fastas: file for the block chain file (one UCSC liftover chain per block and pair, the chains of --paf-out "
                    "joined per pair with the stretches between them as dt dq gaps; GPU); it takes the parameters of --paf-out")
+    p.add_argument("--maf-out", help="with --fastas: file for the block MAF (one pairwise MAF block per record of --paf-out with both aligned rows, made on "
+                   "the GPU); it takes the parameters of --paf-out; a pass of its own")
     p.add_argument("--lift-bed", help="with --fastas, --lift-genome and --lift-out: a BED file of intervals of one genome that are mapped through the block "
                    "alignments into the other genomes (GPU); it takes the parameters of --paf-out")
     p.add_argument("--lift-genome", help="the genome the intervals of --lift-bed lie on: a FASTA base name, as in column 2 of the block table")
@@ -1737,6 +1864,12 @@ def main(argv=None):
     if args.chain_out:
         if not args.fastas:
             p.error("--chain-out needs the genomes: --fastas")
+        message = check_identity_parameters(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits)
+        if message:
+            p.error(message)
+    if args.maf_out:
+        if not args.fastas:
+            p.error("--maf-out needs the genomes: --fastas")
         message = check_identity_parameters(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits)
         if message:
             p.error(message)
@@ -1877,6 +2010,11 @@ def main(argv=None):
                                            ends=(args.ends_max_len, args.ends_max_edits, args.ends_penalty) if args.ends_out else None)
             with open(args.chain_out, "w", encoding="utf-8") as fh:
                 fh.write(chain_table(chain_parts))
+        if args.maf_out:                                      # (a pass of its own)
+            maf_parts = block_mafs(ctx, loaders, read_blocks(args.tsv), *id_args, max_edits=args.identity_max_edits,
+                                   ends=(args.ends_max_len, args.ends_max_edits, args.ends_penalty) if args.ends_out else None)
+            with open(args.maf_out, "w", encoding="utf-8") as fh:
+                fh.write(maf_table(maf_parts))
     finally:
         ctx.close()
     if args.divergence_out:

@@ -1748,3 +1748,182 @@ int cigar_chain_blocks_run(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar
   }
   return NTS_OK;
 }
+
+// ---- the aligned rows of the chains' CIGARs: the sequence lines of a MAF block (nts_cigar_rows; ntsynt_amd/assess.py maf_table) ----
+// docs/design/04_29_block_maf.md.  Input: entries, chain records and spans as for nts_cigar_text with spans, the chains tiling the entries.
+// A COLUMN is one unit of an entry's length; chain c has eq + x + ins + del of them and two ROWS of that many bytes: row A the target
+// base of the column (`-` for I), row B the query base as read (`-` for D); upper case ACGT, N for a code that is no base.
+//   1  cig_index_stage with (A bases, B bases, columns): three columns; behind its check, k_cig_rows_firsts reads the column prefix at
+//      every chain's first entry (timer "cigar_rows_scan").  The chains tile the entries (host check), so a chain's rows are one byte
+//      range of either buffer, the same range in both.
+//   2  k_cig_rows: one lane per aligned 4-byte word of the rows; ONE upper-bound binary search over the column prefix finds the entry
+//      of the word's first column and serves both rows; the lane walks on over the at most three further entries a word touches,
+//      composes four bytes per row in two registers and stores two dwords (timer "cigar_rows_emit").  An entry finds its chain by a
+//      search over the chains' first entries and a base is one code load at the chain's base address plus the A or B prefix difference.
+// No atomic, no launch per chain or entry, no floating point, no runtime division, no host loop over entries.
+
+using CigRowsTuple = rocprim::tuple<uint64_t, uint64_t, uint64_t>; // A bases, B bases, columns
+
+struct CigRowsOf // element e of the scan's input: what entry e consumes and how many columns it has; nothing behind the last entry
+{
+  using Tuple = CigRowsTuple;
+  const uint64_t* cigar;
+  uint64_t n_cigar;
+  __device__ Tuple operator()(uint64_t e) const
+  {
+    if (e >= n_cigar) return Tuple(0, 0, 0);
+    const uint64_t v = cigar[e], code = v & 15u;
+    const CigBases ab = cig_bases(v);
+    const bool known = code == CIG_EQ || code == CIG_X || code == CIG_I || code == CIG_D;
+    return Tuple(rocprim::get<0>(ab), rocprim::get<1>(ab), known ? v >> 4 : 0); // (columns <= A bases + B bases: no wrap where those have none)
+  }
+};
+
+// lane c <= n_chains: where chain c's rows begin, the rows' length for c = n_chains
+__global__ __launch_bounds__(256) void k_cig_rows_firsts(const nts_cig_chain* __restrict__ chains, uint64_t n_chains, uint64_t n_cigar,
+                                                         const uint64_t* __restrict__ PC, uint64_t* __restrict__ row_first)
+{
+  const uint64_t c = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (c > n_chains) return;
+  uint64_t f = c < n_chains ? chains[c].first : n_cigar;
+  if (f > n_cigar) f = n_cigar; // (the host refused this before the launch: a lane still reads nothing outside the prefixes)
+  row_first[c] = PC[f];
+}
+
+// the letter of the base idx of one side of a chain: 'N' for a code that is no base, complemented or not; '?' -- never seen in a row --
+// instead of a load outside the chain or the code array (the chain check and the host's span checks leave none)
+__device__ __forceinline__ uint32_t cig_rows_base(const uint8_t* __restrict__ code, uint64_t size, uint64_t at, uint64_t idx, uint64_t len, bool backwards)
+{
+  if (idx >= len || (backwards ? idx > at : idx >= size - at)) return '?';
+  const uint64_t where = backwards ? at - idx : at + idx;
+  if (where < PAD || where >= size - PAD) return '?';
+  uint32_t c = code[where];
+  if (c >= nts::CODE_INVALID) return 'N';
+  if (backwards) c = 3u - c;
+  return (0x54474341u >> (8u * c)) & 255u; // "ACGT"
+}
+
+__global__ __launch_bounds__(256) void k_cig_rows(const uint64_t* __restrict__ cigar, uint64_t n_cigar, const CigTextChain* __restrict__ chains,
+                                                  uint64_t n_chains, const uint64_t* __restrict__ PA, const uint64_t* __restrict__ PB,
+                                                  const uint64_t* __restrict__ PC, const uint8_t* __restrict__ code_a, uint64_t size_a,
+                                                  const uint8_t* __restrict__ code_b, uint64_t size_b, uint32_t* __restrict__ out_a,
+                                                  uint32_t* __restrict__ out_b, uint64_t n_words)
+{
+  const uint64_t w = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (w >= n_words || n_cigar == 0 || n_chains == 0) return;
+  const uint64_t total = PC[n_cigar], o = 4u * w;
+  uint64_t e = cig_last_at_or_before(n_cigar, o, [PC](uint64_t i) { return PC[i]; }); // the entry of the word's first column (PC[0] = 0 <= o)
+  uint64_t p0 = PC[e], p1 = PC[e + 1u]; // (e < n_cigar)
+  uint64_t chain_of = ~0ull; // the entry whose chain `ch` is, and where that entry's bases begin inside the chain
+  CigTextChain ch = {};
+  uint64_t in_a = 0, in_b = 0;
+  uint32_t code = 0;
+  uint32_t word_a = 0, word_b = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < 4u; ++k) {
+    const uint64_t at = o + k;
+    if (at >= total) break;                // (the padding of the last word stays 0)
+    while (at >= p1 && e + 1u < n_cigar) { // the next entry: an entry has at least 1 column, so at most three steps per word
+      ++e;
+      p0 = p1;
+      p1 = PC[e + 1u];
+    }
+    if (chain_of != e) { // the last chain with first <= e (chains[0].first = 0; empty chains in front of it share its first)
+      ch = chains[cig_last_at_or_before(n_chains, e, [chains](uint64_t c) { return chains[c].first; })];
+      chain_of = e;
+      const uint64_t f = ch.first <= e ? ch.first : e;
+      in_a = PA[e] - PA[f];
+      in_b = PB[e] - PB[f];
+      code = (uint32_t)(cigar[e] & 15u);
+    }
+    const uint64_t off = at - p0;
+    const uint32_t byte_a = code == CIG_I ? (uint32_t)'-' : cig_rows_base(code_a, size_a, ch.at_a, in_a + off, ch.len_a, false);
+    const uint32_t byte_b = code == CIG_D ? (uint32_t)'-' : cig_rows_base(code_b, size_b, ch.at_b, in_b + off, ch.len_b, (ch.flags & NTS_CIG_B_BACKWARDS) != 0);
+    word_a |= byte_a << (8u * k);
+    word_b |= byte_b << (8u * k);
+  }
+  out_a[w] = word_a;
+  out_b[w] = word_b;
+}
+
+int cigar_rows_run(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains, const nts_genome* a,
+                   const nts_genome* b, const nts_cig_span* spans, uint8_t** row_a, uint8_t** row_b, uint64_t* row_first)
+{
+  std::vector<CigTextChain> placed(n_chains);
+  auto place = [&](uint64_t c, auto who) -> int { // chain c's span, behind the checks of its record: nts_cigar_text's rules
+    const nts_cig_chain& ch = chains[c];
+    const nts_cig_span& sp = spans[c];
+    if (sp.flags & ~NTS_CIG_B_BACKWARDS) return fail(ctx, NTS_EINVAL, who() + " has unknown flag bits");
+    if (sp.rec_a >= a->n_rec || sp.rec_b >= b->n_rec) return fail(ctx, NTS_EINVAL, who() + " names a record outside its genome");
+    const uint64_t rl_a = a->rec_len[sp.rec_a], rl_b = b->rec_len[sp.rec_b];
+    const bool backwards = (sp.flags & NTS_CIG_B_BACKWARDS) != 0;
+    bool inside = sp.pos_a <= rl_a && ch.len_a <= rl_a - sp.pos_a;
+    if (ch.len_b == 0) inside = inside && sp.pos_b <= rl_b;
+    else if (backwards) inside = inside && sp.pos_b < rl_b && ch.len_b <= sp.pos_b + 1u;
+    else inside = inside && sp.pos_b <= rl_b && ch.len_b <= rl_b - sp.pos_b;
+    if (!inside) return fail(ctx, NTS_EINVAL, who() + ": its span lies outside its record");
+    placed[c] = { ch.first, PAD + a->rec_off[sp.rec_a] + sp.pos_a, PAD + b->rec_off[sp.rec_b] + sp.pos_b, ch.len_a, ch.len_b, sp.flags, 0u };
+    return NTS_OK;
+  };
+  if (const int rc = cig_chains_check(ctx, "nts_cigar_rows", CIG_TEXT_MAX_BASES_LOG2, true, chains, n_chains, n_cigar, place)) return rc;
+  if (n_cigar == 0) { // (nothing is launched: every row is empty)
+    *row_a = nullptr;
+    *row_b = nullptr;
+    memset(row_first, 0, (n_chains + 1) * 8);
+    return NTS_OK;
+  }
+  // (its own buffers first: while nothing is queued, a request that fails may still return at once)
+  NTS_WS(d_placed, CigTextChain*, "cigr_placed", n_chains * sizeof(CigTextChain));
+  NTS_WS(d_first, uint64_t*, "cigr_first", (n_chains + 1) * 8);
+  std::vector<uint64_t> host_first(n_chains + 1); // (the caller's array is written only when the call succeeds)
+  uint32_t worst = SCRIPT_OK;
+  CigIndex ix; // columns PA, PB, PC (columns)
+  hipError_t e_run;
+  auto firsts = [&] { NTS_LAUNCH(k_cig_rows_firsts, IVL_GRID(n_chains + 1), ix.chains, n_chains, n_cigar, ix.column(2), d_first); };
+  if (const int rc = cig_index_stage<CigRowsOf>(ctx, "cigar_rows_scan", cigar, n_cigar, chains, n_chains, 0, &worst, ix, e_run, firsts)) return rc;
+  if (e_run == hipSuccess) e_run = hipGetLastError();
+  if (e_run == hipSuccess) e_run = hipMemcpyAsync(d_placed, placed.data(), n_chains * sizeof(CigTextChain), hipMemcpyHostToDevice, ctx->stream);
+  if (e_run == hipSuccess) e_run = hipMemcpyAsync(host_first.data(), d_first, (n_chains + 1) * 8, hipMemcpyDeviceToHost, ctx->stream);
+  hipError_t e_sync = hipStreamSynchronize(ctx->stream); // (whatever happened: the caller's arrays were sources of asynchronous copies)
+  HIP_TRY(ctx, e_run);
+  HIP_TRY(ctx, e_sync);
+  if (worst != SCRIPT_OK) return fail(ctx, NTS_EINVAL, "nts_cigar_rows: the entries of chain " + std::to_string(worst) + " are no CIGAR of its lengths");
+  const uint64_t columns = host_first[n_chains];
+  if (columns > 0xFFFFFFFFull) return fail(ctx, NTS_ERANGE, "nts_cigar_rows: rows of 2^32 columns or more");
+  if (columns == 0) { // (checked entries have a column each: kept so that no empty grid is ever launched)
+    *row_a = nullptr;
+    *row_b = nullptr;
+    memset(row_first, 0, (n_chains + 1) * 8);
+    return NTS_OK;
+  }
+  const uint64_t words = (columns + 3) / 4; // (the device buffers are padded to whole words)
+  // (the stream is idle: the rows' buffers are fetched before their kernel is queued)
+  NTS_WS(d_row_a, uint32_t*, "cigr_row_a", std::max<uint64_t>(words, 1) * 4);
+  NTS_WS(d_row_b, uint32_t*, "cigr_row_b", std::max<uint64_t>(words, 1) * 4);
+  uint8_t* host_a = (uint8_t*)malloc(std::max<uint64_t>(columns, 1));
+  uint8_t* host_b = (uint8_t*)malloc(std::max<uint64_t>(columns, 1));
+  if (!host_a || !host_b) {
+    free(host_a);
+    free(host_b);
+    return fail(ctx, NTS_ENOMEM, "nts_cigar_rows: no host memory for the rows");
+  }
+  {
+    ScopedTimer t(ctx, "cigar_rows_emit", true);
+    NTS_LAUNCH(k_cig_rows, IVL_GRID(words), ix.cigar, n_cigar, (const CigTextChain*)d_placed, n_chains, ix.column(0), ix.column(1), ix.column(2),
+               (const uint8_t*)a->d_code, a->n + 2 * PAD, (const uint8_t*)b->d_code, b->n + 2 * PAD, d_row_a, d_row_b, words);
+  }
+  e_run = hipGetLastError();
+  if (e_run == hipSuccess) e_run = hipMemcpyAsync(host_a, d_row_a, columns, hipMemcpyDeviceToHost, ctx->stream);
+  if (e_run == hipSuccess) e_run = hipMemcpyAsync(host_b, d_row_b, columns, hipMemcpyDeviceToHost, ctx->stream);
+  e_sync = hipStreamSynchronize(ctx->stream);
+  if (e_run != hipSuccess || e_sync != hipSuccess) {
+    free(host_a);
+    free(host_b);
+  }
+  HIP_TRY(ctx, e_run);
+  HIP_TRY(ctx, e_sync);
+  *row_a = host_a;
+  *row_b = host_b;
+  memcpy(row_first, host_first.data(), (n_chains + 1) * 8);
+  return NTS_OK;
+}

@@ -1079,6 +1079,18 @@ extern "C" int nts_cigar_chain_blocks(nts_ctx* ctx, const uint64_t* cigar, uint6
   return cigar_chain_blocks_run(ctx, cigar, n_cigar, chains, n_chains, links, n_links, pair_first, n_pairs, pairs, blocks, n_blocks, text, text_first);
 }
 
+extern "C" int nts_cigar_rows(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains, const nts_genome* a,
+                              const nts_genome* b, const nts_cig_span* spans, uint8_t** row_a, uint8_t** row_b, uint64_t* row_first)
+{
+  if (!ctx) return NTS_EINVAL;
+  if (n_cigar > 0xFFFFFFFFull || n_chains > 0xFFFFFFFFull) // (before any array is read)
+    return fail(ctx, NTS_ERANGE, "nts_cigar_rows: 2^32 entries or chains or more");
+  if ((n_cigar && !cigar) || (n_chains && !chains) || !row_a || !row_b || !row_first) return fail(ctx, NTS_EINVAL, "nts_cigar_rows: bad arguments");
+  if (!a || !b || !spans) return fail(ctx, NTS_EINVAL, "nts_cigar_rows: the rows need spans and both genomes");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return cigar_rows_run(ctx, cigar, n_cigar, chains, n_chains, a, b, spans, row_a, row_b, row_first);
+}
+
 extern "C" int nts_graph_budget(nts_ctx* ctx, uint64_t bytes)
 {
   if (!ctx) return NTS_EINVAL;

@@ -481,6 +481,34 @@ class Context:
             return text, firsts[0].copy()
         return text, firsts[0].copy(), self._take(p_cs, int(firsts[1, -1]), np.dtype("u1")), firsts[1].copy()
 
+    def cigar_rows(self, cigar, chains, spans, genome_a, genome_b):
+        """the aligned rows of the chains' CIGARs, the sequence lines of a MAF block (nts_cigar_rows).  cigar, chains, spans and the
+        genomes as for cigar_text with spans; all are required.  Returns (row_a, row_b, row_first): two uint8 arrays of equal length
+        and row_first [len(chains) + 1] uint64 -- chain c's rows are row_a[row_first[c]:row_first[c + 1]] and the same slice of
+        row_b, one byte per alignment column: row_a the target base (`-` for I), row_b the query base as read (`-` for D), upper case
+        ACGT and N for what is no base.  Refusals as cigar_text's; rows of 2^32 columns or more are refused.  Exact and
+        deterministic."""
+        cg = np.ascontiguousarray(cigar, dtype=np.uint64)
+        ch = np.ascontiguousarray(chains, dtype=CHAIN_DTYPE)
+        if cg.ndim != 1 or ch.ndim != 1:
+            raise ValueError("cigar_rows: a list of entries and a list of chain records")
+        assert CHAIN_DTYPE.itemsize == ctypes.sizeof(_lib.CigChain) and CIG_SPAN_DTYPE.itemsize == ctypes.sizeof(_lib.CigSpan)
+        sp = None
+        if spans is not None:
+            sp = np.ascontiguousarray(spans, dtype=CIG_SPAN_DTYPE)
+            if sp.shape != (ch.size,):
+                raise ValueError("cigar_rows: one span per chain")
+            if sp.size == 0:
+                sp = np.zeros(1, dtype=CIG_SPAN_DTYPE)       # (a pointer that is not NULL: spans were given)
+        first = np.zeros(ch.size + 1, dtype=np.uint64)
+        p_a, p_b = c_vp(), c_vp()
+        self.check(self.lib.nts_cigar_rows(self.h, cg.ctypes.data if cg.size else None, cg.size, ch.ctypes.data if ch.size else None, ch.size,
+                                           genome_a.h if genome_a is not None else None, genome_b.h if genome_b is not None else None,
+                                           sp.ctypes.data if sp is not None else None, ctypes.byref(p_a), ctypes.byref(p_b), first.ctypes.data),
+                   "nts_cigar_rows")
+        n = int(first[-1])
+        return self._take(p_a, n, np.dtype("u1")), self._take(p_b, n, np.dtype("u1")), first
+
     def cigar_lift(self, cigar, chains, queries):
         """the coordinate map of the chains' CIGARs (nts_cigar_lift).  cigar [E] uint64 and chains, a CHAIN_DTYPE array: what cigar_build
         returns (entries need not be maximal runs); queries: a LIFT_QUERY_DTYPE array -- pos is an offset on side 0 (A) or 1 (B) of

@@ -499,7 +499,7 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         graph_budget=None, assess=None, gaps=False, gap_links=None, gap_block_links=False, gap_copies=None, gap_copy_sites=None,
         gap_periods=None, gap_families=None, block_identity=None, block_variants=None, block_wide_variants=None, block_ends=None,
         block_end_variants=False, block_paf=None, block_lift=None, block_lift_identity=None, block_windows=None, block_lift_joined=None,
-        block_paf_cs=False, block_chain=None):
+        block_paf_cs=False, block_chain=None, block_maf=None):
     """FASTA paths -> engine (outputs in .outputs and in the CWD).  Mirrors oracle.synteny_oracle.run_pipeline's
     signature so the parity tests read alike.  Under torch.distributed (WORLD_SIZE > 1, process group already
     initialised by the caller) genomes are sharded over the ranks.
@@ -547,7 +547,11 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
     times gain block_paf:cigar_text_scan and block_paf:cigar_text_emit.  block_chain = (k, rate, band, max_len, max_edits, ends), as block_paf and equal to it
     where both are given: <prefix>.block_alignments.chain, one UCSC liftover chain per pair (assess.block_chains; stage block_chain behind
     block_paf, whose pass then serves both files; with `benchmark` the stage times gain block_chain:chain_blocks_scan,
-    block_chain:chain_blocks_emit and block_chain:chain_text).  block_lift =(bed_path, genome, k, rate, band,
+    block_chain:chain_blocks_emit and block_chain:chain_text).  block_maf = (k, rate, band, max_len, max_edits, ends), as block_paf and
+    equal to block_paf / block_chain where several are given: <prefix>.block_alignments.maf, one pairwise MAF block per PAF record with both
+    aligned rows made on the device (assess.block_mafs; stage block_maf behind block_chain; the pass of block_paf, or of block_chain
+    without it, then serves this file too; with `benchmark` the stage times gain block_maf:cigar_rows_scan and
+    block_maf:cigar_rows_emit).  block_lift =(bed_path, genome, k, rate, band,
     max_len, max_edits, ends): behind that file, <prefix>.block_lift.tsv (assess.block_lift: the BED intervals of `genome`, a FASTA base
     name, mapped through the block alignments into the other genomes; one rank only; it needs none of the other switches; with
     block_paf, which then takes the same parameters, the pass of the stage block_paf serves both files); with `benchmark` the stage times
@@ -663,6 +667,19 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
             raise ValueError("block_chain = (k, rate, band, max_len, max_edits, ends): " + message)
         if block_paf is not None and block_paf != block_chain:
             raise ValueError("block_paf and block_chain take the same (k, rate, band, max_len, max_edits, ends)")
+    if block_maf is not None:
+        if world > 1 or (mx_tsvs is not None and initial_only):
+            raise ValueError("block_maf needs every genome resident on one GPU (one rank, genomes loaded)")
+        from .assess import check_ends_parameters, check_identity_parameters
+        if len(block_maf) != 6 or (block_maf[5] is not None and len(block_maf[5]) != 3):
+            raise ValueError("block_maf = (k, rate, band, max_len, max_edits, ends) with ends = (ends_max_len, ends_max_edits, ends_penalty) or None")
+        block_maf = tuple(int(x) for x in block_maf[:5]) + (tuple(int(x) for x in block_maf[5]) if block_maf[5] is not None else None,)
+        message = check_identity_parameters(*block_maf[:5]) or (check_ends_parameters(*block_maf[5]) if block_maf[5] is not None else None)
+        if message:
+            raise ValueError("block_maf = (k, rate, band, max_len, max_edits, ends): " + message)
+        for name, other in (("block_paf", block_paf), ("block_chain", block_chain)):
+            if other is not None and other != block_maf:
+                raise ValueError(f"{name} and block_maf take the same (k, rate, band, max_len, max_edits, ends)")
     if block_lift is not None:
         if world > 1 or (mx_tsvs is not None and initial_only):
             raise ValueError("block_lift needs every genome resident on one GPU (one rank, genomes loaded)")
@@ -1352,6 +1369,11 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
     chain_parts = None                                        # chain_table's parts, once block_paf's pass has made them beside the PAF
     chain_timers = ("chain_blocks_scan", "chain_blocks_emit", "chain_text")
     more = {"chain": True} if chaining else {}               # (only with the switch on: a run without it makes the calls it always made)
+    maffing = block_maf is not None
+    maf_parts = None                                          # maf_table's parts, once the pass of block_paf or block_chain has made them
+    maf_timers = ("cigar_rows_scan", "cigar_rows_emit")
+    if maffing:
+        more["maf"] = True
 
     def joined_pass(with_paf):
         "with block_lift_joined the one pass is assess.block_lifts: (PAF rows, lift rows, [counted rows per table], [joined rows per table]), None for what is off"
@@ -1363,7 +1385,8 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
                                   ends=block_lift_joined[6], lift=bed, identity=([bed] if block_lift_identity is not None else []) + ([windows] if windows is not None else []),
                                   joined=([bed] if bed is not None else []) + ([windows] if windows is not None else []), paf=with_paf, cs=bool(block_paf_cs),
                                   **(more if with_paf else {}))
-        return (got["paf"], got["lift"], got["identity"], got["joined"]) + ((got["chain"],) if with_paf and chaining else ())
+        return (got["paf"], got["lift"], got["identity"], got["joined"]) + ((got["chain"],) if with_paf and chaining else ()) + \
+            ((got["maf"],) if with_paf and maffing else ())
 
     def counted_pass(with_paf):
         "the one pass that serves block_paf, block_lift, block_lift_identity and block_windows: (PAF rows, lift rows, [counted rows per table]), None for what is off"
@@ -1385,7 +1408,8 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         if benchmark:                                         # (device events around the calls of this stage only)
             backend.ctx.profile(True)
             paf_timers = ("cigar_atoms", "cigar_merge") + (("cigar_text_scan", "cigar_text_emit") if block_paf_cs else ())
-            paf_before = {name: backend.ctx.timing(name)[0] for name in paf_timers + lift_timers + stats_timers + (chain_timers if chaining else ())}
+            paf_before = {name: backend.ctx.timing(name)[0]
+                          for name in paf_timers + lift_timers + stats_timers + (chain_timers if chaining else ()) + (maf_timers if maffing else ())}
         if joining:                                           # (one pass serves every file)
             paf_rows, lifted_rows, counted_rows, joined_rows, *chain_made = joined_pass(True)
         elif counting:                                        # (one pass serves every file)
@@ -1396,13 +1420,16 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
                                                 lift=(block_lift[1], assess_.read_bed(block_lift[0])) if block_lift is not None else None, cs=bool(block_paf_cs),
                                                 **more)
             chain_made = []
-            if chaining:                                      # (one pass serves the PAF and the chain file)
-                paf_rows, chain_made = paf_rows[:-1], [paf_rows[-1]]
+            if chaining or maffing:                           # (one pass serves the PAF, the chain file and the MAF: their parts come last)
+                extra = int(chaining) + int(maffing)
+                paf_rows, chain_made = paf_rows[:-extra], list(paf_rows[-extra:])
                 paf_rows = paf_rows[0] if len(paf_rows) == 1 else paf_rows
             if block_lift is not None:                        # (one pass serves both files)
                 paf_rows, lifted_rows = paf_rows
         if chaining:
             chain_parts = chain_made[0]
+        if maffing:
+            maf_parts = chain_made[-1]
         text = assess_.paf_table(paf_rows)
         with open(f"{prefix}.block_alignments.paf", "w", encoding="utf-8") as fh:
             fh.write(text)
@@ -1413,6 +1440,7 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
             lift_times = [(f"block_lift:{name}", (backend.ctx.timing(name)[0] - paf_before[name]) * 1e-3) for name in lift_timers]
             stats_times = [(name, (backend.ctx.timing(name)[0] - paf_before[name]) * 1e-3) for name in stats_timers]
             chain_times = [(f"block_chain:{name}", (backend.ctx.timing(name)[0] - paf_before[name]) * 1e-3) for name in (chain_timers if chaining else ())]
+            maf_times = [(f"block_maf:{name}", (backend.ctx.timing(name)[0] - paf_before[name]) * 1e-3) for name in (maf_timers if maffing else ())]
             backend.ctx.profile(False)
         st.mark("block_paf_done")
     if chaining:
@@ -1421,11 +1449,17 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         if chain_parts is None:                               # (without block_paf: a pass of its own)
             if benchmark:                                     # (device events around the calls of this stage only)
                 backend.ctx.profile(True)
-                chain_before = {name: backend.ctx.timing(name)[0] for name in chain_timers}
-            chain_parts = assess_.block_chains(backend.ctx, {fa.basename(p): genomes[p] for p in fastas}, assess_.read_blocks(f"{prefix}.synteny_blocks.tsv"),
-                                               *block_chain[:5], ends=block_chain[5])
+                chain_before = {name: backend.ctx.timing(name)[0] for name in chain_timers + (maf_timers if maffing else ())}
+            if maffing:                                       # (one pass serves the chain file and the MAF)
+                _, chain_parts, maf_parts = assess_.block_alignments(backend.ctx, {fa.basename(p): genomes[p] for p in fastas},
+                                                                     assess_.read_blocks(f"{prefix}.synteny_blocks.tsv"), *block_chain[:5], ends=block_chain[5],
+                                                                     chain=True, maf=True)
+            else:
+                chain_parts = assess_.block_chains(backend.ctx, {fa.basename(p): genomes[p] for p in fastas}, assess_.read_blocks(f"{prefix}.synteny_blocks.tsv"),
+                                                   *block_chain[:5], ends=block_chain[5])
             if benchmark:
                 chain_times = [(f"block_chain:{name}", (backend.ctx.timing(name)[0] - chain_before[name]) * 1e-3) for name in chain_timers]
+                maf_times = [(f"block_maf:{name}", (backend.ctx.timing(name)[0] - chain_before[name]) * 1e-3) for name in (maf_timers if maffing else ())]
                 backend.ctx.profile(False)
         text = assess_.chain_table(chain_parts)
         with open(f"{prefix}.block_alignments.chain", "w", encoding="utf-8") as fh:
@@ -1435,6 +1469,26 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         if benchmark:
             st.rows += chain_times
         st.mark("block_chain_done")
+    if maffing:
+        st.start("block_maf")
+        from . import assess as assess_
+        if maf_parts is None:                                 # (neither block_paf nor block_chain has made the pass: one of its own)
+            if benchmark:                                     # (device events around the calls of this stage only)
+                backend.ctx.profile(True)
+                maf_before = {name: backend.ctx.timing(name)[0] for name in maf_timers}
+            maf_parts = assess_.block_mafs(backend.ctx, {fa.basename(p): genomes[p] for p in fastas}, assess_.read_blocks(f"{prefix}.synteny_blocks.tsv"),
+                                           *block_maf[:5], ends=block_maf[5])
+            if benchmark:
+                maf_times = [(f"block_maf:{name}", (backend.ctx.timing(name)[0] - maf_before[name]) * 1e-3) for name in maf_timers]
+                backend.ctx.profile(False)
+        text = assess_.maf_table(maf_parts)
+        with open(f"{prefix}.block_alignments.maf", "w", encoding="utf-8") as fh:
+            fh.write(text)
+        eng.outputs[f"{prefix}.block_alignments.maf"] = text
+        st.stop()
+        if benchmark:
+            st.rows += maf_times
+        st.mark("block_maf_done")
     if block_lift is not None:
         st.start("block_lift")
         from . import assess as assess_
