@@ -1064,6 +1064,51 @@ int nts_cigar_text(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const 
 int nts_cigar_rows(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains, const nts_genome* a,
                    const nts_genome* b, const nts_cig_span* spans, uint8_t** row_a, uint8_t** row_b, uint64_t* row_first);
 
+/* ---- the padded CIGARs of a reference-anchored (star) multiple alignment: `--block-maf-multi` -------------------------------------
+ * nts_cigar_pad: cigar and chains as nts_cigar_build returns them (the chains TILE the entries), every non-empty chain beginning and
+ *   ending with an = or X entry (the CORE of a chain: its leading and trailing I and D entries are cut off by the caller), and
+ *   at[c] = {group, t0}: the chains of one GROUP (group < n_groups, nondecreasing over the chains) are aligned on their A side to one
+ *   reference record, chain c covering its bases [t0, t1 = t0 + len_a).  SLOT p lies in front of reference base p.  An I entry that
+ *   precedes base p sits in slot p.  A SITE is a (group, slot) that holds an I entry of a chain of the group; its WIDTH is the longest
+ *   of them.  The PADDED CIGAR of chain c is its entries plus entries of BAM code 6 (P, padding: a column that consumes nothing):
+ *   behind an own I of length L at a site of width W > L one P of W - L; at every other site p of the group with t0 <= p < t1 one P
+ *   of W in front of base p -- between two entries, in front of the chain's first entry for p = t0, or splitting the =, X or D run
+ *   that holds bases p - 1 and p in two entries of its code; runs are never merged again across a P; slot t1 is not the chain's.
+ *   Out: *padded (release with nts_free; NULL when there is no entry): chain c's padded entries are [pad_first[c], pad_first[c + 1]);
+ *   pad_first: n_chains + 1 host entries; the sites ascending by (group, slot): group g's are [site_first[g], site_first[g + 1]) of
+ *   *site_pos (the slot, in the reference record's coordinates) and *site_w (its width) (release both with nts_free; NULL when
+ *   there is no site); site_first: n_groups + 1 host entries.  No genome is read.  NTS_ERANGE before any launch: 2^32 entries, chains
+ *   or groups or more (before any array is read); len_a or len_b that add up to 2^62 or more; t0 + len_a beyond 64 bits; a group
+ *   whose chains span 2^32 reference bases or more.  NTS_EINVAL before any launch, the smallest chain named: chains that do not tile
+ *   the entries, a group at or beyond n_groups, groups that are not nondecreasing, a first or last entry that is not = or X.  After
+ *   the first scan, NTS_EINVAL with the smallest chain named: an entry of code 6 in the input ("is padded already"), and "the entries
+ *   of chain ... are no CIGAR of its lengths"; after the second, NTS_ERANGE for 2^32 output entries or more.  A refused call returns
+ *   no buffer and writes to no caller array.  The check flags any bad entry of a chain, so a chain with an entry of code 6 and another
+ *   fault (a length of 0, say) is reported as "padded already".  PRECONDITION, not checked: no two I entries of one chain are
+ *   neighbours (nts_cigar_build merges such runs); two neighbours share a slot and each would be padded to the width, so the chain
+ *   would have more columns than col0(t1) - col0(t0).  One exclusive scan over the entries (A bases, B bases, I entries) and
+ *   nts_cigar_lift's check; one lane per entry stores an I entry's (group << 32 | slot - the group's smallest t0, length) at its rank,
+ *   one radix sort and one reduce_by_key with the maximum give the sites (timer "cigar_pad_sites"); one lane per entry counts what
+ *   it becomes from two lower-bound searches over the sites, one exclusive scan, and ONE lane per output entry finds its input entry
+ *   by a search over that scan and its piece or P by its rank (timer "cigar_pad_emit").  On the context's stream, in its workspace;
+ *   no atomic, no launch per chain, group or site, no floating point: the same input gives the same entries.
+ *   docs/design/04_30_block_maf_multi.md; csrc/nts_cigar.inc; ntsynt_amd/assess.py block_multi_mafs. */
+typedef struct
+{
+  uint32_t group;    /* the chain's group: nondecreasing over the chains, below n_groups */
+  uint32_t reserved; /* 0 */
+  uint64_t t0;       /* the reference base its A side begins at */
+} nts_cig_pad_at;
+int nts_cigar_pad(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains, const nts_cig_pad_at* at,
+                  uint64_t n_groups, uint64_t** padded, uint64_t* pad_first, uint64_t* site_first, uint64_t** site_pos, uint64_t** site_w);
+
+/* nts_cigar_rows_padded: nts_cigar_rows' arguments, results, refusals and kernels (csrc/nts_cigar.inc: k_cig_rows<true>), except that
+ *   an entry of code 6 is accepted: it has len columns that are `-` in BOTH rows and consumes no base of either side, so the rows of
+ *   a chain nts_cigar_pad has padded are as long as every other row of its group's columns.  nts_cigar_rows itself goes on refusing
+ *   code 6.  Timers "cigar_rows_scan" and "cigar_rows_emit". */
+int nts_cigar_rows_padded(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains, const nts_genome* a,
+                          const nts_genome* b, const nts_cig_span* spans, uint8_t** row_a, uint8_t** row_b, uint64_t* row_first);
+
 /* ---- C1-C5: minimizer graph -> collinear chains -----------------------------------------------------
  * replaces ntjoin_utils.read_minimizers' duplicate removal, filter_minimizers and build_graph
  * (call sites bin/ntsynt_synteny.py:607-612, 483, 539) and the path walk of Ntjoin.find_paths

@@ -92,6 +92,11 @@ class CigSpan(ctypes.Structure):
     _fields_ = [("pos_a", u64), ("pos_b", u64), ("rec_a", u32), ("rec_b", u32), ("flags", u32), ("pad", u32)]
 
 
+class CigPadAt(ctypes.Structure):
+    "nts_cig_pad_at: the group of a chain and the reference base its A side begins at (nts_cigar_pad)"
+    _fields_ = [("group", u32), ("reserved", u32), ("t0", u64)]
+
+
 class LiftQuery(ctypes.Structure):
     "nts_lift_query: an offset on one side of a chain (nts_cigar_lift)"
     _fields_ = [("chain", u32), ("side", u32), ("pos", u64)]
@@ -311,6 +316,8 @@ SYMBOLS = [
     ("nts_cigar_lift_pairs", ctypes.c_int, [c_vp, c_vp, u64, c_vp, u64, c_vp, u64, c_vp, u64, c_vp, u64, c_vp]),
     ("nts_cigar_chain_blocks", ctypes.c_int, [c_vp, c_vp, u64, c_vp, u64, c_vp, u64, c_vp, u64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     ("nts_cigar_rows", ctypes.c_int, [c_vp, c_vp, u64, c_vp, u64, c_vp, c_vp, c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
+    ("nts_cigar_rows_padded", ctypes.c_int, [c_vp, c_vp, u64, c_vp, u64, c_vp, c_vp, c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
+    ("nts_cigar_pad", ctypes.c_int, [c_vp, c_vp, u64, c_vp, u64, c_vp, u64, ctypes.POINTER(c_vp), c_vp, c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp)]),
     ("nts_genome_valid_bases", ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(Interval), u64, c_vp]),
     ("nts_minhash_pairs", ctypes.c_int, [c_vp, u32, c_vp, c_vp, u64, c_vp, c_vp, u64, c_vp, c_vp]),
     ("nts_graph_build", ctypes.c_int, [c_vp, u32, ctypes.POINTER(MxList), ctypes.POINTER(Graph)]),

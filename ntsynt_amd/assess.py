@@ -250,12 +250,13 @@ def check_identity_parameters(k, rate, band, max_len, max_edits=0):
 _Round = namedtuple("_Round", ["name_a", "name_b", "g_a", "g_b", "iv_a", "iv_b", "flip", "segs", "anchors", "lines"])
 
 
-def _identity_rounds(ctx, genomes_by_name, blocks, k, rate, band, max_len, pairs, length):
+def _identity_rounds(ctx, genomes_by_name, blocks, k, rate, band, max_len, pairs, length, star=False):
     """The loop of block_identity and block_variants over pairs of genomes and rounds, as a generator of _Round.  Appends the pairs
     (line a, line b) in the order of the file's rows to `pairs` before the first round and fills length[line] = its clipped length as
     genomes become resident.  One nts_sample_intervals per genome over all its lines; per ordered pair of genomes one
     nts_iv_anchor_segments for every round of pairs in which no line of the first genome occurs twice; the consumer makes the edit
-    calls on what a round holds before it asks for the next (the genomes of a round are resident until then)."""
+    calls on what a round holds before it asks for the next (the genomes of a round are resident until then).  star: only the STAR
+    pairs (a block's first line, each of its other lines) are made -- a subset of the pairs, in their order."""
     import numpy as np
     from .device import NO_MATE
     lines_of, index_of = {}, {}
@@ -266,7 +267,7 @@ def _identity_rounds(ctx, genomes_by_name, blocks, k, rate, band, max_len, pairs
         if name not in genomes_by_name:
             raise ValueError(f"block table names genome {name}, which is not among {sorted(genomes_by_name)}")
     for _, lines in _block_order(blocks):                     # (line a, line b) in the order of the file's rows
-        pairs += [(lines[x], lines[y]) for x in range(len(lines)) for y in range(x + 1, len(lines))]
+        pairs += [(lines[x], lines[y]) for x in range(1 if star else len(lines)) for y in range(x + 1, len(lines))]
     rounds = {}                                               # (genome a, genome b) -> rounds of pairs, a line of a once per round
     for p in pairs:
         todo = rounds.setdefault((blocks[p[0]].genome, blocks[p[1]].genome), [])
@@ -821,7 +822,7 @@ def paf_table(rows):
 _AlignmentRound = namedtuple("_AlignmentRound", ["round", "per_iv", "flanks", "results", "chains", "cigar", "records", "texts", "rows"], defaults=(None, None))
 
 
-def _alignment_rounds(ctx, genomes_by_name, blocks, k, rate, band, max_len, max_edits, ends, pairs, length, only=None, cs=False, maf=False):
+def _alignment_rounds(ctx, genomes_by_name, blocks, k, rate, band, max_len, max_edits, ends, pairs, length, only=None, cs=False, maf=False, star=False):
     """The per-round body of block_alignments and block_lift over _identity_rounds, as a generator of _AlignmentRound: per round
     nts_edit_segments with the per-segment distances, for max_edits > 0 nts_edit_wide and both script calls, else nts_edit_script alone,
     with ends nts_edit_extend and nts_edit_extend_script, then ONE nts_cigar_build for all pairs of the round.  Per pair the NM of its
@@ -829,9 +830,9 @@ def _alignment_rounds(ctx, genomes_by_name, blocks, k, rate, band, max_len, max_
     and aligned_b: RuntimeError otherwise.  only: a genome's name -- rounds in which it takes no part are passed over before any edit
     call.  cs: behind nts_cigar_build ONE nts_cigar_text per round over alignment_spans, its four arrays carried as `texts`; without it
     no call is added.  maf: behind nts_cigar_build ONE nts_cigar_rows per round over the same alignment_spans, its three arrays and the
-    spans carried as `rows`; without it no call is added."""
+    spans carried as `rows`; without it no call is added.  star: _identity_rounds' -- only the star pairs are made."""
     import numpy as np
-    for r in _identity_rounds(ctx, genomes_by_name, blocks, k, rate, band, max_len, pairs, length):
+    for r in _identity_rounds(ctx, genomes_by_name, blocks, k, rate, band, max_len, pairs, length, star=star):
         if only is not None and only not in (r.name_a, r.name_b):
             continue
         per_iv, dist = ctx.edit_segments(r.g_a, r.g_b, r.iv_a, r.iv_b, r.segs, r.flip, band, with_distances=True)
@@ -1114,6 +1115,229 @@ def block_mafs(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_RATE, b
     (_alignment_rounds) with ONE nts_cigar_rows per round, which makes both rows of every chain on the device.  Returns maf_table's parts
     in PAF order."""
     return block_alignments(ctx, genomes_by_name, blocks, k, rate, band, max_len, max_edits, ends, maf=True)[1]
+
+# ---- block multi-MAF: one reference-anchored block per synteny block (docs/design/04_30_block_maf_multi.md) ----
+
+def chain_cores(cigar, records, spans):
+    """The CORE of every chain: the chain without its leading and trailing I and D entries, from the first = or X entry to the last.
+    cigar, records, spans as nts_cigar_build and alignment_spans give them.  Returns (first, n_cig, len_a, len_b, pos_a, pos_b), int64
+    arrays per chain: where the core's entries lie in `cigar` and its span; n_cig = 0 for a chain without = or X, which takes no part.
+    Array operations over the entries alone.  Pure."""
+    import numpy as np
+    from .device import CIG_B_BACKWARDS
+    cigar = np.ascontiguousarray(cigar, dtype=np.uint64)
+    first, n_cig = records["first"].astype(np.int64), records["n_cig"].astype(np.int64)
+    code, size = (cigar & np.uint64(15)).astype(np.int64), (cigar >> np.uint64(4)).astype(np.int64)
+    both = (code == 7) | (code == 8)
+    sum_a = np.concatenate(([0], np.cumsum(np.where(both | (code == 2), size, 0))))
+    sum_b = np.concatenate(([0], np.cumsum(np.where(both | (code == 1), size, 0))))
+    chain_of = np.repeat(np.arange(first.size), n_cig)       # (the chains tile the entries)
+    at = np.flatnonzero(both)
+    lo, hi = np.full(first.size, cigar.size, dtype=np.int64), np.full(first.size, -1, dtype=np.int64)
+    np.minimum.at(lo, chain_of[at], at)
+    np.maximum.at(hi, chain_of[at], at)
+    held = hi >= 0
+    lo, hi = np.where(held, lo, first), np.where(held, hi + 1, first)
+    cut_a, cut_b = sum_a[lo] - sum_a[first], sum_b[lo] - sum_b[first]
+    back = (spans["flags"].astype(np.int64) & CIG_B_BACKWARDS) != 0
+    pos_b = spans["pos_b"].astype(np.int64)
+    return (lo, hi - lo, sum_a[hi] - sum_a[lo], sum_b[hi] - sum_b[lo], spans["pos_a"].astype(np.int64) + cut_a, np.where(back, pos_b - cut_b, pos_b + cut_b))
+
+
+def multi_maf_col0(r0, site_pos, site_w, p):
+    "col0(p) of a group that begins at reference base r0: p - r0 + the widths of its sites in front of slot p.  p: an int or an array.  Pure."
+    import numpy as np
+    before = np.concatenate(([0], np.cumsum(np.asarray(site_w, dtype=np.int64))))
+    return np.asarray(p, dtype=np.int64) - int(r0) + before[np.searchsorted(np.asarray(site_pos, dtype=np.int64), p, side="left")]
+
+
+def multi_maf_parts(ref_name, ref_len, chains, site_pos, site_w):
+    """The sub-blocks of one group.  chains: per core chain, in (row, t0) order, (row, t0, t1, name, src_size, minus, start, row_a,
+    row_b): row >= 1, [t0, t1) its reference bases, name = `<genome>.<contig>`, start = where its bases begin on the strand its `s` line
+    counts on, row_a / row_b = its padded rows (str), col0(t1) - col0(t0) columns.  site_pos / site_w: the group's sites.  The cut
+    points are the sorted distinct t0 and t1; per consecutive pair [c, c') the covering chains (at most one per row: ValueError) give the
+    reference row -- row A of any of them, two are compared: RuntimeError -- and a row each; a row of `-` alone is left out and a
+    sub-block with fewer than two rows is not written.  Returns per sub-block a list of `s` line fields (name, start, size, strand,
+    src_size, row), the reference first.  One slice per chain and sub-block, sizes from str.count: no loop over columns.  Pure."""
+    import numpy as np
+    if not chains:
+        return []
+    r0 = min(int(ch[1]) for ch in chains)
+    cuts = sorted({int(t) for ch in chains for t in ch[1:3]})
+    cols = multi_maf_col0(r0, site_pos, site_w, np.array(cuts, dtype=np.int64)).tolist()
+    base = multi_maf_col0(r0, site_pos, site_w, np.array([int(ch[1]) for ch in chains], dtype=np.int64)).tolist()
+    for prev, ch in zip(chains[:-1], chains[1:]):
+        if prev[0] == ch[0] and int(ch[1]) < int(prev[2]):
+            raise ValueError(f"two chains of row {ch[0]} overlap in the reference at base {int(ch[1])}")
+    seen = [int(ch[6]) for ch in chains]                     # the running base count of every chain's row
+    out = []
+    for (c, c_next), (lo, hi) in zip(zip(cuts[:-1], cuts[1:]), zip(cols[:-1], cols[1:])):
+        reference, lines, compared = None, [], False
+        for j, ch in enumerate(chains):
+            if not (int(ch[1]) <= c and c_next <= int(ch[2])):
+                continue
+            piece_a, piece_b = ch[7][lo - base[j]:hi - base[j]], ch[8][lo - base[j]:hi - base[j]]
+            if reference is None:
+                reference = piece_a
+            elif not compared:
+                compared = True
+                if piece_a != reference:
+                    raise RuntimeError(f"the chains that cover reference bases {c} .. {c_next} of {ref_name} disagree about the reference row")
+            size = len(piece_b) - piece_b.count("-")
+            if size:
+                lines.append((ch[3], seen[j], size, "-" if ch[5] else "+", int(ch[4]), piece_b))
+            seen[j] += size
+        if lines:
+            out.append([(ref_name, c, len(reference) - reference.count("-"), "+", int(ref_len), reference)] + lines)
+    return out
+
+
+def multi_maf_table(parts):
+    "the text of the multi-MAF file: MAF_HEADER, then per sub-block `a`, one `s` line per row and a blank line.  parts: multi_maf_parts' lists, in file order.  Pure."
+    return MAF_HEADER + "".join("a\n" + "".join(f"s {n} {st} {sz} {sd} {src} {row}\n" for n, st, sz, sd, src, row in block) + "\n" for block in parts)
+
+
+def padded_rows_host(entries, target, query_as_read):
+    "maf_rows_host for padded entries: a column of code 6 is `-` in both rows and consumes nothing.  Pure: the spot check of block_multi_mafs."
+    import numpy as np
+    entries = np.ascontiguousarray(entries, dtype=np.uint64)
+    kind = np.repeat((entries & np.uint64(15)).astype(np.int64), (entries >> np.uint64(4)).astype(np.int64))
+    letters = np.full(256, ord("N"), dtype=np.uint8)
+    letters[[ord(c) for c in "ACGT"]] = [ord(c) for c in "ACGT"]
+    rows = []
+    for seq, gap in ((target, 1), (query_as_read, 2)):
+        row = np.full(kind.size, ord("-"), dtype=np.uint8)
+        held = (kind != gap) & (kind != 6)
+        if int(held.sum()) != len(seq):
+            raise ValueError("the entries do not consume the bases given")
+        row[held] = letters[np.asarray(seq, dtype=np.uint8)]
+        rows.append(row)
+    return rows[0].tobytes().decode(), rows[1].tobytes().decode()
+
+
+def unpadded_host(entries):
+    "padded entries without their P entries, the runs P split merged again: the core they were made from.  Array operations.  Pure."
+    import numpy as np
+    entries = np.ascontiguousarray(entries, dtype=np.uint64)
+    kept = entries[(entries & np.uint64(15)) != np.uint64(6)]
+    if kept.size == 0:
+        return kept
+    code = kept & np.uint64(15)
+    head = np.concatenate(([True], code[1:] != code[:-1]))
+    return (np.add.reduceat(kept >> np.uint64(4), np.flatnonzero(head)) << np.uint64(4)) | code[head]
+
+
+def block_multi_mafs(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_RATE, band=IDENTITY_BAND, max_len=IDENTITY_MAX_LEN, max_edits=0, ends=None):
+    """One reference-anchored multiple alignment per synteny block (docs/design/04_30_block_maf_multi.md): the star pairs (first line,
+    other line) of every block are aligned as block_alignments aligns them (_alignment_rounds with star), every chain is trimmed to its
+    core, the cores ordered by (block, row, x) get their gap columns from ONE nts_cigar_pad, and per pair of genomes ONE
+    nts_cigar_rows_padded makes the rows of that pair's padded chains, which multi_maf_parts cuts into sub-blocks.  Genomes given as
+    callables are loaded a second time for the rows, each query one at a time beside the reference's genome.  The first group's padded
+    entries are checked on the host (unpadded_host gives the cores back; every chain has col0(t1) - col0(t0) columns) and the rows of its
+    first chain are made on the host and compared: RuntimeError.  Returns multi_maf_table's parts."""
+    import numpy as np
+    from .device import CHAIN_DTYPE, CIG_B_BACKWARDS, CIG_PAD_AT_DTYPE, CIG_SPAN_DTYPE
+    pairs, length = [], {}
+    order = {lines[0]: (g, lines) for g, (_, lines) in enumerate(_block_order(blocks))}        # first line -> (group, the block's lines)
+    held = []                                                # per core chain: (group, row, pos_a, its entries, len_a, len_b, span fields, names ...)
+    for a in _alignment_rounds(ctx, genomes_by_name, blocks, k, rate, band, max_len, max_edits, ends, pairs, length, star=True):
+        r, records = a.round, a.records
+        spans = alignment_spans(r, a.chains, a.flanks, a.results)
+        first, n_cig, len_a, len_b, pos_a, pos_b = chain_cores(a.cigar, records, spans)
+        pair_of = [r.lines[q] for q in np.asarray(a.chains["line"]).tolist()]
+        for c in np.flatnonzero(n_cig > 0).tolist():
+            la, lb, _ = pair_of[c]
+            group, lines = order[la]
+            held.append((group, lines.index(lb), int(pos_a[c]), a.cigar[first[c]:first[c] + n_cig[c]], int(len_a[c]), int(len_b[c]), int(pos_b[c]),
+                         int(spans["rec_a"][c]), int(spans["rec_b"][c]), int(spans["flags"][c]), la, lb, int(r.g_a.rec_len[int(spans["rec_a"][c])]),
+                         int(r.g_b.rec_len[int(spans["rec_b"][c])])))
+    held.sort(key=lambda h: h[:3])
+    n_groups = len(order)
+    if not held:
+        return []
+    entries = np.concatenate([h[3] for h in held]).astype(np.uint64)
+    records = np.zeros(len(held), dtype=CHAIN_DTYPE)
+    records["n_cig"] = [h[3].size for h in held]
+    records["first"] = np.concatenate(([0], np.cumsum(records["n_cig"][:-1].astype(np.int64))))
+    records["len_a"], records["len_b"] = [h[4] for h in held], [h[5] for h in held]
+    at = np.zeros(len(held), dtype=CIG_PAD_AT_DTYPE)
+    at["group"], at["t0"] = [h[0] for h in held], [h[2] for h in held]
+    for prev, h in zip(held[:-1], held[1:]):
+        if prev[:2] == h[:2] and h[2] < prev[2] + prev[4]:
+            raise ValueError(f"block {blocks[h[10]].block_id}: two chains of {blocks[h[11]].genome} overlap in the reference")
+    padded, pad_first, site_first, site_pos, site_w = ctx.cigar_pad(entries, records, at, n_groups)
+    pad_first, site_first = pad_first.astype(np.int64), site_first.astype(np.int64)
+    group_of = at["group"].astype(np.int64)
+    # the rows: per pair of genomes ONE call over that pair's padded chains
+    rows = [None] * len(held)
+    by_pair = {}
+    for j, h in enumerate(held):
+        by_pair.setdefault((blocks[h[10]].genome, blocks[h[11]].genome), []).append(j)
+    loaded = {}
+
+    def genome(name):
+        if name not in loaded:
+            g = genomes_by_name[name]
+            loaded[name] = (g(), True) if callable(g) else (g, False)
+        return loaded[name][0]
+
+    def release(name):
+        g, mine = loaded.pop(name)
+        if mine:
+            g.free()
+    try:
+        for (name_a, name_b), members in by_pair.items():
+            for name in [n for n in loaded if n not in (name_a, name_b)]:
+                release(name)
+            sub = np.zeros(len(members), dtype=CHAIN_DTYPE)
+            sub["n_cig"] = (pad_first[1:] - pad_first[:-1])[members]
+            sub["first"] = np.concatenate(([0], np.cumsum(sub["n_cig"][:-1].astype(np.int64))))
+            sub["len_a"], sub["len_b"] = records["len_a"][members], records["len_b"][members]
+            spans = np.zeros(len(members), dtype=CIG_SPAN_DTYPE)
+            spans["pos_a"], spans["pos_b"] = [held[j][2] for j in members], [held[j][6] for j in members]
+            spans["rec_a"], spans["rec_b"], spans["flags"] = [held[j][7] for j in members], [held[j][8] for j in members], [held[j][9] for j in members]
+            mine = np.concatenate([padded[pad_first[j]:pad_first[j + 1]] for j in members])
+            g_a, g_b = genome(name_a), genome(name_b)
+            row_a, row_b, row_first = ctx.cigar_rows(mine, sub, spans, g_a, g_b, padded=True)
+            whole_a, whole_b, cut = row_a.tobytes().decode(), row_b.tobytes().decode(), row_first.tolist()
+            for q, j in enumerate(members):
+                rows[j] = (whole_a[cut[q]:cut[q + 1]], whole_b[cut[q]:cut[q + 1]])
+            if members[0] == 0:                              # the spot check: the first group's entries, the first chain's rows
+                for j in np.flatnonzero(group_of == group_of[0]).tolist():
+                    h = held[j]
+                    sites = slice(site_first[h[0]], site_first[h[0] + 1])
+                    r0 = min(held[i][2] for i in np.flatnonzero(group_of == group_of[0]).tolist())
+                    want = int(multi_maf_col0(r0, site_pos[sites], site_w[sites], h[2] + h[4]) - multi_maf_col0(r0, site_pos[sites], site_w[sites], h[2]))
+                    mine_j = padded[pad_first[j]:pad_first[j + 1]]
+                    if not np.array_equal(unpadded_host(mine_j), unpadded_host(h[3])) or int((mine_j >> np.uint64(4)).sum()) != want:
+                        raise RuntimeError(f"block {blocks[h[10]].block_id}: the padded CIGAR of a chain of {blocks[h[11]].genome} is not its core in {want} columns")
+                h = held[0]
+                back = bool(h[9] & CIG_B_BACKWARDS)
+                target = _genome_bases(g_a, h[7], h[2], h[4])
+                query = _genome_bases(g_b, h[8], h[6] - h[5] + 1 if back else h[6], h[5])
+                host = padded_rows_host(padded[pad_first[0]:pad_first[1]], target, _maf_revcomp(query) if back else query)
+                if host != rows[0]:
+                    raise RuntimeError(f"the device's padded rows of the first chain are {rows[0][0][:60]!r} and {rows[0][1][:60]!r}, the host's "
+                                       f"{host[0][:60]!r} and {host[1][:60]!r}")
+    finally:
+        for name in list(loaded):
+            release(name)
+    parts = []
+    cut = np.searchsorted(group_of, np.arange(n_groups + 1))
+    for g in range(n_groups):
+        members = range(int(cut[g]), int(cut[g + 1]))
+        if not len(members):
+            continue
+        ref = blocks[held[members[0]][10]]
+        chains = []
+        for j in members:
+            h = held[j]
+            back, rb = bool(h[9] & CIG_B_BACKWARDS), blocks[h[11]]
+            start = h[13] - h[6] - 1 if back else h[6]        # (a `-` row counts on the reverse strand: rec_len_b - q_to, q_to = pos_b + 1)
+            chains.append((h[1], h[2], h[2] + h[4], f"{rb.genome}.{rb.contig}", h[13], back, start, rows[j][0], rows[j][1]))
+        sites = slice(site_first[g], site_first[g + 1])
+        parts += multi_maf_parts(f"{ref.genome}.{ref.contig}", held[members[0]][12], chains, site_pos[sites], site_w[sites])
+    return parts
 
 
 LIFT_COLUMNS = ("genome", "contig", "start", "end", "name", "block_id", "to_genome", "to_contig", "to_start", "to_end", "orientation", "ch", "src_start",
@@ -1826,6 +2050,9 @@ def main(argv=None):
                    "joined per pair with the stretches between them as dt dq gaps; GPU); it takes the parameters of --paf-out")
     p.add_argument("--maf-out", help="with --fastas: file for the block MAF (one pairwise MAF block per record of --paf-out with both aligned rows, made on "
                    "the GPU); it takes the parameters of --paf-out; a pass of its own")
+    p.add_argument("--multi-maf-out", help="with --fastas: file for the block multi-MAF (one reference-anchored multiple alignment per synteny block, anchored "
+                   "on the block's first line, cut into sub-blocks where the covering genomes change; padded CIGARs and rows made on the GPU); it takes "
+                   "the parameters of --paf-out; a pass of its own, which loads each query genome a second time for the rows")
     p.add_argument("--lift-bed", help="with --fastas, --lift-genome and --lift-out: a BED file of intervals of one genome that are mapped through the block "
                    "alignments into the other genomes (GPU); it takes the parameters of --paf-out")
     p.add_argument("--lift-genome", help="the genome the intervals of --lift-bed lie on: a FASTA base name, as in column 2 of the block table")
@@ -1864,6 +2091,12 @@ def main(argv=None):
     if args.chain_out:
         if not args.fastas:
             p.error("--chain-out needs the genomes: --fastas")
+        message = check_identity_parameters(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits)
+        if message:
+            p.error(message)
+    if args.multi_maf_out:
+        if not args.fastas:
+            p.error("--multi-maf-out needs the genomes: --fastas")
         message = check_identity_parameters(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits)
         if message:
             p.error(message)
@@ -2015,6 +2248,11 @@ def main(argv=None):
                                    ends=(args.ends_max_len, args.ends_max_edits, args.ends_penalty) if args.ends_out else None)
             with open(args.maf_out, "w", encoding="utf-8") as fh:
                 fh.write(maf_table(maf_parts))
+        if args.multi_maf_out:                                # (a pass of its own)
+            multi_parts = block_multi_mafs(ctx, loaders, read_blocks(args.tsv), *id_args, max_edits=args.identity_max_edits,
+                                           ends=(args.ends_max_len, args.ends_max_edits, args.ends_penalty) if args.ends_out else None)
+            with open(args.multi_maf_out, "w", encoding="utf-8") as fh:
+                fh.write(multi_maf_table(multi_parts))
     finally:
         ctx.close()
     if args.divergence_out:

@@ -106,6 +106,10 @@ def build_parser():
                    "aligned sequences themselves (target = the pair's first genome, gaps as -, upper case, no soft-masking), both rows of every\n"
                    "chain made on the GPU, for conservation and phylogeny tools, MAF converters and browsers; takes the parameters of\n"
                    "--block-paf; works with or without it", action="store_true")
+    p.add_argument("--block-maf-multi", help="after the run, write <prefix>.block_alignments.multi.maf: one reference-anchored multiple alignment per synteny\n"
+                   "block -- all its genomes in shared columns, anchored on the block's first line, cut into sub-blocks where the covering genomes\n"
+                   "change --, the gap columns and the rows made on the GPU; takes the parameters of --block-paf; works with or without the other\n"
+                   "block switches; a pass of its own", action="store_true")
     p.add_argument("--block-lift", metavar="BED", help="after the run, write <prefix>.block_lift.tsv: the intervals of this BED file, which lie on the\n"
                    "genome --lift-genome names, mapped through the alignments of --block-paf into the other genomes, one line per interval\n"
                    "and aligned chain it overlaps; takes the parameters of --block-paf; works with or without the other block switches")
@@ -273,6 +277,14 @@ def check_reports(parser, args):
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             parser.error("--block-maf works from the genomes resident on one GPU: run it on one rank, or assess the finished run with "
                          "ntsynt_block_stats --tsv <prefix>.synteny_blocks.tsv --fai ... --fastas ... --maf-out <prefix>.block_alignments.maf")
+        from .assess import check_identity_parameters
+        message = check_identity_parameters(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits)
+        if message:
+            parser.error(message)
+    if args.block_maf_multi:
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            parser.error("--block-maf-multi works from the genomes resident on one GPU: run it on one rank, or assess the finished run with "
+                         "ntsynt_block_stats --tsv <prefix>.synteny_blocks.tsv --fai ... --fastas ... --multi-maf-out <prefix>.block_alignments.multi.maf")
         from .assess import check_identity_parameters
         message = check_identity_parameters(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits)
         if message:
@@ -446,6 +458,10 @@ def main(argv=None):
              f"max_len {args.identity_max_len}, max_edits {args.identity_max_edits}" +
              (f", ends_max_len {args.ends_max_len}, ends_max_edits {args.ends_max_edits}, ends_penalty {args.ends_penalty}" if args.block_ends else "") + ")"]
             if args.block_maf else []) + \
+           ([f"block_maf_multi (cigar_pad_sites, cigar_pad_emit, cigar_rows_scan, cigar_rows_emit; k {args.identity_k}, rate {args.identity_rate}, band "
+             f"{args.identity_band}, max_len {args.identity_max_len}, max_edits {args.identity_max_edits}" +
+             (f", ends_max_len {args.ends_max_len}, ends_max_edits {args.ends_max_edits}, ends_penalty {args.ends_penalty}" if args.block_ends else "") + ")"]
+            if args.block_maf_multi else []) + \
            ([f"block_lift (lift_scan, lift_search; {args.block_lift} on {args.lift_genome}; k {args.identity_k}, rate {args.identity_rate}, band "
              f"{args.identity_band}, max_len {args.identity_max_len}, max_edits {args.identity_max_edits}" +
              (f", ends_max_len {args.ends_max_len}, ends_max_edits {args.ends_max_edits}, ends_penalty {args.ends_penalty}" if args.block_ends else "") + ")"]
@@ -529,6 +545,8 @@ def _run(pipeline, fastas, args, device, quiet):
         more["block_chain"] = lift_args[1:]
     if args.block_maf:
         more["block_maf"] = lift_args[1:]
+    if args.block_maf_multi:
+        more["block_maf_multi"] = lift_args[1:]
     pipeline.run(fastas, **more, k=args.k, w=args.w, fpr=args.fpr, prefix=args.prefix, w_rounds=args.w_rounds,
                  indel=args.indel, merge=args.merge, block_size=args.block_size, common=not args.no_common,
                  simplify=not args.no_simplify_graph, device=device, benchmark=args.benchmark,

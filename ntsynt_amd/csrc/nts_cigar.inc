@@ -14,6 +14,7 @@
 // No genome is read.  No atomic, no launch per piece or chain, no floating point, no host loop beyond the O(n_pieces) checks.
 
 constexpr uint64_t CIG_I = 1, CIG_D = 2, CIG_EQ = 7, CIG_X = 8; // BAM's codes
+constexpr uint64_t CIG_P = 6;                                   // BAM's padding: what nts_cigar_pad adds and nts_cigar_rows_padded alone reads
 constexpr uint64_t CIG_MAX_COLUMNS = 1ull << 60;               // len << 4 stays inside 64 bits
 
 // the last i < n whose key(i) <= e over nondecreasing keys, 0 where there is none (n >= 1): the piece of an op, the chain of an
@@ -372,6 +373,8 @@ __device__ __forceinline__ bool cig_chain_of(const nts_cig_chain* __restrict__ c
 // a record whose entries reach beyond n_cigar (the host refused it before the launch: a lane still reads nothing outside the prefixes)
 __device__ __forceinline__ bool cig_chain_beyond(const nts_cig_chain& ch, uint64_t n_cigar) { return ch.first > n_cigar || ch.n_cig > n_cigar - ch.first; }
 
+// PADDED: an entry of code 6 (P, padding: a column that consumes nothing) passes as well -- for nts_cigar_rows_padded alone
+template <bool PADDED>
 __global__ __launch_bounds__(256) void k_lift_check(const uint64_t* __restrict__ cigar, uint64_t n_cigar, const nts_cig_chain* __restrict__ chains,
                                                     uint64_t n_chains, const uint64_t* __restrict__ PA, const uint64_t* __restrict__ PB,
                                                     uint32_t* __restrict__ status)
@@ -381,7 +384,8 @@ __global__ __launch_bounds__(256) void k_lift_check(const uint64_t* __restrict__
   uint32_t say = SCRIPT_OK;
   if (g < n_cigar) {
     const uint64_t v = cigar[g], code = v & 15u;
-    const bool bad = (code != CIG_I && code != CIG_D && code != CIG_EQ && code != CIG_X) || (v >> 4) == 0 || PA[g + 1] < PA[g] || PB[g + 1] < PB[g];
+    const bool bad = (code != CIG_I && code != CIG_D && code != CIG_EQ && code != CIG_X && !(PADDED && code == CIG_P)) || (v >> 4) == 0 ||
+                     PA[g + 1] < PA[g] || PB[g + 1] < PB[g];
     // its chain: the last whose first <= g, chain 0 for an entry in front of every chain (on this error path only)
     if (bad && n_chains) say = (uint32_t)cig_last_at_or_before(n_chains, g, [chains](uint64_t c) { return chains[c].first; });
   } else {
@@ -440,6 +444,18 @@ struct CigIndex // what cig_index_stage leaves in the context's workspace: dead 
   const uint64_t* column(uint32_t k) const { return prefixes + k * rows; }
 };
 
+// whether a scan functor reads padded entries: one that says `static constexpr bool PADDED = true` (CigRowsOf<true>); no other does
+template <class Of, class = void>
+struct CigOfPadded
+{
+  static constexpr bool value = false;
+};
+template <class Of>
+struct CigOfPadded<Of, std::enable_if_t<Of::PADDED>>
+{
+  static constexpr bool value = true;
+};
+
 // the scan of Of's tuples into the columns (the size query with tmp = nullptr)
 template <class Of, size_t... K>
 hipError_t cig_index_scan(void* tmp, size_t& bytes, const CigIndex& ix, uint64_t n_cigar, hipStream_t stream, std::index_sequence<K...>)
@@ -480,7 +496,7 @@ int cig_index_stage(nts_ctx* ctx, const char* timer, const uint64_t* cigar, uint
     if (e_run == hipSuccess && !ix.tmp) e_run = hipErrorOutOfMemory;
     if (e_run == hipSuccess) e_run = cig_index_scan<Of>(ix.tmp, tmp_s, ix, n_cigar, ctx->stream, columns);
     if (e_run == hipSuccess && lanes) {
-      NTS_LAUNCH(k_lift_check, IVL_GRID(lanes), ix.cigar, n_cigar, ix.chains, n_chains, ix.column(0), ix.column(1), d_status);
+      NTS_LAUNCH(k_lift_check<CigOfPadded<Of>::value>, IVL_GRID(lanes), ix.cigar, n_cigar, ix.chains, n_chains, ix.column(0), ix.column(1), d_status);
       e_run = rocprim::reduce(ix.tmp, ix.tmp_bytes, d_status, d_worst, SCRIPT_OK, lanes, ScriptMin(), ctx->stream);
     }
     if (e_run == hipSuccess) behind();
@@ -1764,9 +1780,11 @@ int cigar_chain_blocks_run(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar
 
 using CigRowsTuple = rocprim::tuple<uint64_t, uint64_t, uint64_t>; // A bases, B bases, columns
 
+template <bool PADDED_> // (true: nts_cigar_rows_padded, where an entry of code 6 has columns and consumes nothing)
 struct CigRowsOf // element e of the scan's input: what entry e consumes and how many columns it has; nothing behind the last entry
 {
   using Tuple = CigRowsTuple;
+  static constexpr bool PADDED = PADDED_;
   const uint64_t* cigar;
   uint64_t n_cigar;
   __device__ Tuple operator()(uint64_t e) const
@@ -1774,7 +1792,7 @@ struct CigRowsOf // element e of the scan's input: what entry e consumes and how
     if (e >= n_cigar) return Tuple(0, 0, 0);
     const uint64_t v = cigar[e], code = v & 15u;
     const CigBases ab = cig_bases(v);
-    const bool known = code == CIG_EQ || code == CIG_X || code == CIG_I || code == CIG_D;
+    const bool known = code == CIG_EQ || code == CIG_X || code == CIG_I || code == CIG_D || (PADDED && code == CIG_P);
     return Tuple(rocprim::get<0>(ab), rocprim::get<1>(ab), known ? v >> 4 : 0); // (columns <= A bases + B bases: no wrap where those have none)
   }
 };
@@ -1803,6 +1821,7 @@ __device__ __forceinline__ uint32_t cig_rows_base(const uint8_t* __restrict__ co
   return (0x54474341u >> (8u * c)) & 255u; // "ACGT"
 }
 
+template <bool PADDED> // (true: a column of an entry of code 6 is `-` in both rows)
 __global__ __launch_bounds__(256) void k_cig_rows(const uint64_t* __restrict__ cigar, uint64_t n_cigar, const CigTextChain* __restrict__ chains,
                                                   uint64_t n_chains, const uint64_t* __restrict__ PA, const uint64_t* __restrict__ PB,
                                                   const uint64_t* __restrict__ PC, const uint8_t* __restrict__ code_a, uint64_t size_a,
@@ -1837,8 +1856,9 @@ __global__ __launch_bounds__(256) void k_cig_rows(const uint64_t* __restrict__ c
       code = (uint32_t)(cigar[e] & 15u);
     }
     const uint64_t off = at - p0;
-    const uint32_t byte_a = code == CIG_I ? (uint32_t)'-' : cig_rows_base(code_a, size_a, ch.at_a, in_a + off, ch.len_a, false);
-    const uint32_t byte_b = code == CIG_D ? (uint32_t)'-' : cig_rows_base(code_b, size_b, ch.at_b, in_b + off, ch.len_b, (ch.flags & NTS_CIG_B_BACKWARDS) != 0);
+    const bool pad = PADDED && code == CIG_P;
+    const uint32_t byte_a = code == CIG_I || pad ? (uint32_t)'-' : cig_rows_base(code_a, size_a, ch.at_a, in_a + off, ch.len_a, false);
+    const uint32_t byte_b = code == CIG_D || pad ? (uint32_t)'-' : cig_rows_base(code_b, size_b, ch.at_b, in_b + off, ch.len_b, (ch.flags & NTS_CIG_B_BACKWARDS) != 0);
     word_a |= byte_a << (8u * k);
     word_b |= byte_b << (8u * k);
   }
@@ -1846,9 +1866,11 @@ __global__ __launch_bounds__(256) void k_cig_rows(const uint64_t* __restrict__ c
   out_b[w] = word_b;
 }
 
+template <bool PADDED>
 int cigar_rows_run(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains, const nts_genome* a,
                    const nts_genome* b, const nts_cig_span* spans, uint8_t** row_a, uint8_t** row_b, uint64_t* row_first)
 {
+  const char* const name = PADDED ? "nts_cigar_rows_padded" : "nts_cigar_rows";
   std::vector<CigTextChain> placed(n_chains);
   auto place = [&](uint64_t c, auto who) -> int { // chain c's span, behind the checks of its record: nts_cigar_text's rules
     const nts_cig_chain& ch = chains[c];
@@ -1865,7 +1887,7 @@ int cigar_rows_run(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const 
     placed[c] = { ch.first, PAD + a->rec_off[sp.rec_a] + sp.pos_a, PAD + b->rec_off[sp.rec_b] + sp.pos_b, ch.len_a, ch.len_b, sp.flags, 0u };
     return NTS_OK;
   };
-  if (const int rc = cig_chains_check(ctx, "nts_cigar_rows", CIG_TEXT_MAX_BASES_LOG2, true, chains, n_chains, n_cigar, place)) return rc;
+  if (const int rc = cig_chains_check(ctx, name, CIG_TEXT_MAX_BASES_LOG2, true, chains, n_chains, n_cigar, place)) return rc;
   if (n_cigar == 0) { // (nothing is launched: every row is empty)
     *row_a = nullptr;
     *row_b = nullptr;
@@ -1880,16 +1902,16 @@ int cigar_rows_run(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const 
   CigIndex ix; // columns PA, PB, PC (columns)
   hipError_t e_run;
   auto firsts = [&] { NTS_LAUNCH(k_cig_rows_firsts, IVL_GRID(n_chains + 1), ix.chains, n_chains, n_cigar, ix.column(2), d_first); };
-  if (const int rc = cig_index_stage<CigRowsOf>(ctx, "cigar_rows_scan", cigar, n_cigar, chains, n_chains, 0, &worst, ix, e_run, firsts)) return rc;
+  if (const int rc = cig_index_stage<CigRowsOf<PADDED>>(ctx, "cigar_rows_scan", cigar, n_cigar, chains, n_chains, 0, &worst, ix, e_run, firsts)) return rc;
   if (e_run == hipSuccess) e_run = hipGetLastError();
   if (e_run == hipSuccess) e_run = hipMemcpyAsync(d_placed, placed.data(), n_chains * sizeof(CigTextChain), hipMemcpyHostToDevice, ctx->stream);
   if (e_run == hipSuccess) e_run = hipMemcpyAsync(host_first.data(), d_first, (n_chains + 1) * 8, hipMemcpyDeviceToHost, ctx->stream);
   hipError_t e_sync = hipStreamSynchronize(ctx->stream); // (whatever happened: the caller's arrays were sources of asynchronous copies)
   HIP_TRY(ctx, e_run);
   HIP_TRY(ctx, e_sync);
-  if (worst != SCRIPT_OK) return fail(ctx, NTS_EINVAL, "nts_cigar_rows: the entries of chain " + std::to_string(worst) + " are no CIGAR of its lengths");
+  if (worst != SCRIPT_OK) return fail(ctx, NTS_EINVAL, std::string(name) + ": the entries of chain " + std::to_string(worst) + " are no CIGAR of its lengths");
   const uint64_t columns = host_first[n_chains];
-  if (columns > 0xFFFFFFFFull) return fail(ctx, NTS_ERANGE, "nts_cigar_rows: rows of 2^32 columns or more");
+  if (columns > 0xFFFFFFFFull) return fail(ctx, NTS_ERANGE, std::string(name) + ": rows of 2^32 columns or more");
   if (columns == 0) { // (checked entries have a column each: kept so that no empty grid is ever launched)
     *row_a = nullptr;
     *row_b = nullptr;
@@ -1905,11 +1927,11 @@ int cigar_rows_run(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const 
   if (!host_a || !host_b) {
     free(host_a);
     free(host_b);
-    return fail(ctx, NTS_ENOMEM, "nts_cigar_rows: no host memory for the rows");
+    return fail(ctx, NTS_ENOMEM, std::string(name) + ": no host memory for the rows");
   }
   {
     ScopedTimer t(ctx, "cigar_rows_emit", true);
-    NTS_LAUNCH(k_cig_rows, IVL_GRID(words), ix.cigar, n_cigar, (const CigTextChain*)d_placed, n_chains, ix.column(0), ix.column(1), ix.column(2),
+    NTS_LAUNCH(k_cig_rows<PADDED>, IVL_GRID(words), ix.cigar, n_cigar, (const CigTextChain*)d_placed, n_chains, ix.column(0), ix.column(1), ix.column(2),
                (const uint8_t*)a->d_code, a->n + 2 * PAD, (const uint8_t*)b->d_code, b->n + 2 * PAD, d_row_a, d_row_b, words);
   }
   e_run = hipGetLastError();
@@ -1925,5 +1947,334 @@ int cigar_rows_run(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const 
   *row_a = host_a;
   *row_b = host_b;
   memcpy(row_first, host_first.data(), (n_chains + 1) * 8);
+  return NTS_OK;
+}
+
+// ---- the padded CIGARs of a star alignment: every chain gets the gap columns the other chains' insertions need (nts_cigar_pad) ----
+// docs/design/04_30_block_maf_multi.md.  Input: entries and chain records that tile them, and per chain {group, t0}: the chains of one
+// GROUP are aligned to one reference record, chain c's A side covering reference bases [t0, t0 + len_a).  SLOT p lies in front of
+// reference base p; an I entry that precedes base p sits in slot p; a SITE is a (group, slot) with an I entry, its WIDTH the longest
+// such I of the group.  The padded CIGAR of a chain is its entries plus entries of code 6 (P): behind an own I shorter than the width
+// the rest of the width, and the whole width at every other site p with t0 <= p < t1 -- in front of the entry that begins at p, or
+// splitting the =, X or D run that holds bases p - 1 and p.  No genome is read.
+//   1  cig_index_stage with (A bases, B bases, I entries): the third prefix compacts the I entries.  k_cigp_keys: one lane per entry,
+//      an I entry stores (group << 32 | slot - R0, len) at its rank; ONE radix sort of the pairs, ONE reduce_by_key with the maximum:
+//      the sites, ascending by group and slot, and their widths.  k_cigp_sites: one lane per site (the absolute slot) and one per
+//      group and one more (where its sites begin: a lower-bound search) (timer "cigar_pad_sites").
+//   2  k_cigp_count: one lane per entry, two lower-bound searches over the site keys give the sites [s_lo, s_hi) of its slots, from
+//      which the number of entries it becomes follows without a walk; ONE exclusive scan; k_cig_rows_firsts reads it at every chain's
+//      first entry.  k_cigp_emit: ONE LANE PER OUTPUT ENTRY: an upper-bound search over the scan finds its input entry, the same two
+//      searches its sites, and its rank r inside the entry says which piece or which P it is -- two site keys or one width are read,
+//      whatever the number of sites that cross the run (timer "cigar_pad_emit").
+// No atomic, no launch per chain, group or site, no floating point, no host loop over entries or sites (one over chains: the checks).
+
+struct CigPadChain // a chain as the padding kernels read it
+{
+  uint64_t first; // its first entry
+  uint64_t key0;  // group << 32 | t0 - R0 of its group (the extent of a group is below 2^32: host check)
+};
+static_assert(sizeof(CigPadChain) == 16 && sizeof(nts_cig_pad_at) == 16, "two 8-byte words; the C ABI's layout");
+
+using CigPadTuple = rocprim::tuple<uint64_t, uint64_t, uint64_t>; // A bases, B bases, I entries
+
+struct CigPadOf // element e of the scan's input: what entry e consumes and whether it is an I; nothing behind the last entry
+{
+  using Tuple = CigPadTuple;
+  const uint64_t* cigar;
+  uint64_t n_cigar;
+  __device__ Tuple operator()(uint64_t e) const
+  {
+    if (e >= n_cigar) return Tuple(0, 0, 0);
+    const uint64_t v = cigar[e];
+    const CigBases ab = cig_bases(v);
+    return Tuple(rocprim::get<0>(ab), rocprim::get<1>(ab), (v & 15u) == CIG_I ? 1u : 0u);
+  }
+};
+
+constexpr uint64_t CIGP_MOST = 1ull << 62; // a count of output entries saturates here: no sum of two wraps
+struct CigPadSatAdd
+{
+  __host__ __device__ uint64_t operator()(uint64_t x, uint64_t y) const { return x + y < CIGP_MOST ? x + y : CIGP_MOST; }
+};
+
+// the first i < n with key[i] >= k over ascending keys, n where there is none
+__device__ __forceinline__ uint64_t cigp_lower(const uint64_t* __restrict__ key, uint64_t n, uint64_t k)
+{
+  uint64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint64_t mid = lo + (hi - lo) / 2u;
+    if (key[mid] < k) lo = mid + 1u;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// the key of the slot in front of entry e: its chain's key0 plus the A bases of the chain in front of e; own: e > the chain's first
+__device__ __forceinline__ uint64_t cigp_key_of(const CigPadChain* __restrict__ chains, uint64_t n_chains, const uint64_t* __restrict__ PA, uint64_t e, bool& inner)
+{
+  const CigPadChain ch = chains[cig_last_at_or_before(n_chains, e, [chains](uint64_t c) { return chains[c].first; })];
+  const uint64_t f = ch.first <= e ? ch.first : e;
+  inner = e > f;
+  return ch.key0 + (PA[e] - PA[f]);
+}
+
+// lane e < n_cigar: an I entry stores its (key, length) at its rank among the I entries
+__global__ __launch_bounds__(256) void k_cigp_keys(const uint64_t* __restrict__ cigar, uint64_t n_cigar, const CigPadChain* __restrict__ chains,
+                                                   uint64_t n_chains, const uint64_t* __restrict__ PA, const uint64_t* __restrict__ PI, uint64_t n_ins,
+                                                   uint64_t* __restrict__ key, uint64_t* __restrict__ len)
+{
+  const uint64_t e = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (e >= n_cigar || n_chains == 0) return;
+  const uint64_t v = cigar[e];
+  if ((v & 15u) != CIG_I) return;
+  const uint64_t i = PI[e];
+  if (i >= n_ins) return; // (n_ins = PI[n_cigar]: every I entry has a rank below it)
+  bool inner;
+  key[i] = cigp_key_of(chains, n_chains, PA, e, inner);
+  len[i] = v >> 4;
+}
+
+// lane i < n_sites: the absolute slot of site i; lane n_sites + g, g <= n_groups: where group g's sites begin
+__global__ __launch_bounds__(256) void k_cigp_sites(const uint64_t* __restrict__ site_key, uint64_t n_sites, const uint64_t* __restrict__ r0, uint64_t n_groups,
+                                                    uint64_t* __restrict__ site_pos, uint64_t* __restrict__ site_first)
+{
+  const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (g < n_sites) {
+    const uint64_t k = site_key[g], group = k >> 32;
+    site_pos[g] = (group < n_groups ? r0[group] : 0) + (k & 0xFFFFFFFFull);
+  } else if (g - n_sites <= n_groups) {
+    site_first[g - n_sites] = cigp_lower(site_key, n_sites, (g - n_sites) << 32);
+  }
+}
+
+struct CigPadPlan // what entry e becomes: its sites [s_lo, s_hi) and whether the first of them lies in front of its first base
+{
+  uint64_t v, key0, s_lo, s_hi;
+  uint32_t has0;
+  __device__ __forceinline__ uint64_t count(const uint64_t* __restrict__ site_w) const
+  {
+    if ((v & 15u) == CIG_I) return 1u + (s_lo < s_hi && site_w[s_lo] > (v >> 4) ? 1u : 0u); // the I, and the rest of the width
+    return 2u * (s_hi - s_lo) - has0 + 1u; // a P per site, a piece in front of every inner site and one behind the last
+  }
+};
+
+__device__ __forceinline__ CigPadPlan cigp_plan(const uint64_t* __restrict__ cigar, const CigPadChain* __restrict__ chains, uint64_t n_chains,
+                                                const uint64_t* __restrict__ PA, const uint64_t* __restrict__ site_key, uint64_t n_sites, uint64_t e)
+{
+  CigPadPlan p;
+  p.v = cigar[e];
+  bool inner;
+  p.key0 = cigp_key_of(chains, n_chains, PA, e, inner);
+  if ((p.v & 15u) == CIG_I) { // its own site (k_cigp_keys stored this key: it is there)
+    p.s_lo = cigp_lower(site_key, n_sites, p.key0);
+    p.s_hi = p.s_lo + (p.s_lo < n_sites && site_key[p.s_lo] == p.key0 ? 1u : 0u);
+    p.has0 = 0;
+  } else { // =, X, D: len A bases; the slot in front of it is the I's in front of it where the chain has one there
+    const bool own = inner && (cigar[e - 1u] & 15u) == CIG_I;
+    p.s_lo = cigp_lower(site_key, n_sites, p.key0 + (own ? 1u : 0u));
+    p.s_hi = cigp_lower(site_key, n_sites, p.key0 + (p.v >> 4));
+    if (p.s_hi < p.s_lo) p.s_hi = p.s_lo; // (ascending keys: never)
+    p.has0 = !own && p.s_lo < p.s_hi && site_key[p.s_lo] == p.key0 ? 1u : 0u;
+  }
+  return p;
+}
+
+// lane e <= n_cigar: the number of entries that entry e becomes, 0 behind the last
+__global__ __launch_bounds__(256) void k_cigp_count(const uint64_t* __restrict__ cigar, uint64_t n_cigar, const CigPadChain* __restrict__ chains,
+                                                    uint64_t n_chains, const uint64_t* __restrict__ PA, const uint64_t* __restrict__ site_key,
+                                                    const uint64_t* __restrict__ site_w, uint64_t n_sites, uint64_t* __restrict__ count)
+{
+  const uint64_t e = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (e > n_cigar) return;
+  count[e] = e < n_cigar && n_chains ? cigp_plan(cigar, chains, n_chains, PA, site_key, n_sites, e).count(site_w) : 0;
+}
+
+// lane o < n_out: output entry o
+__global__ __launch_bounds__(256) void k_cigp_emit(const uint64_t* __restrict__ cigar, uint64_t n_cigar, const CigPadChain* __restrict__ chains,
+                                                   uint64_t n_chains, const uint64_t* __restrict__ PA, const uint64_t* __restrict__ PO,
+                                                   const uint64_t* __restrict__ site_key, const uint64_t* __restrict__ site_w, uint64_t n_sites,
+                                                   uint64_t* __restrict__ out, uint64_t n_out)
+{
+  const uint64_t o = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (o >= n_out || n_cigar == 0 || n_chains == 0) return;
+  const uint64_t e = cig_last_at_or_before(n_cigar, o, [PO](uint64_t i) { return PO[i]; }); // (PO[0] = 0 <= o; every entry becomes at least one)
+  const CigPadPlan p = cigp_plan(cigar, chains, n_chains, PA, site_key, n_sites, e);
+  const uint64_t r = o - PO[e], code = p.v & 15u, len = p.v >> 4;
+  uint64_t say = 0; // (an entry of length 0: no reader takes it; only where the scan and the plan disagree, which they do not)
+  if (r >= p.count(site_w)) {
+  } else if (code == CIG_I) {
+    say = r == 0 ? p.v : (site_w[p.s_lo] - len) << 4 | CIG_P;
+  } else if (p.has0 && r == 0) {
+    say = site_w[p.s_lo] << 4 | CIG_P;
+  } else {
+    const uint64_t k = r - p.has0, q = k >> 1, base = p.s_lo + p.has0, inside = p.s_hi - base; // piece q or the P behind it; base: the first inner site
+    if (k & 1u) {
+      say = site_w[base + q] << 4 | CIG_P; // (k = 2 q + 1 <= 2 inside: q < inside)
+    } else {
+      const uint64_t from = q == 0 ? p.key0 : site_key[base + q - 1u], to = q >= inside ? p.key0 + len : site_key[base + q];
+      say = (to - from) << 4 | code;
+    }
+  }
+  out[o] = say;
+}
+
+int cigar_pad_run(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains, const nts_cig_pad_at* at,
+                  uint64_t n_groups, uint64_t** padded, uint64_t* pad_first, uint64_t* site_first, uint64_t** site_pos, uint64_t** site_w)
+{
+  std::vector<CigPadChain> placed;
+  std::vector<uint64_t> r0;
+  try {
+    placed.resize(n_chains);
+    r0.assign(std::max<uint64_t>(n_groups, 1), 0);
+  } catch (const std::bad_alloc&) {
+    return fail(ctx, NTS_ENOMEM, "nts_cigar_pad: no host memory for the chains and groups");
+  }
+  uint64_t lo = 0, hi = 0; // the extent of the group of the chain in front
+  auto place = [&](uint64_t c, auto who) -> int {
+    const nts_cig_chain& ch = chains[c];
+    const nts_cig_pad_at& a = at[c];
+    if (a.group >= n_groups) return fail(ctx, NTS_EINVAL, who() + " names a group outside n_groups");
+    if (c && a.group < at[c - 1].group) return fail(ctx, NTS_EINVAL, who() + ": the groups are not nondecreasing");
+    if (ch.n_cig) {
+      const uint64_t head = cigar[ch.first] & 15u, tail = cigar[ch.first + ch.n_cig - 1u] & 15u;
+      if ((head != CIG_EQ && head != CIG_X) || (tail != CIG_EQ && tail != CIG_X))
+        return fail(ctx, NTS_EINVAL, who() + ": its first or last entry is not = or X (pad the core of a chain)");
+    }
+    if (a.t0 > ~0ull - ch.len_a) return fail(ctx, NTS_ERANGE, who() + ": t0 + len_a wraps");
+    const bool opens = c == 0 || a.group != at[c - 1].group;
+    lo = opens ? a.t0 : std::min(lo, a.t0);
+    hi = opens ? a.t0 + ch.len_a : std::max(hi, a.t0 + ch.len_a);
+    if (hi - lo > 0xFFFFFFFFull) return fail(ctx, NTS_ERANGE, who() + ": the reference extent of its group is 2^32 or more");
+    r0[a.group] = lo;
+    placed[c] = { ch.first, a.t0 }; // (the key once every chain of the group is seen: below)
+    return NTS_OK;
+  };
+  if (const int rc = cig_chains_check(ctx, "nts_cigar_pad", CIG_TEXT_MAX_BASES_LOG2, true, chains, n_chains, n_cigar, place)) return rc;
+  for (uint64_t c = 0; c < n_chains; ++c) placed[c].key0 = ((uint64_t)at[c].group << 32) + (placed[c].key0 - r0[at[c].group]);
+  auto nothing = [&] {
+    *padded = nullptr;
+    *site_pos = nullptr;
+    *site_w = nullptr;
+    memset(pad_first, 0, (n_chains + 1) * 8);
+    memset(site_first, 0, (n_groups + 1) * 8);
+    return NTS_OK;
+  };
+  if (n_cigar == 0) return nothing(); // (nothing is launched)
+  // (its own buffers first: while nothing is queued, a request that fails may still return at once)
+  NTS_WS(d_placed, CigPadChain*, "cigp_placed", n_chains * sizeof(CigPadChain));
+  NTS_WS(d_r0, uint64_t*, "cigp_r0", std::max<uint64_t>(n_groups, 1) * 8);
+  NTS_WS(d_count, uint64_t*, "cigp_count", (n_cigar + 1) * 8);
+  NTS_WS(d_po, uint64_t*, "cigp_po", (n_cigar + 1) * 8);
+  NTS_WS(d_pad_first, uint64_t*, "cigp_pad_first", (n_chains + 1) * 8);
+  NTS_WS(d_site_first, uint64_t*, "cigp_site_first", (n_groups + 1) * 8);
+  NTS_WS(d_num, uint64_t*, "cigp_num", 8);
+  uint32_t worst = SCRIPT_OK;
+  uint64_t n_ins = 0, n_sites = 0;
+  CigIndex ix; // columns PA, PB, PI (I entries)
+  hipError_t e_run;
+  if (const int rc = cig_index_stage<CigPadOf>(ctx, "cigar_pad_sites", cigar, n_cigar, chains, n_chains, 0, &worst, ix, e_run, [] {})) return rc;
+  if (e_run == hipSuccess) e_run = hipGetLastError();
+  if (e_run == hipSuccess) e_run = hipMemcpyAsync(d_placed, placed.data(), n_chains * sizeof(CigPadChain), hipMemcpyHostToDevice, ctx->stream);
+  if (e_run == hipSuccess && n_groups) e_run = hipMemcpyAsync(d_r0, r0.data(), n_groups * 8, hipMemcpyHostToDevice, ctx->stream);
+  if (e_run == hipSuccess) e_run = hipMemcpyAsync(&n_ins, ix.column(2) + n_cigar, 8, hipMemcpyDeviceToHost, ctx->stream);
+  hipError_t e_sync = hipStreamSynchronize(ctx->stream); // (whatever happened: the caller's arrays were sources of asynchronous copies)
+  HIP_TRY(ctx, e_run);
+  HIP_TRY(ctx, e_sync);
+  if (worst != SCRIPT_OK) {
+    if (worst < n_chains) // (the error path alone looks at the entries of that one chain)
+      for (uint64_t e = chains[worst].first; e < chains[worst].first + chains[worst].n_cig; ++e)
+        if ((cigar[e] & 15u) == CIG_P)
+          return fail(ctx, NTS_EINVAL, "nts_cigar_pad: chain " + std::to_string(worst) + " holds an entry of code 6: it is padded already");
+    return fail(ctx, NTS_EINVAL, "nts_cigar_pad: the entries of chain " + std::to_string(worst) + " are no CIGAR of its lengths");
+  }
+  if (n_ins > n_cigar) return fail(ctx, NTS_EHIP, "nts_cigar_pad: the scan counted more I entries than there are entries");
+  // (the stream is idle: the buffers sized by the I entries are fetched before their kernels are queued)
+  const uint64_t cap = std::max<uint64_t>(n_ins, 1);
+  NTS_WS(d_key, uint64_t*, "cigp_key", cap * 8);
+  NTS_WS(d_len, uint64_t*, "cigp_len", cap * 8);
+  NTS_WS(d_key2, uint64_t*, "cigp_key2", cap * 8);
+  NTS_WS(d_len2, uint64_t*, "cigp_len2", cap * 8);
+  NTS_WS(d_site_key, uint64_t*, "cigp_site_key", cap * 8);
+  NTS_WS(d_site_w, uint64_t*, "cigp_site_w", cap * 8);
+  NTS_WS(d_site_pos, uint64_t*, "cigp_site_pos", cap * 8);
+  size_t tmp_sort = 0, tmp_red = 0, tmp_scan = 0;
+  if (n_ins) {
+    e_run = rocprim::radix_sort_pairs(nullptr, tmp_sort, d_key, d_key2, d_len, d_len2, n_ins, 0, 64, ctx->stream);
+    if (e_run == hipSuccess)
+      e_run = rocprim::reduce_by_key(nullptr, tmp_red, d_key2, d_len2, n_ins, d_site_key, d_site_w, d_num, rocprim::maximum<uint64_t>(),
+                                     rocprim::equal_to<uint64_t>(), ctx->stream);
+  }
+  if (e_run == hipSuccess) e_run = rocprim::exclusive_scan(nullptr, tmp_scan, d_count, d_po, (uint64_t)0, n_cigar + 1, CigPadSatAdd(), ctx->stream);
+  HIP_TRY(ctx, e_run);
+  NTS_WS(d_tmp, void*, "ivs_tmp", std::max<size_t>(std::max(tmp_sort, std::max(tmp_red, tmp_scan)), 16)); // (ix.tmp is dead from here)
+  if (n_ins) {
+    {
+      ScopedTimer t(ctx, "cigar_pad_sites", true);
+      NTS_LAUNCH(k_cigp_keys, IVL_GRID(n_cigar), ix.cigar, n_cigar, (const CigPadChain*)d_placed, n_chains, ix.column(0), ix.column(2), n_ins, d_key, d_len);
+      e_run = rocprim::radix_sort_pairs(d_tmp, tmp_sort, d_key, d_key2, d_len, d_len2, n_ins, 0, 64, ctx->stream);
+      if (e_run == hipSuccess)
+        e_run = rocprim::reduce_by_key(d_tmp, tmp_red, d_key2, d_len2, n_ins, d_site_key, d_site_w, d_num, rocprim::maximum<uint64_t>(),
+                                       rocprim::equal_to<uint64_t>(), ctx->stream);
+    }
+    if (e_run == hipSuccess) e_run = hipGetLastError();
+    if (e_run == hipSuccess) e_run = hipMemcpyAsync(&n_sites, d_num, 8, hipMemcpyDeviceToHost, ctx->stream);
+    e_sync = hipStreamSynchronize(ctx->stream);
+    HIP_TRY(ctx, e_run);
+    HIP_TRY(ctx, e_sync);
+    if (n_sites == 0 || n_sites > n_ins) return fail(ctx, NTS_EHIP, "nts_cigar_pad: the reduction left an impossible number of sites");
+  }
+  std::vector<uint64_t> host_pad_first(n_chains + 1), host_site_first(n_groups + 1); // (the caller's arrays are written only when the call succeeds)
+  {
+    ScopedTimer t(ctx, "cigar_pad_sites", true);
+    NTS_LAUNCH(k_cigp_sites, IVL_GRID(n_sites + n_groups + 1), (const uint64_t*)d_site_key, n_sites, (const uint64_t*)d_r0, n_groups, d_site_pos, d_site_first);
+  }
+  {
+    ScopedTimer t(ctx, "cigar_pad_emit", true);
+    NTS_LAUNCH(k_cigp_count, IVL_GRID(n_cigar + 1), ix.cigar, n_cigar, (const CigPadChain*)d_placed, n_chains, ix.column(0), (const uint64_t*)d_site_key,
+               (const uint64_t*)d_site_w, n_sites, d_count);
+    e_run = rocprim::exclusive_scan(d_tmp, tmp_scan, d_count, d_po, (uint64_t)0, n_cigar + 1, CigPadSatAdd(), ctx->stream);
+    if (e_run == hipSuccess) NTS_LAUNCH(k_cig_rows_firsts, IVL_GRID(n_chains + 1), ix.chains, n_chains, n_cigar, (const uint64_t*)d_po, d_pad_first);
+  }
+  if (e_run == hipSuccess) e_run = hipGetLastError();
+  if (e_run == hipSuccess) e_run = hipMemcpyAsync(host_pad_first.data(), d_pad_first, (n_chains + 1) * 8, hipMemcpyDeviceToHost, ctx->stream);
+  if (e_run == hipSuccess) e_run = hipMemcpyAsync(host_site_first.data(), d_site_first, (n_groups + 1) * 8, hipMemcpyDeviceToHost, ctx->stream);
+  e_sync = hipStreamSynchronize(ctx->stream);
+  HIP_TRY(ctx, e_run);
+  HIP_TRY(ctx, e_sync);
+  const uint64_t n_out = host_pad_first[n_chains];
+  if (n_out > 0xFFFFFFFFull) return fail(ctx, NTS_ERANGE, "nts_cigar_pad: 2^32 output entries or more");
+  if (n_out < n_cigar || host_site_first[n_groups] != n_sites) return fail(ctx, NTS_EHIP, "nts_cigar_pad: the scan left impossible totals");
+  // (the stream is idle: the output's buffer is fetched before its kernel is queued)
+  NTS_WS(d_out, uint64_t*, "cigp_out", n_out * 8);
+  uint64_t* host_out = (uint64_t*)malloc(n_out * 8);
+  uint64_t* host_pos = n_sites ? (uint64_t*)malloc(n_sites * 8) : nullptr;
+  uint64_t* host_w = n_sites ? (uint64_t*)malloc(n_sites * 8) : nullptr;
+  auto drop = [&] {
+    free(host_out);
+    free(host_pos);
+    free(host_w);
+  };
+  if (!host_out || (n_sites && (!host_pos || !host_w))) {
+    drop();
+    return fail(ctx, NTS_ENOMEM, "nts_cigar_pad: no host memory for the padded entries");
+  }
+  {
+    ScopedTimer t(ctx, "cigar_pad_emit", true);
+    NTS_LAUNCH(k_cigp_emit, IVL_GRID(n_out), ix.cigar, n_cigar, (const CigPadChain*)d_placed, n_chains, ix.column(0), (const uint64_t*)d_po,
+               (const uint64_t*)d_site_key, (const uint64_t*)d_site_w, n_sites, d_out, n_out);
+  }
+  e_run = hipGetLastError();
+  if (e_run == hipSuccess) e_run = hipMemcpyAsync(host_out, d_out, n_out * 8, hipMemcpyDeviceToHost, ctx->stream);
+  if (e_run == hipSuccess && n_sites) e_run = hipMemcpyAsync(host_pos, d_site_pos, n_sites * 8, hipMemcpyDeviceToHost, ctx->stream);
+  if (e_run == hipSuccess && n_sites) e_run = hipMemcpyAsync(host_w, d_site_w, n_sites * 8, hipMemcpyDeviceToHost, ctx->stream);
+  e_sync = hipStreamSynchronize(ctx->stream);
+  if (e_run != hipSuccess || e_sync != hipSuccess) drop();
+  HIP_TRY(ctx, e_run);
+  HIP_TRY(ctx, e_sync);
+  *padded = host_out;
+  *site_pos = host_pos;
+  *site_w = host_w;
+  memcpy(pad_first, host_pad_first.data(), (n_chains + 1) * 8);
+  memcpy(site_first, host_site_first.data(), (n_groups + 1) * 8);
   return NTS_OK;
 }

@@ -1088,7 +1088,34 @@ extern "C" int nts_cigar_rows(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_ci
   if ((n_cigar && !cigar) || (n_chains && !chains) || !row_a || !row_b || !row_first) return fail(ctx, NTS_EINVAL, "nts_cigar_rows: bad arguments");
   if (!a || !b || !spans) return fail(ctx, NTS_EINVAL, "nts_cigar_rows: the rows need spans and both genomes");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  return cigar_rows_run(ctx, cigar, n_cigar, chains, n_chains, a, b, spans, row_a, row_b, row_first);
+  return cigar_rows_run<false>(ctx, cigar, n_cigar, chains, n_chains, a, b, spans, row_a, row_b, row_first);
+}
+
+extern "C" int nts_cigar_rows_padded(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains,
+                                     const nts_genome* a, const nts_genome* b, const nts_cig_span* spans, uint8_t** row_a, uint8_t** row_b,
+                                     uint64_t* row_first)
+{
+  if (!ctx) return NTS_EINVAL;
+  if (n_cigar > 0xFFFFFFFFull || n_chains > 0xFFFFFFFFull) // (before any array is read)
+    return fail(ctx, NTS_ERANGE, "nts_cigar_rows_padded: 2^32 entries or chains or more");
+  if ((n_cigar && !cigar) || (n_chains && !chains) || !row_a || !row_b || !row_first)
+    return fail(ctx, NTS_EINVAL, "nts_cigar_rows_padded: bad arguments");
+  if (!a || !b || !spans) return fail(ctx, NTS_EINVAL, "nts_cigar_rows_padded: the rows need spans and both genomes");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return cigar_rows_run<true>(ctx, cigar, n_cigar, chains, n_chains, a, b, spans, row_a, row_b, row_first);
+}
+
+extern "C" int nts_cigar_pad(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains,
+                             const nts_cig_pad_at* at, uint64_t n_groups, uint64_t** padded, uint64_t* pad_first, uint64_t* site_first,
+                             uint64_t** site_pos, uint64_t** site_w)
+{
+  if (!ctx) return NTS_EINVAL;
+  if (n_cigar > 0xFFFFFFFFull || n_chains > 0xFFFFFFFFull || n_groups > 0xFFFFFFFFull) // (before any array is read)
+    return fail(ctx, NTS_ERANGE, "nts_cigar_pad: 2^32 entries, chains or groups or more");
+  if ((n_cigar && !cigar) || (n_chains && (!chains || !at)) || !padded || !pad_first || !site_first || !site_pos || !site_w)
+    return fail(ctx, NTS_EINVAL, "nts_cigar_pad: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return cigar_pad_run(ctx, cigar, n_cigar, chains, n_chains, at, n_groups, padded, pad_first, site_first, site_pos, site_w);
 }
 
 extern "C" int nts_graph_budget(nts_ctx* ctx, uint64_t bytes)

@@ -73,6 +73,9 @@ CIG_INS, CIG_DEL, CIG_EQ, CIG_X = 1, 2, 7, 8
 # CIG_B_BACKWARDS pos_b is its first base as read: backwards and complemented)
 CIG_SPAN_DTYPE = np.dtype([("pos_a", "<u8"), ("pos_b", "<u8"), ("rec_a", "<u4"), ("rec_b", "<u4"), ("flags", "<u4"), ("pad", "<u4")])
 CIG_B_BACKWARDS = 1
+# nts_cig_pad_at: what Context.cigar_pad takes per chain; CIG_PAD: the code of the entries it adds (BAM's P)
+CIG_PAD_AT_DTYPE = np.dtype([("group", "<u4"), ("reserved", "<u4"), ("t0", "<u8")])
+CIG_PAD = 6
 # nts_lift_query / nts_lift_hit: what Context.cigar_lift takes and returns, one per query
 LIFT_QUERY_DTYPE = np.dtype([("chain", "<u4"), ("side", "<u4"), ("pos", "<u8")])
 LIFT_HIT_DTYPE = np.dtype([("pos", "<u8"), ("entry", "<u8"), ("off", "<u8"), ("code", "<u4"), ("reserved", "<u4")])
@@ -481,13 +484,41 @@ class Context:
             return text, firsts[0].copy()
         return text, firsts[0].copy(), self._take(p_cs, int(firsts[1, -1]), np.dtype("u1")), firsts[1].copy()
 
-    def cigar_rows(self, cigar, chains, spans, genome_a, genome_b):
+    def cigar_pad(self, cigar, chains, at, n_groups=None):
+        """the padded CIGARs of a reference-anchored multiple alignment (nts_cigar_pad).  cigar and chains as cigar_build returns them,
+        the chains tiling the entries and every non-empty chain beginning and ending with an = or X entry; at: a CIG_PAD_AT_DTYPE
+        array, one {group, t0} per chain -- the chains of a group are aligned to one reference record, chain c covering its bases
+        [t0, t0 + len_a); groups nondecreasing and below n_groups (default: the last chain's group + 1).  Returns (padded, pad_first,
+        site_first, site_pos, site_w), all uint64: chain c's entries with the entries of code CIG_PAD it needs are
+        padded[pad_first[c]:pad_first[c + 1]]; group g's sites -- the slots in front of a reference base that hold an I entry of the
+        group -- are site_pos[site_first[g]:site_first[g + 1]], ascending, their widths site_w.  Reads no genome.  Exact and
+        deterministic."""
+        cg = np.ascontiguousarray(cigar, dtype=np.uint64)
+        ch = np.ascontiguousarray(chains, dtype=CHAIN_DTYPE)
+        where = np.ascontiguousarray(at, dtype=CIG_PAD_AT_DTYPE)
+        if cg.ndim != 1 or ch.ndim != 1 or where.shape != ch.shape:
+            raise ValueError("cigar_pad: a list of entries, a list of chain records and one {group, t0} per chain")
+        assert CHAIN_DTYPE.itemsize == ctypes.sizeof(_lib.CigChain) and CIG_PAD_AT_DTYPE.itemsize == ctypes.sizeof(_lib.CigPadAt)
+        if n_groups is None:
+            n_groups = int(where["group"][-1]) + 1 if where.size else 0
+        pad_first = np.zeros(ch.size + 1, dtype=np.uint64)
+        site_first = np.zeros(int(n_groups) + 1, dtype=np.uint64)
+        p_out, p_pos, p_w = c_vp(), c_vp(), c_vp()
+        self.check(self.lib.nts_cigar_pad(self.h, cg.ctypes.data if cg.size else None, cg.size, ch.ctypes.data if ch.size else None, ch.size,
+                                          where.ctypes.data if where.size else None, int(n_groups), ctypes.byref(p_out), pad_first.ctypes.data,
+                                          site_first.ctypes.data, ctypes.byref(p_pos), ctypes.byref(p_w)), "nts_cigar_pad")
+        n_sites = int(site_first[-1])
+        return (self._take(p_out, int(pad_first[-1]), np.dtype("<u8")), pad_first, site_first, self._take(p_pos, n_sites, np.dtype("<u8")),
+                self._take(p_w, n_sites, np.dtype("<u8")))
+
+    def cigar_rows(self, cigar, chains, spans, genome_a, genome_b, padded=False):
         """the aligned rows of the chains' CIGARs, the sequence lines of a MAF block (nts_cigar_rows).  cigar, chains, spans and the
         genomes as for cigar_text with spans; all are required.  Returns (row_a, row_b, row_first): two uint8 arrays of equal length
         and row_first [len(chains) + 1] uint64 -- chain c's rows are row_a[row_first[c]:row_first[c + 1]] and the same slice of
         row_b, one byte per alignment column: row_a the target base (`-` for I), row_b the query base as read (`-` for D), upper case
         ACGT and N for what is no base.  Refusals as cigar_text's; rows of 2^32 columns or more are refused.  Exact and
-        deterministic."""
+        deterministic.  padded=True (nts_cigar_rows_padded): entries of code CIG_PAD, as cigar_pad adds them, are accepted: a column
+        that is `-` in both rows and consumes no base; without it such an entry is refused."""
         cg = np.ascontiguousarray(cigar, dtype=np.uint64)
         ch = np.ascontiguousarray(chains, dtype=CHAIN_DTYPE)
         if cg.ndim != 1 or ch.ndim != 1:
@@ -502,10 +533,10 @@ class Context:
                 sp = np.zeros(1, dtype=CIG_SPAN_DTYPE)       # (a pointer that is not NULL: spans were given)
         first = np.zeros(ch.size + 1, dtype=np.uint64)
         p_a, p_b = c_vp(), c_vp()
-        self.check(self.lib.nts_cigar_rows(self.h, cg.ctypes.data if cg.size else None, cg.size, ch.ctypes.data if ch.size else None, ch.size,
-                                           genome_a.h if genome_a is not None else None, genome_b.h if genome_b is not None else None,
-                                           sp.ctypes.data if sp is not None else None, ctypes.byref(p_a), ctypes.byref(p_b), first.ctypes.data),
-                   "nts_cigar_rows")
+        call, name = (self.lib.nts_cigar_rows_padded, "nts_cigar_rows_padded") if padded else (self.lib.nts_cigar_rows, "nts_cigar_rows")
+        self.check(call(self.h, cg.ctypes.data if cg.size else None, cg.size, ch.ctypes.data if ch.size else None, ch.size,
+                        genome_a.h if genome_a is not None else None, genome_b.h if genome_b is not None else None,
+                        sp.ctypes.data if sp is not None else None, ctypes.byref(p_a), ctypes.byref(p_b), first.ctypes.data), name)
         n = int(first[-1])
         return self._take(p_a, n, np.dtype("u1")), self._take(p_b, n, np.dtype("u1")), first
 
