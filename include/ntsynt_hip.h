@@ -1109,6 +1109,36 @@ int nts_cigar_pad(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const n
 int nts_cigar_rows_padded(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains, const nts_genome* a,
                           const nts_genome* b, const nts_cig_span* spans, uint8_t** row_a, uint8_t** row_b, uint64_t* row_first);
 
+/* ---- per-base depth and identity over a star alignment: `--block-conservation` -----------------------------------------------------
+ * nts_cigar_depth: cigar, chains (they TILE the entries) and at[c] = {group, t0} as for nts_cigar_pad, but the chains need NOT be
+ *   cores, the entries need NOT be maximal runs, and the chains of one group may overlap freely (the call does not know rows).  For a
+ *   group g and a reference base p: aligned(g, p) = the chains of g with t0 <= p < t0 + len_a; match(g, p) = those of them in which
+ *   p lies in an = entry; gap(g, p) = those in which it lies in a D entry; the mismatches are aligned - match - gap; I entries
+ *   consume no reference base and change nothing.  A SEGMENT of group g is a maximal run [start, end) of consecutive reference bases
+ *   with aligned > 0 and one constant triple: two = entries separated by an I, two neighbouring X entries, or a chain that ends where
+ *   another begins with equal triples on both sides do not split it.
+ *   Out: *segs (release with nts_free; NULL when there is no segment): every group's segments ascending by (group, start), group
+ *   g's being [seg_first[g], seg_first[g + 1]); seg_first: n_groups + 1 host entries.  No genome is read.  NTS_ERANGE before any
+ *   launch: 2^32 entries, chains or groups or more (before any array is read); len_a or len_b that add up to 2^62 or more;
+ *   t0 + len_a beyond 64 bits; a group whose chains span 2^32 reference bases or more; a group of 2^20 chains or more (a count would
+ *   leave its 21-bit field).  NTS_EINVAL before any launch, the smallest chain named: chains that do not tile the entries, a group at
+ *   or beyond n_groups, groups that are not nondecreasing.  After the first scan, NTS_EINVAL with the smallest chain named: "holds
+ *   an entry of code 6", and "the entries of chain ... are no CIGAR of its lengths".  A refused call returns no buffer and writes
+ *   to no caller array.  One exclusive scan over the entries (A bases, B bases, consuming entries) and nts_cigar_lift's check; one
+ *   lane per entry and chain stores n_consuming + n_chains events (the state entered minus the state left, three 21-bit counts in
+ *   one word, added modulo 2^64), one radix sort and one reduce_by_key with the sum give the boundaries (timer
+ *   "cigar_depth_events"); one inclusive scan gives the states, one lane per boundary marks the heads, one exclusive scan ranks
+ *   them, one lane per boundary writes (timer "cigar_depth_emit").  On the context's stream, in its workspace; no atomic, no launch
+ *   per chain, group or segment, no floating point: the same input gives the same bytes.
+ *   docs/design/04_31_block_conservation.md; csrc/nts_cigar.inc; ntsynt_amd/assess.py block_conservation. */
+typedef struct
+{
+  uint64_t start, end;                  /* reference bases [start, end) of the group's record */
+  uint32_t group, aligned, match, gap;  /* mismatches: aligned - match - gap */
+} nts_cig_depth_seg;
+int nts_cigar_depth(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains, const nts_cig_pad_at* at,
+                    uint64_t n_groups, nts_cig_depth_seg** segs, uint64_t* seg_first);
+
 /* ---- C1-C5: minimizer graph -> collinear chains -----------------------------------------------------
  * replaces ntjoin_utils.read_minimizers' duplicate removal, filter_minimizers and build_graph
  * (call sites bin/ntsynt_synteny.py:607-612, 483, 539) and the path walk of Ntjoin.find_paths

@@ -97,6 +97,11 @@ class CigPadAt(ctypes.Structure):
     _fields_ = [("group", u32), ("reserved", u32), ("t0", u64)]
 
 
+class CigDepthSeg(ctypes.Structure):
+    "nts_cig_depth_seg: reference bases [start, end) of a group with one (aligned, match, gap) (nts_cigar_depth)"
+    _fields_ = [("start", u64), ("end", u64), ("group", u32), ("aligned", u32), ("match", u32), ("gap", u32)]
+
+
 class LiftQuery(ctypes.Structure):
     "nts_lift_query: an offset on one side of a chain (nts_cigar_lift)"
     _fields_ = [("chain", u32), ("side", u32), ("pos", u64)]
@@ -318,6 +323,7 @@ SYMBOLS = [
     ("nts_cigar_rows", ctypes.c_int, [c_vp, c_vp, u64, c_vp, u64, c_vp, c_vp, c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
     ("nts_cigar_rows_padded", ctypes.c_int, [c_vp, c_vp, u64, c_vp, u64, c_vp, c_vp, c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
     ("nts_cigar_pad", ctypes.c_int, [c_vp, c_vp, u64, c_vp, u64, c_vp, u64, ctypes.POINTER(c_vp), c_vp, c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp)]),
+    ("nts_cigar_depth", ctypes.c_int, [c_vp, c_vp, u64, c_vp, u64, c_vp, u64, ctypes.POINTER(c_vp), c_vp]),
     ("nts_genome_valid_bases", ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(Interval), u64, c_vp]),
     ("nts_minhash_pairs", ctypes.c_int, [c_vp, u32, c_vp, c_vp, u64, c_vp, c_vp, u64, c_vp, c_vp]),
     ("nts_graph_build", ctypes.c_int, [c_vp, u32, ctypes.POINTER(MxList), ctypes.POINTER(Graph)]),

@@ -23,6 +23,9 @@ Two things, both over `<prefix>.synteny_blocks.tsv`:
   events in both genomes' coordinates; docs/design/04_21_block_end_variants.md.
 * block MAF (`ntSynt --block-maf`, `ntsynt_block_stats --maf-out`): one pairwise MAF block per PAF record with both aligned rows, made on the
   GPU (nts_cigar_rows); docs/design/04_29_block_maf.md.
+* block conservation (`ntSynt --block-conservation`, `ntsynt_block_stats --conservation-out --conservation-stats-out`): per block the runs
+  of bases of its first line with one (aligned, match, gap) over the star pairs' CIGARs, made on the GPU (nts_cigar_depth), and the
+  covered, core and conserved bases per block; docs/design/04_31_block_conservation.md.
 * block chain file (`ntSynt --block-chain`, `ntsynt_block_stats --chain-out`): one UCSC liftover chain per block and pair, the chains of the
   block alignments joined per pair, blocks and data lines made on the GPU (nts_cigar_chain_blocks); docs/design/04_28_block_chain.md.
 * block alignments (`ntSynt --block-paf`, `ntsynt_block_stats --paf-out`): one PAF record with a cg:Z: CIGAR per aligned chain of every
@@ -1236,35 +1239,10 @@ def block_multi_mafs(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_R
     entries are checked on the host (unpadded_host gives the cores back; every chain has col0(t1) - col0(t0) columns) and the rows of its
     first chain are made on the host and compared: RuntimeError.  Returns multi_maf_table's parts."""
     import numpy as np
-    from .device import CHAIN_DTYPE, CIG_B_BACKWARDS, CIG_PAD_AT_DTYPE, CIG_SPAN_DTYPE
-    pairs, length = [], {}
-    order = {lines[0]: (g, lines) for g, (_, lines) in enumerate(_block_order(blocks))}        # first line -> (group, the block's lines)
-    held = []                                                # per core chain: (group, row, pos_a, its entries, len_a, len_b, span fields, names ...)
-    for a in _alignment_rounds(ctx, genomes_by_name, blocks, k, rate, band, max_len, max_edits, ends, pairs, length, star=True):
-        r, records = a.round, a.records
-        spans = alignment_spans(r, a.chains, a.flanks, a.results)
-        first, n_cig, len_a, len_b, pos_a, pos_b = chain_cores(a.cigar, records, spans)
-        pair_of = [r.lines[q] for q in np.asarray(a.chains["line"]).tolist()]
-        for c in np.flatnonzero(n_cig > 0).tolist():
-            la, lb, _ = pair_of[c]
-            group, lines = order[la]
-            held.append((group, lines.index(lb), int(pos_a[c]), a.cigar[first[c]:first[c] + n_cig[c]], int(len_a[c]), int(len_b[c]), int(pos_b[c]),
-                         int(spans["rec_a"][c]), int(spans["rec_b"][c]), int(spans["flags"][c]), la, lb, int(r.g_a.rec_len[int(spans["rec_a"][c])]),
-                         int(r.g_b.rec_len[int(spans["rec_b"][c])])))
-    held.sort(key=lambda h: h[:3])
-    n_groups = len(order)
+    from .device import CHAIN_DTYPE, CIG_B_BACKWARDS, CIG_SPAN_DTYPE
+    n_groups, held, entries, records, at = _star_cores(ctx, genomes_by_name, blocks, k, rate, band, max_len, max_edits, ends)
     if not held:
         return []
-    entries = np.concatenate([h[3] for h in held]).astype(np.uint64)
-    records = np.zeros(len(held), dtype=CHAIN_DTYPE)
-    records["n_cig"] = [h[3].size for h in held]
-    records["first"] = np.concatenate(([0], np.cumsum(records["n_cig"][:-1].astype(np.int64))))
-    records["len_a"], records["len_b"] = [h[4] for h in held], [h[5] for h in held]
-    at = np.zeros(len(held), dtype=CIG_PAD_AT_DTYPE)
-    at["group"], at["t0"] = [h[0] for h in held], [h[2] for h in held]
-    for prev, h in zip(held[:-1], held[1:]):
-        if prev[:2] == h[:2] and h[2] < prev[2] + prev[4]:
-            raise ValueError(f"block {blocks[h[10]].block_id}: two chains of {blocks[h[11]].genome} overlap in the reference")
     padded, pad_first, site_first, site_pos, site_w = ctx.cigar_pad(entries, records, at, n_groups)
     pad_first, site_first = pad_first.astype(np.int64), site_first.astype(np.int64)
     group_of = at["group"].astype(np.int64)
@@ -1338,6 +1316,175 @@ def block_multi_mafs(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_R
         sites = slice(site_first[g], site_first[g + 1])
         parts += multi_maf_parts(f"{ref.genome}.{ref.contig}", held[members[0]][12], chains, site_pos[sites], site_w[sites])
     return parts
+
+
+def _star_cores(ctx, genomes_by_name, blocks, k, rate, band, max_len, max_edits, ends):
+    """The core chains of every block's star pairs (first line, other line), as block_multi_mafs and block_conservation read them: the
+    pairs are aligned as block_alignments aligns them (_alignment_rounds with star), every chain is trimmed to its core (chain_cores) and
+    the cores are ordered by (block, row, x).  Two chains of one row that overlap in the reference raise ValueError.  Returns (n_groups,
+    held, entries, records, at): the number of blocks (a group each, in block_identity.tsv's order); per core chain (group, row, pos_a,
+    its entries, len_a, len_b, pos_b, rec_a, rec_b, span flags, line a, line b, rec_len_a, rec_len_b); and the chains' entries one behind
+    the other with their CHAIN_DTYPE records and CIG_PAD_AT_DTYPE {group, t0}: what nts_cigar_pad and nts_cigar_depth take (None where no
+    chain is held)."""
+    import numpy as np
+    from .device import CHAIN_DTYPE, CIG_PAD_AT_DTYPE
+    pairs, length = [], {}
+    order = {lines[0]: (g, lines) for g, (_, lines) in enumerate(_block_order(blocks))}        # first line -> (group, the block's lines)
+    held = []                                                # per core chain: (group, row, pos_a, its entries, len_a, len_b, span fields, names ...)
+    for a in _alignment_rounds(ctx, genomes_by_name, blocks, k, rate, band, max_len, max_edits, ends, pairs, length, star=True):
+        r, records = a.round, a.records
+        spans = alignment_spans(r, a.chains, a.flanks, a.results)
+        first, n_cig, len_a, len_b, pos_a, pos_b = chain_cores(a.cigar, records, spans)
+        pair_of = [r.lines[q] for q in np.asarray(a.chains["line"]).tolist()]
+        for c in np.flatnonzero(n_cig > 0).tolist():
+            la, lb, _ = pair_of[c]
+            group, lines = order[la]
+            held.append((group, lines.index(lb), int(pos_a[c]), a.cigar[first[c]:first[c] + n_cig[c]], int(len_a[c]), int(len_b[c]), int(pos_b[c]),
+                         int(spans["rec_a"][c]), int(spans["rec_b"][c]), int(spans["flags"][c]), la, lb, int(r.g_a.rec_len[int(spans["rec_a"][c])]),
+                         int(r.g_b.rec_len[int(spans["rec_b"][c])])))
+    held.sort(key=lambda h: h[:3])
+    n_groups = len(order)
+    if not held:
+        return n_groups, held, None, None, None
+    entries = np.concatenate([h[3] for h in held]).astype(np.uint64)
+    records = np.zeros(len(held), dtype=CHAIN_DTYPE)
+    records["n_cig"] = [h[3].size for h in held]
+    records["first"] = np.concatenate(([0], np.cumsum(records["n_cig"][:-1].astype(np.int64))))
+    records["len_a"], records["len_b"] = [h[4] for h in held], [h[5] for h in held]
+    at = np.zeros(len(held), dtype=CIG_PAD_AT_DTYPE)
+    at["group"], at["t0"] = [h[0] for h in held], [h[2] for h in held]
+    for prev, h in zip(held[:-1], held[1:]):
+        if prev[:2] == h[:2] and h[2] < prev[2] + prev[4]:
+            raise ValueError(f"block {blocks[h[10]].block_id}: two chains of {blocks[h[11]].genome} overlap in the reference")
+    return n_groups, held, entries, records, at
+
+# ---- block conservation: per-base depth and identity over the star alignment (docs/design/04_31_block_conservation.md) ----
+
+CONSERVATION_BED_COLUMNS = ("contig", "start", "end", "block_id", "genome", "rows", "aligned", "match", "mismatch", "gap")
+CONSERVATION_COLUMNS = ("block_id", "genome", "contig", "start", "end", "rows", "covered", "core", "conserved", "by_aligned", "by_match")
+
+
+def depth_segments_host(entries, records, at):
+    """nts_cigar_depth's segments of ONE group on the host: a difference array per count over the group's reference extent, one
+    cumulative sum each and a run-length encoding of the triples with aligned > 0.  entries, records, at: that group's chains (the
+    records' `first` index `entries`).  Returns (start, end, aligned, match, gap), int64 arrays.  Array operations over entries and
+    bases; the spot check of block_conservation and the baseline of scripts/block_conservation_measure.py.  Pure."""
+    import numpy as np
+    entries = np.ascontiguousarray(entries, dtype=np.uint64)
+    code, size = (entries & np.uint64(15)).astype(np.int64), (entries >> np.uint64(4)).astype(np.int64)
+    first, n_cig = records["first"].astype(np.int64), records["n_cig"].astype(np.int64)
+    t0, len_a = at["t0"].astype(np.int64), records["len_a"].astype(np.int64)
+    empty = np.zeros(0, dtype=np.int64)
+    if t0.size == 0:
+        return empty, empty, empty, empty, empty
+    r0, r1 = int(t0.min()), int((t0 + len_a).max())
+    uses = np.where(code == 1, 0, size)                      # the reference bases of every entry
+    before = np.concatenate(([0], np.cumsum(uses)))
+    chain_of = np.repeat(np.arange(first.size), n_cig)       # (the chains tile the entries)
+    begin = t0[chain_of] - r0 + before[:-1] - before[first[chain_of]]
+    counts = []
+    for which in (code != 1, code == 7, code == 2):
+        diff = np.zeros(r1 - r0 + 1, dtype=np.int64)
+        np.add.at(diff, begin[which], 1)
+        np.add.at(diff, (begin + uses)[which], -1)
+        counts.append(np.cumsum(diff)[:-1])
+    aligned, match, gap = counts
+    if aligned.size == 0:
+        return empty, empty, empty, empty, empty
+    same = (aligned[1:] == aligned[:-1]) & (match[1:] == match[:-1]) & (gap[1:] == gap[:-1])
+    head = np.flatnonzero(np.concatenate(([True], ~same)))
+    tail = np.concatenate((head[1:], [aligned.size]))
+    live = aligned[head] > 0
+    head, tail = head[live], tail[live]
+    return head + r0, tail + r0, aligned[head], match[head], gap[head]
+
+
+def block_conservation(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_RATE, band=IDENTITY_BAND, max_len=IDENTITY_MAX_LEN, max_edits=0, ends=None):
+    """Per synteny block the reference bases that its genomes share and those that are identical in all of them
+    (docs/design/04_31_block_conservation.md): the core chains of the star pairs (_star_cores, as block_multi_mafs collects them) go
+    through ONE nts_cigar_depth, which gives every block's maximal runs of reference bases with one (aligned, match, gap).  The first
+    group's segments are recomputed on the host (depth_segments_host) and compared: RuntimeError.  Returns (groups, segs, seg_first):
+    per block, in block_identity.tsv's order, (block_id, genome, contig, start, end, rows) of its first line with rows = its lines - 1;
+    the CIG_DEPTH_SEG_DTYPE segments and where each block's begin: what conservation_bed and conservation_table take."""
+    import numpy as np
+    from .device import CIG_DEPTH_SEG_DTYPE
+    n_groups, held, entries, records, at = _star_cores(ctx, genomes_by_name, blocks, k, rate, band, max_len, max_edits, ends)
+    groups = [(b, blocks[lines[0]].genome, blocks[lines[0]].contig, blocks[lines[0]].start, blocks[lines[0]].end, len(lines) - 1)
+              for b, lines in _block_order(blocks)]
+    if not held:
+        return groups, np.zeros(0, dtype=CIG_DEPTH_SEG_DTYPE), np.zeros(n_groups + 1, dtype=np.uint64)
+    segs, seg_first = ctx.cigar_depth(entries, records, at, n_groups)
+    g0 = int(at["group"][0])                                  # the spot check: the first group that has chains
+    mine = np.flatnonzero(at["group"] == g0)
+    sub = records[mine].copy()
+    sub["first"] -= records["first"][mine[0]]
+    lo, hi = int(records["first"][mine[0]]), int(records["first"][mine[-1]] + records["n_cig"][mine[-1]])
+    host = depth_segments_host(entries[lo:hi], sub, at[mine])
+    got = segs[int(seg_first[g0]):int(seg_first[g0 + 1])]
+    if any(not np.array_equal(got[f].astype(np.int64), h) for f, h in zip(("start", "end", "aligned", "match", "gap"), host)) or \
+            np.any(got["group"] != g0):
+        raise RuntimeError(f"block {groups[g0][0]}: the device's {got.size} conservation segments differ from the host's {host[0].size}")
+    return groups, segs, seg_first
+
+
+def conservation_summary(segs, seg_first, rows):
+    """Per group the bases of its segments by depth.  segs, seg_first: nts_cigar_depth's; rows[g]: the rows of group g besides the
+    reference (its lines - 1).  Returns a list of dicts: covered (aligned >= 1), core (aligned == rows), conserved (match == rows),
+    by_aligned (bases per aligned = 1 .. rows, a list) and by_match (core bases per match = 0 .. rows, a list).  A segment with aligned
+    > rows raises ValueError.  One np.add.at per histogram over all segments: no loop over segments or bases.  Pure."""
+    import numpy as np
+    rows = np.asarray(rows, dtype=np.int64)
+    seg_first = np.asarray(seg_first, dtype=np.int64)
+    n_groups = rows.size
+    if seg_first.size != n_groups + 1:
+        raise ValueError("conservation_summary: one entry of rows per group")
+    group = np.repeat(np.arange(n_groups), seg_first[1:] - seg_first[:-1])
+    size = segs["end"].astype(np.int64) - segs["start"].astype(np.int64)
+    aligned, match = segs["aligned"].astype(np.int64), segs["match"].astype(np.int64)
+    if np.any(aligned > rows[group]):
+        raise ValueError("conservation_summary: a segment is covered by more chains than its group has rows")
+    width = int(rows.max()) + 1 if n_groups else 1           # one histogram row per group: aligned or match 0 .. the most rows
+    by_aligned, by_match = np.zeros((n_groups, width), dtype=np.int64), np.zeros((n_groups, width), dtype=np.int64)
+    is_core = aligned == rows[group]
+    np.add.at(by_aligned, (group, aligned), size)
+    np.add.at(by_match, (group[is_core], match[is_core]), size[is_core])
+    out = []
+    for g, r in enumerate(rows.tolist()):
+        a, m = by_aligned[g, 1:r + 1].tolist(), by_match[g, :r + 1].tolist()
+        out.append({"covered": sum(a), "core": a[r - 1] if r else 0, "conserved": m[r] if r else 0, "by_aligned": a, "by_match": m})
+    return out
+
+
+def _conservation_parameters(k, rate, band, max_len, max_edits, ends):
+    return (f"# k {int(k)}, rate {int(rate)}, band {int(band)}, max_len {int(max_len)}, max_edits {int(max_edits)}" +
+            (f", ends_max_len {int(ends[0])}, ends_max_edits {int(ends[1])}, ends_penalty {int(ends[2])}" if ends is not None else ""))
+
+
+def conservation_bed(groups, segs, seg_first, k, rate, band, max_len, max_edits=0, ends=None):
+    """The text of `<prefix>.block_conservation.bed`: a `#` line with the parameters, then one line per segment, CONSERVATION_BED_COLUMNS:
+    the reference contig and bases [start, end), the block, the reference genome, the block's rows, and aligned, match, mismatch
+    (aligned - match - gap) and gap.  groups: block_conservation's.  Columns are made as arrays and joined once per line.  Pure."""
+    import numpy as np
+    seg_first = np.asarray(seg_first, dtype=np.int64)
+    group = np.repeat(np.arange(len(groups)), seg_first[1:] - seg_first[:-1])
+    of_group = [np.array([str(g[f]) for g in groups], dtype=object)[group] if len(groups) else np.zeros(0, dtype=object) for f in (2, 0, 1, 5)]
+    aligned, match, gap = (segs[f].astype(np.int64) for f in ("aligned", "match", "gap"))
+    columns = [of_group[0], segs["start"].astype(np.int64), segs["end"].astype(np.int64), of_group[1], of_group[2], of_group[3], aligned, match,
+               aligned - match - gap, gap]
+    lines = ["\t".join(line) for line in zip(*(np.asarray(c).astype(str).tolist() for c in columns))]
+    return "\n".join([_conservation_parameters(k, rate, band, max_len, max_edits, ends)] + lines) + "\n"
+
+
+def conservation_table(groups, segs, seg_first, k, rate, band, max_len, max_edits=0, ends=None):
+    """The text of `<prefix>.block_conservation.tsv`: a header, one line per block -- CONSERVATION_COLUMNS, the two histograms
+    comma-joined, integers only -- then the `#` line with the parameters.  Pure."""
+    summary = conservation_summary(segs, seg_first, [g[5] for g in groups])
+    lines = ["\t".join(CONSERVATION_COLUMNS)]
+    for g, s in zip(groups, summary):
+        lines.append("\t".join([str(v) for v in g] + [str(s["covered"]), str(s["core"]), str(s["conserved"]), ",".join(map(str, s["by_aligned"])),
+                                                      ",".join(map(str, s["by_match"]))]))
+    lines.append(_conservation_parameters(k, rate, band, max_len, max_edits, ends))
+    return "\n".join(lines) + "\n"
 
 
 LIFT_COLUMNS = ("genome", "contig", "start", "end", "name", "block_id", "to_genome", "to_contig", "to_start", "to_end", "orientation", "ch", "src_start",
@@ -2053,6 +2200,10 @@ def main(argv=None):
     p.add_argument("--multi-maf-out", help="with --fastas: file for the block multi-MAF (one reference-anchored multiple alignment per synteny block, anchored "
                    "on the block's first line, cut into sub-blocks where the covering genomes change; padded CIGARs and rows made on the GPU); it takes "
                    "the parameters of --paf-out; a pass of its own, which loads each query genome a second time for the rows")
+    p.add_argument("--conservation-out", help="with --fastas and --conservation-stats-out: file for the block conservation segments (BED: per synteny "
+                   "block the runs of bases of its first line with one aligned / match / mismatch / gap count over the star alignment of "
+                   "--multi-maf-out; made on the GPU); it takes the parameters of --paf-out; a pass of its own")
+    p.add_argument("--conservation-stats-out", help="with --conservation-out: file for the per-block table (covered, core and conserved bases, histograms)")
     p.add_argument("--lift-bed", help="with --fastas, --lift-genome and --lift-out: a BED file of intervals of one genome that are mapped through the block "
                    "alignments into the other genomes (GPU); it takes the parameters of --paf-out")
     p.add_argument("--lift-genome", help="the genome the intervals of --lift-bed lie on: a FASTA base name, as in column 2 of the block table")
@@ -2097,6 +2248,14 @@ def main(argv=None):
     if args.multi_maf_out:
         if not args.fastas:
             p.error("--multi-maf-out needs the genomes: --fastas")
+        message = check_identity_parameters(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits)
+        if message:
+            p.error(message)
+    if bool(args.conservation_out) != bool(args.conservation_stats_out):
+        p.error("--conservation-out and --conservation-stats-out go together")
+    if args.conservation_out:
+        if not args.fastas:
+            p.error("--conservation-out needs the genomes: --fastas")
         message = check_identity_parameters(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits)
         if message:
             p.error(message)
@@ -2253,6 +2412,12 @@ def main(argv=None):
                                            ends=(args.ends_max_len, args.ends_max_edits, args.ends_penalty) if args.ends_out else None)
             with open(args.multi_maf_out, "w", encoding="utf-8") as fh:
                 fh.write(multi_maf_table(multi_parts))
+        if args.conservation_out:                             # (a pass of its own)
+            c_ends = (args.ends_max_len, args.ends_max_edits, args.ends_penalty) if args.ends_out else None
+            conserved = block_conservation(ctx, loaders, read_blocks(args.tsv), *id_args, max_edits=args.identity_max_edits, ends=c_ends)
+            for path, table in ((args.conservation_out, conservation_bed), (args.conservation_stats_out, conservation_table)):
+                with open(path, "w", encoding="utf-8") as fh:
+                    fh.write(table(*conserved, *id_args, max_edits=args.identity_max_edits, ends=c_ends))
     finally:
         ctx.close()
     if args.divergence_out:

@@ -2278,3 +2278,304 @@ int cigar_pad_run(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const n
   memcpy(site_first, host_site_first.data(), (n_groups + 1) * 8);
   return NTS_OK;
 }
+
+// ---- per-base depth and identity over a star alignment: the segments of constant (aligned, match, gap) (nts_cigar_depth) ----
+// docs/design/04_31_block_conservation.md.  Input as nts_cigar_pad's -- entries, chain records that tile them, {group, t0} per chain --
+// but the chains need not be cores, the entries need not be maximal runs, and chains of one group may overlap freely.  For a group g
+// and a reference base p: aligned = the chains of g that cover p, match = those in which p lies in an = entry, gap = those in which
+// it lies in a D entry.  A SEGMENT is a maximal run of reference bases of one group with aligned > 0 and one triple.  No genome is read.
+//   1  cig_index_stage with (A bases, B bases, consuming entries): the third prefix PC ranks the =, X and D entries.  k_cigd_events:
+//      one lane per entry and one per chain.  A consuming entry stores ONE event at its rank: key group << 32 | the base it begins at
+//      - R0, value the state it enters minus the state of the consuming entry in front of it in its chain (nothing in front: the state
+//      alone, which opens the chain); chain c stores one closing event at slot n_consuming + c: key t1, value minus the state of its
+//      last consuming entry (0 where it has none).  A state is three counts in one 64-bit word, 21 bits each, added modulo 2^64: exact
+//      where every true count is below 2^21, and a group holds fewer than 2^20 chains.  ONE radix sort of the pairs, ONE reduce_by_key
+//      with the sum: the distinct boundaries, ascending by group and base, and their net deltas (timer "cigar_depth_events").
+//   2  ONE inclusive scan of the deltas over ALL boundaries (every group closes to zero): the state of the stretch behind each.
+//      k_cigd_heads: one lane per boundary; its stretch is LIVE when the next boundary is of its group and aligned > 0, and a HEAD
+//      when the stretch in front is not live or has another triple.  ONE exclusive scan of the heads.  k_cigd_firsts: one lane per
+//      group and one more, a lower-bound search over the boundary keys.  k_cigd_emit: one lane per boundary; a head writes start,
+//      group and triple at its rank, the last live stretch of a run writes end (timer "cigar_depth_emit").
+// No atomic, no launch per chain, group or segment, no floating point, no host loop over entries, events or segments (one over
+// chains: the checks and R0).
+
+static_assert(sizeof(nts_cig_depth_seg) == 32, "the C ABI's layout");
+
+constexpr uint32_t CIGD_FIELD = 21;                         // bits per count
+constexpr uint64_t CIGD_MASK = (1ull << CIGD_FIELD) - 1u;
+constexpr uint64_t CIGD_MOST_CHAINS = 1ull << 20;           // a group of that many chains is refused: a count might leave its field
+constexpr uint64_t CIGD_ALIGNED = 1ull, CIGD_MATCH = 1ull << CIGD_FIELD, CIGD_GAP = 1ull << (2 * CIGD_FIELD);
+constexpr uint64_t CIGD_BAD = 1ull << 63, CIGD_RANK = (1ull << 40) - 1u; // a head count: its rank below 2^40, and whether a group did not close
+
+__host__ __device__ inline bool cigd_consumes(uint64_t v)
+{
+  const uint64_t code = v & 15u;
+  return code == CIG_EQ || code == CIG_X || code == CIG_D;
+}
+
+// what a chain adds to the counts of the reference bases of a consuming entry
+__device__ __forceinline__ uint64_t cigd_state(uint64_t v)
+{
+  const uint64_t code = v & 15u;
+  return CIGD_ALIGNED + (code == CIG_EQ ? CIGD_MATCH : 0u) + (code == CIG_D ? CIGD_GAP : 0u);
+}
+
+using CigDepthTuple = rocprim::tuple<uint64_t, uint64_t, uint64_t>; // A bases, B bases, consuming entries
+
+struct CigDepthOf // element e of the scan's input: what entry e consumes and whether it consumes reference bases; nothing behind the last entry
+{
+  using Tuple = CigDepthTuple;
+  const uint64_t* cigar;
+  uint64_t n_cigar;
+  __device__ Tuple operator()(uint64_t e) const
+  {
+    if (e >= n_cigar) return Tuple(0, 0, 0);
+    const uint64_t v = cigar[e];
+    const CigBases ab = cig_bases(v);
+    return Tuple(rocprim::get<0>(ab), rocprim::get<1>(ab), cigd_consumes(v) ? 1u : 0u);
+  }
+};
+
+struct CigDepthHeadAdd // ranks add (below 2^40: there are fewer than 2^34 boundaries), the flag of a group that did not close is kept
+{
+  __host__ __device__ uint64_t operator()(uint64_t x, uint64_t y) const { return (((x & CIGD_RANK) + (y & CIGD_RANK)) & CIGD_RANK) | ((x | y) & CIGD_BAD); }
+};
+
+// the consuming entry of rank r among entries [lo, hi) with PC[lo] <= r < PC[hi]: the last e with PC[e] <= r
+__device__ __forceinline__ uint64_t cigd_entry_of_rank(const uint64_t* __restrict__ PC, uint64_t lo, uint64_t hi, uint64_t r)
+{
+  while (hi - lo > 1u) {
+    const uint64_t mid = lo + (hi - lo) / 2u;
+    if (PC[mid] <= r) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// lane e < n_cigar: a consuming entry stores its event at its rank; lane n_cigar + c: chain c's closing event at slot n_cons + c
+__global__ __launch_bounds__(256) void k_cigd_events(const uint64_t* __restrict__ cigar, uint64_t n_cigar, const CigPadChain* __restrict__ placed,
+                                                     const nts_cig_chain* __restrict__ chains, uint64_t n_chains, const uint64_t* __restrict__ PA,
+                                                     const uint64_t* __restrict__ PC, uint64_t n_cons, uint64_t* __restrict__ key,
+                                                     uint64_t* __restrict__ val)
+{
+  const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (g >= n_cigar + n_chains || n_chains == 0) return;
+  if (g < n_cigar) {
+    const uint64_t v = cigar[g];
+    if (!cigd_consumes(v)) return;
+    const uint64_t i = PC[g];
+    if (i >= n_cons) return; // (n_cons = PC[n_cigar]: every consuming entry has a rank below it)
+    const CigPadChain ch = placed[cig_last_at_or_before(n_chains, g, [placed](uint64_t c) { return placed[c].first; })];
+    const uint64_t f = ch.first <= g ? ch.first : g;
+    uint64_t before = 0; // the state of the consuming entry in front of it in its chain
+    if (i > PC[f]) {
+      const uint64_t p = cigd_consumes(cigar[g - 1u]) ? g - 1u : cigd_entry_of_rank(PC, f, g, i - 1u); // (i > PC[f]: g > f)
+      before = cigd_state(cigar[p]);
+    }
+    key[i] = ch.key0 + (PA[g] - PA[f]);
+    val[i] = cigd_state(v) - before;
+  } else {
+    const uint64_t c = g - n_cigar;
+    const nts_cig_chain ch = chains[c];
+    uint64_t k = placed[c].key0, last = 0;
+    if (!cig_chain_beyond(ch, n_cigar)) {
+      const uint64_t end = ch.first + ch.n_cig;
+      k += PA[end] - PA[ch.first];
+      if (PC[end] > PC[ch.first]) last = cigd_state(cigar[cigd_entry_of_rank(PC, ch.first, end, PC[end] - 1u)]);
+    }
+    key[n_cons + c] = k; // (n_cons + n_chains words)
+    val[n_cons + c] = 0u - last;
+  }
+}
+
+// whether the stretch behind boundary i is live: the next boundary is of its group and some chain covers it
+__device__ __forceinline__ bool cigd_live(const uint64_t* __restrict__ bkey, const uint64_t* __restrict__ state, uint64_t n_b, uint64_t i)
+{
+  return i + 1u < n_b && (bkey[i + 1u] >> 32) == (bkey[i] >> 32) && (state[i] & CIGD_MASK) != 0;
+}
+
+// whether the live stretch behind boundary i opens a segment: the stretch in front is not live (or of another group: then it is not) or has another triple
+__device__ __forceinline__ bool cigd_head(const uint64_t* __restrict__ bkey, const uint64_t* __restrict__ state, uint64_t n_b, uint64_t i)
+{
+  return !(i > 0 && cigd_live(bkey, state, n_b, i - 1u) && state[i - 1u] == state[i]);
+}
+
+// lane i < n_b: 1 for a head, and the flag of a group that ends with a state other than zero; lane n_b: 0
+__global__ __launch_bounds__(256) void k_cigd_heads(const uint64_t* __restrict__ bkey, const uint64_t* __restrict__ state, uint64_t n_b,
+                                                    uint64_t* __restrict__ head)
+{
+  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (i > n_b) return;
+  uint64_t say = 0;
+  if (i < n_b) {
+    if (cigd_live(bkey, state, n_b, i) && cigd_head(bkey, state, n_b, i)) say = 1u;
+    if ((i + 1u == n_b || (bkey[i + 1u] >> 32) != (bkey[i] >> 32)) && state[i] != 0) say |= CIGD_BAD;
+  }
+  head[i] = say; // (n_b + 1 words)
+}
+
+// lane g <= n_groups: where group g's segments begin; lane n_groups + 1: whether some group did not close
+__global__ __launch_bounds__(256) void k_cigd_firsts(const uint64_t* __restrict__ bkey, uint64_t n_b, const uint64_t* __restrict__ rank, uint64_t n_groups,
+                                                     uint64_t* __restrict__ seg_first)
+{
+  const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (g <= n_groups) seg_first[g] = rank[cigp_lower(bkey, n_b, g << 32)] & CIGD_RANK; // (cigp_lower <= n_b; rank: n_b + 1 words)
+  else if (g == n_groups + 1u) seg_first[g] = rank[n_b] >> 63;                     // (n_groups + 2 words)
+}
+
+// lane i < n_b: a head writes its segment's start, group and triple; the last live stretch of a run writes its end
+__global__ __launch_bounds__(256) void k_cigd_emit(const uint64_t* __restrict__ bkey, const uint64_t* __restrict__ state, uint64_t n_b,
+                                                   const uint64_t* __restrict__ rank, const uint64_t* __restrict__ r0, uint64_t n_groups,
+                                                   nts_cig_depth_seg* __restrict__ segs, uint64_t n_segs)
+{
+  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (i >= n_b || !cigd_live(bkey, state, n_b, i)) return;
+  const uint64_t k = bkey[i], group = k >> 32, s = state[i];
+  const uint64_t base = group < n_groups ? r0[group] : 0;
+  const uint64_t r = (rank[i + 1u] & CIGD_RANK) - 1u; // the heads up to and with this stretch, less one: the head of its run (0 - 1: beyond n_segs)
+  if (r >= n_segs) return;
+  if (cigd_head(bkey, state, n_b, i)) {
+    segs[r].start = base + (k & 0xFFFFFFFFull);
+    segs[r].group = (uint32_t)group;
+    segs[r].aligned = (uint32_t)(s & CIGD_MASK);
+    segs[r].match = (uint32_t)(s >> CIGD_FIELD & CIGD_MASK);
+    segs[r].gap = (uint32_t)(s >> (2 * CIGD_FIELD) & CIGD_MASK);
+  }
+  if (!(cigd_live(bkey, state, n_b, i + 1u) && state[i + 1u] == s)) segs[r].end = base + (bkey[i + 1u] & 0xFFFFFFFFull); // (live: i + 1 < n_b)
+}
+
+int cigar_depth_run(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains, const nts_cig_pad_at* at,
+                    uint64_t n_groups, nts_cig_depth_seg** segs, uint64_t* seg_first)
+{
+  std::vector<CigPadChain> placed;
+  std::vector<uint64_t> r0;
+  try {
+    placed.resize(n_chains);
+    r0.assign(std::max<uint64_t>(n_groups, 1), 0);
+  } catch (const std::bad_alloc&) {
+    return fail(ctx, NTS_ENOMEM, "nts_cigar_depth: no host memory for the chains and groups");
+  }
+  uint64_t lo = 0, hi = 0, members = 0; // the extent and the chains of the group of the chain in front
+  auto place = [&](uint64_t c, auto who) -> int {
+    const nts_cig_chain& ch = chains[c];
+    const nts_cig_pad_at& a = at[c];
+    if (a.group >= n_groups) return fail(ctx, NTS_EINVAL, who() + " names a group outside n_groups");
+    if (c && a.group < at[c - 1].group) return fail(ctx, NTS_EINVAL, who() + ": the groups are not nondecreasing");
+    if (a.t0 > ~0ull - ch.len_a) return fail(ctx, NTS_ERANGE, who() + ": t0 + len_a wraps");
+    const bool opens = c == 0 || a.group != at[c - 1].group;
+    lo = opens ? a.t0 : std::min(lo, a.t0);
+    hi = opens ? a.t0 + ch.len_a : std::max(hi, a.t0 + ch.len_a);
+    members = opens ? 1 : members + 1;
+    if (hi - lo > 0xFFFFFFFFull) return fail(ctx, NTS_ERANGE, who() + ": the reference extent of its group is 2^32 or more");
+    if (members >= CIGD_MOST_CHAINS) return fail(ctx, NTS_ERANGE, who() + ": its group has 2^20 chains or more");
+    r0[a.group] = lo;
+    placed[c] = { ch.first, a.t0 }; // (the key once every chain of the group is seen: below)
+    return NTS_OK;
+  };
+  if (const int rc = cig_chains_check(ctx, "nts_cigar_depth", CIG_TEXT_MAX_BASES_LOG2, true, chains, n_chains, n_cigar, place)) return rc;
+  for (uint64_t c = 0; c < n_chains; ++c) placed[c].key0 = ((uint64_t)at[c].group << 32) + (placed[c].key0 - r0[at[c].group]);
+  if (n_cigar == 0) { // (nothing is launched)
+    *segs = nullptr;
+    memset(seg_first, 0, (n_groups + 1) * 8);
+    return NTS_OK;
+  }
+  // (its own buffers first: while nothing is queued, a request that fails may still return at once)
+  NTS_WS(d_placed, CigPadChain*, "cigd_placed", n_chains * sizeof(CigPadChain));
+  NTS_WS(d_r0, uint64_t*, "cigd_r0", std::max<uint64_t>(n_groups, 1) * 8);
+  NTS_WS(d_seg_first, uint64_t*, "cigd_seg_first", (n_groups + 2) * 8);
+  NTS_WS(d_num, uint64_t*, "cigd_num", 8);
+  uint32_t worst = SCRIPT_OK;
+  uint64_t n_cons = 0, n_b = 0;
+  CigIndex ix; // columns PA, PB, PC (consuming entries)
+  hipError_t e_run;
+  if (const int rc = cig_index_stage<CigDepthOf>(ctx, "cigar_depth_events", cigar, n_cigar, chains, n_chains, 0, &worst, ix, e_run, [] {})) return rc;
+  if (e_run == hipSuccess) e_run = hipGetLastError();
+  if (e_run == hipSuccess) e_run = hipMemcpyAsync(d_placed, placed.data(), n_chains * sizeof(CigPadChain), hipMemcpyHostToDevice, ctx->stream);
+  if (e_run == hipSuccess && n_groups) e_run = hipMemcpyAsync(d_r0, r0.data(), n_groups * 8, hipMemcpyHostToDevice, ctx->stream);
+  if (e_run == hipSuccess) e_run = hipMemcpyAsync(&n_cons, ix.column(2) + n_cigar, 8, hipMemcpyDeviceToHost, ctx->stream);
+  hipError_t e_sync = hipStreamSynchronize(ctx->stream); // (whatever happened: the caller's arrays were sources of asynchronous copies)
+  HIP_TRY(ctx, e_run);
+  HIP_TRY(ctx, e_sync);
+  if (worst != SCRIPT_OK) {
+    if (worst < n_chains) // (the error path alone looks at the entries of that one chain)
+      for (uint64_t e = chains[worst].first; e < chains[worst].first + chains[worst].n_cig; ++e)
+        if ((cigar[e] & 15u) == CIG_P) return fail(ctx, NTS_EINVAL, "nts_cigar_depth: chain " + std::to_string(worst) + " holds an entry of code 6");
+    return fail(ctx, NTS_EINVAL, "nts_cigar_depth: the entries of chain " + std::to_string(worst) + " are no CIGAR of its lengths");
+  }
+  if (n_cons > n_cigar) return fail(ctx, NTS_EHIP, "nts_cigar_depth: the scan counted more consuming entries than there are entries");
+  // (the stream is idle: the buffers sized by the events are fetched before their kernels are queued)
+  const uint64_t n_ev = n_cons + n_chains; // (>= 1: entries have a chain)
+  NTS_WS(d_key, uint64_t*, "cigd_key", n_ev * 8);
+  NTS_WS(d_val, uint64_t*, "cigd_val", n_ev * 8);
+  NTS_WS(d_key2, uint64_t*, "cigd_key2", n_ev * 8);
+  NTS_WS(d_val2, uint64_t*, "cigd_val2", n_ev * 8);
+  NTS_WS(d_bkey, uint64_t*, "cigd_bkey", n_ev * 8);
+  NTS_WS(d_delta, uint64_t*, "cigd_delta", n_ev * 8);
+  NTS_WS(d_state, uint64_t*, "cigd_state", n_ev * 8);
+  NTS_WS(d_head, uint64_t*, "cigd_head", (n_ev + 1) * 8);
+  NTS_WS(d_rank, uint64_t*, "cigd_rank", (n_ev + 1) * 8);
+  size_t tmp_sort = 0, tmp_red = 0, tmp_scan = 0, tmp_ranks = 0;
+  e_run = rocprim::radix_sort_pairs(nullptr, tmp_sort, d_key, d_key2, d_val, d_val2, n_ev, 0, 64, ctx->stream);
+  if (e_run == hipSuccess)
+    e_run = rocprim::reduce_by_key(nullptr, tmp_red, d_key2, d_val2, n_ev, d_bkey, d_delta, d_num, rocprim::plus<uint64_t>(), rocprim::equal_to<uint64_t>(),
+                                   ctx->stream);
+  if (e_run == hipSuccess) e_run = rocprim::inclusive_scan(nullptr, tmp_scan, d_delta, d_state, n_ev, rocprim::plus<uint64_t>(), ctx->stream);
+  if (e_run == hipSuccess) e_run = rocprim::exclusive_scan(nullptr, tmp_ranks, d_head, d_rank, (uint64_t)0, n_ev + 1, CigDepthHeadAdd(), ctx->stream);
+  HIP_TRY(ctx, e_run);
+  NTS_WS(d_tmp, void*, "ivs_tmp", std::max<size_t>(std::max(std::max(tmp_sort, tmp_red), std::max(tmp_scan, tmp_ranks)), 16)); // (ix.tmp is dead from here)
+  {
+    ScopedTimer t(ctx, "cigar_depth_events", true);
+    NTS_LAUNCH(k_cigd_events, IVL_GRID(n_cigar + n_chains), ix.cigar, n_cigar, (const CigPadChain*)d_placed, ix.chains, n_chains, ix.column(0), ix.column(2),
+               n_cons, d_key, d_val);
+    e_run = rocprim::radix_sort_pairs(d_tmp, tmp_sort, d_key, d_key2, d_val, d_val2, n_ev, 0, 64, ctx->stream);
+    if (e_run == hipSuccess)
+      e_run = rocprim::reduce_by_key(d_tmp, tmp_red, d_key2, d_val2, n_ev, d_bkey, d_delta, d_num, rocprim::plus<uint64_t>(), rocprim::equal_to<uint64_t>(),
+                                     ctx->stream);
+  }
+  if (e_run == hipSuccess) e_run = hipGetLastError();
+  if (e_run == hipSuccess) e_run = hipMemcpyAsync(&n_b, d_num, 8, hipMemcpyDeviceToHost, ctx->stream);
+  e_sync = hipStreamSynchronize(ctx->stream);
+  HIP_TRY(ctx, e_run);
+  HIP_TRY(ctx, e_sync);
+  if (n_b == 0 || n_b > n_ev) return fail(ctx, NTS_EHIP, "nts_cigar_depth: the reduction left an impossible number of boundaries");
+  std::vector<uint64_t> host_seg_first(n_groups + 2); // (the caller's array is written only when the call succeeds)
+  {
+    ScopedTimer t(ctx, "cigar_depth_emit", true);
+    e_run = rocprim::inclusive_scan(d_tmp, tmp_scan, d_delta, d_state, n_b, rocprim::plus<uint64_t>(), ctx->stream);
+    if (e_run == hipSuccess) {
+      NTS_LAUNCH(k_cigd_heads, IVL_GRID(n_b + 1), (const uint64_t*)d_bkey, (const uint64_t*)d_state, n_b, d_head);
+      e_run = rocprim::exclusive_scan(d_tmp, tmp_ranks, d_head, d_rank, (uint64_t)0, n_b + 1, CigDepthHeadAdd(), ctx->stream);
+    }
+    if (e_run == hipSuccess)
+      NTS_LAUNCH(k_cigd_firsts, IVL_GRID(n_groups + 2), (const uint64_t*)d_bkey, n_b, (const uint64_t*)d_rank, n_groups, d_seg_first);
+  }
+  if (e_run == hipSuccess) e_run = hipGetLastError();
+  if (e_run == hipSuccess) e_run = hipMemcpyAsync(host_seg_first.data(), d_seg_first, (n_groups + 2) * 8, hipMemcpyDeviceToHost, ctx->stream);
+  e_sync = hipStreamSynchronize(ctx->stream);
+  HIP_TRY(ctx, e_run);
+  HIP_TRY(ctx, e_sync);
+  const uint64_t n_segs = host_seg_first[n_groups];
+  if (host_seg_first[n_groups + 1]) return fail(ctx, NTS_EHIP, "nts_cigar_depth: a group does not close to zero");
+  if (n_segs > n_b) return fail(ctx, NTS_EHIP, "nts_cigar_depth: the scan left an impossible number of segments");
+  nts_cig_depth_seg* host_segs = nullptr;
+  if (n_segs) {
+    // (the stream is idle: the output's buffer is fetched before its kernel is queued)
+    NTS_WS(d_segs, nts_cig_depth_seg*, "cigd_segs", n_segs * sizeof(nts_cig_depth_seg));
+    host_segs = (nts_cig_depth_seg*)malloc(n_segs * sizeof(nts_cig_depth_seg));
+    if (!host_segs) return fail(ctx, NTS_ENOMEM, "nts_cigar_depth: no host memory for the segments");
+    {
+      ScopedTimer t(ctx, "cigar_depth_emit", true);
+      NTS_LAUNCH(k_cigd_emit, IVL_GRID(n_b), (const uint64_t*)d_bkey, (const uint64_t*)d_state, n_b, (const uint64_t*)d_rank, (const uint64_t*)d_r0, n_groups,
+                 d_segs, n_segs);
+    }
+    e_run = hipGetLastError();
+    if (e_run == hipSuccess) e_run = hipMemcpyAsync(host_segs, d_segs, n_segs * sizeof(nts_cig_depth_seg), hipMemcpyDeviceToHost, ctx->stream);
+    e_sync = hipStreamSynchronize(ctx->stream);
+    if (e_run != hipSuccess || e_sync != hipSuccess) free(host_segs);
+    HIP_TRY(ctx, e_run);
+    HIP_TRY(ctx, e_sync);
+  }
+  *segs = host_segs;
+  memcpy(seg_first, host_seg_first.data(), (n_groups + 1) * 8);
+  return NTS_OK;
+}

@@ -1118,6 +1118,17 @@ extern "C" int nts_cigar_pad(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cig
   return cigar_pad_run(ctx, cigar, n_cigar, chains, n_chains, at, n_groups, padded, pad_first, site_first, site_pos, site_w);
 }
 
+extern "C" int nts_cigar_depth(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains,
+                               const nts_cig_pad_at* at, uint64_t n_groups, nts_cig_depth_seg** segs, uint64_t* seg_first)
+{
+  if (!ctx) return NTS_EINVAL;
+  if (n_cigar > 0xFFFFFFFFull || n_chains > 0xFFFFFFFFull || n_groups > 0xFFFFFFFFull) // (before any array is read)
+    return fail(ctx, NTS_ERANGE, "nts_cigar_depth: 2^32 entries, chains or groups or more");
+  if ((n_cigar && !cigar) || (n_chains && (!chains || !at)) || !segs || !seg_first) return fail(ctx, NTS_EINVAL, "nts_cigar_depth: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return cigar_depth_run(ctx, cigar, n_cigar, chains, n_chains, at, n_groups, segs, seg_first);
+}
+
 extern "C" int nts_graph_budget(nts_ctx* ctx, uint64_t bytes)
 {
   if (!ctx) return NTS_EINVAL;

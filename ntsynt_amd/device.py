@@ -76,6 +76,8 @@ CIG_B_BACKWARDS = 1
 # nts_cig_pad_at: what Context.cigar_pad takes per chain; CIG_PAD: the code of the entries it adds (BAM's P)
 CIG_PAD_AT_DTYPE = np.dtype([("group", "<u4"), ("reserved", "<u4"), ("t0", "<u8")])
 CIG_PAD = 6
+# nts_cig_depth_seg: what Context.cigar_depth returns, one per segment of constant (aligned, match, gap)
+CIG_DEPTH_SEG_DTYPE = np.dtype([("start", "<u8"), ("end", "<u8"), ("group", "<u4"), ("aligned", "<u4"), ("match", "<u4"), ("gap", "<u4")])
 # nts_lift_query / nts_lift_hit: what Context.cigar_lift takes and returns, one per query
 LIFT_QUERY_DTYPE = np.dtype([("chain", "<u4"), ("side", "<u4"), ("pos", "<u8")])
 LIFT_HIT_DTYPE = np.dtype([("pos", "<u8"), ("entry", "<u8"), ("off", "<u8"), ("code", "<u4"), ("reserved", "<u4")])
@@ -510,6 +512,29 @@ class Context:
         n_sites = int(site_first[-1])
         return (self._take(p_out, int(pad_first[-1]), np.dtype("<u8")), pad_first, site_first, self._take(p_pos, n_sites, np.dtype("<u8")),
                 self._take(p_w, n_sites, np.dtype("<u8")))
+
+    def cigar_depth(self, cigar, chains, at, n_groups=None):
+        """per-base depth and identity over a reference-anchored group of chains (nts_cigar_depth).  cigar, chains, at and n_groups as
+        for cigar_pad, but the chains need not be cores, the entries need not be maximal runs and chains of a group may overlap.
+        Returns (segs, seg_first): a CIG_DEPTH_SEG_DTYPE array of the maximal runs [start, end) of reference bases of one group with
+        aligned > 0 and one (aligned, match, gap) -- the chains covering a base, those with an = there, those with a D there --
+        ascending by (group, start), and seg_first [n_groups + 1] uint64: group g's are segs[seg_first[g]:seg_first[g + 1]].  Reads no
+        genome.  Exact and deterministic."""
+        cg = np.ascontiguousarray(cigar, dtype=np.uint64)
+        ch = np.ascontiguousarray(chains, dtype=CHAIN_DTYPE)
+        where = np.ascontiguousarray(at, dtype=CIG_PAD_AT_DTYPE)
+        if cg.ndim != 1 or ch.ndim != 1 or where.shape != ch.shape:
+            raise ValueError("cigar_depth: a list of entries, a list of chain records and one {group, t0} per chain")
+        assert CHAIN_DTYPE.itemsize == ctypes.sizeof(_lib.CigChain) and CIG_PAD_AT_DTYPE.itemsize == ctypes.sizeof(_lib.CigPadAt)
+        assert CIG_DEPTH_SEG_DTYPE.itemsize == ctypes.sizeof(_lib.CigDepthSeg)
+        if n_groups is None:
+            n_groups = int(where["group"][-1]) + 1 if where.size else 0
+        seg_first = np.zeros(int(n_groups) + 1, dtype=np.uint64)
+        p_segs = c_vp()
+        self.check(self.lib.nts_cigar_depth(self.h, cg.ctypes.data if cg.size else None, cg.size, ch.ctypes.data if ch.size else None, ch.size,
+                                            where.ctypes.data if where.size else None, int(n_groups), ctypes.byref(p_segs), seg_first.ctypes.data),
+                   "nts_cigar_depth")
+        return self._take(p_segs, int(seg_first[-1]), CIG_DEPTH_SEG_DTYPE), seg_first
 
     def cigar_rows(self, cigar, chains, spans, genome_a, genome_b, padded=False):
         """the aligned rows of the chains' CIGARs, the sequence lines of a MAF block (nts_cigar_rows).  cigar, chains, spans and the
