@@ -1139,6 +1139,49 @@ typedef struct
 int nts_cigar_depth(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains, const nts_cig_pad_at* at,
                     uint64_t n_groups, nts_cig_depth_seg** segs, uint64_t* seg_first);
 
+/* ---- variant sites over a star alignment: `--block-variant-sites` --------------------------------------------------------------------
+ * nts_cigar_var_bases: nts_cigar_rows' arguments, checks and refusals (entries of code 6 are refused).  With nts_cigar_rows' rows, the
+ *   REF bytes of chain c are the bytes of row A at the columns of its X and D entries, in column order, its ALT bytes those of row B at
+ *   the columns of its X and I entries: upper case ACGT, N for a code that is no base, B complemented with NTS_CIG_B_BACKWARDS.
+ *   Out: *ref and *alt (release with nts_free; NULL for an empty buffer), the chains' bytes one behind the other in chain order; chain
+ *   c's are [ref_first[c], ref_first[c + 1]) and [alt_first[c], alt_first[c + 1]): n_chains + 1 host entries each.  Either buffer at
+ *   2^32 bytes or more: NTS_ERANGE.  A refused call returns no buffer and writes to no caller array.  One exclusive scan over the
+ *   entries (A bases, B bases, events, ref bytes, alt bytes), nts_cigar_lift's check and one lane per chain for either first (timer
+ *   "cigar_var_bases_scan"); one lane per aligned 4-byte word of either buffer: an upper-bound search over that buffer's byte prefix,
+ *   four bytes through nts_cigar_rows' base fetch, one dword store (timer "cigar_var_bases_emit"; not launched where no chain has an X,
+ *   D or I entry).
+ * nts_cigar_alleles: cigar, chains (they TILE the entries and are CORES) and at[c] = {group, t0} as for nts_cigar_pad; alt, n_alt: the
+ *   alt bytes of nts_cigar_var_bases over ALL chains in chain order (compared as opaque bytes).  An EVENT of chain c: every column of
+ *   an X entry at reference base p: (pos p, kind NTS_OP_SUB, len 1, one alt byte); every D entry over [p, p + L): (p, NTS_OP_DEL, L, no
+ *   alt byte); every I entry in the slot in front of base p: (p, NTS_OP_INS, L, its L alt bytes).  Two neighbouring D or two
+ *   neighbouring I entries of one chain are two events (a precondition, as for nts_cigar_pad, that they do not occur; not checked).
+ *   Events of equal (group, pos, kind, len, alt bytes) are one ALLELE; its CARRIERS are their chains, its LEADER the event of the
+ *   smallest carrier.  Out: *alleles (release with nts_free; NULL when there is none) ascending by (group, pos, kind, len for DEL and
+ *   INS / alt byte for SNV, smallest carrier), group g's being [allele_first[g], allele_first[g + 1]) (n_groups + 1 host entries);
+ *   *carriers (nts_free), *n_carriers of them = the events: allele r's are carriers[carrier_first, carrier_first + n_carriers),
+ *   ascending; ref_off and alt_off: the leader's offsets into the buffers of nts_cigar_var_bases (a prefix of X + D, of X + I lengths;
+ *   ref_off = 0 for INS, alt_off = 0 for DEL).  No genome is read.  Refusals: nts_cigar_pad's, before any launch and behind the first
+ *   scan; behind the scan also NTS_EINVAL "alt holds N bytes, the X and I entries of the chains have M" and NTS_ERANGE for 2^32
+ *   events or more.  A refused call returns no buffer and writes to no caller array.  One scan as above; one lane per event stores two
+ *   key words, two stable radix sorts (timer "cigar_alleles_events"); one lane per sorted event finds its leader -- for an INS by
+ *   comparing bytes with the events in front of it in its run of equal (group, pos, len): the one non-linear step, an INS run of r
+ *   events costs up to r (r - 1) / 2 comparisons of up to len bytes; exact, no hash --, one stable radix sort by leader, one scan of
+ *   the heads, one lane per event to emit (timer "cigar_alleles_emit").  On the context's stream, in its workspace; no atomic, no launch
+ *   per chain, group, event or allele, no floating point: the same input gives the same bytes.
+ *   docs/design/04_32_block_variant_sites.md; csrc/nts_cigar.inc; ntsynt_amd/assess.py block_variant_sites. */
+int nts_cigar_var_bases(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains, const nts_genome* a,
+                        const nts_genome* b, const nts_cig_span* spans, uint8_t** ref, uint64_t* ref_first, uint8_t** alt, uint64_t* alt_first);
+typedef struct
+{
+  uint64_t pos, len;                     /* reference base (for INS: the slot in front of it) and length: 1 for NTS_OP_SUB */
+  uint64_t ref_off, alt_off;             /* the leader's bytes in nts_cigar_var_bases' buffers */
+  uint64_t carrier_first;                /* its carriers: carriers[carrier_first, carrier_first + n_carriers) */
+  uint32_t group, kind, n_carriers, reserved;
+} nts_cig_allele;
+int nts_cigar_alleles(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains, const nts_cig_pad_at* at,
+                      uint64_t n_groups, const uint8_t* alt, uint64_t n_alt, nts_cig_allele** alleles, uint64_t* allele_first, uint32_t** carriers,
+                      uint64_t* n_carriers);
+
 /* ---- C1-C5: minimizer graph -> collinear chains -----------------------------------------------------
  * replaces ntjoin_utils.read_minimizers' duplicate removal, filter_minimizers and build_graph
  * (call sites bin/ntsynt_synteny.py:607-612, 483, 539) and the path walk of Ntjoin.find_paths

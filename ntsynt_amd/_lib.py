@@ -102,6 +102,12 @@ class CigDepthSeg(ctypes.Structure):
     _fields_ = [("start", u64), ("end", u64), ("group", u32), ("aligned", u32), ("match", u32), ("gap", u32)]
 
 
+class CigAllele(ctypes.Structure):
+    "nts_cig_allele: one allele of a group with where its bytes and its carriers lie (nts_cigar_alleles)"
+    _fields_ = [("pos", u64), ("len", u64), ("ref_off", u64), ("alt_off", u64), ("carrier_first", u64), ("group", u32), ("kind", u32), ("n_carriers", u32),
+                ("reserved", u32)]
+
+
 class LiftQuery(ctypes.Structure):
     "nts_lift_query: an offset on one side of a chain (nts_cigar_lift)"
     _fields_ = [("chain", u32), ("side", u32), ("pos", u64)]
@@ -324,6 +330,9 @@ SYMBOLS = [
     ("nts_cigar_rows_padded", ctypes.c_int, [c_vp, c_vp, u64, c_vp, u64, c_vp, c_vp, c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
     ("nts_cigar_pad", ctypes.c_int, [c_vp, c_vp, u64, c_vp, u64, c_vp, u64, ctypes.POINTER(c_vp), c_vp, c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp)]),
     ("nts_cigar_depth", ctypes.c_int, [c_vp, c_vp, u64, c_vp, u64, c_vp, u64, ctypes.POINTER(c_vp), c_vp]),
+    ("nts_cigar_var_bases", ctypes.c_int, [c_vp, c_vp, u64, c_vp, u64, c_vp, c_vp, c_vp, ctypes.POINTER(c_vp), c_vp, ctypes.POINTER(c_vp), c_vp]),
+    ("nts_cigar_alleles", ctypes.c_int, [c_vp, c_vp, u64, c_vp, u64, c_vp, u64, c_vp, u64, ctypes.POINTER(c_vp), c_vp, ctypes.POINTER(c_vp),
+                                         ctypes.POINTER(u64)]),
     ("nts_genome_valid_bases", ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(Interval), u64, c_vp]),
     ("nts_minhash_pairs", ctypes.c_int, [c_vp, u32, c_vp, c_vp, u64, c_vp, c_vp, u64, c_vp, c_vp]),
     ("nts_graph_build", ctypes.c_int, [c_vp, u32, ctypes.POINTER(MxList), ctypes.POINTER(Graph)]),

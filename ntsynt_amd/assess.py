@@ -26,6 +26,9 @@ Two things, both over `<prefix>.synteny_blocks.tsv`:
 * block conservation (`ntSynt --block-conservation`, `ntsynt_block_stats --conservation-out --conservation-stats-out`): per block the runs
   of bases of its first line with one (aligned, match, gap) over the star pairs' CIGARs, made on the GPU (nts_cigar_depth), and the
   covered, core and conserved bases per block; docs/design/04_31_block_conservation.md.
+* block variant sites (`ntSynt --block-variant-sites`, `ntsynt_block_stats --variant-sites-out`): per block the reference positions at
+  which the other genomes differ, one line per allele with its carriers and one genotype character per row, the bases and the allele
+  table made on the GPU (nts_cigar_var_bases, nts_cigar_alleles); docs/design/04_32_block_variant_sites.md.
 * block chain file (`ntSynt --block-chain`, `ntsynt_block_stats --chain-out`): one UCSC liftover chain per block and pair, the chains of the
   block alignments joined per pair, blocks and data lines made on the GPU (nts_cigar_chain_blocks); docs/design/04_28_block_chain.md.
 * block alignments (`ntSynt --block-paf`, `ntsynt_block_stats --paf-out`): one PAF record with a cg:Z: CIGAR per aligned chain of every
@@ -1487,6 +1490,194 @@ def conservation_table(groups, segs, seg_first, k, rate, band, max_len, max_edit
     return "\n".join(lines) + "\n"
 
 
+# ---- block variant sites: one allele table per block over the star alignment (docs/design/04_32_block_variant_sites.md) ----
+
+VARIANT_SITES_COLUMNS = ("contig", "pos", "block_id", "genome", "type", "length", "ref", "alt", "rows", "aligned", "carriers", "genotypes")
+VARIANT_SITE_TYPES = {1: "snv", 2: "del", 3: "ins"}
+
+
+def alleles_host(entries, records, at, alt):
+    """nts_cigar_alleles' alleles of ONE group on the host.  entries, records, at: that group's chains (the records' `first` index
+    `entries`; the chains tile them); alt: their alt bytes, chain after chain (the X and I entries).  Events are made per entry with
+    np.repeat, the insertions' bytes are gathered into one zero-padded matrix and numbered by np.unique over its rows, the alleles are
+    np.unique over (pos, kind, len or alt byte, byte number) put into the device's order by their first event.  Returns (pos, kind, len,
+    ref_off, alt_off, n_carriers, carriers): int64 arrays, one entry per allele but carriers, which holds every allele's chains one
+    behind the other (indices into records); the offsets count inside this group's bytes.  Array operations over entries, events and
+    bytes; the spot check of block_variant_sites and the baseline of scripts/block_variant_sites_measure.py.  Pure."""
+    import numpy as np
+    entries = np.ascontiguousarray(entries, dtype=np.uint64)
+    alt = np.ascontiguousarray(alt, dtype=np.uint8)
+    code, size = (entries & np.uint64(15)).astype(np.int64), (entries >> np.uint64(4)).astype(np.int64)
+    n_cig, t0 = records["n_cig"].astype(np.int64), at["t0"].astype(np.int64)
+    empty = np.zeros(0, dtype=np.int64)
+    is_x, is_d, is_i = code == 8, code == 2, code == 1
+    count = np.where(is_x, size, (is_d | is_i).astype(np.int64))
+    n_ev = int(count.sum())
+    if n_ev == 0:
+        return empty, empty, empty, empty, empty, empty, empty
+    chain_of = np.repeat(np.arange(n_cig.size), n_cig)        # (the chains tile the entries)
+    first_of = np.concatenate(([0], np.cumsum(n_cig)))[chain_of]
+    before = [np.concatenate(([0], np.cumsum(np.where(which, size, 0)))) for which in (~is_i, is_x | is_d, is_x | is_i)]   # A bases, ref bytes, alt bytes
+    begin = t0[chain_of] + before[0][:-1] - before[0][first_of]
+    ev_entry = np.repeat(np.arange(entries.size), count)
+    off = np.where(is_x[ev_entry], np.arange(n_ev) - np.concatenate(([0], np.cumsum(count)))[ev_entry], 0)
+    pos, kind = begin[ev_entry] + off, np.select([is_x[ev_entry], is_d[ev_entry]], [1, 2], 3)
+    length = np.where(kind == 1, 1, size[ev_entry])
+    ref_off = np.where(kind == 3, 0, before[1][ev_entry] + off)
+    alt_off = np.where(kind == 2, 0, before[2][ev_entry] + off)
+    what = np.zeros(n_ev, dtype=np.int64)                    # what tells events of one (pos, kind, len) apart: the alt byte, or the number of the bytes
+    what[kind == 1] = alt[alt_off[kind == 1]]
+    ins = np.flatnonzero(kind == 3)
+    if ins.size:
+        width = int(length[ins].max())
+        column = np.arange(width)[None, :]
+        padded = np.concatenate((alt, np.zeros(width, dtype=np.uint8)))
+        text = np.where(column < length[ins][:, None], padded[np.minimum(alt_off[ins][:, None] + column, padded.size - 1)], 0)
+        what[ins] = np.unique(text, axis=0, return_inverse=True)[1].reshape(-1)
+    keys = np.stack((pos, kind, length, what), axis=1)
+    _, lead, allele_of = np.unique(keys, axis=0, return_index=True, return_inverse=True)
+    allele_of = allele_of.reshape(-1)
+    by_lead = np.where(kind[lead] == 1, what[lead], 0)       # (an SNV sorts by its byte, the others by their smallest carrier)
+    order = np.lexsort((lead, by_lead, length[lead], kind[lead], pos[lead]))
+    rank = np.empty(order.size, dtype=np.int64)
+    rank[order] = np.arange(order.size)
+    lead = lead[order]
+    events = np.argsort(rank[allele_of], kind="stable")
+    return (pos[lead], kind[lead], length[lead], ref_off[lead], alt_off[lead], np.bincount(rank[allele_of], minlength=order.size).astype(np.int64),
+            chain_of[ev_entry][events])
+
+
+def variant_site_genotypes(alleles, carriers, chain_row, chain_t0, chain_t1, rows, chain_group):
+    """Per allele one character per row 1 .. rows[group]: `1` a chain of that row carries the allele, `0` a chain of that row is aligned
+    at it and does not carry it, `.` otherwise.  Aligned at: t0 <= pos < t1 for an SNV or DEL, t0 < pos < t1 for an INS.  alleles,
+    carriers: nts_cigar_alleles'; chain_group, chain_row, chain_t0, chain_t1: per chain, the chains ascending by (group, row, t0) and
+    those of one row not overlapping (as _star_cores orders and checks them); rows[g]: the rows of group g besides the reference.  ONE
+    np.searchsorted over the keys (group, row, t0) for all alleles and rows.  Returns a list of strings.  Pure."""
+    import numpy as np
+    rows = np.asarray(rows, dtype=np.int64)
+    chain_group, chain_row = np.asarray(chain_group, dtype=np.int64), np.asarray(chain_row, dtype=np.int64)
+    chain_t0, chain_t1 = np.asarray(chain_t0, dtype=np.int64), np.asarray(chain_t1, dtype=np.int64)
+    if alleles.size == 0:
+        return []
+    group, pos, kind = alleles["group"].astype(np.int64), alleles["pos"].astype(np.int64), alleles["kind"].astype(np.int64)
+    most = int(rows.max()) if rows.size else 0
+    big = int(max(chain_t1.max() if chain_t1.size else 0, pos.max())) + 2
+    if (int(rows.size) * (most + 1) + most + 1) * big >= 1 << 62:
+        raise ValueError("variant_site_genotypes: the keys (group, row, t0) leave 62 bits")
+    keys = (chain_group * (most + 1) + chain_row) * big + chain_t0
+    if np.any(keys[1:] < keys[:-1]):
+        raise ValueError("variant_site_genotypes: the chains do not ascend by (group, row, t0)")
+    row = np.arange(1, most + 1)[None, :]
+    slot = (group[:, None] * (most + 1) + row)                 # [alleles, rows]
+    at = np.searchsorted(keys, slot * big + pos[:, None], side="right") - 1
+    hit = np.clip(at, 0, max(keys.size - 1, 0))
+    found = (at >= 0) & (keys.size > 0)
+    same = found & ((chain_group[hit] * (most + 1) + chain_row[hit]) == slot) if keys.size else found
+    inside = same & (pos[:, None] < chain_t1[hit]) & ((kind[:, None] != 3) | (chain_t0[hit] < pos[:, None])) if keys.size else same
+    out = np.where(inside, ord("0"), ord(".")).astype(np.uint8)
+    out[row > rows[group][:, None]] = ord(" ")                # (beyond the group's rows: cut off below)
+    n_car = alleles["n_carriers"].astype(np.int64)
+    allele_of = np.repeat(np.arange(alleles.size), n_car)
+    mine = np.asarray(carriers, dtype=np.int64)[(alleles["carrier_first"].astype(np.int64)[allele_of] + np.arange(allele_of.size) -
+                                                 np.repeat(np.cumsum(n_car) - n_car, n_car))] if allele_of.size else np.zeros(0, dtype=np.int64)
+    out[allele_of, chain_row[mine] - 1] = ord("1")
+    return [line.tobytes().decode()[:r] for line, r in zip(out, rows[group].tolist())]
+
+
+def variant_sites_table(groups, alleles, ref, alt, genotypes, k, rate, band, max_len, max_edits=0, ends=None):
+    """The text of `<prefix>.block_variant_sites.tsv`: a header, one line per allele -- VARIANT_SITES_COLUMNS: the reference contig and
+    0-based position, the block, the reference genome, snv / del / ins, the length, the reference's and the allele's letters (`-` for
+    none), the block's rows, how many of them are aligned at the allele (the characters of `genotypes` that are no `.`), its carriers and
+    the genotypes -- then the `#` line with the parameters.  groups: block_variant_sites'; ref, alt: the byte buffers the alleles' offsets
+    count in.  Columns are made as arrays and joined once per line.  Pure."""
+    import numpy as np
+    ref_text, alt_text = np.asarray(ref, dtype=np.uint8).tobytes().decode(), np.asarray(alt, dtype=np.uint8).tobytes().decode()
+    group, kind, length = alleles["group"].astype(np.int64), alleles["kind"].astype(np.int64).tolist(), alleles["len"].astype(np.int64).tolist()
+    of_group = [np.array([str(g[f]) for g in groups], dtype=object)[group] if len(groups) else np.zeros(0, dtype=object) for f in (2, 0, 1, 5)]
+    ref_of = [ref_text[o:o + n] if t != 3 else "-" for o, n, t in zip(alleles["ref_off"].tolist(), length, kind)]
+    alt_of = [alt_text[o:o + n] if t != 2 else "-" for o, n, t in zip(alleles["alt_off"].tolist(), length, kind)]
+    columns = [of_group[0], alleles["pos"].astype(np.int64), of_group[1], of_group[2], [VARIANT_SITE_TYPES[t] for t in kind], length, ref_of, alt_of,
+               of_group[3], [len(g) - g.count(".") for g in genotypes], alleles["n_carriers"].astype(np.int64), genotypes]
+    lines = ["\t".join(line) for line in zip(*(np.asarray(c, dtype=object).astype(str).tolist() for c in columns))]
+    return "\n".join(["\t".join(VARIANT_SITES_COLUMNS)] + lines + [_conservation_parameters(k, rate, band, max_len, max_edits, ends)]) + "\n"
+
+
+def block_variant_sites(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_RATE, band=IDENTITY_BAND, max_len=IDENTITY_MAX_LEN, max_edits=0, ends=None):
+    """Per synteny block the positions of its first line at which the other genomes differ, with which allele, and which of them share
+    it (docs/design/04_32_block_variant_sites.md): the core chains of the star pairs (_star_cores) give, per pair of genomes, ONE
+    nts_cigar_var_bases -- the bases at the X, D and I columns --, whose bytes are scattered into chain order, and ONE
+    nts_cigar_alleles over all chains.  Genomes given as callables are loaded a second time for the bases, each query one at a time
+    beside the reference's genome.  The first group's alleles and carriers are recomputed on the host (alleles_host) and compared:
+    RuntimeError.  Returns (groups, alleles, ref, alt, genotypes): per block, in block_identity.tsv's order, (block_id, genome, contig,
+    start, end, rows) of its first line; the CIG_ALLELE_DTYPE alleles in the device's order, the two byte buffers their offsets count in
+    and variant_site_genotypes' strings: what variant_sites_table takes."""
+    import numpy as np
+    from .device import CIG_ALLELE_DTYPE, CIG_SPAN_DTYPE
+    n_groups, held, entries, records, at = _star_cores(ctx, genomes_by_name, blocks, k, rate, band, max_len, max_edits, ends)
+    groups = [(b, blocks[lines[0]].genome, blocks[lines[0]].contig, blocks[lines[0]].start, blocks[lines[0]].end, len(lines) - 1)
+              for b, lines in _block_order(blocks)]
+    none = np.zeros(0, dtype=np.uint8)
+    if not held:
+        return groups, np.zeros(0, dtype=CIG_ALLELE_DTYPE), none, none, []
+    code, size = (entries & np.uint64(15)).astype(np.int64), (entries >> np.uint64(4)).astype(np.int64)
+    cut = np.concatenate((records["first"].astype(np.int64), [entries.size]))
+    sums = [np.concatenate(([0], np.cumsum(np.where(np.isin(code, which), size, 0))))[cut] for which in ((8, 2), (8, 1))]
+    ref_first, alt_first = sums                              # where every chain's bytes begin in chain order: prefixes of X + D and of X + I lengths
+    ref, alt = np.zeros(int(ref_first[-1]), dtype=np.uint8), np.zeros(int(alt_first[-1]), dtype=np.uint8)
+    by_pair = {}
+    for j, h in enumerate(held):
+        by_pair.setdefault((blocks[h[10]].genome, blocks[h[11]].genome), []).append(j)
+    loaded = {}
+
+    def genome(name):
+        if name not in loaded:
+            g = genomes_by_name[name]
+            loaded[name] = (g(), True) if callable(g) else (g, False)
+        return loaded[name][0]
+
+    def release(name):
+        g, mine = loaded.pop(name)
+        if mine:
+            g.free()
+    try:
+        for (name_a, name_b), members in by_pair.items():
+            for name in [n for n in loaded if n not in (name_a, name_b)]:
+                release(name)
+            sub = records[members].copy()
+            sub["first"] = np.concatenate(([0], np.cumsum(sub["n_cig"][:-1].astype(np.int64))))
+            spans = np.zeros(len(members), dtype=CIG_SPAN_DTYPE)
+            spans["pos_a"], spans["pos_b"] = [held[j][2] for j in members], [held[j][6] for j in members]
+            spans["rec_a"], spans["rec_b"], spans["flags"] = [held[j][7] for j in members], [held[j][8] for j in members], [held[j][9] for j in members]
+            mine = np.concatenate([held[j][3] for j in members]).astype(np.uint64)
+            got = ctx.cigar_var_bases(mine, sub, spans, genome(name_a), genome(name_b))
+            for whole, first, (part, part_first) in ((ref, ref_first, got[:2]), (alt, alt_first, got[2:])):
+                part_first = part_first.astype(np.int64)
+                sizes = part_first[1:] - part_first[:-1]
+                if not np.array_equal(sizes, (first[1:] - first[:-1])[members]):
+                    raise RuntimeError(f"the device's bytes per chain of {name_a} and {name_b} are not the X, D and I lengths of the chains")
+                whole[np.repeat(first[:-1][members] - part_first[:-1], sizes) + np.arange(part.size)] = part     # (the scatter into chain order)
+    finally:
+        for name in list(loaded):
+            release(name)
+    alleles, allele_first, carriers = ctx.cigar_alleles(entries, records, at, alt, n_groups)
+    g0 = int(at["group"][0])                                  # the spot check: the first group that has chains
+    mine = np.flatnonzero(at["group"] == g0)
+    sub = records[mine].copy()
+    sub["first"] -= records["first"][mine[0]]
+    lo, hi = int(cut[mine[0]]), int(cut[mine[-1] + 1])
+    host = alleles_host(entries[lo:hi], sub, at[mine], alt[int(alt_first[mine[0]]):int(alt_first[mine[-1] + 1])])
+    got = alleles[int(allele_first[g0]):int(allele_first[g0 + 1])]
+    want = list(host[:3]) + [np.where(host[1] == 3, 0, host[3] + ref_first[mine[0]]), np.where(host[1] == 2, 0, host[4] + alt_first[mine[0]]), host[5]]
+    got_carriers = carriers[int(got["carrier_first"][0]):int(got["carrier_first"][-1]) + int(got["n_carriers"][-1])] if got.size else carriers[:0]
+    if got.size != host[0].size or any(not np.array_equal(got[f].astype(np.int64), w) for f, w in zip(("pos", "kind", "len", "ref_off", "alt_off", "n_carriers"), want)) \
+            or np.any(got["group"] != g0) or not np.array_equal(got_carriers.astype(np.int64), host[6] + mine[0]):
+        raise RuntimeError(f"block {groups[g0][0]}: the device's {got.size} alleles differ from the host's {host[0].size}")
+    t0 = at["t0"].astype(np.int64)
+    genotypes = variant_site_genotypes(alleles, carriers, [h[1] for h in held], t0, t0 + records["len_a"].astype(np.int64), [g[5] for g in groups],
+                                       at["group"].astype(np.int64))
+    return groups, alleles, ref, alt, genotypes
+
+
 LIFT_COLUMNS = ("genome", "contig", "start", "end", "name", "block_id", "to_genome", "to_contig", "to_start", "to_end", "orientation", "ch", "src_start",
                 "src_end", "status")
 LIFT_IDENTITY_COLUMNS = LIFT_COLUMNS[:14] + ("matches", "mismatches", "src_gap_bases", "to_gap_bases", "src_gaps", "to_gaps", "columns", "identity", "status")
@@ -2204,6 +2395,9 @@ def main(argv=None):
                    "block the runs of bases of its first line with one aligned / match / mismatch / gap count over the star alignment of "
                    "--multi-maf-out; made on the GPU); it takes the parameters of --paf-out; a pass of its own")
     p.add_argument("--conservation-stats-out", help="with --conservation-out: file for the per-block table (covered, core and conserved bases, histograms)")
+    p.add_argument("--variant-sites-out", help="with --fastas: file for the block variant sites (per synteny block one line per allele over the star "
+                   "alignment of --multi-maf-out: position on the block's first line, snv / del / ins, the letters, the carriers and one genotype "
+                   "character per row; bases and allele table made on the GPU); it takes the parameters of --paf-out; a pass of its own")
     p.add_argument("--lift-bed", help="with --fastas, --lift-genome and --lift-out: a BED file of intervals of one genome that are mapped through the block "
                    "alignments into the other genomes (GPU); it takes the parameters of --paf-out")
     p.add_argument("--lift-genome", help="the genome the intervals of --lift-bed lie on: a FASTA base name, as in column 2 of the block table")
@@ -2256,6 +2450,12 @@ def main(argv=None):
     if args.conservation_out:
         if not args.fastas:
             p.error("--conservation-out needs the genomes: --fastas")
+        message = check_identity_parameters(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits)
+        if message:
+            p.error(message)
+    if args.variant_sites_out:
+        if not args.fastas:
+            p.error("--variant-sites-out needs the genomes: --fastas")
         message = check_identity_parameters(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits)
         if message:
             p.error(message)
@@ -2418,6 +2618,11 @@ def main(argv=None):
             for path, table in ((args.conservation_out, conservation_bed), (args.conservation_stats_out, conservation_table)):
                 with open(path, "w", encoding="utf-8") as fh:
                     fh.write(table(*conserved, *id_args, max_edits=args.identity_max_edits, ends=c_ends))
+        if args.variant_sites_out:                            # (a pass of its own)
+            v_ends = (args.ends_max_len, args.ends_max_edits, args.ends_penalty) if args.ends_out else None
+            sites = block_variant_sites(ctx, loaders, read_blocks(args.tsv), *id_args, max_edits=args.identity_max_edits, ends=v_ends)
+            with open(args.variant_sites_out, "w", encoding="utf-8") as fh:
+                fh.write(variant_sites_table(*sites, *id_args, max_edits=args.identity_max_edits, ends=v_ends))
     finally:
         ctx.close()
     if args.divergence_out:

@@ -1866,27 +1866,30 @@ __global__ __launch_bounds__(256) void k_cig_rows(const uint64_t* __restrict__ c
   out_b[w] = word_b;
 }
 
+// chain c's span, behind the checks of its record: nts_cigar_text's rules; what nts_cigar_rows and nts_cigar_var_bases refuse alike
+template <class Who>
+int cig_rows_place(nts_ctx* ctx, const nts_cig_chain& ch, const nts_cig_span& sp, const nts_genome* a, const nts_genome* b, Who who, CigTextChain& placed)
+{
+  if (sp.flags & ~NTS_CIG_B_BACKWARDS) return fail(ctx, NTS_EINVAL, who() + " has unknown flag bits");
+  if (sp.rec_a >= a->n_rec || sp.rec_b >= b->n_rec) return fail(ctx, NTS_EINVAL, who() + " names a record outside its genome");
+  const uint64_t rl_a = a->rec_len[sp.rec_a], rl_b = b->rec_len[sp.rec_b];
+  const bool backwards = (sp.flags & NTS_CIG_B_BACKWARDS) != 0;
+  bool inside = sp.pos_a <= rl_a && ch.len_a <= rl_a - sp.pos_a;
+  if (ch.len_b == 0) inside = inside && sp.pos_b <= rl_b;
+  else if (backwards) inside = inside && sp.pos_b < rl_b && ch.len_b <= sp.pos_b + 1u;
+  else inside = inside && sp.pos_b <= rl_b && ch.len_b <= rl_b - sp.pos_b;
+  if (!inside) return fail(ctx, NTS_EINVAL, who() + ": its span lies outside its record");
+  placed = { ch.first, PAD + a->rec_off[sp.rec_a] + sp.pos_a, PAD + b->rec_off[sp.rec_b] + sp.pos_b, ch.len_a, ch.len_b, sp.flags, 0u };
+  return NTS_OK;
+}
+
 template <bool PADDED>
 int cigar_rows_run(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains, const nts_genome* a,
                    const nts_genome* b, const nts_cig_span* spans, uint8_t** row_a, uint8_t** row_b, uint64_t* row_first)
 {
   const char* const name = PADDED ? "nts_cigar_rows_padded" : "nts_cigar_rows";
   std::vector<CigTextChain> placed(n_chains);
-  auto place = [&](uint64_t c, auto who) -> int { // chain c's span, behind the checks of its record: nts_cigar_text's rules
-    const nts_cig_chain& ch = chains[c];
-    const nts_cig_span& sp = spans[c];
-    if (sp.flags & ~NTS_CIG_B_BACKWARDS) return fail(ctx, NTS_EINVAL, who() + " has unknown flag bits");
-    if (sp.rec_a >= a->n_rec || sp.rec_b >= b->n_rec) return fail(ctx, NTS_EINVAL, who() + " names a record outside its genome");
-    const uint64_t rl_a = a->rec_len[sp.rec_a], rl_b = b->rec_len[sp.rec_b];
-    const bool backwards = (sp.flags & NTS_CIG_B_BACKWARDS) != 0;
-    bool inside = sp.pos_a <= rl_a && ch.len_a <= rl_a - sp.pos_a;
-    if (ch.len_b == 0) inside = inside && sp.pos_b <= rl_b;
-    else if (backwards) inside = inside && sp.pos_b < rl_b && ch.len_b <= sp.pos_b + 1u;
-    else inside = inside && sp.pos_b <= rl_b && ch.len_b <= rl_b - sp.pos_b;
-    if (!inside) return fail(ctx, NTS_EINVAL, who() + ": its span lies outside its record");
-    placed[c] = { ch.first, PAD + a->rec_off[sp.rec_a] + sp.pos_a, PAD + b->rec_off[sp.rec_b] + sp.pos_b, ch.len_a, ch.len_b, sp.flags, 0u };
-    return NTS_OK;
-  };
+  auto place = [&](uint64_t c, auto who) -> int { return cig_rows_place(ctx, chains[c], spans[c], a, b, who, placed[c]); };
   if (const int rc = cig_chains_check(ctx, name, CIG_TEXT_MAX_BASES_LOG2, true, chains, n_chains, n_cigar, place)) return rc;
   if (n_cigar == 0) { // (nothing is launched: every row is empty)
     *row_a = nullptr;
@@ -2577,5 +2580,474 @@ int cigar_depth_run(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const
   }
   *segs = host_segs;
   memcpy(seg_first, host_seg_first.data(), (n_groups + 1) * 8);
+  return NTS_OK;
+}
+
+// ---- variant sites over a star alignment: the bases at the X, D and I columns, and one allele table per group ----
+// ---- (nts_cigar_var_bases, nts_cigar_alleles; ntsynt_amd/assess.py block_variant_sites) ----
+// docs/design/04_32_block_variant_sites.md.  Both calls stage ONE functor, CigVarOf: (A bases, B bases, events, ref bytes, alt bytes)
+// per entry -- an X of length L has L events, L ref bytes and L alt bytes; a D one event and L ref bytes; an I one event and L alt bytes.
+// nts_cigar_var_bases (entries, records, spans, both genomes; nts_cigar_rows' checks): the REF bytes of a chain are row A at the columns
+// of its X and D entries, the ALT bytes row B at those of its X and I entries.
+//   1  the stage; k_cig_rows_firsts reads the ref and the alt prefix at every chain's first entry (timer "cigar_var_bases_scan").
+//   2  k_cigv_bases: one lane per aligned 4-byte word of EITHER buffer (the ref words first); an upper-bound search over that buffer's
+//      byte prefix finds the entry of the word's first byte, the lane walks on over the entries the word touches (entries without a
+//      byte on its side are stepped over), composes four bytes through cig_rows_base and stores one dword (timer "cigar_var_bases_emit").
+// nts_cigar_alleles (entries, records, {group, t0}, the alt bytes; nts_cigar_pad's checks; no genome): an EVENT is an X column (SNV), a D
+// entry (DEL) or an I entry (INS); events with equal (group, pos, kind, len, alt bytes) are one ALLELE, its CARRIERS their chains.
+//   1  the stage.  k_cigv_events: one lane per event -- its entry by an upper-bound search over the event prefix, its chain by one over
+//      the chains' firsts -- stores key1 = group << 32 | pos - R0, key2 = kind << 62 | (the alt byte of an SNV, else len), its chain and
+//      its two byte offsets.  Stable radix sort by key2 (the values: the event indices), key1 gathered in that order, stable radix sort
+//      by key1, key2 gathered in the final order: events ascend by (key1, key2, event), so by chain inside a run (timer
+//      "cigar_alleles_events").
+//   2  k_cigv_leaders: one lane per sorted event; a lower-bound search gives the start of its run of equal (key1, key2); the leader of
+//      an SNV or DEL is the run's start, of an INS the first event of the run with the same `len` alt bytes (cigv_same_bytes: dwords
+//      where both offsets are congruent modulo 4) -- THE ONE NON-LINEAR STEP: an INS run of r events costs up to r (r - 1) / 2
+//      comparisons of up to len bytes.  Stable radix sort of (leader, sorted index) -- it permutes inside runs only, so the sorted keys
+//      stay valid by position --, a head flag per event, ONE exclusive scan, k_cigd_firsts for allele_first, and k_cigv_emit: a head
+//      writes its allele but n_carriers, the last event of an allele n_carriers, every event its chain (timer "cigar_alleles_emit").
+// No atomic, no floating point, no runtime division, no launch per chain, group, event or allele, no host loop over entries or events.
+
+static_assert(sizeof(nts_cig_allele) == 56, "the C ABI's layout");
+static_assert(NTS_OP_SUB == 1u && NTS_OP_DEL == 2u && NTS_OP_INS == 3u, "the kinds fit the two top bits of key2");
+
+constexpr uint64_t CIGV_MOST_BYTES = 0xFFFFFFFFull;        // a buffer of nts_cigar_var_bases, and the events of nts_cigar_alleles, stay below 2^32
+constexpr uint64_t CIGV_LEN = (1ull << 62) - 1u;           // key2's low bits (lengths are below 2^62: cig_chains_check)
+
+using CigVarTuple = rocprim::tuple<uint64_t, uint64_t, uint64_t, uint64_t, uint64_t>; // A bases, B bases, events, ref bytes, alt bytes
+
+struct CigVarOf // element e of the scan's input: what entry e consumes, its events and its bytes in either buffer; nothing behind the last entry
+{
+  using Tuple = CigVarTuple;
+  const uint64_t* cigar;
+  uint64_t n_cigar;
+  __device__ Tuple operator()(uint64_t e) const
+  {
+    if (e >= n_cigar) return Tuple(0, 0, 0, 0, 0);
+    const uint64_t v = cigar[e], code = v & 15u, len = v >> 4;
+    const CigBases ab = cig_bases(v);
+    const bool x = code == CIG_X, d = code == CIG_D, i = code == CIG_I;
+    return Tuple(rocprim::get<0>(ab), rocprim::get<1>(ab), x ? len : (d || i ? 1u : 0u), x || d ? len : 0, x || i ? len : 0); // (each <= A + B bases: no wrap)
+  }
+};
+
+// lane w < words_ref: word w of the ref bytes; lane words_ref + w, w < words_alt: word w of the alt bytes
+__global__ __launch_bounds__(256) void k_cigv_bases(const uint64_t* __restrict__ cigar, uint64_t n_cigar, const CigTextChain* __restrict__ chains,
+                                                    uint64_t n_chains, const uint64_t* __restrict__ PA, const uint64_t* __restrict__ PB,
+                                                    const uint64_t* __restrict__ PR, const uint64_t* __restrict__ PL,
+                                                    const uint8_t* __restrict__ code_a, uint64_t size_a, const uint8_t* __restrict__ code_b,
+                                                    uint64_t size_b, uint32_t* __restrict__ out_ref, uint64_t words_ref, uint32_t* __restrict__ out_alt,
+                                                    uint64_t words_alt)
+{
+  const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (g >= words_ref + words_alt || n_cigar == 0 || n_chains == 0) return;
+  const bool is_alt = g >= words_ref;
+  const uint64_t* __restrict__ P = is_alt ? PL : PR;
+  const uint64_t w = is_alt ? g - words_ref : g, total = P[n_cigar], o = 4u * w;
+  uint64_t e = cig_last_at_or_before(n_cigar, o, [P](uint64_t i) { return P[i]; }); // the entry of the word's first byte (P[0] = 0 <= o)
+  uint64_t p0 = P[e], p1 = P[e + 1u]; // (e < n_cigar)
+  uint64_t chain_of = ~0ull;
+  CigTextChain ch = {};
+  uint64_t in_a = 0, in_b = 0;
+  uint32_t word = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < 4u; ++k) {
+    const uint64_t at = o + k;
+    if (at >= total) break;                // (the padding of the last word stays 0)
+    while (at >= p1 && e + 1u < n_cigar) { // the next entry with a byte on this side: entries without one have p1 = p0
+      ++e;
+      p0 = p1;
+      p1 = P[e + 1u];
+    }
+    if (chain_of != e) {
+      ch = chains[cig_last_at_or_before(n_chains, e, [chains](uint64_t c) { return chains[c].first; })];
+      chain_of = e;
+      const uint64_t f = ch.first <= e ? ch.first : e;
+      in_a = PA[e] - PA[f];
+      in_b = PB[e] - PB[f];
+    }
+    uint32_t byte = '?'; // (never seen: at < total lies inside an entry)
+    if (at >= p0 && at < p1)
+      byte = is_alt ? cig_rows_base(code_b, size_b, ch.at_b, in_b + (at - p0), ch.len_b, (ch.flags & NTS_CIG_B_BACKWARDS) != 0)
+                    : cig_rows_base(code_a, size_a, ch.at_a, in_a + (at - p0), ch.len_a, false);
+    word |= byte << (8u * k);
+  }
+  if (is_alt) out_alt[w] = word; // (w < words_alt)
+  else out_ref[w] = word;
+}
+
+int cigar_var_bases_run(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains, const nts_genome* a,
+                        const nts_genome* b, const nts_cig_span* spans, uint8_t** ref, uint64_t* ref_first, uint8_t** alt, uint64_t* alt_first)
+{
+  const char* const name = "nts_cigar_var_bases";
+  std::vector<CigTextChain> placed(n_chains);
+  auto place = [&](uint64_t c, auto who) -> int { return cig_rows_place(ctx, chains[c], spans[c], a, b, who, placed[c]); };
+  if (const int rc = cig_chains_check(ctx, name, CIG_TEXT_MAX_BASES_LOG2, true, chains, n_chains, n_cigar, place)) return rc;
+  auto nothing = [&] {
+    *ref = nullptr;
+    *alt = nullptr;
+    memset(ref_first, 0, (n_chains + 1) * 8);
+    memset(alt_first, 0, (n_chains + 1) * 8);
+    return NTS_OK;
+  };
+  if (n_cigar == 0) return nothing(); // (nothing is launched)
+  // (its own buffers first: while nothing is queued, a request that fails may still return at once)
+  NTS_WS(d_placed, CigTextChain*, "cigv_placed", n_chains * sizeof(CigTextChain));
+  NTS_WS(d_first, uint64_t*, "cigv_first", 2 * (n_chains + 1) * 8);
+  std::vector<uint64_t> host_first(2 * (n_chains + 1)); // (the caller's arrays are written only when the call succeeds)
+  uint32_t worst = SCRIPT_OK;
+  CigIndex ix; // columns PA, PB, PE (events: not read here), PR (ref bytes), PL (alt bytes)
+  hipError_t e_run;
+  auto firsts = [&] {
+    NTS_LAUNCH(k_cig_rows_firsts, IVL_GRID(n_chains + 1), ix.chains, n_chains, n_cigar, ix.column(3), d_first);
+    NTS_LAUNCH(k_cig_rows_firsts, IVL_GRID(n_chains + 1), ix.chains, n_chains, n_cigar, ix.column(4), d_first + (n_chains + 1));
+  };
+  if (const int rc = cig_index_stage<CigVarOf>(ctx, "cigar_var_bases_scan", cigar, n_cigar, chains, n_chains, 0, &worst, ix, e_run, firsts)) return rc;
+  if (e_run == hipSuccess) e_run = hipGetLastError();
+  if (e_run == hipSuccess) e_run = hipMemcpyAsync(d_placed, placed.data(), n_chains * sizeof(CigTextChain), hipMemcpyHostToDevice, ctx->stream);
+  if (e_run == hipSuccess) e_run = hipMemcpyAsync(host_first.data(), d_first, 2 * (n_chains + 1) * 8, hipMemcpyDeviceToHost, ctx->stream);
+  hipError_t e_sync = hipStreamSynchronize(ctx->stream); // (whatever happened: the caller's arrays were sources of asynchronous copies)
+  HIP_TRY(ctx, e_run);
+  HIP_TRY(ctx, e_sync);
+  if (worst != SCRIPT_OK) return fail(ctx, NTS_EINVAL, std::string(name) + ": the entries of chain " + std::to_string(worst) + " are no CIGAR of its lengths");
+  const uint64_t n_ref = host_first[n_chains], n_alt = host_first[2 * n_chains + 1];
+  if (n_ref > CIGV_MOST_BYTES || n_alt > CIGV_MOST_BYTES) return fail(ctx, NTS_ERANGE, std::string(name) + ": ref or alt bytes of 2^32 or more");
+  if (n_ref + n_alt == 0) return nothing(); // (no chain with an X, D or I entry: no emit launch)
+  const uint64_t words_ref = (n_ref + 3) / 4, words_alt = (n_alt + 3) / 4; // (the device buffers are padded to whole words)
+  // (the stream is idle: the buffers are fetched before their kernel is queued)
+  NTS_WS(d_ref, uint32_t*, "cigv_ref", std::max<uint64_t>(words_ref, 1) * 4);
+  NTS_WS(d_alt, uint32_t*, "cigv_alt", std::max<uint64_t>(words_alt, 1) * 4);
+  uint8_t* host_ref = n_ref ? (uint8_t*)malloc(n_ref) : nullptr;
+  uint8_t* host_alt = n_alt ? (uint8_t*)malloc(n_alt) : nullptr;
+  if ((n_ref && !host_ref) || (n_alt && !host_alt)) {
+    free(host_ref);
+    free(host_alt);
+    return fail(ctx, NTS_ENOMEM, std::string(name) + ": no host memory for the bytes");
+  }
+  {
+    ScopedTimer t(ctx, "cigar_var_bases_emit", true);
+    NTS_LAUNCH(k_cigv_bases, IVL_GRID(words_ref + words_alt), ix.cigar, n_cigar, (const CigTextChain*)d_placed, n_chains, ix.column(0), ix.column(1),
+               ix.column(3), ix.column(4), (const uint8_t*)a->d_code, a->n + 2 * PAD, (const uint8_t*)b->d_code, b->n + 2 * PAD, d_ref, words_ref, d_alt,
+               words_alt);
+  }
+  e_run = hipGetLastError();
+  if (e_run == hipSuccess && n_ref) e_run = hipMemcpyAsync(host_ref, d_ref, n_ref, hipMemcpyDeviceToHost, ctx->stream);
+  if (e_run == hipSuccess && n_alt) e_run = hipMemcpyAsync(host_alt, d_alt, n_alt, hipMemcpyDeviceToHost, ctx->stream);
+  e_sync = hipStreamSynchronize(ctx->stream);
+  if (e_run != hipSuccess || e_sync != hipSuccess) {
+    free(host_ref);
+    free(host_alt);
+  }
+  HIP_TRY(ctx, e_run);
+  HIP_TRY(ctx, e_sync);
+  *ref = host_ref;
+  *alt = host_alt;
+  memcpy(ref_first, host_first.data(), (n_chains + 1) * 8);
+  memcpy(alt_first, host_first.data() + (n_chains + 1), (n_chains + 1) * 8);
+  return NTS_OK;
+}
+
+// lane i < n_ev: event i, in entry order (so in chain order)
+__global__ __launch_bounds__(256) void k_cigv_events(const uint64_t* __restrict__ cigar, uint64_t n_cigar, const CigPadChain* __restrict__ placed,
+                                                     uint64_t n_chains, const uint64_t* __restrict__ PA, const uint64_t* __restrict__ PE,
+                                                     const uint64_t* __restrict__ PR, const uint64_t* __restrict__ PL, const uint8_t* __restrict__ alt,
+                                                     uint64_t n_alt, uint64_t n_ev, uint64_t* __restrict__ key1, uint64_t* __restrict__ key2,
+                                                     uint64_t* __restrict__ roff, uint64_t* __restrict__ aoff, uint32_t* __restrict__ chain)
+{
+  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (i >= n_ev || n_cigar == 0 || n_chains == 0) return;
+  const uint64_t e = cig_last_at_or_before(n_cigar, i, [PE](uint64_t k) { return PE[k]; }); // (PE[0] = 0 <= i < PE[n_cigar]: an entry with an event)
+  const uint64_t c = cig_last_at_or_before(n_chains, e, [placed](uint64_t k) { return placed[k].first; });
+  const CigPadChain ch = placed[c];
+  const uint64_t f = ch.first <= e ? ch.first : e;
+  const uint64_t v = cigar[e], code = v & 15u, len = v >> 4;
+  const uint64_t off = code == CIG_X ? i - PE[e] : 0; // the column of an X entry
+  uint64_t kind = NTS_OP_SUB, what = 0, r = PR[e] + off, l = PL[e] + off;
+  if (code == CIG_X) {
+    what = l < n_alt ? alt[l] : 0;
+  } else if (code == CIG_D) {
+    kind = NTS_OP_DEL;
+    what = len & CIGV_LEN;
+    l = 0;
+  } else { // (CIG_I: = entries have no event)
+    kind = NTS_OP_INS;
+    what = len & CIGV_LEN;
+    r = 0;
+  }
+  key1[i] = ch.key0 + (PA[e] - PA[f]) + off; // (n_ev words each)
+  key2[i] = kind << 62 | what;
+  roff[i] = r;
+  aoff[i] = l;
+  chain[i] = (uint32_t)c;
+}
+
+// lane j < n: dst[j] = src[at[j]] (at[j] < n, re-checked)
+__global__ __launch_bounds__(256) void k_cigv_gather(const uint64_t* __restrict__ src, const uint64_t* __restrict__ at, uint64_t n, uint64_t* __restrict__ dst)
+{
+  const uint64_t j = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (j >= n) return;
+  const uint64_t i = at[j];
+  dst[j] = i < n ? src[i] : 0;
+}
+
+// whether alt[a, a + len) and alt[b, b + len) are equal bytes (both inside n_alt: the caller's check)
+__device__ __forceinline__ bool cigv_same_bytes(const uint8_t* __restrict__ alt, uint64_t a, uint64_t b, uint64_t len)
+{
+  uint64_t k = 0;
+  if (((a ^ b) & 3u) == 0) { // congruent offsets: the aligned middle by dwords (the buffer begins at a multiple of 4)
+    for (; k < len && ((a + k) & 3u) != 0; ++k)
+      if (alt[a + k] != alt[b + k]) return false;
+    for (; k + 4u <= len; k += 4u)
+      if (*(const uint32_t*)(alt + a + k) != *(const uint32_t*)(alt + b + k)) return false;
+  }
+  for (; k < len; ++k)
+    if (alt[a + k] != alt[b + k]) return false;
+  return true;
+}
+
+// the first s < n with (key1[s], key2[s]) >= (k1, k2) over ascending pairs
+__device__ __forceinline__ uint64_t cigv_lower(const uint64_t* __restrict__ key1, const uint64_t* __restrict__ key2, uint64_t n, uint64_t k1, uint64_t k2)
+{
+  uint64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint64_t mid = lo + (hi - lo) / 2u;
+    const uint64_t m1 = key1[mid];
+    if (m1 < k1 || (m1 == k1 && key2[mid] < k2)) lo = mid + 1u;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// lane s < n_ev: the sorted index of the leader of sorted event s
+__global__ __launch_bounds__(256) void k_cigv_leaders(const uint64_t* __restrict__ key1s, const uint64_t* __restrict__ key2s, const uint64_t* __restrict__ perm,
+                                                      const uint64_t* __restrict__ aoff, const uint8_t* __restrict__ alt, uint64_t n_alt, uint64_t n_ev,
+                                                      uint64_t* __restrict__ lead)
+{
+  const uint64_t s = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (s >= n_ev) return;
+  const uint64_t k1 = key1s[s], k2 = key2s[s];
+  uint64_t start = cigv_lower(key1s, key2s, n_ev, k1, k2);
+  if (start > s) start = s; // (ascending pairs: never)
+  uint64_t say = start;
+  if ((k2 >> 62) == NTS_OP_INS) {
+    say = s;
+    const uint64_t len = k2 & CIGV_LEN, i = perm[s], mine = i < n_ev ? aoff[i] : n_alt;
+    if (mine <= n_alt && len <= n_alt - mine) {
+      for (uint64_t j = start; j < s; ++j) { // the divergent loop: up to s - start comparisons of up to len bytes
+        const uint64_t q = perm[j], theirs = q < n_ev ? aoff[q] : n_alt;
+        if (theirs <= n_alt && len <= n_alt - theirs && cigv_same_bytes(alt, theirs, mine, len)) {
+          say = j;
+          break;
+        }
+      }
+    }
+  }
+  lead[s] = say;
+}
+
+// lane t < n_ev: 1 where the event at t of the leader order opens an allele; lane n_ev: 0
+__global__ __launch_bounds__(256) void k_cigv_heads(const uint64_t* __restrict__ leadc, uint64_t n_ev, uint64_t* __restrict__ head)
+{
+  const uint64_t t = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (t > n_ev) return;
+  head[t] = t < n_ev && (t == 0 || leadc[t] != leadc[t - 1u]) ? 1u : 0u; // (n_ev + 1 words)
+}
+
+// lane t < n_ev: the event at t of the leader order; key1s and key2s hold by position (the leader sort permutes inside runs only)
+__global__ __launch_bounds__(256) void k_cigv_emit(const uint64_t* __restrict__ key1s, const uint64_t* __restrict__ key2s, const uint64_t* __restrict__ perm,
+                                                   const uint64_t* __restrict__ order, const uint64_t* __restrict__ leadc, const uint64_t* __restrict__ rank,
+                                                   const uint64_t* __restrict__ roff, const uint64_t* __restrict__ aoff, const uint32_t* __restrict__ chain,
+                                                   const uint64_t* __restrict__ r0, uint64_t n_groups, uint64_t n_ev, nts_cig_allele* __restrict__ alleles,
+                                                   uint64_t n_alleles, uint32_t* __restrict__ carriers)
+{
+  const uint64_t t = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (t >= n_ev) return;
+  const uint64_t s = order[t], i = s < n_ev ? perm[s] : n_ev;
+  carriers[t] = i < n_ev ? chain[i] : 0xFFFFFFFFu; // (n_ev words)
+  const uint64_t r = rank[t + 1u] - 1u;             // the heads up to and with t, less one (rank: n_ev + 1 words; 0 - 1: beyond n_alleles)
+  if (r >= n_alleles || i >= n_ev) return;
+  const uint64_t me = leadc[t];
+  if (t == 0 || leadc[t - 1u] != me) { // a head: its event is the leader
+    const uint64_t k1 = key1s[t], k2 = key2s[t], group = k1 >> 32, kind = k2 >> 62;
+    alleles[r].pos = (group < n_groups ? r0[group] : 0) + (k1 & 0xFFFFFFFFull);
+    alleles[r].len = kind == NTS_OP_SUB ? 1u : k2 & CIGV_LEN;
+    alleles[r].ref_off = roff[i];
+    alleles[r].alt_off = aoff[i];
+    alleles[r].carrier_first = t;
+    alleles[r].group = (uint32_t)group;
+    alleles[r].kind = (uint32_t)kind;
+    alleles[r].reserved = 0;
+  }
+  if (t + 1u == n_ev || leadc[t + 1u] != me) alleles[r].n_carriers = (uint32_t)(t + 1u - cigp_lower(leadc, n_ev, me)); // the last event of the allele
+}
+
+// nts_cigar_pad's checks of chain c and its place: group order and range, a core, t0 + len_a, the extent of its group; r0[group] = the
+// smallest t0 of the group so far, placed = {first, t0} (the key once every chain of the group is seen: cigv_keys)
+template <class Who>
+int cigv_place(nts_ctx* ctx, const uint64_t* cigar, const nts_cig_chain* chains, const nts_cig_pad_at* at, uint64_t n_groups, uint64_t c, Who who,
+               uint64_t& lo, uint64_t& hi, std::vector<uint64_t>& r0, CigPadChain& placed)
+{
+  const nts_cig_chain& ch = chains[c];
+  const nts_cig_pad_at& a = at[c];
+  if (a.group >= n_groups) return fail(ctx, NTS_EINVAL, who() + " names a group outside n_groups");
+  if (c && a.group < at[c - 1].group) return fail(ctx, NTS_EINVAL, who() + ": the groups are not nondecreasing");
+  if (ch.n_cig) {
+    const uint64_t head = cigar[ch.first] & 15u, tail = cigar[ch.first + ch.n_cig - 1u] & 15u;
+    if ((head != CIG_EQ && head != CIG_X) || (tail != CIG_EQ && tail != CIG_X))
+      return fail(ctx, NTS_EINVAL, who() + ": its first or last entry is not = or X (pass the core of a chain)");
+  }
+  if (a.t0 > ~0ull - ch.len_a) return fail(ctx, NTS_ERANGE, who() + ": t0 + len_a wraps");
+  const bool opens = c == 0 || a.group != at[c - 1].group;
+  lo = opens ? a.t0 : std::min(lo, a.t0);
+  hi = opens ? a.t0 + ch.len_a : std::max(hi, a.t0 + ch.len_a);
+  if (hi - lo > 0xFFFFFFFFull) return fail(ctx, NTS_ERANGE, who() + ": the reference extent of its group is 2^32 or more");
+  r0[a.group] = lo;
+  placed = { ch.first, a.t0 };
+  return NTS_OK;
+}
+
+int cigar_alleles_run(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains, const nts_cig_pad_at* at,
+                      uint64_t n_groups, const uint8_t* alt, uint64_t n_alt, nts_cig_allele** alleles, uint64_t* allele_first, uint32_t** carriers,
+                      uint64_t* n_carriers)
+{
+  std::vector<CigPadChain> placed;
+  std::vector<uint64_t> r0;
+  try {
+    placed.resize(n_chains);
+    r0.assign(std::max<uint64_t>(n_groups, 1), 0);
+  } catch (const std::bad_alloc&) {
+    return fail(ctx, NTS_ENOMEM, "nts_cigar_alleles: no host memory for the chains and groups");
+  }
+  uint64_t lo = 0, hi = 0; // the extent of the group of the chain in front
+  auto place = [&](uint64_t c, auto who) -> int { return cigv_place(ctx, cigar, chains, at, n_groups, c, who, lo, hi, r0, placed[c]); };
+  if (const int rc = cig_chains_check(ctx, "nts_cigar_alleles", CIG_TEXT_MAX_BASES_LOG2, true, chains, n_chains, n_cigar, place)) return rc;
+  for (uint64_t c = 0; c < n_chains; ++c) placed[c].key0 = ((uint64_t)at[c].group << 32) + (placed[c].key0 - r0[at[c].group]);
+  auto nothing = [&] {
+    *alleles = nullptr;
+    *carriers = nullptr;
+    *n_carriers = 0;
+    memset(allele_first, 0, (n_groups + 1) * 8);
+    return NTS_OK;
+  };
+  if (n_cigar == 0) { // (nothing is launched)
+    if (n_alt) return fail(ctx, NTS_EINVAL, "nts_cigar_alleles: alt holds " + std::to_string(n_alt) + " bytes, the X and I entries of the chains have 0");
+    return nothing();
+  }
+  // (its own buffers first: while nothing is queued, a request that fails may still return at once)
+  NTS_WS(d_placed, CigPadChain*, "cigv_placed_at", n_chains * sizeof(CigPadChain));
+  NTS_WS(d_r0, uint64_t*, "cigv_r0", std::max<uint64_t>(n_groups, 1) * 8);
+  NTS_WS(d_allele_first, uint64_t*, "cigv_allele_first", (n_groups + 2) * 8);
+  uint32_t worst = SCRIPT_OK;
+  uint64_t totals[3] = { 0, 0, 0 }; // events, ref bytes, alt bytes
+  CigIndex ix; // columns PA, PB, PE (events), PR (ref bytes), PL (alt bytes)
+  hipError_t e_run;
+  if (const int rc = cig_index_stage<CigVarOf>(ctx, "cigar_alleles_events", cigar, n_cigar, chains, n_chains, 0, &worst, ix, e_run, [] {})) return rc;
+  if (e_run == hipSuccess) e_run = hipGetLastError();
+  if (e_run == hipSuccess) e_run = hipMemcpyAsync(d_placed, placed.data(), n_chains * sizeof(CigPadChain), hipMemcpyHostToDevice, ctx->stream);
+  if (e_run == hipSuccess && n_groups) e_run = hipMemcpyAsync(d_r0, r0.data(), n_groups * 8, hipMemcpyHostToDevice, ctx->stream);
+  for (uint32_t k = 0; k < 3 && e_run == hipSuccess; ++k)
+    e_run = hipMemcpyAsync(&totals[k], ix.column(2 + k) + n_cigar, 8, hipMemcpyDeviceToHost, ctx->stream);
+  hipError_t e_sync = hipStreamSynchronize(ctx->stream); // (whatever happened: the caller's arrays were sources of asynchronous copies)
+  HIP_TRY(ctx, e_run);
+  HIP_TRY(ctx, e_sync);
+  if (worst != SCRIPT_OK) {
+    if (worst < n_chains) // (the error path alone looks at the entries of that one chain)
+      for (uint64_t e = chains[worst].first; e < chains[worst].first + chains[worst].n_cig; ++e)
+        if ((cigar[e] & 15u) == CIG_P) return fail(ctx, NTS_EINVAL, "nts_cigar_alleles: chain " + std::to_string(worst) + " holds an entry of code 6");
+    return fail(ctx, NTS_EINVAL, "nts_cigar_alleles: the entries of chain " + std::to_string(worst) + " are no CIGAR of its lengths");
+  }
+  const uint64_t n_ev = totals[0];
+  if (totals[2] != n_alt)
+    return fail(ctx, NTS_EINVAL, "nts_cigar_alleles: alt holds " + std::to_string(n_alt) + " bytes, the X and I entries of the chains have " + std::to_string(totals[2]));
+  if (n_ev > CIGV_MOST_BYTES) return fail(ctx, NTS_ERANGE, "nts_cigar_alleles: 2^32 events or more");
+  if (n_ev == 0) return nothing(); // (no launch behind the stage)
+  // (the stream is idle: the buffers sized by the events are fetched before their kernels are queued)
+  NTS_WS(d_alt, uint8_t*, "cigv_alt_in", (std::max<uint64_t>(n_alt, 1) + 3) / 4 * 4);
+  NTS_WS(d_key1, uint64_t*, "cigv_key1", n_ev * 8);
+  NTS_WS(d_key2, uint64_t*, "cigv_key2", n_ev * 8);
+  NTS_WS(d_roff, uint64_t*, "cigv_roff", n_ev * 8);
+  NTS_WS(d_aoff, uint64_t*, "cigv_aoff", n_ev * 8);
+  NTS_WS(d_chain, uint32_t*, "cigv_chain", n_ev * 4);
+  NTS_WS(d_key2a, uint64_t*, "cigv_key2a", n_ev * 8);
+  NTS_WS(d_idxa, uint64_t*, "cigv_idxa", n_ev * 8);
+  NTS_WS(d_key1a, uint64_t*, "cigv_key1a", n_ev * 8);
+  NTS_WS(d_key1s, uint64_t*, "cigv_key1s", n_ev * 8);
+  NTS_WS(d_perm, uint64_t*, "cigv_perm", n_ev * 8);
+  NTS_WS(d_key2s, uint64_t*, "cigv_key2s", n_ev * 8);
+  NTS_WS(d_lead, uint64_t*, "cigv_lead", n_ev * 8);
+  NTS_WS(d_leadc, uint64_t*, "cigv_leadc", n_ev * 8);
+  NTS_WS(d_order, uint64_t*, "cigv_order", n_ev * 8);
+  NTS_WS(d_head, uint64_t*, "cigv_head", (n_ev + 1) * 8);
+  NTS_WS(d_rank, uint64_t*, "cigv_rank", (n_ev + 1) * 8);
+  NTS_WS(d_carriers, uint32_t*, "cigv_carriers", n_ev * 4);
+  const rocprim::counting_iterator<uint64_t> iota(0);
+  size_t tmp_a = 0, tmp_b = 0, tmp_c = 0, tmp_scan = 0;
+  e_run = rocprim::radix_sort_pairs(nullptr, tmp_a, d_key2, d_key2a, iota, d_idxa, n_ev, 0, 64, ctx->stream);
+  if (e_run == hipSuccess) e_run = rocprim::radix_sort_pairs(nullptr, tmp_b, d_key1a, d_key1s, d_idxa, d_perm, n_ev, 0, 64, ctx->stream);
+  if (e_run == hipSuccess) e_run = rocprim::radix_sort_pairs(nullptr, tmp_c, d_lead, d_leadc, iota, d_order, n_ev, 0, 32, ctx->stream);
+  if (e_run == hipSuccess) e_run = rocprim::exclusive_scan(nullptr, tmp_scan, d_head, d_rank, (uint64_t)0, n_ev + 1, rocprim::plus<uint64_t>(), ctx->stream);
+  HIP_TRY(ctx, e_run);
+  NTS_WS(d_tmp, void*, "ivs_tmp", std::max<size_t>(std::max(std::max(tmp_a, tmp_b), std::max(tmp_c, tmp_scan)), 16)); // (ix.tmp is dead from here)
+  std::vector<uint64_t> host_first(n_groups + 2); // (the caller's array is written only when the call succeeds)
+  if (n_alt) e_run = hipMemcpyAsync(d_alt, alt, n_alt, hipMemcpyHostToDevice, ctx->stream); // (a source of an asynchronous copy: a synchronisation follows whatever happens)
+  if (e_run == hipSuccess) {
+    ScopedTimer t(ctx, "cigar_alleles_events", true);
+    NTS_LAUNCH(k_cigv_events, IVL_GRID(n_ev), ix.cigar, n_cigar, (const CigPadChain*)d_placed, n_chains, ix.column(0), ix.column(2), ix.column(3),
+               ix.column(4), (const uint8_t*)d_alt, n_alt, n_ev, d_key1, d_key2, d_roff, d_aoff, d_chain);
+    e_run = rocprim::radix_sort_pairs(d_tmp, tmp_a, d_key2, d_key2a, iota, d_idxa, n_ev, 0, 64, ctx->stream);
+    if (e_run == hipSuccess) {
+      NTS_LAUNCH(k_cigv_gather, IVL_GRID(n_ev), (const uint64_t*)d_key1, (const uint64_t*)d_idxa, n_ev, d_key1a);
+      e_run = rocprim::radix_sort_pairs(d_tmp, tmp_b, d_key1a, d_key1s, d_idxa, d_perm, n_ev, 0, 64, ctx->stream);
+    }
+    if (e_run == hipSuccess) NTS_LAUNCH(k_cigv_gather, IVL_GRID(n_ev), (const uint64_t*)d_key2, (const uint64_t*)d_perm, n_ev, d_key2s);
+  }
+  if (e_run == hipSuccess) {
+    ScopedTimer t(ctx, "cigar_alleles_emit", true);
+    NTS_LAUNCH(k_cigv_leaders, IVL_GRID(n_ev), (const uint64_t*)d_key1s, (const uint64_t*)d_key2s, (const uint64_t*)d_perm, (const uint64_t*)d_aoff,
+               (const uint8_t*)d_alt, n_alt, n_ev, d_lead);
+    e_run = rocprim::radix_sort_pairs(d_tmp, tmp_c, d_lead, d_leadc, iota, d_order, n_ev, 0, 32, ctx->stream); // (a leader is a sorted index below 2^32)
+    if (e_run == hipSuccess) {
+      NTS_LAUNCH(k_cigv_heads, IVL_GRID(n_ev + 1), (const uint64_t*)d_leadc, n_ev, d_head);
+      e_run = rocprim::exclusive_scan(d_tmp, tmp_scan, d_head, d_rank, (uint64_t)0, n_ev + 1, rocprim::plus<uint64_t>(), ctx->stream);
+    }
+    if (e_run == hipSuccess)
+      NTS_LAUNCH(k_cigd_firsts, IVL_GRID(n_groups + 2), (const uint64_t*)d_key1s, n_ev, (const uint64_t*)d_rank, n_groups, d_allele_first);
+  }
+  if (e_run == hipSuccess) e_run = hipGetLastError();
+  if (e_run == hipSuccess) e_run = hipMemcpyAsync(host_first.data(), d_allele_first, (n_groups + 2) * 8, hipMemcpyDeviceToHost, ctx->stream);
+  e_sync = hipStreamSynchronize(ctx->stream);
+  HIP_TRY(ctx, e_run);
+  HIP_TRY(ctx, e_sync);
+  const uint64_t n_alleles = host_first[n_groups];
+  if (n_alleles == 0 || n_alleles > n_ev) return fail(ctx, NTS_EHIP, "nts_cigar_alleles: the scan left an impossible number of alleles");
+  // (the stream is idle: the output's buffer is fetched before its kernel is queued)
+  NTS_WS(d_alleles, nts_cig_allele*, "cigv_alleles", n_alleles * sizeof(nts_cig_allele));
+  nts_cig_allele* host_alleles = (nts_cig_allele*)malloc(n_alleles * sizeof(nts_cig_allele));
+  uint32_t* host_carriers = (uint32_t*)malloc(n_ev * 4);
+  auto drop = [&] {
+    free(host_alleles);
+    free(host_carriers);
+  };
+  if (!host_alleles || !host_carriers) {
+    drop();
+    return fail(ctx, NTS_ENOMEM, "nts_cigar_alleles: no host memory for the alleles");
+  }
+  {
+    ScopedTimer t(ctx, "cigar_alleles_emit", true);
+    NTS_LAUNCH(k_cigv_emit, IVL_GRID(n_ev), (const uint64_t*)d_key1s, (const uint64_t*)d_key2s, (const uint64_t*)d_perm, (const uint64_t*)d_order,
+               (const uint64_t*)d_leadc, (const uint64_t*)d_rank, (const uint64_t*)d_roff, (const uint64_t*)d_aoff, (const uint32_t*)d_chain,
+               (const uint64_t*)d_r0, n_groups, n_ev, d_alleles, n_alleles, d_carriers);
+  }
+  e_run = hipGetLastError();
+  if (e_run == hipSuccess) e_run = hipMemcpyAsync(host_alleles, d_alleles, n_alleles * sizeof(nts_cig_allele), hipMemcpyDeviceToHost, ctx->stream);
+  if (e_run == hipSuccess) e_run = hipMemcpyAsync(host_carriers, d_carriers, n_ev * 4, hipMemcpyDeviceToHost, ctx->stream);
+  e_sync = hipStreamSynchronize(ctx->stream);
+  if (e_run != hipSuccess || e_sync != hipSuccess) drop();
+  HIP_TRY(ctx, e_run);
+  HIP_TRY(ctx, e_sync);
+  *alleles = host_alleles;
+  *carriers = host_carriers;
+  *n_carriers = n_ev;
+  memcpy(allele_first, host_first.data(), (n_groups + 1) * 8);
   return NTS_OK;
 }

@@ -1129,6 +1129,33 @@ extern "C" int nts_cigar_depth(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_c
   return cigar_depth_run(ctx, cigar, n_cigar, chains, n_chains, at, n_groups, segs, seg_first);
 }
 
+extern "C" int nts_cigar_var_bases(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains,
+                                   const nts_genome* a, const nts_genome* b, const nts_cig_span* spans, uint8_t** ref, uint64_t* ref_first, uint8_t** alt,
+                                   uint64_t* alt_first)
+{
+  if (!ctx) return NTS_EINVAL;
+  if (n_cigar > 0xFFFFFFFFull || n_chains > 0xFFFFFFFFull) // (before any array is read)
+    return fail(ctx, NTS_ERANGE, "nts_cigar_var_bases: 2^32 entries or chains or more");
+  if ((n_cigar && !cigar) || (n_chains && !chains) || !ref || !ref_first || !alt || !alt_first)
+    return fail(ctx, NTS_EINVAL, "nts_cigar_var_bases: bad arguments");
+  if (!a || !b || !spans) return fail(ctx, NTS_EINVAL, "nts_cigar_var_bases: the bytes need spans and both genomes");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return cigar_var_bases_run(ctx, cigar, n_cigar, chains, n_chains, a, b, spans, ref, ref_first, alt, alt_first);
+}
+
+extern "C" int nts_cigar_alleles(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains,
+                                 const nts_cig_pad_at* at, uint64_t n_groups, const uint8_t* alt, uint64_t n_alt, nts_cig_allele** alleles,
+                                 uint64_t* allele_first, uint32_t** carriers, uint64_t* n_carriers)
+{
+  if (!ctx) return NTS_EINVAL;
+  if (n_cigar > 0xFFFFFFFFull || n_chains > 0xFFFFFFFFull || n_groups > 0xFFFFFFFFull) // (before any array is read)
+    return fail(ctx, NTS_ERANGE, "nts_cigar_alleles: 2^32 entries, chains or groups or more");
+  if ((n_cigar && !cigar) || (n_chains && (!chains || !at)) || (n_alt && !alt) || !alleles || !allele_first || !carriers || !n_carriers)
+    return fail(ctx, NTS_EINVAL, "nts_cigar_alleles: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return cigar_alleles_run(ctx, cigar, n_cigar, chains, n_chains, at, n_groups, alt, n_alt, alleles, allele_first, carriers, n_carriers);
+}
+
 extern "C" int nts_graph_budget(nts_ctx* ctx, uint64_t bytes)
 {
   if (!ctx) return NTS_EINVAL;

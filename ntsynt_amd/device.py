@@ -78,6 +78,9 @@ CIG_PAD_AT_DTYPE = np.dtype([("group", "<u4"), ("reserved", "<u4"), ("t0", "<u8"
 CIG_PAD = 6
 # nts_cig_depth_seg: what Context.cigar_depth returns, one per segment of constant (aligned, match, gap)
 CIG_DEPTH_SEG_DTYPE = np.dtype([("start", "<u8"), ("end", "<u8"), ("group", "<u4"), ("aligned", "<u4"), ("match", "<u4"), ("gap", "<u4")])
+# nts_cig_allele: what Context.cigar_alleles returns, one per allele of a group (kind: 1 SNV, 2 DEL, 3 INS)
+CIG_ALLELE_DTYPE = np.dtype([("pos", "<u8"), ("len", "<u8"), ("ref_off", "<u8"), ("alt_off", "<u8"), ("carrier_first", "<u8"), ("group", "<u4"),
+                             ("kind", "<u4"), ("n_carriers", "<u4"), ("reserved", "<u4")])
 # nts_lift_query / nts_lift_hit: what Context.cigar_lift takes and returns, one per query
 LIFT_QUERY_DTYPE = np.dtype([("chain", "<u4"), ("side", "<u4"), ("pos", "<u8")])
 LIFT_HIT_DTYPE = np.dtype([("pos", "<u8"), ("entry", "<u8"), ("off", "<u8"), ("code", "<u4"), ("reserved", "<u4")])
@@ -535,6 +538,59 @@ class Context:
                                             where.ctypes.data if where.size else None, int(n_groups), ctypes.byref(p_segs), seg_first.ctypes.data),
                    "nts_cigar_depth")
         return self._take(p_segs, int(seg_first[-1]), CIG_DEPTH_SEG_DTYPE), seg_first
+
+    def cigar_var_bases(self, cigar, chains, spans, genome_a, genome_b):
+        """the bases at the variant columns of the chains' CIGARs (nts_cigar_var_bases).  Arguments, checks and refusals as cigar_rows'
+        (entries of code CIG_PAD are refused).  Returns (ref, ref_first, alt, alt_first): ref holds, chain after chain, the bytes of
+        cigar_rows' row A at the columns of the X and D entries, alt those of row B at the columns of the X and I entries -- upper case
+        ACGT, N for what is no base --; chain c's are ref[ref_first[c]:ref_first[c + 1]] and alt[alt_first[c]:alt_first[c + 1]], the
+        firsts [len(chains) + 1] uint64.  A buffer of 2^32 bytes or more is refused.  Exact and deterministic."""
+        cg = np.ascontiguousarray(cigar, dtype=np.uint64)
+        ch = np.ascontiguousarray(chains, dtype=CHAIN_DTYPE)
+        if cg.ndim != 1 or ch.ndim != 1:
+            raise ValueError("cigar_var_bases: a list of entries and a list of chain records")
+        assert CHAIN_DTYPE.itemsize == ctypes.sizeof(_lib.CigChain) and CIG_SPAN_DTYPE.itemsize == ctypes.sizeof(_lib.CigSpan)
+        sp = None
+        if spans is not None:
+            sp = np.ascontiguousarray(spans, dtype=CIG_SPAN_DTYPE)
+            if sp.shape != (ch.size,):
+                raise ValueError("cigar_var_bases: one span per chain")
+            if sp.size == 0:
+                sp = np.zeros(1, dtype=CIG_SPAN_DTYPE)       # (a pointer that is not NULL: spans were given)
+        ref_first, alt_first = np.zeros(ch.size + 1, dtype=np.uint64), np.zeros(ch.size + 1, dtype=np.uint64)
+        p_ref, p_alt = c_vp(), c_vp()
+        self.check(self.lib.nts_cigar_var_bases(self.h, cg.ctypes.data if cg.size else None, cg.size, ch.ctypes.data if ch.size else None, ch.size,
+                                                genome_a.h if genome_a is not None else None, genome_b.h if genome_b is not None else None,
+                                                sp.ctypes.data if sp is not None else None, ctypes.byref(p_ref), ref_first.ctypes.data,
+                                                ctypes.byref(p_alt), alt_first.ctypes.data), "nts_cigar_var_bases")
+        return self._take(p_ref, int(ref_first[-1]), np.dtype("u1")), ref_first, self._take(p_alt, int(alt_first[-1]), np.dtype("u1")), alt_first
+
+    def cigar_alleles(self, cigar, chains, at, alt, n_groups=None):
+        """one allele table per reference-anchored group of chains (nts_cigar_alleles).  cigar, chains, at and n_groups as for cigar_pad
+        (the chains are cores and tile the entries; chains of a group may overlap); alt: the alt bytes of cigar_var_bases over all
+        chains in chain order, uint8.  Returns (alleles, allele_first, carriers): a CIG_ALLELE_DTYPE array -- an allele is the events
+        (an X column: kind 1, a D entry: kind 2, an I entry: kind 3) of equal (group, pos, kind, len, alt bytes) -- ascending by (group,
+        pos, kind, len or alt byte, smallest carrier), group g's being alleles[allele_first[g]:allele_first[g + 1]] (allele_first
+        [n_groups + 1] uint64), and carriers, uint32: the chains that hold allele r are carriers[carrier_first:carrier_first +
+        n_carriers], ascending; ref_off and alt_off: the bytes of its smallest carrier in cigar_var_bases' buffers.  Reads no genome.
+        Exact and deterministic."""
+        cg = np.ascontiguousarray(cigar, dtype=np.uint64)
+        ch = np.ascontiguousarray(chains, dtype=CHAIN_DTYPE)
+        where = np.ascontiguousarray(at, dtype=CIG_PAD_AT_DTYPE)
+        bases = np.ascontiguousarray(alt, dtype=np.uint8)
+        if cg.ndim != 1 or ch.ndim != 1 or where.shape != ch.shape or bases.ndim != 1:
+            raise ValueError("cigar_alleles: a list of entries, a list of chain records, one {group, t0} per chain and a list of bytes")
+        assert CHAIN_DTYPE.itemsize == ctypes.sizeof(_lib.CigChain) and CIG_PAD_AT_DTYPE.itemsize == ctypes.sizeof(_lib.CigPadAt)
+        assert CIG_ALLELE_DTYPE.itemsize == ctypes.sizeof(_lib.CigAllele) == 56
+        if n_groups is None:
+            n_groups = int(where["group"][-1]) + 1 if where.size else 0
+        allele_first = np.zeros(int(n_groups) + 1, dtype=np.uint64)
+        p_alleles, p_carriers, n_carriers = c_vp(), c_vp(), ctypes.c_uint64(0)
+        self.check(self.lib.nts_cigar_alleles(self.h, cg.ctypes.data if cg.size else None, cg.size, ch.ctypes.data if ch.size else None, ch.size,
+                                              where.ctypes.data if where.size else None, int(n_groups), bases.ctypes.data if bases.size else None,
+                                              bases.size, ctypes.byref(p_alleles), allele_first.ctypes.data, ctypes.byref(p_carriers),
+                                              ctypes.byref(n_carriers)), "nts_cigar_alleles")
+        return self._take(p_alleles, int(allele_first[-1]), CIG_ALLELE_DTYPE), allele_first, self._take(p_carriers, int(n_carriers.value), np.dtype("<u4"))
 
     def cigar_rows(self, cigar, chains, spans, genome_a, genome_b, padded=False):
         """the aligned rows of the chains' CIGARs, the sequence lines of a MAF block (nts_cigar_rows).  cigar, chains, spans and the

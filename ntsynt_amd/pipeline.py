@@ -499,7 +499,8 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         graph_budget=None, assess=None, gaps=False, gap_links=None, gap_block_links=False, gap_copies=None, gap_copy_sites=None,
         gap_periods=None, gap_families=None, block_identity=None, block_variants=None, block_wide_variants=None, block_ends=None,
         block_end_variants=False, block_paf=None, block_lift=None, block_lift_identity=None, block_windows=None, block_lift_joined=None,
-        block_paf_cs=False, block_chain=None, block_maf=None, block_maf_multi=None, block_conservation=None):
+        block_paf_cs=False, block_chain=None, block_maf=None, block_maf_multi=None, block_conservation=None,
+        block_variant_sites=None):
     """FASTA paths -> engine (outputs in .outputs and in the CWD).  Mirrors oracle.synteny_oracle.run_pipeline's
     signature so the parity tests read alike.  Under torch.distributed (WORLD_SIZE > 1, process group already
     initialised by the caller) genomes are sharded over the ranks.
@@ -558,6 +559,10 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
     <prefix>.block_conservation.tsv, per block the runs of reference bases with one (aligned, match, gap) over its star alignment and
     their sums (assess.block_conservation; stage block_conservation behind block_maf_multi; always a pass of its own; with `benchmark`
     the stage times gain block_conservation:cigar_depth_events and :cigar_depth_emit).
+    block_variant_sites = (k, rate, band, max_len, max_edits, ends), as block_paf: <prefix>.block_variant_sites.tsv, per block one line per
+    allele over its star alignment with its carriers and genotypes (assess.block_variant_sites; stage block_variant_sites behind
+    block_conservation; always a pass of its own; with `benchmark` the stage times gain block_variant_sites:cigar_var_bases_scan,
+    :cigar_var_bases_emit, :cigar_alleles_events and :cigar_alleles_emit).
     block_lift =(bed_path, genome, k, rate, band,
     max_len, max_edits, ends): behind that file, <prefix>.block_lift.tsv (assess.block_lift: the BED intervals of `genome`, a FASTA base
     name, mapped through the block alignments into the other genomes; one rank only; it needs none of the other switches; with
@@ -709,6 +714,18 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
             (check_ends_parameters(*block_conservation[5]) if block_conservation[5] is not None else None)
         if message:
             raise ValueError("block_conservation = (k, rate, band, max_len, max_edits, ends): " + message)
+    if block_variant_sites is not None:
+        if world > 1 or (mx_tsvs is not None and initial_only):
+            raise ValueError("block_variant_sites needs every genome resident on one GPU (one rank, genomes loaded)")
+        from .assess import check_ends_parameters, check_identity_parameters
+        if len(block_variant_sites) != 6 or (block_variant_sites[5] is not None and len(block_variant_sites[5]) != 3):
+            raise ValueError("block_variant_sites = (k, rate, band, max_len, max_edits, ends) with ends = (ends_max_len, ends_max_edits, ends_penalty) or None")
+        block_variant_sites = tuple(int(x) for x in block_variant_sites[:5]) + \
+            (tuple(int(x) for x in block_variant_sites[5]) if block_variant_sites[5] is not None else None,)
+        message = check_identity_parameters(*block_variant_sites[:5]) or \
+            (check_ends_parameters(*block_variant_sites[5]) if block_variant_sites[5] is not None else None)
+        if message:
+            raise ValueError("block_variant_sites = (k, rate, band, max_len, max_edits, ends): " + message)
     if block_lift is not None:
         if world > 1 or (mx_tsvs is not None and initial_only):
             raise ValueError("block_lift needs every genome resident on one GPU (one rank, genomes loaded)")
@@ -1559,6 +1576,26 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         if benchmark:
             st.rows += depth_times
         st.mark("block_conservation_done")
+    if block_variant_sites is not None:
+        st.start("block_variant_sites")
+        from . import assess as assess_
+        site_timers = ("cigar_var_bases_scan", "cigar_var_bases_emit", "cigar_alleles_events", "cigar_alleles_emit")
+        if benchmark:                                         # (device events around the calls of this stage only)
+            backend.ctx.profile(True)
+            sites_before = {name: backend.ctx.timing(name)[0] for name in site_timers}
+        sites = assess_.block_variant_sites(backend.ctx, {fa.basename(p): genomes[p] for p in fastas}, assess_.read_blocks(f"{prefix}.synteny_blocks.tsv"),
+                                            *block_variant_sites[:5], ends=block_variant_sites[5])
+        if benchmark:
+            site_times = [(f"block_variant_sites:{name}", (backend.ctx.timing(name)[0] - sites_before[name]) * 1e-3) for name in site_timers]
+            backend.ctx.profile(False)
+        text = assess_.variant_sites_table(*sites, *block_variant_sites[:5], ends=block_variant_sites[5])
+        with open(f"{prefix}.block_variant_sites.tsv", "w", encoding="utf-8") as fh:
+            fh.write(text)
+        eng.outputs[f"{prefix}.block_variant_sites.tsv"] = text
+        st.stop()
+        if benchmark:
+            st.rows += site_times
+        st.mark("block_variant_sites_done")
     if block_lift is not None:
         st.start("block_lift")
         from . import assess as assess_
