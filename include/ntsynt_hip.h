@@ -753,7 +753,7 @@ int nts_edit_wide(nts_ctx* ctx, const nts_genome* g_a, const nts_genome* g_b, co
  *   most table_budget bytes (0 = 1 GiB) that is released when the call ends, the host cuts the script set in index order into batches that fit, one launch per batch, and
  *   the result does not depend on the budget.  Two scans and a selection (timer "edit_wide_script_plan"), one 64-lane wave per member
  *   (timer "edit_wide_script"); an empty script set launches nothing.  No atomic, no launch per segment, no floating point: the same
- *   input gives the same bytes.  docs/design/04_19_block_wide_variants.md; csrc/nts_edit_wide_script.inc.
+ *   input gives the same bytes.  docs/design/04_19_block_wide_variants.md; csrc/nts_edit_wide_script.inc, csrc/nts_edit_fr_script.inc.
  * nts_edit_wide_script_last_plan: the last such call on this context: members of the script set, bytes of all their tables, batches
  *   (all 0 when nothing was launched); any pointer may be NULL. */
 int nts_edit_wide_script(nts_ctx* ctx, const nts_genome* g_a, const nts_genome* g_b, const nts_interval* iv_a, const nts_interval* iv_b,
@@ -812,7 +812,7 @@ int nts_edit_extend(nts_ctx* ctx, const nts_genome* g_a, const nts_genome* g_b, 
  *   released when the call ends, the host cuts the tasks with D >= 1 in index order into batches that fit, one launch per batch, and
  *   the result does not depend on the budget.  Two scans and a selection (timer "edit_extend_script_plan"), one 64-lane wave per task
  *   with D >= 1, two rows of 2 Dmax + 3 entries in LDS (timer "edit_extend_script").  No atomic, no launch per task, no floating
- *   point: the same input gives the same bytes.  docs/design/04_21_block_end_variants.md; csrc/nts_edit_extend_script.inc;
+ *   point: the same input gives the same bytes.  docs/design/04_21_block_end_variants.md; csrc/nts_edit_extend_script.inc, csrc/nts_edit_fr_script.inc;
  *   ntsynt_amd/assess.py block_ends, `ntSynt --block-end-variants`, `bin/ntsynt_block_stats --end-variants-out`.
  * nts_edit_extend_script_last_plan: the last such call on this context: tasks with D >= 1, bytes of all their tables, batches (all 0
  *   when nothing was launched); any pointer may be NULL. */

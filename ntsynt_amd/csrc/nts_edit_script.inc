@@ -15,7 +15,6 @@
 constexpr int32_t SCRIPT_NONE = -1;
 constexpr uint32_t SCRIPT_WAVES = 2;  // 2 waves x 64 rows x 64 lanes x 4 B = 32 KiB per workgroup: five workgroups, ten waves per CU
 constexpr uint32_t SCRIPT_ROWS = 64;  // e = 0 .. 2 W + 1 at W = 31
-constexpr uint32_t SCRIPT_OK = 0xFFFFFFFFu;
 static_assert(2 * EDIT_MAX_BAND + 1 < SCRIPT_ROWS, "a row per edit count up to the largest accepted distance");
 static_assert(SCRIPT_WAVES * SCRIPT_ROWS * 64 * 4 <= 64 * 1024, "static LDS of one workgroup");
 static_assert(sizeof(nts_edit_op) == 16, "the C ABI's layout");
@@ -28,11 +27,6 @@ struct ScriptCount // what a segment's dist adds to the number of ops
 struct ScriptKeep
 {
   __host__ __device__ bool operator()(uint32_t d) const { return d >= 1u && d < NTS_EDIT_INVALID; }
-};
-
-struct ScriptMin
-{
-  __host__ __device__ uint32_t operator()(uint32_t x, uint32_t y) const { return x < y ? x : y; }
 };
 
 // the codes of A[p] and of the oriented B[q]; what is not A, C, G or T equals nothing, itself included
@@ -221,49 +215,18 @@ int edit_script_run(nts_ctx* ctx, const nts_genome* ga, const nts_genome* gb, co
   if (e == hipSuccess) e = hipMemcpyAsync(d_dist, dist, n * 4, hipMemcpyHostToDevice, ctx->stream);
   if (e != hipSuccess) hipStreamSynchronize(ctx->stream); // (before `ivs` goes away)
   HIP_TRY(ctx, e);
-  nts_edit_op* host_ops = nullptr;
-  uint32_t worst = SCRIPT_OK;
-  hipError_t e_run = hipSuccess;
-  {
-    ScopedTimer t(ctx, "edit_script_plan");
-    auto counts = rocprim::make_transform_iterator((const uint32_t*)d_dist, ScriptCount());
-    auto flags = rocprim::make_transform_iterator((const uint32_t*)d_dist, ScriptKeep());
-    size_t tmp_scan = 0, tmp_sel = 0;
-    e_run = rocprim::exclusive_scan(nullptr, tmp_scan, counts, d_first, (uint64_t)0, n, rocprim::plus<uint64_t>(), ctx->stream);
-    if (e_run == hipSuccess)
-      e_run = rocprim::select(nullptr, tmp_sel, rocprim::counting_iterator<uint32_t>(0), flags, d_kept, d_num, n, ctx->stream);
-    void* d_tmp = e_run == hipSuccess ? ws_get(ctx, "ivs_tmp", std::max<size_t>(std::max(tmp_scan, tmp_sel), 16)) : nullptr;
-    if (e_run == hipSuccess && !d_tmp) e_run = hipErrorOutOfMemory;
-    if (e_run == hipSuccess) e_run = rocprim::exclusive_scan(d_tmp, tmp_scan, counts, d_first, (uint64_t)0, n, rocprim::plus<uint64_t>(), ctx->stream);
-    if (e_run == hipSuccess) e_run = rocprim::select(d_tmp, tmp_sel, rocprim::counting_iterator<uint32_t>(0), flags, d_kept, d_num, n, ctx->stream);
-  }
-  if (e_run == hipSuccess && kept) {
-    {
-      ScopedTimer t(ctx, "edit_script", true);
-      NTS_LAUNCH(k_edit_script, dim3((uint32_t)((kept + SCRIPT_WAVES - 1) / SCRIPT_WAVES)), dim3(SCRIPT_WAVES * 64), 0, ctx->stream,
-                 (const uint8_t*)ga->d_code + PAD, (const uint8_t*)gb->d_code + PAD, (const EditIv*)d_ivs, n_iv, (const nts_iv_segment*)d_seg, n, band,
-                 (const uint32_t*)d_dist, (const uint64_t*)d_first, (const uint32_t*)d_kept, (const uint64_t*)d_num, kept, d_ops, total, d_status);
-      size_t tmp = 0;
-      e_run = rocprim::reduce(nullptr, tmp, d_status, d_worst, SCRIPT_OK, kept, ScriptMin(), ctx->stream);
-      void* d_tmp = e_run == hipSuccess ? ws_get(ctx, "ivs_tmp", std::max<size_t>(tmp, 16)) : nullptr;
-      if (e_run == hipSuccess && !d_tmp) e_run = hipErrorOutOfMemory;
-      if (e_run == hipSuccess) e_run = rocprim::reduce(d_tmp, tmp, d_status, d_worst, SCRIPT_OK, kept, ScriptMin(), ctx->stream);
-    }
-    if (e_run == hipSuccess) e_run = hipGetLastError();
-    if (e_run == hipSuccess) e_run = hipMemcpyAsync(&worst, d_worst, 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e_run == hipSuccess) {
-      host_ops = (nts_edit_op*)malloc(total * sizeof(nts_edit_op));
-      if (host_ops) e_run = hipMemcpyAsync(host_ops, d_ops, total * sizeof(nts_edit_op), hipMemcpyDeviceToHost, ctx->stream);
-    }
-  }
-  if (e_run == hipSuccess && first) e_run = hipMemcpyAsync(first, d_first, n * 8, hipMemcpyDeviceToHost, ctx->stream);
-  const hipError_t e_sync = hipStreamSynchronize(ctx->stream); // (whatever happened: `ivs` was the source of an asynchronous copy)
-  if (e_run != hipSuccess || e_sync != hipSuccess || worst != SCRIPT_OK || (kept && !host_ops)) free(host_ops);
-  HIP_TRY(ctx, e_run);
-  HIP_TRY(ctx, e_sync);
-  if (kept && !host_ops) return fail(ctx, NTS_ENOMEM, "nts_edit_script: no host memory for the ops");
-  if (worst != SCRIPT_OK) return fail(ctx, NTS_EINVAL, "nts_edit_script: dist is not the distance of segment " + std::to_string(worst));
-  *ops = host_ops;
+  const hipError_t e_plan = script_plan(ctx, "edit_script_plan", rocprim::make_transform_iterator((const uint32_t*)d_dist, ScriptCount()),
+                                        rocprim::make_transform_iterator((const uint32_t*)d_dist, ScriptKeep()), n, d_first, d_kept, d_num);
+  auto launch = [&] {
+    NTS_LAUNCH(k_edit_script, dim3((uint32_t)((kept + SCRIPT_WAVES - 1) / SCRIPT_WAVES)), dim3(SCRIPT_WAVES * 64), 0, ctx->stream,
+               (const uint8_t*)ga->d_code + PAD, (const uint8_t*)gb->d_code + PAD, (const EditIv*)d_ivs, n_iv, (const nts_iv_segment*)d_seg, n, band,
+               (const uint32_t*)d_dist, (const uint64_t*)d_first, (const uint32_t*)d_kept, (const uint64_t*)d_num, kept, d_ops, total, d_status);
+  };
+  ScriptDone done; // (kept = 0: the plan ran, nothing is launched, *ops = NULL)
+  if (int rc = script_finish(ctx, e_plan, "edit_script", launch, d_status, d_worst, kept, d_ops, total, d_first, first, n, done)) return rc;
+  if (done.no_memory) return fail(ctx, NTS_ENOMEM, "nts_edit_script: no host memory for the ops");
+  if (done.worst != SCRIPT_OK) return fail(ctx, NTS_EINVAL, "nts_edit_script: dist is not the distance of segment " + std::to_string(done.worst));
+  *ops = done.ops;
   *n_ops = total;
   return NTS_OK;
 }

@@ -843,6 +843,7 @@ namespace {
 #include "nts_iv_families.inc"
 #include "nts_iv_anchors.inc"
 #include "nts_edit.inc"
+#include "nts_edit_fr_script.inc"
 #include "nts_edit_script.inc"
 #include "nts_edit_wide.inc"
 #include "nts_edit_wide_script.inc"

@@ -1558,8 +1558,9 @@ ENTRIES += [
 ]
 BY_NAME = {e.name: e for e in ENTRIES}
 # where each entry's entry point requests its scratch (ntsynt_amd/csrc): what the host test reads the family table against
-SOURCES = {"edit_segments": ["nts_edit.inc"], "edit_wide": ["nts_edit_wide.inc"], "edit_script": ["nts_edit_script.inc"],
-           "edit_wide_script": ["nts_edit_wide_script.inc"], "edit_extend": ["nts_edit_extend.inc"], "edit_extend_script": ["nts_edit_extend_script.inc"],
+SOURCES = {"edit_segments": ["nts_edit.inc"], "edit_wide": ["nts_edit_wide.inc"], "edit_script": ["nts_edit_script.inc", "nts_edit_fr_script.inc"],
+           "edit_wide_script": ["nts_edit_wide_script.inc", "nts_edit_fr_script.inc"], "edit_extend": ["nts_edit_extend.inc"],
+           "edit_extend_script": ["nts_edit_extend_script.inc", "nts_edit_fr_script.inc"],
            "cigar_build": ["nts_cigar.inc"], "cigar_lift": ["nts_cigar.inc"], "cigar_lift_stats": ["nts_cigar.inc"],
            "cigar_text": ["nts_cigar.inc"], "iv_anchor_segments": ["nts_iv_anchors.inc"], "iv_links": ["nts_iv_links.inc"],
            "iv_sites": ["nts_iv_sites.inc"], "iv_periods": ["nts_iv_periods.inc"], "iv_period_hashes": ["nts_iv_families.inc"],
