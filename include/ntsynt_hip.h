@@ -381,6 +381,9 @@ int nts_path_stats(nts_ctx* ctx, uint64_t* sketch_many_listed, uint64_t* bf_dire
  * k_bin1 was launched with (min(tiles, 2 per CU); 0 when the build did not apply or k > 128 took the run-table walk), its level-1
  * buckets B1 and log2 of its level-2 buckets per level-1 bucket (nts_bf_bin_plan). */
 int nts_bf_bin_last(nts_ctx* ctx, uint32_t* bin1_workgroups, uint32_t* B1, uint32_t* log2_b2);
+/* The same with one figure more: the idx32 the launch was given (1: a residue's place in the level-1 array is a 32-bit index, what the
+ * plan says for B1 * cap1 < 2^32; 0: the general 64-bit place -- beyond ~3.8 G k-mers, or NTS_BIN_IDX32=0 on the experiments build). */
+int nts_bf_bin_last_ex(nts_ctx* ctx, uint32_t* bin1_workgroups, uint32_t* B1, uint32_t* log2_b2, uint32_t* idx32);
 /* Of the last nts_bf_insert_and: whether the level went the literal way of src/ntsynt_make_common_bf.cpp:134-160 -- every k-mer of
  * the genome looked up in the running filter, the bits that were hit kept -- which the library chooses by itself once the running
  * filter is all but empty (its popcount known and below ~6 * 10^5 bits, where two folded tables in LDS answer most look-ups: what is

@@ -340,6 +340,7 @@ SYMBOLS = [
     ("nts_graph_last_plan", ctypes.c_int, [c_vp, c_u32p, c_u32p, c_u64p, c_u32p]),
     ("nts_graph_plan_slices", ctypes.c_int, [c_vp, u32, u64, u64, c_vp, c_vp]),
     ("nts_bf_bin_last", ctypes.c_int, [c_vp, c_vp, c_vp, c_vp]),
+    ("nts_bf_bin_last_ex", ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp]),
     ("nts_bf_bin_plan", ctypes.c_int, [u64, u64, u32, ctypes.c_int, ctypes.c_int, c_vp]),
     ("nts_engine_create", ctypes.c_int, [c_vp, u32, u32, ctypes.POINTER(c_vp)]),
     ("nts_engine_free", None, [c_vp, c_vp]),

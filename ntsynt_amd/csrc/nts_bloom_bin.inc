@@ -1159,7 +1159,10 @@ int bf_insert_binned(nts_ctx* ctx, nts_bf* bf, const nts_genome* g, const Genome
   P.cnt1 = d_cnt1;
   P.out1 = d_out1;
   P.cap1 = (uint32_t)cap1;
-  P.idx32 = plan.idx32;
+  // NTS_BIN_IDX32=0: the 64-bit place whatever the plan says (tests: the path of B1 * cap1 >= 2^32 on a small genome; it is the
+  // general one -- s_gbase without b * cap1, every store through (uint64_t)b * cap1 + pos and its capacity test)
+  P.idx32 = (NTS_KNOB("NTS_BIN_IDX32") && atoi(NTS_KNOB("NTS_BIN_IDX32")) == 0) ? 0u : plan.idx32;
+  ctx->last_bin_idx32 = P.idx32;
   P.late = late;
   ScopedTimer t(ctx, and_mode ? "bf_insert_and" : "bf_insert", true);
   if (k > FAST_K_MAX) {

@@ -476,6 +476,7 @@ struct nts_ctx
   uint64_t last_many_listed = 0; // candidates of k_hash_select_hi tiles that listed more than their slots hold (repeats, pieces)
   uint32_t last_bin1_grid = 0;   // of the last partitioned Bloom build: k_bin1's workgroups (0: k_bin1 did not run), level-1 buckets, log2 of the
   uint32_t last_bin_b1 = 0, last_bin_log2_b2 = 0; // level-2 buckets per level-1 bucket (nts_bf_bin_last)
+  uint32_t last_bin_idx32 = 0;   // ... and the idx32 its kernels were given (nts_bf_bin_last_ex)
   uint64_t last_bf_direct = 0;  // indices of the last partitioned Bloom build that bypassed the buckets (full bucket, lanes in pieces)
   size_t win_fused_lds_set = 0;  // dynamic LDS k_window_min<true> was last allowed
   uint32_t last_comm_sparse = 0; // the last all-reduce of a filter gathered set-bit indices instead of chunks

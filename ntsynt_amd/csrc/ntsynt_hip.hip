@@ -4266,6 +4266,13 @@ extern "C" int nts_bf_bin_last(nts_ctx* ctx, uint32_t* bin1_workgroups, uint32_t
   return NTS_OK;
 }
 
+extern "C" int nts_bf_bin_last_ex(nts_ctx* ctx, uint32_t* bin1_workgroups, uint32_t* B1, uint32_t* log2_b2, uint32_t* idx32)
+{
+  if (!ctx) return NTS_EINVAL;
+  if (idx32) *idx32 = ctx->last_bin_idx32;
+  return nts_bf_bin_last(ctx, bin1_workgroups, B1, log2_b2);
+}
+
 extern "C" int nts_bf_level_stats(nts_ctx* ctx, uint32_t* sparse_level, uint64_t* accepted_kmers)
 {
   if (!ctx) return NTS_EINVAL;

@@ -789,12 +789,16 @@ class Context:
         self.check(self.lib.nts_path_stats(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "nts_path_stats")
         return {"sketch_many_listed": a.value, "bf_direct_indices": b.value, "bf_list_fallback": c.value}
 
-    def bf_bin_last(self):
+    def bf_bin_last(self, idx32=False):
         """dict(bin1_workgroups, B1, log2_b2) of the last partitioned Bloom build: the workgroups of its first pass (0: it did not run)
-        and the bucket geometry it was launched with (nts_bf_bin_last)"""
-        a, b, c = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
-        self.check(self.lib.nts_bf_bin_last(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "nts_bf_bin_last")
-        return {"bin1_workgroups": a.value, "B1": b.value, "log2_b2": c.value}
+        and the bucket geometry it was launched with (nts_bf_bin_last).  idx32=True: one key more, idx32 -- whether a residue's place
+        in the level-1 array was a 32-bit index (nts_bf_bin_last_ex)."""
+        a, b, c, d = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+        self.check(self.lib.nts_bf_bin_last_ex(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d)), "nts_bf_bin_last_ex")
+        out = {"bin1_workgroups": a.value, "B1": b.value, "log2_b2": c.value}
+        if idx32:
+            out["idx32"] = d.value
+        return out
 
     def bf_level_stats(self):
         """dict(sparse_level, accepted_kmers): whether the last BloomFilter.insert_and went the literal way over a running filter that

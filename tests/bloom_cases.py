@@ -286,3 +286,108 @@ def product_case(cus):
             a[at:at + n] = ord("N")
             shift += k - 1 + n
     return [a.tobytes()], k, PRODUCT_FILTER, dict(broken_tiles=tuple(broken), grid=grid, n_tiles=n_tiles)
+
+
+# ---- a family of three genomes of any size ----------------------------------------------------------------------------------------------
+def family(seed, n_bases, second=(40000, 9000)):
+    """geometry_base()'s three genomes at another size: about n_bases random k-mers in a few records with N runs (one record empty, one
+    of 30 bases), a second small genome, and the first one's relative at 2 %"""
+    rng = np.random.default_rng(seed)
+    seqs = []
+    for n in (n_bases * 2 // 3, 0, 30, n_bases - n_bases * 2 // 3 + 1):
+        a = np.frombuffer(bases(rng, n), dtype=np.uint8).copy()
+        for at in rng.integers(0, max(n - 60, 1), size=min(n // 40000, 8)):
+            a[at:at + int(rng.integers(1, 50))] = ord("N")
+        seqs.append(a.tobytes())
+    rel = []
+    for s in seqs:
+        a = np.frombuffer(s, dtype=np.uint8).copy()
+        hit = (rng.random(a.size) < 0.02) & (a != ord("N"))
+        a[hit] = ACGT[rng.integers(0, 4, size=int(hit.sum()))]
+        rel.append(a.tobytes())
+    return dict(seqs=seqs, relative=rel, second=[bases(rng, n) for n in second])
+
+
+def hashes(records, k):
+    "the oracle's first hash of every valid k-mer of a genome, record after record"
+    return np.concatenate([O.hash_all(s, k)[1] for s in records] + [np.zeros(0, dtype=np.uint64)])
+
+
+# ---- the second round of k_bin3's load loop ---------------------------------------------------------------------------------------------
+# k_bin3 loads 4 * BIN3_THREADS 16-byte pieces per trip: 16384 unpacked residues (one partition level) or 8192 packed words of three
+# residues each (two levels).  A final bucket takes a second trip with more than that.
+BIN3_TRIP_RESIDUES, BIN3_TRIP_WORDS = 16384, 8192
+SECOND_TRIP_K = 24
+# name -> (nbytes, random k-mers of the first genome, REPEATS on top, seed, what the fixed plan makes of it)
+SECOND_TRIP = {
+    "one_bucket": (65536, 20000, False, 8810, "F = 1: one level, B1 = 1, cap1 about 26.6 k, the bucket of 20 k residues unclamped"),
+    "two_buckets": (131072, 40000, False, 8811, "F = 2: one level, B1 = 2, 20 k residues each"),
+    "two_buckets_over": (131072, 40000, True, 8816, "F = 2 with the repeats on top: a bucket clamped to cap1 > 16384, the rest set directly"),
+    "packed": (32 * MIB + 8, 13_000_000, False, 8806, "F = 513: B2 = 2, B1 = 257, cap2 > 8192 words, every final bucket beyond 24 576 residues"),
+}
+_trip = {}
+
+
+def second_trip_case(name):
+    "(records, k, nbytes, claims) and (second, relative), as geometry_case(); the last case asked for is kept"
+    if name not in _trip:
+        _trip.clear()
+        nbytes, n, over, seed, what = SECOND_TRIP[name]
+        fam = family(seed, n, second=(n // 2, n - n // 2))    # (as many k-mers as the first: the read-and-OR finish takes the second trip too)
+        extra = list(REPEATS) if over else []
+        claims = dict(shape=what, overflow=over)
+        _trip[name] = ((fam["seqs"] + extra, SECOND_TRIP_K, nbytes, claims), (fam["second"], fam["relative"] + extra))
+    return _trip[name]
+
+
+# ---- the large geometries: log2_b2 = 6 .. 9 ---------------------------------------------------------------------------------------------
+GIB = 1 << 30
+
+
+def partly_real(log2_b2):
+    """a filter of 256 whole level-1 buckets and a 257th of which seven final buckets and 40013 bytes of an eighth are real (a partial
+    last word too): the other 2^log2_b2 - 8 final buckets of that level-1 bucket lie behind the filter's end"""
+    return ((256 << log2_b2) + 7) * 65536 + 40013
+
+
+# nbytes -> what the fixed plan makes of it (tests/test_bloom_cases_host.py holds F, log2_b2, B2, B1, n_final against written-out numbers)
+LARGE = {
+    GIB + 8: "F = 16385: B2 = 64, B1 = 257 (513 under the floor), 63 buckets behind the filter's end",
+    2 * GIB + 8: "F = 32769: B2 = 128, B1 = 257",
+    4 * GIB + 8: "F = 65537: B2 = 256, B1 = 257",
+    8 * GIB + 8: "F = 131073: B2 = 512, B1 = 257: every lane of k_bin2 clears and scans a counter",
+    16 * GIB: "F = 262144: B2 = 512, B1 = 512, the largest geometry the plan accepts",
+    partly_real(6): "F = 16392: B2 = 64, B1 = 257, the last level-1 bucket 8 real final buckets of 64, the last of them partial",
+    partly_real(9): "F = 131080: B2 = 512, B1 = 257, the last level-1 bucket 8 real final buckets of 512, the last of them partial",
+}
+LARGE_K = 24
+LARGE_PARTLY_REAL = (partly_real(6), partly_real(9))
+_large = {}
+
+
+def large_base():
+    "family() at about 2 M k-mers and the hashes of its three genomes (first, second, relative), made once"
+    if not _large:
+        fam = family(977, 2_000_000)
+        genomes = (fam["seqs"], fam["second"], fam["relative"])
+        _large.update(genomes=genomes, h0=tuple(hashes(g, LARGE_K) for g in genomes))
+    return _large
+
+
+# ---- a filter as the set of its indices -------------------------------------------------------------------------------------------------
+def sparse_reference(h0, nbytes):
+    """The oracle's filter of nbytes bytes after each finish, as sorted arrays of distinct bit indices: insert of the first genome
+    (the set of its indices), insert of the second (the union), the cascade level of the third (its indices that the running set
+    holds: O.bf_build(..., prev=...) with one hash function).  h0: the three genomes' hashes (hashes())."""
+    bits = np.uint64(nbytes * 8)
+    first, second, third = (np.unique(h % bits) for h in h0)
+    both = np.union1d(first, second)
+    return first, both, np.intersect1d(third, both)
+
+
+def sparse_bytes(idx):
+    "(byte offsets, byte values) of the filter that holds exactly the bits of the sorted distinct indices idx: its non-zero bytes"
+    byte = (idx >> np.uint64(3)).astype(np.int64)
+    bit = np.left_shift(np.uint8(1), (idx & np.uint64(7)).astype(np.uint8))
+    first = np.flatnonzero(np.concatenate(([True], byte[1:] != byte[:-1])))
+    return byte[first], np.bitwise_or.reduceat(bit, first)

@@ -10,6 +10,7 @@ import pytest
 
 from ntsynt_amd import _lib
 from ntsynt_amd.device import BF_BIN_PLAN_FIELDS, bf_bin_plan
+from tests.test_gpu_bloom_geometry import SWITCHES
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BUCKET_BYTES = 65536                      # a final bucket: 2^19 filter bits
@@ -126,3 +127,12 @@ def test_the_grid_switch_is_not_in_the_product_build():
         with open(os.path.join(ROOT, "ntsynt_amd", lib), "rb") as fh:
             return b"NTS_BIN1_GRID" in fh.read()
     assert holds("libntsynt_hip_exp.so") and not holds("libntsynt_hip.so")
+
+
+@pytest.mark.parametrize("switch", SWITCHES)
+def test_no_switch_of_the_bloom_tests_is_in_the_product_build(switch):
+    "every switch the GPU tests of the partitioned build set (NTS_BIN_IDX32 among them: the 64-bit place on a small genome): in the experiments build alone"
+    def holds(lib):
+        with open(os.path.join(ROOT, "ntsynt_amd", lib), "rb") as fh:
+            return switch.encode("ascii") in fh.read()
+    assert "NTS_BIN_IDX32" in SWITCHES and holds("libntsynt_hip_exp.so") and not holds("libntsynt_hip.so")

@@ -138,6 +138,95 @@ def test_geometry_cases_hold_their_claims(nbytes):
     assert p["n_final"] - p["F"] == {513: 1, 1025: 3, 8193: 31}.get(p["F"], 0)          # final buckets behind the filter's end
 
 
+# ---- the inputs of tests/test_gpu_bloom_large.py ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(BC.SECOND_TRIP))
+def test_second_trip_cases_fill_a_final_bucket_past_one_round_of_k_bin3(name):
+    """every genome of the case -- the first (store-only), the second (read-and-OR) and the relative (the AND finishes) -- fills a final
+    bucket past one trip of k_bin3's load loop; without the repeats nothing is clamped, with them (the first genome and its relative)
+    a level-1 bucket overflows cap1 > 16384"""
+    (records, k, nbytes, c), (second, relative) = BC.second_trip_case(name)
+    assert (nbytes, k) == (BC.SECOND_TRIP[name][0], BC.SECOND_TRIP_K)
+    shape = {"one_bucket": (1, 0, 1), "two_buckets": (2, 0, 2), "two_buckets_over": (2, 0, 2), "packed": (513, 1, 257)}[name]
+    for genome, over in ((records, c["overflow"]), (second, False), (relative, c["overflow"])):
+        h0 = BC.hashes(genome, k)
+        idx = h0 % np.uint64(nbytes * 8)
+        p = bf_bin_plan(h0.size, nbytes, k)
+        assert (p["F"], p["log2_b2"], p["B1"]) == shape and p["idx32"] == 1, c["shape"]
+        final = np.bincount((idx >> np.uint64(BC.FINAL_SHIFT)).astype(np.int64), minlength=p["n_final"])
+        level1 = np.bincount((idx >> np.uint64(BC.FINAL_SHIFT + p["log2_b2"])).astype(np.int64), minlength=p["B1"])
+        assert final.size == p["n_final"] and level1.size == p["B1"]
+        if name == "packed":
+            # a second trip: more than 8192 words, i.e. more than 3 * 8192 residues whatever the partial words (here: every whole bucket)
+            assert p["cap2"] > BC.BIN3_TRIP_WORDS and final[:p["F"] - 1].min() > 3 * BC.BIN3_TRIP_WORDS
+            partial_words = (h0.size // p["B1"] + 1) // T + 2          # one partly filled word per tile of the level-1 bucket
+            assert final.max() <= 3 * (p["cap2"] - partial_words) and level1.max() <= p["cap1"]          # nothing clamped
+        elif over:
+            assert BC.REPEATS[0] in genome and BC.REPEATS[1] in genome
+            assert p["cap1"] > BC.BIN3_TRIP_RESIDUES and level1.max() > p["cap1"]                       # n = cap1, the rest set directly
+            assert level1.min() > BC.BIN3_TRIP_RESIDUES
+        else:
+            assert 26400 < p["cap1"] < 26700 and level1.max() <= p["cap1"]                              # 1.125 * mean1 + 4096: unclamped
+            assert final[:p["F"]].min() > BC.BIN3_TRIP_RESIDUES and final.max() < 2 * BC.BIN3_TRIP_RESIDUES   # two trips, the second partial
+    assert not any(rep in second for rep in BC.REPEATS)
+
+
+LARGE_PLANS = {        # nbytes -> (F, log2_b2, B2, B1, n_final)
+    (1 << 30) + 8: (16385, 6, 64, 257, 16448),
+    (1 << 31) + 8: (32769, 7, 128, 257, 32896),
+    (1 << 32) + 8: (65537, 8, 256, 257, 65792),
+    (1 << 33) + 8: (131073, 9, 512, 257, 131584),
+    1 << 34: (262144, 9, 512, 512, 262144),
+    16391 * 65536 + 40013: (16392, 6, 64, 257, 16448),
+    131079 * 65536 + 40013: (131080, 9, 512, 257, 131584),
+}
+
+
+def test_large_geometries_are_what_the_table_says():
+    "log2_b2 = 6 .. 9 at B1 = 257, the largest geometry, and the two sizes whose last level-1 bucket is partly real and is hit"
+    assert set(BC.LARGE) == set(LARGE_PLANS) and set(BC.LARGE_PARTLY_REAL) == {16391 * 65536 + 40013, 131079 * 65536 + 40013}
+    base = BC.large_base()
+    sizes = [h.size for h in base["h0"]]
+    assert 1_900_000 < sizes[0] < 2_100_000 and sizes[1] > 0 and sizes[2] == sizes[0]
+    for nbytes, want in LARGE_PLANS.items():
+        for V in sizes:
+            p = bf_bin_plan(V, nbytes, BC.LARGE_K)
+            assert (p["F"], p["log2_b2"], p["B2"], p["B1"], p["n_final"]) == want, BC.LARGE[nbytes]
+            assert p["idx32"] == 1
+    assert {LARGE_PLANS[n][1] for n in LARGE_PLANS} == {6, 7, 8, 9}
+    for nbytes in BC.LARGE_PARTLY_REAL:
+        F, log2_b2, B2, B1, n_final = LARGE_PLANS[nbytes]
+        assert F - (B1 - 1) * B2 == 8 and n_final - F == B2 - 8 and nbytes % 65536 != 0 and nbytes % 4 != 0
+        for h0 in (base["h0"][0], base["h0"][2]):                 # the first genome and its relative: the AND keeps bits there
+            idx = h0 % np.uint64(nbytes * 8)
+            assert int(idx.max()) < nbytes * 8
+            assert int(((idx >> np.uint64(BC.FINAL_SHIFT + log2_b2)) == B1 - 1).sum()) >= 64
+            assert int(((idx >> np.uint64(BC.FINAL_SHIFT)) == F - 1).sum()) >= 1
+        first, both, kept = BC.sparse_reference(base["h0"], nbytes)
+        assert int((kept >> np.uint64(BC.FINAL_SHIFT) == F - 1).sum()) >= 1
+
+
+def test_the_sparse_reference_is_the_oracle_filter():
+    """3 MiB + 12 bytes: the non-zero bytes rebuilt from the index sets (bloom_cases.sparse_reference, sparse_bytes) are O.bf_build's
+    filter after insert, OR and cascade -- byte for byte, and the number of indices is its popcount"""
+    from tests.helpers import to_oracle
+    nbytes, k = 3 * BC.MIB + 12, BC.GEOMETRY_K
+    base = BC.geometry_base()
+    genomes = (base["seqs"], base["second"], base["relative"])
+    og = [to_oracle([f"r{i}" for i in range(len(g))], g) for g in genomes]
+    dense = [O.bf_build(og[0], k, nbytes)]
+    dense.append(dense[0] | O.bf_build(og[1], k, nbytes))
+    dense.append(O.bf_build(og[2], k, nbytes, prev=dense[1]))
+    sparse = BC.sparse_reference([BC.hashes(g, k) for g in genomes], nbytes)
+    for what, want, idx in zip(("insert", "or", "cascade"), dense, sparse):
+        assert idx.dtype == np.uint64 and np.all(idx[1:] > idx[:-1]), what
+        off, val = BC.sparse_bytes(idx)
+        assert off.dtype == np.int64 and val.dtype == np.uint8
+        assert np.array_equal(off, np.flatnonzero(want)), what
+        assert np.array_equal(val, want[off]), what
+        assert idx.size == O.bf_popcount(want) > 0, what
+    assert sparse[0].size < sparse[1].size and 0 < sparse[2].size < sparse[0].size
+
+
 @pytest.mark.parametrize("cus", [4, 256])
 def test_product_case_breaks_three_turns_of_two_workgroups(cus):
     records, k, nbytes, c = BC.product_case(cus)

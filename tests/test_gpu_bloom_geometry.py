@@ -20,7 +20,7 @@ from tests.helpers import to_device, to_oracle
 
 pytestmark = pytest.mark.gpu
 STEP_SECONDS = 300
-SWITCHES = ("NTS_BIN1_GRID", "NTS_BIN_STORE", "NTS_BIN_LATE_CAP")
+SWITCHES = ("NTS_BIN1_GRID", "NTS_BIN_STORE", "NTS_BIN_LATE_CAP", "NTS_BIN_IDX32")
 
 
 @pytest.fixture(autouse=True)
