@@ -1185,6 +1185,47 @@ int nts_cigar_alleles(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, con
                       uint64_t n_groups, const uint8_t* alt, uint64_t n_alt, nts_cig_allele** alleles, uint64_t* allele_first, uint32_t** carriers,
                       uint64_t* n_carriers);
 
+/* ---- per-column profile and consensus over a star alignment: `--block-consensus` ------------------------------------------------------
+ * nts_cigar_profile: cigar, chains (they TILE the entries and are CORES) and at[c] = {group, t0} as for nts_cigar_alleles; ref, n_ref and
+ *   alt, n_alt: the ref and alt bytes of nts_cigar_var_bases over ALL chains in chain order (row A at the X and D columns, row B at the
+ *   X and I columns).  Chains of one group may overlap freely; the call does not know rows, every count is a count of chains.  The
+ *   COLUMNS of group g are (pos, sub): sub = i < W(g, pos) is the i-th column of the slot in front of reference base pos (nts_cigar_pad's
+ *   slots and widths), sub = NTS_CIG_PROFILE_REF is base pos itself; ascending (group, pos, sub) is the multi-MAF's column order.  Chain
+ *   j COVERS column and slot p when t0 <= p < t0 + len_a (nts_cigar_pad's rule: a foreign site at t0 gives the chain a leading P, the
+ *   slot at t1 belongs to no chain).  A reference column: aligned, match, gap as nts_cigar_depth's; n[s], s = A C G T N: the covering
+ *   chains with an X there whose alt byte is that letter (any other byte counts under N); match + gap + sum n = aligned; ref: the ref
+ *   byte there of the covering chain of smallest index with an X or D (that two chains agree is not checked).  An insertion column
+ *   (p, i): aligned = the chains covering slot p; n[s]: those that hold an I entry longer than i in the slot whose i-th byte is s;
+ *   gap = aligned - sum n; match = 0; ref = '-'.  CALL: the tallies include the reference row -- on a reference column
+ *   t[ref's symbol] = n[that] + match + 1 (a byte outside ACGT: N) and t[-] = gap, on an insertion column t[-] = gap + 1 --; call is one
+ *   of "ACGTN-", the symbol of the largest tally; among several the reference's symbol if it is one of them, else the first of A C G T
+ *   N -.  EMITTED: every insertion column of every site and every reference column with match < aligned, once each; all others are
+ *   unanimous.  Two neighbouring I or D entries of one chain: a precondition, as for nts_cigar_pad, that they do not occur; not
+ *   checked.  Split X or D entries give the records of the merged one.
+ *   Out: *cols (release with nts_free; NULL when there is none) ascending by (group, pos, sub), group g's being [col_first[g],
+ *   col_first[g + 1]) (n_groups + 1 host entries).  No genome is read.  Refusals: nts_cigar_alleles', with the same words, before any
+ *   launch and behind the first scan; behind the scan also NTS_EINVAL "alt holds N bytes, the X and I entries of the chains have M",
+ *   "ref holds N bytes, the X and D entries of the chains have M" and NTS_ERANGE for 2^32 events or more.  A refused call returns no
+ *   buffer and writes to no caller array.  One exclusive scan over the entries (A bases, B bases, events -- one per column of an X, D
+ *   or I entry --, ref bytes, alt bytes) and nts_cigar_lift's check; one lane per event stores two key words, two stable radix sorts;
+ *   one lane per chain stores where it begins and ends, two radix sorts (timer "cigar_profile_events"); one lane per sorted event
+ *   marks the heads, one scan ranks them, one lane per column counts its symbols by lower-bound searches inside its run, its covering
+ *   chains by two searches over the chains' sorted ends, and stores the whole record, reserved bytes included (timer
+ *   "cigar_profile_emit").  Entries alone: no launch; no event: no launch behind the scan.  On the context's stream, in its workspace;
+ *   no atomic, no launch per chain, group, site or column, no floating point: the same input gives the same bytes.
+ *   docs/design/04_33_block_consensus.md; csrc/nts_cigar.inc; ntsynt_amd/assess.py block_consensus. */
+#define NTS_CIG_PROFILE_REF 0xFFFFFFFFu
+typedef struct
+{
+  uint64_t pos;                          /* reference base; for sub != NTS_CIG_PROFILE_REF the slot in front of it */
+  uint32_t group, sub, aligned, match, gap;
+  uint32_t n[5];                         /* A C G T N */
+  uint8_t ref, call, reserved[6];        /* a letter or '-'; reserved: 0 */
+} nts_cig_profile_col;
+int nts_cigar_profile(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains, const nts_cig_pad_at* at,
+                      uint64_t n_groups, const uint8_t* ref, uint64_t n_ref, const uint8_t* alt, uint64_t n_alt, nts_cig_profile_col** cols,
+                      uint64_t* col_first);
+
 /* ---- C1-C5: minimizer graph -> collinear chains -----------------------------------------------------
  * replaces ntjoin_utils.read_minimizers' duplicate removal, filter_minimizers and build_graph
  * (call sites bin/ntsynt_synteny.py:607-612, 483, 539) and the path walk of Ntjoin.find_paths

@@ -108,6 +108,12 @@ class CigAllele(ctypes.Structure):
                 ("reserved", u32)]
 
 
+class CigProfileCol(ctypes.Structure):
+    "nts_cig_profile_col: one variable column of a group's star alignment with its counts, reference byte and call (nts_cigar_profile)"
+    _fields_ = [("pos", u64), ("group", u32), ("sub", u32), ("aligned", u32), ("match", u32), ("gap", u32), ("n", u32 * 5), ("ref", ctypes.c_uint8),
+                ("call", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 6)]
+
+
 class LiftQuery(ctypes.Structure):
     "nts_lift_query: an offset on one side of a chain (nts_cigar_lift)"
     _fields_ = [("chain", u32), ("side", u32), ("pos", u64)]
@@ -333,6 +339,7 @@ SYMBOLS = [
     ("nts_cigar_var_bases", ctypes.c_int, [c_vp, c_vp, u64, c_vp, u64, c_vp, c_vp, c_vp, ctypes.POINTER(c_vp), c_vp, ctypes.POINTER(c_vp), c_vp]),
     ("nts_cigar_alleles", ctypes.c_int, [c_vp, c_vp, u64, c_vp, u64, c_vp, u64, c_vp, u64, ctypes.POINTER(c_vp), c_vp, ctypes.POINTER(c_vp),
                                          ctypes.POINTER(u64)]),
+    ("nts_cigar_profile", ctypes.c_int, [c_vp, c_vp, u64, c_vp, u64, c_vp, u64, c_vp, u64, c_vp, u64, ctypes.POINTER(c_vp), c_vp]),
     ("nts_genome_valid_bases", ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(Interval), u64, c_vp]),
     ("nts_minhash_pairs", ctypes.c_int, [c_vp, u32, c_vp, c_vp, u64, c_vp, c_vp, u64, c_vp, c_vp]),
     ("nts_graph_build", ctypes.c_int, [c_vp, u32, ctypes.POINTER(MxList), ctypes.POINTER(Graph)]),

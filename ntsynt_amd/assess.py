@@ -29,6 +29,9 @@ Two things, both over `<prefix>.synteny_blocks.tsv`:
 * block variant sites (`ntSynt --block-variant-sites`, `ntsynt_block_stats --variant-sites-out`): per block the reference positions at
   which the other genomes differ, one line per allele with its carriers and one genotype character per row, the bases and the allele
   table made on the GPU (nts_cigar_var_bases, nts_cigar_alleles); docs/design/04_32_block_variant_sites.md.
+* block consensus (`ntSynt --block-consensus`, `ntsynt_block_stats --profile-out --consensus-out`): per block one line per variable column
+  of its star alignment, insertion columns included, with the tallies of A C G T N and the gap and the plurality call, made on the GPU
+  (nts_cigar_profile), and the block's first line with the calls applied; docs/design/04_33_block_consensus.md.
 * block chain file (`ntSynt --block-chain`, `ntsynt_block_stats --chain-out`): one UCSC liftover chain per block and pair, the chains of the
   block alignments joined per pair, blocks and data lines made on the GPU (nts_cigar_chain_blocks); docs/design/04_28_block_chain.md.
 * block alignments (`ntSynt --block-paf`, `ntsynt_block_stats --paf-out`): one PAF record with a cg:Z: CIGAR per aligned chain of every
@@ -1602,23 +1605,14 @@ def variant_sites_table(groups, alleles, ref, alt, genotypes, k, rate, band, max
     return "\n".join(["\t".join(VARIANT_SITES_COLUMNS)] + lines + [_conservation_parameters(k, rate, band, max_len, max_edits, ends)]) + "\n"
 
 
-def block_variant_sites(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_RATE, band=IDENTITY_BAND, max_len=IDENTITY_MAX_LEN, max_edits=0, ends=None):
-    """Per synteny block the positions of its first line at which the other genomes differ, with which allele, and which of them share
-    it (docs/design/04_32_block_variant_sites.md): the core chains of the star pairs (_star_cores) give, per pair of genomes, ONE
-    nts_cigar_var_bases -- the bases at the X, D and I columns --, whose bytes are scattered into chain order, and ONE
-    nts_cigar_alleles over all chains.  Genomes given as callables are loaded a second time for the bases, each query one at a time
-    beside the reference's genome.  The first group's alleles and carriers are recomputed on the host (alleles_host) and compared:
-    RuntimeError.  Returns (groups, alleles, ref, alt, genotypes): per block, in block_identity.tsv's order, (block_id, genome, contig,
-    start, end, rows) of its first line; the CIG_ALLELE_DTYPE alleles in the device's order, the two byte buffers their offsets count in
-    and variant_site_genotypes' strings: what variant_sites_table takes."""
+def _star_var_bases(ctx, genomes_by_name, blocks, held, entries, records):
+    """The ref and alt bytes of _star_cores' chains in chain order, as nts_cigar_alleles and nts_cigar_profile take them: ONE
+    nts_cigar_var_bases per pair of genomes over that pair's cores, the pairs' bytes scattered into chain order with one fancy-indexed
+    store per pair and buffer.  Genomes given as callables are loaded for the bases, each query one at a time beside the reference's
+    genome.  Returns (ref, ref_first, alt, alt_first): the bytes and where every chain's begin, the prefixes of the chains' X + D and
+    X + I lengths (int64, len(held) + 1), which the device's firsts must agree with: RuntimeError."""
     import numpy as np
-    from .device import CIG_ALLELE_DTYPE, CIG_SPAN_DTYPE
-    n_groups, held, entries, records, at = _star_cores(ctx, genomes_by_name, blocks, k, rate, band, max_len, max_edits, ends)
-    groups = [(b, blocks[lines[0]].genome, blocks[lines[0]].contig, blocks[lines[0]].start, blocks[lines[0]].end, len(lines) - 1)
-              for b, lines in _block_order(blocks)]
-    none = np.zeros(0, dtype=np.uint8)
-    if not held:
-        return groups, np.zeros(0, dtype=CIG_ALLELE_DTYPE), none, none, []
+    from .device import CIG_SPAN_DTYPE
     code, size = (entries & np.uint64(15)).astype(np.int64), (entries >> np.uint64(4)).astype(np.int64)
     cut = np.concatenate((records["first"].astype(np.int64), [entries.size]))
     sums = [np.concatenate(([0], np.cumsum(np.where(np.isin(code, which), size, 0))))[cut] for which in ((8, 2), (8, 1))]
@@ -1659,6 +1653,28 @@ def block_variant_sites(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTIT
     finally:
         for name in list(loaded):
             release(name)
+    return ref, ref_first, alt, alt_first
+
+
+def block_variant_sites(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_RATE, band=IDENTITY_BAND, max_len=IDENTITY_MAX_LEN, max_edits=0, ends=None):
+    """Per synteny block the positions of its first line at which the other genomes differ, with which allele, and which of them share
+    it (docs/design/04_32_block_variant_sites.md): the core chains of the star pairs (_star_cores) give, per pair of genomes, ONE
+    nts_cigar_var_bases -- the bases at the X, D and I columns --, whose bytes are scattered into chain order, and ONE
+    nts_cigar_alleles over all chains.  Genomes given as callables are loaded a second time for the bases, each query one at a time
+    beside the reference's genome.  The first group's alleles and carriers are recomputed on the host (alleles_host) and compared:
+    RuntimeError.  Returns (groups, alleles, ref, alt, genotypes): per block, in block_identity.tsv's order, (block_id, genome, contig,
+    start, end, rows) of its first line; the CIG_ALLELE_DTYPE alleles in the device's order, the two byte buffers their offsets count in
+    and variant_site_genotypes' strings: what variant_sites_table takes."""
+    import numpy as np
+    from .device import CIG_ALLELE_DTYPE
+    n_groups, held, entries, records, at = _star_cores(ctx, genomes_by_name, blocks, k, rate, band, max_len, max_edits, ends)
+    groups = [(b, blocks[lines[0]].genome, blocks[lines[0]].contig, blocks[lines[0]].start, blocks[lines[0]].end, len(lines) - 1)
+              for b, lines in _block_order(blocks)]
+    none = np.zeros(0, dtype=np.uint8)
+    if not held:
+        return groups, np.zeros(0, dtype=CIG_ALLELE_DTYPE), none, none, []
+    ref, ref_first, alt, alt_first = _star_var_bases(ctx, genomes_by_name, blocks, held, entries, records)
+    cut = np.concatenate((records["first"].astype(np.int64), [entries.size]))
     alleles, allele_first, carriers = ctx.cigar_alleles(entries, records, at, alt, n_groups)
     g0 = int(at["group"][0])                                  # the spot check: the first group that has chains
     mine = np.flatnonzero(at["group"] == g0)
@@ -1676,6 +1692,211 @@ def block_variant_sites(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTIT
     genotypes = variant_site_genotypes(alleles, carriers, [h[1] for h in held], t0, t0 + records["len_a"].astype(np.int64), [g[5] for g in groups],
                                        at["group"].astype(np.int64))
     return groups, alleles, ref, alt, genotypes
+
+
+# ---- block consensus: per-column profile and consensus over the star alignment (docs/design/04_33_block_consensus.md) ----
+
+PROFILE_COLUMNS = ("contig", "pos", "sub", "block_id", "genome", "rows", "depth", "ref", "A", "C", "G", "T", "N", "gap", "call")
+PROFILE_SYMBOLS = "ACGTN-"
+
+
+def _profile_symbols(byte):
+    "A C G T -> 0 .. 3, every other byte -> 4 (N), `-` -> 5: per element of a uint8 array"
+    import numpy as np
+    table = np.full(256, 4, dtype=np.int64)
+    table[[ord(c) for c in "ACGT-"]] = [0, 1, 2, 3, 5]
+    return table[np.asarray(byte, dtype=np.uint8)]
+
+
+def _profile_tallies(cols):
+    "[columns, 6] int64: the tallies of A C G T N - with the reference row counted in, as nts_cigar_profile's call reads them"
+    import numpy as np
+    from .device import CIG_PROFILE_REF
+    tally = np.concatenate((cols["n"].astype(np.int64).reshape(-1, 5), cols["gap"].astype(np.int64)[:, None]), axis=1)
+    is_ref = cols["sub"] == CIG_PROFILE_REF
+    own = np.where(is_ref, np.minimum(_profile_symbols(cols["ref"]), 4), 5)          # (a reference byte that is no base counts under N)
+    tally[np.arange(cols.size), own] += np.where(is_ref, cols["match"].astype(np.int64), 0) + 1
+    return tally
+
+
+def profile_host(entries, records, at, ref, alt):
+    """nts_cigar_profile's columns of ONE group on the host.  entries, records, at: that group's chains (the records' `first` index
+    `entries`; the chains tile them); ref, alt: their ref and alt bytes, chain after chain.  Events -- one per column of an X, D or I
+    entry -- are made with np.repeat over the entries, `aligned` is a difference array over the group's reference extent, the
+    per-symbol counts are np.unique over (pos, sub, symbol), the reference byte of a column is that of its first event (events are in
+    chain order).  Returns a CIG_PROFILE_COL_DTYPE array in the device's order with group 0.  Array operations over entries, events
+    and bases; the spot check of block_consensus and the baseline of scripts/block_consensus_measure.py.  Pure."""
+    import numpy as np
+    from .device import CIG_PROFILE_COL_DTYPE, CIG_PROFILE_REF
+    entries = np.ascontiguousarray(entries, dtype=np.uint64)
+    ref, alt = np.ascontiguousarray(ref, dtype=np.uint8), np.ascontiguousarray(alt, dtype=np.uint8)
+    code, size = (entries & np.uint64(15)).astype(np.int64), (entries >> np.uint64(4)).astype(np.int64)
+    n_cig, t0, len_a = records["n_cig"].astype(np.int64), at["t0"].astype(np.int64), records["len_a"].astype(np.int64)
+    is_x, is_d, is_i = code == 8, code == 2, code == 1
+    count = np.where(is_x | is_d | is_i, size, 0)
+    n_ev = int(count.sum())
+    if n_ev == 0:
+        return np.zeros(0, dtype=CIG_PROFILE_COL_DTYPE)
+    chain_of = np.repeat(np.arange(n_cig.size), n_cig)        # (the chains tile the entries)
+    first_of = np.concatenate(([0], np.cumsum(n_cig)))[chain_of]
+    before = [np.concatenate(([0], np.cumsum(np.where(which, size, 0)))) for which in (~is_i, is_x | is_d, is_x | is_i)]   # A bases, ref bytes, alt bytes
+    begin = t0[chain_of] + before[0][:-1] - before[0][first_of]
+    ev_entry = np.repeat(np.arange(entries.size), count)
+    off = np.arange(n_ev) - np.concatenate(([0], np.cumsum(count)))[ev_entry]
+    ins, gone = is_i[ev_entry], is_d[ev_entry]
+    pos = begin[ev_entry] + np.where(ins, 0, off)
+    sub = np.where(ins, off, CIG_PROFILE_REF)
+    symbol = np.full(n_ev, 5, dtype=np.int64)
+    symbol[~gone] = np.minimum(_profile_symbols(alt[(before[2][ev_entry] + off)[~gone]]), 4)
+    ref_at = before[1][ev_entry] + off                       # (of an X or D event)
+    keys, counts = np.unique(np.stack((pos, sub, symbol), axis=1), axis=0, return_counts=True)
+    columns, lead, of_column = np.unique(np.stack((pos, sub), axis=1), axis=0, return_index=True, return_inverse=True)
+    column_of_key = np.unique(keys[:, :2], axis=0, return_inverse=True)[1].reshape(-1)
+    held = np.zeros((columns.shape[0], 6), dtype=np.int64)
+    held[column_of_key, keys[:, 2]] = counts
+    r0, r1 = int(t0.min()), int((t0 + len_a).max())
+    diff = np.zeros(r1 - r0 + 1, dtype=np.int64)
+    np.add.at(diff, t0 - r0, 1)
+    np.add.at(diff, t0 + len_a - r0, -1)
+    aligned = np.cumsum(diff)[columns[:, 0] - r0]
+    out = np.zeros(columns.shape[0], dtype=CIG_PROFILE_COL_DTYPE)
+    is_ref = columns[:, 1] == CIG_PROFILE_REF
+    out["pos"], out["sub"], out["aligned"] = columns[:, 0], columns[:, 1], aligned
+    out["n"] = held[:, :5]
+    out["gap"] = np.where(is_ref, held[:, 5], aligned - held[:, :5].sum(axis=1))
+    out["match"] = np.where(is_ref, aligned - held.sum(axis=1), 0)
+    out["ref"] = ord("-")
+    if np.any(is_ref):
+        out["ref"][is_ref] = ref[ref_at[lead[is_ref]]]
+    tally = _profile_tallies(out)
+    own = np.where(is_ref, np.minimum(_profile_symbols(out["ref"]), 4), 5)
+    best = np.argmax(tally, axis=1)                           # (the first of A C G T N - among the largest)
+    rows = np.arange(out.size)
+    best = np.where(tally[rows, own] == tally[rows, best], own, best)
+    out["call"] = np.frombuffer(PROFILE_SYMBOLS.encode(), dtype=np.uint8)[best]
+    return out
+
+
+def block_consensus(ctx, genomes_by_name, blocks, k=IDENTITY_K, rate=IDENTITY_RATE, band=IDENTITY_BAND, max_len=IDENTITY_MAX_LEN, max_edits=0, ends=None):
+    """Per synteny block what the majority of its genomes hold at every variable column of its star alignment
+    (docs/design/04_33_block_consensus.md): the core chains of the star pairs (_star_cores), their ref and alt bytes (_star_var_bases, as
+    block_variant_sites makes them) and ONE nts_cigar_profile over all chains.  The columns of the first group that has chains are
+    recomputed on the host (profile_host) and compared field by field: RuntimeError.  Returns (groups, cols, col_first, extents): per
+    block, in block_identity.tsv's order, (block_id, genome, contig, start, end, rows) of its first line; the CIG_PROFILE_COL_DTYPE
+    columns and where each block's begin; and per block (R0, R1), the smallest t0 and the largest t1 of its chains, None for a block
+    without chains: what profile_table, consensus_reference_bases and consensus_fasta take."""
+    import numpy as np
+    from .device import CIG_PROFILE_COL_DTYPE
+    n_groups, held, entries, records, at = _star_cores(ctx, genomes_by_name, blocks, k, rate, band, max_len, max_edits, ends)
+    groups = [(b, blocks[lines[0]].genome, blocks[lines[0]].contig, blocks[lines[0]].start, blocks[lines[0]].end, len(lines) - 1)
+              for b, lines in _block_order(blocks)]
+    if not held:
+        return groups, np.zeros(0, dtype=CIG_PROFILE_COL_DTYPE), np.zeros(n_groups + 1, dtype=np.uint64), [None] * n_groups
+    ref, ref_first, alt, alt_first = _star_var_bases(ctx, genomes_by_name, blocks, held, entries, records)
+    cols, col_first = ctx.cigar_profile(entries, records, at, ref, alt, n_groups)
+    group_of, t0 = at["group"].astype(np.int64), at["t0"].astype(np.int64)
+    t1 = t0 + records["len_a"].astype(np.int64)
+    cut = np.searchsorted(group_of, np.arange(n_groups + 1))
+    extents = [(int(t0[lo:hi].min()), int(t1[lo:hi].max())) if hi > lo else None for lo, hi in zip(cut[:-1].tolist(), cut[1:].tolist())]
+    g0 = int(group_of[0])                                     # the spot check: the first group that has chains
+    mine = np.arange(int(cut[g0]), int(cut[g0 + 1]))
+    sub = records[mine].copy()
+    sub["first"] -= records["first"][mine[0]]
+    lo, hi = int(records["first"][mine[0]]), int(records["first"][mine[-1]] + records["n_cig"][mine[-1]])
+    host = profile_host(entries[lo:hi], sub, at[mine], ref[int(ref_first[mine[0]]):int(ref_first[mine[-1] + 1])],
+                        alt[int(alt_first[mine[0]]):int(alt_first[mine[-1] + 1])])
+    got = cols[int(col_first[g0]):int(col_first[g0 + 1])]
+    if got.size != host.size or np.any(got["group"] != g0) or \
+            any(not np.array_equal(got[f], host[f]) for f in ("pos", "sub", "aligned", "match", "gap", "n", "ref", "call", "reserved")):
+        raise RuntimeError(f"block {groups[g0][0]}: the device's {got.size} profile columns differ from the host's {host.size}")
+    return groups, cols, col_first, extents
+
+
+def consensus_reference_bases(genomes_by_name, groups, extents):
+    """The upper-case reference bytes [R0, R1) of every group that has chains, None for the others: one read per group (_genome_bases)
+    from the record named by the group's contig.  A genome given as a callable is loaded for its groups and freed behind them."""
+    by_genome = {}
+    for g, (group, extent) in enumerate(zip(groups, extents)):
+        if extent is not None:
+            by_genome.setdefault(group[1], []).append(g)
+    out = [None] * len(groups)
+    for name, members in by_genome.items():
+        source = genomes_by_name[name]
+        genome = source() if callable(source) else source
+        try:
+            record = {contig: r for r, contig in enumerate(genome.names)}
+            for g in members:
+                out[g] = _genome_bases(genome, record[groups[g][2]], extents[g][0], extents[g][1] - extents[g][0])
+        finally:
+            if callable(source):
+                genome.free()
+    return out
+
+
+def consensus_sequences(groups, cols, col_first, extents, reference_bases):
+    """Per group its reference bases [R0, R1) with the calls of its columns applied, as a str; None for a group without chains.
+    reference_bases[g]: the upper-case bytes of the group's [R0, R1) (consensus_reference_bases).  A reference column whose call is a
+    letter replaces the base, one whose call is `-` drops it; an insertion column whose call is a letter is inserted in front of base
+    pos, in sub order, one whose call is `-` adds nothing; every other base keeps the reference's letter.  Array operations over one
+    group's columns and bases: one np.insert and one mask per group.  Pure."""
+    import numpy as np
+    from .device import CIG_PROFILE_REF
+    col_first = np.asarray(col_first, dtype=np.int64)
+    out = []
+    for g, extent in enumerate(extents):
+        if extent is None:
+            out.append(None)
+            continue
+        bases = np.array(reference_bases[g], dtype=np.uint8)
+        if bases.size != extent[1] - extent[0]:
+            raise ValueError(f"consensus_sequences: group {g} has {bases.size} reference bytes for [{extent[0]}, {extent[1]})")
+        mine = cols[int(col_first[g]):int(col_first[g + 1])]
+        at = mine["pos"].astype(np.int64) - extent[0]
+        is_ref, gap = mine["sub"] == CIG_PROFILE_REF, mine["call"] == ord("-")
+        keep = np.ones(bases.size, dtype=bool)
+        bases[at[is_ref & ~gap]] = mine["call"][is_ref & ~gap]
+        keep[at[is_ref & gap]] = False
+        more = ~is_ref & ~gap                                 # (ascending by (pos, sub): np.insert keeps that order in front of one base)
+        bases, keep = np.insert(bases, at[more], mine["call"][more]), np.insert(keep, at[more], True)
+        out.append(bases[keep].tobytes().decode())
+    return out
+
+
+def consensus_fasta(groups, cols, col_first, extents, reference_bases):
+    """The text of `<prefix>.block_consensus.fa`: per group that has chains, in block_identity.tsv's block order, the header
+    `>block_<id> <genome>.<contig>:<R0>-<R1> rows=<rows> columns=<its emitted columns> changed=<those with call != ref>` and one
+    unwrapped line, consensus_sequences' sequence.  Pure."""
+    import numpy as np
+    col_first = np.asarray(col_first, dtype=np.int64)
+    lines = []
+    for g, (group, extent, text) in enumerate(zip(groups, extents, consensus_sequences(groups, cols, col_first, extents, reference_bases))):
+        if extent is None:
+            continue
+        mine = cols[int(col_first[g]):int(col_first[g + 1])]
+        lines.append(f">block_{group[0]} {group[1]}.{group[2]}:{extent[0]}-{extent[1]} rows={group[5]} columns={mine.size} "
+                     f"changed={int(np.count_nonzero(mine['call'] != mine['ref']))}")
+        lines.append(text)
+    return "\n".join(lines) + "\n" if lines else ""
+
+
+def profile_table(groups, cols, col_first, k, rate, band, max_len, max_edits=0, ends=None):
+    """The text of `<prefix>.block_profile.tsv`: a header, one line per column -- PROFILE_COLUMNS: the reference contig, the 0-based
+    position, the column inside the slot in front of it (`.` for the reference base itself), the block, the reference genome, the
+    block's rows, depth = aligned + 1, the reference's letter or `-`, the six tallies with the reference row counted in (they add up to
+    depth) and the call -- then the `#` line with the parameters.  Integers only.  Columns are made as arrays and joined once per
+    line.  Pure."""
+    import numpy as np
+    from .device import CIG_PROFILE_REF
+    col_first = np.asarray(col_first, dtype=np.int64)
+    group = np.repeat(np.arange(len(groups)), col_first[1:] - col_first[:-1])
+    of_group = [np.array([str(g[f]) for g in groups], dtype=object)[group] if len(groups) else np.zeros(0, dtype=object) for f in (2, 0, 1, 5)]
+    tally = _profile_tallies(cols)
+    sub = np.where(cols["sub"] == CIG_PROFILE_REF, ".", cols["sub"].astype(np.int64).astype(str).astype(object))
+    letters = [np.asarray(cols[f], dtype=np.uint8).tobytes().decode() for f in ("ref", "call")]
+    columns = [of_group[0], cols["pos"].astype(np.int64), sub, of_group[1], of_group[2], of_group[3], cols["aligned"].astype(np.int64) + 1,
+               list(letters[0])] + [tally[:, s] for s in range(6)] + [list(letters[1])]
+    lines = ["\t".join(line) for line in zip(*(np.asarray(c, dtype=object).astype(str).tolist() for c in columns))]
+    return "\n".join(["\t".join(PROFILE_COLUMNS)] + lines + [_conservation_parameters(k, rate, band, max_len, max_edits, ends)]) + "\n"
 
 
 LIFT_COLUMNS = ("genome", "contig", "start", "end", "name", "block_id", "to_genome", "to_contig", "to_start", "to_end", "orientation", "ch", "src_start",
@@ -2398,6 +2619,11 @@ def main(argv=None):
     p.add_argument("--variant-sites-out", help="with --fastas: file for the block variant sites (per synteny block one line per allele over the star "
                    "alignment of --multi-maf-out: position on the block's first line, snv / del / ins, the letters, the carriers and one genotype "
                    "character per row; bases and allele table made on the GPU); it takes the parameters of --paf-out; a pass of its own")
+    p.add_argument("--profile-out", help="with --fastas and --consensus-out: file for the block profile (per synteny block one line per variable column "
+                   "of the star alignment of --multi-maf-out, reference bases and insertion columns alike: the tallies of A C G T N and the gap with "
+                   "the reference row counted in, and the plurality call; made on the GPU); it takes the parameters of --paf-out; a pass of its own")
+    p.add_argument("--consensus-out", help="with --profile-out: file for the block consensus (FASTA: per synteny block its first line's bases with the "
+                   "calls applied)")
     p.add_argument("--lift-bed", help="with --fastas, --lift-genome and --lift-out: a BED file of intervals of one genome that are mapped through the block "
                    "alignments into the other genomes (GPU); it takes the parameters of --paf-out")
     p.add_argument("--lift-genome", help="the genome the intervals of --lift-bed lie on: a FASTA base name, as in column 2 of the block table")
@@ -2456,6 +2682,14 @@ def main(argv=None):
     if args.variant_sites_out:
         if not args.fastas:
             p.error("--variant-sites-out needs the genomes: --fastas")
+        message = check_identity_parameters(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits)
+        if message:
+            p.error(message)
+    if bool(args.profile_out) != bool(args.consensus_out):
+        p.error("--profile-out and --consensus-out go together")
+    if args.profile_out:
+        if not args.fastas:
+            p.error("--profile-out needs the genomes: --fastas")
         message = check_identity_parameters(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits)
         if message:
             p.error(message)
@@ -2623,6 +2857,13 @@ def main(argv=None):
             sites = block_variant_sites(ctx, loaders, read_blocks(args.tsv), *id_args, max_edits=args.identity_max_edits, ends=v_ends)
             with open(args.variant_sites_out, "w", encoding="utf-8") as fh:
                 fh.write(variant_sites_table(*sites, *id_args, max_edits=args.identity_max_edits, ends=v_ends))
+        if args.profile_out:                                  # (a pass of its own)
+            f_ends = (args.ends_max_len, args.ends_max_edits, args.ends_penalty) if args.ends_out else None
+            profile = block_consensus(ctx, loaders, read_blocks(args.tsv), *id_args, max_edits=args.identity_max_edits, ends=f_ends)
+            with open(args.profile_out, "w", encoding="utf-8") as fh:
+                fh.write(profile_table(*profile[:3], *id_args, max_edits=args.identity_max_edits, ends=f_ends))
+            with open(args.consensus_out, "w", encoding="utf-8") as fh:
+                fh.write(consensus_fasta(*profile, consensus_reference_bases(loaders, profile[0], profile[3])))
     finally:
         ctx.close()
     if args.divergence_out:

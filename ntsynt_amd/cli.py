@@ -120,6 +120,11 @@ def build_parser():
                    "ins with its letters), the genomes that share it and one genotype character per row, the bases and the allele table made on\n"
                    "the GPU; takes the parameters of --block-paf; works with or without the other block switches; a pass of its own",
                    action="store_true")
+    p.add_argument("--block-consensus", help="after the run, write <prefix>.block_profile.tsv and <prefix>.block_consensus.fa: per synteny block one line\n"
+                   "per variable column of the star alignment of --block-maf-multi -- reference bases and insertion columns alike -- with how\n"
+                   "many genomes hold A, C, G, T, N or a gap there, the reference row counted in, and the plurality call, the tallies made on\n"
+                   "the GPU; and per block its first line's bases with the calls applied; takes the parameters of --block-paf; works with or\n"
+                   "without the other block switches; a pass of its own", action="store_true")
     p.add_argument("--block-lift", metavar="BED", help="after the run, write <prefix>.block_lift.tsv: the intervals of this BED file, which lie on the\n"
                    "genome --lift-genome names, mapped through the alignments of --block-paf into the other genomes, one line per interval\n"
                    "and aligned chain it overlaps; takes the parameters of --block-paf; works with or without the other block switches")
@@ -316,6 +321,15 @@ def check_reports(parser, args):
         message = check_identity_parameters(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits)
         if message:
             parser.error(message)
+    if args.block_consensus:
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            parser.error("--block-consensus works from the genomes resident on one GPU: run it on one rank, or assess the finished run with "
+                         "ntsynt_block_stats --tsv <prefix>.synteny_blocks.tsv --fai ... --fastas ... --profile-out <prefix>.block_profile.tsv "
+                         "--consensus-out <prefix>.block_consensus.fa")
+        from .assess import check_identity_parameters
+        message = check_identity_parameters(args.identity_k, args.identity_rate, args.identity_band, args.identity_max_len, args.identity_max_edits)
+        if message:
+            parser.error(message)
     if args.lift_genome and not args.block_lift and args.lift_windows is None:
         parser.error("--lift-genome names the genome of the intervals of --block-lift BED")
     if args.lift_identity:
@@ -497,6 +511,10 @@ def main(argv=None):
              f"{args.identity_rate}, band {args.identity_band}, max_len {args.identity_max_len}, max_edits {args.identity_max_edits}" +
              (f", ends_max_len {args.ends_max_len}, ends_max_edits {args.ends_max_edits}, ends_penalty {args.ends_penalty}" if args.block_ends else "") + ")"]
             if args.block_variant_sites else []) + \
+           ([f"block_consensus (cigar_var_bases_scan, cigar_var_bases_emit, cigar_profile_events, cigar_profile_emit; k {args.identity_k}, rate "
+             f"{args.identity_rate}, band {args.identity_band}, max_len {args.identity_max_len}, max_edits {args.identity_max_edits}" +
+             (f", ends_max_len {args.ends_max_len}, ends_max_edits {args.ends_max_edits}, ends_penalty {args.ends_penalty}" if args.block_ends else "") + ")"]
+            if args.block_consensus else []) + \
            ([f"block_lift (lift_scan, lift_search; {args.block_lift} on {args.lift_genome}; k {args.identity_k}, rate {args.identity_rate}, band "
              f"{args.identity_band}, max_len {args.identity_max_len}, max_edits {args.identity_max_edits}" +
              (f", ends_max_len {args.ends_max_len}, ends_max_edits {args.ends_max_edits}, ends_penalty {args.ends_penalty}" if args.block_ends else "") + ")"]
@@ -586,6 +604,8 @@ def _run(pipeline, fastas, args, device, quiet):
         more["block_conservation"] = lift_args[1:]
     if args.block_variant_sites:
         more["block_variant_sites"] = lift_args[1:]
+    if args.block_consensus:
+        more["block_consensus"] = lift_args[1:]
     pipeline.run(fastas, **more, k=args.k, w=args.w, fpr=args.fpr, prefix=args.prefix, w_rounds=args.w_rounds,
                  indel=args.indel, merge=args.merge, block_size=args.block_size, common=not args.no_common,
                  simplify=not args.no_simplify_graph, device=device, benchmark=args.benchmark,

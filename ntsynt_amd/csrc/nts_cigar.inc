@@ -2881,6 +2881,13 @@ __global__ __launch_bounds__(256) void k_cigv_emit(const uint64_t* __restrict__ 
   if (t + 1u == n_ev || leadc[t + 1u] != me) alleles[r].n_carriers = (uint32_t)(t + 1u - cigp_lower(leadc, n_ev, me)); // the last event of the allele
 }
 
+// the temporary of the sorts and the scan that nts_cigar_alleles and nts_cigar_profile queue behind the stage: the shared "ivs_tmp",
+// fetched a second time per docs/design/04_24_call_order.md's rule, once every size is known
+inline void* cigv_sort_tmp(nts_ctx* ctx, size_t bytes)
+{
+  return ws_get(ctx, "ivs_tmp", std::max<size_t>(bytes, 16));
+}
+
 // nts_cigar_pad's checks of chain c and its place: group order and range, a core, t0 + len_a, the extent of its group; r0[group] = the
 // smallest t0 of the group so far, placed = {first, t0} (the key once every chain of the group is seen: cigv_keys)
 template <class Who>
@@ -2987,7 +2994,8 @@ int cigar_alleles_run(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, con
   if (e_run == hipSuccess) e_run = rocprim::radix_sort_pairs(nullptr, tmp_c, d_lead, d_leadc, iota, d_order, n_ev, 0, 32, ctx->stream);
   if (e_run == hipSuccess) e_run = rocprim::exclusive_scan(nullptr, tmp_scan, d_head, d_rank, (uint64_t)0, n_ev + 1, rocprim::plus<uint64_t>(), ctx->stream);
   HIP_TRY(ctx, e_run);
-  NTS_WS(d_tmp, void*, "ivs_tmp", std::max<size_t>(std::max(std::max(tmp_a, tmp_b), std::max(tmp_c, tmp_scan)), 16)); // (ix.tmp is dead from here)
+  void* const d_tmp = cigv_sort_tmp(ctx, std::max(std::max(tmp_a, tmp_b), std::max(tmp_c, tmp_scan))); // (ix.tmp is dead from here)
+  if (!d_tmp) return NTS_ENOMEM;
   std::vector<uint64_t> host_first(n_groups + 2); // (the caller's array is written only when the call succeeds)
   if (n_alt) e_run = hipMemcpyAsync(d_alt, alt, n_alt, hipMemcpyHostToDevice, ctx->stream); // (a source of an asynchronous copy: a synchronisation follows whatever happens)
   if (e_run == hipSuccess) {
@@ -3049,5 +3057,325 @@ int cigar_alleles_run(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, con
   *carriers = host_carriers;
   *n_carriers = n_ev;
   memcpy(allele_first, host_first.data(), (n_groups + 1) * 8);
+  return NTS_OK;
+}
+
+// ---- per-column profile and consensus over a star alignment (nts_cigar_profile; ntsynt_amd/assess.py block_consensus) ----
+// docs/design/04_33_block_consensus.md.  The third reader of a group of chains: one record per VARIABLE column of the group's star
+// alignment -- every reference base at which some covering chain has an X or a D, and every column of every insertion slot -- with how
+// many chains cover it, how many hold each of A, C, G, T, N or a gap there, the reference's byte and the plurality call.
+//   1  cig_index_stage with CigProfOf: (A bases, B bases, events, ref bytes, alt bytes), an X, D or I entry of length L having L events.
+//      k_cigf_events: one lane per event -- its entry by an upper-bound search over the event prefix, its chain by one over the chains'
+//      firsts -- stores key1 = group << 32 | pos - R0, key2 = sub << 3 | symbol (sub: the column inside an I entry, NTS_CIG_PROFILE_REF
+//      for an X or D column; symbol: A C G T N 0..4, 5 a deleted base) and its ref byte's offset.  Stable radix sort by key2 (35 bits;
+//      the values: the event indices), key1 gathered in that order, stable radix sort by key1, key2 gathered in the final order: events
+//      ascend by (group, pos, sub, symbol, event), so by chain inside a run.  k_cigf_chain_keys: one lane per chain, group << 32 |
+//      t0 - R0 and group << 32 | t1 - R0; two radix sorts of them (timer "cigar_profile_events").
+//   2  k_cigf_heads: a flag where (group, pos, sub) changes; ONE exclusive scan; k_cigd_firsts for col_first; k_cigf_emit: one lane
+//      per sorted event, a head alone goes on: six bounded lower-bound searches inside its column's run give the per-symbol counts,
+//      two cigp_lower searches over the chains' sorted keys give aligned = (chains of the group with t0 <= pos) - (those with t1 <= pos),
+//      match = aligned - gap - sum n, the ref byte is that of the column's smallest event (its smallest chain), the call is decided and
+//      the whole 56-byte record is stored (timer "cigar_profile_emit").
+// No atomic, no floating point, no runtime division, no launch per chain, group, site or column, no host loop over entries, events or
+// columns (one over chains: the checks and R0).
+
+static_assert(sizeof(nts_cig_profile_col) == 56, "the C ABI's layout");
+
+constexpr uint64_t CIGF_SYMBOLS = 6;  // A C G T N and the gap
+constexpr uint64_t CIGF_GAP = 5;
+constexpr uint32_t CIGF_KEY2_BITS = 35; // sub << 3 | symbol
+
+struct CigProfOf // element e of the scan's input: what entry e consumes, its events (one per column of an X, D or I) and its bytes; nothing behind the last entry
+{
+  using Tuple = CigVarTuple;
+  const uint64_t* cigar;
+  uint64_t n_cigar;
+  __device__ Tuple operator()(uint64_t e) const
+  {
+    if (e >= n_cigar) return Tuple(0, 0, 0, 0, 0);
+    const uint64_t v = cigar[e], code = v & 15u, len = v >> 4;
+    const CigBases ab = cig_bases(v);
+    const bool x = code == CIG_X, d = code == CIG_D, i = code == CIG_I;
+    return Tuple(rocprim::get<0>(ab), rocprim::get<1>(ab), x || d || i ? len : 0, x || d ? len : 0, x || i ? len : 0); // (each <= A + B bases: no wrap)
+  }
+};
+
+// A C G T -> 0..3, any other byte -> 4 (N)
+__host__ __device__ inline uint32_t cigf_symbol(uint32_t byte)
+{
+  return byte == 'A' ? 0u : byte == 'C' ? 1u : byte == 'G' ? 2u : byte == 'T' ? 3u : 4u;
+}
+
+// lane i < n_ev: event i, in entry order (so in chain order)
+__global__ __launch_bounds__(256) void k_cigf_events(const uint64_t* __restrict__ cigar, uint64_t n_cigar, const CigPadChain* __restrict__ placed,
+                                                     uint64_t n_chains, const uint64_t* __restrict__ PA, const uint64_t* __restrict__ PE,
+                                                     const uint64_t* __restrict__ PR, const uint64_t* __restrict__ PL, const uint8_t* __restrict__ alt,
+                                                     uint64_t n_alt, uint64_t n_ev, uint64_t* __restrict__ key1, uint64_t* __restrict__ key2,
+                                                     uint32_t* __restrict__ roff)
+{
+  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (i >= n_ev || n_cigar == 0 || n_chains == 0) return;
+  const uint64_t e = cig_last_at_or_before(n_cigar, i, [PE](uint64_t k) { return PE[k]; }); // (PE[0] = 0 <= i < PE[n_cigar]: an entry with an event)
+  const uint64_t c = cig_last_at_or_before(n_chains, e, [placed](uint64_t k) { return placed[k].first; });
+  const CigPadChain ch = placed[c];
+  const uint64_t f = ch.first <= e ? ch.first : e;
+  const uint64_t code = cigar[e] & 15u, off = i - PE[e]; // the column inside the entry (off < n_ev < 2^32)
+  uint64_t at = ch.key0 + (PA[e] - PA[f]), sub = NTS_CIG_PROFILE_REF, symbol = CIGF_GAP, r = 0;
+  if (code == CIG_I) {
+    sub = off;
+  } else { // (CIG_X or CIG_D: = entries have no event)
+    at += off;
+    r = PR[e] + off;
+  }
+  if (code != CIG_D) {
+    const uint64_t l = PL[e] + off;
+    symbol = cigf_symbol(l < n_alt ? alt[l] : 0);
+  }
+  key1[i] = at; // (n_ev words each)
+  key2[i] = sub << 3 | symbol;
+  roff[i] = (uint32_t)r; // (the ref bytes are as many as the X and D events: below 2^32)
+}
+
+// lane c < n_chains: the keys of where chain c begins and ends on its group's reference
+__global__ __launch_bounds__(256) void k_cigf_chain_keys(const CigPadChain* __restrict__ placed, const nts_cig_chain* __restrict__ chains, uint64_t n_chains,
+                                                         uint64_t* __restrict__ begins, uint64_t* __restrict__ ends)
+{
+  const uint64_t c = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (c >= n_chains) return;
+  const uint64_t k = placed[c].key0;
+  begins[c] = k;
+  ends[c] = k + chains[c].len_a; // (t1 - R0 <= 2^32 - 1: the extent of a group was checked)
+}
+
+// lane t < n_ev: 1 where the sorted event at t opens a column; lane n_ev: 0
+__global__ __launch_bounds__(256) void k_cigf_heads(const uint64_t* __restrict__ key1s, const uint64_t* __restrict__ key2s, uint64_t n_ev,
+                                                    uint64_t* __restrict__ head)
+{
+  const uint64_t t = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (t > n_ev) return;
+  head[t] = t < n_ev && (t == 0 || key1s[t] != key1s[t - 1u] || (key2s[t] >> 3) != (key2s[t - 1u] >> 3)) ? 1u : 0u; // (n_ev + 1 words)
+}
+
+// the first s in [lo, n) with (key1[s], key2[s]) >= (k1, k2) over ascending pairs
+__device__ __forceinline__ uint64_t cigf_lower_from(const uint64_t* __restrict__ key1, const uint64_t* __restrict__ key2, uint64_t lo, uint64_t n, uint64_t k1,
+                                                    uint64_t k2)
+{
+  uint64_t hi = n;
+  while (lo < hi) {
+    const uint64_t mid = lo + (hi - lo) / 2u;
+    const uint64_t m1 = key1[mid];
+    if (m1 < k1 || (m1 == k1 && key2[mid] < k2)) lo = mid + 1u;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// lane t < n_ev: the sorted event at t; one that opens a column writes the column's whole record
+__global__ __launch_bounds__(256) void k_cigf_emit(const uint64_t* __restrict__ key1s, const uint64_t* __restrict__ key2s, const uint64_t* __restrict__ perm,
+                                                   const uint64_t* __restrict__ rank, const uint32_t* __restrict__ roff, const uint8_t* __restrict__ ref,
+                                                   uint64_t n_ref, const uint64_t* __restrict__ begins, const uint64_t* __restrict__ ends, uint64_t n_chains,
+                                                   const uint64_t* __restrict__ r0, uint64_t n_groups, uint64_t n_ev, nts_cig_profile_col* __restrict__ cols,
+                                                   uint64_t n_cols)
+{
+  const uint64_t t = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (t >= n_ev) return;
+  const uint64_t k1 = key1s[t], k2 = key2s[t], sub = k2 >> 3;
+  if (t > 0 && key1s[t - 1u] == k1 && (key2s[t - 1u] >> 3) == sub) return; // no head
+  const uint64_t r = rank[t]; // the heads in front of t (rank: n_ev + 1 words)
+  if (r >= n_cols) return;
+  const bool is_ref = sub == NTS_CIG_PROFILE_REF;
+  // the runs of the six symbols inside the column: [b, next b)
+  uint64_t b = t, first_ev = ~0ull, sum = 0;
+  uint32_t count[CIGF_SYMBOLS];
+#pragma unroll
+  for (uint32_t s = 0; s < CIGF_SYMBOLS; ++s) {
+    const uint64_t e = cigf_lower_from(key1s, key2s, b, n_ev, k1, (sub << 3) + s + 1u);
+    if (e > b) { // the run's first event is that of its smallest chain
+      const uint64_t i = perm[b];
+      first_ev = i < first_ev ? i : first_ev;
+    }
+    count[s] = (uint32_t)(e - b);
+    sum += e - b;
+    b = e;
+  }
+  // the chains of the group that begin at or in front of pos, less those that end there or in front of it (equal keys: the same group's chains in front)
+  const uint64_t aligned = cigp_lower(begins, n_chains, k1 + 1u) - cigp_lower(ends, n_chains, k1 + 1u);
+  const uint64_t group = k1 >> 32;
+  nts_cig_profile_col out;
+  out.pos = (group < n_groups ? r0[group] : 0) + (k1 & 0xFFFFFFFFull);
+  out.group = (uint32_t)group;
+  out.sub = (uint32_t)sub;
+  out.aligned = (uint32_t)aligned;
+  uint32_t tally[CIGF_SYMBOLS], ref_symbol = CIGF_GAP;
+#pragma unroll
+  for (uint32_t s = 0; s < CIGF_SYMBOLS; ++s) tally[s] = count[s];
+  if (is_ref) {
+    const uint64_t at = first_ev < n_ev ? roff[first_ev] : n_ref;
+    out.ref = at < n_ref ? ref[at] : (uint8_t)'N';
+    out.gap = count[CIGF_GAP];
+    out.match = (uint32_t)(aligned - sum);
+    ref_symbol = cigf_symbol(out.ref);
+#pragma unroll
+    for (uint32_t s = 0; s < 5u; ++s) tally[s] += s == ref_symbol ? out.match + 1u : 0u; // the reference row and the chains that equal it
+  } else {
+    out.ref = (uint8_t)'-';
+    out.gap = (uint32_t)(aligned - sum); // (an insertion column has no event of symbol 5)
+    out.match = 0;
+    tally[CIGF_GAP] = out.gap + 1u; // the reference row
+  }
+  uint32_t best = 0;
+#pragma unroll
+  for (uint32_t s = 1; s < CIGF_SYMBOLS; ++s) best = tally[s] > tally[best] ? s : best; // the first of A C G T N - among the largest
+  uint32_t ref_tally = 0;
+#pragma unroll
+  for (uint32_t s = 0; s < CIGF_SYMBOLS; ++s) ref_tally = s == ref_symbol ? tally[s] : ref_tally;
+  uint32_t most = 0;
+#pragma unroll
+  for (uint32_t s = 0; s < CIGF_SYMBOLS; ++s) most = s == best ? tally[s] : most;
+  if (ref_tally == most) best = ref_symbol;
+#pragma unroll
+  for (uint32_t s = 0; s < 5u; ++s) out.n[s] = count[s];
+  out.call = (uint8_t)(best == 0 ? 'A' : best == 1 ? 'C' : best == 2 ? 'G' : best == 3 ? 'T' : best == 4 ? 'N' : '-');
+#pragma unroll
+  for (uint32_t k = 0; k < 6u; ++k) out.reserved[k] = 0;
+  cols[r] = out; // (every byte of the record, once)
+}
+
+int cigar_profile_run(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains, const nts_cig_pad_at* at,
+                      uint64_t n_groups, const uint8_t* ref, uint64_t n_ref, const uint8_t* alt, uint64_t n_alt, nts_cig_profile_col** cols,
+                      uint64_t* col_first)
+{
+  std::vector<CigPadChain> placed;
+  std::vector<uint64_t> r0;
+  try {
+    placed.resize(n_chains);
+    r0.assign(std::max<uint64_t>(n_groups, 1), 0);
+  } catch (const std::bad_alloc&) {
+    return fail(ctx, NTS_ENOMEM, "nts_cigar_profile: no host memory for the chains and groups");
+  }
+  uint64_t lo = 0, hi = 0; // the extent of the group of the chain in front
+  auto place = [&](uint64_t c, auto who) -> int { return cigv_place(ctx, cigar, chains, at, n_groups, c, who, lo, hi, r0, placed[c]); };
+  if (const int rc = cig_chains_check(ctx, "nts_cigar_profile", CIG_TEXT_MAX_BASES_LOG2, true, chains, n_chains, n_cigar, place)) return rc;
+  for (uint64_t c = 0; c < n_chains; ++c) placed[c].key0 = ((uint64_t)at[c].group << 32) + (placed[c].key0 - r0[at[c].group]);
+  auto nothing = [&] {
+    *cols = nullptr;
+    memset(col_first, 0, (n_groups + 1) * 8);
+    return NTS_OK;
+  };
+  auto bytes_differ = [&](const char* which, uint64_t given, const char* entries, uint64_t have) {
+    return fail(ctx, NTS_EINVAL, std::string("nts_cigar_profile: ") + which + " holds " + std::to_string(given) + " bytes, the " + entries +
+                                   " entries of the chains have " + std::to_string(have));
+  };
+  if (n_cigar == 0) { // (nothing is launched)
+    if (n_alt) return bytes_differ("alt", n_alt, "X and I", 0);
+    if (n_ref) return bytes_differ("ref", n_ref, "X and D", 0);
+    return nothing();
+  }
+  // (its own buffers first: while nothing is queued, a request that fails may still return at once)
+  NTS_WS(d_placed, CigPadChain*, "cigf_placed", n_chains * sizeof(CigPadChain));
+  NTS_WS(d_r0, uint64_t*, "cigf_r0", std::max<uint64_t>(n_groups, 1) * 8);
+  NTS_WS(d_col_first, uint64_t*, "cigf_col_first", (n_groups + 2) * 8);
+  NTS_WS(d_begins, uint64_t*, "cigf_begins", n_chains * 8);
+  NTS_WS(d_ends, uint64_t*, "cigf_ends", n_chains * 8);
+  NTS_WS(d_begins_s, uint64_t*, "cigf_begins_s", n_chains * 8);
+  NTS_WS(d_ends_s, uint64_t*, "cigf_ends_s", n_chains * 8);
+  uint32_t worst = SCRIPT_OK;
+  uint64_t totals[3] = { 0, 0, 0 }; // events, ref bytes, alt bytes
+  CigIndex ix; // columns PA, PB, PE (events), PR (ref bytes), PL (alt bytes)
+  hipError_t e_run;
+  if (const int rc = cig_index_stage<CigProfOf>(ctx, "cigar_profile_events", cigar, n_cigar, chains, n_chains, 0, &worst, ix, e_run, [] {})) return rc;
+  if (e_run == hipSuccess) e_run = hipGetLastError();
+  if (e_run == hipSuccess) e_run = hipMemcpyAsync(d_placed, placed.data(), n_chains * sizeof(CigPadChain), hipMemcpyHostToDevice, ctx->stream);
+  if (e_run == hipSuccess && n_groups) e_run = hipMemcpyAsync(d_r0, r0.data(), n_groups * 8, hipMemcpyHostToDevice, ctx->stream);
+  for (uint32_t k = 0; k < 3 && e_run == hipSuccess; ++k)
+    e_run = hipMemcpyAsync(&totals[k], ix.column(2 + k) + n_cigar, 8, hipMemcpyDeviceToHost, ctx->stream);
+  hipError_t e_sync = hipStreamSynchronize(ctx->stream); // (whatever happened: the caller's arrays were sources of asynchronous copies)
+  HIP_TRY(ctx, e_run);
+  HIP_TRY(ctx, e_sync);
+  if (worst != SCRIPT_OK) {
+    if (worst < n_chains) // (the error path alone looks at the entries of that one chain)
+      for (uint64_t e = chains[worst].first; e < chains[worst].first + chains[worst].n_cig; ++e)
+        if ((cigar[e] & 15u) == CIG_P) return fail(ctx, NTS_EINVAL, "nts_cigar_profile: chain " + std::to_string(worst) + " holds an entry of code 6");
+    return fail(ctx, NTS_EINVAL, "nts_cigar_profile: the entries of chain " + std::to_string(worst) + " are no CIGAR of its lengths");
+  }
+  const uint64_t n_ev = totals[0];
+  if (totals[2] != n_alt) return bytes_differ("alt", n_alt, "X and I", totals[2]);
+  if (totals[1] != n_ref) return bytes_differ("ref", n_ref, "X and D", totals[1]);
+  if (n_ev > CIGV_MOST_BYTES) return fail(ctx, NTS_ERANGE, "nts_cigar_profile: 2^32 events or more");
+  if (n_ev == 0) return nothing(); // (no launch behind the stage)
+  // (the stream is idle: the buffers sized by the events are fetched before their kernels are queued)
+  NTS_WS(d_alt, uint8_t*, "cigf_alt_in", (std::max<uint64_t>(n_alt, 1) + 3) / 4 * 4);
+  NTS_WS(d_ref, uint8_t*, "cigf_ref_in", (std::max<uint64_t>(n_ref, 1) + 3) / 4 * 4);
+  NTS_WS(d_key1, uint64_t*, "cigf_key1", n_ev * 8);
+  NTS_WS(d_key2, uint64_t*, "cigf_key2", n_ev * 8);
+  NTS_WS(d_roff, uint32_t*, "cigf_roff", n_ev * 4);
+  NTS_WS(d_key2a, uint64_t*, "cigf_key2a", n_ev * 8);
+  NTS_WS(d_idxa, uint64_t*, "cigf_idxa", n_ev * 8);
+  NTS_WS(d_key1a, uint64_t*, "cigf_key1a", n_ev * 8);
+  NTS_WS(d_key1s, uint64_t*, "cigf_key1s", n_ev * 8);
+  NTS_WS(d_perm, uint64_t*, "cigf_perm", n_ev * 8);
+  NTS_WS(d_key2s, uint64_t*, "cigf_key2s", n_ev * 8);
+  NTS_WS(d_head, uint64_t*, "cigf_head", (n_ev + 1) * 8);
+  NTS_WS(d_rank, uint64_t*, "cigf_rank", (n_ev + 1) * 8);
+  const rocprim::counting_iterator<uint64_t> iota(0);
+  size_t tmp_a = 0, tmp_b = 0, tmp_c = 0, tmp_scan = 0;
+  e_run = rocprim::radix_sort_pairs(nullptr, tmp_a, d_key2, d_key2a, iota, d_idxa, n_ev, 0, CIGF_KEY2_BITS, ctx->stream);
+  if (e_run == hipSuccess) e_run = rocprim::radix_sort_pairs(nullptr, tmp_b, d_key1a, d_key1s, d_idxa, d_perm, n_ev, 0, 64, ctx->stream);
+  if (e_run == hipSuccess) e_run = rocprim::radix_sort_keys(nullptr, tmp_c, d_begins, d_begins_s, n_chains, 0, 64, ctx->stream);
+  if (e_run == hipSuccess) e_run = rocprim::exclusive_scan(nullptr, tmp_scan, d_head, d_rank, (uint64_t)0, n_ev + 1, rocprim::plus<uint64_t>(), ctx->stream);
+  HIP_TRY(ctx, e_run);
+  void* const d_tmp = cigv_sort_tmp(ctx, std::max(std::max(tmp_a, tmp_b), std::max(tmp_c, tmp_scan))); // (ix.tmp is dead from here)
+  if (!d_tmp) return NTS_ENOMEM;
+  std::vector<uint64_t> host_first(n_groups + 2); // (the caller's array is written only when the call succeeds)
+  if (n_alt) e_run = hipMemcpyAsync(d_alt, alt, n_alt, hipMemcpyHostToDevice, ctx->stream); // (sources of asynchronous copies: a synchronisation follows whatever happens)
+  if (e_run == hipSuccess && n_ref) e_run = hipMemcpyAsync(d_ref, ref, n_ref, hipMemcpyHostToDevice, ctx->stream);
+  if (e_run == hipSuccess) {
+    ScopedTimer t(ctx, "cigar_profile_events", true);
+    NTS_LAUNCH(k_cigf_events, IVL_GRID(n_ev), ix.cigar, n_cigar, (const CigPadChain*)d_placed, n_chains, ix.column(0), ix.column(2), ix.column(3),
+               ix.column(4), (const uint8_t*)d_alt, n_alt, n_ev, d_key1, d_key2, d_roff);
+    e_run = rocprim::radix_sort_pairs(d_tmp, tmp_a, d_key2, d_key2a, iota, d_idxa, n_ev, 0, CIGF_KEY2_BITS, ctx->stream);
+    if (e_run == hipSuccess) {
+      NTS_LAUNCH(k_cigv_gather, IVL_GRID(n_ev), (const uint64_t*)d_key1, (const uint64_t*)d_idxa, n_ev, d_key1a);
+      e_run = rocprim::radix_sort_pairs(d_tmp, tmp_b, d_key1a, d_key1s, d_idxa, d_perm, n_ev, 0, 64, ctx->stream);
+    }
+    if (e_run == hipSuccess) {
+      NTS_LAUNCH(k_cigv_gather, IVL_GRID(n_ev), (const uint64_t*)d_key2, (const uint64_t*)d_perm, n_ev, d_key2s);
+      NTS_LAUNCH(k_cigf_chain_keys, IVL_GRID(n_chains), (const CigPadChain*)d_placed, ix.chains, n_chains, d_begins, d_ends);
+      e_run = rocprim::radix_sort_keys(d_tmp, tmp_c, d_begins, d_begins_s, n_chains, 0, 64, ctx->stream);
+    }
+    if (e_run == hipSuccess) e_run = rocprim::radix_sort_keys(d_tmp, tmp_c, d_ends, d_ends_s, n_chains, 0, 64, ctx->stream);
+  }
+  if (e_run == hipSuccess) {
+    ScopedTimer t(ctx, "cigar_profile_emit", true);
+    NTS_LAUNCH(k_cigf_heads, IVL_GRID(n_ev + 1), (const uint64_t*)d_key1s, (const uint64_t*)d_key2s, n_ev, d_head);
+    e_run = rocprim::exclusive_scan(d_tmp, tmp_scan, d_head, d_rank, (uint64_t)0, n_ev + 1, rocprim::plus<uint64_t>(), ctx->stream);
+    if (e_run == hipSuccess)
+      NTS_LAUNCH(k_cigd_firsts, IVL_GRID(n_groups + 2), (const uint64_t*)d_key1s, n_ev, (const uint64_t*)d_rank, n_groups, d_col_first);
+  }
+  if (e_run == hipSuccess) e_run = hipGetLastError();
+  if (e_run == hipSuccess) e_run = hipMemcpyAsync(host_first.data(), d_col_first, (n_groups + 2) * 8, hipMemcpyDeviceToHost, ctx->stream);
+  e_sync = hipStreamSynchronize(ctx->stream);
+  HIP_TRY(ctx, e_run);
+  HIP_TRY(ctx, e_sync);
+  const uint64_t n_cols = host_first[n_groups];
+  if (n_cols == 0 || n_cols > n_ev) return fail(ctx, NTS_EHIP, "nts_cigar_profile: the scan left an impossible number of columns");
+  // (the stream is idle: the output's buffer is fetched before its kernel is queued)
+  NTS_WS(d_cols, nts_cig_profile_col*, "cigf_cols", n_cols * sizeof(nts_cig_profile_col));
+  nts_cig_profile_col* host_cols = (nts_cig_profile_col*)malloc(n_cols * sizeof(nts_cig_profile_col));
+  if (!host_cols) return fail(ctx, NTS_ENOMEM, "nts_cigar_profile: no host memory for the columns");
+  {
+    ScopedTimer t(ctx, "cigar_profile_emit", true);
+    NTS_LAUNCH(k_cigf_emit, IVL_GRID(n_ev), (const uint64_t*)d_key1s, (const uint64_t*)d_key2s, (const uint64_t*)d_perm, (const uint64_t*)d_rank,
+               (const uint32_t*)d_roff, (const uint8_t*)d_ref, n_ref, (const uint64_t*)d_begins_s, (const uint64_t*)d_ends_s, n_chains,
+               (const uint64_t*)d_r0, n_groups, n_ev, d_cols, n_cols);
+  }
+  e_run = hipGetLastError();
+  if (e_run == hipSuccess) e_run = hipMemcpyAsync(host_cols, d_cols, n_cols * sizeof(nts_cig_profile_col), hipMemcpyDeviceToHost, ctx->stream);
+  e_sync = hipStreamSynchronize(ctx->stream);
+  if (e_run != hipSuccess || e_sync != hipSuccess) free(host_cols);
+  HIP_TRY(ctx, e_run);
+  HIP_TRY(ctx, e_sync);
+  *cols = host_cols;
+  memcpy(col_first, host_first.data(), (n_groups + 1) * 8);
   return NTS_OK;
 }

@@ -1157,6 +1157,19 @@ extern "C" int nts_cigar_alleles(nts_ctx* ctx, const uint64_t* cigar, uint64_t n
   return cigar_alleles_run(ctx, cigar, n_cigar, chains, n_chains, at, n_groups, alt, n_alt, alleles, allele_first, carriers, n_carriers);
 }
 
+extern "C" int nts_cigar_profile(nts_ctx* ctx, const uint64_t* cigar, uint64_t n_cigar, const nts_cig_chain* chains, uint64_t n_chains,
+                                 const nts_cig_pad_at* at, uint64_t n_groups, const uint8_t* ref, uint64_t n_ref, const uint8_t* alt, uint64_t n_alt,
+                                 nts_cig_profile_col** cols, uint64_t* col_first)
+{
+  if (!ctx) return NTS_EINVAL;
+  if (n_cigar > 0xFFFFFFFFull || n_chains > 0xFFFFFFFFull || n_groups > 0xFFFFFFFFull) // (before any array is read)
+    return fail(ctx, NTS_ERANGE, "nts_cigar_profile: 2^32 entries, chains or groups or more");
+  if ((n_cigar && !cigar) || (n_chains && (!chains || !at)) || (n_ref && !ref) || (n_alt && !alt) || !cols || !col_first)
+    return fail(ctx, NTS_EINVAL, "nts_cigar_profile: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return cigar_profile_run(ctx, cigar, n_cigar, chains, n_chains, at, n_groups, ref, n_ref, alt, n_alt, cols, col_first);
+}
+
 extern "C" int nts_graph_budget(nts_ctx* ctx, uint64_t bytes)
 {
   if (!ctx) return NTS_EINVAL;

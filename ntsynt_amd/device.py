@@ -81,6 +81,11 @@ CIG_DEPTH_SEG_DTYPE = np.dtype([("start", "<u8"), ("end", "<u8"), ("group", "<u4
 # nts_cig_allele: what Context.cigar_alleles returns, one per allele of a group (kind: 1 SNV, 2 DEL, 3 INS)
 CIG_ALLELE_DTYPE = np.dtype([("pos", "<u8"), ("len", "<u8"), ("ref_off", "<u8"), ("alt_off", "<u8"), ("carrier_first", "<u8"), ("group", "<u4"),
                              ("kind", "<u4"), ("n_carriers", "<u4"), ("reserved", "<u4")])
+# nts_cig_profile_col: what Context.cigar_profile returns, one per variable column of a group (sub: CIG_PROFILE_REF for a reference base,
+# else the column inside the slot in front of base pos; n: A C G T N; ref, call: a letter or `-`)
+CIG_PROFILE_COL_DTYPE = np.dtype([("pos", "<u8"), ("group", "<u4"), ("sub", "<u4"), ("aligned", "<u4"), ("match", "<u4"), ("gap", "<u4"),
+                                  ("n", "<u4", (5,)), ("ref", "u1"), ("call", "u1"), ("reserved", "u1", (6,))])
+CIG_PROFILE_REF = 0xFFFFFFFF
 # nts_lift_query / nts_lift_hit: what Context.cigar_lift takes and returns, one per query
 LIFT_QUERY_DTYPE = np.dtype([("chain", "<u4"), ("side", "<u4"), ("pos", "<u8")])
 LIFT_HIT_DTYPE = np.dtype([("pos", "<u8"), ("entry", "<u8"), ("off", "<u8"), ("code", "<u4"), ("reserved", "<u4")])
@@ -591,6 +596,34 @@ class Context:
                                               bases.size, ctypes.byref(p_alleles), allele_first.ctypes.data, ctypes.byref(p_carriers),
                                               ctypes.byref(n_carriers)), "nts_cigar_alleles")
         return self._take(p_alleles, int(allele_first[-1]), CIG_ALLELE_DTYPE), allele_first, self._take(p_carriers, int(n_carriers.value), np.dtype("<u4"))
+
+    def cigar_profile(self, cigar, chains, at, ref, alt, n_groups=None):
+        """the variable columns of every reference-anchored group of chains, with their counts and plurality call (nts_cigar_profile).
+        cigar, chains, at and n_groups as for cigar_alleles (the chains are cores and tile the entries; chains of a group may overlap);
+        ref, alt: the bytes of cigar_var_bases over all chains in chain order, uint8.  Returns (cols, col_first): a
+        CIG_PROFILE_COL_DTYPE array -- one record per reference base at which a covering chain has an X or a D (sub CIG_PROFILE_REF)
+        and per column of every insertion slot (sub: the column; pos: the base the slot lies in front of) -- ascending by (group, pos,
+        sub), the multi-MAF's column order; group g's are cols[col_first[g]:col_first[g + 1]] (col_first [n_groups + 1] uint64).
+        aligned: the chains covering the column (t0 <= pos < t1), match / gap: those with an = / a D there, n: those holding A, C, G, T
+        or another byte there; ref: the reference's byte (`-` in a slot); call: the symbol with the largest tally, the reference row
+        counted in, ties to the reference's symbol, else to the first of A C G T N -.  Reads no genome.  Exact and deterministic."""
+        cg = np.ascontiguousarray(cigar, dtype=np.uint64)
+        ch = np.ascontiguousarray(chains, dtype=CHAIN_DTYPE)
+        where = np.ascontiguousarray(at, dtype=CIG_PAD_AT_DTYPE)
+        ref_b, alt_b = np.ascontiguousarray(ref, dtype=np.uint8), np.ascontiguousarray(alt, dtype=np.uint8)
+        if cg.ndim != 1 or ch.ndim != 1 or where.shape != ch.shape or ref_b.ndim != 1 or alt_b.ndim != 1:
+            raise ValueError("cigar_profile: a list of entries, a list of chain records, one {group, t0} per chain and two lists of bytes")
+        assert CHAIN_DTYPE.itemsize == ctypes.sizeof(_lib.CigChain) and CIG_PAD_AT_DTYPE.itemsize == ctypes.sizeof(_lib.CigPadAt)
+        assert CIG_PROFILE_COL_DTYPE.itemsize == ctypes.sizeof(_lib.CigProfileCol) == 56
+        if n_groups is None:
+            n_groups = int(where["group"][-1]) + 1 if where.size else 0
+        col_first = np.zeros(int(n_groups) + 1, dtype=np.uint64)
+        p_cols = c_vp()
+        self.check(self.lib.nts_cigar_profile(self.h, cg.ctypes.data if cg.size else None, cg.size, ch.ctypes.data if ch.size else None, ch.size,
+                                              where.ctypes.data if where.size else None, int(n_groups), ref_b.ctypes.data if ref_b.size else None,
+                                              ref_b.size, alt_b.ctypes.data if alt_b.size else None, alt_b.size, ctypes.byref(p_cols),
+                                              col_first.ctypes.data), "nts_cigar_profile")
+        return self._take(p_cols, int(col_first[-1]), CIG_PROFILE_COL_DTYPE), col_first
 
     def cigar_rows(self, cigar, chains, spans, genome_a, genome_b, padded=False):
         """the aligned rows of the chains' CIGARs, the sequence lines of a MAF block (nts_cigar_rows).  cigar, chains, spans and the

@@ -500,7 +500,7 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         gap_periods=None, gap_families=None, block_identity=None, block_variants=None, block_wide_variants=None, block_ends=None,
         block_end_variants=False, block_paf=None, block_lift=None, block_lift_identity=None, block_windows=None, block_lift_joined=None,
         block_paf_cs=False, block_chain=None, block_maf=None, block_maf_multi=None, block_conservation=None,
-        block_variant_sites=None):
+        block_variant_sites=None, block_consensus=None):
     """FASTA paths -> engine (outputs in .outputs and in the CWD).  Mirrors oracle.synteny_oracle.run_pipeline's
     signature so the parity tests read alike.  Under torch.distributed (WORLD_SIZE > 1, process group already
     initialised by the caller) genomes are sharded over the ranks.
@@ -563,6 +563,11 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
     allele over its star alignment with its carriers and genotypes (assess.block_variant_sites; stage block_variant_sites behind
     block_conservation; always a pass of its own; with `benchmark` the stage times gain block_variant_sites:cigar_var_bases_scan,
     :cigar_var_bases_emit, :cigar_alleles_events and :cigar_alleles_emit).
+    block_consensus = (k, rate, band, max_len, max_edits, ends), as block_paf: <prefix>.block_profile.tsv, per block one line per variable
+    column of its star alignment with the tallies of A C G T N and the gap and the plurality call, and <prefix>.block_consensus.fa, per block
+    its reference bases with the calls applied (assess.block_consensus; stage block_consensus behind block_variant_sites; always a pass of
+    its own; with `benchmark` the stage times gain block_consensus:cigar_var_bases_scan, :cigar_var_bases_emit, :cigar_profile_events and
+    :cigar_profile_emit).
     block_lift =(bed_path, genome, k, rate, band,
     max_len, max_edits, ends): behind that file, <prefix>.block_lift.tsv (assess.block_lift: the BED intervals of `genome`, a FASTA base
     name, mapped through the block alignments into the other genomes; one rank only; it needs none of the other switches; with
@@ -726,6 +731,18 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
             (check_ends_parameters(*block_variant_sites[5]) if block_variant_sites[5] is not None else None)
         if message:
             raise ValueError("block_variant_sites = (k, rate, band, max_len, max_edits, ends): " + message)
+    if block_consensus is not None:
+        if world > 1 or (mx_tsvs is not None and initial_only):
+            raise ValueError("block_consensus needs every genome resident on one GPU (one rank, genomes loaded)")
+        from .assess import check_ends_parameters, check_identity_parameters
+        if len(block_consensus) != 6 or (block_consensus[5] is not None and len(block_consensus[5]) != 3):
+            raise ValueError("block_consensus = (k, rate, band, max_len, max_edits, ends) with ends = (ends_max_len, ends_max_edits, ends_penalty) or None")
+        block_consensus = tuple(int(x) for x in block_consensus[:5]) + \
+            (tuple(int(x) for x in block_consensus[5]) if block_consensus[5] is not None else None,)
+        message = check_identity_parameters(*block_consensus[:5]) or \
+            (check_ends_parameters(*block_consensus[5]) if block_consensus[5] is not None else None)
+        if message:
+            raise ValueError("block_consensus = (k, rate, band, max_len, max_edits, ends): " + message)
     if block_lift is not None:
         if world > 1 or (mx_tsvs is not None and initial_only):
             raise ValueError("block_lift needs every genome resident on one GPU (one rank, genomes loaded)")
@@ -1596,6 +1613,28 @@ def run(fastas, k=24, w=1000, fpr=0.025, prefix=None, w_rounds=(100, 10), indel=
         if benchmark:
             st.rows += site_times
         st.mark("block_variant_sites_done")
+    if block_consensus is not None:
+        st.start("block_consensus")
+        from . import assess as assess_
+        consensus_timers = ("cigar_var_bases_scan", "cigar_var_bases_emit", "cigar_profile_events", "cigar_profile_emit")
+        if benchmark:                                         # (device events around the calls of this stage only)
+            backend.ctx.profile(True)
+            consensus_before = {name: backend.ctx.timing(name)[0] for name in consensus_timers}
+        by_name = {fa.basename(p): genomes[p] for p in fastas}
+        profile = assess_.block_consensus(backend.ctx, by_name, assess_.read_blocks(f"{prefix}.synteny_blocks.tsv"), *block_consensus[:5],
+                                          ends=block_consensus[5])
+        if benchmark:
+            consensus_times = [(f"block_consensus:{name}", (backend.ctx.timing(name)[0] - consensus_before[name]) * 1e-3) for name in consensus_timers]
+            backend.ctx.profile(False)
+        for name, text in (("block_profile.tsv", assess_.profile_table(*profile[:3], *block_consensus[:5], ends=block_consensus[5])),
+                           ("block_consensus.fa", assess_.consensus_fasta(*profile, assess_.consensus_reference_bases(by_name, profile[0], profile[3])))):
+            with open(f"{prefix}.{name}", "w", encoding="utf-8") as fh:
+                fh.write(text)
+            eng.outputs[f"{prefix}.{name}"] = text
+        st.stop()
+        if benchmark:
+            st.rows += consensus_times
+        st.mark("block_consensus_done")
     if block_lift is not None:
         st.start("block_lift")
         from . import assess as assess_
